@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — frames/s of encode+decode on the ScanNet-scale 1M-point frame.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: either under torch.distributed.run — RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment — or
      plain, in which case this process starts the N ranks itself: launch_ranks())
 
@@ -9,9 +9,14 @@ One step = the reference's operator contract: CompressionPipeline.compress(gop o
 capturer leaves them — int16 points, float64 colours — at the three quality settings of shared/config.yaml:12-15)
 + DecompressionPipeline.decompress(container of the last quality) -> host numpy frames
 (sender/encoder/codec_pipeline.py:239-267, receiver/decoder/codec_parallel.py:474-502).  `value` is that rate, PCIe
-legs included; `value_hbm_resident` is the same K steps with the frame already in HBM and the reconstruction left
-there (the figure the kernels' roofline refers to).  D1-PSNR / Y-PSNR of the reconstruction (metrics.py, outside
-the timed region) are reported for the HIP path and for the CPU oracle; the two reconstructions must be equal.
+legs included.  A plain run sets up, warms up, times the K steps, writes the last step's results if --dump-outputs
+asks for them (dump_outputs) and prints the line.
+
+--full adds everything else, each outside the headline's timed region: the per-op table and the roofline of the
+dominant kernel, `value_hbm_resident` (the same K steps with the frame already in HBM and the reconstruction left
+there, the figure the kernels' roofline refers to), the version-1 and seek-point containers, GOPs in flight, the CPU
+oracle's baseline, D1-PSNR / Y-PSNR of the reconstruction (metrics.py) for the HIP path and for the CPU oracle (the two
+reconstructions must be equal) and the other configurations of BASELINE.json.
 
 N = 1: the C2 frame (BASELINE.json configs[1]).  N > 1: BASELINE.json configs[4]'s tiling — a fused scan of N C2
 rooms side by side (N x 1M voxels), cut into 2N octree blocks of 256 x 512 x 256 voxels (tiled.cut_tiles), two per
@@ -210,6 +215,42 @@ def bench_configs(pkg, wl, device, threads, steps=5, warmup=2, with_oracle=True)
     return res
 
 
+DUMP_BUDGET = 64 << 20      # bytes of all --dump-outputs files together
+
+
+def dump_outputs(path, out, side, rec):
+    """--dump-outputs: what a caller of the timed path received from its last step, as <path>/<name>.npy — the
+    container of every quality (its bytes as values), the GOP's bpp, and every decoded frame's points and colours.
+    float32 where that holds the values exactly, float64 otherwise.  If the arrays exceed DUMP_BUDGET together, each
+    keeps the same fraction of its rows, chosen by a fixed seed (the same rows for arrays of the same length)."""
+    arrays = {f"container_q{q}": np.frombuffer(bytes(b), np.uint8) for q, b in sorted(out.items()) if q}
+    arrays["bpp"] = np.asarray(side["gop_info"]["bpp"], np.float64)
+    for i, r in enumerate(rec):
+        arrays[f"frame{i}_points"] = np.asarray(r["points"])
+        arrays[f"frame{i}_colors"] = np.asarray(r["colors"])
+
+    def as_float(a):
+        if a.dtype == np.float32 or a.dtype == np.float64:
+            return a
+        exact = a.dtype.itemsize <= 2 or a.size == 0 or int(np.abs(a.astype(np.int64)).max()) <= 1 << 24
+        return a.astype(np.float32 if exact else np.float64)
+
+    arrays = {k: as_float(a) for k, a in arrays.items()}
+    room = DUMP_BUDGET - 4096 * len(arrays)                # .npy headers; arrays of < 4096 rows stay whole
+    small = sum(a.nbytes for a in arrays.values() if a.shape[0] < 4096)
+    large = sum(a.nbytes for a in arrays.values() if a.shape[0] >= 4096)
+    if small + large > room:
+        keep = (room - small) / large
+        for k, a in arrays.items():
+            if a.shape[0] >= 4096:
+                rows = np.random.default_rng(0).choice(a.shape[0], int(a.shape[0] * keep), replace=False)
+                arrays[k] = a[np.sort(rows)]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    log(f"outputs of the last timed step: {len(arrays)} arrays, {sum(a.nbytes for a in arrays.values())} bytes in {path}")
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher around it (the driver's command): start the N ranks here, one
     fresh child process per GPU, with the environment torch.distributed.run would give them.  This parent never
@@ -274,7 +315,14 @@ def main():
     ap.add_argument("--inflight", type=int, default=3, help="also report throughput with this many GOPs in flight (0/1 = skip)")
     ap.add_argument("--no-configs", action="store_true", help="skip the C1 / C3 / C4 / C5-on-one-GPU / ZED-GOP entries")
     ap.add_argument("--config-steps", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need (see the module docstring); the "
+                         "--no-* / --cpu-* / --inflight / --config-steps options apply to these legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the results of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))      # plain `python bench.py --gpus N`: this process only starts the ranks
@@ -328,13 +376,14 @@ def main():
     log(f"[rank {rank}] workload: {len(frames)} frame(s), {n_pts} voxels generated in {time.time() - t0:.1f}s")
     assert all(f["points"].dtype == np.int16 and f["colors"].dtype == np.float64 for f in frames)
     d_frames = [{"points": torch.from_numpy(f["points"].astype(np.int32)).to(dev),
-                 "colors": torch.from_numpy(f["colors"].astype(np.float32)).to(dev)} for f in frames]
+                 "colors": torch.from_numpy(f["colors"].astype(np.float32)).to(dev)} for f in frames] if args.full else None
 
     enc = pkg.CompressionPipeline(SETTINGS, device=local, slots=1)
     dec = pkg.DecompressionPipeline(device=local, slots=1, output="numpy")
-    dec_dev = pkg.DecompressionPipeline(device=local, slots=1, output="device")
+    dec_dev = pkg.DecompressionPipeline(device=local, slots=1, output="device") if args.full else None
 
-    enc_v1 = pkg.CompressionPipeline(SETTINGS, device=local, slots=1, container_version=1) if not tiled_mode else None
+    enc_v1 = (pkg.CompressionPipeline(SETTINGS, device=local, slots=1, container_version=1)
+              if args.full and not tiled_mode else None)
 
     def step(host=True, enc=enc):
         """one pass of the operator contract.  host=True: numpy frames in, numpy frames out (the contract of the
@@ -364,19 +413,21 @@ def main():
             g[1] += ms
         return sorted(groups.items(), key=lambda kv: -kv[1][1]), sum(v[1] for v in groups.values()) / n_steps
 
-    # warm-up; its last step (untimed) runs with an event pair around EVERY C-ABI call: the per-op table below
-    # and the choice of the dominant kernel come from it
+    # warm-up; with --full its last step (untimed) runs with an event pair around EVERY C-ABI call: the per-op table
+    # below and the choice of the dominant kernel come from it
     rts = enc.runtimes + dec.runtimes
     for i in range(max(args.warmup, 1)):
-        if i == max(args.warmup, 1) - 1:
+        if args.full and i == max(args.warmup, 1) - 1:
             for r in rts:
                 r.prof_enable(True, reserve=400)
         out, side, rec, dside, decoded = step()
     assert sum(int(r["points"].shape[0]) for r in rec) == n_pts or tiled_mode
     torch.cuda.synchronize()
-    table_all, sum_all = prof_table(rts, 1)
-    layer_all = [(k, v) for k, v in table_all if k[0] in ("sparse_conv", "convT_gen")]
-    step(host=False)                       # warm the HBM-resident variant's decoder slot too
+    table_all, sum_all, layer_all = [], 0.0, []
+    if args.full:
+        table_all, sum_all = prof_table(rts, 1)
+        layer_all = [(k, v) for k, v in table_all if k[0] in ("sparse_conv", "convT_gen")]
+        step(host=False)                   # warm the HBM-resident variant's decoder slot too
 
     def fence():
         torch.cuda.synchronize()
@@ -419,22 +470,26 @@ def main():
             + " ".join(f"{a:.1f}+{b:.1f}" for a, b in zip(e_ms, d_ms)))
         return dt, float(np.mean(e_ms)), float(np.mean(d_ms)), last
 
-    # timed region (`value`): K steps of the operator contract, host numpy in / host numpy out.  Only the dominant
-    # kernel is bracketed by HIP events (one pair per step); bracketing all ~150 calls of a step costs the step
-    # ~0.5 ms of stream bubbles
+    # timed region (`value`): K steps of the operator contract, host numpy in / host numpy out.  With --full only the
+    # dominant kernel is bracketed by HIP events (one pair per step); bracketing all ~150 calls of a step costs the
+    # step ~0.5 ms of stream bubbles
     if layer_all:
         (dom_op, dom_dims), _ = layer_all[0]
         for r in rts:
             r.prof_enable(True, reserve=8 * (args.steps + 1), only=dom_op, rows=dom_dims[0])
     elapsed, enc_ms, dec_ms, (out, side, rec, dside, decoded) = timed(host=True)
-    # ---- launches of the dominant kernel inside the timed region (HIP events on the ctx streams)
-    table, _ = prof_table(rts, args.steps)
-    # secondary: the same K steps with the frame resident in HBM and the reconstruction left there (no events)
-    elapsed_hbm, enc_ms_hbm, dec_ms_hbm, _ = timed(host=False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, side, rec)
+    table, elapsed_hbm, enc_ms_hbm, dec_ms_hbm = [], None, None, None
+    if args.full:
+        # ---- launches of the dominant kernel inside the timed region (HIP events on the ctx streams)
+        table, _ = prof_table(rts, args.steps)
+        # secondary: the same K steps with the frame resident in HBM and the reconstruction left there (no events)
+        elapsed_hbm, enc_ms_hbm, dec_ms_hbm, _ = timed(host=False)
     # the flagged container (version 1): y / z strings coded by the GPU's interleaved rANS in both directions, no
     # serial host coder on the path.  One profiled step for the coder kernels' own figures, then K timed steps.
     gpu_rans = None
-    if not tiled_mode:
+    if args.full and not tiled_mode:
         step(True, enc_v1)
         rts1 = enc_v1.runtimes + dec.runtimes
         for r in rts1:
@@ -470,7 +525,7 @@ def main():
     # is unchanged — it stops at the last frame record, in front of the trailer — and this library's decoder decodes the
     # y string in pieces on host threads.  Informational like value_gpu_rans; `value` stays the plain container.
     seek = None
-    if not tiled_mode:
+    if args.full and not tiled_mode:
         pieces = int(os.environ.get("PCC_BENCH_SEEK_POINTS", "16"))
         enc_sk = pkg.CompressionPipeline(SETTINGS, device=local, slots=1, seek_points=pieces)
         step(True, enc_sk)
@@ -486,11 +541,15 @@ def main():
         del enc_sk
     table = [kv for kv in table if layer_all and kv[0] == (dom_op, dom_dims)]
     if rank == 0:
-        log("per-op device time of the last warm-up step (HIP events around every C-ABI call):")
-        for (op, dims), (cnt, tot) in table_all[:25]:
-            log(f"  {op:14s} {str(dims):34s} x{cnt:4d}  total {tot:9.3f} ms  avg {tot / cnt:8.4f} ms")
-        log(f"  sum of recorded ops of that step: {sum_all:.3f} ms; "
-            f"timed region: wall per step {1e3 * elapsed / args.steps:.3f} ms (enc {np.mean(enc_ms):.2f} + dec {np.mean(dec_ms):.2f})")
+        wall = (f"timed region: wall per step {1e3 * elapsed / args.steps:.3f} ms "
+                f"(enc {np.mean(enc_ms):.2f} + dec {np.mean(dec_ms):.2f})")
+        if args.full:
+            log("per-op device time of the last warm-up step (HIP events around every C-ABI call):")
+            for (op, dims), (cnt, tot) in table_all[:25]:
+                log(f"  {op:14s} {str(dims):34s} x{cnt:4d}  total {tot:9.3f} ms  avg {tot / cnt:8.4f} ms")
+            log(f"  sum of recorded ops of that step: {sum_all:.3f} ms; {wall}")
+        else:
+            log(f"  {wall}")
         st = side["enc_time_measurements"]
         log("  encode stages ms:", {k: (round(1e3 * v, 3) if not isinstance(v, list) else [round(1e3 * x, 3) for x in v])
                                     for k, v in st.items()})
@@ -499,7 +558,7 @@ def main():
     # ---- roofline of the dominant kernel (largest total device time among the layer kernels)
     roofline = None
     layer_ops = table
-    if layer_ops and rank == 0:
+    if args.full and layer_ops and rank == 0:
         (op, dims), (cnt, tot) = layer_ops[0]
         avg_s = tot / cnt / 1e3
         # one extra untimed step through the op-by-op engine (same kernels, same rule books) to count the
@@ -576,7 +635,7 @@ def main():
     # the codec (3 pool threads, sender/encoder/encoder.py:50, receiver/decoder/decoder.py:47): host
     # entropy coding of one frame overlaps GPU work of another.  Not the reported `value`.
     inflight = None
-    if args.inflight > 1 and not tiled_mode:
+    if args.full and args.inflight > 1 and not tiled_mode:
         import concurrent.futures as cf
         enc_n = pkg.CompressionPipeline(SETTINGS, device=local, slots=args.inflight)
         dec_n = pkg.DecompressionPipeline(device=local, slots=args.inflight, output="device")
@@ -603,7 +662,7 @@ def main():
         del enc_n, dec_n
 
     cpu, oracle_full = None, None
-    if rank == 0 and not tiled_mode and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not tiled_mode and not args.no_cpu_baseline:
         abi = importlib.import_module(PKG + "._abi")
         t0 = time.time()
         cpu, oracle_full = cpu_baseline(wl, frames[0], args.cpu_sample, abi.host_cpu_budget(), runs=args.cpu_runs)
@@ -613,7 +672,7 @@ def main():
     # point-to-point D1 and luma PSNR of the decoded frame against the source, outside the timed region; for the HIP
     # reconstruction and for the CPU oracle's, which must be the same arrays
     quality = None
-    if rank == 0 and not tiled_mode and not args.no_psnr:
+    if args.full and rank == 0 and not tiled_mode and not args.no_psnr:
         metrics = importlib.import_module(PKG + ".metrics")
         t0 = time.time()
         quality = {"hip": metrics.frame_quality(frames[0], rec[0])}
@@ -629,7 +688,7 @@ def main():
         log(f"distortion figures in {time.time() - t0:.1f}s:", quality)
 
     configs = None
-    if rank == 0 and not tiled_mode and not args.no_configs:
+    if args.full and rank == 0 and not tiled_mode and not args.no_configs:
         abi = importlib.import_module(PKG + "._abi")
         t0 = time.time()
         configs = bench_configs(pkg, wl, local, abi.host_cpu_budget(), steps=args.config_steps,
@@ -666,6 +725,7 @@ def main():
             "data": "synthetic",
             "timing": "K steps one after the other between two fences; the interpreter's cyclic garbage collector is "
                       "collected before and disabled inside every timed region (timeit's practice)",
+            "full": args.full,
             "config": {"workload": workload,
                        "weights": "UNTRAINED: seeded synthetic checkpoint (tools/make_checkpoint.py) — the reference's "
                                   "weights are not in its tree; bpp and PSNR below are those of this checkpoint, not of "
@@ -681,8 +741,8 @@ def main():
                                       "behind its last frame record (invisible to the reference's reader) from which "
                                       "this decoder decodes the y string on 16 host threads"},
             "encode_ms": enc_ms, "decode_ms": dec_ms,
-            "value_hbm_resident": frames_total / elapsed_hbm,
-            "ms_per_step_hbm_resident": 1e3 * elapsed_hbm / args.steps,
+            "value_hbm_resident": frames_total / elapsed_hbm if elapsed_hbm else None,
+            "ms_per_step_hbm_resident": 1e3 * elapsed_hbm / args.steps if elapsed_hbm else None,
             "encode_ms_hbm_resident": enc_ms_hbm, "decode_ms_hbm_resident": dec_ms_hbm,
             "bpp": [float(b) for b in side["gop_info"]["bpp"]],
             "value_gpu_rans": gpu_rans["value"] if gpu_rans else None,

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -66,10 +67,11 @@ def test_rccl_on_a_one_gpu_box_is_refused():
 
 @pytest.mark.gpu
 def test_driver_line_carries_every_config():
-    """the N = 1 line: headline fields of the contract, roofline + cpu_baseline objects, and one entry per BASELINE.json
+    """the N = 1 line of --full: headline fields of the contract, roofline + cpu_baseline objects, and one entry per BASELINE.json
     configuration beside the headline's (C1, C3, C4, C5 on one GPU) plus the reference's operating point (a GOP of 5
     recorded ZED frames), the affordable ones checked against the oracle inside the run"""
-    r = _run(["--steps", "2", "--warmup", "1", "--points", "60000", "--cpu-runs", "1", "--inflight", "0", "--config-steps", "1"])
+    r = _run(["--steps", "2", "--warmup", "1", "--points", "60000", "--cpu-runs", "1", "--inflight", "0", "--config-steps", "1",
+              "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -97,3 +99,32 @@ def test_rccl_leg_with_a_world_of_one():
     assert line["n_gpus"] == line["ranks_seen"] == 1 and line["backend"].startswith("nccl")
     assert "configs[4]" in line["config"]["workload"] and line["config"]["frames_per_step_per_gpu"] == 2
     assert len(line["ms_per_step_per_rank"]) == 1 and line["value"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path, wl, oracle):
+    """a plain run: exactly --steps timed steps, the figures of --full left out, and --dump-outputs writes what the
+    last timed step returned — the containers of the three qualities and the decoded frame, which are the CPU
+    oracle's for the same seeded frame"""
+    dump = tmp_path / "out"
+    r = _run(["--steps", "3", "--warmup", "1", "--points", "60000", "--dump-outputs", str(dump)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["full"] is False and line["unit"] == "frames/s" and line["dtype"] == "f32"
+    assert line["value"] * line["ms_per_step"] == pytest.approx(1e3)
+    every = [ln for ln in r.stderr.splitlines() if "per-step ms (host frames)" in ln]
+    assert len(every) == 1 and len(every[0].split("every step: ")[1].split()) == 3
+    for key in ("roofline", "cpu_baseline", "configs", "gpu_rans", "seek_points", "value_hbm_resident", "d1_psnr",
+                "throughput_in_flight"):
+        assert line[key] is None, key
+    settings = [[1.0, 0.0], [0.0, 1.0], [1, 1]]
+    frame = wl.room(60000, seed=0)
+    ref, _ = oracle.compress([dict(frame)], settings)
+    for q in (1, 2, 3):
+        got = np.load(dump / f"container_q{q}.npy")
+        assert got.dtype == np.float32 and bytes(got.astype(np.uint8)) == ref[q], q
+    assert np.load(dump / "bpp.npy").tolist() == line["bpp"]
+    rec = oracle.decompress(ref[3])
+    assert len(rec) == 1 and not (dump / "frame1_points.npy").exists()
+    assert np.array_equal(np.load(dump / "frame0_points.npy"), rec[0]["points"])
+    assert np.array_equal(np.load(dump / "frame0_colors.npy"), rec[0]["colors"])

@@ -6,7 +6,7 @@ cp "$LIB" /tmp/libpcc_orig.so
 for v in "$@"; do
   echo "=== $v"
   cp "$v" "$LIB"
-  python bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-psnr --inflight 0 2>/dev/null | python3 -c "
+  python bench.py --full --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-psnr --inflight 0 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

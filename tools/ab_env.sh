@@ -5,7 +5,7 @@ set -u
 VAR=$1; shift
 for rep in 1 2; do
 for v in "$@"; do
-  env $VAR=$v python bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-psnr --inflight 0 --no-configs 2> /tmp/ab_env.log | python3 -c "
+  env $VAR=$v python bench.py --full --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-psnr --inflight 0 --no-configs 2> /tmp/ab_env.log | python3 -c "
 import sys, json, re
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Mean SQ counters of the largest launch of kernels whose name contains a pattern.
 
-    gpurun: rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_INST_ANY ... --output-format csv \
-                -d gpurun_out/pmc_sq -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --inflight 0
-    here:   python tools/pmc_sq.py gpurun_out/pmc_sq k_gconv_mfma
+    on the GPU: rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_INST_ANY ... --output-format csv \
+                    -d prof_out/pmc_sq -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --inflight 0
+    then:       python tools/pmc_sq.py prof_out/pmc_sq k_gconv_mfma
 """
 import collections
 import csv
