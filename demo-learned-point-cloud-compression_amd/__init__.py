@@ -22,6 +22,9 @@ def __getattr__(name):
     if name in ("SparseTensor", "CoordSet"):
         from . import sparse
         return getattr(sparse, name)
+    if name == "GeometryCodec":
+        from .geometry import GeometryCodec
+        return GeometryCodec
     if name == "Runtime":
         from .runtime import Runtime
         return Runtime

@@ -76,6 +76,9 @@ PROTOTYPES = {
     "pcc_octree_blob_version": (i32, [vp, i64]),
     "pcc_octree_decode_ctx": (i32, [vp, vp, i64, vp, i64, pi64]),
     "pcc_octree_decode_dev": (i32, [vp, vp, i64, vp, i64, pi64, pi64]),
+    "pcc_morton_keys_frames": (i32, [vp, vp, i32, i64, vp, i32, vp, vp]),
+    "pcc_octree_encode_frames": (i32, [vp, vp, i64, i32, i32, vp, i64, pi64]),
+    "pcc_octree_decode_frames": (i32, [vp, C.POINTER(C.c_void_p), pi64, i32, vp, vp, i64, pi64]),
     "pcc_abi_version": (i32, []),
     "pcc_last_error": (C.c_char_p, []),
     "pcc_create": (vp, [i32, vp]),

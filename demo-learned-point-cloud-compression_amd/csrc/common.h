@@ -106,6 +106,20 @@ int pcc_descendant_map(pcc_ctx* ctx, const int32_t* d_nbr_parent, int64_t parent
 int pcc_octree_small_max();
 int pcc_octree_small_async(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int key_shift, int depth, uint8_t* d_occ,
                            int64_t cap_s, uint32_t* d_counts);
+// octree.hip: the levels of many frames in launches whose number does not depend on the frame count (octree2.hip's
+// batched coder).  One row per frame; its level counts and leaf count go to counts + PCC_OCT_CSTRIDE * slot.
+#define PCC_OCT_CSTRIDE 20
+struct PccOctFrame {
+  int64_t key_lo, n;       // leaves d_keys[key_lo, key_lo + n), Morton-sorted, distinct
+  int64_t occ_off, cap;    // the occupancy bytes, root-first, at d_occ + occ_off (4-aligned), at most cap bytes
+  int64_t wave0;           // wave form (n > pcc_octree_small_max()): the frame's first wave among the large frames
+  uint64_t mask;           // pcc_octree_leaf_mask(depth)
+  int32_t depth, slot;
+};
+uint64_t pcc_octree_leaf_mask(int depth);
+size_t pcc_octree_frames_scratch(int64_t n_waves, int nl);
+int pcc_octree_frames_async(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, const PccOctFrame* h_tab,
+                            const PccOctFrame* d_tab, int ns, int nl, uint8_t* d_occ, uint32_t* d_counts);
 // parts of a blob of version 3 for n leaves: min(8, n / 4096), at least 2 (the rule oracle/pcc_oracle.c states)
 static inline int pcc_octree_parts_for(int64_t n) {
   const int64_t k = n / 4096;

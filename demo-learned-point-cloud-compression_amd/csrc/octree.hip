@@ -253,68 +253,113 @@ int pcc_octree_parts_async(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int 
   return PCC_OK;
 }
 
-// ---- many-workgroup form (n > OCT_SMALL_MAX): one wave per 64 consecutive leaves -----------------------------
-// hist[L][w] = leaves of wave w that open a level-L node (lmin <= L); rows L >= depth stay 0
-__global__ __launch_bounds__(256) void k_octw_hist(const uint64_t* __restrict__ keys, int64_t n, int shift, uint64_t mask,
-                                                   int depth, int64_t n_waves, uint32_t* __restrict__ hist) {
+// ---- many frames, one launch per step (octree2.hip's batched coder) -----------------------------------------------
+// tab[f] (PccOctFrame, common.h) describes frame f: its leaves, its occupancy bytes, where its counts go.  Frames of
+// at most OCT_SMALL_MAX leaves take one workgroup each (the single-workgroup form); larger ones the wave form below.
+__global__ __launch_bounds__(OCT_T) void k_oct_frames(const uint64_t* __restrict__ keys, int shift,
+                                                      const PccOctFrame* __restrict__ tab, uint8_t* __restrict__ occ,
+                                                      uint32_t* __restrict__ counts) {
+  const PccOctFrame fr = tab[blockIdx.x];
+  oct_small_body(keys + fr.key_lo, (int)fr.n, shift, fr.mask, fr.depth, reinterpret_cast<uint32_t*>(occ + fr.occ_off),
+                 (int)fr.cap, counts + (int64_t)PCC_OCT_CSTRIDE * fr.slot);
+}
+
+// ---- many-workgroup form (n > OCT_SMALL_MAX): one wave per 64 consecutive leaves of a frame --------------------------
+// The waves of all large frames are numbered in one sequence (frame f owns waves [wave0, wave0 + nw)); a wave finds
+// its frame by a search over wave0, the same for all its lanes.
+__device__ __forceinline__ int octw_frame(const PccOctFrame* __restrict__ tab, int nl, int64_t w) {
+  int lo = 0, hi = nl - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].wave0 <= w) lo = mid; else hi = mid - 1;
+  }
+  return __builtin_amdgcn_readfirstlane(lo);
+}
+
+// hist[16 wave0 + L nw + w] = leaves of wave w of its frame that open a level-L node (lmin <= L); rows L >= depth stay 0
+__global__ __launch_bounds__(256) void k_octw_hist(const uint64_t* __restrict__ keys, int shift,
+                                                   const PccOctFrame* __restrict__ tab, int nl, int64_t n_waves,
+                                                   uint32_t* __restrict__ hist) {
   const int lane = threadIdx.x & 63;
-  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (w >= n_waves) return;
+  const int64_t wg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wg >= n_waves) return;
+  const PccOctFrame fr = tab[octw_frame(tab, nl, wg)];
+  const int64_t n = fr.n, nw = (n + 63) / 64, w = wg - fr.wave0;
+  const uint64_t* fk = keys + fr.key_lo;
+  const int depth = fr.depth;
   const int64_t e = w * 64 + lane, ec = e < n ? e : n - 1;
-  const uint64_t kc = (keys[ec] >> shift) & mask, kp = ec > 0 ? (keys[ec - 1] >> shift) & mask : 0ull;
+  const uint64_t kc = (fk[ec] >> shift) & fr.mask, kp = ec > 0 ? (fk[ec - 1] >> shift) & fr.mask : 0ull;
   const int lm = e < n ? oct_lmin(kp, kc, e == 0, depth) : OCT_MAXD + 2;
   uint32_t mine = 0;
   for (int L = 0; L < depth; ++L) {
     const uint32_t c = (uint32_t)__popcll(__ballot(lm <= L));
     mine = lane == L ? c : mine;
   }
-  if (lane < OCT_MAXD) hist[(int64_t)lane * n_waves + w] = mine;
+  if (lane < OCT_MAXD) hist[OCT_MAXD * fr.wave0 + (int64_t)lane * nw + w] = mine;
 }
 
-// from the exclusive scan of hist (flattened [16][n_waves]): counts[L] = nodes of level L (counts[depth] = leaves),
-// offs[L] = bytes in front of level L in the root-first packed array (offs[depth] = all nodes)
-__global__ void k_octw_offsets(const uint32_t* __restrict__ scan, const uint32_t* __restrict__ total, int64_t n_waves,
-                               int depth, uint32_t n, uint32_t* __restrict__ counts, uint32_t* __restrict__ offs) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// from the exclusive scan of hist (cells entries): per frame (one thread each) counts[L] = nodes of level L
+// (counts[depth] = leaves), offs[17 f + L] = bytes in front of level L in its root-first packed array (offs[.. depth] =
+// all nodes)
+__global__ __launch_bounds__(64) void k_octw_offsets(const uint32_t* __restrict__ scan, const uint32_t* __restrict__ total,
+                                                     int64_t cells, const PccOctFrame* __restrict__ tab, int nl,
+                                                     uint32_t* __restrict__ counts, uint32_t* __restrict__ offs) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nl) return;
+  const PccOctFrame fr = tab[f];
+  const int64_t base = OCT_MAXD * fr.wave0, nw = (fr.n + 63) / 64;
+  uint32_t* cf = counts + (int64_t)PCC_OCT_CSTRIDE * fr.slot;
+  uint32_t* of = offs + (int64_t)(OCT_MAXD + 1) * f;
   uint32_t off = 0;
-  for (int L = 0; L < depth; ++L) {
-    const uint32_t lo = scan[(int64_t)L * n_waves], hi = L + 1 < OCT_MAXD ? scan[(int64_t)(L + 1) * n_waves] : *total;
-    counts[L] = hi - lo;
-    offs[L] = off;
+  for (int L = 0; L < fr.depth; ++L) {
+    const int64_t at = base + (int64_t)(L + 1) * nw;
+    const uint32_t lo = scan[base + (int64_t)L * nw], hi = at < cells ? scan[at] : *total;
+    cf[L] = hi - lo;
+    of[L] = off;
     off += hi - lo;
   }
-  counts[depth] = n;
-  offs[depth] = off;
+  cf[fr.depth] = (uint32_t)fr.n;
+  of[fr.depth] = off;
 }
 
-__global__ __launch_bounds__(256) void k_octw_zero(uint32_t* __restrict__ occ32, const uint32_t* __restrict__ offs, int depth,
-                                                   int64_t cap_words) {
-  int64_t words = ((int64_t)offs[depth] + 3) / 4;
-  words = words < cap_words ? words : cap_words;
+// blockIdx.y = frame: its packed bytes (as many as its nodes, at most its capacity) to zero
+__global__ __launch_bounds__(256) void k_octw_zero(uint8_t* __restrict__ occ, const PccOctFrame* __restrict__ tab,
+                                                   const uint32_t* __restrict__ offs) {
+  const PccOctFrame fr = tab[blockIdx.y];
+  uint32_t* occ32 = reinterpret_cast<uint32_t*>(occ + fr.occ_off);
+  int64_t words = ((int64_t)offs[(int64_t)(OCT_MAXD + 1) * blockIdx.y + fr.depth] + 3) / 4;
+  words = words < fr.cap / 4 ? words : fr.cap / 4;
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < words; j += (int64_t)gridDim.x * blockDim.x) occ32[j] = 0u;
 }
 
 // ranks the wave's leaves per level and ORs the octants in.  The bits of lanes that hit the same 32-bit word are
 // merged inside the wave first (the children of a node and the nodes of a word are neighbouring lanes: a segmented OR
 // over runs of equal word index), so that a word receives one atomic per wave that touches it
-__global__ __launch_bounds__(256) void k_octw_emit(const uint64_t* __restrict__ keys, int64_t n, int shift, uint64_t mask,
-                                                   int depth, int64_t n_waves, const uint32_t* __restrict__ scan,
-                                                   const uint32_t* __restrict__ offs, uint32_t* __restrict__ occ32,
-                                                   int64_t cap) {
+__global__ __launch_bounds__(256) void k_octw_emit(const uint64_t* __restrict__ keys, int shift,
+                                                   const PccOctFrame* __restrict__ tab, int nl, int64_t n_waves,
+                                                   const uint32_t* __restrict__ scan, const uint32_t* __restrict__ offs,
+                                                   uint8_t* __restrict__ occ) {
   const int lane = threadIdx.x & 63;
-  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (w >= n_waves) return;
-  if ((int64_t)offs[depth] > cap) return;   // the host sees the counts and reports the capacity error
+  const int64_t wg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wg >= n_waves) return;
+  const int f = octw_frame(tab, nl, wg);
+  const PccOctFrame fr = tab[f];
+  const uint32_t* of = offs + (int64_t)(OCT_MAXD + 1) * f;
+  const int depth = fr.depth;
+  if ((int64_t)of[depth] > (fr.cap & ~(int64_t)3)) return;   // the host sees the counts and reports the capacity error
+  uint32_t* occ32 = reinterpret_cast<uint32_t*>(occ + fr.occ_off);
+  const int64_t n = fr.n, nw = (n + 63) / 64, w = wg - fr.wave0, base = OCT_MAXD * fr.wave0;
+  const uint64_t* fk = keys + fr.key_lo;
   const uint64_t lanes_le = ~0ull >> (63 - lane);
   const int64_t e = w * 64 + lane, ec = e < n ? e : n - 1;
   const bool valid = e < n;
-  const uint64_t kc = (keys[ec] >> shift) & mask, kp = ec > 0 ? (keys[ec - 1] >> shift) & mask : 0ull;
+  const uint64_t kc = (fk[ec] >> shift) & fr.mask, kp = ec > 0 ? (fk[ec - 1] >> shift) & fr.mask : 0ull;
   const int lm = valid ? oct_lmin(kp, kc, e == 0, depth) : OCT_MAXD + 2;
   // level-L nodes opened before this wave, and the level's offset, in lane L's registers
   uint32_t before_reg = 0, off_reg = 0;
   if (lane < depth) {
-    before_reg = scan[(int64_t)lane * n_waves + w] - scan[(int64_t)lane * n_waves];
-    off_reg = offs[lane];
+    before_reg = scan[base + (int64_t)lane * nw + w] - scan[base + (int64_t)lane * nw];
+    off_reg = of[lane];
   }
   int lo = lm;
 #pragma unroll
@@ -340,39 +385,53 @@ __global__ __launch_bounds__(256) void k_octw_emit(const uint64_t* __restrict__ 
   }
 }
 
-// Internal (octree2.hip): the levels of a large input and nothing read back — root-first packed into d_occ (4-byte
-// aligned, cap bytes), node counts of levels 0 .. depth-1 and the leaf count into d_counts[depth + 1].  A total above
-// cap leaves d_occ untouched.  Scratch from the arena behind what the caller has allocated (the caller reserves
-// pcc_octree_wave_scratch(n) bytes for it).
-size_t pcc_octree_wave_scratch(int64_t n) {
-  const int64_t n_waves = (n + 63) / 64;
-  return 2 * pcc_align((size_t)n_waves * OCT_MAXD * 4) + pcc_scan_scratch_bytes(n_waves * OCT_MAXD) + 4096;
+uint64_t pcc_octree_leaf_mask(int depth) { return depth == 16 ? ~0ull >> 16 : ((1ull << (3 * depth)) - 1); }
+
+// Internal (octree2.hip): the levels of many frames and nothing read back.  h_tab / d_tab: the same table on the host
+// and on the device (already queued on the stream), the ns frames of the single-workgroup form first, then the nl of
+// the wave form (wave0 numbered from 0 in that order).  Scratch from the arena behind what the caller has allocated
+// (the caller reserves pcc_octree_frames_scratch(waves of the large frames, nl) bytes for it).  Launches: one for the
+// small frames, five and a scan for the large ones, whatever the frame count.
+size_t pcc_octree_frames_scratch(int64_t n_waves, int nl) {
+  return 2 * pcc_align((size_t)n_waves * OCT_MAXD * 4) + pcc_align((size_t)nl * (OCT_MAXD + 1) * 4) +
+         pcc_scan_scratch_bytes(n_waves * OCT_MAXD) + 4096;
 }
-int pcc_octree_wave_async(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int key_shift, int depth, uint8_t* d_occ,
-                          int64_t cap, uint32_t* d_counts) {
-  PCC_REQUIRE(ctx && d_keys && d_occ && d_counts && n >= 1 && n < ((int64_t)1 << 27) && depth >= 1 && depth <= 16 &&
-                  key_shift >= 0 && key_shift % 3 == 0 && key_shift + 3 * depth <= 48 && cap >= 4 &&
-                  (uintptr_t)d_occ % 4 == 0,
-              PCC_E_ARG, "pcc_octree_wave_async: bad argument (n=%lld depth=%d)", (long long)n, depth);
+int pcc_octree_frames_async(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, const PccOctFrame* h_tab,
+                            const PccOctFrame* d_tab, int ns, int nl, uint8_t* d_occ, uint32_t* d_counts) {
+  PCC_REQUIRE(ctx && d_keys && h_tab && d_tab && d_occ && d_counts && ns >= 0 && nl >= 0 && key_shift >= 0 &&
+                  key_shift % 3 == 0 && (uintptr_t)d_occ % 4 == 0,
+              PCC_E_ARG, "pcc_octree_frames_async: bad argument");
   hipStream_t st = ctx->stream;
-  const int64_t n_waves = (n + 63) / 64, cells = n_waves * OCT_MAXD;
+  for (int f = 0; f < ns + nl; ++f) {
+    const PccOctFrame& fr = h_tab[f];
+    PCC_REQUIRE(fr.n >= 1 && (f < ns ? fr.n <= OCT_SMALL_MAX : fr.n > OCT_SMALL_MAX) && fr.n < ((int64_t)1 << 27) &&
+                    fr.depth >= 1 && fr.depth <= 16 && key_shift + 3 * fr.depth <= 48 && fr.cap >= 4 &&
+                    fr.cap < ((int64_t)1 << (f < ns ? 31 : 32)) && fr.occ_off % 4 == 0,
+                PCC_E_ARG, "pcc_octree_frames_async: frame %d (n=%lld depth=%d)", f, (long long)fr.n, fr.depth);
+  }
+  if (ns > 0) {
+    hipLaunchKernelGGL(k_oct_frames, dim3((unsigned)ns), dim3(OCT_T), 0, st, d_keys, key_shift, d_tab, d_occ, d_counts);
+    PCC_CHECK_LAUNCH();
+  }
+  if (nl == 0) return PCC_OK;
+  const PccOctFrame* tl = d_tab + ns;
+  const PccOctFrame& last = h_tab[ns + nl - 1];
+  const int64_t n_waves = last.wave0 + (last.n + 63) / 64, cells = n_waves * OCT_MAXD;
   uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, (size_t)cells * 4);
   uint32_t* scan = (uint32_t*)pcc_arena_alloc(ctx, (size_t)cells * 4);
-  uint32_t* small = (uint32_t*)pcc_arena_alloc(ctx, 256);   // total | offs[17]
-  if (!hist || !scan || !small) return PCC_E_NOMEM;
-  uint32_t* total = small;
-  uint32_t* offs = small + 1;
-  const uint64_t leaf_mask = (depth == 16 ? ~0ull >> 16 : ((1ull << (3 * depth)) - 1));
-  hipLaunchKernelGGL(k_octw_hist, dim3(nblk(n_waves, 4)), dim3(256), 0, st, d_keys, n, key_shift, leaf_mask, depth, n_waves, hist);
+  uint32_t* offs = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nl * (OCT_MAXD + 1) * 4);
+  uint32_t* total = (uint32_t*)pcc_arena_alloc(ctx, 256);
+  if (!hist || !scan || !offs || !total) return PCC_E_NOMEM;
+  hipLaunchKernelGGL(k_octw_hist, dim3(nblk(n_waves, 4)), dim3(256), 0, st, d_keys, key_shift, tl, nl, n_waves, hist);
   PCC_CHECK_LAUNCH();
   PCC_TRY(pcc_scan_exclusive_u32(ctx, hist, scan, cells, total));
-  hipLaunchKernelGGL(k_octw_offsets, dim3(1), dim3(64), 0, st, (const uint32_t*)scan, (const uint32_t*)total, n_waves, depth,
-                     (uint32_t)n, d_counts, offs);
+  hipLaunchKernelGGL(k_octw_offsets, dim3(nblk(nl, 64)), dim3(64), 0, st, (const uint32_t*)scan, (const uint32_t*)total, cells,
+                     tl, nl, d_counts, offs);
   PCC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_octw_zero, dim3(512), dim3(256), 0, st, (uint32_t*)d_occ, (const uint32_t*)offs, depth, cap / 4);
+  hipLaunchKernelGGL(k_octw_zero, dim3(128, (unsigned)nl), dim3(256), 0, st, d_occ, tl, (const uint32_t*)offs);
   PCC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_octw_emit, dim3(nblk(n_waves, 4)), dim3(256), 0, st, d_keys, n, key_shift, leaf_mask, depth, n_waves,
-                     (const uint32_t*)scan, (const uint32_t*)offs, (uint32_t*)d_occ, cap / 4 * 4);
+  hipLaunchKernelGGL(k_octw_emit, dim3(nblk(n_waves, 4)), dim3(256), 0, st, d_keys, key_shift, tl, nl, n_waves,
+                     (const uint32_t*)scan, (const uint32_t*)offs, d_occ);
   PCC_CHECK_LAUNCH();
   return PCC_OK;
 }
@@ -388,9 +447,9 @@ extern "C" int pcc_octree_levels(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n
   hipStream_t st = ctx->stream;
   const size_t n1 = pcc_align((size_t)n);
   const size_t cap_s = (size_t)depth * n1;   // bytes of the assembled levels (n * depth always suffices)
-  PCC_TRY(pcc_arena_reserve(ctx, cap_s + pcc_octree_wave_scratch(n) + 4096));
+  PCC_TRY(pcc_arena_reserve(ctx, cap_s + pcc_octree_frames_scratch((n + 63) / 64, 1) + 8192));
   uint8_t* occ_lv = (uint8_t*)pcc_arena_alloc(ctx, cap_s);
-  uint32_t* counts = (uint32_t*)pcc_arena_alloc(ctx, (size_t)(depth + 1) * 4);  // counts[L] = nodes at level L
+  uint32_t* counts = (uint32_t*)pcc_arena_alloc(ctx, (size_t)PCC_OCT_CSTRIDE * 4);  // counts[L] = nodes at level L
   if (!occ_lv || !counts) return PCC_E_NOMEM;
   PccProfScope prof(ctx, "octree_levels", n, depth, 0, 0);
   if (n <= OCT_SMALL_MAX) {
@@ -400,7 +459,13 @@ extern "C" int pcc_octree_levels(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n
     PCC_CHECK_LAUNCH();
   } else {
     PCC_REQUIRE(cap_s < ((size_t)1 << 32), PCC_E_ARG, "pcc_octree_levels: %lld leaves at depth %d", (long long)n, depth);
-    PCC_TRY(pcc_octree_wave_async(ctx, d_keys, n, key_shift, depth, occ_lv, (int64_t)cap_s, counts));
+    // the one frame's table crosses from the pinned block (bytes 2048 ..; the read-back below uses the first bytes)
+    PccOctFrame* h_tab = (PccOctFrame*)((char*)ctx->pinned + 2048);
+    *h_tab = PccOctFrame{0, n, 0, (int64_t)cap_s, 0, pcc_octree_leaf_mask(depth), depth, 0};
+    PccOctFrame* d_tab = (PccOctFrame*)pcc_arena_alloc(ctx, sizeof(PccOctFrame));
+    if (!d_tab) return PCC_E_NOMEM;
+    PCC_HIP(hipMemcpyAsync(d_tab, h_tab, sizeof(PccOctFrame), hipMemcpyHostToDevice, st));
+    PCC_TRY(pcc_octree_frames_async(ctx, d_keys, key_shift, h_tab, d_tab, 0, 1, occ_lv, counts));
   }
   // one read-back (the counts), one copy (the caller's array need not be aligned)
   uint32_t* hc = (uint32_t*)ctx->pinned;

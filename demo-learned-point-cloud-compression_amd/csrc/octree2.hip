@@ -39,11 +39,9 @@
 #include <string.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
-size_t pcc_octree_wave_scratch(int64_t n);
-int pcc_octree_wave_async(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int key_shift, int depth, uint8_t* d_occ,
-                          int64_t cap, uint32_t* d_counts);
 void octree_root(uint64_t first, uint64_t last, int key_shift, int* depth, int32_t origin[3]);
 
 namespace {
@@ -85,14 +83,44 @@ static O2Layout o2_layout(int64_t n_nodes) {
   return O2Layout{s, c};
 }
 
+// Every kernel below codes or decodes the frames of one call side by side: a table in device memory has one row per
+// frame, a block finds its frame by a search over the rows' first block (the same for all its threads), and a single
+// frame is the table of one row.  Last row whose start <= v:
+template <typename Start>
+__device__ __forceinline__ int o2_find(int nf, int64_t v, Start start) {
+  int lo = 0, hi = nf - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (start(mid) <= v) lo = mid; else hi = mid - 1;
+  }
+  return __builtin_amdgcn_readfirstlane(lo);
+}
+
 // ---- encoder -----------------------------------------------------------------------------------------------------
-// zeros and ones seen per context over the whole frame: cnt[2 ctx + bit]
-__global__ __launch_bounds__(256) void k_o2_stats(const uint8_t* __restrict__ occ, int64_t n_nodes, int64_t start_last,
-                                                  int64_t start_prev, uint32_t* __restrict__ cnt) {
+// one frame (>= 1 leaf) of an encode call
+struct O2Frame {
+  int64_t occ_off;                     // its occupancy bytes (4-aligned) in the call's node array
+  int64_t n_nodes, start_last, start_prev;
+  int64_t rec_off;                     // 16-bit words of records (and of word regions) of the frames in front of it
+  int64_t out_off, out_cap;            // its blob in the output staging: offset, bound
+  int32_t S, nc, cb, sb, sn;           // chunks: S, count, first (of the call); stats blocks: first, count
+  int32_t depth;
+  uint32_t n_points;
+  int32_t origin[3];
+};
+
+// zeros and ones seen per context over the whole frame: cnt[216 f + 2 ctx + bit]; frame f takes blocks [sb, sb + sn)
+__global__ __launch_bounds__(256) void k_o2_stats(const uint8_t* __restrict__ occ_all, const O2Frame* __restrict__ tab, int nf,
+                                                  uint32_t* __restrict__ cnt_all) {
   __shared__ uint32_t s_cnt[2 * kCtx];
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].sb; });
+  const uint8_t* occ = occ_all + tab[f].occ_off;
+  const int64_t n_nodes = tab[f].n_nodes, start_last = tab[f].start_last, start_prev = tab[f].start_prev;
+  const int64_t b = (int64_t)blockIdx.x - tab[f].sb, nb = tab[f].sn;
+  uint32_t* cnt = cnt_all + 2 * kCtx * (int64_t)f;
   for (int i = threadIdx.x; i < 2 * kCtx; i += blockDim.x) s_cnt[i] = 0u;
   __syncthreads();
-  for (int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; node < n_nodes; node += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t node = b * blockDim.x + threadIdx.x; node < n_nodes; node += nb * blockDim.x) {
     const uint32_t byte = occ[node];
     const int cls = node >= start_last ? 0 : (node >= start_prev ? 1 : 2);
     int ones = 0;
@@ -127,17 +155,26 @@ __device__ const O2Rcp kO2Rcp = o2_rcp_table();
 // in reverse, every renormalisation word stored downwards from the end of the lane's own T-word region of `work`
 // ([chunk][lane][T]: a step emits at most one word).  states[chunk][128] and lens[chunk][64] receive the final states
 // and the word counts; words_out[chunk] = 192 + sum of the counts.  Every global access of the coding loop is
-// unconditional (rans_gpu.hip's rule).
-__global__ __launch_bounds__(64) void k_o2_enc(const uint32_t* __restrict__ occ32, int64_t n_nodes, int64_t start_last,
-                                               int64_t start_prev, int S, const uint32_t* __restrict__ cnt,
-                                               uint16_t* __restrict__ rec, uint16_t* __restrict__ work,
-                                               uint16_t* __restrict__ states, uint16_t* __restrict__ lens,
-                                               uint32_t* __restrict__ words_out, uint16_t* __restrict__ p0_out) {
+// unconditional (rans_gpu.hip's rule).  Block = chunk of the call: frame f owns blocks [cb, cb + nc); its records and
+// word regions start rec_off words in, states / lens / words_out are indexed by the call's chunk.
+__global__ __launch_bounds__(64) void k_o2_enc(const uint8_t* __restrict__ occ_all, const O2Frame* __restrict__ tab, int nf,
+                                               const uint32_t* __restrict__ cnt_all, uint16_t* __restrict__ rec_all,
+                                               uint16_t* __restrict__ work_all, uint16_t* __restrict__ states,
+                                               uint16_t* __restrict__ lens, uint32_t* __restrict__ words_out,
+                                               uint16_t* __restrict__ p0_all) {
   __shared__ uint16_t s_model[(kCtx + 1) * kLanes];   // [ctx][lane]; row kCtx takes the writes of decisions that are not coded
   __shared__ uint16_t s_p0[kCtx];
   __shared__ __attribute__((aligned(16))) uint32_t s_rcp[4096];
   const int lane = threadIdx.x;
-  const int64_t c = blockIdx.x;
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].cb; });
+  const int64_t cg = blockIdx.x, c = cg - tab[f].cb;
+  const uint32_t* occ32 = reinterpret_cast<const uint32_t*>(occ_all + tab[f].occ_off);
+  const int64_t n_nodes = tab[f].n_nodes, start_last = tab[f].start_last, start_prev = tab[f].start_prev;
+  const int S = tab[f].S;
+  const uint32_t* cnt = cnt_all + 2 * kCtx * (int64_t)f;
+  uint16_t* p0_out = p0_all + kCtx * (int64_t)f;
+  uint16_t* rec = rec_all + tab[f].rec_off;
+  uint16_t* work = work_all + tab[f].rec_off;
   for (int ctx = lane; ctx < kCtx; ctx += kLanes) {
     const uint32_t p = o2_p0(cnt[2 * ctx], cnt[2 * ctx + 1]);
     s_p0[ctx] = (uint16_t)p;
@@ -244,34 +281,36 @@ __global__ __launch_bounds__(64) void k_o2_enc(const uint32_t* __restrict__ occ3
       R[d] = fetch(sn - kAhead);   // the slot is free: node sn - kAhead into it
     }
   }
-  states[c * 2 * kLanes + 2 * lane] = (uint16_t)x;
-  states[c * 2 * kLanes + 2 * lane + 1] = (uint16_t)(x >> 16);
+  states[cg * 2 * kLanes + 2 * lane] = (uint16_t)x;
+  states[cg * 2 * kLanes + 2 * lane + 1] = (uint16_t)(x >> 16);
   const uint32_t len = (uint32_t)((int)T - wp);
-  lens[c * kLanes + lane] = (uint16_t)len;
+  lens[cg * kLanes + lane] = (uint16_t)len;
   uint32_t tot = len;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) tot += (uint32_t)__shfl_xor((int)tot, d, 64);
-  if (lane == 0) words_out[c] = 3u * kLanes + tot;
+  if (lane == 0) words_out[cg] = 3u * kLanes + tot;
 }
 
-struct O2Head {
-  int depth;
-  uint32_t n_points;
-  int32_t origin[3];
-  uint32_t S, nc;
-};
-
-// the blob, assembled where `out` points (pinned host memory: the bytes cross PCIe as the kernel writes them):
-// workgroup c < nc moves chunk c (states, length table, the 64 runs), workgroup nc writes the header; *len_out = bytes,
-// or -1 (cap)
-__global__ __launch_bounds__(256) void k_o2_pack(const uint16_t* __restrict__ work, int64_t T,
-                                                 const uint16_t* __restrict__ states, const uint16_t* __restrict__ lens,
-                                                 const uint32_t* __restrict__ words, const uint32_t* __restrict__ counts,
-                                                 const uint16_t* __restrict__ p0, O2Head h, uint8_t* __restrict__ out,
-                                                 int64_t cap, long long* __restrict__ len_out) {
+// the blobs, assembled where `out_all` points (pinned host memory: the bytes cross PCIe as the kernel writes them),
+// frame f's at out_off: frame f owns workgroups [cb + f, cb + f + nc + 1) — workgroup c < nc of them moves chunk c
+// (states, length table, the 64 runs), workgroup nc writes the header; len_out[f] = bytes, or -1 (out_cap)
+__global__ __launch_bounds__(256) void k_o2_pack(const uint16_t* __restrict__ work_all, const O2Frame* __restrict__ tab, int nf,
+                                                 const uint16_t* __restrict__ states_all, const uint16_t* __restrict__ lens_all,
+                                                 const uint32_t* __restrict__ words_all, const uint32_t* __restrict__ counts_all,
+                                                 const uint16_t* __restrict__ p0_all, uint8_t* __restrict__ out_all,
+                                                 long long* __restrict__ len_out) {
   __shared__ unsigned long long s_sum[256];
   __shared__ uint32_t s_off[kLanes + 1];
-  const int64_t c = blockIdx.x, nc = h.nc;
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].cb + i; });
+  const O2Frame& h = tab[f];
+  const int64_t c = (int64_t)blockIdx.x - h.cb - f, nc = h.nc, T = 8 * (int64_t)h.S, cap = h.out_cap;
+  const uint16_t* work = work_all + h.rec_off;
+  const uint16_t* states = states_all + h.cb * 2 * kLanes;
+  const uint16_t* lens = lens_all + h.cb * kLanes;
+  const uint32_t* words = words_all + h.cb;
+  const uint32_t* counts = counts_all + (int64_t)PCC_OCT_CSTRIDE * f;
+  const uint16_t* p0 = p0_all + kCtx * (int64_t)f;
+  uint8_t* out = out_all + h.out_off;
   unsigned long long part = 0;
   const int64_t upto = c < nc ? c : nc;
   for (int64_t j = threadIdx.x; j < upto; j += blockDim.x) part += words[j];
@@ -287,7 +326,7 @@ __global__ __launch_bounds__(256) void k_o2_pack(const uint16_t* __restrict__ wo
     const unsigned long long total = head + before * 2;
     const bool fits = (long long)total <= cap;
     if (threadIdx.x == 0) {
-      *len_out = fits ? (long long)total : -1;
+      len_out[f] = fits ? (long long)total : -1;
       __threadfence_system();
     }
     if (!fits) return;
@@ -299,8 +338,8 @@ __global__ __launch_bounds__(256) void k_o2_pack(const uint16_t* __restrict__ wo
       o32[3] = (uint32_t)h.origin[1];
       o32[4] = (uint32_t)h.origin[2];
       o32[5] = (uint32_t)(total - kHeader);
-      o32[6 + h.depth] = h.S;
-      o32[7 + h.depth] = h.nc;
+      o32[6 + h.depth] = (uint32_t)h.S;
+      o32[7 + h.depth] = (uint32_t)h.nc;
     }
     if ((int)threadIdx.x < h.depth) o32[6 + threadIdx.x] = counts[threadIdx.x];
     uint16_t* o16 = reinterpret_cast<uint16_t*>(o32 + 8 + h.depth);
@@ -334,9 +373,19 @@ __global__ __launch_bounds__(256) void k_o2_pack(const uint16_t* __restrict__ wo
 
 // ---- decoder -----------------------------------------------------------------------------------------------------
 // status (int32): OR of 1 = a chunk ran out of words or did not use all of its words, 2 = an empty node,
-// 8 = the child counts do not add up to the announced level sizes / point count
-struct O2Offs {
-  int64_t off[18];   // off[L] = nodes in front of level L; off[depth] = n_nodes; off[depth + 1] = n_nodes + n_points
+// 8 = the child counts do not add up to the announced level sizes / point count; one per frame of the call
+//
+// one frame (>= 1 point) of a decode call
+struct O2DFrame {
+  int64_t body_off;                    // p0 | chunk table | payload of its blob in the call's uploaded bodies (4-aligned)
+  int64_t table_off, payload_off;      // from body_off
+  int64_t n_nodes, start_last, start_prev, n_points;
+  int64_t node_base;                   // its nodes in the call's node arrays (occupancy, child counts, scan): 4-aligned
+  int64_t link_base;                   // its links in the call's link array: nodes, then leaves
+  int64_t pt_base;                     // its first point in the output
+  int64_t off[17];                     // nodes in front of level L (off[depth] = n_nodes)
+  int32_t S, nc, cb, lb, qb, depth;    // first chunk, first block of k_o2_link, of k_o2_points
+  int32_t origin[3];
 };
 
 // the chunk's words in LDS when they fit (a chunk is 64 S nodes: <= 32 KB of payload for S = 512 unless the stream was
@@ -427,14 +476,22 @@ __device__ __forceinline__ void o2_decode_chunk(uint16_t* s_model, const uint16_
   if (pos != rend) bad |= 1;   // every word of the run consumed
 }
 
-__global__ __launch_bounds__(64) void k_o2_dec(const uint16_t* __restrict__ p0, const uint32_t* __restrict__ table,
-                                               const uint16_t* __restrict__ payload, int64_t n_nodes, int64_t start_last,
-                                               int64_t start_prev, int S, uint32_t* __restrict__ occ32,
-                                               int32_t* __restrict__ status) {
+// block = chunk of the call: frame f owns blocks [cb, cb + nc)
+__global__ __launch_bounds__(64) void k_o2_dec(const uint8_t* __restrict__ bodies, const O2DFrame* __restrict__ tab, int nf,
+                                               uint8_t* __restrict__ occ_all, int32_t* __restrict__ status_all) {
   __shared__ uint16_t s_model[(kCtx + 1) * kLanes];   // row kCtx: dummy (o2_decode_chunk)
   __shared__ __attribute__((aligned(16))) uint16_t s_words[kDecLdsWords];
   const int lane = threadIdx.x;
-  const int64_t c = blockIdx.x;
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].cb; });
+  const int64_t c = (int64_t)blockIdx.x - tab[f].cb;
+  const uint8_t* body = bodies + tab[f].body_off;
+  const uint16_t* p0 = reinterpret_cast<const uint16_t*>(body);
+  const uint32_t* table = reinterpret_cast<const uint32_t*>(body + tab[f].table_off);
+  const uint16_t* payload = reinterpret_cast<const uint16_t*>(body + tab[f].payload_off);
+  const int64_t n_nodes = tab[f].n_nodes, start_last = tab[f].start_last, start_prev = tab[f].start_prev;
+  const int S = tab[f].S;
+  uint32_t* occ32 = reinterpret_cast<uint32_t*>(occ_all + tab[f].node_base);
+  int32_t* status = status_all + f;
   for (int ctx = 0; ctx < kCtx; ++ctx) s_model[ctx * kLanes + lane] = p0[ctx];
   unsigned long long before = 0;
   for (int64_t j = lane; j < c; j += kLanes) before += table[j];
@@ -472,21 +529,31 @@ __global__ __launch_bounds__(256) void k_o2_popc(const uint8_t* __restrict__ occ
 }
 
 // link[child] = parent << 3 | octant for every child the occupancy bytes announce (breadth-first numbering: the first
-// child of node i is node 1 + excl[i]); the first node of every level checks that its level starts where the header
-// says, node 0 checks the total
+// child of node i is node 1 + excl[i], excl the exclusive scan of the child counts over the frame's nodes — the
+// call's one scan minus its value at the frame's first node); the first node of every level checks that its level
+// starts where the header says, node 0 checks the frame's total.  Frame f owns blocks [lb, lb + ceil(n_nodes / 256)).
 __global__ __launch_bounds__(256) void k_o2_link(const uint8_t* __restrict__ occ, const uint32_t* __restrict__ excl,
-                                                 const uint32_t* __restrict__ total, int64_t n_nodes, int64_t n_all,
-                                                 O2Offs offs, int depth, uint32_t* __restrict__ link,
-                                                 int32_t* __restrict__ status) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+                                                 const uint32_t* __restrict__ total, int64_t n_tot,
+                                                 const O2DFrame* __restrict__ tab, int nf, uint32_t* __restrict__ link_all,
+                                                 int32_t* __restrict__ status_all) {
+  const int f = o2_find(nf, blockIdx.x, [&](int j) { return (int64_t)tab[j].lb; });
+  const O2DFrame& fr = tab[f];
+  const int64_t i = ((int64_t)blockIdx.x - fr.lb) * blockDim.x + threadIdx.x, n_nodes = fr.n_nodes;
   if (i >= n_nodes) return;
-  const uint32_t byte = occ[i];
-  const int64_t first = 1 + (int64_t)excl[i];
+  const int64_t base = fr.node_base, n_all = n_nodes + fr.n_points;
+  const uint32_t e0 = excl[base];
+  const uint32_t byte = occ[base + i];
+  const int64_t first = 1 + (int64_t)(excl[base + i] - e0);
   int bad = 0;
-  if (i == 0 && (int64_t)*total != n_all - 1) bad = 8;
-  for (int L = 0; L < depth; ++L)
-    if (i == offs.off[L] && first != offs.off[L + 1]) bad = 8;
-  if (bad) atomicOr(status, bad);
+  if (i == 0) {   // behind the frame's last node: its padding (no children), then the next frame or the end
+    const int64_t end = base + ((n_nodes + 3) & ~(int64_t)3);
+    const uint32_t ev = end < n_tot ? excl[end] : *total;
+    if ((int64_t)(ev - e0) != n_all - 1) bad = 8;
+  }
+  for (int L = 0; L < fr.depth; ++L)
+    if (i == fr.off[L] && first != fr.off[L + 1]) bad = 8;
+  if (bad) atomicOr(status_all + f, bad);
+  uint32_t* link = link_all + fr.link_base;
   int k = 0;
   for (int j = 0; j < 8; ++j)
     if ((byte >> j) & 1u) {
@@ -496,23 +563,68 @@ __global__ __launch_bounds__(256) void k_o2_link(const uint8_t* __restrict__ occ
     }
 }
 
-// every leaf walks up its `depth` links: the octants on the way are its cell inside the root cube
-__global__ __launch_bounds__(256) void k_o2_points(const uint32_t* __restrict__ link, int64_t n_nodes, int64_t n_points,
-                                                   int depth, int ox, int oy, int oz, int32_t* __restrict__ points,
-                                                   int32_t* __restrict__ status) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n_points) return;
+// every leaf walks up its `depth` links: the octants on the way are its cell inside the root cube.  Frame f owns blocks
+// [qb, qb + ceil(n_points / 256)); a link holds a node of its own frame (or 0), so the walk stays inside the frame
+__global__ __launch_bounds__(256) void k_o2_points(const uint32_t* __restrict__ link_all, const O2DFrame* __restrict__ tab, int nf,
+                                                   int32_t* __restrict__ points_all, int32_t* __restrict__ status_all) {
+  const int f = o2_find(nf, blockIdx.x, [&](int j) { return (int64_t)tab[j].qb; });
+  const O2DFrame& fr = tab[f];
+  const int64_t e = ((int64_t)blockIdx.x - fr.qb) * blockDim.x + threadIdx.x;
+  if (e >= fr.n_points) return;
+  const uint32_t* link = link_all + fr.link_base;
+  const int depth = fr.depth;
   uint64_t code = 0;
-  uint32_t idx = (uint32_t)(n_nodes + e);
+  uint32_t idx = (uint32_t)(fr.n_nodes + e);
   for (int d = 0; d < depth; ++d) {
     const uint32_t l = link[idx];
     code |= (uint64_t)(l & 7u) << (3 * d);
     idx = l >> 3;
   }
-  if (idx != 0u) atomicOr(status, 8);
-  points[3 * e] = (int32_t)pcc_compact3(code >> 2) + ox;
-  points[3 * e + 1] = (int32_t)pcc_compact3(code >> 1) + oy;
-  points[3 * e + 2] = (int32_t)pcc_compact3(code) + oz;
+  if (idx != 0u) atomicOr(status_all + f, 8);
+  int32_t* points = points_all + 3 * (fr.pt_base + e);
+  points[0] = (int32_t)pcc_compact3(code >> 2) + fr.origin[0];
+  points[1] = (int32_t)pcc_compact3(code >> 1) + fr.origin[1];
+  points[2] = (int32_t)pcc_compact3(code) + fr.origin[2];
+}
+
+// checks of the keys of an encode call (sorted, distinct after the key shift, frame index < n_frames):
+// flag |= 1 duplicate, 2 out of order, 4 frame index
+__global__ __launch_bounds__(256) void k_of_check(const uint64_t* __restrict__ keys, int64_t n, int shift, int n_frames,
+                                                  int32_t* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t b = keys[i];
+  int bad = (int64_t)(b >> 48) >= n_frames ? 4 : 0;
+  if (i > 0) {
+    const uint64_t a = keys[i - 1];
+    bad |= (a >> shift) == (b >> shift) ? 1 : 0;
+    bad |= a > b ? 2 : 0;
+  }
+  if (bad) atomicOr(flag, bad);
+}
+
+// per frame (thread f <= n_frames): offs[f] = first key of frame f (or n); ends[2 f], ends[2 f + 1] = its first and
+// last key (frames with keys)
+__global__ __launch_bounds__(64) void k_of_frames(const uint64_t* __restrict__ keys, int64_t n, int n_frames,
+                                                  int64_t* __restrict__ offs, uint64_t* __restrict__ ends) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f > n_frames) return;
+  auto lower = [&](uint64_t target) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (keys[mid] < target) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+  };
+  const int64_t lo = lower((uint64_t)f << 48);
+  offs[f] = lo;
+  if (f == n_frames) return;
+  const int64_t hi = lower((uint64_t)(f + 1) << 48);
+  if (hi > lo) {
+    ends[2 * f] = keys[lo];
+    ends[2 * f + 1] = keys[hi - 1];
+  }
 }
 
 inline uint32_t get_u32(const uint8_t* p) {
@@ -537,53 +649,126 @@ static int o2_stage_reserve(pcc_ctx* ctx, size_t bytes) {
 
 // ======================================================================== entry points (internal + C-ABI)
 
-// blob version 2 of the rows d_keys[0 .. n) (Morton-sorted, one frame): two synchronisations (the level counts size
-// the chunks; the blob's length), the blob itself is written into pinned memory by the packing kernel
-int pcc_octree2_encode(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int key_shift, int depth, const int32_t origin[3],
-                       uint8_t* h_out, int64_t cap, int64_t* h_len) {
-  PCC_REQUIRE(ctx && d_keys && h_out && h_len && n >= 1 && n < ((int64_t)1 << 27) && depth >= 1 && depth <= 16, PCC_E_ARG,
-              "pcc_octree2_encode: bad argument");
+static inline int64_t o2_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+// the last error, prefixed with the frame it belongs to
+static int o2_frame_error(int rc, const char* who, int frame) {
+  const std::string m = pcc_last_error();
+  pcc_set_error("%s: frame %d: %s", who, frame, m.c_str());
+  return rc;
+}
+
+struct O2In {   // one frame of an encode call: leaves d_keys[lo, lo + n) (n >= 1), its root cube
+  int64_t lo, n;
+  int depth;
+  int32_t origin[3];
+};
+
+// blobs of version 2 of the frames fr[0 .. nf): the levels of all frames (launches independent of nf), ONE
+// synchronisation for all level counts (they size the chunks), the coder's three launches over all frames' chunks,
+// ONE synchronisation for all blob lengths.  Blob f is left in the pinned staging at (*offs)[f], (*lens)[f] bytes.
+static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, const O2In* fr, int nf,
+                           std::vector<int64_t>* offs, std::vector<int64_t>* lens) {
   hipStream_t st = ctx->stream;
-  const size_t cap_occ = pcc_align((size_t)n) * (size_t)depth;
-  PCC_REQUIRE(cap_occ < ((size_t)1 << 31), PCC_E_ARG, "pcc_octree2_encode: %lld leaves at depth %d", (long long)n, depth);
-  // The coder's scratch is sized by the node count, which is known after the first synchronisation, and a second
-  // reservation would drop what the first holds: the arena is reserved for the node counts of surfaces and sweeps
-  // (<= 2.5 nodes per leaf); a sparser set (up to `depth` nodes per leaf) takes a block of its own for this call.
-  const int64_t nodes_guess = std::min<int64_t>((int64_t)cap_occ, 5 * n / 2 + 64 * depth + 4096);
-  auto coder_bytes = [](int64_t nodes) -> size_t {
-    const O2Layout l = o2_layout(nodes);
-    const int64_t T = 8 * l.S;
-    return (size_t)l.nc * ((size_t)T * kLanes * 2 * 2 + 4 + 3 * kLanes * 2) + 3 * 256 + 4096;   // records, word regions, tables
-  };
-  PCC_TRY(pcc_arena_reserve(ctx, cap_occ + pcc_octree_wave_scratch(n) + coder_bytes(nodes_guess) + 16384));
-  uint8_t* occ = (uint8_t*)pcc_arena_alloc(ctx, cap_occ + 16);
-  uint32_t* counts = (uint32_t*)pcc_arena_alloc(ctx, 32 * 4);
-  uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, 2 * kCtx * 4);
-  uint16_t* p0 = (uint16_t*)pcc_arena_alloc(ctx, kCtx * 2);
-  if (!occ || !counts || !cnt || !p0) return PCC_E_NOMEM;
-  PccProfScope prof(ctx, "octree2_encode", n, depth, 0, 0);
-  if (n <= pcc_octree_small_max())
-    PCC_TRY(pcc_octree_small_async(ctx, d_keys, n, key_shift, depth, occ, (int64_t)cap_occ, counts));
-  else
-    PCC_TRY(pcc_octree_wave_async(ctx, d_keys, n, key_shift, depth, occ, (int64_t)cap_occ, counts));
-  uint32_t* hc = (uint32_t*)ctx->pinned;
-  PCC_HIP(hipMemcpyAsync(hc, counts, (size_t)(depth + 1) * 4, hipMemcpyDeviceToHost, st));
-  PCC_HIP(hipMemsetAsync(cnt, 0, 2 * kCtx * 4, st));
+  const int64_t small_max = pcc_octree_small_max();
+  // levels: the frames of the single-workgroup form first, then those of the wave form
+  std::vector<PccOctFrame> lt((size_t)nf);
+  std::vector<int64_t> cap_of((size_t)nf);
+  int ns = 0, nl = 0;
+  for (int f = 0; f < nf; ++f) ns += fr[f].n <= small_max ? 1 : 0;
+  int64_t occ_bytes = 0, waves = 0, leaves = 0;
+  size_t coder_b = 3 * 256 + 4096;
+  for (int f = 0, is = 0, il = 0; f < nf; ++f) {
+    const O2In& g = fr[f];
+    PCC_REQUIRE(g.n >= 1 && g.depth >= 1 && g.depth <= 16 && key_shift + 3 * g.depth <= 48, PCC_E_ARG,
+                "octree blob v2: frame %d: %lld leaves at depth %d", f, (long long)g.n, g.depth);
+    cap_of[(size_t)f] = o2_round(g.n * g.depth, 16);
+    PccOctFrame& r = lt[(size_t)(g.n <= small_max ? is++ : ns + il++)];
+    r.key_lo = g.lo;
+    r.n = g.n;
+    r.occ_off = occ_bytes;
+    r.cap = cap_of[(size_t)f];
+    r.wave0 = g.n <= small_max ? -1 : waves;
+    r.mask = pcc_octree_leaf_mask(g.depth);
+    r.depth = g.depth;
+    r.slot = f;
+    if (g.n > small_max) waves += (g.n + 63) / 64;
+    occ_bytes += cap_of[(size_t)f];
+    leaves += g.n;
+    // the coder's scratch is sized by the node counts, known after the first synchronisation, and a second reservation
+    // would drop what the first holds: the arena is reserved for the node counts of surfaces and sweeps (<= 2.5 nodes
+    // per leaf); a sparser batch (up to `depth` nodes per leaf) takes a block of its own for this call
+    const int64_t guess = std::min<int64_t>(cap_of[(size_t)f], 5 * g.n / 2 + 64 * g.depth + 4096);
+    const O2Layout l = o2_layout(guess);
+    coder_b += (size_t)l.nc * (8 * l.S * kLanes * 2 * 2 + 4 + 3 * kLanes * 2);   // records, word regions, tables
+  }
+  nl = nf - ns;
+  PCC_REQUIRE(leaves < ((int64_t)1 << 27) && occ_bytes < ((int64_t)1 << 32), PCC_E_ARG, "octree blob v2: %lld leaves in %d frames",
+              (long long)leaves, nf);
+  const size_t lt_b = pcc_align((size_t)nf * sizeof(PccOctFrame)), ct_b = pcc_align((size_t)nf * sizeof(O2Frame));
+  const size_t counts_b = pcc_align((size_t)nf * PCC_OCT_CSTRIDE * 4);
+  PCC_TRY(pcc_arena_reserve(ctx, (size_t)occ_bytes + 16 + counts_b + pcc_align((size_t)nf * 2 * kCtx * 4) + pcc_align((size_t)nf * kCtx * 2) +
+                                     lt_b + ct_b + pcc_octree_frames_scratch(waves, nl) + coder_b + 16384));
+  uint8_t* occ = (uint8_t*)pcc_arena_alloc(ctx, (size_t)occ_bytes + 16);
+  uint32_t* counts = (uint32_t*)pcc_arena_alloc(ctx, counts_b);
+  uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nf * 2 * kCtx * 4);
+  uint16_t* p0 = (uint16_t*)pcc_arena_alloc(ctx, (size_t)nf * kCtx * 2);
+  PccOctFrame* d_lt = (PccOctFrame*)pcc_arena_alloc(ctx, lt_b);
+  O2Frame* d_ct = (O2Frame*)pcc_arena_alloc(ctx, ct_b);
+  if (!occ || !counts || !cnt || !p0 || !d_lt || !d_ct) return PCC_E_NOMEM;
+  PccProfScope prof(ctx, "octree2_encode", leaves, fr[0].depth, nf > 1 ? nf : 0, 0);
+  PCC_TRY(o2_stage_reserve(ctx, lt_b + counts_b));
+  memcpy(ctx->stage, lt.data(), (size_t)nf * sizeof(PccOctFrame));
+  PCC_HIP(hipMemcpyAsync(d_lt, ctx->stage, (size_t)nf * sizeof(PccOctFrame), hipMemcpyHostToDevice, st));
+  PCC_TRY(pcc_octree_frames_async(ctx, d_keys, key_shift, lt.data(), d_lt, ns, nl, occ, counts));
+  uint32_t* hc = (uint32_t*)((char*)ctx->stage + lt_b);
+  PCC_HIP(hipMemcpyAsync(hc, counts, (size_t)nf * PCC_OCT_CSTRIDE * 4, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipMemsetAsync(cnt, 0, (size_t)nf * 2 * kCtx * 4, st));
   PCC_HIP(hipStreamSynchronize(st));
-  int64_t n_nodes = 0;
-  for (int L = 0; L < depth; ++L) n_nodes += (int64_t)hc[L];
-  PCC_REQUIRE(hc[0] == 1, PCC_E_ARG, "pcc_octree2_encode: keys exceed 3*depth bits (root level has %u nodes)", hc[0]);
-  PCC_REQUIRE(n_nodes <= (int64_t)cap_occ, PCC_E_NOMEM, "pcc_octree2_encode: %lld nodes for %lld leaves", (long long)n_nodes, (long long)n);
-  const int64_t start_last = n_nodes - (int64_t)hc[depth - 1];
-  const int64_t start_prev = depth >= 2 ? start_last - (int64_t)hc[depth - 2] : 0;
-  const O2Layout lay = o2_layout(n_nodes);
-  const int64_t T = 8 * lay.S, cap_words = 3 * kLanes + kLanes * T;   // bound of a chunk in the blob
+  // the coder's table from the level counts
+  std::vector<O2Frame> ct((size_t)nf);
+  int64_t rec_words = 0, out_bytes = 0, chunks = 0, stats_blocks = 0;
+  for (int f = 0; f < nf; ++f) {
+    const uint32_t* c = hc + (size_t)PCC_OCT_CSTRIDE * f;
+    const int depth = fr[f].depth;
+    int64_t n_nodes = 0;
+    for (int L = 0; L < depth; ++L) n_nodes += (int64_t)c[L];
+    PCC_REQUIRE(c[0] == 1, PCC_E_ARG, "pcc_octree2_encode: keys exceed 3*depth bits (root level has %u nodes)", c[0]);
+    PCC_REQUIRE(n_nodes <= cap_of[(size_t)f], PCC_E_NOMEM, "pcc_octree2_encode: %lld nodes for %lld leaves", (long long)n_nodes,
+                (long long)fr[f].n);
+    const O2Layout lay = o2_layout(n_nodes);
+    const int64_t T = 8 * lay.S, cap_words = 3 * kLanes + kLanes * T;   // bound of a chunk in the blob
+    const int64_t head = kHeader + 4 * depth + 8 + 2 * kCtx + 4 * lay.nc;
+    O2Frame& r = ct[(size_t)f];
+    r.occ_off = 0;   // below, from the levels' table
+    r.n_nodes = n_nodes;
+    r.start_last = n_nodes - (int64_t)c[depth - 1];
+    r.start_prev = depth >= 2 ? r.start_last - (int64_t)c[depth - 2] : 0;
+    r.rec_off = rec_words;
+    r.out_off = out_bytes;
+    // a step emits at most one word, and only for a coded decision (<= 8 per node): a frame of few nodes gets a bound
+    // in proportion to them, not to its chunk's 64 x T steps
+    r.out_cap = head + 2 * std::min<int64_t>(lay.nc * cap_words, 3 * kLanes * lay.nc + 8 * n_nodes);
+    r.S = (int32_t)lay.S;
+    r.nc = (int32_t)lay.nc;
+    r.cb = (int32_t)chunks;
+    r.sb = (int32_t)stats_blocks;
+    r.sn = (int32_t)std::min<unsigned>(nblk(n_nodes, 256), 256u);
+    r.depth = depth;
+    r.n_points = (uint32_t)fr[f].n;
+    for (int a = 0; a < 3; ++a) r.origin[a] = fr[f].origin[a];
+    rec_words += lay.nc * T * kLanes;
+    out_bytes += o2_round(r.out_cap, 16);
+    chunks += lay.nc;
+    stats_blocks += r.sn;
+  }
+  for (const PccOctFrame& r : lt) ct[(size_t)r.slot].occ_off = r.occ_off;
   struct Own {   // the rare block of its own, freed on every way out
     void* p = nullptr;
     ~Own() { if (p) (void)hipFree(p); }
   } own;
-  const size_t rec_b = pcc_align((size_t)lay.nc * T * kLanes * 2), work_b = rec_b;   // [chunk][step][lane] / [chunk][lane][T]
-  const size_t small_b = pcc_align((size_t)lay.nc * (4 + 2 * kLanes * 2 + kLanes * 2));   // words | states | lens
+  const size_t rec_b = pcc_align((size_t)rec_words * 2), work_b = rec_b;   // [chunk][step][lane] / [chunk][lane][T]
+  const size_t small_b = pcc_align((size_t)chunks * (4 + 2 * kLanes * 2 + kLanes * 2));   // words | states | lens
   uint16_t *rec, *work;
   char* small;
   if (pcc_align(ctx->arena_off) + rec_b + work_b + small_b + 1024 <= ctx->arena_cap) {
@@ -598,35 +783,55 @@ int pcc_octree2_encode(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int key_
   }
   if (!rec || !work || !small) return PCC_E_NOMEM;
   uint32_t* words = (uint32_t*)small;
-  uint16_t* states = (uint16_t*)(small + (size_t)lay.nc * 4);
-  uint16_t* lens = states + (size_t)lay.nc * 2 * kLanes;
-  const int64_t head = kHeader + 4 * depth + 8 + 2 * kCtx + 4 * lay.nc;
-  const int64_t bound = head + 2 * lay.nc * cap_words;
-  const int64_t cap_blob = std::min<int64_t>(bound, std::max<int64_t>(cap, head));
-  PCC_TRY(o2_stage_reserve(ctx, (size_t)cap_blob + 64));
+  uint16_t* states = (uint16_t*)(small + (size_t)chunks * 4);
+  uint16_t* lens_d = states + (size_t)chunks * 2 * kLanes;
+  // staging: the coder's table on its way to the device | the blobs | their lengths
+  const size_t lens_at = ct_b + (size_t)out_bytes;
+  PCC_TRY(o2_stage_reserve(ctx, lens_at + (size_t)nf * 8 + 64));
   uint8_t* stage = (uint8_t*)ctx->stage;
-  long long* len_dev = (long long*)ctx->pinned + 64;   // bytes 512 .. of the 4-KB pinned block (device-visible)
-  hipLaunchKernelGGL(k_o2_stats, dim3(std::min<unsigned>(nblk(n_nodes, 256), 256u)), dim3(256), 0, st, (const uint8_t*)occ, n_nodes,
-                     start_last, start_prev, cnt);
+  memcpy(stage, ct.data(), (size_t)nf * sizeof(O2Frame));
+  PCC_HIP(hipMemcpyAsync(d_ct, stage, (size_t)nf * sizeof(O2Frame), hipMemcpyHostToDevice, st));
+  long long* len_dev = (long long*)(stage + lens_at);
+  hipLaunchKernelGGL(k_o2_stats, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nf, cnt);
   PCC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_o2_enc, dim3((unsigned)lay.nc), dim3(64), 0, st, (const uint32_t*)occ, n_nodes, start_last, start_prev,
-                     (int)lay.S, (const uint32_t*)cnt, rec, work, states, lens, words, p0);
+  hipLaunchKernelGGL(k_o2_enc, dim3((unsigned)chunks), dim3(64), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nf,
+                     (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
   PCC_CHECK_LAUNCH();
-  O2Head h;
-  h.depth = depth;
-  h.n_points = (uint32_t)n;
-  for (int a = 0; a < 3; ++a) h.origin[a] = origin[a];
-  h.S = (uint32_t)lay.S;
-  h.nc = (uint32_t)lay.nc;
-  hipLaunchKernelGGL(k_o2_pack, dim3((unsigned)lay.nc + 1), dim3(256), 0, st, (const uint16_t*)work, T, (const uint16_t*)states,
-                     (const uint16_t*)lens, (const uint32_t*)words, (const uint32_t*)counts, (const uint16_t*)p0, h, stage,
-                     cap_blob, len_dev);
+  hipLaunchKernelGGL(k_o2_pack, dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work, (const O2Frame*)d_ct, nf,
+                     (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words, (const uint32_t*)counts,
+                     (const uint16_t*)p0, stage + ct_b, len_dev);
   PCC_CHECK_LAUNCH();
   PCC_HIP(hipStreamSynchronize(st));
-  const long long total = *(volatile long long*)len_dev;
-  PCC_REQUIRE(total >= 0 && total <= cap, PCC_E_NOMEM, "pcc_octree2_encode: blob does not fit %lld bytes", (long long)cap);
-  memcpy(h_out, stage, (size_t)total);
-  *h_len = total;
+  offs->resize((size_t)nf);
+  lens->resize((size_t)nf);
+  for (int f = 0; f < nf; ++f) {
+    const long long total = ((volatile long long*)len_dev)[f];
+    PCC_REQUIRE(total >= 0 && total <= ct[(size_t)f].out_cap, PCC_E_NOMEM, "octree blob v2: frame %d: blob beyond its bound", f);
+    (*offs)[(size_t)f] = (int64_t)ct_b + ct[(size_t)f].out_off;
+    (*lens)[(size_t)f] = total;
+  }
+  return PCC_OK;
+}
+
+// blob version 2 of the rows d_keys[0 .. n) (Morton-sorted, one frame): the batch of one frame — two synchronisations
+// (the level counts size the chunks; the blob's length), the blob itself is written into pinned memory by the packing
+// kernel
+int pcc_octree2_encode(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int key_shift, int depth, const int32_t origin[3],
+                       uint8_t* h_out, int64_t cap, int64_t* h_len) {
+  PCC_REQUIRE(ctx && d_keys && h_out && h_len && n >= 1 && n < ((int64_t)1 << 27) && depth >= 1 && depth <= 16, PCC_E_ARG,
+              "pcc_octree2_encode: bad argument");
+  PCC_REQUIRE(pcc_align((size_t)n) * (size_t)depth < ((size_t)1 << 31), PCC_E_ARG, "pcc_octree2_encode: %lld leaves at depth %d",
+              (long long)n, depth);
+  O2In one;
+  one.lo = 0;
+  one.n = n;
+  one.depth = depth;
+  for (int a = 0; a < 3; ++a) one.origin[a] = origin[a];
+  std::vector<int64_t> offs, lens;
+  PCC_TRY(o2_encode_batch(ctx, d_keys, key_shift, &one, 1, &offs, &lens));
+  PCC_REQUIRE(lens[0] <= cap, PCC_E_NOMEM, "pcc_octree2_encode: blob does not fit %lld bytes", (long long)cap);
+  memcpy(h_out, (uint8_t*)ctx->stage + offs[0], (size_t)lens[0]);
+  *h_len = lens[0];
   return PCC_OK;
 }
 
@@ -664,7 +869,9 @@ static int o2_parse(const uint8_t* h_in, int64_t len, O2Info* o) {
   o->S = (int64_t)get_u32(q);
   o->nc = (int64_t)get_u32(q + 4);
   q += 8;
-  PCC_REQUIRE(o->S >= 4 && o->S % 4 == 0 && o->S <= 4096 && o->nc >= 1 && kLanes * o->S * o->nc >= o->n_nodes &&
+  // S <= kSMax, as the encoder writes it: a chunk then codes at most 32768 nodes, so the announced node count is bound
+  // by the chunk table's length (every chunk has at least 384 bytes of states and lengths)
+  PCC_REQUIRE(o->S >= 4 && o->S % 4 == 0 && o->S <= kSMax && o->nc >= 1 && kLanes * o->S * o->nc >= o->n_nodes &&
                   kLanes * o->S * (o->nc - 1) < o->n_nodes,
               PCC_E_STREAM, "octree blob v2: %lld nodes in %lld chunks of 64 x %lld", (long long)o->n_nodes, (long long)o->nc,
               (long long)o->S);
@@ -688,79 +895,243 @@ static int o2_parse(const uint8_t* h_in, int64_t len, O2Info* o) {
   return PCC_OK;
 }
 
-// version-2 blob -> Morton-ordered points int32 [n, 3] (origin added): on the device (d_points) and / or on the host
-// (h_points).  h_level_n (16 entries, nullable) receives the node counts of the levels.  One synchronisation.
+// version-2 blobs -> their points, Morton order inside a frame (origin added), concatenated in frame order: on the device
+// (d_points) and / or on the host (h_points).  h_point_offsets[nb + 1] receives where every frame's points start;
+// h_level_n (16 entries, nullable, nb == 1) the node counts of the levels.  Every header is checked, and the sizes the
+// batch announces are summed and checked, before anything is reserved.  `who` names the frame in errors (nullptr: the
+// one-blob messages).  One synchronisation.
+static int o2_decode_batch(pcc_ctx* ctx, const uint8_t* const* blobs, const int64_t* lens, int nb, const char* who,
+                           int32_t* d_points, int32_t* h_points, int64_t cap_points, int64_t* h_point_offsets,
+                           int64_t* h_level_n) {
+  std::vector<O2Info> info((size_t)nb);
+  int64_t points = 0, nodes = 0, links = 0, bodies = 0;
+  h_point_offsets[0] = 0;
+  for (int f = 0; f < nb; ++f) {
+    O2Info& o = info[(size_t)f];
+    if (who) {
+      const int v = pcc_octree_blob_version(blobs[f], lens[f]);
+      if (v < 0) return o2_frame_error(v, who, f);
+      PCC_REQUIRE(v == 2, PCC_E_ARG, "%s: frame %d: blob version %d (this call reads version 2)", who, f, v);
+      const int rc = o2_parse(blobs[f], lens[f], &o);
+      if (rc != PCC_OK) return o2_frame_error(rc, who, f);
+    } else {
+      PCC_TRY(o2_parse(blobs[f], lens[f], &o));
+    }
+    points += o.n;
+    h_point_offsets[f + 1] = points;
+    if (o.n == 0) continue;
+    nodes += o2_round(o.n_nodes, 4);
+    links += o.n_nodes + o.n;
+    bodies += o2_round(lens[f] - o.off_p0, 16);
+  }
+  if (h_level_n) {
+    for (int L = 0; L < 16; ++L) h_level_n[L] = 0;
+    if (info[0].n)
+      for (int L = 0; L < info[0].depth; ++L) h_level_n[L] = info[0].level_n[L];
+  }
+  PCC_REQUIRE(nodes < ((int64_t)1 << 28) && points < ((int64_t)1 << 31) && links < ((int64_t)1 << 32), PCC_E_ARG,
+              "%s: the blobs announce %lld nodes and %lld points in all", who ? who : "pcc_octree2_decode", (long long)nodes,
+              (long long)points);
+  if (points == 0 || (!d_points && !h_points)) return PCC_OK;
+  PCC_REQUIRE(cap_points >= points, PCC_E_NOMEM, "%s: %lld points, capacity %lld", who ? who : "pcc_octree2_decode",
+              (long long)points, (long long)cap_points);
+  // the table: frames with points only
+  std::vector<O2DFrame> tab;
+  int64_t node_base = 0, link_base = 0, body_off = 0, chunks = 0, lblocks = 0, qblocks = 0;
+  for (int f = 0; f < nb; ++f) {
+    const O2Info& o = info[(size_t)f];
+    if (o.n == 0) continue;
+    O2DFrame r;
+    r.body_off = body_off;
+    r.table_off = o.off_table - o.off_p0;
+    r.payload_off = o.off_payload - o.off_p0;
+    r.n_nodes = o.n_nodes;
+    r.start_last = o.n_nodes - o.level_n[o.depth - 1];
+    r.start_prev = o.depth >= 2 ? r.start_last - o.level_n[o.depth - 2] : 0;
+    r.n_points = o.n;
+    r.node_base = node_base;
+    r.link_base = link_base;
+    r.pt_base = h_point_offsets[f];
+    int64_t run = 0;
+    for (int L = 0; L <= 16; ++L) {
+      r.off[L] = run;
+      if (L < o.depth) run += o.level_n[L];
+    }
+    r.S = (int32_t)o.S;
+    r.nc = (int32_t)o.nc;
+    r.cb = (int32_t)chunks;
+    r.lb = (int32_t)lblocks;
+    r.qb = (int32_t)qblocks;
+    r.depth = o.depth;
+    for (int a = 0; a < 3; ++a) r.origin[a] = o.origin[a];
+    tab.push_back(r);
+    node_base += o2_round(o.n_nodes, 4);
+    link_base += o.n_nodes + o.n;
+    body_off += o2_round(lens[f] - o.off_p0, 16);
+    chunks += o.nc;
+    lblocks += nblk(o.n_nodes, 256);
+    qblocks += nblk(o.n, 256);
+  }
+  const int nf = (int)tab.size();
+  hipStream_t st = ctx->stream;
+  const size_t tab_b = pcc_align((size_t)nf * sizeof(O2DFrame));
+  PCC_TRY(pcc_arena_reserve(ctx, tab_b + pcc_align((size_t)bodies + 16) + pcc_align((size_t)nodes + 16) + 2 * pcc_align((size_t)nodes * 4) +
+                                     pcc_align((size_t)links * 4) + (d_points ? 0 : pcc_align((size_t)points * 12)) +
+                                     pcc_align((size_t)nf * 4 + 64) + pcc_scan_scratch_bytes(nodes) + 8192));
+  // the table and the bodies (p0 | chunk table | payload: 4-byte aligned inside a blob, header 24 + 4 depth + 8) cross in
+  // one copy
+  uint8_t* d_in = (uint8_t*)pcc_arena_alloc(ctx, tab_b + (size_t)bodies + 16);
+  uint8_t* occ = (uint8_t*)pcc_arena_alloc(ctx, (size_t)nodes + 16);
+  uint32_t* pc = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nodes * 4);
+  uint32_t* excl = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nodes * 4);
+  uint32_t* link = (uint32_t*)pcc_arena_alloc(ctx, (size_t)links * 4);
+  int32_t* pts = d_points ? d_points : (int32_t*)pcc_arena_alloc(ctx, (size_t)points * 12);
+  int32_t* status = (int32_t*)pcc_arena_alloc(ctx, (size_t)nf * 4 + 64);   // per frame | total of the scan
+  if (!d_in || !occ || !pc || !excl || !link || !pts || !status) return PCC_E_NOMEM;
+  uint32_t* total = (uint32_t*)(status + nf);
+  const O2DFrame* d_tab = (const O2DFrame*)d_in;
+  const uint8_t* d_bodies = d_in + tab_b;
+  PccProfScope prof(ctx, "octree2_decode", points, info[0].depth, nodes, chunks);
+  const size_t in_b = tab_b + (size_t)bodies;
+  // a caller's array in pinned host memory receives the points straight from the device; any other one through the
+  // staging (a failed query of an ordinary pointer leaves its error behind: cleared here)
+  bool direct = false;
+  if (h_points) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, h_points) == hipSuccess)
+      direct = attr.type == hipMemoryTypeHost;
+    else
+      (void)hipGetLastError();
+  }
+  const size_t out_bytes = h_points && !direct ? (size_t)points * 12 : 0;
+  PCC_TRY(o2_stage_reserve(ctx, pcc_align(in_b) + pcc_align(out_bytes) + (size_t)nf * 4 + 64));
+  uint8_t* stage = (uint8_t*)ctx->stage;
+  memcpy(stage, tab.data(), (size_t)nf * sizeof(O2DFrame));
+  for (int f = 0, k = 0; f < nb; ++f) {
+    const O2Info& o = info[(size_t)f];
+    if (o.n == 0) continue;
+    memcpy(stage + tab_b + tab[(size_t)k].body_off, blobs[f] + o.off_p0, (size_t)(lens[f] - o.off_p0));
+    ++k;
+  }
+  PCC_HIP(hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
+  PCC_HIP(hipMemsetAsync(status, 0, (size_t)nf * 4 + 64, st));
+  PCC_HIP(hipMemsetAsync(link, 0, (size_t)links * 4, st));
+  hipLaunchKernelGGL(k_o2_dec, dim3((unsigned)chunks), dim3(64), 0, st, d_bodies, d_tab, nf, occ, status);
+  PCC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_o2_popc, dim3(nblk(nodes, 256)), dim3(256), 0, st, (const uint8_t*)occ, nodes, pc);
+  PCC_CHECK_LAUNCH();
+  PCC_TRY(pcc_scan_exclusive_u32(ctx, pc, excl, nodes, total));
+  hipLaunchKernelGGL(k_o2_link, dim3((unsigned)lblocks), dim3(256), 0, st, (const uint8_t*)occ, (const uint32_t*)excl,
+                     (const uint32_t*)total, nodes, d_tab, nf, link, status);
+  PCC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_o2_points, dim3((unsigned)qblocks), dim3(256), 0, st, (const uint32_t*)link, d_tab, nf, pts, status);
+  PCC_CHECK_LAUNCH();
+  uint8_t* stage_out = stage + pcc_align(in_b);
+  int32_t* h_status = (int32_t*)(stage_out + pcc_align(out_bytes));
+  if (h_points) PCC_HIP(hipMemcpyAsync(direct ? (void*)h_points : (void*)stage_out, pts, (size_t)points * 12, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipMemcpyAsync(h_status, status, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipStreamSynchronize(st));
+  for (int f = 0, k = 0; f < nb; ++f) {
+    if (info[(size_t)f].n == 0) continue;
+    const int32_t bad = h_status[k++];
+    if (!who)
+      PCC_REQUIRE(bad == 0, PCC_E_STREAM, "octree blob v2: corrupt stream (status %d: 1 = words, 2 = empty node, 8 = counts)", bad);
+    else
+      PCC_REQUIRE(bad == 0, PCC_E_STREAM, "%s: frame %d: octree blob v2: corrupt stream (status %d: 1 = words, 2 = empty node, 8 = counts)",
+                  who, f, bad);
+  }
+  if (h_points && !direct) memcpy(h_points, stage_out, out_bytes);
+  return PCC_OK;
+}
+
+// version-2 blob -> Morton-ordered points int32 [n, 3] (origin added): the batch of one blob
 int pcc_octree2_decode(pcc_ctx* ctx, const uint8_t* h_in, int64_t len, int32_t* d_points, int32_t* h_points, int64_t cap_points,
                        int64_t* h_n_points, int64_t* h_level_n) {
   PCC_REQUIRE(ctx, PCC_E_ARG, "pcc_octree2_decode: null ctx");
-  O2Info o;
-  PCC_TRY(o2_parse(h_in, len, &o));
-  if (h_n_points) *h_n_points = o.n;
-  if (h_level_n) {
-    for (int L = 0; L < 16; ++L) h_level_n[L] = 0;
-    if (o.n)
-      for (int L = 0; L < o.depth; ++L) h_level_n[L] = o.level_n[L];
-  }
-  if (o.n == 0 || (!d_points && !h_points)) return PCC_OK;
-  PCC_REQUIRE(cap_points >= o.n, PCC_E_NOMEM, "pcc_octree2_decode: %lld points, capacity %lld", (long long)o.n, (long long)cap_points);
+  int64_t offs[2] = {0, 0};
+  const int rc = o2_decode_batch(ctx, &h_in, &len, 1, nullptr, d_points, h_points, cap_points, offs, h_level_n);
+  if (h_n_points && (rc == PCC_OK || offs[1] > 0)) *h_n_points = offs[1];
+  return rc;
+}
+
+// ---- C-ABI: many frames per call (include/pcc.h) ----------------------------------------------------------------------
+extern "C" int pcc_octree_encode_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int key_shift,
+                                        uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
+  PCC_REQUIRE(ctx && h_out && h_offsets && n >= 0 && (n == 0 || d_keys) && n < ((int64_t)1 << 27) && n_frames >= 1 &&
+                  n_frames <= 65535 && key_shift >= 0 && key_shift % 3 == 0 && key_shift <= 45 && cap >= 0,
+              PCC_E_ARG, "pcc_octree_encode_frames: bad argument (n=%lld n_frames=%d key_shift=%d)", (long long)n, n_frames,
+              key_shift);
   hipStream_t st = ctx->stream;
-  const int64_t n_all = o.n_nodes + o.n;
-  const int64_t body = len - o.off_p0;   // p0 | table | payload: 4-byte aligned inside the blob (header 24 + 4 depth + 8)
-  const size_t occ_bytes = (size_t)(kLanes * o.S * o.nc) + 16;
-  PCC_TRY(pcc_arena_reserve(ctx, pcc_align((size_t)body + 16) + pcc_align(occ_bytes) + 2 * pcc_align((size_t)o.n_nodes * 4) +
-                                     pcc_align((size_t)n_all * 4) + pcc_align((size_t)o.n * 12) +
-                                     pcc_scan_scratch_bytes(o.n_nodes) + 8192));
-  uint8_t* d_body = (uint8_t*)pcc_arena_alloc(ctx, (size_t)body + 16);
-  uint8_t* occ = (uint8_t*)pcc_arena_alloc(ctx, occ_bytes);
-  uint32_t* pc = (uint32_t*)pcc_arena_alloc(ctx, (size_t)o.n_nodes * 4);
-  uint32_t* excl = (uint32_t*)pcc_arena_alloc(ctx, (size_t)o.n_nodes * 4);
-  uint32_t* link = (uint32_t*)pcc_arena_alloc(ctx, (size_t)n_all * 4);
-  int32_t* pts = d_points ? d_points : (int32_t*)pcc_arena_alloc(ctx, (size_t)o.n * 12);
-  uint32_t* small = (uint32_t*)pcc_arena_alloc(ctx, 64);   // status | total
-  if (!d_body || !occ || !pc || !excl || !link || !pts || !small) return PCC_E_NOMEM;
-  PccProfScope prof(ctx, "octree2_decode", o.n, o.depth, o.n_nodes, o.nc);
-  const size_t out_bytes = h_points ? (size_t)o.n * 12 : 0;
-  PCC_TRY(o2_stage_reserve(ctx, pcc_align((size_t)body) + out_bytes + 64));
-  uint8_t* stage = (uint8_t*)ctx->stage;
-  memcpy(stage, h_in + o.off_p0, (size_t)body);
-  PCC_HIP(hipMemcpyAsync(d_body, stage, (size_t)body, hipMemcpyHostToDevice, st));
-  PCC_HIP(hipMemsetAsync(small, 0, 64, st));
-  PCC_HIP(hipMemsetAsync(link, 0, (size_t)n_all * 4, st));
-  int32_t* status = (int32_t*)small;
-  const int64_t start_last = o.n_nodes - o.level_n[o.depth - 1];
-  const int64_t start_prev = o.depth >= 2 ? start_last - o.level_n[o.depth - 2] : 0;
-  const uint16_t* d_p0 = (const uint16_t*)d_body;
-  const uint32_t* d_table = (const uint32_t*)(d_body + (o.off_table - o.off_p0));
-  const uint16_t* d_payload = (const uint16_t*)(d_body + (o.off_payload - o.off_p0));
-  hipLaunchKernelGGL(k_o2_dec, dim3((unsigned)o.nc), dim3(64), 0, st, d_p0, d_table, d_payload, o.n_nodes, start_last, start_prev,
-                     (int)o.S, (uint32_t*)occ, status);
-  PCC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_o2_popc, dim3(nblk(o.n_nodes, 256)), dim3(256), 0, st, (const uint8_t*)occ, o.n_nodes, pc);
-  PCC_CHECK_LAUNCH();
-  PCC_TRY(pcc_scan_exclusive_u32(ctx, pc, excl, o.n_nodes, small + 1));
-  O2Offs offs;
-  int64_t run = 0;
-  for (int L = 0; L < o.depth; ++L) {
-    offs.off[L] = run;
-    run += o.level_n[L];
+  std::vector<int64_t> offs((size_t)n_frames + 1, 0);
+  std::vector<uint64_t> ends((size_t)2 * n_frames, 0);
+  if (n > 0) {   // frame boundaries, every frame's end keys and the checks of the keys: one synchronisation
+    const size_t offs_b = (size_t)(n_frames + 1) * 8, ends_b = (size_t)n_frames * 16, rd_b = offs_b + ends_b + 8;
+    PCC_TRY(pcc_arena_reserve(ctx, rd_b + 256));
+    uint8_t* rd = (uint8_t*)pcc_arena_alloc(ctx, rd_b);
+    if (!rd) return PCC_E_NOMEM;
+    int64_t* d_offs = (int64_t*)rd;
+    uint64_t* d_ends = (uint64_t*)(rd + offs_b);
+    int32_t* d_flag = (int32_t*)(rd + offs_b + ends_b);
+    PCC_TRY(o2_stage_reserve(ctx, rd_b));
+    PCC_HIP(hipMemsetAsync(rd, 0, rd_b, st));
+    hipLaunchKernelGGL(k_of_check, dim3(nblk(n, 256)), dim3(256), 0, st, d_keys, n, key_shift, n_frames, d_flag);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_of_frames, dim3(nblk(n_frames + 1, 64)), dim3(64), 0, st, d_keys, n, n_frames, d_offs, d_ends);
+    PCC_CHECK_LAUNCH();
+    PCC_HIP(hipMemcpyAsync(ctx->stage, rd, rd_b, hipMemcpyDeviceToHost, st));
+    PCC_HIP(hipStreamSynchronize(st));
+    const uint8_t* h = (const uint8_t*)ctx->stage;
+    int32_t flag;
+    memcpy(&flag, h + offs_b + ends_b, 4);
+    PCC_REQUIRE(!(flag & 4), PCC_E_ARG, "pcc_octree_encode_frames: a key's frame index is not below n_frames=%d", n_frames);
+    PCC_REQUIRE(!(flag & 2), PCC_E_ARG, "pcc_octree_encode_frames: keys not sorted (pcc_sort_pairs)");
+    PCC_REQUIRE(!(flag & 1), PCC_E_DUP, "pcc_octree_encode_frames: duplicate keys (after the key shift of %d)", key_shift);
+    memcpy(offs.data(), h, offs_b);
+    memcpy(ends.data(), h + offs_b, ends_b);
   }
-  offs.off[o.depth] = run;
-  offs.off[o.depth + 1] = n_all;
-  hipLaunchKernelGGL(k_o2_link, dim3(nblk(o.n_nodes, 256)), dim3(256), 0, st, (const uint8_t*)occ, (const uint32_t*)excl,
-                     (const uint32_t*)(small + 1), o.n_nodes, n_all, offs, o.depth, link, status);
-  PCC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_o2_points, dim3(nblk(o.n, 256)), dim3(256), 0, st, (const uint32_t*)link, o.n_nodes, o.n, o.depth,
-                     o.origin[0], o.origin[1], o.origin[2], pts, status);
-  PCC_CHECK_LAUNCH();
-  uint8_t* stage_out = stage + pcc_align((size_t)body);
-  if (h_points) PCC_HIP(hipMemcpyAsync(stage_out, pts, out_bytes, hipMemcpyDeviceToHost, st));
-  int32_t* h_status = (int32_t*)ctx->pinned;
-  PCC_HIP(hipMemcpyAsync(h_status, status, 4, hipMemcpyDeviceToHost, st));
-  PCC_HIP(hipStreamSynchronize(st));
-  PCC_REQUIRE(*h_status == 0, PCC_E_STREAM, "octree blob v2: corrupt stream (status %d: 1 = words, 2 = empty node, 8 = counts)",
-              *h_status);
-  if (h_points) memcpy(h_points, stage_out, out_bytes);
+  std::vector<O2In> fr;
+  std::vector<int> frame_of;
+  for (int f = 0; f < n_frames; ++f) {
+    const int64_t lo = offs[(size_t)f], hi = offs[(size_t)f + 1];
+    if (hi <= lo) continue;
+    O2In g;
+    g.lo = lo;
+    g.n = hi - lo;
+    octree_root(ends[2 * (size_t)f], ends[2 * (size_t)f + 1], key_shift, &g.depth, g.origin);
+    fr.push_back(g);
+    frame_of.push_back(f);
+  }
+  std::vector<int64_t> boff, blen;
+  if (!fr.empty()) PCC_TRY(o2_encode_batch(ctx, d_keys, key_shift, fr.data(), (int)fr.size(), &boff, &blen));
+  // blob f = h_out[h_offsets[f], h_offsets[f + 1]); frames without keys get the 24-byte empty blob
+  std::vector<int64_t> len_of((size_t)n_frames, kHeader);
+  for (size_t k = 0; k < fr.size(); ++k) len_of[(size_t)frame_of[k]] = blen[k];
+  int64_t total = 0;
+  for (int f = 0; f < n_frames; ++f) total += len_of[(size_t)f];
+  PCC_REQUIRE(total <= cap, PCC_E_NOMEM, "pcc_octree_encode_frames: %lld bytes of blobs, capacity %lld", (long long)total,
+              (long long)cap);
+  h_offsets[0] = 0;
+  for (int f = 0, k = 0; f < n_frames; ++f) {
+    uint8_t* dst = h_out + h_offsets[f];
+    if (k < (int)fr.size() && frame_of[(size_t)k] == f) {
+      memcpy(dst, (const uint8_t*)ctx->stage + boff[(size_t)k], (size_t)blen[(size_t)k]);
+      ++k;
+    } else {
+      memset(dst, 0, kHeader);
+      dst[0] = 'O';
+      dst[1] = 2;
+    }
+    h_offsets[f + 1] = h_offsets[f] + len_of[(size_t)f];
+  }
   return PCC_OK;
+}
+
+extern "C" int pcc_octree_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
+                                        int32_t* d_points, int32_t* h_points, int64_t cap_points, int64_t* h_point_offsets) {
+  PCC_REQUIRE(ctx && h_blobs && h_lens && h_point_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
+              "pcc_octree_decode_frames: bad argument (n_frames=%d)", n_frames);
+  return o2_decode_batch(ctx, h_blobs, h_lens, n_frames, "pcc_octree_decode_frames", d_points, h_points, cap_points,
+                         h_point_offsets, nullptr);
 }
 
 // ---- C-ABI: the geometry slot, one call each (utils.gpcc_encode / gpcc_decode, shared/utils.py:169-240) -------------

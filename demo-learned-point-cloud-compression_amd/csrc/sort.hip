@@ -490,6 +490,41 @@ int pcc_morton_keys_batch(pcc_ctx* ctx, const int32_t* d_coords, int64_t n, int 
   return PCC_OK;
 }
 
+// keys of a sequence of frames straight from their rows as the caller has them: xyz [n, 3] of int16 (elem_bytes 2) or
+// int32 (4), frames concatenated, frame f = rows [offs[f], offs[f + 1]); the frame index is the batch index.  A thread
+// finds its frame by a search over the offsets (n_frames <= 65535: at most 16 steps, the same lines for a whole wave)
+template <typename T>
+__global__ void k_morton_keys_frames(const T* __restrict__ xyz, int64_t n, const int64_t* __restrict__ offs,
+                                     int n_frames, uint64_t* __restrict__ keys, int32_t* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int lo = 0, hi = n_frames - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (offs[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  const int x = (int)xyz[3 * i], y = (int)xyz[3 * i + 1], z = (int)xyz[3 * i + 2];
+  const bool bad = (x < -32768) | (x > 32767) | (y < -32768) | (y > 32767) | (z < -32768) | (z > 32767);
+  if (bad) atomicOr(flag, 1);
+  keys[i] = pcc_morton(lo, x, y, z);
+}
+
+extern "C" int pcc_morton_keys_frames(pcc_ctx* ctx, const void* d_xyz, int elem_bytes, int64_t n,
+                                      const int64_t* d_frame_offsets, int n_frames, uint64_t* d_keys, int32_t* d_flag) {
+  PCC_REQUIRE(ctx && (elem_bytes == 2 || elem_bytes == 4) && n_frames >= 1 && n_frames <= 65535 &&
+                  (n == 0 || (d_xyz && d_frame_offsets && d_keys && d_flag)),
+              PCC_E_ARG, "pcc_morton_keys_frames: bad argument (elem_bytes=%d n_frames=%d)", elem_bytes, n_frames);
+  if (n <= 0) return PCC_OK;
+  if (elem_bytes == 2)
+    hipLaunchKernelGGL(k_morton_keys_frames<int16_t>, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, (const int16_t*)d_xyz, n,
+                       d_frame_offsets, n_frames, d_keys, d_flag);
+  else
+    hipLaunchKernelGGL(k_morton_keys_frames<int32_t>, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, (const int32_t*)d_xyz, n,
+                       d_frame_offsets, n_frames, d_keys, d_flag);
+  PCC_CHECK_LAUNCH();
+  return PCC_OK;
+}
+
 extern "C" int pcc_keys_to_coords(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n,
                                   int32_t* d_coords) {
   PCC_REQUIRE(ctx && (n == 0 || (d_coords && d_keys)), PCC_E_ARG, "pcc_keys_to_coords: null arg");

@@ -550,6 +550,42 @@ class Runtime:
                   "pcc_octree_decode_ctx")
         return pts
 
+    def octree_encode_frames(self, keys, n_frames, key_shift=0):
+        """version-2 blobs of n_frames frames at once (pcc_octree_encode_frames): `keys` Morton-sorted and distinct, the
+        batch index of a key is its frame.  A list of n_frames bytes objects, blob f equal to octree_encode(frame f's
+        keys, key_shift, version=2); a frame without keys gives the 24-byte empty blob."""
+        n = keys.shape[0]
+        cap = 4096 * n_frames + 17 * max(n, 1)
+        out = np.empty(cap, dtype=np.uint8)
+        offs = (C.c_int64 * (n_frames + 1))()
+        check(self.lib.pcc_octree_encode_frames(self.ctx, _ptr(keys), n, n_frames, key_shift, _np_ptr(out), cap, offs),
+              "pcc_octree_encode_frames")
+        return [out[offs[f]:offs[f + 1]].tobytes() for f in range(n_frames)]
+
+    def octree_decode_frames(self, blobs, device=False):
+        """version-2 blobs -> one int32 [n_f, 3] array per blob, Morton order (pcc_octree_decode_frames): numpy arrays,
+        or views of one device tensor (device=True)"""
+        nb = len(blobs)
+        if nb == 0:
+            return []
+        bufs = [np.frombuffer(b, dtype=np.uint8) for b in blobs]
+        ptrs = (C.c_void_p * nb)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
+        lens = (C.c_int64 * nb)(*[b.shape[0] for b in bufs])
+        offs = (C.c_int64 * (nb + 1))()
+        check(self.lib.pcc_octree_decode_frames(self.ctx, ptrs, lens, nb, None, None, 0, offs), "pcc_octree_decode_frames")
+        total = offs[nb]
+        if device:
+            pts = self.empty((total, 3), torch.int32)
+            if total:
+                check(self.lib.pcc_octree_decode_frames(self.ctx, ptrs, lens, nb, _ptr(pts), None, total, offs),
+                      "pcc_octree_decode_frames")
+        else:   # pinned: the library copies the points straight into it (torch's host cache keeps the pages mapped)
+            pts = torch.empty((total, 3), dtype=torch.int32, pin_memory=True).numpy()
+            if total:
+                check(self.lib.pcc_octree_decode_frames(self.ctx, ptrs, lens, nb, None, _np_ptr(pts), total, offs),
+                      "pcc_octree_decode_frames")
+        return [pts[offs[f]:offs[f + 1]] for f in range(nb)]
+
 
 OCTREE_V2_MIN_LEAVES = 65536     # include/pcc.h PCC_OCTREE_V2_MIN_LEAVES
 OCTREE_V3_MIN_LEAVES = 8192      # include/pcc.h PCC_OCTREE_V3_MIN_LEAVES

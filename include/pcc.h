@@ -114,6 +114,14 @@ int pcc_count_nonneg(pcc_ctx* ctx, const int32_t* d_p, int64_t n,
  * out of range. */
 int pcc_morton_keys(pcc_ctx* ctx, const int32_t* d_coords, int64_t n,
                     uint64_t* d_keys, int32_t* d_flag);
+/* the same for a sequence of frames as their rows come: d_xyz = the frames'
+ * [n_f, 3] rows concatenated, int16 (elem_bytes 2) or int32 (4); frame f =
+ * rows d_frame_offsets[f] .. d_frame_offsets[f+1] (n_frames+1 entries in
+ * device memory, 1 <= n_frames <= 65535) gets batch index f.  *d_flag |= 1
+ * for a coordinate outside [-32768, 32767]. */
+int pcc_morton_keys_frames(pcc_ctx* ctx, const void* d_xyz, int elem_bytes,
+                           int64_t n, const int64_t* d_frame_offsets,
+                           int n_frames, uint64_t* d_keys, int32_t* d_flag);
 /* inverse: keys -> (b,x,y,z) */
 int pcc_keys_to_coords(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n,
                        int32_t* d_coords);
@@ -579,6 +587,44 @@ int pcc_octree_decode_ctx(pcc_ctx* ctx, const uint8_t* h_in, int64_t len,
 int pcc_octree_decode_dev(pcc_ctx* ctx, const uint8_t* h_in, int64_t len,
                           int32_t* d_points, int64_t cap_points,
                           int64_t* h_n_points, int64_t* h_level_n);
+
+/* Geometry-only coding of a SEQUENCE of point sets (LiDAR sweeps): B frames
+ * into B independent version-2 blobs in one call, and back.  Every blob is
+ * byte-identical to what the one-frame call writes for that frame alone, so
+ * _decode_ctx / _decode_dev read each of them.  The frames' chunks are coded
+ * side by side: the number of launches does not grow with B, nor the number of
+ * synchronisations (encode: 3 — end keys, level counts, blob lengths;
+ * decode: 1).
+ *   _encode_frames : d_keys = Morton keys of pcc_morton_keys with the frame
+ *     index as batch index (0 .. n_frames-1), sorted (pcc_sort_pairs) and
+ *     distinct after the key shift (PCC_E_DUP otherwise; unsorted keys or a
+ *     frame index >= n_frames: PCC_E_ARG).  Blob f is
+ *     h_out[h_offsets[f] .. h_offsets[f+1]) (h_offsets: n_frames+1 entries);
+ *     a frame without keys gives the 24-byte empty blob.  More bytes than
+ *     cap: PCC_E_NOMEM, nothing written.  Fewer than 2^27 leaves in all,
+ *     1 <= n_frames <= 65535.
+ *   _decode_frames : n_frames blobs of version 2 (another version: PCC_E_ARG
+ *     naming the frame) -> their points int32 [n,3], origin added, Morton
+ *     order inside a frame (as _decode_dev), concatenated in frame order;
+ *     frame f's points are rows h_point_offsets[f] .. h_point_offsets[f+1]
+ *     (n_frames+1 entries).  d_points (HBM) and / or h_points (host), both
+ *     NULL = sizes only; more points than cap_points: PCC_E_NOMEM.  Every
+ *     header is checked, and the sizes all of them announce summed, before
+ *     anything is reserved; a corrupt blob is PCC_E_STREAM naming its frame.
+ *     An h_points in pinned host memory (hipHostMalloc) receives the points
+ *     straight from the device; any other array through the ctx's staging.
+ * After an error the ctx stays usable.  Scratch per encoded frame is at least
+ * one chunk (64 lanes x S >= 4 nodes): about 8 KB of device scratch even for a
+ * one-point frame, so 65 535 tiny frames in one call take about 0.5 GB; a
+ * frame's blob is staged at a bound in proportion to its nodes
+ * (8 words per node + 384 B per chunk + header). */
+int pcc_octree_encode_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n,
+                             int n_frames, int key_shift, uint8_t* h_out,
+                             int64_t cap, int64_t* h_offsets);
+int pcc_octree_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs,
+                             const int64_t* h_lens, int n_frames,
+                             int32_t* d_points, int32_t* h_points,
+                             int64_t cap_points, int64_t* h_point_offsets);
 
 /* ---- whole-GOP entry points ------------------------------ */
 
