@@ -1,0 +1,677 @@
+// attr.hip — lossless per-point attributes (intensity, RGB: uint8 or uint16, 1..4 channels) beside the geometry blobs
+// of pcc_octree_encode_frames, coded by the lane-parallel adaptive binary rANS scheme of blob version 2 (lanerans.h).
+//
+// Attribute blob, version 1 (one per frame; little-endian):
+//
+//   'A' 1 bpv c | u32 n | u32 payload_len | u32 S | u32 n_chunks | u16 p0[nctx] | u32 words[n_chunks] | chunk payloads
+//   (n == 0: the 12 bytes up to payload_len = 0, nothing more)
+//   bpv             bytes per value, 1 (uint8) or 2 (uint16); c channels, 1 .. 4
+//   chunk k, lane l : points [(64 k + l) S, (64 k + l + 1) S) below n, S c <= 512 values (attr_blob.h attr_layout)
+//   payload         = 64 x (state lo, state hi) | u16 len[64] | words of lane 0 | words of lane 1 | ..: every lane has
+//                     its own run of 16-bit renormalisation words, in the order its decoder consumes them (as version 2)
+//
+// A lane codes its points in order, the c channels of a point one after the other.  Value v of channel ch of the run's
+// s-th point is predicted from the same channel earlier in the run: pred = 0 (s = 0), v[s-1] (s = 1), else the rounded
+// mean (v[s-1] + v[s-2] + 1) >> 1.  The residual wraps to the value width: r = ((v - pred + h) & mask) - h, h = 2^(8 bpv
+// - 1) (the decoder's v = (pred + r) & mask), and is binarised as
+//   zero flag (r != 0) | sign (r < 0) | prefix: k = floor(log2 |r|) ones and a zero (no zero when k = kmax = 8 bpv - 1)
+//   | suffix: bits k-1 .. 0 of |r|
+// Context = (channel, bucket of the magnitude of the channel's previous residual in the run (edges 2, 5, 12, 30; 0 for
+// the run's first point), position): positions 0 zero flag, 1 sign, 2 + i prefix bit i, 2 + kmax + j suffix bit j, so
+// nctx = c x 5 x 16 bpv.  Model: version 2's (12-bit probabilities, adaptation shift 4, every lane's model starts from
+// the frame's p0, a counting pass), integer only.  The blob depends on the geometry through n alone.
+// tests/attr_ref.py restates the format in numpy.
+#include "common.h"
+#include "lanerans.h"
+#include "attr_blob.h"
+
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+namespace {
+
+constexpr uint32_t kAL = 1u << 16;
+constexpr int kAMaxCtx = 4 * kAttrBuckets * 32;   // c = 4, uint16
+
+__host__ __device__ inline int a_bucket(uint32_t m) { return (m >= 2) + (m >= 5) + (m >= 12) + (m >= 30); }
+
+// the decisions of residual r in coding order: emit(position, bit)
+template <typename Emit>
+__device__ __forceinline__ void a_binarise(int r, int kmax, Emit emit) {
+  emit(0, r != 0 ? 1u : 0u);
+  if (r == 0) return;
+  emit(1, r < 0 ? 1u : 0u);
+  const uint32_t m = (uint32_t)(r < 0 ? -r : r);
+  const int k = 31 - __clz(m);
+  for (int i = 0; i < kmax; ++i) {
+    const uint32_t bit = i < k ? 1u : 0u;
+    emit(2 + i, bit);
+    if (!bit) break;
+  }
+  for (int j = k - 1; j >= 0; --j) emit(2 + kmax + j, (m >> j) & 1u);
+}
+
+// residual of point i (run position s) in channel ch of a frame's merged values v[n][c]
+__device__ __forceinline__ int a_resid(const uint16_t* __restrict__ v, int64_t i, int64_t s, int c, int ch, uint32_t mask, int half) {
+  const uint32_t x = v[i * c + ch];
+  const uint32_t a = s >= 1 ? v[(i - 1) * c + ch] : 0u, b = s >= 2 ? v[(i - 2) * c + ch] : 0u;
+  const uint32_t pred = s == 0 ? 0u : (s == 1 ? a : (a + b + 1u) >> 1);
+  return (int)((x - pred + (uint32_t)half) & mask) - half;
+}
+
+// ---- encoder -----------------------------------------------------------------------------------------------------
+// one frame (>= 1 point) of an encode call
+struct AFrame {
+  int64_t in_off;            // its values as they came: bytes into the call's input
+  int64_t row0, rows;        // its input rows among the call's sorted keys
+  int64_t u0, n;             // its points: runs [u0, u0 + n) of the call's run starts
+  int64_t val_off;           // its merged values (uint16 [n][c]) in the call's merged array
+  int64_t rec_off;           // 16-bit words of records (and of word regions) of the frames in front of it
+  int64_t out_off, out_cap;  // its blob in the output staging: offset, bound
+  int32_t S, nc, cb, sb, sn, mb;   // chunks: S, count, first (of the call); stats blocks: first, count; merge blocks
+  int32_t c, bpv, nctx, ctx_off, T;   // T: records (and words) a lane may leave, S c 16 bpv
+};
+
+// merged value of every point: the rounded mean (sum + cnt / 2) / cnt of the run of equal keys behind it (order-free).
+// Frame f owns blocks [mb, mb + ceil(n / 256)); perm[t] is the input row of sorted key t, runs[u] the first sorted key
+// of run u, n_keys the call's key count.
+__global__ __launch_bounds__(256) void k_a_merge(const uint8_t* __restrict__ in, const AFrame* __restrict__ tab, int nf,
+                                                 const uint32_t* __restrict__ perm, const uint32_t* __restrict__ runs,
+                                                 int64_t n_runs, int64_t n_keys, uint16_t* __restrict__ merged) {
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].mb; });
+  const AFrame& h = tab[f];
+  const int64_t i = ((int64_t)blockIdx.x - h.mb) * blockDim.x + threadIdx.x;
+  if (i >= h.n) return;
+  const int c = h.c, bpv = h.bpv;
+  const int64_t u = h.u0 + i;
+  const int64_t t0 = runs[u], t1 = u + 1 < n_runs ? (int64_t)runs[u + 1] : n_keys;
+  uint64_t sum[4] = {0, 0, 0, 0};
+  int64_t cnt = 0;
+  for (int64_t t = t0; t < t1; ++t) {
+    const int64_t row = (int64_t)perm[t] - h.row0;
+    if (row < 0 || row >= h.rows) continue;   // not a row of this frame: the keys were not sorted frame by frame
+    const uint8_t* p = in + h.in_off + row * c * bpv;
+    for (int ch = 0; ch < c; ++ch)
+      sum[ch] += bpv == 1 ? (uint64_t)p[ch] : (uint64_t)p[2 * ch] | ((uint64_t)p[2 * ch + 1] << 8);
+    ++cnt;
+  }
+  if (cnt == 0) cnt = 1;
+  for (int ch = 0; ch < c; ++ch) merged[h.val_off + i * c + ch] = (uint16_t)((sum[ch] + (uint64_t)(cnt / 2)) / (uint64_t)cnt);
+}
+
+// zeros and ones seen per context over the whole frame: cnt[2 (ctx_off + ctx) + bit]; frame f takes blocks [sb, sb + sn)
+__global__ __launch_bounds__(256) void k_a_stats(const uint16_t* __restrict__ merged, const AFrame* __restrict__ tab, int nf,
+                                                 uint32_t* __restrict__ cnt_all) {
+  __shared__ uint32_t s_cnt[2 * kAMaxCtx];
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].sb; });
+  const AFrame& h = tab[f];
+  const uint16_t* v = merged + h.val_off;
+  const int c = h.c, P = attr_positions(h.bpv), kmax = 8 * h.bpv - 1, half = 1 << kmax;
+  const uint32_t mask = (1u << (8 * h.bpv)) - 1u;
+  const int64_t b = (int64_t)blockIdx.x - h.sb, nb = h.sn, S = h.S;
+  for (int i = threadIdx.x; i < 2 * h.nctx; i += blockDim.x) s_cnt[i] = 0u;
+  __syncthreads();
+  for (int64_t i = b * blockDim.x + threadIdx.x; i < h.n; i += nb * blockDim.x) {
+    const int64_t s = i % S;
+    for (int ch = 0; ch < c; ++ch) {
+      const int bk = s == 0 ? 0 : a_bucket((uint32_t)abs(a_resid(v, i - 1, s - 1, c, ch, mask, half)));
+      const int cbase = (ch * kAttrBuckets + bk) * P;
+      a_binarise(a_resid(v, i, s, c, ch, mask, half), kmax,
+                 [&](int pos, uint32_t bit) { atomicAdd(&s_cnt[2 * (cbase + pos) + bit], 1u); });
+    }
+  }
+  __syncthreads();
+  uint32_t* cnt = cnt_all + 2 * (int64_t)h.ctx_off;
+  for (int i = threadIdx.x; i < 2 * h.nctx; i += blockDim.x)
+    if (s_cnt[i]) atomicAdd(&cnt[i], s_cnt[i]);
+}
+
+// One wave per chunk (dynamic LDS: the reciprocal table, then the models [ctx][lane] with a dummy row).  Forward pass:
+// every lane walks its points with its own model and leaves one record per coded decision (probability of a one |
+// bit << 15) in rec[chunk][k][lane]; backward pass: the lane's rANS steps over its records in reverse (lockstep to the
+// wave's longest list, the rest masked), every renormalisation word stored downwards from the end of the lane's own
+// T-word region of `work` ([chunk][lane][T]: a step emits at most one word).  states / lens / words_out as k_o2_enc.
+__global__ __launch_bounds__(64) void k_a_enc(const uint16_t* __restrict__ merged, const AFrame* __restrict__ tab, int nf,
+                                              const uint32_t* __restrict__ cnt_all, uint16_t* __restrict__ rec_all,
+                                              uint16_t* __restrict__ work_all, uint16_t* __restrict__ states,
+                                              uint16_t* __restrict__ lens, uint32_t* __restrict__ words_out,
+                                              uint16_t* __restrict__ p0_all) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
+  uint32_t* s_rcp = s_dyn;
+  uint16_t* s_model = reinterpret_cast<uint16_t*>(s_dyn + 4096);
+  const int lane = threadIdx.x;
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].cb; });
+  const AFrame& h = tab[f];
+  const int64_t cg = blockIdx.x, ck = cg - h.cb;
+  const int c = h.c, P = attr_positions(h.bpv), kmax = 8 * h.bpv - 1, half = 1 << kmax, nctx = h.nctx, T = h.T;
+  const uint32_t mask = (1u << (8 * h.bpv)) - 1u;
+  const uint32_t* cnt = cnt_all + 2 * (int64_t)h.ctx_off;
+  const uint16_t* v = merged + h.val_off;
+  for (int ctx = lane; ctx < nctx; ctx += kLanes) {
+    const uint32_t p = o2_p0(cnt[2 * ctx], cnt[2 * ctx + 1]);
+    if (ck == 0) p0_all[h.ctx_off + ctx] = (uint16_t)p;
+    for (int l = 0; l < kLanes; ++l) s_model[ctx * kLanes + l] = (uint16_t)p;
+  }
+  lr_load_rcp(s_rcp, lane);
+  __syncthreads();
+  uint16_t* rec = rec_all + h.rec_off + ck * (int64_t)kLanes * T;
+  const int64_t base = (ck * kLanes + lane) * h.S;
+  const int64_t npts = std::max<int64_t>(0, std::min<int64_t>(h.S, h.n - base));
+  int K = 0;
+  uint32_t bk = 0;   // 4 bits per channel: the bucket of its previous residual
+  for (int64_t s = 0; s < npts; ++s) {
+    for (int ch = 0; ch < c; ++ch) {
+      const int r = a_resid(v, base + s, s, c, ch, mask, half);
+      const int cbase = (ch * kAttrBuckets + (int)((bk >> (4 * ch)) & 15u)) * P;
+      a_binarise(r, kmax, [&](int pos, uint32_t bit) {
+        const int at = (cbase + pos) * kLanes + lane;
+        const uint32_t p = s_model[at];
+        rec[(int64_t)K * kLanes + lane] = (uint16_t)(p | (bit << 15));
+        ++K;
+        s_model[at] = (uint16_t)o2_adapt(p, bit);
+      });
+      bk = (bk & ~(15u << (4 * ch))) | ((uint32_t)a_bucket((uint32_t)abs(r)) << (4 * ch));
+    }
+  }
+  __syncthreads();   // the records of the wave before they are read back
+
+  // backward pass
+  int kmax_w = K;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) kmax_w = std::max(kmax_w, __shfl_xor(kmax_w, d, 64));
+  constexpr int kAhead = 8;
+  const int kr = (kmax_w + kAhead - 1) / kAhead * kAhead;
+  uint16_t* reg_w = reinterpret_cast<uint16_t*>(uniform_u64((uint64_t)(work_all + h.rec_off + ck * (int64_t)kLanes * T)));
+  const __amdgpu_buffer_rsrc_t reg_rs = __builtin_amdgcn_make_buffer_rsrc(reg_w, 0, (int)(uint32_t)(kLanes * T * 2), 0x00027000);
+  int wp = T;   // words [wp, T) of the lane's region are written
+  const uint32_t lane_off = (uint32_t)lane * (uint32_t)T * 2u;
+  uint32_t x = kAL;
+  auto fetch = [&](int t) -> uint32_t { return rec[(int64_t)(t < 0 ? 0 : (t < T ? t : T - 1)) * kLanes + lane]; };
+  uint32_t R[kAhead];
+#pragma unroll
+  for (int d = 0; d < kAhead; ++d) R[d] = fetch(kr - 1 - d);
+  for (int t0 = kr - 1; t0 >= 0; t0 -= kAhead) {
+#pragma unroll
+    for (int d = 0; d < kAhead; ++d) {
+      const int t = t0 - d;
+      const uint32_t r = t < K ? R[d] : 0u;   // records beyond the lane's own count: nothing coded
+      R[d] = fetch(t - kAhead);
+      const uint32_t p1 = r & 0xFFFu, bit = r >> 15;
+      const bool act = r != 0u;
+      const uint32_t freq = bit ? p1 : 4096u - p1, start = bit ? 4096u - p1 : 0u, rcp = s_rcp[freq & 4095u];
+      const bool need = act && x >= (freq << 20);
+      wp -= need ? 1 : 0;
+      __builtin_amdgcn_raw_buffer_store_b16((unsigned short)x, reg_rs, need ? lane_off + (uint32_t)wp * 2u : 0xFFFFFFF0u, 0, 0);
+      x = need ? x >> 16 : x;
+      const uint32_t q0 = __umulhi(x, rcp);
+      const uint32_t r0 = x - q0 * freq;
+      const bool over = r0 >= freq;
+      const uint32_t qd = q0 + (over ? 1u : 0u), rem = r0 - (over ? freq : 0u);
+      x = act ? (qd << 12) + rem + start : x;
+    }
+  }
+  states[cg * 2 * kLanes + 2 * lane] = (uint16_t)x;
+  states[cg * 2 * kLanes + 2 * lane + 1] = (uint16_t)(x >> 16);
+  const uint32_t len = (uint32_t)(T - wp);
+  lens[cg * kLanes + lane] = (uint16_t)len;
+  uint32_t tot = len;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) tot += (uint32_t)__shfl_xor((int)tot, d, 64);
+  if (lane == 0) words_out[cg] = 3u * kLanes + tot;
+}
+
+// the blobs, assembled where `out_all` points (pinned host memory), frame f's at out_off: frame f owns workgroups
+// [cb + f, cb + f + nc + 1) — workgroup k < nc of them moves chunk k, workgroup nc writes the header; len_out[f] =
+// bytes, or -1 (out_cap)
+__global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ work_all, const AFrame* __restrict__ tab, int nf,
+                                                const uint16_t* __restrict__ states_all, const uint16_t* __restrict__ lens_all,
+                                                const uint32_t* __restrict__ words_all, const uint16_t* __restrict__ p0_all,
+                                                uint8_t* __restrict__ out_all, long long* __restrict__ len_out) {
+  __shared__ unsigned long long s_sum[256];
+  __shared__ uint32_t s_off[kLanes + 1];
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].cb + i; });
+  const AFrame& h = tab[f];
+  const int64_t k = (int64_t)blockIdx.x - h.cb - f, nc = h.nc, cap = h.out_cap;
+  const uint32_t* words = words_all + h.cb;
+  uint8_t* out = out_all + h.out_off;
+  unsigned long long part = 0;
+  const int64_t upto = k < nc ? k : nc;
+  for (int64_t j = threadIdx.x; j < upto; j += blockDim.x) part += words[j];
+  s_sum[threadIdx.x] = part;
+  __syncthreads();
+  for (int d = 128; d >= 1; d >>= 1) {
+    if ((int)threadIdx.x < d) s_sum[threadIdx.x] += s_sum[threadIdx.x + d];
+    __syncthreads();
+  }
+  const unsigned long long before = s_sum[0];
+  const unsigned long long head = (unsigned long long)kAttrHead + 8ull + 2ull * h.nctx + 4ull * nc;
+  if (k == nc) {
+    const unsigned long long total = head + before * 2;
+    const bool fits = (long long)total <= cap;
+    if (threadIdx.x == 0) {
+      len_out[f] = fits ? (long long)total : -1;
+      __threadfence_system();
+    }
+    if (!fits) return;
+    uint32_t* o32 = reinterpret_cast<uint32_t*>(out);
+    if (threadIdx.x == 0) {
+      o32[0] = (uint32_t)'A' | (1u << 8) | ((uint32_t)h.bpv << 16) | ((uint32_t)h.c << 24);
+      o32[1] = (uint32_t)h.n;
+      o32[2] = (uint32_t)(total - kAttrHead);
+      o32[3] = (uint32_t)h.S;
+      o32[4] = (uint32_t)h.nc;
+    }
+    uint16_t* o16 = reinterpret_cast<uint16_t*>(o32 + 5);
+    for (int i = threadIdx.x; i < h.nctx; i += blockDim.x) o16[i] = p0_all[h.ctx_off + i];
+    uint32_t* wt = reinterpret_cast<uint32_t*>(o16 + h.nctx);
+    for (int64_t j = threadIdx.x; j < nc; j += blockDim.x) wt[j] = words[j];
+    return;
+  }
+  if ((long long)(head + (before + words[k]) * 2) > cap) return;   // the header block reports it
+  uint16_t* dst = reinterpret_cast<uint16_t*>(out + head) + before;
+  lr_stage_chunk(work_all + h.rec_off, k, h.T, states_all + h.cb * 2 * kLanes, lens_all + h.cb * kLanes, s_off, dst);
+}
+
+// ---- decoder -----------------------------------------------------------------------------------------------------
+// status (int32) per frame: OR of 1 = a lane ran out of words or did not use all of its words, 4 = a lane's final
+// state is not the encoder's initial one
+//
+// one frame (>= 1 point) of a decode call
+struct ADFrame {
+  int64_t body_off;               // p0 | chunk table | payload of its blob in the call's uploaded bodies (4-aligned)
+  int64_t table_off, payload_off; // from body_off
+  int64_t n, out_off;             // points; its values in the output: bytes
+  int32_t S, nc, cb, c, bpv, nctx;
+};
+
+template <bool IN_LDS>
+__device__ __forceinline__ void a_decode_chunk(uint16_t* s_model, const uint16_t* __restrict__ s_words,
+                                               const uint16_t* __restrict__ p /* the chunk in the stream */, uint32_t cw,
+                                               const ADFrame& h, int64_t ck, int lane, uint8_t* __restrict__ out, int& bad) {
+  uint32_t x = (uint32_t)p[2 * lane] | ((uint32_t)p[2 * lane + 1] << 16);
+  const uint32_t my_len = p[2 * kLanes + lane];
+  uint32_t incl = my_len;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
+    incl += lane >= d ? o : 0u;
+  }
+  const uint32_t total = (uint32_t)__shfl((int)incl, 63, 64);
+  if (3u * kLanes + total != cw) {   // wave-uniform
+    bad |= 1;
+    return;
+  }
+  const uint32_t rbase = 3u * kLanes + incl - my_len, rend = rbase + my_len;
+  uint32_t pos = rbase;
+  auto word_at = [&](uint32_t i) -> uint32_t {
+    const uint32_t ic = i < cw ? i : cw - 1;   // a lane at the end of the chunk's last run looks one word too far: never used
+    if constexpr (IN_LDS) return s_words[ic];
+    return p[ic];
+  };
+  uint32_t nextw = word_at(pos);
+  const int c = h.c, bpv = h.bpv, P = attr_positions(bpv), kmax = 8 * bpv - 1;
+  const uint32_t mask = (1u << (8 * bpv)) - 1u;
+  const int64_t base = (ck * kLanes + lane) * h.S;
+  const int npts = (int)std::max<int64_t>(0, std::min<int64_t>(h.S, h.n - base));
+  const int a_dummy = h.nctx * kLanes + lane;
+  // the lane's place in its binarisation: phase 0 zero flag, 1 sign, 2 prefix (i ones so far), 3 suffix (i bits left)
+  int s = 0, ch = 0, phase = 0, i = 0;
+  uint32_t acc = 0, neg = 0, bk = 0;
+  uint64_t v1 = 0, v2 = 0;   // the channels' previous two values, 16 bits each
+  while (__ballot(s < npts)) {
+    const bool act = s < npts;
+    const int cpos = phase == 0 ? 0 : (phase == 1 ? 1 : (phase == 2 ? 2 + i : 1 + kmax + i));
+    const int at = act ? ((ch * kAttrBuckets + (int)((bk >> (4 * ch)) & 15u)) * P + cpos) * kLanes + lane : a_dummy;
+    const uint32_t p1 = s_model[at];
+    const uint32_t cum = x & 4095u;
+    const uint32_t bit = cum >= 4096u - p1 ? 1u : 0u;
+    const uint32_t start = bit ? 4096u - p1 : 0u, freq = bit ? p1 : 4096u - p1;
+    const uint32_t xn = freq * (x >> 12) + cum - start;
+    x = act ? xn : x;
+    s_model[at] = (uint16_t)o2_adapt(p1, bit);
+    const bool need = act && x < kAL;
+    bad |= (need && pos >= rend) ? 1 : 0;
+    x = need ? (x << 16) | nextw : x;
+    pos += need ? 1u : 0u;
+    nextw = word_at(pos);   // every step (the same word again when nothing was consumed): no branch
+    // the next place in the binarisation, and whether the value is complete (its magnitude m)
+    bool done = false;
+    uint32_t m = 0;
+    int nphase = phase, ni = i;
+    uint32_t nacc = acc;
+    if (phase == 0) {
+      done = bit == 0u;
+      nphase = 1;
+    } else if (phase == 1) {
+      neg = bit;
+      nphase = 2;
+      ni = 0;
+    } else if (phase == 2) {
+      const int k = i + (int)bit;
+      if (bit == 0u || k == kmax) {
+        done = k == 0;
+        m = 1;
+        nphase = 3;
+        ni = k;
+        nacc = 1;
+      } else {
+        ni = k;
+      }
+    } else {
+      nacc = 2 * acc + bit;
+      ni = i - 1;
+      done = ni == 0;
+      m = nacc;
+    }
+    phase = nphase;
+    i = ni;
+    acc = nacc;
+    if (act && done) {
+      const uint32_t sh = 16u * (uint32_t)ch;
+      const uint32_t a = (uint32_t)(v1 >> sh) & 0xFFFFu, b = (uint32_t)(v2 >> sh) & 0xFFFFu;
+      const uint32_t pred = s == 0 ? 0u : (s == 1 ? a : (a + b + 1u) >> 1);
+      const uint32_t val = (pred + (neg ? 0u - m : m)) & mask;
+      const int64_t o = ((base + s) * c + ch) * bpv;
+      out[o] = (uint8_t)val;
+      if (bpv == 2) out[o + 1] = (uint8_t)(val >> 8);
+      v2 = (v2 & ~(0xFFFFull << sh)) | ((uint64_t)a << sh);
+      v1 = (v1 & ~(0xFFFFull << sh)) | ((uint64_t)val << sh);
+      bk = (bk & ~(15u << (4 * ch))) | ((uint32_t)a_bucket(m) << (4 * ch));
+      phase = 0;
+      neg = 0;
+      ++ch;
+      if (ch == c) {
+        ch = 0;
+        ++s;
+      }
+    }
+  }
+  if (pos != rend) bad |= 1;   // every word of the run consumed
+  if (x != kAL) bad |= 4;      // back at the encoder's initial state
+}
+
+// block = chunk of the call: frame f owns blocks [cb, cb + nc).  Dynamic LDS: the models (nctx_max + 1 rows of 64),
+// then lds_words words for a chunk's payload
+__global__ __launch_bounds__(64) void k_a_dec(const uint8_t* __restrict__ bodies, const ADFrame* __restrict__ tab, int nf,
+                                              int model_rows, int lds_words, uint8_t* __restrict__ out_all,
+                                              int32_t* __restrict__ status_all) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
+  uint16_t* s_model = reinterpret_cast<uint16_t*>(s_dyn);
+  uint16_t* s_words = s_model + (int64_t)model_rows * kLanes;
+  const int lane = threadIdx.x;
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].cb; });
+  const ADFrame& h = tab[f];
+  const int64_t ck = (int64_t)blockIdx.x - h.cb;
+  const uint8_t* body = bodies + h.body_off;
+  const uint16_t* p0 = reinterpret_cast<const uint16_t*>(body);
+  const uint32_t* table = reinterpret_cast<const uint32_t*>(body + h.table_off);
+  const uint16_t* payload = reinterpret_cast<const uint16_t*>(body + h.payload_off);
+  for (int ctx = 0; ctx < h.nctx; ++ctx) s_model[ctx * kLanes + lane] = p0[ctx];
+  unsigned long long before = 0;
+  for (int64_t j = lane; j < ck; j += kLanes) before += table[j];
+  for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d, 64);
+  const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)table[ck]);
+  const uint16_t* p = payload + before;
+  int bad = 0;
+  if (cw <= (uint32_t)lds_words) {
+    for (uint32_t i = lane; i < cw; i += kLanes) s_words[i] = p[i];
+    __syncthreads();
+    a_decode_chunk<true>(s_model, s_words, p, cw, h, ck, lane, out_all + h.out_off, bad);
+  } else {
+    a_decode_chunk<false>(s_model, s_words, p, cw, h, ck, lane, out_all + h.out_off, bad);
+  }
+  const unsigned long long b1 = __ballot((bad & 1) != 0), b4 = __ballot((bad & 4) != 0);
+  if (lane == 0 && (b1 | b4) != 0ull) atomicOr(status_all + f, (b1 ? 1 : 0) | (b4 ? 4 : 0));
+}
+
+}  // namespace
+
+static inline int64_t a_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+// ======================================================================== C-ABI (include/pcc.h)
+extern "C" int pcc_attr_encode_frames(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets, const int32_t* h_format,
+                                      const int64_t* h_rows, const int64_t* h_points, int n_frames, const uint32_t* d_perm,
+                                      const uint32_t* d_run_starts, int64_t n_unique, uint8_t* h_out, int64_t cap,
+                                      int64_t* h_offsets) {
+  PCC_REQUIRE(ctx && h_value_offsets && h_format && h_rows && h_points && h_out && h_offsets && n_frames >= 1 &&
+                  n_frames <= 65535 && n_unique >= 0 && cap >= 0,
+              PCC_E_ARG, "pcc_attr_encode_frames: bad argument (n_frames=%d)", n_frames);
+  const int64_t n_keys = h_rows[n_frames];
+  PCC_REQUIRE(h_rows[0] == 0 && n_keys < ((int64_t)1 << 27) && n_unique <= n_keys &&
+                  (n_keys == 0 || (d_values && d_perm && d_run_starts)),
+              PCC_E_ARG, "pcc_attr_encode_frames: %lld rows, %lld points", (long long)n_keys, (long long)n_unique);
+  std::vector<AFrame> tab;
+  std::vector<int> frame_of;
+  int64_t u = 0, vals = 0, rec_words = 0, out_bytes = 0, chunks = 0, stats_blocks = 0, merge_blocks = 0, ctxs = 0, nctx_max = 0;
+  for (int f = 0; f < n_frames; ++f) {
+    const int bpv = h_format[f] & 0xFF, c = h_format[f] >> 8;
+    const int64_t rows = h_rows[f + 1] - h_rows[f], n = h_points[f];
+    PCC_REQUIRE((bpv == 1 || bpv == 2) && c >= 1 && c <= 4, PCC_E_ARG, "pcc_attr_encode_frames: frame %d: format %d", f,
+                h_format[f]);
+    PCC_REQUIRE(rows >= 0 && n >= 0 && n <= rows && (n == 0) == (rows == 0) && h_value_offsets[f] >= 0, PCC_E_ARG,
+                "pcc_attr_encode_frames: frame %d: %lld rows, %lld points", f, (long long)rows, (long long)n);
+    if (n == 0) continue;
+    AFrame r;
+    int64_t S, nc;
+    attr_layout(n, c, &S, &nc);
+    r.in_off = h_value_offsets[f];
+    r.row0 = h_rows[f];
+    r.rows = rows;
+    r.u0 = u;
+    r.n = n;
+    r.val_off = vals;
+    r.rec_off = rec_words;
+    r.c = c;
+    r.bpv = bpv;
+    r.nctx = attr_contexts(bpv, c);
+    r.ctx_off = (int32_t)ctxs;
+    r.T = (int32_t)(S * c * attr_positions(bpv));
+    const int64_t head = kAttrHead + 8 + 2 * r.nctx + 4 * nc;
+    // a coded decision emits at most one word: the bound follows the frame's decisions, not its chunks' regions
+    r.out_cap = head + 2 * (3 * kLanes * nc + std::min<int64_t>(nc * kLanes * r.T, (int64_t)attr_positions(bpv) * c * n));
+    r.out_off = out_bytes;
+    r.S = (int32_t)S;
+    r.nc = (int32_t)nc;
+    r.cb = (int32_t)chunks;
+    r.sb = (int32_t)stats_blocks;
+    r.sn = (int32_t)std::min<unsigned>(nblk(n, 256), 256u);
+    r.mb = (int32_t)merge_blocks;
+    tab.push_back(r);
+    frame_of.push_back(f);
+    u += n;
+    vals += n * c;
+    rec_words += nc * kLanes * r.T;
+    out_bytes += a_round(r.out_cap, 16);
+    chunks += nc;
+    stats_blocks += r.sn;
+    merge_blocks += nblk(n, 256);
+    ctxs += r.nctx;
+    nctx_max = std::max<int64_t>(nctx_max, r.nctx);
+  }
+  PCC_REQUIRE(u == n_unique, PCC_E_ARG, "pcc_attr_encode_frames: the frames have %lld points, the runs %lld", (long long)u,
+              (long long)n_unique);
+  const int nf = (int)tab.size();
+  std::vector<int64_t> len_of((size_t)n_frames, kAttrHead);
+  std::vector<int64_t> off_of((size_t)n_frames, -1);
+  hipStream_t st = ctx->stream;
+  if (nf > 0) {
+    const size_t tab_b = pcc_align((size_t)nf * sizeof(AFrame));
+    const size_t merged_b = pcc_align((size_t)vals * 2), cnt_b = pcc_align((size_t)ctxs * 8), p0_b = pcc_align((size_t)ctxs * 2);
+    const size_t rec_b = pcc_align((size_t)rec_words * 2), small_b = pcc_align((size_t)chunks * (4 + 2 * kLanes * 2 + kLanes * 2));
+    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + 8192));
+    AFrame* d_tab = (AFrame*)pcc_arena_alloc(ctx, tab_b);
+    uint16_t* merged = (uint16_t*)pcc_arena_alloc(ctx, merged_b);
+    uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, cnt_b);
+    uint16_t* p0 = (uint16_t*)pcc_arena_alloc(ctx, p0_b);
+    uint16_t* rec = (uint16_t*)pcc_arena_alloc(ctx, rec_b);
+    uint16_t* work = (uint16_t*)pcc_arena_alloc(ctx, rec_b);
+    char* small = (char*)pcc_arena_alloc(ctx, small_b);
+    if (!d_tab || !merged || !cnt || !p0 || !rec || !work || !small) return PCC_E_NOMEM;
+    uint32_t* words = (uint32_t*)small;
+    uint16_t* states = (uint16_t*)(small + (size_t)chunks * 4);
+    uint16_t* lens_d = states + (size_t)chunks * 2 * kLanes;
+    // staging: the table on its way to the device | the blobs | their lengths
+    const size_t lens_at = tab_b + (size_t)out_bytes;
+    PCC_TRY(o2_stage_reserve(ctx, lens_at + (size_t)nf * 8 + 64));
+    uint8_t* stage = (uint8_t*)ctx->stage;
+    memcpy(stage, tab.data(), (size_t)nf * sizeof(AFrame));
+    long long* len_dev = (long long*)(stage + lens_at);
+    PccProfScope prof(ctx, "attr_encode", u, nf, chunks, 0);
+    PCC_HIP(hipMemcpyAsync(d_tab, stage, (size_t)nf * sizeof(AFrame), hipMemcpyHostToDevice, st));
+    PCC_HIP(hipMemsetAsync(cnt, 0, (size_t)ctxs * 8, st));
+    hipLaunchKernelGGL(k_a_merge, dim3((unsigned)merge_blocks), dim3(256), 0, st, (const uint8_t*)d_values, (const AFrame*)d_tab, nf,
+                       d_perm, d_run_starts, n_unique, n_keys, merged);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_a_stats, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)merged, (const AFrame*)d_tab, nf, cnt);
+    PCC_CHECK_LAUNCH();
+    const size_t lds = 4096 * 4 + (size_t)(nctx_max + 1) * kLanes * 2;   // <= 98 KB (c = 4, uint16)
+    PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_a_enc, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)merged, (const AFrame*)d_tab, nf,
+                       (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_a_pack, dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work, (const AFrame*)d_tab, nf,
+                       (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words, (const uint16_t*)p0,
+                       stage + tab_b, len_dev);
+    PCC_CHECK_LAUNCH();
+    PCC_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < nf; ++k) {
+      const long long total = ((volatile long long*)len_dev)[k];
+      PCC_REQUIRE(total >= 0 && total <= tab[(size_t)k].out_cap, PCC_E_NOMEM,
+                  "pcc_attr_encode_frames: frame %d: blob beyond its bound", frame_of[(size_t)k]);
+      len_of[(size_t)frame_of[(size_t)k]] = total;
+      off_of[(size_t)frame_of[(size_t)k]] = (int64_t)tab_b + tab[(size_t)k].out_off;
+    }
+  }
+  int64_t total = 0;
+  for (int f = 0; f < n_frames; ++f) total += len_of[(size_t)f];
+  PCC_REQUIRE(total <= cap, PCC_E_NOMEM, "pcc_attr_encode_frames: %lld bytes of blobs, capacity %lld", (long long)total,
+              (long long)cap);
+  h_offsets[0] = 0;
+  for (int f = 0; f < n_frames; ++f) {
+    uint8_t* dst = h_out + h_offsets[f];
+    if (off_of[(size_t)f] >= 0) {
+      memcpy(dst, (const uint8_t*)ctx->stage + off_of[(size_t)f], (size_t)len_of[(size_t)f]);
+    } else {   // no points: the 12-byte empty blob
+      memset(dst, 0, kAttrHead);
+      dst[0] = 'A';
+      dst[1] = 1;
+      dst[2] = (uint8_t)(h_format[f] & 0xFF);
+      dst[3] = (uint8_t)(h_format[f] >> 8);
+    }
+    h_offsets[f + 1] = h_offsets[f] + len_of[(size_t)f];
+  }
+  return PCC_OK;
+}
+
+extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
+                                      const int64_t* h_points, uint8_t* d_out, uint8_t* h_out, int64_t cap_bytes,
+                                      int64_t* h_out_offsets, int32_t* h_format) {
+  PCC_REQUIRE(ctx && h_blobs && h_lens && h_out_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
+              "pcc_attr_decode_frames: bad argument (n_frames=%d)", n_frames);
+  std::vector<AttrInfo> info((size_t)n_frames);
+  int64_t bytes = 0, bodies = 0, points = 0;
+  h_out_offsets[0] = 0;
+  for (int f = 0; f < n_frames; ++f) {
+    AttrInfo& o = info[(size_t)f];
+    const int rc = attr_parse(h_blobs[f], h_lens[f], &o);
+    if (rc != PCC_OK) {
+      const std::string m = pcc_last_error();
+      pcc_set_error("pcc_attr_decode_frames: frame %d: %s", f, m.c_str());
+      return rc;
+    }
+    PCC_REQUIRE(!h_points || h_points[f] == o.n, PCC_E_STREAM,
+                "pcc_attr_decode_frames: frame %d: the attribute blob has %lld points, its geometry %lld", f, (long long)o.n,
+                (long long)(h_points ? h_points[f] : 0));
+    if (h_format) h_format[f] = o.bpv | (o.c << 8);
+    bytes = a_round(bytes + o.n * o.c * o.bpv, 16);
+    points += o.n;
+    h_out_offsets[f + 1] = bytes;
+    if (o.n) bodies += a_round(h_lens[f] - o.off_p0, 16);
+  }
+  PCC_REQUIRE(points < ((int64_t)1 << 31), PCC_E_ARG, "pcc_attr_decode_frames: the blobs announce %lld points in all",
+              (long long)points);
+  if (bytes == 0 || (!d_out && !h_out)) return PCC_OK;
+  PCC_REQUIRE(cap_bytes >= bytes, PCC_E_NOMEM, "pcc_attr_decode_frames: %lld bytes, capacity %lld", (long long)bytes,
+              (long long)cap_bytes);
+  std::vector<ADFrame> tab;
+  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0;
+  for (int f = 0; f < n_frames; ++f) {
+    const AttrInfo& o = info[(size_t)f];
+    if (o.n == 0) continue;
+    ADFrame r;
+    r.body_off = body_off;
+    r.table_off = o.off_table - o.off_p0;
+    r.payload_off = o.off_payload - o.off_p0;
+    r.n = o.n;
+    r.out_off = h_out_offsets[f];
+    r.S = (int32_t)o.S;
+    r.nc = (int32_t)o.nc;
+    r.cb = (int32_t)chunks;
+    r.c = o.c;
+    r.bpv = o.bpv;
+    r.nctx = o.nctx;
+    tab.push_back(r);
+    for (int64_t k = 0; k < o.nc; ++k) cw_max = std::max<int64_t>(cw_max, attr_u32(h_blobs[f] + o.off_table + 4 * k));
+    body_off += a_round(h_lens[f] - o.off_p0, 16);
+    chunks += o.nc;
+    nctx_max = std::max<int64_t>(nctx_max, o.nctx);
+  }
+  const int nf = (int)tab.size();
+  hipStream_t st = ctx->stream;
+  const size_t tab_b = pcc_align((size_t)nf * sizeof(ADFrame));
+  PCC_TRY(pcc_arena_reserve(ctx, tab_b + pcc_align((size_t)bodies + 16) + (d_out ? 0 : pcc_align((size_t)bytes)) +
+                                     pcc_align((size_t)nf * 4 + 64) + 4096));
+  uint8_t* d_in = (uint8_t*)pcc_arena_alloc(ctx, tab_b + (size_t)bodies + 16);
+  uint8_t* out = d_out ? d_out : (uint8_t*)pcc_arena_alloc(ctx, (size_t)bytes);
+  int32_t* status = (int32_t*)pcc_arena_alloc(ctx, (size_t)nf * 4 + 64);
+  if (!d_in || !out || !status) return PCC_E_NOMEM;
+  PccProfScope prof(ctx, "attr_decode", points, nf, chunks, 0);
+  // a caller's array in pinned host memory receives the values straight from the device; any other one through the
+  // staging (a failed query of an ordinary pointer leaves its error behind: cleared here)
+  bool direct = false;
+  if (h_out) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, h_out) == hipSuccess)
+      direct = attr.type == hipMemoryTypeHost;
+    else
+      (void)hipGetLastError();
+  }
+  const size_t in_b = tab_b + (size_t)bodies;
+  const size_t out_b = h_out && !direct ? (size_t)bytes : 0;
+  PCC_TRY(o2_stage_reserve(ctx, pcc_align(in_b) + pcc_align(out_b) + (size_t)nf * 4 + 64));
+  uint8_t* stage = (uint8_t*)ctx->stage;
+  memcpy(stage, tab.data(), (size_t)nf * sizeof(ADFrame));
+  for (int f = 0, k = 0; f < n_frames; ++f) {
+    const AttrInfo& o = info[(size_t)f];
+    if (o.n == 0) continue;
+    memcpy(stage + tab_b + tab[(size_t)k].body_off, h_blobs[f] + o.off_p0, (size_t)(h_lens[f] - o.off_p0));
+    ++k;
+  }
+  PCC_HIP(hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
+  PCC_HIP(hipMemsetAsync(status, 0, (size_t)nf * 4 + 64, st));
+  // a chunk's payload in LDS beside the models when it fits in 128 KB in all, else read where it lies
+  const int model_rows = (int)nctx_max + 1;
+  const int64_t room = ((int64_t)128 * 1024 - (int64_t)model_rows * kLanes * 2) / 2;
+  const int lds_words = (int)std::max<int64_t>(0, std::min<int64_t>(cw_max, room));
+  const size_t lds = (size_t)model_rows * kLanes * 2 + (size_t)lds_words * 2;
+  PCC_HIP(hipFuncSetAttribute((const void*)k_a_dec, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_a_dec, dim3((unsigned)chunks), dim3(64), lds, st, (const uint8_t*)(d_in + tab_b), (const ADFrame*)d_in, nf,
+                     model_rows, lds_words, out, status);
+  PCC_CHECK_LAUNCH();
+  uint8_t* stage_out = stage + pcc_align(in_b);
+  int32_t* h_status = (int32_t*)(stage_out + pcc_align(out_b));
+  if (h_out) PCC_HIP(hipMemcpyAsync(direct ? (void*)h_out : (void*)stage_out, out, (size_t)bytes, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipMemcpyAsync(h_status, status, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipStreamSynchronize(st));
+  for (int f = 0, k = 0; f < n_frames; ++f) {
+    if (info[(size_t)f].n == 0) continue;
+    const int32_t bad = h_status[k++];
+    PCC_REQUIRE(bad == 0, PCC_E_STREAM, "pcc_attr_decode_frames: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state)",
+                f, bad);
+  }
+  if (h_out && !direct) memcpy(h_out, stage_out, out_b);
+  return PCC_OK;
+}

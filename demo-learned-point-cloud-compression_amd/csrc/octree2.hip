@@ -35,6 +35,7 @@
 // writes every child's (parent, octant) link and a pass in which every leaf walks up `depth` links.
 // All integer: bit-exact against oracle/pcc_oracle.c (orc_octree2_encode / orc_octree_decode).
 #include "common.h"
+#include "lanerans.h"
 
 #include <string.h>
 
@@ -46,29 +47,13 @@ void octree_root(uint64_t first, uint64_t last, int key_shift, int* depth, int32
 
 namespace {
 
-constexpr int kLanes = 64;
 constexpr int kCtx = 108;        // 3 level classes x 36 (bit position, ones so far)
 constexpr int kSMax = 512;       // nodes per lane: a launch lasts 8 S dependent steps of one wave
 constexpr int kHeader = 24;
 constexpr uint32_t kL = 1u << 16;
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
-__host__ __device__ inline uint32_t o2_p0(uint64_t c0, uint64_t c1) {
-  const uint64_t p = (4096ull * (2 * c1 + 1)) / (2 * (c0 + c1 + 1));
-  return (uint32_t)(p < 16 ? 16 : (p > 4080 ? 4080 : p));
-}
-// (both sides computed and merged by a mask: written as a conditional expression the compiler made it a divergent branch)
-__device__ __forceinline__ uint32_t o2_adapt(uint32_t p, uint32_t bit) {
-  const uint32_t up = p + ((4096u - p) >> 4), dn = p - (p >> 4), m = 0u - bit;
-  return (up & m) | (dn & ~m);
-}
 __device__ __forceinline__ int lane_rank(unsigned long long bal) {
   return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-}
-__device__ __forceinline__ uint64_t uniform_u64(uint64_t u) {
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(u >> 32)) << 32) |
-         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u);
 }
 
 struct O2Layout {
@@ -81,19 +66,6 @@ static O2Layout o2_layout(int64_t n_nodes) {
   s = (s + 3) / 4 * 4;
   if (s < 4) s = 4;
   return O2Layout{s, c};
-}
-
-// Every kernel below codes or decodes the frames of one call side by side: a table in device memory has one row per
-// frame, a block finds its frame by a search over the rows' first block (the same for all its threads), and a single
-// frame is the table of one row.  Last row whose start <= v:
-template <typename Start>
-__device__ __forceinline__ int o2_find(int nf, int64_t v, Start start) {
-  int lo = 0, hi = nf - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (start(mid) <= v) lo = mid; else hi = mid - 1;
-  }
-  return __builtin_amdgcn_readfirstlane(lo);
 }
 
 // ---- encoder -----------------------------------------------------------------------------------------------------
@@ -136,20 +108,6 @@ __global__ __launch_bounds__(256) void k_o2_stats(const uint8_t* __restrict__ oc
     if (s_cnt[i]) atomicAdd(&cnt[i], s_cnt[i]);
 }
 
-// floor(2^32 / f) for f = 1 .. 4095 (entry 0 and 1 unused: a frequency is 15 .. 4081): x / f for x < 2^32 is
-// mulhi(x, rcp[f]) or one more (checked by the remainder)
-struct O2Rcp {
-  uint32_t v[4096];
-};
-__host__ __device__ constexpr O2Rcp o2_rcp_table() {
-  O2Rcp t{};
-  for (int f = 2; f < 4096; ++f) t.v[f] = (uint32_t)(0x100000000ull / (uint64_t)f);
-  t.v[0] = 0;
-  t.v[1] = 0xFFFFFFFFu;
-  return t;
-}
-__device__ const O2Rcp kO2Rcp = o2_rcp_table();
-
 // One wave per chunk.  Forward pass: every lane walks its S nodes with its own model and leaves one record per step
 // (probability of a one | bit << 15, 0 = nothing coded) in rec[chunk][step][lane]; backward pass: the lane's rANS steps
 // in reverse, every renormalisation word stored downwards from the end of the lane's own T-word region of `work`
@@ -180,12 +138,7 @@ __global__ __launch_bounds__(64) void k_o2_enc(const uint8_t* __restrict__ occ_a
     s_p0[ctx] = (uint16_t)p;
     if (c == 0) p0_out[ctx] = (uint16_t)p;
   }
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(kO2Rcp.v);
-    uint4* dst = reinterpret_cast<uint4*>(s_rcp);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) dst[lane + 64 * i] = src[lane + 64 * i];
-  }
+  lr_load_rcp(s_rcp, lane);
   __syncthreads();
   for (int ctx = 0; ctx < kCtx; ++ctx) s_model[ctx * kLanes + lane] = s_p0[ctx];
   const int64_t T = 8 * (int64_t)S;
@@ -627,14 +580,10 @@ __global__ __launch_bounds__(64) void k_of_frames(const uint64_t* __restrict__ k
   }
 }
 
-inline uint32_t get_u32(const uint8_t* p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-
 }  // namespace
 
 // pinned staging of a context, grown on demand (blobs and decoded points cross PCIe through it)
-static int o2_stage_reserve(pcc_ctx* ctx, size_t bytes) {
+int o2_stage_reserve(pcc_ctx* ctx, size_t bytes) {
   if (bytes <= ctx->stage_cap) return PCC_OK;
   size_t want = ctx->stage_cap ? ctx->stage_cap : ((size_t)1 << 20);
   while (want < bytes) want *= 2;

@@ -9,10 +9,17 @@ are coded side by side by one pcc_octree_encode_frames call and decoded by one p
     frames = codec.decompress(blobs)                     # int32 [n_f, 3], Morton order (as pcc_octree_decode_dev)
     frames = codec.decompress(blobs, output="device")    # the same as views of one device tensor
 
+    blobs, attr_blobs = codec.compress(frames, attributes=[a0, a1, ...])   # uint8 / uint16 [n_f] or [n_f, c], c <= 4
+    frames, attrs = codec.decompress(blobs, attr_blobs)  # attrs[f]: [n_f, c] in its dtype, row i = point i
+
+Attributes are lossless (attribute blob version 1, csrc/attr.hip), one blob per frame beside its geometry blob; the
+values of duplicate points merge to their rounded mean per channel, (sum + cnt // 2) // cnt.
+
 One Runtime (ctx + stream) per codec; calls on the same instance are serialised, instances on different threads run
 side by side.
 """
 import ctypes as C
+import struct
 import threading
 
 import numpy as np
@@ -46,13 +53,36 @@ class GeometryCodec:
             raise ValueError(f"{len(out)} frames in one call, at most {MAX_FRAMES}")
         return out
 
-    def compress(self, frames):
+    @staticmethod
+    def _check_attributes(frames, attributes):
+        attributes = list(attributes)
+        if len(attributes) != len(frames):
+            raise ValueError(f"{len(attributes)} attribute arrays for {len(frames)} frames")
+        out = []
+        for f, (a, p) in enumerate(zip(attributes, frames)):
+            a = np.asarray(a)
+            if a.dtype not in (np.uint8, np.uint16):
+                raise TypeError(f"frame {f}: expected uint8 or uint16 attributes, got {a.dtype}")
+            if a.ndim == 1:
+                a = a[:, None]
+            if a.ndim != 2 or not 1 <= a.shape[1] <= 4:
+                raise ValueError(f"frame {f}: expected attributes of shape [n] or [n, c] with 1 <= c <= 4, got {a.shape}")
+            if a.shape[0] != p.shape[0]:
+                raise ValueError(f"frame {f}: {a.shape[0]} attribute rows for {p.shape[0]} points")
+            out.append(np.ascontiguousarray(a.astype(a.dtype.newbyteorder("<"), copy=False)))
+        return out
+
+    def compress(self, frames, attributes=None):
         """frames: a sequence of int16 / int32 [n_f, 3] arrays -> a list of bytes, one version-2 blob per frame.
-        Duplicate points are removed (as np.unique), out-of-range coordinates raise PccError (PCC_E_RANGE)."""
+        Duplicate points are removed (as np.unique), out-of-range coordinates raise PccError (PCC_E_RANGE).
+        attributes (optional): one uint8 / uint16 [n_f] or [n_f, c] array per frame (1 <= c <= 4) -> (blobs,
+        attribute blobs): attribute blob f holds, losslessly, one row per decoded point of frame f (Morton order), the
+        rows of duplicate points merged to their rounded mean per channel."""
         frames = self._check_frames(frames)
+        attrs = None if attributes is None else self._check_attributes(frames, attributes)
         nb = len(frames)
         if nb == 0:
-            return []
+            return [] if attrs is None else ([], [])
         sizes = [a.shape[0] for a in frames]
         n = int(sum(sizes))
         # one upload, the rows as they come (6 or 12 B per point) behind the frame offsets; the frame index and the
@@ -67,14 +97,15 @@ class GeometryCodec:
             np.concatenate(frames, axis=0, out=h[rows_at:].view(dtype).reshape(n, 3))
         with self._lock, self.rt as rt:
             if n == 0:
-                return rt.octree_encode_frames(rt.empty((0,), torch.int64), nb)
+                blobs = rt.octree_encode_frames(rt.empty((0,), torch.int64), nb)
+                return blobs if attrs is None else (blobs, self._encode_attributes(rt, attrs, sizes, blobs, None, None, 0))
             dev = rt.to_device(host)
             keys = rt.empty((n,), torch.int64)
             flag = torch.zeros(1, dtype=torch.int32, device=rt.device)
             check(rt.lib.pcc_morton_keys_frames(rt.ctx, C.c_void_p(dev.data_ptr() + rows_at), np.dtype(dtype).itemsize, n,
                                                 C.c_void_p(dev.data_ptr()), nb, _ptr(keys), _ptr(flag)),
                   "pcc_morton_keys_frames")
-            rt.sort_pairs(keys)
+            perm = rt.sort_pairs(keys)
             # duplicates (np.unique): the first row of every run of equal keys
             rows = rt.empty((n,), torch.int32)
             n_u = C.c_int64(0)
@@ -84,18 +115,51 @@ class GeometryCodec:
                 raise PccError(PCC_E_RANGE, "GeometryCodec.compress", "coordinate outside [-32768, 32767]")
             if n_u.value < n:
                 keys = rt.gather_rows(keys, rows[:n_u.value])
-            return rt.octree_encode_frames(keys, nb)
+            blobs = rt.octree_encode_frames(keys, nb)
+            if attrs is None:
+                return blobs
+            return blobs, self._encode_attributes(rt, attrs, sizes, blobs, perm, rows, n_u.value)
 
-    def decompress(self, blobs, output="numpy"):
+    @staticmethod
+    def _encode_attributes(rt, attrs, sizes, blobs, perm, rows, n_unique):
+        # the values as they come, frame by frame at 16-byte offsets, in one upload; the merge into Morton order
+        # happens on the device from the sort's permutation and the runs of equal keys
+        offs, at = [], 0
+        for a in attrs:
+            offs.append(at)
+            at += (a.nbytes + 15) // 16 * 16
+        host = torch.empty(max(at, 16), dtype=torch.uint8, pin_memory=True)
+        h = host.numpy()
+        for o, a in zip(offs, attrs):
+            h[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+        values = rt.to_device(host) if at else None
+        formats = [a.dtype.itemsize | (a.shape[1] << 8) for a in attrs]
+        points = [struct.unpack_from("<I", b, 4)[0] for b in blobs]
+        row_offsets = np.cumsum([0] + list(sizes)).tolist()
+        return rt.attr_encode_frames(values, offs, formats, row_offsets, points, perm, rows, n_unique)
+
+    def decompress(self, blobs, attr_blobs=None, output="numpy"):
         """version-2 blobs -> a list of int32 [n_f, 3] point sets in Morton order: numpy arrays (output="numpy") or
-        device tensors (output="device", on this codec's device)"""
+        device tensors (output="device", on this codec's device).  With attr_blobs (compress(..., attributes=...)):
+        (point sets, attributes), attributes[f] an [n_f, c] array in its original dtype, row i belonging to point i; an
+        attribute blob decodes only with the geometry blob of its own frame (another point count raises PccError)."""
+        if isinstance(attr_blobs, str):      # decompress(blobs, "device"), as before attributes
+            attr_blobs, output = None, attr_blobs
         if output not in ("numpy", "device"):
             raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
         blobs = [bytes(b) for b in blobs]
         if len(blobs) > MAX_FRAMES:
             raise ValueError(f"{len(blobs)} blobs in one call, at most {MAX_FRAMES}")
+        if attr_blobs is not None:
+            attr_blobs = [bytes(b) for b in attr_blobs]
+            if len(attr_blobs) != len(blobs):
+                raise ValueError(f"{len(attr_blobs)} attribute blobs for {len(blobs)} geometry blobs")
         with self._lock, self.rt as rt:
-            return rt.octree_decode_frames(blobs, device=(output == "device"))
+            frames = rt.octree_decode_frames(blobs, device=(output == "device"))
+            if attr_blobs is None:
+                return frames
+            return frames, rt.attr_decode_frames(attr_blobs, points=[f.shape[0] for f in frames],
+                                                 device=(output == "device"))
 
 
 __all__ = ["GeometryCodec", "PccError", "MAX_FRAMES"]

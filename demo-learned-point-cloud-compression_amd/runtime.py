@@ -9,6 +9,7 @@ to three concurrent calls, sender/encoder/encoder.py:50).
 """
 import ctypes as C
 import os
+import struct
 import threading
 
 import numpy as np
@@ -585,6 +586,62 @@ class Runtime:
                 check(self.lib.pcc_octree_decode_frames(self.ctx, ptrs, lens, nb, None, _np_ptr(pts), total, offs),
                       "pcc_octree_decode_frames")
         return [pts[offs[f]:offs[f + 1]] for f in range(nb)]
+
+    def attr_encode_frames(self, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique):
+        """attribute blobs (version 1, csrc/attr.hip) of len(formats) frames at once (pcc_attr_encode_frames): `values` a
+        device uint8 tensor with frame f's [rows_f, c_f] values at byte value_offsets[f], formats[f] = bytes per value |
+        c_f << 8, row_offsets (n_frames + 1) the frames' rows among the call's keys, perm / run_starts what
+        sort_pairs / pcc_unique_rows returned for those keys, points[f] frame f's points after the merge.  A list of
+        n_frames bytes objects."""
+        nf = len(formats)
+        cap = 0
+        for fmt, n in zip(formats, points):
+            bpv, c = fmt & 0xFF, fmt >> 8
+            cap += 32 + 2 * 80 * bpv * c + 388 * (n // 64 + 1) + 32 * bpv * c * n
+        out = np.empty(cap, dtype=np.uint8)
+        offs = (C.c_int64 * (nf + 1))()
+        check(self.lib.pcc_attr_encode_frames(self.ctx, _ptr(values), (C.c_int64 * nf)(*value_offsets),
+                                              (C.c_int32 * nf)(*formats), (C.c_int64 * (nf + 1))(*row_offsets),
+                                              (C.c_int64 * nf)(*points), nf, _ptr(perm), _ptr(run_starts), n_unique,
+                                              _np_ptr(out), cap, offs), "pcc_attr_encode_frames")
+        return [out[offs[f]:offs[f + 1]].tobytes() for f in range(nf)]
+
+    def attr_decode_frames(self, blobs, points=None, device=False):
+        """attribute blobs -> one [n_f, c_f] array per blob in its dtype (uint8 / uint16), row i belonging to decoded
+        point i (pcc_attr_decode_frames): numpy arrays, or views of one device tensor (device=True).  points[f]
+        (optional): frame f's geometry point count, checked against the blob before anything is launched."""
+        nb = len(blobs)
+        if nb == 0:
+            return []
+        bufs = [np.frombuffer(b, dtype=np.uint8) for b in blobs]
+        ptrs = (C.c_void_p * nb)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
+        lens = (C.c_int64 * nb)(*[b.shape[0] for b in bufs])
+        pts = (C.c_int64 * nb)(*points) if points is not None else None
+        offs = (C.c_int64 * (nb + 1))()
+        fmt = (C.c_int32 * nb)()
+        check(self.lib.pcc_attr_decode_frames(self.ctx, ptrs, lens, nb, pts, None, None, 0, offs, fmt),
+              "pcc_attr_decode_frames")
+        total = offs[nb]
+        if device:
+            out = self.empty((max(total, 16),), torch.uint8)
+            if total:
+                check(self.lib.pcc_attr_decode_frames(self.ctx, ptrs, lens, nb, pts, _ptr(out), None, total, offs, fmt),
+                      "pcc_attr_decode_frames")
+        else:   # pinned: the library copies the values straight into it
+            out = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True).numpy()
+            if total:
+                check(self.lib.pcc_attr_decode_frames(self.ctx, ptrs, lens, nb, pts, None, _np_ptr(out), total, offs, fmt),
+                      "pcc_attr_decode_frames")
+        res = []
+        for f in range(nb):
+            bpv, c = fmt[f] & 0xFF, fmt[f] >> 8
+            n = struct.unpack_from("<I", blobs[f], 4)[0]
+            seg = out[offs[f]:offs[f] + n * c * bpv]
+            if device:
+                res.append(seg.view(torch.uint8 if bpv == 1 else torch.uint16).reshape(n, c))
+            else:
+                res.append(seg.view(np.uint8 if bpv == 1 else np.uint16).reshape(n, c))
+        return res
 
 
 OCTREE_V2_MIN_LEAVES = 65536     # include/pcc.h PCC_OCTREE_V2_MIN_LEAVES

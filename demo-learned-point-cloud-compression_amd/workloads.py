@@ -124,6 +124,20 @@ def lidar_sweep(n_beams=64, n_az=1800, seed=0, voxel=0.02):
     return frame(pts, rng)
 
 
+def lidar_intensity(points, seed=0):
+    """intensity (reflectance) of a sweep's points, uint8 [n]: range r = 0.02 |p| metres; reflectivity 0.3 on the ground
+    (0.02 z < -1.55), else a seeded uniform value in [0.1, 0.9] per 2-m cell floor(p / 100);
+    I = clip(rint(255 rho exp(-r / 60) + N(0, 2)), 0, 255)"""
+    p = np.asarray(points, dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    r = 0.02 * np.linalg.norm(p, axis=1)
+    cells, inv = np.unique(np.floor(p / 100).astype(np.int64), axis=0, return_inverse=True)
+    rho = rng.uniform(0.1, 0.9, cells.shape[0])[inv.reshape(-1)]
+    rho = np.where(0.02 * p[:, 2] < -1.55, 0.3, rho)
+    i = np.rint(255 * rho * np.exp(-r / 60) + rng.normal(0, 2, p.shape[0]))
+    return np.clip(i, 0, 255).astype(np.uint8)
+
+
 def body(n_target=800_000, bits=10, seed=0):
     """C4: 8iVFB-like dense closed surface on a 2^bits grid (union of ellipsoids), RGB texture"""
     rng = np.random.default_rng(seed)

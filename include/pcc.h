@@ -626,6 +626,56 @@ int pcc_octree_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs,
                              int32_t* d_points, int32_t* h_points,
                              int64_t cap_points, int64_t* h_point_offsets);
 
+/* Lossless per-point attributes of such a sequence (csrc/attr.hip: attribute
+ * blob version 1, one per frame, its layout in that file's header): uint8 or
+ * uint16 values, 1 <= c <= 4 channels, in the Morton order of the frame's
+ * decoded points.  The blob depends on the geometry only through the point
+ * count n.  Encode: one launch each of merge, counting pass, coder and packing
+ * for all frames, one synchronisation (blob lengths); decode: one launch, one
+ * synchronisation.
+ *   _encode_frames : the rows of the call's pcc_octree_encode_frames before
+ *     duplicates were dropped.  h_rows (n_frames+1 entries, h_rows[0] = 0):
+ *     frame f is rows h_rows[f] .. h_rows[f+1] of the call's keys;
+ *     d_values + h_value_offsets[f] holds its values as rows [rows_f, c_f] of
+ *     h_format[f] = bytes per value (1 | 2) | c_f << 8, little-endian.
+ *     d_perm = the permutation pcc_sort_pairs returned for those keys (frame
+ *     index as batch index), d_run_starts = pcc_unique_rows' first sorted row
+ *     of every run of equal keys (n_unique entries), h_points[f] = frame f's
+ *     points after the merge (its geometry blob's n; summed: n_unique).
+ *     Duplicates keep per channel the rounded mean (sum + cnt / 2) / cnt.
+ *     Blob f is h_out[h_offsets[f] .. h_offsets[f+1]); a frame without points
+ *     gives the 12-byte empty blob, which still names its dtype and c.  More
+ *     bytes than cap: PCC_E_NOMEM, nothing written.  Fewer than 2^27 rows in
+ *     all, 1 <= n_frames <= 65535; a bad format or counts that do not add up:
+ *     PCC_E_ARG naming the frame.
+ *   _decode_frames : n_frames attribute blobs -> their values: frame f's
+ *     [n_f, c_f] values of h_format[f] (nullable) start at byte
+ *     h_out_offsets[f] (n_frames+1 entries, 16-aligned; the last = bytes
+ *     needed) of d_out (HBM) and / or h_out (host); both NULL = sizes only
+ *     (host parse, nothing launched); more than cap_bytes: PCC_E_NOMEM.
+ *     h_points (nullable): every frame's geometry point count (from
+ *     h_point_offsets of pcc_octree_decode_frames); a blob that announces
+ *     another count is PCC_E_STREAM naming the frame.  Every header is parsed
+ *     and checked on the host (csrc/attr_blob.h) before anything is reserved
+ *     or launched, and what is reserved follows the blobs' lengths; a corrupt
+ *     payload is PCC_E_STREAM naming its frame.  An h_out in pinned host
+ *     memory receives the values straight from the device.
+ * After an error the ctx stays usable.  Device scratch per encoded frame is at
+ * least one chunk: 64 lanes x S c 16 bpv records and as many words (at most
+ * 2 MB per chunk). */
+int pcc_attr_encode_frames(pcc_ctx* ctx, const void* d_values,
+                           const int64_t* h_value_offsets,
+                           const int32_t* h_format, const int64_t* h_rows,
+                           const int64_t* h_points, int n_frames,
+                           const uint32_t* d_perm,
+                           const uint32_t* d_run_starts, int64_t n_unique,
+                           uint8_t* h_out, int64_t cap, int64_t* h_offsets);
+int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs,
+                           const int64_t* h_lens, int n_frames,
+                           const int64_t* h_points, uint8_t* d_out,
+                           uint8_t* h_out, int64_t cap_bytes,
+                           int64_t* h_out_offsets, int32_t* h_format);
+
 /* ---- whole-GOP entry points ------------------------------ */
 
 /* replaces: CompressionPipeline.compress() (sender/encoder/codec_pipeline.py:
