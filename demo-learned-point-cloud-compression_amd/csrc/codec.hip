@@ -113,18 +113,6 @@ struct DevPool {
   }
 };
 
-// hipEvent that cannot leak on an early return
-struct Event {
-  hipEvent_t e = nullptr;
-  int create() { return hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess ? PCC_OK : PCC_E_HIP; }
-  ~Event() {
-    if (e) (void)hipEventDestroy(e);
-  }
-  Event() = default;
-  Event(const Event&) = delete;
-  Event& operator=(const Event&) = delete;
-};
-
 struct Pinned {
   uint8_t* p = nullptr;
   size_t cap = 0;
@@ -245,6 +233,13 @@ struct PccWorkers {
     for (auto& t : th)
       if (t.joinable()) t.join();
   }
+};
+
+// waits for the workers when it leaves scope: their jobs reference the state of the call that started them, and no
+// early return may leave that state while one of them is running
+struct WorkersGuard {
+  PccWorkers* w;
+  ~WorkersGuard() { if (w) w->wait_all(); }
 };
 
 struct pcc_codec {
@@ -1117,33 +1112,298 @@ static void upload_run(pcc_codec* cd, const std::vector<UploadPiece>& pieces, ch
     });
 }
 
-static int encode_gop_impl(pcc_codec* cd, const int32_t* d_coords, const float* d_feats, int64_t n, int n_frames,
-                           const double* h_q, int n_q, pcc_buf* h_out, int64_t* h_k, double* h_stage_s,
-                           const FrameTab* frames_in = nullptr, const HostFrames* host = nullptr) {
-  PCC_REQUIRE(cd && cd->ctx, PCC_E_ARG, "pcc_encode_gop: null codec");
-  PCC_REQUIRE(n > 0 && (frames_in || (d_coords && d_feats)) && n_frames >= 1 && n_frames <= 65535 && h_q && n_q >= 1 &&
-                  n_q <= 64 && h_out,
-              PCC_E_ARG, "pcc_encode_gop: bad argument (n=%lld frames=%d q=%d)", (long long)n, n_frames, n_q);
-  pcc_ctx* ctx = cd->ctx;
-  hipStream_t st = ctx->stream;
+// the first steps of both directions: the previous call's tensors are dead from here on
+static int begin_call(pcc_codec* cd) {
   PCC_HIP(hipSetDevice(cd->device));
-  PCC_TRY(pcc_sync(ctx));  // the previous call's tensors are dead from here on
-  // ... and so are its colour uploads: a call that left early (duplicate coordinates, a coordinate out of range) may have
-  // returned with DMAs of cd->up_stream still writing into pool memory
+  PCC_TRY(pcc_sync(cd->ctx));
+  // ... and so are its colour uploads: an encode that left early (duplicate coordinates, a coordinate out of range) may
+  // have returned with DMAs of cd->up_stream still writing into pool memory
   if (cd->up_stream) PCC_HIP(hipStreamSynchronize(cd->up_stream));
   if (cd->side_stream) PCC_HIP(hipStreamSynchronize(cd->side_stream));   // likewise
   cd->pool.reset();
   cd->events_used = 0;
   cd->sets.clear();
-  cd->out.assign((size_t)n_q, {});
-  const int cy = cd->c_y, cz = cd->c_z;
-  double ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double t0 = now_s();
+  return PCC_OK;
+}
 
-  // ---- unpack_batch: SparseTensor(coordinates, features) -> Morton-sorted rows
-  Feat x;
+// runs one stage of a call and adds its wall time to *clock (a slot of h_stage_s)
+template <class F>
+static int timed(double* clock, F&& stage) {
+  const double t0 = now_s();
+  const int rc = stage();
+  *clock += now_s() - t0;
+  return rc;
+}
+
+namespace {
+
+// one octree blob (or one part of a version-3 blob) from its occupancy bytes in pinned memory; an empty one has no levels
+int pack_octree(const uint8_t* occ, const std::vector<int64_t>& level_n, int depth, int64_t n, const int32_t origin[3],
+                int64_t nodes, std::vector<uint8_t>* out) {
+  const int64_t zero = 0;
+  const int32_t org0[3] = {0, 0, 0};
+  out->resize((size_t)(64 + 2 * nodes + 16));
+  int64_t len = 0;
+  const int rc = pcc_octree_pack(n ? occ : nullptr, n ? level_n.data() : &zero, n ? depth : 0, n, n ? origin : org0,
+                                 out->data(), (int64_t)out->size(), &len);
+  out->resize((size_t)(rc == PCC_OK ? len : 0));
+  return rc;
+}
+
+// ---- step 6: geometry slot of every frame (codec_pipeline.py:441-462).  Nothing on the GPU path needs it: it runs on
+// the caller's thread after the y symbols are on their way to the coder threads, its kernels queue up behind the
+// quantiser instead of in front of h_a, and its host half (occupancy coding, z string) overlaps the y coders.
+struct GeoSlotEncoder {
+  struct Frame {
+    int64_t n = 0, occ_off = 0, occ_len = 0, cap = 0;
+    int depth = 0;
+    int32_t origin[3] = {0, 0, 0};
+    std::vector<int64_t> level_n;
+    std::vector<uint8_t> v2;   // a frame whose blob the device half finished: version 2 (octree2.hip), or version 3 on the synchronous path
+    // blob version 3 (PCC_OCTREE_V3_MIN_LEAVES leaves and more): the frame's leaves in K parts under the frame's root
+    struct Part {
+      int64_t n = 0, occ_off = 0, nodes = 0;
+      std::vector<int64_t> level_n;
+    };
+    int K = 1;
+    int counts_at = 0;   // first counts block of the frame (kCounts words each, one per part)
+    std::vector<Part> parts;
+  };
+  static constexpr int kCounts = 20;  // uint32 per frame in the counts block (depth + 1 <= 17 used)
+  pcc_codec* cd = nullptr;
+  const CS* ycs = nullptr;           // the latents, frame after frame
+  const std::vector<int64_t>* yoffs = nullptr;
+  const uint64_t* ends = nullptr;    // first / last input key of every frame, when the frames came as a table
+  std::vector<Frame> fr;
+  int n_blocks = 0;
+  // Asynchronous form — every frame's latent within the single-workgroup octree kernel and the frames' end keys on the
+  // host since the sort: the octree kernels are queued and an event recorded, nothing waits.  The kernels write their
+  // (small) output — occupancy bytes and level counts — straight into pinned host memory; finish() waits for the event.
+  bool small = false, queued = false, async = false;
+  hipEvent_t ev = nullptr;
+  double dev_s = 0, host_s = 0;
+  void init(pcc_codec* c, int nf, const CS* y, const std::vector<int64_t>* offs, const std::vector<uint64_t>& root_keys) {
+    cd = c;
+    ycs = y;
+    yoffs = offs;
+    ends = root_keys.data();
+    fr.resize((size_t)nf);
+    small = (int)root_keys.size() == 2 * nf;
+    for (int f = 0; f < nf; ++f) small &= (*offs)[f + 1] - (*offs)[f] <= pcc_octree_small_max();
+  }
+  // leaf count, root cube and room of every frame's slot (roots from the end keys, or from keys_h: the keys on the host)
+  int64_t layout(const uint64_t* keys_h) {
+    int64_t total = 0;
+    for (int f = 0; f < (int)fr.size(); ++f) {
+      Frame& g = fr[f];
+      g.n = (*yoffs)[f + 1] - (*yoffs)[f];
+      g.occ_off = total;
+      if (small) {
+        g.K = g.n >= PCC_OCTREE_V3_MIN_LEAVES ? pcc_octree_parts_for(g.n) : 1;
+        g.counts_at = n_blocks;
+        n_blocks += g.K;
+      }
+      if (g.n == 0) continue;
+      octree_root(small ? ends[2 * f] : keys_h[(*yoffs)[f]], small ? ends[2 * f + 1] : keys_h[(*yoffs)[f + 1] - 1], 9,
+                  &g.depth, g.origin);
+      g.cap = small ? (g.n * g.depth + 4 * g.K + 4 + 255) & ~(int64_t)255 : g.n * g.depth;
+      total += g.cap;
+    }
+    return total;
+  }
+  // queues the device half, once; gctx: where the asynchronous form queues its kernels
+  int device_half(pcc_ctx* gctx) {
+    if (queued) return PCC_OK;
+    queued = true;
+    const double tg = now_s();
+    if (small) {
+      const int64_t cap_total = layout(nullptr);
+      PCC_TRY(cd->pin_occ.ensure((size_t)std::max<int64_t>(cap_total, 1)));
+      PCC_TRY(cd->pin_keys.ensure((size_t)kCounts * 4 * n_blocks));
+      if (!ev) PCC_TRY(call_event(cd, &ev));
+      for (int f = 0; f < (int)fr.size(); ++f) {
+        Frame& g = fr[f];
+        if (g.n == 0) continue;
+        // the kernel writes its (small) output straight into the pinned host buffers — they are device-accessible —
+        // so the slot needs no transfer of its own
+        if (g.K > 1)
+          PCC_TRY(pcc_octree_parts_async(gctx, ycs->keys + (*yoffs)[f], g.n, 9, g.depth, g.K, cd->pin_occ.p + g.occ_off,
+                                         g.cap, (uint32_t*)cd->pin_keys.p + kCounts * g.counts_at, kCounts));
+        else
+          PCC_TRY(pcc_octree_small_async(gctx, ycs->keys + (*yoffs)[f], g.n, 9, g.depth, cd->pin_occ.p + g.occ_off, g.cap,
+                                         (uint32_t*)cd->pin_keys.p + kCounts * g.counts_at));
+      }
+      PCC_HIP(hipEventRecord(ev, gctx->stream));
+      async = true;
+      dev_s = now_s() - tg;
+      return PCC_OK;
+    }
+    // synchronous form: the latents' keys come to the host first
+    pcc_ctx* ctx = cd->ctx;
+    hipStream_t st = ctx->stream;
+    PCC_TRY(cd->pin_keys.ensure((size_t)std::max<int64_t>(ycs->n, 1) * 8));
+    if (ycs->n > 0) PCC_HIP(hipMemcpyAsync(cd->pin_keys.p, ycs->keys, (size_t)ycs->n * 8, hipMemcpyDeviceToHost, st));
+    PCC_HIP(hipStreamSynchronize(st));
+    const int64_t cap_total = layout((const uint64_t*)cd->pin_keys.p);
+    CODEC_ALLOC(occ, uint8_t, std::max<int64_t>(cap_total, 1));
+    PCC_TRY(cd->pin_occ.ensure((size_t)std::max<int64_t>(cap_total, 1)));
+    for (int f = 0; f < (int)fr.size(); ++f) {
+      Frame& g = fr[f];
+      if (g.n == 0) continue;
+      // blob version 2 (levels AND entropy coder on the GPU) above PCC_OCTREE_V2_MIN_LEAVES leaves, else version 3 on
+      // this (synchronous) path: the one-call form
+      if (g.n >= PCC_OCTREE_V3_MIN_LEAVES) {
+        const bool v2 = g.n > PCC_OCTREE_V2_MIN_LEAVES;
+        const int64_t cap2 = v2 ? 4096 + 17 * g.n : 4096 + 3 * g.n * g.depth;
+        int64_t len2 = 0;
+        g.v2.resize((size_t)cap2);
+        PCC_TRY(v2 ? pcc_octree2_encode(ctx, ycs->keys + (*yoffs)[f], g.n, 9, g.depth, g.origin, g.v2.data(), cap2, &len2)
+                   : pcc_octree_encode_version(ctx, ycs->keys + (*yoffs)[f], g.n, 9, 3, g.v2.data(), cap2, &len2));
+        g.v2.resize((size_t)len2);
+        continue;
+      }
+      g.level_n.assign((size_t)g.depth, 0);
+      PCC_TRY(pcc_octree_levels(ctx, ycs->keys + (*yoffs)[f], g.n, 9, g.depth, occ + g.occ_off, g.n * g.depth,
+                                g.level_n.data()));
+      for (int64_t v : g.level_n) g.occ_len += v;
+      PCC_HIP(hipMemcpyAsync(cd->pin_occ.p + g.occ_off, occ + g.occ_off, (size_t)g.occ_len, hipMemcpyDeviceToHost, st));
+    }
+    PCC_HIP(hipStreamSynchronize(st));  // occupancy bytes and (earlier in the stream) the z symbols are on the host
+    dev_s = now_s() - tg;
+    return PCC_OK;
+  }
+  // the device half has arrived (asynchronous form): level counts, and the occupancy bytes the guess did not cover
+  int arrived() {
+    if (!async) return PCC_OK;
+    PCC_HIP(hipEventSynchronize(ev));
+    const uint32_t* hc = (const uint32_t*)cd->pin_keys.p;
+    for (int f = 0; f < (int)fr.size(); ++f) {
+      Frame& g = fr[f];
+      if (g.n == 0) continue;
+      if (g.K > 1) {   // parts: leaf counts first (they place the parts' bytes), then the level counts of each
+        g.parts.assign((size_t)g.K, Frame::Part());
+        int64_t start = 0;
+        for (int k = 0; k < g.K; ++k) {
+          const uint32_t* c = hc + kCounts * (g.counts_at + k);
+          Frame::Part& pt = g.parts[(size_t)k];
+          pt.n = (int64_t)c[g.depth];
+          pt.occ_off = g.occ_off + (int64_t)((((uint64_t)start * (uint64_t)g.depth) + 3) & ~(uint64_t)3) + 4 * k;
+          pt.level_n.assign((size_t)g.depth, 0);
+          for (int L = 0; L < g.depth && pt.n > 0; ++L) {
+            pt.level_n[L] = (int64_t)c[L];
+            pt.nodes += pt.level_n[L];
+          }
+          PCC_REQUIRE(start + pt.n <= g.n && pt.nodes <= pt.n * g.depth && (pt.n == 0 || pt.level_n[0] == 1), PCC_E_ARG,
+                      "pcc_encode_gop: octree of frame %d, part %d: %lld leaves behind %lld of %lld, %lld nodes", f, k,
+                      (long long)pt.n, (long long)start, (long long)g.n, (long long)pt.nodes);
+          start += pt.n;
+        }
+        PCC_REQUIRE(start == g.n, PCC_E_ARG, "pcc_encode_gop: octree of frame %d: its parts hold %lld of %lld leaves", f,
+                    (long long)start, (long long)g.n);
+        continue;
+      }
+      g.level_n.assign((size_t)g.depth, 0);
+      for (int L = 0; L < g.depth; ++L) {
+        g.level_n[L] = (int64_t)hc[kCounts * g.counts_at + L];
+        g.occ_len += g.level_n[L];
+      }
+      PCC_REQUIRE(g.level_n[0] == 1 && g.occ_len <= g.n * g.depth, PCC_E_ARG,
+                  "pcc_encode_gop: octree of frame %d: %lld root nodes, %lld nodes for %lld leaves", f,
+                  (long long)g.level_n[0], (long long)g.occ_len, (long long)g.n);
+    }
+    return PCC_OK;
+  }
+  // the host half: every frame's blob.  threads: the codec's threads are free to take the parts of a version-3 blob
+  // (container version 1; in version 0 they are coding the y strings while this runs)
+  int finish(bool threads, std::vector<std::vector<uint8_t>>& blobs) {
+    PCC_TRY(arrived());
+    const double t = now_s();
+    for (int f = 0; f < (int)fr.size(); ++f) {
+      Frame& g = fr[f];
+      if (!g.v2.empty()) {
+        blobs[f].swap(g.v2);
+        continue;
+      }
+      if (g.K == 1 || g.parts.empty()) {
+        PCC_TRY(pack_octree(cd->pin_occ.p + g.occ_off, g.level_n, g.depth, g.n, g.origin, g.occ_len, &blobs[f]));
+        continue;
+      }
+      // blob version 3: the parts' coders side by side where threads are free
+      std::vector<std::vector<uint8_t>> pb((size_t)g.K);
+      std::vector<int> prc((size_t)g.K, PCC_OK);
+      std::vector<std::string> perr((size_t)g.K);
+      auto pack_part = [&](int k) {
+        const Frame::Part& pt = g.parts[(size_t)k];
+        prc[(size_t)k] = pack_octree(cd->pin_occ.p + pt.occ_off, pt.level_n, g.depth, pt.n, g.origin, pt.nodes,
+                                     &pb[(size_t)k]);
+        if (prc[(size_t)k] != PCC_OK) perr[(size_t)k] = pcc_last_error();
+      };
+      if (threads) {
+        cd->workers.ensure(g.K - 1);
+        for (int k = 1; k < g.K; ++k) cd->workers.run(k - 1, [&pack_part, k]() { pack_part(k); });
+        pack_part(0);
+        cd->workers.wait_all();
+      } else {
+        for (int k = 0; k < g.K; ++k) pack_part(k);
+      }
+      for (int k = 0; k < g.K; ++k)
+        if (prc[(size_t)k] != PCC_OK) {
+          pcc_set_error("pcc_encode_gop (geometry, frame %d part %d): %s", f, k, perr[(size_t)k].c_str());
+          return prc[(size_t)k];
+        }
+      int64_t tot = 64 + 4 * g.K;
+      for (const auto& b : pb) tot += (int64_t)b.size();
+      blobs[f].resize((size_t)tot);
+      int64_t len = 0;
+      PCC_TRY(pcc_octree_join_parts(g.depth, g.origin, g.n, pb.data(), g.K, blobs[f].data(), tot, &len));
+      blobs[f].resize((size_t)len);
+    }
+    host_s = now_s() - t;
+    return PCC_OK;
+  }
+};
+
+struct EncodeCall {
+  pcc_codec* cd;
+  pcc_ctx* ctx;
+  hipStream_t st;
+  const double* h_q;
+  int n_frames, n_q, cy, cz;
+  bool v1 = false;   // y / z strings coded on the GPU (rans_gpu.hip), flagged container
+  pcc_ctx* side = nullptr;
+  double ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  Feat x, y, z, z_hat, gp;
+  View yv, zv;
+  int64_t ny = 0, nz = 0;
+  float* ys_f = nullptr;
+  int32_t* zsym_dev = nullptr;
+  const std::vector<int64_t>* yoffs = nullptr;
   std::vector<uint64_t> root_keys;  // first / last input key of every frame, when the frames came as a table
-  {
+  std::vector<int64_t> counts[3];   // rows of every frame at strides 1, 2, 4
+  GeoSlotEncoder geo;
+  // version 1: room of the coded strings in pinned memory, their lengths on the device, the z coder's end on the side stream
+  int64_t cap_y = 0, cap_z = 0;
+  long long* d_lens = nullptr;
+  hipEvent_t z_done = nullptr;
+  const Tensor *eb_cdf = nullptr, *eb_len = nullptr, *eb_off = nullptr;
+  const Tensor *gc_cdf = nullptr, *gc_len = nullptr, *gc_off = nullptr;
+  std::vector<std::vector<uint8_t>> blobs, y_strings;   // y_strings: version 1 and the int16-overflow path fill these
+  std::vector<uint8_t> z_string, head_done;
+  std::vector<int64_t> seek_idx;                     // seek points of the y strings (cd->seek_points; version 0 only)
+  std::vector<std::vector<uint64_t>> seek_state;     // [quality][point]
+  std::vector<std::vector<int64_t>> seek_word;
+  // version 0: the pieces of the symbol arrays the y coders wait for (events evc), the coders' results
+  int n_chunks = 1;
+  std::vector<int64_t> bound;
+  std::vector<hipEvent_t> evc;
+  std::vector<int> rcq;
+  std::vector<std::string> errq;
+  double helper_z_s = 0;
+  EncodeCall(pcc_codec* c, int nf, const double* q, int nq)
+      : cd(c), ctx(c->ctx), st(c->ctx->stream), h_q(q), n_frames(nf), n_q(nq), cy(c->c_y), cz(c->c_z),
+        blobs((size_t)nf), y_strings((size_t)nq), head_done((size_t)nq, 0) {}
+  // ---- unpack_batch: SparseTensor(coordinates, features) -> Morton-sorted rows
+  int unpack(int64_t n, const int32_t* d_coords, const float* d_feats, const FrameTab* frames_in, const HostFrames* host) {
     CODEC_ALLOC(keys, uint64_t, n);
     CODEC_ALLOC(flag, int32_t, 1);
     CODEC_ALLOC(perm, uint32_t, n);
@@ -1153,12 +1413,7 @@ static int encode_gop_impl(pcc_codec* cd, const int32_t* d_coords, const float* 
     const FrameTab* frames = frames_in;
     std::vector<UploadPiece> col_pieces;
     std::atomic<int> up_status{0};
-    struct WaitWorkers {  // the upload jobs read this frame's locals: no way out of the block with one of them running
-      PccWorkers* w = nullptr;
-      ~WaitWorkers() { if (w) w->wait_all(); }
-    } up_guard;
-    char* dc = nullptr;
-    size_t pts_bytes = 0;
+    WorkersGuard up_guard{nullptr};   // the upload jobs read this frame's locals: no way out with one of them running
     if (host) {
       // the frame arrays are host memory: points first (6 B per point), keys + sort are queued behind them, and the
       // colours (float32 from here on) cross PCIe on cd->up_stream while the GPU sorts and builds the rule books
@@ -1170,7 +1425,7 @@ static int encode_gop_impl(pcc_codec* cd, const int32_t* d_coords, const float* 
       ftab = *frames_in;
       const size_t pb = ftab.pts_i16 ? 6 : 12, cb = 12;
       char* dp = (char*)cd->pool.alloc((size_t)n * pb + 256 * (size_t)ftab.nf);
-      dc = (char*)cd->pool.alloc((size_t)n * cb + 256 * (size_t)ftab.nf);
+      char* dc = (char*)cd->pool.alloc((size_t)n * cb + 256 * (size_t)ftab.nf);
       if (!dp || !dc) return PCC_E_NOMEM;
       std::vector<UploadPiece> pt_pieces;
       size_t po = 0, co = 0;
@@ -1180,7 +1435,7 @@ static int encode_gop_impl(pcc_codec* cd, const int32_t* d_coords, const float* 
         upload_pieces(&pt_pieces, po, host->pts[f], nf * pb, 0);
         po += (nf * pb + 255) & ~(size_t)255;
       }
-      pts_bytes = po;
+      const size_t pts_bytes = po;
       for (int f = 0; f < ftab.nf; ++f) {  // colours staged behind the points
         const size_t nf = (size_t)(ftab.off[f + 1] - ftab.off[f]);
         ftab.cols[f] = dc + co;
@@ -1241,238 +1496,62 @@ static int encode_gop_impl(pcc_codec* cd, const int32_t* d_coords, const float* 
       hipLaunchKernelGGL(k_frames_feats, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *frames,
                          (const uint32_t*)perm, n, (float4*)f);
       PCC_CHECK_LAUNCH();
-    } else {
-      PCC_TRY(pcc_gather_rows(ctx, d_feats, perm, n, 16, f));
-    }
-  }
-
-  // ---- step 1: analysis g_a + canonical order of y (codec_pipeline.py:270-281)
-  std::vector<std::vector<int64_t>> counts(3);
-  Feat h = x, y;
-  for (int j = 0; j < 3; ++j) {
-    const std::vector<int64_t>* offs;
-    PCC_TRY(offsets_of(cd, h.cs, &offs));
-    for (int f = 0; f < n_frames; ++f) counts[j].push_back((*offs)[f + 1] - (*offs)[f]);
-    Feat a, b;
-    PCC_TRY(conv3(cd, "g_a.conv" + std::to_string(j), h, 1, &a));
-    PCC_TRY(down2(cd, "g_a.down" + std::to_string(j), a, 1, &b));
-    h = b;
-  }
-  PCC_TRY(conv3(cd, "g_a.conv3", h, 0, &y));
-  // k[scale][frame]: strides 4, 2, 1 (coarse -> fine)
-  const std::vector<int64_t>* kk[3] = {&counts[2], &counts[1], &counts[0]};
-  if (h_k)
-    for (int s = 0; s < 3; ++s)
-      for (int f = 0; f < n_frames; ++f) h_k[s * n_frames + f] = (*kk[s])[f];
-  const int64_t ny = y.cs->n;
-  View yv;
-  PCC_TRY(view_of(cd, y.cs, &yv));
-  CODEC_ALLOC(ys_f, float, std::max<int64_t>(ny, 1) * cy);
-  if (ny > 0) PCC_TRY(pcc_gather_rows(ctx, y.f, yv.perm, ny, 4 * cy, ys_f));
-  const std::vector<int64_t>* yoffs;
-  PCC_TRY(offsets_of(cd, y.cs, &yoffs));
-  ts[0] = now_s() - t0;
-
-  // ---- step 6: geometry slot of every frame (codec_pipeline.py:441-462).  Nothing on the GPU path needs it, so it is
-  // only DEFINED here: it runs on this thread after the y symbols are on their way to the coder threads (below), its
-  // kernels queue up behind the quantiser instead of in front of h_a, and its host half (occupancy coding, z string)
-  // overlaps the y coders.
-  struct FrameGeo {
-    int64_t n, occ_off, occ_len;
-    int depth;
-    int32_t origin[3];
-    std::vector<int64_t> level_n;
-    std::vector<uint8_t> v2;   // a frame whose blob the device half finished: version 2 (octree2.hip), or version 3 on the synchronous path
-    // blob version 3 (PCC_OCTREE_V3_MIN_LEAVES leaves and more): the frame's leaves in K parts under the frame's root
-    struct Part {
-      int64_t n = 0, occ_off = 0, nodes = 0;
-      std::vector<int64_t> level_n;
-    };
-    int K = 1;
-    int counts_at = 0;   // first counts block of the frame (kGeoCounts words each, one per part)
-    std::vector<Part> parts;
-  };
-  std::vector<FrameGeo> geo((size_t)n_frames);
-  double geo_dev_s = 0;
-  // Asynchronous form — every frame's latent within the single-workgroup octree kernel and the frames' end keys on the
-  // host since the sort: the octree kernels are queued and an event recorded, nothing waits.  The kernels write their
-  // (small) output — occupancy bytes and level counts — straight into pinned host memory; geometry_finish() waits for
-  // the event.
-  bool geo_async = false;
-  hipEvent_t geo_ev = nullptr;
-  std::vector<int64_t> geo_cap((size_t)n_frames, 0);
-  constexpr int kGeoCounts = 20;  // uint32 per frame in the counts block (depth + 1 <= 17 used)
-  bool geo_small = (int)root_keys.size() == 2 * n_frames;
-  for (int f = 0; f < n_frames; ++f) geo_small &= (*yoffs)[f + 1] - (*yoffs)[f] <= pcc_octree_small_max();
-  bool geo_queued = false;
-  auto geometry_device_half = [&](pcc_ctx* gctx) -> int {   // gctx: where the asynchronous form queues its kernels
-    if (geo_queued) return PCC_OK;
-    geo_queued = true;
-    const double tg = now_s();
-    const bool small = geo_small;
-    if (small) {
-      int64_t cap_total = 0;
-      int n_blocks = 0;
-      for (int f = 0; f < n_frames; ++f) {
-        FrameGeo& g = geo[f];
-        g.n = (*yoffs)[f + 1] - (*yoffs)[f];
-        g.depth = 0;
-        g.occ_off = cap_total;
-        g.occ_len = 0;
-        g.origin[0] = g.origin[1] = g.origin[2] = 0;
-        g.K = g.n >= PCC_OCTREE_V3_MIN_LEAVES ? pcc_octree_parts_for(g.n) : 1;
-        g.counts_at = n_blocks;
-        n_blocks += g.K;
-        if (g.n > 0) {
-          octree_root(root_keys[2 * f], root_keys[2 * f + 1], 9, &g.depth, g.origin);
-          geo_cap[f] = (g.n * g.depth + 4 * g.K + 4 + 255) & ~(int64_t)255;
-          cap_total += geo_cap[f];
-        }
-      }
-      PCC_TRY(cd->pin_occ.ensure((size_t)std::max<int64_t>(cap_total, 1)));
-      PCC_TRY(cd->pin_keys.ensure((size_t)kGeoCounts * 4 * n_blocks));
-      if (!geo_ev) PCC_TRY(call_event(cd, &geo_ev));
-      for (int f = 0; f < n_frames; ++f) {
-        FrameGeo& g = geo[f];
-        if (g.n == 0) continue;
-        // the kernel writes its (small) output straight into the pinned host buffers — they are device-accessible —
-        // so the slot needs no transfer of its own
-        if (g.K > 1)
-          PCC_TRY(pcc_octree_parts_async(gctx, y.cs->keys + (*yoffs)[f], g.n, 9, g.depth, g.K, cd->pin_occ.p + g.occ_off,
-                                         geo_cap[f], (uint32_t*)cd->pin_keys.p + kGeoCounts * g.counts_at, kGeoCounts));
-        else
-          PCC_TRY(pcc_octree_small_async(gctx, y.cs->keys + (*yoffs)[f], g.n, 9, g.depth, cd->pin_occ.p + g.occ_off, geo_cap[f],
-                                         (uint32_t*)cd->pin_keys.p + kGeoCounts * g.counts_at));
-      }
-      PCC_HIP(hipEventRecord(geo_ev, gctx->stream));
-      geo_async = true;
-      geo_dev_s = now_s() - tg;
       return PCC_OK;
     }
-    PCC_TRY(cd->pin_keys.ensure((size_t)std::max<int64_t>(ny, 1) * 8));
-    if (ny > 0) PCC_HIP(hipMemcpyAsync(cd->pin_keys.p, y.cs->keys, (size_t)ny * 8, hipMemcpyDeviceToHost, st));
-    PCC_HIP(hipStreamSynchronize(st));
-    const uint64_t* ykeys_h = (const uint64_t*)cd->pin_keys.p;
-    int64_t cap_total = 0;
-    for (int f = 0; f < n_frames; ++f) {
-      FrameGeo& g = geo[f];
-      g.n = (*yoffs)[f + 1] - (*yoffs)[f];
-      g.depth = 0;
-      g.occ_off = cap_total;
-      g.occ_len = 0;
-      g.origin[0] = g.origin[1] = g.origin[2] = 0;
-      if (g.n > 0) {
-        octree_root(ykeys_h[(*yoffs)[f]], ykeys_h[(*yoffs)[f + 1] - 1], 9, &g.depth, g.origin);
-        cap_total += g.n * g.depth;
-      }
+    return pcc_gather_rows(ctx, d_feats, perm, n, 16, f);
+  }
+  // ---- step 1: analysis g_a + canonical order of y (codec_pipeline.py:270-281)
+  int analysis(int64_t* h_k) {
+    Feat h = x;
+    for (int j = 0; j < 3; ++j) {
+      const std::vector<int64_t>* offs;
+      PCC_TRY(offsets_of(cd, h.cs, &offs));
+      for (int f = 0; f < n_frames; ++f) counts[j].push_back((*offs)[f + 1] - (*offs)[f]);
+      Feat a, b;
+      PCC_TRY(conv3(cd, "g_a.conv" + std::to_string(j), h, 1, &a));
+      PCC_TRY(down2(cd, "g_a.down" + std::to_string(j), a, 1, &b));
+      h = b;
     }
-    CODEC_ALLOC(occ, uint8_t, std::max<int64_t>(cap_total, 1));
-    PCC_TRY(cd->pin_occ.ensure((size_t)std::max<int64_t>(cap_total, 1)));
-    for (int f = 0; f < n_frames; ++f) {
-      FrameGeo& g = geo[f];
-      if (g.n == 0) continue;
-      if (g.n > PCC_OCTREE_V2_MIN_LEAVES) {   // blob version 2: levels AND entropy coder on the GPU
-        const int64_t cap2 = 4096 + 17 * g.n;
-        int64_t len2 = 0;
-        g.v2.resize((size_t)cap2);
-        PCC_TRY(pcc_octree2_encode(ctx, y.cs->keys + (*yoffs)[f], g.n, 9, g.depth, g.origin, g.v2.data(), cap2, &len2));
-        g.v2.resize((size_t)len2);
-        continue;
-      }
-      if (g.n >= PCC_OCTREE_V3_MIN_LEAVES) {   // blob version 3 on this (synchronous) path: the one-call form
-        const int64_t cap3 = 4096 + 3 * g.n * g.depth;
-        int64_t len3 = 0;
-        g.v2.resize((size_t)cap3);
-        PCC_TRY(pcc_octree_encode_version(ctx, y.cs->keys + (*yoffs)[f], g.n, 9, 3, g.v2.data(), cap3, &len3));
-        g.v2.resize((size_t)len3);
-        continue;
-      }
-      g.level_n.assign((size_t)g.depth, 0);
-      PCC_TRY(pcc_octree_levels(ctx, y.cs->keys + (*yoffs)[f], g.n, 9, g.depth, occ + g.occ_off, g.n * g.depth,
-                                g.level_n.data()));
-      for (int64_t v : g.level_n) g.occ_len += v;
-      PCC_HIP(hipMemcpyAsync(cd->pin_occ.p + g.occ_off, occ + g.occ_off, (size_t)g.occ_len, hipMemcpyDeviceToHost, st));
-    }
-    PCC_HIP(hipStreamSynchronize(st));  // occupancy bytes and (earlier in the stream) the z symbols are on the host
-    geo_dev_s = now_s() - tg;
-    return PCC_OK;
-  };
-  // the device half has arrived (asynchronous form): level counts, and the occupancy bytes the guess did not cover
-  auto geometry_arrived = [&]() -> int {
-    if (!geo_async) return PCC_OK;
-    PCC_HIP(hipEventSynchronize(geo_ev));
-    const uint32_t* hc = (const uint32_t*)cd->pin_keys.p;
-    for (int f = 0; f < n_frames; ++f) {
-      FrameGeo& g = geo[f];
-      if (g.n == 0) continue;
-      if (g.K > 1) {   // parts: leaf counts first (they place the parts' bytes), then the level counts of each
-        g.parts.assign((size_t)g.K, FrameGeo::Part());
-        int64_t start = 0;
-        for (int k = 0; k < g.K; ++k) {
-          const uint32_t* c = hc + kGeoCounts * (g.counts_at + k);
-          FrameGeo::Part& pt = g.parts[(size_t)k];
-          pt.n = (int64_t)c[g.depth];
-          pt.occ_off = g.occ_off + (int64_t)((((uint64_t)start * (uint64_t)g.depth) + 3) & ~(uint64_t)3) + 4 * k;
-          pt.level_n.assign((size_t)g.depth, 0);
-          for (int L = 0; L < g.depth && pt.n > 0; ++L) {
-            pt.level_n[L] = (int64_t)c[L];
-            pt.nodes += pt.level_n[L];
-          }
-          PCC_REQUIRE(start + pt.n <= g.n && pt.nodes <= pt.n * g.depth && (pt.n == 0 || pt.level_n[0] == 1), PCC_E_ARG,
-                      "pcc_encode_gop: octree of frame %d, part %d: %lld leaves behind %lld of %lld, %lld nodes", f, k,
-                      (long long)pt.n, (long long)start, (long long)g.n, (long long)pt.nodes);
-          start += pt.n;
-        }
-        PCC_REQUIRE(start == g.n, PCC_E_ARG, "pcc_encode_gop: octree of frame %d: its parts hold %lld of %lld leaves", f,
-                    (long long)start, (long long)g.n);
-        continue;
-      }
-      g.level_n.assign((size_t)g.depth, 0);
-      for (int L = 0; L < g.depth; ++L) {
-        g.level_n[L] = (int64_t)hc[kGeoCounts * g.counts_at + L];
-        g.occ_len += g.level_n[L];
-      }
-      PCC_REQUIRE(g.level_n[0] == 1 && g.occ_len <= g.n * g.depth, PCC_E_ARG,
-                  "pcc_encode_gop: octree of frame %d: %lld root nodes, %lld nodes for %lld leaves", f,
-                  (long long)g.level_n[0], (long long)g.occ_len, (long long)g.n);
-    }
-    return PCC_OK;
-  };
-
+    PCC_TRY(conv3(cd, "g_a.conv3", h, 0, &y));
+    // k[scale][frame]: strides 4, 2, 1 (coarse -> fine)
+    if (h_k)
+      for (int s = 0; s < 3; ++s)
+        for (int f = 0; f < n_frames; ++f) h_k[s * n_frames + f] = counts[2 - s][f];
+    ny = y.cs->n;
+    PCC_TRY(view_of(cd, y.cs, &yv));
+    CODEC_ALLOC(ys, float, std::max<int64_t>(ny, 1) * cy);
+    ys_f = ys;
+    if (ny > 0) PCC_TRY(pcc_gather_rows(ctx, y.f, yv.perm, ny, 4 * cy, ys_f));
+    return offsets_of(cd, y.cs, &yoffs);
+  }
   // Container version 1 codes its strings on the GPU; what does not lie on the way to them runs on the codec's second
   // stream: the octree kernel of the latents here — one workgroup, 58 us — beside h_a, the z string's coder (step 3)
   // beside h_s.  Both had been queued in the compute stream, which they held up for their whole length.
-  const bool v1 = cd->container_version == 1;  // y / z strings coded on the GPU (rans_gpu.hip), flagged container
   // (same box, 2 x 30 steps each way: 217.3 / 212.2 frames/s with everything on the compute stream, 222.2 / 224.2 so)
-  pcc_ctx* side = nullptr;
-  if (v1) PCC_TRY(side_of(cd, &side));
-  if (side && geo_small) {
-    hipEvent_t ev_y;
-    PCC_TRY(call_event(cd, &ev_y));
-    PCC_HIP(hipEventRecord(ev_y, st));
-    PCC_HIP(hipStreamWaitEvent(side->stream, ev_y, 0));
-    PCC_TRY(geometry_device_half(side));
+  int start_side() {
+    geo.init(cd, n_frames, y.cs, yoffs, root_keys);
+    v1 = cd->container_version == 1;
+    if (v1) PCC_TRY(side_of(cd, &side));
+    if (side && geo.small) {
+      hipEvent_t ev_y;
+      PCC_TRY(call_event(cd, &ev_y));
+      PCC_HIP(hipEventRecord(ev_y, st));
+      PCC_HIP(hipStreamWaitEvent(side->stream, ev_y, 0));
+      PCC_TRY(geo.device_half(side));
+    }
+    return PCC_OK;
   }
-
   // ---- step 2: hyper analysis h_a
-  t0 = now_s();
-  Feat z;
-  {
+  int hyper_analysis() {
     Feat a, b;
     PCC_TRY(conv3(cd, "h_a.conv0", y, 1, &a));
     PCC_TRY(down2(cd, "h_a.down0", a, 1, &b));
-    PCC_TRY(down2(cd, "h_a.down1", b, 0, &z));
+    return down2(cd, "h_a.down1", b, 0, &z);
   }
-  ts[1] = now_s() - t0;
-
   // ---- step 3: factorized model over the canonically sorted z; z_hat formed on the device
-  t0 = now_s();
-  const int64_t nz = z.cs->n;
-  View zv;
-  PCC_TRY(view_of(cd, z.cs, &zv));
-  Feat z_hat;
-  int32_t* zsym_dev = nullptr;
-  {
+  int factorized() {
+    nz = z.cs->n;
+    PCC_TRY(view_of(cd, z.cs, &zv));
     CODEC_ALLOC(zs_f, float, std::max<int64_t>(nz, 1) * cz);
     CODEC_ALLOC(zsym, int32_t, std::max<int64_t>(nz, 1) * cz);
     CODEC_ALLOC(zhat_rows, float, std::max<int64_t>(nz, 1) * cz);
@@ -1486,132 +1565,47 @@ static int encode_gop_impl(pcc_codec* cd, const int32_t* d_coords, const float* 
     float* zf;
     PCC_TRY(rows_to_tensor(cd, zv, zhat_rows, cz, &zf));
     z_hat = {z.cs, zf, cz};
-  }
-  // version 1: room of the coded strings in pinned memory (first attempt: 6 bytes per symbol; the coder's own first
-  // attempt holds 1.5 words per symbol), and the z string's coder queued on the second stream
-  const int64_t per_y = (int64_t)cy * ny, nzs = (int64_t)cz * nz;
-  int64_t cap_y = 0, cap_z = 0;
-  long long* d_lens = nullptr;
-  hipEvent_t z_done = nullptr;
-  if (v1) {
-    PCC_REQUIRE(cd->gc_dev && cd->eb_dev, PCC_E_ARG, "pcc_encode_gop: container version 1 without device CDF tables");
-    cap_y = std::min<int64_t>(pcc_rans_dev_bound(per_y), (6 * per_y + 65536) / 4 * 4);
-    cap_z = std::min<int64_t>(pcc_rans_dev_bound(nzs), (6 * nzs + 65536) / 4 * 4);
-    PCC_TRY(cd->pin_ysym.ensure((size_t)cap_y * n_q + (size_t)cap_z + 256));
-    d_lens = (long long*)cd->pool.alloc(sizeof(long long) * (size_t)(n_q + 1));
-    if (!d_lens) return PCC_E_NOMEM;
-    if (side) {
-      hipEvent_t ev_z;
-      PCC_TRY(call_event(cd, &ev_z));
-      PCC_TRY(call_event(cd, &z_done));
-      PCC_HIP(hipEventRecord(ev_z, st));
-      PCC_HIP(hipStreamWaitEvent(side->stream, ev_z, 0));
-      PCC_TRY(pcc_rans_encode_dev_async(side, cd->eb_dev, zsym_dev, nullptr, std::max<int64_t>(nz, 1), nzs, 1,
-                                        cd->pin_ysym.p + (size_t)cap_y * n_q, cap_z, d_lens + n_q, 0));
-      PCC_HIP(hipEventRecord(z_done, side->stream));
-    }
-  }
-  // host half of the geometry slot + the z string (codec_pipeline.py:294-317): run by this thread next to the y coders
-  std::vector<std::vector<uint8_t>> blobs((size_t)n_frames);
-  std::vector<uint8_t> z_string;
-  double helper_geo_s = 0, helper_z_s = 0;
-  const Tensor *eb_cdf = find(cd, "entropy_bottleneck.quantized_cdf"), *eb_len = find(cd, "entropy_bottleneck.cdf_length"),
-               *eb_off = find(cd, "entropy_bottleneck.offset");
-  PCC_REQUIRE(eb_cdf && eb_len && eb_off, PCC_E_ARG, "pcc_encode_gop: entropy_bottleneck tables missing");
-  const bool geo_threads = v1;   // version 0: the codec's threads are coding the y strings while this runs
-  auto geometry_finish = [&]() -> int {
-    PCC_TRY(geometry_arrived());
-    const double t = now_s();
-    for (int f = 0; f < n_frames; ++f) {
-      FrameGeo& g = geo[f];
-      if (!g.v2.empty()) {
-        blobs[f].swap(g.v2);
-        continue;
+    // version 1: room of the coded strings in pinned memory (first attempt: 6 bytes per symbol; the coder's own first
+    // attempt holds 1.5 words per symbol), and the z string's coder queued on the second stream
+    const int64_t per_y = (int64_t)cy * ny, nzs = (int64_t)cz * nz;
+    if (v1) {
+      PCC_REQUIRE(cd->gc_dev && cd->eb_dev, PCC_E_ARG, "pcc_encode_gop: container version 1 without device CDF tables");
+      cap_y = std::min<int64_t>(pcc_rans_dev_bound(per_y), (6 * per_y + 65536) / 4 * 4);
+      cap_z = std::min<int64_t>(pcc_rans_dev_bound(nzs), (6 * nzs + 65536) / 4 * 4);
+      PCC_TRY(cd->pin_ysym.ensure((size_t)cap_y * n_q + (size_t)cap_z + 256));
+      d_lens = (long long*)cd->pool.alloc(sizeof(long long) * (size_t)(n_q + 1));
+      if (!d_lens) return PCC_E_NOMEM;
+      if (side) {
+        hipEvent_t ev_z;
+        PCC_TRY(call_event(cd, &ev_z));
+        PCC_TRY(call_event(cd, &z_done));
+        PCC_HIP(hipEventRecord(ev_z, st));
+        PCC_HIP(hipStreamWaitEvent(side->stream, ev_z, 0));
+        PCC_TRY(pcc_rans_encode_dev_async(side, cd->eb_dev, zsym_dev, nullptr, std::max<int64_t>(nz, 1), nzs, 1,
+                                          cd->pin_ysym.p + (size_t)cap_y * n_q, cap_z, d_lens + n_q, 0));
+        PCC_HIP(hipEventRecord(z_done, side->stream));
       }
-      if (g.K > 1 && !g.parts.empty()) {   // blob version 3: the parts' coders side by side where threads are free
-        std::vector<std::vector<uint8_t>> pb((size_t)g.K);
-        std::vector<int> prc((size_t)g.K, PCC_OK);
-        std::vector<std::string> perr((size_t)g.K);
-        const int64_t zero = 0;
-        const int32_t org0[3] = {0, 0, 0};
-        auto pack_part = [&](int k) {
-          const FrameGeo::Part& pt = g.parts[(size_t)k];
-          pb[(size_t)k].resize((size_t)(64 + 2 * pt.nodes + 16));
-          int64_t len = 0;
-          prc[(size_t)k] = pcc_octree_pack(pt.n ? cd->pin_occ.p + pt.occ_off : nullptr, pt.n ? pt.level_n.data() : &zero,
-                                           pt.n ? g.depth : 0, pt.n, pt.n ? g.origin : org0, pb[(size_t)k].data(),
-                                           (int64_t)pb[(size_t)k].size(), &len);
-          if (prc[(size_t)k] != PCC_OK) perr[(size_t)k] = pcc_last_error();
-          pb[(size_t)k].resize((size_t)(prc[(size_t)k] == PCC_OK ? len : 0));
-        };
-        if (geo_threads) {   // container version 1: the codec's threads have nothing else to do at this point
-          cd->workers.ensure(g.K - 1);
-          for (int k = 1; k < g.K; ++k) cd->workers.run(k - 1, [&pack_part, k]() { pack_part(k); });
-          pack_part(0);
-          cd->workers.wait_all();
-        } else {
-          for (int k = 0; k < g.K; ++k) pack_part(k);
-        }
-        for (int k = 0; k < g.K; ++k)
-          if (prc[(size_t)k] != PCC_OK) {
-            pcc_set_error("pcc_encode_gop (geometry, frame %d part %d): %s", f, k, perr[(size_t)k].c_str());
-            return prc[(size_t)k];
-          }
-        int64_t tot = 64 + 4 * g.K;
-        for (const auto& b : pb) tot += (int64_t)b.size();
-        blobs[f].resize((size_t)tot);
-        int64_t len = 0;
-        PCC_TRY(pcc_octree_join_parts(g.depth, g.origin, g.n, pb.data(), g.K, blobs[f].data(), tot, &len));
-        blobs[f].resize((size_t)len);
-        continue;
-      }
-      const int64_t cap = 64 + 2 * g.occ_len + 16;
-      blobs[f].resize((size_t)cap);
-      int64_t len = 0;
-      const int64_t zero = 0;
-      PCC_TRY(pcc_octree_pack(g.n ? cd->pin_occ.p + g.occ_off : nullptr, g.n ? g.level_n.data() : &zero, g.depth, g.n,
-                              g.origin, blobs[f].data(), cap, &len));
-      blobs[f].resize((size_t)len);
     }
-    helper_geo_s = now_s() - t;
+    eb_cdf = find(cd, "entropy_bottleneck.quantized_cdf");
+    eb_len = find(cd, "entropy_bottleneck.cdf_length");
+    eb_off = find(cd, "entropy_bottleneck.offset");
+    PCC_REQUIRE(eb_cdf && eb_len && eb_off, PCC_E_ARG, "pcc_encode_gop: entropy_bottleneck tables missing");
     return PCC_OK;
-  };
-  auto side_streams = [&]() -> int {
-    PCC_TRY(geometry_device_half(ctx));
-    PCC_TRY(geometry_finish());
-    double t = now_s();
-    std::vector<int32_t> idx((size_t)nz * cz);
-    for (int c = 0; c < cz; ++c) std::fill(idx.begin() + (size_t)c * nz, idx.begin() + (size_t)(c + 1) * nz, c);
-    PCC_TRY(rans_encode_grow((const int32_t*)cd->pin_zsym.p, idx.data(), nz * cz, eb_cdf, eb_len, eb_off, &z_string));
-    helper_z_s = now_s() - t;
-    return PCC_OK;
-  };
-  ts[2] = now_s() - t0;
-
-  // ---- step 4: hyper synthesis h_s -> (scales_hat | means_hat) at stride 8
-  t0 = now_s();
-  Feat gp;
-  PCC_TRY(h_s_up(cd, z_hat, &gp));
-  ts[3] = now_s() - t0;
-
+  }
   // ---- step 5: all Q quality streams at once (codec_pipeline.py:397-437)
-  t0 = now_s();
-  std::vector<std::vector<uint8_t>> y_strings((size_t)n_q);  // only the int16-overflow path below fills these
-  std::vector<uint8_t> head_done((size_t)n_q, 0);
-  std::vector<int64_t> seek_idx;                     // seek points of the y strings (cd->seek_points; version 0 only)
-  std::vector<std::vector<uint64_t>> seek_state;     // [quality][point]
-  std::vector<std::vector<int64_t>> seek_word;
-  if (v1) {
-    // Container version 1: symbols and indexes stay in HBM, the Q y streams and the z stream are coded by the GPU's
-    // interleaved coder behind the quantiser, and only the finished streams cross PCIe.  The geometry slots (device
-    // half + host occupancy coder) follow in the stream / on this thread as in version 0.
-    float* params;
+  int gaussian() {
+    float *params, *scale_d;
     PCC_TRY(h_s_out_at(cd, gp, y.cs, yv, &params));
-    float* scale_d;
     PCC_TRY(scale_rows_dev(cd, 0, h_q, n_q, &scale_d));
     const Tensor* tab = find(cd, "gaussian_conditional.scale_table");
+    return v1 ? gaussian_v1(params, scale_d, tab) : gaussian_v0(params, scale_d, tab);
+  }
+  // Container version 1: symbols and indexes stay in HBM, the Q y streams and the z stream are coded by the GPU's
+  // interleaved coder behind the quantiser, and only the finished streams cross PCIe.  The geometry slots (device
+  // half + host occupancy coder) follow in the stream / on this thread as in version 0.
+  int gaussian_v1(float* params, float* scale_d, const Tensor* tab) {
     PCC_REQUIRE(tab, PCC_E_ARG, "pcc_encode_gop: gaussian_conditional tables missing");
-    const int64_t per = per_y, tot = per * n_q;
+    const int64_t per = (int64_t)cy * ny, tot = per * n_q, nzs = (int64_t)cz * nz;
     CODEC_ALLOC(sym32, int32_t, std::max<int64_t>(tot, 1));
     CODEC_ALLOC(idx8, uint8_t, std::max<int64_t>(tot, 1));
     if (ny > 0)
@@ -1620,7 +1614,7 @@ static int encode_gop_impl(pcc_codec* cd, const int32_t* d_coords, const float* 
     PCC_TRY(cd->pin_flag.ensure(8 * 65 + 64));
     long long* h_lens = (long long*)cd->pin_flag.p;
     uint8_t *ystreams = nullptr, *zstream = nullptr;
-    PCC_TRY(geometry_device_half(ctx));  // (unless it runs on the second stream already) in front of the coder kernels: its output is on the host while they run
+    PCC_TRY(geo.device_half(ctx));  // (unless it runs on the second stream already) in front of the coder kernels: its output is on the host while they run
     for (int attempt = 0; attempt < 2; ++attempt) {
       // attempt 0: the room reserved above; attempt 1: the bound
       if (attempt == 1) {
@@ -1641,7 +1635,8 @@ static int encode_gop_impl(pcc_codec* cd, const int32_t* d_coords, const float* 
         PCC_TRY(pcc_rans_encode_dev_async(ctx, cd->eb_dev, zsym_dev, nullptr, std::max<int64_t>(nz, 1), nzs, 1, zstream, cap_z,
                                           d_lens + n_q, attempt));
       PCC_HIP(hipMemcpyAsync(h_lens, d_lens, (size_t)(n_q + 1) * 8, hipMemcpyDeviceToHost, st));
-      if (attempt == 0) PCC_TRY(geometry_finish());   // the occupancy coder of this thread runs while the GPU codes
+      // the occupancy coder of this thread runs while the GPU codes; the codec's threads have nothing else to do
+      if (attempt == 0) PCC_TRY(geo.finish(true, blobs));
       PCC_HIP(hipStreamSynchronize(st));
       bool fits = true;
       for (int q = 0; q <= n_q; ++q) fits &= h_lens[q] >= 0;
@@ -1650,14 +1645,13 @@ static int encode_gop_impl(pcc_codec* cd, const int32_t* d_coords, const float* 
     }
     for (int q = 0; q < n_q; ++q) y_strings[q].assign(ystreams + (size_t)q * cap_y, ystreams + (size_t)q * cap_y + h_lens[q]);
     z_string.assign(zstream, zstream + h_lens[n_q]);
-  } else {
-    float* params;
-    PCC_TRY(h_s_out_at(cd, gp, y.cs, yv, &params));
-    float* scale_d;
-    PCC_TRY(scale_rows_dev(cd, 0, h_q, n_q, &scale_d));
-    const Tensor* tab = find(cd, "gaussian_conditional.scale_table");
-    const Tensor *gc_cdf = find(cd, "gaussian_conditional.quantized_cdf"), *gc_len = find(cd, "gaussian_conditional.cdf_length"),
-                 *gc_off = find(cd, "gaussian_conditional.offset");
+    return PCC_OK;
+  }
+  // container version 0: the y strings coded on the codec's threads, the int16-overflow case by gaussian_int32
+  int gaussian_v0(float* params, float* scale_d, const Tensor* tab) {
+    gc_cdf = find(cd, "gaussian_conditional.quantized_cdf");
+    gc_len = find(cd, "gaussian_conditional.cdf_length");
+    gc_off = find(cd, "gaussian_conditional.offset");
     PCC_REQUIRE(tab && gc_cdf && gc_len && gc_off, PCC_E_ARG, "pcc_encode_gop: gaussian_conditional tables missing");
     const int ntab = (int)tab->dims[0];
     const int64_t per = (int64_t)cy * ny, tot = per * n_q;
@@ -1675,10 +1669,10 @@ static int encode_gop_impl(pcc_codec* cd, const int32_t* d_coords, const float* 
     // in kChunks pieces, last piece first (one strided copy moves that piece of every quality), and a coder only
     // waits for the piece it is about to enter — all Q threads start after the first ~2 MB instead of after their
     // whole quality (the last thread used to start 0.2 ms after the quantiser finished).
-    const int n_chunks = per >= (1 << 16) ? 4 : 1;
-    std::vector<int64_t> bound((size_t)n_chunks);
+    n_chunks = per >= (1 << 16) ? 4 : 1;
+    bound.resize((size_t)n_chunks);
     for (int c = 0; c < n_chunks; ++c) bound[c] = (per * (n_chunks - 1 - c) / n_chunks) & ~(int64_t)63;
-    std::vector<hipEvent_t> evc((size_t)n_chunks, nullptr);
+    evc.assign((size_t)n_chunks, nullptr);
     for (int c = 0; c < n_chunks; ++c) {
       const int64_t lo = bound[c], hi = c == 0 ? per : bound[c - 1];
       if (ny > 0 && hi > lo) {
@@ -1690,79 +1684,17 @@ static int encode_gop_impl(pcc_codec* cd, const int32_t* d_coords, const float* 
       PCC_TRY(call_event(cd, &evc[c]));
       PCC_HIP(hipEventRecord(evc[c], st));
     }
-    struct GateUser {
-      hipEvent_t* ev;
-      bool failed;
-    };
-    std::vector<int64_t> lens((size_t)n_q, 0);
-    std::vector<uint8_t> stage;
-    int rc = PCC_OK;
-    int64_t cap = 2 * per + 4096;
-    std::vector<int> rcq((size_t)n_q, PCC_OK);
-    std::vector<std::string> errq((size_t)n_q);
-    seek_indexes(per, v1 ? 0 : cd->seek_points, &seek_idx);
+    rcq.assign((size_t)n_q, PCC_OK);
+    errq.assign((size_t)n_q, std::string());
+    seek_indexes(per, cd->seek_points, &seek_idx);
     seek_state.assign((size_t)n_q, std::vector<uint64_t>(seek_idx.size() + 1, 0));
     seek_word.assign((size_t)n_q, std::vector<int64_t>(seek_idx.size() + 1, 0));
     int side_rc = PCC_OK;
-    const int64_t nz_for_header = nz;
-    auto code_quality = [&](int q) {
-      (void)hipSetDevice(cd->device);
-      GateUser gu{evc.data(), false};
-      PccRansGate gate{n_chunks, bound.data(),
-                       [](void* u, int c) {
-                         GateUser* g = (GateUser*)u;
-                         if (hipEventSynchronize(g->ev[c]) != hipSuccess) g->failed = true;
-                       },
-                       &gu};
-      gate.fn(&gu, 0);  // the overflow flag travels ahead of the first piece
-      if (gu.failed) {
-        rcq[q] = PCC_E_HIP;
-        errq[q] = "hipEventSynchronize failed";
-        return;
-      }
-      if (*(volatile int32_t*)cd->pin_flag.p != 0) return;  // int16 overflow: the generic path below codes everything
-      int64_t capq = cap, got = 0;
-      std::unique_ptr<uint8_t[]> ybuf;  // not cleared: a std::vector of the worst-case size would memset 1.7 MB first
-      for (int attempt = 0; attempt < 2; ++attempt) {
-        ybuf.reset(new uint8_t[(size_t)capq]);
-        PccRansSeek seek{(int)seek_idx.size(), seek_idx.data(), seek_state[q].data(), seek_word[q].data()};
-        rcq[q] = pcc_rans_encode16_seek((const int16_t*)cd->pin_ysym.p + (size_t)q * per,
-                                        cd->pin_yidx.p + (size_t)q * per, per, gc_cdf->i32(), (int)gc_cdf->dims[1],
-                                        gc_len->i32(), gc_off->i32(), (int)gc_cdf->dims[0], ybuf.get(), capq, &got,
-                                        &gate, cd->gc_tables, seek_idx.empty() ? nullptr : &seek);
-        if (rcq[q] != PCC_E_NOMEM) break;
-        capq = 48 * per + 4096;
-      }
-      if (rcq[q] == PCC_OK && gu.failed) {
-        rcq[q] = PCC_E_HIP;
-        errq[q] = "hipEventSynchronize failed";
-      } else if (rcq[q] == PCC_OK) {
-        // head of the container (codec_pipeline.py:477-499) + y string, written here in parallel with the other
-        // qualities; the z string, whose length is patched into the header, and the frame slots follow after the join
-        std::vector<uint8_t>& o = cd->out[q];
-        o.clear();
-        o.reserve((size_t)got + 65536);
-        put_be32(o, n_frames);
-        put_be_f64(o, h_q[2 * q]);
-        put_be_f64(o, h_q[2 * q + 1]);
-        put_be32(o, (int32_t)ny);
-        put_be32(o, (int32_t)nz_for_header);
-        put_be32(o, (int32_t)got);
-        put_be32(o, 0);
-        o.insert(o.end(), ybuf.get(), ybuf.get() + got);
-        head_done[q] = 1;
-      } else {
-        errq[q] = pcc_last_error();
-      }
-    };
     {
-      struct WaitAll {  // the jobs reference locals of this frame: never leave it while one is running
-        PccWorkers& w;
-        ~WaitAll() { w.wait_all(); }
-      } wait_all{cd->workers};
+      WorkersGuard wait_all{&cd->workers};   // the jobs reference this call's state: never leave while one is running
       cd->workers.ensure(n_q);
-      for (int q = 0; q < n_q; ++q) cd->workers.run(q, [&code_quality, q]() { code_quality(q); });
-      side_rc = side_streams();  // geometry slots + z string on this thread meanwhile (waits on scope exit)
+      for (int q = 0; q < n_q; ++q) cd->workers.run(q, [this, q]() { code_quality(q); });
+      side_rc = geometry_and_z();  // geometry slots + z string on this thread meanwhile (waits on scope exit)
     }
     PCC_TRY(side_rc);
     for (int q = 0; q < n_q; ++q)
@@ -1770,75 +1702,168 @@ static int encode_gop_impl(pcc_codec* cd, const int32_t* d_coords, const float* 
         pcc_set_error("pcc_encode_gop (y stream %d): %s", q, errq[q].c_str());
         return rcq[q];
       }
-    if (*(int32_t*)cd->pin_flag.p == 0) {
-      // coded above
-    } else {  // a symbol outside int16: the generic int32 form
-      std::fill(head_done.begin(), head_done.end(), 0);
-      CODEC_ALLOC(sym32, int32_t, std::max<int64_t>(tot, 1));
-      CODEC_ALLOC(idx32, int32_t, std::max<int64_t>(tot, 1));
-      PCC_TRY(pcc_gaussian_quant(ctx, ys_f, params, ny, cy, scale_d, n_q, cd->dev["gaussian_conditional.scale_table"],
-                                 ntab, sym32, idx32));
-      PCC_HIP(hipMemcpyAsync(cd->pin_ysym.p, sym32, (size_t)tot * 4, hipMemcpyDeviceToHost, st));
-      PCC_HIP(hipMemcpyAsync(cd->pin_yidx.p, idx32, (size_t)tot * 4, hipMemcpyDeviceToHost, st));
-      PCC_HIP(hipStreamSynchronize(st));
-      for (int attempt = 0; attempt < 2; ++attempt) {
-        stage.resize((size_t)cap * n_q);
-        rc = pcc_rans_encode_multi((const int32_t*)cd->pin_ysym.p, (const int32_t*)cd->pin_yidx.p, per, n_q,
-                                   gc_cdf->i32(), (int)gc_cdf->dims[1], gc_len->i32(), gc_off->i32(),
-                                   (int)gc_cdf->dims[0], stage.data(), cap, lens.data());
-        if (rc != PCC_E_NOMEM) break;
-        cap = 48 * per + 4096;
-      }
-      PCC_TRY(rc);
-      for (int q = 0; q < n_q; ++q)
-        y_strings[q].assign(stage.begin() + (size_t)q * cap, stage.begin() + (size_t)q * cap + (size_t)lens[q]);
-    }
+    if (*(int32_t*)cd->pin_flag.p == 0) return PCC_OK;   // coded above
+    return gaussian_int32(params, scale_d, ntab);
   }
-  ts[5] = now_s() - t0;
-
-  ts[4] = geo_dev_s + helper_geo_s;  // these two ran next to the y coders, inside the gaussian stage's wall time
-  ts[2] += helper_z_s;
-
-  // ---- step 7: containers, field for field the reference writer (codec_pipeline.py:464-517)
-  t0 = now_s();
-  for (int q = 0; q < n_q; ++q) {
-    std::vector<uint8_t>& o = cd->out[q];
-    if (head_done[q]) {  // header + y string are in place: patch len_z (bytes 32..35, big-endian)
-      const uint32_t lz = (uint32_t)z_string.size();
-      o[32] = (uint8_t)(lz >> 24); o[33] = (uint8_t)(lz >> 16); o[34] = (uint8_t)(lz >> 8); o[35] = (uint8_t)lz;
-    } else {
+  // y string q of version 0, on a thread of the codec
+  void code_quality(int q) {
+    struct GateUser {
+      hipEvent_t* ev;
+      bool failed;
+    };
+    (void)hipSetDevice(cd->device);
+    GateUser gu{evc.data(), false};
+    PccRansGate gate{n_chunks, bound.data(),
+                     [](void* u, int c) {
+                       GateUser* g = (GateUser*)u;
+                       if (hipEventSynchronize(g->ev[c]) != hipSuccess) g->failed = true;
+                     },
+                     &gu};
+    gate.fn(&gu, 0);  // the overflow flag travels ahead of the first piece
+    if (gu.failed) {
+      rcq[q] = PCC_E_HIP;
+      errq[q] = "hipEventSynchronize failed";
+      return;
+    }
+    if (*(volatile int32_t*)cd->pin_flag.p != 0) return;  // int16 overflow: gaussian_int32 codes everything
+    const int64_t per = (int64_t)cy * ny;
+    int64_t capq = 2 * per + 4096, got = 0;
+    std::unique_ptr<uint8_t[]> ybuf;  // not cleared: a std::vector of the worst-case size would memset 1.7 MB first
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      ybuf.reset(new uint8_t[(size_t)capq]);
+      PccRansSeek seek{(int)seek_idx.size(), seek_idx.data(), seek_state[q].data(), seek_word[q].data()};
+      rcq[q] = pcc_rans_encode16_seek((const int16_t*)cd->pin_ysym.p + (size_t)q * per, cd->pin_yidx.p + (size_t)q * per,
+                                      per, gc_cdf->i32(), (int)gc_cdf->dims[1], gc_len->i32(), gc_off->i32(),
+                                      (int)gc_cdf->dims[0], ybuf.get(), capq, &got, &gate, cd->gc_tables,
+                                      seek_idx.empty() ? nullptr : &seek);
+      if (rcq[q] != PCC_E_NOMEM) break;
+      capq = 48 * per + 4096;
+    }
+    if (rcq[q] == PCC_OK && gu.failed) {
+      rcq[q] = PCC_E_HIP;
+      errq[q] = "hipEventSynchronize failed";
+    } else if (rcq[q] == PCC_OK) {
+      // head of the container + y string, written here in parallel with the other qualities; the z string, whose
+      // length is patched into the header, and the frame slots follow after the join
+      std::vector<uint8_t>& o = cd->out[q];
       o.clear();
-      put_be32(o, n_frames | (cd->container_version << 24));
-      put_be_f64(o, h_q[2 * q]);
-      put_be_f64(o, h_q[2 * q + 1]);
-      put_be32(o, (int32_t)ny);
-      put_be32(o, (int32_t)nz);
-      put_be32(o, (int32_t)y_strings[q].size());
-      put_be32(o, (int32_t)z_string.size());
-      o.insert(o.end(), y_strings[q].begin(), y_strings[q].end());
+      o.reserve((size_t)got + 65536);
+      put_head(o, n_frames, q, got, 0);
+      o.insert(o.end(), ybuf.get(), ybuf.get() + got);
+      head_done[q] = 1;
+    } else {
+      errq[q] = pcc_last_error();
     }
-    o.insert(o.end(), z_string.begin(), z_string.end());
-    for (int f = 0; f < n_frames; ++f) {
-      put_be32(o, (int32_t)blobs[f].size());
-      for (int s = 0; s < 3; ++s) put_be32(o, (int32_t)(*kk[s])[f]);
-      o.insert(o.end(), blobs[f].begin(), blobs[f].end());
-    }
-    if (head_done[q] && !seek_idx.empty()) {   // "PCSK" | count | count x (index | state | words consumed), big-endian
-      const char magic[4] = {'P', 'C', 'S', 'K'};
-      o.insert(o.end(), magic, magic + 4);
-      put_be32(o, (int32_t)seek_idx.size());
-      for (size_t k = 0; k < seek_idx.size(); ++k) {
-        put_be32(o, (int32_t)seek_idx[k]);
-        put_be32(o, (int32_t)(uint32_t)(seek_state[q][k] >> 32));
-        put_be32(o, (int32_t)(uint32_t)seek_state[q][k]);
-        put_be32(o, (int32_t)seek_word[q][k]);
-      }
-    }
-    h_out[q].data = o.data();
-    h_out[q].len = (int64_t)o.size();
   }
-  ts[6] = now_s() - t0;
-  if (h_stage_s) memcpy(h_stage_s, ts, 7 * sizeof(double));
+  // host half of the geometry slot + the z string (codec_pipeline.py:294-317): run by this thread next to the y coders
+  int geometry_and_z() {
+    PCC_TRY(geo.device_half(ctx));
+    PCC_TRY(geo.finish(false, blobs));
+    double t = now_s();
+    std::vector<int32_t> idx((size_t)nz * cz);
+    for (int c = 0; c < cz; ++c) std::fill(idx.begin() + (size_t)c * nz, idx.begin() + (size_t)(c + 1) * nz, c);
+    PCC_TRY(rans_encode_grow((const int32_t*)cd->pin_zsym.p, idx.data(), nz * cz, eb_cdf, eb_len, eb_off, &z_string));
+    helper_z_s = now_s() - t;
+    return PCC_OK;
+  }
+  // a symbol outside int16: the generic int32 form
+  int gaussian_int32(const float* params, const float* scale_d, int ntab) {
+    const int64_t per = (int64_t)cy * ny, tot = per * n_q;
+    int64_t cap = 2 * per + 4096;
+    std::fill(head_done.begin(), head_done.end(), 0);
+    CODEC_ALLOC(sym32, int32_t, std::max<int64_t>(tot, 1));
+    CODEC_ALLOC(idx32, int32_t, std::max<int64_t>(tot, 1));
+    PCC_TRY(pcc_gaussian_quant(ctx, ys_f, params, ny, cy, scale_d, n_q, cd->dev["gaussian_conditional.scale_table"],
+                               ntab, sym32, idx32));
+    PCC_HIP(hipMemcpyAsync(cd->pin_ysym.p, sym32, (size_t)tot * 4, hipMemcpyDeviceToHost, st));
+    PCC_HIP(hipMemcpyAsync(cd->pin_yidx.p, idx32, (size_t)tot * 4, hipMemcpyDeviceToHost, st));
+    PCC_HIP(hipStreamSynchronize(st));
+    std::vector<int64_t> lens((size_t)n_q, 0);
+    std::vector<uint8_t> stage;
+    int rc = PCC_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      stage.resize((size_t)cap * n_q);
+      rc = pcc_rans_encode_multi((const int32_t*)cd->pin_ysym.p, (const int32_t*)cd->pin_yidx.p, per, n_q,
+                                 gc_cdf->i32(), (int)gc_cdf->dims[1], gc_len->i32(), gc_off->i32(),
+                                 (int)gc_cdf->dims[0], stage.data(), cap, lens.data());
+      if (rc != PCC_E_NOMEM) break;
+      cap = 48 * per + 4096;
+    }
+    PCC_TRY(rc);
+    for (int q = 0; q < n_q; ++q)
+      y_strings[q].assign(stage.begin() + (size_t)q * cap, stage.begin() + (size_t)q * cap + (size_t)lens[q]);
+    return PCC_OK;
+  }
+  // head of container q (codec_pipeline.py:477-499); word0 is the frame count, with the version in its top byte
+  // where the container is written whole
+  void put_head(std::vector<uint8_t>& o, int32_t word0, int q, int64_t ylen, int64_t zlen) const {
+    put_be32(o, word0);
+    put_be_f64(o, h_q[2 * q]);
+    put_be_f64(o, h_q[2 * q + 1]);
+    put_be32(o, (int32_t)ny);
+    put_be32(o, (int32_t)nz);
+    put_be32(o, (int32_t)ylen);
+    put_be32(o, (int32_t)zlen);
+  }
+  // ---- step 7: containers, field for field the reference writer (codec_pipeline.py:464-517)
+  void write_containers(pcc_buf* h_out) {
+    for (int q = 0; q < n_q; ++q) {
+      std::vector<uint8_t>& o = cd->out[q];
+      if (head_done[q]) {  // header + y string are in place: patch len_z (bytes 32..35, big-endian)
+        const uint32_t lz = (uint32_t)z_string.size();
+        o[32] = (uint8_t)(lz >> 24); o[33] = (uint8_t)(lz >> 16); o[34] = (uint8_t)(lz >> 8); o[35] = (uint8_t)lz;
+      } else {
+        o.clear();
+        put_head(o, n_frames | (cd->container_version << 24), q, (int64_t)y_strings[q].size(), (int64_t)z_string.size());
+        o.insert(o.end(), y_strings[q].begin(), y_strings[q].end());
+      }
+      o.insert(o.end(), z_string.begin(), z_string.end());
+      for (int f = 0; f < n_frames; ++f) {
+        put_be32(o, (int32_t)blobs[f].size());
+        for (int s = 0; s < 3; ++s) put_be32(o, (int32_t)counts[2 - s][f]);
+        o.insert(o.end(), blobs[f].begin(), blobs[f].end());
+      }
+      if (head_done[q] && !seek_idx.empty()) {   // "PCSK" | count | count x (index | state | words consumed), big-endian
+        const char magic[4] = {'P', 'C', 'S', 'K'};
+        o.insert(o.end(), magic, magic + 4);
+        put_be32(o, (int32_t)seek_idx.size());
+        for (size_t k = 0; k < seek_idx.size(); ++k) {
+          put_be32(o, (int32_t)seek_idx[k]);
+          put_be32(o, (int32_t)(uint32_t)(seek_state[q][k] >> 32));
+          put_be32(o, (int32_t)(uint32_t)seek_state[q][k]);
+          put_be32(o, (int32_t)seek_word[q][k]);
+        }
+      }
+      h_out[q].data = o.data();
+      h_out[q].len = (int64_t)o.size();
+    }
+  }
+};
+
+}  // namespace
+
+static int encode_gop_impl(pcc_codec* cd, const int32_t* d_coords, const float* d_feats, int64_t n, int n_frames,
+                           const double* h_q, int n_q, pcc_buf* h_out, int64_t* h_k, double* h_stage_s,
+                           const FrameTab* frames_in = nullptr, const HostFrames* host = nullptr) {
+  PCC_REQUIRE(cd && cd->ctx, PCC_E_ARG, "pcc_encode_gop: null codec");
+  PCC_REQUIRE(n > 0 && (frames_in || (d_coords && d_feats)) && n_frames >= 1 && n_frames <= 65535 && h_q && n_q >= 1 &&
+                  n_q <= 64 && h_out,
+              PCC_E_ARG, "pcc_encode_gop: bad argument (n=%lld frames=%d q=%d)", (long long)n, n_frames, n_q);
+  PCC_TRY(begin_call(cd));
+  cd->out.assign((size_t)n_q, {});
+  EncodeCall c(cd, n_frames, h_q, n_q);
+  PCC_TRY(timed(&c.ts[0], [&] { return c.unpack(n, d_coords, d_feats, frames_in, host); }));
+  PCC_TRY(timed(&c.ts[0], [&] { return c.analysis(h_k); }));
+  PCC_TRY(c.start_side());
+  PCC_TRY(timed(&c.ts[1], [&] { return c.hyper_analysis(); }));
+  PCC_TRY(timed(&c.ts[2], [&] { return c.factorized(); }));
+  // ---- step 4: hyper synthesis h_s -> (scales_hat | means_hat) at stride 8
+  PCC_TRY(timed(&c.ts[3], [&] { return h_s_up(cd, c.z_hat, &c.gp); }));
+  PCC_TRY(timed(&c.ts[5], [&] { return c.gaussian(); }));
+  c.ts[4] = c.geo.dev_s + c.geo.host_s;  // these two ran next to the y coders, inside the gaussian stage's wall time
+  c.ts[2] += c.helper_z_s;
+  PCC_TRY(timed(&c.ts[6], [&] { c.write_containers(h_out); return PCC_OK; }));
+  if (h_stage_s) memcpy(h_stage_s, c.ts, 7 * sizeof(double));
   return PCC_OK;
 }
 
@@ -1852,126 +1877,193 @@ struct PackedDst {
 __global__ __launch_bounds__(256) void k_pack_cloud(const int4* __restrict__ coords, const float* __restrict__ colors,
                                                     int64_t n, int32_t* __restrict__ xyz, float* __restrict__ rgb);
 
-static int decode_gop_impl(pcc_codec* cd, const uint8_t* h_in, int64_t len, pcc_cloud_info* h_info,
-                           double* h_stage_s, const PackedDst* dst = nullptr) {
-  PCC_REQUIRE(cd && cd->ctx, PCC_E_ARG, "pcc_decode_gop: null codec");
-  PCC_REQUIRE(h_in && len >= 36 && h_info, PCC_E_STREAM, "pcc_decode_gop: container shorter than its header");
-  pcc_ctx* ctx = cd->ctx;
-  hipStream_t st = ctx->stream;
-  PCC_HIP(hipSetDevice(cd->device));
-  PCC_TRY(pcc_sync(ctx));
-  if (cd->up_stream) PCC_HIP(hipStreamSynchronize(cd->up_stream));   // an encode on this codec that left early (see there)
-  if (cd->side_stream) PCC_HIP(hipStreamSynchronize(cd->side_stream));
-  cd->pool.reset();
-  cd->events_used = 0;
-  cd->sets.clear();
-  cd->rec_n = 0;
-  cd->rec_offsets.clear();
-  const int cy = cd->c_y, cz = cd->c_z;
-  double ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+// pack_batches' arrays of the last decode queued on the compute stream, into destinations that may be device or host
+// memory (pageable host memory is staged by the runtime); the caller synchronises
+static int queue_packed(pcc_codec* cd, int32_t* points, float* colors) {
+  hipStream_t st = cd->ctx->stream;
+  const int64_t n = cd->rec_n;
+  CODEC_ALLOC(xyz, int32_t, 3 * n);
+  CODEC_ALLOC(rgb, float, 3 * n);
+  hipLaunchKernelGGL(k_pack_cloud, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int4*)cd->rec_coords,
+                     (const float*)cd->rec_colors, n, xyz, rgb);
+  PCC_CHECK_LAUNCH();
+  PCC_HIP(hipMemcpyAsync(points, xyz, (size_t)n * 12, hipMemcpyDefault, st));
+  PCC_HIP(hipMemcpyAsync(colors, rgb, (size_t)n * 12, hipMemcpyDefault, st));
+  return PCC_OK;
+}
 
-  // ---- step 1: container (codec_parallel.py:173-216)
-  double t0 = now_s();
-  Reader r{h_in, len};
-  // first word: frame count, with the container version in its top byte (0 = the reference's layout; 1 = y / z strings
-  // in the GPU coder's interleaved form, rans_gpu.hip)
-  const int32_t word0 = r.be32();
-  const int version = (int)(((uint32_t)word0 >> 24) & 0xFFu);
-  const int32_t n_frames = (int32_t)((uint32_t)word0 & 0x00FFFFFFu);
-  PCC_REQUIRE(version == 0 || version == 1, PCC_E_STREAM, "pcc_decode_gop: container version %d", version);
-  const bool v1 = version == 1;
-  PCC_REQUIRE(!v1 || (cd->gc_dev && cd->eb_dev), PCC_E_ARG, "pcc_decode_gop: version-1 container, but the checkpoint's CDF "
-              "tables have no device form");
-  const double qg = r.be_f64(), qa = r.be_f64();
-  const int32_t ny_hdr = r.be32(), nz_hdr = r.be32(), ylen = r.be32(), zlen = r.be32();
-  const uint8_t* ystr = r.bytes(ylen);
-  const uint8_t* zstr = r.bytes(zlen);
-  PCC_REQUIRE(!r.bad && n_frames >= 0 && n_frames <= 65535 && ny_hdr >= 0 && nz_hdr >= 0, PCC_E_STREAM,
-              "pcc_decode_gop: truncated container");
+namespace {
+
+// rows (f, 8 x, 8 y, 8 z) of n decoded latent points; true when one of them lies outside [-4096, 4095]
+bool put_leaf_rows(const int32_t* pts, int64_t n, int f, int32_t* dst) {
+  bool bad = false;
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+    bad |= (x < -4096) | (x > 4095) | (y < -4096) | (y > 4095) | (z < -4096) | (z > 4095);
+    dst[4 * i] = f;
+    dst[4 * i + 1] = x * 8;
+    dst[4 * i + 2] = y * 8;
+    dst[4 * i + 3] = z * 8;
+  }
+  return bad;
+}
+
+// blob version 3: one part of a frame's octree
+struct PartJob {
+  int f, k;
+  const uint8_t* p;
+  int64_t len, n, row0;
+  int32_t org[3];
+  PccOctPart out;
+  bool out_of_range = false;
+  int rc = PCC_OK;
+  std::string err;
+};
+
+void run_part_job(PartJob& pj, int32_t* rows) {
+  pj.rc = pcc_octree_unpack_part(pj.p, pj.len, &pj.out);
+  if (pj.rc != PCC_OK) {
+    pj.err = pcc_last_error();
+    return;
+  }
+  if ((int64_t)pj.out.cells.size() != pj.n) {   // (the part's decoder has checked this against the part's header)
+    pj.rc = PCC_E_STREAM;
+    pj.err = "part decoded another number of leaves than its header says";
+    return;
+  }
+  int32_t xyz[3 * 64];
+  for (int64_t i0 = 0; i0 < pj.n; i0 += 64) {
+    const int64_t m = std::min<int64_t>(64, pj.n - i0);
+    pcc_octree_cells_to_points(pj.out.cells.data() + i0, m, pj.org, xyz);
+    pj.out_of_range |= put_leaf_rows(xyz, m, pj.f, rows + 4 * (pj.row0 + i0));
+  }
+}
+
+struct DecodeCall {
   struct Slot {
     const uint8_t* p;
     int32_t len;
   };
-  std::vector<Slot> slots((size_t)n_frames);
+  pcc_codec* cd;
+  pcc_ctx* ctx;
+  hipStream_t st;
+  int cy, cz;
+  double ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  bool v1 = false;
+  int32_t n_frames = 0, ny_hdr = 0, nz_hdr = 0, ylen = 0, zlen = 0;
+  double qg = 0, qa = 0;
+  const uint8_t *ystr = nullptr, *zstr = nullptr;
+  std::vector<Slot> slots;
   std::vector<int64_t> ks[3];
-  for (int f = 0; f < n_frames; ++f) {
-    const int32_t pl = r.be32();
-    for (int s = 0; s < 3; ++s) ks[s].push_back(r.be32());
-    slots[f] = {r.bytes(pl), pl};
-    PCC_REQUIRE(!r.bad, PCC_E_STREAM, "pcc_decode_gop: truncated container");
-  }
-  // Behind the last frame record the reference's reader stops (codec_parallel.py:200-213).  This library's encoder may
-  // have left the seek points of the y string there ("PCSK" | count | count x (index | state | words consumed)); they
-  // are a hint — every piece decoded from one is checked against the next point, and a trailer that does not parse or
-  // does not check out is ignored (the string is then decoded serially, as the reference decodes it)
-  std::vector<int64_t> sk_idx, sk_word;
+  std::vector<int64_t> sk_idx, sk_word;   // seek points of the y string, when the container has a valid trailer
   std::vector<uint64_t> sk_state;
-  if (!v1 && len - r.pos >= 8 && memcmp(h_in + r.pos, "PCSK", 4) == 0) {
-    Reader t{h_in + r.pos + 4, len - r.pos - 4};
-    const int32_t cnt = t.be32();
-    bool ok = cnt >= 1 && cnt <= 63 && (int64_t)cnt * 16 <= t.len - t.pos;
-    for (int k = 0; ok && k < cnt; ++k) {
-      const int64_t i = t.be32();
-      const uint64_t hi = (uint32_t)t.be32(), lo = (uint32_t)t.be32();
-      const int64_t w = t.be32();
-      ok = !t.bad && i > (sk_idx.empty() ? 0 : sk_idx.back()) && i < (int64_t)ny_hdr * cy && w >= 2 && w * 4 <= ylen &&
-           ((hi << 32) | lo) >= ((uint64_t)1 << 31);
-      sk_idx.push_back(i);
-      sk_state.push_back((hi << 32) | lo);
-      sk_word.push_back(w);
+  int64_t ny = 0;               // sum of the point counts the blobs announce
+  std::vector<int64_t> fn;
+  std::vector<int> fdepth;
+  const Tensor *eb_cdf = nullptr, *eb_len = nullptr, *eb_off = nullptr;
+  std::vector<int32_t> zsym;    // the host job's z symbols (version 0)
+  int z_rc = PCC_OK;
+  std::string z_err;
+  bool z_early = false;
+  // version 1: the streams are decoded on the device; their headers are checked on the host copy
+  int64_t z_steps = 0, z_chunks = 0, y_steps = 0, y_chunks = 0;
+  int32_t* d_status = nullptr;
+  int32_t* zsym_early = nullptr;   // version 1: the z symbols in HBM, when queued before the geometry
+  uint8_t* d_ystr = nullptr;       // version 1: the y string in HBM
+  int n_batch = 0;
+  int64_t n16 = 0, n32 = 0;
+  CS* ycs = nullptr;
+  Feat z_hat, gp, y_hat;
+  explicit DecodeCall(pcc_codec* c) : cd(c), ctx(c->ctx), st(c->ctx->stream), cy(c->c_y), cz(c->c_z) {}
+  // ---- step 1: container (codec_parallel.py:173-216)
+  int parse(const uint8_t* h_in, int64_t len) {
+    Reader r{h_in, len};
+    // first word: frame count, with the container version in its top byte (0 = the reference's layout; 1 = y / z strings
+    // in the GPU coder's interleaved form, rans_gpu.hip)
+    const int32_t word0 = r.be32();
+    const int version = (int)(((uint32_t)word0 >> 24) & 0xFFu);
+    n_frames = (int32_t)((uint32_t)word0 & 0x00FFFFFFu);
+    PCC_REQUIRE(version == 0 || version == 1, PCC_E_STREAM, "pcc_decode_gop: container version %d", version);
+    v1 = version == 1;
+    PCC_REQUIRE(!v1 || (cd->gc_dev && cd->eb_dev), PCC_E_ARG, "pcc_decode_gop: version-1 container, but the checkpoint's CDF "
+                "tables have no device form");
+    qg = r.be_f64();
+    qa = r.be_f64();
+    ny_hdr = r.be32();
+    nz_hdr = r.be32();
+    ylen = r.be32();
+    zlen = r.be32();
+    ystr = r.bytes(ylen);
+    zstr = r.bytes(zlen);
+    PCC_REQUIRE(!r.bad && n_frames >= 0 && n_frames <= 65535 && ny_hdr >= 0 && nz_hdr >= 0, PCC_E_STREAM,
+                "pcc_decode_gop: truncated container");
+    slots.resize((size_t)n_frames);
+    for (int f = 0; f < n_frames; ++f) {
+      const int32_t pl = r.be32();
+      for (int s = 0; s < 3; ++s) ks[s].push_back(r.be32());
+      slots[f] = {r.bytes(pl), pl};
+      PCC_REQUIRE(!r.bad, PCC_E_STREAM, "pcc_decode_gop: truncated container");
     }
-    if (!ok) sk_idx.clear();
+    // Behind the last frame record the reference's reader stops (codec_parallel.py:200-213).  This library's encoder may
+    // have left the seek points of the y string there ("PCSK" | count | count x (index | state | words consumed)); they
+    // are a hint — every piece decoded from one is checked against the next point, and a trailer that does not parse or
+    // does not check out is ignored (the string is then decoded serially, as the reference decodes it)
+    if (!v1 && len - r.pos >= 8 && memcmp(h_in + r.pos, "PCSK", 4) == 0) {
+      Reader t{h_in + r.pos + 4, len - r.pos - 4};
+      const int32_t cnt = t.be32();
+      bool ok = cnt >= 1 && cnt <= 63 && (int64_t)cnt * 16 <= t.len - t.pos;
+      for (int k = 0; ok && k < cnt; ++k) {
+        const int64_t i = t.be32();
+        const uint64_t hi = (uint32_t)t.be32(), lo = (uint32_t)t.be32();
+        const int64_t w = t.be32();
+        ok = !t.bad && i > (sk_idx.empty() ? 0 : sk_idx.back()) && i < (int64_t)ny_hdr * cy && w >= 2 && w * 4 <= ylen &&
+             ((hi << 32) | lo) >= ((uint64_t)1 << 31);
+        sk_idx.push_back(i);
+        sk_state.push_back((hi << 32) | lo);
+        sk_word.push_back(w);
+      }
+      if (!ok) sk_idx.clear();
+    }
+    return PCC_OK;
   }
-  ts[0] = now_s() - t0;
-
   // point counts the blobs announce, checked against the header BEFORE anything is sized from them:
   // a rANS symbol costs at least ~2^-16 bit and an octree point at least a fraction of a bit, so a
   // count far beyond what the payload can hold is a corrupt header, not a big frame
-  int64_t ny = 0;
-  std::vector<int64_t> fn((size_t)n_frames, 0);
-  std::vector<int> fdepth((size_t)n_frames, 0);
-  for (int f = 0; f < n_frames; ++f) {
-    int32_t org[3];
-    PCC_TRY(pcc_octree_peek(slots[f].p, slots[f].len, &fn[f], &fdepth[f], org));
-    PCC_REQUIRE(fn[f] >= 0 && fn[f] <= ((int64_t)slots[f].len + 64) * 4096, PCC_E_STREAM,
-                "pcc_decode_gop: frame %d announces %lld points in a %d-byte blob", f, (long long)fn[f], slots[f].len);
-    // The root cube must sit on the 2^depth grid of the biased latent lattice, as octree_root() places it: only then
-    // are the octree's upper levels the frame's stride-16 / stride-32 coordinate sets, whose sizes the device path
-    // below takes from the geometry decoder without a read-back.  An origin off that grid (a flipped bit in the 12
-    // origin bytes passes every other check) would make those counts too small for the kernels that trust them.
-    if (fn[f] > 0) {
-      const int d = fdepth[f];
-      PCC_REQUIRE(d >= 1 && d <= 13, PCC_E_STREAM, "pcc_decode_gop: frame %d: octree depth %d", f, d);
-      for (int a = 0; a < 3; ++a) {
-        const int64_t biased = (int64_t)org[a] + 4096;
-        PCC_REQUIRE(biased >= 0 && biased + ((int64_t)1 << d) <= 8192 && (biased & (((int64_t)1 << d) - 1)) == 0,
-                    PCC_E_STREAM, "pcc_decode_gop: frame %d: octree origin %d (axis %d) is not on the 2^%d grid", f,
-                    org[a], a, d);
+  int check_sizes() {
+    fn.assign((size_t)n_frames, 0);
+    fdepth.assign((size_t)n_frames, 0);
+    for (int f = 0; f < n_frames; ++f) {
+      int32_t org[3];
+      PCC_TRY(pcc_octree_peek(slots[f].p, slots[f].len, &fn[f], &fdepth[f], org));
+      PCC_REQUIRE(fn[f] >= 0 && fn[f] <= ((int64_t)slots[f].len + 64) * 4096, PCC_E_STREAM,
+                  "pcc_decode_gop: frame %d announces %lld points in a %d-byte blob", f, (long long)fn[f], slots[f].len);
+      // The root cube must sit on the 2^depth grid of the biased latent lattice, as octree_root() places it: only then
+      // are the octree's upper levels the frame's stride-16 / stride-32 coordinate sets, whose sizes the device path
+      // below takes from the geometry decoder without a read-back.  An origin off that grid (a flipped bit in the 12
+      // origin bytes passes every other check) would make those counts too small for the kernels that trust them.
+      if (fn[f] > 0) {
+        const int d = fdepth[f];
+        PCC_REQUIRE(d >= 1 && d <= 13, PCC_E_STREAM, "pcc_decode_gop: frame %d: octree depth %d", f, d);
+        for (int a = 0; a < 3; ++a) {
+          const int64_t biased = (int64_t)org[a] + 4096;
+          PCC_REQUIRE(biased >= 0 && biased + ((int64_t)1 << d) <= 8192 && (biased & (((int64_t)1 << d) - 1)) == 0,
+                      PCC_E_STREAM, "pcc_decode_gop: frame %d: octree origin %d (axis %d) is not on the 2^%d grid", f,
+                      org[a], a, d);
+        }
       }
+      ny += fn[f];
     }
-    ny += fn[f];
+    PCC_REQUIRE(ny == ny_hdr, PCC_E_STREAM, "pcc_decode_gop: container says N_y=%d, geometry gives %lld", ny_hdr,
+                (long long)ny);
+    PCC_REQUIRE(nz_hdr <= ny_hdr, PCC_E_STREAM, "pcc_decode_gop: container says N_z=%d > N_y=%d", nz_hdr, ny_hdr);
+    PCC_REQUIRE(ny_hdr <= kMaxLatentRows, PCC_E_STREAM, "pcc_decode_gop: container says N_y=%d, this build decodes at most %lld",
+                ny_hdr, (long long)kMaxLatentRows);
+    return PCC_OK;
   }
-  PCC_REQUIRE(ny == ny_hdr, PCC_E_STREAM, "pcc_decode_gop: container says N_y=%d, geometry gives %lld", ny_hdr,
-              (long long)ny);
-  PCC_REQUIRE(nz_hdr <= ny_hdr, PCC_E_STREAM, "pcc_decode_gop: container says N_z=%d > N_y=%d", nz_hdr, ny_hdr);
-  PCC_REQUIRE(ny_hdr <= kMaxLatentRows, PCC_E_STREAM, "pcc_decode_gop: container says N_y=%d, this build decodes at most %lld",
-              ny_hdr, (long long)kMaxLatentRows);
-
-  // z string: nothing from the GPU is needed, decode it on a helper thread right away
-  const Tensor *eb_cdf = find(cd, "entropy_bottleneck.quantized_cdf"), *eb_len = find(cd, "entropy_bottleneck.cdf_length"),
-               *eb_off = find(cd, "entropy_bottleneck.offset");
-  PCC_REQUIRE(eb_cdf && eb_len && eb_off, PCC_E_ARG, "pcc_decode_gop: entropy_bottleneck tables missing");
-  std::vector<int32_t> zsym;
-  int z_rc = PCC_OK;
-  std::string z_err;
-  struct WaitAll {  // the job references locals of this frame: never leave it while the job is running
-    PccWorkers& w;
-    ~WaitAll() { w.wait_all(); }
-  } wait_all{cd->workers};
-  cd->workers.ensure(1);
-  auto start_z_job = [&]() {
+  // z string: nothing from the GPU is needed, decode it on a helper thread (worker 0) right away
+  void start_z_job() {
     zsym.resize((size_t)std::max<int64_t>((int64_t)nz_hdr * cz, 1));
-    cd->workers.run(0, [&]() {
+    cd->workers.run(0, [this]() {
       if (nz_hdr == 0) return;
       std::vector<int32_t> idx((size_t)nz_hdr * cz);
       for (int c = 0; c < cz; ++c) std::fill(idx.begin() + (size_t)c * nz_hdr, idx.begin() + (size_t)(c + 1) * nz_hdr, c);
@@ -1979,17 +2071,18 @@ static int decode_gop_impl(pcc_codec* cd, const uint8_t* h_in, int64_t len, pcc_
                              eb_len->i32(), eb_off->i32(), (int)eb_cdf->dims[0], zsym.data());
       if (z_rc != PCC_OK) z_err = pcc_last_error();
     });
-  };
-  // N_z is still only an announced number here.  Up to kEarlyZSymbols symbols (16 MB of buffers) the job starts at once
-  // and overlaps the geometry decode; a container announcing more waits until the geometry streams have confirmed N_y.
-  const bool z_early = !v1 && (int64_t)nz_hdr * cz <= kEarlyZSymbols;
-  if (z_early) start_z_job();
-  // version 1: the streams are decoded on the device; their headers are checked here, on the host copy
-  int64_t z_steps = 0, z_chunks = 0, y_steps = 0, y_chunks = 0;
-  int32_t* d_status = nullptr;
-  uint8_t* d_streams_early = nullptr;   // version 1: the strings in HBM and the z symbols, when queued before the geometry
-  int32_t* zsym_early = nullptr;
-  if (v1) {
+  }
+  int start_z() {
+    eb_cdf = find(cd, "entropy_bottleneck.quantized_cdf");
+    eb_len = find(cd, "entropy_bottleneck.cdf_length");
+    eb_off = find(cd, "entropy_bottleneck.offset");
+    PCC_REQUIRE(eb_cdf && eb_len && eb_off, PCC_E_ARG, "pcc_decode_gop: entropy_bottleneck tables missing");
+    cd->workers.ensure(1);
+    // N_z is still only an announced number here.  Up to kEarlyZSymbols symbols (16 MB of buffers) the job starts at once
+    // and overlaps the geometry decode; a container announcing more waits until the geometry streams have confirmed N_y.
+    z_early = !v1 && (int64_t)nz_hdr * cz <= kEarlyZSymbols;
+    if (z_early) start_z_job();
+    if (!v1) return PCC_OK;
     int64_t zn = 0, yn = 0;
     PCC_TRY(pcc_rans_stream_info(zstr, zlen, &zn, &z_steps, &z_chunks));
     PCC_TRY(pcc_rans_stream_info(ystr, ylen, &yn, &y_steps, &y_chunks));
@@ -2006,112 +2099,66 @@ static int decode_gop_impl(pcc_codec* cd, const uint8_t* h_in, int64_t len, pcc_
     // ... and the z stream is decoded at once (its symbol count is what its own header says, checked against the
     // container's above; up to kEarlyZSymbols of them, like the host job of version 0): the kernel runs while this thread
     // decodes the octrees
-    if ((int64_t)nz_hdr * cz <= kEarlyZSymbols) {
-      const size_t zpad = ((size_t)zlen + 255) & ~(size_t)255;
-      CODEC_ALLOC(d_str, uint8_t, zpad + (size_t)ylen + 256);
-      CODEC_ALLOC(zs, int32_t, std::max<int64_t>((int64_t)nz_hdr, 1) * cz);
-      PCC_HIP(hipMemcpyAsync(d_str, cd->pin_dec.p, zpad + (size_t)ylen, hipMemcpyHostToDevice, st));
-      PCC_TRY(pcc_rans_decode_dev(ctx, cd->eb_dev, d_str, zlen, (int64_t)nz_hdr * cz, z_steps, z_chunks, nullptr,
-                                  std::max<int64_t>(nz_hdr, 1), zs, d_status));
-      d_streams_early = d_str;
-      zsym_early = zs;
-    }
+    if ((int64_t)nz_hdr * cz <= kEarlyZSymbols) return z_stream_dev(&zsym_early);
+    return PCC_OK;
   }
-
+  // version 1: both strings into HBM and the z string decoded there into *zs (allocated here when null)
+  int z_stream_dev(int32_t** zs) {
+    const size_t zpad = ((size_t)zlen + 255) & ~(size_t)255;
+    CODEC_ALLOC(d_str, uint8_t, zpad + (size_t)ylen + 256);
+    if (!*zs) *zs = (int32_t*)cd->pool.alloc(sizeof(int32_t) * (size_t)(std::max<int64_t>((int64_t)nz_hdr, 1) * cz));
+    if (!*zs) return PCC_E_NOMEM;
+    PCC_HIP(hipMemcpyAsync(d_str, cd->pin_dec.p, zpad + (size_t)ylen, hipMemcpyHostToDevice, st));
+    d_ystr = d_str + zpad;
+    return pcc_rans_decode_dev(ctx, cd->eb_dev, d_str, zlen, (int64_t)nz_hdr * cz, z_steps, z_chunks, nullptr,
+                               std::max<int64_t>(nz_hdr, 1), *zs, d_status);
+  }
   // ---- step 2: latent coordinates of every frame (codec_parallel.py:266-289)
-  t0 = now_s();
   // Every frame's stream is decoded into a vector that grows with what the stream holds; only after all of them have
   // confirmed their announced counts is anything sized from N_y.
   // The octree's upper levels ARE the stride-16 / stride-32 coordinate sets of the frame (its root cube is aligned to
   // the same power-of-two grid — checked above), so their sizes come out of the geometry decoder and the device never
   // has to report them back; the leaves of an octree are distinct by construction and the range check is done here on
   // the host.
-  int n_batch = 0;
-  int64_t n16 = 0, n32 = 0;
-  std::vector<std::vector<int32_t>> fpts((size_t)n_frames);
-  // The rows (frame, 8 x, 8 y, 8 z) of all latents, in pinned memory for the upload.  ny is the sum of the announced
-  // counts, bounded above; a frame's rows are written only by what its stream decoded.
-  PCC_TRY(cd->pin_keys.ensure((size_t)std::max<int64_t>(ny, 1) * 16));
-  int32_t* yc_h = (int32_t*)cd->pin_keys.p;  // [ny,4]
-  std::vector<int64_t> frow((size_t)n_frames + 1, 0);
-  for (int f = 0; f < n_frames; ++f) frow[(size_t)f + 1] = frow[(size_t)f] + fn[f];
-  // blob version 3: the parts of all frames decoded side by side on the codec's threads (worker 0 may hold the z job:
-  // workers 1 .. take parts, this thread takes the first of every round).  A job decodes its part and writes its rows
-  // itself — the part's leaf count is in its header and the part's decoder holds the stream to it —, so what is left
-  // for this thread is the check of the parts against each other.
-  struct PartJob {
-    int f, k;
-    const uint8_t* p;
-    int64_t len, n, row0;
-    int32_t org[3];
-    PccOctPart out;
-    bool out_of_range = false;
-    int rc = PCC_OK;
-    std::string err;
-  };
-  std::vector<PartJob> pjobs;
-  std::vector<int> fpart0((size_t)n_frames, -1), fparts((size_t)n_frames, 0);
-  for (int f = 0; f < n_frames; ++f) {
-    if (fn[f] == 0 || slots[f].p[1] != 3) continue;
-    int K = 0;
-    const uint8_t* pp[16];
-    int64_t pl[16];
-    PCC_TRY(pcc_octree_parts(slots[f].p, slots[f].len, &K, pp, pl));   // the parts' counts add up to fn[f]
-    int32_t org[3];
-    PCC_TRY(pcc_octree_peek(slots[f].p, slots[f].len, nullptr, nullptr, org));
-    fpart0[f] = (int)pjobs.size();
-    fparts[f] = K;
-    int64_t row = frow[(size_t)f];
-    for (int k = 0; k < K; ++k) {
-      pjobs.emplace_back();
-      PartJob& pj = pjobs.back();
-      pj.f = f;
-      pj.k = k;
-      pj.p = pp[k];
-      pj.len = pl[k];
-      PCC_TRY(pcc_octree_peek(pp[k], pl[k], &pj.n, nullptr, nullptr));
-      pj.row0 = row;
-      memcpy(pj.org, org, sizeof(org));
-      row += pj.n;
+  int geometry() {
+    std::vector<std::vector<int32_t>> fpts((size_t)n_frames);
+    // The rows (frame, 8 x, 8 y, 8 z) of all latents, in pinned memory for the upload.  ny is the sum of the announced
+    // counts, bounded above; a frame's rows are written only by what its stream decoded.
+    PCC_TRY(cd->pin_keys.ensure((size_t)std::max<int64_t>(ny, 1) * 16));
+    int32_t* yc_h = (int32_t*)cd->pin_keys.p;  // [ny,4]
+    std::vector<int64_t> frow((size_t)n_frames + 1, 0);
+    for (int f = 0; f < n_frames; ++f) frow[(size_t)f + 1] = frow[(size_t)f] + fn[f];
+    // blob version 3: the parts of all frames decoded side by side on the codec's threads (worker 0 may hold the z job:
+    // workers 1 .. take parts, this thread takes the first of every round).  A job decodes its part and writes its rows
+    // itself — the part's leaf count is in its header and the part's decoder holds the stream to it —, so what is left
+    // for this thread is the check of the parts against each other.
+    std::vector<PartJob> pjobs;
+    std::vector<int> fpart0((size_t)n_frames, -1), fparts((size_t)n_frames, 0);
+    for (int f = 0; f < n_frames; ++f) {
+      if (fn[f] == 0 || slots[f].p[1] != 3) continue;
+      int K = 0;
+      const uint8_t* pp[16];
+      int64_t pl[16];
+      PCC_TRY(pcc_octree_parts(slots[f].p, slots[f].len, &K, pp, pl));   // the parts' counts add up to fn[f]
+      int32_t org[3];
+      PCC_TRY(pcc_octree_peek(slots[f].p, slots[f].len, nullptr, nullptr, org));
+      fpart0[f] = (int)pjobs.size();
+      fparts[f] = K;
+      int64_t row = frow[(size_t)f];
+      for (int k = 0; k < K; ++k) {
+        int64_t n = 0;
+        PCC_TRY(pcc_octree_peek(pp[k], pl[k], &n, nullptr, nullptr));
+        pjobs.push_back({f, k, pp[k], pl[k], n, row, {org[0], org[1], org[2]}});
+        row += n;
+      }
     }
-  }
-  if (!pjobs.empty()) {
     constexpr int kPartThreads = 8;
-    auto run_job = [&pjobs, yc_h](int j) {
-      PartJob& pj = pjobs[(size_t)j];
-      pj.rc = pcc_octree_unpack_part(pj.p, pj.len, &pj.out);
-      if (pj.rc != PCC_OK) {
-        pj.err = pcc_last_error();
-        return;
-      }
-      if ((int64_t)pj.out.cells.size() != pj.n) {   // (the part's decoder has checked this against the part's header)
-        pj.rc = PCC_E_STREAM;
-        pj.err = "part decoded another number of leaves than its header says";
-        return;
-      }
-      int32_t xyz[3 * 64];
-      bool bad = false;
-      for (int64_t i0 = 0; i0 < pj.n; i0 += 64) {
-        const int64_t m = std::min<int64_t>(64, pj.n - i0);
-        pcc_octree_cells_to_points(pj.out.cells.data() + i0, m, pj.org, xyz);
-        int32_t* dst = yc_h + 4 * (pj.row0 + i0);
-        for (int64_t i = 0; i < m; ++i) {
-          const int32_t x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-          bad |= (x < -4096) | (x > 4095) | (y < -4096) | (y > 4095) | (z < -4096) | (z > 4095);
-          dst[4 * i] = pj.f;
-          dst[4 * i + 1] = x * 8;
-          dst[4 * i + 2] = y * 8;
-          dst[4 * i + 3] = z * 8;
-        }
-      }
-      pj.out_of_range = bad;
-    };
-    cd->workers.ensure(kPartThreads);
     const int nj = (int)pjobs.size();
+    if (nj > 0) cd->workers.ensure(kPartThreads);
     for (int j0 = 0; j0 < nj; j0 += kPartThreads) {
       const int j1 = std::min(nj, j0 + kPartThreads);
-      for (int j = j0 + 1; j < j1; ++j) cd->workers.run(j - j0, [&run_job, j]() { run_job(j); });
-      run_job(j0);
+      for (int j = j0 + 1; j < j1; ++j) cd->workers.run(j - j0, [&pjobs, yc_h, j]() { run_part_job(pjobs[(size_t)j], yc_h); });
+      run_part_job(pjobs[(size_t)j0], yc_h);
       cd->workers.wait_range(1, kPartThreads);
     }
     for (const PartJob& pj : pjobs)
@@ -2119,70 +2166,58 @@ static int decode_gop_impl(pcc_codec* cd, const uint8_t* h_in, int64_t len, pcc_
         pcc_set_error("pcc_decode_gop (geometry, frame %d part %d): %s", pj.f, pj.k, pj.err.c_str());
         return pj.rc;
       }
-  }
-  bool out_of_range = false;
-  for (int f = 0; f < n_frames; ++f) {
-    if (fn[f] == 0) continue;
-    int64_t level_n[16];
-    if (slots[f].p[1] == 3) {   // the parts against each other: order, counts; the rows are written
-      for (int L = 0; L < 16; ++L) level_n[L] = 0;
-      bool any = false;
-      uint64_t last = 0;
-      int64_t total = 0;
-      for (int k = 0; k < fparts[f]; ++k) {
-        const PartJob& pj = pjobs[(size_t)(fpart0[f] + k)];
-        out_of_range |= pj.out_of_range;
-        if (pj.out.cells.empty()) continue;
-        PCC_REQUIRE(!any || (pj.out.cells.front() >> 6) > (last >> 6), PCC_E_STREAM,
-                    "pcc_decode_gop: frame %d: part %d begins inside or in front of the cell the part before it ends in", f, k);
-        any = true;
-        last = pj.out.cells.back();
-        total += (int64_t)pj.out.cells.size();
-        for (int L = 0; L < 16; ++L) level_n[L] += pj.out.level_n[L];
-      }
-      PCC_REQUIRE(total == fn[f], PCC_E_STREAM, "pcc_decode_gop: frame %d decoded %lld points, announced %lld", f, (long long)total,
-                  (long long)fn[f]);
-    } else {
-      if (slots[f].p[1] == 2) {   // blob version 2: decoded by the GPU; fn[f] has passed the plausibility checks above
-        int64_t n2 = 0;
-        fpts[f].resize((size_t)(3 * fn[f]));
-        PCC_TRY(pcc_octree2_decode(ctx, slots[f].p, slots[f].len, nullptr, fpts[f].data(), fn[f], &n2, level_n));
+    bool out_of_range = false;
+    for (int f = 0; f < n_frames; ++f) {
+      if (fn[f] == 0) continue;
+      int64_t level_n[16];
+      if (slots[f].p[1] == 3) {   // the parts against each other: order, counts; the rows are written
+        for (int L = 0; L < 16; ++L) level_n[L] = 0;
+        bool any = false;
+        uint64_t last = 0;
+        int64_t total = 0;
+        for (int k = 0; k < fparts[f]; ++k) {
+          const PartJob& pj = pjobs[(size_t)(fpart0[f] + k)];
+          out_of_range |= pj.out_of_range;
+          if (pj.out.cells.empty()) continue;
+          PCC_REQUIRE(!any || (pj.out.cells.front() >> 6) > (last >> 6), PCC_E_STREAM,
+                      "pcc_decode_gop: frame %d: part %d begins inside or in front of the cell the part before it ends in", f, k);
+          any = true;
+          last = pj.out.cells.back();
+          total += (int64_t)pj.out.cells.size();
+          for (int L = 0; L < 16; ++L) level_n[L] += pj.out.level_n[L];
+        }
+        PCC_REQUIRE(total == fn[f], PCC_E_STREAM, "pcc_decode_gop: frame %d decoded %lld points, announced %lld", f, (long long)total,
+                    (long long)fn[f]);
       } else {
-        PCC_TRY(pcc_octree_unpack_vec(slots[f].p, slots[f].len, &fpts[f], level_n));
+        if (slots[f].p[1] == 2) {   // blob version 2: decoded by the GPU; fn[f] has passed the plausibility checks above
+          int64_t n2 = 0;
+          fpts[f].resize((size_t)(3 * fn[f]));
+          PCC_TRY(pcc_octree2_decode(ctx, slots[f].p, slots[f].len, nullptr, fpts[f].data(), fn[f], &n2, level_n));
+        } else {
+          PCC_TRY(pcc_octree_unpack_vec(slots[f].p, slots[f].len, &fpts[f], level_n));
+        }
+        PCC_REQUIRE((int64_t)fpts[f].size() == 3 * fn[f], PCC_E_STREAM, "pcc_decode_gop: frame %d decoded %zu points, announced %lld",
+                    f, fpts[f].size() / 3, (long long)fn[f]);
+        out_of_range |= put_leaf_rows(fpts[f].data(), fn[f], f, yc_h + 4 * frow[(size_t)f]);
       }
-      PCC_REQUIRE((int64_t)fpts[f].size() == 3 * fn[f], PCC_E_STREAM, "pcc_decode_gop: frame %d decoded %zu points, announced %lld",
-                  f, fpts[f].size() / 3, (long long)fn[f]);
-      const int32_t* pts = fpts[f].data();
-      int32_t* dst = yc_h + 4 * frow[(size_t)f];
-      for (int64_t i = 0; i < fn[f]; ++i) {
-        const int32_t x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-        out_of_range |= (x < -4096) | (x > 4095) | (y < -4096) | (y > 4095) | (z < -4096) | (z > 4095);
-        dst[4 * i] = f;
-        dst[4 * i + 1] = x * 8;
-        dst[4 * i + 2] = y * 8;
-        dst[4 * i + 3] = z * 8;
-      }
+      const int depth = fdepth[f];
+      n16 += depth >= 1 ? level_n[depth - 1] : 1;
+      n32 += depth >= 2 ? level_n[depth - 2] : 1;
+      n_batch = f + 1;
     }
-    const int depth = fdepth[f];
-    n16 += depth >= 1 ? level_n[depth - 1] : 1;
-    n32 += depth >= 2 ? level_n[depth - 2] : 1;
-    n_batch = f + 1;
+    if (!z_early && !v1) start_z_job();
+    PCC_REQUIRE(!out_of_range && n_batch <= 65535, PCC_E_RANGE, "pcc_decode_gop: decoded coordinate out of range");
+    return PCC_OK;
   }
-  if (!z_early && !v1) start_z_job();
-  PCC_REQUIRE(!out_of_range && n_batch <= 65535, PCC_E_RANGE, "pcc_decode_gop: decoded coordinate out of range");
-  ts[1] = now_s() - t0;
-
   // ---- step 3: z coordinates re-derived from the y coordinates, z decoded (codec_parallel.py:291-318)
-  t0 = now_s();
-  CS* ycs;
-  {
+  int z_decode() {
     std::vector<int64_t> y_level_n(2, 0);
     CODEC_ALLOC(yc, int32_t, 4 * std::max<int64_t>(ny, 1));
     CODEC_ALLOC(keys, uint64_t, std::max<int64_t>(ny, 1));
     CODEC_ALLOC(flag, int32_t, 1);
     CODEC_ALLOC(perm, uint32_t, std::max<int64_t>(ny, 1));
     if (ny > 0) {
-      PCC_HIP(hipMemcpyAsync(yc, yc_h, (size_t)ny * 16, hipMemcpyHostToDevice, st));
+      PCC_HIP(hipMemcpyAsync(yc, cd->pin_keys.p, (size_t)ny * 16, hipMemcpyHostToDevice, st));
       PCC_HIP(hipMemsetAsync(flag, 0, 4, st));
       PCC_TRY(pcc_morton_keys(ctx, yc, ny, keys, flag));
       PCC_TRY(pcc_sort_pairs(ctx, keys, perm, ny, 0));
@@ -2191,38 +2226,27 @@ static int decode_gop_impl(pcc_codec* cd, const uint8_t* h_in, int64_t len, pcc_
     }
     ycs = new_set(cd, keys, ny, 8, std::max(n_batch, 1));
     if (ny > 0) ycs->down_counts = y_level_n;
-  }
-  PCC_TRY(down_of(cd, ycs));
-  PCC_TRY(down_of(cd, ycs->down));
-  CS* zcs = ycs->down->down;
-  View zv;
-  PCC_TRY(view_of(cd, zcs, &zv));
-  PCC_REQUIRE(zcs->n == nz_hdr, PCC_E_STREAM, "pcc_decode_gop: container says N_z=%d, coordinates give %lld", nz_hdr,
-              (long long)zcs->n);
-  cd->workers.wait_all();
-  if (z_rc != PCC_OK) {
-    pcc_set_error("pcc_decode_gop (z stream): %s", z_err.c_str());
-    return z_rc;
-  }
-  Feat z_hat;
-  uint8_t* d_ystr = nullptr;
-  {
+    PCC_TRY(down_of(cd, ycs));
+    PCC_TRY(down_of(cd, ycs->down));
+    CS* zcs = ycs->down->down;
+    View zv;
+    PCC_TRY(view_of(cd, zcs, &zv));
+    PCC_REQUIRE(zcs->n == nz_hdr, PCC_E_STREAM, "pcc_decode_gop: container says N_z=%d, coordinates give %lld", nz_hdr,
+                (long long)zcs->n);
+    cd->workers.wait_all();
+    if (z_rc != PCC_OK) {
+      pcc_set_error("pcc_decode_gop (z stream): %s", z_err.c_str());
+      return z_rc;
+    }
     const int64_t nz = zcs->n;
     CODEC_ALLOC(zsym_d_own, int32_t, std::max<int64_t>(nz, 1) * cz);
     int32_t* zsym_d = zsym_d_own;
     CODEC_ALLOC(rows, float, std::max<int64_t>(nz, 1) * cz);
     if (v1) {
-      const size_t zpad = ((size_t)zlen + 255) & ~(size_t)255;
-      if (zsym_early) {  // (nz == nz_hdr was checked above)
-        d_ystr = d_streams_early + zpad;
+      if (zsym_early)  // (nz == nz_hdr was checked above)
         zsym_d = zsym_early;
-      } else {
-        CODEC_ALLOC(d_str, uint8_t, zpad + (size_t)ylen + 256);
-        PCC_HIP(hipMemcpyAsync(d_str, cd->pin_dec.p, zpad + (size_t)ylen, hipMemcpyHostToDevice, st));
-        d_ystr = d_str + zpad;
-        PCC_TRY(pcc_rans_decode_dev(ctx, cd->eb_dev, d_str, zlen, nz * cz, z_steps, z_chunks, nullptr, std::max<int64_t>(nz, 1),
-                                    zsym_d, d_status));
-      }
+      else
+        PCC_TRY(z_stream_dev(&zsym_d));
       if (nz > 0) PCC_TRY(pcc_factorized_dequant(ctx, zsym_d, nz, cz, cd->dev["entropy_bottleneck.medians"], rows));
     } else if (nz > 0) {
       PCC_TRY(cd->pin_zsym.ensure((size_t)nz * cz * 4));
@@ -2233,19 +2257,10 @@ static int decode_gop_impl(pcc_codec* cd, const uint8_t* h_in, int64_t len, pcc_
     float* zf;
     PCC_TRY(rows_to_tensor(cd, zv, rows, cz, &zf));
     z_hat = {zcs, zf, cz};
+    return PCC_OK;
   }
-  ts[2] = now_s() - t0;
-
-  // ---- step 4: hyper synthesis
-  t0 = now_s();
-  Feat gp;
-  PCC_TRY(h_s_up(cd, z_hat, &gp));
-  ts[3] = now_s() - t0;
-
   // ---- step 5: decode y, de-quantise with offsets (codec_parallel.py:382-419)
-  t0 = now_s();
-  Feat y_hat;
-  {
+  int y_decode() {
     View yv;
     PCC_TRY(view_of(cd, ycs, &yv));
     float* params;
@@ -2296,10 +2311,7 @@ static int decode_gop_impl(pcc_codec* cd, const uint8_t* h_in, int64_t len, pcc_
                                           k == 0 ? 0 : sk_state[k - 1], k == 0 ? 0 : sk_word[k - 1], &end_x[k], &end_w[k]);
         };
         {
-          struct WaitPieces {
-            PccWorkers& w;
-            ~WaitPieces() { w.wait_all(); }
-          } wait_pieces{cd->workers};
+          WorkersGuard wait_pieces{&cd->workers};
           cd->workers.ensure(pieces - 1);
           for (int k = 1; k < pieces; ++k) cd->workers.run(k - 1, [&piece, k]() { piece(k); });
           piece(0);
@@ -2342,179 +2354,222 @@ static int decode_gop_impl(pcc_codec* cd, const uint8_t* h_in, int64_t len, pcc_
     float* yf;
     PCC_TRY(rows_to_tensor(cd, yv, rows, cy, &yf));
     y_hat = {ycs, yf, cy};
+    return PCC_OK;
   }
-  ts[4] = now_s() - t0;
-
   // ---- step 6: synthesis g_s with per-frame top-k pruning (codec_parallel.py:465-472)
-  t0 = now_s();
-  Feat h = y_hat;
-  const int nb = h.cs->n_batch;
-  {
-    const std::vector<int64_t>* o0;
-    PCC_TRY(offsets_of(cd, h.cs, &o0));
-  }
-  const float* rgb_cand = nullptr;  // colours of the last stage's candidate rows, when its conv evaluated the colour head
-  for (int j = 0; j < 3; ++j) {
-    const std::string uname = "g_s.up" + std::to_string(j);
-    const std::string cname = "g_s.conv" + std::to_string(j), oname = "g_s.occ" + std::to_string(j);
-    const float *w, *b, *hw, *hb;
-    const Tensor *tw, *thw;
-    PCC_TRY(wb(cd, cname, &w, &b, &tw));
-    PCC_TRY(wb(cd, oname, &hw, &hb, &thw));
-    const int cin = (int)tw->dims[1], cout = (int)tw->dims[2];
-    // the conv that forms its rule book in-kernel reads candidate rows stored channel-permuted: the up stage writes them so
-    const bool fused = pcc_conv_up_fused() && cin == 32 && cout == 32 && cd->dev.count(uname + ".weight#perm");
-    Feat u;
-    PCC_TRY(up2(cd, uname, h, 1, &u, fused));
-    const int64_t nu = u.cs->n;
-    // last stage: only the occupancy logit and the colour of a candidate row are ever read again, so the conv evaluates
-    // the colour head on every candidate row too and does not store the rows (128 B each) at all
-    const Tensor* tcol = find(cd, "g_s.color.weight");
-    const bool with_rgb = fused && j == 2 && nu > 0 && tcol && tcol->dims.size() == 2 && tcol->dims[0] == 32 &&
-                          tcol->dims[1] == 3;
-    float* feats = nullptr;
-    if (!with_rgb) {
-      feats = (float*)cd->pool.alloc(sizeof(float) * (size_t)(std::max<int64_t>(nu, 1) * cout));
-      if (!feats) return PCC_E_NOMEM;
+  int synthesis(const PackedDst* dst) {
+    Feat h = y_hat;
+    const int nb = h.cs->n_batch;
+    {
+      const std::vector<int64_t>* o0;
+      PCC_TRY(offsets_of(cd, h.cs, &o0));
     }
-    CODEC_ALLOC(logits, float, std::max<int64_t>(nu, 1));
-    if (with_rgb) {
-      int32_t* pn;
-      PCC_TRY(nbr27_of(cd, h.cs, &pn));
-      CODEC_ALLOC(rgb_all, float, nu * 3);
-      rgb_cand = rgb_all;
-      PCC_TRY(pcc_sparse_conv_head_up_perm_rgb(ctx, u.f, h.cs->n, pn, h.cs->n, w, b, 1, hw, hb, logits,
-                                               cd->dev["g_s.color.weight"], cd->dev["g_s.color.bias"], rgb_all));
-    } else if (fused && nu > 0) {
-      // rule book of the 8N candidates formed inside the conv from the book of the N rows below
-      int32_t* pn;
-      PCC_TRY(nbr27_of(cd, h.cs, &pn));
-      PCC_TRY(pcc_sparse_conv_head_up_perm(ctx, u.f, h.cs->n, pn, h.cs->n, w, b, 1, feats, hw, hb, logits));
-    } else if (nu == 0) {
-      // nothing to convolve
-    } else {
-      int32_t* nbr;
-      PCC_TRY(nbr27_of(cd, u.cs, &nbr));
-      PCC_TRY(pcc_sparse_conv_head(ctx, u.f, nu, nbr, 27, nu, nu, w, b, cin, cout, 1, feats, hw, hb, logits));
-    }
-    const std::vector<int64_t>* offs;
-    PCC_TRY(offsets_of(cd, u.cs, &offs));
-    std::vector<int64_t> kj((size_t)nb), new_offs(1, 0);
-    for (int f = 0; f < nb; ++f) {
-      const int64_t want = f < (int)ks[j].size() ? ks[j][f] : 0;
-      kj[f] = std::max<int64_t>(0, std::min<int64_t>(want, (*offs)[f + 1] - (*offs)[f]));
-      new_offs.push_back(new_offs.back() + kj[f]);
-    }
-    CODEC_ALLOC(keep, uint32_t, std::max<int64_t>(nu, 1));
-    // exact top-k keeps sum_f kj[f] rows: no count to read back, the stage stays asynchronous
-    const int64_t n_keep = new_offs.back();
-    // the stages that are followed by another want the rule book of what they keep (nbr27_of): the placement writes the
-    // candidates' positions among the kept rows as it goes
-    int32_t* keep_remap = nullptr;
-    if (nu > 0 && j + 1 < 3) {
-      keep_remap = (int32_t*)cd->pool.alloc(sizeof(int32_t) * (size_t)nu);
-      if (!keep_remap) return PCC_E_NOMEM;
-    }
-    if (nu > 0) PCC_TRY(pcc_topk_prune_map(ctx, logits, nu, nb, offs->data(), kj.data(), keep, nullptr, keep_remap));
-    CODEC_ALLOC(pkeys, uint64_t, std::max<int64_t>(n_keep, 1));
-    CODEC_ALLOC(pf, float, std::max<int64_t>(n_keep, 1) * cout);
-    // the kept rows stay where they are: the next up stage / the colour head read them through `keep`
-    const bool in_place = cout == 32;
-    if (n_keep > 0) {
-      if (!u.cs->keys && u.cs->gen_parent) {   // the kept candidates' keys from their parents': the 8N are never written
-        uint64_t* pk;
-        PCC_TRY(keys_of(cd, u.cs->gen_parent, &pk));
-        PCC_TRY(pcc_up_coords_rows(ctx, pk, u.cs->gen_parent->n, 3 * log2i(u.cs->stride), keep, n_keep, pkeys));
-      } else {
-        PCC_TRY(pcc_gather_rows(ctx, u.cs->keys, keep, n_keep, 8, pkeys));
+    const float* rgb_cand = nullptr;  // colours of the last stage's candidate rows, when its conv evaluated the colour head
+    for (int j = 0; j < 3; ++j) {
+      const std::string uname = "g_s.up" + std::to_string(j);
+      const std::string cname = "g_s.conv" + std::to_string(j), oname = "g_s.occ" + std::to_string(j);
+      const float *w, *b, *hw, *hb;
+      const Tensor *tw, *thw;
+      PCC_TRY(wb(cd, cname, &w, &b, &tw));
+      PCC_TRY(wb(cd, oname, &hw, &hb, &thw));
+      const int cin = (int)tw->dims[1], cout = (int)tw->dims[2];
+      // the conv that forms its rule book in-kernel reads candidate rows stored channel-permuted: the up stage writes them so
+      const bool fused = pcc_conv_up_fused() && cin == 32 && cout == 32 && cd->dev.count(uname + ".weight#perm");
+      Feat u;
+      PCC_TRY(up2(cd, uname, h, 1, &u, fused));
+      const int64_t nu = u.cs->n;
+      // last stage: only the occupancy logit and the colour of a candidate row are ever read again, so the conv evaluates
+      // the colour head on every candidate row too and does not store the rows (128 B each) at all
+      const Tensor* tcol = find(cd, "g_s.color.weight");
+      const bool with_rgb = fused && j == 2 && nu > 0 && tcol && tcol->dims.size() == 2 && tcol->dims[0] == 32 &&
+                            tcol->dims[1] == 3;
+      float* feats = nullptr;
+      if (!with_rgb) {
+        feats = (float*)cd->pool.alloc(sizeof(float) * (size_t)(std::max<int64_t>(nu, 1) * cout));
+        if (!feats) return PCC_E_NOMEM;
       }
-      if (!in_place) PCC_TRY(pcc_gather_rows(ctx, feats, keep, n_keep, 4 * cout, pf));
+      CODEC_ALLOC(logits, float, std::max<int64_t>(nu, 1));
+      if (with_rgb) {
+        int32_t* pn;
+        PCC_TRY(nbr27_of(cd, h.cs, &pn));
+        CODEC_ALLOC(rgb_all, float, nu * 3);
+        rgb_cand = rgb_all;
+        PCC_TRY(pcc_sparse_conv_head_up_perm_rgb(ctx, u.f, h.cs->n, pn, h.cs->n, w, b, 1, hw, hb, logits,
+                                                 cd->dev["g_s.color.weight"], cd->dev["g_s.color.bias"], rgb_all));
+      } else if (fused && nu > 0) {
+        // rule book of the 8N candidates formed inside the conv from the book of the N rows below
+        int32_t* pn;
+        PCC_TRY(nbr27_of(cd, h.cs, &pn));
+        PCC_TRY(pcc_sparse_conv_head_up_perm(ctx, u.f, h.cs->n, pn, h.cs->n, w, b, 1, feats, hw, hb, logits));
+      } else if (nu == 0) {
+        // nothing to convolve
+      } else {
+        int32_t* nbr;
+        PCC_TRY(nbr27_of(cd, u.cs, &nbr));
+        PCC_TRY(pcc_sparse_conv_head(ctx, u.f, nu, nbr, 27, nu, nu, w, b, cin, cout, 1, feats, hw, hb, logits));
+      }
+      const std::vector<int64_t>* offs;
+      PCC_TRY(offsets_of(cd, u.cs, &offs));
+      std::vector<int64_t> kj((size_t)nb), new_offs(1, 0);
+      for (int f = 0; f < nb; ++f) {
+        const int64_t want = f < (int)ks[j].size() ? ks[j][f] : 0;
+        kj[f] = std::max<int64_t>(0, std::min<int64_t>(want, (*offs)[f + 1] - (*offs)[f]));
+        new_offs.push_back(new_offs.back() + kj[f]);
+      }
+      CODEC_ALLOC(keep, uint32_t, std::max<int64_t>(nu, 1));
+      // exact top-k keeps sum_f kj[f] rows: no count to read back, the stage stays asynchronous
+      const int64_t n_keep = new_offs.back();
+      // the stages that are followed by another want the rule book of what they keep (nbr27_of): the placement writes the
+      // candidates' positions among the kept rows as it goes
+      int32_t* keep_remap = nullptr;
+      if (nu > 0 && j + 1 < 3) {
+        keep_remap = (int32_t*)cd->pool.alloc(sizeof(int32_t) * (size_t)nu);
+        if (!keep_remap) return PCC_E_NOMEM;
+      }
+      if (nu > 0) PCC_TRY(pcc_topk_prune_map(ctx, logits, nu, nb, offs->data(), kj.data(), keep, nullptr, keep_remap));
+      CODEC_ALLOC(pkeys, uint64_t, std::max<int64_t>(n_keep, 1));
+      CODEC_ALLOC(pf, float, std::max<int64_t>(n_keep, 1) * cout);
+      // the kept rows stay where they are: the next up stage / the colour head read them through `keep`
+      const bool in_place = cout == 32;
+      if (n_keep > 0) {
+        if (!u.cs->keys && u.cs->gen_parent) {   // the kept candidates' keys from their parents': the 8N are never written
+          uint64_t* pk;
+          PCC_TRY(keys_of(cd, u.cs->gen_parent, &pk));
+          PCC_TRY(pcc_up_coords_rows(ctx, pk, u.cs->gen_parent->n, 3 * log2i(u.cs->stride), keep, n_keep, pkeys));
+        } else {
+          PCC_TRY(pcc_gather_rows(ctx, u.cs->keys, keep, n_keep, 8, pkeys));
+        }
+        if (!in_place) PCC_TRY(pcc_gather_rows(ctx, feats, keep, n_keep, 4 * cout, pf));
+      }
+      CS* ps = new_set(cd, pkeys, n_keep, u.cs->stride, nb);
+      ps->offsets = new_offs;
+      ps->subset_of = u.cs;
+      ps->keep = keep;
+      ps->keep_remap = keep_remap;
+      h = {ps, in_place ? feats : pf, cout, in_place ? keep : nullptr};
     }
-    CS* ps = new_set(cd, pkeys, n_keep, u.cs->stride, nb);
-    ps->offsets = new_offs;
-    ps->subset_of = u.cs;
-    ps->keep = keep;
-    ps->keep_remap = keep_remap;
-    h = {ps, in_place ? feats : pf, cout, in_place ? keep : nullptr};
-  }
-  {
-    const float *w, *b;
-    const Tensor* tw;
-    PCC_TRY(wb(cd, "g_s.color", &w, &b, &tw));
-    const int64_t nr = h.cs->n;
-    CODEC_ALLOC(rgb, float, std::max<int64_t>(nr, 1) * 3);
-    CODEC_ALLOC(coords, int32_t, std::max<int64_t>(nr, 1) * 4);
-    if (nr > 0) {
-      if (rgb_cand && h.rows)
-        PCC_TRY(pcc_gather_rows(ctx, rgb_cand, h.rows, nr, 12, rgb));
-      else if (h.rows && (int)tw->dims[0] == 32 && (int)tw->dims[1] <= 8)
-        PCC_TRY(pcc_linear_gather(ctx, h.f, h.rows, nr, w, b, (int)tw->dims[1], 0, rgb));
-      else if (h.rows) {  // a head the fused form does not cover: gather first
-        CODEC_ALLOC(pf, float, nr * h.c);
-        PCC_TRY(pcc_gather_rows(ctx, h.f, h.rows, nr, 4 * h.c, pf));
-        PCC_TRY(pcc_linear(ctx, pf, nr, w, b, (int)tw->dims[0], (int)tw->dims[1], 0, rgb));
-      } else
-        PCC_TRY(pcc_linear(ctx, h.f, nr, w, b, (int)tw->dims[0], (int)tw->dims[1], 0, rgb));
-      uint64_t* hkeys;
-      PCC_TRY(keys_of(cd, h.cs, &hkeys));
-      PCC_TRY(pcc_keys_to_coords(ctx, hkeys, nr, coords));
+    {
+      const float *w, *b;
+      const Tensor* tw;
+      PCC_TRY(wb(cd, "g_s.color", &w, &b, &tw));
+      const int64_t nr = h.cs->n;
+      CODEC_ALLOC(rgb, float, std::max<int64_t>(nr, 1) * 3);
+      CODEC_ALLOC(coords, int32_t, std::max<int64_t>(nr, 1) * 4);
+      if (nr > 0) {
+        if (rgb_cand && h.rows)
+          PCC_TRY(pcc_gather_rows(ctx, rgb_cand, h.rows, nr, 12, rgb));
+        else if (h.rows && (int)tw->dims[0] == 32 && (int)tw->dims[1] <= 8)
+          PCC_TRY(pcc_linear_gather(ctx, h.f, h.rows, nr, w, b, (int)tw->dims[1], 0, rgb));
+        else if (h.rows) {  // a head the fused form does not cover: gather first
+          CODEC_ALLOC(pf, float, nr * h.c);
+          PCC_TRY(pcc_gather_rows(ctx, h.f, h.rows, nr, 4 * h.c, pf));
+          PCC_TRY(pcc_linear(ctx, pf, nr, w, b, (int)tw->dims[0], (int)tw->dims[1], 0, rgb));
+        } else
+          PCC_TRY(pcc_linear(ctx, h.f, nr, w, b, (int)tw->dims[0], (int)tw->dims[1], 0, rgb));
+        uint64_t* hkeys;
+        PCC_TRY(keys_of(cd, h.cs, &hkeys));
+        PCC_TRY(pcc_keys_to_coords(ctx, hkeys, nr, coords));
+      }
+      cd->rec_coords = coords;
+      cd->rec_colors = rgb;
+      cd->rec_n = nr;
+      cd->rec_offsets = h.cs->offsets;
     }
-    cd->rec_coords = coords;
-    cd->rec_colors = rgb;
-    cd->rec_n = nr;
-    cd->rec_offsets = h.cs->offsets;
+    return finish(dst);
   }
-  if (v1) {
-    PCC_TRY(cd->pin_flag.ensure(64));
-    PCC_HIP(hipMemcpyAsync(cd->pin_flag.p, d_status, 4, hipMemcpyDeviceToHost, st));
+  // version 1's stream status and pcc_decode_fetch_packed's work queued behind the last kernel, then the one
+  // synchronisation of the call: no trip through the caller in between
+  int finish(const PackedDst* dst) {
+    if (v1) {
+      PCC_TRY(cd->pin_flag.ensure(64));
+      PCC_HIP(hipMemcpyAsync(cd->pin_flag.p, d_status, 4, hipMemcpyDeviceToHost, st));
+    }
+    if (dst && cd->rec_n > 0) {
+      PCC_REQUIRE(cd->rec_n <= dst->cap && dst->points && dst->colors, PCC_E_ARG,
+                  "pcc_decode_gop_packed: %lld points decoded, destination holds %lld", (long long)cd->rec_n,
+                  (long long)dst->cap);
+      PCC_TRY(queue_packed(cd, dst->points, dst->colors));
+    }
+    PCC_TRY(pcc_sync(ctx));
+    if (v1 && *(volatile int32_t*)cd->pin_flag.p != 0) {
+      cd->rec_n = 0;
+      cd->rec_offsets.clear();
+      pcc_set_error("pcc_decode_gop: malformed interleaved rANS stream (status %d)", *(int32_t*)cd->pin_flag.p);
+      return PCC_E_STREAM;
+    }
+    return PCC_OK;
   }
-  if (dst && cd->rec_n > 0) {
-    // pcc_decode_fetch_packed's work, queued here: no synchronisation and no trip through the caller in between
-    const int64_t n = cd->rec_n;
-    PCC_REQUIRE(n <= dst->cap && dst->points && dst->colors, PCC_E_ARG,
-                "pcc_decode_gop_packed: %lld points decoded, destination holds %lld", (long long)n, (long long)dst->cap);
-    CODEC_ALLOC(xyz, int32_t, 3 * n);
-    CODEC_ALLOC(rgb3, float, 3 * n);
-    hipLaunchKernelGGL(k_pack_cloud, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int4*)cd->rec_coords,
-                       (const float*)cd->rec_colors, n, xyz, rgb3);
-    PCC_CHECK_LAUNCH();
-    PCC_HIP(hipMemcpyAsync(dst->points, xyz, (size_t)n * 12, hipMemcpyDefault, st));
-    PCC_HIP(hipMemcpyAsync(dst->colors, rgb3, (size_t)n * 12, hipMemcpyDefault, st));
-  }
-  PCC_TRY(pcc_sync(ctx));
-  if (v1 && *(volatile int32_t*)cd->pin_flag.p != 0) {
-    cd->rec_n = 0;
-    cd->rec_offsets.clear();
-    pcc_set_error("pcc_decode_gop: malformed interleaved rANS stream (status %d)", *(int32_t*)cd->pin_flag.p);
-    return PCC_E_STREAM;
-  }
-  ts[5] = now_s() - t0;
+};
 
+}  // namespace
+
+static int decode_gop_impl(pcc_codec* cd, const uint8_t* h_in, int64_t len, pcc_cloud_info* h_info,
+                           double* h_stage_s, const PackedDst* dst = nullptr) {
+  PCC_REQUIRE(cd && cd->ctx, PCC_E_ARG, "pcc_decode_gop: null codec");
+  PCC_REQUIRE(h_in && len >= 36 && h_info, PCC_E_STREAM, "pcc_decode_gop: container shorter than its header");
+  PCC_TRY(begin_call(cd));
+  cd->rec_n = 0;
+  cd->rec_offsets.clear();
+  DecodeCall c(cd);
+  PCC_TRY(timed(&c.ts[0], [&] { return c.parse(h_in, len); }));
+  PCC_TRY(c.check_sizes());
+  WorkersGuard z_job{&cd->workers};   // the z job reads the call's state: never leave while it is running
+  PCC_TRY(c.start_z());
+  PCC_TRY(timed(&c.ts[1], [&] { return c.geometry(); }));
+  PCC_TRY(timed(&c.ts[2], [&] { return c.z_decode(); }));
+  // ---- step 4: hyper synthesis
+  PCC_TRY(timed(&c.ts[3], [&] { return h_s_up(cd, c.z_hat, &c.gp); }));
+  PCC_TRY(timed(&c.ts[4], [&] { return c.y_decode(); }));
+  PCC_TRY(timed(&c.ts[5], [&] { return c.synthesis(dst); }));
   h_info->n_points = cd->rec_n;
-  h_info->n_frames = n_frames;
+  h_info->n_frames = c.n_frames;
   h_info->n_offsets = (int32_t)cd->rec_offsets.size();
   h_info->h_offsets = cd->rec_offsets.data();
   h_info->d_coords = cd->rec_coords;
   h_info->d_colors = cd->rec_colors;
-  h_info->q_g = qg;
-  h_info->q_a = qa;
-  if (h_stage_s) memcpy(h_stage_s, ts, 6 * sizeof(double));
+  h_info->q_g = c.qg;
+  h_info->q_a = c.qa;
+  if (h_stage_s) memcpy(h_stage_s, c.ts, 6 * sizeof(double));
   return PCC_OK;
 }
 
 // the library never throws across the ABI: allocation failures of the host containers become codes
+template <class F>
+static int no_throw(const char* name, int code, F&& call) {
+  try {
+    return call();
+  } catch (const std::bad_alloc&) {
+    pcc_set_error("%s: out of host memory", name);
+    return PCC_E_NOMEM;
+  } catch (const std::exception& e) {
+    pcc_set_error("%s: %s", name, e.what());
+    return code;
+  }
+}
+
+// the frame table of the per-frame entry points: arrays, their types and the frames' row offsets
+static int frame_table(const char* name, const void* const* pts, int points_i16, const void* const* cols, int colors_f64,
+                       const int64_t* h_n, int n_frames, FrameTab* t) {
+  memset(t, 0, sizeof(*t));
+  t->nf = n_frames;
+  t->pts_i16 = points_i16 ? 1 : 0;
+  t->cols_f64 = colors_f64 ? 1 : 0;
+  for (int f = 0; f < n_frames; ++f) {
+    PCC_REQUIRE(h_n[f] >= 0 && (h_n[f] == 0 || (pts[f] && cols[f])), PCC_E_ARG, "%s: frame %d: n=%lld or null arrays", name,
+                f, (long long)h_n[f]);
+    t->pts[f] = pts[f];
+    t->cols[f] = cols[f];
+    t->off[f + 1] = t->off[f] + h_n[f];
+  }
+  PCC_REQUIRE(t->off[n_frames] < ((int64_t)1 << 32), PCC_E_ARG, "%s: %lld points", name, (long long)t->off[n_frames]);
+  return PCC_OK;
+}
+
 extern "C" int pcc_encode_gop(pcc_codec* cd, const int32_t* d_coords, const float* d_feats, int64_t n,
                               int n_frames, const double* h_q, int n_q, pcc_buf* h_out, int64_t* h_k,
                               double* h_stage_s) {
-  try {
-    return encode_gop_impl(cd, d_coords, d_feats, n, n_frames, h_q, n_q, h_out, h_k, h_stage_s);
-  } catch (const std::bad_alloc&) {
-    pcc_set_error("pcc_encode_gop: out of host memory");
-    return PCC_E_NOMEM;
-  } catch (const std::exception& e) {
-    pcc_set_error("pcc_encode_gop: %s", e.what());
-    return PCC_E_ARG;
-  }
+  return no_throw("pcc_encode_gop", PCC_E_ARG,
+                  [&] { return encode_gop_impl(cd, d_coords, d_feats, n, n_frames, h_q, n_q, h_out, h_k, h_stage_s); });
 }
 
 extern "C" int pcc_encode_gop_frames(pcc_codec* cd, const void* const* h_d_points, int points_i16,
@@ -2525,30 +2580,13 @@ extern "C" int pcc_encode_gop_frames(pcc_codec* cd, const void* const* h_d_point
               "pcc_encode_gop_frames: %d frames, at most %d per call (concatenate and use pcc_encode_gop)", n_frames,
               PCC_MAX_FRAMES_ARG);
   FrameTab t;
-  memset(&t, 0, sizeof(t));
-  t.nf = n_frames;
-  t.pts_i16 = points_i16 ? 1 : 0;
-  t.cols_f64 = colors_f64 ? 1 : 0;
-  for (int f = 0; f < n_frames; ++f) {
-    PCC_REQUIRE(h_n[f] >= 0 && (h_n[f] == 0 || (h_d_points[f] && h_d_colors[f])), PCC_E_ARG,
-                "pcc_encode_gop_frames: frame %d: n=%lld or null arrays", f, (long long)h_n[f]);
-    t.pts[f] = h_d_points[f];
-    t.cols[f] = h_d_colors[f];
-    t.off[f + 1] = t.off[f] + h_n[f];
-  }
-  const int64_t n = t.off[n_frames];
-  PCC_REQUIRE(n < ((int64_t)1 << 32), PCC_E_ARG, "pcc_encode_gop_frames: %lld points", (long long)n);
-  try {
-    return encode_gop_impl(cd, nullptr, nullptr, n, n_frames, h_q, n_q, h_out, h_k, h_stage_s, &t);
-  } catch (const std::bad_alloc&) {
-    pcc_set_error("pcc_encode_gop_frames: out of host memory");
-    return PCC_E_NOMEM;
-  } catch (const std::exception& e) {
-    pcc_set_error("pcc_encode_gop_frames: %s", e.what());
-    return PCC_E_ARG;
-  }
+  PCC_TRY(frame_table("pcc_encode_gop_frames", h_d_points, points_i16, h_d_colors, colors_f64, h_n, n_frames, &t));
+  return no_throw("pcc_encode_gop_frames", PCC_E_ARG, [&] {
+    return encode_gop_impl(cd, nullptr, nullptr, t.off[n_frames], n_frames, h_q, n_q, h_out, h_k, h_stage_s, &t);
+  });
 }
 
+// the frame arrays in host memory: encode_gop_impl uploads them (the table's array pointers are replaced there)
 extern "C" int pcc_encode_gop_host_frames(pcc_codec* cd, const void* const* h_points, int points_i16,
                                           const void* const* h_colors, int colors_f64, const int64_t* h_n, int n_frames,
                                           const double* h_q, int n_q, pcc_buf* h_out, int64_t* h_k, double* h_stage_s) {
@@ -2556,55 +2594,23 @@ extern "C" int pcc_encode_gop_host_frames(pcc_codec* cd, const void* const* h_po
   PCC_REQUIRE(n_frames <= PCC_MAX_FRAMES_ARG, PCC_E_ARG, "pcc_encode_gop_host_frames: %d frames, at most %d per call",
               n_frames, PCC_MAX_FRAMES_ARG);
   FrameTab t;
-  memset(&t, 0, sizeof(t));
-  t.nf = n_frames;
-  t.pts_i16 = points_i16 ? 1 : 0;
-  t.cols_f64 = colors_f64 ? 1 : 0;
-  for (int f = 0; f < n_frames; ++f) {
-    PCC_REQUIRE(h_n[f] >= 0 && (h_n[f] == 0 || (h_points[f] && h_colors[f])), PCC_E_ARG,
-                "pcc_encode_gop_host_frames: frame %d: n=%lld or null arrays", f, (long long)h_n[f]);
-    t.off[f + 1] = t.off[f] + h_n[f];
-  }
-  const int64_t n = t.off[n_frames];
-  PCC_REQUIRE(n < ((int64_t)1 << 32), PCC_E_ARG, "pcc_encode_gop_host_frames: %lld points", (long long)n);
+  PCC_TRY(frame_table("pcc_encode_gop_host_frames", h_points, points_i16, h_colors, colors_f64, h_n, n_frames, &t));
   const HostFrames host{h_points, h_colors};
-  try {
-    return encode_gop_impl(cd, nullptr, nullptr, n, n_frames, h_q, n_q, h_out, h_k, h_stage_s, &t, &host);
-  } catch (const std::bad_alloc&) {
-    pcc_set_error("pcc_encode_gop_host_frames: out of host memory");
-    return PCC_E_NOMEM;
-  } catch (const std::exception& e) {
-    pcc_set_error("pcc_encode_gop_host_frames: %s", e.what());
-    return PCC_E_ARG;
-  }
+  return no_throw("pcc_encode_gop_host_frames", PCC_E_ARG, [&] {
+    return encode_gop_impl(cd, nullptr, nullptr, t.off[n_frames], n_frames, h_q, n_q, h_out, h_k, h_stage_s, &t, &host);
+  });
 }
 
 extern "C" int pcc_decode_gop(pcc_codec* cd, const uint8_t* h_in, int64_t len, pcc_cloud_info* h_info,
                               double* h_stage_s) {
-  try {
-    return decode_gop_impl(cd, h_in, len, h_info, h_stage_s);
-  } catch (const std::bad_alloc&) {
-    pcc_set_error("pcc_decode_gop: out of host memory");
-    return PCC_E_NOMEM;
-  } catch (const std::exception& e) {
-    pcc_set_error("pcc_decode_gop: %s", e.what());
-    return PCC_E_STREAM;
-  }
+  return no_throw("pcc_decode_gop", PCC_E_STREAM, [&] { return decode_gop_impl(cd, h_in, len, h_info, h_stage_s); });
 }
 
 extern "C" int pcc_decode_gop_packed(pcc_codec* cd, const uint8_t* h_in, int64_t len, int32_t* points, float* colors,
                                      int64_t cap_points, pcc_cloud_info* h_info, double* h_stage_s) {
   PCC_REQUIRE(points && colors && cap_points >= 0, PCC_E_ARG, "pcc_decode_gop_packed: null destination");
   const PackedDst dst{points, colors, cap_points};
-  try {
-    return decode_gop_impl(cd, h_in, len, h_info, h_stage_s, &dst);
-  } catch (const std::bad_alloc&) {
-    pcc_set_error("pcc_decode_gop_packed: out of host memory");
-    return PCC_E_NOMEM;
-  } catch (const std::exception& e) {
-    pcc_set_error("pcc_decode_gop_packed: %s", e.what());
-    return PCC_E_STREAM;
-  }
+  return no_throw("pcc_decode_gop_packed", PCC_E_STREAM, [&] { return decode_gop_impl(cd, h_in, len, h_info, h_stage_s, &dst); });
 }
 
 // Point count a container announces: the sum over its frames of the finest of the three k (the decoder keeps at most
@@ -2659,17 +2665,8 @@ extern "C" int pcc_decode_fetch_packed(pcc_codec* cd, int32_t* points, float* co
   if (cd->rec_n == 0) return PCC_OK;
   PCC_REQUIRE(cd->rec_coords && cd->rec_colors && points && colors, PCC_E_ARG,
               "pcc_decode_fetch_packed: no decoded GOP on this codec, or null destination");
-  hipStream_t st = cd->ctx->stream;
-  const int64_t n = cd->rec_n;
-  CODEC_ALLOC(xyz, int32_t, 3 * n);
-  CODEC_ALLOC(rgb, float, 3 * n);
-  hipLaunchKernelGGL(k_pack_cloud, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int4*)cd->rec_coords,
-                     (const float*)cd->rec_colors, n, xyz, rgb);
-  PCC_CHECK_LAUNCH();
-  // destinations may be device or host memory (pageable host memory is staged by the runtime)
-  PCC_HIP(hipMemcpyAsync(points, xyz, (size_t)n * 12, hipMemcpyDefault, st));
-  PCC_HIP(hipMemcpyAsync(colors, rgb, (size_t)n * 12, hipMemcpyDefault, st));
-  PCC_HIP(hipStreamSynchronize(st));
+  PCC_TRY(queue_packed(cd, points, colors));
+  PCC_HIP(hipStreamSynchronize(cd->ctx->stream));
   return PCC_OK;
 }
 
