@@ -11,9 +11,11 @@
 // stream runs analysis, hyper path and quantiser without a host synchronisation; the Q quality
 // streams are then coded on Q threads while this thread produces the geometry slots — their kernels
 // queue up behind the quantiser — and the z string; decoder: a helper thread decodes the z string
-// while the coordinates are rebuilt, and the first synthesis rule book is built during the y decode).
+// while the coordinates are rebuilt and everything that needs coordinates only is queued, the first synthesis rule
+// book is built during the y decode, and the cloud's points are widened to int32 on the codec's threads while its
+// colours cross the link).
 //
-// Host-only code (no kernels); compiled as HIP source for the runtime API.
+// Host code and the few kernels that reshape a call's inputs and outputs; compiled as HIP source.
 #include "common.h"
 
 #include <string.h>
@@ -250,6 +252,7 @@ struct pcc_codec {
   std::map<std::string, float*> dev;  // weights / biases / tables in HBM
   int c_y = 32, c_z = 32;
   PccRansTables* gc_tables = nullptr;  // coder tables of the Gaussian CDFs, built once (rans_gate.h)
+  PccRansTables* eb_tables = nullptr;  // ... and of the entropy bottleneck's (the decoder's z job); null = built per call
   // container version written by pcc_encode_gop* (pcc_codec_set_container_version): 0 = the reference's layout, y and z
   // strings single rANS streams coded on the host; 1 = flagged extension, y and z strings wave-interleaved streams
   // coded on the GPU (rans_gpu.hip).  The decoder reads the version from the container.
@@ -289,6 +292,15 @@ struct pcc_codec {
   float* rec_colors = nullptr;    // [n,3]
   int64_t rec_n = 0;
   std::vector<int64_t> rec_offsets;
+  // ... and its way to host memory (queue_packed): true when every coordinate of rec_coords came out of pcc_unmorton
+  // (16 bits per axis - 32768: inside int16 whatever the stream held); pack_batches' arrays when the last kernel of
+  // the decode wrote them as well (pool-owned, else null); staging of the int16 points, the event behind their copy
+  bool rec_i16 = false;
+  int16_t* rec_xyz16 = nullptr;   // [n,3]
+  float* rec_rgbp = nullptr;      // [n,3]
+  Pinned pin_out;
+  hipEvent_t out_pts = nullptr;
+  std::atomic<int> widen_status{0};
 };
 
 // ---------------------------------------------------------------- geometry slot (utils.py)
@@ -648,7 +660,31 @@ int h_s_up(pcc_codec* cd, const Feat& z_hat, Feat* pre) {
 // h_s output layer + features_at_coordinates(qcoords) in one: the reference evaluates the 32 -> 64 conv on every
 // descendant (4x the latent's rows) and then samples it at the latent's coordinates; a row's value depends only on its
 // own neighbour list, so the conv is run on the sampled rows alone (their rule-book columns), absent rows -> 0.
-int h_s_out_at(pcc_codec* cd, const Feat& pre, const CS* ycs, const View& yv, float** out) {
+//
+// The coordinate half of the structural form, for a caller that has the coordinate sets before the features (the
+// decoder, while the host still decodes z): *book = the latent voxels' rule-book columns among pre_cs's rows, or null
+// where the structure does not hold (h_s_out_at then takes the general form).
+// pre = up(up(z)) and z = down(down(y)): every latent voxel IS one of the 64 descendants of its stride-32
+// ancestor, its row and its rule-book column follow from the two parent maps and the book one level up — no
+// hash table, no lookup, no book of the descendants, and no row is absent (the conv's output is used as it is)
+int h_s_book_at(pcc_codec* cd, const CS* pre_cs, const CS* ycs, const View& yv, int32_t** book) {
+  *book = nullptr;
+  const int64_t m = yv.n;
+  const CS* z16 = ycs->down;
+  const CS* z32 = z16 ? z16->down : nullptr;
+  const bool by_structure = m > 0 && ycs->stride == 8 && ycs->n == m && z32 && ycs->parent_of && z16->parent_of &&
+                            pre_cs->gen_parent && pre_cs->gen_parent->gen_parent == z32;
+  if (!by_structure) return PCC_OK;
+  CODEC_ALLOC(nbr_sub, int32_t, 27 * m);
+  int32_t* pn;
+  PCC_TRY(nbr27_of(cd, pre_cs->gen_parent, &pn));
+  PCC_TRY(pcc_descendant_map(cd->ctx, pn, pre_cs->gen_parent->n, (const uint32_t*)yv.perm, (const uint64_t*)ycs->keys,
+                             (const int32_t*)ycs->parent_of, (const int32_t*)z16->parent_of, m, nbr_sub));
+  *book = nbr_sub;
+  return PCC_OK;
+}
+
+int h_s_out_at(pcc_codec* cd, const Feat& pre, const CS* ycs, const View& yv, float** out, int32_t* book = nullptr) {
   const int32_t* qcoords = yv.coords;
   const int64_t m = yv.n;
   const float *w, *b;
@@ -656,23 +692,13 @@ int h_s_out_at(pcc_codec* cd, const Feat& pre, const CS* ycs, const View& yv, fl
   PCC_TRY(wb(cd, "h_s.conv0", &w, &b, &tw));
   const int cin = (int)tw->dims[1], cout = (int)tw->dims[2];
   const int64_t cap = std::max<int64_t>(m, 1);
-  CODEC_ALLOC(nbr_sub, int32_t, 27 * cap);
   CODEC_ALLOC(o, float, cap * cout);
   if (m > 0) {
-    const CS* z16 = ycs->down;
-    const CS* z32 = z16 ? z16->down : nullptr;
-    const bool by_structure = ycs->stride == 8 && ycs->n == m && z32 && ycs->parent_of && z16->parent_of &&
-                              pre.cs->gen_parent && pre.cs->gen_parent->gen_parent == z32;
-    if (by_structure) {
-      // pre = up(up(z)) and z = down(down(y)): every latent voxel IS one of the 64 descendants of its stride-32
-      // ancestor, its row and its rule-book column follow from the two parent maps and the book one level up — no
-      // hash table, no lookup, no book of the descendants, and no row is absent (o = the conv's output as it is)
-      int32_t* pn;
-      PCC_TRY(nbr27_of(cd, pre.cs->gen_parent, &pn));
-      PCC_TRY(pcc_descendant_map(cd->ctx, pn, pre.cs->gen_parent->n, (const uint32_t*)yv.perm, (const uint64_t*)ycs->keys,
-                                 (const int32_t*)ycs->parent_of, (const int32_t*)z16->parent_of, m, nbr_sub));
-      PCC_TRY(pcc_sparse_conv(cd->ctx, pre.f, pre.cs->n, nbr_sub, 27, m, m, w, b, cin, cout, 0, o));
+    if (!book) PCC_TRY(h_s_book_at(cd, pre.cs, ycs, yv, &book));
+    if (book) {
+      PCC_TRY(pcc_sparse_conv(cd->ctx, pre.f, pre.cs->n, book, 27, m, m, w, b, cin, cout, 0, o));
     } else {  // general form: hash the descendants' keys and look the coordinates up
+      CODEC_ALLOC(nbr_sub, int32_t, 27 * cap);
       int32_t* nbr;
       PCC_TRY(nbr27_of(cd, pre.cs, &nbr));
       CODEC_ALLOC(qkeys, uint64_t, cap);
@@ -927,6 +953,9 @@ extern "C" pcc_codec* pcc_codec_create(const void* h_ckpt, size_t n, int device,
     const Tensor *eb_cdf = find(cd, "entropy_bottleneck.quantized_cdf"), *eb_len = find(cd, "entropy_bottleneck.cdf_length"),
                  *eb_off = find(cd, "entropy_bottleneck.offset");
     cd->gc_dev = pcc_rans_dev_create(gc_cdf->i32(), (int)gc_cdf->dims[1], gc_len->i32(), gc_off->i32(), (int)gc_cdf->dims[0]);
+    if (eb_cdf && eb_len && eb_off)   // (tables the builder refuses stay with the per-call path and its error report)
+      cd->eb_tables = pcc_rans_tables_build(eb_cdf->i32(), (int)eb_cdf->dims[1], eb_len->i32(), eb_off->i32(),
+                                            (int)eb_cdf->dims[0]);
     if (eb_cdf && eb_len && eb_off)
       cd->eb_dev = pcc_rans_dev_create(eb_cdf->i32(), (int)eb_cdf->dims[1], eb_len->i32(), eb_off->i32(), (int)eb_cdf->dims[0]);
     // (a table set too large for the coder's LDS image leaves the pointer null: version 1 is then refused, not faked)
@@ -969,6 +998,7 @@ extern "C" void pcc_codec_destroy(pcc_codec* cd) {
   for (auto& sl : cd->scale_slot)
     if (sl.dev) (void)hipFree(sl.dev);
   pcc_rans_tables_free(cd->gc_tables);
+  pcc_rans_tables_free(cd->eb_tables);
   pcc_rans_dev_destroy(cd->gc_dev);
   pcc_rans_dev_destroy(cd->eb_dev);
   cd->pool.release();
@@ -979,9 +1009,10 @@ extern "C" void pcc_codec_destroy(pcc_codec* cd) {
   if (cd->side_ctx) pcc_destroy(cd->side_ctx);   // synchronises its stream
   if (cd->side_stream) (void)hipStreamDestroy(cd->side_stream);
   if (cd->up_done) (void)hipEventDestroy(cd->up_done);
+  if (cd->out_pts) (void)hipEventDestroy(cd->out_pts);
   for (hipEvent_t e : cd->events) (void)hipEventDestroy(e);
   for (Pinned* p : {&cd->pin_keys, &cd->pin_occ, &cd->pin_zsym, &cd->pin_ysym, &cd->pin_yidx, &cd->pin_flag, &cd->pin_dec,
-                    &cd->pin_up})
+                    &cd->pin_up, &cd->pin_out})
     p->release();
   pcc_destroy(cd->ctx);
   delete cd;
@@ -1073,7 +1104,7 @@ struct UploadPiece {
   size_t count;    // bytes (raw) or elements (f64 -> f32)
   int f64;
 };
-constexpr int kUploadThreads = 4;
+constexpr int kUploadThreads = 4;   // 8 measured no better (profiles/host_legs_ab.txt)
 constexpr size_t kUploadPieceBytes = (size_t)1 << 20;  // of staged output
 
 static void upload_pieces(std::vector<UploadPiece>* out, size_t base, const void* src, size_t n_bytes_out, int f64) {
@@ -1445,9 +1476,15 @@ struct EncodeCall {
       ftab.cols_f64 = 0;
       PCC_TRY(cd->pin_up.ensure(pts_bytes + co));
       up_guard.w = &cd->workers;
-      upload_run(cd, pt_pieces, (char*)cd->pin_up.p, nullptr, nullptr, &up_status);
+      // every piece of the points goes up as soon as its thread has staged it, so the link works while the later
+      // pieces are still being written; the compute stream waits behind the last of them, the colours follow
+      upload_run(cd, pt_pieces, (char*)cd->pin_up.p, dp, cd->up_stream, &up_status);
       cd->workers.wait_all();
-      if (po) PCC_HIP(hipMemcpyAsync(dp, cd->pin_up.p, po, hipMemcpyHostToDevice, st));
+      PCC_REQUIRE(up_status.load() == 0, PCC_E_HIP, "pcc_encode_gop_host_frames: upload of the frame arrays failed");
+      hipEvent_t pts_up;
+      PCC_TRY(call_event(cd, &pts_up));
+      PCC_HIP(hipEventRecord(pts_up, cd->up_stream));
+      PCC_HIP(hipStreamWaitEvent(st, pts_up, 0));
       upload_run(cd, col_pieces, (char*)cd->pin_up.p + pts_bytes, dc, cd->up_stream, &up_status);
       frames = &ftab;
     }
@@ -1877,18 +1914,74 @@ struct PackedDst {
 __global__ __launch_bounds__(256) void k_pack_cloud(const int4* __restrict__ coords, const float* __restrict__ colors,
                                                     int64_t n, int32_t* __restrict__ xyz, float* __restrict__ rgb);
 
+__global__ __launch_bounds__(256) void k_pack_cloud16(const int4* __restrict__ coords, const float* __restrict__ colors,
+                                                      int64_t n, int16_t* __restrict__ xyz, float* __restrict__ rgb);
+__global__ __launch_bounds__(256) void k_decode_tail(const uint64_t* __restrict__ pkeys, int cshift,
+                                                     const uint32_t* __restrict__ keep, int64_t n,
+                                                     const float* __restrict__ rgb_cand, int4* __restrict__ coords,
+                                                     float* __restrict__ rgb, int16_t* __restrict__ xyz16,
+                                                     float* __restrict__ rgbp);
+
+constexpr int kWidenThreads = 8;
+
 // pack_batches' arrays of the last decode queued on the compute stream, into destinations that may be device or host
-// memory (pageable host memory is staged by the runtime); the caller synchronises
+// memory (pageable host memory is staged by the runtime); the caller synchronises the stream and then waits for the
+// codec's threads (cd->workers.wait_all()), and reads cd->widen_status.
+// Host destination, coordinates known to fit 16 bits (cd->rec_i16): the points cross the link as int16 triples — half
+// the bytes of the int32 rows, whose upper halves are sign extension — into pinned staging, the colours follow straight
+// into the caller's array, and while they cross, the parked threads widen the points into the caller's int32 array.
 static int queue_packed(pcc_codec* cd, int32_t* points, float* colors) {
   hipStream_t st = cd->ctx->stream;
   const int64_t n = cd->rec_n;
-  CODEC_ALLOC(xyz, int32_t, 3 * n);
-  CODEC_ALLOC(rgb, float, 3 * n);
-  hipLaunchKernelGGL(k_pack_cloud, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int4*)cd->rec_coords,
-                     (const float*)cd->rec_colors, n, xyz, rgb);
-  PCC_CHECK_LAUNCH();
-  PCC_HIP(hipMemcpyAsync(points, xyz, (size_t)n * 12, hipMemcpyDefault, st));
-  PCC_HIP(hipMemcpyAsync(colors, rgb, (size_t)n * 12, hipMemcpyDefault, st));
+  bool host_dst = true;
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, points) == hipSuccess)
+    host_dst = at.type == hipMemoryTypeHost || at.type == hipMemoryTypeUnregistered;
+  else
+    (void)hipGetLastError();   // plain host memory, to runtimes that do not report it as unregistered
+  if (!cd->rec_i16 || !host_dst) {
+    CODEC_ALLOC(xyz, int32_t, 3 * n);
+    CODEC_ALLOC(rgb, float, 3 * n);
+    hipLaunchKernelGGL(k_pack_cloud, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int4*)cd->rec_coords,
+                       (const float*)cd->rec_colors, n, xyz, rgb);
+    PCC_CHECK_LAUNCH();
+    PCC_HIP(hipMemcpyAsync(points, xyz, (size_t)n * 12, hipMemcpyDefault, st));
+    PCC_HIP(hipMemcpyAsync(colors, rgb, (size_t)n * 12, hipMemcpyDefault, st));
+    return PCC_OK;
+  }
+  PCC_TRY(cd->pin_out.ensure((size_t)n * 6));
+  if (!cd->out_pts) PCC_HIP(hipEventCreateWithFlags(&cd->out_pts, hipEventDisableTiming));
+  const int16_t* xyz16 = cd->rec_xyz16;
+  const float* rgbp = cd->rec_rgbp;
+  if (!xyz16 || !rgbp) {   // the decode did not pack as it went (pcc_decode_fetch_packed, the tails without the fused kernel)
+    CODEC_ALLOC(xyz, int16_t, 3 * n);
+    CODEC_ALLOC(rgb, float, 3 * n);
+    hipLaunchKernelGGL(k_pack_cloud16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int4*)cd->rec_coords,
+                       (const float*)cd->rec_colors, n, xyz, rgb);
+    PCC_CHECK_LAUNCH();
+    xyz16 = xyz;
+    rgbp = rgb;
+  }
+  PCC_HIP(hipMemcpyAsync(cd->pin_out.p, xyz16, (size_t)n * 6, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipEventRecord(cd->out_pts, st));
+  // the threads first: a copy into pageable memory may hold this thread until it is done
+  cd->workers.ensure(kWidenThreads);
+  cd->widen_status.store(0);
+  const int64_t tot = 3 * n, per = ((tot + kWidenThreads - 1) / kWidenThreads + 63) & ~(int64_t)63;
+  const int16_t* src = (const int16_t*)cd->pin_out.p;
+  std::atomic<int>* status = &cd->widen_status;
+  hipEvent_t ev = cd->out_pts;
+  const int device = cd->device;
+  for (int w = 0; w < kWidenThreads; ++w)
+    cd->workers.run(w, [=]() {
+      if (hipSetDevice(device) != hipSuccess || hipEventSynchronize(ev) != hipSuccess) {
+        status->store(1);
+        return;
+      }
+      const int64_t lo = std::min(tot, per * w), hi = std::min(tot, lo + per);
+      for (int64_t i = lo; i < hi; ++i) points[i] = src[i];
+    });
+  PCC_HIP(hipMemcpyAsync(colors, rgbp, (size_t)n * 12, hipMemcpyDefault, st));
   return PCC_OK;
 }
 
@@ -1973,6 +2066,8 @@ struct DecodeCall {
   int n_batch = 0;
   int64_t n16 = 0, n32 = 0;
   CS* ycs = nullptr;
+  View yv;                      // canonical order of the y rows
+  int32_t* hs_book = nullptr;   // h_s_book_at's columns, where the structural form holds
   Feat z_hat, gp, y_hat;
   explicit DecodeCall(pcc_codec* c) : cd(c), ctx(c->ctx), st(c->ctx->stream), cy(c->c_y), cz(c->c_z) {}
   // ---- step 1: container (codec_parallel.py:173-216)
@@ -2065,6 +2160,14 @@ struct DecodeCall {
     zsym.resize((size_t)std::max<int64_t>((int64_t)nz_hdr * cz, 1));
     cd->workers.run(0, [this]() {
       if (nz_hdr == 0) return;
+      if (cd->eb_tables && cz <= 256) {   // the codec's tables, built once; channel indexes fit a byte
+        std::vector<uint8_t> idx8((size_t)nz_hdr * cz);
+        for (int c = 0; c < cz; ++c) memset(idx8.data() + (size_t)c * nz_hdr, c, (size_t)nz_hdr);
+        z_rc = pcc_rans_decode8_gated(zstr, zlen, idx8.data(), (int64_t)nz_hdr * cz, eb_cdf->i32(), (int)eb_cdf->dims[1],
+                                      eb_len->i32(), eb_off->i32(), (int)eb_cdf->dims[0], zsym.data(), nullptr, cd->eb_tables);
+        if (z_rc != PCC_OK) z_err = pcc_last_error();
+        return;
+      }
       std::vector<int32_t> idx((size_t)nz_hdr * cz);
       for (int c = 0; c < cz; ++c) std::fill(idx.begin() + (size_t)c * nz_hdr, idx.begin() + (size_t)(c + 1) * nz_hdr, c);
       z_rc = pcc_rans_decode(zstr, zlen, idx.data(), (int64_t)nz_hdr * cz, eb_cdf->i32(), (int)eb_cdf->dims[1],
@@ -2233,6 +2336,16 @@ struct DecodeCall {
     PCC_TRY(view_of(cd, zcs, &zv));
     PCC_REQUIRE(zcs->n == nz_hdr, PCC_E_STREAM, "pcc_decode_gop: container says N_z=%d, coordinates give %lld", nz_hdr,
                 (long long)zcs->n);
+    // What the steps below need of the coordinates alone is queued before this thread waits for the z string's host
+    // job: the canonical order of the y rows (step 5), the two generated levels of h_s with the rule book one level up,
+    // and the y rows' rule-book columns among h_s's 64 descendants (the coordinate half of h_s_out_at).
+    PCC_TRY(view_of(cd, ycs, &yv));
+    {
+      CS *a_cs, *pre_cs;
+      PCC_TRY(up_of(cd, zcs, &a_cs));
+      PCC_TRY(up_of(cd, a_cs, &pre_cs));
+      PCC_TRY(h_s_book_at(cd, pre_cs, ycs, yv, &hs_book));
+    }
     cd->workers.wait_all();
     if (z_rc != PCC_OK) {
       pcc_set_error("pcc_decode_gop (z stream): %s", z_err.c_str());
@@ -2261,10 +2374,8 @@ struct DecodeCall {
   }
   // ---- step 5: decode y, de-quantise with offsets (codec_parallel.py:382-419)
   int y_decode() {
-    View yv;
-    PCC_TRY(view_of(cd, ycs, &yv));
-    float* params;
-    PCC_TRY(h_s_out_at(cd, gp, ycs, yv, &params));
+    float* params;   // (yv and hs_book: queued in z_decode, ahead of the z values)
+    PCC_TRY(h_s_out_at(cd, gp, ycs, yv, &params, hs_book));
     float* scale_d;
     const double q_dec[2] = {qg, qa};
     PCC_TRY(scale_rows_dev(cd, 1, q_dec, 1, &scale_d));
@@ -2365,6 +2476,9 @@ struct DecodeCall {
       PCC_TRY(offsets_of(cd, h.cs, &o0));
     }
     const float* rgb_cand = nullptr;  // colours of the last stage's candidate rows, when its conv evaluated the colour head
+    bool tail = false;                // the last stage left its kept rows' keys to k_decode_tail: their parents' keys, octant shift
+    uint64_t* tail_pkeys = nullptr;
+    int tail_shift = 0;
     for (int j = 0; j < 3; ++j) {
       const std::string uname = "g_s.up" + std::to_string(j);
       const std::string cname = "g_s.conv" + std::to_string(j), oname = "g_s.occ" + std::to_string(j);
@@ -2431,7 +2545,14 @@ struct DecodeCall {
       CODEC_ALLOC(pf, float, std::max<int64_t>(n_keep, 1) * cout);
       // the kept rows stay where they are: the next up stage / the colour head read them through `keep`
       const bool in_place = cout == 32;
-      if (n_keep > 0) {
+      // last stage with the candidates' colours at hand: the kept rows' keys are formed where they are turned into
+      // coordinates (k_decode_tail below) and never written
+      tail = with_rgb && in_place && n_keep > 0 && !u.cs->keys && u.cs->gen_parent;
+      if (tail) {
+        PCC_TRY(keys_of(cd, u.cs->gen_parent, &tail_pkeys));
+        tail_shift = 3 * log2i(u.cs->stride);
+        pkeys = nullptr;
+      } else if (n_keep > 0) {
         if (!u.cs->keys && u.cs->gen_parent) {   // the kept candidates' keys from their parents': the 8N are never written
           uint64_t* pk;
           PCC_TRY(keys_of(cd, u.cs->gen_parent, &pk));
@@ -2455,7 +2576,20 @@ struct DecodeCall {
       const int64_t nr = h.cs->n;
       CODEC_ALLOC(rgb, float, std::max<int64_t>(nr, 1) * 3);
       CODEC_ALLOC(coords, int32_t, std::max<int64_t>(nr, 1) * 4);
-      if (nr > 0) {
+      cd->rec_xyz16 = nullptr;
+      cd->rec_rgbp = nullptr;
+      if (nr > 0 && tail && rgb_cand && h.rows) {
+        // one kernel over the kept rows; with a destination waiting it writes pack_batches' arrays in the same pass
+        if (dst && nr <= dst->cap) {
+          CODEC_ALLOC(xyz16, int16_t, nr * 3);
+          CODEC_ALLOC(rgbp, float, nr * 3);
+          cd->rec_xyz16 = xyz16;
+          cd->rec_rgbp = rgbp;
+        }
+        hipLaunchKernelGGL(k_decode_tail, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, (const uint64_t*)tail_pkeys,
+                           tail_shift, h.rows, nr, rgb_cand, (int4*)coords, rgb, cd->rec_xyz16, cd->rec_rgbp);
+        PCC_CHECK_LAUNCH();
+      } else if (nr > 0) {
         if (rgb_cand && h.rows)
           PCC_TRY(pcc_gather_rows(ctx, rgb_cand, h.rows, nr, 12, rgb));
         else if (h.rows && (int)tw->dims[0] == 32 && (int)tw->dims[1] <= 8)
@@ -2471,6 +2605,7 @@ struct DecodeCall {
         PCC_TRY(pcc_keys_to_coords(ctx, hkeys, nr, coords));
       }
       cd->rec_coords = coords;
+      cd->rec_i16 = true;   // both forms above take every coordinate out of a Morton key (pcc_unmorton)
       cd->rec_colors = rgb;
       cd->rec_n = nr;
       cd->rec_offsets = h.cs->offsets;
@@ -2491,6 +2626,10 @@ struct DecodeCall {
       PCC_TRY(queue_packed(cd, dst->points, dst->colors));
     }
     PCC_TRY(pcc_sync(ctx));
+    if (dst && cd->rec_n > 0) {   // the threads widening the points (queue_packed)
+      cd->workers.wait_all();
+      PCC_REQUIRE(cd->widen_status.load() == 0, PCC_E_HIP, "pcc_decode_gop_packed: wait for the points' copy failed");
+    }
     if (v1 && *(volatile int32_t*)cd->pin_flag.p != 0) {
       cd->rec_n = 0;
       cd->rec_offsets.clear();
@@ -2510,6 +2649,9 @@ static int decode_gop_impl(pcc_codec* cd, const uint8_t* h_in, int64_t len, pcc_
   PCC_TRY(begin_call(cd));
   cd->rec_n = 0;
   cd->rec_offsets.clear();
+  cd->rec_i16 = false;
+  cd->rec_xyz16 = nullptr;
+  cd->rec_rgbp = nullptr;
   DecodeCall c(cd);
   PCC_TRY(timed(&c.ts[0], [&] { return c.parse(h_in, len); }));
   PCC_TRY(c.check_sizes());
@@ -2660,13 +2802,66 @@ __global__ __launch_bounds__(256) void k_pack_cloud(const int4* __restrict__ coo
   }
 }
 
+// the same with the points as int16 triples (every coordinate pcc_unmorton returns fits: queue_packed)
+__global__ __launch_bounds__(256) void k_pack_cloud16(const int4* __restrict__ coords, const float* __restrict__ colors,
+                                                      int64_t n, int16_t* __restrict__ xyz, float* __restrict__ rgb) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int4 c = coords[i];
+  xyz[3 * i] = (int16_t)c.y;
+  xyz[3 * i + 1] = (int16_t)c.z;
+  xyz[3 * i + 2] = (int16_t)c.w;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    float v = colors[3 * i + k];
+    v = (v != v) ? 0.0f : v;
+    rgb[3 * i + k] = __fdiv_rn(fminf(fmaxf(__fmul_rn(v, 255.0f), 0.0f), 255.0f), 255.0f);
+  }
+}
+
+// The tail of a decode whose last conv evaluated the colour head on every candidate: kept row i is candidate keep[i] =
+// 8 p + o, octant o of parent p.  One pass forms its key from the parent's (k_up_keys_rows), takes its colour
+// (pcc_gather_rows) and writes the row (frame, x, y, z) (k_keys_to_coords) and, when xyz16 is given, pack_batches'
+// arrays with k_pack_cloud16's operations.
+__global__ __launch_bounds__(256) void k_decode_tail(const uint64_t* __restrict__ pkeys, int cshift,
+                                                     const uint32_t* __restrict__ keep, int64_t n,
+                                                     const float* __restrict__ rgb_cand, int4* __restrict__ coords,
+                                                     float* __restrict__ rgb, int16_t* __restrict__ xyz16 /*nullable*/,
+                                                     float* __restrict__ rgbp /*with xyz16*/) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t r = keep[i];
+  const uint64_t key = pkeys[r >> 3] | ((uint64_t)(r & 7u) << cshift);
+  int b, x, y, z;
+  pcc_unmorton(key, &b, &x, &y, &z);
+  coords[i] = make_int4(b, x, y, z);
+  float c[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    c[k] = rgb_cand[3 * (int64_t)r + k];
+    rgb[3 * i + k] = c[k];
+  }
+  if (!xyz16) return;
+  xyz16[3 * i] = (int16_t)x;
+  xyz16[3 * i + 1] = (int16_t)y;
+  xyz16[3 * i + 2] = (int16_t)z;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float v = (c[k] != c[k]) ? 0.0f : c[k];
+    rgbp[3 * i + k] = __fdiv_rn(fminf(fmaxf(__fmul_rn(v, 255.0f), 0.0f), 255.0f), 255.0f);
+  }
+}
+
 extern "C" int pcc_decode_fetch_packed(pcc_codec* cd, int32_t* points, float* colors) {
   PCC_REQUIRE(cd && cd->ctx, PCC_E_ARG, "pcc_decode_fetch_packed: null codec");
   if (cd->rec_n == 0) return PCC_OK;
   PCC_REQUIRE(cd->rec_coords && cd->rec_colors && points && colors, PCC_E_ARG,
               "pcc_decode_fetch_packed: no decoded GOP on this codec, or null destination");
+  WorkersGuard widen{&cd->workers};   // the widening jobs write the caller's array: never leave while one is running
   PCC_TRY(queue_packed(cd, points, colors));
   PCC_HIP(hipStreamSynchronize(cd->ctx->stream));
+  cd->workers.wait_all();
+  PCC_REQUIRE(cd->widen_status.load() == 0, PCC_E_HIP, "pcc_decode_fetch_packed: wait for the points' copy failed");
   return PCC_OK;
 }
 
