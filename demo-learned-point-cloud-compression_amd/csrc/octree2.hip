@@ -34,8 +34,19 @@
 // (breadth-first numbering: the first child of node i is node 1 + sum of the child counts in front of i), a pass that
 // writes every child's (parent, octant) link and a pass in which every leaf walks up `depth` links.
 // All integer: bit-exact against oracle/pcc_oracle.c (orc_octree2_encode / orc_octree_decode).
+//
+// Levels of detail (the header's parser and the rule in full: octree2_blob.h).  Breadth-first numbering, the chunk table
+// in front of the payload and a contiguous run of words per lane make the levels above a cut a PREFIX of the bytes, and
+// the nodes of level L are indexed exactly where the leaves of a tree of depth L would be.  For lod k in 0 .. 15:
+// Lc = max(depth - k, 0); cells m = n (k = 0), level_n[Lc] (0 < k < depth), 1 (k >= depth); nodes needed
+// N' = level_n[0] + .. + level_n[Lc - 1]; result = the m distinct cell indices p >> k in Morton order (corner c << k,
+// centre (c << k) + ((1 << k) >> 1)); shortest prefix = the whole blob (k = 0), off_payload (N' = 0), else with
+// lanes = ceil(N' / S), c* = (lanes - 1) / 64, l* = (lanes - 1) % 64:
+// off_payload + 2 (words[0] + .. + words[c* - 1]) + 2 (192 + len[0] + .. + len[l*]) of chunk c*'s length table.
+// The decoder below is one path for all k: the tree with depth := Lc, n_nodes := N', n_points := m, origin >> k.
 #include "common.h"
 #include "lanerans.h"
+#include "octree2_blob.h"
 
 #include <string.h>
 
@@ -47,9 +58,9 @@ void octree_root(uint64_t first, uint64_t last, int key_shift, int* depth, int32
 
 namespace {
 
-constexpr int kCtx = 108;        // 3 level classes x 36 (bit position, ones so far)
-constexpr int kSMax = 512;       // nodes per lane: a launch lasts 8 S dependent steps of one wave
-constexpr int kHeader = 24;
+constexpr int kCtx = kO2Ctx;      // 3 level classes x 36 (bit position, ones so far)
+constexpr int kSMax = kO2SMax;     // nodes per lane: a launch lasts 8 S dependent steps of one wave
+constexpr int kHeader = kO2Header;
 constexpr uint32_t kL = 1u << 16;
 
 __device__ __forceinline__ int lane_rank(unsigned long long bal) {
@@ -328,16 +339,22 @@ __global__ __launch_bounds__(256) void k_o2_pack(const uint16_t* __restrict__ wo
 // status (int32): OR of 1 = a chunk ran out of words or did not use all of its words, 2 = an empty node,
 // 8 = the child counts do not add up to the announced level sizes / point count; one per frame of the call
 //
-// one frame (>= 1 point) of a decode call
+// one frame (>= 1 node to decode) of a decode call.  At a level of detail (octree2_blob.h) the frame is the tree cut
+// at level Lc: n_nodes = N', n_points = m cells, depth = Lc, origin >> lod, nc / lanes_last / last_words what the
+// prefix holds of its chunks — while the coder's parameters (S, start_last, start_prev: the level classes) and n_full
+// stay the FULL tree's
 struct O2DFrame {
   int64_t body_off;                    // p0 | chunk table | payload of its blob in the call's uploaded bodies (4-aligned)
   int64_t table_off, payload_off;      // from body_off
   int64_t n_nodes, start_last, start_prev, n_points;
+  int64_t n_full;                      // nodes of the whole tree (n_nodes < n_full: a cut tree)
   int64_t node_base;                   // its nodes in the call's node arrays (occupancy, child counts, scan): 4-aligned
   int64_t link_base;                   // its links in the call's link array: nodes, then leaves
   int64_t pt_base;                     // its first point in the output
   int64_t off[17];                     // nodes in front of level L (off[depth] = n_nodes)
   int32_t S, nc, cb, lb, qb, depth;    // first chunk, first block of k_o2_link, of k_o2_points
+  int32_t lanes_last;
+  uint32_t last_words;                 // of chunk nc - 1: lanes whose runs are present, words present (whole tree: 64, all)
   int32_t origin[3];
 };
 
@@ -348,8 +365,9 @@ constexpr int kDecLdsWords = 24576;   // 48 KB beside the 13.9 KB of models
 template <bool IN_LDS>
 __device__ __forceinline__ void o2_decode_chunk(uint16_t* s_model, const uint16_t* __restrict__ s_words,
                                                 const uint16_t* __restrict__ p /* the chunk in the stream */, uint32_t cw,
-                                                int64_t c, int lane, int64_t n_nodes, int64_t start_last, int64_t start_prev,
-                                                int S, uint32_t* __restrict__ occ32, int& bad) {
+                                                int lanes_here, int64_t c, int lane, int64_t n_nodes, bool cut,
+                                                int64_t start_last, int64_t start_prev, int S,
+                                                uint32_t* __restrict__ occ32, int& bad) {
   uint32_t x = (uint32_t)p[2 * lane] | ((uint32_t)p[2 * lane + 1] << 16);
   // the lane's run: [rbase, rend) in 16-bit words from the chunk's start
   const uint32_t my_len = p[2 * kLanes + lane];
@@ -359,7 +377,8 @@ __device__ __forceinline__ void o2_decode_chunk(uint16_t* s_model, const uint16_
     const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
     incl += lane >= d ? o : 0u;
   }
-  const uint32_t total = (uint32_t)__shfl((int)incl, 63, 64);
+  // the runs that are present (all 64 unless this is the last chunk of a cut tree) fill the words that are present
+  const uint32_t total = (uint32_t)__shfl((int)incl, lanes_here - 1, 64);
   if (3u * kLanes + total != cw) {   // wave-uniform
     bad |= 1;
     return;
@@ -383,7 +402,13 @@ __device__ __forceinline__ void o2_decode_chunk(uint16_t* s_model, const uint16_
   // so far, and one more) — so that the LDS round trip is not on the chain from state to state
   uint32_t p_cur = s_model[(cls_of(node0) * 36) * kLanes + lane];
   const int a_dummy = kCtx * kLanes + lane;   // takes the model writes of decisions that are not coded (no branch)
-  for (int s = 0; s < S; s += 4) {
+  // the wave's trip count is lane 0's (the lanes' runs lie one behind the other): up to the dword that holds the
+  // frame's last node (a cut tree's N' - 1).  Behind that node a lane's steps code nothing and consume nothing, so the
+  // lane that straddles it stops there and a lane whose run starts behind it does nothing — without a branch in the
+  // steps and with a scalar loop counter, as for the whole tree
+  const int64_t left = n_nodes - node0, left0 = n_nodes - c * kLanes * S;
+  const int s_end = __builtin_amdgcn_readfirstlane(left0 >= (int64_t)S ? S : (left0 > 0 ? (int)((left0 + 3) & ~(int64_t)3) : 0));
+  for (int s = 0; s < s_end; s += 4) {
     uint32_t dw = 0;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -426,7 +451,8 @@ __device__ __forceinline__ void o2_decode_chunk(uint16_t* s_model, const uint16_
     }
     __builtin_amdgcn_raw_buffer_store_b32(dw, occ_rs, (uint32_t)(node0 + s), 0, 0);
   }
-  if (pos != rend) bad |= 1;   // every word of the run consumed
+  // every word of the run consumed — but for the lanes of a cut tree whose runs go on (or lie) behind node N' - 1
+  if (pos != rend && !(cut && left < (int64_t)S)) bad |= 1;
 }
 
 // block = chunk of the call: frame f owns blocks [cb, cb + nc)
@@ -443,13 +469,17 @@ __global__ __launch_bounds__(64) void k_o2_dec(const uint8_t* __restrict__ bodie
   const uint16_t* payload = reinterpret_cast<const uint16_t*>(body + tab[f].payload_off);
   const int64_t n_nodes = tab[f].n_nodes, start_last = tab[f].start_last, start_prev = tab[f].start_prev;
   const int S = tab[f].S;
+  const bool cut = n_nodes < tab[f].n_full, last = c == tab[f].nc - 1;
+  const int lanes_here = last ? tab[f].lanes_last : kLanes;
   uint32_t* occ32 = reinterpret_cast<uint32_t*>(occ_all + tab[f].node_base);
   int32_t* status = status_all + f;
   for (int ctx = 0; ctx < kCtx; ++ctx) s_model[ctx * kLanes + lane] = p0[ctx];
   unsigned long long before = 0;
   for (int64_t j = lane; j < c; j += kLanes) before += table[j];
   for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d, 64);
-  const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)table[c]);
+  // the words of the chunk that are here: all of them, or what a prefix holds of a cut tree's last chunk (the host
+  // read them off the same length table and checked them against the chunk table: o2_parse)
+  const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)(last ? tab[f].last_words : table[c]));
   const uint16_t* p = payload + before;
   int bad = 0;
   if (cw < 3 * kLanes) {
@@ -468,9 +498,9 @@ __global__ __launch_bounds__(64) void k_o2_dec(const uint8_t* __restrict__ bodie
       if (w0 + 1 >= 0 && w0 + 1 < (int)cw) s_words[w0 + 1] = (uint16_t)(v >> 16);
     }
     __syncthreads();
-    o2_decode_chunk<true>(s_model, s_words, p, cw, c, lane, n_nodes, start_last, start_prev, S, occ32, bad);
+    o2_decode_chunk<true>(s_model, s_words, p, cw, lanes_here, c, lane, n_nodes, cut, start_last, start_prev, S, occ32, bad);
   } else {
-    o2_decode_chunk<false>(s_model, s_words, p, cw, c, lane, n_nodes, start_last, start_prev, S, occ32, bad);
+    o2_decode_chunk<false>(s_model, s_words, p, cw, lanes_here, c, lane, n_nodes, cut, start_last, start_prev, S, occ32, bad);
   }
   const unsigned long long b1 = __ballot((bad & 1) != 0), b2 = __ballot((bad & 2) != 0);
   if (lane == 0 && (b1 | b2) != 0ull) atomicOr(status, (b1 ? 1 : 0) | (b2 ? 2 : 0));
@@ -784,96 +814,49 @@ int pcc_octree2_encode(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int key_
   return PCC_OK;
 }
 
-// header of a version-2 blob, checked against its length: everything a decoder sizes from
-struct O2Info {
-  int depth;
-  int64_t n, n_nodes, S, nc, level_n[16];
-  int32_t origin[3];
-  int64_t off_p0, off_table, off_payload, payload_words;
-};
-static int o2_parse(const uint8_t* h_in, int64_t len, O2Info* o) {
-  PCC_REQUIRE(h_in && len >= kHeader && h_in[0] == 'O' && h_in[1] == 2, PCC_E_STREAM, "octree blob v2: bad header");
-  o->depth = h_in[2];
-  o->n = (int64_t)get_u32(h_in + 4);
-  for (int a = 0; a < 3; ++a) o->origin[a] = (int32_t)get_u32(h_in + 8 + 4 * a);
-  const int64_t payload = (int64_t)get_u32(h_in + 20);
-  PCC_REQUIRE(kHeader + payload <= len, PCC_E_STREAM, "octree blob v2: truncated");
-  if (o->n == 0) {
-    o->n_nodes = 0;
-    return PCC_OK;
-  }
-  const int d = o->depth;
-  PCC_REQUIRE(d >= 1 && d <= 16 && payload >= 4 * d + 8 + 2 * kCtx + 4, PCC_E_STREAM, "octree blob v2: depth %d, payload %lld", d,
-              (long long)payload);
-  const uint8_t* q = h_in + kHeader;
-  o->n_nodes = 0;
-  for (int L = 0; L < d; ++L, q += 4) {
-    o->level_n[L] = (int64_t)get_u32(q);
-    o->n_nodes += o->level_n[L];
-    PCC_REQUIRE(o->level_n[L] >= 1 && (L == 0 ? o->level_n[0] == 1 : o->level_n[L] <= 8 * o->level_n[L - 1]) && o->level_n[L] <= o->n,
-                PCC_E_STREAM, "octree blob v2: level %d has %lld nodes", L, (long long)o->level_n[L]);
-  }
-  PCC_REQUIRE(o->n <= 8 * o->level_n[d - 1] && o->n >= o->level_n[d - 1] && o->n_nodes < ((int64_t)1 << 28), PCC_E_STREAM,
-              "octree blob v2: %lld points under %lld nodes", (long long)o->n, (long long)o->level_n[d - 1]);
-  o->S = (int64_t)get_u32(q);
-  o->nc = (int64_t)get_u32(q + 4);
-  q += 8;
-  // S <= kSMax, as the encoder writes it: a chunk then codes at most 32768 nodes, so the announced node count is bound
-  // by the chunk table's length (every chunk has at least 384 bytes of states and lengths)
-  PCC_REQUIRE(o->S >= 4 && o->S % 4 == 0 && o->S <= kSMax && o->nc >= 1 && kLanes * o->S * o->nc >= o->n_nodes &&
-                  kLanes * o->S * (o->nc - 1) < o->n_nodes,
-              PCC_E_STREAM, "octree blob v2: %lld nodes in %lld chunks of 64 x %lld", (long long)o->n_nodes, (long long)o->nc,
-              (long long)o->S);
-  o->off_p0 = q - h_in;
-  for (int i = 0; i < kCtx; ++i, q += 2) {
-    const uint32_t p = (uint32_t)q[0] | ((uint32_t)q[1] << 8);
-    PCC_REQUIRE(p >= 16 && p <= 4080, PCC_E_STREAM, "octree blob v2: initial probability %u", p);
-  }
-  o->off_table = q - h_in;
-  PCC_REQUIRE(kHeader + payload - o->off_table >= 4 * o->nc, PCC_E_STREAM, "octree blob v2: truncated chunk table");
-  int64_t words = 0;
-  for (int64_t c = 0; c < o->nc; ++c) {
-    const int64_t cw = (int64_t)get_u32(q + 4 * c);
-    PCC_REQUIRE(cw >= 3 * kLanes, PCC_E_STREAM, "octree blob v2: chunk %lld has no states", (long long)c);
-    words += cw;
-  }
-  o->off_payload = o->off_table + 4 * o->nc;
-  o->payload_words = words;
-  PCC_REQUIRE(o->off_payload + 2 * words == kHeader + payload, PCC_E_STREAM, "octree blob v2: chunks take %lld bytes, blob has %lld",
-              (long long)(2 * words), (long long)(kHeader + payload - o->off_payload));
-  return PCC_OK;
-}
-
 // version-2 blobs -> their points, Morton order inside a frame (origin added), concatenated in frame order: on the device
 // (d_points) and / or on the host (h_points).  h_point_offsets[nb + 1] receives where every frame's points start;
 // h_level_n (16 entries, nullable, nb == 1) the node counts of the levels.  Every header is checked, and the sizes the
 // batch announces are summed and checked, before anything is reserved.  `who` names the frame in errors (nullptr: the
 // one-blob messages).  One synchronisation.
-static int o2_decode_batch(pcc_ctx* ctx, const uint8_t* const* blobs, const int64_t* lens, int nb, const char* who,
+//
+// lod > 0 (octree2_blob.h): blobs or prefixes of them, every frame cut at level Lc = max(depth - lod, 0) — the same
+// kernels over the tree of the first N' nodes, whose "points" are the m cells of level Lc: only the plan's bytes are
+// uploaded, only the needed chunks launched, and nodes, scan, links and output are sized from N' and m, which the
+// stream verifies (k_o2_link: the level boundaries above the cut, the children of the first N' nodes).  The level
+// sizes below the cut and n are out of a prefix's reach: they stay bounded by the header checks alone, and nothing is
+// sized from them.  A frame with Lc = 0 is its root cube: one cell, origin >> lod, no launch.
+static int o2_decode_batch(pcc_ctx* ctx, const uint8_t* const* blobs, const int64_t* lens, int nb, const char* who, int lod,
                            int32_t* d_points, int32_t* h_points, int64_t cap_points, int64_t* h_point_offsets,
                            int64_t* h_level_n) {
   std::vector<O2Info> info((size_t)nb);
+  std::vector<O2Plan> plan((size_t)nb);
   int64_t points = 0, nodes = 0, links = 0, bodies = 0;
+  int roots = 0;   // frames that are their root cube alone
   h_point_offsets[0] = 0;
   for (int f = 0; f < nb; ++f) {
     O2Info& o = info[(size_t)f];
+    O2Plan& pl = plan[(size_t)f];
     if (who) {
       const int v = pcc_octree_blob_version(blobs[f], lens[f]);
       if (v < 0) return o2_frame_error(v, who, f);
       PCC_REQUIRE(v == 2, PCC_E_ARG, "%s: frame %d: blob version %d (this call reads version 2)", who, f, v);
-      const int rc = o2_parse(blobs[f], lens[f], &o);
+      const int rc = o2_parse(blobs[f], lens[f], lod, true, &o, &pl);
       if (rc != PCC_OK) return o2_frame_error(rc, who, f);
     } else {
-      PCC_TRY(o2_parse(blobs[f], lens[f], &o));
+      PCC_TRY(o2_parse(blobs[f], lens[f], lod, true, &o, &pl));
     }
-    points += o.n;
+    points += pl.m;
     h_point_offsets[f + 1] = points;
-    if (o.n == 0) continue;
-    nodes += o2_round(o.n_nodes, 4);
-    links += o.n_nodes + o.n;
-    bodies += o2_round(lens[f] - o.off_p0, 16);
+    if (pl.n_dec == 0) {
+      roots += pl.m ? 1 : 0;
+      continue;
+    }
+    nodes += o2_round(pl.n_dec, 4);
+    links += pl.n_dec + pl.m;
+    bodies += o2_round(pl.bytes - o.off_p0, 16);
   }
-  if (h_level_n) {
+  if (h_level_n) {   // (lod 0 callers only)
     for (int L = 0; L < 16; ++L) h_level_n[L] = 0;
     if (info[0].n)
       for (int L = 0; L < info[0].depth; ++L) h_level_n[L] = info[0].level_n[L];
@@ -884,42 +867,46 @@ static int o2_decode_batch(pcc_ctx* ctx, const uint8_t* const* blobs, const int6
   if (points == 0 || (!d_points && !h_points)) return PCC_OK;
   PCC_REQUIRE(cap_points >= points, PCC_E_NOMEM, "%s: %lld points, capacity %lld", who ? who : "pcc_octree2_decode",
               (long long)points, (long long)cap_points);
-  // the table: frames with points only
+  // the table: frames with nodes to decode only
   std::vector<O2DFrame> tab;
   int64_t node_base = 0, link_base = 0, body_off = 0, chunks = 0, lblocks = 0, qblocks = 0;
   for (int f = 0; f < nb; ++f) {
     const O2Info& o = info[(size_t)f];
-    if (o.n == 0) continue;
+    const O2Plan& pl = plan[(size_t)f];
+    if (pl.n_dec == 0) continue;
     O2DFrame r;
     r.body_off = body_off;
     r.table_off = o.off_table - o.off_p0;
     r.payload_off = o.off_payload - o.off_p0;
-    r.n_nodes = o.n_nodes;
+    r.n_nodes = pl.n_dec;
     r.start_last = o.n_nodes - o.level_n[o.depth - 1];
     r.start_prev = o.depth >= 2 ? r.start_last - o.level_n[o.depth - 2] : 0;
-    r.n_points = o.n;
+    r.n_points = pl.m;
+    r.n_full = o.n_nodes;
     r.node_base = node_base;
     r.link_base = link_base;
     r.pt_base = h_point_offsets[f];
     int64_t run = 0;
     for (int L = 0; L <= 16; ++L) {
       r.off[L] = run;
-      if (L < o.depth) run += o.level_n[L];
+      if (L < pl.Lc) run += o.level_n[L];
     }
     r.S = (int32_t)o.S;
-    r.nc = (int32_t)o.nc;
+    r.nc = (int32_t)pl.chunks;
     r.cb = (int32_t)chunks;
     r.lb = (int32_t)lblocks;
     r.qb = (int32_t)qblocks;
-    r.depth = o.depth;
-    for (int a = 0; a < 3; ++a) r.origin[a] = o.origin[a];
+    r.depth = pl.Lc;
+    r.lanes_last = (int32_t)pl.lanes;
+    r.last_words = (uint32_t)pl.last_words;
+    for (int a = 0; a < 3; ++a) r.origin[a] = o.origin[a] >> lod;
     tab.push_back(r);
-    node_base += o2_round(o.n_nodes, 4);
-    link_base += o.n_nodes + o.n;
-    body_off += o2_round(lens[f] - o.off_p0, 16);
-    chunks += o.nc;
-    lblocks += nblk(o.n_nodes, 256);
-    qblocks += nblk(o.n, 256);
+    node_base += o2_round(pl.n_dec, 4);
+    link_base += pl.n_dec + pl.m;
+    body_off += o2_round(pl.bytes - o.off_p0, 16);
+    chunks += pl.chunks;
+    lblocks += nblk(pl.n_dec, 256);
+    qblocks += nblk(pl.m, 256);
   }
   const int nf = (int)tab.size();
   hipStream_t st = ctx->stream;
@@ -936,7 +923,7 @@ static int o2_decode_batch(pcc_ctx* ctx, const uint8_t* const* blobs, const int6
   uint32_t* link = (uint32_t*)pcc_arena_alloc(ctx, (size_t)links * 4);
   int32_t* pts = d_points ? d_points : (int32_t*)pcc_arena_alloc(ctx, (size_t)points * 12);
   int32_t* status = (int32_t*)pcc_arena_alloc(ctx, (size_t)nf * 4 + 64);   // per frame | total of the scan
-  if (!d_in || !occ || !pc || !excl || !link || !pts || !status) return PCC_E_NOMEM;
+  if (!pts || !status || (nf > 0 && (!d_in || !occ || !pc || !excl || !link))) return PCC_E_NOMEM;
   uint32_t* total = (uint32_t*)(status + nf);
   const O2DFrame* d_tab = (const O2DFrame*)d_in;
   const uint8_t* d_bodies = d_in + tab_b;
@@ -953,35 +940,46 @@ static int o2_decode_batch(pcc_ctx* ctx, const uint8_t* const* blobs, const int6
       (void)hipGetLastError();
   }
   const size_t out_bytes = h_points && !direct ? (size_t)points * 12 : 0;
-  PCC_TRY(o2_stage_reserve(ctx, pcc_align(in_b) + pcc_align(out_bytes) + (size_t)nf * 4 + 64));
+  const size_t roots_at = pcc_align(in_b) + pcc_align(out_bytes) + (size_t)nf * 4 + 64;
+  PCC_TRY(o2_stage_reserve(ctx, roots_at + (size_t)roots * 12));
   uint8_t* stage = (uint8_t*)ctx->stage;
   memcpy(stage, tab.data(), (size_t)nf * sizeof(O2DFrame));
   for (int f = 0, k = 0; f < nb; ++f) {
     const O2Info& o = info[(size_t)f];
-    if (o.n == 0) continue;
-    memcpy(stage + tab_b + tab[(size_t)k].body_off, blobs[f] + o.off_p0, (size_t)(lens[f] - o.off_p0));
+    if (plan[(size_t)f].n_dec == 0) continue;
+    memcpy(stage + tab_b + tab[(size_t)k].body_off, blobs[f] + o.off_p0, (size_t)(plan[(size_t)f].bytes - o.off_p0));
     ++k;
   }
-  PCC_HIP(hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
-  PCC_HIP(hipMemsetAsync(status, 0, (size_t)nf * 4 + 64, st));
-  PCC_HIP(hipMemsetAsync(link, 0, (size_t)links * 4, st));
-  hipLaunchKernelGGL(k_o2_dec, dim3((unsigned)chunks), dim3(64), 0, st, d_bodies, d_tab, nf, occ, status);
-  PCC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_o2_popc, dim3(nblk(nodes, 256)), dim3(256), 0, st, (const uint8_t*)occ, nodes, pc);
-  PCC_CHECK_LAUNCH();
-  PCC_TRY(pcc_scan_exclusive_u32(ctx, pc, excl, nodes, total));
-  hipLaunchKernelGGL(k_o2_link, dim3((unsigned)lblocks), dim3(256), 0, st, (const uint8_t*)occ, (const uint32_t*)excl,
-                     (const uint32_t*)total, nodes, d_tab, nf, link, status);
-  PCC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_o2_points, dim3((unsigned)qblocks), dim3(256), 0, st, (const uint32_t*)link, d_tab, nf, pts, status);
-  PCC_CHECK_LAUNCH();
+  // the frames that are their root cube alone: the one cell goes to its row as it is
+  int32_t* h_roots = (int32_t*)(stage + roots_at);
+  for (int f = 0, k = 0; f < nb && k < roots; ++f) {
+    if (plan[(size_t)f].n_dec != 0 || plan[(size_t)f].m == 0) continue;
+    for (int a = 0; a < 3; ++a) h_roots[3 * k + a] = info[(size_t)f].origin[a] >> lod;
+    PCC_HIP(hipMemcpyAsync(pts + 3 * h_point_offsets[f], h_roots + 3 * k, 12, hipMemcpyHostToDevice, st));
+    ++k;
+  }
+  if (nf > 0) {   // (no frame with nodes: a call of root cubes alone, at a lod at or beyond every depth)
+    PCC_HIP(hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
+    PCC_HIP(hipMemsetAsync(status, 0, (size_t)nf * 4 + 64, st));
+    PCC_HIP(hipMemsetAsync(link, 0, (size_t)links * 4, st));
+    hipLaunchKernelGGL(k_o2_dec, dim3((unsigned)chunks), dim3(64), 0, st, d_bodies, d_tab, nf, occ, status);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_o2_popc, dim3(nblk(nodes, 256)), dim3(256), 0, st, (const uint8_t*)occ, nodes, pc);
+    PCC_CHECK_LAUNCH();
+    PCC_TRY(pcc_scan_exclusive_u32(ctx, pc, excl, nodes, total));
+    hipLaunchKernelGGL(k_o2_link, dim3((unsigned)lblocks), dim3(256), 0, st, (const uint8_t*)occ, (const uint32_t*)excl,
+                       (const uint32_t*)total, nodes, d_tab, nf, link, status);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_o2_points, dim3((unsigned)qblocks), dim3(256), 0, st, (const uint32_t*)link, d_tab, nf, pts, status);
+    PCC_CHECK_LAUNCH();
+  }
   uint8_t* stage_out = stage + pcc_align(in_b);
   int32_t* h_status = (int32_t*)(stage_out + pcc_align(out_bytes));
   if (h_points) PCC_HIP(hipMemcpyAsync(direct ? (void*)h_points : (void*)stage_out, pts, (size_t)points * 12, hipMemcpyDeviceToHost, st));
-  PCC_HIP(hipMemcpyAsync(h_status, status, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
+  if (nf > 0) PCC_HIP(hipMemcpyAsync(h_status, status, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
   PCC_HIP(hipStreamSynchronize(st));
   for (int f = 0, k = 0; f < nb; ++f) {
-    if (info[(size_t)f].n == 0) continue;
+    if (plan[(size_t)f].n_dec == 0) continue;
     const int32_t bad = h_status[k++];
     if (!who)
       PCC_REQUIRE(bad == 0, PCC_E_STREAM, "octree blob v2: corrupt stream (status %d: 1 = words, 2 = empty node, 8 = counts)", bad);
@@ -998,7 +996,7 @@ int pcc_octree2_decode(pcc_ctx* ctx, const uint8_t* h_in, int64_t len, int32_t* 
                        int64_t* h_n_points, int64_t* h_level_n) {
   PCC_REQUIRE(ctx, PCC_E_ARG, "pcc_octree2_decode: null ctx");
   int64_t offs[2] = {0, 0};
-  const int rc = o2_decode_batch(ctx, &h_in, &len, 1, nullptr, d_points, h_points, cap_points, offs, h_level_n);
+  const int rc = o2_decode_batch(ctx, &h_in, &len, 1, nullptr, 0, d_points, h_points, cap_points, offs, h_level_n);
   if (h_n_points && (rc == PCC_OK || offs[1] > 0)) *h_n_points = offs[1];
   return rc;
 }
@@ -1075,12 +1073,39 @@ extern "C" int pcc_octree_encode_frames(pcc_ctx* ctx, const uint64_t* d_keys, in
   return PCC_OK;
 }
 
+static int o2_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
+                            int lod, int32_t* d_points, int32_t* h_points, int64_t cap_points, int64_t* h_point_offsets) {
+  PCC_REQUIRE(ctx && h_blobs && h_lens && h_point_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
+              "%s: bad argument (n_frames=%d)", who, n_frames);
+  PCC_REQUIRE(lod >= 0 && lod <= kO2MaxLod, PCC_E_ARG, "%s: level of detail %d outside 0 .. %d", who, lod, kO2MaxLod);
+  return o2_decode_batch(ctx, h_blobs, h_lens, n_frames, who, lod, d_points, h_points, cap_points, h_point_offsets, nullptr);
+}
+
 extern "C" int pcc_octree_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
                                         int32_t* d_points, int32_t* h_points, int64_t cap_points, int64_t* h_point_offsets) {
-  PCC_REQUIRE(ctx && h_blobs && h_lens && h_point_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
-              "pcc_octree_decode_frames: bad argument (n_frames=%d)", n_frames);
-  return o2_decode_batch(ctx, h_blobs, h_lens, n_frames, "pcc_octree_decode_frames", d_points, h_points, cap_points,
-                         h_point_offsets, nullptr);
+  return o2_decode_frames("pcc_octree_decode_frames", ctx, h_blobs, h_lens, n_frames, 0, d_points, h_points, cap_points,
+                          h_point_offsets);
+}
+
+extern "C" int pcc_octree_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
+                                            int lod, int32_t* d_points, int32_t* h_points, int64_t cap_points,
+                                            int64_t* h_point_offsets) {
+  return o2_decode_frames("pcc_octree_decode_frames_lod", ctx, h_blobs, h_lens, n_frames, lod, d_points, h_points, cap_points,
+                          h_point_offsets);
+}
+
+// host only: what level `lod` of a version-2 blob needs (bytes of its shortest prefix) and gives (cells)
+extern "C" int pcc_octree_lod_info(const uint8_t* h_in, int64_t len, int lod, int64_t* h_bytes, int64_t* h_cells) {
+  PCC_REQUIRE(lod >= 0 && lod <= kO2MaxLod, PCC_E_ARG, "pcc_octree_lod_info: level of detail %d outside 0 .. %d", lod, kO2MaxLod);
+  const int v = pcc_octree_blob_version(h_in, len);
+  if (v < 0) return v;
+  PCC_REQUIRE(v == 2, PCC_E_ARG, "pcc_octree_lod_info: blob version %d (levels of detail are a property of version 2)", v);
+  O2Info o;
+  O2Plan pl;
+  PCC_TRY(o2_parse(h_in, len, lod, false, &o, &pl));
+  if (h_bytes) *h_bytes = pl.bytes;
+  if (h_cells) *h_cells = pl.m;
+  return PCC_OK;
 }
 
 // ---- C-ABI: the geometry slot, one call each (utils.gpcc_encode / gpcc_decode, shared/utils.py:169-240) -------------

@@ -12,6 +12,12 @@ are coded side by side by one pcc_octree_encode_frames call and decoded by one p
     blobs, attr_blobs = codec.compress(frames, attributes=[a0, a1, ...])   # uint8 / uint16 [n_f] or [n_f, c], c <= 4
     frames, attrs = codec.decompress(blobs, attr_blobs)  # attrs[f]: [n_f, c] in its dtype, row i = point i
 
+Levels of detail (csrc/octree2_blob.h has the rule): a stored blob holds every coarser level as a prefix of its bytes.
+
+    nbytes, cells = GeometryCodec.lod_info(blob, 2)      # host only: what a server publishes as a byte range
+    cells = codec.decompress([b[:nbytes]], lod=2)        # int32 [cells, 3]: the distinct points >> 2, Morton order
+    blobs = codec.compress(frames, lod=2)                # the sender's side: blobs of those cells themselves
+
 Attributes are lossless (attribute blob version 1, csrc/attr.hip), one blob per frame beside its geometry blob; the
 values of duplicate points merge to their rounded mean per channel, (sum + cnt // 2) // cnt.
 
@@ -29,6 +35,7 @@ from ._abi import check, PccError, PCC_E_RANGE
 from .runtime import Runtime, _ptr
 
 MAX_FRAMES = 65535      # the batch-index range of pcc_morton_keys
+MAX_LOD = 15            # levels of detail 0 .. 15 (csrc/octree2_blob.h)
 
 
 class GeometryCodec:
@@ -72,12 +79,30 @@ class GeometryCodec:
             out.append(np.ascontiguousarray(a.astype(a.dtype.newbyteorder("<"), copy=False)))
         return out
 
-    def compress(self, frames, attributes=None):
+    @staticmethod
+    def _check_lod(lod):
+        if not isinstance(lod, (int, np.integer)) or isinstance(lod, bool) or not 0 <= lod <= MAX_LOD:
+            raise ValueError(f"lod must be an integer in 0 .. {MAX_LOD}, got {lod!r} (32768 is not a multiple of 2^16: "
+                             "the cells of level 16 would not nest in a root cube)")
+        return int(lod)
+
+    @staticmethod
+    def lod_info(blob, lod):
+        """(bytes, cells) of level of detail `lod` of a version-2 blob: blob[:bytes] is the shortest prefix that
+        decompress(..., lod=lod) reads, `cells` the rows it gives.  Host only (no GPU needed); `blob` may be a prefix
+        that reaches the last needed chunk's length table."""
+        return Runtime.octree_lod_info(bytes(blob), GeometryCodec._check_lod(lod))
+
+    def compress(self, frames, attributes=None, lod=0):
         """frames: a sequence of int16 / int32 [n_f, 3] arrays -> a list of bytes, one version-2 blob per frame.
         Duplicate points are removed (as np.unique), out-of-range coordinates raise PccError (PCC_E_RANGE).
+        lod = k > 0: the sender's side of a level of detail — blob f is the version-2 blob of the distinct cells
+        points_f >> k (under bias 32768 >> k), which every decoder reads as those cell indices; the rows of a CELL
+        merge as duplicate points do, in one merge over all input rows of the cell.
         attributes (optional): one uint8 / uint16 [n_f] or [n_f, c] array per frame (1 <= c <= 4) -> (blobs,
         attribute blobs): attribute blob f holds, losslessly, one row per decoded point of frame f (Morton order), the
         rows of duplicate points merged to their rounded mean per channel."""
+        lod = self._check_lod(lod)
         frames = self._check_frames(frames)
         attrs = None if attributes is None else self._check_attributes(frames, attributes)
         nb = len(frames)
@@ -106,6 +131,8 @@ class GeometryCodec:
                                                 C.c_void_p(dev.data_ptr()), nb, _ptr(keys), _ptr(flag)),
                   "pcc_morton_keys_frames")
             perm = rt.sort_pairs(keys)
+            if lod:      # a cell's keys differ in their low 3 lod bits only (the batch index above bit 48 stays)
+                keys.bitwise_and_(-(1 << (3 * lod)))
             # duplicates (np.unique): the first row of every run of equal keys
             rows = rt.empty((n,), torch.int32)
             n_u = C.c_int64(0)
@@ -115,7 +142,7 @@ class GeometryCodec:
                 raise PccError(PCC_E_RANGE, "GeometryCodec.compress", "coordinate outside [-32768, 32767]")
             if n_u.value < n:
                 keys = rt.gather_rows(keys, rows[:n_u.value])
-            blobs = rt.octree_encode_frames(keys, nb)
+            blobs = rt.octree_encode_frames(keys, nb, 3 * lod)
             if attrs is None:
                 return blobs
             return blobs, self._encode_attributes(rt, attrs, sizes, blobs, perm, rows, n_u.value)
@@ -138,15 +165,24 @@ class GeometryCodec:
         row_offsets = np.cumsum([0] + list(sizes)).tolist()
         return rt.attr_encode_frames(values, offs, formats, row_offsets, points, perm, rows, n_unique)
 
-    def decompress(self, blobs, attr_blobs=None, output="numpy"):
+    def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0):
         """version-2 blobs -> a list of int32 [n_f, 3] point sets in Morton order: numpy arrays (output="numpy") or
         device tensors (output="device", on this codec's device).  With attr_blobs (compress(..., attributes=...)):
         (point sets, attributes), attributes[f] an [n_f, c] array in its original dtype, row i belonging to point i; an
-        attribute blob decodes only with the geometry blob of its own frame (another point count raises PccError)."""
+        attribute blob decodes only with the geometry blob of its own frame (another point count raises PccError).
+        lod = k > 0: blobs or prefixes of them (lod_info) -> the distinct cell indices points >> k of every frame, int32
+        [cells, 3] in Morton order (corner of a cell c << k, centre (c << k) + ((1 << k) >> 1)); not together with
+        attr_blobs."""
         if isinstance(attr_blobs, str):      # decompress(blobs, "device"), as before attributes
             attr_blobs, output = None, attr_blobs
         if output not in ("numpy", "device"):
             raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
+        lod = self._check_lod(lod)
+        if lod and attr_blobs is not None:
+            raise ValueError("attributes cannot be decoded at lod > 0: an attribute blob is one predictive stream in "
+                             "full-resolution Morton order and a cell's mean needs the cell's leaf count, so neither "
+                             "its bytes nor its decoding can be cut; ship coarse attributes with "
+                             "compress(frames, attributes=..., lod=k)")
         blobs = [bytes(b) for b in blobs]
         if len(blobs) > MAX_FRAMES:
             raise ValueError(f"{len(blobs)} blobs in one call, at most {MAX_FRAMES}")
@@ -155,11 +191,11 @@ class GeometryCodec:
             if len(attr_blobs) != len(blobs):
                 raise ValueError(f"{len(attr_blobs)} attribute blobs for {len(blobs)} geometry blobs")
         with self._lock, self.rt as rt:
-            frames = rt.octree_decode_frames(blobs, device=(output == "device"))
+            frames = rt.octree_decode_frames(blobs, device=(output == "device"), lod=lod)
             if attr_blobs is None:
                 return frames
             return frames, rt.attr_decode_frames(attr_blobs, points=[f.shape[0] for f in frames],
                                                  device=(output == "device"))
 
 
-__all__ = ["GeometryCodec", "PccError", "MAX_FRAMES"]
+__all__ = ["GeometryCodec", "PccError", "MAX_FRAMES", "MAX_LOD"]

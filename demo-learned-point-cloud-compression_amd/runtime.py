@@ -563,28 +563,47 @@ class Runtime:
               "pcc_octree_encode_frames")
         return [out[offs[f]:offs[f + 1]].tobytes() for f in range(n_frames)]
 
-    def octree_decode_frames(self, blobs, device=False):
-        """version-2 blobs -> one int32 [n_f, 3] array per blob, Morton order (pcc_octree_decode_frames): numpy arrays,
-        or views of one device tensor (device=True)"""
+    @staticmethod
+    def octree_lod_info(blob, lod):
+        """(bytes, cells) of level of detail `lod` (0 .. 15) of a version-2 blob (pcc_octree_lod_info, host only): the
+        shortest prefix of the blob that decodes at that level, and the cells it gives.  `blob` may itself be a prefix
+        that reaches the last needed chunk's length table."""
+        buf = np.frombuffer(blob, dtype=np.uint8)
+        nbytes, cells = C.c_int64(0), C.c_int64(0)
+        check(_abi.lib().pcc_octree_lod_info(_np_ptr(buf) if buf.shape[0] else None, buf.shape[0], int(lod),
+                                             C.byref(nbytes), C.byref(cells)), "pcc_octree_lod_info")
+        return nbytes.value, cells.value
+
+    def octree_decode_frames(self, blobs, device=False, lod=0):
+        """version-2 blobs -> one int32 [n_f, 3] array per blob, Morton order (pcc_octree_decode_frames_lod): numpy
+        arrays, or views of one device tensor (device=True).  lod = k > 0: blobs or prefixes of them (octree_lod_info)
+        -> the distinct cell indices points >> k of every frame, Morton order"""
         nb = len(blobs)
         if nb == 0:
             return []
+        lod = int(lod)
+        if lod == 0:      # today's call, by its own name
+            name = "pcc_octree_decode_frames"
+            call = lambda *a: self.lib.pcc_octree_decode_frames(self.ctx, ptrs, lens, nb, *a)
+        else:
+            name = "pcc_octree_decode_frames_lod"
+            call = lambda *a: self.lib.pcc_octree_decode_frames_lod(self.ctx, ptrs, lens, nb, lod, *a)
         bufs = [np.frombuffer(b, dtype=np.uint8) for b in blobs]
         ptrs = (C.c_void_p * nb)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
         lens = (C.c_int64 * nb)(*[b.shape[0] for b in bufs])
         offs = (C.c_int64 * (nb + 1))()
-        check(self.lib.pcc_octree_decode_frames(self.ctx, ptrs, lens, nb, None, None, 0, offs), "pcc_octree_decode_frames")
+        check(call(None, None, 0, offs), name)
         total = offs[nb]
         if device:
             pts = self.empty((total, 3), torch.int32)
             if total:
-                check(self.lib.pcc_octree_decode_frames(self.ctx, ptrs, lens, nb, _ptr(pts), None, total, offs),
-                      "pcc_octree_decode_frames")
+                check(call(_ptr(pts), None, total, offs),
+                      name)
         else:   # pinned: the library copies the points straight into it (torch's host cache keeps the pages mapped)
             pts = torch.empty((total, 3), dtype=torch.int32, pin_memory=True).numpy()
             if total:
-                check(self.lib.pcc_octree_decode_frames(self.ctx, ptrs, lens, nb, None, _np_ptr(pts), total, offs),
-                      "pcc_octree_decode_frames")
+                check(call(None, _np_ptr(pts), total, offs),
+                      name)
         return [pts[offs[f]:offs[f + 1]] for f in range(nb)]
 
     def attr_encode_frames(self, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique):

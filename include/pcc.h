@@ -626,6 +626,56 @@ int pcc_octree_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs,
                              int32_t* d_points, int32_t* h_points,
                              int64_t cap_points, int64_t* h_point_offsets);
 
+/* Levels of detail of a version-2 blob: coarser cells from a PREFIX of its
+ * bytes (csrc/octree2_blob.h parses and plans it on the host).  Nodes are
+ * numbered breadth-first and dealt to lanes and chunks in that order, the
+ * chunk table lies in front of the payload and every lane owns a contiguous
+ * run of words, so the levels above a cut are a prefix of the blob; the root
+ * cube is aligned to 2^depth in biased coordinates, so the nodes of a level
+ * are global cells.  For n > 0 points, depth d, level sizes level_n[0..d-1],
+ * S, chunk table words[nc], first payload byte off_payload and a level of
+ * detail lod = k in 0 .. 15 (16 is excluded: 32768 is not a multiple of 2^16):
+ *   cut level Lc = max(d - k, 0);
+ *   cells m = n (k = 0), level_n[Lc] (0 < k < d), 1 (k >= d);
+ *   nodes needed N' = level_n[0] + .. + level_n[Lc-1];
+ *   result: int32 [m,3] CELL INDICES p >> k (arithmetic shift) of the frame's
+ *     points, distinct, in Morton order; corner of a cell c << k, centre
+ *     (c << k) + ((1 << k) >> 1).  k = 0 is pcc_octree_decode_frames' result;
+ *   shortest prefix: k = 0 the whole blob; N' = 0: off_payload bytes (header,
+ *     level table, S, nc, p0 and the WHOLE chunk table are always needed);
+ *     otherwise with lanes = ceil(N' / S), c* = (lanes-1) / 64,
+ *     l* = (lanes-1) % 64:
+ *       off_payload + 2 (words[0] + .. + words[c*-1])
+ *                   + 2 (192 + len[0] + .. + len[l*]),
+ *     len being chunk c*'s own length table.  Any longer prefix, the whole
+ *     blob included, decodes to the same result;
+ *   an empty blob (24 bytes, n = 0) has 0 cells and needs its 24 bytes at
+ *     every k.
+ *   _lod_info : host only, no ctx: h_bytes / h_cells (nullable) receive what
+ *     level `lod` needs and gives.  h_in may be the blob or any prefix long
+ *     enough to answer (it must reach the last needed chunk's length table);
+ *     a shorter one, or a damaged header: PCC_E_STREAM; another blob version
+ *     or lod outside 0 .. 15: PCC_E_ARG.
+ *   _decode_frames_lod : pcc_octree_decode_frames at a level of detail: blobs
+ *     or prefixes of them, every frame at the same lod (outside 0 .. 15:
+ *     PCC_E_ARG); pcc_octree_decode_frames is its lod = 0 call.  A prefix even
+ *     two bytes short of its level is PCC_E_STREAM ("truncated") naming the
+ *     frame, refused on the host before anything is reserved or launched.
+ *     Only the needed part of every blob is uploaded and only the needed
+ *     chunks are decoded; nodes, links and output are sized from N' and m,
+ *     which the stream verifies (level boundaries above the cut, the children
+ *     of the first N' nodes).  What a prefix cannot verify (the level sizes
+ *     below the cut, n) stays bounded by the header checks alone.  Same
+ *     launches per call as _decode_frames, one synchronisation.
+ * The sender's side of the same cells is pcc_octree_encode_frames with
+ * key_shift = 3 lod over keys that are distinct per cell. */
+int pcc_octree_lod_info(const uint8_t* h_in, int64_t len, int lod,
+                        int64_t* h_bytes, int64_t* h_cells);
+int pcc_octree_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs,
+                                 const int64_t* h_lens, int n_frames, int lod,
+                                 int32_t* d_points, int32_t* h_points,
+                                 int64_t cap_points, int64_t* h_point_offsets);
+
 /* Lossless per-point attributes of such a sequence (csrc/attr.hip: attribute
  * blob version 1, one per frame, its layout in that file's header): uint8 or
  * uint16 values, 1 <= c <= 4 channels, in the Morton order of the frame's
