@@ -21,6 +21,11 @@
 // nctx = c x 5 x 16 bpv.  Model: version 2's (12-bit probabilities, adaptation shift 4, every lane's model starts from
 // the frame's p0, a counting pass), integer only.  The blob depends on the geometry through n alone.
 // tests/attr_ref.py restates the format in numpy.
+//
+// Attribute blob, version 2 (attr_blob.h has the layout and the rule): the values of every coarser level of detail are a
+// prefix of its bytes.  The same coder over the residuals in INTRODUCTION order (k_a2_size / k_a2_scan / k_a2_place), each
+// value predicted from the Morton-first point of the next larger cell; a decoder at a level reads the level's bytes,
+// decodes its residuals and sums them along every cell's chain (k_a2_walk).  tests/attr2_ref.py restates it in numpy.
 #include "common.h"
 #include "lanerans.h"
 #include "attr_blob.h"
@@ -54,9 +59,12 @@ __device__ __forceinline__ void a_binarise(int r, int kmax, Emit emit) {
   for (int j = k - 1; j >= 0; --j) emit(2 + kmax + j, (m >> j) & 1u);
 }
 
-// residual of point i (run position s) in channel ch of a frame's merged values v[n][c]
+// residual of point i (run position s) in channel ch of a frame's merged values v[n][c]; PRED = false (version 2): v
+// holds the residuals themselves, wrapped to the value width, and the lane codes what it is handed
+template <bool PRED = true>
 __device__ __forceinline__ int a_resid(const uint16_t* __restrict__ v, int64_t i, int64_t s, int c, int ch, uint32_t mask, int half) {
   const uint32_t x = v[i * c + ch];
+  if constexpr (!PRED) return (int)((x + (uint32_t)half) & mask) - half;
   const uint32_t a = s >= 1 ? v[(i - 1) * c + ch] : 0u, b = s >= 2 ? v[(i - 2) * c + ch] : 0u;
   const uint32_t pred = s == 0 ? 0u : (s == 1 ? a : (a + b + 1u) >> 1);
   return (int)((x - pred + (uint32_t)half) & mask) - half;
@@ -103,6 +111,7 @@ __global__ __launch_bounds__(256) void k_a_merge(const uint8_t* __restrict__ in,
 }
 
 // zeros and ones seen per context over the whole frame: cnt[2 (ctx_off + ctx) + bit]; frame f takes blocks [sb, sb + sn)
+template <bool PRED>
 __global__ __launch_bounds__(256) void k_a_stats(const uint16_t* __restrict__ merged, const AFrame* __restrict__ tab, int nf,
                                                  uint32_t* __restrict__ cnt_all) {
   __shared__ uint32_t s_cnt[2 * kAMaxCtx];
@@ -117,9 +126,9 @@ __global__ __launch_bounds__(256) void k_a_stats(const uint16_t* __restrict__ me
   for (int64_t i = b * blockDim.x + threadIdx.x; i < h.n; i += nb * blockDim.x) {
     const int64_t s = i % S;
     for (int ch = 0; ch < c; ++ch) {
-      const int bk = s == 0 ? 0 : a_bucket((uint32_t)abs(a_resid(v, i - 1, s - 1, c, ch, mask, half)));
+      const int bk = s == 0 ? 0 : a_bucket((uint32_t)abs(a_resid<PRED>(v, i - 1, s - 1, c, ch, mask, half)));
       const int cbase = (ch * kAttrBuckets + bk) * P;
-      a_binarise(a_resid(v, i, s, c, ch, mask, half), kmax,
+      a_binarise(a_resid<PRED>(v, i, s, c, ch, mask, half), kmax,
                  [&](int pos, uint32_t bit) { atomicAdd(&s_cnt[2 * (cbase + pos) + bit], 1u); });
     }
   }
@@ -134,6 +143,7 @@ __global__ __launch_bounds__(256) void k_a_stats(const uint16_t* __restrict__ me
 // bit << 15) in rec[chunk][k][lane]; backward pass: the lane's rANS steps over its records in reverse (lockstep to the
 // wave's longest list, the rest masked), every renormalisation word stored downwards from the end of the lane's own
 // T-word region of `work` ([chunk][lane][T]: a step emits at most one word).  states / lens / words_out as k_o2_enc.
+template <bool PRED>
 __global__ __launch_bounds__(64) void k_a_enc(const uint16_t* __restrict__ merged, const AFrame* __restrict__ tab, int nf,
                                               const uint32_t* __restrict__ cnt_all, uint16_t* __restrict__ rec_all,
                                               uint16_t* __restrict__ work_all, uint16_t* __restrict__ states,
@@ -164,7 +174,7 @@ __global__ __launch_bounds__(64) void k_a_enc(const uint16_t* __restrict__ merge
   uint32_t bk = 0;   // 4 bits per channel: the bucket of its previous residual
   for (int64_t s = 0; s < npts; ++s) {
     for (int ch = 0; ch < c; ++ch) {
-      const int r = a_resid(v, base + s, s, c, ch, mask, half);
+      const int r = a_resid<PRED>(v, base + s, s, c, ch, mask, half);
       const int cbase = (ch * kAttrBuckets + (int)((bk >> (4 * ch)) & 15u)) * P;
       a_binarise(r, kmax, [&](int pos, uint32_t bit) {
         const int at = (cbase + pos) * kLanes + lane;
@@ -225,11 +235,14 @@ __global__ __launch_bounds__(64) void k_a_enc(const uint16_t* __restrict__ merge
 
 // the blobs, assembled where `out_all` points (pinned host memory), frame f's at out_off: frame f owns workgroups
 // [cb + f, cb + f + nc + 1) — workgroup k < nc of them moves chunk k, workgroup nc writes the header; len_out[f] =
-// bytes, or -1 (out_cap)
+// bytes, or -1 (out_cap).  V2: the head of attribute blob version 2, with the frame's 16 values-per-level counts
+// (cells_all[16 f + k], attr_blob.h) and the sender's level of detail
+template <bool V2>
 __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ work_all, const AFrame* __restrict__ tab, int nf,
                                                 const uint16_t* __restrict__ states_all, const uint16_t* __restrict__ lens_all,
                                                 const uint32_t* __restrict__ words_all, const uint16_t* __restrict__ p0_all,
-                                                uint8_t* __restrict__ out_all, long long* __restrict__ len_out) {
+                                                uint8_t* __restrict__ out_all, long long* __restrict__ len_out,
+                                                const uint32_t* __restrict__ cells_all, int slod) {
   __shared__ unsigned long long s_sum[256];
   __shared__ uint32_t s_off[kLanes + 1];
   const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].cb + i; });
@@ -247,7 +260,7 @@ __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ wor
     __syncthreads();
   }
   const unsigned long long before = s_sum[0];
-  const unsigned long long head = (unsigned long long)kAttrHead + 8ull + 2ull * h.nctx + 4ull * nc;
+  const unsigned long long head = (unsigned long long)(V2 ? kAttr2Head : kAttrHead + 8) + 2ull * h.nctx + 4ull * nc;
   if (k == nc) {
     const unsigned long long total = head + before * 2;
     const bool fits = (long long)total <= cap;
@@ -258,13 +271,16 @@ __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ wor
     if (!fits) return;
     uint32_t* o32 = reinterpret_cast<uint32_t*>(out);
     if (threadIdx.x == 0) {
-      o32[0] = (uint32_t)'A' | (1u << 8) | ((uint32_t)h.bpv << 16) | ((uint32_t)h.c << 24);
+      o32[0] = (uint32_t)'A' | ((V2 ? 2u : 1u) << 8) | ((uint32_t)(h.bpv | (V2 ? slod << 4 : 0)) << 16) | ((uint32_t)h.c << 24);
       o32[1] = (uint32_t)h.n;
       o32[2] = (uint32_t)(total - kAttrHead);
-      o32[3] = (uint32_t)h.S;
-      o32[4] = (uint32_t)h.nc;
+      o32[V2 ? 19 : 3] = (uint32_t)h.S;
+      o32[V2 ? 20 : 4] = (uint32_t)h.nc;
     }
-    uint16_t* o16 = reinterpret_cast<uint16_t*>(o32 + 5);
+    if constexpr (V2) {
+      if (threadIdx.x < 16) o32[3 + threadIdx.x] = cells_all[16 * f + threadIdx.x];
+    }
+    uint16_t* o16 = reinterpret_cast<uint16_t*>(o32 + (V2 ? 21 : 5));
     for (int i = threadIdx.x; i < h.nctx; i += blockDim.x) o16[i] = p0_all[h.ctx_off + i];
     uint32_t* wt = reinterpret_cast<uint32_t*>(o16 + h.nctx);
     for (int64_t j = threadIdx.x; j < nc; j += blockDim.x) wt[j] = words[j];
@@ -285,12 +301,23 @@ struct ADFrame {
   int64_t table_off, payload_off; // from body_off
   int64_t n, out_off;             // points; its values in the output: bytes
   int32_t S, nc, cb, c, bpv, nctx;
+  static constexpr bool kV2 = false;
+};
+// version 2 at a level of detail: n stays the whole blob's values, nc counts the chunks the level needs, n_dec its values
+// (the first n_dec of the introduction sequence), last_words the words of chunk nc - 1 that were uploaded
+struct AD2Frame : ADFrame {
+  int64_t n_dec;
+  int32_t last_words, pad;
+  static constexpr bool kV2 = true;
 };
 
-template <bool IN_LDS>
+// avail: the words of the chunk that are there to read (cw; fewer in the last chunk of a level of detail).  Version 2:
+// the values written are the residuals, in introduction order; a lane whose run the level cuts short stops there and is
+// exempt from the end checks, a lane behind it does nothing.
+template <bool IN_LDS, typename F>
 __device__ __forceinline__ void a_decode_chunk(uint16_t* s_model, const uint16_t* __restrict__ s_words,
                                                const uint16_t* __restrict__ p /* the chunk in the stream */, uint32_t cw,
-                                               const ADFrame& h, int64_t ck, int lane, uint8_t* __restrict__ out, int& bad) {
+                                               uint32_t avail, const F& h, int64_t ck, int lane, uint8_t* __restrict__ out, int& bad) {
   uint32_t x = (uint32_t)p[2 * lane] | ((uint32_t)p[2 * lane + 1] << 16);
   const uint32_t my_len = p[2 * kLanes + lane];
   uint32_t incl = my_len;
@@ -307,7 +334,7 @@ __device__ __forceinline__ void a_decode_chunk(uint16_t* s_model, const uint16_t
   const uint32_t rbase = 3u * kLanes + incl - my_len, rend = rbase + my_len;
   uint32_t pos = rbase;
   auto word_at = [&](uint32_t i) -> uint32_t {
-    const uint32_t ic = i < cw ? i : cw - 1;   // a lane at the end of the chunk's last run looks one word too far: never used
+    const uint32_t ic = i < avail ? i : avail - 1;   // a lane at the end of the chunk's last run looks one word too far: never used
     if constexpr (IN_LDS) return s_words[ic];
     return p[ic];
   };
@@ -315,7 +342,13 @@ __device__ __forceinline__ void a_decode_chunk(uint16_t* s_model, const uint16_t
   const int c = h.c, bpv = h.bpv, P = attr_positions(bpv), kmax = 8 * bpv - 1;
   const uint32_t mask = (1u << (8 * bpv)) - 1u;
   const int64_t base = (ck * kLanes + lane) * h.S;
-  const int npts = (int)std::max<int64_t>(0, std::min<int64_t>(h.S, h.n - base));
+  int npts = (int)std::max<int64_t>(0, std::min<int64_t>(h.S, h.n - base));
+  bool whole = true;
+  if constexpr (F::kV2) {
+    const int cut = (int)std::max<int64_t>(0, std::min<int64_t>(h.S, h.n_dec - base));
+    whole = cut == npts;
+    npts = cut;
+  }
   const int a_dummy = h.nctx * kLanes + lane;
   // the lane's place in its binarisation: phase 0 zero flag, 1 sign, 2 prefix (i ones so far), 3 suffix (i bits left)
   int s = 0, ch = 0, phase = 0, i = 0;
@@ -372,7 +405,7 @@ __device__ __forceinline__ void a_decode_chunk(uint16_t* s_model, const uint16_t
     if (act && done) {
       const uint32_t sh = 16u * (uint32_t)ch;
       const uint32_t a = (uint32_t)(v1 >> sh) & 0xFFFFu, b = (uint32_t)(v2 >> sh) & 0xFFFFu;
-      const uint32_t pred = s == 0 ? 0u : (s == 1 ? a : (a + b + 1u) >> 1);
+      const uint32_t pred = F::kV2 || s == 0 ? 0u : (s == 1 ? a : (a + b + 1u) >> 1);
       const uint32_t val = (pred + (neg ? 0u - m : m)) & mask;
       const int64_t o = ((base + s) * c + ch) * bpv;
       out[o] = (uint8_t)val;
@@ -389,13 +422,14 @@ __device__ __forceinline__ void a_decode_chunk(uint16_t* s_model, const uint16_t
       }
     }
   }
-  if (pos != rend) bad |= 1;   // every word of the run consumed
-  if (x != kAL) bad |= 4;      // back at the encoder's initial state
+  if (whole && pos != rend) bad |= 1;   // every word of the run consumed
+  if (whole && x != kAL) bad |= 4;      // back at the encoder's initial state
 }
 
 // block = chunk of the call: frame f owns blocks [cb, cb + nc).  Dynamic LDS: the models (nctx_max + 1 rows of 64),
 // then lds_words words for a chunk's payload
-__global__ __launch_bounds__(64) void k_a_dec(const uint8_t* __restrict__ bodies, const ADFrame* __restrict__ tab, int nf,
+template <typename F>
+__global__ __launch_bounds__(64) void k_a_dec(const uint8_t* __restrict__ bodies, const F* __restrict__ tab, int nf,
                                               int model_rows, int lds_words, uint8_t* __restrict__ out_all,
                                               int32_t* __restrict__ status_all) {
   extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
@@ -403,7 +437,7 @@ __global__ __launch_bounds__(64) void k_a_dec(const uint8_t* __restrict__ bodies
   uint16_t* s_words = s_model + (int64_t)model_rows * kLanes;
   const int lane = threadIdx.x;
   const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].cb; });
-  const ADFrame& h = tab[f];
+  const F& h = tab[f];
   const int64_t ck = (int64_t)blockIdx.x - h.cb;
   const uint8_t* body = bodies + h.body_off;
   const uint16_t* p0 = reinterpret_cast<const uint16_t*>(body);
@@ -416,43 +450,253 @@ __global__ __launch_bounds__(64) void k_a_dec(const uint8_t* __restrict__ bodies
   const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)table[ck]);
   const uint16_t* p = payload + before;
   int bad = 0;
-  if (cw <= (uint32_t)lds_words) {
-    for (uint32_t i = lane; i < cw; i += kLanes) s_words[i] = p[i];
+  uint32_t avail = cw;
+  if constexpr (F::kV2) {
+    if (ck == h.nc - 1) avail = (uint32_t)h.last_words;
+  }
+  if (avail <= (uint32_t)lds_words) {
+    for (uint32_t i = lane; i < avail; i += kLanes) s_words[i] = p[i];
     __syncthreads();
-    a_decode_chunk<true>(s_model, s_words, p, cw, h, ck, lane, out_all + h.out_off, bad);
+    a_decode_chunk<true>(s_model, s_words, p, cw, avail, h, ck, lane, out_all + h.out_off, bad);
   } else {
-    a_decode_chunk<false>(s_model, s_words, p, cw, h, ck, lane, out_all + h.out_off, bad);
+    a_decode_chunk<false>(s_model, s_words, p, cw, avail, h, ck, lane, out_all + h.out_off, bad);
   }
   const unsigned long long b1 = __ballot((bad & 1) != 0), b4 = __ballot((bad & 4) != 0);
   if (lane == 0 && (b1 | b4) != 0ull) atomicOr(status_all + f, (b1 ? 1 : 0) | (b4 ? 4 : 0));
 }
 
+// ---- version 2: the introduction order ----------------------------------------------------------------------------
+// (attr_blob.h states the rule.)  One row per frame (>= 1 point) of a call, for the encoder over the call's distinct
+// sorted keys and for the decoder over the cells its geometry decode left in HBM: frame f's points are [pt0, pt0 + n)
+// of the call's, it owns blocks [blk0, blk0 + ceil(n / 256)) of the three kernels below.  shift: the encoder's
+// key_shift (keys of cells: a multiple of 3 low bits are zero), the decoder's level of detail (cells p >> lod, biased
+// by 32768 >> lod, lod counting from the points the sender had).
+struct A2Order {
+  int64_t pt0, n;
+  int32_t blk0, shift;
+};
+constexpr int kA2Bins = 17;   // sizes of introduction 0 .. 16
+
+__device__ __forceinline__ uint64_t a2_cell_key(const int32_t* __restrict__ cells, int64_t i, int bias) {
+  const int32_t* q = cells + 3 * i;
+  return (pcc_spread3((uint32_t)(q[0] + bias)) << 2) | (pcc_spread3((uint32_t)(q[1] + bias)) << 1) | pcc_spread3((uint32_t)(q[2] + bias));
+}
+
+// s(i) of every point, its rank among the points of its block with the same s (packed[i] = s << 8 | rank) and the
+// block's count per s (hist[17 block + s]); FROM_CELLS: the keys of the cells are computed here and kept (keys_out)
+template <bool FROM_CELLS>
+__global__ __launch_bounds__(256) void k_a2_size(const void* __restrict__ src, const A2Order* __restrict__ tab, int nf,
+                                                 uint64_t* __restrict__ keys_out, uint16_t* __restrict__ packed,
+                                                 uint32_t* __restrict__ hist) {
+  __shared__ uint32_t s_cnt[4][kA2Bins];
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].blk0; });
+  const A2Order& h = tab[f];
+  const int64_t i = ((int64_t)blockIdx.x - h.blk0) * blockDim.x + threadIdx.x;
+  const bool act = i < h.n;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int bin = kA2Bins;   // none
+  if (act) {
+    uint64_t key, prev = 0;
+    int sh = 0;
+    if constexpr (FROM_CELLS) {
+      const int32_t* cells = static_cast<const int32_t*>(src);
+      const int bias = 32768 >> h.shift;
+      key = a2_cell_key(cells, h.pt0 + i, bias);
+      if (i > 0) prev = a2_cell_key(cells, h.pt0 + i - 1, bias);
+      keys_out[h.pt0 + i] = key;
+    } else {
+      const uint64_t* keys = static_cast<const uint64_t*>(src);
+      key = keys[h.pt0 + i];
+      if (i > 0) prev = keys[h.pt0 + i - 1];
+      sh = h.shift;
+    }
+    const uint64_t x = ((key ^ prev) & 0xFFFFFFFFFFFFull) >> sh;
+    bin = i == 0 ? 16 : (x ? (63 - __clzll((long long)x)) / 3 : 0);
+  }
+  int lr = 0;
+#pragma unroll
+  for (int b = 0; b < kA2Bins; ++b) {
+    const unsigned long long m = __ballot(bin == b);
+    if (bin == b) lr = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_cnt[wave][b] = (uint32_t)__popcll(m);
+  }
+  __syncthreads();
+  if (act) {
+    for (int w = 0; w < wave; ++w) lr += (int)s_cnt[w][bin];
+    packed[h.pt0 + i] = (uint16_t)((bin << 8) | lr);
+  }
+  if (threadIdx.x < kA2Bins)
+    hist[(int64_t)blockIdx.x * kA2Bins + threadIdx.x] =
+        s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
+}
+
+// one block per frame: hist[17 block + s] becomes the number of points of size s in the frame's blocks in front of it;
+// bins[17 f + s] = the points of a larger size (where size s starts in the introduction order), cells[16 f + k] =
+// #{s >= k}
+__global__ __launch_bounds__(256) void k_a2_scan(const A2Order* __restrict__ tab, uint32_t* __restrict__ hist,
+                                                 uint32_t* __restrict__ bins, uint32_t* __restrict__ cells) {
+  __shared__ uint32_t s_w[4][kA2Bins];
+  const int f = blockIdx.x;
+  const A2Order& h = tab[f];
+  const int64_t nb = (h.n + 255) / 256;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t carry[kA2Bins];
+#pragma unroll
+  for (int b = 0; b < kA2Bins; ++b) carry[b] = 0u;
+  for (int64_t t0 = 0; t0 < nb; t0 += 256) {
+    const int64_t blk = t0 + threadIdx.x;
+    const bool in = blk < nb;
+    uint32_t* row = hist + (h.blk0 + blk) * kA2Bins;
+    uint32_t v[kA2Bins], inc[kA2Bins];
+#pragma unroll
+    for (int b = 0; b < kA2Bins; ++b) {
+      v[b] = in ? row[b] : 0u;
+      uint32_t x = v[b];
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)x, d, 64);
+        x += lane >= d ? o : 0u;
+      }
+      inc[b] = x;
+      if (lane == 63) s_w[wave][b] = x;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < kA2Bins; ++b) {
+      uint32_t pre = carry[b];
+      for (int w = 0; w < wave; ++w) pre += s_w[w][b];
+      if (in) row[b] = pre + inc[b] - v[b];
+      carry[b] += s_w[0][b] + s_w[1][b] + s_w[2][b] + s_w[3][b];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    uint32_t run = 0;
+#pragma unroll
+    for (int b = kA2Bins - 1; b >= 0; --b) {
+      bins[f * kA2Bins + b] = run;
+      run += carry[b];
+      if (b < 16) cells[f * 16 + b] = run;
+    }
+  }
+}
+
+// first(i): the first key of the frame not below key_i with its low `bits` bits cleared (bits = 3 (s + 1), + the
+// encoder's key_shift); searched in [0, i], so the result never lies behind i
+__device__ __forceinline__ int64_t a2_first(const uint64_t* __restrict__ keys, int64_t i, int bits) {
+  const uint64_t low = bits >= 48 ? 0xFFFFFFFFFFFFull : (1ull << bits) - 1ull;
+  const uint64_t t = keys[i] & ~low;
+  int64_t lo = 0, hi = i;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < t) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// the place of every point in the introduction order and its predictor.  ENC: the residual of its merged value against
+// the predictor's goes to that place of resid ([n][c] per frame at val_off, wrapped to the value width); otherwise
+// (decoder) place and predictor are kept: rank[pt0 + i], first[pt0 + i]
+template <bool ENC>
+__global__ __launch_bounds__(256) void k_a2_place(const uint64_t* __restrict__ keys_all, const A2Order* __restrict__ tab, int nf,
+                                                  const uint16_t* __restrict__ packed, const uint32_t* __restrict__ hist,
+                                                  const uint32_t* __restrict__ bins, const AFrame* __restrict__ ftab,
+                                                  const uint16_t* __restrict__ merged, uint16_t* __restrict__ resid,
+                                                  uint32_t* __restrict__ rank, uint32_t* __restrict__ first) {
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].blk0; });
+  const A2Order& h = tab[f];
+  const int64_t i = ((int64_t)blockIdx.x - h.blk0) * blockDim.x + threadIdx.x;
+  if (i >= h.n) return;
+  const uint32_t pk = packed[h.pt0 + i];
+  const int s = (int)(pk >> 8);
+  const int64_t r = (int64_t)bins[f * kA2Bins + s] + hist[(int64_t)blockIdx.x * kA2Bins + s] + (pk & 255u);
+  const int64_t j = i > 0 ? a2_first(keys_all + h.pt0, i, 3 * (s + 1) + (ENC ? h.shift : 0)) : 0;
+  if constexpr (ENC) {
+    const AFrame& a = ftab[f];
+    const uint32_t mask = (1u << (8 * a.bpv)) - 1u;
+    if (r >= h.n) return;   // cannot happen: the places are a permutation of the frame's points
+    for (int ch = 0; ch < a.c; ++ch) {
+      const uint32_t v = merged[a.val_off + i * a.c + ch], pv = i > 0 ? merged[a.val_off + j * a.c + ch] : 0u;
+      resid[a.val_off + r * a.c + ch] = (uint16_t)((v - pv) & mask);
+    }
+  } else {
+    rank[h.pt0 + i] = (uint32_t)r;
+    first[h.pt0 + i] = (uint32_t)j;
+  }
+}
+
+// decoder: the value of point (cell) i = the wrapped sum of the residuals along i -> first(i) -> .. -> 0, at most 17
+// links since every link leads to a strictly larger size.  Every index is checked against the frame's value count;
+// status |= 8 where a walk leaves it or does not end at point 0.  resid_all / out_all: the frames' [m][c] values of bpv
+// bytes at out_off, residuals in introduction order / values in Morton order.
+__global__ __launch_bounds__(256) void k_a2_walk(const A2Order* __restrict__ tab, int nf, const AD2Frame* __restrict__ ftab,
+                                                 const uint32_t* __restrict__ rank, const uint32_t* __restrict__ first,
+                                                 const uint8_t* __restrict__ resid_all, uint8_t* __restrict__ out_all,
+                                                 int32_t* __restrict__ status_all) {
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].blk0; });
+  const A2Order& h = tab[f];
+  const AD2Frame& a = ftab[f];
+  const int64_t i = ((int64_t)blockIdx.x - h.blk0) * blockDim.x + threadIdx.x;
+  if (i >= h.n) return;
+  const int c = a.c, bpv = a.bpv;
+  const uint8_t* resid = resid_all + a.out_off;
+  uint32_t acc[4] = {0u, 0u, 0u, 0u};
+  int64_t j = i;
+  bool ok = false;
+  for (int step = 0; step < kA2Bins; ++step) {
+    const int64_t r = rank[h.pt0 + j];
+    if (r >= h.n) break;
+    const uint8_t* q = resid + r * c * bpv;
+    for (int ch = 0; ch < c; ++ch) acc[ch] += bpv == 1 ? (uint32_t)q[ch] : (uint32_t)q[2 * ch] | ((uint32_t)q[2 * ch + 1] << 8);
+    if (j == 0) {
+      ok = true;
+      break;
+    }
+    const int64_t nj = first[h.pt0 + j];
+    if (nj >= j) break;
+    j = nj;
+  }
+  if (!ok) atomicOr(status_all + f, 8);
+  uint8_t* o = out_all + a.out_off + i * c * bpv;
+  for (int ch = 0; ch < c; ++ch) {
+    o[bpv * ch] = (uint8_t)acc[ch];
+    if (bpv == 2) o[2 * ch + 1] = (uint8_t)(acc[ch] >> 8);
+  }
+}
+
 }  // namespace
 
 static inline int64_t a_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+static inline size_t merged_b_of(int64_t vals) { return pcc_align((size_t)vals * 2); }
 
 // ======================================================================== C-ABI (include/pcc.h)
-extern "C" int pcc_attr_encode_frames(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets, const int32_t* h_format,
-                                      const int64_t* h_rows, const int64_t* h_points, int n_frames, const uint32_t* d_perm,
-                                      const uint32_t* d_run_starts, int64_t n_unique, uint8_t* h_out, int64_t cap,
-                                      int64_t* h_offsets) {
+// both versions' encoder: version 2 codes, instead of the merged values, their residuals in introduction order
+// (k_a2_size / k_a2_scan / k_a2_place over d_keys, the call's distinct sorted keys)
+static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
+                           const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
+                           const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys,
+                           int key_shift, uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
+  const bool v2 = version == 2;
   PCC_REQUIRE(ctx && h_value_offsets && h_format && h_rows && h_points && h_out && h_offsets && n_frames >= 1 &&
                   n_frames <= 65535 && n_unique >= 0 && cap >= 0,
-              PCC_E_ARG, "pcc_attr_encode_frames: bad argument (n_frames=%d)", n_frames);
+              PCC_E_ARG, "%s: bad argument (n_frames=%d)", who, n_frames);
   const int64_t n_keys = h_rows[n_frames];
   PCC_REQUIRE(h_rows[0] == 0 && n_keys < ((int64_t)1 << 27) && n_unique <= n_keys &&
                   (n_keys == 0 || (d_values && d_perm && d_run_starts)),
-              PCC_E_ARG, "pcc_attr_encode_frames: %lld rows, %lld points", (long long)n_keys, (long long)n_unique);
+              PCC_E_ARG, "%s: %lld rows, %lld points", who, (long long)n_keys, (long long)n_unique);
+  PCC_REQUIRE(!v2 || (key_shift >= 0 && key_shift <= 45 && key_shift % 3 == 0 && (n_keys == 0 || d_keys)), PCC_E_ARG,
+              "%s: bad argument (key_shift=%d)", who, key_shift);
   std::vector<AFrame> tab;
+  std::vector<A2Order> order;
   std::vector<int> frame_of;
   int64_t u = 0, vals = 0, rec_words = 0, out_bytes = 0, chunks = 0, stats_blocks = 0, merge_blocks = 0, ctxs = 0, nctx_max = 0;
   for (int f = 0; f < n_frames; ++f) {
     const int bpv = h_format[f] & 0xFF, c = h_format[f] >> 8;
     const int64_t rows = h_rows[f + 1] - h_rows[f], n = h_points[f];
-    PCC_REQUIRE((bpv == 1 || bpv == 2) && c >= 1 && c <= 4, PCC_E_ARG, "pcc_attr_encode_frames: frame %d: format %d", f,
+    PCC_REQUIRE((bpv == 1 || bpv == 2) && c >= 1 && c <= 4, PCC_E_ARG, "%s: frame %d: format %d", who, f,
                 h_format[f]);
     PCC_REQUIRE(rows >= 0 && n >= 0 && n <= rows && (n == 0) == (rows == 0) && h_value_offsets[f] >= 0, PCC_E_ARG,
-                "pcc_attr_encode_frames: frame %d: %lld rows, %lld points", f, (long long)rows, (long long)n);
+                "%s: frame %d: %lld rows, %lld points", who, f, (long long)rows, (long long)n);
     if (n == 0) continue;
     AFrame r;
     int64_t S, nc;
@@ -469,7 +713,7 @@ extern "C" int pcc_attr_encode_frames(pcc_ctx* ctx, const void* d_values, const 
     r.nctx = attr_contexts(bpv, c);
     r.ctx_off = (int32_t)ctxs;
     r.T = (int32_t)(S * c * attr_positions(bpv));
-    const int64_t head = kAttrHead + 8 + 2 * r.nctx + 4 * nc;
+    const int64_t head = (v2 ? kAttr2Head : kAttrHead + 8) + 2 * r.nctx + 4 * nc;
     // a coded decision emits at most one word: the bound follows the frame's decisions, not its chunks' regions
     r.out_cap = head + 2 * (3 * kLanes * nc + std::min<int64_t>(nc * kLanes * r.T, (int64_t)attr_positions(bpv) * c * n));
     r.out_off = out_bytes;
@@ -480,6 +724,7 @@ extern "C" int pcc_attr_encode_frames(pcc_ctx* ctx, const void* d_values, const 
     r.sn = (int32_t)std::min<unsigned>(nblk(n, 256), 256u);
     r.mb = (int32_t)merge_blocks;
     tab.push_back(r);
+    order.push_back(A2Order{u, n, r.mb, key_shift});
     frame_of.push_back(f);
     u += n;
     vals += n * c;
@@ -491,17 +736,21 @@ extern "C" int pcc_attr_encode_frames(pcc_ctx* ctx, const void* d_values, const 
     ctxs += r.nctx;
     nctx_max = std::max<int64_t>(nctx_max, r.nctx);
   }
-  PCC_REQUIRE(u == n_unique, PCC_E_ARG, "pcc_attr_encode_frames: the frames have %lld points, the runs %lld", (long long)u,
+  PCC_REQUIRE(u == n_unique, PCC_E_ARG, "%s: the frames have %lld points, the runs %lld", who, (long long)u,
               (long long)n_unique);
   const int nf = (int)tab.size();
   std::vector<int64_t> len_of((size_t)n_frames, kAttrHead);
   std::vector<int64_t> off_of((size_t)n_frames, -1);
   hipStream_t st = ctx->stream;
   if (nf > 0) {
-    const size_t tab_b = pcc_align((size_t)nf * sizeof(AFrame));
+    const size_t ord_b = v2 ? pcc_align((size_t)nf * sizeof(A2Order)) : 0;
+    const size_t tab_b = pcc_align((size_t)nf * sizeof(AFrame)) + ord_b;
+    const size_t v2_b = v2 ? 2 * merged_b_of(vals) + pcc_align((size_t)u * 2) + pcc_align((size_t)merge_blocks * 17 * 4) +
+                                 pcc_align((size_t)nf * 33 * 4)
+                           : 0;
     const size_t merged_b = pcc_align((size_t)vals * 2), cnt_b = pcc_align((size_t)ctxs * 8), p0_b = pcc_align((size_t)ctxs * 2);
     const size_t rec_b = pcc_align((size_t)rec_words * 2), small_b = pcc_align((size_t)chunks * (4 + 2 * kLanes * 2 + kLanes * 2));
-    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + 8192));
+    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + v2_b + 8192));
     AFrame* d_tab = (AFrame*)pcc_arena_alloc(ctx, tab_b);
     uint16_t* merged = (uint16_t*)pcc_arena_alloc(ctx, merged_b);
     uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, cnt_b);
@@ -518,36 +767,67 @@ extern "C" int pcc_attr_encode_frames(pcc_ctx* ctx, const void* d_values, const 
     PCC_TRY(o2_stage_reserve(ctx, lens_at + (size_t)nf * 8 + 64));
     uint8_t* stage = (uint8_t*)ctx->stage;
     memcpy(stage, tab.data(), (size_t)nf * sizeof(AFrame));
+    if (v2) memcpy(stage + tab_b - ord_b, order.data(), (size_t)nf * sizeof(A2Order));
     long long* len_dev = (long long*)(stage + lens_at);
     PccProfScope prof(ctx, "attr_encode", u, nf, chunks, 0);
-    PCC_HIP(hipMemcpyAsync(d_tab, stage, (size_t)nf * sizeof(AFrame), hipMemcpyHostToDevice, st));
+    PCC_HIP(hipMemcpyAsync(d_tab, stage, v2 ? tab_b - ord_b + (size_t)nf * sizeof(A2Order) : (size_t)nf * sizeof(AFrame),
+                           hipMemcpyHostToDevice, st));
     PCC_HIP(hipMemsetAsync(cnt, 0, (size_t)ctxs * 8, st));
     hipLaunchKernelGGL(k_a_merge, dim3((unsigned)merge_blocks), dim3(256), 0, st, (const uint8_t*)d_values, (const AFrame*)d_tab, nf,
                        d_perm, d_run_starts, n_unique, n_keys, merged);
     PCC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_a_stats, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)merged, (const AFrame*)d_tab, nf, cnt);
-    PCC_CHECK_LAUNCH();
     const size_t lds = 4096 * 4 + (size_t)(nctx_max + 1) * kLanes * 2;   // <= 98 KB (c = 4, uint16)
-    PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_a_enc, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)merged, (const AFrame*)d_tab, nf,
-                       (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
-    PCC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_a_pack, dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work, (const AFrame*)d_tab, nf,
-                       (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words, (const uint16_t*)p0,
-                       stage + tab_b, len_dev);
-    PCC_CHECK_LAUNCH();
+    if (!v2) {
+      hipLaunchKernelGGL(k_a_stats<true>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)merged, (const AFrame*)d_tab, nf, cnt);
+      PCC_CHECK_LAUNCH();
+      PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(k_a_enc<true>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)merged, (const AFrame*)d_tab, nf,
+                         (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
+      PCC_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_a_pack<false>, dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work, (const AFrame*)d_tab, nf,
+                         (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words, (const uint16_t*)p0,
+                         stage + tab_b, len_dev, (const uint32_t*)nullptr, 0);
+      PCC_CHECK_LAUNCH();
+    } else {
+      const A2Order* d_ord = (const A2Order*)((const uint8_t*)d_tab + tab_b - ord_b);
+      uint16_t* resid = (uint16_t*)pcc_arena_alloc(ctx, merged_b_of(vals));
+      uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, (size_t)u * 2);
+      uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, (size_t)merge_blocks * 17 * 4);
+      uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nf * 33 * 4);   // 17 bin bases, then 16 counts per frame
+      if (!resid || !packed || !hist || !bins) return PCC_E_NOMEM;
+      uint32_t* cells = bins + (size_t)nf * 17;
+      hipLaunchKernelGGL(k_a2_size<false>, dim3((unsigned)merge_blocks), dim3(256), 0, st, (const void*)d_keys, d_ord, nf,
+                         (uint64_t*)nullptr, packed, hist);
+      PCC_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_a2_scan, dim3((unsigned)nf), dim3(256), 0, st, d_ord, hist, bins, cells);
+      PCC_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_a2_place<true>, dim3((unsigned)merge_blocks), dim3(256), 0, st, d_keys, d_ord, nf,
+                         (const uint16_t*)packed, (const uint32_t*)hist, (const uint32_t*)bins, (const AFrame*)d_tab,
+                         (const uint16_t*)merged, resid, (uint32_t*)nullptr, (uint32_t*)nullptr);
+      PCC_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_a_stats<false>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)resid, (const AFrame*)d_tab, nf, cnt);
+      PCC_CHECK_LAUNCH();
+      PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(k_a_enc<false>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)resid, (const AFrame*)d_tab, nf,
+                         (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
+      PCC_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_a_pack<true>, dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work, (const AFrame*)d_tab, nf,
+                         (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words, (const uint16_t*)p0,
+                         stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3);
+      PCC_CHECK_LAUNCH();
+    }
     PCC_HIP(hipStreamSynchronize(st));
     for (int k = 0; k < nf; ++k) {
       const long long total = ((volatile long long*)len_dev)[k];
       PCC_REQUIRE(total >= 0 && total <= tab[(size_t)k].out_cap, PCC_E_NOMEM,
-                  "pcc_attr_encode_frames: frame %d: blob beyond its bound", frame_of[(size_t)k]);
+                  "%s: frame %d: blob beyond its bound", who, frame_of[(size_t)k]);
       len_of[(size_t)frame_of[(size_t)k]] = total;
       off_of[(size_t)frame_of[(size_t)k]] = (int64_t)tab_b + tab[(size_t)k].out_off;
     }
   }
   int64_t total = 0;
   for (int f = 0; f < n_frames; ++f) total += len_of[(size_t)f];
-  PCC_REQUIRE(total <= cap, PCC_E_NOMEM, "pcc_attr_encode_frames: %lld bytes of blobs, capacity %lld", (long long)total,
+  PCC_REQUIRE(total <= cap, PCC_E_NOMEM, "%s: %lld bytes of blobs, capacity %lld", who, (long long)total,
               (long long)cap);
   h_offsets[0] = 0;
   for (int f = 0; f < n_frames; ++f) {
@@ -557,13 +837,29 @@ extern "C" int pcc_attr_encode_frames(pcc_ctx* ctx, const void* d_values, const 
     } else {   // no points: the 12-byte empty blob
       memset(dst, 0, kAttrHead);
       dst[0] = 'A';
-      dst[1] = 1;
-      dst[2] = (uint8_t)(h_format[f] & 0xFF);
+      dst[1] = (uint8_t)version;
+      dst[2] = (uint8_t)((h_format[f] & 0xFF) | (v2 ? (key_shift / 3) << 4 : 0));
       dst[3] = (uint8_t)(h_format[f] >> 8);
     }
     h_offsets[f + 1] = h_offsets[f] + len_of[(size_t)f];
   }
   return PCC_OK;
+}
+
+extern "C" int pcc_attr_encode_frames(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets, const int32_t* h_format,
+                                      const int64_t* h_rows, const int64_t* h_points, int n_frames, const uint32_t* d_perm,
+                                      const uint32_t* d_run_starts, int64_t n_unique, uint8_t* h_out, int64_t cap,
+                                      int64_t* h_offsets) {
+  return a_encode_frames("pcc_attr_encode_frames", 1, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm,
+                         d_run_starts, n_unique, nullptr, 0, h_out, cap, h_offsets);
+}
+
+extern "C" int pcc_attr_encode_frames_v2(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets, const int32_t* h_format,
+                                         const int64_t* h_rows, const int64_t* h_points, int n_frames, const uint32_t* d_perm,
+                                         const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys, int key_shift,
+                                         uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
+  return a_encode_frames("pcc_attr_encode_frames_v2", 2, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm,
+                         d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets);
 }
 
 extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
@@ -657,8 +953,8 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
   const int64_t room = ((int64_t)128 * 1024 - (int64_t)model_rows * kLanes * 2) / 2;
   const int lds_words = (int)std::max<int64_t>(0, std::min<int64_t>(cw_max, room));
   const size_t lds = (size_t)model_rows * kLanes * 2 + (size_t)lds_words * 2;
-  PCC_HIP(hipFuncSetAttribute((const void*)k_a_dec, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_a_dec, dim3((unsigned)chunks), dim3(64), lds, st, (const uint8_t*)(d_in + tab_b), (const ADFrame*)d_in, nf,
+  PCC_HIP(hipFuncSetAttribute((const void*)k_a_dec<ADFrame>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_a_dec<ADFrame>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint8_t*)(d_in + tab_b), (const ADFrame*)d_in, nf,
                      model_rows, lds_words, out, status);
   PCC_CHECK_LAUNCH();
   uint8_t* stage_out = stage + pcc_align(in_b);
@@ -671,6 +967,183 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
     const int32_t bad = h_status[k++];
     PCC_REQUIRE(bad == 0, PCC_E_STREAM, "pcc_attr_decode_frames: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state)",
                 f, bad);
+  }
+  if (h_out && !direct) memcpy(h_out, stage_out, out_b);
+  return PCC_OK;
+}
+
+// ---- version 2: levels of detail ----------------------------------------------------------------------------------
+extern "C" int pcc_attr_lod_info(const uint8_t* h_in, int64_t len, int lod, int64_t* h_bytes, int64_t* h_values) {
+  PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "pcc_attr_lod_info: level of detail %d outside 0 .. %d", lod, kAttrMaxLod);
+  PCC_REQUIRE(h_in && len >= 2 && h_in[0] == 'A', PCC_E_STREAM, "pcc_attr_lod_info: not an attribute blob (len=%lld)", (long long)len);
+  PCC_REQUIRE(h_in[1] == 2, PCC_E_ARG, "pcc_attr_lod_info: attribute blob version %d (levels of detail are a property of version 2)",
+              (int)h_in[1]);
+  Attr2Info o;
+  Attr2Plan pl;
+  const int rc = attr2_parse(h_in, len, lod, false, &o, &pl);
+  if (rc != PCC_OK) {
+    const std::string m = pcc_last_error();
+    pcc_set_error("pcc_attr_lod_info: %s", m.c_str());
+    return rc;
+  }
+  if (h_bytes) *h_bytes = pl.bytes;
+  if (h_values) *h_values = pl.m;
+  return PCC_OK;
+}
+
+extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames, int lod,
+                                          const int32_t* d_cells, const int64_t* h_cell_offsets, uint8_t* d_out, uint8_t* h_out,
+                                          int64_t cap_bytes, int64_t* h_out_offsets, int32_t* h_format) {
+  const char* who = "pcc_attr_decode_frames_lod";
+  PCC_REQUIRE(ctx && h_blobs && h_lens && h_out_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
+              "%s: bad argument (n_frames=%d)", who, n_frames);
+  PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "%s: level of detail %d outside 0 .. %d", who, lod, kAttrMaxLod);
+  std::vector<Attr2Info> info((size_t)n_frames);
+  std::vector<Attr2Plan> plan((size_t)n_frames);
+  int64_t bytes = 0, bodies = 0, points = 0;
+  h_out_offsets[0] = 0;
+  for (int f = 0; f < n_frames; ++f) {
+    Attr2Info& o = info[(size_t)f];
+    Attr2Plan& pl = plan[(size_t)f];
+    const int rc = attr2_parse(h_blobs[f], h_lens[f], lod, true, &o, &pl);
+    if (rc != PCC_OK) {
+      const std::string m = pcc_last_error();
+      pcc_set_error("%s: frame %d: %s", who, f, m.c_str());
+      return rc;
+    }
+    if (h_cell_offsets) {
+      const int64_t m = h_cell_offsets[f + 1] - h_cell_offsets[f];
+      PCC_REQUIRE(m == pl.m, PCC_E_STREAM, "%s: frame %d: the attribute blob has %lld values at level of detail %d, its geometry %lld cells",
+                  who, f, (long long)pl.m, lod, (long long)m);
+    }
+    PCC_REQUIRE(o.slod + lod <= kAttrMaxLod, PCC_E_ARG,
+                "%s: frame %d: level of detail %d of cells the sender coded at its level %d: beyond %d", who, f, lod, o.slod, kAttrMaxLod);
+    if (h_format) h_format[f] = o.bpv | (o.c << 8);
+    bytes = a_round(bytes + pl.m * o.c * o.bpv, 16);
+    points += pl.m;
+    h_out_offsets[f + 1] = bytes;
+    if (pl.m) bodies += a_round(pl.bytes - o.off_p0, 16);
+  }
+  PCC_REQUIRE(points < ((int64_t)1 << 31), PCC_E_ARG, "%s: the blobs announce %lld values in all", who, (long long)points);
+  if (bytes == 0 || (!d_out && !h_out)) return PCC_OK;
+  PCC_REQUIRE(d_cells && h_cell_offsets && h_cell_offsets[0] >= 0, PCC_E_ARG, "%s: the cells of the frames are needed", who);
+  PCC_REQUIRE(cap_bytes >= bytes, PCC_E_NOMEM, "%s: %lld bytes, capacity %lld", who, (long long)bytes, (long long)cap_bytes);
+  std::vector<AD2Frame> tab;
+  std::vector<A2Order> order;
+  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, blocks = 0;
+  const int64_t cell0 = h_cell_offsets[0];
+  for (int f = 0; f < n_frames; ++f) {
+    const Attr2Info& o = info[(size_t)f];
+    const Attr2Plan& pl = plan[(size_t)f];
+    if (pl.m == 0) continue;
+    AD2Frame r;
+    r.body_off = body_off;
+    r.table_off = o.off_table - o.off_p0;
+    r.payload_off = o.off_payload - o.off_p0;
+    r.n = o.n;
+    r.out_off = h_out_offsets[f];
+    r.S = (int32_t)o.S;
+    r.nc = (int32_t)pl.chunks;
+    r.cb = (int32_t)chunks;
+    r.c = o.c;
+    r.bpv = o.bpv;
+    r.nctx = o.nctx;
+    r.n_dec = pl.m;
+    r.last_words = (int32_t)pl.last_words;
+    r.pad = 0;
+    tab.push_back(r);
+    order.push_back(A2Order{h_cell_offsets[f] - cell0, pl.m, (int32_t)blocks, lod + o.slod});
+    for (int64_t k = 0; k + 1 < pl.chunks; ++k) cw_max = std::max<int64_t>(cw_max, attr_u32(h_blobs[f] + o.off_table + 4 * k));
+    cw_max = std::max<int64_t>(cw_max, pl.last_words);
+    body_off += a_round(pl.bytes - o.off_p0, 16);
+    chunks += pl.chunks;
+    blocks += nblk(pl.m, 256);
+    nctx_max = std::max<int64_t>(nctx_max, o.nctx);
+  }
+  const int64_t cells_all = h_cell_offsets[n_frames] - cell0;
+  const int32_t* cells = d_cells + 3 * cell0;
+  const int nf = (int)tab.size();
+  hipStream_t st = ctx->stream;
+  const size_t ftab_b = pcc_align((size_t)nf * sizeof(AD2Frame)), ord_b = pcc_align((size_t)nf * sizeof(A2Order));
+  const size_t tab_b = ftab_b + ord_b;
+  const size_t keys_b = pcc_align((size_t)cells_all * 8), u32_b = pcc_align((size_t)cells_all * 4), pk_b = pcc_align((size_t)cells_all * 2);
+  // 17 bin bases per frame | 16 counts per frame | status per frame: the last two come back in one copy
+  const size_t hist_b = pcc_align((size_t)blocks * kA2Bins * 4), bins_b = pcc_align((size_t)nf * 34 * 4 + 64);
+  PCC_TRY(pcc_arena_reserve(ctx, tab_b + pcc_align((size_t)bodies + 16) + (d_out ? 1 : 2) * pcc_align((size_t)bytes) + keys_b +
+                                     2 * u32_b + pk_b + hist_b + bins_b + 8192));
+  uint8_t* d_in = (uint8_t*)pcc_arena_alloc(ctx, tab_b + (size_t)bodies + 16);
+  uint8_t* out = d_out ? d_out : (uint8_t*)pcc_arena_alloc(ctx, (size_t)bytes);
+  uint8_t* resid = (uint8_t*)pcc_arena_alloc(ctx, (size_t)bytes);
+  uint64_t* keys = (uint64_t*)pcc_arena_alloc(ctx, keys_b);
+  uint32_t* rank = (uint32_t*)pcc_arena_alloc(ctx, u32_b);
+  uint32_t* first = (uint32_t*)pcc_arena_alloc(ctx, u32_b);
+  uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, pk_b);
+  uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, hist_b);
+  uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, bins_b);
+  if (!d_in || !out || !resid || !keys || !rank || !first || !packed || !hist || !bins) return PCC_E_NOMEM;
+  uint32_t* counts = bins + (size_t)nf * kA2Bins;
+  int32_t* status = (int32_t*)(counts + (size_t)nf * 16);
+  PccProfScope prof(ctx, "attr_decode_lod", points, nf, chunks, 0);
+  bool direct = false;
+  if (h_out) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, h_out) == hipSuccess)
+      direct = attr.type == hipMemoryTypeHost;
+    else
+      (void)hipGetLastError();
+  }
+  const size_t in_b = tab_b + (size_t)bodies;
+  const size_t out_b = h_out && !direct ? (size_t)bytes : 0;
+  PCC_TRY(o2_stage_reserve(ctx, pcc_align(in_b) + pcc_align(out_b) + (size_t)nf * 17 * 4 + 64));
+  uint8_t* stage = (uint8_t*)ctx->stage;
+  memcpy(stage, tab.data(), (size_t)nf * sizeof(AD2Frame));
+  memcpy(stage + ftab_b, order.data(), (size_t)nf * sizeof(A2Order));
+  for (int f = 0, k = 0; f < n_frames; ++f) {
+    if (plan[(size_t)f].m == 0) continue;
+    const Attr2Info& o = info[(size_t)f];
+    memcpy(stage + tab_b + tab[(size_t)k].body_off, h_blobs[f] + o.off_p0, (size_t)(plan[(size_t)f].bytes - o.off_p0));   // the level's bytes only
+    ++k;
+  }
+  PCC_HIP(hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
+  PCC_HIP(hipMemsetAsync(status, 0, (size_t)nf * 4, st));
+  const AD2Frame* d_tab = (const AD2Frame*)d_in;
+  const A2Order* d_ord = (const A2Order*)(d_in + ftab_b);
+  // the introduction order of the cells: nothing of it depends on the attribute stream
+  hipLaunchKernelGGL(k_a2_size<true>, dim3((unsigned)blocks), dim3(256), 0, st, (const void*)cells, d_ord, nf, keys, packed, hist);
+  PCC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_a2_scan, dim3((unsigned)nf), dim3(256), 0, st, d_ord, hist, bins, counts);
+  PCC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_a2_place<false>, dim3((unsigned)blocks), dim3(256), 0, st, (const uint64_t*)keys, d_ord, nf, (const uint16_t*)packed,
+                     (const uint32_t*)hist, (const uint32_t*)bins, (const AFrame*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr,
+                     rank, first);
+  PCC_CHECK_LAUNCH();
+  const int model_rows = (int)nctx_max + 1;
+  const int64_t room = ((int64_t)128 * 1024 - (int64_t)model_rows * kLanes * 2) / 2;
+  const int lds_words = (int)std::max<int64_t>(0, std::min<int64_t>(cw_max, room));
+  const size_t lds = (size_t)model_rows * kLanes * 2 + (size_t)lds_words * 2;
+  PCC_HIP(hipFuncSetAttribute((const void*)k_a_dec<AD2Frame>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_a_dec<AD2Frame>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint8_t*)(d_in + tab_b), d_tab, nf, model_rows,
+                     lds_words, resid, status);
+  PCC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_a2_walk, dim3((unsigned)blocks), dim3(256), 0, st, d_ord, nf, d_tab, (const uint32_t*)rank, (const uint32_t*)first,
+                     (const uint8_t*)resid, out, status);
+  PCC_CHECK_LAUNCH();
+  uint8_t* stage_out = stage + pcc_align(in_b);
+  uint32_t* h_counts = (uint32_t*)(stage_out + pcc_align(out_b));
+  int32_t* h_status = (int32_t*)(h_counts + (size_t)nf * 16);
+  if (h_out) PCC_HIP(hipMemcpyAsync(direct ? (void*)h_out : (void*)stage_out, out, (size_t)bytes, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipMemcpyAsync(h_counts, counts, (size_t)nf * 17 * 4, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipStreamSynchronize(st));
+  for (int f = 0, k = 0; f < n_frames; ++f) {
+    if (plan[(size_t)f].m == 0) continue;
+    // the coarser levels' counts of the header against those of the cells themselves
+    for (int j = 0; lod + j <= kAttrMaxLod; ++j)
+      PCC_REQUIRE((int64_t)h_counts[16 * k + j] == info[(size_t)f].cells[lod + j], PCC_E_STREAM,
+                  "%s: frame %d: attribute blob: level of detail %d announces %lld values, the cells give %u", who, f, lod + j,
+                  (long long)info[(size_t)f].cells[lod + j], h_counts[16 * k + j]);
+    const int32_t bad = h_status[k++];
+    PCC_REQUIRE(bad == 0, PCC_E_STREAM,
+                "%s: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state, 8 = predictor chain)", who, f, bad);
   }
   if (h_out && !direct) memcpy(h_out, stage_out, out_b);
   return PCC_OK;

@@ -606,55 +606,97 @@ class Runtime:
                       name)
         return [pts[offs[f]:offs[f + 1]] for f in range(nb)]
 
-    def attr_encode_frames(self, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique):
-        """attribute blobs (version 1, csrc/attr.hip) of len(formats) frames at once (pcc_attr_encode_frames): `values` a
+    def attr_encode_frames(self, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique,
+                           version=1, keys=None, key_shift=0):
+        """attribute blobs (csrc/attr.hip) of len(formats) frames at once (pcc_attr_encode_frames): `values` a
         device uint8 tensor with frame f's [rows_f, c_f] values at byte value_offsets[f], formats[f] = bytes per value |
         c_f << 8, row_offsets (n_frames + 1) the frames' rows among the call's keys, perm / run_starts what
         sort_pairs / pcc_unique_rows returned for those keys, points[f] frame f's points after the merge.  A list of
-        n_frames bytes objects."""
+        n_frames bytes objects.  version=2 (pcc_attr_encode_frames_v2): the blobs whose coarser levels of detail are
+        prefixes; `keys` the call's distinct sorted keys on the device (what octree_encode_frames took) and their
+        key_shift."""
+        if version not in (1, 2):
+            raise ValueError(f"attribute blob version {version!r}: 1 or 2")
         nf = len(formats)
         cap = 0
         for fmt, n in zip(formats, points):
             bpv, c = fmt & 0xFF, fmt >> 8
-            cap += 32 + 2 * 80 * bpv * c + 388 * (n // 64 + 1) + 32 * bpv * c * n
+            cap += 96 + 2 * 80 * bpv * c + 388 * (n // 64 + 1) + 32 * bpv * c * n
         out = np.empty(cap, dtype=np.uint8)
         offs = (C.c_int64 * (nf + 1))()
-        check(self.lib.pcc_attr_encode_frames(self.ctx, _ptr(values), (C.c_int64 * nf)(*value_offsets),
-                                              (C.c_int32 * nf)(*formats), (C.c_int64 * (nf + 1))(*row_offsets),
-                                              (C.c_int64 * nf)(*points), nf, _ptr(perm), _ptr(run_starts), n_unique,
-                                              _np_ptr(out), cap, offs), "pcc_attr_encode_frames")
+        head = (self.ctx, _ptr(values), (C.c_int64 * nf)(*value_offsets), (C.c_int32 * nf)(*formats),
+                (C.c_int64 * (nf + 1))(*row_offsets), (C.c_int64 * nf)(*points), nf, _ptr(perm), _ptr(run_starts), n_unique)
+        if version == 1:
+            check(self.lib.pcc_attr_encode_frames(*head, _np_ptr(out), cap, offs), "pcc_attr_encode_frames")
+        else:
+            check(self.lib.pcc_attr_encode_frames_v2(*head, _ptr(keys), int(key_shift), _np_ptr(out), cap, offs),
+                  "pcc_attr_encode_frames_v2")
         return [out[offs[f]:offs[f + 1]].tobytes() for f in range(nf)]
 
-    def attr_decode_frames(self, blobs, points=None, device=False):
+    @staticmethod
+    def attr_lod_info(blob, lod):
+        """(bytes, values) of level of detail `lod` (0 .. 15) of a version-2 attribute blob (pcc_attr_lod_info, host
+        only): the shortest prefix that decodes at that level, and the rows it gives.  `blob` may itself be a prefix
+        that reaches the last needed chunk's length table."""
+        buf = np.frombuffer(blob, dtype=np.uint8)
+        nbytes, values = C.c_int64(0), C.c_int64(0)
+        check(_abi.lib().pcc_attr_lod_info(_np_ptr(buf) if buf.shape[0] else None, buf.shape[0], int(lod),
+                                           C.byref(nbytes), C.byref(values)), "pcc_attr_lod_info")
+        return nbytes.value, values.value
+
+    def attr_decode_frames(self, blobs, points=None, device=False, lod=None, cells=None):
         """attribute blobs -> one [n_f, c_f] array per blob in its dtype (uint8 / uint16), row i belonging to decoded
         point i (pcc_attr_decode_frames): numpy arrays, or views of one device tensor (device=True).  points[f]
-        (optional): frame f's geometry point count, checked against the blob before anything is launched."""
+        (optional): frame f's geometry point count, checked against the blob before anything is launched.
+        lod = k (0 .. 15) with cells (pcc_attr_decode_frames_lod): version-2 blobs or prefixes of them (attr_lod_info)
+        -> row j the value of the j-th cell of the frame's geometry at that lod; `cells` the device tensors
+        octree_decode_frames(..., device=True, lod=k) returned for the same frames (views of one tensor)."""
         nb = len(blobs)
         if nb == 0:
             return []
         bufs = [np.frombuffer(b, dtype=np.uint8) for b in blobs]
         ptrs = (C.c_void_p * nb)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
         lens = (C.c_int64 * nb)(*[b.shape[0] for b in bufs])
-        pts = (C.c_int64 * nb)(*points) if points is not None else None
         offs = (C.c_int64 * (nb + 1))()
         fmt = (C.c_int32 * nb)()
-        check(self.lib.pcc_attr_decode_frames(self.ctx, ptrs, lens, nb, pts, None, None, 0, offs, fmt),
-              "pcc_attr_decode_frames")
+        if lod is None:
+            name = "pcc_attr_decode_frames"
+            pts = (C.c_int64 * nb)(*points) if points is not None else None
+            call = lambda *a: self.lib.pcc_attr_decode_frames(self.ctx, ptrs, lens, nb, pts, *a, offs, fmt)
+            rows = [struct.unpack_from("<I", b, 4)[0] if len(b) >= 8 else 0 for b in blobs]
+        else:
+            name = "pcc_attr_decode_frames_lod"
+            if cells is None or len(cells) != nb:
+                raise ValueError("attr_decode_frames at a lod needs the decoded cells of every frame")
+            rows = [int(c.shape[0]) for c in cells]
+            base = None
+            cell_offs = [0]
+            for c in cells:      # the frames' cells must lie behind one another, as octree_decode_frames leaves them
+                if c.shape[0]:
+                    if not (c.is_cuda and c.dtype == torch.int32 and c.is_contiguous()):
+                        raise ValueError("the cells must be contiguous int32 device tensors")
+                    if base is None:
+                        base = c.data_ptr() - 12 * cell_offs[-1]
+                    if c.data_ptr() != base + 12 * cell_offs[-1]:
+                        raise ValueError("the cells of the frames must be consecutive views of one device tensor")
+                cell_offs.append(cell_offs[-1] + int(c.shape[0]))
+            coffs = (C.c_int64 * (nb + 1))(*cell_offs)
+            call = lambda *a: self.lib.pcc_attr_decode_frames_lod(self.ctx, ptrs, lens, nb, int(lod), C.c_void_p(base), coffs,
+                                                                  *a, offs, fmt)
+        check(call(None, None, 0), name)
         total = offs[nb]
         if device:
             out = self.empty((max(total, 16),), torch.uint8)
             if total:
-                check(self.lib.pcc_attr_decode_frames(self.ctx, ptrs, lens, nb, pts, _ptr(out), None, total, offs, fmt),
-                      "pcc_attr_decode_frames")
+                check(call(_ptr(out), None, total), name)
         else:   # pinned: the library copies the values straight into it
             out = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True).numpy()
             if total:
-                check(self.lib.pcc_attr_decode_frames(self.ctx, ptrs, lens, nb, pts, None, _np_ptr(out), total, offs, fmt),
-                      "pcc_attr_decode_frames")
+                check(call(None, _np_ptr(out), total), name)
         res = []
         for f in range(nb):
             bpv, c = fmt[f] & 0xFF, fmt[f] >> 8
-            n = struct.unpack_from("<I", blobs[f], 4)[0]
+            n = rows[f]
             seg = out[offs[f]:offs[f] + n * c * bpv]
             if device:
                 res.append(seg.view(torch.uint8 if bpv == 1 else torch.uint16).reshape(n, c))

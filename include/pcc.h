@@ -726,6 +726,66 @@ int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs,
                            uint8_t* h_out, int64_t cap_bytes,
                            int64_t* h_out_offsets, int32_t* h_format);
 
+/* Attributes at every level of detail: attribute blob version 2 (its layout
+ * and rule in csrc/attr_blob.h's header).  Lossless like version 1, chosen by
+ * the sender; the values a decoder needs at level of detail k are a prefix of
+ * the blob's bytes, and the value of a cell is the value of its Morton-first
+ * point (a sample of the cell; the sender's side lod codes the cell's mean).
+ *   for n > 0 values and lod k in 0 .. 15:
+ *   values m = cells[k] of the header (cells[0] = n), which a decoder checks
+ *     against the cell count of the frame's geometry at the same lod;
+ *   shortest prefix: k = 0 the whole blob; otherwise lanes = ceil(m / S),
+ *     c* = (lanes-1) / 64, l* = (lanes-1) % 64:
+ *       off_payload + 2 (words[0] + .. + words[c*-1])
+ *                   + 2 (192 + len[0] + .. + len[l*]),
+ *     len being chunk c*'s own length table; header, p0 and the WHOLE chunk
+ *     table are always needed.  Any longer prefix decodes to the same result;
+ *   an empty blob (12 bytes, n = 0) has 0 values and needs its 12 bytes.
+ *   _lod_info : host only, no ctx: h_bytes / h_values (nullable) receive what
+ *     level `lod` needs and gives.  h_in may be the blob or any prefix that
+ *     reaches the last needed chunk's length table; a shorter one, or a damaged
+ *     header: PCC_E_STREAM; another blob version or lod outside 0 .. 15:
+ *     PCC_E_ARG.
+ *   _encode_frames_v2 : pcc_attr_encode_frames writing version 2.  Beside its
+ *     arguments: d_keys, the call's n_unique distinct sorted keys in HBM (what
+ *     pcc_octree_encode_frames took, frame after frame) and their key_shift
+ *     (3 lod on the sender's side of a lod, else 0; the blob records that lod
+ *     and decodes at a further level j with lod + j <= 15).  Launches: merge, size,
+ *     scan and residuals of the introduction order, counting pass, coder,
+ *     packing (7); one synchronisation.
+ *   _decode_frames_lod : version-2 blobs or prefixes of them, every frame at
+ *     the same lod (outside 0 .. 15: PCC_E_ARG), as pcc_attr_decode_frames
+ *     returns its values: row j of frame f is the value of the j-th cell.
+ *     d_cells: the int32 [*, 3] cells of all frames in HBM as
+ *     pcc_octree_decode_frames_lod left them at the same lod (they are not
+ *     uploaded again), frame f's rows h_cell_offsets[f] .. h_cell_offsets[f+1]
+ *     (n_frames+1 entries, its h_point_offsets).  A frame whose cell count
+ *     differs from the blob's cells[lod] is PCC_E_STREAM naming the frame; so
+ *     is a prefix even two bytes short of its level ("truncated"), both on the
+ *     host before anything is reserved or launched.  d_out and h_out both
+ *     NULL = sizes only (d_cells and h_cell_offsets may then be NULL).  Only
+ *     the level's bytes are uploaded and only its chunks decoded; the lane the
+ *     level cuts short stops there.  Every index of the reconstruction is
+ *     checked against the frame's value count: a corrupt stream is
+ *     PCC_E_STREAM naming its frame.  Launches: size, scan, place, coder,
+ *     walk (5); one synchronisation.  After an error the ctx stays usable. */
+int pcc_attr_lod_info(const uint8_t* h_in, int64_t len, int lod,
+                      int64_t* h_bytes, int64_t* h_values);
+int pcc_attr_encode_frames_v2(pcc_ctx* ctx, const void* d_values,
+                              const int64_t* h_value_offsets,
+                              const int32_t* h_format, const int64_t* h_rows,
+                              const int64_t* h_points, int n_frames,
+                              const uint32_t* d_perm,
+                              const uint32_t* d_run_starts, int64_t n_unique,
+                              const uint64_t* d_keys, int key_shift,
+                              uint8_t* h_out, int64_t cap, int64_t* h_offsets);
+int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs,
+                               const int64_t* h_lens, int n_frames, int lod,
+                               const int32_t* d_cells,
+                               const int64_t* h_cell_offsets, uint8_t* d_out,
+                               uint8_t* h_out, int64_t cap_bytes,
+                               int64_t* h_out_offsets, int32_t* h_format);
+
 /* ---- whole-GOP entry points ------------------------------ */
 
 /* replaces: CompressionPipeline.compress() (sender/encoder/codec_pipeline.py:
