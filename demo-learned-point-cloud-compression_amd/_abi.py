@@ -77,6 +77,10 @@ PROTOTYPES = {
     "pcc_octree_decode_ctx": (i32, [vp, vp, i64, vp, i64, pi64]),
     "pcc_octree_decode_dev": (i32, [vp, vp, i64, vp, i64, pi64, pi64]),
     "pcc_morton_keys_frames": (i32, [vp, vp, i32, i64, vp, i32, vp, vp]),
+    "pcc_morton_keys_frames_f32": (i32, [vp, vp, i64, vp, i32, f32, pf32, i32, vp, vp]),
+    "pcc_rows_index": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, i32, vp]),
+    "pcc_points_to_metric": (i32, [vp, vp, i64, i32, f32, pf32, vp]),
+    "pcc_attr_encode_frames_kept": (i32, [vp, i32, vp, pi64, pi32, pi64, pi64, i32, vp, vp, i64, i64, vp, i32, vp, i64, pi64]),
     "pcc_octree_encode_frames": (i32, [vp, vp, i64, i32, i32, vp, i64, pi64]),
     "pcc_octree_decode_frames": (i32, [vp, C.POINTER(C.c_void_p), pi64, i32, vp, vp, i64, pi64]),
     "pcc_octree_decode_frames_lod": (i32, [vp, C.POINTER(C.c_void_p), pi64, i32, i32, vp, vp, i64, pi64]),

@@ -675,13 +675,17 @@ static inline size_t merged_b_of(int64_t vals) { return pcc_align((size_t)vals *
 static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
                            const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
                            const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys,
-                           int key_shift, uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
+                           int key_shift, uint8_t* h_out, int64_t cap, int64_t* h_offsets, int64_t n_kept = -1) {
   const bool v2 = version == 2;
   PCC_REQUIRE(ctx && h_value_offsets && h_format && h_rows && h_points && h_out && h_offsets && n_frames >= 1 &&
                   n_frames <= 65535 && n_unique >= 0 && cap >= 0,
               PCC_E_ARG, "%s: bad argument (n_frames=%d)", who, n_frames);
-  const int64_t n_keys = h_rows[n_frames];
-  PCC_REQUIRE(h_rows[0] == 0 && n_keys < ((int64_t)1 << 27) && n_unique <= n_keys &&
+  // n_kept (pcc_attr_encode_frames_kept): the sorted keys behind it belong to dropped rows, which no run may reach
+  const bool drops = n_kept >= 0;
+  PCC_REQUIRE(!drops || n_kept <= h_rows[n_frames], PCC_E_ARG, "%s: %lld kept rows of %lld", who, (long long)n_kept,
+              (long long)h_rows[n_frames]);
+  const int64_t n_keys = drops ? n_kept : h_rows[n_frames];
+  PCC_REQUIRE(h_rows[0] == 0 && h_rows[n_frames] < ((int64_t)1 << 27) && n_unique <= n_keys &&
                   (n_keys == 0 || (d_values && d_perm && d_run_starts)),
               PCC_E_ARG, "%s: %lld rows, %lld points", who, (long long)n_keys, (long long)n_unique);
   PCC_REQUIRE(!v2 || (key_shift >= 0 && key_shift <= 45 && key_shift % 3 == 0 && (n_keys == 0 || d_keys)), PCC_E_ARG,
@@ -695,7 +699,8 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     const int64_t rows = h_rows[f + 1] - h_rows[f], n = h_points[f];
     PCC_REQUIRE((bpv == 1 || bpv == 2) && c >= 1 && c <= 4, PCC_E_ARG, "%s: frame %d: format %d", who, f,
                 h_format[f]);
-    PCC_REQUIRE(rows >= 0 && n >= 0 && n <= rows && (n == 0) == (rows == 0) && h_value_offsets[f] >= 0, PCC_E_ARG,
+    PCC_REQUIRE(rows >= 0 && n >= 0 && n <= rows && ((n == 0) == (rows == 0) || (drops && n == 0)) &&
+                    h_value_offsets[f] >= 0, PCC_E_ARG,
                 "%s: frame %d: %lld rows, %lld points", who, f, (long long)rows, (long long)n);
     if (n == 0) continue;
     AFrame r;
@@ -860,6 +865,18 @@ extern "C" int pcc_attr_encode_frames_v2(pcc_ctx* ctx, const void* d_values, con
                                          uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
   return a_encode_frames("pcc_attr_encode_frames_v2", 2, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm,
                          d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets);
+}
+
+extern "C" int pcc_attr_encode_frames_kept(pcc_ctx* ctx, int version, const void* d_values, const int64_t* h_value_offsets,
+                                           const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
+                                           const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, int64_t n_kept,
+                                           const uint64_t* d_keys, int key_shift, uint8_t* h_out, int64_t cap,
+                                           int64_t* h_offsets) {
+  PCC_REQUIRE((version == 1 || version == 2) && n_kept >= 0, PCC_E_ARG,
+              "pcc_attr_encode_frames_kept: bad argument (version=%d n_kept=%lld)", version, (long long)n_kept);
+  return a_encode_frames("pcc_attr_encode_frames_kept", version, ctx, d_values, h_value_offsets, h_format, h_rows, h_points,
+                         n_frames, d_perm, d_run_starts, n_unique, version == 2 ? d_keys : nullptr, version == 2 ? key_shift : 0,
+                         h_out, cap, h_offsets, n_kept);
 }
 
 extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,

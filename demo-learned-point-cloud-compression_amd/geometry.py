@@ -31,6 +31,16 @@ the values of every coarser level are a prefix of that blob's bytes too.
 Row j of attrs[f] is the value of the Morton-first point of cell j: a SAMPLE of the cell, where the sender's side
 compress(frames, attributes=..., lod=2) stores the cell's MEAN.  At lod 0 version 2 returns what version 1 returns.
 
+Metric frames (include/pcc.h has the rule): float32 points in the caller's unit, from the host or from this codec's
+device, are put on the lattice by the codec, q = rint((x - origin) / voxel) per coordinate in float32; rows without a
+return (NaN / Inf) can be dropped, and the row index says which decoded row every input row became.
+
+    blobs = codec.compress([xyz0, xyz1, ...], voxel=0.02, invalid="drop")      # float32 [n_f, 3], numpy or torch
+    blobs, index = codec.compress(frames, voxel=0.02, return_index=True)       # index[f]: int32 [n_f], -1 = dropped
+    frames = codec.decompress(blobs, voxel=0.02)                               # float32 [n_f, 3]: origin + c * voxel
+
+voxel and origin are not written into any blob: the caller carries the grid.
+
 One Runtime (ctx + stream) per codec; calls on the same instance are serialised, instances on different threads run
 side by side.
 """
@@ -57,19 +67,57 @@ class GeometryCodec:
     def close(self):
         self.rt.close()
 
-    @staticmethod
-    def _check_frames(frames):
-        out = []
+    def _check_frames(self, frames):
+        """-> (frames, is_float, on_device): numpy arrays (host) or tensors on this codec's device, all integer (int16 /
+        int32) or all float32"""
+        out, kinds, places = [], [], []
         for f, a in enumerate(frames):
-            a = np.asarray(a)
+            if isinstance(a, torch.Tensor):
+                if a.device.type == "cpu":
+                    a = a.detach().numpy()
+                elif a.device != self.rt.device:
+                    raise ValueError(f"frame {f}: a tensor on {a.device}, this codec runs on {self.rt.device}")
+            else:
+                a = np.asarray(a)
             if a.ndim != 2 or a.shape[1] != 3:
-                raise ValueError(f"frame {f}: expected an [n, 3] array, got shape {a.shape}")
-            if a.dtype not in (np.int16, np.int32):
+                raise ValueError(f"frame {f}: expected an [n, 3] array, got shape {tuple(a.shape)}")
+            name = str(a.dtype).replace("torch.", "")
+            if name == "float32":
+                kinds.append(True)
+            elif name in ("int16", "int32"):
+                kinds.append(False)
+            elif name == "float64":
+                raise TypeError(f"frame {f}: float64 coordinates are not narrowed silently; pass float32 (with voxel=), "
+                                "int16 or int32")
+            else:
                 raise TypeError(f"frame {f}: expected int16 or int32 coordinates, got {a.dtype}")
+            places.append(isinstance(a, torch.Tensor))
+            if kinds[-1] != kinds[0]:
+                raise ValueError(f"frame {f}: {a.dtype} beside {out[0].dtype} in frame 0: the frames of a call are all "
+                                 "integer or all float32")
+            if places[-1] != places[0]:
+                raise ValueError(f"frame {f}: on the {'device' if places[-1] else 'host'}, frame 0 on the "
+                                 f"{'device' if places[0] else 'host'}: the frames of a call are all on the host or all "
+                                 "on the device")
             out.append(a)
         if len(out) > MAX_FRAMES:
             raise ValueError(f"{len(out)} frames in one call, at most {MAX_FRAMES}")
-        return out
+        return out, bool(kinds and kinds[0]), bool(places and places[0])
+
+    @staticmethod
+    def _check_grid(voxel, origin, what):
+        """voxel and origin narrowed to float32 once: (float, (float, float, float)) as the device will use them"""
+        try:
+            with np.errstate(all="ignore"):
+                v = np.float32(voxel)
+                o = np.asarray(origin, dtype=np.float32).reshape(-1)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError(f"{what}: voxel must be a number and origin three numbers, got {voxel!r}, {origin!r}") from None
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"{what}: voxel must be a positive finite number (as float32), got {voxel!r}")
+        if o.shape != (3,) or not np.isfinite(o).all():
+            raise ValueError(f"{what}: origin must be three finite numbers (as float32), got {origin!r}")
+        return float(v), tuple(float(x) for x in o)
 
     @staticmethod
     def _check_attributes(frames, attributes):
@@ -112,7 +160,8 @@ class GeometryCodec:
         chunk's length table."""
         return Runtime.attr_lod_info(bytes(attr_blob), GeometryCodec._check_lod(lod))
 
-    def compress(self, frames, attributes=None, lod=0, scalable=False):
+    def compress(self, frames, attributes=None, lod=0, scalable=False, *, voxel=None, origin=(0.0, 0.0, 0.0),
+                 invalid="raise", return_index=False):
         """frames: a sequence of int16 / int32 [n_f, 3] arrays -> a list of bytes, one version-2 blob per frame.
         Duplicate points are removed (as np.unique), out-of-range coordinates raise PccError (PCC_E_RANGE).
         lod = k > 0: the sender's side of a level of detail — blob f is the version-2 blob of the distinct cells
@@ -122,55 +171,140 @@ class GeometryCodec:
         attribute blobs): attribute blob f holds, losslessly, one row per decoded point of frame f (Morton order), the
         rows of duplicate points merged to their rounded mean per channel.  scalable=True: attribute blobs of version 2,
         whose coarser levels of detail are prefixes (attr_lod_info, decompress(..., lod=k)); the geometry blobs are the
-        same, the default stays version 1.  With lod = k it codes the cells' means over the cells' keys."""
+        same, the default stays version 1.  With lod = k it codes the cells' means over the cells' keys.
+
+        Frame types: numpy int16 / int32 as above, numpy float32, or torch tensors of those three dtypes on the host or
+        on this codec's device; all frames of a call integer or all float32, all on the host or all on the device
+        (ValueError naming the frame otherwise; a tensor on another device: ValueError; float64: TypeError).  Device
+        frames are not staged through the host.  Attributes stay host arrays with every frame type (device-resident
+        attribute tensors are not supported).
+        voxel, origin: float32 frames are points in the caller's unit and need voxel > 0; the codec codes the lattice
+        points q = rint((x - origin) / voxel), per coordinate in float32 (include/pcc.h has the rule; voxel and origin
+        are narrowed to float32 once, and the blobs are those of compress([q])).  Neither is written into a blob.
+        Integer frames refuse voxel (ValueError).
+        invalid: "raise" — a non-finite coordinate, or a q outside [-32768, 32767], raises PccError (PCC_E_RANGE) that
+        says which; "drop" — rows with a non-finite coordinate (beams without a return) are left out before coding,
+        a frame of such rows alone gives the 24-byte empty blob; a finite coordinate off the grid still raises.  No
+        effect on integer frames.
+        return_index=True appends `index` to the result, (blobs, index) or (blobs, attr_blobs, index): index[f] is int32
+        [n_f], index[f][i] the row of decompress(blobs)[f] that input row i became (duplicates share a row; with lod = k
+        the row of the cell), -1 for a dropped row; numpy arrays for host frames, device tensors for device frames."""
         lod = self._check_lod(lod)
         version = 2 if scalable else 1
-        frames = self._check_frames(frames)
+        frames, is_float, on_device = self._check_frames(frames)
+        if invalid not in ("raise", "drop"):
+            raise ValueError(f"invalid must be 'raise' or 'drop', got {invalid!r}")
+        if is_float:
+            if voxel is None:
+                raise ValueError("float32 frames need voxel=, the edge of a lattice cell in the frames' unit")
+            voxel, origin = self._check_grid(voxel, origin, "compress")
+        elif voxel is not None:
+            raise ValueError("voxel= with integer frames: they are on the lattice already")
         attrs = None if attributes is None else self._check_attributes(frames, attributes)
         nb = len(frames)
+
+        def result(blobs, attr_blobs=None, index=None):
+            out = (blobs,) if attrs is None else (blobs, attr_blobs)
+            if return_index:
+                out += (index,)
+            return out[0] if len(out) == 1 else out
         if nb == 0:
-            return [] if attrs is None else ([], [])
-        sizes = [a.shape[0] for a in frames]
+            return result([], [], [])
+        sizes = [int(a.shape[0]) for a in frames]
         n = int(sum(sizes))
         # one upload, the rows as they come (6 or 12 B per point) behind the frame offsets; the frame index and the
-        # widening to keys happen on the device (pcc_morton_keys_frames)
-        dtype = np.int16 if all(a.dtype == np.int16 for a in frames) else np.int32
+        # widening to keys happen on the device (pcc_morton_keys_frames); device frames send the offsets alone
+        if is_float:
+            dtype = np.float32
+        else:
+            dtype = np.int16 if all(a.element_size() == 2 if on_device else a.dtype == np.int16 for a in frames) else np.int32
         offs_b = 8 * (nb + 1)
         rows_at = (offs_b + 15) // 16 * 16
-        host = torch.empty(rows_at + 3 * n * np.dtype(dtype).itemsize, dtype=torch.uint8, pin_memory=True)
+        host_rows = 0 if on_device else 3 * n * np.dtype(dtype).itemsize
+        host = torch.empty(rows_at + host_rows, dtype=torch.uint8, pin_memory=True)
         h = host.numpy()
         np.cumsum([0] + sizes, out=h[:offs_b].view(np.int64))
-        if n:
+        if n and not on_device:
             np.concatenate(frames, axis=0, out=h[rows_at:].view(dtype).reshape(n, 3))
+        if on_device:
+            caller = torch.cuda.current_stream(self.rt.device)
         with self._lock, self.rt as rt:
             if n == 0:
                 blobs = rt.octree_encode_frames(rt.empty((0,), torch.int64), nb)
-                return blobs if attrs is None else (blobs, self._encode_attributes(rt, attrs, sizes, blobs, None, None, 0, version))
+                index = [rt.empty((0,), torch.int32) if on_device else np.zeros(0, np.int32) for _ in range(nb)]
+                return result(blobs, None if attrs is None else
+                              self._encode_attributes(rt, attrs, sizes, blobs, None, None, 0, version), index)
             dev = rt.to_device(host)
-            keys = rt.empty((n,), torch.int64)
-            flag = torch.zeros(1, dtype=torch.int32, device=rt.device)
-            check(rt.lib.pcc_morton_keys_frames(rt.ctx, C.c_void_p(dev.data_ptr() + rows_at), np.dtype(dtype).itemsize, n,
-                                                C.c_void_p(dev.data_ptr()), nb, _ptr(keys), _ptr(flag)),
-                  "pcc_morton_keys_frames")
+            if on_device:      # one device-side concatenation, behind whatever the caller's stream still does to them
+                rt.stream.wait_stream(caller)
+                tdtype = {np.float32: torch.float32, np.int16: torch.int16, np.int32: torch.int32}[dtype]
+                xyz = torch.cat([a.detach().to(tdtype) for a in frames], 0).contiguous()
+                xyz_ptr = xyz.data_ptr()
+            else:
+                xyz_ptr = dev.data_ptr() + rows_at
+            n_keep = n
+            if is_float:
+                keys, status = rt.morton_keys_frames_f32(xyz_ptr, n, dev.data_ptr(), nb, voxel, origin, invalid == "drop")
+                bits, dropped = status.tolist()      # one synchronisation, in place of the flag's below
+                if bits & 2:
+                    raise PccError(PCC_E_RANGE, "GeometryCodec.compress", "non-finite coordinate (NaN or Inf) in a frame; "
+                                   "invalid='drop' leaves such rows out")
+                if bits & 1:
+                    raise PccError(PCC_E_RANGE, "GeometryCodec.compress", "coordinate outside [-32768, 32767] after "
+                                   "rint((x - origin) / voxel): a finite point off the grid")
+                n_keep = n - dropped
+            else:
+                keys = rt.empty((n,), torch.int64)
+                flag = torch.zeros(1, dtype=torch.int32, device=rt.device)
+                check(rt.lib.pcc_morton_keys_frames(rt.ctx, C.c_void_p(xyz_ptr), np.dtype(dtype).itemsize, n,
+                                                    C.c_void_p(dev.data_ptr()), nb, _ptr(keys), _ptr(flag)),
+                      "pcc_morton_keys_frames")
             perm = rt.sort_pairs(keys)
+            if n_keep < n:      # the dropped rows' keys sorted behind every frame's: nothing below sees them
+                keys = keys[:n_keep]
+            if n_keep == 0:
+                blobs = rt.octree_encode_frames(rt.empty((0,), torch.int64), nb)
+                attr_blobs = None if attrs is None else self._encode_attributes(rt, attrs, sizes, blobs, None, None, 0, version,
+                                                                                n_kept=0)
+                index = None
+                if return_index:
+                    index = self._split_index(torch.full((n,), -1, dtype=torch.int32, device=rt.device), sizes, on_device)
+                return result(blobs, attr_blobs, index)
             if lod:      # a cell's keys differ in their low 3 lod bits only (the batch index above bit 48 stays)
                 keys.bitwise_and_(-(1 << (3 * lod)))
             # duplicates (np.unique): the first row of every run of equal keys
-            rows = rt.empty((n,), torch.int32)
+            rows = rt.empty((n_keep,), torch.int32)
             n_u = C.c_int64(0)
-            check(rt.lib.pcc_unique_rows(rt.ctx, _ptr(rt.keys_to_coords(keys)), n, _ptr(rows), C.byref(n_u)),
+            check(rt.lib.pcc_unique_rows(rt.ctx, _ptr(rt.keys_to_coords(keys)), n_keep, _ptr(rows), C.byref(n_u)),
                   "pcc_unique_rows")
-            if int(flag.item()) != 0:      # read behind the synchronisation of pcc_unique_rows
+            if not is_float and int(flag.item()) != 0:      # read behind the synchronisation of pcc_unique_rows
                 raise PccError(PCC_E_RANGE, "GeometryCodec.compress", "coordinate outside [-32768, 32767]")
-            if n_u.value < n:
+            if n_u.value < n_keep:
                 keys = rt.gather_rows(keys, rows[:n_u.value])
             blobs = rt.octree_encode_frames(keys, nb, 3 * lod)
-            if attrs is None:
-                return blobs
-            return blobs, self._encode_attributes(rt, attrs, sizes, blobs, perm, rows, n_u.value, version, keys, 3 * lod)
+            attr_blobs = index = None
+            if attrs is not None:
+                attr_blobs = self._encode_attributes(rt, attrs, sizes, blobs, perm, rows, n_u.value, version, keys, 3 * lod,
+                                                     n_keep if n_keep < n else None)
+            if return_index:
+                first_run = torch.empty(nb, dtype=torch.int64, pin_memory=True)
+                np.cumsum([0] + [struct.unpack_from("<I", b, 4)[0] for b in blobs[:-1]], out=first_run.numpy())
+                index = rt.rows_index(perm, n_keep, rows, n_u.value, dev.data_ptr(), rt.to_device(first_run), nb)
+                index = self._split_index(index, sizes, on_device)
+            return result(blobs, attr_blobs, index)
+
+    def _split_index(self, index, sizes, on_device):
+        """the call's index [n] on the device -> one int32 [n_f] per frame: views of it (device frames), or of one
+        copy of it on the host"""
+        if on_device:
+            self.rt.sync()      # the caller's stream may read it at once
+        else:
+            index = index.cpu().numpy()
+        ends = np.cumsum([0] + list(sizes)).tolist()
+        return [index[a:b] for a, b in zip(ends[:-1], ends[1:])]
 
     @staticmethod
-    def _encode_attributes(rt, attrs, sizes, blobs, perm, rows, n_unique, version=1, keys=None, key_shift=0):
+    def _encode_attributes(rt, attrs, sizes, blobs, perm, rows, n_unique, version=1, keys=None, key_shift=0, n_kept=None):
         # the values as they come, frame by frame at 16-byte offsets, in one upload; the merge into Morton order
         # happens on the device from the sort's permutation and the runs of equal keys
         offs, at = [], 0
@@ -185,9 +319,10 @@ class GeometryCodec:
         formats = [a.dtype.itemsize | (a.shape[1] << 8) for a in attrs]
         points = [struct.unpack_from("<I", b, 4)[0] for b in blobs]
         row_offsets = np.cumsum([0] + list(sizes)).tolist()
-        return rt.attr_encode_frames(values, offs, formats, row_offsets, points, perm, rows, n_unique, version, keys, key_shift)
+        return rt.attr_encode_frames(values, offs, formats, row_offsets, points, perm, rows, n_unique, version, keys, key_shift,
+                                     n_kept)
 
-    def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0):
+    def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0, *, voxel=None, origin=(0.0, 0.0, 0.0)):
         """version-2 blobs -> a list of int32 [n_f, 3] point sets in Morton order: numpy arrays (output="numpy") or
         device tensors (output="device", on this codec's device).  With attr_blobs (compress(..., attributes=...)):
         (point sets, attributes), attributes[f] an [n_f, c] array in its original dtype, row i belonging to point i; an
@@ -196,12 +331,19 @@ class GeometryCodec:
         [cells, 3] in Morton order (corner of a cell c << k, centre (c << k) + ((1 << k) >> 1)); with attr_blobs of
         version 2 (compress(..., scalable=True)), or prefixes of them (attr_lod_info): attributes[f] is [cells, c], row j
         the value of the Morton-first point of cell j.  Versions may be mixed at lod 0; an attribute blob of version 1
-        at lod > 0 raises ValueError."""
+        at lod > 0 raises ValueError.
+        voxel (with origin): the point sets come back as float32 [n_f, 3] in the caller's unit instead of int32,
+        x = origin + t * voxel, one float32 multiplication and then one addition on the device (include/pcc.h has the
+        rule): t the lattice index at lod 0 and, at lod k, the centre of the cell's lattice points
+        (c << k) + (2^k - 1) / 2 — a half-integer, not the integer centre above, which stays the centre in lattice
+        units.  The blobs do not hold voxel or origin: pass what compress was given.  Attributes are unchanged."""
         if isinstance(attr_blobs, str):      # decompress(blobs, "device"), as before attributes
             attr_blobs, output = None, attr_blobs
         if output not in ("numpy", "device"):
             raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
         lod = self._check_lod(lod)
+        if voxel is not None:
+            voxel, origin = self._check_grid(voxel, origin, "decompress")
         blobs = [bytes(b) for b in blobs]
         if len(blobs) > MAX_FRAMES:
             raise ValueError(f"{len(blobs)} blobs in one call, at most {MAX_FRAMES}")
@@ -218,14 +360,18 @@ class GeometryCodec:
         with self._lock, self.rt as rt:
             # version 2 reads the cells where the geometry decode left them: on the device
             on_device = attr_blobs is not None and not all(v1)
-            frames = rt.octree_decode_frames(blobs, device=(output == "device" or on_device), lod=lod)
+            if voxel is not None:      # the points in the caller's unit, dequantised where the decode left them
+                cells, whole = rt.octree_decode_frames(blobs, device=True, lod=lod, whole=True)
+                frames = self._metric_frames(rt, cells, whole, lod, voxel, origin, output)
+            else:
+                frames = rt.octree_decode_frames(blobs, device=(output == "device" or on_device), lod=lod)
+                cells = frames
             if attr_blobs is None:
                 return frames
             if all(v1):
                 return frames, rt.attr_decode_frames(attr_blobs, points=[f.shape[0] for f in frames],
                                                      device=(output == "device"))
-            cells = frames
-            if output == "numpy":      # one copy of the call's cells to the host, split as the device tensor is
+            if output == "numpy" and voxel is None:      # one copy of the call's cells to the host, split as the device tensor is
                 host = torch.cat(cells).cpu().numpy()
                 ends = np.cumsum([0] + [c.shape[0] for c in cells])
                 frames = [host[a:b] for a, b in zip(ends[:-1], ends[1:])]
@@ -244,6 +390,21 @@ class GeometryCodec:
                 attrs[f:g] = self._named(f, call)
                 f = g
             return frames, attrs
+
+    @staticmethod
+    def _metric_frames(rt, cells, whole, lod, voxel, origin, output):
+        """the decoded int32 cells of a call (views of the device tensor `whole`) as float32 points: views of one device
+        tensor, or of one host copy of it (12 B per point, as the int32 result's)"""
+        if whole is None:
+            return []
+        pts = rt.points_to_metric(whole, lod, voxel, origin)
+        if output == "numpy":
+            host = torch.empty(pts.shape, dtype=torch.float32, pin_memory=True)
+            host.copy_(pts, non_blocking=True)
+            pts = host.numpy()
+        rt.sync()      # the host copy is complete; a device result may be read from the caller's stream at once
+        ends = np.cumsum([0] + [int(c.shape[0]) for c in cells]).tolist()
+        return [pts[a:b] for a, b in zip(ends[:-1], ends[1:])]
 
     @staticmethod
     def _named(first, call):

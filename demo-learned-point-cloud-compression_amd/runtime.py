@@ -180,6 +180,38 @@ class Runtime:
         check(self.lib.pcc_keys_to_coords(self.ctx, _ptr(keys), n, _ptr(coords)), "pcc_keys_to_coords")
         return coords
 
+    def morton_keys_frames_f32(self, xyz_ptr, n, offsets_ptr, n_frames, voxel, origin, drop=False):
+        """keys of n float32 rows at device address xyz_ptr, quantised by the metric rule of include/pcc.h
+        (pcc_morton_keys_frames_f32); offsets_ptr: the n_frames + 1 frame offsets (int64) on the device.  Returns (keys,
+        status): status an int32 [2] device tensor, [0] bit 0 = off the grid, bit 1 = non-finite, [1] = rows dropped
+        (drop=True).  Does not synchronise."""
+        keys = self.empty((n,), torch.int64)
+        status = torch.zeros(2, dtype=torch.int32, device=self.device)
+        check(self.lib.pcc_morton_keys_frames_f32(self.ctx, C.c_void_p(xyz_ptr), n, C.c_void_p(offsets_ptr), n_frames,
+                                                  float(voxel), (C.c_float * 3)(*[float(v) for v in origin]),
+                                                  1 if drop else 0, _ptr(keys), _ptr(status)), "pcc_morton_keys_frames_f32")
+        return keys, status
+
+    def rows_index(self, perm, n_keep, run_starts, n_unique, offsets_ptr, first_run, n_frames):
+        """int32 [n] device tensor: the decoded row of its frame that every input row of a compress call became, -1 for
+        a dropped row (pcc_rows_index).  perm: sort_pairs' permutation of the call's n keys; run_starts / n_unique:
+        pcc_unique_rows over the first n_keep sorted keys; offsets_ptr: the frame offsets on the device; first_run: an
+        int64 [n_frames] device tensor, the points of the frames in front of each frame."""
+        n = perm.shape[0]
+        index = self.empty((n,), torch.int32)
+        check(self.lib.pcc_rows_index(self.ctx, _ptr(perm), n, int(n_keep), _ptr(run_starts), int(n_unique),
+                                      C.c_void_p(offsets_ptr), _ptr(first_run), n_frames, _ptr(index)), "pcc_rows_index")
+        return index
+
+    def points_to_metric(self, points, lod, voxel, origin):
+        """int32 [n, 3] lattice points or cells of level of detail `lod` on the device -> float32 [n, 3], x = o + t v
+        (pcc_points_to_metric, the rule of include/pcc.h)"""
+        n = points.shape[0]
+        out = self.empty((n, 3), torch.float32)
+        check(self.lib.pcc_points_to_metric(self.ctx, _ptr(points), n, int(lod), float(voxel),
+                                            (C.c_float * 3)(*[float(v) for v in origin]), _ptr(out)), "pcc_points_to_metric")
+        return out
+
     def linear_keys(self, coords):
         n = coords.shape[0]
         keys = self.empty((n,), torch.int64)
@@ -574,13 +606,14 @@ class Runtime:
                                              C.byref(nbytes), C.byref(cells)), "pcc_octree_lod_info")
         return nbytes.value, cells.value
 
-    def octree_decode_frames(self, blobs, device=False, lod=0):
+    def octree_decode_frames(self, blobs, device=False, lod=0, whole=False):
         """version-2 blobs -> one int32 [n_f, 3] array per blob, Morton order (pcc_octree_decode_frames_lod): numpy
         arrays, or views of one device tensor (device=True).  lod = k > 0: blobs or prefixes of them (octree_lod_info)
-        -> the distinct cell indices points >> k of every frame, Morton order"""
+        -> the distinct cell indices points >> k of every frame, Morton order.  whole=True: (that list, the one array
+        or tensor [total, 3] its entries are views of)"""
         nb = len(blobs)
         if nb == 0:
-            return []
+            return ([], None) if whole else []
         lod = int(lod)
         if lod == 0:      # today's call, by its own name
             name = "pcc_octree_decode_frames"
@@ -604,17 +637,19 @@ class Runtime:
             if total:
                 check(call(None, _np_ptr(pts), total, offs),
                       name)
-        return [pts[offs[f]:offs[f + 1]] for f in range(nb)]
+        views = [pts[offs[f]:offs[f + 1]] for f in range(nb)]
+        return (views, pts) if whole else views
 
     def attr_encode_frames(self, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique,
-                           version=1, keys=None, key_shift=0):
+                           version=1, keys=None, key_shift=0, n_kept=None):
         """attribute blobs (csrc/attr.hip) of len(formats) frames at once (pcc_attr_encode_frames): `values` a
         device uint8 tensor with frame f's [rows_f, c_f] values at byte value_offsets[f], formats[f] = bytes per value |
         c_f << 8, row_offsets (n_frames + 1) the frames' rows among the call's keys, perm / run_starts what
         sort_pairs / pcc_unique_rows returned for those keys, points[f] frame f's points after the merge.  A list of
         n_frames bytes objects.  version=2 (pcc_attr_encode_frames_v2): the blobs whose coarser levels of detail are
         prefixes; `keys` the call's distinct sorted keys on the device (what octree_encode_frames took) and their
-        key_shift."""
+        key_shift.  n_kept (pcc_attr_encode_frames_kept): the call dropped rows; row_offsets still count every input row,
+        n_kept of the sorted keys belong to kept rows."""
         if version not in (1, 2):
             raise ValueError(f"attribute blob version {version!r}: 1 or 2")
         nf = len(formats)
@@ -626,7 +661,11 @@ class Runtime:
         offs = (C.c_int64 * (nf + 1))()
         head = (self.ctx, _ptr(values), (C.c_int64 * nf)(*value_offsets), (C.c_int32 * nf)(*formats),
                 (C.c_int64 * (nf + 1))(*row_offsets), (C.c_int64 * nf)(*points), nf, _ptr(perm), _ptr(run_starts), n_unique)
-        if version == 1:
+        if n_kept is not None:
+            check(self.lib.pcc_attr_encode_frames_kept(head[0], version, *head[1:], int(n_kept), _ptr(keys) if version == 2
+                                                       else None, int(key_shift), _np_ptr(out), cap, offs),
+                  "pcc_attr_encode_frames_kept")
+        elif version == 1:
             check(self.lib.pcc_attr_encode_frames(*head, _np_ptr(out), cap, offs), "pcc_attr_encode_frames")
         else:
             check(self.lib.pcc_attr_encode_frames_v2(*head, _ptr(keys), int(key_shift), _np_ptr(out), cap, offs),

@@ -122,6 +122,62 @@ int pcc_morton_keys(pcc_ctx* ctx, const int32_t* d_coords, int64_t n,
 int pcc_morton_keys_frames(pcc_ctx* ctx, const void* d_xyz, int elem_bytes,
                            int64_t n, const int64_t* d_frame_offsets,
                            int n_frames, uint64_t* d_keys, int32_t* d_flag);
+/* THE METRIC RULE of the frame codec (GeometryCodec's voxel / origin), stated
+ * here once; tests/metric_ref.py restates it in numpy.  With voxel v > 0 and
+ * origin o = (ox, oy, oz), all float32, per coordinate in float32 arithmetic:
+ *   forwards   q = rint((x - o) / v): one IEEE subtraction, one IEEE correctly
+ *     rounded division, then round-half-to-even.  Not a multiplication by a
+ *     reciprocal, nothing contracted; f32 denormals are kept.  q is tested ON
+ *     THE FLOAT, !(q >= -32768 && q <= 32767), before it becomes an integer;
+ *   backwards  x = o + t * v: one multiplication, then one addition, with
+ *     t = c for a lattice point c and, for a cell c of level of detail k,
+ *     t = (c << k) + (2^k - 1) / 2, the centre of the cell's lattice points: a
+ *     half-integer, exact in float32 for every cell of the int16 range at
+ *     every k <= 15.  (The integer centre (c << k) + ((1 << k) >> 1) of
+ *     pcc_octree_decode_frames_lod's comment stays the centre in lattice
+ *     units.)
+ * v and o are not part of any blob: the caller carries the grid.
+ *
+ *   _keys_frames_f32 : pcc_morton_keys_frames for float32 rows d_xyz [n, 3] in
+ *     the caller's unit, quantised by the rule in the same pass (12 B read,
+ *     8 B written per row).  d_status (int32[2] in device memory, zeroed by
+ *     the caller): d_status[0] |= 1 for a finite coordinate whose q is off the
+ *     grid, |= 2 for a non-finite coordinate (NaN, +-Inf); the key of such a
+ *     row is unspecified and the caller must not go on.  drop != 0: a row with
+ *     a non-finite coordinate is DROPPED instead: its key is n_frames << 48,
+ *     which sorts behind the keys of every frame (n_frames <= 65535 fits the
+ *     batch index), bit 1 stays clear and d_status[1] counts such rows; after
+ *     pcc_sort_pairs the kept rows are the first n - d_status[1] keys, and
+ *     nothing behind them may be handed to pcc_unique_rows or a coder.  A
+ *     finite coordinate off the grid is flagged under both settings.
+ *     h_origin: 3 floats on the host.  voxel not positive and finite, or a
+ *     non-finite origin: PCC_E_ARG.  No synchronisation.
+ *   pcc_rows_index : which decoded row every input row of such a call became.
+ *     d_perm = the permutation pcc_sort_pairs returned for the call's n keys,
+ *     n_keep = the kept rows (n without drops), d_run_starts / n_unique what
+ *     pcc_unique_rows returned for the first n_keep sorted keys,
+ *     d_frame_offsets the frames' input rows (n_frames+1 entries, device, as
+ *     for pcc_morton_keys_frames), d_first_run[f] (n_frames entries, device)
+ *     the first run of frame f = the points of the frames in front of it.
+ *     d_index[r] (int32 [n]) = the run of input row r counted from its frame's
+ *     first run, i.e. its row in pcc_octree_decode_frames' result for that
+ *     frame, or -1 for a dropped row.  One launch, a binary search among the
+ *     run starts per row (at most 27 steps), no synchronisation.
+ *   pcc_points_to_metric : int32 [n, 3] lattice points (lod 0) or cells of
+ *     level of detail lod (0 .. 15) in device memory -> float32 [n, 3] by the
+ *     rule backwards.  One launch, 12 B read and written per point, no
+ *     synchronisation. */
+int pcc_morton_keys_frames_f32(pcc_ctx* ctx, const float* d_xyz, int64_t n,
+                               const int64_t* d_frame_offsets, int n_frames,
+                               float voxel, const float* h_origin, int drop,
+                               uint64_t* d_keys, int32_t* d_status);
+int pcc_rows_index(pcc_ctx* ctx, const uint32_t* d_perm, int64_t n,
+                   int64_t n_keep, const uint32_t* d_run_starts,
+                   int64_t n_unique, const int64_t* d_frame_offsets,
+                   const int64_t* d_first_run, int n_frames, int32_t* d_index);
+int pcc_points_to_metric(pcc_ctx* ctx, const int32_t* d_points, int64_t n,
+                         int lod, float voxel, const float* h_origin,
+                         float* d_out);
 /* inverse: keys -> (b,x,y,z) */
 int pcc_keys_to_coords(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n,
                        int32_t* d_coords);
@@ -779,6 +835,21 @@ int pcc_attr_encode_frames_v2(pcc_ctx* ctx, const void* d_values,
                               const uint32_t* d_run_starts, int64_t n_unique,
                               const uint64_t* d_keys, int key_shift,
                               uint8_t* h_out, int64_t cap, int64_t* h_offsets);
+/* pcc_attr_encode_frames (version 1) / _v2 (version 2) for a call that dropped
+ * rows (pcc_morton_keys_frames_f32 with drop): h_rows still counts every input
+ * row, dropped ones included, since d_perm and the values do; n_kept is the
+ * number of sorted keys that belong to kept rows.  The merge closes its last
+ * run there, so no dropped row reaches a value, and a frame may have input
+ * rows and no point.  d_keys / key_shift are read by version 2 only. */
+int pcc_attr_encode_frames_kept(pcc_ctx* ctx, int version, const void* d_values,
+                                const int64_t* h_value_offsets,
+                                const int32_t* h_format, const int64_t* h_rows,
+                                const int64_t* h_points, int n_frames,
+                                const uint32_t* d_perm,
+                                const uint32_t* d_run_starts, int64_t n_unique,
+                                int64_t n_kept, const uint64_t* d_keys,
+                                int key_shift, uint8_t* h_out, int64_t cap,
+                                int64_t* h_offsets);
 int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs,
                                const int64_t* h_lens, int n_frames, int lod,
                                const int32_t* d_cells,
