@@ -26,6 +26,14 @@
 // prefix of its bytes.  The same coder over the residuals in INTRODUCTION order (k_a2_size / k_a2_scan / k_a2_place), each
 // value predicted from the Morton-first point of the next larger cell; a decoder at a level reads the level's bytes,
 // decodes its residuals and sums them along every cell's chain (k_a2_walk).  tests/attr2_ref.py restates it in numpy.
+//
+// Near-lossless, versions 4 and 7 (attr_blob.h has the rule and the layout; e = max_error, q = 2 e + 1): version 1's and
+// version 2's streams over the INDICES j of a closed prediction loop instead of wrapped residuals.  Encoder: one pass in
+// front of the counting pass runs the loop over the merged values and leaves the j where the PRED = false coder reads
+// its residuals — k_a4_quant per (lane run, channel), k_a7_quant per point along its chain of first() — and k_a_stats /
+// k_a_enc<false> code them as they code version 2's.  Decoder: k_a_dec<AD2Frame> returns the j, then k_a4_recon redoes
+// the loop of every run, or k_a7_walk sums the chain, scales by q and clamps.  The kernels of versions 1 and 2 are the
+// instantiations they were.  tests/attr_nl_ref.py restates both kinds in numpy.
 #include "common.h"
 #include "lanerans.h"
 #include "attr_blob.h"
@@ -81,7 +89,15 @@ struct AFrame {
   int64_t out_off, out_cap;  // its blob in the output staging: offset, bound
   int32_t S, nc, cb, sb, sn, mb;   // chunks: S, count, first (of the call); stats blocks: first, count; merge blocks
   int32_t c, bpv, nctx, ctx_off, T;   // T: records (and words) a lane may leave, S c 16 bpv
+  int32_t e;                          // max_error of versions 4 and 7 (in what was padding: no other field moves)
 };
+static_assert(sizeof(AFrame) == 120, "AFrame: the rows of versions 1 and 2 keep their size");
+
+// index of the quantised prediction error d = v - p: sgn(d) floor((|d| + e) / q), q = 2 e + 1
+__device__ __forceinline__ int a_quant(int d, int e, int q) {
+  const int m = (int)((uint32_t)((d < 0 ? -d : d) + e) / (uint32_t)q);
+  return d < 0 ? -m : m;
+}
 
 // merged value of every point: the rounded mean (sum + cnt / 2) / cnt of the run of equal keys behind it (order-free).
 // Frame f owns blocks [mb, mb + ceil(n / 256)); perm[t] is the input row of sorted key t, runs[u] the first sorted key
@@ -108,6 +124,42 @@ __global__ __launch_bounds__(256) void k_a_merge(const uint8_t* __restrict__ in,
   }
   if (cnt == 0) cnt = 1;
   for (int ch = 0; ch < c; ++ch) merged[h.val_off + i * c + ch] = (uint16_t)((sum[ch] + (uint64_t)(cnt / 2)) / (uint64_t)cnt);
+}
+
+// Version 4: the closed loop of every (lane run, channel) over the frame's merged values, frame = blockIdx.y.  The
+// predictor is built from the reconstructions v^ = p + j q (unclamped), as the decoder will build it; index j of point
+// i, channel ch goes to idx[val_off + i c + ch] wrapped to the value width, where the PRED = false coder reads it.
+// One thread per (run, channel), channel fastest: the chain is a few integer operations per value and the loads do not
+// depend on it, so they are issued eight values ahead; the threads of a run's channels share their cache lines.
+__global__ __launch_bounds__(256) void k_a4_quant(const uint16_t* __restrict__ merged, const AFrame* __restrict__ tab,
+                                                  uint16_t* __restrict__ idx) {
+  const AFrame& h = tab[blockIdx.y];
+  const int c = h.c, e = h.e, q = 2 * e + 1;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t base = t / c * h.S;
+  const int ch = (int)(t % c);
+  if (base >= h.n) return;
+  const int npts = (int)std::min<int64_t>(h.S, h.n - base);
+  const uint32_t mask = (1u << (8 * h.bpv)) - 1u;
+  const uint16_t* v = merged + h.val_off + base * c + ch;
+  uint16_t* o = idx + h.val_off + base * c + ch;
+  int a = 0, b = 0;   // v^[s - 1], v^[s - 2]
+  for (int s0 = 0; s0 < npts; s0 += 8) {
+    int x[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x[k] = s0 + k < npts ? (int)v[(int64_t)(s0 + k) * c] : 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int s = s0 + k;
+      if (s < npts) {
+        const int p = s == 0 ? 0 : (s == 1 ? a : (a + b + 1) >> 1);
+        const int j = a_quant(x[k] - p, e, q);
+        b = a;
+        a = p + j * q;
+        o[(int64_t)s * c] = (uint16_t)((uint32_t)j & mask);
+      }
+    }
+  }
 }
 
 // zeros and ones seen per context over the whole frame: cnt[2 (ctx_off + ctx) + bit]; frame f takes blocks [sb, sb + sn)
@@ -236,8 +288,9 @@ __global__ __launch_bounds__(64) void k_a_enc(const uint16_t* __restrict__ merge
 // the blobs, assembled where `out_all` points (pinned host memory), frame f's at out_off: frame f owns workgroups
 // [cb + f, cb + f + nc + 1) — workgroup k < nc of them moves chunk k, workgroup nc writes the header; len_out[f] =
 // bytes, or -1 (out_cap).  V2: the head of attribute blob version 2, with the frame's 16 values-per-level counts
-// (cells_all[16 f + k], attr_blob.h) and the sender's level of detail
-template <bool V2>
+// (cells_all[16 f + k], attr_blob.h) and the sender's level of detail.  NL: the heads of versions 4 / 7, the frame's
+// max_error behind payload_len and everything else one word later
+template <bool V2, bool NL = false>
 __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ work_all, const AFrame* __restrict__ tab, int nf,
                                                 const uint16_t* __restrict__ states_all, const uint16_t* __restrict__ lens_all,
                                                 const uint32_t* __restrict__ words_all, const uint16_t* __restrict__ p0_all,
@@ -260,7 +313,8 @@ __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ wor
     __syncthreads();
   }
   const unsigned long long before = s_sum[0];
-  const unsigned long long head = (unsigned long long)(V2 ? kAttr2Head : kAttrHead + 8) + 2ull * h.nctx + 4ull * nc;
+  constexpr int X = NL ? 1 : 0;
+  const unsigned long long head = (unsigned long long)((V2 ? kAttr2Head : kAttrHead + 8) + 4 * X) + 2ull * h.nctx + 4ull * nc;
   if (k == nc) {
     const unsigned long long total = head + before * 2;
     const bool fits = (long long)total <= cap;
@@ -271,16 +325,17 @@ __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ wor
     if (!fits) return;
     uint32_t* o32 = reinterpret_cast<uint32_t*>(out);
     if (threadIdx.x == 0) {
-      o32[0] = (uint32_t)'A' | ((V2 ? 2u : 1u) << 8) | ((uint32_t)(h.bpv | (V2 ? slod << 4 : 0)) << 16) | ((uint32_t)h.c << 24);
+      o32[0] = (uint32_t)'A' | ((NL ? (V2 ? 7u : 4u) : (V2 ? 2u : 1u)) << 8) | ((uint32_t)(h.bpv | (V2 ? slod << 4 : 0)) << 16) | ((uint32_t)h.c << 24);
       o32[1] = (uint32_t)h.n;
       o32[2] = (uint32_t)(total - kAttrHead);
-      o32[V2 ? 19 : 3] = (uint32_t)h.S;
-      o32[V2 ? 20 : 4] = (uint32_t)h.nc;
+      if constexpr (NL) o32[3] = (uint32_t)h.e;
+      o32[(V2 ? 19 : 3) + X] = (uint32_t)h.S;
+      o32[(V2 ? 20 : 4) + X] = (uint32_t)h.nc;
     }
     if constexpr (V2) {
-      if (threadIdx.x < 16) o32[3 + threadIdx.x] = cells_all[16 * f + threadIdx.x];
+      if (threadIdx.x < 16) o32[3 + X + threadIdx.x] = cells_all[16 * f + threadIdx.x];
     }
-    uint16_t* o16 = reinterpret_cast<uint16_t*>(o32 + (V2 ? 21 : 5));
+    uint16_t* o16 = reinterpret_cast<uint16_t*>(o32 + (V2 ? 21 : 5) + X);
     for (int i = threadIdx.x; i < h.nctx; i += blockDim.x) o16[i] = p0_all[h.ctx_off + i];
     uint32_t* wt = reinterpret_cast<uint32_t*>(o16 + h.nctx);
     for (int64_t j = threadIdx.x; j < nc; j += blockDim.x) wt[j] = words[j];
@@ -304,10 +359,11 @@ struct ADFrame {
   static constexpr bool kV2 = false;
 };
 // version 2 at a level of detail: n stays the whole blob's values, nc counts the chunks the level needs, n_dec its values
-// (the first n_dec of the introduction sequence), last_words the words of chunk nc - 1 that were uploaded
+// (the first n_dec of the introduction sequence), last_words the words of chunk nc - 1 that were uploaded.  Versions 4
+// and 7 decode their indices through the same rows (version 4: n_dec = n, every chunk whole): max_error is their e
 struct AD2Frame : ADFrame {
   int64_t n_dec;
-  int32_t last_words, pad;
+  int32_t last_words, max_error;
   static constexpr bool kV2 = true;
 };
 
@@ -465,6 +521,42 @@ __global__ __launch_bounds__(64) void k_a_dec(const uint8_t* __restrict__ bodies
   if (lane == 0 && (b1 | b4) != 0ull) atomicOr(status_all + f, (b1 ? 1 : 0) | (b4 ? 4 : 0));
 }
 
+// Version 4, behind k_a_dec<AD2Frame>: the decoder's side of k_a4_quant's loop, frame = blockIdx.y, one thread per (lane
+// run, channel).  idx_all / out_all: the frames' [n][c] values of bpv bytes at out_off, the indices j as the coder
+// wrapped them / the values clamped to the value width.  An encoder's reconstruction never leaves [-e, mask + e]:
+// status |= 16 where one does (and the loop goes on from the nearest value inside).
+__global__ __launch_bounds__(256) void k_a4_recon(const AD2Frame* __restrict__ tab, const uint8_t* __restrict__ idx_all,
+                                                  uint8_t* __restrict__ out_all, int32_t* __restrict__ status_all) {
+  const AD2Frame& h = tab[blockIdx.y];
+  const int c = h.c, bpv = h.bpv, e = h.max_error, q = 2 * e + 1;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t base = t / c * h.S;
+  const int ch = (int)(t % c);
+  if (base >= h.n) return;
+  const int npts = (int)std::min<int64_t>(h.S, h.n - base);
+  const int mask = (1 << (8 * bpv)) - 1;
+  const uint8_t* r = idx_all + h.out_off + (base * c + ch) * bpv;
+  uint8_t* o = out_all + h.out_off + (base * c + ch) * bpv;
+  int a = 0, b = 0;   // v^[s - 1], v^[s - 2]
+  bool bad = false;
+  for (int s = 0; s < npts; ++s) {
+    const int64_t at = (int64_t)s * c * bpv;
+    const int j = bpv == 1 ? (int)(int8_t)r[at] : (int)(int16_t)((uint32_t)r[at] | ((uint32_t)r[at + 1] << 8));
+    const int p = s == 0 ? 0 : (s == 1 ? a : (a + b + 1) >> 1);
+    int64_t x = (int64_t)p + (int64_t)j * q;
+    if (x < -e || x > mask + e) {
+      bad = true;
+      x = x < -e ? -e : mask + e;
+    }
+    b = a;
+    a = (int)x;
+    const int val = a < 0 ? 0 : (a > mask ? mask : a);
+    o[at] = (uint8_t)val;
+    if (bpv == 2) o[at + 1] = (uint8_t)(val >> 8);
+  }
+  if (bad) atomicOr(status_all + blockIdx.y, 16);
+}
+
 // ---- version 2: the introduction order ----------------------------------------------------------------------------
 // (attr_blob.h states the rule.)  One row per frame (>= 1 point) of a call, for the encoder over the call's distinct
 // sorted keys and for the decoder over the cells its geometry decode left in HBM: frame f's points are [pt0, pt0 + n)
@@ -596,8 +688,9 @@ __device__ __forceinline__ int64_t a2_first(const uint64_t* __restrict__ keys, i
 
 // the place of every point in the introduction order and its predictor.  ENC: the residual of its merged value against
 // the predictor's goes to that place of resid ([n][c] per frame at val_off, wrapped to the value width); otherwise
-// (decoder) place and predictor are kept: rank[pt0 + i], first[pt0 + i]
-template <bool ENC>
+// (decoder; KEEP) place and predictor are kept: rank[pt0 + i], first[pt0 + i].  ENC and KEEP: the encoder of version 7,
+// whose k_a7_quant follows the kept predictors instead of searching again
+template <bool ENC, bool KEEP = !ENC>
 __global__ __launch_bounds__(256) void k_a2_place(const uint64_t* __restrict__ keys_all, const A2Order* __restrict__ tab, int nf,
                                                   const uint16_t* __restrict__ packed, const uint32_t* __restrict__ hist,
                                                   const uint32_t* __restrict__ bins, const AFrame* __restrict__ ftab,
@@ -611,7 +704,7 @@ __global__ __launch_bounds__(256) void k_a2_place(const uint64_t* __restrict__ k
   const int s = (int)(pk >> 8);
   const int64_t r = (int64_t)bins[f * kA2Bins + s] + hist[(int64_t)blockIdx.x * kA2Bins + s] + (pk & 255u);
   const int64_t j = i > 0 ? a2_first(keys_all + h.pt0, i, 3 * (s + 1) + (ENC ? h.shift : 0)) : 0;
-  if constexpr (ENC) {
+  if constexpr (ENC && !KEEP) {
     const AFrame& a = ftab[f];
     const uint32_t mask = (1u << (8 * a.bpv)) - 1u;
     if (r >= h.n) return;   // cannot happen: the places are a permutation of the frame's points
@@ -622,6 +715,49 @@ __global__ __launch_bounds__(256) void k_a2_place(const uint64_t* __restrict__ k
   } else {
     rank[h.pt0 + i] = (uint32_t)r;
     first[h.pt0 + i] = (uint32_t)j;
+  }
+}
+
+// Version 7, encoder, behind k_a2_place<true, true>: point i follows first() up to point 0 (at most 17 links, each to a
+// strictly larger size of introduction, so strictly downwards in Morton index), then walks back down quantising every
+// member of the chain against the running reconstruction v^ (what that member's own thread computes too: its chain is
+// the tail of this one), and writes its own index j to its place rank[i] of idx, wrapped to the value width.  No thread
+// waits for another; the chain's 17 indices stay in registers (every loop is unrolled to constant subscripts).
+__global__ __launch_bounds__(256) void k_a7_quant(const A2Order* __restrict__ tab, int nf, const AFrame* __restrict__ ftab,
+                                                  const uint16_t* __restrict__ merged, const uint32_t* __restrict__ rank,
+                                                  const uint32_t* __restrict__ first, uint16_t* __restrict__ idx) {
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].blk0; });
+  const A2Order& h = tab[f];
+  const AFrame& a = ftab[f];
+  const int64_t i = ((int64_t)blockIdx.x - h.blk0) * blockDim.x + threadIdx.x;
+  if (i >= h.n) return;
+  const int64_t r = rank[h.pt0 + i];
+  if (r >= h.n) return;   // cannot happen: the places are a permutation of the frame's points
+  uint32_t chain[kA2Bins];
+  int len = 0;
+  int64_t j = i;
+#pragma unroll
+  for (int step = 0; step < kA2Bins; ++step) {
+    if (j >= 0) {
+      chain[step] = (uint32_t)j;
+      len = step + 1;
+      const int64_t nj = j > 0 ? (int64_t)first[h.pt0 + j] : -1;
+      j = nj < j ? nj : -1;   // first(j) < j for every j > 0
+    }
+  }
+  const int c = a.c, e = a.e, q = 2 * e + 1;
+  const uint32_t mask = (1u << (8 * a.bpv)) - 1u;
+  const uint16_t* v = merged + a.val_off;
+  for (int ch = 0; ch < c; ++ch) {
+    int vh = 0, jj = 0;
+#pragma unroll
+    for (int step = kA2Bins - 1; step >= 0; --step) {
+      if (step < len) {
+        jj = a_quant((int)v[(int64_t)chain[step] * c + ch] - vh, e, q);
+        vh += jj * q;
+      }
+    }
+    idx[a.val_off + r * c + ch] = (uint16_t)((uint32_t)jj & mask);
   }
 }
 
@@ -664,6 +800,50 @@ __global__ __launch_bounds__(256) void k_a2_walk(const A2Order* __restrict__ tab
   }
 }
 
+// Version 7's k_a2_walk (a kernel of its own, so that version 2's stays the code it was): the same walk with the same
+// index checks over the indices j, sign-extended from the value width; the value is their sum times q = 2 e + 1, clamped
+// to the value width.  status |= 16 where the sum of a complete walk lies outside [-e, mask + e], which no encoder's
+// reconstruction does.
+__global__ __launch_bounds__(256) void k_a7_walk(const A2Order* __restrict__ tab, int nf, const AD2Frame* __restrict__ ftab,
+                                                 const uint32_t* __restrict__ rank, const uint32_t* __restrict__ first,
+                                                 const uint8_t* __restrict__ idx_all, uint8_t* __restrict__ out_all,
+                                                 int32_t* __restrict__ status_all) {
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].blk0; });
+  const A2Order& h = tab[f];
+  const AD2Frame& a = ftab[f];
+  const int64_t i = ((int64_t)blockIdx.x - h.blk0) * blockDim.x + threadIdx.x;
+  if (i >= h.n) return;
+  const int c = a.c, bpv = a.bpv, e = a.max_error, mask = (1 << (8 * bpv)) - 1;
+  const uint8_t* idx = idx_all + a.out_off;
+  uint32_t acc[4] = {0u, 0u, 0u, 0u};   // sums of int32 in two's complement
+  int64_t j = i;
+  bool ok = false;
+  for (int step = 0; step < kA2Bins; ++step) {
+    const int64_t r = rank[h.pt0 + j];
+    if (r >= h.n) break;
+    const uint8_t* q = idx + r * c * bpv;
+    for (int ch = 0; ch < c; ++ch)
+      acc[ch] += bpv == 1 ? (uint32_t)(int32_t)(int8_t)q[ch] : (uint32_t)(int32_t)(int16_t)((uint32_t)q[2 * ch] | ((uint32_t)q[2 * ch + 1] << 8));
+    if (j == 0) {
+      ok = true;
+      break;
+    }
+    const int64_t nj = first[h.pt0 + j];
+    if (nj >= j) break;
+    j = nj;
+  }
+  bool far = false;
+  uint8_t* o = out_all + a.out_off + i * c * bpv;
+  for (int ch = 0; ch < c; ++ch) {
+    const int64_t x = (int64_t)(int32_t)acc[ch] * (2 * e + 1);
+    far |= x < -e || x > mask + e;
+    const uint32_t val = (uint32_t)(x < 0 ? 0 : (x > mask ? mask : x));
+    o[bpv * ch] = (uint8_t)val;
+    if (bpv == 2) o[2 * ch + 1] = (uint8_t)(val >> 8);
+  }
+  if (!ok || far) atomicOr(status_all + f, (ok ? 0 : 8) | (ok && far ? 16 : 0));
+}
+
 }  // namespace
 
 static inline int64_t a_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
@@ -671,12 +851,15 @@ static inline size_t merged_b_of(int64_t vals) { return pcc_align((size_t)vals *
 
 // ======================================================================== C-ABI (include/pcc.h)
 // both versions' encoder: version 2 codes, instead of the merged values, their residuals in introduction order
-// (k_a2_size / k_a2_scan / k_a2_place over d_keys, the call's distinct sorted keys)
+// (k_a2_size / k_a2_scan / k_a2_place over d_keys, the call's distinct sorted keys).  max_error > 0: the near-lossless
+// kind of that version (4 for 1, 7 for 2), the indices of k_a4_quant / k_a7_quant through the PRED = false coder
 static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
                            const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
                            const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys,
-                           int key_shift, uint8_t* h_out, int64_t cap, int64_t* h_offsets, int64_t n_kept = -1) {
-  const bool v2 = version == 2;
+                           int key_shift, uint8_t* h_out, int64_t cap, int64_t* h_offsets, int64_t n_kept = -1,
+                           int max_error = 0) {
+  const bool v2 = version == 2, nl = max_error > 0;
+  const int blob_version = nl ? (v2 ? 7 : 4) : version;
   PCC_REQUIRE(ctx && h_value_offsets && h_format && h_rows && h_points && h_out && h_offsets && n_frames >= 1 &&
                   n_frames <= 65535 && n_unique >= 0 && cap >= 0,
               PCC_E_ARG, "%s: bad argument (n_frames=%d)", who, n_frames);
@@ -693,6 +876,7 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
   std::vector<AFrame> tab;
   std::vector<A2Order> order;
   std::vector<int> frame_of;
+  int64_t run_threads = 0;   // k_a4_quant: the most (run, channel) pairs of a frame
   int64_t u = 0, vals = 0, rec_words = 0, out_bytes = 0, chunks = 0, stats_blocks = 0, merge_blocks = 0, ctxs = 0, nctx_max = 0;
   for (int f = 0; f < n_frames; ++f) {
     const int bpv = h_format[f] & 0xFF, c = h_format[f] >> 8;
@@ -702,10 +886,13 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     PCC_REQUIRE(rows >= 0 && n >= 0 && n <= rows && ((n == 0) == (rows == 0) || (drops && n == 0)) &&
                     h_value_offsets[f] >= 0, PCC_E_ARG,
                 "%s: frame %d: %lld rows, %lld points", who, f, (long long)rows, (long long)n);
+    PCC_REQUIRE(!nl || (uint32_t)max_error <= attr_max_error(bpv), PCC_E_ARG,
+                "%s: frame %d: max_error %d with %d bytes per value (at most %u)", who, f, max_error, bpv, attr_max_error(bpv));
     if (n == 0) continue;
     AFrame r;
     int64_t S, nc;
     attr_layout(n, c, &S, &nc);
+    r.e = max_error;
     r.in_off = h_value_offsets[f];
     r.row0 = h_rows[f];
     r.rows = rows;
@@ -718,7 +905,7 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     r.nctx = attr_contexts(bpv, c);
     r.ctx_off = (int32_t)ctxs;
     r.T = (int32_t)(S * c * attr_positions(bpv));
-    const int64_t head = (v2 ? kAttr2Head : kAttrHead + 8) + 2 * r.nctx + 4 * nc;
+    const int64_t head = (v2 ? kAttr2Head : kAttrHead + 8) + (nl ? 4 : 0) + 2 * r.nctx + 4 * nc;
     // a coded decision emits at most one word: the bound follows the frame's decisions, not its chunks' regions
     r.out_cap = head + 2 * (3 * kLanes * nc + std::min<int64_t>(nc * kLanes * r.T, (int64_t)attr_positions(bpv) * c * n));
     r.out_off = out_bytes;
@@ -731,6 +918,7 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     tab.push_back(r);
     order.push_back(A2Order{u, n, r.mb, key_shift});
     frame_of.push_back(f);
+    run_threads = std::max<int64_t>(run_threads, nc * kLanes * c);
     u += n;
     vals += n * c;
     rec_words += nc * kLanes * r.T;
@@ -753,9 +941,10 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     const size_t v2_b = v2 ? 2 * merged_b_of(vals) + pcc_align((size_t)u * 2) + pcc_align((size_t)merge_blocks * 17 * 4) +
                                  pcc_align((size_t)nf * 33 * 4)
                            : 0;
+    const size_t nl_b = nl ? merged_b_of(vals) + 2 * pcc_align((size_t)u * 4) : 0;   // the indices; rank and first (version 7)
     const size_t merged_b = pcc_align((size_t)vals * 2), cnt_b = pcc_align((size_t)ctxs * 8), p0_b = pcc_align((size_t)ctxs * 2);
     const size_t rec_b = pcc_align((size_t)rec_words * 2), small_b = pcc_align((size_t)chunks * (4 + 2 * kLanes * 2 + kLanes * 2));
-    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + v2_b + 8192));
+    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + v2_b + nl_b + 8192));
     AFrame* d_tab = (AFrame*)pcc_arena_alloc(ctx, tab_b);
     uint16_t* merged = (uint16_t*)pcc_arena_alloc(ctx, merged_b);
     uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, cnt_b);
@@ -782,7 +971,52 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
                        d_perm, d_run_starts, n_unique, n_keys, merged);
     PCC_CHECK_LAUNCH();
     const size_t lds = 4096 * 4 + (size_t)(nctx_max + 1) * kLanes * 2;   // <= 98 KB (c = 4, uint16)
-    if (!v2) {
+    if (nl) {
+      const A2Order* d_ord = (const A2Order*)((const uint8_t*)d_tab + tab_b - ord_b);
+      uint16_t* idx = (uint16_t*)pcc_arena_alloc(ctx, merged_b_of(vals));
+      if (!idx) return PCC_E_NOMEM;
+      uint32_t* cells = nullptr;
+      if (!v2) {
+        hipLaunchKernelGGL(k_a4_quant, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const uint16_t*)merged,
+                           (const AFrame*)d_tab, idx);
+        PCC_CHECK_LAUNCH();
+      } else {
+        uint32_t* rank = (uint32_t*)pcc_arena_alloc(ctx, (size_t)u * 4);
+        uint32_t* first = (uint32_t*)pcc_arena_alloc(ctx, (size_t)u * 4);
+        uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, (size_t)u * 2);
+        uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, (size_t)merge_blocks * 17 * 4);
+        uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nf * 33 * 4);   // 17 bin bases, then 16 counts per frame
+        if (!rank || !first || !packed || !hist || !bins) return PCC_E_NOMEM;
+        cells = bins + (size_t)nf * 17;
+        hipLaunchKernelGGL(k_a2_size<false>, dim3((unsigned)merge_blocks), dim3(256), 0, st, (const void*)d_keys, d_ord, nf,
+                           (uint64_t*)nullptr, packed, hist);
+        PCC_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_a2_scan, dim3((unsigned)nf), dim3(256), 0, st, d_ord, hist, bins, cells);
+        PCC_CHECK_LAUNCH();
+        hipLaunchKernelGGL((k_a2_place<true, true>), dim3((unsigned)merge_blocks), dim3(256), 0, st, d_keys, d_ord, nf,
+                           (const uint16_t*)packed, (const uint32_t*)hist, (const uint32_t*)bins, (const AFrame*)d_tab,
+                           (const uint16_t*)merged, (uint16_t*)nullptr, rank, first);
+        PCC_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_a7_quant, dim3((unsigned)merge_blocks), dim3(256), 0, st, d_ord, nf, (const AFrame*)d_tab,
+                           (const uint16_t*)merged, (const uint32_t*)rank, (const uint32_t*)first, idx);
+        PCC_CHECK_LAUNCH();
+      }
+      hipLaunchKernelGGL(k_a_stats<false>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)idx, (const AFrame*)d_tab, nf, cnt);
+      PCC_CHECK_LAUNCH();
+      PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(k_a_enc<false>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)idx, (const AFrame*)d_tab, nf,
+                         (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
+      PCC_CHECK_LAUNCH();
+      if (!v2)
+        hipLaunchKernelGGL((k_a_pack<false, true>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work,
+                           (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words,
+                           (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)nullptr, 0);
+      else
+        hipLaunchKernelGGL((k_a_pack<true, true>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work,
+                           (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words,
+                           (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3);
+      PCC_CHECK_LAUNCH();
+    } else if (!v2) {
       hipLaunchKernelGGL(k_a_stats<true>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)merged, (const AFrame*)d_tab, nf, cnt);
       PCC_CHECK_LAUNCH();
       PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -842,7 +1076,7 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     } else {   // no points: the 12-byte empty blob
       memset(dst, 0, kAttrHead);
       dst[0] = 'A';
-      dst[1] = (uint8_t)version;
+      dst[1] = (uint8_t)blob_version;
       dst[2] = (uint8_t)((h_format[f] & 0xFF) | (v2 ? (key_shift / 3) << 4 : 0));
       dst[3] = (uint8_t)(h_format[f] >> 8);
     }
@@ -879,17 +1113,62 @@ extern "C" int pcc_attr_encode_frames_kept(pcc_ctx* ctx, int version, const void
                          h_out, cap, h_offsets, n_kept);
 }
 
+extern "C" int pcc_attr_encode_frames_nl(pcc_ctx* ctx, int version, const void* d_values, const int64_t* h_value_offsets,
+                                         const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
+                                         const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, int64_t n_kept,
+                                         const uint64_t* d_keys, int key_shift, int max_error, uint8_t* h_out, int64_t cap,
+                                         int64_t* h_offsets) {
+  PCC_REQUIRE((version == 1 || version == 2) && n_kept >= -1 && max_error >= 0, PCC_E_ARG,
+              "pcc_attr_encode_frames_nl: bad argument (version=%d n_kept=%lld max_error=%d)", version, (long long)n_kept, max_error);
+  return a_encode_frames("pcc_attr_encode_frames_nl", version, ctx, d_values, h_value_offsets, h_format, h_rows, h_points,
+                         n_frames, d_perm, d_run_starts, n_unique, version == 2 ? d_keys : nullptr, version == 2 ? key_shift : 0,
+                         h_out, cap, h_offsets, n_kept, max_error);
+}
+
+// host only: what the head of an attribute blob of any kind says (h_in may be a prefix that holds the head)
+extern "C" int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_version, int32_t* h_bpv, int32_t* h_channels,
+                             int64_t* h_points, int32_t* h_max_error, int32_t* h_scalable, int32_t* h_lod) {
+  PCC_REQUIRE(h_in && len >= kAttrHead && h_in[0] == 'A', PCC_E_STREAM, "pcc_attr_info: not an attribute blob (len=%lld)", (long long)len);
+  const int ver = h_in[1];
+  PCC_REQUIRE(ver == 1 || ver == 2 || ver == 4 || ver == 7, PCC_E_STREAM, "pcc_attr_info: attribute blob version %d", ver);
+  const bool scal = ver == 2 || ver == 7, nl = ver == 4 || ver == 7;
+  const int bpv = scal ? h_in[2] & 15 : h_in[2], slod = scal ? h_in[2] >> 4 : 0, c = h_in[3];
+  PCC_REQUIRE((bpv == 1 || bpv == 2) && c >= 1 && c <= 4, PCC_E_STREAM, "pcc_attr_info: %d bytes per value, %d channels", bpv, c);
+  const int64_t n = (int64_t)attr_u32(h_in + 4);
+  PCC_REQUIRE(n < ((int64_t)1 << 27), PCC_E_STREAM, "pcc_attr_info: %lld points", (long long)n);
+  uint32_t e = 0;
+  if (nl && n > 0) {
+    PCC_REQUIRE(len >= kAttrHead + 4, PCC_E_STREAM, "pcc_attr_info: truncated in front of max_error (len=%lld)", (long long)len);
+    e = attr_u32(h_in + kAttrHead);
+    PCC_REQUIRE(e >= 1 && e <= attr_max_error(bpv), PCC_E_STREAM, "pcc_attr_info: max_error %u with %d bytes per value", e, bpv);
+  }
+  if (h_version) *h_version = ver;
+  if (h_bpv) *h_bpv = bpv;
+  if (h_channels) *h_channels = c;
+  if (h_points) *h_points = n;
+  if (h_max_error) *h_max_error = (int32_t)e;
+  if (h_scalable) *h_scalable = scal ? 1 : 0;
+  if (h_lod) *h_lod = slod;
+  return PCC_OK;
+}
+
 extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
                                       const int64_t* h_points, uint8_t* d_out, uint8_t* h_out, int64_t cap_bytes,
                                       int64_t* h_out_offsets, int32_t* h_format) {
   PCC_REQUIRE(ctx && h_blobs && h_lens && h_out_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
               "pcc_attr_decode_frames: bad argument (n_frames=%d)", n_frames);
+  // the blobs of a call are of one version, the first blob's: 1, or 4 (its indices through the rows and the decoder of
+  // version 2 at lod 0, then k_a4_recon)
+  const bool nl = h_blobs[0] && h_lens[0] >= 2 && h_blobs[0][0] == 'A' && h_blobs[0][1] == 4;
   std::vector<AttrInfo> info((size_t)n_frames);
   int64_t bytes = 0, bodies = 0, points = 0;
   h_out_offsets[0] = 0;
   for (int f = 0; f < n_frames; ++f) {
     AttrInfo& o = info[(size_t)f];
-    const int rc = attr_parse(h_blobs[f], h_lens[f], &o);
+    PCC_REQUIRE(!(h_blobs[f] && h_lens[f] >= 2 && h_blobs[f][0] == 'A' && h_blobs[f][1] == (nl ? 1 : 4)), PCC_E_ARG,
+                "pcc_attr_decode_frames: frame %d: attribute blob version %d in a call of version %d blobs (one version per call)", f,
+                nl ? 1 : 4, nl ? 4 : 1);
+    const int rc = attr_parse_kind(h_blobs[f], h_lens[f], nl, &o);
     if (rc != PCC_OK) {
       const std::string m = pcc_last_error();
       pcc_set_error("pcc_attr_decode_frames: frame %d: %s", f, m.c_str());
@@ -910,11 +1189,12 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
   PCC_REQUIRE(cap_bytes >= bytes, PCC_E_NOMEM, "pcc_attr_decode_frames: %lld bytes, capacity %lld", (long long)bytes,
               (long long)cap_bytes);
   std::vector<ADFrame> tab;
-  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0;
+  std::vector<AD2Frame> tab4;
+  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, run_threads = 0;
   for (int f = 0; f < n_frames; ++f) {
     const AttrInfo& o = info[(size_t)f];
     if (o.n == 0) continue;
-    ADFrame r;
+    AD2Frame r;
     r.body_off = body_off;
     r.table_off = o.off_table - o.off_p0;
     r.payload_off = o.off_payload - o.off_p0;
@@ -926,21 +1206,29 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
     r.c = o.c;
     r.bpv = o.bpv;
     r.nctx = o.nctx;
-    tab.push_back(r);
+    r.n_dec = o.n;
+    r.last_words = (int32_t)attr_u32(h_blobs[f] + o.off_table + 4 * (o.nc - 1));
+    r.max_error = (int32_t)o.max_error;
+    if (nl) tab4.push_back(r); else tab.push_back(r);
+    run_threads = std::max<int64_t>(run_threads, o.nc * kLanes * o.c);
     for (int64_t k = 0; k < o.nc; ++k) cw_max = std::max<int64_t>(cw_max, attr_u32(h_blobs[f] + o.off_table + 4 * k));
     body_off += a_round(h_lens[f] - o.off_p0, 16);
     chunks += o.nc;
     nctx_max = std::max<int64_t>(nctx_max, o.nctx);
   }
-  const int nf = (int)tab.size();
+  const int nf = (int)(nl ? tab4.size() : tab.size());
+  const size_t row_b = nl ? sizeof(AD2Frame) : sizeof(ADFrame);
+  const void* rows = nl ? (const void*)tab4.data() : (const void*)tab.data();
+  auto body_of = [&](int k) { return nl ? tab4[(size_t)k].body_off : tab[(size_t)k].body_off; };
   hipStream_t st = ctx->stream;
-  const size_t tab_b = pcc_align((size_t)nf * sizeof(ADFrame));
-  PCC_TRY(pcc_arena_reserve(ctx, tab_b + pcc_align((size_t)bodies + 16) + (d_out ? 0 : pcc_align((size_t)bytes)) +
+  const size_t tab_b = pcc_align((size_t)nf * row_b);
+  PCC_TRY(pcc_arena_reserve(ctx, tab_b + pcc_align((size_t)bodies + 16) + ((d_out ? 0 : 1) + (nl ? 1 : 0)) * pcc_align((size_t)bytes) +
                                      pcc_align((size_t)nf * 4 + 64) + 4096));
   uint8_t* d_in = (uint8_t*)pcc_arena_alloc(ctx, tab_b + (size_t)bodies + 16);
   uint8_t* out = d_out ? d_out : (uint8_t*)pcc_arena_alloc(ctx, (size_t)bytes);
+  uint8_t* idx = nl ? (uint8_t*)pcc_arena_alloc(ctx, (size_t)bytes) : out;   // version 4: the indices, as version 2's residuals
   int32_t* status = (int32_t*)pcc_arena_alloc(ctx, (size_t)nf * 4 + 64);
-  if (!d_in || !out || !status) return PCC_E_NOMEM;
+  if (!d_in || !out || !idx || !status) return PCC_E_NOMEM;
   PccProfScope prof(ctx, "attr_decode", points, nf, chunks, 0);
   // a caller's array in pinned host memory receives the values straight from the device; any other one through the
   // staging (a failed query of an ordinary pointer leaves its error behind: cleared here)
@@ -956,11 +1244,11 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
   const size_t out_b = h_out && !direct ? (size_t)bytes : 0;
   PCC_TRY(o2_stage_reserve(ctx, pcc_align(in_b) + pcc_align(out_b) + (size_t)nf * 4 + 64));
   uint8_t* stage = (uint8_t*)ctx->stage;
-  memcpy(stage, tab.data(), (size_t)nf * sizeof(ADFrame));
+  memcpy(stage, rows, (size_t)nf * row_b);
   for (int f = 0, k = 0; f < n_frames; ++f) {
     const AttrInfo& o = info[(size_t)f];
     if (o.n == 0) continue;
-    memcpy(stage + tab_b + tab[(size_t)k].body_off, h_blobs[f] + o.off_p0, (size_t)(h_lens[f] - o.off_p0));
+    memcpy(stage + tab_b + body_of(k), h_blobs[f] + o.off_p0, (size_t)(h_lens[f] - o.off_p0));
     ++k;
   }
   PCC_HIP(hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
@@ -970,10 +1258,20 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
   const int64_t room = ((int64_t)128 * 1024 - (int64_t)model_rows * kLanes * 2) / 2;
   const int lds_words = (int)std::max<int64_t>(0, std::min<int64_t>(cw_max, room));
   const size_t lds = (size_t)model_rows * kLanes * 2 + (size_t)lds_words * 2;
-  PCC_HIP(hipFuncSetAttribute((const void*)k_a_dec<ADFrame>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_a_dec<ADFrame>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint8_t*)(d_in + tab_b), (const ADFrame*)d_in, nf,
-                     model_rows, lds_words, out, status);
-  PCC_CHECK_LAUNCH();
+  if (!nl) {
+    PCC_HIP(hipFuncSetAttribute((const void*)k_a_dec<ADFrame>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_a_dec<ADFrame>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint8_t*)(d_in + tab_b), (const ADFrame*)d_in, nf,
+                       model_rows, lds_words, out, status);
+    PCC_CHECK_LAUNCH();
+  } else {
+    PCC_HIP(hipFuncSetAttribute((const void*)k_a_dec<AD2Frame>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_a_dec<AD2Frame>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint8_t*)(d_in + tab_b), (const AD2Frame*)d_in,
+                       nf, model_rows, lds_words, idx, status);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_a4_recon, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const AD2Frame*)d_in,
+                       (const uint8_t*)idx, out, status);
+    PCC_CHECK_LAUNCH();
+  }
   uint8_t* stage_out = stage + pcc_align(in_b);
   int32_t* h_status = (int32_t*)(stage_out + pcc_align(out_b));
   if (h_out) PCC_HIP(hipMemcpyAsync(direct ? (void*)h_out : (void*)stage_out, out, (size_t)bytes, hipMemcpyDeviceToHost, st));
@@ -982,8 +1280,8 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
   for (int f = 0, k = 0; f < n_frames; ++f) {
     if (info[(size_t)f].n == 0) continue;
     const int32_t bad = h_status[k++];
-    PCC_REQUIRE(bad == 0, PCC_E_STREAM, "pcc_attr_decode_frames: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state)",
-                f, bad);
+    PCC_REQUIRE(bad == 0, PCC_E_STREAM, "pcc_attr_decode_frames: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state%s)",
+                f, bad, nl ? ", 16 = reconstruction out of range" : "");
   }
   if (h_out && !direct) memcpy(h_out, stage_out, out_b);
   return PCC_OK;
@@ -993,11 +1291,11 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
 extern "C" int pcc_attr_lod_info(const uint8_t* h_in, int64_t len, int lod, int64_t* h_bytes, int64_t* h_values) {
   PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "pcc_attr_lod_info: level of detail %d outside 0 .. %d", lod, kAttrMaxLod);
   PCC_REQUIRE(h_in && len >= 2 && h_in[0] == 'A', PCC_E_STREAM, "pcc_attr_lod_info: not an attribute blob (len=%lld)", (long long)len);
-  PCC_REQUIRE(h_in[1] == 2, PCC_E_ARG, "pcc_attr_lod_info: attribute blob version %d (levels of detail are a property of version 2)",
-              (int)h_in[1]);
+  PCC_REQUIRE(h_in[1] == 2 || h_in[1] == 7, PCC_E_ARG,
+              "pcc_attr_lod_info: attribute blob version %d (levels of detail are a property of version 2)", (int)h_in[1]);
   Attr2Info o;
   Attr2Plan pl;
-  const int rc = attr2_parse(h_in, len, lod, false, &o, &pl);
+  const int rc = attr2_parse_kind(h_in, len, lod, false, h_in[1] == 7, &o, &pl);
   if (rc != PCC_OK) {
     const std::string m = pcc_last_error();
     pcc_set_error("pcc_attr_lod_info: %s", m.c_str());
@@ -1015,6 +1313,8 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   PCC_REQUIRE(ctx && h_blobs && h_lens && h_out_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
               "%s: bad argument (n_frames=%d)", who, n_frames);
   PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "%s: level of detail %d outside 0 .. %d", who, lod, kAttrMaxLod);
+  // the blobs of a call are of one version, the first blob's: 2, or 7 (k_a7_walk in place of k_a2_walk)
+  const bool nl = h_blobs[0] && h_lens[0] >= 2 && h_blobs[0][0] == 'A' && h_blobs[0][1] == 7;
   std::vector<Attr2Info> info((size_t)n_frames);
   std::vector<Attr2Plan> plan((size_t)n_frames);
   int64_t bytes = 0, bodies = 0, points = 0;
@@ -1022,7 +1322,10 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   for (int f = 0; f < n_frames; ++f) {
     Attr2Info& o = info[(size_t)f];
     Attr2Plan& pl = plan[(size_t)f];
-    const int rc = attr2_parse(h_blobs[f], h_lens[f], lod, true, &o, &pl);
+    PCC_REQUIRE(!(h_blobs[f] && h_lens[f] >= 2 && h_blobs[f][0] == 'A' && h_blobs[f][1] == (nl ? 2 : 7)), PCC_E_ARG,
+                "%s: frame %d: attribute blob version %d in a call of version %d blobs (one version per call)", who, f, nl ? 2 : 7,
+                nl ? 7 : 2);
+    const int rc = attr2_parse_kind(h_blobs[f], h_lens[f], lod, true, nl, &o, &pl);
     if (rc != PCC_OK) {
       const std::string m = pcc_last_error();
       pcc_set_error("%s: frame %d: %s", who, f, m.c_str());
@@ -1067,7 +1370,7 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
     r.nctx = o.nctx;
     r.n_dec = pl.m;
     r.last_words = (int32_t)pl.last_words;
-    r.pad = 0;
+    r.max_error = (int32_t)o.max_error;
     tab.push_back(r);
     order.push_back(A2Order{h_cell_offsets[f] - cell0, pl.m, (int32_t)blocks, lod + o.slod});
     for (int64_t k = 0; k + 1 < pl.chunks; ++k) cw_max = std::max<int64_t>(cw_max, attr_u32(h_blobs[f] + o.off_table + 4 * k));
@@ -1142,8 +1445,8 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   hipLaunchKernelGGL(k_a_dec<AD2Frame>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint8_t*)(d_in + tab_b), d_tab, nf, model_rows,
                      lds_words, resid, status);
   PCC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_a2_walk, dim3((unsigned)blocks), dim3(256), 0, st, d_ord, nf, d_tab, (const uint32_t*)rank, (const uint32_t*)first,
-                     (const uint8_t*)resid, out, status);
+  hipLaunchKernelGGL((nl ? k_a7_walk : k_a2_walk), dim3((unsigned)blocks), dim3(256), 0, st, d_ord, nf, d_tab, (const uint32_t*)rank,
+                     (const uint32_t*)first, (const uint8_t*)resid, out, status);
   PCC_CHECK_LAUNCH();
   uint8_t* stage_out = stage + pcc_align(in_b);
   uint32_t* h_counts = (uint32_t*)(stage_out + pcc_align(out_b));
@@ -1160,7 +1463,8 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
                   (long long)info[(size_t)f].cells[lod + j], h_counts[16 * k + j]);
     const int32_t bad = h_status[k++];
     PCC_REQUIRE(bad == 0, PCC_E_STREAM,
-                "%s: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state, 8 = predictor chain)", who, f, bad);
+                "%s: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state, 8 = predictor chain%s)", who, f, bad,
+                nl ? ", 16 = reconstruction out of range" : "");
   }
   if (h_out && !direct) memcpy(h_out, stage_out, out_b);
   return PCC_OK;

@@ -31,6 +31,19 @@
 // c* = (lanes - 1) / 64, l* = (lanes - 1) % 64: off_payload + 2 (words[0] + .. + words[c* - 1]) + 2 (192 + len[0] + ..
 // + len[l*]), len being chunk c*'s own length table (the rule of octree2_blob.h).  Header, p0 and the whole chunk table
 // are always needed.  tests/attr2_ref.py restates the format in numpy.
+//
+// Near-lossless kinds, versions 4 and 7 (attr_parse_kind / attr2_parse_kind): version 1's and version 2's layouts with
+// a u32 max_error = e directly behind payload_len (counted in it; everything behind it 4 bytes later; n == 0: the 12
+// bytes alone, which do not record e).  The valid version bytes 1, 2, 4, 7 differ pairwise in two bits.  What the lanes
+// code is, instead of a wrapped residual, the INDEX j of the quantised prediction error of a closed loop (the predictor
+// sees what the decoder will see; include/pcc.h states the rule in full):
+//   q = 2 e + 1, 1 <= e < 2^(8 bpv - 1);  d = v - p (no wrap);  j = sgn(d) floor((|d| + e) / q);  v^ = p + j q kept as an
+//   unclamped signed integer inside the loop, clamp(v^, 0, mask) written out;  |v - v^| <= e and |j| < 2^(8 bpv - 1)
+//   version 4   p = 0, v^[s-1], (v^[s-1] + v^[s-2] + 1) >> 1 (arithmetic shift) for s = 0, 1, >= 2 of the lane's run
+//   version 7   p = v^[first(i)] (point 0: 0), so v^_i = q x the sum of j along i -> first(i) -> .. -> 0; the value of a
+//               cell at a level of detail is the reconstruction of its Morton-first point
+// Binarisation, contexts (bucket of |j| of the channel's previous point in the run, edges 2 / 5 / 12 / 30, not retuned),
+// model, S, chunks, word runs and the prefix rule are unchanged.  tests/attr_nl_ref.py restates both kinds in numpy.
 #pragma once
 #include <stdint.h>
 
@@ -54,6 +67,8 @@ ATTR_HD static inline int attr_positions(int bpv) { return 16 * bpv; }
 ATTR_HD static inline int attr_contexts(int bpv, int c) { return c * kAttrBuckets * attr_positions(bpv); }
 
 struct AttrInfo {
+  int version;          // 1 | 4 (attr_parse_kind), 2 | 7 (attr2_parse_kind)
+  uint32_t max_error;   // e of versions 4 and 7 (0: lossless, and every blob without points)
   int bpv, c, nctx;
   int64_t n, S, nc;
   int64_t off_p0, off_table, off_payload, payload_words;
@@ -75,22 +90,30 @@ static inline void attr_layout(int64_t n, int c, int64_t* S, int64_t* nc) {
   *nc = k;
 }
 
-static inline int attr_parse(const uint8_t* b, int64_t len, AttrInfo* o) {
-  if (!b || len < kAttrHead || b[0] != 'A' || b[1] != 1) {
-    pcc_set_error("attribute blob: bad header (len=%lld)", (long long)len);
+// the largest e of a value width: e < 2^(8 bpv - 1)
+ATTR_HD static inline uint32_t attr_max_error(int bpv) { return (1u << (8 * bpv - 1)) - 1u; }
+
+// version 1 (nl = false) or 4 (nl = true): x = 4 bytes of max_error move everything behind payload_len
+static inline int attr_parse_kind(const uint8_t* b, int64_t len, bool nl, AttrInfo* o) {
+  const char* tag = nl ? " v4" : "";
+  const int x = nl ? 4 : 0;
+  if (!b || len < kAttrHead || b[0] != 'A' || b[1] != (nl ? 4 : 1)) {
+    pcc_set_error("attribute blob%s: bad header (len=%lld)", tag, (long long)len);
     return PCC_E_STREAM;
   }
+  o->version = b[1];
+  o->max_error = 0;
   o->bpv = b[2];
   o->c = b[3];
   if ((o->bpv != 1 && o->bpv != 2) || o->c < 1 || o->c > 4) {
-    pcc_set_error("attribute blob: %d bytes per value, %d channels", o->bpv, o->c);
+    pcc_set_error("attribute blob%s: %d bytes per value, %d channels", tag, o->bpv, o->c);
     return PCC_E_STREAM;
   }
   o->nctx = attr_contexts(o->bpv, o->c);
   o->n = (int64_t)attr_u32(b + 4);
   const int64_t payload = (int64_t)attr_u32(b + 8);
   if (kAttrHead + payload != len) {
-    pcc_set_error("attribute blob: payload of %lld bytes in a blob of %lld", (long long)payload, (long long)len);
+    pcc_set_error("attribute blob%s: payload of %lld bytes in a blob of %lld", tag, (long long)payload, (long long)len);
     return PCC_E_STREAM;
   }
   o->S = o->nc = 0;
@@ -98,32 +121,39 @@ static inline int attr_parse(const uint8_t* b, int64_t len, AttrInfo* o) {
   o->payload_words = 0;
   if (o->n == 0) {
     if (payload != 0) {
-      pcc_set_error("attribute blob: no points, %lld bytes of payload", (long long)payload);
+      pcc_set_error("attribute blob%s: no points, %lld bytes of payload", tag, (long long)payload);
       return PCC_E_STREAM;
     }
     return PCC_OK;
   }
-  if (o->n >= ((int64_t)1 << 27) || payload < 8) {
-    pcc_set_error("attribute blob: %lld points, payload %lld", (long long)o->n, (long long)payload);
+  if (o->n >= ((int64_t)1 << 27) || payload < 8 + x) {
+    pcc_set_error("attribute blob%s: %lld points, payload %lld", tag, (long long)o->n, (long long)payload);
     return PCC_E_STREAM;
   }
-  o->S = (int64_t)attr_u32(b + kAttrHead);
-  o->nc = (int64_t)attr_u32(b + kAttrHead + 4);
+  if (nl) {
+    o->max_error = attr_u32(b + kAttrHead);
+    if (o->max_error < 1 || o->max_error > attr_max_error(o->bpv)) {
+      pcc_set_error("attribute blob%s: max_error %u with %d bytes per value", tag, o->max_error, o->bpv);
+      return PCC_E_STREAM;
+    }
+  }
+  o->S = (int64_t)attr_u32(b + kAttrHead + x);
+  o->nc = (int64_t)attr_u32(b + kAttrHead + x + 4);
   if (o->S < 1 || o->S * o->c > kAttrMaxValues || o->nc < 1 || o->nc > o->n || kAttrLanes * o->S * o->nc < o->n ||
       kAttrLanes * o->S * (o->nc - 1) >= o->n) {
-    pcc_set_error("attribute blob: %lld points in %lld chunks of 64 x %lld", (long long)o->n, (long long)o->nc, (long long)o->S);
+    pcc_set_error("attribute blob%s: %lld points in %lld chunks of 64 x %lld", tag, (long long)o->n, (long long)o->nc, (long long)o->S);
     return PCC_E_STREAM;
   }
-  o->off_p0 = kAttrHead + 8;
+  o->off_p0 = kAttrHead + 8 + x;
   o->off_table = o->off_p0 + 2 * (int64_t)o->nctx;
   if (o->off_table + 4 * o->nc > len) {
-    pcc_set_error("attribute blob: truncated header (%lld chunks)", (long long)o->nc);
+    pcc_set_error("attribute blob%s: truncated header (%lld chunks)", tag, (long long)o->nc);
     return PCC_E_STREAM;
   }
   for (int i = 0; i < o->nctx; ++i) {
     const uint32_t p = (uint32_t)b[o->off_p0 + 2 * i] | ((uint32_t)b[o->off_p0 + 2 * i + 1] << 8);
     if (p < 16 || p > 4080) {
-      pcc_set_error("attribute blob: initial probability %u", p);
+      pcc_set_error("attribute blob%s: initial probability %u", tag, p);
       return PCC_E_STREAM;
     }
   }
@@ -132,7 +162,7 @@ static inline int attr_parse(const uint8_t* b, int64_t len, AttrInfo* o) {
     const int64_t cw = (int64_t)attr_u32(b + o->off_table + 4 * k);
     // a lane codes at most 512 values of at most 16 bpv decisions, one word each
     if (cw < 3 * kAttrLanes || cw > 3 * kAttrLanes + (int64_t)kAttrLanes * kAttrMaxValues * attr_positions(o->bpv)) {
-      pcc_set_error("attribute blob: chunk %lld has %lld words", (long long)k, (long long)cw);
+      pcc_set_error("attribute blob%s: chunk %lld has %lld words", tag, (long long)k, (long long)cw);
       return PCC_E_STREAM;
     }
     words += cw;
@@ -140,12 +170,14 @@ static inline int attr_parse(const uint8_t* b, int64_t len, AttrInfo* o) {
   o->off_payload = o->off_table + 4 * o->nc;
   o->payload_words = words;
   if (o->off_payload + 2 * words != len) {
-    pcc_set_error("attribute blob: chunks take %lld bytes, blob has %lld", (long long)(2 * words),
+    pcc_set_error("attribute blob%s: chunks take %lld bytes, blob has %lld", tag, (long long)(2 * words),
                   (long long)(len - o->off_payload));
     return PCC_E_STREAM;
   }
   return PCC_OK;
 }
+
+static inline int attr_parse(const uint8_t* b, int64_t len, AttrInfo* o) { return attr_parse_kind(b, len, false, o); }
 
 // ---- version 2 ---------------------------------------------------------------------------------------------------
 constexpr int kAttr2Head = kAttrHead + 64 + 8;   // .. | u32 cells[16] | u32 S | u32 n_chunks
@@ -177,18 +209,22 @@ struct Attr2Plan {
 // b[0 .. len): the blob, or a prefix of it.  need_all: the decoder's form — the plan's bytes must be present (lod 0: the
 // blob, whole and nothing behind it); otherwise (pcc_attr_lod_info) the bytes must only reach what the plan is computed
 // from, the last needed chunk's length table.  Nothing beyond b[len) is read.
-static inline int attr2_parse(const uint8_t* b, int64_t len, int lod, bool need_all, Attr2Info* o, Attr2Plan* pl) {
-  ATTR2_REQUIRE(b && len >= kAttrHead && b[0] == 'A' && b[1] == 2, "attribute blob v2: bad header (len=%lld)", (long long)len);
+// Version 2 (nl = false) or 7 (nl = true, x = 4 bytes of max_error in front of cells[16]).
+static inline int attr2_parse_kind(const uint8_t* b, int64_t len, int lod, bool need_all, bool nl, Attr2Info* o, Attr2Plan* pl) {
+  const int tag = nl ? 7 : 2, x = nl ? 4 : 0;
+  ATTR2_REQUIRE(b && len >= kAttrHead && b[0] == 'A' && b[1] == tag, "attribute blob v%d: bad header (len=%lld)", tag, (long long)len);
+  o->version = tag;
+  o->max_error = 0;
   o->bpv = b[2] & 15;
   o->slod = b[2] >> 4;
   o->c = b[3];
-  ATTR2_REQUIRE((o->bpv == 1 || o->bpv == 2) && o->c >= 1 && o->c <= 4, "attribute blob v2: %d bytes per value, %d channels",
+  ATTR2_REQUIRE((o->bpv == 1 || o->bpv == 2) && o->c >= 1 && o->c <= 4, "attribute blob v%d: %d bytes per value, %d channels", tag,
                 o->bpv, o->c);
   o->nctx = attr_contexts(o->bpv, o->c);
   o->n = (int64_t)attr_u32(b + 4);
   const int64_t payload = (int64_t)attr_u32(b + 8), total = kAttrHead + payload;
-  ATTR2_REQUIRE(len <= total, "attribute blob v2: payload of %lld bytes in a blob of %lld", (long long)payload, (long long)len);
-  ATTR2_REQUIRE(!(need_all && lod == 0) || len == total, "attribute blob v2: truncated (%lld bytes of %lld)", (long long)len,
+  ATTR2_REQUIRE(len <= total, "attribute blob v%d: payload of %lld bytes in a blob of %lld", tag, (long long)payload, (long long)len);
+  ATTR2_REQUIRE(!(need_all && lod == 0) || len == total, "attribute blob v%d: truncated (%lld bytes of %lld)", tag, (long long)len,
                 (long long)total);
   o->S = o->nc = 0;
   o->off_p0 = o->off_table = o->off_payload = kAttrHead;
@@ -198,42 +234,47 @@ static inline int attr2_parse(const uint8_t* b, int64_t len, int lod, bool need_
   pl->m = pl->chunks = pl->lanes = pl->last_off = pl->last_words = 0;
   pl->bytes = kAttrHead;
   if (o->n == 0) {
-    ATTR2_REQUIRE(payload == 0, "attribute blob v2: no points, %lld bytes of payload", (long long)payload);
+    ATTR2_REQUIRE(payload == 0, "attribute blob v%d: no points, %lld bytes of payload", tag, (long long)payload);
     return PCC_OK;
   }
-  o->off_p0 = kAttr2Head;
+  o->off_p0 = kAttr2Head + x;
   o->off_table = o->off_p0 + 2 * (int64_t)o->nctx;
   ATTR2_REQUIRE(o->n < ((int64_t)1 << 27) && payload >= o->off_table - kAttrHead + 4 + 2 * 3 * kAttrLanes,
-                "attribute blob v2: %lld points, payload %lld", (long long)o->n, (long long)payload);
-  ATTR2_REQUIRE(len >= o->off_table, "attribute blob v2: truncated header");
-  for (int k = 0; k < 16; ++k) {
-    o->cells[k] = (int64_t)attr_u32(b + kAttrHead + 4 * k);
-    ATTR2_REQUIRE(k == 0 ? o->cells[0] == o->n : (o->cells[k] >= 1 && o->cells[k] <= o->cells[k - 1] && 8 * o->cells[k] >= o->cells[k - 1]),
-                  "attribute blob v2: level of detail %d has %lld values", k, (long long)o->cells[k]);
+                "attribute blob v%d: %lld points, payload %lld", tag, (long long)o->n, (long long)payload);
+  ATTR2_REQUIRE(len >= o->off_table, "attribute blob v%d: truncated header", tag);
+  if (nl) {
+    o->max_error = attr_u32(b + kAttrHead);
+    ATTR2_REQUIRE(o->max_error >= 1 && o->max_error <= attr_max_error(o->bpv), "attribute blob v%d: max_error %u with %d bytes per value",
+                  tag, o->max_error, o->bpv);
   }
-  o->S = (int64_t)attr_u32(b + kAttrHead + 64);
-  o->nc = (int64_t)attr_u32(b + kAttrHead + 68);
+  for (int k = 0; k < 16; ++k) {
+    o->cells[k] = (int64_t)attr_u32(b + kAttrHead + x + 4 * k);
+    ATTR2_REQUIRE(k == 0 ? o->cells[0] == o->n : (o->cells[k] >= 1 && o->cells[k] <= o->cells[k - 1] && 8 * o->cells[k] >= o->cells[k - 1]),
+                  "attribute blob v%d: level of detail %d has %lld values", tag, k, (long long)o->cells[k]);
+  }
+  o->S = (int64_t)attr_u32(b + kAttrHead + x + 64);
+  o->nc = (int64_t)attr_u32(b + kAttrHead + x + 68);
   ATTR2_REQUIRE(o->S >= 1 && o->S * o->c <= kAttrMaxValues && o->nc >= 1 && o->nc <= o->n && kAttrLanes * o->S * o->nc >= o->n &&
                     kAttrLanes * o->S * (o->nc - 1) < o->n,
-                "attribute blob v2: %lld points in %lld chunks of 64 x %lld", (long long)o->n, (long long)o->nc, (long long)o->S);
+                "attribute blob v%d: %lld points in %lld chunks of 64 x %lld", tag, (long long)o->n, (long long)o->nc, (long long)o->S);
   for (int i = 0; i < o->nctx; ++i) {
     const uint32_t p = (uint32_t)b[o->off_p0 + 2 * i] | ((uint32_t)b[o->off_p0 + 2 * i + 1] << 8);
-    ATTR2_REQUIRE(p >= 16 && p <= 4080, "attribute blob v2: initial probability %u", p);
+    ATTR2_REQUIRE(p >= 16 && p <= 4080, "attribute blob v%d: initial probability %u", tag, p);
   }
-  ATTR2_REQUIRE(total - o->off_table >= 4 * o->nc, "attribute blob v2: truncated chunk table");
-  ATTR2_REQUIRE(len - o->off_table >= 4 * o->nc, "attribute blob v2: truncated inside the chunk table");
+  ATTR2_REQUIRE(total - o->off_table >= 4 * o->nc, "attribute blob v%d: truncated chunk table", tag);
+  ATTR2_REQUIRE(len - o->off_table >= 4 * o->nc, "attribute blob v%d: truncated inside the chunk table", tag);
   const uint8_t* q = b + o->off_table;
   int64_t words = 0;
   for (int64_t k = 0; k < o->nc; ++k) {
     const int64_t cw = (int64_t)attr_u32(q + 4 * k);
     // a lane codes at most 512 values of at most 16 bpv decisions, one word each
     ATTR2_REQUIRE(cw >= 3 * kAttrLanes && cw <= 3 * kAttrLanes + (int64_t)kAttrLanes * kAttrMaxValues * attr_positions(o->bpv),
-                  "attribute blob v2: chunk %lld has %lld words", (long long)k, (long long)cw);
+                  "attribute blob v%d: chunk %lld has %lld words", tag, (long long)k, (long long)cw);
     words += cw;
   }
   o->off_payload = o->off_table + 4 * o->nc;
   o->payload_words = words;
-  ATTR2_REQUIRE(o->off_payload + 2 * words == total, "attribute blob v2: chunks take %lld bytes, blob has %lld",
+  ATTR2_REQUIRE(o->off_payload + 2 * words == total, "attribute blob v%d: chunks take %lld bytes, blob has %lld", tag,
                 (long long)(2 * words), (long long)(total - o->off_payload));
   // the plan
   if (lod == 0) {
@@ -251,17 +292,21 @@ static inline int attr2_parse(const uint8_t* b, int64_t len, int lod, bool need_
   for (int64_t k = 0; k < cs; ++k) pl->last_off += (int64_t)attr_u32(q + 4 * k);
   const int64_t cw = (int64_t)attr_u32(q + 4 * cs);
   const int64_t at = o->off_payload + 2 * pl->last_off;   // the chunk: 128 state words, then its length table
-  ATTR2_REQUIRE(len >= at + 2 * 3 * kAttrLanes, "attribute blob v2: truncated in front of the length table of chunk %lld",
+  ATTR2_REQUIRE(len >= at + 2 * 3 * kAttrLanes, "attribute blob v%d: truncated in front of the length table of chunk %lld", tag,
                 (long long)cs);
   int64_t run = 3 * kAttrLanes;
   for (int64_t l = 0; l <= ls; ++l) run += (int64_t)b[at + 4 * kAttrLanes + 2 * l] | ((int64_t)b[at + 4 * kAttrLanes + 2 * l + 1] << 8);
-  ATTR2_REQUIRE(run <= cw, "attribute blob v2: the runs of chunk %lld take %lld words of its %lld", (long long)cs, (long long)run,
+  ATTR2_REQUIRE(run <= cw, "attribute blob v%d: the runs of chunk %lld take %lld words of its %lld", tag, (long long)cs, (long long)run,
                 (long long)cw);
   pl->chunks = cs + 1;
   pl->lanes = ls + 1;
   pl->last_words = run;
   pl->bytes = at + 2 * run;
-  ATTR2_REQUIRE(!need_all || pl->bytes <= len, "attribute blob v2: truncated (level of detail %d needs %lld bytes, %lld are here)", lod,
+  ATTR2_REQUIRE(!need_all || pl->bytes <= len, "attribute blob v%d: truncated (level of detail %d needs %lld bytes, %lld are here)", tag, lod,
                 (long long)pl->bytes, (long long)len);
   return PCC_OK;
+}
+
+static inline int attr2_parse(const uint8_t* b, int64_t len, int lod, bool need_all, Attr2Info* o, Attr2Plan* pl) {
+  return attr2_parse_kind(b, len, lod, need_all, false, o, pl);
 }

@@ -31,6 +31,15 @@ the values of every coarser level are a prefix of that blob's bytes too.
 Row j of attrs[f] is the value of the Morton-first point of cell j: a SAMPLE of the cell, where the sender's side
 compress(frames, attributes=..., lod=2) stores the cell's MEAN.  At lod 0 version 2 returns what version 1 returns.
 
+Near-lossless attributes (attribute blob versions 4 and 7): a quality setting with a guarantee, chosen by the sender:
+
+    blobs, attr_blobs = codec.compress(frames, attributes=attrs, max_error=2)      # scalable=True, lod=k as before
+    GeometryCodec.attr_info(attr_blobs[0])["max_error"]                            # 2: host only, what a receiver reads
+    frames, attrs = codec.decompress(blobs, attr_blobs)                            # the kind is read from the blob
+
+No decoded value is off by more than max_error from what max_error=0 (the default, lossless, the bytes of before)
+returns for the same call.  include/pcc.h states the rule.
+
 Metric frames (include/pcc.h has the rule): float32 points in the caller's unit, from the host or from this codec's
 device, are put on the lattice by the codec, q = rint((x - origin) / voxel) per coordinate in float32; rows without a
 return (NaN / Inf) can be dropped, and the row index says which decoded row every input row became.
@@ -160,8 +169,30 @@ class GeometryCodec:
         chunk's length table."""
         return Runtime.attr_lod_info(bytes(attr_blob), GeometryCodec._check_lod(lod))
 
+    @staticmethod
+    def attr_info(attr_blob):
+        """what the head of an attribute blob of any kind says, as a dict: version (1, 2, 4, 7), bpv (bytes per value),
+        channels, points, max_error (0: lossless; a blob without points records none), scalable, lod (the sender's).
+        Host only; `attr_blob` may be a prefix of 16 bytes or more."""
+        return Runtime.attr_info(bytes(attr_blob))
+
+    @staticmethod
+    def _check_max_error(max_error, attrs):
+        if isinstance(max_error, bool) or not isinstance(max_error, (int, np.integer)):
+            raise TypeError(f"max_error must be an integer >= 0, got {max_error!r}")
+        max_error = int(max_error)
+        if max_error < 0:
+            raise ValueError(f"max_error must be an integer >= 0, got {max_error}")
+        if max_error and attrs is None:
+            raise ValueError("max_error bounds the error of attributes: it needs attributes=")
+        for f, a in enumerate(attrs or ()):
+            if max_error >= 1 << (8 * a.dtype.itemsize - 1):
+                raise ValueError(f"frame {f}: max_error {max_error} is too large for {a.dtype} attributes, at most "
+                                 f"{(1 << (8 * a.dtype.itemsize - 1)) - 1}")
+        return max_error
+
     def compress(self, frames, attributes=None, lod=0, scalable=False, *, voxel=None, origin=(0.0, 0.0, 0.0),
-                 invalid="raise", return_index=False):
+                 invalid="raise", return_index=False, max_error=0):
         """frames: a sequence of int16 / int32 [n_f, 3] arrays -> a list of bytes, one version-2 blob per frame.
         Duplicate points are removed (as np.unique), out-of-range coordinates raise PccError (PCC_E_RANGE).
         lod = k > 0: the sender's side of a level of detail — blob f is the version-2 blob of the distinct cells
@@ -172,6 +203,11 @@ class GeometryCodec:
         rows of duplicate points merged to their rounded mean per channel.  scalable=True: attribute blobs of version 2,
         whose coarser levels of detail are prefixes (attr_lod_info, decompress(..., lod=k)); the geometry blobs are the
         same, the default stays version 1.  With lod = k it codes the cells' means over the cells' keys.
+        max_error = e > 0 (an integer; bool or non-integer: TypeError; negative, without attributes, or 2^(8 bytes per
+        value - 1) and more for a frame's dtype: ValueError): near-lossless attribute blobs, version 4 (7 with
+        scalable=True) — no decoded value is off by more than e from what max_error=0 returns for the same call, at
+        every level of detail (attr_info reads e back from a blob).  The geometry blobs are the same; 0, the default, is
+        the lossless coder and its bytes.
 
         Frame types: numpy int16 / int32 as above, numpy float32, or torch tensors of those three dtypes on the host or
         on this codec's device; all frames of a call integer or all float32, all on the host or all on the device
@@ -201,6 +237,7 @@ class GeometryCodec:
         elif voxel is not None:
             raise ValueError("voxel= with integer frames: they are on the lattice already")
         attrs = None if attributes is None else self._check_attributes(frames, attributes)
+        max_error = self._check_max_error(max_error, attrs)
         nb = len(frames)
 
         def result(blobs, attr_blobs=None, index=None):
@@ -233,7 +270,8 @@ class GeometryCodec:
                 blobs = rt.octree_encode_frames(rt.empty((0,), torch.int64), nb)
                 index = [rt.empty((0,), torch.int32) if on_device else np.zeros(0, np.int32) for _ in range(nb)]
                 return result(blobs, None if attrs is None else
-                              self._encode_attributes(rt, attrs, sizes, blobs, None, None, 0, version), index)
+                              self._encode_attributes(rt, attrs, sizes, blobs, None, None, 0, version, max_error=max_error),
+                              index)
             dev = rt.to_device(host)
             if on_device:      # one device-side concatenation, behind whatever the caller's stream still does to them
                 rt.stream.wait_stream(caller)
@@ -265,7 +303,7 @@ class GeometryCodec:
             if n_keep == 0:
                 blobs = rt.octree_encode_frames(rt.empty((0,), torch.int64), nb)
                 attr_blobs = None if attrs is None else self._encode_attributes(rt, attrs, sizes, blobs, None, None, 0, version,
-                                                                                n_kept=0)
+                                                                                n_kept=0, max_error=max_error)
                 index = None
                 if return_index:
                     index = self._split_index(torch.full((n,), -1, dtype=torch.int32, device=rt.device), sizes, on_device)
@@ -285,7 +323,7 @@ class GeometryCodec:
             attr_blobs = index = None
             if attrs is not None:
                 attr_blobs = self._encode_attributes(rt, attrs, sizes, blobs, perm, rows, n_u.value, version, keys, 3 * lod,
-                                                     n_keep if n_keep < n else None)
+                                                     n_keep if n_keep < n else None, max_error)
             if return_index:
                 first_run = torch.empty(nb, dtype=torch.int64, pin_memory=True)
                 np.cumsum([0] + [struct.unpack_from("<I", b, 4)[0] for b in blobs[:-1]], out=first_run.numpy())
@@ -304,7 +342,8 @@ class GeometryCodec:
         return [index[a:b] for a, b in zip(ends[:-1], ends[1:])]
 
     @staticmethod
-    def _encode_attributes(rt, attrs, sizes, blobs, perm, rows, n_unique, version=1, keys=None, key_shift=0, n_kept=None):
+    def _encode_attributes(rt, attrs, sizes, blobs, perm, rows, n_unique, version=1, keys=None, key_shift=0, n_kept=None,
+                           max_error=0):
         # the values as they come, frame by frame at 16-byte offsets, in one upload; the merge into Morton order
         # happens on the device from the sort's permutation and the runs of equal keys
         offs, at = [], 0
@@ -320,7 +359,7 @@ class GeometryCodec:
         points = [struct.unpack_from("<I", b, 4)[0] for b in blobs]
         row_offsets = np.cumsum([0] + list(sizes)).tolist()
         return rt.attr_encode_frames(values, offs, formats, row_offsets, points, perm, rows, n_unique, version, keys, key_shift,
-                                     n_kept)
+                                     n_kept, max_error)
 
     def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0, *, voxel=None, origin=(0.0, 0.0, 0.0)):
         """version-2 blobs -> a list of int32 [n_f, 3] point sets in Morton order: numpy arrays (output="numpy") or
@@ -330,8 +369,10 @@ class GeometryCodec:
         lod = k > 0: blobs or prefixes of them (lod_info) -> the distinct cell indices points >> k of every frame, int32
         [cells, 3] in Morton order (corner of a cell c << k, centre (c << k) + ((1 << k) >> 1)); with attr_blobs of
         version 2 (compress(..., scalable=True)), or prefixes of them (attr_lod_info): attributes[f] is [cells, c], row j
-        the value of the Morton-first point of cell j.  Versions may be mixed at lod 0; an attribute blob of version 1
-        at lod > 0 raises ValueError.
+        the value of the Morton-first point of cell j.  The kind of every attribute blob (lossless 1 / 2, near-lossless
+        4 / 7 of compress(..., max_error=e)) is read from the blob; version 7 behaves as version 2 and its prefixes do,
+        every value within e.  The four kinds may be mixed at lod 0; an attribute blob of version 1 or 4 at lod > 0
+        raises ValueError.
         voxel (with origin): the point sets come back as float32 [n_f, 3] in the caller's unit instead of int32,
         x = origin + t * voxel, one float32 multiplication and then one addition on the device (include/pcc.h has the
         rule): t the lattice index at lod 0 and, at lod k, the centre of the cell's lattice points
@@ -351,15 +392,17 @@ class GeometryCodec:
             attr_blobs = [bytes(b) for b in attr_blobs]
             if len(attr_blobs) != len(blobs):
                 raise ValueError(f"{len(attr_blobs)} attribute blobs for {len(blobs)} geometry blobs")
-            v1 = [len(b) > 1 and b[1] == 1 for b in attr_blobs]
+            kind = [b[1] if len(b) > 1 else 0 for b in attr_blobs]      # runs of one kind are decoded in one call
+            v1 = [k in (1, 4) for k in kind]
             if lod and any(v1):
-                raise ValueError(f"frame {v1.index(True)}: attributes of blob version 1 cannot be decoded at lod > 0: it "
+                raise ValueError(f"frame {v1.index(True)}: attributes of blob version {kind[v1.index(True)]} cannot be decoded at lod > 0: it "
                                  "is one predictive stream in full-resolution Morton order, so neither its bytes nor "
-                                 "its decoding can be cut; store version 2 (compress(..., scalable=True)) or ship "
+                                 "its decoding can be cut; store version 2 or 7 (compress(..., scalable=True)) or ship "
                                  "coarse attributes with compress(frames, attributes=..., lod=k)")
         with self._lock, self.rt as rt:
             # version 2 reads the cells where the geometry decode left them: on the device
-            on_device = attr_blobs is not None and not all(v1)
+            one_call = attr_blobs is not None and all(v1) and len(set(kind)) == 1
+            on_device = attr_blobs is not None and not one_call
             if voxel is not None:      # the points in the caller's unit, dequantised where the decode left them
                 cells, whole = rt.octree_decode_frames(blobs, device=True, lod=lod, whole=True)
                 frames = self._metric_frames(rt, cells, whole, lod, voxel, origin, output)
@@ -368,7 +411,7 @@ class GeometryCodec:
                 cells = frames
             if attr_blobs is None:
                 return frames
-            if all(v1):
+            if one_call:
                 return frames, rt.attr_decode_frames(attr_blobs, points=[f.shape[0] for f in frames],
                                                      device=(output == "device"))
             if output == "numpy" and voxel is None:      # one copy of the call's cells to the host, split as the device tensor is
@@ -379,7 +422,7 @@ class GeometryCodec:
             f = 0
             while f < len(blobs):      # runs of frames of one version, each in one call
                 g = f
-                while g < len(blobs) and v1[g] == v1[f]:
+                while g < len(blobs) and kind[g] == kind[f]:
                     g += 1
                 if v1[f]:
                     call = lambda: rt.attr_decode_frames(attr_blobs[f:g], points=[c.shape[0] for c in cells[f:g]],

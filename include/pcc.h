@@ -732,7 +732,8 @@ int pcc_octree_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs,
                                  int32_t* d_points, int32_t* h_points,
                                  int64_t cap_points, int64_t* h_point_offsets);
 
-/* Lossless per-point attributes of such a sequence (csrc/attr.hip: attribute
+/* Lossless per-point attributes of such a sequence (near-lossless ones with a
+ * bounded error: pcc_attr_encode_frames_nl below) (csrc/attr.hip: attribute
  * blob version 1, one per frame, its layout in that file's header): uint8 or
  * uint16 values, 1 <= c <= 4 channels, in the Morton order of the frame's
  * decoded points.  The blob depends on the geometry only through the point
@@ -856,6 +857,69 @@ int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs,
                                const int64_t* h_cell_offsets, uint8_t* d_out,
                                uint8_t* h_out, int64_t cap_bytes,
                                int64_t* h_out_offsets, int32_t* h_format);
+
+/* Near-lossless attributes with a bounded error: attribute blob versions 4
+ * (unscalable, version 1's order and layout) and 7 (scalable, version 2's
+ * introduction order, cells[16], sender's lod and prefix rule).  No decoded
+ * value is off by more than e = max_error from what the lossless coder would
+ * return for the same call (the merged value v: the rounded mean of duplicate
+ * points, or of a cell on the sender's side of a lod).
+ *
+ * The rule, one quantiser for both kinds.  bpv = bytes per value (1 | 2),
+ * mask = 2^(8 bpv) - 1, e an integer with 1 <= e < 2^(8 bpv - 1), step
+ * q = 2 e + 1.  Inside the prediction loop reconstructions v^ are UNCLAMPED
+ * signed integers; they are clamped to [0, mask] only when written out.
+ *   residual        d = v - p                      (no wrap)
+ *   index           j = sgn(d) floor((|d| + e) / q)
+ *   reconstruction  v^ = p + j q                    so |v - v^| <= e
+ *   output          clamp(v^, 0, mask)              (moves towards v: the bound
+ *                                                   holds)
+ * |j| <= (mask + 2 e) / q < 2^(8 bpv - 1): j takes the place of the lossless
+ * kinds' residual in their binarisation (zero flag, sign, Exp-Golomb prefix and
+ * suffix, kmax = 8 bpv - 1), contexts (channel, bucket of |j| of the channel's
+ * previous point in the lane's run, edges 2 / 5 / 12 / 30, position) and model.
+ *   version 4: a lane codes its run of S points in Morton order; p = 0 for the
+ *     run's first point, v^[s-1] for the second, floor((v^[s-1] + v^[s-2] + 1)
+ *     / 2) after that (an arithmetic shift: v^ may be negative or above mask).
+ *   version 7: p = v^[first(i)], point 0 predicted from 0, so v^_i = q times
+ *     the sum of j along the chain i -> first(i) -> .. -> 0 (order-free).  Level
+ *     of detail k holds the first cells[k] indices, a prefix of the bytes by
+ *     version 2's lane-granular rule; the value of a cell is the reconstruction
+ *     of its Morton-first point.
+ * Layout: version 1's / version 2's with a u32 max_error directly behind
+ * payload_len (counted in it, everything behind it 4 bytes later); n = 0 gives
+ * the 12-byte head alone, which records no e.  The version bytes 1, 2, 4, 7
+ * differ pairwise in two bits.
+ *   _encode_frames_nl : pcc_attr_encode_frames_kept with max_error.  version
+ *     1 | 2 chooses the unscalable / scalable kind; n_kept = -1: the call
+ *     dropped no rows (pcc_attr_encode_frames / _v2); max_error = 0: the
+ *     lossless blob of that version, byte for byte; max_error = e > 0: version
+ *     4 / 7.  An e of 2^(8 bpv - 1) or more for a frame's bpv: PCC_E_ARG naming
+ *     the frame.  One launch more than the lossless encoder of the version (4:
+ *     the loop of every lane run; 7: the walk of every point's chain).
+ *   _info : host only, no ctx: what the head of an attribute blob of any of
+ *     the four kinds says (all outputs nullable): version, bytes per value,
+ *     channels, points n, max_error (0: lossless; 0 too for n = 0), scalable
+ *     (versions 2 and 7), the sender's lod.  h_in may be a prefix of 12 bytes
+ *     or more (16 for n > 0 of versions 4 and 7).  Anything else: PCC_E_STREAM.
+ *   pcc_attr_decode_frames reads versions 1 and 4, pcc_attr_decode_frames_lod
+ *     versions 2 and 7 (pcc_attr_lod_info likewise), one version per call: the
+ *     first blob's; a blob of the call's other version is PCC_E_ARG naming the
+ *     frame.  The near-lossless decoders keep every check of the lossless ones
+ *     and add one (status 16): a reconstruction outside [-e, mask + e], which
+ *     no encoder produces, is PCC_E_STREAM naming its frame. */
+int pcc_attr_encode_frames_nl(pcc_ctx* ctx, int version, const void* d_values,
+                              const int64_t* h_value_offsets,
+                              const int32_t* h_format, const int64_t* h_rows,
+                              const int64_t* h_points, int n_frames,
+                              const uint32_t* d_perm,
+                              const uint32_t* d_run_starts, int64_t n_unique,
+                              int64_t n_kept, const uint64_t* d_keys,
+                              int key_shift, int max_error, uint8_t* h_out,
+                              int64_t cap, int64_t* h_offsets);
+int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_version,
+                  int32_t* h_bpv, int32_t* h_channels, int64_t* h_points,
+                  int32_t* h_max_error, int32_t* h_scalable, int32_t* h_lod);
 
 /* ---- whole-GOP entry points ------------------------------ */
 
