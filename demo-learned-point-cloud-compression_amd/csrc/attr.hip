@@ -31,9 +31,12 @@
 // version 2's streams over the INDICES j of a closed prediction loop instead of wrapped residuals.  Encoder: one pass in
 // front of the counting pass runs the loop over the merged values and leaves the j where the PRED = false coder reads
 // its residuals — k_a4_quant per (lane run, channel), k_a7_quant per point along its chain of first() — and k_a_stats /
-// k_a_enc<false> code them as they code version 2's.  Decoder: k_a_dec<AD2Frame> returns the j, then k_a4_recon redoes
-// the loop of every run, or k_a7_walk sums the chain, scales by q and clamps.  The kernels of versions 1 and 2 are the
-// instantiations they were.  tests/attr_nl_ref.py restates both kinds in numpy.
+// k_a_enc<false> code them as they code version 2's.  Decoder: k_a_dec<true> returns the j, then k_a4_recon redoes
+// the loop of every run, or k_a2_walk<true> sums the chain, scales by q and clamps.  tests/attr_nl_ref.py restates both
+// kinds in numpy.
+//
+// Host side: the four kinds share one encode sequence (a_encode_frames) and the helpers of the two decoders; DESIGN.md,
+// "attr.hip: one encode path, shared decode helpers".
 #include "common.h"
 #include "lanerans.h"
 #include "attr_blob.h"
@@ -42,6 +45,7 @@
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -67,6 +71,27 @@ __device__ __forceinline__ void a_binarise(int r, int kmax, Emit emit) {
   for (int j = k - 1; j >= 0; --j) emit(2 + kmax + j, (m >> j) & 1u);
 }
 
+// the predictor inside a lane's run (versions 1 and 4) from the previous two values a = v[s-1], b = v[s-2]: nothing, a,
+// their rounded mean.  T = uint32_t (values) or int (reconstructions: the shift is arithmetic)
+template <typename I, typename T>
+__host__ __device__ __forceinline__ T a_pred(I s, T a, T b) {
+  return s == 0 ? (T)0 : (s == 1 ? a : (a + b + 1) >> 1);
+}
+
+// value ch of a row of bpv-byte little-endian values at p: zero-extended, sign-extended, stored.  Indexed as the
+// kernels always indexed (p[ch] | p[2 ch], p[2 ch + 1]; the store's first byte at p[bpv ch]) and not through p + bpv ch:
+// that form compiles k_a_merge and k_a2_walk<false> to other instructions than they have had.  ch = 0: one value at p
+__device__ __forceinline__ uint32_t a_load(const uint8_t* p, int bpv, int ch = 0) {
+  return bpv == 1 ? (uint32_t)p[ch] : (uint32_t)p[2 * ch] | ((uint32_t)p[2 * ch + 1] << 8);
+}
+__device__ __forceinline__ int a_load_s(const uint8_t* p, int bpv, int ch = 0) {
+  return bpv == 1 ? (int)(int8_t)p[ch] : (int)(int16_t)((uint32_t)p[2 * ch] | ((uint32_t)p[2 * ch + 1] << 8));
+}
+__device__ __forceinline__ void a_store(uint8_t* p, int bpv, uint32_t val, int ch = 0) {
+  p[bpv * ch] = (uint8_t)val;
+  if (bpv == 2) p[2 * ch + 1] = (uint8_t)(val >> 8);
+}
+
 // residual of point i (run position s) in channel ch of a frame's merged values v[n][c]; PRED = false (version 2): v
 // holds the residuals themselves, wrapped to the value width, and the lane codes what it is handed
 template <bool PRED = true>
@@ -74,7 +99,7 @@ __device__ __forceinline__ int a_resid(const uint16_t* __restrict__ v, int64_t i
   const uint32_t x = v[i * c + ch];
   if constexpr (!PRED) return (int)((x + (uint32_t)half) & mask) - half;
   const uint32_t a = s >= 1 ? v[(i - 1) * c + ch] : 0u, b = s >= 2 ? v[(i - 2) * c + ch] : 0u;
-  const uint32_t pred = s == 0 ? 0u : (s == 1 ? a : (a + b + 1u) >> 1);
+  const uint32_t pred = a_pred(s, a, b);
   return (int)((x - pred + (uint32_t)half) & mask) - half;
 }
 
@@ -119,7 +144,7 @@ __global__ __launch_bounds__(256) void k_a_merge(const uint8_t* __restrict__ in,
     if (row < 0 || row >= h.rows) continue;   // not a row of this frame: the keys were not sorted frame by frame
     const uint8_t* p = in + h.in_off + row * c * bpv;
     for (int ch = 0; ch < c; ++ch)
-      sum[ch] += bpv == 1 ? (uint64_t)p[ch] : (uint64_t)p[2 * ch] | ((uint64_t)p[2 * ch + 1] << 8);
+      sum[ch] += a_load(p, bpv, ch);
     ++cnt;
   }
   if (cnt == 0) cnt = 1;
@@ -152,7 +177,7 @@ __global__ __launch_bounds__(256) void k_a4_quant(const uint16_t* __restrict__ m
     for (int k = 0; k < 8; ++k) {
       const int s = s0 + k;
       if (s < npts) {
-        const int p = s == 0 ? 0 : (s == 1 ? a : (a + b + 1) >> 1);
+        const int p = a_pred(s, a, b);
         const int j = a_quant(x[k] - p, e, q);
         b = a;
         a = p + j * q;
@@ -356,24 +381,21 @@ struct ADFrame {
   int64_t table_off, payload_off; // from body_off
   int64_t n, out_off;             // points; its values in the output: bytes
   int32_t S, nc, cb, c, bpv, nctx;
-  static constexpr bool kV2 = false;
-};
-// version 2 at a level of detail: n stays the whole blob's values, nc counts the chunks the level needs, n_dec its values
-// (the first n_dec of the introduction sequence), last_words the words of chunk nc - 1 that were uploaded.  Versions 4
-// and 7 decode their indices through the same rows (version 4: n_dec = n, every chunk whole): max_error is their e
-struct AD2Frame : ADFrame {
+  // version 2 at a level of detail: n stays the whole blob's values, nc counts the chunks the level needs, n_dec its
+  // values (the first n_dec of the introduction sequence), last_words the words of chunk nc - 1 that were uploaded.
+  // Versions 1 and 4: n_dec = n, every chunk whole.  max_error: the e of versions 4 and 7
   int64_t n_dec;
   int32_t last_words, max_error;
-  static constexpr bool kV2 = true;
 };
 
-// avail: the words of the chunk that are there to read (cw; fewer in the last chunk of a level of detail).  Version 2:
-// the values written are the residuals, in introduction order; a lane whose run the level cuts short stops there and is
-// exempt from the end checks, a lane behind it does nothing.
-template <bool IN_LDS, typename F>
+// avail: the words of the chunk that are there to read (cw; fewer in the last chunk of a level of detail).  V2 (the
+// rows of versions 2, 4 and 7): no prediction inside the run, the values written are what was coded (version 2: the
+// residuals, in introduction order); a lane whose run the level cuts short stops there and is exempt from the end
+// checks, a lane behind it does nothing.
+template <bool IN_LDS, bool V2>
 __device__ __forceinline__ void a_decode_chunk(uint16_t* s_model, const uint16_t* __restrict__ s_words,
                                                const uint16_t* __restrict__ p /* the chunk in the stream */, uint32_t cw,
-                                               uint32_t avail, const F& h, int64_t ck, int lane, uint8_t* __restrict__ out, int& bad) {
+                                               uint32_t avail, const ADFrame& h, int64_t ck, int lane, uint8_t* __restrict__ out, int& bad) {
   uint32_t x = (uint32_t)p[2 * lane] | ((uint32_t)p[2 * lane + 1] << 16);
   const uint32_t my_len = p[2 * kLanes + lane];
   uint32_t incl = my_len;
@@ -400,7 +422,7 @@ __device__ __forceinline__ void a_decode_chunk(uint16_t* s_model, const uint16_t
   const int64_t base = (ck * kLanes + lane) * h.S;
   int npts = (int)std::max<int64_t>(0, std::min<int64_t>(h.S, h.n - base));
   bool whole = true;
-  if constexpr (F::kV2) {
+  if constexpr (V2) {
     const int cut = (int)std::max<int64_t>(0, std::min<int64_t>(h.S, h.n_dec - base));
     whole = cut == npts;
     npts = cut;
@@ -461,11 +483,10 @@ __device__ __forceinline__ void a_decode_chunk(uint16_t* s_model, const uint16_t
     if (act && done) {
       const uint32_t sh = 16u * (uint32_t)ch;
       const uint32_t a = (uint32_t)(v1 >> sh) & 0xFFFFu, b = (uint32_t)(v2 >> sh) & 0xFFFFu;
-      const uint32_t pred = F::kV2 || s == 0 ? 0u : (s == 1 ? a : (a + b + 1u) >> 1);
+      const uint32_t pred = V2 ? 0u : a_pred(s, a, b);
       const uint32_t val = (pred + (neg ? 0u - m : m)) & mask;
       const int64_t o = ((base + s) * c + ch) * bpv;
-      out[o] = (uint8_t)val;
-      if (bpv == 2) out[o + 1] = (uint8_t)(val >> 8);
+      a_store(out + o, bpv, val);
       v2 = (v2 & ~(0xFFFFull << sh)) | ((uint64_t)a << sh);
       v1 = (v1 & ~(0xFFFFull << sh)) | ((uint64_t)val << sh);
       bk = (bk & ~(15u << (4 * ch))) | ((uint32_t)a_bucket(m) << (4 * ch));
@@ -484,8 +505,8 @@ __device__ __forceinline__ void a_decode_chunk(uint16_t* s_model, const uint16_t
 
 // block = chunk of the call: frame f owns blocks [cb, cb + nc).  Dynamic LDS: the models (nctx_max + 1 rows of 64),
 // then lds_words words for a chunk's payload
-template <typename F>
-__global__ __launch_bounds__(64) void k_a_dec(const uint8_t* __restrict__ bodies, const F* __restrict__ tab, int nf,
+template <bool V2>
+__global__ __launch_bounds__(64) void k_a_dec(const uint8_t* __restrict__ bodies, const ADFrame* __restrict__ tab, int nf,
                                               int model_rows, int lds_words, uint8_t* __restrict__ out_all,
                                               int32_t* __restrict__ status_all) {
   extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
@@ -493,7 +514,7 @@ __global__ __launch_bounds__(64) void k_a_dec(const uint8_t* __restrict__ bodies
   uint16_t* s_words = s_model + (int64_t)model_rows * kLanes;
   const int lane = threadIdx.x;
   const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].cb; });
-  const F& h = tab[f];
+  const ADFrame& h = tab[f];
   const int64_t ck = (int64_t)blockIdx.x - h.cb;
   const uint8_t* body = bodies + h.body_off;
   const uint16_t* p0 = reinterpret_cast<const uint16_t*>(body);
@@ -507,27 +528,27 @@ __global__ __launch_bounds__(64) void k_a_dec(const uint8_t* __restrict__ bodies
   const uint16_t* p = payload + before;
   int bad = 0;
   uint32_t avail = cw;
-  if constexpr (F::kV2) {
+  if constexpr (V2) {
     if (ck == h.nc - 1) avail = (uint32_t)h.last_words;
   }
   if (avail <= (uint32_t)lds_words) {
     for (uint32_t i = lane; i < avail; i += kLanes) s_words[i] = p[i];
     __syncthreads();
-    a_decode_chunk<true>(s_model, s_words, p, cw, avail, h, ck, lane, out_all + h.out_off, bad);
+    a_decode_chunk<true, V2>(s_model, s_words, p, cw, avail, h, ck, lane, out_all + h.out_off, bad);
   } else {
-    a_decode_chunk<false>(s_model, s_words, p, cw, avail, h, ck, lane, out_all + h.out_off, bad);
+    a_decode_chunk<false, V2>(s_model, s_words, p, cw, avail, h, ck, lane, out_all + h.out_off, bad);
   }
   const unsigned long long b1 = __ballot((bad & 1) != 0), b4 = __ballot((bad & 4) != 0);
   if (lane == 0 && (b1 | b4) != 0ull) atomicOr(status_all + f, (b1 ? 1 : 0) | (b4 ? 4 : 0));
 }
 
-// Version 4, behind k_a_dec<AD2Frame>: the decoder's side of k_a4_quant's loop, frame = blockIdx.y, one thread per (lane
+// Version 4, behind k_a_dec<true>: the decoder's side of k_a4_quant's loop, frame = blockIdx.y, one thread per (lane
 // run, channel).  idx_all / out_all: the frames' [n][c] values of bpv bytes at out_off, the indices j as the coder
 // wrapped them / the values clamped to the value width.  An encoder's reconstruction never leaves [-e, mask + e]:
 // status |= 16 where one does (and the loop goes on from the nearest value inside).
-__global__ __launch_bounds__(256) void k_a4_recon(const AD2Frame* __restrict__ tab, const uint8_t* __restrict__ idx_all,
+__global__ __launch_bounds__(256) void k_a4_recon(const ADFrame* __restrict__ tab, const uint8_t* __restrict__ idx_all,
                                                   uint8_t* __restrict__ out_all, int32_t* __restrict__ status_all) {
-  const AD2Frame& h = tab[blockIdx.y];
+  const ADFrame& h = tab[blockIdx.y];
   const int c = h.c, bpv = h.bpv, e = h.max_error, q = 2 * e + 1;
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t base = t / c * h.S;
@@ -541,8 +562,8 @@ __global__ __launch_bounds__(256) void k_a4_recon(const AD2Frame* __restrict__ t
   bool bad = false;
   for (int s = 0; s < npts; ++s) {
     const int64_t at = (int64_t)s * c * bpv;
-    const int j = bpv == 1 ? (int)(int8_t)r[at] : (int)(int16_t)((uint32_t)r[at] | ((uint32_t)r[at + 1] << 8));
-    const int p = s == 0 ? 0 : (s == 1 ? a : (a + b + 1) >> 1);
+    const int j = a_load_s(r + at, bpv);
+    const int p = a_pred(s, a, b);
     int64_t x = (int64_t)p + (int64_t)j * q;
     if (x < -e || x > mask + e) {
       bad = true;
@@ -551,8 +572,7 @@ __global__ __launch_bounds__(256) void k_a4_recon(const AD2Frame* __restrict__ t
     b = a;
     a = (int)x;
     const int val = a < 0 ? 0 : (a > mask ? mask : a);
-    o[at] = (uint8_t)val;
-    if (bpv == 2) o[at + 1] = (uint8_t)(val >> 8);
+    a_store(o + at, bpv, (uint32_t)val);
   }
   if (bad) atomicOr(status_all + blockIdx.y, 16);
 }
@@ -765,25 +785,29 @@ __global__ __launch_bounds__(256) void k_a7_quant(const A2Order* __restrict__ ta
 // links since every link leads to a strictly larger size.  Every index is checked against the frame's value count;
 // status |= 8 where a walk leaves it or does not end at point 0.  resid_all / out_all: the frames' [m][c] values of bpv
 // bytes at out_off, residuals in introduction order / values in Morton order.
-__global__ __launch_bounds__(256) void k_a2_walk(const A2Order* __restrict__ tab, int nf, const AD2Frame* __restrict__ ftab,
+// NL (version 7): the same walk over the indices j, sign-extended from the value width; the value is their sum times
+// q = 2 e + 1, clamped to the value width.  status |= 16 where the sum of a complete walk lies outside [-e, mask + e],
+// which no encoder's reconstruction does.
+template <bool NL>
+__global__ __launch_bounds__(256) void k_a2_walk(const A2Order* __restrict__ tab, int nf, const ADFrame* __restrict__ ftab,
                                                  const uint32_t* __restrict__ rank, const uint32_t* __restrict__ first,
                                                  const uint8_t* __restrict__ resid_all, uint8_t* __restrict__ out_all,
                                                  int32_t* __restrict__ status_all) {
   const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].blk0; });
   const A2Order& h = tab[f];
-  const AD2Frame& a = ftab[f];
+  const ADFrame& a = ftab[f];
   const int64_t i = ((int64_t)blockIdx.x - h.blk0) * blockDim.x + threadIdx.x;
   if (i >= h.n) return;
   const int c = a.c, bpv = a.bpv;
   const uint8_t* resid = resid_all + a.out_off;
-  uint32_t acc[4] = {0u, 0u, 0u, 0u};
+  uint32_t acc[4] = {0u, 0u, 0u, 0u};   // NL: sums of int32 in two's complement
   int64_t j = i;
   bool ok = false;
   for (int step = 0; step < kA2Bins; ++step) {
     const int64_t r = rank[h.pt0 + j];
     if (r >= h.n) break;
     const uint8_t* q = resid + r * c * bpv;
-    for (int ch = 0; ch < c; ++ch) acc[ch] += bpv == 1 ? (uint32_t)q[ch] : (uint32_t)q[2 * ch] | ((uint32_t)q[2 * ch + 1] << 8);
+    for (int ch = 0; ch < c; ++ch) acc[ch] += NL ? (uint32_t)a_load_s(q, bpv, ch) : a_load(q, bpv, ch);
     if (j == 0) {
       ok = true;
       break;
@@ -792,56 +816,20 @@ __global__ __launch_bounds__(256) void k_a2_walk(const A2Order* __restrict__ tab
     if (nj >= j) break;
     j = nj;
   }
-  if (!ok) atomicOr(status_all + f, 8);
   uint8_t* o = out_all + a.out_off + i * c * bpv;
-  for (int ch = 0; ch < c; ++ch) {
-    o[bpv * ch] = (uint8_t)acc[ch];
-    if (bpv == 2) o[2 * ch + 1] = (uint8_t)(acc[ch] >> 8);
-  }
-}
-
-// Version 7's k_a2_walk (a kernel of its own, so that version 2's stays the code it was): the same walk with the same
-// index checks over the indices j, sign-extended from the value width; the value is their sum times q = 2 e + 1, clamped
-// to the value width.  status |= 16 where the sum of a complete walk lies outside [-e, mask + e], which no encoder's
-// reconstruction does.
-__global__ __launch_bounds__(256) void k_a7_walk(const A2Order* __restrict__ tab, int nf, const AD2Frame* __restrict__ ftab,
-                                                 const uint32_t* __restrict__ rank, const uint32_t* __restrict__ first,
-                                                 const uint8_t* __restrict__ idx_all, uint8_t* __restrict__ out_all,
-                                                 int32_t* __restrict__ status_all) {
-  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].blk0; });
-  const A2Order& h = tab[f];
-  const AD2Frame& a = ftab[f];
-  const int64_t i = ((int64_t)blockIdx.x - h.blk0) * blockDim.x + threadIdx.x;
-  if (i >= h.n) return;
-  const int c = a.c, bpv = a.bpv, e = a.max_error, mask = (1 << (8 * bpv)) - 1;
-  const uint8_t* idx = idx_all + a.out_off;
-  uint32_t acc[4] = {0u, 0u, 0u, 0u};   // sums of int32 in two's complement
-  int64_t j = i;
-  bool ok = false;
-  for (int step = 0; step < kA2Bins; ++step) {
-    const int64_t r = rank[h.pt0 + j];
-    if (r >= h.n) break;
-    const uint8_t* q = idx + r * c * bpv;
-    for (int ch = 0; ch < c; ++ch)
-      acc[ch] += bpv == 1 ? (uint32_t)(int32_t)(int8_t)q[ch] : (uint32_t)(int32_t)(int16_t)((uint32_t)q[2 * ch] | ((uint32_t)q[2 * ch + 1] << 8));
-    if (j == 0) {
-      ok = true;
-      break;
+  if constexpr (!NL) {
+    if (!ok) atomicOr(status_all + f, 8);
+    for (int ch = 0; ch < c; ++ch) a_store(o, bpv, acc[ch], ch);
+  } else {
+    const int e = a.max_error, mask = (1 << (8 * bpv)) - 1;
+    bool far = false;
+    for (int ch = 0; ch < c; ++ch) {
+      const int64_t x = (int64_t)(int32_t)acc[ch] * (2 * e + 1);
+      far |= x < -e || x > mask + e;
+      a_store(o, bpv, (uint32_t)(x < 0 ? 0 : (x > mask ? mask : x)), ch);
     }
-    const int64_t nj = first[h.pt0 + j];
-    if (nj >= j) break;
-    j = nj;
+    if (!ok || far) atomicOr(status_all + f, (ok ? 0 : 8) | (ok && far ? 16 : 0));
   }
-  bool far = false;
-  uint8_t* o = out_all + a.out_off + i * c * bpv;
-  for (int ch = 0; ch < c; ++ch) {
-    const int64_t x = (int64_t)(int32_t)acc[ch] * (2 * e + 1);
-    far |= x < -e || x > mask + e;
-    const uint32_t val = (uint32_t)(x < 0 ? 0 : (x > mask ? mask : x));
-    o[bpv * ch] = (uint8_t)val;
-    if (bpv == 2) o[2 * ch + 1] = (uint8_t)(val >> 8);
-  }
-  if (!ok || far) atomicOr(status_all + f, (ok ? 0 : 8) | (ok && far ? 16 : 0));
 }
 
 }  // namespace
@@ -938,13 +926,15 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
   if (nf > 0) {
     const size_t ord_b = v2 ? pcc_align((size_t)nf * sizeof(A2Order)) : 0;
     const size_t tab_b = pcc_align((size_t)nf * sizeof(AFrame)) + ord_b;
-    const size_t v2_b = v2 ? 2 * merged_b_of(vals) + pcc_align((size_t)u * 2) + pcc_align((size_t)merge_blocks * 17 * 4) +
-                                 pcc_align((size_t)nf * 33 * 4)
-                           : 0;
-    const size_t nl_b = nl ? merged_b_of(vals) + 2 * pcc_align((size_t)u * 4) : 0;   // the indices; rank and first (version 7)
-    const size_t merged_b = pcc_align((size_t)vals * 2), cnt_b = pcc_align((size_t)ctxs * 8), p0_b = pcc_align((size_t)ctxs * 2);
+    const size_t merged_b = merged_b_of(vals), cnt_b = pcc_align((size_t)ctxs * 8), p0_b = pcc_align((size_t)ctxs * 2);
     const size_t rec_b = pcc_align((size_t)rec_words * 2), small_b = pcc_align((size_t)chunks * (4 + 2 * kLanes * 2 + kLanes * 2));
-    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + v2_b + nl_b + 8192));
+    // the order stage's (versions 2 and 7): packed | hist | 17 bin bases, then 16 counts per frame; rank, first (7)
+    const size_t pk_b = pcc_align((size_t)u * 2), hist_b = pcc_align((size_t)merge_blocks * kA2Bins * 4);
+    const size_t bins_b = pcc_align((size_t)nf * 33 * 4), link_b = pcc_align((size_t)u * 4);
+    // src is one more array of the merged values' size.  The sum counts it twice for version 2 and the links for
+    // version 4 too: it is what these calls have always reserved, and no call reserves less than it did
+    const size_t order_b = v2 ? 2 * merged_b + pk_b + hist_b + bins_b : 0, nl_b = nl ? merged_b + 2 * link_b : 0;
+    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + order_b + nl_b + 8192));
     AFrame* d_tab = (AFrame*)pcc_arena_alloc(ctx, tab_b);
     uint16_t* merged = (uint16_t*)pcc_arena_alloc(ctx, merged_b);
     uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, cnt_b);
@@ -952,10 +942,13 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     uint16_t* rec = (uint16_t*)pcc_arena_alloc(ctx, rec_b);
     uint16_t* work = (uint16_t*)pcc_arena_alloc(ctx, rec_b);
     char* small = (char*)pcc_arena_alloc(ctx, small_b);
-    if (!d_tab || !merged || !cnt || !p0 || !rec || !work || !small) return PCC_E_NOMEM;
+    // what the lanes code: the merged values (version 1), their residuals in introduction order (2), the indices (4, 7)
+    uint16_t* src = v2 || nl ? (uint16_t*)pcc_arena_alloc(ctx, merged_b) : merged;
+    if (!d_tab || !merged || !cnt || !p0 || !rec || !work || !small || !src) return PCC_E_NOMEM;
     uint32_t* words = (uint32_t*)small;
     uint16_t* states = (uint16_t*)(small + (size_t)chunks * 4);
     uint16_t* lens_d = states + (size_t)chunks * 2 * kLanes;
+    const A2Order* d_ord = (const A2Order*)((const uint8_t*)d_tab + tab_b - ord_b);
     // staging: the table on its way to the device | the blobs | their lengths
     const size_t lens_at = tab_b + (size_t)out_bytes;
     PCC_TRY(o2_stage_reserve(ctx, lens_at + (size_t)nf * 8 + 64));
@@ -970,91 +963,60 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     hipLaunchKernelGGL(k_a_merge, dim3((unsigned)merge_blocks), dim3(256), 0, st, (const uint8_t*)d_values, (const AFrame*)d_tab, nf,
                        d_perm, d_run_starts, n_unique, n_keys, merged);
     PCC_CHECK_LAUNCH();
-    const size_t lds = 4096 * 4 + (size_t)(nctx_max + 1) * kLanes * 2;   // <= 98 KB (c = 4, uint16)
-    if (nl) {
-      const A2Order* d_ord = (const A2Order*)((const uint8_t*)d_tab + tab_b - ord_b);
-      uint16_t* idx = (uint16_t*)pcc_arena_alloc(ctx, merged_b_of(vals));
-      if (!idx) return PCC_E_NOMEM;
-      uint32_t* cells = nullptr;
-      if (!v2) {
-        hipLaunchKernelGGL(k_a4_quant, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const uint16_t*)merged,
-                           (const AFrame*)d_tab, idx);
-        PCC_CHECK_LAUNCH();
-      } else {
-        uint32_t* rank = (uint32_t*)pcc_arena_alloc(ctx, (size_t)u * 4);
-        uint32_t* first = (uint32_t*)pcc_arena_alloc(ctx, (size_t)u * 4);
-        uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, (size_t)u * 2);
-        uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, (size_t)merge_blocks * 17 * 4);
-        uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nf * 33 * 4);   // 17 bin bases, then 16 counts per frame
-        if (!rank || !first || !packed || !hist || !bins) return PCC_E_NOMEM;
-        cells = bins + (size_t)nf * 17;
-        hipLaunchKernelGGL(k_a2_size<false>, dim3((unsigned)merge_blocks), dim3(256), 0, st, (const void*)d_keys, d_ord, nf,
-                           (uint64_t*)nullptr, packed, hist);
-        PCC_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_a2_scan, dim3((unsigned)nf), dim3(256), 0, st, d_ord, hist, bins, cells);
-        PCC_CHECK_LAUNCH();
-        hipLaunchKernelGGL((k_a2_place<true, true>), dim3((unsigned)merge_blocks), dim3(256), 0, st, d_keys, d_ord, nf,
-                           (const uint16_t*)packed, (const uint32_t*)hist, (const uint32_t*)bins, (const AFrame*)d_tab,
-                           (const uint16_t*)merged, (uint16_t*)nullptr, rank, first);
-        PCC_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_a7_quant, dim3((unsigned)merge_blocks), dim3(256), 0, st, d_ord, nf, (const AFrame*)d_tab,
-                           (const uint16_t*)merged, (const uint32_t*)rank, (const uint32_t*)first, idx);
-        PCC_CHECK_LAUNCH();
+    // the introduction order of the frames' points.  keep = false (version 2): the residuals against the predictors go
+    // to src; keep (version 7): places and predictors are kept for k_a7_quant
+    uint32_t *cells = nullptr, *rank = nullptr, *first = nullptr;
+    auto a_order_stage = [&](bool keep) -> int {
+      if (keep) {
+        rank = (uint32_t*)pcc_arena_alloc(ctx, link_b);
+        first = (uint32_t*)pcc_arena_alloc(ctx, link_b);
       }
-      hipLaunchKernelGGL(k_a_stats<false>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)idx, (const AFrame*)d_tab, nf, cnt);
-      PCC_CHECK_LAUNCH();
-      PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k_a_enc<false>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)idx, (const AFrame*)d_tab, nf,
-                         (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
-      PCC_CHECK_LAUNCH();
-      if (!v2)
-        hipLaunchKernelGGL((k_a_pack<false, true>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work,
-                           (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words,
-                           (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)nullptr, 0);
-      else
-        hipLaunchKernelGGL((k_a_pack<true, true>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work,
-                           (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words,
-                           (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3);
-      PCC_CHECK_LAUNCH();
-    } else if (!v2) {
-      hipLaunchKernelGGL(k_a_stats<true>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)merged, (const AFrame*)d_tab, nf, cnt);
-      PCC_CHECK_LAUNCH();
-      PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k_a_enc<true>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)merged, (const AFrame*)d_tab, nf,
-                         (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
-      PCC_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_a_pack<false>, dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work, (const AFrame*)d_tab, nf,
-                         (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words, (const uint16_t*)p0,
-                         stage + tab_b, len_dev, (const uint32_t*)nullptr, 0);
-      PCC_CHECK_LAUNCH();
-    } else {
-      const A2Order* d_ord = (const A2Order*)((const uint8_t*)d_tab + tab_b - ord_b);
-      uint16_t* resid = (uint16_t*)pcc_arena_alloc(ctx, merged_b_of(vals));
-      uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, (size_t)u * 2);
-      uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, (size_t)merge_blocks * 17 * 4);
-      uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nf * 33 * 4);   // 17 bin bases, then 16 counts per frame
-      if (!resid || !packed || !hist || !bins) return PCC_E_NOMEM;
-      uint32_t* cells = bins + (size_t)nf * 17;
+      uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, pk_b);
+      uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, hist_b);
+      uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, bins_b);
+      if ((keep && (!rank || !first)) || !packed || !hist || !bins) return PCC_E_NOMEM;
+      cells = bins + (size_t)nf * kA2Bins;
       hipLaunchKernelGGL(k_a2_size<false>, dim3((unsigned)merge_blocks), dim3(256), 0, st, (const void*)d_keys, d_ord, nf,
                          (uint64_t*)nullptr, packed, hist);
       PCC_CHECK_LAUNCH();
       hipLaunchKernelGGL(k_a2_scan, dim3((unsigned)nf), dim3(256), 0, st, d_ord, hist, bins, cells);
       PCC_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_a2_place<true>, dim3((unsigned)merge_blocks), dim3(256), 0, st, d_keys, d_ord, nf,
-                         (const uint16_t*)packed, (const uint32_t*)hist, (const uint32_t*)bins, (const AFrame*)d_tab,
-                         (const uint16_t*)merged, resid, (uint32_t*)nullptr, (uint32_t*)nullptr);
+      const auto place = keep ? k_a2_place<true, true> : k_a2_place<true, false>;
+      hipLaunchKernelGGL(place, dim3((unsigned)merge_blocks), dim3(256), 0, st, d_keys, d_ord, nf, (const uint16_t*)packed,
+                         (const uint32_t*)hist, (const uint32_t*)bins, (const AFrame*)d_tab, (const uint16_t*)merged,
+                         keep ? (uint16_t*)nullptr : src, rank, first);
       PCC_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_a_stats<false>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)resid, (const AFrame*)d_tab, nf, cnt);
+      return PCC_OK;
+    };
+    if (v2) PCC_TRY(a_order_stage(nl));
+    if (nl && !v2) {
+      hipLaunchKernelGGL(k_a4_quant, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const uint16_t*)merged,
+                         (const AFrame*)d_tab, src);
       PCC_CHECK_LAUNCH();
-      PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k_a_enc<false>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)resid, (const AFrame*)d_tab, nf,
-                         (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
-      PCC_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_a_pack<true>, dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work, (const AFrame*)d_tab, nf,
-                         (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words, (const uint16_t*)p0,
-                         stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3);
+    } else if (nl) {
+      hipLaunchKernelGGL(k_a7_quant, dim3((unsigned)merge_blocks), dim3(256), 0, st, d_ord, nf, (const AFrame*)d_tab,
+                         (const uint16_t*)merged, (const uint32_t*)rank, (const uint32_t*)first, src);
       PCC_CHECK_LAUNCH();
     }
+    // counting pass, coder, blobs: only version 1 predicts inside the run (PRED)
+    const size_t lds = 4096 * 4 + (size_t)(nctx_max + 1) * kLanes * 2;   // <= 98 KB (c = 4, uint16)
+    auto a_code = [&](auto v2c, auto nlc) -> int {
+      constexpr bool V2 = decltype(v2c)::value, NL = decltype(nlc)::value, PRED = !V2 && !NL;
+      hipLaunchKernelGGL(k_a_stats<PRED>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)src, (const AFrame*)d_tab, nf, cnt);
+      PCC_CHECK_LAUNCH();
+      PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<PRED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(k_a_enc<PRED>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)src, (const AFrame*)d_tab, nf,
+                         (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
+      PCC_CHECK_LAUNCH();
+      hipLaunchKernelGGL((k_a_pack<V2, NL>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work,
+                         (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words,
+                         (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3);
+      PCC_CHECK_LAUNCH();
+      return PCC_OK;
+    };
+    using Yes = std::true_type;
+    using No = std::false_type;
+    PCC_TRY(v2 ? (nl ? a_code(Yes{}, Yes{}) : a_code(Yes{}, No{})) : (nl ? a_code(No{}, Yes{}) : a_code(No{}, No{})));
     PCC_HIP(hipStreamSynchronize(st));
     for (int k = 0; k < nf; ++k) {
       const long long total = ((volatile long long*)len_dev)[k];
@@ -1152,76 +1114,136 @@ extern "C" int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_versio
   return PCC_OK;
 }
 
+// ---- what the two decoders share ------------------------------------------------------------------------------------
+static bool a_is_version(const uint8_t* b, int64_t len, int version) { return b && len >= 2 && b[0] == 'A' && b[1] == version; }
+
+// the blobs of a call are of one version, `mine`: the entry point's other version is refused by name
+static int a_mixed_version(const char* who, int f, const uint8_t* b, int64_t len, int other, int mine) {
+  PCC_REQUIRE(!a_is_version(b, len, other), PCC_E_ARG,
+              "%s: frame %d: attribute blob version %d in a call of version %d blobs (one version per call)", who, f, other, mine);
+  return PCC_OK;
+}
+
+// the parser's error, named by entry point and frame
+static int a_wrap_error(const char* who, int f, int rc) {
+  const std::string m = pcc_last_error();
+  pcc_set_error("%s: frame %d: %s", who, f, m.c_str());
+  return rc;
+}
+
+// the row of a frame with points: its body at body_off of the upload, its values at out_off of the output, its chunks
+// [cb, cb + nc) of the call's, the last of them with last_words words there to read, n_dec values to decode
+static ADFrame a_dec_row(const AttrInfo& o, int64_t body_off, int64_t out_off, int64_t cb, int64_t nc, int64_t n_dec,
+                         int64_t last_words) {
+  ADFrame r;
+  r.body_off = body_off;
+  r.table_off = o.off_table - o.off_p0;
+  r.payload_off = o.off_payload - o.off_p0;
+  r.n = o.n;
+  r.out_off = out_off;
+  r.S = (int32_t)o.S;
+  r.nc = (int32_t)nc;
+  r.cb = (int32_t)cb;
+  r.c = o.c;
+  r.bpv = o.bpv;
+  r.nctx = o.nctx;
+  r.n_dec = n_dec;
+  r.last_words = (int32_t)last_words;
+  r.max_error = (int32_t)o.max_error;
+  return r;
+}
+
+// a caller's array in pinned host memory receives the values straight from the device; any other one through the
+// staging (a failed query of an ordinary pointer leaves its error behind: cleared here)
+static bool a_host_is_pinned(const void* h_out) {
+  hipPointerAttribute_t attr;
+  if (!h_out) return false;
+  if (hipPointerGetAttributes(&attr, h_out) == hipSuccess) return attr.type == hipMemoryTypeHost;
+  (void)hipGetLastError();
+  return false;
+}
+
+// staging of a decode call: rows and bodies on their way up (in_b) | the values on their way down, unless they go
+// straight to the caller's array | back_b bytes of counts and status read back.  *down: where the device copies the
+// values to (h_out itself when pinned, the staging otherwise, nullptr without h_out); a_copy_out finishes
+static int a_dec_stage(pcc_ctx* ctx, uint8_t* h_out, size_t in_b, int64_t bytes, size_t back_b, uint8_t** down, uint8_t** back) {
+  const bool direct = a_host_is_pinned(h_out);
+  const size_t out_b = h_out && !direct ? (size_t)bytes : 0;
+  PCC_TRY(o2_stage_reserve(ctx, pcc_align(in_b) + pcc_align(out_b) + back_b + 64));
+  uint8_t* stage_out = (uint8_t*)ctx->stage + pcc_align(in_b);
+  *down = !h_out ? nullptr : (direct ? h_out : stage_out);
+  *back = stage_out + pcc_align(out_b);
+  return PCC_OK;
+}
+static void a_copy_out(uint8_t* h_out, const uint8_t* down, int64_t bytes) {
+  if (down && down != h_out) memcpy(h_out, down, (size_t)bytes);
+}
+
+// k_a_dec's dynamic LDS: a chunk's payload beside the models when it fits in 128 KB in all, else read where it lies
+static size_t a_dec_lds(int64_t nctx_max, int64_t cw_max, int* model_rows, int* lds_words) {
+  *model_rows = (int)nctx_max + 1;
+  const int64_t room = ((int64_t)128 * 1024 - (int64_t)*model_rows * kLanes * 2) / 2;
+  *lds_words = (int)std::max<int64_t>(0, std::min<int64_t>(cw_max, room));
+  return (size_t)*model_rows * kLanes * 2 + (size_t)*lds_words * 2;
+}
+
+// d_in: the call's rows, then (tab_b) its bodies
+template <bool V2>
+static int a_launch_dec(hipStream_t st, int64_t chunks, const uint8_t* d_in, size_t tab_b, int nf, int64_t nctx_max, int64_t cw_max,
+                        uint8_t* out, int32_t* status) {
+  int model_rows, lds_words;
+  const size_t lds = a_dec_lds(nctx_max, cw_max, &model_rows, &lds_words);
+  PCC_HIP(hipFuncSetAttribute((const void*)k_a_dec<V2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_a_dec<V2>, dim3((unsigned)chunks), dim3(64), lds, st, d_in + tab_b, (const ADFrame*)d_in, nf, model_rows, lds_words,
+                     out, status);
+  PCC_CHECK_LAUNCH();
+  return PCC_OK;
+}
+
 extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
                                       const int64_t* h_points, uint8_t* d_out, uint8_t* h_out, int64_t cap_bytes,
                                       int64_t* h_out_offsets, int32_t* h_format) {
+  const char* who = "pcc_attr_decode_frames";
   PCC_REQUIRE(ctx && h_blobs && h_lens && h_out_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
-              "pcc_attr_decode_frames: bad argument (n_frames=%d)", n_frames);
-  // the blobs of a call are of one version, the first blob's: 1, or 4 (its indices through the rows and the decoder of
-  // version 2 at lod 0, then k_a4_recon)
-  const bool nl = h_blobs[0] && h_lens[0] >= 2 && h_blobs[0][0] == 'A' && h_blobs[0][1] == 4;
+              "%s: bad argument (n_frames=%d)", who, n_frames);
+  // the blobs of a call are of one version, the first blob's: 1, or 4 (its indices through the decoder of version 2 at
+  // lod 0, then k_a4_recon)
+  const bool nl = a_is_version(h_blobs[0], h_lens[0], 4);
   std::vector<AttrInfo> info((size_t)n_frames);
   int64_t bytes = 0, bodies = 0, points = 0;
   h_out_offsets[0] = 0;
   for (int f = 0; f < n_frames; ++f) {
     AttrInfo& o = info[(size_t)f];
-    PCC_REQUIRE(!(h_blobs[f] && h_lens[f] >= 2 && h_blobs[f][0] == 'A' && h_blobs[f][1] == (nl ? 1 : 4)), PCC_E_ARG,
-                "pcc_attr_decode_frames: frame %d: attribute blob version %d in a call of version %d blobs (one version per call)", f,
-                nl ? 1 : 4, nl ? 4 : 1);
+    PCC_TRY(a_mixed_version(who, f, h_blobs[f], h_lens[f], nl ? 1 : 4, nl ? 4 : 1));
     const int rc = attr_parse_kind(h_blobs[f], h_lens[f], nl, &o);
-    if (rc != PCC_OK) {
-      const std::string m = pcc_last_error();
-      pcc_set_error("pcc_attr_decode_frames: frame %d: %s", f, m.c_str());
-      return rc;
-    }
-    PCC_REQUIRE(!h_points || h_points[f] == o.n, PCC_E_STREAM,
-                "pcc_attr_decode_frames: frame %d: the attribute blob has %lld points, its geometry %lld", f, (long long)o.n,
-                (long long)(h_points ? h_points[f] : 0));
+    if (rc != PCC_OK) return a_wrap_error(who, f, rc);
+    PCC_REQUIRE(!h_points || h_points[f] == o.n, PCC_E_STREAM, "%s: frame %d: the attribute blob has %lld points, its geometry %lld",
+                who, f, (long long)o.n, (long long)(h_points ? h_points[f] : 0));
     if (h_format) h_format[f] = o.bpv | (o.c << 8);
     bytes = a_round(bytes + o.n * o.c * o.bpv, 16);
     points += o.n;
     h_out_offsets[f + 1] = bytes;
     if (o.n) bodies += a_round(h_lens[f] - o.off_p0, 16);
   }
-  PCC_REQUIRE(points < ((int64_t)1 << 31), PCC_E_ARG, "pcc_attr_decode_frames: the blobs announce %lld points in all",
-              (long long)points);
+  PCC_REQUIRE(points < ((int64_t)1 << 31), PCC_E_ARG, "%s: the blobs announce %lld points in all", who, (long long)points);
   if (bytes == 0 || (!d_out && !h_out)) return PCC_OK;
-  PCC_REQUIRE(cap_bytes >= bytes, PCC_E_NOMEM, "pcc_attr_decode_frames: %lld bytes, capacity %lld", (long long)bytes,
-              (long long)cap_bytes);
+  PCC_REQUIRE(cap_bytes >= bytes, PCC_E_NOMEM, "%s: %lld bytes, capacity %lld", who, (long long)bytes, (long long)cap_bytes);
   std::vector<ADFrame> tab;
-  std::vector<AD2Frame> tab4;
   int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, run_threads = 0;
   for (int f = 0; f < n_frames; ++f) {
     const AttrInfo& o = info[(size_t)f];
     if (o.n == 0) continue;
-    AD2Frame r;
-    r.body_off = body_off;
-    r.table_off = o.off_table - o.off_p0;
-    r.payload_off = o.off_payload - o.off_p0;
-    r.n = o.n;
-    r.out_off = h_out_offsets[f];
-    r.S = (int32_t)o.S;
-    r.nc = (int32_t)o.nc;
-    r.cb = (int32_t)chunks;
-    r.c = o.c;
-    r.bpv = o.bpv;
-    r.nctx = o.nctx;
-    r.n_dec = o.n;
-    r.last_words = (int32_t)attr_u32(h_blobs[f] + o.off_table + 4 * (o.nc - 1));
-    r.max_error = (int32_t)o.max_error;
-    if (nl) tab4.push_back(r); else tab.push_back(r);
+    const uint8_t* table = h_blobs[f] + o.off_table;
+    tab.push_back(a_dec_row(o, body_off, h_out_offsets[f], chunks, o.nc, o.n, attr_u32(table + 4 * (o.nc - 1))));
     run_threads = std::max<int64_t>(run_threads, o.nc * kLanes * o.c);
-    for (int64_t k = 0; k < o.nc; ++k) cw_max = std::max<int64_t>(cw_max, attr_u32(h_blobs[f] + o.off_table + 4 * k));
+    for (int64_t k = 0; k < o.nc; ++k) cw_max = std::max<int64_t>(cw_max, attr_u32(table + 4 * k));
     body_off += a_round(h_lens[f] - o.off_p0, 16);
     chunks += o.nc;
     nctx_max = std::max<int64_t>(nctx_max, o.nctx);
   }
-  const int nf = (int)(nl ? tab4.size() : tab.size());
-  const size_t row_b = nl ? sizeof(AD2Frame) : sizeof(ADFrame);
-  const void* rows = nl ? (const void*)tab4.data() : (const void*)tab.data();
-  auto body_of = [&](int k) { return nl ? tab4[(size_t)k].body_off : tab[(size_t)k].body_off; };
+  const int nf = (int)tab.size();
   hipStream_t st = ctx->stream;
-  const size_t tab_b = pcc_align((size_t)nf * row_b);
+  const size_t tab_b = pcc_align((size_t)nf * sizeof(ADFrame));
   PCC_TRY(pcc_arena_reserve(ctx, tab_b + pcc_align((size_t)bodies + 16) + ((d_out ? 0 : 1) + (nl ? 1 : 0)) * pcc_align((size_t)bytes) +
                                      pcc_align((size_t)nf * 4 + 64) + 4096));
   uint8_t* d_in = (uint8_t*)pcc_arena_alloc(ctx, tab_b + (size_t)bodies + 16);
@@ -1230,60 +1252,37 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
   int32_t* status = (int32_t*)pcc_arena_alloc(ctx, (size_t)nf * 4 + 64);
   if (!d_in || !out || !idx || !status) return PCC_E_NOMEM;
   PccProfScope prof(ctx, "attr_decode", points, nf, chunks, 0);
-  // a caller's array in pinned host memory receives the values straight from the device; any other one through the
-  // staging (a failed query of an ordinary pointer leaves its error behind: cleared here)
-  bool direct = false;
-  if (h_out) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, h_out) == hipSuccess)
-      direct = attr.type == hipMemoryTypeHost;
-    else
-      (void)hipGetLastError();
-  }
   const size_t in_b = tab_b + (size_t)bodies;
-  const size_t out_b = h_out && !direct ? (size_t)bytes : 0;
-  PCC_TRY(o2_stage_reserve(ctx, pcc_align(in_b) + pcc_align(out_b) + (size_t)nf * 4 + 64));
+  uint8_t *down, *back;
+  PCC_TRY(a_dec_stage(ctx, h_out, in_b, bytes, (size_t)nf * 4, &down, &back));
   uint8_t* stage = (uint8_t*)ctx->stage;
-  memcpy(stage, rows, (size_t)nf * row_b);
+  memcpy(stage, tab.data(), (size_t)nf * sizeof(ADFrame));
   for (int f = 0, k = 0; f < n_frames; ++f) {
     const AttrInfo& o = info[(size_t)f];
     if (o.n == 0) continue;
-    memcpy(stage + tab_b + body_of(k), h_blobs[f] + o.off_p0, (size_t)(h_lens[f] - o.off_p0));
-    ++k;
+    memcpy(stage + tab_b + tab[(size_t)k++].body_off, h_blobs[f] + o.off_p0, (size_t)(h_lens[f] - o.off_p0));
   }
   PCC_HIP(hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
   PCC_HIP(hipMemsetAsync(status, 0, (size_t)nf * 4 + 64, st));
-  // a chunk's payload in LDS beside the models when it fits in 128 KB in all, else read where it lies
-  const int model_rows = (int)nctx_max + 1;
-  const int64_t room = ((int64_t)128 * 1024 - (int64_t)model_rows * kLanes * 2) / 2;
-  const int lds_words = (int)std::max<int64_t>(0, std::min<int64_t>(cw_max, room));
-  const size_t lds = (size_t)model_rows * kLanes * 2 + (size_t)lds_words * 2;
   if (!nl) {
-    PCC_HIP(hipFuncSetAttribute((const void*)k_a_dec<ADFrame>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_a_dec<ADFrame>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint8_t*)(d_in + tab_b), (const ADFrame*)d_in, nf,
-                       model_rows, lds_words, out, status);
-    PCC_CHECK_LAUNCH();
+    PCC_TRY(a_launch_dec<false>(st, chunks, d_in, tab_b, nf, nctx_max, cw_max, out, status));
   } else {
-    PCC_HIP(hipFuncSetAttribute((const void*)k_a_dec<AD2Frame>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_a_dec<AD2Frame>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint8_t*)(d_in + tab_b), (const AD2Frame*)d_in,
-                       nf, model_rows, lds_words, idx, status);
-    PCC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_a4_recon, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const AD2Frame*)d_in,
+    PCC_TRY(a_launch_dec<true>(st, chunks, d_in, tab_b, nf, nctx_max, cw_max, idx, status));
+    hipLaunchKernelGGL(k_a4_recon, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const ADFrame*)d_in,
                        (const uint8_t*)idx, out, status);
     PCC_CHECK_LAUNCH();
   }
-  uint8_t* stage_out = stage + pcc_align(in_b);
-  int32_t* h_status = (int32_t*)(stage_out + pcc_align(out_b));
-  if (h_out) PCC_HIP(hipMemcpyAsync(direct ? (void*)h_out : (void*)stage_out, out, (size_t)bytes, hipMemcpyDeviceToHost, st));
+  int32_t* h_status = (int32_t*)back;
+  if (down) PCC_HIP(hipMemcpyAsync(down, out, (size_t)bytes, hipMemcpyDeviceToHost, st));
   PCC_HIP(hipMemcpyAsync(h_status, status, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
   PCC_HIP(hipStreamSynchronize(st));
   for (int f = 0, k = 0; f < n_frames; ++f) {
     if (info[(size_t)f].n == 0) continue;
     const int32_t bad = h_status[k++];
-    PCC_REQUIRE(bad == 0, PCC_E_STREAM, "pcc_attr_decode_frames: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state%s)",
-                f, bad, nl ? ", 16 = reconstruction out of range" : "");
+    PCC_REQUIRE(bad == 0, PCC_E_STREAM, "%s: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state%s)", who, f,
+                bad, nl ? ", 16 = reconstruction out of range" : "");
   }
-  if (h_out && !direct) memcpy(h_out, stage_out, out_b);
+  a_copy_out(h_out, down, bytes);
   return PCC_OK;
 }
 
@@ -1313,8 +1312,8 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   PCC_REQUIRE(ctx && h_blobs && h_lens && h_out_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
               "%s: bad argument (n_frames=%d)", who, n_frames);
   PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "%s: level of detail %d outside 0 .. %d", who, lod, kAttrMaxLod);
-  // the blobs of a call are of one version, the first blob's: 2, or 7 (k_a7_walk in place of k_a2_walk)
-  const bool nl = h_blobs[0] && h_lens[0] >= 2 && h_blobs[0][0] == 'A' && h_blobs[0][1] == 7;
+  // the blobs of a call are of one version, the first blob's: 2, or 7 (k_a2_walk<true> scales and clamps)
+  const bool nl = a_is_version(h_blobs[0], h_lens[0], 7);
   std::vector<Attr2Info> info((size_t)n_frames);
   std::vector<Attr2Plan> plan((size_t)n_frames);
   int64_t bytes = 0, bodies = 0, points = 0;
@@ -1322,15 +1321,9 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   for (int f = 0; f < n_frames; ++f) {
     Attr2Info& o = info[(size_t)f];
     Attr2Plan& pl = plan[(size_t)f];
-    PCC_REQUIRE(!(h_blobs[f] && h_lens[f] >= 2 && h_blobs[f][0] == 'A' && h_blobs[f][1] == (nl ? 2 : 7)), PCC_E_ARG,
-                "%s: frame %d: attribute blob version %d in a call of version %d blobs (one version per call)", who, f, nl ? 2 : 7,
-                nl ? 7 : 2);
+    PCC_TRY(a_mixed_version(who, f, h_blobs[f], h_lens[f], nl ? 2 : 7, nl ? 7 : 2));
     const int rc = attr2_parse_kind(h_blobs[f], h_lens[f], lod, true, nl, &o, &pl);
-    if (rc != PCC_OK) {
-      const std::string m = pcc_last_error();
-      pcc_set_error("%s: frame %d: %s", who, f, m.c_str());
-      return rc;
-    }
+    if (rc != PCC_OK) return a_wrap_error(who, f, rc);
     if (h_cell_offsets) {
       const int64_t m = h_cell_offsets[f + 1] - h_cell_offsets[f];
       PCC_REQUIRE(m == pl.m, PCC_E_STREAM, "%s: frame %d: the attribute blob has %lld values at level of detail %d, its geometry %lld cells",
@@ -1348,7 +1341,7 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   if (bytes == 0 || (!d_out && !h_out)) return PCC_OK;
   PCC_REQUIRE(d_cells && h_cell_offsets && h_cell_offsets[0] >= 0, PCC_E_ARG, "%s: the cells of the frames are needed", who);
   PCC_REQUIRE(cap_bytes >= bytes, PCC_E_NOMEM, "%s: %lld bytes, capacity %lld", who, (long long)bytes, (long long)cap_bytes);
-  std::vector<AD2Frame> tab;
+  std::vector<ADFrame> tab;
   std::vector<A2Order> order;
   int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, blocks = 0;
   const int64_t cell0 = h_cell_offsets[0];
@@ -1356,22 +1349,7 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
     const Attr2Info& o = info[(size_t)f];
     const Attr2Plan& pl = plan[(size_t)f];
     if (pl.m == 0) continue;
-    AD2Frame r;
-    r.body_off = body_off;
-    r.table_off = o.off_table - o.off_p0;
-    r.payload_off = o.off_payload - o.off_p0;
-    r.n = o.n;
-    r.out_off = h_out_offsets[f];
-    r.S = (int32_t)o.S;
-    r.nc = (int32_t)pl.chunks;
-    r.cb = (int32_t)chunks;
-    r.c = o.c;
-    r.bpv = o.bpv;
-    r.nctx = o.nctx;
-    r.n_dec = pl.m;
-    r.last_words = (int32_t)pl.last_words;
-    r.max_error = (int32_t)o.max_error;
-    tab.push_back(r);
+    tab.push_back(a_dec_row(o, body_off, h_out_offsets[f], chunks, pl.chunks, pl.m, pl.last_words));
     order.push_back(A2Order{h_cell_offsets[f] - cell0, pl.m, (int32_t)blocks, lod + o.slod});
     for (int64_t k = 0; k + 1 < pl.chunks; ++k) cw_max = std::max<int64_t>(cw_max, attr_u32(h_blobs[f] + o.off_table + 4 * k));
     cw_max = std::max<int64_t>(cw_max, pl.last_words);
@@ -1384,7 +1362,7 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   const int32_t* cells = d_cells + 3 * cell0;
   const int nf = (int)tab.size();
   hipStream_t st = ctx->stream;
-  const size_t ftab_b = pcc_align((size_t)nf * sizeof(AD2Frame)), ord_b = pcc_align((size_t)nf * sizeof(A2Order));
+  const size_t ftab_b = pcc_align((size_t)nf * sizeof(ADFrame)), ord_b = pcc_align((size_t)nf * sizeof(A2Order));
   const size_t tab_b = ftab_b + ord_b;
   const size_t keys_b = pcc_align((size_t)cells_all * 8), u32_b = pcc_align((size_t)cells_all * 4), pk_b = pcc_align((size_t)cells_all * 2);
   // 17 bin bases per frame | 16 counts per frame | status per frame: the last two come back in one copy
@@ -1404,29 +1382,20 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   uint32_t* counts = bins + (size_t)nf * kA2Bins;
   int32_t* status = (int32_t*)(counts + (size_t)nf * 16);
   PccProfScope prof(ctx, "attr_decode_lod", points, nf, chunks, 0);
-  bool direct = false;
-  if (h_out) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, h_out) == hipSuccess)
-      direct = attr.type == hipMemoryTypeHost;
-    else
-      (void)hipGetLastError();
-  }
   const size_t in_b = tab_b + (size_t)bodies;
-  const size_t out_b = h_out && !direct ? (size_t)bytes : 0;
-  PCC_TRY(o2_stage_reserve(ctx, pcc_align(in_b) + pcc_align(out_b) + (size_t)nf * 17 * 4 + 64));
+  uint8_t *down, *back;
+  PCC_TRY(a_dec_stage(ctx, h_out, in_b, bytes, (size_t)nf * 17 * 4, &down, &back));
   uint8_t* stage = (uint8_t*)ctx->stage;
-  memcpy(stage, tab.data(), (size_t)nf * sizeof(AD2Frame));
+  memcpy(stage, tab.data(), (size_t)nf * sizeof(ADFrame));
   memcpy(stage + ftab_b, order.data(), (size_t)nf * sizeof(A2Order));
   for (int f = 0, k = 0; f < n_frames; ++f) {
     if (plan[(size_t)f].m == 0) continue;
     const Attr2Info& o = info[(size_t)f];
-    memcpy(stage + tab_b + tab[(size_t)k].body_off, h_blobs[f] + o.off_p0, (size_t)(plan[(size_t)f].bytes - o.off_p0));   // the level's bytes only
-    ++k;
+    memcpy(stage + tab_b + tab[(size_t)k++].body_off, h_blobs[f] + o.off_p0, (size_t)(plan[(size_t)f].bytes - o.off_p0));   // the level's bytes only
   }
   PCC_HIP(hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
   PCC_HIP(hipMemsetAsync(status, 0, (size_t)nf * 4, st));
-  const AD2Frame* d_tab = (const AD2Frame*)d_in;
+  const ADFrame* d_tab = (const ADFrame*)d_in;
   const A2Order* d_ord = (const A2Order*)(d_in + ftab_b);
   // the introduction order of the cells: nothing of it depends on the attribute stream
   hipLaunchKernelGGL(k_a2_size<true>, dim3((unsigned)blocks), dim3(256), 0, st, (const void*)cells, d_ord, nf, keys, packed, hist);
@@ -1437,21 +1406,13 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
                      (const uint32_t*)hist, (const uint32_t*)bins, (const AFrame*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr,
                      rank, first);
   PCC_CHECK_LAUNCH();
-  const int model_rows = (int)nctx_max + 1;
-  const int64_t room = ((int64_t)128 * 1024 - (int64_t)model_rows * kLanes * 2) / 2;
-  const int lds_words = (int)std::max<int64_t>(0, std::min<int64_t>(cw_max, room));
-  const size_t lds = (size_t)model_rows * kLanes * 2 + (size_t)lds_words * 2;
-  PCC_HIP(hipFuncSetAttribute((const void*)k_a_dec<AD2Frame>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_a_dec<AD2Frame>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint8_t*)(d_in + tab_b), d_tab, nf, model_rows,
-                     lds_words, resid, status);
+  PCC_TRY(a_launch_dec<true>(st, chunks, d_in, tab_b, nf, nctx_max, cw_max, resid, status));
+  hipLaunchKernelGGL((nl ? k_a2_walk<true> : k_a2_walk<false>), dim3((unsigned)blocks), dim3(256), 0, st, d_ord, nf, d_tab,
+                     (const uint32_t*)rank, (const uint32_t*)first, (const uint8_t*)resid, out, status);
   PCC_CHECK_LAUNCH();
-  hipLaunchKernelGGL((nl ? k_a7_walk : k_a2_walk), dim3((unsigned)blocks), dim3(256), 0, st, d_ord, nf, d_tab, (const uint32_t*)rank,
-                     (const uint32_t*)first, (const uint8_t*)resid, out, status);
-  PCC_CHECK_LAUNCH();
-  uint8_t* stage_out = stage + pcc_align(in_b);
-  uint32_t* h_counts = (uint32_t*)(stage_out + pcc_align(out_b));
+  uint32_t* h_counts = (uint32_t*)back;
   int32_t* h_status = (int32_t*)(h_counts + (size_t)nf * 16);
-  if (h_out) PCC_HIP(hipMemcpyAsync(direct ? (void*)h_out : (void*)stage_out, out, (size_t)bytes, hipMemcpyDeviceToHost, st));
+  if (down) PCC_HIP(hipMemcpyAsync(down, out, (size_t)bytes, hipMemcpyDeviceToHost, st));
   PCC_HIP(hipMemcpyAsync(h_counts, counts, (size_t)nf * 17 * 4, hipMemcpyDeviceToHost, st));
   PCC_HIP(hipStreamSynchronize(st));
   for (int f = 0, k = 0; f < n_frames; ++f) {
@@ -1466,6 +1427,6 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
                 "%s: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state, 8 = predictor chain%s)", who, f, bad,
                 nl ? ", 16 = reconstruction out of range" : "");
   }
-  if (h_out && !direct) memcpy(h_out, stage_out, out_b);
+  a_copy_out(h_out, down, bytes);
   return PCC_OK;
 }

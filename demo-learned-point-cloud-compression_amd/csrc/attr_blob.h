@@ -93,6 +93,34 @@ static inline void attr_layout(int64_t n, int c, int64_t* S, int64_t* nc) {
 // the largest e of a value width: e < 2^(8 bpv - 1)
 ATTR_HD static inline uint32_t attr_max_error(int bpv) { return (1u << (8 * bpv - 1)) - 1u; }
 
+// the nctx initial probabilities at b + off lie in [16, 4080]; else *bad_p is the first that does not
+static inline bool attr_check_p0(const uint8_t* b, int64_t off, int nctx, uint32_t* bad_p) {
+  for (int i = 0; i < nctx; ++i) {
+    const uint32_t p = (uint32_t)b[off + 2 * i] | ((uint32_t)b[off + 2 * i + 1] << 8);
+    if (p < 16 || p > 4080) {
+      *bad_p = p;
+      return false;
+    }
+  }
+  return true;
+}
+
+// *words = the sum of a chunk table's nc entries; false at the first chunk (*bad_k) whose words (*bad_cw) a chunk cannot
+// have: a lane codes at most 512 values of at most 16 bpv decisions, one word each
+static inline bool attr_sum_chunks(const uint8_t* table, int64_t nc, int bpv, int64_t* words, int64_t* bad_k, int64_t* bad_cw) {
+  *words = 0;
+  for (int64_t k = 0; k < nc; ++k) {
+    const int64_t cw = (int64_t)attr_u32(table + 4 * k);
+    if (cw < 3 * kAttrLanes || cw > 3 * kAttrLanes + (int64_t)kAttrLanes * kAttrMaxValues * attr_positions(bpv)) {
+      *bad_k = k;
+      *bad_cw = cw;
+      return false;
+    }
+    *words += cw;
+  }
+  return true;
+}
+
 // version 1 (nl = false) or 4 (nl = true): x = 4 bytes of max_error move everything behind payload_len
 static inline int attr_parse_kind(const uint8_t* b, int64_t len, bool nl, AttrInfo* o) {
   const char* tag = nl ? " v4" : "";
@@ -150,22 +178,15 @@ static inline int attr_parse_kind(const uint8_t* b, int64_t len, bool nl, AttrIn
     pcc_set_error("attribute blob%s: truncated header (%lld chunks)", tag, (long long)o->nc);
     return PCC_E_STREAM;
   }
-  for (int i = 0; i < o->nctx; ++i) {
-    const uint32_t p = (uint32_t)b[o->off_p0 + 2 * i] | ((uint32_t)b[o->off_p0 + 2 * i + 1] << 8);
-    if (p < 16 || p > 4080) {
-      pcc_set_error("attribute blob%s: initial probability %u", tag, p);
-      return PCC_E_STREAM;
-    }
+  uint32_t bad_p = 0;
+  if (!attr_check_p0(b, o->off_p0, o->nctx, &bad_p)) {
+    pcc_set_error("attribute blob%s: initial probability %u", tag, bad_p);
+    return PCC_E_STREAM;
   }
-  int64_t words = 0;
-  for (int64_t k = 0; k < o->nc; ++k) {
-    const int64_t cw = (int64_t)attr_u32(b + o->off_table + 4 * k);
-    // a lane codes at most 512 values of at most 16 bpv decisions, one word each
-    if (cw < 3 * kAttrLanes || cw > 3 * kAttrLanes + (int64_t)kAttrLanes * kAttrMaxValues * attr_positions(o->bpv)) {
-      pcc_set_error("attribute blob%s: chunk %lld has %lld words", tag, (long long)k, (long long)cw);
-      return PCC_E_STREAM;
-    }
-    words += cw;
+  int64_t words = 0, bad_k = 0, bad_cw = 0;
+  if (!attr_sum_chunks(b + o->off_table, o->nc, o->bpv, &words, &bad_k, &bad_cw)) {
+    pcc_set_error("attribute blob%s: chunk %lld has %lld words", tag, (long long)bad_k, (long long)bad_cw);
+    return PCC_E_STREAM;
   }
   o->off_payload = o->off_table + 4 * o->nc;
   o->payload_words = words;
@@ -257,21 +278,14 @@ static inline int attr2_parse_kind(const uint8_t* b, int64_t len, int lod, bool 
   ATTR2_REQUIRE(o->S >= 1 && o->S * o->c <= kAttrMaxValues && o->nc >= 1 && o->nc <= o->n && kAttrLanes * o->S * o->nc >= o->n &&
                     kAttrLanes * o->S * (o->nc - 1) < o->n,
                 "attribute blob v%d: %lld points in %lld chunks of 64 x %lld", tag, (long long)o->n, (long long)o->nc, (long long)o->S);
-  for (int i = 0; i < o->nctx; ++i) {
-    const uint32_t p = (uint32_t)b[o->off_p0 + 2 * i] | ((uint32_t)b[o->off_p0 + 2 * i + 1] << 8);
-    ATTR2_REQUIRE(p >= 16 && p <= 4080, "attribute blob v%d: initial probability %u", tag, p);
-  }
+  uint32_t bad_p = 0;
+  ATTR2_REQUIRE(attr_check_p0(b, o->off_p0, o->nctx, &bad_p), "attribute blob v%d: initial probability %u", tag, bad_p);
   ATTR2_REQUIRE(total - o->off_table >= 4 * o->nc, "attribute blob v%d: truncated chunk table", tag);
   ATTR2_REQUIRE(len - o->off_table >= 4 * o->nc, "attribute blob v%d: truncated inside the chunk table", tag);
   const uint8_t* q = b + o->off_table;
-  int64_t words = 0;
-  for (int64_t k = 0; k < o->nc; ++k) {
-    const int64_t cw = (int64_t)attr_u32(q + 4 * k);
-    // a lane codes at most 512 values of at most 16 bpv decisions, one word each
-    ATTR2_REQUIRE(cw >= 3 * kAttrLanes && cw <= 3 * kAttrLanes + (int64_t)kAttrLanes * kAttrMaxValues * attr_positions(o->bpv),
-                  "attribute blob v%d: chunk %lld has %lld words", tag, (long long)k, (long long)cw);
-    words += cw;
-  }
+  int64_t words = 0, bad_k = 0, bad_cw = 0;
+  ATTR2_REQUIRE(attr_sum_chunks(q, o->nc, o->bpv, &words, &bad_k, &bad_cw), "attribute blob v%d: chunk %lld has %lld words", tag,
+                (long long)bad_k, (long long)bad_cw);
   o->off_payload = o->off_table + 4 * o->nc;
   o->payload_words = words;
   ATTR2_REQUIRE(o->off_payload + 2 * words == total, "attribute blob v%d: chunks take %lld bytes, blob has %lld", tag,
