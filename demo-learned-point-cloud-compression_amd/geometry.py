@@ -50,6 +50,13 @@ return (NaN / Inf) can be dropped, and the row index says which decoded row ever
 
 voxel and origin are not written into any blob: the caller carries the grid.
 
+Distortion (include/pcc.h has the rule): what a lossy setting costs, as the D1 (point-to-point) figures of MPEG's
+pc_error, by exact nearest neighbours on the device; lattice frames from the host or from this codec's device.
+
+    cells = codec.decompress([b[:nbytes]], lod=2)[0]
+    rep = codec.distortion([pts], [(cells << 2) + 2], peak=1023)     # rep[0]: mse_ab, mse_ba, max_ab, max_ba, d1_psnr
+    rep = codec.distortion(frames, lossy, attributes_a=attrs, attributes_b=lossy_attrs)      # + attr_mse_ab / _ba
+
 One Runtime (ctx + stream) per codec; calls on the same instance are serialised, instances on different threads run
 side by side.
 """
@@ -448,6 +455,158 @@ class GeometryCodec:
         rt.sync()      # the host copy is complete; a device result may be read from the caller's stream at once
         ends = np.cumsum([0] + [int(c.shape[0]) for c in cells]).tolist()
         return [pts[a:b] for a, b in zip(ends[:-1], ends[1:])]
+
+    def _lattice_keys(self, rt, frames, on_device, caller):
+        """integer frames of a call -> (keys, perm, distinct): the call's Morton keys, frame index above bit 48, sorted
+        with their duplicates; the sort's permutation; the distinct keys (`keys` itself where there is no duplicate).
+        The front of compress for integer frames: one upload, keys, sort, distinct."""
+        nb = len(frames)
+        sizes = [int(a.shape[0]) for a in frames]
+        n = int(sum(sizes))
+        if n == 0:
+            none = rt.empty((0,), torch.int64)
+            return none, rt.empty((0,), torch.int32), none
+        dtype = np.int16 if all(a.element_size() == 2 if on_device else a.dtype == np.int16 for a in frames) else np.int32
+        offs_b = 8 * (nb + 1)
+        rows_at = (offs_b + 15) // 16 * 16
+        host = torch.empty(rows_at + (0 if on_device else 3 * n * np.dtype(dtype).itemsize), dtype=torch.uint8, pin_memory=True)
+        h = host.numpy()
+        np.cumsum([0] + sizes, out=h[:offs_b].view(np.int64))
+        if not on_device:
+            np.concatenate(frames, axis=0, out=h[rows_at:].view(dtype).reshape(n, 3))
+        dev = rt.to_device(host)
+        if on_device:
+            rt.stream.wait_stream(caller)
+            xyz = torch.cat([a.detach().to(torch.int16 if dtype == np.int16 else torch.int32) for a in frames], 0).contiguous()
+            xyz_ptr = xyz.data_ptr()
+        else:
+            xyz_ptr = dev.data_ptr() + rows_at
+        keys = rt.empty((n,), torch.int64)
+        flag = torch.zeros(1, dtype=torch.int32, device=rt.device)
+        check(rt.lib.pcc_morton_keys_frames(rt.ctx, C.c_void_p(xyz_ptr), np.dtype(dtype).itemsize, n, C.c_void_p(dev.data_ptr()),
+                                            nb, _ptr(keys), _ptr(flag)), "pcc_morton_keys_frames")
+        perm = rt.sort_pairs(keys)
+        rows = rt.empty((n,), torch.int32)
+        n_u = C.c_int64(0)
+        check(rt.lib.pcc_unique_rows(rt.ctx, _ptr(rt.keys_to_coords(keys)), n, _ptr(rows), C.byref(n_u)), "pcc_unique_rows")
+        if int(flag.item()) != 0:      # read behind the synchronisation of pcc_unique_rows
+            raise PccError(PCC_E_RANGE, "GeometryCodec.distortion", "coordinate outside [-32768, 32767]")
+        return keys, perm, keys if n_u.value == n else rt.gather_rows(keys, rows[:n_u.value])
+
+    @staticmethod
+    def _sorted_values(rt, attrs, perm, dtype, channels):
+        """the attribute rows of a call in the order of its sorted keys, as one [n, channels] device tensor of `dtype`:
+        every frame widened to the call's common format (absent channels 0 on both sides, so their differences are 0),
+        one upload, and the sort's permutation applied on the device"""
+        n = int(sum(a.shape[0] for a in attrs))
+        host = torch.zeros(max(n, 1) * channels * np.dtype(dtype).itemsize, dtype=torch.uint8, pin_memory=True)
+        h = host.numpy()[:n * channels * np.dtype(dtype).itemsize].view(dtype).reshape(n, channels)
+        at = 0
+        for a in attrs:
+            h[at:at + a.shape[0], :a.shape[1]] = a
+            at += a.shape[0]
+        dev = rt.to_device(host)[:h.nbytes].view(torch.uint8 if dtype == np.uint8 else torch.uint16).reshape(n, channels)
+        return rt.gather_rows(dev, perm)
+
+    def distortion(self, frames_a, frames_b, attributes_a=None, attributes_b=None, peak=None):
+        """The D1 (point-to-point) distortion between two sequences of lattice frames, frame by frame, by exact nearest
+        neighbours on the device (pcc_nn_frames; include/pcc.h has the rule) -> one dict per frame:
+
+            points_a, points_b     the rows given (duplicates count, as pc_error counts them)
+            mse_ab, mse_ba         mean over the rows of one side of the squared distance to the nearest point of the
+                                   other side, in lattice units: integer sum / count, in float64
+            max_ab, max_ba         the largest such squared distance, an int
+            d1_psnr                10 log10(3 peak^2 / max(mse_ab, mse_ba)) (metrics.d1_psnr's formula), inf when both
+                                   are 0, None when peak is None
+            attr_mse_ab, attr_mse_ba   with attributes: per channel, the mean squared difference between a row's value
+                                   and the value of its nearest point of the other side (Morton-first among equidistant)
+
+        frames_a, frames_b: as compress takes them, int16 / int32 only, numpy or torch, all on the host or all on this
+        codec's device, the same number on both sides.  float32 frames raise TypeError: pass lattice points — what
+        compress was given, or decompress without voxel= returns; metric distances are these times voxel^2.  A frame
+        pair with points on one side and none on the other raises ValueError naming the frame; two empty frames give
+        0.0 and inf.  Cells of a level of detail compare as their centres: (cells << k) + ((1 << k) >> 1).
+        attributes_a, attributes_b: host uint8 / uint16 [n] or [n, c] per frame, as compress takes them, dtype and
+        channel count equal per frame pair; both sides must then be free of duplicate points (ValueError naming the
+        frame): the typical call compares a lossless decode with a lossy one."""
+        fa, float_a, dev_a = self._check_frames(frames_a)
+        fb, float_b, dev_b = self._check_frames(frames_b)
+        if float_a or float_b:
+            raise TypeError("distortion: float32 frames: pass lattice points (int16 / int32) — the input of compress, or "
+                            "what decompress returns without voxel=; metric distances are lattice distances times voxel^2")
+        if len(fa) != len(fb):
+            raise ValueError(f"distortion: {len(fa)} frames against {len(fb)}")
+        if fa and dev_a != dev_b:
+            raise ValueError("distortion: one side on the host, the other on the device: the frames of a call are all on "
+                             "the host or all on the device")
+        if (attributes_a is None) != (attributes_b is None):
+            raise ValueError("distortion: attributes on one side only")
+        if peak is not None and not (isinstance(peak, (int, float, np.integer, np.floating)) and not isinstance(peak, bool)
+                                     and np.isfinite(peak) and peak > 0):
+            raise ValueError(f"distortion: peak must be a positive number (grid extent - 1), got {peak!r}")
+        attrs_a = attrs_b = None
+        if attributes_a is not None:
+            attrs_a = self._check_attributes(fa, attributes_a)
+            attrs_b = self._check_attributes(fb, attributes_b)
+            for f, (a, b) in enumerate(zip(attrs_a, attrs_b)):
+                if a.dtype != b.dtype or a.shape[1] != b.shape[1]:
+                    raise ValueError(f"frame {f}: {a.dtype} attributes of {a.shape[1]} channels against {b.dtype} of "
+                                     f"{b.shape[1]}: dtype and channel count must be equal")
+        nb = len(fa)
+        sizes_a = [int(a.shape[0]) for a in fa]
+        sizes_b = [int(b.shape[0]) for b in fb]
+        for f, (na, nr) in enumerate(zip(sizes_a, sizes_b)):
+            if (na == 0) != (nr == 0):
+                raise ValueError(f"frame {f}: {na} points against {nr}: the distance to an empty set is undefined")
+        if nb == 0:
+            return []
+        ab = ba = [[0, 0, 0]] * nb
+        sse_ab = sse_ba = None
+        if sum(sizes_a):
+            caller = torch.cuda.current_stream(self.rt.device) if dev_a else None
+            with self._lock, self.rt as rt:
+                ka, pa, ua = self._lattice_keys(rt, fa, dev_a, caller)
+                kb, pb, ub = self._lattice_keys(rt, fb, dev_b, caller)
+                if attrs_a is not None:
+                    self._refuse_duplicates(ka, ua, sizes_a, "frames_a")
+                    self._refuse_duplicates(kb, ub, sizes_b, "frames_b")
+                _, row_ab, ab = rt.nn_frames(ka, ub, nb, want_dist=False, want_row=attrs_a is not None)
+                _, row_ba, ba = rt.nn_frames(kb, ua, nb, want_dist=False, want_row=attrs_a is not None)
+                if attrs_a is not None:
+                    dtype = np.uint16 if any(a.dtype == np.uint16 for a in attrs_a) else np.uint8
+                    channels = max(a.shape[1] for a in attrs_a)
+                    channels = 4 if dtype == np.uint8 or channels > 2 else 2      # rows of 4 or 8 bytes (pcc_gather_rows)
+                    va = self._sorted_values(rt, attrs_a, pa, dtype, channels)
+                    vb = self._sorted_values(rt, attrs_b, pb, dtype, channels)
+                    sse_ab = rt.nn_attr_sse_frames(ka, row_ab, va, vb, nb)
+                    sse_ba = rt.nn_attr_sse_frames(kb, row_ba, vb, va, nb)
+        elif attrs_a is not None:
+            sse_ab = sse_ba = [[0] * 4] * nb
+        report = []
+        for f in range(nb):
+            (ca, sa, ma), (cb, sb, mb) = ab[f], ba[f]
+            rep = {"points_a": sizes_a[f], "points_b": sizes_b[f],
+                   "mse_ab": float(sa) / float(ca) if ca else 0.0, "mse_ba": float(sb) / float(cb) if cb else 0.0,
+                   "max_ab": int(ma), "max_ba": int(mb)}
+            worst = max(rep["mse_ab"], rep["mse_ba"])
+            rep["d1_psnr"] = None if peak is None else (float("inf") if worst == 0.0 else
+                                                       float(10.0 * np.log10(3.0 * float(peak) ** 2 / worst)))
+            if attrs_a is not None:
+                c = attrs_a[f].shape[1]
+                rep["attr_mse_ab"] = [float(s) / float(ca) if ca else 0.0 for s in sse_ab[f][:c]]
+                rep["attr_mse_ba"] = [float(s) / float(cb) if cb else 0.0 for s in sse_ba[f][:c]]
+            report.append(rep)
+        return report
+
+    @staticmethod
+    def _refuse_duplicates(keys, distinct, sizes, side):
+        """ValueError naming the first frame of `side` whose sorted keys hold a duplicate (the distinct count says so)"""
+        if distinct.shape[0] == keys.shape[0]:
+            return
+        counts = np.bincount(((distinct >> 48) & 0xFFFF).cpu().numpy(), minlength=len(sizes))
+        f = next(f for f, (n, u) in enumerate(zip(sizes, counts)) if u < n)
+        raise ValueError(f"frame {f}: {sizes[f] - int(counts[f])} duplicate points in {side}: attributes are compared point by "
+                         "point, so both sides must be free of duplicates (a decoded frame is)")
 
     @staticmethod
     def _named(first, call):

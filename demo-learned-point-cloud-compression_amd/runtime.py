@@ -212,6 +212,40 @@ class Runtime:
                                             (C.c_float * 3)(*[float(v) for v in origin]), _ptr(out)), "pcc_points_to_metric")
         return out
 
+    def nn_frames(self, qkeys, rkeys, n_frames, want_dist=True, want_row=True):
+        """exact nearest neighbours on the lattice, frame by frame (pcc_nn_frames, the rule of include/pcc.h).  qkeys:
+        Morton keys of the queries on the device, any order, duplicates allowed; rkeys: the reference keys, sorted and
+        distinct.  Returns (sqdist, row, stats): sqdist an int64 [n_q] device tensor holding the uint64 squared
+        distances (2^64 - 1 reads as -1: a frame without a reference), row an int32 [n_q] device tensor, the row of
+        rkeys of the nearest point (-1 likewise) — either None when not wanted — and stats, an [n_frames, 3] list of
+        Python ints (count, sum, max per frame).  Synchronises."""
+        n_q, n_r = int(qkeys.shape[0]), int(rkeys.shape[0])
+        sqdist = self.empty((n_q,), torch.int64) if want_dist else None
+        row = self.empty((n_q,), torch.int32) if want_row else None
+        stats = self.empty((n_frames, 3), torch.int64)
+        check(self.lib.pcc_nn_frames(self.ctx, _ptr(qkeys), n_q, _ptr(rkeys), n_r, int(n_frames), _ptr(sqdist), _ptr(row),
+                                     _ptr(stats)), "pcc_nn_frames")
+        return sqdist, row, self._u64_rows(stats)
+
+    def nn_attr_sse_frames(self, qkeys, row, a, b, n_frames):
+        """per frame and channel the sum of (a[i] - b[row[i]])^2 over the frame's queries (pcc_nn_attr_sse_frames): a
+        [n_q, c] and b [n_r, c] uint8 or uint16 device tensors in the order of qkeys and of the reference keys that gave
+        `row`.  Returns an [n_frames, c] list of Python ints.  Synchronises."""
+        if a.dtype != b.dtype or a.dtype not in (torch.uint8, torch.uint16) or a.dim() != 2 or b.dim() != 2 or \
+                a.shape[1] != b.shape[1] or a.shape[0] != qkeys.shape[0] or row.shape[0] != qkeys.shape[0]:
+            raise ValueError(f"nn_attr_sse_frames: values {tuple(a.shape)} {a.dtype} against {tuple(b.shape)} {b.dtype} for "
+                             f"{qkeys.shape[0]} queries")
+        sse = self.empty((n_frames, int(a.shape[1])), torch.int64)
+        check(self.lib.pcc_nn_attr_sse_frames(self.ctx, _ptr(qkeys), _ptr(row), int(qkeys.shape[0]), _ptr(a), _ptr(b),
+                                              int(b.shape[0]), a.element_size(), int(a.shape[1]), int(n_frames), _ptr(sse)),
+              "pcc_nn_attr_sse_frames")
+        return self._u64_rows(sse)
+
+    def _u64_rows(self, t):
+        """an int64 device tensor holding uint64 values, written on this runtime's stream -> nested lists of Python ints"""
+        self.sync()
+        return t.cpu().numpy().view(np.uint64).tolist()
+
     def linear_keys(self, coords):
         n = coords.shape[0]
         keys = self.empty((n,), torch.int64)

@@ -921,6 +921,60 @@ int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_version,
                   int32_t* h_bpv, int32_t* h_channels, int64_t* h_points,
                   int32_t* h_max_error, int32_t* h_scalable, int32_t* h_lod);
 
+/* ---- exact nearest neighbours on the lattice: the D1 metric (csrc/nn.hip) -- */
+
+/* The rule (tests/nn_ref.py restates it in numpy).  For a frame f there are
+ * two sets of lattice points, every coordinate in [-32768, 32767]:
+ *   queries    Q_f, a multiset: duplicates count, as pc_error counts them;
+ *   reference  R_f, distinct points in Morton order.
+ * For q in Q_f
+ *   d2(q)  = min over r in R_f of (qx-rx)^2 + (qy-ry)^2 + (qz-rz)^2, an
+ *            unsigned 64-bit integer (at most 3 * 65535^2 = 12 884 508 675,
+ *            above 2^32);
+ *   row(q) = the row of the minimiser among the call's sorted reference keys
+ *            (counted over the whole call, not from the frame's first row);
+ *            among equidistant minimisers the SMALLEST row, the Morton-first.
+ * Only points of the same frame are candidates.  Per frame: count = |Q_f|,
+ * sum = the sum of d2(q) (uint64: 2^27 rows * 2^34 < 2^64), max = the largest
+ * d2(q).  A frame with queries and an empty reference: each such query gets
+ * d2 = 2^64 - 1 and row = -1, and the frame's three statistics are 0.
+ *
+ *   pcc_nn_frames : d_qkeys: Morton keys of the queries (pcc_morton_keys_frames),
+ *     in any order, duplicates allowed; d_rkeys: the reference keys, sorted and
+ *     distinct, as pcc_octree_encode_frames takes them.  Outputs, each
+ *     nullable: d_sqdist [n_q], d_row [n_q], d_stats [n_frames][3] (count,
+ *     sum, max; zeroed by the call).  One thread per query walks the implicit
+ *     octree of the sorted keys of its frame without a stack; the result does
+ *     not depend on the order of the queries, sorted queries are faster.
+ *     Checked before the search is launched (one synchronisation): n_frames in
+ *     1 .. 65535 and n_q, n_r <= 2^27 (PCC_E_ARG); a reference or query key
+ *     whose frame index is not below n_frames (PCC_E_RANGE); reference keys
+ *     not sorted (PCC_E_ARG) or not distinct (PCC_E_DUP), as
+ *     pcc_octree_encode_frames reports them; pcc_last_error says which.
+ *     n_q = 0 and n_r = 0 launch no search (n_r = 0 fills the sentinels).
+ *   pcc_nn_attr_sse_frames : the attribute side of the same pairing.  d_row:
+ *     pcc_nn_frames' rows for d_qkeys; d_a [n_q][channels] and d_b
+ *     [n_r][channels]: values of bpv = 1 (uint8) or 2 (uint16) bytes, 1 .. 4
+ *     channels, row i of d_a belonging to query i and row j of d_b to
+ *     reference row j.  d_sse [n_frames][channels] (zeroed by the call):
+ *     the sum over the frame's queries of (a[i][ch] - b[row[i]][ch])^2, uint64.
+ *     A query whose row is -1 adds nothing.
+ *   pcc_nn_replay_host : host only, no ctx.  The traversal of pcc_nn_frames,
+ *     the same function compiled for the host, run query by query on the
+ *     calling thread: d2, row and the nodes each query tried (cells tested and
+ *     points measured), each output nullable.  For counting nodes and for
+ *     checks where there is no device; not a product path. */
+int pcc_nn_frames(pcc_ctx* ctx, const uint64_t* d_qkeys, int64_t n_q,
+                  const uint64_t* d_rkeys, int64_t n_r, int n_frames,
+                  uint64_t* d_sqdist, int32_t* d_row, uint64_t* d_stats);
+int pcc_nn_attr_sse_frames(pcc_ctx* ctx, const uint64_t* d_qkeys,
+                           const int32_t* d_row, int64_t n_q, const void* d_a,
+                           const void* d_b, int64_t n_r, int bpv, int channels,
+                           int n_frames, uint64_t* d_sse);
+int pcc_nn_replay_host(const uint64_t* h_qkeys, int64_t n_q,
+                       const uint64_t* h_rkeys, int64_t n_r, uint64_t* h_sqdist,
+                       int32_t* h_row, uint32_t* h_nodes);
+
 /* ---- whole-GOP entry points ------------------------------ */
 
 /* replaces: CompressionPipeline.compress() (sender/encoder/codec_pipeline.py:
