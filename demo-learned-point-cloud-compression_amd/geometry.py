@@ -64,6 +64,7 @@ import ctypes as C
 import re
 import struct
 import threading
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -73,6 +74,32 @@ from .runtime import Runtime, _ptr
 
 MAX_FRAMES = 65535      # the batch-index range of pcc_morton_keys
 MAX_LOD = 15            # levels of detail 0 .. 15 (csrc/octree2_blob.h)
+
+
+def _ends(sizes):
+    """[0, n_0, n_0 + n_1, ...]: where the rows of every frame of a call begin, and behind them the call's total"""
+    return np.cumsum([0] + list(sizes)).tolist()
+
+
+def _split(whole, sizes):
+    """the rows of a call, frame behind frame -> one view of `whole` per frame"""
+    ends = _ends(sizes)
+    return [whole[a:b] for a, b in zip(ends[:-1], ends[1:])]
+
+
+class _Front(NamedTuple):
+    """What the front end of a call (GeometryCodec._front: stage, keys, sorted / distinct) hands to compress and to
+    distortion.  Nothing to code (n_keep == 0): the fields behind n_keep stay at their defaults."""
+    nb: int                      # frames
+    sizes: list                  # input rows per frame
+    n: int                       # input rows of the call
+    n_keep: int                  # rows that were not dropped: the sorted keys in front of the dropped rows' keys
+    offsets: object = None       # the upload, the int64 frame offsets first: rows_index reads them on the device
+    perm: object = None          # sort_pairs' permutation of all n keys
+    sorted_keys: object = None   # the n_keep sorted keys with their duplicates, under the lod mask
+    rows: object = None          # pcc_unique_rows: the first row of every run of equal keys
+    n_unique: int = 0
+    keys: object = None          # the distinct keys (sorted_keys itself where there is no duplicate)
 
 
 class GeometryCodec:
@@ -254,89 +281,109 @@ class GeometryCodec:
             return out[0] if len(out) == 1 else out
         if nb == 0:
             return result([], [], [])
+        caller = torch.cuda.current_stream(self.rt.device) if on_device else None      # inside `with rt` it is the codec's
+        with self._lock, self.rt as rt:
+            front = self._front(rt, frames, is_float, on_device, caller, "GeometryCodec.compress", lod, voxel, origin,
+                                invalid == "drop")
+            if front.n_keep == 0:
+                return result(*self._nothing_coded(rt, front, attrs, version, max_error, return_index, on_device))
+            blobs = rt.octree_encode_frames(front.keys, nb, 3 * lod)
+            attr_blobs = index = None
+            if attrs is not None:
+                attr_blobs = self._encode_attributes(rt, attrs, blobs, front, version, 3 * lod, max_error)
+            if return_index:
+                first_run = torch.empty(nb, dtype=torch.int64, pin_memory=True)
+                np.cumsum([0] + [struct.unpack_from("<I", b, 4)[0] for b in blobs[:-1]], out=first_run.numpy())
+                index = rt.rows_index(front.perm, front.n_keep, front.rows, front.n_unique, front.offsets.data_ptr(),
+                                      rt.to_device(first_run), nb)
+                index = self._split_index(index, front.sizes, on_device)
+            return result(blobs, attr_blobs, index)
+
+    def _front(self, rt, frames, is_float, on_device, caller, where, lod=0, voxel=None, origin=None, drop=False):
+        """the frames of a call -> _Front: stage, keys, sorted / distinct.  Called under `with self._lock, self.rt`;
+        `caller` is the stream that was current before that block (device frames), `where` the origin an error names."""
         sizes = [int(a.shape[0]) for a in frames]
         n = int(sum(sizes))
-        # one upload, the rows as they come (6 or 12 B per point) behind the frame offsets; the frame index and the
-        # widening to keys happen on the device (pcc_morton_keys_frames); device frames send the offsets alone
+        if n == 0:
+            return _Front(len(frames), sizes, 0, 0)
+        offsets, xyz, dtype = self._stage(rt, frames, sizes, is_float, on_device, caller)
+        keys, n_keep, flag = self._keys(rt, offsets, xyz, dtype, n, len(frames), where, voxel, origin, drop)
+        return self._distinct(rt, _Front(len(frames), sizes, n, n_keep, offsets), keys, flag, lod, where)
+
+    @staticmethod
+    def _stage(rt, frames, sizes, is_float, on_device, caller):
+        """one upload, the rows as they come (6 or 12 B per point) at the next 16-byte boundary behind the int64 frame
+        offsets; the frame index and the widening to keys happen on the device.  Device frames send the offsets alone
+        and are concatenated once on the device.  -> (the upload, the rows on the device, their numpy dtype)"""
         if is_float:
             dtype = np.float32
         else:
             dtype = np.int16 if all(a.element_size() == 2 if on_device else a.dtype == np.int16 for a in frames) else np.int32
-        offs_b = 8 * (nb + 1)
+        offs_b = 8 * (len(frames) + 1)
         rows_at = (offs_b + 15) // 16 * 16
-        host_rows = 0 if on_device else 3 * n * np.dtype(dtype).itemsize
+        host_rows = 0 if on_device else 3 * sum(sizes) * np.dtype(dtype).itemsize
         host = torch.empty(rows_at + host_rows, dtype=torch.uint8, pin_memory=True)
         h = host.numpy()
         np.cumsum([0] + sizes, out=h[:offs_b].view(np.int64))
-        if n and not on_device:
-            np.concatenate(frames, axis=0, out=h[rows_at:].view(dtype).reshape(n, 3))
-        if on_device:
-            caller = torch.cuda.current_stream(self.rt.device)
-        with self._lock, self.rt as rt:
-            if n == 0:
-                blobs = rt.octree_encode_frames(rt.empty((0,), torch.int64), nb)
-                index = [rt.empty((0,), torch.int32) if on_device else np.zeros(0, np.int32) for _ in range(nb)]
-                return result(blobs, None if attrs is None else
-                              self._encode_attributes(rt, attrs, sizes, blobs, None, None, 0, version, max_error=max_error),
-                              index)
-            dev = rt.to_device(host)
-            if on_device:      # one device-side concatenation, behind whatever the caller's stream still does to them
-                rt.stream.wait_stream(caller)
-                tdtype = {np.float32: torch.float32, np.int16: torch.int16, np.int32: torch.int32}[dtype]
-                xyz = torch.cat([a.detach().to(tdtype) for a in frames], 0).contiguous()
-                xyz_ptr = xyz.data_ptr()
-            else:
-                xyz_ptr = dev.data_ptr() + rows_at
-            n_keep = n
-            if is_float:
-                keys, status = rt.morton_keys_frames_f32(xyz_ptr, n, dev.data_ptr(), nb, voxel, origin, invalid == "drop")
-                bits, dropped = status.tolist()      # one synchronisation, in place of the flag's below
-                if bits & 2:
-                    raise PccError(PCC_E_RANGE, "GeometryCodec.compress", "non-finite coordinate (NaN or Inf) in a frame; "
-                                   "invalid='drop' leaves such rows out")
-                if bits & 1:
-                    raise PccError(PCC_E_RANGE, "GeometryCodec.compress", "coordinate outside [-32768, 32767] after "
-                                   "rint((x - origin) / voxel): a finite point off the grid")
-                n_keep = n - dropped
-            else:
-                keys = rt.empty((n,), torch.int64)
-                flag = torch.zeros(1, dtype=torch.int32, device=rt.device)
-                check(rt.lib.pcc_morton_keys_frames(rt.ctx, C.c_void_p(xyz_ptr), np.dtype(dtype).itemsize, n,
-                                                    C.c_void_p(dev.data_ptr()), nb, _ptr(keys), _ptr(flag)),
-                      "pcc_morton_keys_frames")
-            perm = rt.sort_pairs(keys)
-            if n_keep < n:      # the dropped rows' keys sorted behind every frame's: nothing below sees them
-                keys = keys[:n_keep]
-            if n_keep == 0:
-                blobs = rt.octree_encode_frames(rt.empty((0,), torch.int64), nb)
-                attr_blobs = None if attrs is None else self._encode_attributes(rt, attrs, sizes, blobs, None, None, 0, version,
-                                                                                n_kept=0, max_error=max_error)
-                index = None
-                if return_index:
-                    index = self._split_index(torch.full((n,), -1, dtype=torch.int32, device=rt.device), sizes, on_device)
-                return result(blobs, attr_blobs, index)
-            if lod:      # a cell's keys differ in their low 3 lod bits only (the batch index above bit 48 stays)
-                keys.bitwise_and_(-(1 << (3 * lod)))
-            # duplicates (np.unique): the first row of every run of equal keys
-            rows = rt.empty((n_keep,), torch.int32)
-            n_u = C.c_int64(0)
-            check(rt.lib.pcc_unique_rows(rt.ctx, _ptr(rt.keys_to_coords(keys)), n_keep, _ptr(rows), C.byref(n_u)),
-                  "pcc_unique_rows")
-            if not is_float and int(flag.item()) != 0:      # read behind the synchronisation of pcc_unique_rows
-                raise PccError(PCC_E_RANGE, "GeometryCodec.compress", "coordinate outside [-32768, 32767]")
-            if n_u.value < n_keep:
-                keys = rt.gather_rows(keys, rows[:n_u.value])
-            blobs = rt.octree_encode_frames(keys, nb, 3 * lod)
-            attr_blobs = index = None
-            if attrs is not None:
-                attr_blobs = self._encode_attributes(rt, attrs, sizes, blobs, perm, rows, n_u.value, version, keys, 3 * lod,
-                                                     n_keep if n_keep < n else None, max_error)
-            if return_index:
-                first_run = torch.empty(nb, dtype=torch.int64, pin_memory=True)
-                np.cumsum([0] + [struct.unpack_from("<I", b, 4)[0] for b in blobs[:-1]], out=first_run.numpy())
-                index = rt.rows_index(perm, n_keep, rows, n_u.value, dev.data_ptr(), rt.to_device(first_run), nb)
-                index = self._split_index(index, sizes, on_device)
-            return result(blobs, attr_blobs, index)
+        if not on_device:
+            np.concatenate(frames, axis=0, out=h[rows_at:].view(dtype).reshape(-1, 3))
+        dev = rt.to_device(host)
+        if not on_device:
+            return dev, dev[rows_at:], dtype
+        rt.stream.wait_stream(caller)      # behind whatever the caller's stream still does to the frames
+        tdtype = {np.float32: torch.float32, np.int16: torch.int16, np.int32: torch.int32}[dtype]
+        return dev, torch.cat([a.detach().to(tdtype) for a in frames], 0).contiguous(), dtype
+
+    @staticmethod
+    def _keys(rt, offsets, xyz, dtype, n, nb, where, voxel, origin, drop):
+        """-> (the call's n Morton keys, frame index above bit 48; n_keep; the integer kernel's range flag, not read
+        yet, or None).  float32 reads its status here, behind one synchronisation in place of the flag's."""
+        if dtype == np.float32:
+            keys, status = rt.morton_keys_frames_f32(xyz.data_ptr(), n, offsets.data_ptr(), nb, voxel, origin, drop)
+            bits, dropped = status.tolist()
+            if bits & 2:
+                raise PccError(PCC_E_RANGE, where, "non-finite coordinate (NaN or Inf) in a frame; "
+                               "invalid='drop' leaves such rows out")
+            if bits & 1:
+                raise PccError(PCC_E_RANGE, where, "coordinate outside [-32768, 32767] after "
+                               "rint((x - origin) / voxel): a finite point off the grid")
+            return keys, n - dropped, None
+        keys = rt.empty((n,), torch.int64)
+        flag = torch.zeros(1, dtype=torch.int32, device=rt.device)
+        check(rt.lib.pcc_morton_keys_frames(rt.ctx, C.c_void_p(xyz.data_ptr()), np.dtype(dtype).itemsize, n,
+                                            C.c_void_p(offsets.data_ptr()), nb, _ptr(keys), _ptr(flag)),
+              "pcc_morton_keys_frames")
+        return keys, n, flag
+
+    @staticmethod
+    def _distinct(rt, front, keys, flag, lod, where):
+        """sort, cut to the kept rows, lod mask, duplicates (np.unique) -> `front` filled in"""
+        perm = rt.sort_pairs(keys)
+        n_keep = front.n_keep
+        if n_keep < front.n:      # the dropped rows' keys sorted behind every frame's: nothing below sees them
+            keys = keys[:n_keep]
+        if n_keep == 0:
+            return front
+        if lod:      # a cell's keys differ in their low 3 lod bits only (the batch index above bit 48 stays)
+            keys.bitwise_and_(-(1 << (3 * lod)))
+        rows = rt.empty((n_keep,), torch.int32)      # the first row of every run of equal keys
+        n_u = C.c_int64(0)
+        check(rt.lib.pcc_unique_rows(rt.ctx, _ptr(rt.keys_to_coords(keys)), n_keep, _ptr(rows), C.byref(n_u)),
+              "pcc_unique_rows")
+        if flag is not None and int(flag.item()) != 0:      # read behind the synchronisation of pcc_unique_rows
+            raise PccError(PCC_E_RANGE, where, "coordinate outside [-32768, 32767]")
+        distinct = keys if n_u.value == n_keep else rt.gather_rows(keys, rows[:n_u.value])
+        return front._replace(perm=perm, sorted_keys=keys, rows=rows, n_unique=n_u.value, keys=distinct)
+
+    def _nothing_coded(self, rt, front, attrs, version, max_error, return_index, on_device):
+        """(blobs, attribute blobs, index) of a call none of whose rows is coded: the empty blobs, the attribute blobs
+        of frames without points, and -1 for every input row"""
+        blobs = rt.octree_encode_frames(rt.empty((0,), torch.int64), front.nb)
+        attr_blobs = None if attrs is None else self._encode_attributes(rt, attrs, blobs, front, version, 0, max_error)
+        if not return_index:
+            return blobs, attr_blobs, None
+        index = torch.full((front.n,), -1, dtype=torch.int32, device=rt.device)
+        return blobs, attr_blobs, self._split_index(index, front.sizes, on_device)
 
     def _split_index(self, index, sizes, on_device):
         """the call's index [n] on the device -> one int32 [n_f] per frame: views of it (device frames), or of one
@@ -345,12 +392,10 @@ class GeometryCodec:
             self.rt.sync()      # the caller's stream may read it at once
         else:
             index = index.cpu().numpy()
-        ends = np.cumsum([0] + list(sizes)).tolist()
-        return [index[a:b] for a, b in zip(ends[:-1], ends[1:])]
+        return _split(index, sizes)
 
     @staticmethod
-    def _encode_attributes(rt, attrs, sizes, blobs, perm, rows, n_unique, version=1, keys=None, key_shift=0, n_kept=None,
-                           max_error=0):
+    def _encode_attributes(rt, attrs, blobs, front, version, key_shift, max_error):
         # the values as they come, frame by frame at 16-byte offsets, in one upload; the merge into Morton order
         # happens on the device from the sort's permutation and the runs of equal keys
         offs, at = [], 0
@@ -364,9 +409,9 @@ class GeometryCodec:
         values = rt.to_device(host) if at else None
         formats = [a.dtype.itemsize | (a.shape[1] << 8) for a in attrs]
         points = [struct.unpack_from("<I", b, 4)[0] for b in blobs]
-        row_offsets = np.cumsum([0] + list(sizes)).tolist()
-        return rt.attr_encode_frames(values, offs, formats, row_offsets, points, perm, rows, n_unique, version, keys, key_shift,
-                                     n_kept, max_error)
+        n_kept = front.n_keep if front.n_keep < front.n else None      # None: no row was dropped
+        return rt.attr_encode_frames(values, offs, formats, _ends(front.sizes), points, front.perm, front.rows, front.n_unique,
+                                     version, front.keys, key_shift, n_kept, max_error)
 
     def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0, *, voxel=None, origin=(0.0, 0.0, 0.0)):
         """version-2 blobs -> a list of int32 [n_f, 3] point sets in Morton order: numpy arrays (output="numpy") or
@@ -422,9 +467,7 @@ class GeometryCodec:
                 return frames, rt.attr_decode_frames(attr_blobs, points=[f.shape[0] for f in frames],
                                                      device=(output == "device"))
             if output == "numpy" and voxel is None:      # one copy of the call's cells to the host, split as the device tensor is
-                host = torch.cat(cells).cpu().numpy()
-                ends = np.cumsum([0] + [c.shape[0] for c in cells])
-                frames = [host[a:b] for a, b in zip(ends[:-1], ends[1:])]
+                frames = _split(torch.cat(cells).cpu().numpy(), [c.shape[0] for c in cells])
             attrs = [None] * len(blobs)
             f = 0
             while f < len(blobs):      # runs of frames of one version, each in one call
@@ -453,45 +496,7 @@ class GeometryCodec:
             host.copy_(pts, non_blocking=True)
             pts = host.numpy()
         rt.sync()      # the host copy is complete; a device result may be read from the caller's stream at once
-        ends = np.cumsum([0] + [int(c.shape[0]) for c in cells]).tolist()
-        return [pts[a:b] for a, b in zip(ends[:-1], ends[1:])]
-
-    def _lattice_keys(self, rt, frames, on_device, caller):
-        """integer frames of a call -> (keys, perm, distinct): the call's Morton keys, frame index above bit 48, sorted
-        with their duplicates; the sort's permutation; the distinct keys (`keys` itself where there is no duplicate).
-        The front of compress for integer frames: one upload, keys, sort, distinct."""
-        nb = len(frames)
-        sizes = [int(a.shape[0]) for a in frames]
-        n = int(sum(sizes))
-        if n == 0:
-            none = rt.empty((0,), torch.int64)
-            return none, rt.empty((0,), torch.int32), none
-        dtype = np.int16 if all(a.element_size() == 2 if on_device else a.dtype == np.int16 for a in frames) else np.int32
-        offs_b = 8 * (nb + 1)
-        rows_at = (offs_b + 15) // 16 * 16
-        host = torch.empty(rows_at + (0 if on_device else 3 * n * np.dtype(dtype).itemsize), dtype=torch.uint8, pin_memory=True)
-        h = host.numpy()
-        np.cumsum([0] + sizes, out=h[:offs_b].view(np.int64))
-        if not on_device:
-            np.concatenate(frames, axis=0, out=h[rows_at:].view(dtype).reshape(n, 3))
-        dev = rt.to_device(host)
-        if on_device:
-            rt.stream.wait_stream(caller)
-            xyz = torch.cat([a.detach().to(torch.int16 if dtype == np.int16 else torch.int32) for a in frames], 0).contiguous()
-            xyz_ptr = xyz.data_ptr()
-        else:
-            xyz_ptr = dev.data_ptr() + rows_at
-        keys = rt.empty((n,), torch.int64)
-        flag = torch.zeros(1, dtype=torch.int32, device=rt.device)
-        check(rt.lib.pcc_morton_keys_frames(rt.ctx, C.c_void_p(xyz_ptr), np.dtype(dtype).itemsize, n, C.c_void_p(dev.data_ptr()),
-                                            nb, _ptr(keys), _ptr(flag)), "pcc_morton_keys_frames")
-        perm = rt.sort_pairs(keys)
-        rows = rt.empty((n,), torch.int32)
-        n_u = C.c_int64(0)
-        check(rt.lib.pcc_unique_rows(rt.ctx, _ptr(rt.keys_to_coords(keys)), n, _ptr(rows), C.byref(n_u)), "pcc_unique_rows")
-        if int(flag.item()) != 0:      # read behind the synchronisation of pcc_unique_rows
-            raise PccError(PCC_E_RANGE, "GeometryCodec.distortion", "coordinate outside [-32768, 32767]")
-        return keys, perm, keys if n_u.value == n else rt.gather_rows(keys, rows[:n_u.value])
+        return _split(pts, [int(c.shape[0]) for c in cells])
 
     @staticmethod
     def _sorted_values(rt, attrs, perm, dtype, channels):
@@ -565,21 +570,21 @@ class GeometryCodec:
         if sum(sizes_a):
             caller = torch.cuda.current_stream(self.rt.device) if dev_a else None
             with self._lock, self.rt as rt:
-                ka, pa, ua = self._lattice_keys(rt, fa, dev_a, caller)
-                kb, pb, ub = self._lattice_keys(rt, fb, dev_b, caller)
+                front_a = self._front(rt, fa, False, dev_a, caller, "GeometryCodec.distortion")
+                front_b = self._front(rt, fb, False, dev_b, caller, "GeometryCodec.distortion")
                 if attrs_a is not None:
-                    self._refuse_duplicates(ka, ua, sizes_a, "frames_a")
-                    self._refuse_duplicates(kb, ub, sizes_b, "frames_b")
-                _, row_ab, ab = rt.nn_frames(ka, ub, nb, want_dist=False, want_row=attrs_a is not None)
-                _, row_ba, ba = rt.nn_frames(kb, ua, nb, want_dist=False, want_row=attrs_a is not None)
+                    self._refuse_duplicates(front_a, "frames_a")
+                    self._refuse_duplicates(front_b, "frames_b")
+                _, row_ab, ab = rt.nn_frames(front_a.sorted_keys, front_b.keys, nb, want_dist=False, want_row=attrs_a is not None)
+                _, row_ba, ba = rt.nn_frames(front_b.sorted_keys, front_a.keys, nb, want_dist=False, want_row=attrs_a is not None)
                 if attrs_a is not None:
                     dtype = np.uint16 if any(a.dtype == np.uint16 for a in attrs_a) else np.uint8
                     channels = max(a.shape[1] for a in attrs_a)
                     channels = 4 if dtype == np.uint8 or channels > 2 else 2      # rows of 4 or 8 bytes (pcc_gather_rows)
-                    va = self._sorted_values(rt, attrs_a, pa, dtype, channels)
-                    vb = self._sorted_values(rt, attrs_b, pb, dtype, channels)
-                    sse_ab = rt.nn_attr_sse_frames(ka, row_ab, va, vb, nb)
-                    sse_ba = rt.nn_attr_sse_frames(kb, row_ba, vb, va, nb)
+                    va = self._sorted_values(rt, attrs_a, front_a.perm, dtype, channels)
+                    vb = self._sorted_values(rt, attrs_b, front_b.perm, dtype, channels)
+                    sse_ab = rt.nn_attr_sse_frames(front_a.sorted_keys, row_ab, va, vb, nb)
+                    sse_ba = rt.nn_attr_sse_frames(front_b.sorted_keys, row_ba, vb, va, nb)
         elif attrs_a is not None:
             sse_ab = sse_ba = [[0] * 4] * nb
         report = []
@@ -599,11 +604,12 @@ class GeometryCodec:
         return report
 
     @staticmethod
-    def _refuse_duplicates(keys, distinct, sizes, side):
+    def _refuse_duplicates(front, side):
         """ValueError naming the first frame of `side` whose sorted keys hold a duplicate (the distinct count says so)"""
-        if distinct.shape[0] == keys.shape[0]:
+        if front.n_unique == front.n_keep:
             return
-        counts = np.bincount(((distinct >> 48) & 0xFFFF).cpu().numpy(), minlength=len(sizes))
+        sizes = front.sizes
+        counts = np.bincount(((front.keys >> 48) & 0xFFFF).cpu().numpy(), minlength=len(sizes))
         f = next(f for f, (n, u) in enumerate(zip(sizes, counts)) if u < n)
         raise ValueError(f"frame {f}: {sizes[f] - int(counts[f])} duplicate points in {side}: attributes are compared point by "
                          "point, so both sides must be free of duplicates (a decoded frame is)")
