@@ -18,14 +18,20 @@ def unpack_colors(xyzrgba):
     return np.stack([((int_colors >> (8 * i)) & 0xFF) for i in range(3)], axis=-1).reshape(-1, 3)
 
 
+def valid_mask(xyzrgba, depth_clip=1.4):
+    """capturer.py:96-100: finite and within the depth clip.  np.linalg.norm on float32 rows is
+    sqrt((x*x + y*y) + z*z) with every step rounded to float32."""
+    points = np.asarray(xyzrgba, dtype=np.float32)[:, :3]
+    with np.errstate(invalid="ignore", over="ignore"):
+        distances = np.linalg.norm(points, axis=1)
+        return np.isfinite(points).all(axis=1) & (distances <= np.float32(depth_clip))
+
+
 def voxelize(xyzrgba, depth_clip=1.4, voxel_size=0.005, max_points=None):
     data = np.asarray(xyzrgba, dtype=np.float32)
     points = data[:, :3]
     colors = unpack_colors(data)
-    # capturer.py:96-100
-    with np.errstate(invalid="ignore", over="ignore"):
-        distances = np.linalg.norm(points, axis=1)
-        valid = np.isfinite(points).all(axis=1) & (distances <= np.float32(depth_clip))
+    valid = valid_mask(data, depth_clip)
     points, colors = points[valid], colors[valid]
     if points.shape[0] == 0:
         return {"points": np.zeros((0, 3), np.int16), "colors": np.zeros((0, 3), np.float64)}
@@ -72,8 +78,7 @@ def voxelize_open3d_semantics(xyzrgba, depth_clip=1.4, voxel_size=0.005):
     restatement above on inputs where several Open3D voxels round to the same integer voxel."""
     data = np.asarray(xyzrgba, dtype=np.float32)
     points, colors = data[:, :3], unpack_colors(data)
-    with np.errstate(invalid="ignore", over="ignore"):
-        valid = np.isfinite(points).all(axis=1) & (np.linalg.norm(points, axis=1) <= np.float32(depth_clip))
+    valid = valid_mask(data, depth_clip)
     p64, c64 = points[valid].astype(np.float64), colors[valid].astype(np.float64) / 255.0
     vs = np.float64(voxel_size)
     vmb = p64.min(axis=0) - vs * 0.5
