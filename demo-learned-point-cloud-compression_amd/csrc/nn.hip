@@ -23,11 +23,10 @@
 // Statistics: after the walk the wave's lanes meet again; per frame present in the wave one reduction over the lanes
 // (shuffles) and then three 64-bit atomics from one lane.  Sorted queries of one frame: one round per wave.
 #include "common.h"
+#include "nn_cells.h"
 #include <algorithm>
 
 static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
-#define NN_KEY48 0xFFFFFFFFFFFFull
 
 // bit 0: equal neighbours, bit 1: descending neighbours, bit 2: a reference key's frame index >= n_frames,
 // bit 3: a query key's frame index >= n_frames
@@ -62,20 +61,6 @@ __global__ __launch_bounds__(64) void k_nn_offsets(const uint64_t* __restrict__ 
     if (rkeys[mid] < want) lo = mid + 1; else hi = mid;
   }
   offs[f] = lo;
-}
-
-__host__ __device__ static inline uint32_t nn_sq(uint32_t a, uint32_t b) {
-  const uint32_t d = a > b ? a - b : b - a;      // at most 65535: the square fits 32 bits
-  return d * d;
-}
-// the gap between coordinate q and the cell of edge 2^L that holds coordinate c, squared
-__host__ __device__ static inline uint32_t nn_gap_sq(uint32_t q, uint32_t c, int L) {
-  const uint32_t lo = (c >> L) << L, hi = lo | ((1u << L) - 1u);
-  const uint32_t g = q < lo ? lo - q : (q > hi ? q - hi : 0u);
-  return g * g;
-}
-__host__ __device__ static inline uint64_t nn_d2(uint32_t qx, uint32_t qy, uint32_t qz, uint64_t k) {
-  return (uint64_t)nn_sq(qx, pcc_compact3(k >> 2)) + nn_sq(qy, pcc_compact3(k >> 1)) + nn_sq(qz, pcc_compact3(k));
 }
 
 // the search of one query among the rows [flo, fhi) of its frame, flo < fhi: seed and walk as described above.

@@ -56,6 +56,12 @@ pc_error, by exact nearest neighbours on the device; lattice frames from the hos
     cells = codec.decompress([b[:nbytes]], lod=2)[0]
     rep = codec.distortion([pts], [(cells << 2) + 2], peak=1023)     # rep[0]: mse_ab, mse_ba, max_ab, max_ba, d1_psnr
     rep = codec.distortion(frames, lossy, attributes_a=attrs, attributes_b=lossy_attrs)      # + attr_mse_ab / _ba
+    rep = codec.distortion(frames, lossy, normals_a="estimate", peak=1023)      # + d2_mse_ab / _ba, d2_psnr (point-to-plane)
+
+Surface normals (include/pcc.h has the rule): per point the eigenvector of the smallest eigenvalue of the scatter
+matrix of its k nearest neighbours, found exactly on the device; for shading, registration and the D2 figures above.
+
+    normals = codec.normals(frames, k=16, viewpoint=(0, 0, 0))      # float32 [n_f, 3] per frame, row i = input row i
 
 One Runtime (ctx + stream) per codec; calls on the same instance are serialised, instances on different threads run
 side by side.
@@ -513,7 +519,99 @@ class GeometryCodec:
         dev = rt.to_device(host)[:h.nbytes].view(torch.uint8 if dtype == np.uint8 else torch.uint16).reshape(n, channels)
         return rt.gather_rows(dev, perm)
 
-    def distortion(self, frames_a, frames_b, attributes_a=None, attributes_b=None, peak=None):
+    @staticmethod
+    def _check_k(k, name):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 3 <= k <= 32:
+            raise ValueError(f"{name} must be an integer in 3 .. 32, got {k!r}")
+        return int(k)
+
+    @staticmethod
+    def _frame_counts(keys, nb):
+        """the distinct points of every frame of a call, from the frame index of its distinct keys"""
+        return np.bincount(((keys >> 48) & 0xFFFF).to(torch.int32).cpu().numpy(), minlength=nb)
+
+    @staticmethod
+    def _refuse_few(front, where):
+        """ValueError naming the first frame with 1 or 2 distinct points: three points and more span a plane"""
+        for f, u in enumerate(GeometryCodec._frame_counts(front.keys, front.nb)):
+            if 0 < u < 3:
+                raise ValueError(f"frame {f}: {int(u)} distinct points in {where}: a normal needs at least 3")
+
+    def normals(self, frames, k=16, viewpoint=None, output="numpy"):
+        """Surface normals of lattice frames, estimated on the device (pcc_knn_frames; include/pcc.h has the rule) -> one
+        float32 [n_f, 3] per frame, row i the unit normal of input row i: the eigenvector of the smallest eigenvalue of
+        the scatter matrix of the point's k nearest neighbours among the frame's distinct points (the point itself
+        included; exact, ties to the Morton-first point).  Duplicate rows share their point's normal.
+        frames: as distortion takes them, int16 / int32, numpy or torch, all on the host or all on this codec's device;
+        float32 frames raise TypeError: pass lattice points.  k: an integer in 3 .. 32 (ValueError).  viewpoint: three
+        integers in lattice units (the sensor): every normal is flipped to n . (viewpoint - p) >= 0; None leaves the sign
+        unspecified.  output: "numpy" arrays, or "device": views of one tensor on this codec's device.  An empty frame
+        gives [0, 3]; a frame with 1 or 2 distinct points raises ValueError naming the frame."""
+        k = self._check_k(k, "k")
+        if viewpoint is not None:
+            try:
+                vp = [v for v in viewpoint]
+            except TypeError:
+                vp = []
+            if len(vp) != 3 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and abs(int(v)) < 1 << 30
+                                       for v in vp):
+                raise ValueError(f"viewpoint must be three integers in lattice units, got {viewpoint!r}")
+            viewpoint = [int(v) for v in vp]
+        if output not in ("numpy", "device"):
+            raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
+        frames, is_float, on_device = self._check_frames(frames)
+        if is_float:
+            raise TypeError("normals: float32 frames: pass lattice points (int16 / int32) — the input of compress, or "
+                            "what decompress returns without voxel=")
+        nb = len(frames)
+        if nb == 0:
+            return []
+        sizes = [int(a.shape[0]) for a in frames]
+        if sum(sizes) == 0:
+            none = torch.empty((0, 3), dtype=torch.float32, device=self.rt.device) if output == "device" else \
+                np.zeros((0, 3), np.float32)
+            return [none[:0] for _ in sizes]
+        caller = torch.cuda.current_stream(self.rt.device) if on_device else None
+        with self._lock, self.rt as rt:
+            front = self._front(rt, frames, False, on_device, caller, "GeometryCodec.normals")
+            self._refuse_few(front, "frames")
+            distinct = rt.knn_frames(front.keys, nb, k, viewpoint=viewpoint)[3]
+            # the distinct row of every input row: rows_index with no frame's rows taken off
+            index = rt.rows_index(front.perm, front.n_keep, front.rows, front.n_unique, front.offsets.data_ptr(),
+                                  torch.zeros(nb, dtype=torch.int64, device=rt.device), nb)
+            out = rt.gather_rows(distinct, index)
+            if output == "numpy":
+                host = torch.empty(out.shape, dtype=torch.float32, pin_memory=True)
+                host.copy_(out, non_blocking=True)
+                out = host.numpy()
+            rt.sync()      # the host copy is complete; a device result may be read from the caller's stream at once
+            return _split(out, sizes)
+
+    @staticmethod
+    def _check_normals(frames, normals):
+        """given normals: one finite float32 [n_f, 3] host array per frame"""
+        normals = list(normals)
+        if len(normals) != len(frames):
+            raise ValueError(f"{len(normals)} normal arrays for {len(frames)} frames")
+        out = []
+        for f, (a, p) in enumerate(zip(normals, frames)):
+            if isinstance(a, torch.Tensor):
+                if a.device.type != "cpu":
+                    raise TypeError(f"frame {f}: normals are host arrays, got a tensor on {a.device}")
+                a = a.detach().numpy()
+            a = np.asarray(a)
+            if a.dtype != np.float32:
+                raise TypeError(f"frame {f}: expected float32 normals, got {a.dtype}")
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError(f"frame {f}: expected normals of shape [n, 3], got {a.shape}")
+            if a.shape[0] != p.shape[0]:
+                raise ValueError(f"frame {f}: {a.shape[0]} normals for {p.shape[0]} points")
+            if not np.isfinite(a).all():
+                raise ValueError(f"frame {f}: non-finite normal")
+            out.append(np.ascontiguousarray(a))
+        return out
+
+    def distortion(self, frames_a, frames_b, attributes_a=None, attributes_b=None, peak=None, normals_a=None, normal_k=16):
         """The D1 (point-to-point) distortion between two sequences of lattice frames, frame by frame, by exact nearest
         neighbours on the device (pcc_nn_frames; include/pcc.h has the rule) -> one dict per frame:
 
@@ -525,6 +623,10 @@ class GeometryCodec:
                                    are 0, None when peak is None
             attr_mse_ab, attr_mse_ba   with attributes: per channel, the mean squared difference between a row's value
                                    and the value of its nearest point of the other side (Morton-first among equidistant)
+            d2_mse_ab, d2_mse_ba   with normals_a: the D2 (point-to-plane) figures — mean over the rows of one side of
+                                   the squared projection of the error vector to the nearest point of the other side
+                                   onto the normal of the pair's A point, float64
+            d2_psnr                10 log10(3 peak^2 / max(d2_mse_ab, d2_mse_ba)), inf and None as d1_psnr
 
         frames_a, frames_b: as compress takes them, int16 / int32 only, numpy or torch, all on the host or all on this
         codec's device, the same number on both sides.  float32 frames raise TypeError: pass lattice points — what
@@ -533,7 +635,11 @@ class GeometryCodec:
         0.0 and inf.  Cells of a level of detail compare as their centres: (cells << k) + ((1 << k) >> 1).
         attributes_a, attributes_b: host uint8 / uint16 [n] or [n, c] per frame, as compress takes them, dtype and
         channel count equal per frame pair; both sides must then be free of duplicate points (ValueError naming the
-        frame): the typical call compares a lossless decode with a lossy one."""
+        frame): the typical call compares a lossless decode with a lossy one.
+        normals_a: only side A (the original) carries normals, as with pc_error -n.  "estimate": the normals of A's
+        distinct points from their normal_k (3 .. 32) nearest neighbours, as normals() gives them; A may hold duplicates,
+        a frame of A with 1 or 2 distinct points raises ValueError.  Or one finite float32 [n_f, 3] host array per frame,
+        row i the normal of row i of A, used as given: A must then be free of duplicate points."""
         fa, float_a, dev_a = self._check_frames(frames_a)
         fb, float_b, dev_b = self._check_frames(frames_b)
         if float_a or float_b:
@@ -557,6 +663,13 @@ class GeometryCodec:
                 if a.dtype != b.dtype or a.shape[1] != b.shape[1]:
                     raise ValueError(f"frame {f}: {a.dtype} attributes of {a.shape[1]} channels against {b.dtype} of "
                                      f"{b.shape[1]}: dtype and channel count must be equal")
+        given = None
+        if isinstance(normals_a, str):
+            if normals_a != "estimate":
+                raise ValueError(f"normals_a must be 'estimate' or one float32 [n, 3] array per frame, got {normals_a!r}")
+            normal_k = self._check_k(normal_k, "normal_k")
+        elif normals_a is not None:
+            given = self._check_normals(fa, normals_a)
         nb = len(fa)
         sizes_a = [int(a.shape[0]) for a in fa]
         sizes_b = [int(b.shape[0]) for b in fb]
@@ -567,6 +680,7 @@ class GeometryCodec:
             return []
         ab = ba = [[0, 0, 0]] * nb
         sse_ab = sse_ba = None
+        d2_ab = d2_ba = [0.0] * nb
         if sum(sizes_a):
             caller = torch.cuda.current_stream(self.rt.device) if dev_a else None
             with self._lock, self.rt as rt:
@@ -575,8 +689,15 @@ class GeometryCodec:
                 if attrs_a is not None:
                     self._refuse_duplicates(front_a, "frames_a")
                     self._refuse_duplicates(front_b, "frames_b")
-                _, row_ab, ab = rt.nn_frames(front_a.sorted_keys, front_b.keys, nb, want_dist=False, want_row=attrs_a is not None)
-                _, row_ba, ba = rt.nn_frames(front_b.sorted_keys, front_a.keys, nb, want_dist=False, want_row=attrs_a is not None)
+                if given is not None:
+                    self._refuse_duplicates(front_a, "frames_a")
+                elif normals_a is not None:
+                    self._refuse_few(front_a, "frames_a")
+                want_row = attrs_a is not None or normals_a is not None
+                _, row_ab, ab = rt.nn_frames(front_a.sorted_keys, front_b.keys, nb, want_dist=False, want_row=want_row)
+                _, row_ba, ba = rt.nn_frames(front_b.sorted_keys, front_a.keys, nb, want_dist=False, want_row=want_row)
+                if normals_a is not None:
+                    d2_ab, d2_ba = self._d2_sums(rt, front_a, front_b, row_ab, row_ba, given, normal_k)
                 if attrs_a is not None:
                     dtype = np.uint16 if any(a.dtype == np.uint16 for a in attrs_a) else np.uint8
                     channels = max(a.shape[1] for a in attrs_a)
@@ -596,12 +717,37 @@ class GeometryCodec:
             worst = max(rep["mse_ab"], rep["mse_ba"])
             rep["d1_psnr"] = None if peak is None else (float("inf") if worst == 0.0 else
                                                        float(10.0 * np.log10(3.0 * float(peak) ** 2 / worst)))
+            if normals_a is not None:
+                rep["d2_mse_ab"] = d2_ab[f] / float(ca) if ca else 0.0
+                rep["d2_mse_ba"] = d2_ba[f] / float(cb) if cb else 0.0
+                worst = max(rep["d2_mse_ab"], rep["d2_mse_ba"])
+                rep["d2_psnr"] = None if peak is None else (float("inf") if worst == 0.0 else
+                                                           float(10.0 * np.log10(3.0 * float(peak) ** 2 / worst)))
             if attrs_a is not None:
                 c = attrs_a[f].shape[1]
                 rep["attr_mse_ab"] = [float(s) / float(ca) if ca else 0.0 for s in sse_ab[f][:c]]
                 rep["attr_mse_ba"] = [float(s) / float(cb) if cb else 0.0 for s in sse_ba[f][:c]]
             report.append(rep)
         return report
+
+    @staticmethod
+    def _d2_sums(rt, front_a, front_b, row_ab, row_ba, given, normal_k):
+        """the per-frame sums of the D2 projections of both directions: the normals of A's distinct points — estimated,
+        or `given` per input row of a duplicate-free A and brought into the order of its sorted keys — then one
+        pcc_nn_d2_frames per direction, the normal of a pair always that of its A point"""
+        nb = front_a.nb
+        of_query = None      # A -> B: query i of the sorted keys is distinct row i, unless A holds duplicates
+        if given is None:
+            normals = rt.knn_frames(front_a.keys, nb, normal_k)[3]
+            if front_a.n_unique != front_a.n_keep:
+                of_query = rt.lookup(front_a.keys, front_a.sorted_keys)
+        else:
+            host = torch.empty((front_a.n, 3), dtype=torch.float32, pin_memory=True)
+            np.concatenate(given, axis=0, out=host.numpy())
+            normals = rt.gather_rows(rt.to_device(host), front_a.perm)
+        _, d2_ab = rt.nn_d2_frames(front_a.sorted_keys, row_ab, front_b.keys, normals, nb, of_query)
+        _, d2_ba = rt.nn_d2_frames(front_b.sorted_keys, row_ba, front_a.keys, normals, nb, row_ba)
+        return d2_ab, d2_ba
 
     @staticmethod
     def _refuse_duplicates(front, side):

@@ -241,6 +241,39 @@ class Runtime:
               "pcc_nn_attr_sse_frames")
         return self._u64_rows(sse)
 
+    def knn_frames(self, keys, n_frames, k, want_rows=False, want_dist=False, want_cov=False, want_normals=True,
+                   viewpoint=None):
+        """the k nearest neighbours of every point of a frame among the frame's own points, their scatter matrix and
+        the surface normal (pcc_knn_frames, the rules of include/pcc.h).  keys: sorted distinct Morton keys on the
+        device.  Returns (rows int32 [n, k], sqdist int64 [n, k] holding uint64 values, cov int64 [n, 6], normals
+        float32 [n, 3]) as device tensors, None where not wanted.  viewpoint: three ints, or None.  Synchronises once,
+        in front of the search (the checks of the keys); the results are on this runtime's stream."""
+        n, k = int(keys.shape[0]), int(k)
+        rows = self.empty((n, k), torch.int32) if want_rows else None
+        sqdist = self.empty((n, k), torch.int64) if want_dist else None
+        cov = self.empty((n, 6), torch.int64) if want_cov else None
+        normals = self.empty((n, 3), torch.float32) if want_normals else None
+        vp = None if viewpoint is None else (C.c_int * 3)(*[int(v) for v in viewpoint])
+        check(self.lib.pcc_knn_frames(self.ctx, _ptr(keys), n, int(n_frames), k, _ptr(rows), _ptr(sqdist), _ptr(cov),
+                                      _ptr(normals), vp), "pcc_knn_frames")
+        return rows, sqdist, cov, normals
+
+    def nn_d2_frames(self, qkeys, row, rkeys, normals, n_frames, normal_row=None, want_proj=False):
+        """the D2 (point-to-plane) side of a pairing (pcc_nn_d2_frames): row, nn_frames' rows of qkeys among rkeys;
+        normals a float32 [m, 3] device tensor; normal_row an int32 [n_q] device tensor, the row of normals to use for
+        query i (every entry below m), or None: row i, and then m == n_q.  Returns (proj, sums): proj a float64 [n_q]
+        device tensor (None unless want_proj), sums a list of n_frames floats.  Synchronises."""
+        n_q = int(qkeys.shape[0])
+        if normals.dtype != torch.float32 or normals.dim() != 2 or normals.shape[1] != 3 or row.shape[0] != n_q or \
+                (normal_row is None and normals.shape[0] != n_q) or (normal_row is not None and normal_row.shape[0] != n_q):
+            raise ValueError(f"nn_d2_frames: normals {tuple(normals.shape)} {normals.dtype} for {n_q} queries")
+        proj = self.empty((n_q,), torch.float64) if want_proj else None
+        sums = self.empty((n_frames,), torch.float64)
+        check(self.lib.pcc_nn_d2_frames(self.ctx, _ptr(qkeys), _ptr(row), n_q, _ptr(rkeys), int(rkeys.shape[0]), _ptr(normals),
+                                        _ptr(normal_row), int(n_frames), _ptr(proj), _ptr(sums)), "pcc_nn_d2_frames")
+        self.sync()
+        return proj, sums.cpu().tolist()
+
     def _u64_rows(self, t):
         """an int64 device tensor holding uint64 values, written on this runtime's stream -> nested lists of Python ints"""
         self.sync()

@@ -975,6 +975,77 @@ int pcc_nn_replay_host(const uint64_t* h_qkeys, int64_t n_q,
                        const uint64_t* h_rkeys, int64_t n_r, uint64_t* h_sqdist,
                        int32_t* h_row, uint32_t* h_nodes);
 
+/* ---- k nearest neighbours, surface normals, the D2 metric (csrc/knn.hip) -- */
+
+/* The rules (tests/normals_ref.py restates them in numpy).
+ *
+ * k nearest neighbours.  Per frame the reference R is the frame's distinct
+ * points in Morton order (sorted distinct keys, the frame index above bit 48);
+ * the queries are those same points.  For a point p and an integer k in
+ * 3 .. 32, knn(p) is the first k_eff = min(k, n_f) rows of the frame ordered by
+ * (|r - p|^2, row) ascending: p itself is its own nearest neighbour, at
+ * distance 0 (Open3D's KDTreeSearchParamKNN convention), and among equidistant
+ * rows the smaller row (Morton-first) comes first.  Rows are counted over the
+ * whole call's keys, as pcc_nn_frames counts them.  Slots k_eff .. k - 1 hold
+ * row -1 and d2 = 2^64 - 1.  Distances are unsigned 64-bit integers, at most
+ * 3 * 65535^2.  Only points of the same frame are candidates.
+ *
+ * Scatter matrix.  With d_j = r_j - p over the m = k_eff neighbours (the zero
+ * vector of p itself included),
+ *   C = m * sum d_j d_j^T - (sum d_j)(sum d_j)^T,
+ * m^2 times the covariance, exact in int64: |C| <= 2 * 32 * 32 * 65535^2 < 2^46.
+ * Stored as six int64: xx, xy, xz, yy, yz, zz.
+ *
+ * Normal.  A unit eigenvector of C for its smallest eigenvalue, computed in
+ * float64 on the device and returned as float32 [3].  Where the eigenspace has
+ * more than one dimension (collinear neighbours, a symmetric lattice
+ * neighbourhood) any unit vector of it is right.  The result is always finite
+ * and of unit length.  A frame with fewer than 3 distinct points has no normal:
+ * (0, 0, 0) and C = 0 are written for its points.  Sign: with a viewpoint
+ * (three int32 lattice coordinates, e.g. the sensor) n is flipped where
+ * n . (viewpoint - p) < 0; without one the sign is unspecified.
+ *
+ * D2 (point-to-plane).  Only side A (the original) carries normals, as with
+ * pc_error -n: the normal of a pair is always the normal of the pair's A point.
+ *   A -> B: for row a of A with r = nn_B(a), proj(a) = ((a - b_r) . n_a)^2;
+ *   B -> A: for row b of B with r = nn_A(b), proj(b) = ((b - a_r) . n_{a_r})^2.
+ * The dot product is formed in float64 as (ex*nx + ey*ny) + ez*nz: each product
+ * is an integer of at most 17 bits times a float32, exact in float64, so the
+ * value does not depend on fma contraction.  d2_mse = sum proj / count;
+ * d2_psnr = 10 log10(3 peak^2 / max(d2_mse_ab, d2_mse_ba)).
+ *
+ *   pcc_knn_frames : d_keys: n sorted distinct keys of n_frames frames.
+ *     Outputs, each written only when its pointer is non-null: d_rows [n][k],
+ *     d_sqdist [n][k], d_cov [n][6], d_normals [n][3]; h_viewpoint: three
+ *     int32 on the host, or null.  One thread per point walks the implicit
+ *     octree of its frame's keys without a stack, the k best in registers.
+ *     Checked before the search is launched (one synchronisation): k in
+ *     3 .. 32, n <= 2^27 and n_frames in 1 .. 65535 (PCC_E_ARG); keys not
+ *     sorted (PCC_E_ARG) or not distinct (PCC_E_DUP); a frame index not below
+ *     n_frames (PCC_E_RANGE).  n = 0 launches nothing.
+ *   pcc_nn_d2_frames : d_row: pcc_nn_frames' rows of d_qkeys among d_rkeys;
+ *     d_normals: float32 [.][3]; d_normal_row [n_q]: the row of d_normals to
+ *     use for query i, null: row i (the caller keeps them inside d_normals).
+ *     d_proj [n_q] (nullable): proj per query; d_sum [n_frames] (nullable,
+ *     zeroed by the call): the frame's sum of proj, float64, added in an
+ *     unspecified order.  A row of -1 or out of range, a negative normal row
+ *     or a frame index not below n_frames adds nothing (proj 0).
+ *   pcc_knn_replay_host : host only, no ctx.  The traversal and the epilogue
+ *     of pcc_knn_frames, the same functions compiled for the host, without a
+ *     viewpoint; additionally h_nodes [n]: the nodes each query tried (cells
+ *     tested and points measured).  k and n as above (PCC_E_ARG), keys not
+ *     sorted (PCC_E_ARG) or not distinct (PCC_E_DUP).  Not a product path. */
+int pcc_knn_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames,
+                   int k, int32_t* d_rows, uint64_t* d_sqdist, int64_t* d_cov,
+                   float* d_normals, const int32_t* h_viewpoint);
+int pcc_nn_d2_frames(pcc_ctx* ctx, const uint64_t* d_qkeys, const int32_t* d_row,
+                     int64_t n_q, const uint64_t* d_rkeys, int64_t n_r,
+                     const float* d_normals, const int32_t* d_normal_row,
+                     int n_frames, double* d_proj, double* d_sum);
+int pcc_knn_replay_host(const uint64_t* h_keys, int64_t n, int k, int32_t* h_rows,
+                        uint64_t* h_sqdist, int64_t* h_cov, float* h_normals,
+                        uint32_t* h_nodes);
+
 /* ---- whole-GOP entry points ------------------------------ */
 
 /* replaces: CompressionPipeline.compress() (sender/encoder/codec_pipeline.py:
