@@ -1,9 +1,9 @@
 // knn.hip — the k nearest neighbours of every point of a frame among the frame's own points, the scatter matrix of
-// that neighbourhood and its surface normal; and the D2 (point-to-plane) projection of a 1-NN pairing (nn.hip) onto
-// such normals.  include/pcc.h has the rules; tests/normals_ref.py restates them in numpy.
+// that neighbourhood and its surface normal.  include/pcc.h has the rules; tests/normals_ref.py restates them in numpy.
+// (The D2 projection onto these normals consumes a 1-NN pairing and lives beside that search, in nn.hip.)
 //
-// k_knn_frames is the k-best form of nn.hip's walk: sorted distinct Morton keys are an implicit octree, one thread per
-// query walks the cells of its own frame in row order with scalar state and no stack.
+// k_knn_frames is the k-best form of nn.hip's search: one thread per query walks the cells of its own frame in row
+// order with nn_walk (nn_cells.h has the walk and why it ends).
 //
 //   list   the k best (d2, row) so far, ascending by (d2, row), in registers: a capacity template (8 / 16 / 32, chosen
 //          by the host from k) whose insertion is fully unrolled, so every index is static and nothing lives in
@@ -11,13 +11,7 @@
 //          front hold (0, -1), below every candidate, so the pruning bound is always the last slot.  Free slots hold
 //          (2^64 - 1, INT32_MAX): until the list holds k_eff = min(k, frame rows) entries nothing is pruned.
 //   seed   the k_eff rows around the query's place in key order, clamped to the frame's rows, fill the list before the
-//          walk starts; the walk measures every other row at most once, so no row enters twice.
-//   walk   nn_search's: at row r the cells that begin at r are tried from the largest down; a cell whose box distance
-//          exceeds the bound's d2, or equals it while r > the bound's row, is left out whole.
-//
-// Termination: every iteration of the walk moves r forward — a skip lands on a row of [r + 1, fhi], a measured point
-// on r + 1 — and every binary search runs inside the frame's rows [flo, fhi): at most 47 halvings.  The seed loop
-// counts k_eff rows.  No step waits for another thread.  Keep both properties: a walk that can stand still is a hang.
+//          walk starts; the walk passes over them (seeded), so no row enters twice.  The seed loop counts k_eff rows.
 //
 // Epilogue, same thread: C = m sum d d^T - (sum d)(sum d)^T over the m = k_eff neighbours in int64 (below 2^46), then
 // a unit eigenvector of its smallest eigenvalue in float64 — eigenvalues in closed form (trigonometric), the vector
@@ -33,37 +27,6 @@ static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / 
 
 #define KNN_NO_DIST (~0ull)
 #define KNN_NO_ROW 0x7FFFFFFF
-
-// bit 0: equal neighbours, bit 1: descending neighbours, bit 2: a key's frame index >= n_frames
-__global__ __launch_bounds__(256) void k_knn_check(const uint64_t* __restrict__ keys, int64_t n, int n_frames,
-                                                   int32_t* __restrict__ flag) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  int bits = 0;
-  const uint64_t k = keys[i];
-  if ((k >> 48) >= (uint64_t)n_frames) bits |= 4;
-  if (i > 0) {
-    const uint64_t p = keys[i - 1];
-    if (p == k) bits |= 1;
-    if (p > k) bits |= 2;
-  }
-  if (bits) atomicOr(flag, bits);
-}
-
-// offs[f] = the first row of frame f, offs[n_frames] = n
-__global__ __launch_bounds__(64) void k_knn_offsets(const uint64_t* __restrict__ keys, int64_t n, int n_frames,
-                                                    int64_t* __restrict__ offs) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f > n_frames) return;
-  int64_t lo = 0, hi = n;
-  if (f == n_frames) lo = n;
-  const uint64_t want = (uint64_t)f << 48;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < want) lo = mid + 1; else hi = mid;
-  }
-  offs[f] = lo;
-}
 
 // ---------------------------------------------------------------- the list
 template <int CAP>
@@ -105,74 +68,33 @@ __host__ __device__ static inline void knn_insert(KnnList<CAP>& L, uint64_t d, i
   }
 }
 
+// the k-NN bound of nn_walk: the list's last slot; the seed rows [s0, s1) are in the list already
+template <int CAP>
+struct KnnBest {
+  KnnList<CAP>& L;
+  int64_t s0, s1;
+  __host__ __device__ uint64_t bound() const { return L.d[CAP - 1]; }
+  __host__ __device__ int64_t bound_row() const { return L.r[CAP - 1]; }
+  __host__ __device__ bool seeded(int64_t r) const { return r >= s0 && r < s1; }
+  __host__ __device__ void offer(uint64_t d, int64_t r) { knn_insert(L, d, (int32_t)r); }
+};
+
 // the k-best search of one query among the rows [flo, fhi) of its frame, flo < fhi, 1 <= k <= CAP; L comes from
-// knn_init.  Returns the nodes tried (cells tested and points measured, the seeds included).  One function for the
-// device and the host, so pcc_knn_replay_host is the kernel's traversal.
+// knn_init.  Returns the nodes tried (cells tested and points measured, the seeds included).
 template <int CAP>
 __host__ __device__ static inline uint32_t knn_search(const uint64_t* __restrict__ keys, int64_t flo, int64_t fhi, uint64_t qk,
                                                       int k, KnnList<CAP>& L) {
   const uint32_t qx = pcc_compact3(qk >> 2), qy = pcc_compact3(qk >> 1), qz = pcc_compact3(qk);
   const int64_t n_f = fhi - flo;
   const int64_t k_eff = n_f < k ? n_f : k;
-  uint32_t nodes = 0;
-  int64_t lo = flo, hi = fhi;      // the first row of the frame whose key is not below the query's
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < qk) lo = mid + 1; else hi = mid;
-  }
+  const int64_t lo = nn_lower_bound(keys, flo, fhi, qk);      // the first row of the frame whose key is not below the query's
   int64_t s0 = lo - k_eff / 2;      // the seed rows [s0, s1) inside [flo, fhi)
   if (s0 > fhi - k_eff) s0 = fhi - k_eff;
   if (s0 < flo) s0 = flo;
-  const int64_t s1 = s0 + k_eff;
-  for (int64_t r = s0; r < s1; ++r) {
-    knn_insert(L, nn_d2(qx, qy, qz, keys[r]), (int32_t)r);
-    ++nodes;
-  }
-  if (k_eff == n_f) return nodes;      // the seed was the whole frame
-  int64_t r = flo;
-  uint64_t prev = 0;
-  while (r < fhi) {
-    const uint64_t key = keys[r];
-    int Lv = r == flo ? 15 : (63 - __builtin_clzll(((prev ^ key) & NN_KEY48) | 1ull)) / 3;      // keys are distinct
-    const uint32_t cx = pcc_compact3(key >> 2), cy = pcc_compact3(key >> 1), cz = pcc_compact3(key);
-    // the cells of levels 0 .. l1 hold row r alone (key r + 1 leaves them): measuring the point is their test
-    const int l1 = r + 1 < fhi ? (63 - __builtin_clzll(((key ^ keys[r + 1]) & NN_KEY48) | 1ull)) / 3 : 15;
-    const uint64_t bound = L.d[CAP - 1];
-    const int64_t bound_row = L.r[CAP - 1];
-    bool skipped = false;
-    for (; Lv > l1; --Lv) {
-      const uint64_t bd = (uint64_t)nn_gap_sq(qx, cx, Lv) + nn_gap_sq(qy, cy, Lv) + nn_gap_sq(qz, cz, Lv);
-      ++nodes;
-      if (bd > bound || (bd == bound && r > bound_row)) {
-        // the first row behind the cell, whose keys are [p << 3L, (p + 1) << 3L)
-        const uint64_t end = (((key & NN_KEY48) >> (3 * Lv)) + 1ull) << (3 * Lv);
-        int64_t a = r + 1, b = fhi;
-        if (end <= NN_KEY48) {
-          const uint64_t want = (key & ~NN_KEY48) | end;
-          while (a < b) {
-            const int64_t mid = (a + b) >> 1;
-            if (keys[mid] < want) a = mid + 1; else b = mid;
-          }
-        } else {
-          a = fhi;      // the cell reaches the end of the key range
-        }
-        r = a;
-        skipped = true;
-        break;
-      }
-    }
-    if (skipped) {
-      if (r < fhi) prev = keys[r - 1];
-      continue;
-    }
-    if (r < s0 || r >= s1) {      // a seed row is in the list already
-      knn_insert(L, (uint64_t)nn_sq(qx, cx) + nn_sq(qy, cy) + nn_sq(qz, cz), (int32_t)r);
-      ++nodes;
-    }
-    prev = key;
-    ++r;
-  }
-  return nodes;
+  KnnBest<CAP> b = {L, s0, s0 + k_eff};
+  for (int64_t r = b.s0; r < b.s1; ++r) knn_insert(L, nn_d2(qx, qy, qz, keys[r]), (int32_t)r);
+  if (k_eff == n_f) return (uint32_t)k_eff;      // the seed was the whole frame
+  return (uint32_t)k_eff + nn_walk(keys, flo, fhi, qx, qy, qz, b);
 }
 
 // ---------------------------------------------------------------- scatter matrix and normal
@@ -361,52 +283,9 @@ __global__ __launch_bounds__(256) void k_knn_frames(const uint64_t* __restrict__
                                                     int vy, int vz) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int f = (int)(keys[i] >> 48);      // below n_frames: k_knn_check
+  const int f = (int)(keys[i] >> 48);      // below n_frames: k_nn_check
   const int64_t flo = offs[f], fhi = offs[f + 1];      // flo <= i < fhi: row i is a row of its own frame
   (void)knn_point<CAP>(keys, flo, fhi, i, k, rows, sqdist, cov, normals, has_vp != 0, vx, vy, vz);
-}
-
-// proj[i] = ((q_i - r_row[i]) . n)^2 in float64, n = row normal_row[i] (row i without normal_row) of normals, the dot
-// product as (ex nx + ey ny) + ez nz; sum[f] += proj over the queries i of frame f.  A query without a row (-1), a
-// row outside the reference, a negative normal row or a frame index outside the call adds nothing (proj 0).  The
-// reduction is k_nn_frames': per frame present in the wave shuffles, then one atomic from one lane.
-__global__ __launch_bounds__(256) void k_nn_d2(const uint64_t* __restrict__ qkeys, const int32_t* __restrict__ row, int64_t n_q,
-                                               const uint64_t* __restrict__ rkeys, int64_t n_r, const float* __restrict__ normals,
-                                               const int32_t* __restrict__ normal_row, int n_frames, double* __restrict__ proj,
-                                               double* __restrict__ sum) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool valid = false;
-  int f = 0;
-  double p = 0.0;
-  if (i < n_q) {
-    const int64_t r = row[i];
-    const uint64_t qk = qkeys[i];
-    const int64_t nr = normal_row ? (int64_t)normal_row[i] : i;
-    f = (int)(qk >> 48);
-    if (r >= 0 && r < n_r && nr >= 0 && f < n_frames) {
-      valid = true;
-      const uint64_t rk = rkeys[r];
-      const double ex = (double)((int)pcc_compact3(qk >> 2) - (int)pcc_compact3(rk >> 2)),
-                   ey = (double)((int)pcc_compact3(qk >> 1) - (int)pcc_compact3(rk >> 1)),
-                   ez = (double)((int)pcc_compact3(qk) - (int)pcc_compact3(rk));
-      const float* n = normals + nr * 3;
-      const double d = (ex * (double)n[0] + ey * (double)n[1]) + ez * (double)n[2];
-      p = d * d;
-    }
-    if (proj) proj[i] = p;
-  }
-  if (!sum) return;      // the same in every lane
-  const int lane = threadIdx.x & 63;
-  unsigned long long todo = __ballot(valid);
-  while (todo) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const int f0 = __shfl(f, leader);
-    const bool mine = valid && f == f0;
-    double s = mine ? p : 0.0;
-    for (int off = 32; off; off >>= 1) s += __shfl_xor(s, off);
-    if (lane == leader) atomicAdd(&sum[f0], s);
-    todo &= ~__ballot(mine);
-  }
 }
 
 // ---------------------------------------------------------------- C-ABI (include/pcc.h)
@@ -419,57 +298,19 @@ static void knn_launch(hipStream_t st, const uint64_t* d_keys, int64_t n, const 
 
 extern "C" int pcc_knn_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int k, int32_t* d_rows,
                               uint64_t* d_sqdist, int64_t* d_cov, float* d_normals, const int32_t* h_viewpoint) {
-  const int64_t kMax = (int64_t)1 << 27;
-  PCC_REQUIRE(ctx && k >= 3 && k <= 32 && n >= 0 && n <= kMax && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
+  PCC_REQUIRE(ctx && k >= 3 && k <= 32 && n >= 0 && n <= NN_MAX_KEYS && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
               "pcc_knn_frames: bad argument (n=%lld n_frames=%d k=%d; k in 3 .. 32, at most 2^27 keys, 1 .. 65535 frames)",
               (long long)n, n_frames, k);
   PCC_REQUIRE(n == 0 || d_keys, PCC_E_ARG, "pcc_knn_frames: null keys");
   if (n == 0) return PCC_OK;
   hipStream_t st = ctx->stream;
-  const size_t offs_b = (size_t)(n_frames + 1) * 8;
-  PCC_TRY(pcc_arena_reserve(ctx, pcc_align(offs_b) + 512));
-  int64_t* offs = (int64_t*)pcc_arena_alloc(ctx, offs_b);
-  int32_t* flag = (int32_t*)pcc_arena_alloc(ctx, 4);
-  if (!offs || !flag) return PCC_E_NOMEM;
-  PCC_HIP(hipMemsetAsync(flag, 0, 4, st));
-  hipLaunchKernelGGL(k_knn_check, dim3(nblk(n, 256)), dim3(256), 0, st, d_keys, n, n_frames, flag);
-  PCC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_knn_offsets, dim3(nblk(n_frames + 1, 64)), dim3(64), 0, st, d_keys, n, n_frames, offs);
-  PCC_CHECK_LAUNCH();
-  int32_t* h = (int32_t*)ctx->pinned;
-  PCC_HIP(hipMemcpyAsync(h, flag, 4, hipMemcpyDeviceToHost, st));
-  PCC_HIP(hipStreamSynchronize(st));
-  const int32_t bits = h[0];
-  PCC_REQUIRE(!(bits & 4), PCC_E_RANGE, "pcc_knn_frames: a key's frame index is not below n_frames=%d", n_frames);
-  PCC_REQUIRE(!(bits & 2), PCC_E_ARG, "pcc_knn_frames: keys not sorted (pcc_sort_pairs)");
-  PCC_REQUIRE(!(bits & 1), PCC_E_DUP, "pcc_knn_frames: duplicate keys");
+  const int64_t* offs;
+  PCC_TRY(nn_check_and_offsets(ctx, "pcc_knn_frames", "a key's", "keys", d_keys, n, nullptr, 0, n_frames, &offs));
   if (!d_rows && !d_sqdist && !d_cov && !d_normals) return PCC_OK;
   PccProfScope prof(ctx, "knn_frames", n, k, n_frames, 0);
   if (k <= 8) knn_launch<8>(st, d_keys, n, offs, k, d_rows, d_sqdist, d_cov, d_normals, h_viewpoint);
   else if (k <= 16) knn_launch<16>(st, d_keys, n, offs, k, d_rows, d_sqdist, d_cov, d_normals, h_viewpoint);
   else knn_launch<32>(st, d_keys, n, offs, k, d_rows, d_sqdist, d_cov, d_normals, h_viewpoint);
-  PCC_CHECK_LAUNCH();
-  return PCC_OK;
-}
-
-extern "C" int pcc_nn_d2_frames(pcc_ctx* ctx, const uint64_t* d_qkeys, const int32_t* d_row, int64_t n_q, const uint64_t* d_rkeys,
-                                int64_t n_r, const float* d_normals, const int32_t* d_normal_row, int n_frames, double* d_proj,
-                                double* d_sum) {
-  const int64_t kMax = (int64_t)1 << 27;
-  PCC_REQUIRE(ctx && n_frames >= 1 && n_frames <= 65535 && n_q >= 0 && n_q <= kMax && n_r >= 0 && n_r <= kMax, PCC_E_ARG,
-              "pcc_nn_d2_frames: bad argument (n_q=%lld n_r=%lld n_frames=%d)", (long long)n_q, (long long)n_r, n_frames);
-  PCC_REQUIRE(n_q == 0 || (d_qkeys && d_row), PCC_E_ARG, "pcc_nn_d2_frames: null query arrays");
-  PCC_REQUIRE(n_q == 0 || n_r == 0 || (d_rkeys && d_normals), PCC_E_ARG, "pcc_nn_d2_frames: null reference keys or normals");
-  hipStream_t st = ctx->stream;
-  if (d_sum) PCC_HIP(hipMemsetAsync(d_sum, 0, (size_t)n_frames * 8, st));
-  if (n_q == 0 || (!d_proj && !d_sum)) return PCC_OK;
-  if (n_r == 0) {      // no row can be valid
-    if (d_proj) PCC_HIP(hipMemsetAsync(d_proj, 0, (size_t)n_q * 8, st));
-    return PCC_OK;
-  }
-  PccProfScope prof(ctx, "nn_d2", n_q, n_r, n_frames, 0);
-  hipLaunchKernelGGL(k_nn_d2, dim3(nblk(n_q, 256)), dim3(256), 0, st, d_qkeys, d_row, n_q, d_rkeys, n_r, d_normals, d_normal_row,
-                     n_frames, d_proj, d_sum);
   PCC_CHECK_LAUNCH();
   return PCC_OK;
 }
@@ -493,13 +334,9 @@ static void knn_replay(const uint64_t* h_keys, int64_t n, int k, int32_t* h_rows
 
 extern "C" int pcc_knn_replay_host(const uint64_t* h_keys, int64_t n, int k, int32_t* h_rows, uint64_t* h_sqdist, int64_t* h_cov,
                                    float* h_normals, uint32_t* h_nodes) {
-  const int64_t kMax = (int64_t)1 << 27;
-  PCC_REQUIRE(k >= 3 && k <= 32 && n >= 0 && n <= kMax && (n == 0 || h_keys), PCC_E_ARG,
+  PCC_REQUIRE(k >= 3 && k <= 32 && n >= 0 && n <= NN_MAX_KEYS && (n == 0 || h_keys), PCC_E_ARG,
               "pcc_knn_replay_host: bad argument (n=%lld k=%d; k in 3 .. 32, at most 2^27 keys)", (long long)n, k);
-  for (int64_t i = 1; i < n; ++i) {
-    PCC_REQUIRE(h_keys[i - 1] <= h_keys[i], PCC_E_ARG, "pcc_knn_replay_host: keys not sorted (pcc_sort_pairs)");
-    PCC_REQUIRE(h_keys[i - 1] != h_keys[i], PCC_E_DUP, "pcc_knn_replay_host: duplicate keys");
-  }
+  PCC_TRY(nn_host_sorted_distinct("pcc_knn_replay_host", "keys", h_keys, n));
   if (k <= 8) knn_replay<8>(h_keys, n, k, h_rows, h_sqdist, h_cov, h_normals, h_nodes);
   else if (k <= 16) knn_replay<16>(h_keys, n, k, h_rows, h_sqdist, h_cov, h_normals, h_nodes);
   else knn_replay<32>(h_keys, n, k, h_rows, h_sqdist, h_cov, h_normals, h_nodes);

@@ -921,7 +921,7 @@ int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_version,
                   int32_t* h_bpv, int32_t* h_channels, int64_t* h_points,
                   int32_t* h_max_error, int32_t* h_scalable, int32_t* h_lod);
 
-/* ---- exact nearest neighbours on the lattice: the D1 metric (csrc/nn.hip) -- */
+/* ---- exact nearest neighbours on the lattice: the D1 metric (csrc/nn.hip, the walk in csrc/nn_cells.h) -- */
 
 /* The rule (tests/nn_ref.py restates it in numpy).  For a frame f there are
  * two sets of lattice points, every coordinate in [-32768, 32767]:
@@ -975,7 +975,7 @@ int pcc_nn_replay_host(const uint64_t* h_qkeys, int64_t n_q,
                        const uint64_t* h_rkeys, int64_t n_r, uint64_t* h_sqdist,
                        int32_t* h_row, uint32_t* h_nodes);
 
-/* ---- k nearest neighbours, surface normals, the D2 metric (csrc/knn.hip) -- */
+/* ---- k nearest neighbours, surface normals (csrc/knn.hip), the D2 metric (csrc/nn.hip) -- */
 
 /* The rules (tests/normals_ref.py restates them in numpy).
  *

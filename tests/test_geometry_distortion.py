@@ -134,6 +134,11 @@ def test_restatement_against_the_kd_tree():
     assert np.array_equal(((a - b[row]) ** 2).sum(1).astype(np.uint64), d2)
 
 
+# (sum, max) of the nodes pcc_nn_replay_host reports per case, recorded from the library built at commit 4c134a5 (the
+# last one with a walk of its own in nn.hip): the shared walk has to visit what that one visited, node for node
+NODES_AT_4C134A5 = {"three frames": (237153, 277), "seams": (432, 22), "ties": (61, 28), "worst case for pruning": (3008, 45)}
+
+
 def _replay(qkeys, rkeys):
     lib = pkg("_abi").lib()
     qkeys, rkeys = np.ascontiguousarray(qkeys, np.uint64), np.ascontiguousarray(rkeys, np.uint64)
@@ -146,13 +151,14 @@ def _replay(qkeys, rkeys):
 @pytest.mark.parametrize("name", list(CASES))
 def test_traversal_replayed_on_the_host(cases, name):
     """the kernel's search function, compiled for the host, against the restatement; a query tries no more nodes than
-    its frame's octree has (at most 16 per reference row, and the two seeds)"""
+    its frame's octree has (at most 16 per reference row, and the two seeds), and the case as many as recorded"""
     qkeys, rkeys, n_frames, d2, row, _ = cases[name]
     rc, got_d2, got_row, nodes = _replay(qkeys, rkeys)
     assert rc == 0
     assert np.array_equal(got_d2, d2) and np.array_equal(got_row, row)
     per_frame = np.bincount((rkeys >> np.uint64(48)).astype(np.int64), minlength=n_frames)
     assert np.all(nodes <= 2 + 16 * per_frame[(qkeys >> np.uint64(48)).astype(np.int64)])
+    assert (int(nodes.sum(dtype=np.uint64)), int(nodes.max())) == NODES_AT_4C134A5[name]
 
 
 def test_replay_corners_and_refusals():

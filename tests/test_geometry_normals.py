@@ -158,6 +158,16 @@ def test_restatement_solver_passes_the_rayleigh_check(cases, name):
     assert normals_ref.rayleigh_check(c, [[2, 0, 0]]) == 1 and normals_ref.rayleigh_check(c, [[np.nan, 0, 0]]) == 1
 
 
+# (sum, max) of the nodes pcc_knn_replay_host reports per case at k = 3, 8, 16, 32, recorded from the library built at
+# commit 4c134a5 (the last one with a walk of its own in knn.hip): the shared walk has to visit what that one visited
+NODES_AT_4C134A5 = {
+    "frame sizes": {3: (376786, 595), 8: (648341, 752), 16: (932665, 968), 32: (1345727, 1217)},
+    "ties": {3: (33094, 228), 8: (56459, 298), 16: (78063, 332), 32: (109559, 387)},
+    "range and pruning": {3: (114263, 361), 8: (190162, 459), 16: (281353, 545), 32: (430385, 654)},
+    "flat": {3: (2275, 73), 8: (3131, 79), 16: (4078, 79), 32: (5176, 79)},
+}
+
+
 def _replay(keys, k):
     lib = pkg("_abi").lib()
     keys = np.ascontiguousarray(keys, np.uint64)
@@ -174,7 +184,7 @@ def _replay(keys, k):
 @pytest.mark.parametrize("name", list(CASES))
 def test_traversal_replayed_on_the_host(cases, name, k):
     """the kernel's search and epilogue, compiled for the host, against the restatement; a query tries no more nodes
-    than its frame's octree has (at most 16 per row) beside its k seeds"""
+    than its frame's octree has (at most 16 per row) beside its k seeds, and the case as many as recorded"""
     case = cases[name]
     want_rows, want_d2, want_cov = case.expected(k)
     rc, rows, d2, cov, normals, nodes = _replay(case.keys, k)
@@ -183,6 +193,7 @@ def test_traversal_replayed_on_the_host(cases, name, k):
     _check_normals(case, cov, normals)
     per_point = np.concatenate([np.full(f.shape[0], f.shape[0]) for f in case.frames])
     assert np.all(nodes <= k + 16 * per_point) and np.all(nodes >= np.minimum(k, per_point))
+    assert (int(nodes.sum(dtype=np.uint64)), int(nodes.max())) == NODES_AT_4C134A5[name][k]
 
 
 def test_replay_refusals():
@@ -443,6 +454,48 @@ def test_nn_d2_frames_against_the_restatement(rt, lossy):
     keep[1::4] = False
     kept = want["proj_ab"][order] * keep
     assert np.array_equal(proj.cpu().numpy(), kept) and abs(sums[0] - math.fsum(kept.tolist())) <= _sum_bound(kept) and sums[1] == 0.0
+
+
+@pytest.mark.gpu
+def test_per_frame_rounds_of_a_mixed_wave(rt):
+    """the reduction that pcc_nn_frames, pcc_nn_attr_sse_frames and pcc_nn_d2_frames share, on the smallest shape in
+    which its rounds per frame, its choice of a leader and a partial wave can go wrong together: 70 queries (one full
+    wave and 6 lanes of a second), three frames interleaved lane by lane, frame 1 without a reference (all of its
+    lanes are invalid, lane 1 among them) and one query of frame 0 whose row is taken away"""
+    import torch
+    rng = np.random.default_rng(61)
+    q = rng.integers(-20, 20, (70, 3))
+    frame = np.arange(70) % 3
+    refs = [nn_ref.morton_sorted_unique(rng.integers(-20, 20, (25, 3))), np.zeros((0, 3), np.int64),
+            nn_ref.morton_sorted_unique(rng.integers(-20, 20, (9, 3)))]
+    d2s, rows, stats = nn_ref.nn_frames([q[frame == f] for f in range(3)], refs)
+    want_d2, want_row = np.zeros(70, np.uint64), np.zeros(70, np.int64)
+    for f in range(3):
+        want_d2[frame == f], want_row[frame == f] = d2s[f], rows[f]
+    assert stats[1] == [0, 0, 0] and np.all(want_row[frame == 1] == -1) and stats[0][0] == 24 and stats[2][0] == 23
+    qkeys = _dev(rt, np.concatenate([nn_ref.morton_keys(q[i:i + 1], int(frame[i])) for i in range(70)]))
+    rkeys = _dev(rt, np.concatenate([nn_ref.morton_keys(r, f) for f, r in enumerate(refs)]))
+    sqdist, row, got_stats = rt.nn_frames(qkeys, rkeys, 3)
+    assert np.array_equal(sqdist.cpu().numpy().view(np.uint64), want_d2) and np.array_equal(row.cpu().numpy(), want_row)
+    assert got_stats == stats
+    want_row[3] = -1      # lane 3, frame 0: the wave's first round loses a lane behind its leader
+    row[3] = -1
+    keep = want_row >= 0
+    rpts = np.concatenate(refs)
+    a, b = rng.integers(0, 256, (70, 3)).astype(np.uint8), rng.integers(0, 256, (rpts.shape[0], 3)).astype(np.uint8)
+    a[0], b[:] = 255, 0      # the largest difference, whichever row the first query gets
+    sq = (a.astype(np.int64) - b.astype(np.int64)[np.where(keep, want_row, 0)]) ** 2 * keep[:, None]
+    got = rt.nn_attr_sse_frames(qkeys, row, torch.from_numpy(a).to(rt.device), torch.from_numpy(b).to(rt.device), 3)
+    assert got == [[int(v) for v in sq[frame == f].sum(0)] for f in range(3)] and got[1] == [0, 0, 0]
+    n = rng.normal(size=(70, 3))
+    n = (n / np.linalg.norm(n, axis=1, keepdims=True)).astype(np.float32)
+    want_proj = normals_ref.proj(q, rpts[np.where(keep, want_row, 0)], n) * keep
+    proj, sums = rt.nn_d2_frames(qkeys, row, rkeys, torch.from_numpy(n).to(rt.device), 3, want_proj=True)
+    assert np.array_equal(proj.cpu().numpy(), want_proj)      # bit for bit
+    for f in range(3):
+        mine = want_proj[frame == f]
+        assert abs(sums[f] - math.fsum(mine.tolist())) <= _sum_bound(mine), f
+    assert sums[1] == 0.0 and sums[0] > 0 and sums[2] > 0
 
 
 @pytest.mark.gpu
