@@ -394,7 +394,11 @@ int pcc_linear_gather(pcc_ctx* ctx, const float* d_in, const uint32_t* d_rows,
 
 /* replaces: the per-frame top-k occupancy pruning inside model.g_s(y_hat,k=ks)
  * (codec_parallel.py:469): within each batch segment keep the k[b] rows with
- * the largest logit (ties: lower row first).  d_keep_rows receives the kept
+ * the largest logit (ties: lower row first).  "Largest" is the order of the
+ * logit's bit image (sign bit set: all bits complemented, else the sign bit
+ * set; compared as uint32), which is the order of the values wherever they
+ * have one and fixes the rest: -0.0 below +0.0, a positive NaN above +inf, a
+ * negative NaN below -inf, NaNs among themselves by payload.  d_keep_rows receives the kept
  * row indices in ascending order; *h_n_keep their number.  h_offsets as from
  * pcc_batch_offsets (n_batch+1 entries), h_k n_batch entries.  The number of
  * kept rows is sum_f min(k[f], rows of frame f) by construction (no read-back);

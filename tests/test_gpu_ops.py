@@ -175,7 +175,8 @@ def test_batch_offsets(rt, oracle, clouds):
     assert offs == oracle.batch_offsets(keys, 3)
 
 
-@pytest.mark.parametrize("n", [1, 7, 2047, 2048, 2049, 4096, 100_003, 3_262_640, 20_000_000])
+@pytest.mark.parametrize("n", [1, 7, 2047, 2048, 2049, 4096, 100_003, 3_262_640, 4_194_303, 4_194_304, 4_194_305,
+                               4_196_353, 20_000_000])
 def test_exclusive_scan(rt, n):
     """sizes from one tile to ~10k tiles (one to three levels of recursion), repeated on the same ctx, in place
     and out of place, with values that wrap mod 2^32"""
