@@ -14,6 +14,7 @@
 
 static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
 
+// (restated in tests/map_cases.py, with its inverse: the probe-chain tests place valid keys on one home slot)
 __device__ __forceinline__ uint64_t hash64(uint64_t k) {
   k ^= k >> 33;
   k *= 0xff51afd7ed558ccdull;
@@ -396,6 +397,7 @@ extern "C" int pcc_inverse_rows(pcc_ctx* ctx, const uint32_t* d_rows, int64_t m,
   return PCC_OK;
 }
 
+// (restated in tests/map_cases.py: the probe-chain tests make their chains for the capacity of their row count)
 static int64_t hash_capacity(int64_t n) {
   int64_t cap = 1024;
   while (cap < 4 * n) cap <<= 1;  // load factor <= 0.25: short probe sequences (the rounds of k_build_map27)
