@@ -150,6 +150,38 @@ int pcc_arena_reserve(pcc_ctx* c, size_t bytes);
 void* pcc_arena_alloc(pcc_ctx* c, size_t bytes);
 
 static inline size_t pcc_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// blocks of t threads that cover n items
+static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
+
+// ---- prefix sums inside a wave and a workgroup (scan.hip, sort.hip, pyramid.hip, topk.hip) ----------------------
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    uint32_t t = __shfl_up(v, d, 64);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+// exclusive scan of one value per thread over a workgroup of THREADS; returns the exclusive prefix, and the
+// workgroup's total through *total (valid in every thread)
+template <int THREADS>
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* total, uint32_t* lds /*[THREADS / 64]*/) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t inc = wave_incl_scan(v);
+  if (lane == 63) lds[wave] = inc;
+  __syncthreads();
+  uint32_t base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < THREADS / 64; ++w) {
+    uint32_t s = lds[w];
+    if (w < wave) base += s;
+    tot += s;
+  }
+  __syncthreads();
+  *total = tot;
+  return base + inc - v;
+}
 
 // ---- Morton helpers (host + device) ---------------------------------------
 // spread the low 16 bits of v so that bit i lands at bit 3i

@@ -25,8 +25,6 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 #define GC_WAVES 4
 #ifndef PCC_FIRST_DEPTH
 #define PCC_FIRST_DEPTH 8

@@ -12,8 +12,6 @@
 // (the order CompressAI flattens [B,C,N] in).
 #include "common.h"
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 // thread t -> (ch = t / n, i = t % n): coalesced channel-major writes
 __global__ __launch_bounds__(256) void k_factorized_quant(const float* __restrict__ z, int64_t n, int c,
                                                           const float* __restrict__ med,

@@ -23,8 +23,6 @@
 #include <algorithm>
 #include <math.h>
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 #define KNN_NO_DIST (~0ull)
 #define KNN_NO_ROW 0x7FFFFFFF
 

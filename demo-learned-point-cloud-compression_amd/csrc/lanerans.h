@@ -14,8 +14,6 @@ namespace {
 
 constexpr int kLanes = 64;
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 // the initial probability of a one from the zeros and ones a context saw over the whole frame
 __host__ __device__ inline uint32_t o2_p0(uint64_t c0, uint64_t c1) {
   const uint64_t p = (4096ull * (2 * c1 + 1)) / (2 * (c0 + c1 + 1));

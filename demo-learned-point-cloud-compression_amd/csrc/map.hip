@@ -12,8 +12,6 @@
 
 #define HASH_EMPTY (~0ull)
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 // (restated in tests/map_cases.py, with its inverse: the probe-chain tests place valid keys on one home slot)
 __device__ __forceinline__ uint64_t hash64(uint64_t k) {
   k ^= k >> 33;

@@ -9,8 +9,6 @@
 // Three plain data-parallel passes: no LDS, every global access guarded by the row count.
 #include "common.h"
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 // one coordinate: *q = rint((x - o) / v) as a float; 0 = on the grid, 1 = finite but off the grid, 2 = not finite
 __device__ __forceinline__ int quantise(float x, float o, float v, float* q) {
   if (!(fabsf(x) <= 3.402823466e+38f)) return 2;   // NaN, +Inf, -Inf

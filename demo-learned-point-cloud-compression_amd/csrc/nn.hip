@@ -21,8 +21,6 @@
 #include "nn_cells.h"
 #include <algorithm>
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 // bit 0: equal neighbours, bit 1: descending neighbours, bit 2: a reference key's frame index >= n_frames,
 // bit 3: a query key's frame index >= n_frames
 __global__ __launch_bounds__(256) void k_nn_check(const uint64_t* __restrict__ rkeys, int64_t n_r,

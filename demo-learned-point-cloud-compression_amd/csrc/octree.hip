@@ -17,8 +17,6 @@
 // whatever the depth.
 #include "common.h"
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 // ---- single-workgroup form (n <= OCT_SMALL_MAX): every level in one launch, from the leaves alone -----------
 // Latent frames are ~1e3..3e4 leaves; per-level launches are pure launch latency for them, and walking the
 // levels bottom-up inside one workgroup still pays a dependent global round trip per level (117 us for the

@@ -10,8 +10,6 @@
 //   up  : h_s / g_s generative up stages (codec_pipeline.py:354, codec_parallel.py:376,469)
 #include "common.h"
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 __global__ void k_parent_flags(const uint64_t* __restrict__ keys, int64_t n, int pshift,
                                uint32_t* __restrict__ flags) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -133,32 +131,6 @@ extern "C" int pcc_down_coords_known(pcc_ctx* ctx, const uint64_t* d_keys, int64
 #define DC_ITEMS 8
 #define DC_TILE (DC_THREADS * DC_ITEMS)
 
-__device__ __forceinline__ uint32_t dc_wave_incl(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(v, d, 64);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t dc_block_excl(uint32_t v, uint32_t* total, uint32_t* lds /*[4]*/) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t inc = dc_wave_incl(v);
-  if (lane == 63) lds[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < DC_THREADS / 64; ++w) {
-    const uint32_t sv = lds[w];
-    if (w < wave) base += sv;
-    tot += sv;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
-
 // (also presets the kernel-2 rule book, 8 m entries, to -1 = "octant without a child": the emit launch follows)
 __global__ __launch_bounds__(DC_THREADS) void k_parent_tile_counts(const uint64_t* __restrict__ keys, int64_t n, int pshift,
                                                                    uint32_t* __restrict__ sums, int32_t* __restrict__ nbr8,
@@ -178,7 +150,7 @@ __global__ __launch_bounds__(DC_THREADS) void k_parent_tile_counts(const uint64_
     }
   }
   uint32_t tot;
-  dc_block_excl(c, &tot, lds);
+  block_excl_scan<DC_THREADS>(c, &tot, lds);
   if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 
@@ -192,7 +164,7 @@ __global__ __launch_bounds__(DC_THREADS) void k_parent_scan_emit(const uint64_t*
   uint32_t part = 0;
   for (int i = threadIdx.x; i < (int)blockIdx.x; i += DC_THREADS) part += sums[i];
   uint32_t tile_off;
-  dc_block_excl(part, &tile_off, lds);
+  block_excl_scan<DC_THREADS>(part, &tile_off, lds);
   uint64_t kv[DC_ITEMS];
   uint32_t f[DC_ITEMS];
   uint32_t c = 0;
@@ -207,7 +179,7 @@ __global__ __launch_bounds__(DC_THREADS) void k_parent_scan_emit(const uint64_t*
     c += f[j];
   }
   uint32_t tot;
-  uint32_t ex = dc_block_excl(c, &tot, lds) + tile_off;   // parents started in front of this thread's first key
+  uint32_t ex = block_excl_scan<DC_THREADS>(c, &tot, lds) + tile_off;   // parents started in front of this thread's first key
 #pragma unroll
   for (int j = 0; j < DC_ITEMS; ++j) {
     const int64_t i = base + j;

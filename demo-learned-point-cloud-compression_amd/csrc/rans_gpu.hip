@@ -48,8 +48,6 @@ constexpr int kLanes = 64;
 constexpr int kChunksPerWg = 4;
 constexpr int kHeaderWords = 4;
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 }  // namespace
 
 struct pcc_rans_dev {

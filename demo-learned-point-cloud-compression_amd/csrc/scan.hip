@@ -18,36 +18,6 @@
 #define SCAN_ITEMS 8
 #define SCAN_TILE (SCAN_THREADS * SCAN_ITEMS)
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    uint32_t t = __shfl_up(v, d, 64);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-
-// block-wide exclusive scan of one value per thread; returns exclusive prefix
-// and the block total through *total (valid in every thread).
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* total,
-                                                    uint32_t* lds /*[8]*/) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = wave_incl_scan(v);
-  if (lane == 63) lds[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < SCAN_THREADS / 64; ++w) {
-    uint32_t s = lds[w];
-    if (w < wave) base += s;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
-
 __global__ __launch_bounds__(SCAN_THREADS) void k_scan_block_sums(
     const uint32_t* __restrict__ in, int64_t n, uint32_t* __restrict__ sums) {
   __shared__ uint32_t lds[8];
@@ -62,7 +32,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_block_sums(
       if (base + i < n) s += in[base + i];
   }
   uint32_t tot;
-  block_excl_scan(s, &tot, lds);
+  block_excl_scan<SCAN_THREADS>(s, &tot, lds);
   if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 
@@ -90,7 +60,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_apply(
   if constexpr (SUMS_RAW) {
     uint32_t part = 0;
     for (int i = threadIdx.x; i < (int)blockIdx.x; i += SCAN_THREADS) part += block_offs[i];
-    block_excl_scan(part, &tile_off, lds);
+    block_excl_scan<SCAN_THREADS>(part, &tile_off, lds);
   } else {
     tile_off = block_offs ? block_offs[blockIdx.x] : 0u;
   }
@@ -98,7 +68,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_apply(
 #pragma unroll
   for (int i = 0; i < SCAN_ITEMS; ++i) s += v[i];
   uint32_t tot;
-  uint32_t ex = block_excl_scan(s, &tot, lds);
+  uint32_t ex = block_excl_scan<SCAN_THREADS>(s, &tot, lds);
   ex += tile_off;
   uint32_t o[SCAN_ITEMS];
 #pragma unroll
@@ -133,27 +103,27 @@ int pcc_scan_exclusive_u32(pcc_ctx* ctx, const uint32_t* d_in, uint32_t* d_out,
     if (d_total) PCC_HIP(hipMemsetAsync(d_total, 0, 4, ctx->stream));
     return PCC_OK;
   }
-  const int64_t nblk = (n + SCAN_TILE - 1) / SCAN_TILE;
-  if (nblk == 1) {
+  const int64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
+  if (tiles == 1) {
     hipLaunchKernelGGL((k_scan_apply<false>), dim3(1), dim3(SCAN_THREADS), 0, ctx->stream,
                        d_in, d_out, n, (const uint32_t*)nullptr, d_total);
     PCC_CHECK_LAUNCH();
     return PCC_OK;
   }
-  uint32_t* sums = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nblk * 4);
+  uint32_t* sums = (uint32_t*)pcc_arena_alloc(ctx, (size_t)tiles * 4);
   if (!sums) return PCC_E_NOMEM;
-  hipLaunchKernelGGL(k_scan_block_sums, dim3((unsigned)nblk), dim3(SCAN_THREADS), 0,
+  hipLaunchKernelGGL(k_scan_block_sums, dim3((unsigned)tiles), dim3(SCAN_THREADS), 0,
                      ctx->stream, d_in, n, sums);
   PCC_CHECK_LAUNCH();
-  if (nblk <= SCAN_TILE) {
+  if (tiles <= SCAN_TILE) {
     // up to 2048 tiles (4M elements): every block sums the tiles before its own — two launches instead of three
-    hipLaunchKernelGGL((k_scan_apply<true>), dim3((unsigned)nblk), dim3(SCAN_THREADS), 0, ctx->stream, d_in, d_out, n,
+    hipLaunchKernelGGL((k_scan_apply<true>), dim3((unsigned)tiles), dim3(SCAN_THREADS), 0, ctx->stream, d_in, d_out, n,
                        (const uint32_t*)sums, d_total);
     PCC_CHECK_LAUNCH();
     return PCC_OK;
   }
-  PCC_TRY(pcc_scan_exclusive_u32(ctx, sums, sums, nblk, nullptr));
-  hipLaunchKernelGGL((k_scan_apply<false>), dim3((unsigned)nblk), dim3(SCAN_THREADS), 0,
+  PCC_TRY(pcc_scan_exclusive_u32(ctx, sums, sums, tiles, nullptr));
+  hipLaunchKernelGGL((k_scan_apply<false>), dim3((unsigned)tiles), dim3(SCAN_THREADS), 0,
                      ctx->stream, d_in, d_out, n, (const uint32_t*)sums, d_total);
   PCC_CHECK_LAUNCH();
   return PCC_OK;

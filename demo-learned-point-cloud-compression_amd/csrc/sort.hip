@@ -16,6 +16,114 @@
 #define RS_THREADS 256
 #define RS_WAVES (RS_THREADS / 64)
 
+// ---------------------------------------------------------------- rules the routes share, each stated once
+// The canonical order (the comment at k_compact_coord_keys says why it may be taken on a compact key).
+// shared/utils.py:131-132: (C * [1e15,1e10,1e5,1]).sum(dim=1) in int64
+__device__ __forceinline__ int64_t ck_decimal_key(const int4 c) {
+  return (int64_t)c.x * 1000000000000000ll + (int64_t)c.y * 10000000000ll + (int64_t)c.z * 100000ll + (int64_t)c.w;
+}
+// outside the range in which the decimal key orders rows like the tuple (b, x, y, z)
+__device__ __forceinline__ bool ck_out_of_range(const int4 c) {
+  return (c.x < 0) | (c.y <= -50000) | (c.y >= 50000) | (c.z <= -50000) | (c.z >= 50000) | (c.w <= -50000) |
+         (c.w >= 50000);
+}
+// per field: min, max, the bits in which rows differ from row 0 (the lowest such bit is the lowest set bit of
+// OR(c - min): both say "all rows are congruent mod 2^tz"); bad = some row is out of range.  One per thread while it
+// sweeps rows, one per workgroup in LDS, one per workgroup of k_ckm_range in memory.
+struct CkmPart { int mn[4], mx[4]; unsigned orv[4]; int bad; };
+__device__ __forceinline__ CkmPart ck_range_init() {
+  CkmPart r;
+#pragma unroll
+  for (int f = 0; f < 4; ++f) { r.mn[f] = 0x7fffffff; r.mx[f] = (int)0x80000000; r.orv[f] = 0u; }
+  r.bad = 0;
+  return r;
+}
+__device__ __forceinline__ void ck_range_add(CkmPart& r, const int4 c, const int4 row0) {
+  const int v[4] = {c.x, c.y, c.z, c.w};
+  const int r0[4] = {row0.x, row0.y, row0.z, row0.w};
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    r.mn[f] = min(r.mn[f], v[f]);
+    r.mx[f] = max(r.mx[f], v[f]);
+    r.orv[f] |= (unsigned)(v[f] ^ r0[f]);
+  }
+  r.bad |= ck_out_of_range(c) ? 1 : 0;
+}
+// the range over the 64 lanes of a wave, in every lane
+__device__ __forceinline__ CkmPart ck_range_wave(CkmPart r) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      r.mn[f] = min(r.mn[f], __shfl_xor(r.mn[f], d, 64));
+      r.mx[f] = max(r.mx[f], __shfl_xor(r.mx[f], d, 64));
+      r.orv[f] |= (unsigned)__shfl_xor((int)r.orv[f], d, 64);
+    }
+  }
+  r.bad = __any(r.bad != 0) ? 1 : 0;
+  return r;
+}
+// a wave's range into the workgroup's LDS copy (reduce in the wave first: 1024 lanes hitting the same 12 LDS words
+// serialise — that alone was ~30 us)
+__device__ __forceinline__ void ck_range_fold(CkmPart* lds, const CkmPart& r) {
+  if ((threadIdx.x & 63) != 0) return;
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    atomicMin(&lds->mn[f], r.mn[f]);
+    atomicMax(&lds->mx[f], r.mx[f]);
+    atomicOr(&lds->orv[f], r.orv[f]);
+  }
+  if (r.bad) atomicOr(&lds->bad, 1);
+}
+// from the range of all rows: per field the minimum, the trailing zero bits every row shares and the bits that remain;
+// compact = the compact key exists (rows in range, 63 bits at the most)
+struct CkmParams { int m[4], tz[4], w[4], total; bool compact; };
+__device__ __forceinline__ CkmParams ck_widths(const CkmPart& r) {
+  CkmParams q;
+  q.total = 0;
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    const unsigned o = r.orv[f];
+    q.m[f] = r.mn[f];
+    q.tz[f] = o ? __builtin_ctz(o) : 0;
+    const unsigned span = ((unsigned)(r.mx[f] - r.mn[f])) >> q.tz[f];
+    q.w[f] = span ? 32 - __builtin_clz(span) : 0;
+    q.total += q.w[f];
+  }
+  q.compact = r.bad == 0 && q.total <= 63;
+  return q;
+}
+__device__ __forceinline__ uint64_t ckm_key(const CkmParams& q, const int4 c) {
+  uint64_t k = (uint64_t)((unsigned)(c.x - q.m[0]) >> q.tz[0]);
+  k = (k << q.w[1]) | (uint64_t)((unsigned)(c.y - q.m[1]) >> q.tz[1]);
+  k = (k << q.w[2]) | (uint64_t)((unsigned)(c.z - q.m[2]) >> q.tz[2]);
+  k = (k << q.w[3]) | (uint64_t)((unsigned)(c.w - q.m[3]) >> q.tz[3]);
+  return k;
+}
+
+// The radix sort.  OR and AND of a wave's keys, in every lane: a digit varies where they differ
+__device__ __forceinline__ void wave_key_bits(uint64_t& o, uint64_t& a) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    o |= __shfl_xor((unsigned long long)o, d, 64);
+    a &= __shfl_xor((unsigned long long)a, d, 64);
+  }
+}
+// Stable rank of a lane's digit by match-ballot: rank = the valid lanes below this one that hold the same digit,
+// count = all the valid lanes that hold it.  (The caller adds rank to the digit's running base and lets the lane of
+// rank 0 advance the base by count between two wave barriers: that is what keeps equal digits in input order.)
+struct DigitRank { uint32_t rank, count; };
+__device__ __forceinline__ DigitRank wave_digit_rank(uint32_t d, bool valid, uint64_t lanes_below) {
+  uint64_t mask = __ballot(valid);
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const bool bit = (d >> b) & 1u;
+    const uint64_t bal = __ballot(bit);
+    mask &= bit ? bal : ~bal;
+  }
+  return {(uint32_t)__popcll(mask & lanes_below), (uint32_t)__popcll(mask)};
+}
+
 // ---------------------------------------------------------------- key kernels
 // n_batch: batch indexes must lie below it (65535 = any legal index)
 __global__ void k_morton_keys(const int4* __restrict__ coords, int64_t n,
@@ -42,10 +150,7 @@ __global__ void k_linear_keys(const int4* __restrict__ coords, int64_t n,
                               int64_t* __restrict__ keys) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  int4 c = coords[i];
-  // shared/utils.py:131-132: (C * [1e15,1e10,1e5,1]).sum(dim=1) in int64
-  keys[i] = (int64_t)c.x * 1000000000000000ll + (int64_t)c.y * 10000000000ll +
-            (int64_t)c.z * 100000ll + (int64_t)c.w;
+  keys[i] = ck_decimal_key(coords[i]);
 }
 
 // ---------------------------------------------------------------- radix sort
@@ -59,11 +164,7 @@ __global__ __launch_bounds__(256) void k_key_bits(const uint64_t* __restrict__ k
     o |= k;
     a &= k;
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    o |= __shfl_xor((unsigned long long)o, d, 64);
-    a &= __shfl_xor((unsigned long long)a, d, 64);
-  }
+  wave_key_bits(o, a);
   // one atomic pair per block (same-address atomics serialise at the memory side)
   __shared__ unsigned long long s_o[4], s_a[4];
   if ((threadIdx.x & 63) == 0) { s_o[threadIdx.x >> 6] = o; s_a[threadIdx.x >> 6] = a; }
@@ -131,19 +232,11 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_scatter(
     const uint64_t key = keys[r];
     const uint32_t val = vals[r];
     const uint32_t d = (uint32_t)(((key ^ flip) >> shift) & 255u);
-    uint64_t mask = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const uint64_t bal = __ballot(bit);
-      mask &= bit ? bal : ~bal;
-    }
-    const uint32_t rank = (uint32_t)__popcll(mask & lanes_below);
-    const uint32_t cnt = (uint32_t)__popcll(mask);
+    const DigitRank dr = wave_digit_rank(d, valid, lanes_below);
     uint32_t pos = 0;
-    if (valid) pos = base[d] + rank;
+    if (valid) pos = base[d] + dr.rank;
     __builtin_amdgcn_wave_barrier();
-    if (valid && rank == 0) base[d] = pos + cnt;
+    if (valid && dr.rank == 0) base[d] = pos + dr.count;
     __builtin_amdgcn_wave_barrier();
     if (valid) {
       keys_out[pos] = key;
@@ -156,8 +249,6 @@ __global__ void k_iota(uint32_t* __restrict__ p, int64_t n) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = (uint32_t)i;
 }
-
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
 
 static size_t sort_scratch_bytes(int64_t n) {
   const int64_t nw = (n + RS_WAVE_TILE - 1) / RS_WAVE_TILE;
@@ -207,11 +298,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_sort_small(uint64_t* __restrict_
 #pragma unroll
       for (int u = 0; u < 4; ++u) { o |= k[u]; a &= k[u]; }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      o |= __shfl_xor((unsigned long long)o, d, 64);
-      a &= __shfl_xor((unsigned long long)a, d, 64);
-    }
+    wave_key_bits(o, a);
     if (lane == 0) { atomicOr(&s_or, (unsigned long long)o); atomicAnd(&s_and, (unsigned long long)a); }
   }
   __syncthreads();
@@ -266,12 +353,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_sort_small(uint64_t* __restrict_
     if (tid < 256) {
       for (int w = 0; w < SS_WAVES; ++w) { const uint32_t c = cnt[w][tid]; cnt[w][tid] = tot; tot += c; }
     }
-    uint32_t inc = tot;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t t = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += t;
-    }
+    const uint32_t inc = wave_incl_scan(tot);
     if (lane == 63) s_wsum[wave] = inc;
     __syncthreads();
     if (tid < 256) {
@@ -300,19 +382,11 @@ __global__ __launch_bounds__(SS_THREADS) void k_sort_small(uint64_t* __restrict_
       const uint64_t key = valid ? pk[u] : 0ull;
       const uint32_t val = valid ? pv[u] : 0u;
       const uint32_t d = (uint32_t)(((key ^ flip) >> shift) & 255u);
-      uint64_t mask = __ballot(valid);
-#pragma unroll
-      for (int b = 0; b < 8; ++b) {
-        const bool bit = (d >> b) & 1u;
-        const uint64_t bal = __ballot(bit);
-        mask &= bit ? bal : ~bal;
-      }
-      const uint32_t rank = (uint32_t)__popcll(mask & lanes_below);
-      const uint32_t c = (uint32_t)__popcll(mask);
+      const DigitRank dr = wave_digit_rank(d, valid, lanes_below);
       uint32_t pos = 0;
-      if (valid) pos = base[d] + rank;
+      if (valid) pos = base[d] + dr.rank;
       __builtin_amdgcn_wave_barrier();
-      if (valid && rank == 0) base[d] = pos + c;
+      if (valid && dr.rank == 0) base[d] = pos + dr.count;
       __builtin_amdgcn_wave_barrier();
       if (valid) { kout[pos] = key; vout[pos] = val; }
       }
@@ -589,81 +663,29 @@ __global__ __launch_bounds__(SS_THREADS) void k_compact_coord_keys(const int4* _
                                                                    uint32_t* __restrict__ perm,
                                                                    int* __restrict__ done,
                                                                    int4* __restrict__ sorted_out) {
-  __shared__ int s_mn[4], s_mx[4], s_bad, s_dup;
-  __shared__ unsigned s_or[4];
+  __shared__ CkmPart s_rng;
+  __shared__ int s_dup;
   __shared__ uint32_t s_chunk[SS_THREADS], s_wsum[SS_WAVES];
   __shared__ uint32_t bm[(1 << CK_BITMAP_BITS) / 32];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid < 4) { s_mn[tid] = 0x7fffffff; s_mx[tid] = (int)0x80000000; s_or[tid] = 0u; }
-  if (tid == 0) { s_bad = 0; s_dup = 0; }
+  if (tid == 0) { s_rng = ck_range_init(); s_dup = 0; }
   __syncthreads();
-  // one sweep: min / max per field, range check, and the bits in which rows differ from row 0 (the lowest such
-  // bit is the lowest set bit of OR(c - min): both say "all rows are congruent mod 2^tz")
+  // one sweep: the range of every field and the range check
   const int4 c0 = coords[0];
-  int mn[4] = {0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff};
-  int mx[4] = {(int)0x80000000, (int)0x80000000, (int)0x80000000, (int)0x80000000};
-  unsigned orv[4] = {0u, 0u, 0u, 0u};
-  bool bad = false;
+  CkmPart rng = ck_range_init();
   for (int e0 = tid; e0 < n; e0 += CK_U * SS_THREADS) {
     int4 cc[CK_U];  // CK_U independent loads in flight per lane (clamped index: duplicates do not change min / max / or)
 #pragma unroll
     for (int u = 0; u < CK_U; ++u) cc[u] = coords[min(e0 + u * SS_THREADS, n - 1)];
 #pragma unroll
-    for (int u = 0; u < CK_U; ++u) {
-      const int4 c = cc[u];
-      const int v[4] = {c.x, c.y, c.z, c.w};
-      const int r[4] = {c0.x, c0.y, c0.z, c0.w};
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        mn[f] = min(mn[f], v[f]);
-        mx[f] = max(mx[f], v[f]);
-        orv[f] |= (unsigned)(v[f] ^ r[f]);
-      }
-      bad |= (c.x < 0) | (c.y <= -50000) | (c.y >= 50000) | (c.z <= -50000) | (c.z >= 50000) | (c.w <= -50000) |
-             (c.w >= 50000);
-    }
+    for (int u = 0; u < CK_U; ++u) ck_range_add(rng, cc[u], c0);
   }
-  // reduce in the wave first: 1024 lanes hitting the same 12 LDS words serialise (that alone was ~30 us)
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      mn[f] = min(mn[f], __shfl_xor(mn[f], d, 64));
-      mx[f] = max(mx[f], __shfl_xor(mx[f], d, 64));
-      orv[f] |= (unsigned)__shfl_xor((int)orv[f], d, 64);
-    }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      atomicMin(&s_mn[f], mn[f]);
-      atomicMax(&s_mx[f], mx[f]);
-      atomicOr(&s_or[f], orv[f]);
-    }
-  }
-  if (__any(bad) && lane == 0) atomicOr(&s_bad, 1);
+  ck_range_fold(&s_rng, ck_range_wave(rng));
   __syncthreads();
-  int tz[4], w[4], total = 0;
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    const unsigned o = s_or[f];
-    tz[f] = o ? __builtin_ctz(o) : 0;
-    const unsigned span = ((unsigned)(s_mx[f] - s_mn[f])) >> tz[f];
-    w[f] = span ? 32 - __builtin_clz(span) : 0;
-    total += w[f];
-  }
-  const bool compact = !s_bad && total <= 63;
-  const int m0 = s_mn[0], m1 = s_mn[1], m2 = s_mn[2], m3 = s_mn[3];
-  auto compact_key = [&](const int4 c) -> uint64_t {
-    uint64_t k = (uint64_t)((unsigned)(c.x - m0) >> tz[0]);
-    k = (k << w[1]) | (uint64_t)((unsigned)(c.y - m1) >> tz[1]);
-    k = (k << w[2]) | (uint64_t)((unsigned)(c.z - m2) >> tz[2]);
-    k = (k << w[3]) | (uint64_t)((unsigned)(c.w - m3) >> tz[3]);
-    return k;
-  };
+  const CkmParams q = ck_widths(s_rng);
 
-  if (compact && total <= CK_BITMAP_BITS) {  // block-uniform
-    const int nwords = max((1 << total) >> 5, 1);
+  if (q.compact && q.total <= CK_BITMAP_BITS) {  // block-uniform
+    const int nwords = max((1 << q.total) >> 5, 1);
     for (int j = tid; j < nwords; j += SS_THREADS) bm[j] = 0u;
     __syncthreads();
     bool dup = false;
@@ -674,7 +696,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_compact_coord_keys(const int4* _
 #pragma unroll
       for (int u = 0; u < CK_U; ++u) {
         if (e0 + u * SS_THREADS < n) {
-          const uint32_t k = (uint32_t)compact_key(cc[u]);
+          const uint32_t k = (uint32_t)ckm_key(q, cc[u]);
           const uint32_t bit = 1u << (k & 31u);
           dup |= (atomicOr(&bm[k >> 5], bit) & bit) != 0u;
         }
@@ -687,16 +709,11 @@ __global__ __launch_bounds__(SS_THREADS) void k_compact_coord_keys(const int4* _
       const int nw = (nwords + SS_THREADS - 1) / SS_THREADS;
       uint32_t sum = 0;
       for (int j = tid * nw; j < min((tid + 1) * nw, nwords); ++j) sum += (uint32_t)__popc(bm[j]);
-      uint32_t inc = sum;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-      }
+      const uint32_t inc = wave_incl_scan(sum);
       if (lane == 63) s_wsum[wave] = inc;
       __syncthreads();
       uint32_t base = inc - sum;
-      for (int q = 0; q < wave; ++q) base += s_wsum[q];
+      for (int w = 0; w < wave; ++w) base += s_wsum[w];
       s_chunk[tid] = base;
       __syncthreads();
       for (int e0 = tid; e0 < n; e0 += CK_U * SS_THREADS) {
@@ -707,7 +724,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_compact_coord_keys(const int4* _
         for (int u = 0; u < CK_U; ++u) {
           const int e = e0 + u * SS_THREADS;
           if (e < n) {
-            const uint32_t k = (uint32_t)compact_key(cc[u]);
+            const uint32_t k = (uint32_t)ckm_key(q, cc[u]);
             const int wi = (int)(k >> 5), ch = wi / nw;
             uint32_t r = s_chunk[ch];
             for (int j = ch * nw; j < wi; ++j) r += (uint32_t)__popc(bm[j]);
@@ -729,16 +746,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_compact_coord_keys(const int4* _
 #pragma unroll
     for (int u = 0; u < CK_U; ++u) {
       const int e = e0 + u * SS_THREADS;
-      const int4 c = cc[u];
-      uint64_t k;
-      if (compact) {
-        k = compact_key(c);
-      } else {
-        const int64_t lin = (int64_t)c.x * 1000000000000000ll + (int64_t)c.y * 10000000000ll +
-                            (int64_t)c.z * 100000ll + (int64_t)c.w;
-        k = (uint64_t)lin ^ (1ull << 63);
-      }
-      if (e < n) keys[e] = k;
+      if (e < n) keys[e] = q.compact ? ckm_key(q, cc[u]) : (uint64_t)ck_decimal_key(cc[u]) ^ (1ull << 63);
     }
   }
 }
@@ -755,121 +763,50 @@ __global__ __launch_bounds__(SS_THREADS) void k_compact_coord_keys(const int4* _
 constexpr int CKM_THREADS = 256;
 constexpr int CKM_ROWS = 1024;          // rows per workgroup
 constexpr int64_t CKM_MIN = 8192;       // below: the single-workgroup kernel (10-13 us at 2-3k rows)
-struct CkmPart { int mn[4], mx[4]; unsigned orv[4]; int bad; };
-struct CkmParams { int m[4], tz[4], w[4], total; bool compact; };
+static_assert(SS_MAX / CKM_ROWS <= 64, "ckm_params reduces the workgroups' ranges in one wave");
 
-__device__ __forceinline__ CkmParams ckm_params(const CkmPart* __restrict__ part, int n_part, int* lds /* [16] */) {
+__device__ __forceinline__ CkmParams ckm_params(const CkmPart* __restrict__ part, int n_part, CkmPart* lds) {
   // n_part <= 64: one wave reduces the partial ranges, everybody reads the result
   if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    CkmPart p;
-    if (lane < n_part) p = part[lane];
-    else {
-#pragma unroll
-      for (int f = 0; f < 4; ++f) { p.mn[f] = 0x7fffffff; p.mx[f] = (int)0x80000000; p.orv[f] = 0u; }
-      p.bad = 0;
-    }
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) {
-        p.mn[f] = min(p.mn[f], __shfl_xor(p.mn[f], d, 64));
-        p.mx[f] = max(p.mx[f], __shfl_xor(p.mx[f], d, 64));
-        p.orv[f] |= (unsigned)__shfl_xor((int)p.orv[f], d, 64);
-      }
-    }
-    const int bad = __any(p.bad != 0) ? 1 : 0;
-    if (lane == 0) {
-#pragma unroll
-      for (int f = 0; f < 4; ++f) { lds[f] = p.mn[f]; lds[4 + f] = p.mx[f]; lds[8 + f] = (int)p.orv[f]; }
-      lds[12] = bad;
-    }
+    CkmPart p = ck_range_init();
+    if ((int)threadIdx.x < n_part) p = part[threadIdx.x];
+    p = ck_range_wave(p);
+    if (threadIdx.x == 0) *lds = p;
   }
   __syncthreads();
-  CkmParams q;
-  q.total = 0;
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    const unsigned o = (unsigned)lds[8 + f];
-    q.m[f] = lds[f];
-    q.tz[f] = o ? __builtin_ctz(o) : 0;
-    const unsigned span = ((unsigned)(lds[4 + f] - lds[f])) >> q.tz[f];
-    q.w[f] = span ? 32 - __builtin_clz(span) : 0;
-    q.total += q.w[f];
-  }
-  q.compact = lds[12] == 0 && q.total <= 63;
-  return q;
-}
-__device__ __forceinline__ uint64_t ckm_key(const CkmParams& q, const int4 c) {
-  uint64_t k = (uint64_t)((unsigned)(c.x - q.m[0]) >> q.tz[0]);
-  k = (k << q.w[1]) | (uint64_t)((unsigned)(c.y - q.m[1]) >> q.tz[1]);
-  k = (k << q.w[2]) | (uint64_t)((unsigned)(c.z - q.m[2]) >> q.tz[2]);
-  k = (k << q.w[3]) | (uint64_t)((unsigned)(c.w - q.m[3]) >> q.tz[3]);
-  return k;
+  return ck_widths(*lds);
 }
 
 __global__ __launch_bounds__(CKM_THREADS) void k_ckm_range(const uint64_t* __restrict__ mkeys, int n, int4* __restrict__ coords,
                                                            CkmPart* __restrict__ part, uint32_t* __restrict__ bitmap,
                                                            int* __restrict__ flags /* [0] dup */) {
-  __shared__ int s_mn[4], s_mx[4], s_bad;
-  __shared__ unsigned s_or[4];
-  const int tid = threadIdx.x, lane = tid & 63;
-  if (tid < 4) { s_mn[tid] = 0x7fffffff; s_mx[tid] = (int)0x80000000; s_or[tid] = 0u; }
-  if (tid == 0) s_bad = 0;
+  __shared__ CkmPart s_rng;
+  const int tid = threadIdx.x;
+  if (tid == 0) s_rng = ck_range_init();
   if (blockIdx.x == 0 && tid == 0) flags[0] = 0;
   // this workgroup's share of the 2^20-bit bitmap
   const int words = (1 << CK_BITMAP_BITS) / 32, per = (words + gridDim.x - 1) / gridDim.x;
   for (int j = blockIdx.x * per + tid; j < min((int)(blockIdx.x + 1) * per, words); j += CKM_THREADS) bitmap[j] = 0u;
   __syncthreads();
-  int b0, x0, y0, z0;
-  pcc_unmorton(mkeys[0], &b0, &x0, &y0, &z0);
-  const int r[4] = {b0, x0, y0, z0};
-  int mn[4] = {0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff};
-  int mx[4] = {(int)0x80000000, (int)0x80000000, (int)0x80000000, (int)0x80000000};
-  unsigned orv[4] = {0u, 0u, 0u, 0u};
-  bool bad = false;
+  int4 c0;
+  pcc_unmorton(mkeys[0], &c0.x, &c0.y, &c0.z, &c0.w);
+  CkmPart rng = ck_range_init();
   const int e_lo = blockIdx.x * CKM_ROWS, e_hi = min(e_lo + CKM_ROWS, n);
   for (int e = e_lo + tid; e < e_hi; e += CKM_THREADS) {
-    int b, x, y, z;
-    pcc_unmorton(mkeys[e], &b, &x, &y, &z);
-    coords[e] = make_int4(b, x, y, z);
-    const int v[4] = {b, x, y, z};
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      mn[f] = min(mn[f], v[f]);
-      mx[f] = max(mx[f], v[f]);
-      orv[f] |= (unsigned)(v[f] ^ r[f]);
-    }
-    bad |= (b < 0) | (x <= -50000) | (x >= 50000) | (y <= -50000) | (y >= 50000) | (z <= -50000) | (z >= 50000);
+    int4 c;
+    pcc_unmorton(mkeys[e], &c.x, &c.y, &c.z, &c.w);
+    coords[e] = c;
+    ck_range_add(rng, c, c0);
   }
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      mn[f] = min(mn[f], __shfl_xor(mn[f], d, 64));
-      mx[f] = max(mx[f], __shfl_xor(mx[f], d, 64));
-      orv[f] |= (unsigned)__shfl_xor((int)orv[f], d, 64);
-    }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int f = 0; f < 4; ++f) { atomicMin(&s_mn[f], mn[f]); atomicMax(&s_mx[f], mx[f]); atomicOr(&s_or[f], orv[f]); }
-  }
-  if (__any(bad) && lane == 0) atomicOr(&s_bad, 1);
+  ck_range_fold(&s_rng, ck_range_wave(rng));
   __syncthreads();
-  if (tid == 0) {
-    CkmPart p;
-#pragma unroll
-    for (int f = 0; f < 4; ++f) { p.mn[f] = s_mn[f]; p.mx[f] = s_mx[f]; p.orv[f] = s_or[f]; }
-    p.bad = s_bad;
-    part[blockIdx.x] = p;
-  }
+  if (tid == 0) part[blockIdx.x] = s_rng;
 }
 
 __global__ __launch_bounds__(CKM_THREADS) void k_ckm_bits(const int4* __restrict__ coords, int n, const CkmPart* __restrict__ part,
                                                           uint32_t* __restrict__ bitmap, int* __restrict__ flags) {
-  __shared__ int lds[16];
-  const CkmParams q = ckm_params(part, gridDim.x, lds);
+  __shared__ CkmPart lds;
+  const CkmParams q = ckm_params(part, gridDim.x, &lds);
   if (!(q.compact && q.total <= CK_BITMAP_BITS)) return;   // block-uniform
   const int e_lo = blockIdx.x * CKM_ROWS, e_hi = min(e_lo + CKM_ROWS, n);
   bool dup = false;
@@ -890,13 +827,13 @@ __global__ __launch_bounds__(SS_THREADS) void k_ckm_scan(const CkmPart* __restri
                                                          const uint32_t* __restrict__ bitmap, uint32_t* __restrict__ prefix,
                                                          const int* __restrict__ flags, int* __restrict__ done) {
   constexpr int kPer = (1 << CK_BITMAP_BITS) / 32 / SS_THREADS;   // rows of 1024 words: 32
-  __shared__ int lds[16];
+  __shared__ CkmPart lds;
   __shared__ uint32_t s_tot[kPer * SS_WAVES];   // totals of (row, wave), row-major = word order
   uint32_t pc[kPer];
 #pragma unroll
   for (int i = 0; i < kPer; ++i) pc[i] = (uint32_t)__popc(bitmap[threadIdx.x + i * SS_THREADS]);
   const int dup = flags[0];
-  const CkmParams q = ckm_params(part, n_part, lds);
+  const CkmParams q = ckm_params(part, n_part, &lds);
   const bool ok = q.compact && q.total <= CK_BITMAP_BITS && dup == 0;
   if (threadIdx.x == 0) *done = ok ? 1 : 0;
   if (!ok) return;
@@ -908,12 +845,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_ckm_scan(const CkmPart* __restri
   for (int i = 0; i < kPer; ++i) {
     if (i < rows) {
       const uint32_t c = tid + i * SS_THREADS < nwords ? pc[i] : 0u;
-      uint32_t inc = c;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-      }
+      const uint32_t inc = wave_incl_scan(c);
       ex[i] = inc - c;
       if (lane == 63) s_tot[i * SS_WAVES + wave] = inc;
     }
@@ -923,12 +855,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_ckm_scan(const CkmPart* __restri
     uint32_t carry = 0;
     for (int b0 = 0; b0 < rows * SS_WAVES; b0 += 64) {
       const uint32_t c = s_tot[b0 + lane];
-      uint32_t inc = c;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-      }
+      const uint32_t inc = wave_incl_scan(c);
       s_tot[b0 + lane] = carry + inc - c;
       carry += __shfl(inc, 63, 64);
     }
@@ -943,8 +870,8 @@ __global__ __launch_bounds__(CKM_THREADS) void k_ckm_place(const int4* __restric
                                                            const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ prefix,
                                                            const int* __restrict__ done, uint64_t* __restrict__ keys,
                                                            uint32_t* __restrict__ perm, int4* __restrict__ sorted_out) {
-  __shared__ int lds[16];
-  const CkmParams q = ckm_params(part, gridDim.x, lds);
+  __shared__ CkmPart lds;
+  const CkmParams q = ckm_params(part, gridDim.x, &lds);
   const bool placed = *done != 0;
   const int e_lo = blockIdx.x * CKM_ROWS, e_hi = min(e_lo + CKM_ROWS, n);
   for (int e = e_lo + threadIdx.x; e < e_hi; e += CKM_THREADS) {
@@ -954,12 +881,8 @@ __global__ __launch_bounds__(CKM_THREADS) void k_ckm_place(const int4* __restric
       const uint32_t r = prefix[k >> 5] + (uint32_t)__popc(bitmap[k >> 5] & ((1u << (k & 31u)) - 1u));
       perm[r] = (uint32_t)e;
       if (sorted_out) sorted_out[r] = c;
-    } else if (q.compact) {
-      keys[e] = ckm_key(q, c);
     } else {
-      const int64_t lin = (int64_t)c.x * 1000000000000000ll + (int64_t)c.y * 10000000000ll + (int64_t)c.z * 100000ll +
-                          (int64_t)c.w;
-      keys[e] = (uint64_t)lin ^ (1ull << 63);
+      keys[e] = q.compact ? ckm_key(q, c) : (uint64_t)ck_decimal_key(c) ^ (1ull << 63);
     }
   }
 }
@@ -990,6 +913,7 @@ extern "C" int pcc_sort_coords(pcc_ctx* ctx, const int32_t* d_coords, int64_t n,
 // rows [n,4] (b,x,y,z) in that order, for sets within the single-workgroup kernels (n <= pcc_sort_small_max()): the
 // keys are turned into coordinates by a plain parallel kernel (inside the one-workgroup kernel, which sweeps the rows
 // three times, the bit de-interleaving cost 28 us for 26k rows), the order kernel writes the ordered rows itself.
+// (Fields out of a Morton key are 16 bits wide, never ck_out_of_range: only pcc_sort_coords reaches the decimal-key branch.)
 int64_t pcc_sort_small_max() { return SS_MAX; }
 int pcc_sort_keys_canonical(pcc_ctx* ctx, const uint64_t* d_mkeys, int64_t n, uint32_t* d_perm, int32_t* d_sorted_coords) {
   PCC_REQUIRE(ctx && d_mkeys && d_perm && d_sorted_coords && n >= 1 && n <= SS_MAX, PCC_E_ARG,

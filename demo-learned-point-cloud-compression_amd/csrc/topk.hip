@@ -18,8 +18,6 @@
 #include <string.h>
 #include <algorithm>
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 struct TopkState {
   uint32_t prefix;     // threshold key bits fixed so far
   uint32_t k_rem;      // how many still to take among keys matching the prefix
@@ -68,12 +66,7 @@ __device__ __forceinline__ TopkState topk_state_after(TopkState s, const uint32_
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   for (int p = 0; p < passes; ++p) {
     const uint32_t c = t < 256 ? hist[((size_t)p * n_frames + f) * 256 + (255 - t)] : 0u;  // thread t holds digit 255 - t
-    uint32_t inc = c;  // inclusive prefix over descending digits = keys with digit >= 255 - t
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t u = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += u;
-    }
+    uint32_t inc = wave_incl_scan(c);  // inclusive prefix over descending digits = keys with digit >= 255 - t
     if (lane == 63 && wave < 4) lds[wave] = inc;
     __syncthreads();
     uint32_t base = 0;

@@ -11,8 +11,6 @@
 #include "common.h"
 #include <string.h>
 
-static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 __device__ __forceinline__ uint32_t f2ord(float v) {
   const uint32_t u = __float_as_uint(v);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);

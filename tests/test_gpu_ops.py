@@ -57,7 +57,7 @@ def test_morton_range_error(rt):
     assert e.value.code == -3
 
 
-@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 1000, 1024, 1025, 40000])
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 1000, 1024, 1025, 40000, 65536])
 def test_sort_pairs_matches_stable_argsort(rt, n):
     rng = np.random.default_rng(n)
     # few distinct values in some digits -> exercises pass skipping and stability
@@ -167,6 +167,88 @@ def test_sort_coords_routes(rt, oracle, case):
         c = np.concatenate([np.zeros((len(g), 1), np.int64), g], 1).astype(np.int32)
     perm = host(rt.sort_coords(dev(rt, c))).view(np.uint32)
     assert np.array_equal(perm, oracle.canonical_perm(c).astype(np.uint32))
+
+
+@pytest.fixture(scope="module")
+def sort_keys_canonical(rt):
+    """pcc_sort_keys_canonical (sort.hip) is an internal C++ entry point: bound by its mangled name, as
+    test_cpu.py::test_rans_gated_coders_equal_the_plain_ones binds the gated coders"""
+    import ctypes as C
+    import subprocess
+    names = subprocess.run(["nm", "-D", pkg("_abi").LIB_PATH], capture_output=True, text=True).stdout.split()
+    fn = getattr(rt.lib, next(s for s in names if "pcc_sort_keys_canonical" in s))
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+
+    def call(keys):
+        n = keys.shape[0]
+        perm = rt.empty((n,), torch.int32)
+        rows = rt.empty((n, 4), torch.int32)
+        code = fn(rt.ctx, keys.data_ptr(), n, perm.data_ptr(), rows.data_ptr())
+        assert code == 0, rt.lib.pcc_last_error().decode()
+        return host(perm).view(np.uint32), host(rows)
+    return call
+
+
+# (batches, nx, ny, nz) cells of stride 8 from a negative offset, and the width of the compact key they give
+CANON_DOMAINS = {"bitmap20": ((2, 128, 64, 64), 20), "wide21": ((2, 256, 64, 64), 21), "repeats20": ((2, 128, 64, 64), 20)}
+CANON_STRIDE, CANON_OFFSET = 8, -404
+# one row is a case of its own (no widths at all); two rows are the two corners of a domain; "repeats" appends a seventh
+# of the rows again, which takes eight rows or more
+CANON_CASES = [(1, "single")] + [(2, d) for d in ("bitmap20", "wide21")] + \
+              [(n, d) for n in (8191, 8192, 8193, 65536) for d in CANON_DOMAINS]
+
+
+def _canon_rows(rng, n, domain):
+    """n rows (b, x, y, z) of the domain: both extreme corners of every field, a row one stride from the low corner in
+    every field, the rest distinct cells drawn at once"""
+    if domain == "single":
+        return np.array([[1, -404, 20, 3]], np.int32)
+    dims = np.array(CANON_DOMAINS[domain][0])
+    cells = int(dims.prod())
+    fixed = np.array([0, cells - 1, int(np.ravel_multi_index((1, 1, 1, 1), dims))])[:min(n, 3)]
+    n_rep = n // 8 if domain == "repeats20" else 0           # a seventh of the n - n // 8 distinct rows
+    drawn = rng.choice(cells, n, replace=False)
+    idx = np.concatenate([fixed, drawn[~np.isin(drawn, fixed)][:n - n_rep - len(fixed)]])
+    idx = np.concatenate([idx, rng.choice(idx, n_rep, replace=False)])
+    f = np.stack(np.unravel_index(idx, dims), 1)
+    f[:, 1:] = f[:, 1:] * CANON_STRIDE + CANON_OFFSET
+    return f.astype(np.int32)
+
+
+def _canon_total_width(rows):
+    """the width rule of the canonical order, restated: per field min, max, OR of the differences from row 0, the
+    trailing zeros every row shares, the bits that remain"""
+    total = 0
+    for f in range(4):
+        v = rows[:, f].astype(np.int64)
+        o = int(np.bitwise_or.reduce(v ^ v[0]) & 0xFFFFFFFF)
+        tz = (o & -o).bit_length() - 1 if o else 0
+        total += ((int(v.max()) - int(v.min())) >> tz).bit_length()
+    return total
+
+
+@pytest.mark.parametrize("n,domain", CANON_CASES)
+def test_sort_keys_canonical_routes(rt, oracle, sort_keys_canonical, n, domain):
+    """the canonical order from Morton keys (codec.hip view_of): the single-workgroup kernel up to 8 191 rows, four
+    launches over workgroups of 1 024 rows from 8 192 on (8, 9 with one row in the last, 64 = as many partial ranges as
+    one wave reduces = the largest n accepted).  Per count: rank by bitmap (distinct rows, key of exactly 20 bits), radix
+    passes on the compact key (21 bits: just too wide; or 20 bits with repeated rows, found by the bitmap pass: the order
+    among equal rows is the stable one).  Each case first shows on the CPU that it sits where it says."""
+    rng = np.random.default_rng(1000 * n + len(domain))
+    rows = _canon_rows(rng, n, domain)
+    assert rows.shape == (n, 4)
+    assert _canon_total_width(rows) == (0 if domain == "single" else CANON_DOMAINS[domain][1])
+    assert (-(-n // 1024) if n >= 8192 else 0) == {1: 0, 2: 0, 8191: 0, 8192: 8, 8193: 9, 65536: 64}[n]
+    distinct = len(np.unique(rows, axis=0))
+    assert distinct == (n - n // 8 if domain == "repeats20" else n) and (domain != "repeats20" or distinct < n)
+    keys = u64(rt.morton_keys(dev(rt, rows)))
+    order = np.argsort(keys, kind="stable")
+    rows, keys = rows[order], keys[order]                   # as view_of hands them over: keys ascending
+    perm, out = sort_keys_canonical(dev(rt, keys.view(np.int64)))
+    ref = oracle.canonical_perm(rows)
+    assert np.array_equal(perm, ref.astype(np.uint32))
+    assert np.array_equal(out, rows[ref])
 
 
 def test_batch_offsets(rt, oracle, clouds):
