@@ -35,7 +35,14 @@
 // the loop of every run, or k_a2_walk<true> sums the chain, scales by q and clamps.  tests/attr_nl_ref.py restates both
 // kinds in numpy.
 //
-// Host side: the four kinds share one encode sequence (a_encode_frames) and the helpers of the two decoders; DESIGN.md,
+// Cross-channel kinds, versions 8, 11, 13 and 14 (attr_blob.h has the rule; the cross forms of 1, 2, 4 and 7 for frames
+// of two and more channels): what the plain kind would code for a channel of the mask is coded as its wrapped difference
+// to the channel before it.  Encoder: one elementwise pass (k_ax_fwd) in front of the counting pass, over the array the
+// PRED = false coder reads; for version 8 it first writes version 1's run residuals there.  Decoder: k_a_dec<true>
+// returns the differences, k_ax_inv undoes them in place, and the plain kind's last step follows (k_a8_recon redoes
+// version 1's predictor).  Launched for these kinds only.  tests/attr_cross_ref.py restates them in numpy.
+//
+// Host side: the kinds share one encode sequence (a_encode_frames) and the helpers of the two decoders; DESIGN.md,
 // "attr.hip: one encode path, shared decode helpers".
 #include "common.h"
 #include "lanerans.h"
@@ -314,13 +321,15 @@ __global__ __launch_bounds__(64) void k_a_enc(const uint16_t* __restrict__ merge
 // [cb + f, cb + f + nc + 1) — workgroup k < nc of them moves chunk k, workgroup nc writes the header; len_out[f] =
 // bytes, or -1 (out_cap).  V2: the head of attribute blob version 2, with the frame's 16 values-per-level counts
 // (cells_all[16 f + k], attr_blob.h) and the sender's level of detail.  NL: the heads of versions 4 / 7, the frame's
-// max_error behind payload_len and everything else one word later
-template <bool V2, bool NL = false>
+// max_error behind payload_len and everything else one word later.  XC (a call with cross-channel frames): frame f with
+// cross_all[f] = m != 0 gets the cross form of the version byte and its mask above the channels of byte 3
+template <bool V2, bool NL = false, bool XC = false>
 __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ work_all, const AFrame* __restrict__ tab, int nf,
                                                 const uint16_t* __restrict__ states_all, const uint16_t* __restrict__ lens_all,
                                                 const uint32_t* __restrict__ words_all, const uint16_t* __restrict__ p0_all,
                                                 uint8_t* __restrict__ out_all, long long* __restrict__ len_out,
-                                                const uint32_t* __restrict__ cells_all, int slod) {
+                                                const uint32_t* __restrict__ cells_all, int slod,
+                                                const int32_t* __restrict__ cross_all) {
   __shared__ unsigned long long s_sum[256];
   __shared__ uint32_t s_off[kLanes + 1];
   const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].cb + i; });
@@ -351,6 +360,10 @@ __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ wor
     uint32_t* o32 = reinterpret_cast<uint32_t*>(out);
     if (threadIdx.x == 0) {
       o32[0] = (uint32_t)'A' | ((NL ? (V2 ? 7u : 4u) : (V2 ? 2u : 1u)) << 8) | ((uint32_t)(h.bpv | (V2 ? slod << 4 : 0)) << 16) | ((uint32_t)h.c << 24);
+      if constexpr (XC) {
+        const uint32_t m = (uint32_t)cross_all[f];
+        if (m) out[1] = (uint8_t)attr_version(V2, NL, true), out[3] = (uint8_t)((uint32_t)h.c | (m << 4));
+      }
       o32[1] = (uint32_t)h.n;
       o32[2] = (uint32_t)(total - kAttrHead);
       if constexpr (NL) o32[3] = (uint32_t)h.e;
@@ -832,6 +845,105 @@ __global__ __launch_bounds__(256) void k_a2_walk(const A2Order* __restrict__ tab
   }
 }
 
+// ---- cross-channel kinds (versions 8, 11, 13, 14; attr_blob.h states the rule) -------------------------------------
+// Elementwise passes: one thread per point, the point's channels in registers, frame = blockIdx.y.  cross[f]: the
+// frame's mask m, bit ch - 1 set where channel ch is coded against channel ch - 1.  A point's c values are 2 c (or bpv c)
+// consecutive bytes and a wave's 64 points one contiguous stretch, read value by value: a frame's rows start wherever the
+// frames in front of it end (c = 3 leaves no 8-byte alignment), and the passes stand beside a coder that walks the same
+// values one decision at a time.
+//
+// x of a point's w[0 .. c), wrapped to the value width: from the last channel down, so that every difference is taken
+// against the original w of the channel before it; and its inverse, from channel 1 up
+__device__ __forceinline__ void a_cross_fwd(uint32_t (&w)[4], int c, int m, uint32_t mask) {
+#pragma unroll
+  for (int ch = 3; ch >= 1; --ch)
+    if (ch < c && ((m >> (ch - 1)) & 1)) w[ch] = (w[ch] - w[ch - 1]) & mask;
+}
+__device__ __forceinline__ void a_cross_inv(uint32_t (&w)[4], int c, int m, uint32_t mask) {
+#pragma unroll
+  for (int ch = 1; ch <= 3; ++ch)
+    if (ch < c && ((m >> (ch - 1)) & 1)) w[ch] = (w[ch] + w[ch - 1]) & mask;
+}
+
+// Encoder, in front of the counting pass.  RUN = false (versions 11, 13, 14): in place over the [n][c] array that
+// k_a2_place<true>, k_a4_quant or k_a7_quant left for the coder; a frame with m = 0 keeps what it has.  RUN = true
+// (version 8): w is version 1's residual inside the lane's run, computed here from the merged values (run position
+// s = i % S) and written to src for EVERY frame of the call, so that the PRED = false coder serves them all: a frame
+// with m = 0 gets the bytes of its plain kind, which codes these residuals under the same contexts.
+template <bool RUN>
+__global__ __launch_bounds__(256) void k_ax_fwd(const AFrame* __restrict__ tab, const int32_t* __restrict__ cross,
+                                                const uint16_t* __restrict__ merged, uint16_t* __restrict__ src) {
+  const AFrame& h = tab[blockIdx.y];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= h.n) return;
+  const int c = h.c, m = cross[blockIdx.y];
+  if (!RUN && m == 0) return;
+  const uint32_t mask = (1u << (8 * h.bpv)) - 1u;
+  uint16_t* o = src + h.val_off + i * c;
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  if constexpr (RUN) {
+    const uint16_t* v = merged + h.val_off + i * c;
+    const int64_t s = i % h.S;
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch)
+      if (ch < c) {
+        const uint32_t a = s >= 1 ? v[ch - c] : 0u, b = s >= 2 ? v[ch - 2 * c] : 0u;
+        w[ch] = ((uint32_t)v[ch] - a_pred(s, a, b)) & mask;
+      }
+  } else {
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch)
+      if (ch < c) w[ch] = o[ch];
+  }
+  a_cross_fwd(w, c, m, mask);
+#pragma unroll
+  for (int ch = 0; ch < 4; ++ch)
+    if (ch < c) o[ch] = (uint16_t)w[ch];
+}
+
+// Decoder, behind k_a_dec<true>: the inverse, in place over the frame's first n_dec points (all of them; the values of
+// a level of detail for versions 11 and 14, whose rows stand in introduction order).  data_all: the frames' [n_dec][c]
+// values of bpv bytes at out_off, as the coder wrapped them
+__global__ __launch_bounds__(256) void k_ax_inv(const ADFrame* __restrict__ tab, const int32_t* __restrict__ cross,
+                                                uint8_t* __restrict__ data_all) {
+  const ADFrame& h = tab[blockIdx.y];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= h.n_dec) return;
+  const int c = h.c, bpv = h.bpv;
+  const uint32_t mask = (1u << (8 * bpv)) - 1u;
+  uint8_t* p = data_all + h.out_off + i * c * bpv;
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int ch = 0; ch < 4; ++ch)
+    if (ch < c) w[ch] = a_load(p, bpv, ch);
+  a_cross_inv(w, c, cross[blockIdx.y], mask);
+#pragma unroll
+  for (int ch = 1; ch < 4; ++ch)
+    if (ch < c) a_store(p, bpv, w[ch], ch);
+}
+
+// Version 8, behind k_ax_inv: version 1's predictor inside the run over the residuals, modulo 2^(8 bpv) as
+// a_decode_chunk<.., false> applies it, in place; frame = blockIdx.y, one thread per (lane run, channel) as k_a4_recon
+__global__ __launch_bounds__(256) void k_a8_recon(const ADFrame* __restrict__ tab, uint8_t* __restrict__ data_all) {
+  const ADFrame& h = tab[blockIdx.y];
+  const int c = h.c, bpv = h.bpv;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t base = t / c * h.S;
+  const int ch = (int)(t % c);
+  if (base >= h.n) return;
+  const int npts = (int)std::min<int64_t>(h.S, h.n - base);
+  const uint32_t mask = (1u << (8 * bpv)) - 1u;
+  uint8_t* o = data_all + h.out_off + (base * c + ch) * bpv;
+  uint32_t a = 0, b = 0;   // v[s - 1], v[s - 2]
+  for (int s = 0; s < npts; ++s) {
+    const int64_t at = (int64_t)s * c * bpv;
+    const uint32_t val = (a_pred(s, a, b) + a_load(o + at, bpv)) & mask;
+    b = a;
+    a = val;
+    a_store(o + at, bpv, val);
+  }
+}
+
 }  // namespace
 
 static inline int64_t a_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
@@ -840,12 +952,14 @@ static inline size_t merged_b_of(int64_t vals) { return pcc_align((size_t)vals *
 // ======================================================================== C-ABI (include/pcc.h)
 // both versions' encoder: version 2 codes, instead of the merged values, their residuals in introduction order
 // (k_a2_size / k_a2_scan / k_a2_place over d_keys, the call's distinct sorted keys).  max_error > 0: the near-lossless
-// kind of that version (4 for 1, 7 for 2), the indices of k_a4_quant / k_a7_quant through the PRED = false coder
+// kind of that version (4 for 1, 7 for 2), the indices of k_a4_quant / k_a7_quant through the PRED = false coder.
+// h_cross: per frame the cross-channel mask m (0: the frame's plain kind); a call with any m != 0 among its frames with
+// points runs k_ax_fwd in front of the coder and codes every frame with PRED = false
 static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
                            const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
                            const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys,
                            int key_shift, uint8_t* h_out, int64_t cap, int64_t* h_offsets, int64_t n_kept = -1,
-                           int max_error = 0) {
+                           int max_error = 0, const int32_t* h_cross = nullptr) {
   const bool v2 = version == 2, nl = max_error > 0;
   const int blob_version = nl ? (v2 ? 7 : 4) : version;
   PCC_REQUIRE(ctx && h_value_offsets && h_format && h_rows && h_points && h_out && h_offsets && n_frames >= 1 &&
@@ -864,6 +978,9 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
   std::vector<AFrame> tab;
   std::vector<A2Order> order;
   std::vector<int> frame_of;
+  std::vector<int32_t> cross;   // the masks of the frames with points
+  bool xc = false;              // one of them is not 0
+  int64_t n_max = 0;            // k_ax_fwd: the most points of a frame
   int64_t run_threads = 0;   // k_a4_quant: the most (run, channel) pairs of a frame
   int64_t u = 0, vals = 0, rec_words = 0, out_bytes = 0, chunks = 0, stats_blocks = 0, merge_blocks = 0, ctxs = 0, nctx_max = 0;
   for (int f = 0; f < n_frames; ++f) {
@@ -876,7 +993,12 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
                 "%s: frame %d: %lld rows, %lld points", who, f, (long long)rows, (long long)n);
     PCC_REQUIRE(!nl || (uint32_t)max_error <= attr_max_error(bpv), PCC_E_ARG,
                 "%s: frame %d: max_error %d with %d bytes per value (at most %u)", who, f, max_error, bpv, attr_max_error(bpv));
+    const int32_t m = h_cross ? h_cross[f] : 0;
+    PCC_REQUIRE(m >= 0 && m < (1 << (c - 1)), PCC_E_ARG, "%s: frame %d: cross-channel mask %d with %d channels", who, f, m, c);
     if (n == 0) continue;
+    cross.push_back(m);
+    xc |= m != 0;
+    n_max = std::max(n_max, n);
     AFrame r;
     int64_t S, nc;
     attr_layout(n, c, &S, &nc);
@@ -925,7 +1047,9 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
   hipStream_t st = ctx->stream;
   if (nf > 0) {
     const size_t ord_b = v2 ? pcc_align((size_t)nf * sizeof(A2Order)) : 0;
-    const size_t tab_b = pcc_align((size_t)nf * sizeof(AFrame)) + ord_b;
+    // the rows | the masks (a call with cross-channel frames) | the order rows
+    const size_t fr_b = pcc_align((size_t)nf * sizeof(AFrame)), cross_b = xc ? pcc_align((size_t)nf * 4) : 0;
+    const size_t tab_b = fr_b + cross_b + ord_b;
     const size_t merged_b = merged_b_of(vals), cnt_b = pcc_align((size_t)ctxs * 8), p0_b = pcc_align((size_t)ctxs * 2);
     const size_t rec_b = pcc_align((size_t)rec_words * 2), small_b = pcc_align((size_t)chunks * (4 + 2 * kLanes * 2 + kLanes * 2));
     // the order stage's (versions 2 and 7): packed | hist | 17 bin bases, then 16 counts per frame; rank, first (7)
@@ -934,7 +1058,8 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     // src is one more array of the merged values' size.  The sum counts it twice for version 2 and the links for
     // version 4 too: it is what these calls have always reserved, and no call reserves less than it did
     const size_t order_b = v2 ? 2 * merged_b + pk_b + hist_b + bins_b : 0, nl_b = nl ? merged_b + 2 * link_b : 0;
-    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + order_b + nl_b + 8192));
+    const size_t x8_b = xc && !v2 && !nl ? merged_b : 0;   // version 8: the run residuals
+    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + order_b + nl_b + x8_b + 8192));
     AFrame* d_tab = (AFrame*)pcc_arena_alloc(ctx, tab_b);
     uint16_t* merged = (uint16_t*)pcc_arena_alloc(ctx, merged_b);
     uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, cnt_b);
@@ -942,22 +1067,26 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     uint16_t* rec = (uint16_t*)pcc_arena_alloc(ctx, rec_b);
     uint16_t* work = (uint16_t*)pcc_arena_alloc(ctx, rec_b);
     char* small = (char*)pcc_arena_alloc(ctx, small_b);
-    // what the lanes code: the merged values (version 1), their residuals in introduction order (2), the indices (4, 7)
-    uint16_t* src = v2 || nl ? (uint16_t*)pcc_arena_alloc(ctx, merged_b) : merged;
+    // what the lanes code: the merged values (version 1), their residuals in introduction order (2), the indices (4, 7);
+    // a call with cross-channel frames: the run residuals (8) and all of these after k_ax_fwd
+    uint16_t* src = v2 || nl || xc ? (uint16_t*)pcc_arena_alloc(ctx, merged_b) : merged;
     if (!d_tab || !merged || !cnt || !p0 || !rec || !work || !small || !src) return PCC_E_NOMEM;
     uint32_t* words = (uint32_t*)small;
     uint16_t* states = (uint16_t*)(small + (size_t)chunks * 4);
     uint16_t* lens_d = states + (size_t)chunks * 2 * kLanes;
     const A2Order* d_ord = (const A2Order*)((const uint8_t*)d_tab + tab_b - ord_b);
+    const int32_t* d_cross = xc ? (const int32_t*)((const uint8_t*)d_tab + fr_b) : nullptr;
     // staging: the table on its way to the device | the blobs | their lengths
     const size_t lens_at = tab_b + (size_t)out_bytes;
     PCC_TRY(o2_stage_reserve(ctx, lens_at + (size_t)nf * 8 + 64));
     uint8_t* stage = (uint8_t*)ctx->stage;
     memcpy(stage, tab.data(), (size_t)nf * sizeof(AFrame));
+    if (xc) memcpy(stage + fr_b, cross.data(), (size_t)nf * 4);
     if (v2) memcpy(stage + tab_b - ord_b, order.data(), (size_t)nf * sizeof(A2Order));
     long long* len_dev = (long long*)(stage + lens_at);
     PccProfScope prof(ctx, "attr_encode", u, nf, chunks, 0);
-    PCC_HIP(hipMemcpyAsync(d_tab, stage, v2 ? tab_b - ord_b + (size_t)nf * sizeof(A2Order) : (size_t)nf * sizeof(AFrame),
+    PCC_HIP(hipMemcpyAsync(d_tab, stage,
+                           v2 ? tab_b - ord_b + (size_t)nf * sizeof(A2Order) : (xc ? fr_b + (size_t)nf * 4 : (size_t)nf * sizeof(AFrame)),
                            hipMemcpyHostToDevice, st));
     PCC_HIP(hipMemsetAsync(cnt, 0, (size_t)ctxs * 8, st));
     hipLaunchKernelGGL(k_a_merge, dim3((unsigned)merge_blocks), dim3(256), 0, st, (const uint8_t*)d_values, (const AFrame*)d_tab, nf,
@@ -998,25 +1127,32 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
                          (const uint16_t*)merged, (const uint32_t*)rank, (const uint32_t*)first, src);
       PCC_CHECK_LAUNCH();
     }
-    // counting pass, coder, blobs: only version 1 predicts inside the run (PRED)
+    if (xc) {
+      const auto fwd = !v2 && !nl ? k_ax_fwd<true> : k_ax_fwd<false>;
+      hipLaunchKernelGGL(fwd, dim3(nblk(n_max, 256), (unsigned)nf), dim3(256), 0, st, (const AFrame*)d_tab, d_cross,
+                         (const uint16_t*)merged, src);
+      PCC_CHECK_LAUNCH();
+    }
+    // counting pass, coder, blobs: only version 1 predicts inside the run (PRED), and not beside cross-channel frames
     const size_t lds = 4096 * 4 + (size_t)(nctx_max + 1) * kLanes * 2;   // <= 98 KB (c = 4, uint16)
-    auto a_code = [&](auto v2c, auto nlc) -> int {
-      constexpr bool V2 = decltype(v2c)::value, NL = decltype(nlc)::value, PRED = !V2 && !NL;
+    auto a_code = [&](auto v2c, auto nlc, auto xcc) -> int {
+      constexpr bool V2 = decltype(v2c)::value, NL = decltype(nlc)::value, XC = decltype(xcc)::value, PRED = !V2 && !NL && !XC;
       hipLaunchKernelGGL(k_a_stats<PRED>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)src, (const AFrame*)d_tab, nf, cnt);
       PCC_CHECK_LAUNCH();
       PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<PRED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL(k_a_enc<PRED>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)src, (const AFrame*)d_tab, nf,
                          (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
       PCC_CHECK_LAUNCH();
-      hipLaunchKernelGGL((k_a_pack<V2, NL>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work,
+      hipLaunchKernelGGL((k_a_pack<V2, NL, XC>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work,
                          (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words,
-                         (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3);
+                         (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3, d_cross);
       PCC_CHECK_LAUNCH();
       return PCC_OK;
     };
     using Yes = std::true_type;
     using No = std::false_type;
-    PCC_TRY(v2 ? (nl ? a_code(Yes{}, Yes{}) : a_code(Yes{}, No{})) : (nl ? a_code(No{}, Yes{}) : a_code(No{}, No{})));
+    auto a_kind = [&](auto v2c, auto nlc) -> int { return xc ? a_code(v2c, nlc, Yes{}) : a_code(v2c, nlc, No{}); };
+    PCC_TRY(v2 ? (nl ? a_kind(Yes{}, Yes{}) : a_kind(Yes{}, No{})) : (nl ? a_kind(No{}, Yes{}) : a_kind(No{}, No{})));
     PCC_HIP(hipStreamSynchronize(st));
     for (int k = 0; k < nf; ++k) {
       const long long total = ((volatile long long*)len_dev)[k];
@@ -1036,11 +1172,12 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     if (off_of[(size_t)f] >= 0) {
       memcpy(dst, (const uint8_t*)ctx->stage + off_of[(size_t)f], (size_t)len_of[(size_t)f]);
     } else {   // no points: the 12-byte empty blob
+      const int32_t m = h_cross ? h_cross[f] : 0;
       memset(dst, 0, kAttrHead);
       dst[0] = 'A';
-      dst[1] = (uint8_t)blob_version;
+      dst[1] = (uint8_t)(m ? attr_version(v2, nl, true) : blob_version);
       dst[2] = (uint8_t)((h_format[f] & 0xFF) | (v2 ? (key_shift / 3) << 4 : 0));
-      dst[3] = (uint8_t)(h_format[f] >> 8);
+      dst[3] = (uint8_t)((h_format[f] >> 8) | (m << 4));
     }
     h_offsets[f + 1] = h_offsets[f] + len_of[(size_t)f];
   }
@@ -1087,15 +1224,44 @@ extern "C" int pcc_attr_encode_frames_nl(pcc_ctx* ctx, int version, const void* 
                          h_out, cap, h_offsets, n_kept, max_error);
 }
 
+extern "C" int pcc_attr_encode_frames_cross(pcc_ctx* ctx, int version, const void* d_values, const int64_t* h_value_offsets,
+                                            const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
+                                            const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, int64_t n_kept,
+                                            const uint64_t* d_keys, int key_shift, int max_error, const int32_t* h_cross,
+                                            uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
+  PCC_REQUIRE((version == 1 || version == 2) && n_kept >= -1 && max_error >= 0 && h_cross, PCC_E_ARG,
+              "pcc_attr_encode_frames_cross: bad argument (version=%d n_kept=%lld max_error=%d)", version, (long long)n_kept, max_error);
+  return a_encode_frames("pcc_attr_encode_frames_cross", version, ctx, d_values, h_value_offsets, h_format, h_rows, h_points,
+                         n_frames, d_perm, d_run_starts, n_unique, version == 2 ? d_keys : nullptr, version == 2 ? key_shift : 0,
+                         h_out, cap, h_offsets, n_kept, max_error, h_cross);
+}
+
+// host only: the version byte and byte 3 of a head, checked: its kind, channels and mask
+static int a_head_kind(const char* who, const uint8_t* h_in, int64_t len, bool* scal, bool* nl, bool* xc, int* c, int* m) {
+  PCC_REQUIRE(h_in && len >= kAttrHead && h_in[0] == 'A', PCC_E_STREAM, "%s: not an attribute blob (len=%lld)", who, (long long)len);
+  PCC_REQUIRE(attr_kind(h_in[1], scal, nl, xc), PCC_E_STREAM, "%s: attribute blob version %d", who, (int)h_in[1]);
+  const int bpv = *scal ? h_in[2] & 15 : h_in[2];
+  PCC_REQUIRE((bpv == 1 || bpv == 2) && attr_channels(h_in[3], *xc, c, m), PCC_E_STREAM, "%s: %d bytes per value, %d channels%s", who,
+              bpv, *c, *xc ? ", or their mask" : "");
+  return PCC_OK;
+}
+
+// host only: the cross-channel mask of a head, 0 for the plain kinds
+extern "C" int pcc_attr_cross_mask(const uint8_t* h_in, int64_t len, int32_t* h_mask) {
+  bool scal, nl, xc;
+  int c, m;
+  PCC_TRY(a_head_kind("pcc_attr_cross_mask", h_in, len, &scal, &nl, &xc, &c, &m));
+  if (h_mask) *h_mask = m;
+  return PCC_OK;
+}
+
 // host only: what the head of an attribute blob of any kind says (h_in may be a prefix that holds the head)
 extern "C" int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_version, int32_t* h_bpv, int32_t* h_channels,
                              int64_t* h_points, int32_t* h_max_error, int32_t* h_scalable, int32_t* h_lod) {
-  PCC_REQUIRE(h_in && len >= kAttrHead && h_in[0] == 'A', PCC_E_STREAM, "pcc_attr_info: not an attribute blob (len=%lld)", (long long)len);
-  const int ver = h_in[1];
-  PCC_REQUIRE(ver == 1 || ver == 2 || ver == 4 || ver == 7, PCC_E_STREAM, "pcc_attr_info: attribute blob version %d", ver);
-  const bool scal = ver == 2 || ver == 7, nl = ver == 4 || ver == 7;
-  const int bpv = scal ? h_in[2] & 15 : h_in[2], slod = scal ? h_in[2] >> 4 : 0, c = h_in[3];
-  PCC_REQUIRE((bpv == 1 || bpv == 2) && c >= 1 && c <= 4, PCC_E_STREAM, "pcc_attr_info: %d bytes per value, %d channels", bpv, c);
+  bool scal, nl, xc;
+  int c, m;
+  PCC_TRY(a_head_kind("pcc_attr_info", h_in, len, &scal, &nl, &xc, &c, &m));
+  const int ver = h_in[1], bpv = scal ? h_in[2] & 15 : h_in[2], slod = scal ? h_in[2] >> 4 : 0;
   const int64_t n = (int64_t)attr_u32(h_in + 4);
   PCC_REQUIRE(n < ((int64_t)1 << 27), PCC_E_STREAM, "pcc_attr_info: %lld points", (long long)n);
   uint32_t e = 0;
@@ -1117,10 +1283,18 @@ extern "C" int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_versio
 // ---- what the two decoders share ------------------------------------------------------------------------------------
 static bool a_is_version(const uint8_t* b, int64_t len, int version) { return b && len >= 2 && b[0] == 'A' && b[1] == version; }
 
-// the blobs of a call are of one version, `mine`: the entry point's other version is refused by name
-static int a_mixed_version(const char* who, int f, const uint8_t* b, int64_t len, int other, int mine) {
-  PCC_REQUIRE(!a_is_version(b, len, other), PCC_E_ARG,
-              "%s: frame %d: attribute blob version %d in a call of version %d blobs (one version per call)", who, f, other, mine);
+// the version of a call's blobs: the first blob's when it is one of the entry point's four, else the first of them
+static int a_call_version(const uint8_t* b, int64_t len, const int (&kinds)[4]) {
+  for (int k : kinds)
+    if (a_is_version(b, len, k)) return k;
+  return kinds[0];
+}
+
+// the blobs of a call are of one version, `mine`: the entry point's other versions are refused by name
+static int a_mixed_version(const char* who, int f, const uint8_t* b, int64_t len, const int (&kinds)[4], int mine) {
+  for (int other : kinds)
+    PCC_REQUIRE(other == mine || !a_is_version(b, len, other), PCC_E_ARG,
+                "%s: frame %d: attribute blob version %d in a call of version %d blobs (one version per call)", who, f, other, mine);
   return PCC_OK;
 }
 
@@ -1207,15 +1381,18 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
   PCC_REQUIRE(ctx && h_blobs && h_lens && h_out_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
               "%s: bad argument (n_frames=%d)", who, n_frames);
   // the blobs of a call are of one version, the first blob's: 1, or 4 (its indices through the decoder of version 2 at
-  // lod 0, then k_a4_recon)
-  const bool nl = a_is_version(h_blobs[0], h_lens[0], 4);
+  // lod 0, then k_a4_recon), or their cross-channel forms 8 and 13 (k_ax_inv behind that decoder, then k_a8_recon /
+  // k_a4_recon)
+  const int kinds[4] = {1, 4, 8, 13};
+  const int mine = a_call_version(h_blobs[0], h_lens[0], kinds);
+  const bool nl = mine == 4 || mine == 13, xc = mine == 8 || mine == 13;
   std::vector<AttrInfo> info((size_t)n_frames);
   int64_t bytes = 0, bodies = 0, points = 0;
   h_out_offsets[0] = 0;
   for (int f = 0; f < n_frames; ++f) {
     AttrInfo& o = info[(size_t)f];
-    PCC_TRY(a_mixed_version(who, f, h_blobs[f], h_lens[f], nl ? 1 : 4, nl ? 4 : 1));
-    const int rc = attr_parse_kind(h_blobs[f], h_lens[f], nl, &o);
+    PCC_TRY(a_mixed_version(who, f, h_blobs[f], h_lens[f], kinds, mine));
+    const int rc = attr_parse_kind(h_blobs[f], h_lens[f], nl, &o, xc);
     if (rc != PCC_OK) return a_wrap_error(who, f, rc);
     PCC_REQUIRE(!h_points || h_points[f] == o.n, PCC_E_STREAM, "%s: frame %d: the attribute blob has %lld points, its geometry %lld",
                 who, f, (long long)o.n, (long long)(h_points ? h_points[f] : 0));
@@ -1229,12 +1406,15 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
   if (bytes == 0 || (!d_out && !h_out)) return PCC_OK;
   PCC_REQUIRE(cap_bytes >= bytes, PCC_E_NOMEM, "%s: %lld bytes, capacity %lld", who, (long long)bytes, (long long)cap_bytes);
   std::vector<ADFrame> tab;
-  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, run_threads = 0;
+  std::vector<int32_t> cross;   // the masks of versions 8 and 13
+  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, run_threads = 0, n_max = 0;
   for (int f = 0; f < n_frames; ++f) {
     const AttrInfo& o = info[(size_t)f];
     if (o.n == 0) continue;
     const uint8_t* table = h_blobs[f] + o.off_table;
     tab.push_back(a_dec_row(o, body_off, h_out_offsets[f], chunks, o.nc, o.n, attr_u32(table + 4 * (o.nc - 1))));
+    cross.push_back(o.cross);
+    n_max = std::max(n_max, o.n);
     run_threads = std::max<int64_t>(run_threads, o.nc * kLanes * o.c);
     for (int64_t k = 0; k < o.nc; ++k) cw_max = std::max<int64_t>(cw_max, attr_u32(table + 4 * k));
     body_off += a_round(h_lens[f] - o.off_p0, 16);
@@ -1243,7 +1423,7 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
   }
   const int nf = (int)tab.size();
   hipStream_t st = ctx->stream;
-  const size_t tab_b = pcc_align((size_t)nf * sizeof(ADFrame));
+  const size_t tab_b = pcc_align((size_t)nf * (sizeof(ADFrame) + (xc ? 4 : 0)));   // the rows, then the masks
   PCC_TRY(pcc_arena_reserve(ctx, tab_b + pcc_align((size_t)bodies + 16) + ((d_out ? 0 : 1) + (nl ? 1 : 0)) * pcc_align((size_t)bytes) +
                                      pcc_align((size_t)nf * 4 + 64) + 4096));
   uint8_t* d_in = (uint8_t*)pcc_arena_alloc(ctx, tab_b + (size_t)bodies + 16);
@@ -1257,6 +1437,7 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
   PCC_TRY(a_dec_stage(ctx, h_out, in_b, bytes, (size_t)nf * 4, &down, &back));
   uint8_t* stage = (uint8_t*)ctx->stage;
   memcpy(stage, tab.data(), (size_t)nf * sizeof(ADFrame));
+  if (xc) memcpy(stage + (size_t)nf * sizeof(ADFrame), cross.data(), (size_t)nf * 4);
   for (int f = 0, k = 0; f < n_frames; ++f) {
     const AttrInfo& o = info[(size_t)f];
     if (o.n == 0) continue;
@@ -1264,10 +1445,20 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
   }
   PCC_HIP(hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
   PCC_HIP(hipMemsetAsync(status, 0, (size_t)nf * 4 + 64, st));
-  if (!nl) {
+  if (!nl && !xc) {
     PCC_TRY(a_launch_dec<false>(st, chunks, d_in, tab_b, nf, nctx_max, cw_max, out, status));
   } else {
     PCC_TRY(a_launch_dec<true>(st, chunks, d_in, tab_b, nf, nctx_max, cw_max, idx, status));
+    if (xc) {
+      hipLaunchKernelGGL(k_ax_inv, dim3(nblk(n_max, 256), (unsigned)nf), dim3(256), 0, st, (const ADFrame*)d_in,
+                         (const int32_t*)(d_in + (size_t)nf * sizeof(ADFrame)), idx);
+      PCC_CHECK_LAUNCH();
+    }
+  }
+  if (xc && !nl) {   // version 8: idx is out
+    hipLaunchKernelGGL(k_a8_recon, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const ADFrame*)d_in, out);
+    PCC_CHECK_LAUNCH();
+  } else if (nl) {
     hipLaunchKernelGGL(k_a4_recon, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const ADFrame*)d_in,
                        (const uint8_t*)idx, out, status);
     PCC_CHECK_LAUNCH();
@@ -1290,11 +1481,12 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
 extern "C" int pcc_attr_lod_info(const uint8_t* h_in, int64_t len, int lod, int64_t* h_bytes, int64_t* h_values) {
   PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "pcc_attr_lod_info: level of detail %d outside 0 .. %d", lod, kAttrMaxLod);
   PCC_REQUIRE(h_in && len >= 2 && h_in[0] == 'A', PCC_E_STREAM, "pcc_attr_lod_info: not an attribute blob (len=%lld)", (long long)len);
-  PCC_REQUIRE(h_in[1] == 2 || h_in[1] == 7, PCC_E_ARG,
+  bool scal = false, nl = false, xc = false;
+  PCC_REQUIRE(attr_kind(h_in[1], &scal, &nl, &xc) && scal, PCC_E_ARG,
               "pcc_attr_lod_info: attribute blob version %d (levels of detail are a property of version 2)", (int)h_in[1]);
   Attr2Info o;
   Attr2Plan pl;
-  const int rc = attr2_parse_kind(h_in, len, lod, false, h_in[1] == 7, &o, &pl);
+  const int rc = attr2_parse_kind(h_in, len, lod, false, nl, &o, &pl, xc);
   if (rc != PCC_OK) {
     const std::string m = pcc_last_error();
     pcc_set_error("pcc_attr_lod_info: %s", m.c_str());
@@ -1312,8 +1504,11 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   PCC_REQUIRE(ctx && h_blobs && h_lens && h_out_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
               "%s: bad argument (n_frames=%d)", who, n_frames);
   PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "%s: level of detail %d outside 0 .. %d", who, lod, kAttrMaxLod);
-  // the blobs of a call are of one version, the first blob's: 2, or 7 (k_a2_walk<true> scales and clamps)
-  const bool nl = a_is_version(h_blobs[0], h_lens[0], 7);
+  // the blobs of a call are of one version, the first blob's: 2, or 7 (k_a2_walk<true> scales and clamps), or their
+  // cross-channel forms 11 and 14 (k_ax_inv between the decoder and the walk)
+  const int kinds[4] = {2, 7, 11, 14};
+  const int mine = a_call_version(h_blobs[0], h_lens[0], kinds);
+  const bool nl = mine == 7 || mine == 14, xc = mine == 11 || mine == 14;
   std::vector<Attr2Info> info((size_t)n_frames);
   std::vector<Attr2Plan> plan((size_t)n_frames);
   int64_t bytes = 0, bodies = 0, points = 0;
@@ -1321,8 +1516,8 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   for (int f = 0; f < n_frames; ++f) {
     Attr2Info& o = info[(size_t)f];
     Attr2Plan& pl = plan[(size_t)f];
-    PCC_TRY(a_mixed_version(who, f, h_blobs[f], h_lens[f], nl ? 2 : 7, nl ? 7 : 2));
-    const int rc = attr2_parse_kind(h_blobs[f], h_lens[f], lod, true, nl, &o, &pl);
+    PCC_TRY(a_mixed_version(who, f, h_blobs[f], h_lens[f], kinds, mine));
+    const int rc = attr2_parse_kind(h_blobs[f], h_lens[f], lod, true, nl, &o, &pl, xc);
     if (rc != PCC_OK) return a_wrap_error(who, f, rc);
     if (h_cell_offsets) {
       const int64_t m = h_cell_offsets[f + 1] - h_cell_offsets[f];
@@ -1343,7 +1538,8 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   PCC_REQUIRE(cap_bytes >= bytes, PCC_E_NOMEM, "%s: %lld bytes, capacity %lld", who, (long long)bytes, (long long)cap_bytes);
   std::vector<ADFrame> tab;
   std::vector<A2Order> order;
-  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, blocks = 0;
+  std::vector<int32_t> cross;   // the masks of versions 11 and 14
+  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, blocks = 0, n_max = 0;
   const int64_t cell0 = h_cell_offsets[0];
   for (int f = 0; f < n_frames; ++f) {
     const Attr2Info& o = info[(size_t)f];
@@ -1351,6 +1547,8 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
     if (pl.m == 0) continue;
     tab.push_back(a_dec_row(o, body_off, h_out_offsets[f], chunks, pl.chunks, pl.m, pl.last_words));
     order.push_back(A2Order{h_cell_offsets[f] - cell0, pl.m, (int32_t)blocks, lod + o.slod});
+    cross.push_back(o.cross);
+    n_max = std::max(n_max, pl.m);
     for (int64_t k = 0; k + 1 < pl.chunks; ++k) cw_max = std::max<int64_t>(cw_max, attr_u32(h_blobs[f] + o.off_table + 4 * k));
     cw_max = std::max<int64_t>(cw_max, pl.last_words);
     body_off += a_round(pl.bytes - o.off_p0, 16);
@@ -1362,7 +1560,8 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   const int32_t* cells = d_cells + 3 * cell0;
   const int nf = (int)tab.size();
   hipStream_t st = ctx->stream;
-  const size_t ftab_b = pcc_align((size_t)nf * sizeof(ADFrame)), ord_b = pcc_align((size_t)nf * sizeof(A2Order));
+  // the rows, then (versions 11 and 14) the masks | the order rows
+  const size_t ftab_b = pcc_align((size_t)nf * (sizeof(ADFrame) + (xc ? 4 : 0))), ord_b = pcc_align((size_t)nf * sizeof(A2Order));
   const size_t tab_b = ftab_b + ord_b;
   const size_t keys_b = pcc_align((size_t)cells_all * 8), u32_b = pcc_align((size_t)cells_all * 4), pk_b = pcc_align((size_t)cells_all * 2);
   // 17 bin bases per frame | 16 counts per frame | status per frame: the last two come back in one copy
@@ -1387,6 +1586,7 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   PCC_TRY(a_dec_stage(ctx, h_out, in_b, bytes, (size_t)nf * 17 * 4, &down, &back));
   uint8_t* stage = (uint8_t*)ctx->stage;
   memcpy(stage, tab.data(), (size_t)nf * sizeof(ADFrame));
+  if (xc) memcpy(stage + (size_t)nf * sizeof(ADFrame), cross.data(), (size_t)nf * 4);
   memcpy(stage + ftab_b, order.data(), (size_t)nf * sizeof(A2Order));
   for (int f = 0, k = 0; f < n_frames; ++f) {
     if (plan[(size_t)f].m == 0) continue;
@@ -1407,6 +1607,11 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
                      rank, first);
   PCC_CHECK_LAUNCH();
   PCC_TRY(a_launch_dec<true>(st, chunks, d_in, tab_b, nf, nctx_max, cw_max, resid, status));
+  if (xc) {
+    hipLaunchKernelGGL(k_ax_inv, dim3(nblk(n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab,
+                       (const int32_t*)(d_in + (size_t)nf * sizeof(ADFrame)), resid);
+    PCC_CHECK_LAUNCH();
+  }
   hipLaunchKernelGGL((nl ? k_a2_walk<true> : k_a2_walk<false>), dim3((unsigned)blocks), dim3(256), 0, st, d_ord, nf, d_tab,
                      (const uint32_t*)rank, (const uint32_t*)first, (const uint8_t*)resid, out, status);
   PCC_CHECK_LAUNCH();

@@ -1,6 +1,6 @@
 // attr_blob.h — the header of an attribute blob (attr.hip), parsed and checked on the host before anything is reserved
-// or launched.  Plain C++ (no HIP): tests/fuzz/fuzz_attr_header.cpp and fuzz_attr2_header.cpp put it under the
-// sanitizers.
+// or launched.  Plain C++ (no HIP): tests/fuzz/fuzz_attr_header.cpp, fuzz_attr2_header.cpp, fuzz_attr_nl_header.cpp
+// and fuzz_attr_cross_header.cpp put it under the sanitizers.
 //
 // Every size the decoder reserves or reads follows from what this parse accepted: the chunk table must add up to the
 // blob's own length, so a header cannot announce more words than the blob holds; n is bounded by the chunks
@@ -44,6 +44,22 @@
 //               cell at a level of detail is the reconstruction of its Morton-first point
 // Binarisation, contexts (bucket of |j| of the channel's previous point in the run, edges 2 / 5 / 12 / 30, not retuned),
 // model, S, chunks, word runs and the prefix rule are unchanged.  tests/attr_nl_ref.py restates both kinds in numpy.
+//
+// Cross-channel kinds, versions 8, 11, 13 and 14 (the cross forms of 1, 2, 4 and 7; the eight valid version bytes keep
+// odd parity, so any two differ in two bits): the plain kind's layout, byte for byte, with byte 3 = c | m << 4, bit
+// ch - 1 of m set for every channel ch of the mask M, a subset of {1 .. c - 1} (m != 0, m < 2^(c - 1); a plain kind
+// keeps byte 3 = c).  An empty frame is the 12-byte head with the cross version byte and that channel byte.
+// Let w[i][ch] be what the plain kind codes for point i, channel ch in its coding order — the wrapped residual r of
+// versions 1 and 2, the index j of versions 4 and 7 — an integer in [-h, h), h = 2^(8 bpv - 1).  The cross kind codes
+//   x[i][ch] = w[i][ch]                                         ch = 0 or ch not in M
+//   x[i][ch] = ((w[i][ch] - w[i][ch - 1] + h) & mask) - h       ch in M: a chain, against the ORIGINAL w of channel
+//                                                               ch - 1, not against x
+// through the coder as version 2's residuals go (no prediction inside the run; context = the bucket of |x| of the
+// channel's previous point in the lane's run, 0 for the run's first point).  The decoder undoes it per point, channel by
+// channel in ascending order (w[ch] = ((x[ch] + w[ch - 1] + h) & mask) - h), then continues exactly as the plain kind
+// does: a cross kind decodes to the values of the plain kind of the same call, at every level of detail, and the
+// near-lossless bound holds unchanged.  Binarisation, model, p0, S, chunks, word runs and the prefix rule are unchanged.
+// tests/attr_cross_ref.py restates the four kinds in numpy.
 #pragma once
 #include <stdint.h>
 
@@ -67,8 +83,9 @@ ATTR_HD static inline int attr_positions(int bpv) { return 16 * bpv; }
 ATTR_HD static inline int attr_contexts(int bpv, int c) { return c * kAttrBuckets * attr_positions(bpv); }
 
 struct AttrInfo {
-  int version;          // 1 | 4 (attr_parse_kind), 2 | 7 (attr2_parse_kind)
-  uint32_t max_error;   // e of versions 4 and 7 (0: lossless, and every blob without points)
+  int version;          // 1 | 4 | 8 | 13 (attr_parse_kind), 2 | 7 | 11 | 14 (attr2_parse_kind)
+  uint32_t max_error;   // e of versions 4, 7, 13 and 14 (0: lossless, and every blob without points)
+  int cross;            // m of the cross-channel kinds (bit ch - 1: channel ch is coded against ch - 1), 0: a plain kind
   int bpv, c, nctx;
   int64_t n, S, nc;
   int64_t off_p0, off_table, off_payload, payload_words;
@@ -92,6 +109,27 @@ static inline void attr_layout(int64_t n, int c, int64_t* S, int64_t* nc) {
 
 // the largest e of a value width: e < 2^(8 bpv - 1)
 ATTR_HD static inline uint32_t attr_max_error(int bpv) { return (1u << (8 * bpv - 1)) - 1u; }
+
+// the eight kinds of attribute blob: what a version byte says; false for every other byte
+static inline bool attr_kind(int version, bool* scalable, bool* nl, bool* cross) {
+  const int plain = version == 8 ? 1 : (version == 11 ? 2 : (version == 13 ? 4 : (version == 14 ? 7 : version)));
+  if (plain != 1 && plain != 2 && plain != 4 && plain != 7) return false;
+  *scalable = plain == 2 || plain == 7;
+  *nl = plain == 4 || plain == 7;
+  *cross = plain != version;
+  return true;
+}
+ATTR_HD static inline int attr_version(bool scalable, bool nl, bool cross) {
+  return cross ? (scalable ? (nl ? 14 : 11) : (nl ? 13 : 8)) : (scalable ? (nl ? 7 : 2) : (nl ? 4 : 1));
+}
+
+// byte 3 of a head: c channels (1 .. 4) and, in a cross kind, the mask m above them (m != 0, bits below c - 1 only); a
+// plain kind has nothing above c
+static inline bool attr_channels(uint8_t b3, bool cross, int* c, int* m) {
+  *c = cross ? b3 & 15 : b3;
+  *m = cross ? b3 >> 4 : 0;
+  return *c >= 1 && *c <= 4 && (!cross || (*m != 0 && *m < (1 << (*c - 1))));
+}
 
 // the nctx initial probabilities at b + off lie in [16, 4080]; else *bad_p is the first that does not
 static inline bool attr_check_p0(const uint8_t* b, int64_t off, int nctx, uint32_t* bad_p) {
@@ -121,20 +159,20 @@ static inline bool attr_sum_chunks(const uint8_t* table, int64_t nc, int bpv, in
   return true;
 }
 
-// version 1 (nl = false) or 4 (nl = true): x = 4 bytes of max_error move everything behind payload_len
-static inline int attr_parse_kind(const uint8_t* b, int64_t len, bool nl, AttrInfo* o) {
-  const char* tag = nl ? " v4" : "";
+// version 1 (nl = false) or 4 (nl = true): x = 4 bytes of max_error move everything behind payload_len; cross: their
+// cross-channel forms 8 and 13, the mask above the channels of byte 3
+static inline int attr_parse_kind(const uint8_t* b, int64_t len, bool nl, AttrInfo* o, bool cross = false) {
+  const char* tag = cross ? (nl ? " v13" : " v8") : (nl ? " v4" : "");
   const int x = nl ? 4 : 0;
-  if (!b || len < kAttrHead || b[0] != 'A' || b[1] != (nl ? 4 : 1)) {
+  if (!b || len < kAttrHead || b[0] != 'A' || b[1] != attr_version(false, nl, cross)) {
     pcc_set_error("attribute blob%s: bad header (len=%lld)", tag, (long long)len);
     return PCC_E_STREAM;
   }
   o->version = b[1];
   o->max_error = 0;
   o->bpv = b[2];
-  o->c = b[3];
-  if ((o->bpv != 1 && o->bpv != 2) || o->c < 1 || o->c > 4) {
-    pcc_set_error("attribute blob%s: %d bytes per value, %d channels", tag, o->bpv, o->c);
+  if ((o->bpv != 1 && o->bpv != 2) || !attr_channels(b[3], cross, &o->c, &o->cross)) {
+    pcc_set_error("attribute blob%s: %d bytes per value, %d channels%s", tag, o->bpv, o->c, cross ? ", or their mask" : "");
     return PCC_E_STREAM;
   }
   o->nctx = attr_contexts(o->bpv, o->c);
@@ -230,17 +268,18 @@ struct Attr2Plan {
 // b[0 .. len): the blob, or a prefix of it.  need_all: the decoder's form — the plan's bytes must be present (lod 0: the
 // blob, whole and nothing behind it); otherwise (pcc_attr_lod_info) the bytes must only reach what the plan is computed
 // from, the last needed chunk's length table.  Nothing beyond b[len) is read.
-// Version 2 (nl = false) or 7 (nl = true, x = 4 bytes of max_error in front of cells[16]).
-static inline int attr2_parse_kind(const uint8_t* b, int64_t len, int lod, bool need_all, bool nl, Attr2Info* o, Attr2Plan* pl) {
-  const int tag = nl ? 7 : 2, x = nl ? 4 : 0;
+// Version 2 (nl = false) or 7 (nl = true, x = 4 bytes of max_error in front of cells[16]); cross: their cross-channel
+// forms 11 and 14, the mask above the channels of byte 3.
+static inline int attr2_parse_kind(const uint8_t* b, int64_t len, int lod, bool need_all, bool nl, Attr2Info* o, Attr2Plan* pl,
+                                   bool cross = false) {
+  const int tag = attr_version(true, nl, cross), x = nl ? 4 : 0;
   ATTR2_REQUIRE(b && len >= kAttrHead && b[0] == 'A' && b[1] == tag, "attribute blob v%d: bad header (len=%lld)", tag, (long long)len);
   o->version = tag;
   o->max_error = 0;
   o->bpv = b[2] & 15;
   o->slod = b[2] >> 4;
-  o->c = b[3];
-  ATTR2_REQUIRE((o->bpv == 1 || o->bpv == 2) && o->c >= 1 && o->c <= 4, "attribute blob v%d: %d bytes per value, %d channels", tag,
-                o->bpv, o->c);
+  ATTR2_REQUIRE((o->bpv == 1 || o->bpv == 2) && attr_channels(b[3], cross, &o->c, &o->cross),
+                "attribute blob v%d: %d bytes per value, %d channels%s", tag, o->bpv, o->c, cross ? ", or their mask" : "");
   o->nctx = attr_contexts(o->bpv, o->c);
   o->n = (int64_t)attr_u32(b + 4);
   const int64_t payload = (int64_t)attr_u32(b + 8), total = kAttrHead + payload;

@@ -37,6 +37,15 @@ Near-lossless attributes (attribute blob versions 4 and 7): a quality setting wi
     GeometryCodec.attr_info(attr_blobs[0])["max_error"]                            # 2: host only, what a receiver reads
     frames, attrs = codec.decompress(blobs, attr_blobs)                            # the kind is read from the blob
 
+Cross-channel prediction (attribute blob versions 8, 11, 13, 14, the cross forms of 1, 2, 4, 7; include/pcc.h has the
+rule): what a channel would code is coded as its difference to the channel before it.  The sender's choice for
+correlated channels such as a camera's RGB, about a fifth off the colour bytes of recorded frames; uncorrelated channels
+grow under it.  The decoded values are exactly those of the same call without it, at every level of detail:
+
+    blobs, attr_blobs = codec.compress(frames, attributes=rgb, cross_channel=True)     # with scalable, lod, max_error
+    blobs, attr_blobs = codec.compress(frames, attributes=rgbx, cross_channel=(1, 2))  # G against R, B against G, X alone
+    GeometryCodec.attr_info(attr_blobs[0])["cross_channel"]                            # (1, 2); absent from a plain kind
+
 No decoded value is off by more than max_error from what max_error=0 (the default, lossless, the bytes of before)
 returns for the same call.  include/pcc.h states the rule.
 
@@ -76,7 +85,7 @@ import numpy as np
 import torch
 
 from ._abi import check, PccError, PCC_E_RANGE
-from .runtime import Runtime, _ptr
+from .runtime import Runtime, _ptr, ATTR_RUN_KINDS
 
 MAX_FRAMES = 65535      # the batch-index range of pcc_morton_keys
 MAX_LOD = 15            # levels of detail 0 .. 15 (csrc/octree2_blob.h)
@@ -211,8 +220,10 @@ class GeometryCodec:
 
     @staticmethod
     def attr_info(attr_blob):
-        """what the head of an attribute blob of any kind says, as a dict: version (1, 2, 4, 7), bpv (bytes per value),
-        channels, points, max_error (0: lossless; a blob without points records none), scalable, lod (the sender's).
+        """what the head of an attribute blob of any kind says, as a dict: version (1, 2, 4, 7, or their cross-channel
+        forms 8, 11, 13, 14), bpv (bytes per value), channels, points, max_error (0: lossless; a blob without points
+        records none), scalable, lod (the sender's); a cross-channel kind adds cross_channel, the tuple of channel
+        indices coded against the channel before them (a plain kind's dict has no such key).
         Host only; `attr_blob` may be a prefix of 16 bytes or more."""
         return Runtime.attr_info(bytes(attr_blob))
 
@@ -231,8 +242,35 @@ class GeometryCodec:
                                  f"{(1 << (8 * a.dtype.itemsize - 1)) - 1}")
         return max_error
 
+    @staticmethod
+    def _check_cross(cross_channel, attrs):
+        """cross_channel of compress -> one mask per frame (bit ch - 1: channel ch against ch - 1), or None for False"""
+        if cross_channel is False:
+            return None
+        if cross_channel is True:
+            chans = None
+        elif isinstance(cross_channel, (tuple, list, range)) and all(
+                isinstance(ch, (int, np.integer)) and not isinstance(ch, bool) for ch in cross_channel):
+            chans = sorted(int(ch) for ch in cross_channel)
+            if len(set(chans)) != len(chans) or any(ch < 1 or ch > 3 for ch in chans):
+                raise ValueError(f"cross_channel must name distinct channels in 1 .. 3, got {tuple(cross_channel)!r}")
+        else:
+            raise TypeError(f"cross_channel must be False, True or a sequence of channel indices, got {cross_channel!r}")
+        if attrs is None:
+            raise ValueError("cross_channel predicts the channels of attributes: it needs attributes=")
+        masks = []
+        for f, a in enumerate(attrs):
+            c = a.shape[1]
+            if chans is None:
+                masks.append((1 << (c - 1)) - 1)
+                continue
+            if chans and chans[-1] >= c:
+                raise ValueError(f"frame {f}: cross_channel names channel {chans[-1]}, the frame has channels 0 .. {c - 1}")
+            masks.append(sum(1 << (ch - 1) for ch in chans))
+        return masks
+
     def compress(self, frames, attributes=None, lod=0, scalable=False, *, voxel=None, origin=(0.0, 0.0, 0.0),
-                 invalid="raise", return_index=False, max_error=0):
+                 invalid="raise", return_index=False, max_error=0, cross_channel=False):
         """frames: a sequence of int16 / int32 [n_f, 3] arrays -> a list of bytes, one version-2 blob per frame.
         Duplicate points are removed (as np.unique), out-of-range coordinates raise PccError (PCC_E_RANGE).
         lod = k > 0: the sender's side of a level of detail — blob f is the version-2 blob of the distinct cells
@@ -248,6 +286,13 @@ class GeometryCodec:
         scalable=True) — no decoded value is off by more than e from what max_error=0 returns for the same call, at
         every level of detail (attr_info reads e back from a blob).  The geometry blobs are the same; 0, the default, is
         the lossless coder and its bytes.
+        cross_channel: False (the default, the bytes of before); True — in every frame each channel 1 .. c_f - 1 is coded
+        against the channel before it, attribute blob versions 8 / 11 / 13 / 14 in place of 1 / 2 / 4 / 7 (include/pcc.h
+        has the rule), a frame of one channel keeps its plain kind; or a sequence of distinct channel indices in 1 .. 3,
+        those channels only — (1, 2) for RGB beside an unrelated fourth channel — where an index no frame f has raises
+        ValueError naming f.  Anything else: TypeError; without attributes: ValueError.  The decoded values are exactly
+        those of the same call without it, at every level of detail and under max_error; the geometry blobs are the same.
+        For correlated channels (a camera's colour: about a fifth smaller); uncorrelated ones grow, the sender chooses.
 
         Frame types: numpy int16 / int32 as above, numpy float32, or torch tensors of those three dtypes on the host or
         on this codec's device; all frames of a call integer or all float32, all on the host or all on the device
@@ -278,6 +323,7 @@ class GeometryCodec:
             raise ValueError("voxel= with integer frames: they are on the lattice already")
         attrs = None if attributes is None else self._check_attributes(frames, attributes)
         max_error = self._check_max_error(max_error, attrs)
+        cross = self._check_cross(cross_channel, attrs)
         nb = len(frames)
 
         def result(blobs, attr_blobs=None, index=None):
@@ -292,11 +338,11 @@ class GeometryCodec:
             front = self._front(rt, frames, is_float, on_device, caller, "GeometryCodec.compress", lod, voxel, origin,
                                 invalid == "drop")
             if front.n_keep == 0:
-                return result(*self._nothing_coded(rt, front, attrs, version, max_error, return_index, on_device))
+                return result(*self._nothing_coded(rt, front, attrs, version, max_error, return_index, on_device, cross))
             blobs = rt.octree_encode_frames(front.keys, nb, 3 * lod)
             attr_blobs = index = None
             if attrs is not None:
-                attr_blobs = self._encode_attributes(rt, attrs, blobs, front, version, 3 * lod, max_error)
+                attr_blobs = self._encode_attributes(rt, attrs, blobs, front, version, 3 * lod, max_error, cross)
             if return_index:
                 first_run = torch.empty(nb, dtype=torch.int64, pin_memory=True)
                 np.cumsum([0] + [struct.unpack_from("<I", b, 4)[0] for b in blobs[:-1]], out=first_run.numpy())
@@ -381,11 +427,11 @@ class GeometryCodec:
         distinct = keys if n_u.value == n_keep else rt.gather_rows(keys, rows[:n_u.value])
         return front._replace(perm=perm, sorted_keys=keys, rows=rows, n_unique=n_u.value, keys=distinct)
 
-    def _nothing_coded(self, rt, front, attrs, version, max_error, return_index, on_device):
+    def _nothing_coded(self, rt, front, attrs, version, max_error, return_index, on_device, cross=None):
         """(blobs, attribute blobs, index) of a call none of whose rows is coded: the empty blobs, the attribute blobs
         of frames without points, and -1 for every input row"""
         blobs = rt.octree_encode_frames(rt.empty((0,), torch.int64), front.nb)
-        attr_blobs = None if attrs is None else self._encode_attributes(rt, attrs, blobs, front, version, 0, max_error)
+        attr_blobs = None if attrs is None else self._encode_attributes(rt, attrs, blobs, front, version, 0, max_error, cross)
         if not return_index:
             return blobs, attr_blobs, None
         index = torch.full((front.n,), -1, dtype=torch.int32, device=rt.device)
@@ -401,7 +447,7 @@ class GeometryCodec:
         return _split(index, sizes)
 
     @staticmethod
-    def _encode_attributes(rt, attrs, blobs, front, version, key_shift, max_error):
+    def _encode_attributes(rt, attrs, blobs, front, version, key_shift, max_error, cross=None):
         # the values as they come, frame by frame at 16-byte offsets, in one upload; the merge into Morton order
         # happens on the device from the sort's permutation and the runs of equal keys
         offs, at = [], 0
@@ -417,7 +463,7 @@ class GeometryCodec:
         points = [struct.unpack_from("<I", b, 4)[0] for b in blobs]
         n_kept = front.n_keep if front.n_keep < front.n else None      # None: no row was dropped
         return rt.attr_encode_frames(values, offs, formats, _ends(front.sizes), points, front.perm, front.rows, front.n_unique,
-                                     version, front.keys, key_shift, n_kept, max_error)
+                                     version, front.keys, key_shift, n_kept, max_error, cross)
 
     def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0, *, voxel=None, origin=(0.0, 0.0, 0.0)):
         """version-2 blobs -> a list of int32 [n_f, 3] point sets in Morton order: numpy arrays (output="numpy") or
@@ -428,9 +474,10 @@ class GeometryCodec:
         [cells, 3] in Morton order (corner of a cell c << k, centre (c << k) + ((1 << k) >> 1)); with attr_blobs of
         version 2 (compress(..., scalable=True)), or prefixes of them (attr_lod_info): attributes[f] is [cells, c], row j
         the value of the Morton-first point of cell j.  The kind of every attribute blob (lossless 1 / 2, near-lossless
-        4 / 7 of compress(..., max_error=e)) is read from the blob; version 7 behaves as version 2 and its prefixes do,
-        every value within e.  The four kinds may be mixed at lod 0; an attribute blob of version 1 or 4 at lod > 0
-        raises ValueError.
+        4 / 7 of compress(..., max_error=e), their cross-channel forms 8 / 11 / 13 / 14 of compress(...,
+        cross_channel=...)) is read from the blob; version 7 behaves as version 2 and its prefixes do, every value within
+        e, and a cross-channel kind returns what its plain kind returns.  The eight kinds may be mixed at lod 0; an
+        attribute blob of version 1, 4, 8 or 13 at lod > 0 raises ValueError.
         voxel (with origin): the point sets come back as float32 [n_f, 3] in the caller's unit instead of int32,
         x = origin + t * voxel, one float32 multiplication and then one addition on the device (include/pcc.h has the
         rule): t the lattice index at lod 0 and, at lod k, the centre of the cell's lattice points
@@ -451,11 +498,11 @@ class GeometryCodec:
             if len(attr_blobs) != len(blobs):
                 raise ValueError(f"{len(attr_blobs)} attribute blobs for {len(blobs)} geometry blobs")
             kind = [b[1] if len(b) > 1 else 0 for b in attr_blobs]      # runs of one kind are decoded in one call
-            v1 = [k in (1, 4) for k in kind]
+            v1 = [k in ATTR_RUN_KINDS for k in kind]
             if lod and any(v1):
                 raise ValueError(f"frame {v1.index(True)}: attributes of blob version {kind[v1.index(True)]} cannot be decoded at lod > 0: it "
                                  "is one predictive stream in full-resolution Morton order, so neither its bytes nor "
-                                 "its decoding can be cut; store version 2 or 7 (compress(..., scalable=True)) or ship "
+                                 "its decoding can be cut; store version 2, 7, 11 or 14 (compress(..., scalable=True)) or ship "
                                  "coarse attributes with compress(frames, attributes=..., lod=k)")
         with self._lock, self.rt as rt:
             # version 2 reads the cells where the geometry decode left them: on the device

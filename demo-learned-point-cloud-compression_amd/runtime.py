@@ -708,7 +708,7 @@ class Runtime:
         return (views, pts) if whole else views
 
     def attr_encode_frames(self, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique,
-                           version=1, keys=None, key_shift=0, n_kept=None, max_error=0):
+                           version=1, keys=None, key_shift=0, n_kept=None, max_error=0, cross=None):
         """attribute blobs (csrc/attr.hip) of len(formats) frames at once (pcc_attr_encode_frames): `values` a
         device uint8 tensor with frame f's [rows_f, c_f] values at byte value_offsets[f], formats[f] = bytes per value |
         c_f << 8, row_offsets (n_frames + 1) the frames' rows among the call's keys, perm / run_starts what
@@ -717,7 +717,10 @@ class Runtime:
         prefixes; `keys` the call's distinct sorted keys on the device (what octree_encode_frames took) and their
         key_shift.  n_kept (pcc_attr_encode_frames_kept): the call dropped rows; row_offsets still count every input row,
         n_kept of the sorted keys belong to kept rows.  max_error = e > 0 (pcc_attr_encode_frames_nl): the near-lossless
-        kind of that version, blob version 4 (for 1) or 7 (for 2), no decoded value off by more than e."""
+        kind of that version, blob version 4 (for 1) or 7 (for 2), no decoded value off by more than e.  cross
+        (pcc_attr_encode_frames_cross): one cross-channel mask per frame, bit ch - 1 set where channel ch is coded
+        against channel ch - 1 (include/pcc.h has the rule) -> blob versions 8, 11, 13, 14 for 1, 2, 4, 7; a frame whose
+        mask is 0 gets its plain kind, and so does every frame with cross=None or all masks 0."""
         if version not in (1, 2):
             raise ValueError(f"attribute blob version {version!r}: 1 or 2")
         max_error = int(max_error)
@@ -730,7 +733,14 @@ class Runtime:
         offs = (C.c_int64 * (nf + 1))()
         head = (self.ctx, _ptr(values), (C.c_int64 * nf)(*value_offsets), (C.c_int32 * nf)(*formats),
                 (C.c_int64 * (nf + 1))(*row_offsets), (C.c_int64 * nf)(*points), nf, _ptr(perm), _ptr(run_starts), n_unique)
-        if max_error:
+        if cross is not None and len(cross) != nf:
+            raise ValueError(f"{len(cross)} cross-channel masks for {nf} frames")
+        if cross is not None and any(cross):
+            check(self.lib.pcc_attr_encode_frames_cross(head[0], version, *head[1:], -1 if n_kept is None else int(n_kept),
+                                                        _ptr(keys) if version == 2 else None, int(key_shift), max_error,
+                                                        (C.c_int32 * nf)(*[int(m) for m in cross]), _np_ptr(out), cap, offs),
+                  "pcc_attr_encode_frames_cross")
+        elif max_error:
             check(self.lib.pcc_attr_encode_frames_nl(head[0], version, *head[1:], -1 if n_kept is None else int(n_kept),
                                                      _ptr(keys) if version == 2 else None, int(key_shift), max_error,
                                                      _np_ptr(out), cap, offs), "pcc_attr_encode_frames_nl")
@@ -759,21 +769,28 @@ class Runtime:
     @staticmethod
     def attr_info(blob):
         """what the head of an attribute blob of any kind says (pcc_attr_info, host only): a dict of version (1, 2, 4,
-        7), bpv, channels, points, max_error (0: lossless), scalable, lod (the sender's)"""
+        7, or their cross-channel forms 8, 11, 13, 14), bpv, channels, points, max_error (0: lossless), scalable, lod (the
+        sender's); for the cross-channel kinds also cross_channel, the tuple of channels coded against the channel
+        before them (pcc_attr_cross_mask)"""
         buf = np.frombuffer(blob, dtype=np.uint8)
         v = [C.c_int32(0) for _ in range(6)]
         n = C.c_int64(0)
         check(_abi.lib().pcc_attr_info(_np_ptr(buf) if buf.shape[0] else None, buf.shape[0], C.byref(v[0]), C.byref(v[1]),
                                        C.byref(v[2]), C.byref(n), C.byref(v[3]), C.byref(v[4]), C.byref(v[5])), "pcc_attr_info")
-        return {"version": v[0].value, "bpv": v[1].value, "channels": v[2].value, "points": n.value,
+        info = {"version": v[0].value, "bpv": v[1].value, "channels": v[2].value, "points": n.value,
                 "max_error": v[3].value, "scalable": bool(v[4].value), "lod": v[5].value}
+        if info["version"] in ATTR_CROSS_KINDS:
+            m = C.c_int32(0)
+            check(_abi.lib().pcc_attr_cross_mask(_np_ptr(buf), buf.shape[0], C.byref(m)), "pcc_attr_cross_mask")
+            info["cross_channel"] = tuple(ch for ch in range(1, 4) if m.value >> (ch - 1) & 1)
+        return info
 
     def attr_decode_frames(self, blobs, points=None, device=False, lod=None, cells=None):
         """attribute blobs -> one [n_f, c_f] array per blob in its dtype (uint8 / uint16), row i belonging to decoded
-        point i (pcc_attr_decode_frames: versions 1 and 4, one version per call): numpy arrays, or views of one device
+        point i (pcc_attr_decode_frames: versions 1, 4, 8 and 13, one version per call): numpy arrays, or views of one device
         tensor (device=True).  points[f]
         (optional): frame f's geometry point count, checked against the blob before anything is launched.
-        lod = k (0 .. 15) with cells (pcc_attr_decode_frames_lod): blobs of version 2, or of version 7, or prefixes of them (attr_lod_info)
+        lod = k (0 .. 15) with cells (pcc_attr_decode_frames_lod): blobs of version 2, or of 7, 11 or 14, or prefixes of them (attr_lod_info)
         -> row j the value of the j-th cell of the frame's geometry at that lod; `cells` the device tensors
         octree_decode_frames(..., device=True, lod=k) returned for the same frames (views of one tensor)."""
         nb = len(blobs)
@@ -829,6 +846,11 @@ class Runtime:
                 res.append(seg.view(np.uint8 if bpv == 1 else np.uint16).reshape(n, c))
         return res
 
+
+# the kinds of attribute blob by version byte (csrc/attr_blob.h): those one lane run predicts through, which decode at
+# lod 0 only (pcc_attr_decode_frames), and the cross-channel forms 8, 11, 13, 14 of 1, 2, 4, 7
+ATTR_RUN_KINDS = (1, 4, 8, 13)
+ATTR_CROSS_KINDS = (8, 11, 13, 14)
 
 OCTREE_V2_MIN_LEAVES = 65536     # include/pcc.h PCC_OCTREE_V2_MIN_LEAVES
 OCTREE_V3_MIN_LEAVES = 8192      # include/pcc.h PCC_OCTREE_V3_MIN_LEAVES

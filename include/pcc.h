@@ -925,6 +925,61 @@ int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_version,
                   int32_t* h_bpv, int32_t* h_channels, int64_t* h_points,
                   int32_t* h_max_error, int32_t* h_scalable, int32_t* h_lod);
 
+/* Cross-channel prediction for attributes of two and more channels: attribute
+ * blob versions 8, 11, 13 and 14, the cross forms of 1, 2, 4 and 7, chosen by
+ * the sender frame by frame.  The channels of a camera's colour are strongly
+ * correlated, and so are what the plain kinds code for them; a cross kind
+ * codes the difference.
+ *
+ * The rule.  A frame of c >= 2 channels and a mask M, a subset of
+ * {1 .. c - 1}.  Let w[i][ch] be what the plain kind codes for point i,
+ * channel ch, in the plain kind's coding order: the wrapped residual r of
+ * versions 1 and 2, the index j of versions 4 and 7, both integers in
+ * [-h, h), h = 2^(8 bpv - 1), mask = 2^(8 bpv) - 1.  The cross kind codes
+ *   x[i][ch] = w[i][ch]                                    ch = 0 or not in M
+ *   x[i][ch] = ((w[i][ch] - w[i][ch-1] + h) & mask) - h    ch in M
+ * a chain: channel ch against the ORIGINAL w of channel ch - 1, not against
+ * x.  The decoder undoes it per point, channel by channel in ascending order,
+ * w[ch] = ((x[ch] + w[ch-1] + h) & mask) - h, then continues exactly as the
+ * plain kind does.  x goes through the coder as version 2's residuals do: no
+ * prediction inside the run, context (channel, bucket of |x| of the channel's
+ * previous point in the lane's run, 0 for the run's first point, position).
+ * Binarisation, model, p0, S, chunks, word runs and the prefix rule of the
+ * levels of detail are the plain kind's.
+ * Consequence: a cross kind decodes to exactly the values the plain kind of
+ * the same call decodes to, at every level of detail, and the near-lossless
+ * bound holds unchanged.  Uncorrelated channels grow under it: the sender
+ * chooses.
+ * Layout: the plain kind's, with the cross version byte and byte 3 =
+ * c | m << 4, bit ch - 1 of m set for ch in M (m != 0, m < 2^(c - 1); a plain
+ * kind has byte 3 = c).  n = 0: the 12-byte head with those two bytes.  The
+ * eight valid version bytes 1, 2, 4, 7, 8, 11, 13, 14 have odd parity, so any
+ * two differ in two bits.
+ *   _encode_frames_cross : pcc_attr_encode_frames_nl with h_cross, one mask m
+ *     per frame (n_frames entries, not NULL): 0 gives the frame's plain kind,
+ *     byte for byte; m < 0 or m >= 2^(c - 1) for the frame's c: PCC_E_ARG
+ *     naming the frame.  A call whose frames with points all have m = 0 runs
+ *     what _encode_frames_nl runs; any other call one elementwise launch more.
+ *   _cross_mask : host only, no ctx: m of a head (0 for the plain kinds); the
+ *     checks of pcc_attr_info, PCC_E_STREAM where they fail (among them a
+ *     cross version byte with m = 0 or a bit at c - 1 or above, and a plain one
+ *     with anything above c in byte 3).
+ *   pcc_attr_decode_frames reads 8 and 13 beside 1 and 4,
+ *     pcc_attr_decode_frames_lod and pcc_attr_lod_info 11 and 14 beside 2 and
+ *     7, still one version per call; pcc_attr_info reports the cross version
+ *     byte and c (the low nibble of byte 3). */
+int pcc_attr_encode_frames_cross(pcc_ctx* ctx, int version, const void* d_values,
+                                 const int64_t* h_value_offsets,
+                                 const int32_t* h_format, const int64_t* h_rows,
+                                 const int64_t* h_points, int n_frames,
+                                 const uint32_t* d_perm,
+                                 const uint32_t* d_run_starts, int64_t n_unique,
+                                 int64_t n_kept, const uint64_t* d_keys,
+                                 int key_shift, int max_error,
+                                 const int32_t* h_cross, uint8_t* h_out,
+                                 int64_t cap, int64_t* h_offsets);
+int pcc_attr_cross_mask(const uint8_t* h_in, int64_t len, int32_t* h_mask);
+
 /* ---- exact nearest neighbours on the lattice: the D1 metric (csrc/nn.hip, the walk in csrc/nn_cells.h) -- */
 
 /* The rule (tests/nn_ref.py restates it in numpy).  For a frame f there are
