@@ -42,6 +42,14 @@
 // returns the differences, k_ax_inv undoes them in place, and the plain kind's last step follows (k_a8_recon redoes
 // version 1's predictor).  Launched for these kinds only.  tests/attr_cross_ref.py restates them in numpy.
 //
+// Transform-coded, version 19 (attr_blob.h has the rule and the layout; q = qstep): lossy, an integer lifting transform
+// over the binary splits of the Morton tree.  Encoder: the coding order at bit granularity (k_at_size / k_at_scan /
+// k_at_place), one synchronisation that tells which of the 48 sublevels hold a point, one k_at_lift<true> per such
+// sublevel bottom-up over the merged values in place (all frames of the call in one launch), the mean (k_at_mean), and
+// k_a_stats / k_a_enc<false> / k_a_pack<.., TR> over the indices.  Decoder (pcc_attr_decode_frames_lod at lod 0, against
+// the cells): the same order stage, k_a_dec<true>, k_at_root, k_at_lift<false> top-down, k_at_store.
+// tests/attr_transform_ref.py restates the kind in numpy.
+//
 // Host side: the kinds share one encode sequence (a_encode_frames) and the helpers of the two decoders; DESIGN.md,
 // "attr.hip: one encode path, shared decode helpers".
 #include "common.h"
@@ -322,8 +330,9 @@ __global__ __launch_bounds__(64) void k_a_enc(const uint16_t* __restrict__ merge
 // bytes, or -1 (out_cap).  V2: the head of attribute blob version 2, with the frame's 16 values-per-level counts
 // (cells_all[16 f + k], attr_blob.h) and the sender's level of detail.  NL: the heads of versions 4 / 7, the frame's
 // max_error behind payload_len and everything else one word later.  XC (a call with cross-channel frames): frame f with
-// cross_all[f] = m != 0 gets the cross form of the version byte and its mask above the channels of byte 3
-template <bool V2, bool NL = false, bool XC = false>
+// cross_all[f] = m != 0 gets the cross form of the version byte and its mask above the channels of byte 3.  TR (with NL
+// and without V2): version 19's head — version 4's with q = h.e where e stands, byte 19 and the slod nibble
+template <bool V2, bool NL = false, bool XC = false, bool TR = false>
 __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ work_all, const AFrame* __restrict__ tab, int nf,
                                                 const uint16_t* __restrict__ states_all, const uint16_t* __restrict__ lens_all,
                                                 const uint32_t* __restrict__ words_all, const uint16_t* __restrict__ p0_all,
@@ -364,6 +373,7 @@ __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ wor
         const uint32_t m = (uint32_t)cross_all[f];
         if (m) out[1] = (uint8_t)attr_version(V2, NL, true), out[3] = (uint8_t)((uint32_t)h.c | (m << 4));
       }
+      if constexpr (TR) out[1] = (uint8_t)kAttrTVersion, out[2] = (uint8_t)(h.bpv | (slod << 4));
       o32[1] = (uint32_t)h.n;
       o32[2] = (uint32_t)(total - kAttrHead);
       if constexpr (NL) o32[3] = (uint32_t)h.e;
@@ -944,10 +954,275 @@ __global__ __launch_bounds__(256) void k_a8_recon(const ADFrame* __restrict__ ta
   }
 }
 
+// ---- version 19: the transform over the binary splits of the Morton tree (attr_blob.h states the rule) --------------
+// The coding order is version 2's introduction order at bit granularity: 49 sublevels b = 0 .. 48 in place of 17 sizes,
+// found by the same three steps (k_at_size / k_at_scan / k_at_place are k_a2_size / k_a2_scan / k_a2_place over 49
+// bins; the rows are A2Order's: shift = the encoder's key_shift, the decoder's slod).  What they leave is, per frame,
+// where every sublevel starts in the coding order and how many points it holds (bins[98 f + b], bins[98 f + 49 + b]) and
+// the Morton index of every place (inv[pt0 + r]); the host reads the counts and launches k_at_lift once per sublevel
+// that holds a point in any frame of the call, over the most points a frame has there.
+constexpr int kATBins = 49;
+
+template <bool FROM_CELLS>
+__global__ __launch_bounds__(256) void k_at_size(const void* __restrict__ src, const A2Order* __restrict__ tab, int nf,
+                                                 uint64_t* __restrict__ keys_out, uint16_t* __restrict__ packed,
+                                                 uint32_t* __restrict__ hist) {
+  __shared__ uint32_t s_cnt[4][kATBins];
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].blk0; });
+  const A2Order& h = tab[f];
+  const int64_t i = ((int64_t)blockIdx.x - h.blk0) * blockDim.x + threadIdx.x;
+  const bool act = i < h.n;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int bin = kATBins;   // none
+  if (act) {
+    uint64_t key, prev = 0;
+    int sh = 0;
+    if constexpr (FROM_CELLS) {
+      const int32_t* cells = static_cast<const int32_t*>(src);
+      const int bias = 32768 >> h.shift;
+      key = a2_cell_key(cells, h.pt0 + i, bias);
+      if (i > 0) prev = a2_cell_key(cells, h.pt0 + i - 1, bias);
+      keys_out[h.pt0 + i] = key;
+    } else {
+      const uint64_t* keys = static_cast<const uint64_t*>(src);
+      key = keys[h.pt0 + i];
+      if (i > 0) prev = keys[h.pt0 + i - 1];
+      sh = h.shift;
+    }
+    const uint64_t x = ((key ^ prev) & 0xFFFFFFFFFFFFull) >> sh;
+    bin = i == 0 ? 48 : (x ? 63 - __clzll((long long)x) : 0);
+  }
+  int lr = 0;
+  for (int b = 0; b < kATBins; ++b) {
+    const unsigned long long m = __ballot(bin == b);
+    if (bin == b) lr = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_cnt[wave][b] = (uint32_t)__popcll(m);
+  }
+  __syncthreads();
+  if (act) {
+    for (int w = 0; w < wave; ++w) lr += (int)s_cnt[w][bin];
+    packed[h.pt0 + i] = (uint16_t)((bin << 8) | lr);
+  }
+  if (threadIdx.x < kATBins)
+    hist[(int64_t)blockIdx.x * kATBins + threadIdx.x] =
+        s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
+}
+
+// one block per frame, thread b < 49 owns sublevel b: hist[49 block + b] becomes the number of points of sublevel b in
+// the frame's blocks in front of it (a serial walk over the frame's blocks, 49 neighbouring words per step); then
+// bins[98 f + b] = the points of a higher sublevel, bins[98 f + 49 + b] = the points of sublevel b
+__global__ __launch_bounds__(64) void k_at_scan(const A2Order* __restrict__ tab, uint32_t* __restrict__ hist,
+                                                uint32_t* __restrict__ bins) {
+  __shared__ uint32_t s_tot[kATBins];
+  const int f = blockIdx.x, b = threadIdx.x;
+  const A2Order& h = tab[f];
+  const int64_t nb = (h.n + 255) / 256;
+  if (b < kATBins) {
+    uint32_t run = 0;
+    uint32_t* col = hist + (int64_t)h.blk0 * kATBins + b;
+    for (int64_t k0 = 0; k0 < nb; k0 += 8) {   // eight loads in flight
+      uint32_t v[8];
+#pragma unroll
+      for (int d = 0; d < 8; ++d) v[d] = k0 + d < nb ? col[(k0 + d) * kATBins] : 0u;
+#pragma unroll
+      for (int d = 0; d < 8; ++d) {
+        if (k0 + d < nb) col[(k0 + d) * kATBins] = run;
+        run += v[d];
+      }
+    }
+    s_tot[b] = run;
+  }
+  __syncthreads();
+  if (b < kATBins) {
+    uint32_t above = 0;
+    for (int k = b + 1; k < kATBins; ++k) above += s_tot[k];
+    bins[f * 2 * kATBins + b] = above;
+    bins[f * 2 * kATBins + kATBins + b] = s_tot[b];
+  }
+}
+
+// inv[pt0 + r] = the Morton index of the point at place r of the frame's coding order
+__global__ __launch_bounds__(256) void k_at_place(const A2Order* __restrict__ tab, int nf, const uint16_t* __restrict__ packed,
+                                                  const uint32_t* __restrict__ hist, const uint32_t* __restrict__ bins,
+                                                  uint32_t* __restrict__ inv) {
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].blk0; });
+  const A2Order& h = tab[f];
+  const int64_t i = ((int64_t)blockIdx.x - h.blk0) * blockDim.x + threadIdx.x;
+  if (i >= h.n) return;
+  const uint32_t pk = packed[h.pt0 + i];
+  const int b = (int)(pk >> 8);
+  const int64_t r = (int64_t)bins[f * 2 * kATBins + b] + hist[(int64_t)blockIdx.x * kATBins + b] + (pk & 255u);
+  if (r >= h.n) return;   // cannot happen: the places are a permutation of the frame's points
+  inv[h.pt0 + r] = (uint32_t)i;
+}
+
+// floor(a / w), w > 0
+__device__ __forceinline__ int64_t at_floor_div(int64_t a, int64_t w) {
+  const int64_t d = a / w;
+  return d - ((a % w != 0 && a < 0) ? 1 : 0);
+}
+
+// s = max(2, isqrt(floor(q^2 w / (wa wb)))): the quotient is at most 2 q^2 < 2^31, which a double holds exactly; the
+// root's estimate is corrected in integers
+__device__ __forceinline__ int64_t at_step(int64_t q, int64_t wa, int64_t wb) {
+  const uint64_t v = (uint64_t)(q * q) * (uint64_t)(wa + wb) / ((uint64_t)wa * (uint64_t)wb);
+  uint64_t r = (uint64_t)sqrt((double)v);
+  while (r * r > v) --r;
+  while ((r + 1) * (r + 1) <= v) ++r;
+  return r < 2 ? 2 : (int64_t)r;
+}
+
+// The pairs of sublevel t, frame = blockIdx.y: thread j takes place bins[..][t] + j of the frame's coding order, point
+// i = inv[place]; lo and hi by two binary searches in the frame's keys (sh: the low bits of an encoder's keys that are
+// not the cells').  ENC: val = the frame's merged values, lifted in place (a node's value lies between its children's,
+// so it stays a uint16), the index to the point's place of idx, wrapped to the value width.  Otherwise (decoder): x_all
+// the decoded indices in coding order (bpv bytes each, at out_off), val_all int64 [n][c] at element out_off; status |= 8
+// where the keys give a pair without a left or a right leaf (keys that are not sorted and distinct).
+template <bool ENC>
+__global__ __launch_bounds__(256) void k_at_lift(const uint64_t* __restrict__ keys_all, const A2Order* __restrict__ tab,
+                                                 const uint32_t* __restrict__ bins, const uint32_t* __restrict__ inv, int t,
+                                                 const AFrame* __restrict__ etab, uint16_t* __restrict__ val_e, uint16_t* __restrict__ idx,
+                                                 const ADFrame* __restrict__ dtab, const uint8_t* __restrict__ x_all,
+                                                 int64_t* __restrict__ val_d, int32_t* __restrict__ status_all) {
+  const int f = blockIdx.y;
+  const A2Order& h = tab[f];
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= (int64_t)bins[f * 2 * kATBins + kATBins + t]) return;
+  const int64_t r = (int64_t)bins[f * 2 * kATBins + t] + j;
+  if (r >= h.n) return;
+  const int64_t i = inv[h.pt0 + r];
+  if (i <= 0 || i >= h.n) return;
+  const uint64_t* keys = keys_all + h.pt0;
+  const int bit = t + (ENC ? h.shift : 0);   // <= 47
+  const uint64_t key = keys[i], low = (1ull << bit) - 1ull;
+  const uint64_t t_lo = key & ~((low << 1) | 1ull), t_hi = (key | low) + 1ull;
+  int64_t lo = 0, hi = i;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < t_lo) lo = mid + 1; else hi = mid;
+  }
+  int64_t a = i + 1, b = h.n;
+  while (a < b) {
+    const int64_t mid = (a + b) >> 1;
+    if (keys[mid] < t_hi) a = mid + 1; else b = mid;
+  }
+  const int64_t wa = i - lo, wb = a - i, w = wa + wb;
+  if constexpr (ENC) {
+    const AFrame& fr = etab[f];
+    if (wa < 1) return;   // cannot happen: the keys are sorted and distinct
+    const int c = fr.c;
+    const int64_t s = at_step(fr.e, wa, wb), H = (int64_t)1 << (8 * fr.bpv - 1);
+    const uint32_t mask = (1u << (8 * fr.bpv)) - 1u;
+    uint16_t* v = val_e + fr.val_off;
+    for (int ch = 0; ch < c; ++ch) {
+      const int64_t va = v[lo * c + ch], hh = (int64_t)v[i * c + ch] - va;
+      v[lo * c + ch] = (uint16_t)(va + at_floor_div(wb * hh, w));
+      const int64_t m = std::min<int64_t>(((hh < 0 ? -hh : hh) + s / 2) / s, H - 1);
+      idx[fr.val_off + r * c + ch] = (uint16_t)((uint32_t)(hh < 0 ? -m : m) & mask);
+    }
+  } else {
+    const ADFrame& fr = dtab[f];
+    if (wa < 1) {
+      atomicOr(status_all + f, 8);
+      return;
+    }
+    const int c = fr.c, bpv = fr.bpv;
+    const int64_t s = at_step(fr.max_error, wa, wb);
+    const uint8_t* x = x_all + fr.out_off + r * c * bpv;
+    int64_t* v = val_d + fr.out_off;
+    for (int ch = 0; ch < c; ++ch) {
+      const int64_t hh = (int64_t)a_load_s(x, bpv, ch) * s;   // |x| < 2^15, s < 2^16; wb < 2^27: no product leaves int64
+      const int64_t va = v[lo * c + ch] - at_floor_div(wb * hh, w);
+      v[lo * c + ch] = va;
+      v[i * c + ch] = va + hh;
+    }
+  }
+}
+
+// encoder, behind the last sublevel: x[0] = val[0] - H to place 0; one thread per (frame, channel)
+__global__ __launch_bounds__(256) void k_at_mean(const AFrame* __restrict__ tab, int nf, const uint16_t* __restrict__ val,
+                                                 uint16_t* __restrict__ idx) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x, f = t >> 2, ch = t & 3;
+  if (f >= nf || ch >= tab[f].c) return;
+  const AFrame& h = tab[f];
+  idx[h.val_off + ch] = (uint16_t)(((uint32_t)val[h.val_off + ch] - (1u << (8 * h.bpv - 1))) & ((1u << (8 * h.bpv)) - 1u));
+}
+
+// decoder, in front of the first sublevel: val[0] = x[0] + H
+__global__ __launch_bounds__(256) void k_at_root(const ADFrame* __restrict__ tab, int nf, const uint8_t* __restrict__ x_all,
+                                                 int64_t* __restrict__ val) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x, f = t >> 2, ch = t & 3;
+  if (f >= nf || ch >= tab[f].c) return;
+  const ADFrame& h = tab[f];
+  val[h.out_off + ch] = (int64_t)a_load_s(x_all + h.out_off, h.bpv, ch) + ((int64_t)1 << (8 * h.bpv - 1));
+}
+
+// decoder, behind the last sublevel: the clamp and the narrowing store, frame = blockIdx.y, one thread per value
+__global__ __launch_bounds__(256) void k_at_store(const ADFrame* __restrict__ tab, const int64_t* __restrict__ val,
+                                                  uint8_t* __restrict__ out_all) {
+  const ADFrame& h = tab[blockIdx.y];
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= h.n * h.c) return;
+  const int64_t mask = ((int64_t)1 << (8 * h.bpv)) - 1, x = val[h.out_off + k];
+  a_store(out_all + h.out_off + k * h.bpv, h.bpv, (uint32_t)(x < 0 ? 0 : (x > mask ? mask : x)));
+}
+
 }  // namespace
 
 static inline int64_t a_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 static inline size_t merged_b_of(int64_t vals) { return pcc_align((size_t)vals * 2); }
+
+// version 19, what encoder and decoder share: the order stage over the call's keys (src: the encoder's distinct sorted
+// keys, or the decoder's cells, whose keys go to keys_out), then the sublevels' starts and counts read back into h_bins
+// (pinned; 98 per frame) behind one synchronisation.  grid[t] = the blocks of k_at_lift at sublevel t: 0 where no frame
+// of the call has a point there
+static int a_t_order(hipStream_t st, bool from_cells, const void* src, uint64_t* keys_out, const A2Order* d_ord, int nf,
+                     int64_t blocks, uint16_t* packed, uint32_t* hist, uint32_t* bins, uint32_t* inv, uint32_t* h_bins,
+                     unsigned (&grid)[kATBins]) {
+  hipLaunchKernelGGL((from_cells ? k_at_size<true> : k_at_size<false>), dim3((unsigned)blocks), dim3(256), 0, st, src, d_ord, nf, keys_out,
+                     packed, hist);
+  PCC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_at_scan, dim3((unsigned)nf), dim3(64), 0, st, d_ord, hist, bins);
+  PCC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_at_place, dim3((unsigned)blocks), dim3(256), 0, st, d_ord, nf, (const uint16_t*)packed, (const uint32_t*)hist,
+                     (const uint32_t*)bins, inv);
+  PCC_CHECK_LAUNCH();
+  PCC_HIP(hipMemcpyAsync(h_bins, bins, (size_t)nf * 2 * kATBins * 4, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipStreamSynchronize(st));
+  for (int t = 0; t < kATBins; ++t) {
+    uint32_t most = 0;
+    for (int f = 0; f < nf; ++f) {
+      const uint32_t cnt = ((volatile uint32_t*)h_bins)[f * 2 * kATBins + kATBins + t];
+      most = std::max(most, cnt);
+    }
+    grid[t] = nblk(most, 256);
+  }
+  return PCC_OK;
+}
+
+// version 19, encoder, behind k_a_merge: the order stage, one k_at_lift<true> per occupied sublevel bottom-up over the
+// merged values in place, and the mean; idx then holds x in coding order where the PRED = false coder reads it
+static int a_t_forward(pcc_ctx* ctx, hipStream_t st, const uint64_t* d_keys, const A2Order* d_ord, const AFrame* d_tab, int nf,
+                       int64_t blocks, size_t pk_b, size_t hist_b, size_t bins_b, size_t link_b, uint16_t* merged,
+                       uint16_t* idx, uint32_t* h_bins) {
+  uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, pk_b);
+  uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, hist_b);
+  uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, bins_b);
+  uint32_t* inv = (uint32_t*)pcc_arena_alloc(ctx, link_b);
+  if (!packed || !hist || !bins || !inv) return PCC_E_NOMEM;
+  unsigned grid[kATBins];
+  PCC_TRY(a_t_order(st, false, (const void*)d_keys, nullptr, d_ord, nf, blocks, packed, hist, bins, inv, h_bins, grid));
+  for (int t = 0; t < kATBins - 1; ++t) {
+    if (!grid[t]) continue;
+    hipLaunchKernelGGL(k_at_lift<true>, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, d_keys, d_ord, (const uint32_t*)bins,
+                       (const uint32_t*)inv, t, d_tab, merged, idx, (const ADFrame*)nullptr, (const uint8_t*)nullptr, (int64_t*)nullptr,
+                       (int32_t*)nullptr);
+    PCC_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_at_mean, dim3(nblk(4 * (int64_t)nf, 256)), dim3(256), 0, st, d_tab, nf, (const uint16_t*)merged, idx);
+  PCC_CHECK_LAUNCH();
+  return PCC_OK;
+}
 
 // ======================================================================== C-ABI (include/pcc.h)
 // both versions' encoder: version 2 codes, instead of the merged values, their residuals in introduction order
@@ -959,9 +1234,13 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
                            const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
                            const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys,
                            int key_shift, uint8_t* h_out, int64_t cap, int64_t* h_offsets, int64_t n_kept = -1,
-                           int max_error = 0, const int32_t* h_cross = nullptr) {
-  const bool v2 = version == 2, nl = max_error > 0;
-  const int blob_version = nl ? (v2 ? 7 : 4) : version;
+                           int max_error = 0, const int32_t* h_cross = nullptr, int qstep = 0) {
+  // qstep > 0: version 19.  Its head is version 4's with q where e stands (and the slod nibble), so it runs as that
+  // kind does (nl, r.e = q) with the order stage and the lifting passes in place of k_a4_quant
+  const bool tr = qstep > 0;
+  if (tr) max_error = qstep;
+  const bool v2 = version == 2 && !tr, nl = max_error > 0, keyed = v2 || tr;
+  const int blob_version = tr ? kAttrTVersion : (nl ? (v2 ? 7 : 4) : version);
   PCC_REQUIRE(ctx && h_value_offsets && h_format && h_rows && h_points && h_out && h_offsets && n_frames >= 1 &&
                   n_frames <= 65535 && n_unique >= 0 && cap >= 0,
               PCC_E_ARG, "%s: bad argument (n_frames=%d)", who, n_frames);
@@ -973,7 +1252,7 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
   PCC_REQUIRE(h_rows[0] == 0 && h_rows[n_frames] < ((int64_t)1 << 27) && n_unique <= n_keys &&
                   (n_keys == 0 || (d_values && d_perm && d_run_starts)),
               PCC_E_ARG, "%s: %lld rows, %lld points", who, (long long)n_keys, (long long)n_unique);
-  PCC_REQUIRE(!v2 || (key_shift >= 0 && key_shift <= 45 && key_shift % 3 == 0 && (n_keys == 0 || d_keys)), PCC_E_ARG,
+  PCC_REQUIRE(!keyed || (key_shift >= 0 && key_shift <= 45 && key_shift % 3 == 0 && (n_keys == 0 || d_keys)), PCC_E_ARG,
               "%s: bad argument (key_shift=%d)", who, key_shift);
   std::vector<AFrame> tab;
   std::vector<A2Order> order;
@@ -992,7 +1271,8 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
                     h_value_offsets[f] >= 0, PCC_E_ARG,
                 "%s: frame %d: %lld rows, %lld points", who, f, (long long)rows, (long long)n);
     PCC_REQUIRE(!nl || (uint32_t)max_error <= attr_max_error(bpv), PCC_E_ARG,
-                "%s: frame %d: max_error %d with %d bytes per value (at most %u)", who, f, max_error, bpv, attr_max_error(bpv));
+                "%s: frame %d: %s %d with %d bytes per value (at most %u)", who, f, tr ? "qstep" : "max_error", max_error, bpv,
+                attr_max_error(bpv));
     const int32_t m = h_cross ? h_cross[f] : 0;
     PCC_REQUIRE(m >= 0 && m < (1 << (c - 1)), PCC_E_ARG, "%s: frame %d: cross-channel mask %d with %d channels", who, f, m, c);
     if (n == 0) continue;
@@ -1046,7 +1326,7 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
   std::vector<int64_t> off_of((size_t)n_frames, -1);
   hipStream_t st = ctx->stream;
   if (nf > 0) {
-    const size_t ord_b = v2 ? pcc_align((size_t)nf * sizeof(A2Order)) : 0;
+    const size_t ord_b = keyed ? pcc_align((size_t)nf * sizeof(A2Order)) : 0;
     // the rows | the masks (a call with cross-channel frames) | the order rows
     const size_t fr_b = pcc_align((size_t)nf * sizeof(AFrame)), cross_b = xc ? pcc_align((size_t)nf * 4) : 0;
     const size_t tab_b = fr_b + cross_b + ord_b;
@@ -1059,7 +1339,10 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     // version 4 too: it is what these calls have always reserved, and no call reserves less than it did
     const size_t order_b = v2 ? 2 * merged_b + pk_b + hist_b + bins_b : 0, nl_b = nl ? merged_b + 2 * link_b : 0;
     const size_t x8_b = xc && !v2 && !nl ? merged_b : 0;   // version 8: the run residuals
-    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + order_b + nl_b + x8_b + 8192));
+    // version 19's order stage: packed | hist (49 per block) | starts and counts (98 per frame); inv is one of nl_b's links
+    const size_t thist_b = pcc_align((size_t)merge_blocks * kATBins * 4), tbins_b = pcc_align((size_t)nf * 2 * kATBins * 4);
+    const size_t tr_b = tr ? pk_b + thist_b + tbins_b : 0;
+    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + order_b + nl_b + x8_b + tr_b + 8192));
     AFrame* d_tab = (AFrame*)pcc_arena_alloc(ctx, tab_b);
     uint16_t* merged = (uint16_t*)pcc_arena_alloc(ctx, merged_b);
     uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, cnt_b);
@@ -1078,15 +1361,16 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     const int32_t* d_cross = xc ? (const int32_t*)((const uint8_t*)d_tab + fr_b) : nullptr;
     // staging: the table on its way to the device | the blobs | their lengths
     const size_t lens_at = tab_b + (size_t)out_bytes;
-    PCC_TRY(o2_stage_reserve(ctx, lens_at + (size_t)nf * 8 + 64));
+    const size_t tcnt_at = lens_at + (size_t)nf * 8 + 64;   // version 19: the sublevels' starts and counts, read back
+    PCC_TRY(o2_stage_reserve(ctx, tcnt_at + (tr ? (size_t)nf * 2 * kATBins * 4 : 0) + 64));
     uint8_t* stage = (uint8_t*)ctx->stage;
     memcpy(stage, tab.data(), (size_t)nf * sizeof(AFrame));
     if (xc) memcpy(stage + fr_b, cross.data(), (size_t)nf * 4);
-    if (v2) memcpy(stage + tab_b - ord_b, order.data(), (size_t)nf * sizeof(A2Order));
+    if (keyed) memcpy(stage + tab_b - ord_b, order.data(), (size_t)nf * sizeof(A2Order));
     long long* len_dev = (long long*)(stage + lens_at);
     PccProfScope prof(ctx, "attr_encode", u, nf, chunks, 0);
     PCC_HIP(hipMemcpyAsync(d_tab, stage,
-                           v2 ? tab_b - ord_b + (size_t)nf * sizeof(A2Order) : (xc ? fr_b + (size_t)nf * 4 : (size_t)nf * sizeof(AFrame)),
+                           keyed ? tab_b - ord_b + (size_t)nf * sizeof(A2Order) : (xc ? fr_b + (size_t)nf * 4 : (size_t)nf * sizeof(AFrame)),
                            hipMemcpyHostToDevice, st));
     PCC_HIP(hipMemsetAsync(cnt, 0, (size_t)ctxs * 8, st));
     hipLaunchKernelGGL(k_a_merge, dim3((unsigned)merge_blocks), dim3(256), 0, st, (const uint8_t*)d_values, (const AFrame*)d_tab, nf,
@@ -1118,7 +1402,10 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
       return PCC_OK;
     };
     if (v2) PCC_TRY(a_order_stage(nl));
-    if (nl && !v2) {
+    if (tr) {
+      PCC_TRY(a_t_forward(ctx, st, d_keys, d_ord, (const AFrame*)d_tab, nf, merge_blocks, pk_b, thist_b, tbins_b, link_b, merged, src,
+                          (uint32_t*)(stage + tcnt_at)));
+    } else if (nl && !v2) {
       hipLaunchKernelGGL(k_a4_quant, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const uint16_t*)merged,
                          (const AFrame*)d_tab, src);
       PCC_CHECK_LAUNCH();
@@ -1135,15 +1422,16 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     }
     // counting pass, coder, blobs: only version 1 predicts inside the run (PRED), and not beside cross-channel frames
     const size_t lds = 4096 * 4 + (size_t)(nctx_max + 1) * kLanes * 2;   // <= 98 KB (c = 4, uint16)
-    auto a_code = [&](auto v2c, auto nlc, auto xcc) -> int {
-      constexpr bool V2 = decltype(v2c)::value, NL = decltype(nlc)::value, XC = decltype(xcc)::value, PRED = !V2 && !NL && !XC;
+    auto a_code = [&](auto v2c, auto nlc, auto xcc, auto trc) -> int {
+      constexpr bool V2 = decltype(v2c)::value, NL = decltype(nlc)::value, XC = decltype(xcc)::value, TR = decltype(trc)::value;
+      constexpr bool PRED = !V2 && !NL && !XC;
       hipLaunchKernelGGL(k_a_stats<PRED>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)src, (const AFrame*)d_tab, nf, cnt);
       PCC_CHECK_LAUNCH();
       PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<PRED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL(k_a_enc<PRED>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)src, (const AFrame*)d_tab, nf,
                          (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
       PCC_CHECK_LAUNCH();
-      hipLaunchKernelGGL((k_a_pack<V2, NL, XC>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work,
+      hipLaunchKernelGGL((k_a_pack<V2, NL, XC, TR>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work,
                          (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words,
                          (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3, d_cross);
       PCC_CHECK_LAUNCH();
@@ -1151,8 +1439,8 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     };
     using Yes = std::true_type;
     using No = std::false_type;
-    auto a_kind = [&](auto v2c, auto nlc) -> int { return xc ? a_code(v2c, nlc, Yes{}) : a_code(v2c, nlc, No{}); };
-    PCC_TRY(v2 ? (nl ? a_kind(Yes{}, Yes{}) : a_kind(Yes{}, No{})) : (nl ? a_kind(No{}, Yes{}) : a_kind(No{}, No{})));
+    auto a_kind = [&](auto v2c, auto nlc) -> int { return xc ? a_code(v2c, nlc, Yes{}, No{}) : a_code(v2c, nlc, No{}, No{}); };
+    PCC_TRY(tr ? a_code(No{}, Yes{}, No{}, Yes{}) : v2 ? (nl ? a_kind(Yes{}, Yes{}) : a_kind(Yes{}, No{})) : (nl ? a_kind(No{}, Yes{}) : a_kind(No{}, No{})));
     PCC_HIP(hipStreamSynchronize(st));
     for (int k = 0; k < nf; ++k) {
       const long long total = ((volatile long long*)len_dev)[k];
@@ -1176,7 +1464,7 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
       memset(dst, 0, kAttrHead);
       dst[0] = 'A';
       dst[1] = (uint8_t)(m ? attr_version(v2, nl, true) : blob_version);
-      dst[2] = (uint8_t)((h_format[f] & 0xFF) | (v2 ? (key_shift / 3) << 4 : 0));
+      dst[2] = (uint8_t)((h_format[f] & 0xFF) | (keyed ? (key_shift / 3) << 4 : 0));
       dst[3] = (uint8_t)((h_format[f] >> 8) | (m << 4));
     }
     h_offsets[f + 1] = h_offsets[f] + len_of[(size_t)f];
@@ -1236,6 +1524,17 @@ extern "C" int pcc_attr_encode_frames_cross(pcc_ctx* ctx, int version, const voi
                          h_out, cap, h_offsets, n_kept, max_error, h_cross);
 }
 
+extern "C" int pcc_attr_encode_frames_transform(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
+                                                const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
+                                                const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, int64_t n_kept,
+                                                const uint64_t* d_keys, int key_shift, int qstep, uint8_t* h_out, int64_t cap,
+                                                int64_t* h_offsets) {
+  PCC_REQUIRE(n_kept >= -1 && qstep >= 1, PCC_E_ARG, "pcc_attr_encode_frames_transform: bad argument (n_kept=%lld qstep=%d)",
+              (long long)n_kept, qstep);
+  return a_encode_frames("pcc_attr_encode_frames_transform", 2, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames,
+                         d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets, n_kept, 0, nullptr, qstep);
+}
+
 // host only: the version byte and byte 3 of a head, checked: its kind, channels and mask
 static int a_head_kind(const char* who, const uint8_t* h_in, int64_t len, bool* scal, bool* nl, bool* xc, int* c, int* m) {
   PCC_REQUIRE(h_in && len >= kAttrHead && h_in[0] == 'A', PCC_E_STREAM, "%s: not an attribute blob (len=%lld)", who, (long long)len);
@@ -1255,9 +1554,40 @@ extern "C" int pcc_attr_cross_mask(const uint8_t* h_in, int64_t len, int32_t* h_
   return PCC_OK;
 }
 
+// host only: q of a version-19 head, 0 for every other kind and for a blob without points
+extern "C" int pcc_attr_qstep(const uint8_t* h_in, int64_t len, int32_t* h_qstep) {
+  int32_t ver = 0;
+  PCC_TRY(pcc_attr_info(h_in, len, &ver, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+  int32_t q = 0;
+  if (attr_t_kind(ver)) {
+    AttrTInfo o;
+    PCC_TRY(attr_t_parse(h_in, len, &o, true));
+    q = (int32_t)o.qstep;
+  }
+  if (h_qstep) *h_qstep = q;
+  return PCC_OK;
+}
+
 // host only: what the head of an attribute blob of any kind says (h_in may be a prefix that holds the head)
 extern "C" int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_version, int32_t* h_bpv, int32_t* h_channels,
                              int64_t* h_points, int32_t* h_max_error, int32_t* h_scalable, int32_t* h_lod) {
+  if (h_in && len >= kAttrHead && h_in[0] == 'A' && attr_t_kind(h_in[1])) {   // version 19: its own parser; q through pcc_attr_qstep
+    AttrTInfo o;
+    const int rc = attr_t_parse(h_in, len, &o, true);
+    if (rc != PCC_OK) {
+      const std::string msg = pcc_last_error();
+      pcc_set_error("pcc_attr_info: %s", msg.c_str());
+      return rc;
+    }
+    if (h_version) *h_version = o.version;
+    if (h_bpv) *h_bpv = o.bpv;
+    if (h_channels) *h_channels = o.c;
+    if (h_points) *h_points = o.n;
+    if (h_max_error) *h_max_error = 0;
+    if (h_scalable) *h_scalable = 0;
+    if (h_lod) *h_lod = o.slod;
+    return PCC_OK;
+  }
   bool scal, nl, xc;
   int c, m;
   PCC_TRY(a_head_kind("pcc_attr_info", h_in, len, &scal, &nl, &xc, &c, &m));
@@ -1477,11 +1807,127 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
   return PCC_OK;
 }
 
+// ---- version 19: the decoder -----------------------------------------------------------------------------------------
+// Against the cells its geometry decode left in HBM, as version 2's at lod 0: the order stage over the cells' keys, the
+// lane decoder (x in coding order), the root, one k_at_lift<false> per occupied sublevel top-down, clamp and store.
+static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
+                             const int32_t* d_cells, const int64_t* h_cell_offsets, uint8_t* d_out, uint8_t* h_out, int64_t cap_bytes,
+                             int64_t* h_out_offsets, int32_t* h_format) {
+  std::vector<AttrTInfo> info((size_t)n_frames);
+  int64_t bytes = 0, bodies = 0, points = 0;
+  h_out_offsets[0] = 0;
+  for (int f = 0; f < n_frames; ++f) {
+    AttrTInfo& o = info[(size_t)f];
+    const int rc = attr_t_parse(h_blobs[f], h_lens[f], &o);
+    if (rc != PCC_OK) return a_wrap_error(who, f, rc);
+    if (h_cell_offsets) {
+      const int64_t m = h_cell_offsets[f + 1] - h_cell_offsets[f];
+      PCC_REQUIRE(m == o.n, PCC_E_STREAM, "%s: frame %d: the attribute blob has %lld values, its geometry %lld points", who, f,
+                  (long long)o.n, (long long)m);
+    }
+    if (h_format) h_format[f] = o.bpv | (o.c << 8);
+    bytes = a_round(bytes + o.n * o.c * o.bpv, 16);
+    points += o.n;
+    h_out_offsets[f + 1] = bytes;
+    if (o.n) bodies += a_round(h_lens[f] - o.off_p0, 16);
+  }
+  PCC_REQUIRE(points < ((int64_t)1 << 31), PCC_E_ARG, "%s: the blobs announce %lld values in all", who, (long long)points);
+  if (bytes == 0 || (!d_out && !h_out)) return PCC_OK;
+  PCC_REQUIRE(d_cells && h_cell_offsets && h_cell_offsets[0] >= 0, PCC_E_ARG, "%s: the cells of the frames are needed", who);
+  PCC_REQUIRE(cap_bytes >= bytes, PCC_E_NOMEM, "%s: %lld bytes, capacity %lld", who, (long long)bytes, (long long)cap_bytes);
+  std::vector<ADFrame> tab;
+  std::vector<A2Order> order;
+  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, blocks = 0, vals_max = 0;
+  const int64_t cell0 = h_cell_offsets[0];
+  for (int f = 0; f < n_frames; ++f) {
+    const AttrTInfo& o = info[(size_t)f];
+    if (o.n == 0) continue;
+    const uint8_t* table = h_blobs[f] + o.off_table;
+    ADFrame r = a_dec_row(o, body_off, h_out_offsets[f], chunks, o.nc, o.n, attr_u32(table + 4 * (o.nc - 1)));
+    r.max_error = (int32_t)o.qstep;   // q where the near-lossless kinds keep e
+    tab.push_back(r);
+    order.push_back(A2Order{h_cell_offsets[f] - cell0, o.n, (int32_t)blocks, o.slod});
+    vals_max = std::max(vals_max, o.n * o.c);
+    for (int64_t k = 0; k < o.nc; ++k) cw_max = std::max<int64_t>(cw_max, attr_u32(table + 4 * k));
+    body_off += a_round(h_lens[f] - o.off_p0, 16);
+    chunks += o.nc;
+    blocks += nblk(o.n, 256);
+    nctx_max = std::max<int64_t>(nctx_max, o.nctx);
+  }
+  const int64_t cells_all = h_cell_offsets[n_frames] - cell0;
+  const int32_t* cells = d_cells + 3 * cell0;
+  const int nf = (int)tab.size();
+  hipStream_t st = ctx->stream;
+  const size_t ftab_b = pcc_align((size_t)nf * sizeof(ADFrame)), ord_b = pcc_align((size_t)nf * sizeof(A2Order));
+  const size_t tab_b = ftab_b + ord_b;
+  const size_t keys_b = pcc_align((size_t)cells_all * 8), u32_b = pcc_align((size_t)cells_all * 4), pk_b = pcc_align((size_t)cells_all * 2);
+  const size_t hist_b = pcc_align((size_t)blocks * kATBins * 4), bins_b = pcc_align((size_t)nf * 2 * kATBins * 4);
+  const size_t val_b = pcc_align((size_t)bytes * 8), status_b = pcc_align((size_t)nf * 4 + 64);
+  PCC_TRY(pcc_arena_reserve(ctx, tab_b + pcc_align((size_t)bodies + 16) + (d_out ? 1 : 2) * pcc_align((size_t)bytes) + val_b + keys_b + u32_b +
+                                     pk_b + hist_b + bins_b + status_b + 8192));
+  uint8_t* d_in = (uint8_t*)pcc_arena_alloc(ctx, tab_b + (size_t)bodies + 16);
+  uint8_t* out = d_out ? d_out : (uint8_t*)pcc_arena_alloc(ctx, (size_t)bytes);
+  uint8_t* x = (uint8_t*)pcc_arena_alloc(ctx, (size_t)bytes);
+  int64_t* val = (int64_t*)pcc_arena_alloc(ctx, val_b);
+  uint64_t* keys = (uint64_t*)pcc_arena_alloc(ctx, keys_b);
+  uint32_t* inv = (uint32_t*)pcc_arena_alloc(ctx, u32_b);
+  uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, pk_b);
+  uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, hist_b);
+  uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, bins_b);
+  int32_t* status = (int32_t*)pcc_arena_alloc(ctx, status_b);
+  if (!d_in || !out || !x || !val || !keys || !inv || !packed || !hist || !bins || !status) return PCC_E_NOMEM;
+  PccProfScope prof(ctx, "attr_decode_transform", points, nf, chunks, 0);
+  const size_t in_b = tab_b + (size_t)bodies;
+  uint8_t *down, *back;
+  PCC_TRY(a_dec_stage(ctx, h_out, in_b, bytes, (size_t)nf * (2 * kATBins + 1) * 4, &down, &back));
+  uint8_t* stage = (uint8_t*)ctx->stage;
+  memcpy(stage, tab.data(), (size_t)nf * sizeof(ADFrame));
+  memcpy(stage + ftab_b, order.data(), (size_t)nf * sizeof(A2Order));
+  for (int f = 0, k = 0; f < n_frames; ++f) {
+    const AttrTInfo& o = info[(size_t)f];
+    if (o.n == 0) continue;
+    memcpy(stage + tab_b + tab[(size_t)k++].body_off, h_blobs[f] + o.off_p0, (size_t)(h_lens[f] - o.off_p0));
+  }
+  PCC_HIP(hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
+  PCC_HIP(hipMemsetAsync(status, 0, (size_t)nf * 4, st));
+  const ADFrame* d_tab = (const ADFrame*)d_in;
+  const A2Order* d_ord = (const A2Order*)(d_in + ftab_b);
+  PCC_TRY(a_launch_dec<true>(st, chunks, d_in, tab_b, nf, nctx_max, cw_max, x, status));
+  unsigned grid[kATBins];
+  PCC_TRY(a_t_order(st, true, (const void*)cells, keys, d_ord, nf, blocks, packed, hist, bins, inv, (uint32_t*)back, grid));
+  hipLaunchKernelGGL(k_at_root, dim3(nblk(4 * (int64_t)nf, 256)), dim3(256), 0, st, d_tab, nf, (const uint8_t*)x, val);
+  PCC_CHECK_LAUNCH();
+  for (int t = kATBins - 2; t >= 0; --t) {
+    if (!grid[t]) continue;
+    hipLaunchKernelGGL(k_at_lift<false>, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, (const uint64_t*)keys, d_ord, (const uint32_t*)bins,
+                       (const uint32_t*)inv, t, (const AFrame*)nullptr, (uint16_t*)nullptr, (uint16_t*)nullptr, d_tab, (const uint8_t*)x, val,
+                       status);
+    PCC_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_at_store, dim3(nblk(vals_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, (const int64_t*)val, out);
+  PCC_CHECK_LAUNCH();
+  int32_t* h_status = (int32_t*)back + (size_t)nf * 2 * kATBins;
+  if (down) PCC_HIP(hipMemcpyAsync(down, out, (size_t)bytes, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipMemcpyAsync(h_status, status, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipStreamSynchronize(st));
+  for (int f = 0, k = 0; f < n_frames; ++f) {
+    if (info[(size_t)f].n == 0) continue;
+    const int32_t bad = h_status[k++];
+    PCC_REQUIRE(bad == 0, PCC_E_STREAM, "%s: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state, 8 = keys)", who, f,
+                bad);
+  }
+  a_copy_out(h_out, down, bytes);
+  return PCC_OK;
+}
+
 // ---- version 2: levels of detail ----------------------------------------------------------------------------------
 extern "C" int pcc_attr_lod_info(const uint8_t* h_in, int64_t len, int lod, int64_t* h_bytes, int64_t* h_values) {
   PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "pcc_attr_lod_info: level of detail %d outside 0 .. %d", lod, kAttrMaxLod);
   PCC_REQUIRE(h_in && len >= 2 && h_in[0] == 'A', PCC_E_STREAM, "pcc_attr_lod_info: not an attribute blob (len=%lld)", (long long)len);
   bool scal = false, nl = false, xc = false;
+  PCC_REQUIRE(!attr_t_kind(h_in[1]), PCC_E_ARG,
+              "pcc_attr_lod_info: attribute blob version 19 (a transform-coded blob has no level-of-detail prefixes: the weights of its "
+              "transform need every point)");
   PCC_REQUIRE(attr_kind(h_in[1], &scal, &nl, &xc) && scal, PCC_E_ARG,
               "pcc_attr_lod_info: attribute blob version %d (levels of detail are a property of version 2)", (int)h_in[1]);
   Attr2Info o;
@@ -1504,6 +1950,16 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   PCC_REQUIRE(ctx && h_blobs && h_lens && h_out_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
               "%s: bad argument (n_frames=%d)", who, n_frames);
   PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "%s: level of detail %d outside 0 .. %d", who, lod, kAttrMaxLod);
+  // version 19 (one version per call, the first blob's): its own decoder, at lod 0
+  bool any_t = false;
+  for (int f = 0; f < n_frames; ++f) any_t |= a_is_version(h_blobs[f], h_lens[f], kAttrTVersion);
+  if (any_t) {
+    for (int f = 0; f < n_frames; ++f)
+      PCC_REQUIRE(a_is_version(h_blobs[f], h_lens[f], kAttrTVersion), PCC_E_ARG,
+                  "%s: frame %d: attribute blobs of version 19 and of another version in one call (one version per call)", who, f);
+    PCC_REQUIRE(lod == 0, PCC_E_ARG, "%s: attribute blob version 19 at level of detail %d (it decodes at 0 only)", who, lod);
+    return a_t_decode_frames(who, ctx, h_blobs, h_lens, n_frames, d_cells, h_cell_offsets, d_out, h_out, cap_bytes, h_out_offsets, h_format);
+  }
   // the blobs of a call are of one version, the first blob's: 2, or 7 (k_a2_walk<true> scales and clamps), or their
   // cross-channel forms 11 and 14 (k_ax_inv between the decoder and the walk)
   const int kinds[4] = {2, 7, 11, 14};

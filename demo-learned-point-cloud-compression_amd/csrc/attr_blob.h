@@ -1,6 +1,6 @@
 // attr_blob.h — the header of an attribute blob (attr.hip), parsed and checked on the host before anything is reserved
-// or launched.  Plain C++ (no HIP): tests/fuzz/fuzz_attr_header.cpp, fuzz_attr2_header.cpp, fuzz_attr_nl_header.cpp
-// and fuzz_attr_cross_header.cpp put it under the sanitizers.
+// or launched.  Plain C++ (no HIP): tests/fuzz/fuzz_attr_header.cpp, fuzz_attr2_header.cpp, fuzz_attr_nl_header.cpp,
+// fuzz_attr_cross_header.cpp and fuzz_attr_transform_header.cpp put it under the sanitizers.
 //
 // Every size the decoder reserves or reads follows from what this parse accepted: the chunk table must add up to the
 // blob's own length, so a header cannot announce more words than the blob holds; n is bounded by the chunks
@@ -362,4 +362,106 @@ static inline int attr2_parse_kind(const uint8_t* b, int64_t len, int lod, bool 
 
 static inline int attr2_parse(const uint8_t* b, int64_t len, int lod, bool need_all, Attr2Info* o, Attr2Plan* pl) {
   return attr2_parse_kind(b, len, lod, need_all, false, o, pl);
+}
+
+// ---- version 19: transform-coded attributes ------------------------------------------------------------------------
+// A ninth kind, lossy, for rates below about a byte per point (compress(..., qstep=q)): an integer lifting form of the
+// region-adaptive hierarchical transform over the binary splits of the Morton tree.  Version 4's layout with version 2's
+// slod nibble:
+//
+//   'A' 19 (bpv | slod << 4) c | u32 n | u32 payload_len | u32 qstep | u32 S | u32 n_chunks | u16 p0[nctx] |
+//   u32 words[n_chunks] | chunk payloads                  (n == 0: the 12 bytes up to payload_len = 0; they record no q)
+//
+// Byte 19 keeps the odd parity of the eight bytes above, so it differs from each of them in two bits; it is not one of
+// attr_kind's and has its own predicate (attr_t_kind) and parser (attr_t_parse).
+// The frame's n distinct points in Morton order, their 48-bit keys key_i (biased by 32768 >> slod) and merged values v_i
+// per channel; H = 2^(8 bpv - 1), mask = 2 H - 1, q = qstep in 1 .. H - 1:
+//   sublevel of introduction   b(0) = 48; b(i) = hb(key_i xor key_{i-1}) in 0 .. 47: point i is the first leaf of the
+//                              RIGHT child of exactly one binary split of the Morton tree, the one at bit b(i) (version
+//                              2's size of introduction at bit granularity, s = floor(b / 3))
+//   the pair of point i, b(i) = t:  lo = lower_bound(keys, key_i with its low t + 1 bits cleared), hi = lower_bound(keys,
+//                              (key_i | (2^t - 1)) + 1) within the frame; wa = i - lo, wb = hi - i, w = wa + wb: the
+//                              leaves of the left child, of the right child, of the node
+//   step                       s = max(2, isqrt(floor(q^2 w / (wa wb))))        (the product stays below 2^63)
+// Forward, val = v as signed integers never clamped inside, sublevels t = 0, 1, .., 47 in that order, the pairs of a
+// sublevel independent of each other (no two touch the same slot):
+//   h = val[i] - val[lo];  val[lo] += floor(wb h / w) (towards -inf: the node's value, kept at its first leaf)
+//   x[i] = sgn(h) min(floor((|h| + floor(s / 2)) / s), H - 1)     (s >= 2 and |h| <= mask: the min moves an index by at
+//                                                                  most 1)
+// and after sublevel 47  x[0] = val[0] - H, the frame's integer weighted mean, in [-H, H), not quantised.
+// Inverse, val[0] = x[0] + H, sublevels t = 47 .. 0 with the same lo, hi, wa, wb, s:
+//   h^ = x[i] s;  va = val[lo] - floor(wb h^ / w);  val[lo] = va;  val[i] = va + h^;      output clamp(val, 0, mask)
+// A step of 1 would let the min clamp indices (it cost the first form of this kind 10 dB), hence the floor of 2: the
+// kind has no lossless setting.
+// Coding order: (b descending, Morton index ascending), point 0 first.  x in that order is dealt to lanes and chunks
+// (attr_layout) and coded exactly as version 2 codes its residuals — binarisation, contexts (channel, bucket of |x| of
+// the channel's previous point in the lane's run, position; the buckets are not retuned), p0 and model, no prediction
+// inside the run.  The decoder needs the frame's keys, so the kind decodes against the cells of its geometry at lod 0 and
+// has no level-of-detail prefixes: a decoder at a cut does not know how many points lie under a cell and cannot form the
+// weights.  tests/attr_transform_ref.py restates the kind in numpy.
+constexpr int kAttrTVersion = 19;
+constexpr int kAttrTHead = kAttrHead + 12;   // .. | u32 qstep | u32 S | u32 n_chunks
+
+struct AttrTInfo : AttrInfo {
+  int slod;          // the sender's level of detail
+  uint32_t qstep;    // q (0: a blob without points)
+};
+
+static inline bool attr_t_kind(int version) { return version == kAttrTVersion; }
+
+// b[0 .. len): the whole blob, and nothing behind it; or (prefix: pcc_attr_info) the blob or a prefix of it that reaches q
+// (16 bytes), of which every part of the header that is there is checked as the whole blob's is — S and n_chunks against
+// n and the blob's announced length, p0, the chunk table against that length.  Nothing beyond b[len) is read.
+static inline int attr_t_parse(const uint8_t* b, int64_t len, AttrTInfo* o, bool prefix = false) {
+  ATTR2_REQUIRE(b && len >= kAttrHead && b[0] == 'A' && attr_t_kind(b[1]), "attribute blob v19: bad header (len=%lld)", (long long)len);
+  o->version = kAttrTVersion;
+  o->max_error = 0;
+  o->cross = 0;
+  o->qstep = 0;
+  o->bpv = b[2] & 15;
+  o->slod = b[2] >> 4;
+  o->c = b[3];
+  ATTR2_REQUIRE((o->bpv == 1 || o->bpv == 2) && o->c >= 1 && o->c <= 4 && o->slod <= kAttrMaxLod,
+                "attribute blob v19: %d bytes per value, %d channels", o->bpv, o->c);
+  o->nctx = attr_contexts(o->bpv, o->c);
+  o->n = (int64_t)attr_u32(b + 4);
+  const int64_t payload = (int64_t)attr_u32(b + 8), total = kAttrHead + payload;
+  ATTR2_REQUIRE(prefix ? len <= total : len == total, "attribute blob v19: payload of %lld bytes in a blob of %lld", (long long)payload,
+                (long long)len);
+  o->S = o->nc = 0;
+  o->off_p0 = o->off_table = o->off_payload = kAttrHead;
+  o->payload_words = 0;
+  if (o->n == 0) {
+    ATTR2_REQUIRE(payload == 0, "attribute blob v19: no points, %lld bytes of payload", (long long)payload);
+    return PCC_OK;
+  }
+  o->off_p0 = kAttrTHead;
+  o->off_table = o->off_p0 + 2 * (int64_t)o->nctx;
+  ATTR2_REQUIRE(o->n < ((int64_t)1 << 27) && payload >= o->off_table - kAttrHead + 4 + 2 * 3 * kAttrLanes,
+                "attribute blob v19: %lld points, payload %lld", (long long)o->n, (long long)payload);
+  ATTR2_REQUIRE(len >= kAttrHead + 4, "attribute blob v19: truncated in front of qstep (len=%lld)", (long long)len);
+  o->qstep = attr_u32(b + kAttrHead);
+  ATTR2_REQUIRE(o->qstep >= 1 && o->qstep <= attr_max_error(o->bpv), "attribute blob v19: qstep %u with %d bytes per value", o->qstep,
+                o->bpv);
+  if (len < kAttrTHead && prefix) return PCC_OK;
+  ATTR2_REQUIRE(len >= kAttrTHead, "attribute blob v19: truncated header");
+  o->S = (int64_t)attr_u32(b + kAttrHead + 4);
+  o->nc = (int64_t)attr_u32(b + kAttrHead + 8);
+  ATTR2_REQUIRE(o->S >= 1 && o->S * o->c <= kAttrMaxValues && o->nc >= 1 && o->nc <= o->n && kAttrLanes * o->S * o->nc >= o->n &&
+                    kAttrLanes * o->S * (o->nc - 1) < o->n,
+                "attribute blob v19: %lld points in %lld chunks of 64 x %lld", (long long)o->n, (long long)o->nc, (long long)o->S);
+  ATTR2_REQUIRE(total - o->off_table >= 4 * o->nc, "attribute blob v19: truncated chunk table");
+  if (len < o->off_table && prefix) return PCC_OK;
+  ATTR2_REQUIRE(len >= o->off_table, "attribute blob v19: truncated header");
+  uint32_t bad_p = 0;
+  ATTR2_REQUIRE(attr_check_p0(b, o->off_p0, o->nctx, &bad_p), "attribute blob v19: initial probability %u", bad_p);
+  if (len - o->off_table < 4 * o->nc && prefix) return PCC_OK;
+  int64_t words = 0, bad_k = 0, bad_cw = 0;
+  ATTR2_REQUIRE(attr_sum_chunks(b + o->off_table, o->nc, o->bpv, &words, &bad_k, &bad_cw), "attribute blob v19: chunk %lld has %lld words",
+                (long long)bad_k, (long long)bad_cw);
+  o->off_payload = o->off_table + 4 * o->nc;
+  o->payload_words = words;
+  ATTR2_REQUIRE(o->off_payload + 2 * words == total, "attribute blob v19: chunks take %lld bytes, blob has %lld", (long long)(2 * words),
+                (long long)(total - o->off_payload));
+  return PCC_OK;
 }

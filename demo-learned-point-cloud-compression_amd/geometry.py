@@ -85,7 +85,7 @@ import numpy as np
 import torch
 
 from ._abi import check, PccError, PCC_E_RANGE
-from .runtime import Runtime, _ptr, ATTR_RUN_KINDS
+from .runtime import Runtime, _ptr, ATTR_RUN_KINDS, ATTR_TRANSFORM_KIND
 
 MAX_FRAMES = 65535      # the batch-index range of pcc_morton_keys
 MAX_LOD = 15            # levels of detail 0 .. 15 (csrc/octree2_blob.h)
@@ -220,10 +220,11 @@ class GeometryCodec:
 
     @staticmethod
     def attr_info(attr_blob):
-        """what the head of an attribute blob of any kind says, as a dict: version (1, 2, 4, 7, or their cross-channel
-        forms 8, 11, 13, 14), bpv (bytes per value), channels, points, max_error (0: lossless; a blob without points
-        records none), scalable, lod (the sender's); a cross-channel kind adds cross_channel, the tuple of channel
-        indices coded against the channel before them (a plain kind's dict has no such key).
+        """what the head of an attribute blob of any kind says, as a dict: version (1, 2, 4, 7, their cross-channel
+        forms 8, 11, 13, 14, or the transform-coded 19), bpv (bytes per value), channels, points, max_error (0: lossless,
+        and version 19; a blob without points records none), scalable, lod (the sender's); a cross-channel kind adds
+        cross_channel, the tuple of channel indices coded against the channel before them (a plain kind's dict has no
+        such key), version 19 adds qstep (0 in a blob without points).
         Host only; `attr_blob` may be a prefix of 16 bytes or more."""
         return Runtime.attr_info(bytes(attr_blob))
 
@@ -241,6 +242,31 @@ class GeometryCodec:
                 raise ValueError(f"frame {f}: max_error {max_error} is too large for {a.dtype} attributes, at most "
                                  f"{(1 << (8 * a.dtype.itemsize - 1)) - 1}")
         return max_error
+
+    @staticmethod
+    def _check_qstep(qstep, attrs, max_error, scalable, cross):
+        if isinstance(qstep, bool) or not isinstance(qstep, (int, np.integer)):
+            raise TypeError(f"qstep must be an integer >= 0, got {qstep!r}")
+        qstep = int(qstep)
+        if qstep < 0:
+            raise ValueError(f"qstep must be an integer >= 0, got {qstep}")
+        if qstep == 0:
+            return 0
+        if attrs is None:
+            raise ValueError("qstep is the quantiser step of transform-coded attributes: it needs attributes=")
+        if max_error:
+            raise ValueError("qstep with max_error: a transform-coded blob (version 19) bounds no single value's error; choose "
+                             "one of the two")
+        if scalable:
+            raise ValueError("qstep with scalable=True: a transform-coded blob (version 19) has no level-of-detail prefixes, "
+                             "the weights of its transform need every point")
+        if cross is not None:
+            raise ValueError("qstep with cross_channel: attribute blob version 19 has no cross-channel form")
+        for f, a in enumerate(attrs):
+            if qstep >= 1 << (8 * a.dtype.itemsize - 1):
+                raise ValueError(f"frame {f}: qstep {qstep} is too large for {a.dtype} attributes, at most "
+                                 f"{(1 << (8 * a.dtype.itemsize - 1)) - 1}")
+        return qstep
 
     @staticmethod
     def _check_cross(cross_channel, attrs):
@@ -270,7 +296,7 @@ class GeometryCodec:
         return masks
 
     def compress(self, frames, attributes=None, lod=0, scalable=False, *, voxel=None, origin=(0.0, 0.0, 0.0),
-                 invalid="raise", return_index=False, max_error=0, cross_channel=False):
+                 invalid="raise", return_index=False, max_error=0, cross_channel=False, qstep=0):
         """frames: a sequence of int16 / int32 [n_f, 3] arrays -> a list of bytes, one version-2 blob per frame.
         Duplicate points are removed (as np.unique), out-of-range coordinates raise PccError (PCC_E_RANGE).
         lod = k > 0: the sender's side of a level of detail — blob f is the version-2 blob of the distinct cells
@@ -293,6 +319,15 @@ class GeometryCodec:
         ValueError naming f.  Anything else: TypeError; without attributes: ValueError.  The decoded values are exactly
         those of the same call without it, at every level of detail and under max_error; the geometry blobs are the same.
         For correlated channels (a camera's colour: about a fifth smaller); uncorrelated ones grow, the sender chooses.
+        qstep = q > 0 (an integer; bool or non-integer: TypeError; negative, without attributes, or 2^(8 bytes per value -
+        1) and more for a frame's dtype: ValueError naming the frame; with max_error, scalable=True or cross_channel:
+        ValueError saying why): transform-coded attribute blobs, version 19 (include/pcc.h has the rule) — lossy, for
+        rates below about a byte per point, where max_error's staircase is the wrong tool: on recorded camera colour
+        q = 32 gives fewer bytes than max_error=16 at two thirds of its mean squared error.  No single value's error is
+        bounded, and the step never falls below 2, so the kind has no lossless setting (q = 1 is its finest).  It
+        combines with lod=k (the cells' means over the cells' keys), float32 / device frames, invalid="drop" and
+        return_index; decompress reads it at lod 0 only.  The geometry blobs are the same; 0, the default, is the bytes
+        of before (attr_info reads q back from a blob).
 
         Frame types: numpy int16 / int32 as above, numpy float32, or torch tensors of those three dtypes on the host or
         on this codec's device; all frames of a call integer or all float32, all on the host or all on the device
@@ -324,6 +359,7 @@ class GeometryCodec:
         attrs = None if attributes is None else self._check_attributes(frames, attributes)
         max_error = self._check_max_error(max_error, attrs)
         cross = self._check_cross(cross_channel, attrs)
+        qstep = self._check_qstep(qstep, attrs, max_error, scalable, cross)
         nb = len(frames)
 
         def result(blobs, attr_blobs=None, index=None):
@@ -338,11 +374,11 @@ class GeometryCodec:
             front = self._front(rt, frames, is_float, on_device, caller, "GeometryCodec.compress", lod, voxel, origin,
                                 invalid == "drop")
             if front.n_keep == 0:
-                return result(*self._nothing_coded(rt, front, attrs, version, max_error, return_index, on_device, cross))
+                return result(*self._nothing_coded(rt, front, attrs, version, max_error, return_index, on_device, cross, qstep))
             blobs = rt.octree_encode_frames(front.keys, nb, 3 * lod)
             attr_blobs = index = None
             if attrs is not None:
-                attr_blobs = self._encode_attributes(rt, attrs, blobs, front, version, 3 * lod, max_error, cross)
+                attr_blobs = self._encode_attributes(rt, attrs, blobs, front, version, 3 * lod, max_error, cross, qstep)
             if return_index:
                 first_run = torch.empty(nb, dtype=torch.int64, pin_memory=True)
                 np.cumsum([0] + [struct.unpack_from("<I", b, 4)[0] for b in blobs[:-1]], out=first_run.numpy())
@@ -427,11 +463,11 @@ class GeometryCodec:
         distinct = keys if n_u.value == n_keep else rt.gather_rows(keys, rows[:n_u.value])
         return front._replace(perm=perm, sorted_keys=keys, rows=rows, n_unique=n_u.value, keys=distinct)
 
-    def _nothing_coded(self, rt, front, attrs, version, max_error, return_index, on_device, cross=None):
+    def _nothing_coded(self, rt, front, attrs, version, max_error, return_index, on_device, cross=None, qstep=0):
         """(blobs, attribute blobs, index) of a call none of whose rows is coded: the empty blobs, the attribute blobs
         of frames without points, and -1 for every input row"""
         blobs = rt.octree_encode_frames(rt.empty((0,), torch.int64), front.nb)
-        attr_blobs = None if attrs is None else self._encode_attributes(rt, attrs, blobs, front, version, 0, max_error, cross)
+        attr_blobs = None if attrs is None else self._encode_attributes(rt, attrs, blobs, front, version, 0, max_error, cross, qstep)
         if not return_index:
             return blobs, attr_blobs, None
         index = torch.full((front.n,), -1, dtype=torch.int32, device=rt.device)
@@ -447,7 +483,7 @@ class GeometryCodec:
         return _split(index, sizes)
 
     @staticmethod
-    def _encode_attributes(rt, attrs, blobs, front, version, key_shift, max_error, cross=None):
+    def _encode_attributes(rt, attrs, blobs, front, version, key_shift, max_error, cross=None, qstep=0):
         # the values as they come, frame by frame at 16-byte offsets, in one upload; the merge into Morton order
         # happens on the device from the sort's permutation and the runs of equal keys
         offs, at = [], 0
@@ -463,7 +499,7 @@ class GeometryCodec:
         points = [struct.unpack_from("<I", b, 4)[0] for b in blobs]
         n_kept = front.n_keep if front.n_keep < front.n else None      # None: no row was dropped
         return rt.attr_encode_frames(values, offs, formats, _ends(front.sizes), points, front.perm, front.rows, front.n_unique,
-                                     version, front.keys, key_shift, n_kept, max_error, cross)
+                                     version, front.keys, key_shift, n_kept, max_error, cross, qstep)
 
     def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0, *, voxel=None, origin=(0.0, 0.0, 0.0)):
         """version-2 blobs -> a list of int32 [n_f, 3] point sets in Morton order: numpy arrays (output="numpy") or
@@ -475,9 +511,10 @@ class GeometryCodec:
         version 2 (compress(..., scalable=True)), or prefixes of them (attr_lod_info): attributes[f] is [cells, c], row j
         the value of the Morton-first point of cell j.  The kind of every attribute blob (lossless 1 / 2, near-lossless
         4 / 7 of compress(..., max_error=e), their cross-channel forms 8 / 11 / 13 / 14 of compress(...,
-        cross_channel=...)) is read from the blob; version 7 behaves as version 2 and its prefixes do, every value within
-        e, and a cross-channel kind returns what its plain kind returns.  The eight kinds may be mixed at lod 0; an
-        attribute blob of version 1, 4, 8 or 13 at lod > 0 raises ValueError.
+        cross_channel=...), transform-coded 19 of compress(..., qstep=q)) is read from the blob; version 7 behaves as
+        version 2 and its prefixes do, every value within e, and a cross-channel kind returns what its plain kind
+        returns.  The nine kinds may be mixed at lod 0; an attribute blob of version 1, 4, 8, 13 or 19 at lod > 0 raises
+        ValueError naming the frame.
         voxel (with origin): the point sets come back as float32 [n_f, 3] in the caller's unit instead of int32,
         x = origin + t * voxel, one float32 multiplication and then one addition on the device (include/pcc.h has the
         rule): t the lattice index at lod 0 and, at lod k, the centre of the cell's lattice points
@@ -499,6 +536,12 @@ class GeometryCodec:
                 raise ValueError(f"{len(attr_blobs)} attribute blobs for {len(blobs)} geometry blobs")
             kind = [b[1] if len(b) > 1 else 0 for b in attr_blobs]      # runs of one kind are decoded in one call
             v1 = [k in ATTR_RUN_KINDS for k in kind]
+            if lod and ATTR_TRANSFORM_KIND in kind:
+                f = kind.index(ATTR_TRANSFORM_KIND)
+                raise ValueError(f"frame {f}: attributes of blob version {ATTR_TRANSFORM_KIND} cannot be decoded at lod > 0: the weights of "
+                                 "its transform are the point counts under every node, which a decoder at a cut does not "
+                                 "have; store version 2, 7, 11 or 14 (compress(..., scalable=True)) or ship coarse "
+                                 "attributes with compress(frames, attributes=..., lod=k, qstep=q)")
             if lod and any(v1):
                 raise ValueError(f"frame {v1.index(True)}: attributes of blob version {kind[v1.index(True)]} cannot be decoded at lod > 0: it "
                                  "is one predictive stream in full-resolution Morton order, so neither its bytes nor "

@@ -708,7 +708,7 @@ class Runtime:
         return (views, pts) if whole else views
 
     def attr_encode_frames(self, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique,
-                           version=1, keys=None, key_shift=0, n_kept=None, max_error=0, cross=None):
+                           version=1, keys=None, key_shift=0, n_kept=None, max_error=0, cross=None, qstep=0):
         """attribute blobs (csrc/attr.hip) of len(formats) frames at once (pcc_attr_encode_frames): `values` a
         device uint8 tensor with frame f's [rows_f, c_f] values at byte value_offsets[f], formats[f] = bytes per value |
         c_f << 8, row_offsets (n_frames + 1) the frames' rows among the call's keys, perm / run_starts what
@@ -720,10 +720,14 @@ class Runtime:
         kind of that version, blob version 4 (for 1) or 7 (for 2), no decoded value off by more than e.  cross
         (pcc_attr_encode_frames_cross): one cross-channel mask per frame, bit ch - 1 set where channel ch is coded
         against channel ch - 1 (include/pcc.h has the rule) -> blob versions 8, 11, 13, 14 for 1, 2, 4, 7; a frame whose
-        mask is 0 gets its plain kind, and so does every frame with cross=None or all masks 0."""
+        mask is 0 gets its plain kind, and so does every frame with cross=None or all masks 0.  qstep = q > 0
+        (pcc_attr_encode_frames_transform): the transform-coded kind, blob version 19, with `keys` and key_shift as
+        version 2 takes them; `version` is not read, and max_error or a cross-channel mask beside it raise ValueError."""
         if version not in (1, 2):
             raise ValueError(f"attribute blob version {version!r}: 1 or 2")
-        max_error = int(max_error)
+        max_error, qstep = int(max_error), int(qstep)
+        if qstep and (max_error or (cross is not None and any(cross))):
+            raise ValueError("qstep (attribute blob version 19) has no near-lossless and no cross-channel form")
         nf = len(formats)
         cap = 0
         for fmt, n in zip(formats, points):
@@ -735,7 +739,10 @@ class Runtime:
                 (C.c_int64 * (nf + 1))(*row_offsets), (C.c_int64 * nf)(*points), nf, _ptr(perm), _ptr(run_starts), n_unique)
         if cross is not None and len(cross) != nf:
             raise ValueError(f"{len(cross)} cross-channel masks for {nf} frames")
-        if cross is not None and any(cross):
+        if qstep:
+            check(self.lib.pcc_attr_encode_frames_transform(*head, -1 if n_kept is None else int(n_kept), _ptr(keys), int(key_shift),
+                                                            qstep, _np_ptr(out), cap, offs), "pcc_attr_encode_frames_transform")
+        elif cross is not None and any(cross):
             check(self.lib.pcc_attr_encode_frames_cross(head[0], version, *head[1:], -1 if n_kept is None else int(n_kept),
                                                         _ptr(keys) if version == 2 else None, int(key_shift), max_error,
                                                         (C.c_int32 * nf)(*[int(m) for m in cross]), _np_ptr(out), cap, offs),
@@ -769,9 +776,10 @@ class Runtime:
     @staticmethod
     def attr_info(blob):
         """what the head of an attribute blob of any kind says (pcc_attr_info, host only): a dict of version (1, 2, 4,
-        7, or their cross-channel forms 8, 11, 13, 14), bpv, channels, points, max_error (0: lossless), scalable, lod (the
-        sender's); for the cross-channel kinds also cross_channel, the tuple of channels coded against the channel
-        before them (pcc_attr_cross_mask)"""
+        7, their cross-channel forms 8, 11, 13, 14, or the transform-coded 19), bpv, channels, points, max_error (0:
+        lossless, and version 19), scalable, lod (the sender's); for the cross-channel kinds also cross_channel, the tuple
+        of channels coded against the channel before them (pcc_attr_cross_mask); for version 19 also qstep
+        (pcc_attr_qstep; 0 in a blob without points)"""
         buf = np.frombuffer(blob, dtype=np.uint8)
         v = [C.c_int32(0) for _ in range(6)]
         n = C.c_int64(0)
@@ -783,6 +791,10 @@ class Runtime:
             m = C.c_int32(0)
             check(_abi.lib().pcc_attr_cross_mask(_np_ptr(buf), buf.shape[0], C.byref(m)), "pcc_attr_cross_mask")
             info["cross_channel"] = tuple(ch for ch in range(1, 4) if m.value >> (ch - 1) & 1)
+        if info["version"] == ATTR_TRANSFORM_KIND:
+            q = C.c_int32(0)
+            check(_abi.lib().pcc_attr_qstep(_np_ptr(buf), buf.shape[0], C.byref(q)), "pcc_attr_qstep")
+            info["qstep"] = q.value
         return info
 
     def attr_decode_frames(self, blobs, points=None, device=False, lod=None, cells=None):
@@ -791,7 +803,8 @@ class Runtime:
         tensor (device=True).  points[f]
         (optional): frame f's geometry point count, checked against the blob before anything is launched.
         lod = k (0 .. 15) with cells (pcc_attr_decode_frames_lod): blobs of version 2, or of 7, 11 or 14, or prefixes of them (attr_lod_info)
-        -> row j the value of the j-th cell of the frame's geometry at that lod; `cells` the device tensors
+        -> row j the value of the j-th cell of the frame's geometry at that lod; lod = 0 with cells also reads whole
+        blobs of version 19, whose transform needs the frame's keys (a call of them at lod > 0: PccError); `cells` the device tensors
         octree_decode_frames(..., device=True, lod=k) returned for the same frames (views of one tensor)."""
         nb = len(blobs)
         if nb == 0:
@@ -851,6 +864,8 @@ class Runtime:
 # lod 0 only (pcc_attr_decode_frames), and the cross-channel forms 8, 11, 13, 14 of 1, 2, 4, 7
 ATTR_RUN_KINDS = (1, 4, 8, 13)
 ATTR_CROSS_KINDS = (8, 11, 13, 14)
+# the transform-coded kind: it decodes against the cells as version 2's family does, but at lod 0 only
+ATTR_TRANSFORM_KIND = 19
 
 OCTREE_V2_MIN_LEAVES = 65536     # include/pcc.h PCC_OCTREE_V2_MIN_LEAVES
 OCTREE_V3_MIN_LEAVES = 8192      # include/pcc.h PCC_OCTREE_V3_MIN_LEAVES

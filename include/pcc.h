@@ -980,6 +980,96 @@ int pcc_attr_encode_frames_cross(pcc_ctx* ctx, int version, const void* d_values
                                  int64_t cap, int64_t* h_offsets);
 int pcc_attr_cross_mask(const uint8_t* h_in, int64_t len, int32_t* h_mask);
 
+/* Transform-coded attributes: attribute blob version 19, a ninth kind, lossy,
+ * for rates below about a byte per point, where a near-lossless predictive
+ * coder (a staircase on the prediction error) is the wrong tool.  An integer
+ * lifting form of the region-adaptive hierarchical transform (G-PCC's RAHT)
+ * over the binary splits of the Morton tree.
+ *
+ * The rule (tests/attr_transform_ref.py restates it in numpy).  Per frame, as
+ * for version 2: n distinct points in Morton order, their 48-bit keys key_i
+ * biased by 32768 >> slod (slod the sender's level of detail), merged values
+ * v_i per channel of bpv bytes; H = 2^(8 bpv - 1), mask = 2 H - 1, and an
+ * integer q = qstep in 1 .. H - 1.
+ *   Sublevel of introduction: b(0) = 48; b(i) = hb(key_i xor key_{i-1}) in
+ *     0 .. 47 for i > 0 (hb: highest set bit).  Point i is the first leaf of
+ *     the RIGHT child of exactly one binary split of the Morton tree, the
+ *     split at bit b(i): version 2's size of introduction at bit granularity
+ *     (s = floor(b / 3)).
+ *   The pair of point i, t = b(i) < 48:
+ *     lo = lower_bound(keys, key_i with its low t + 1 bits cleared)
+ *     hi = lower_bound(keys, (key_i | (2^t - 1)) + 1), within the frame
+ *     wa = i - lo, wb = hi - i, w = wa + wb: the leaves of the left child,
+ *     of the right child and of the node.
+ *     step s = max(2, isqrt(floor(q^2 w / (wa wb)))); the product stays
+ *     below 2^63.
+ *   Forward: val = v, signed integers that are never clamped inside;
+ *     sublevels t = 0, 1, .., 47 in that order, the pairs of a sublevel
+ *     independent of each other (no two touch the same slot):
+ *       h = val[i] - val[lo]
+ *       val[lo] += floor(wb h / w)        floor towards -inf: the node's value,
+ *                                         kept at its first leaf
+ *       x[i] = sgn(h) min(floor((|h| + floor(s / 2)) / s), H - 1)
+ *     (s >= 2 and |h| <= mask: the min changes an index by at most 1.)  After
+ *     sublevel 47, x[0] = val[0] - H: the frame's integer weighted mean, in
+ *     [-H, H), not quantised.
+ *   Inverse: val[0] = x[0] + H; sublevels t = 47 .. 0, every i with b(i) = t,
+ *     with the same lo, hi, wa, wb, s:
+ *       h^ = x[i] s;  va = val[lo] - floor(wb h^ / w);
+ *       val[lo] = va;  val[i] = va + h^
+ *     and the output is clamp(val, 0, mask).
+ *   The floor of 2 under the step: with a step of 1 the min clamps indices
+ *     (|h| can reach mask, an index only H - 1), which cost the first form of
+ *     this kind 10 dB.  The kind therefore has NO lossless setting; q = 1
+ *     codes with s = 2 where q^2 w / (wa wb) < 4.
+ *   Coding order: (b descending, Morton index ascending), point 0 first.  x in
+ *     that order is dealt to lanes and chunks (S points per lane, as every
+ *     kind) and coded exactly as version 2 codes its residuals: the same
+ *     binarisation, contexts (channel, bucket of |x| of the channel's previous
+ *     point in the lane's run, position; buckets not retuned), p0 and model,
+ *     no prediction inside the run.
+ *   Layout: 'A' 19 (bpv | slod << 4) c | u32 n | u32 payload_len | u32 qstep |
+ *     u32 S | u32 n_chunks | u16 p0[nctx] | u32 words[n_chunks] | chunk
+ *     payloads: version 4's layout with version 2's slod nibble.  n = 0: the
+ *     12-byte head alone, which records no q.  Byte 19 keeps the odd parity
+ *     of the eight other version bytes.
+ * The decoder needs the frame's keys, so a version-19 blob decodes as the
+ * version-2 family does, against the cells its geometry decode left on the
+ * device, and at lod 0 only: a decoder at a cut does not know how many points
+ * lie under a cell and cannot form the weights, so the kind has no
+ * level-of-detail prefixes.
+ *   _encode_frames_transform : the arguments of pcc_attr_encode_frames_nl with
+ *     version 2 (d_keys, key_shift as pcc_attr_encode_frames_v2 takes them;
+ *     n_kept = -1: no row was dropped) and qstep in place of max_error:
+ *     qstep < 1, or >= H for a frame's format: PCC_E_ARG.  Launches: the merge,
+ *     three for the coding order, ONE synchronisation that reads which
+ *     sublevels hold a point, one launch per such sublevel (at most 48, over
+ *     all frames of the call at once), the mean, and the counting pass, coder
+ *     and blob assembly of every kind.
+ *   pcc_attr_decode_frames_lod with lod = 0 reads version 19 (one version per
+ *     call; lod > 0: PCC_E_ARG): three launches for the order and the same
+ *     synchronisation, the lane decoder, the root, one launch per occupied
+ *     sublevel top-down, the clamp.  A blob whose point count is not that of
+ *     its cells: PCC_E_STREAM.
+ *   pcc_attr_info reports version 19 with max_error 0, scalable 0 and the
+ *     sender's lod, from the blob or a prefix of 16 bytes or more; every part
+ *     of the header that is present is checked (q in 1 .. H - 1, S and
+ *     n_chunks against n, p0, the chunk table against the blob's announced
+ *     length), PCC_E_STREAM where a check fails.  pcc_attr_qstep: host only,
+ *     q of such a head, 0 for every other kind and for a blob without points.
+ *   pcc_attr_lod_info refuses version 19 as it refuses the kinds 1, 4, 8 and
+ *     13: PCC_E_ARG. */
+int pcc_attr_encode_frames_transform(pcc_ctx* ctx, const void* d_values,
+                                     const int64_t* h_value_offsets,
+                                     const int32_t* h_format, const int64_t* h_rows,
+                                     const int64_t* h_points, int n_frames,
+                                     const uint32_t* d_perm,
+                                     const uint32_t* d_run_starts, int64_t n_unique,
+                                     int64_t n_kept, const uint64_t* d_keys,
+                                     int key_shift, int qstep, uint8_t* h_out,
+                                     int64_t cap, int64_t* h_offsets);
+int pcc_attr_qstep(const uint8_t* h_in, int64_t len, int32_t* h_qstep);
+
 /* ---- exact nearest neighbours on the lattice: the D1 metric (csrc/nn.hip, the walk in csrc/nn_cells.h) -- */
 
 /* The rule (tests/nn_ref.py restates it in numpy).  For a frame f there are
