@@ -50,6 +50,13 @@
 // the cells): the same order stage, k_a_dec<true>, k_at_root, k_at_lift<false> top-down, k_at_store.
 // tests/attr_transform_ref.py restates the kind in numpy.
 //
+// Version 21 (attr_blob.h has the rule and the layout): version 19 with a colour word and one step per channel.  The
+// frames' steps and colour words travel in a table of their own (aux: 5 words per frame).  Encoder: version 19's
+// launches with k_at_lift<true, const int32_t*> and k_a_pack<.., TR, const int32_t*> (the same statements, one argument
+// more), and k_ac_fwd between the merge and the order stage of a call with colour = 1.  Decoder: version 19's with
+// k_at_lift<false, const int32_t*>, and k_ac_store in place of k_at_store where a frame of the call has colour = 1.
+// tests/attr_colour_ref.py restates the kind in numpy.
+//
 // Host side: the kinds share one encode sequence (a_encode_frames) and the helpers of the two decoders; DESIGN.md,
 // "attr.hip: one encode path, shared decode helpers".
 #include "common.h"
@@ -325,20 +332,28 @@ __global__ __launch_bounds__(64) void k_a_enc(const uint16_t* __restrict__ merge
   if (lane == 0) words_out[cg] = 3u * kLanes + tot;
 }
 
+// version 21's table of steps and colour words (5 words per frame: q[4], colour), the one argument more of the
+// kernels that read it (Aux = const int32_t*); the instantiations without it keep their arguments
+__device__ __forceinline__ const int32_t* a_aux() { return nullptr; }
+__device__ __forceinline__ const int32_t* a_aux(const int32_t* p) { return p; }
+
 // the blobs, assembled where `out_all` points (pinned host memory), frame f's at out_off: frame f owns workgroups
 // [cb + f, cb + f + nc + 1) — workgroup k < nc of them moves chunk k, workgroup nc writes the header; len_out[f] =
 // bytes, or -1 (out_cap).  V2: the head of attribute blob version 2, with the frame's 16 values-per-level counts
 // (cells_all[16 f + k], attr_blob.h) and the sender's level of detail.  NL: the heads of versions 4 / 7, the frame's
 // max_error behind payload_len and everything else one word later.  XC (a call with cross-channel frames): frame f with
 // cross_all[f] = m != 0 gets the cross form of the version byte and its mask above the channels of byte 3.  TR (with NL
-// and without V2): version 19's head — version 4's with q = h.e where e stands, byte 19 and the slod nibble
-template <bool V2, bool NL = false, bool XC = false, bool TR = false>
+// and without V2): version 19's head — version 4's with q = h.e where e stands, byte 19 and the slod nibble.  TC (with
+// TR): version 21's head — byte 21, and where q stands the colour word and the frame's c steps (aux_all[5 f + 4] and
+// aux_all[5 f + ch], a_aux(aux...)), everything else c words later
+template <bool V2, bool NL = false, bool XC = false, bool TR = false, typename... Aux>
 __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ work_all, const AFrame* __restrict__ tab, int nf,
                                                 const uint16_t* __restrict__ states_all, const uint16_t* __restrict__ lens_all,
                                                 const uint32_t* __restrict__ words_all, const uint16_t* __restrict__ p0_all,
                                                 uint8_t* __restrict__ out_all, long long* __restrict__ len_out,
                                                 const uint32_t* __restrict__ cells_all, int slod,
-                                                const int32_t* __restrict__ cross_all) {
+                                                const int32_t* __restrict__ cross_all, Aux... aux) {
+  constexpr bool TC = sizeof...(Aux) > 0;
   __shared__ unsigned long long s_sum[256];
   __shared__ uint32_t s_off[kLanes + 1];
   const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].cb + i; });
@@ -356,7 +371,9 @@ __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ wor
     __syncthreads();
   }
   const unsigned long long before = s_sum[0];
-  constexpr int X = NL ? 1 : 0;
+  constexpr int X0 = NL ? 1 : 0;
+  int X = X0;
+  if constexpr (TC) X = 1 + h.c;
   const unsigned long long head = (unsigned long long)((V2 ? kAttr2Head : kAttrHead + 8) + 4 * X) + 2ull * h.nctx + 4ull * nc;
   if (k == nc) {
     const unsigned long long total = head + before * 2;
@@ -376,7 +393,14 @@ __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ wor
       if constexpr (TR) out[1] = (uint8_t)kAttrTVersion, out[2] = (uint8_t)(h.bpv | (slod << 4));
       o32[1] = (uint32_t)h.n;
       o32[2] = (uint32_t)(total - kAttrHead);
-      if constexpr (NL) o32[3] = (uint32_t)h.e;
+      if constexpr (TC) {
+        out[1] = (uint8_t)kAttrCVersion;
+        const int32_t* aux_all = a_aux(aux...);
+        o32[3] = (uint32_t)aux_all[5 * f + 4];
+        for (int ch = 0; ch < h.c; ++ch) o32[4 + ch] = (uint32_t)aux_all[5 * f + ch];
+      } else if constexpr (NL) {
+        o32[3] = (uint32_t)h.e;
+      }
       o32[(V2 ? 19 : 3) + X] = (uint32_t)h.S;
       o32[(V2 ? 20 : 4) + X] = (uint32_t)h.nc;
     }
@@ -1077,13 +1101,17 @@ __device__ __forceinline__ int64_t at_step(int64_t q, int64_t wa, int64_t wb) {
 // not the cells').  ENC: val = the frame's merged values, lifted in place (a node's value lies between its children's,
 // so it stays a uint16), the index to the point's place of idx, wrapped to the value width.  Otherwise (decoder): x_all
 // the decoded indices in coding order (bpv bytes each, at out_off), val_all int64 [n][c] at element out_off; status |= 8
-// where the keys give a pair without a left or a right leaf (keys that are not sorted and distinct).
-template <bool ENC>
+// where the keys give a pair without a left or a right leaf (keys that are not sorted and distinct).  PC (version 21):
+// one step per channel, q[ch] = aux_all[5 f + ch], in place of the frame's one q (Aux = const int32_t*, one argument
+// more); the two searches serve every channel, at_step runs once per channel.
+template <bool ENC, typename... Aux>
 __global__ __launch_bounds__(256) void k_at_lift(const uint64_t* __restrict__ keys_all, const A2Order* __restrict__ tab,
                                                  const uint32_t* __restrict__ bins, const uint32_t* __restrict__ inv, int t,
                                                  const AFrame* __restrict__ etab, uint16_t* __restrict__ val_e, uint16_t* __restrict__ idx,
                                                  const ADFrame* __restrict__ dtab, const uint8_t* __restrict__ x_all,
-                                                 int64_t* __restrict__ val_d, int32_t* __restrict__ status_all) {
+                                                 int64_t* __restrict__ val_d, int32_t* __restrict__ status_all, Aux... aux) {
+  constexpr bool PC = sizeof...(Aux) > 0;
+  [[maybe_unused]] const int32_t* aux_all = a_aux(aux...);
   const int f = blockIdx.y;
   const A2Order& h = tab[f];
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1111,10 +1139,12 @@ __global__ __launch_bounds__(256) void k_at_lift(const uint64_t* __restrict__ ke
     const AFrame& fr = etab[f];
     if (wa < 1) return;   // cannot happen: the keys are sorted and distinct
     const int c = fr.c;
-    const int64_t s = at_step(fr.e, wa, wb), H = (int64_t)1 << (8 * fr.bpv - 1);
+    int64_t s = PC ? 0 : at_step(fr.e, wa, wb);
+    const int64_t H = (int64_t)1 << (8 * fr.bpv - 1);
     const uint32_t mask = (1u << (8 * fr.bpv)) - 1u;
     uint16_t* v = val_e + fr.val_off;
     for (int ch = 0; ch < c; ++ch) {
+      if constexpr (PC) s = at_step(aux_all[5 * f + ch], wa, wb);
       const int64_t va = v[lo * c + ch], hh = (int64_t)v[i * c + ch] - va;
       v[lo * c + ch] = (uint16_t)(va + at_floor_div(wb * hh, w));
       const int64_t m = std::min<int64_t>(((hh < 0 ? -hh : hh) + s / 2) / s, H - 1);
@@ -1127,10 +1157,11 @@ __global__ __launch_bounds__(256) void k_at_lift(const uint64_t* __restrict__ ke
       return;
     }
     const int c = fr.c, bpv = fr.bpv;
-    const int64_t s = at_step(fr.max_error, wa, wb);
+    int64_t s = PC ? 0 : at_step(fr.max_error, wa, wb);
     const uint8_t* x = x_all + fr.out_off + r * c * bpv;
     int64_t* v = val_d + fr.out_off;
     for (int ch = 0; ch < c; ++ch) {
+      if constexpr (PC) s = at_step(aux_all[5 * f + ch], wa, wb);
       const int64_t hh = (int64_t)a_load_s(x, bpv, ch) * s;   // |x| < 2^15, s < 2^16; wb < 2^27: no product leaves int64
       const int64_t va = v[lo * c + ch] - at_floor_div(wb * hh, w);
       v[lo * c + ch] = va;
@@ -1167,6 +1198,51 @@ __global__ __launch_bounds__(256) void k_at_store(const ADFrame* __restrict__ ta
   a_store(out_all + h.out_off + k * h.bpv, h.bpv, (uint32_t)(x < 0 ? 0 : (x > mask ? mask : x)));
 }
 
+// ---- version 21: the colour transform (attr_blob.h states the rule) ------------------------------------------------
+// encoder, between the merge and the order stage: R, G, B of every point of a frame whose aux_all[5 f + 4] is 1 become
+// Y, Co, Cg in place (all three in 0 .. mask); frame = blockIdx.y, one thread per point, a fourth channel untouched
+__global__ __launch_bounds__(256) void k_ac_fwd(const AFrame* __restrict__ tab, const int32_t* __restrict__ aux_all,
+                                                uint16_t* __restrict__ val) {
+  const int f = blockIdx.y;
+  const AFrame& h = tab[f];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= h.n || h.c < 3 || aux_all[5 * f + 4] != 1) return;
+  uint16_t* v = val + h.val_off + i * h.c;
+  const int H = 1 << (8 * h.bpv - 1);
+  const int R = v[0], G = v[1], B = v[2];
+  const int co = R - B, t = B + (co >> 1), cg = G - t;
+  v[0] = (uint16_t)(t + (cg >> 1));
+  v[1] = (uint16_t)((co >> 1) + H);
+  v[2] = (uint16_t)((cg >> 1) + H);
+}
+
+// decoder, in place of k_at_store for a call with a colour frame: k_at_store's clamp, the inverse colour transform of
+// a frame whose aux_all[5 f + 4] is 1, the second clamp and the narrowing store; frame = blockIdx.y, one thread per point
+__global__ __launch_bounds__(256) void k_ac_store(const ADFrame* __restrict__ tab, const int32_t* __restrict__ aux_all,
+                                                  const int64_t* __restrict__ val, uint8_t* __restrict__ out_all) {
+  const int f = blockIdx.y;
+  const ADFrame& h = tab[f];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= h.n) return;
+  const int c = h.c, bpv = h.bpv;
+  const int64_t mask = ((int64_t)1 << (8 * bpv)) - 1;
+  int x[4] = {0, 0, 0, 0};
+  for (int ch = 0; ch < c; ++ch) {
+    const int64_t a = val[h.out_off + i * c + ch];
+    x[ch] = (int)(a < 0 ? 0 : (a > mask ? mask : a));
+  }
+  if (c >= 3 && aux_all[5 * f + 4] == 1) {
+    const int H = 1 << (8 * bpv - 1), m = (int)mask;
+    const int co = 2 * (x[1] - H), cg = 2 * (x[2] - H), t = x[0] - (cg >> 1);
+    const int G = cg + t, B = t - (co >> 1), R = B + co;
+    x[0] = R < 0 ? 0 : (R > m ? m : R);
+    x[1] = G < 0 ? 0 : (G > m ? m : G);
+    x[2] = B < 0 ? 0 : (B > m ? m : B);
+  }
+  uint8_t* o = out_all + h.out_off + i * c * bpv;
+  for (int ch = 0; ch < c; ++ch) a_store(o, bpv, (uint32_t)x[ch], ch);
+}
+
 }  // namespace
 
 static inline int64_t a_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
@@ -1201,10 +1277,11 @@ static int a_t_order(hipStream_t st, bool from_cells, const void* src, uint64_t*
 }
 
 // version 19, encoder, behind k_a_merge: the order stage, one k_at_lift<true> per occupied sublevel bottom-up over the
-// merged values in place, and the mean; idx then holds x in coding order where the PRED = false coder reads it
+// merged values in place, and the mean; idx then holds x in coding order where the PRED = false coder reads it.
+// d_aux (version 21): the frames' steps and colour words; the lift takes a step per channel from it
 static int a_t_forward(pcc_ctx* ctx, hipStream_t st, const uint64_t* d_keys, const A2Order* d_ord, const AFrame* d_tab, int nf,
                        int64_t blocks, size_t pk_b, size_t hist_b, size_t bins_b, size_t link_b, uint16_t* merged,
-                       uint16_t* idx, uint32_t* h_bins) {
+                       uint16_t* idx, uint32_t* h_bins, const int32_t* d_aux = nullptr) {
   uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, pk_b);
   uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, hist_b);
   uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, bins_b);
@@ -1214,9 +1291,14 @@ static int a_t_forward(pcc_ctx* ctx, hipStream_t st, const uint64_t* d_keys, con
   PCC_TRY(a_t_order(st, false, (const void*)d_keys, nullptr, d_ord, nf, blocks, packed, hist, bins, inv, h_bins, grid));
   for (int t = 0; t < kATBins - 1; ++t) {
     if (!grid[t]) continue;
-    hipLaunchKernelGGL(k_at_lift<true>, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, d_keys, d_ord, (const uint32_t*)bins,
-                       (const uint32_t*)inv, t, d_tab, merged, idx, (const ADFrame*)nullptr, (const uint8_t*)nullptr, (int64_t*)nullptr,
-                       (int32_t*)nullptr);
+    if (d_aux)
+      hipLaunchKernelGGL((k_at_lift<true, const int32_t*>), dim3(grid[t], (unsigned)nf), dim3(256), 0, st, d_keys, d_ord, (const uint32_t*)bins,
+                         (const uint32_t*)inv, t, d_tab, merged, idx, (const ADFrame*)nullptr, (const uint8_t*)nullptr, (int64_t*)nullptr,
+                         (int32_t*)nullptr, d_aux);
+    else
+      hipLaunchKernelGGL(k_at_lift<true>, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, d_keys, d_ord, (const uint32_t*)bins,
+                         (const uint32_t*)inv, t, d_tab, merged, idx, (const ADFrame*)nullptr, (const uint8_t*)nullptr, (int64_t*)nullptr,
+                         (int32_t*)nullptr);
     PCC_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(k_at_mean, dim3(nblk(4 * (int64_t)nf, 256)), dim3(256), 0, st, d_tab, nf, (const uint16_t*)merged, idx);
@@ -1234,13 +1316,18 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
                            const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
                            const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys,
                            int key_shift, uint8_t* h_out, int64_t cap, int64_t* h_offsets, int64_t n_kept = -1,
-                           int max_error = 0, const int32_t* h_cross = nullptr, int qstep = 0) {
+                           int max_error = 0, const int32_t* h_cross = nullptr, int qstep = 0, const int32_t* h_qsteps = nullptr,
+                           int colour = 0) {
   // qstep > 0: version 19.  Its head is version 4's with q where e stands (and the slod nibble), so it runs as that
-  // kind does (nl, r.e = q) with the order stage and the lifting passes in place of k_a4_quant
+  // kind does (nl, r.e = q) with the order stage and the lifting passes in place of k_a4_quant.  h_qsteps: version 21,
+  // which runs as version 19 does (r.e = 1, which nothing reads) with a frame's steps and colour word in a table of
+  // their own (aux: 5 words per frame), k_ac_fwd behind the merge where colour = 1, and a longer head
+  const bool tc = h_qsteps != nullptr;
+  if (tc) qstep = 1;
   const bool tr = qstep > 0;
   if (tr) max_error = qstep;
   const bool v2 = version == 2 && !tr, nl = max_error > 0, keyed = v2 || tr;
-  const int blob_version = tr ? kAttrTVersion : (nl ? (v2 ? 7 : 4) : version);
+  const int blob_version = tc ? kAttrCVersion : (tr ? kAttrTVersion : (nl ? (v2 ? 7 : 4) : version));
   PCC_REQUIRE(ctx && h_value_offsets && h_format && h_rows && h_points && h_out && h_offsets && n_frames >= 1 &&
                   n_frames <= 65535 && n_unique >= 0 && cap >= 0,
               PCC_E_ARG, "%s: bad argument (n_frames=%d)", who, n_frames);
@@ -1258,6 +1345,7 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
   std::vector<A2Order> order;
   std::vector<int> frame_of;
   std::vector<int32_t> cross;   // the masks of the frames with points
+  std::vector<int32_t> aux;     // version 21: q[4] and the colour word of the frames with points
   bool xc = false;              // one of them is not 0
   int64_t n_max = 0;            // k_ax_fwd: the most points of a frame
   int64_t run_threads = 0;   // k_a4_quant: the most (run, channel) pairs of a frame
@@ -1270,14 +1358,25 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     PCC_REQUIRE(rows >= 0 && n >= 0 && n <= rows && ((n == 0) == (rows == 0) || (drops && n == 0)) &&
                     h_value_offsets[f] >= 0, PCC_E_ARG,
                 "%s: frame %d: %lld rows, %lld points", who, f, (long long)rows, (long long)n);
-    PCC_REQUIRE(!nl || (uint32_t)max_error <= attr_max_error(bpv), PCC_E_ARG,
+    PCC_REQUIRE(!nl || tc || (uint32_t)max_error <= attr_max_error(bpv), PCC_E_ARG,
                 "%s: frame %d: %s %d with %d bytes per value (at most %u)", who, f, tr ? "qstep" : "max_error", max_error, bpv,
                 attr_max_error(bpv));
+    if (tc) {
+      for (int ch = 0; ch < c; ++ch)
+        PCC_REQUIRE(h_qsteps[ch] >= 1 && (uint32_t)h_qsteps[ch] <= attr_max_error(bpv), PCC_E_ARG,
+                    "%s: frame %d: qstep %d of channel %d with %d bytes per value (1 .. %u)", who, f, h_qsteps[ch], ch, bpv,
+                    attr_max_error(bpv));
+      PCC_REQUIRE(!colour || c >= 3, PCC_E_ARG, "%s: frame %d: the colour transform needs 3 channels, the frame has %d", who, f, c);
+    }
     const int32_t m = h_cross ? h_cross[f] : 0;
     PCC_REQUIRE(m >= 0 && m < (1 << (c - 1)), PCC_E_ARG, "%s: frame %d: cross-channel mask %d with %d channels", who, f, m, c);
     if (n == 0) continue;
     cross.push_back(m);
     xc |= m != 0;
+    if (tc) {
+      for (int ch = 0; ch < 4; ++ch) aux.push_back(ch < c ? h_qsteps[ch] : 0);
+      aux.push_back(colour);
+    }
     n_max = std::max(n_max, n);
     AFrame r;
     int64_t S, nc;
@@ -1295,7 +1394,7 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     r.nctx = attr_contexts(bpv, c);
     r.ctx_off = (int32_t)ctxs;
     r.T = (int32_t)(S * c * attr_positions(bpv));
-    const int64_t head = (v2 ? kAttr2Head : kAttrHead + 8) + (nl ? 4 : 0) + 2 * r.nctx + 4 * nc;
+    const int64_t head = (v2 ? kAttr2Head : kAttrHead + 8) + (nl ? 4 : 0) + (tc ? 4 * c : 0) + 2 * r.nctx + 4 * nc;
     // a coded decision emits at most one word: the bound follows the frame's decisions, not its chunks' regions
     r.out_cap = head + 2 * (3 * kLanes * nc + std::min<int64_t>(nc * kLanes * r.T, (int64_t)attr_positions(bpv) * c * n));
     r.out_off = out_bytes;
@@ -1327,9 +1426,10 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
   hipStream_t st = ctx->stream;
   if (nf > 0) {
     const size_t ord_b = keyed ? pcc_align((size_t)nf * sizeof(A2Order)) : 0;
-    // the rows | the masks (a call with cross-channel frames) | the order rows
+    // the rows | the masks (a call with cross-channel frames) | steps and colour (version 21) | the order rows
     const size_t fr_b = pcc_align((size_t)nf * sizeof(AFrame)), cross_b = xc ? pcc_align((size_t)nf * 4) : 0;
-    const size_t tab_b = fr_b + cross_b + ord_b;
+    const size_t aux_b = tc ? pcc_align((size_t)nf * 20) : 0;
+    const size_t tab_b = fr_b + cross_b + aux_b + ord_b;
     const size_t merged_b = merged_b_of(vals), cnt_b = pcc_align((size_t)ctxs * 8), p0_b = pcc_align((size_t)ctxs * 2);
     const size_t rec_b = pcc_align((size_t)rec_words * 2), small_b = pcc_align((size_t)chunks * (4 + 2 * kLanes * 2 + kLanes * 2));
     // the order stage's (versions 2 and 7): packed | hist | 17 bin bases, then 16 counts per frame; rank, first (7)
@@ -1359,6 +1459,7 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     uint16_t* lens_d = states + (size_t)chunks * 2 * kLanes;
     const A2Order* d_ord = (const A2Order*)((const uint8_t*)d_tab + tab_b - ord_b);
     const int32_t* d_cross = xc ? (const int32_t*)((const uint8_t*)d_tab + fr_b) : nullptr;
+    const int32_t* d_aux = tc ? (const int32_t*)((const uint8_t*)d_tab + fr_b + cross_b) : nullptr;
     // staging: the table on its way to the device | the blobs | their lengths
     const size_t lens_at = tab_b + (size_t)out_bytes;
     const size_t tcnt_at = lens_at + (size_t)nf * 8 + 64;   // version 19: the sublevels' starts and counts, read back
@@ -1366,6 +1467,7 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     uint8_t* stage = (uint8_t*)ctx->stage;
     memcpy(stage, tab.data(), (size_t)nf * sizeof(AFrame));
     if (xc) memcpy(stage + fr_b, cross.data(), (size_t)nf * 4);
+    if (tc) memcpy(stage + fr_b + cross_b, aux.data(), (size_t)nf * 20);
     if (keyed) memcpy(stage + tab_b - ord_b, order.data(), (size_t)nf * sizeof(A2Order));
     long long* len_dev = (long long*)(stage + lens_at);
     PccProfScope prof(ctx, "attr_encode", u, nf, chunks, 0);
@@ -1403,8 +1505,12 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     };
     if (v2) PCC_TRY(a_order_stage(nl));
     if (tr) {
+      if (tc && colour) {
+        hipLaunchKernelGGL(k_ac_fwd, dim3(nblk(n_max, 256), (unsigned)nf), dim3(256), 0, st, (const AFrame*)d_tab, d_aux, merged);
+        PCC_CHECK_LAUNCH();
+      }
       PCC_TRY(a_t_forward(ctx, st, d_keys, d_ord, (const AFrame*)d_tab, nf, merge_blocks, pk_b, thist_b, tbins_b, link_b, merged, src,
-                          (uint32_t*)(stage + tcnt_at)));
+                          (uint32_t*)(stage + tcnt_at), d_aux));
     } else if (nl && !v2) {
       hipLaunchKernelGGL(k_a4_quant, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const uint16_t*)merged,
                          (const AFrame*)d_tab, src);
@@ -1422,8 +1528,9 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     }
     // counting pass, coder, blobs: only version 1 predicts inside the run (PRED), and not beside cross-channel frames
     const size_t lds = 4096 * 4 + (size_t)(nctx_max + 1) * kLanes * 2;   // <= 98 KB (c = 4, uint16)
-    auto a_code = [&](auto v2c, auto nlc, auto xcc, auto trc) -> int {
+    auto a_code = [&](auto v2c, auto nlc, auto xcc, auto trc, auto tcc) -> int {
       constexpr bool V2 = decltype(v2c)::value, NL = decltype(nlc)::value, XC = decltype(xcc)::value, TR = decltype(trc)::value;
+      constexpr bool TC = decltype(tcc)::value;
       constexpr bool PRED = !V2 && !NL && !XC;
       hipLaunchKernelGGL(k_a_stats<PRED>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)src, (const AFrame*)d_tab, nf, cnt);
       PCC_CHECK_LAUNCH();
@@ -1431,16 +1538,22 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
       hipLaunchKernelGGL(k_a_enc<PRED>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)src, (const AFrame*)d_tab, nf,
                          (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
       PCC_CHECK_LAUNCH();
-      hipLaunchKernelGGL((k_a_pack<V2, NL, XC, TR>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work,
-                         (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words,
-                         (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3, d_cross);
+      if constexpr (TC)
+        hipLaunchKernelGGL((k_a_pack<V2, NL, XC, TR, const int32_t*>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st,
+                           (const uint16_t*)work, (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d,
+                           (const uint32_t*)words, (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3,
+                           d_cross, d_aux);
+      else
+        hipLaunchKernelGGL((k_a_pack<V2, NL, XC, TR>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work,
+                           (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words,
+                           (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3, d_cross);
       PCC_CHECK_LAUNCH();
       return PCC_OK;
     };
     using Yes = std::true_type;
     using No = std::false_type;
-    auto a_kind = [&](auto v2c, auto nlc) -> int { return xc ? a_code(v2c, nlc, Yes{}, No{}) : a_code(v2c, nlc, No{}, No{}); };
-    PCC_TRY(tr ? a_code(No{}, Yes{}, No{}, Yes{}) : v2 ? (nl ? a_kind(Yes{}, Yes{}) : a_kind(Yes{}, No{})) : (nl ? a_kind(No{}, Yes{}) : a_kind(No{}, No{})));
+    auto a_kind = [&](auto v2c, auto nlc) -> int { return xc ? a_code(v2c, nlc, Yes{}, No{}, No{}) : a_code(v2c, nlc, No{}, No{}, No{}); };
+    PCC_TRY(tc ? a_code(No{}, Yes{}, No{}, Yes{}, Yes{}) : tr ? a_code(No{}, Yes{}, No{}, Yes{}, No{}) : v2 ? (nl ? a_kind(Yes{}, Yes{}) : a_kind(Yes{}, No{})) : (nl ? a_kind(No{}, Yes{}) : a_kind(No{}, No{})));
     PCC_HIP(hipStreamSynchronize(st));
     for (int k = 0; k < nf; ++k) {
       const long long total = ((volatile long long*)len_dev)[k];
@@ -1535,6 +1648,17 @@ extern "C" int pcc_attr_encode_frames_transform(pcc_ctx* ctx, const void* d_valu
                          d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets, n_kept, 0, nullptr, qstep);
 }
 
+extern "C" int pcc_attr_encode_frames_transform2(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
+                                                 const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
+                                                 const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, int64_t n_kept,
+                                                 const uint64_t* d_keys, int key_shift, const int32_t h_qstep[4], int colour,
+                                                 uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
+  PCC_REQUIRE(n_kept >= -1 && h_qstep && (colour == 0 || colour == 1), PCC_E_ARG,
+              "pcc_attr_encode_frames_transform2: bad argument (n_kept=%lld colour=%d)", (long long)n_kept, colour);
+  return a_encode_frames("pcc_attr_encode_frames_transform2", 2, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames,
+                         d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets, n_kept, 0, nullptr, 0, h_qstep, colour);
+}
+
 // host only: the version byte and byte 3 of a head, checked: its kind, channels and mask
 static int a_head_kind(const char* who, const uint8_t* h_in, int64_t len, bool* scal, bool* nl, bool* xc, int* c, int* m) {
   PCC_REQUIRE(h_in && len >= kAttrHead && h_in[0] == 'A', PCC_E_STREAM, "%s: not an attribute blob (len=%lld)", who, (long long)len);
@@ -1568,9 +1692,40 @@ extern "C" int pcc_attr_qstep(const uint8_t* h_in, int64_t len, int32_t* h_qstep
   return PCC_OK;
 }
 
+// host only: the colour word and the steps of a version-21 head (h_in may be a prefix that reaches q[c - 1]), 0s for
+// every other kind and for a blob without points
+extern "C" int pcc_attr_transform_info(const uint8_t* h_in, int64_t len, int32_t* h_colour, int32_t h_qstep[4]) {
+  int32_t ver = 0;
+  PCC_TRY(pcc_attr_info(h_in, len, &ver, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+  AttrCInfo o;
+  o.colour = 0;
+  for (int ch = 0; ch < 4; ++ch) o.q[ch] = 0;
+  if (attr_c_kind(ver)) PCC_TRY(attr_c_parse(h_in, len, &o, true));
+  if (h_colour) *h_colour = (int32_t)o.colour;
+  for (int ch = 0; h_qstep && ch < 4; ++ch) h_qstep[ch] = (int32_t)o.q[ch];
+  return PCC_OK;
+}
+
 // host only: what the head of an attribute blob of any kind says (h_in may be a prefix that holds the head)
 extern "C" int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_version, int32_t* h_bpv, int32_t* h_channels,
                              int64_t* h_points, int32_t* h_max_error, int32_t* h_scalable, int32_t* h_lod) {
+  if (h_in && len >= kAttrHead && h_in[0] == 'A' && attr_c_kind(h_in[1])) {   // version 21: its own parser; steps through pcc_attr_transform_info
+    AttrCInfo o;
+    const int rc = attr_c_parse(h_in, len, &o, true);
+    if (rc != PCC_OK) {
+      const std::string msg = pcc_last_error();
+      pcc_set_error("pcc_attr_info: %s", msg.c_str());
+      return rc;
+    }
+    if (h_version) *h_version = o.version;
+    if (h_bpv) *h_bpv = o.bpv;
+    if (h_channels) *h_channels = o.c;
+    if (h_points) *h_points = o.n;
+    if (h_max_error) *h_max_error = 0;
+    if (h_scalable) *h_scalable = 0;
+    if (h_lod) *h_lod = o.slod;
+    return PCC_OK;
+  }
   if (h_in && len >= kAttrHead && h_in[0] == 'A' && attr_t_kind(h_in[1])) {   // version 19: its own parser; q through pcc_attr_qstep
     AttrTInfo o;
     const int rc = attr_t_parse(h_in, len, &o, true);
@@ -1810,15 +1965,17 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
 // ---- version 19: the decoder -----------------------------------------------------------------------------------------
 // Against the cells its geometry decode left in HBM, as version 2's at lod 0: the order stage over the cells' keys, the
 // lane decoder (x in coding order), the root, one k_at_lift<false> per occupied sublevel top-down, clamp and store.
+// tc: a call of version-21 blobs — their steps and colour words in a table behind the order rows (aux: 5 words per
+// frame), the lift with a step per channel, and k_ac_store in place of k_at_store where a frame has the colour transform
 static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
                              const int32_t* d_cells, const int64_t* h_cell_offsets, uint8_t* d_out, uint8_t* h_out, int64_t cap_bytes,
-                             int64_t* h_out_offsets, int32_t* h_format) {
-  std::vector<AttrTInfo> info((size_t)n_frames);
+                             int64_t* h_out_offsets, int32_t* h_format, bool tc = false) {
+  std::vector<AttrCInfo> info((size_t)n_frames);
   int64_t bytes = 0, bodies = 0, points = 0;
   h_out_offsets[0] = 0;
   for (int f = 0; f < n_frames; ++f) {
-    AttrTInfo& o = info[(size_t)f];
-    const int rc = attr_t_parse(h_blobs[f], h_lens[f], &o);
+    AttrCInfo& o = info[(size_t)f];
+    const int rc = tc ? attr_c_parse(h_blobs[f], h_lens[f], &o) : attr_t_parse(h_blobs[f], h_lens[f], &o);
     if (rc != PCC_OK) return a_wrap_error(who, f, rc);
     if (h_cell_offsets) {
       const int64_t m = h_cell_offsets[f + 1] - h_cell_offsets[f];
@@ -1837,11 +1994,19 @@ static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const
   PCC_REQUIRE(cap_bytes >= bytes, PCC_E_NOMEM, "%s: %lld bytes, capacity %lld", who, (long long)bytes, (long long)cap_bytes);
   std::vector<ADFrame> tab;
   std::vector<A2Order> order;
-  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, blocks = 0, vals_max = 0;
+  std::vector<int32_t> aux;
+  bool any_colour = false;
+  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, blocks = 0, vals_max = 0, n_max = 0;
   const int64_t cell0 = h_cell_offsets[0];
   for (int f = 0; f < n_frames; ++f) {
-    const AttrTInfo& o = info[(size_t)f];
+    const AttrCInfo& o = info[(size_t)f];
     if (o.n == 0) continue;
+    if (tc) {
+      for (int ch = 0; ch < 4; ++ch) aux.push_back((int32_t)o.q[ch]);
+      aux.push_back((int32_t)o.colour);
+      any_colour |= o.colour != 0;
+    }
+    n_max = std::max(n_max, o.n);
     const uint8_t* table = h_blobs[f] + o.off_table;
     ADFrame r = a_dec_row(o, body_off, h_out_offsets[f], chunks, o.nc, o.n, attr_u32(table + 4 * (o.nc - 1)));
     r.max_error = (int32_t)o.qstep;   // q where the near-lossless kinds keep e
@@ -1859,7 +2024,8 @@ static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const
   const int nf = (int)tab.size();
   hipStream_t st = ctx->stream;
   const size_t ftab_b = pcc_align((size_t)nf * sizeof(ADFrame)), ord_b = pcc_align((size_t)nf * sizeof(A2Order));
-  const size_t tab_b = ftab_b + ord_b;
+  const size_t aux_b = tc ? pcc_align((size_t)nf * 20) : 0;
+  const size_t tab_b = ftab_b + ord_b + aux_b;
   const size_t keys_b = pcc_align((size_t)cells_all * 8), u32_b = pcc_align((size_t)cells_all * 4), pk_b = pcc_align((size_t)cells_all * 2);
   const size_t hist_b = pcc_align((size_t)blocks * kATBins * 4), bins_b = pcc_align((size_t)nf * 2 * kATBins * 4);
   const size_t val_b = pcc_align((size_t)bytes * 8), status_b = pcc_align((size_t)nf * 4 + 64);
@@ -1883,8 +2049,9 @@ static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const
   uint8_t* stage = (uint8_t*)ctx->stage;
   memcpy(stage, tab.data(), (size_t)nf * sizeof(ADFrame));
   memcpy(stage + ftab_b, order.data(), (size_t)nf * sizeof(A2Order));
+  if (tc) memcpy(stage + ftab_b + ord_b, aux.data(), (size_t)nf * 20);
   for (int f = 0, k = 0; f < n_frames; ++f) {
-    const AttrTInfo& o = info[(size_t)f];
+    const AttrCInfo& o = info[(size_t)f];
     if (o.n == 0) continue;
     memcpy(stage + tab_b + tab[(size_t)k++].body_off, h_blobs[f] + o.off_p0, (size_t)(h_lens[f] - o.off_p0));
   }
@@ -1892,6 +2059,7 @@ static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const
   PCC_HIP(hipMemsetAsync(status, 0, (size_t)nf * 4, st));
   const ADFrame* d_tab = (const ADFrame*)d_in;
   const A2Order* d_ord = (const A2Order*)(d_in + ftab_b);
+  const int32_t* d_aux = tc ? (const int32_t*)(d_in + ftab_b + ord_b) : nullptr;
   PCC_TRY(a_launch_dec<true>(st, chunks, d_in, tab_b, nf, nctx_max, cw_max, x, status));
   unsigned grid[kATBins];
   PCC_TRY(a_t_order(st, true, (const void*)cells, keys, d_ord, nf, blocks, packed, hist, bins, inv, (uint32_t*)back, grid));
@@ -1899,12 +2067,20 @@ static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const
   PCC_CHECK_LAUNCH();
   for (int t = kATBins - 2; t >= 0; --t) {
     if (!grid[t]) continue;
-    hipLaunchKernelGGL(k_at_lift<false>, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, (const uint64_t*)keys, d_ord, (const uint32_t*)bins,
-                       (const uint32_t*)inv, t, (const AFrame*)nullptr, (uint16_t*)nullptr, (uint16_t*)nullptr, d_tab, (const uint8_t*)x, val,
-                       status);
+    if (tc)
+      hipLaunchKernelGGL((k_at_lift<false, const int32_t*>), dim3(grid[t], (unsigned)nf), dim3(256), 0, st, (const uint64_t*)keys, d_ord,
+                         (const uint32_t*)bins, (const uint32_t*)inv, t, (const AFrame*)nullptr, (uint16_t*)nullptr, (uint16_t*)nullptr, d_tab,
+                         (const uint8_t*)x, val, status, d_aux);
+    else
+      hipLaunchKernelGGL(k_at_lift<false>, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, (const uint64_t*)keys, d_ord, (const uint32_t*)bins,
+                         (const uint32_t*)inv, t, (const AFrame*)nullptr, (uint16_t*)nullptr, (uint16_t*)nullptr, d_tab, (const uint8_t*)x, val,
+                         status);
     PCC_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(k_at_store, dim3(nblk(vals_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, (const int64_t*)val, out);
+  if (any_colour)
+    hipLaunchKernelGGL(k_ac_store, dim3(nblk(n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, d_aux, (const int64_t*)val, out);
+  else
+    hipLaunchKernelGGL(k_at_store, dim3(nblk(vals_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, (const int64_t*)val, out);
   PCC_CHECK_LAUNCH();
   int32_t* h_status = (int32_t*)back + (size_t)nf * 2 * kATBins;
   if (down) PCC_HIP(hipMemcpyAsync(down, out, (size_t)bytes, hipMemcpyDeviceToHost, st));
@@ -1927,6 +2103,9 @@ extern "C" int pcc_attr_lod_info(const uint8_t* h_in, int64_t len, int lod, int6
   bool scal = false, nl = false, xc = false;
   PCC_REQUIRE(!attr_t_kind(h_in[1]), PCC_E_ARG,
               "pcc_attr_lod_info: attribute blob version 19 (a transform-coded blob has no level-of-detail prefixes: the weights of its "
+              "transform need every point)");
+  PCC_REQUIRE(!attr_c_kind(h_in[1]), PCC_E_ARG,
+              "pcc_attr_lod_info: attribute blob version 21 (a transform-coded blob has no level-of-detail prefixes: the weights of its "
               "transform need every point)");
   PCC_REQUIRE(attr_kind(h_in[1], &scal, &nl, &xc) && scal, PCC_E_ARG,
               "pcc_attr_lod_info: attribute blob version %d (levels of detail are a property of version 2)", (int)h_in[1]);
@@ -1959,6 +2138,17 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
                   "%s: frame %d: attribute blobs of version 19 and of another version in one call (one version per call)", who, f);
     PCC_REQUIRE(lod == 0, PCC_E_ARG, "%s: attribute blob version 19 at level of detail %d (it decodes at 0 only)", who, lod);
     return a_t_decode_frames(who, ctx, h_blobs, h_lens, n_frames, d_cells, h_cell_offsets, d_out, h_out, cap_bytes, h_out_offsets, h_format);
+  }
+  // version 21 likewise
+  bool any_c = false;
+  for (int f = 0; f < n_frames; ++f) any_c |= a_is_version(h_blobs[f], h_lens[f], kAttrCVersion);
+  if (any_c) {
+    for (int f = 0; f < n_frames; ++f)
+      PCC_REQUIRE(a_is_version(h_blobs[f], h_lens[f], kAttrCVersion), PCC_E_ARG,
+                  "%s: frame %d: attribute blobs of version 21 and of another version in one call (one version per call)", who, f);
+    PCC_REQUIRE(lod == 0, PCC_E_ARG, "%s: attribute blob version 21 at level of detail %d (it decodes at 0 only)", who, lod);
+    return a_t_decode_frames(who, ctx, h_blobs, h_lens, n_frames, d_cells, h_cell_offsets, d_out, h_out, cap_bytes, h_out_offsets, h_format,
+                             true);
   }
   // the blobs of a call are of one version, the first blob's: 2, or 7 (k_a2_walk<true> scales and clamps), or their
   // cross-channel forms 11 and 14 (k_ax_inv between the decoder and the walk)

@@ -1,6 +1,6 @@
 // attr_blob.h — the header of an attribute blob (attr.hip), parsed and checked on the host before anything is reserved
 // or launched.  Plain C++ (no HIP): tests/fuzz/fuzz_attr_header.cpp, fuzz_attr2_header.cpp, fuzz_attr_nl_header.cpp,
-// fuzz_attr_cross_header.cpp and fuzz_attr_transform_header.cpp put it under the sanitizers.
+// fuzz_attr_cross_header.cpp, fuzz_attr_transform_header.cpp and fuzz_attr_colour_header.cpp put it under the sanitizers.
 //
 // Every size the decoder reserves or reads follows from what this parse accepted: the chunk table must add up to the
 // blob's own length, so a header cannot announce more words than the blob holds; n is bounded by the chunks
@@ -462,6 +462,109 @@ static inline int attr_t_parse(const uint8_t* b, int64_t len, AttrTInfo* o, bool
   o->off_payload = o->off_table + 4 * o->nc;
   o->payload_words = words;
   ATTR2_REQUIRE(o->off_payload + 2 * words == total, "attribute blob v19: chunks take %lld bytes, blob has %lld", (long long)(2 * words),
+                (long long)(total - o->off_payload));
+  return PCC_OK;
+}
+
+// ---- version 21: transform-coded attributes with a colour transform and one step per channel ------------------------
+// A tenth kind (compress(..., qstep=(q0, q1, ..)) and compress(..., qstep=q, colour="ycocg")): version 19 with a colour
+// word and c steps where version 19 keeps its one q:
+//
+//   'A' 21 (bpv | slod << 4) c | u32 n | u32 payload_len | u32 colour | u32 q[c] | u32 S | u32 n_chunks | u16 p0[nctx] |
+//   u32 words[n_chunks] | chunk payloads                  (n == 0: the 12 bytes up to payload_len = 0; they record
+//                                                          neither colour nor steps)
+//
+// Byte 21 = 10101b has odd parity as the nine bytes above, so it differs from each of them in two bits; it has its own
+// predicate (attr_c_kind) and parser (attr_c_parse), and every other parser refuses it.
+// Everything is version 19's — keys, sublevels, pairs, weights, forward and inverse lift, the mean, coding order,
+// entropy stage, the clamp of an index at H - 1 — except:
+//   steps      q[ch] in 1 .. H - 1 for every channel ch < c; the step of a pair in channel ch is
+//              s[ch] = max(2, isqrt(floor(q[ch]^2 w / (wa wb)))).  With all q[ch] equal and colour = 0 the indices are
+//              exactly version 19's; only the head differs.
+//   colour     0: none.  1 (frames with c >= 3; channels 0, 1, 2 = R, G, B, a fourth channel is untouched): applied to
+//              the merged values of every distinct point after the merge and before the first lift.  Signed integers,
+//              >> the arithmetic shift (floor), H = 2^(8 bpv - 1), mask = 2 H - 1:
+//                co = R - B;  t = B + (co >> 1);  cg = G - t;  y = t + (cg >> 1)
+//                Y = y,  Co = (co >> 1) + H,  Cg = (cg >> 1) + H                      all three in 0 .. mask
+//              YCoCg-R with the low bit of each chroma difference dropped, so the three values fit the value width and
+//              a node's value stays a uint16.  Inverse, applied to the inverse lift's output after its clamp to
+//              0 .. mask, then clamped again per channel:
+//                co' = 2 (Co - H);  cg' = 2 (Cg - H);  t = Y - (cg' >> 1)
+//                G = cg' + t;  B = t - (co' >> 1);  R = B + co'
+//              Without quantisation the round trip moves no channel by more than 1.  Anything but 0 and 1, and 1 with
+//              c < 3, is PCC_E_STREAM.
+// tests/attr_colour_ref.py restates the kind in numpy.
+constexpr int kAttrCVersion = 21;
+
+struct AttrCInfo : AttrTInfo {
+  uint32_t colour;   // 0 | 1 (0: a blob without points)
+  uint32_t q[4];     // q[ch], ch < c (0s: a blob without points); qstep stays 0
+};
+
+static inline bool attr_c_kind(int version) { return version == kAttrCVersion; }
+static inline int attr_c_head(int c) { return kAttrHead + 4 + 4 * c + 8; }   // .. | u32 colour | u32 q[c] | u32 S | u32 n_chunks
+
+// b[0 .. len): the whole blob, and nothing behind it; or (prefix: pcc_attr_info, pcc_attr_transform_info) the blob or a
+// prefix of it that reaches q[c - 1] (16 + 4 c bytes), of which every part of the header that is there is checked as the
+// whole blob's is.  Nothing beyond b[len) is read.
+static inline int attr_c_parse(const uint8_t* b, int64_t len, AttrCInfo* o, bool prefix = false) {
+  ATTR2_REQUIRE(b && len >= kAttrHead && b[0] == 'A' && attr_c_kind(b[1]), "attribute blob v21: bad header (len=%lld)", (long long)len);
+  o->version = kAttrCVersion;
+  o->max_error = 0;
+  o->cross = 0;
+  o->qstep = 0;
+  o->colour = 0;
+  for (int ch = 0; ch < 4; ++ch) o->q[ch] = 0;
+  o->bpv = b[2] & 15;
+  o->slod = b[2] >> 4;
+  o->c = b[3];
+  ATTR2_REQUIRE((o->bpv == 1 || o->bpv == 2) && o->c >= 1 && o->c <= 4 && o->slod <= kAttrMaxLod,
+                "attribute blob v21: %d bytes per value, %d channels", o->bpv, o->c);
+  o->nctx = attr_contexts(o->bpv, o->c);
+  o->n = (int64_t)attr_u32(b + 4);
+  const int64_t payload = (int64_t)attr_u32(b + 8), total = kAttrHead + payload;
+  ATTR2_REQUIRE(prefix ? len <= total : len == total, "attribute blob v21: payload of %lld bytes in a blob of %lld", (long long)payload,
+                (long long)len);
+  o->S = o->nc = 0;
+  o->off_p0 = o->off_table = o->off_payload = kAttrHead;
+  o->payload_words = 0;
+  if (o->n == 0) {
+    ATTR2_REQUIRE(payload == 0, "attribute blob v21: no points, %lld bytes of payload", (long long)payload);
+    return PCC_OK;
+  }
+  const int head = attr_c_head(o->c);
+  o->off_p0 = head;
+  o->off_table = o->off_p0 + 2 * (int64_t)o->nctx;
+  ATTR2_REQUIRE(o->n < ((int64_t)1 << 27) && payload >= o->off_table - kAttrHead + 4 + 2 * 3 * kAttrLanes,
+                "attribute blob v21: %lld points, payload %lld", (long long)o->n, (long long)payload);
+  ATTR2_REQUIRE(len >= head - 8, "attribute blob v21: truncated in front of its steps (len=%lld)", (long long)len);
+  o->colour = attr_u32(b + kAttrHead);
+  ATTR2_REQUIRE(o->colour <= 1 && (o->colour == 0 || o->c >= 3), "attribute blob v21: colour transform %u with %d channels", o->colour,
+                o->c);
+  for (int ch = 0; ch < o->c; ++ch) {
+    o->q[ch] = attr_u32(b + kAttrHead + 4 + 4 * ch);
+    ATTR2_REQUIRE(o->q[ch] >= 1 && o->q[ch] <= attr_max_error(o->bpv), "attribute blob v21: qstep %u of channel %d with %d bytes per value",
+                  o->q[ch], ch, o->bpv);
+  }
+  if (len < head && prefix) return PCC_OK;
+  ATTR2_REQUIRE(len >= head, "attribute blob v21: truncated header");
+  o->S = (int64_t)attr_u32(b + head - 8);
+  o->nc = (int64_t)attr_u32(b + head - 4);
+  ATTR2_REQUIRE(o->S >= 1 && o->S * o->c <= kAttrMaxValues && o->nc >= 1 && o->nc <= o->n && kAttrLanes * o->S * o->nc >= o->n &&
+                    kAttrLanes * o->S * (o->nc - 1) < o->n,
+                "attribute blob v21: %lld points in %lld chunks of 64 x %lld", (long long)o->n, (long long)o->nc, (long long)o->S);
+  ATTR2_REQUIRE(total - o->off_table >= 4 * o->nc, "attribute blob v21: truncated chunk table");
+  if (len < o->off_table && prefix) return PCC_OK;
+  ATTR2_REQUIRE(len >= o->off_table, "attribute blob v21: truncated header");
+  uint32_t bad_p = 0;
+  ATTR2_REQUIRE(attr_check_p0(b, o->off_p0, o->nctx, &bad_p), "attribute blob v21: initial probability %u", bad_p);
+  if (len - o->off_table < 4 * o->nc && prefix) return PCC_OK;
+  int64_t words = 0, bad_k = 0, bad_cw = 0;
+  ATTR2_REQUIRE(attr_sum_chunks(b + o->off_table, o->nc, o->bpv, &words, &bad_k, &bad_cw), "attribute blob v21: chunk %lld has %lld words",
+                (long long)bad_k, (long long)bad_cw);
+  o->off_payload = o->off_table + 4 * o->nc;
+  o->payload_words = words;
+  ATTR2_REQUIRE(o->off_payload + 2 * words == total, "attribute blob v21: chunks take %lld bytes, blob has %lld", (long long)(2 * words),
                 (long long)(total - o->off_payload));
   return PCC_OK;
 }

@@ -49,6 +49,16 @@ grow under it.  The decoded values are exactly those of the same call without it
 No decoded value is off by more than max_error from what max_error=0 (the default, lossless, the bytes of before)
 returns for the same call.  include/pcc.h states the rule.
 
+Transform-coded attributes (attribute blob versions 19 and 21, include/pcc.h has the rule): lossy, for rates below about
+a byte per point.  Version 21 decorrelates colour first (luma and two chroma differences) and gives every channel its own
+step: on recorded camera colour it is shorter AND closer at q = 16 than plain RGB at q = 32.
+
+    blobs, attr_blobs = codec.compress(frames, attributes=rgb, qstep=32)                     # version 19: one step, R G B
+    blobs, attr_blobs = codec.compress(frames, attributes=rgb, qstep=16, colour="ycocg")     # version 21: Y Co Cg
+    blobs, attr_blobs = codec.compress(frames, attributes=rgb, qstep=(16, 32, 32), colour="ycocg")   # coarser chroma
+    blobs, attr_blobs = codec.compress(frames, attributes=rgbi, qstep=(8, 8, 8, 40))         # a step per channel, no transform
+    GeometryCodec.attr_info(attr_blobs[0])       # version 21: "qstep" a tuple of c steps, "colour" "ycocg" or None
+
 Metric frames (include/pcc.h has the rule): float32 points in the caller's unit, from the host or from this codec's
 device, are put on the lattice by the codec, q = rint((x - origin) / voxel) per coordinate in float32; rows without a
 return (NaN / Inf) can be dropped, and the row index says which decoded row every input row became.
@@ -85,7 +95,7 @@ import numpy as np
 import torch
 
 from ._abi import check, PccError, PCC_E_RANGE
-from .runtime import Runtime, _ptr, ATTR_RUN_KINDS, ATTR_TRANSFORM_KIND
+from .runtime import Runtime, _ptr, ATTR_RUN_KINDS, ATTR_TRANSFORM_KINDS
 
 MAX_FRAMES = 65535      # the batch-index range of pcc_morton_keys
 MAX_LOD = 15            # levels of detail 0 .. 15 (csrc/octree2_blob.h)
@@ -100,6 +110,11 @@ def _split(whole, sizes):
     """the rows of a call, frame behind frame -> one view of `whole` per frame"""
     ends = _ends(sizes)
     return [whole[a:b] for a, b in zip(ends[:-1], ends[1:])]
+
+
+class QstepLengthError(ValueError, TypeError):
+    """compress(..., qstep=(..)) with another number of steps than a frame has channels.  A ValueError; also a TypeError,
+    which every sequence qstep raised before sequences had a meaning, so a caller that caught that still does."""
 
 
 class _Front(NamedTuple):
@@ -224,8 +239,9 @@ class GeometryCodec:
         forms 8, 11, 13, 14, or the transform-coded 19), bpv (bytes per value), channels, points, max_error (0: lossless,
         and version 19; a blob without points records none), scalable, lod (the sender's); a cross-channel kind adds
         cross_channel, the tuple of channel indices coded against the channel before them (a plain kind's dict has no
-        such key), version 19 adds qstep (0 in a blob without points).
-        Host only; `attr_blob` may be a prefix of 16 bytes or more."""
+        such key), version 19 adds qstep (0 in a blob without points), version 21 qstep as a tuple of one step per
+        channel and colour, "ycocg" or None (zeros and None in a blob without points).
+        Host only; `attr_blob` may be a prefix of 16 bytes or more (version 21: 16 + 4 channels)."""
         return Runtime.attr_info(bytes(attr_blob))
 
     @staticmethod
@@ -269,6 +285,41 @@ class GeometryCodec:
         return qstep
 
     @staticmethod
+    def _check_colour(qstep, colour, attrs, max_error, scalable, cross):
+        """qstep and colour of compress -> (qstep, steps, colour): steps None and colour 0 for the calls of before (no
+        transform-coded blob, or version 19 with its one integer step); else version 21, steps a list of one step per
+        channel of the widest frame (an integer qstep serves every channel) and colour 0 or 1"""
+        if colour is not None and colour != "ycocg":
+            raise ValueError(f"colour must be None or 'ycocg', got {colour!r}")
+        if isinstance(qstep, (tuple, list)):
+            if any(isinstance(q, bool) or not isinstance(q, (int, np.integer)) for q in qstep):
+                raise TypeError(f"qstep must be an integer >= 0 or a sequence of integers >= 1, one per channel, got {qstep!r}")
+            steps = [int(q) for q in qstep]
+            if attrs is None:
+                raise ValueError("qstep is the quantiser step of transform-coded attributes: it needs attributes=")
+            for f, a in enumerate(attrs):
+                if len(steps) != a.shape[1]:
+                    raise QstepLengthError(f"frame {f}: qstep has {len(steps)} steps, the frame has {a.shape[1]} channels")
+        else:
+            steps = None
+        q = GeometryCodec._check_qstep(qstep if steps is None else 1, attrs, max_error, scalable, cross)      # a sequence: what it refuses beside it
+        if steps is None and colour is None:
+            return q, None, 0
+        if steps is None:
+            if q == 0:
+                raise ValueError("colour='ycocg' is the colour transform of transform-coded attributes: it needs qstep= (the "
+                                 "lossless and bounded kinds have cross_channel= for correlated channels)")
+            steps = [q] * max(a.shape[1] for a in attrs)
+        for f, a in enumerate(attrs):
+            top = (1 << (8 * a.dtype.itemsize - 1)) - 1
+            for ch, sq in enumerate(steps[:a.shape[1]]):
+                if sq < 1 or sq > top:
+                    raise ValueError(f"frame {f}: qstep {sq} of channel {ch} is outside 1 .. {top} for {a.dtype} attributes")
+            if colour is not None and a.shape[1] < 3:
+                raise ValueError(f"frame {f}: colour='ycocg' needs 3 channels (R, G, B), the frame has {a.shape[1]}")
+        return 1, steps, int(colour is not None)
+
+    @staticmethod
     def _check_cross(cross_channel, attrs):
         """cross_channel of compress -> one mask per frame (bit ch - 1: channel ch against ch - 1), or None for False"""
         if cross_channel is False:
@@ -296,7 +347,7 @@ class GeometryCodec:
         return masks
 
     def compress(self, frames, attributes=None, lod=0, scalable=False, *, voxel=None, origin=(0.0, 0.0, 0.0),
-                 invalid="raise", return_index=False, max_error=0, cross_channel=False, qstep=0):
+                 invalid="raise", return_index=False, max_error=0, cross_channel=False, qstep=0, colour=None):
         """frames: a sequence of int16 / int32 [n_f, 3] arrays -> a list of bytes, one version-2 blob per frame.
         Duplicate points are removed (as np.unique), out-of-range coordinates raise PccError (PCC_E_RANGE).
         lod = k > 0: the sender's side of a level of detail — blob f is the version-2 blob of the distinct cells
@@ -328,6 +379,18 @@ class GeometryCodec:
         combines with lod=k (the cells' means over the cells' keys), float32 / device frames, invalid="drop" and
         return_index; decompress reads it at lod 0 only.  The geometry blobs are the same; 0, the default, is the bytes
         of before (attr_info reads q back from a blob).
+        qstep a tuple / list of integers: one step per channel, attribute blob version 21 (include/pcc.h has the rule) —
+        version 19 with a step of its own for every channel, for RGB beside an unrelated fourth channel, or chroma coarser
+        than luma.  A bool or non-integer entry: TypeError; an entry below 1, or 2^(8 bytes per value - 1) and more for
+        a frame's dtype, or a length other than a frame's channel count: ValueError naming the frame.
+        colour="ycocg": version 21 with the luma / chroma transform (YCoCg-R with the low bit of each chroma difference
+        dropped; channels 0, 1, 2 are R, G, B, a fourth is untouched) in front of the lift: an integer qstep then serves
+        every channel and drives Y, Co and Cg where it drove R, G and B.  On recorded camera colour q = 16 with it is
+        shorter and closer than q = 32 without.  Without qstep: ValueError (the lossless and bounded kinds have
+        cross_channel= for this); a frame of fewer than 3 channels: ValueError naming the frame; any other value:
+        ValueError.  Both refuse max_error, scalable=True and cross_channel as qstep does, and combine with lod=k,
+        float32 / device frames, invalid="drop" and return_index as it does.  An integer qstep without colour stays
+        version 19, the bytes of before.
 
         Frame types: numpy int16 / int32 as above, numpy float32, or torch tensors of those three dtypes on the host or
         on this codec's device; all frames of a call integer or all float32, all on the host or all on the device
@@ -359,7 +422,9 @@ class GeometryCodec:
         attrs = None if attributes is None else self._check_attributes(frames, attributes)
         max_error = self._check_max_error(max_error, attrs)
         cross = self._check_cross(cross_channel, attrs)
-        qstep = self._check_qstep(qstep, attrs, max_error, scalable, cross)
+        qstep, steps, colour = self._check_colour(qstep, colour, attrs, max_error, scalable, cross)
+        if steps is not None:      # version 21: the steps travel where the one step did
+            qstep = (steps, colour)
         nb = len(frames)
 
         def result(blobs, attr_blobs=None, index=None):
@@ -498,8 +563,9 @@ class GeometryCodec:
         formats = [a.dtype.itemsize | (a.shape[1] << 8) for a in attrs]
         points = [struct.unpack_from("<I", b, 4)[0] for b in blobs]
         n_kept = front.n_keep if front.n_keep < front.n else None      # None: no row was dropped
+        steps, colour = qstep if isinstance(qstep, tuple) else (qstep, None)      # version 21: (steps, colour)
         return rt.attr_encode_frames(values, offs, formats, _ends(front.sizes), points, front.perm, front.rows, front.n_unique,
-                                     version, front.keys, key_shift, n_kept, max_error, cross, qstep)
+                                     version, front.keys, key_shift, n_kept, max_error, cross, steps, colour)
 
     def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0, *, voxel=None, origin=(0.0, 0.0, 0.0)):
         """version-2 blobs -> a list of int32 [n_f, 3] point sets in Morton order: numpy arrays (output="numpy") or
@@ -511,10 +577,10 @@ class GeometryCodec:
         version 2 (compress(..., scalable=True)), or prefixes of them (attr_lod_info): attributes[f] is [cells, c], row j
         the value of the Morton-first point of cell j.  The kind of every attribute blob (lossless 1 / 2, near-lossless
         4 / 7 of compress(..., max_error=e), their cross-channel forms 8 / 11 / 13 / 14 of compress(...,
-        cross_channel=...), transform-coded 19 of compress(..., qstep=q)) is read from the blob; version 7 behaves as
-        version 2 and its prefixes do, every value within e, and a cross-channel kind returns what its plain kind
-        returns.  The nine kinds may be mixed at lod 0; an attribute blob of version 1, 4, 8, 13 or 19 at lod > 0 raises
-        ValueError naming the frame.
+        cross_channel=...), transform-coded 19 of compress(..., qstep=q) and 21 of compress(..., qstep=(..)) or
+        colour="ycocg") is read from the blob; version 7 behaves as version 2 and its prefixes do, every value within e,
+        and a cross-channel kind returns what its plain kind returns.  The ten kinds may be mixed at lod 0; an attribute
+        blob of version 1, 4, 8, 13, 19 or 21 at lod > 0 raises ValueError naming the frame.
         voxel (with origin): the point sets come back as float32 [n_f, 3] in the caller's unit instead of int32,
         x = origin + t * voxel, one float32 multiplication and then one addition on the device (include/pcc.h has the
         rule): t the lattice index at lod 0 and, at lod k, the centre of the cell's lattice points
@@ -536,9 +602,9 @@ class GeometryCodec:
                 raise ValueError(f"{len(attr_blobs)} attribute blobs for {len(blobs)} geometry blobs")
             kind = [b[1] if len(b) > 1 else 0 for b in attr_blobs]      # runs of one kind are decoded in one call
             v1 = [k in ATTR_RUN_KINDS for k in kind]
-            if lod and ATTR_TRANSFORM_KIND in kind:
-                f = kind.index(ATTR_TRANSFORM_KIND)
-                raise ValueError(f"frame {f}: attributes of blob version {ATTR_TRANSFORM_KIND} cannot be decoded at lod > 0: the weights of "
+            if lod and any(k in ATTR_TRANSFORM_KINDS for k in kind):
+                f = min(kind.index(k) for k in ATTR_TRANSFORM_KINDS if k in kind)
+                raise ValueError(f"frame {f}: attributes of blob version {kind[f]} cannot be decoded at lod > 0: the weights of "
                                  "its transform are the point counts under every node, which a decoder at a cut does not "
                                  "have; store version 2, 7, 11 or 14 (compress(..., scalable=True)) or ship coarse "
                                  "attributes with compress(frames, attributes=..., lod=k, qstep=q)")

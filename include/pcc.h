@@ -1070,6 +1070,73 @@ int pcc_attr_encode_frames_transform(pcc_ctx* ctx, const void* d_values,
                                      int64_t cap, int64_t* h_offsets);
 int pcc_attr_qstep(const uint8_t* h_in, int64_t len, int32_t* h_qstep);
 
+/* Transform-coded attributes with a colour transform and one step per channel:
+ * attribute blob version 21, a tenth kind.  It is version 19 with a colour
+ * word and c steps where version 19 keeps its one q; every lossy image, video
+ * and point-cloud coder decorrelates colour first (luma and two chroma
+ * differences) and gives each channel its own step, G-PCC's RAHT included.
+ *
+ * The rule (tests/attr_colour_ref.py restates it in numpy).  Everything is
+ * version 19's -- keys, sublevels, pairs, weights, the forward and inverse
+ * lift, the mean, the coding order, the entropy stage, the clamp of an index
+ * at H - 1 -- except the following.
+ *   Steps: q[ch] in 1 .. H - 1 for every channel ch < c.  The step of a pair
+ *     in channel ch is s[ch] = max(2, isqrt(floor(q[ch]^2 w / (wa wb)))).
+ *     With all q[ch] equal and no colour transform the indices are exactly
+ *     version 19's; only the head differs.
+ *   Colour transform (colour = 1; frames with c >= 3; channels 0, 1, 2 are R,
+ *     G, B, a fourth channel is untouched).  Applied to the merged values of
+ *     every distinct point after the merge and before the first lift.  All
+ *     arithmetic on signed integers, >> the arithmetic shift (floor),
+ *     H = 2^(8 bpv - 1), mask = 2 H - 1:
+ *       co = R - B;  t = B + (co >> 1);  cg = G - t;  y = t + (cg >> 1)
+ *       Y = y,  Co = (co >> 1) + H,  Cg = (cg >> 1) + H
+ *     all three in 0 .. mask: YCoCg-R with the low bit of each chroma
+ *     difference dropped, so the values fit the value width, a node's value
+ *     stays a uint16 in the lift and the index clamp stays as it is.
+ *   Inverse, applied to the inverse lift's output after its clamp to
+ *     0 .. mask, then clamped again per channel:
+ *       co' = 2 (Co - H);  cg' = 2 (Cg - H);  t = Y - (cg' >> 1)
+ *       G = cg' + t;  B = t - (co' >> 1);  R = B + co'
+ *     Without quantisation the round trip moves no channel by more than 1.
+ *     For bpv = 1: (255, 255, 255) -> (255, 128, 128) -> (255, 255, 255);
+ *     (255, 0, 0) -> (63, 255, 64) -> (254, 0, 0), G = -1 before the clamp;
+ *     (0, 255, 0) -> (127, 128, 255); (0, 0, 255) -> (63, 0, 64).
+ *   Layout: 'A' 21 (bpv | slod << 4) c | u32 n | u32 payload_len | u32 colour |
+ *     u32 q[c] | u32 S | u32 n_chunks | u16 p0[nctx] | u32 words[n_chunks] |
+ *     chunk payloads.  colour: 0 none, 1 the transform above; anything else,
+ *     and 1 with c < 3, is PCC_E_STREAM.  n = 0: the 12-byte head alone, which
+ *     records neither colour nor steps.  Byte 21 keeps the odd parity of the
+ *     nine other version bytes.
+ *   _encode_frames_transform2 : the arguments of
+ *     pcc_attr_encode_frames_transform with h_qstep[4], colour in place of
+ *     qstep; a frame reads its first c entries.  A step < 1, or >= H for a
+ *     frame's format: PCC_E_ARG naming the frame; so is colour outside {0, 1},
+ *     and colour = 1 with a frame of fewer than 3 channels.  Launches: version
+ *     19's, and with colour = 1 one elementwise pass between the merge and the
+ *     coding order.
+ *   pcc_attr_decode_frames_lod with lod = 0 reads version 21 (one version per
+ *     call; lod > 0: PCC_E_ARG): version 19's launches, the last of them the
+ *     inverse colour store where a frame of the call has colour = 1.
+ *   pcc_attr_info reports version 21 as it reports 19, from the blob or a
+ *     prefix that reaches q[c - 1] (16 + 4 c bytes).  pcc_attr_transform_info:
+ *     host only, the colour word and the steps of such a head (h_qstep[ch] = 0
+ *     for ch >= c); 0s for every other kind and for a blob without points.
+ *     pcc_attr_qstep stays as it is: 0 for version 21.
+ *   pcc_attr_lod_info refuses version 21 as it refuses 19: PCC_E_ARG. */
+int pcc_attr_encode_frames_transform2(pcc_ctx* ctx, const void* d_values,
+                                      const int64_t* h_value_offsets,
+                                      const int32_t* h_format, const int64_t* h_rows,
+                                      const int64_t* h_points, int n_frames,
+                                      const uint32_t* d_perm,
+                                      const uint32_t* d_run_starts, int64_t n_unique,
+                                      int64_t n_kept, const uint64_t* d_keys,
+                                      int key_shift, const int32_t h_qstep[4],
+                                      int colour, uint8_t* h_out, int64_t cap,
+                                      int64_t* h_offsets);
+int pcc_attr_transform_info(const uint8_t* h_in, int64_t len, int32_t* h_colour,
+                            int32_t h_qstep[4]);
+
 /* ---- exact nearest neighbours on the lattice: the D1 metric (csrc/nn.hip, the walk in csrc/nn_cells.h) -- */
 
 /* The rule (tests/nn_ref.py restates it in numpy).  For a frame f there are
