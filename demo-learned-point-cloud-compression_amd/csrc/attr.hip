@@ -57,8 +57,10 @@
 // k_at_lift<false, const int32_t*>, and k_ac_store in place of k_at_store where a frame of the call has colour = 1.
 // tests/attr_colour_ref.py restates the kind in numpy.
 //
-// Host side: the kinds share one encode sequence (a_encode_frames) and the helpers of the two decoders; DESIGN.md,
-// "attr.hip: one encode path, shared decode helpers".
+// Host side: the kinds share one encode sequence (a_encode_frames over an AEncKind, the entry point's kind resolved
+// once) and one decode-call skeleton (ADecCall: accounting, rows, layout, upload, status) under the three decoders, each
+// of which keeps its parser, its side tables, its arena arrays and its kernels; DESIGN.md, "attr.hip: one encode path,
+// shared decode helpers" and "attr.hip: the host code of kinds 8 to 21, folded".
 #include "common.h"
 #include "lanerans.h"
 #include "attr_blob.h"
@@ -1248,6 +1250,19 @@ __global__ __launch_bounds__(256) void k_ac_store(const ADFrame* __restrict__ ta
 static inline int64_t a_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 static inline size_t merged_b_of(int64_t vals) { return pcc_align((size_t)vals * 2); }
 
+// sub-tables behind one another in one upload, each on pcc_align's boundary: add(b) = where a table of b bytes starts
+// (b = 0: a table the call does not have, which takes no room).  bytes: all of them, padded; end: where the last table
+// with data ends, the bytes an upload of the tables alone has to carry
+struct ATables {
+  size_t bytes = 0, end = 0;
+  size_t add(size_t b) {
+    const size_t at = bytes;
+    if (b) end = at + b;
+    bytes += pcc_align(b);
+    return at;
+  }
+};
+
 // version 19, what encoder and decoder share: the order stage over the call's keys (src: the encoder's distinct sorted
 // keys, or the decoder's cells, whose keys go to keys_out), then the sublevels' starts and counts read back into h_bins
 // (pinned; 98 per frame) behind one synchronisation.  grid[t] = the blocks of k_at_lift at sublevel t: 0 where no frame
@@ -1276,12 +1291,27 @@ static int a_t_order(hipStream_t st, bool from_cells, const void* src, uint64_t*
   return PCC_OK;
 }
 
+// one sublevel of the lift over all frames of a call: forward (ENC; etab, merged, idx) or inverse (dtab, x, val,
+// status).  d_aux (version 21): the frames' steps and colour words; the lift then takes a step per channel from it
+template <bool ENC>
+static int a_launch_lift(hipStream_t st, unsigned blocks, int nf, const uint64_t* keys, const A2Order* d_ord, const uint32_t* bins,
+                         const uint32_t* inv, int t, const AFrame* etab, uint16_t* merged, uint16_t* idx, const ADFrame* dtab,
+                         const uint8_t* x, int64_t* val, int32_t* status, const int32_t* d_aux) {
+  if (d_aux)
+    hipLaunchKernelGGL((k_at_lift<ENC, const int32_t*>), dim3(blocks, (unsigned)nf), dim3(256), 0, st, keys, d_ord, bins, inv, t, etab, merged,
+                       idx, dtab, x, val, status, d_aux);
+  else
+    hipLaunchKernelGGL(k_at_lift<ENC>, dim3(blocks, (unsigned)nf), dim3(256), 0, st, keys, d_ord, bins, inv, t, etab, merged, idx, dtab, x, val,
+                       status);
+  PCC_CHECK_LAUNCH();
+  return PCC_OK;
+}
+
 // version 19, encoder, behind k_a_merge: the order stage, one k_at_lift<true> per occupied sublevel bottom-up over the
-// merged values in place, and the mean; idx then holds x in coding order where the PRED = false coder reads it.
-// d_aux (version 21): the frames' steps and colour words; the lift takes a step per channel from it
+// merged values in place, and the mean; idx then holds x in coding order where the PRED = false coder reads it
 static int a_t_forward(pcc_ctx* ctx, hipStream_t st, const uint64_t* d_keys, const A2Order* d_ord, const AFrame* d_tab, int nf,
                        int64_t blocks, size_t pk_b, size_t hist_b, size_t bins_b, size_t link_b, uint16_t* merged,
-                       uint16_t* idx, uint32_t* h_bins, const int32_t* d_aux = nullptr) {
+                       uint16_t* idx, uint32_t* h_bins, const int32_t* d_aux) {
   uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, pk_b);
   uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, hist_b);
   uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, bins_b);
@@ -1289,53 +1319,71 @@ static int a_t_forward(pcc_ctx* ctx, hipStream_t st, const uint64_t* d_keys, con
   if (!packed || !hist || !bins || !inv) return PCC_E_NOMEM;
   unsigned grid[kATBins];
   PCC_TRY(a_t_order(st, false, (const void*)d_keys, nullptr, d_ord, nf, blocks, packed, hist, bins, inv, h_bins, grid));
-  for (int t = 0; t < kATBins - 1; ++t) {
-    if (!grid[t]) continue;
-    if (d_aux)
-      hipLaunchKernelGGL((k_at_lift<true, const int32_t*>), dim3(grid[t], (unsigned)nf), dim3(256), 0, st, d_keys, d_ord, (const uint32_t*)bins,
-                         (const uint32_t*)inv, t, d_tab, merged, idx, (const ADFrame*)nullptr, (const uint8_t*)nullptr, (int64_t*)nullptr,
-                         (int32_t*)nullptr, d_aux);
-    else
-      hipLaunchKernelGGL(k_at_lift<true>, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, d_keys, d_ord, (const uint32_t*)bins,
-                         (const uint32_t*)inv, t, d_tab, merged, idx, (const ADFrame*)nullptr, (const uint8_t*)nullptr, (int64_t*)nullptr,
-                         (int32_t*)nullptr);
-    PCC_CHECK_LAUNCH();
-  }
+  for (int t = 0; t < kATBins - 1; ++t)
+    if (grid[t])
+      PCC_TRY(a_launch_lift<true>(st, grid[t], nf, d_keys, d_ord, bins, inv, t, d_tab, merged, idx, nullptr, nullptr, nullptr, nullptr, d_aux));
   hipLaunchKernelGGL(k_at_mean, dim3(nblk(4 * (int64_t)nf, 256)), dim3(256), 0, st, d_tab, nf, (const uint16_t*)merged, idx);
   PCC_CHECK_LAUNCH();
   return PCC_OK;
 }
 
 // ======================================================================== C-ABI (include/pcc.h)
-// both versions' encoder: version 2 codes, instead of the merged values, their residuals in introduction order
-// (k_a2_size / k_a2_scan / k_a2_place over d_keys, the call's distinct sorted keys).  max_error > 0: the near-lossless
-// kind of that version (4 for 1, 7 for 2), the indices of k_a4_quant / k_a7_quant through the PRED = false coder.
-// h_cross: per frame the cross-channel mask m (0: the frame's plain kind); a call with any m != 0 among its frames with
-// points runs k_ax_fwd in front of the coder and codes every frame with PRED = false
-static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
+// what an encode entry point asks for, resolved once.  The table of kinds (attr_blob.h):
+//   version   v2  nl  tr  tc   e           between k_a_merge and the coder
+//   1                          0           nothing (the coder predicts inside the run)
+//   2         x                0           order stage, residuals against first()
+//   4             x            max_error   k_a4_quant
+//   7         x   x            max_error   order stage (kept), k_a7_quant
+//   19            x   x        qstep       [k_ac_fwd,] order stage at bit granularity, lift, mean (a_t_forward)
+//   21            x   x   x    1 (unread)  as 19, the steps and the colour word in the aux table
+// nl: an index stream with one u32 (e, q, or the colour word) directly behind payload_len, so versions 19 and 21 run as
+// version 4 does with a_t_forward in place of k_a4_quant.  A frame with a mask in h_cross is coded as the cross form
+// of the call's version (8, 11, 13, 14)
+struct AEncKind {
+  int version;               // the version byte of a frame without a mask
+  bool v2, nl, tr, tc;
+  int e;                     // AFrame::e
+  int64_t n_kept;            // >= 0 (pcc_attr_encode_frames_kept): the sorted keys behind it belong to dropped rows; -1: none dropped
+  const int32_t* h_cross;    // per frame the cross-channel mask m (0: the frame's plain kind), or nullptr
+  const int32_t* h_qsteps;   // version 21: q[4]
+  int colour;                // version 21: 0 | 1
+  bool keyed() const { return v2 || tr; }   // d_keys and key_shift are read
+};
+static AEncKind a_kind_plain(int version, int64_t n_kept, int max_error, const int32_t* h_cross) {
+  const bool v2 = version == 2, nl = max_error > 0;
+  return AEncKind{attr_version(v2, nl, false), v2, nl, false, false, max_error, n_kept, h_cross, nullptr, 0};
+}
+static AEncKind a_kind_transform(int64_t n_kept, int qstep, const int32_t* h_qsteps, int colour) {
+  const bool tc = h_qsteps != nullptr;
+  return AEncKind{tc ? kAttrCVersion : kAttrTVersion, false, true, true, tc, tc ? 1 : qstep, n_kept, nullptr, h_qsteps, colour};
+}
+
+// bytes of a blob in front of its chunk payloads: the kind's head, p0 and the chunk table
+static int64_t a_head_bytes(const AEncKind& k, int c, int nctx, int64_t nc) {
+  const int64_t head = k.tc ? attr_c_head(c) : (k.tr ? kAttrTHead : (k.v2 ? kAttr2Head : kAttrHead + 8) + (k.nl ? 4 : 0));
+  return head + 2 * nctx + 4 * nc;
+}
+
+// the template arguments of a kind's coder: k_a_stats / k_a_enc<PRED>, k_a_pack<V2, NL, XC[, TR[, const int32_t*]]>
+template <bool V2_, bool NL_, bool XC_, bool TR_ = false, bool TC_ = false>
+struct ACoder {
+  static constexpr bool V2 = V2_, NL = NL_, XC = XC_, TR = TR_, TC = TC_;
+  static constexpr bool PRED = !V2 && !NL && !XC;   // only version 1 predicts inside the run, and not beside cross-channel frames
+};
+
+// the encoder of every kind: k_a_merge, the kind's passes of the table above, k_ax_fwd in a call with any m != 0 among
+// its frames with points (every frame is then coded with PRED = false), counting pass, coder, blobs
+static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
                            const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
                            const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys,
-                           int key_shift, uint8_t* h_out, int64_t cap, int64_t* h_offsets, int64_t n_kept = -1,
-                           int max_error = 0, const int32_t* h_cross = nullptr, int qstep = 0, const int32_t* h_qsteps = nullptr,
-                           int colour = 0) {
-  // qstep > 0: version 19.  Its head is version 4's with q where e stands (and the slod nibble), so it runs as that
-  // kind does (nl, r.e = q) with the order stage and the lifting passes in place of k_a4_quant.  h_qsteps: version 21,
-  // which runs as version 19 does (r.e = 1, which nothing reads) with a frame's steps and colour word in a table of
-  // their own (aux: 5 words per frame), k_ac_fwd behind the merge where colour = 1, and a longer head
-  const bool tc = h_qsteps != nullptr;
-  if (tc) qstep = 1;
-  const bool tr = qstep > 0;
-  if (tr) max_error = qstep;
-  const bool v2 = version == 2 && !tr, nl = max_error > 0, keyed = v2 || tr;
-  const int blob_version = tc ? kAttrCVersion : (tr ? kAttrTVersion : (nl ? (v2 ? 7 : 4) : version));
+                           int key_shift, uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
+  const bool v2 = k.v2, nl = k.nl, tr = k.tr, tc = k.tc, keyed = k.keyed(), drops = k.n_kept >= 0;
   PCC_REQUIRE(ctx && h_value_offsets && h_format && h_rows && h_points && h_out && h_offsets && n_frames >= 1 &&
                   n_frames <= 65535 && n_unique >= 0 && cap >= 0,
               PCC_E_ARG, "%s: bad argument (n_frames=%d)", who, n_frames);
-  // n_kept (pcc_attr_encode_frames_kept): the sorted keys behind it belong to dropped rows, which no run may reach
-  const bool drops = n_kept >= 0;
-  PCC_REQUIRE(!drops || n_kept <= h_rows[n_frames], PCC_E_ARG, "%s: %lld kept rows of %lld", who, (long long)n_kept,
+  PCC_REQUIRE(!drops || k.n_kept <= h_rows[n_frames], PCC_E_ARG, "%s: %lld kept rows of %lld", who, (long long)k.n_kept,
               (long long)h_rows[n_frames]);
-  const int64_t n_keys = drops ? n_kept : h_rows[n_frames];
+  const int64_t n_keys = drops ? k.n_kept : h_rows[n_frames];   // no run may reach a dropped row's key
   PCC_REQUIRE(h_rows[0] == 0 && h_rows[n_frames] < ((int64_t)1 << 27) && n_unique <= n_keys &&
                   (n_keys == 0 || (d_values && d_perm && d_run_starts)),
               PCC_E_ARG, "%s: %lld rows, %lld points", who, (long long)n_keys, (long long)n_unique);
@@ -1358,30 +1406,30 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     PCC_REQUIRE(rows >= 0 && n >= 0 && n <= rows && ((n == 0) == (rows == 0) || (drops && n == 0)) &&
                     h_value_offsets[f] >= 0, PCC_E_ARG,
                 "%s: frame %d: %lld rows, %lld points", who, f, (long long)rows, (long long)n);
-    PCC_REQUIRE(!nl || tc || (uint32_t)max_error <= attr_max_error(bpv), PCC_E_ARG,
-                "%s: frame %d: %s %d with %d bytes per value (at most %u)", who, f, tr ? "qstep" : "max_error", max_error, bpv,
+    PCC_REQUIRE(!nl || tc || (uint32_t)k.e <= attr_max_error(bpv), PCC_E_ARG,
+                "%s: frame %d: %s %d with %d bytes per value (at most %u)", who, f, tr ? "qstep" : "max_error", k.e, bpv,
                 attr_max_error(bpv));
     if (tc) {
       for (int ch = 0; ch < c; ++ch)
-        PCC_REQUIRE(h_qsteps[ch] >= 1 && (uint32_t)h_qsteps[ch] <= attr_max_error(bpv), PCC_E_ARG,
-                    "%s: frame %d: qstep %d of channel %d with %d bytes per value (1 .. %u)", who, f, h_qsteps[ch], ch, bpv,
+        PCC_REQUIRE(k.h_qsteps[ch] >= 1 && (uint32_t)k.h_qsteps[ch] <= attr_max_error(bpv), PCC_E_ARG,
+                    "%s: frame %d: qstep %d of channel %d with %d bytes per value (1 .. %u)", who, f, k.h_qsteps[ch], ch, bpv,
                     attr_max_error(bpv));
-      PCC_REQUIRE(!colour || c >= 3, PCC_E_ARG, "%s: frame %d: the colour transform needs 3 channels, the frame has %d", who, f, c);
+      PCC_REQUIRE(!k.colour || c >= 3, PCC_E_ARG, "%s: frame %d: the colour transform needs 3 channels, the frame has %d", who, f, c);
     }
-    const int32_t m = h_cross ? h_cross[f] : 0;
+    const int32_t m = k.h_cross ? k.h_cross[f] : 0;
     PCC_REQUIRE(m >= 0 && m < (1 << (c - 1)), PCC_E_ARG, "%s: frame %d: cross-channel mask %d with %d channels", who, f, m, c);
     if (n == 0) continue;
     cross.push_back(m);
     xc |= m != 0;
     if (tc) {
-      for (int ch = 0; ch < 4; ++ch) aux.push_back(ch < c ? h_qsteps[ch] : 0);
-      aux.push_back(colour);
+      for (int ch = 0; ch < 4; ++ch) aux.push_back(ch < c ? k.h_qsteps[ch] : 0);
+      aux.push_back(k.colour);
     }
     n_max = std::max(n_max, n);
     AFrame r;
     int64_t S, nc;
     attr_layout(n, c, &S, &nc);
-    r.e = max_error;
+    r.e = k.e;
     r.in_off = h_value_offsets[f];
     r.row0 = h_rows[f];
     r.rows = rows;
@@ -1394,9 +1442,8 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     r.nctx = attr_contexts(bpv, c);
     r.ctx_off = (int32_t)ctxs;
     r.T = (int32_t)(S * c * attr_positions(bpv));
-    const int64_t head = (v2 ? kAttr2Head : kAttrHead + 8) + (nl ? 4 : 0) + (tc ? 4 * c : 0) + 2 * r.nctx + 4 * nc;
     // a coded decision emits at most one word: the bound follows the frame's decisions, not its chunks' regions
-    r.out_cap = head + 2 * (3 * kLanes * nc + std::min<int64_t>(nc * kLanes * r.T, (int64_t)attr_positions(bpv) * c * n));
+    r.out_cap = a_head_bytes(k, c, r.nctx, nc) + 2 * (3 * kLanes * nc + std::min<int64_t>(nc * kLanes * r.T, (int64_t)attr_positions(bpv) * c * n));
     r.out_off = out_bytes;
     r.S = (int32_t)S;
     r.nc = (int32_t)nc;
@@ -1425,11 +1472,11 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
   std::vector<int64_t> off_of((size_t)n_frames, -1);
   hipStream_t st = ctx->stream;
   if (nf > 0) {
-    const size_t ord_b = keyed ? pcc_align((size_t)nf * sizeof(A2Order)) : 0;
     // the rows | the masks (a call with cross-channel frames) | steps and colour (version 21) | the order rows
-    const size_t fr_b = pcc_align((size_t)nf * sizeof(AFrame)), cross_b = xc ? pcc_align((size_t)nf * 4) : 0;
-    const size_t aux_b = tc ? pcc_align((size_t)nf * 20) : 0;
-    const size_t tab_b = fr_b + cross_b + aux_b + ord_b;
+    ATables lay;
+    lay.add((size_t)nf * sizeof(AFrame));
+    const size_t cross_at = lay.add(xc ? (size_t)nf * 4 : 0), aux_at = lay.add(tc ? (size_t)nf * 20 : 0);
+    const size_t ord_at = lay.add(keyed ? (size_t)nf * sizeof(A2Order) : 0), tab_b = lay.bytes;
     const size_t merged_b = merged_b_of(vals), cnt_b = pcc_align((size_t)ctxs * 8), p0_b = pcc_align((size_t)ctxs * 2);
     const size_t rec_b = pcc_align((size_t)rec_words * 2), small_b = pcc_align((size_t)chunks * (4 + 2 * kLanes * 2 + kLanes * 2));
     // the order stage's (versions 2 and 7): packed | hist | 17 bin bases, then 16 counts per frame; rank, first (7)
@@ -1457,23 +1504,21 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     uint32_t* words = (uint32_t*)small;
     uint16_t* states = (uint16_t*)(small + (size_t)chunks * 4);
     uint16_t* lens_d = states + (size_t)chunks * 2 * kLanes;
-    const A2Order* d_ord = (const A2Order*)((const uint8_t*)d_tab + tab_b - ord_b);
-    const int32_t* d_cross = xc ? (const int32_t*)((const uint8_t*)d_tab + fr_b) : nullptr;
-    const int32_t* d_aux = tc ? (const int32_t*)((const uint8_t*)d_tab + fr_b + cross_b) : nullptr;
+    const A2Order* d_ord = (const A2Order*)((const uint8_t*)d_tab + ord_at);
+    const int32_t* d_cross = xc ? (const int32_t*)((const uint8_t*)d_tab + cross_at) : nullptr;
+    const int32_t* d_aux = tc ? (const int32_t*)((const uint8_t*)d_tab + aux_at) : nullptr;
     // staging: the table on its way to the device | the blobs | their lengths
     const size_t lens_at = tab_b + (size_t)out_bytes;
     const size_t tcnt_at = lens_at + (size_t)nf * 8 + 64;   // version 19: the sublevels' starts and counts, read back
     PCC_TRY(o2_stage_reserve(ctx, tcnt_at + (tr ? (size_t)nf * 2 * kATBins * 4 : 0) + 64));
     uint8_t* stage = (uint8_t*)ctx->stage;
     memcpy(stage, tab.data(), (size_t)nf * sizeof(AFrame));
-    if (xc) memcpy(stage + fr_b, cross.data(), (size_t)nf * 4);
-    if (tc) memcpy(stage + fr_b + cross_b, aux.data(), (size_t)nf * 20);
-    if (keyed) memcpy(stage + tab_b - ord_b, order.data(), (size_t)nf * sizeof(A2Order));
+    if (xc) memcpy(stage + cross_at, cross.data(), (size_t)nf * 4);
+    if (tc) memcpy(stage + aux_at, aux.data(), (size_t)nf * 20);
+    if (keyed) memcpy(stage + ord_at, order.data(), (size_t)nf * sizeof(A2Order));
     long long* len_dev = (long long*)(stage + lens_at);
     PccProfScope prof(ctx, "attr_encode", u, nf, chunks, 0);
-    PCC_HIP(hipMemcpyAsync(d_tab, stage,
-                           keyed ? tab_b - ord_b + (size_t)nf * sizeof(A2Order) : (xc ? fr_b + (size_t)nf * 4 : (size_t)nf * sizeof(AFrame)),
-                           hipMemcpyHostToDevice, st));
+    PCC_HIP(hipMemcpyAsync(d_tab, stage, lay.end, hipMemcpyHostToDevice, st));
     PCC_HIP(hipMemsetAsync(cnt, 0, (size_t)ctxs * 8, st));
     hipLaunchKernelGGL(k_a_merge, dim3((unsigned)merge_blocks), dim3(256), 0, st, (const uint8_t*)d_values, (const AFrame*)d_tab, nf,
                        d_perm, d_run_starts, n_unique, n_keys, merged);
@@ -1505,7 +1550,7 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     };
     if (v2) PCC_TRY(a_order_stage(nl));
     if (tr) {
-      if (tc && colour) {
+      if (tc && k.colour) {
         hipLaunchKernelGGL(k_ac_fwd, dim3(nblk(n_max, 256), (unsigned)nf), dim3(256), 0, st, (const AFrame*)d_tab, d_aux, merged);
         PCC_CHECK_LAUNCH();
       }
@@ -1526,12 +1571,11 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
                          (const uint16_t*)merged, src);
       PCC_CHECK_LAUNCH();
     }
-    // counting pass, coder, blobs: only version 1 predicts inside the run (PRED), and not beside cross-channel frames
+    // counting pass, coder, blobs
     const size_t lds = 4096 * 4 + (size_t)(nctx_max + 1) * kLanes * 2;   // <= 98 KB (c = 4, uint16)
-    auto a_code = [&](auto v2c, auto nlc, auto xcc, auto trc, auto tcc) -> int {
-      constexpr bool V2 = decltype(v2c)::value, NL = decltype(nlc)::value, XC = decltype(xcc)::value, TR = decltype(trc)::value;
-      constexpr bool TC = decltype(tcc)::value;
-      constexpr bool PRED = !V2 && !NL && !XC;
+    auto a_code = [&](auto coder) -> int {
+      using K = decltype(coder);
+      constexpr bool V2 = K::V2, NL = K::NL, XC = K::XC, TR = K::TR, TC = K::TC, PRED = K::PRED;
       hipLaunchKernelGGL(k_a_stats<PRED>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)src, (const AFrame*)d_tab, nf, cnt);
       PCC_CHECK_LAUNCH();
       PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<PRED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1550,17 +1594,28 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
       PCC_CHECK_LAUNCH();
       return PCC_OK;
     };
-    using Yes = std::true_type;
-    using No = std::false_type;
-    auto a_kind = [&](auto v2c, auto nlc) -> int { return xc ? a_code(v2c, nlc, Yes{}, No{}, No{}) : a_code(v2c, nlc, No{}, No{}, No{}); };
-    PCC_TRY(tc ? a_code(No{}, Yes{}, No{}, Yes{}, Yes{}) : tr ? a_code(No{}, Yes{}, No{}, Yes{}, No{}) : v2 ? (nl ? a_kind(Yes{}, Yes{}) : a_kind(Yes{}, No{})) : (nl ? a_kind(No{}, Yes{}) : a_kind(No{}, No{})));
+    // by the version byte of the call's frames with a mask, where it has any, else of its plain frames
+    int rc = PCC_E_ARG;
+    switch (xc ? attr_version(v2, nl, true) : k.version) {   //   V2     NL     XC     TR    TC
+      case 1: rc = a_code(ACoder<false, false, false>{}); break;
+      case 2: rc = a_code(ACoder<true, false, false>{}); break;
+      case 4: rc = a_code(ACoder<false, true, false>{}); break;
+      case 7: rc = a_code(ACoder<true, true, false>{}); break;
+      case 8: rc = a_code(ACoder<false, false, true>{}); break;
+      case 11: rc = a_code(ACoder<true, false, true>{}); break;
+      case 13: rc = a_code(ACoder<false, true, true>{}); break;
+      case 14: rc = a_code(ACoder<true, true, true>{}); break;
+      case kAttrTVersion: rc = a_code(ACoder<false, true, false, true>{}); break;
+      case kAttrCVersion: rc = a_code(ACoder<false, true, false, true, true>{}); break;
+    }
+    PCC_TRY(rc);
     PCC_HIP(hipStreamSynchronize(st));
-    for (int k = 0; k < nf; ++k) {
-      const long long total = ((volatile long long*)len_dev)[k];
-      PCC_REQUIRE(total >= 0 && total <= tab[(size_t)k].out_cap, PCC_E_NOMEM,
-                  "%s: frame %d: blob beyond its bound", who, frame_of[(size_t)k]);
-      len_of[(size_t)frame_of[(size_t)k]] = total;
-      off_of[(size_t)frame_of[(size_t)k]] = (int64_t)tab_b + tab[(size_t)k].out_off;
+    for (int i = 0; i < nf; ++i) {
+      const long long total = ((volatile long long*)len_dev)[i];
+      PCC_REQUIRE(total >= 0 && total <= tab[(size_t)i].out_cap, PCC_E_NOMEM,
+                  "%s: frame %d: blob beyond its bound", who, frame_of[(size_t)i]);
+      len_of[(size_t)frame_of[(size_t)i]] = total;
+      off_of[(size_t)frame_of[(size_t)i]] = (int64_t)tab_b + tab[(size_t)i].out_off;
     }
   }
   int64_t total = 0;
@@ -1573,10 +1628,10 @@ static int a_encode_frames(const char* who, int version, pcc_ctx* ctx, const voi
     if (off_of[(size_t)f] >= 0) {
       memcpy(dst, (const uint8_t*)ctx->stage + off_of[(size_t)f], (size_t)len_of[(size_t)f]);
     } else {   // no points: the 12-byte empty blob
-      const int32_t m = h_cross ? h_cross[f] : 0;
+      const int32_t m = k.h_cross ? k.h_cross[f] : 0;
       memset(dst, 0, kAttrHead);
       dst[0] = 'A';
-      dst[1] = (uint8_t)(m ? attr_version(v2, nl, true) : blob_version);
+      dst[1] = (uint8_t)(m ? attr_version(v2, nl, true) : k.version);
       dst[2] = (uint8_t)((h_format[f] & 0xFF) | (keyed ? (key_shift / 3) << 4 : 0));
       dst[3] = (uint8_t)((h_format[f] >> 8) | (m << 4));
     }
@@ -1589,16 +1644,16 @@ extern "C" int pcc_attr_encode_frames(pcc_ctx* ctx, const void* d_values, const 
                                       const int64_t* h_rows, const int64_t* h_points, int n_frames, const uint32_t* d_perm,
                                       const uint32_t* d_run_starts, int64_t n_unique, uint8_t* h_out, int64_t cap,
                                       int64_t* h_offsets) {
-  return a_encode_frames("pcc_attr_encode_frames", 1, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm,
-                         d_run_starts, n_unique, nullptr, 0, h_out, cap, h_offsets);
+  return a_encode_frames("pcc_attr_encode_frames", a_kind_plain(1, -1, 0, nullptr), ctx, d_values, h_value_offsets, h_format, h_rows,
+                         h_points, n_frames, d_perm, d_run_starts, n_unique, nullptr, 0, h_out, cap, h_offsets);
 }
 
 extern "C" int pcc_attr_encode_frames_v2(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets, const int32_t* h_format,
                                          const int64_t* h_rows, const int64_t* h_points, int n_frames, const uint32_t* d_perm,
                                          const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys, int key_shift,
                                          uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
-  return a_encode_frames("pcc_attr_encode_frames_v2", 2, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm,
-                         d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets);
+  return a_encode_frames("pcc_attr_encode_frames_v2", a_kind_plain(2, -1, 0, nullptr), ctx, d_values, h_value_offsets, h_format, h_rows,
+                         h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets);
 }
 
 extern "C" int pcc_attr_encode_frames_kept(pcc_ctx* ctx, int version, const void* d_values, const int64_t* h_value_offsets,
@@ -1608,9 +1663,9 @@ extern "C" int pcc_attr_encode_frames_kept(pcc_ctx* ctx, int version, const void
                                            int64_t* h_offsets) {
   PCC_REQUIRE((version == 1 || version == 2) && n_kept >= 0, PCC_E_ARG,
               "pcc_attr_encode_frames_kept: bad argument (version=%d n_kept=%lld)", version, (long long)n_kept);
-  return a_encode_frames("pcc_attr_encode_frames_kept", version, ctx, d_values, h_value_offsets, h_format, h_rows, h_points,
-                         n_frames, d_perm, d_run_starts, n_unique, version == 2 ? d_keys : nullptr, version == 2 ? key_shift : 0,
-                         h_out, cap, h_offsets, n_kept);
+  return a_encode_frames("pcc_attr_encode_frames_kept", a_kind_plain(version, n_kept, 0, nullptr), ctx, d_values, h_value_offsets, h_format,
+                         h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, version == 2 ? d_keys : nullptr,
+                         version == 2 ? key_shift : 0, h_out, cap, h_offsets);
 }
 
 extern "C" int pcc_attr_encode_frames_nl(pcc_ctx* ctx, int version, const void* d_values, const int64_t* h_value_offsets,
@@ -1620,9 +1675,9 @@ extern "C" int pcc_attr_encode_frames_nl(pcc_ctx* ctx, int version, const void* 
                                          int64_t* h_offsets) {
   PCC_REQUIRE((version == 1 || version == 2) && n_kept >= -1 && max_error >= 0, PCC_E_ARG,
               "pcc_attr_encode_frames_nl: bad argument (version=%d n_kept=%lld max_error=%d)", version, (long long)n_kept, max_error);
-  return a_encode_frames("pcc_attr_encode_frames_nl", version, ctx, d_values, h_value_offsets, h_format, h_rows, h_points,
-                         n_frames, d_perm, d_run_starts, n_unique, version == 2 ? d_keys : nullptr, version == 2 ? key_shift : 0,
-                         h_out, cap, h_offsets, n_kept, max_error);
+  return a_encode_frames("pcc_attr_encode_frames_nl", a_kind_plain(version, n_kept, max_error, nullptr), ctx, d_values, h_value_offsets,
+                         h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, version == 2 ? d_keys : nullptr,
+                         version == 2 ? key_shift : 0, h_out, cap, h_offsets);
 }
 
 extern "C" int pcc_attr_encode_frames_cross(pcc_ctx* ctx, int version, const void* d_values, const int64_t* h_value_offsets,
@@ -1632,9 +1687,9 @@ extern "C" int pcc_attr_encode_frames_cross(pcc_ctx* ctx, int version, const voi
                                             uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
   PCC_REQUIRE((version == 1 || version == 2) && n_kept >= -1 && max_error >= 0 && h_cross, PCC_E_ARG,
               "pcc_attr_encode_frames_cross: bad argument (version=%d n_kept=%lld max_error=%d)", version, (long long)n_kept, max_error);
-  return a_encode_frames("pcc_attr_encode_frames_cross", version, ctx, d_values, h_value_offsets, h_format, h_rows, h_points,
-                         n_frames, d_perm, d_run_starts, n_unique, version == 2 ? d_keys : nullptr, version == 2 ? key_shift : 0,
-                         h_out, cap, h_offsets, n_kept, max_error, h_cross);
+  return a_encode_frames("pcc_attr_encode_frames_cross", a_kind_plain(version, n_kept, max_error, h_cross), ctx, d_values, h_value_offsets,
+                         h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, version == 2 ? d_keys : nullptr,
+                         version == 2 ? key_shift : 0, h_out, cap, h_offsets);
 }
 
 extern "C" int pcc_attr_encode_frames_transform(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
@@ -1644,8 +1699,8 @@ extern "C" int pcc_attr_encode_frames_transform(pcc_ctx* ctx, const void* d_valu
                                                 int64_t* h_offsets) {
   PCC_REQUIRE(n_kept >= -1 && qstep >= 1, PCC_E_ARG, "pcc_attr_encode_frames_transform: bad argument (n_kept=%lld qstep=%d)",
               (long long)n_kept, qstep);
-  return a_encode_frames("pcc_attr_encode_frames_transform", 2, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames,
-                         d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets, n_kept, 0, nullptr, qstep);
+  return a_encode_frames("pcc_attr_encode_frames_transform", a_kind_transform(n_kept, qstep, nullptr, 0), ctx, d_values, h_value_offsets,
+                         h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets);
 }
 
 extern "C" int pcc_attr_encode_frames_transform2(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
@@ -1655,8 +1710,8 @@ extern "C" int pcc_attr_encode_frames_transform2(pcc_ctx* ctx, const void* d_val
                                                  uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
   PCC_REQUIRE(n_kept >= -1 && h_qstep && (colour == 0 || colour == 1), PCC_E_ARG,
               "pcc_attr_encode_frames_transform2: bad argument (n_kept=%lld colour=%d)", (long long)n_kept, colour);
-  return a_encode_frames("pcc_attr_encode_frames_transform2", 2, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames,
-                         d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets, n_kept, 0, nullptr, 0, h_qstep, colour);
+  return a_encode_frames("pcc_attr_encode_frames_transform2", a_kind_transform(n_kept, 0, h_qstep, colour), ctx, d_values, h_value_offsets,
+                         h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets);
 }
 
 // host only: the version byte and byte 3 of a head, checked: its kind, channels and mask
@@ -1709,51 +1764,30 @@ extern "C" int pcc_attr_transform_info(const uint8_t* h_in, int64_t len, int32_t
 // host only: what the head of an attribute blob of any kind says (h_in may be a prefix that holds the head)
 extern "C" int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_version, int32_t* h_bpv, int32_t* h_channels,
                              int64_t* h_points, int32_t* h_max_error, int32_t* h_scalable, int32_t* h_lod) {
-  if (h_in && len >= kAttrHead && h_in[0] == 'A' && attr_c_kind(h_in[1])) {   // version 21: its own parser; steps through pcc_attr_transform_info
-    AttrCInfo o;
-    const int rc = attr_c_parse(h_in, len, &o, true);
-    if (rc != PCC_OK) {
-      const std::string msg = pcc_last_error();
-      pcc_set_error("pcc_attr_info: %s", msg.c_str());
-      return rc;
-    }
-    if (h_version) *h_version = o.version;
-    if (h_bpv) *h_bpv = o.bpv;
-    if (h_channels) *h_channels = o.c;
-    if (h_points) *h_points = o.n;
-    if (h_max_error) *h_max_error = 0;
-    if (h_scalable) *h_scalable = 0;
-    if (h_lod) *h_lod = o.slod;
-    return PCC_OK;
-  }
-  if (h_in && len >= kAttrHead && h_in[0] == 'A' && attr_t_kind(h_in[1])) {   // version 19: its own parser; q through pcc_attr_qstep
-    AttrTInfo o;
-    const int rc = attr_t_parse(h_in, len, &o, true);
-    if (rc != PCC_OK) {
-      const std::string msg = pcc_last_error();
-      pcc_set_error("pcc_attr_info: %s", msg.c_str());
-      return rc;
-    }
-    if (h_version) *h_version = o.version;
-    if (h_bpv) *h_bpv = o.bpv;
-    if (h_channels) *h_channels = o.c;
-    if (h_points) *h_points = o.n;
-    if (h_max_error) *h_max_error = 0;
-    if (h_scalable) *h_scalable = 0;
-    if (h_lod) *h_lod = o.slod;
-    return PCC_OK;
-  }
-  bool scal, nl, xc;
-  int c, m;
-  PCC_TRY(a_head_kind("pcc_attr_info", h_in, len, &scal, &nl, &xc, &c, &m));
-  const int ver = h_in[1], bpv = scal ? h_in[2] & 15 : h_in[2], slod = scal ? h_in[2] >> 4 : 0;
-  const int64_t n = (int64_t)attr_u32(h_in + 4);
-  PCC_REQUIRE(n < ((int64_t)1 << 27), PCC_E_STREAM, "pcc_attr_info: %lld points", (long long)n);
+  bool scal = false, nl, xc;
+  int ver, bpv, c, m, slod;
+  int64_t n;
   uint32_t e = 0;
-  if (nl && n > 0) {
-    PCC_REQUIRE(len >= kAttrHead + 4, PCC_E_STREAM, "pcc_attr_info: truncated in front of max_error (len=%lld)", (long long)len);
-    e = attr_u32(h_in + kAttrHead);
-    PCC_REQUIRE(e >= 1 && e <= attr_max_error(bpv), PCC_E_STREAM, "pcc_attr_info: max_error %u with %d bytes per value", e, bpv);
+  if (h_in && len >= kAttrHead && h_in[0] == 'A' && (attr_t_kind(h_in[1]) || attr_c_kind(h_in[1]))) {
+    // versions 19 and 21: their own parser; q through pcc_attr_qstep, steps and colour through pcc_attr_transform_info
+    AttrCInfo o;
+    const int rc = attr_tc_parse(h_in, len, &o, attr_c_kind(h_in[1]) ? &o : nullptr, true);
+    if (rc != PCC_OK) {
+      const std::string msg = pcc_last_error();
+      pcc_set_error("pcc_attr_info: %s", msg.c_str());
+      return rc;
+    }
+    ver = o.version, bpv = o.bpv, c = o.c, n = o.n, slod = o.slod;
+  } else {
+    PCC_TRY(a_head_kind("pcc_attr_info", h_in, len, &scal, &nl, &xc, &c, &m));
+    ver = h_in[1], bpv = scal ? h_in[2] & 15 : h_in[2], slod = scal ? h_in[2] >> 4 : 0;
+    n = (int64_t)attr_u32(h_in + 4);
+    PCC_REQUIRE(n < ((int64_t)1 << 27), PCC_E_STREAM, "pcc_attr_info: %lld points", (long long)n);
+    if (nl && n > 0) {
+      PCC_REQUIRE(len >= kAttrHead + 4, PCC_E_STREAM, "pcc_attr_info: truncated in front of max_error (len=%lld)", (long long)len);
+      e = attr_u32(h_in + kAttrHead);
+      PCC_REQUIRE(e >= 1 && e <= attr_max_error(bpv), PCC_E_STREAM, "pcc_attr_info: max_error %u with %d bytes per value", e, bpv);
+    }
   }
   if (h_version) *h_version = ver;
   if (h_bpv) *h_bpv = bpv;
@@ -1765,7 +1799,7 @@ extern "C" int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_versio
   return PCC_OK;
 }
 
-// ---- what the two decoders share ------------------------------------------------------------------------------------
+// ---- what the three decoders share -----------------------------------------------------------------------------------
 static bool a_is_version(const uint8_t* b, int64_t len, int version) { return b && len >= 2 && b[0] == 'A' && b[1] == version; }
 
 // the version of a call's blobs: the first blob's when it is one of the entry point's four, else the first of them
@@ -1790,28 +1824,6 @@ static int a_wrap_error(const char* who, int f, int rc) {
   return rc;
 }
 
-// the row of a frame with points: its body at body_off of the upload, its values at out_off of the output, its chunks
-// [cb, cb + nc) of the call's, the last of them with last_words words there to read, n_dec values to decode
-static ADFrame a_dec_row(const AttrInfo& o, int64_t body_off, int64_t out_off, int64_t cb, int64_t nc, int64_t n_dec,
-                         int64_t last_words) {
-  ADFrame r;
-  r.body_off = body_off;
-  r.table_off = o.off_table - o.off_p0;
-  r.payload_off = o.off_payload - o.off_p0;
-  r.n = o.n;
-  r.out_off = out_off;
-  r.S = (int32_t)o.S;
-  r.nc = (int32_t)nc;
-  r.cb = (int32_t)cb;
-  r.c = o.c;
-  r.bpv = o.bpv;
-  r.nctx = o.nctx;
-  r.n_dec = n_dec;
-  r.last_words = (int32_t)last_words;
-  r.max_error = (int32_t)o.max_error;
-  return r;
-}
-
 // a caller's array in pinned host memory receives the values straight from the device; any other one through the
 // staging (a failed query of an ordinary pointer leaves its error behind: cleared here)
 static bool a_host_is_pinned(const void* h_out) {
@@ -1822,22 +1834,6 @@ static bool a_host_is_pinned(const void* h_out) {
   return false;
 }
 
-// staging of a decode call: rows and bodies on their way up (in_b) | the values on their way down, unless they go
-// straight to the caller's array | back_b bytes of counts and status read back.  *down: where the device copies the
-// values to (h_out itself when pinned, the staging otherwise, nullptr without h_out); a_copy_out finishes
-static int a_dec_stage(pcc_ctx* ctx, uint8_t* h_out, size_t in_b, int64_t bytes, size_t back_b, uint8_t** down, uint8_t** back) {
-  const bool direct = a_host_is_pinned(h_out);
-  const size_t out_b = h_out && !direct ? (size_t)bytes : 0;
-  PCC_TRY(o2_stage_reserve(ctx, pcc_align(in_b) + pcc_align(out_b) + back_b + 64));
-  uint8_t* stage_out = (uint8_t*)ctx->stage + pcc_align(in_b);
-  *down = !h_out ? nullptr : (direct ? h_out : stage_out);
-  *back = stage_out + pcc_align(out_b);
-  return PCC_OK;
-}
-static void a_copy_out(uint8_t* h_out, const uint8_t* down, int64_t bytes) {
-  if (down && down != h_out) memcpy(h_out, down, (size_t)bytes);
-}
-
 // k_a_dec's dynamic LDS: a chunk's payload beside the models when it fits in 128 KB in all, else read where it lies
 static size_t a_dec_lds(int64_t nctx_max, int64_t cw_max, int* model_rows, int* lds_words) {
   *model_rows = (int)nctx_max + 1;
@@ -1846,17 +1842,193 @@ static size_t a_dec_lds(int64_t nctx_max, int64_t cw_max, int* model_rows, int* 
   return (size_t)*model_rows * kLanes * 2 + (size_t)*lds_words * 2;
 }
 
-// d_in: the call's rows, then (tab_b) its bodies
+// One decode call, the skeleton of pcc_attr_decode_frames, pcc_attr_decode_frames_lod and the transform decoder.  An
+// entry point parses and checks frame by frame and hands every frame to a_dec_count; builds its side tables; then
+// a_dec_plan (rows, layout, arena), its own arena arrays, a_dec_send (staging, upload), its kernels, a_dec_finish
+// (values and status back behind the call's last synchronisation, the status of every frame, the copy out).
+struct ADecIn {             // a frame as its parser left it
+  const AttrInfo* o;        // the parsed head; the entry point keeps it
+  int64_t n_dec;            // values to decode: the frame's points, or its cells at a level of detail
+  int64_t nc, last_words;   // the chunks that takes, and the words of the last of them that are there to read
+  int64_t body_b;           // the bytes of the blob from off_p0 on that go to the device
+  uint32_t e;               // the row's max_error: e of the near-lossless kinds, q of version 19
+  int shift;                // decoders against cells: the level of the frame's cells, the sender's and the call's
+};
+struct ADecCall {
+  const char* who;
+  pcc_ctx* ctx;
+  const uint8_t* const* h_blobs;
+  int n_frames;
+  uint8_t *d_out, *h_out;
+  int64_t cap_bytes;
+  int64_t* h_out_offsets;
+  int32_t* h_format;
+  std::vector<ADecIn> in;
+  int nf = 0;                                                // frames with values: the rows of every table
+  int64_t bytes = 0, bodies = 0, points = 0;                 // the accounting pass
+  const int32_t* masks = nullptr;                            // side tables, one entry per row (nullptr: not in this call):
+  const A2Order* order = nullptr;                            //   cross-channel masks | order rows | steps and colour word
+  const int32_t* aux = nullptr;
+  std::vector<ADFrame> tab;                                  // the rows pass
+  int64_t chunks = 0, nctx_max = 0, cw_max = 0, n_max = 0;
+  ATables lay;                                               // the upload: rows, masks directly behind | order | aux | bodies
+  size_t ord_at = 0, aux_at = 0;
+  uint8_t *d_in = nullptr, *out = nullptr;                   // the upload in the arena; the values in HBM
+  uint8_t *down = nullptr, *back = nullptr;                  // staging: where the values come down to; what is read back
+  size_t masks_at() const { return (size_t)nf * sizeof(ADFrame); }
+};
+
+static ADecCall a_dec_call(const char* who, pcc_ctx* ctx, const uint8_t* const* h_blobs, int n_frames, uint8_t* d_out, uint8_t* h_out,
+                           int64_t cap_bytes, int64_t* h_out_offsets, int32_t* h_format) {
+  h_out_offsets[0] = 0;
+  return ADecCall{who, ctx, h_blobs, n_frames, d_out, h_out, cap_bytes, h_out_offsets, h_format, std::vector<ADecIn>((size_t)n_frames)};
+}
+
+// accounting, frame f, once it has passed its entry point's checks: format and offsets out, every frame's values on 16 bytes
+static void a_dec_count(ADecCall& d, int f, const ADecIn& in) {
+  const AttrInfo& o = *in.o;
+  d.in[(size_t)f] = in;
+  if (d.h_format) d.h_format[f] = o.bpv | (o.c << 8);
+  d.bytes = a_round(d.bytes + in.n_dec * o.c * o.bpv, 16);
+  d.points += in.n_dec;
+  d.h_out_offsets[f + 1] = d.bytes;
+  if (in.n_dec) {
+    d.bodies += a_round(in.body_b, 16);
+    ++d.nf;
+  }
+}
+
+// behind the parse loop.  *idle: nothing to decode, or nowhere to put it (a call that asks for sizes)
+static int a_dec_counted(const ADecCall& d, const char* noun, bool* idle) {
+  PCC_REQUIRE(d.points < ((int64_t)1 << 31), PCC_E_ARG, "%s: the blobs announce %lld %s in all", d.who, (long long)d.points, noun);
+  *idle = d.bytes == 0 || (!d.d_out && !d.h_out);
+  return PCC_OK;
+}
+
+// decoders against the cells of the geometry (levels of detail, the transform kinds): the cells are needed; one order
+// row per frame with values, its cells [at, at + n_dec) of the call's, its blocks of 256 from *blocks on
+static int a_dec_order(const ADecCall& d, const int32_t* d_cells, const int64_t* h_cell_offsets, std::vector<A2Order>* order,
+                       int64_t* blocks, int64_t* cells_all, const int32_t** cells) {
+  PCC_REQUIRE(d_cells && h_cell_offsets && h_cell_offsets[0] >= 0, PCC_E_ARG, "%s: the cells of the frames are needed", d.who);
+  const int64_t cell0 = h_cell_offsets[0];
+  *blocks = 0;
+  for (int f = 0; f < d.n_frames; ++f) {
+    const ADecIn& in = d.in[(size_t)f];
+    if (in.n_dec == 0) continue;
+    order->push_back(A2Order{h_cell_offsets[f] - cell0, in.n_dec, (int32_t)*blocks, in.shift});
+    *blocks += nblk(in.n_dec, 256);
+  }
+  *cells_all = h_cell_offsets[d.n_frames] - cell0;
+  *cells = d_cells + 3 * cell0;
+  return PCC_OK;
+}
+
+// the row of a frame with points: its body at body_off of the upload, its values at out_off of the output, its chunks
+// [cb, cb + nc) of the call's, the last of them with last_words words there to read, n_dec values to decode
+static ADFrame a_dec_row(const ADecIn& in, int64_t body_off, int64_t out_off, int64_t cb) {
+  const AttrInfo& o = *in.o;
+  ADFrame r;
+  r.body_off = body_off;
+  r.table_off = o.off_table - o.off_p0;
+  r.payload_off = o.off_payload - o.off_p0;
+  r.n = o.n;
+  r.out_off = out_off;
+  r.S = (int32_t)o.S;
+  r.nc = (int32_t)in.nc;
+  r.cb = (int32_t)cb;
+  r.c = o.c;
+  r.bpv = o.bpv;
+  r.nctx = o.nctx;
+  r.n_dec = in.n_dec;
+  r.last_words = (int32_t)in.last_words;
+  r.max_error = (int32_t)in.e;
+  return r;
+}
+
+// capacity, the rows pass, the layout of the upload, and the arena: own_b bytes for the entry point's arrays besides
+// the upload and value_arrays arrays of the call's bytes (the values unless d_out takes them, indices, residuals)
+static int a_dec_plan(ADecCall& d, int value_arrays, size_t own_b) {
+  PCC_REQUIRE(d.cap_bytes >= d.bytes, PCC_E_NOMEM, "%s: %lld bytes, capacity %lld", d.who, (long long)d.bytes, (long long)d.cap_bytes);
+  int64_t body_off = 0;
+  for (int f = 0; f < d.n_frames; ++f) {
+    const ADecIn& in = d.in[(size_t)f];
+    if (in.n_dec == 0) continue;
+    const uint8_t* table = d.h_blobs[f] + in.o->off_table;
+    d.tab.push_back(a_dec_row(in, body_off, d.h_out_offsets[f], d.chunks));
+    for (int64_t k = 0; k + 1 < in.nc; ++k) d.cw_max = std::max<int64_t>(d.cw_max, attr_u32(table + 4 * k));
+    d.cw_max = std::max<int64_t>(d.cw_max, in.last_words);
+    d.n_max = std::max(d.n_max, in.n_dec);
+    body_off += a_round(in.body_b, 16);
+    d.chunks += in.nc;
+    d.nctx_max = std::max<int64_t>(d.nctx_max, in.o->nctx);
+  }
+  d.lay.add((size_t)d.nf * (sizeof(ADFrame) + (d.masks ? 4 : 0)));
+  d.ord_at = d.lay.add(d.order ? (size_t)d.nf * sizeof(A2Order) : 0);
+  d.aux_at = d.lay.add(d.aux ? (size_t)d.nf * 20 : 0);
+  PCC_TRY(pcc_arena_reserve(d.ctx, d.lay.bytes + pcc_align((size_t)d.bodies + 16) + (size_t)value_arrays * pcc_align((size_t)d.bytes) + own_b));
+  d.d_in = (uint8_t*)pcc_arena_alloc(d.ctx, d.lay.bytes + (size_t)d.bodies + 16);
+  d.out = d.d_out ? d.d_out : (uint8_t*)pcc_arena_alloc(d.ctx, (size_t)d.bytes);
+  return d.d_in && d.out ? PCC_OK : PCC_E_NOMEM;
+}
+
+// staging: rows, side tables and bodies on their way up | the values on their way down, unless they go straight to the
+// caller's pinned array | back_b bytes of counts and status read back; then the upload
+static int a_dec_send(ADecCall& d, size_t back_b) {
+  const size_t in_b = d.lay.bytes + (size_t)d.bodies, nf = (size_t)d.nf;
+  const bool direct = a_host_is_pinned(d.h_out);
+  const size_t out_b = d.h_out && !direct ? (size_t)d.bytes : 0;
+  PCC_TRY(o2_stage_reserve(d.ctx, pcc_align(in_b) + pcc_align(out_b) + back_b + 64));
+  uint8_t* stage = (uint8_t*)d.ctx->stage;
+  d.down = !d.h_out ? nullptr : (direct ? d.h_out : stage + pcc_align(in_b));
+  d.back = stage + pcc_align(in_b) + pcc_align(out_b);
+  memcpy(stage, d.tab.data(), nf * sizeof(ADFrame));
+  if (d.masks) memcpy(stage + d.masks_at(), d.masks, nf * 4);
+  if (d.order) memcpy(stage + d.ord_at, d.order, nf * sizeof(A2Order));
+  if (d.aux) memcpy(stage + d.aux_at, d.aux, nf * 20);
+  for (int f = 0, k = 0; f < d.n_frames; ++f) {
+    const ADecIn& in = d.in[(size_t)f];
+    if (in.n_dec == 0) continue;
+    memcpy(stage + d.lay.bytes + d.tab[(size_t)k++].body_off, d.h_blobs[f] + in.o->off_p0, (size_t)in.body_b);
+  }
+  PCC_HIP(hipMemcpyAsync(d.d_in, stage, in_b, hipMemcpyHostToDevice, d.ctx->stream));
+  return PCC_OK;
+}
+
+// the lane decoder over the call's chunks: values, residuals or indices to dst
 template <bool V2>
-static int a_launch_dec(hipStream_t st, int64_t chunks, const uint8_t* d_in, size_t tab_b, int nf, int64_t nctx_max, int64_t cw_max,
-                        uint8_t* out, int32_t* status) {
+static int a_launch_dec(const ADecCall& d, uint8_t* dst, int32_t* status) {
   int model_rows, lds_words;
-  const size_t lds = a_dec_lds(nctx_max, cw_max, &model_rows, &lds_words);
+  const size_t lds = a_dec_lds(d.nctx_max, d.cw_max, &model_rows, &lds_words);
   PCC_HIP(hipFuncSetAttribute((const void*)k_a_dec<V2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_a_dec<V2>, dim3((unsigned)chunks), dim3(64), lds, st, d_in + tab_b, (const ADFrame*)d_in, nf, model_rows, lds_words,
-                     out, status);
+  hipLaunchKernelGGL(k_a_dec<V2>, dim3((unsigned)d.chunks), dim3(64), lds, d.ctx->stream, d.d_in + d.lay.bytes, (const ADFrame*)d.d_in, d.nf,
+                     model_rows, lds_words, dst, status);
   PCC_CHECK_LAUNCH();
   return PCC_OK;
+}
+
+// the end of a call: the values down, back_b bytes of back_dev to back_at of what is read back, one synchronisation;
+// then per frame with values (row k) the entry point's own check and the frame's status, an int32 per row at status_at
+// of what was read back; and the values out of the staging where they came down there
+template <typename Check>
+static int a_dec_finish(ADecCall& d, const void* back_dev, size_t back_b, size_t back_at, size_t status_at, const char* legend,
+                        Check&& frame_check) {
+  hipStream_t st = d.ctx->stream;
+  if (d.down) PCC_HIP(hipMemcpyAsync(d.down, d.out, (size_t)d.bytes, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipMemcpyAsync(d.back + back_at, back_dev, back_b, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipStreamSynchronize(st));
+  const int32_t* h_status = (const int32_t*)(d.back + status_at);
+  for (int f = 0, k = 0; f < d.n_frames; ++f) {
+    if (d.in[(size_t)f].n_dec == 0) continue;
+    PCC_TRY(frame_check(f, k));
+    const int32_t bad = h_status[k++];
+    PCC_REQUIRE(bad == 0, PCC_E_STREAM, "%s: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state%s)", d.who, f, bad,
+                legend);
+  }
+  if (d.down && d.down != d.h_out) memcpy(d.h_out, d.down, (size_t)d.bytes);
+  return PCC_OK;
+}
+static int a_dec_finish(ADecCall& d, const void* back_dev, size_t back_b, size_t back_at, size_t status_at, const char* legend) {
+  return a_dec_finish(d, back_dev, back_b, back_at, status_at, legend, [](int, int) { return PCC_OK; });
 }
 
 extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
@@ -1871,9 +2043,8 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
   const int kinds[4] = {1, 4, 8, 13};
   const int mine = a_call_version(h_blobs[0], h_lens[0], kinds);
   const bool nl = mine == 4 || mine == 13, xc = mine == 8 || mine == 13;
+  ADecCall d = a_dec_call(who, ctx, h_blobs, n_frames, d_out, h_out, cap_bytes, h_out_offsets, h_format);
   std::vector<AttrInfo> info((size_t)n_frames);
-  int64_t bytes = 0, bodies = 0, points = 0;
-  h_out_offsets[0] = 0;
   for (int f = 0; f < n_frames; ++f) {
     AttrInfo& o = info[(size_t)f];
     PCC_TRY(a_mixed_version(who, f, h_blobs[f], h_lens[f], kinds, mine));
@@ -1881,159 +2052,99 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
     if (rc != PCC_OK) return a_wrap_error(who, f, rc);
     PCC_REQUIRE(!h_points || h_points[f] == o.n, PCC_E_STREAM, "%s: frame %d: the attribute blob has %lld points, its geometry %lld",
                 who, f, (long long)o.n, (long long)(h_points ? h_points[f] : 0));
-    if (h_format) h_format[f] = o.bpv | (o.c << 8);
-    bytes = a_round(bytes + o.n * o.c * o.bpv, 16);
-    points += o.n;
-    h_out_offsets[f + 1] = bytes;
-    if (o.n) bodies += a_round(h_lens[f] - o.off_p0, 16);
+    const int64_t last_words = o.n ? attr_u32(h_blobs[f] + o.off_table + 4 * (o.nc - 1)) : 0;
+    a_dec_count(d, f, ADecIn{&o, o.n, o.nc, last_words, h_lens[f] - o.off_p0, o.max_error, 0});
   }
-  PCC_REQUIRE(points < ((int64_t)1 << 31), PCC_E_ARG, "%s: the blobs announce %lld points in all", who, (long long)points);
-  if (bytes == 0 || (!d_out && !h_out)) return PCC_OK;
-  PCC_REQUIRE(cap_bytes >= bytes, PCC_E_NOMEM, "%s: %lld bytes, capacity %lld", who, (long long)bytes, (long long)cap_bytes);
-  std::vector<ADFrame> tab;
+  bool idle;
+  PCC_TRY(a_dec_counted(d, "points", &idle));
+  if (idle) return PCC_OK;
   std::vector<int32_t> cross;   // the masks of versions 8 and 13
-  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, run_threads = 0, n_max = 0;
-  for (int f = 0; f < n_frames; ++f) {
-    const AttrInfo& o = info[(size_t)f];
+  int64_t run_threads = 0;
+  for (const AttrInfo& o : info) {
     if (o.n == 0) continue;
-    const uint8_t* table = h_blobs[f] + o.off_table;
-    tab.push_back(a_dec_row(o, body_off, h_out_offsets[f], chunks, o.nc, o.n, attr_u32(table + 4 * (o.nc - 1))));
     cross.push_back(o.cross);
-    n_max = std::max(n_max, o.n);
     run_threads = std::max<int64_t>(run_threads, o.nc * kLanes * o.c);
-    for (int64_t k = 0; k < o.nc; ++k) cw_max = std::max<int64_t>(cw_max, attr_u32(table + 4 * k));
-    body_off += a_round(h_lens[f] - o.off_p0, 16);
-    chunks += o.nc;
-    nctx_max = std::max<int64_t>(nctx_max, o.nctx);
   }
-  const int nf = (int)tab.size();
+  if (xc) d.masks = cross.data();
+  const size_t status_b = (size_t)d.nf * 4 + 64;
+  PCC_TRY(a_dec_plan(d, (d_out ? 0 : 1) + (nl ? 1 : 0), pcc_align(status_b) + 4096));
+  const int nf = d.nf;
   hipStream_t st = ctx->stream;
-  const size_t tab_b = pcc_align((size_t)nf * (sizeof(ADFrame) + (xc ? 4 : 0)));   // the rows, then the masks
-  PCC_TRY(pcc_arena_reserve(ctx, tab_b + pcc_align((size_t)bodies + 16) + ((d_out ? 0 : 1) + (nl ? 1 : 0)) * pcc_align((size_t)bytes) +
-                                     pcc_align((size_t)nf * 4 + 64) + 4096));
-  uint8_t* d_in = (uint8_t*)pcc_arena_alloc(ctx, tab_b + (size_t)bodies + 16);
-  uint8_t* out = d_out ? d_out : (uint8_t*)pcc_arena_alloc(ctx, (size_t)bytes);
-  uint8_t* idx = nl ? (uint8_t*)pcc_arena_alloc(ctx, (size_t)bytes) : out;   // version 4: the indices, as version 2's residuals
-  int32_t* status = (int32_t*)pcc_arena_alloc(ctx, (size_t)nf * 4 + 64);
-  if (!d_in || !out || !idx || !status) return PCC_E_NOMEM;
-  PccProfScope prof(ctx, "attr_decode", points, nf, chunks, 0);
-  const size_t in_b = tab_b + (size_t)bodies;
-  uint8_t *down, *back;
-  PCC_TRY(a_dec_stage(ctx, h_out, in_b, bytes, (size_t)nf * 4, &down, &back));
-  uint8_t* stage = (uint8_t*)ctx->stage;
-  memcpy(stage, tab.data(), (size_t)nf * sizeof(ADFrame));
-  if (xc) memcpy(stage + (size_t)nf * sizeof(ADFrame), cross.data(), (size_t)nf * 4);
-  for (int f = 0, k = 0; f < n_frames; ++f) {
-    const AttrInfo& o = info[(size_t)f];
-    if (o.n == 0) continue;
-    memcpy(stage + tab_b + tab[(size_t)k++].body_off, h_blobs[f] + o.off_p0, (size_t)(h_lens[f] - o.off_p0));
-  }
-  PCC_HIP(hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
-  PCC_HIP(hipMemsetAsync(status, 0, (size_t)nf * 4 + 64, st));
+  uint8_t* out = d.out;
+  uint8_t* idx = nl ? (uint8_t*)pcc_arena_alloc(ctx, (size_t)d.bytes) : out;   // version 4: the indices, as version 2's residuals
+  int32_t* status = (int32_t*)pcc_arena_alloc(ctx, status_b);
+  if (!idx || !status) return PCC_E_NOMEM;
+  PccProfScope prof(ctx, "attr_decode", d.points, nf, d.chunks, 0);
+  PCC_TRY(a_dec_send(d, (size_t)nf * 4));
+  PCC_HIP(hipMemsetAsync(status, 0, status_b, st));
+  const ADFrame* d_tab = (const ADFrame*)d.d_in;
   if (!nl && !xc) {
-    PCC_TRY(a_launch_dec<false>(st, chunks, d_in, tab_b, nf, nctx_max, cw_max, out, status));
+    PCC_TRY(a_launch_dec<false>(d, out, status));
   } else {
-    PCC_TRY(a_launch_dec<true>(st, chunks, d_in, tab_b, nf, nctx_max, cw_max, idx, status));
+    PCC_TRY(a_launch_dec<true>(d, idx, status));
     if (xc) {
-      hipLaunchKernelGGL(k_ax_inv, dim3(nblk(n_max, 256), (unsigned)nf), dim3(256), 0, st, (const ADFrame*)d_in,
-                         (const int32_t*)(d_in + (size_t)nf * sizeof(ADFrame)), idx);
+      hipLaunchKernelGGL(k_ax_inv, dim3(nblk(d.n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, (const int32_t*)(d.d_in + d.masks_at()), idx);
       PCC_CHECK_LAUNCH();
     }
   }
   if (xc && !nl) {   // version 8: idx is out
-    hipLaunchKernelGGL(k_a8_recon, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const ADFrame*)d_in, out);
+    hipLaunchKernelGGL(k_a8_recon, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, d_tab, out);
     PCC_CHECK_LAUNCH();
   } else if (nl) {
-    hipLaunchKernelGGL(k_a4_recon, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const ADFrame*)d_in,
-                       (const uint8_t*)idx, out, status);
+    hipLaunchKernelGGL(k_a4_recon, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, d_tab, (const uint8_t*)idx, out, status);
     PCC_CHECK_LAUNCH();
   }
-  int32_t* h_status = (int32_t*)back;
-  if (down) PCC_HIP(hipMemcpyAsync(down, out, (size_t)bytes, hipMemcpyDeviceToHost, st));
-  PCC_HIP(hipMemcpyAsync(h_status, status, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
-  PCC_HIP(hipStreamSynchronize(st));
-  for (int f = 0, k = 0; f < n_frames; ++f) {
-    if (info[(size_t)f].n == 0) continue;
-    const int32_t bad = h_status[k++];
-    PCC_REQUIRE(bad == 0, PCC_E_STREAM, "%s: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state%s)", who, f,
-                bad, nl ? ", 16 = reconstruction out of range" : "");
-  }
-  a_copy_out(h_out, down, bytes);
-  return PCC_OK;
+  return a_dec_finish(d, status, (size_t)nf * 4, 0, 0, nl ? ", 16 = reconstruction out of range" : "");
 }
 
-// ---- version 19: the decoder -----------------------------------------------------------------------------------------
+// ---- versions 19 and 21: the decoder ---------------------------------------------------------------------------------
 // Against the cells its geometry decode left in HBM, as version 2's at lod 0: the order stage over the cells' keys, the
 // lane decoder (x in coding order), the root, one k_at_lift<false> per occupied sublevel top-down, clamp and store.
 // tc: a call of version-21 blobs — their steps and colour words in a table behind the order rows (aux: 5 words per
 // frame), the lift with a step per channel, and k_ac_store in place of k_at_store where a frame has the colour transform
 static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
                              const int32_t* d_cells, const int64_t* h_cell_offsets, uint8_t* d_out, uint8_t* h_out, int64_t cap_bytes,
-                             int64_t* h_out_offsets, int32_t* h_format, bool tc = false) {
+                             int64_t* h_out_offsets, int32_t* h_format, bool tc) {
+  ADecCall d = a_dec_call(who, ctx, h_blobs, n_frames, d_out, h_out, cap_bytes, h_out_offsets, h_format);
   std::vector<AttrCInfo> info((size_t)n_frames);
-  int64_t bytes = 0, bodies = 0, points = 0;
-  h_out_offsets[0] = 0;
   for (int f = 0; f < n_frames; ++f) {
     AttrCInfo& o = info[(size_t)f];
-    const int rc = tc ? attr_c_parse(h_blobs[f], h_lens[f], &o) : attr_t_parse(h_blobs[f], h_lens[f], &o);
+    const int rc = attr_tc_parse(h_blobs[f], h_lens[f], &o, tc ? &o : nullptr, false);
     if (rc != PCC_OK) return a_wrap_error(who, f, rc);
     if (h_cell_offsets) {
       const int64_t m = h_cell_offsets[f + 1] - h_cell_offsets[f];
       PCC_REQUIRE(m == o.n, PCC_E_STREAM, "%s: frame %d: the attribute blob has %lld values, its geometry %lld points", who, f,
                   (long long)o.n, (long long)m);
     }
-    if (h_format) h_format[f] = o.bpv | (o.c << 8);
-    bytes = a_round(bytes + o.n * o.c * o.bpv, 16);
-    points += o.n;
-    h_out_offsets[f + 1] = bytes;
-    if (o.n) bodies += a_round(h_lens[f] - o.off_p0, 16);
+    const int64_t last_words = o.n ? attr_u32(h_blobs[f] + o.off_table + 4 * (o.nc - 1)) : 0;
+    a_dec_count(d, f, ADecIn{&o, o.n, o.nc, last_words, h_lens[f] - o.off_p0, o.qstep, o.slod});   // q where the near-lossless kinds keep e
   }
-  PCC_REQUIRE(points < ((int64_t)1 << 31), PCC_E_ARG, "%s: the blobs announce %lld values in all", who, (long long)points);
-  if (bytes == 0 || (!d_out && !h_out)) return PCC_OK;
-  PCC_REQUIRE(d_cells && h_cell_offsets && h_cell_offsets[0] >= 0, PCC_E_ARG, "%s: the cells of the frames are needed", who);
-  PCC_REQUIRE(cap_bytes >= bytes, PCC_E_NOMEM, "%s: %lld bytes, capacity %lld", who, (long long)bytes, (long long)cap_bytes);
-  std::vector<ADFrame> tab;
+  bool idle;
+  PCC_TRY(a_dec_counted(d, "values", &idle));
+  if (idle) return PCC_OK;
   std::vector<A2Order> order;
   std::vector<int32_t> aux;
+  int64_t blocks, cells_all, vals_max = 0;
+  const int32_t* cells;
+  PCC_TRY(a_dec_order(d, d_cells, h_cell_offsets, &order, &blocks, &cells_all, &cells));
   bool any_colour = false;
-  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, blocks = 0, vals_max = 0, n_max = 0;
-  const int64_t cell0 = h_cell_offsets[0];
-  for (int f = 0; f < n_frames; ++f) {
-    const AttrCInfo& o = info[(size_t)f];
+  for (const AttrCInfo& o : info) {
     if (o.n == 0) continue;
-    if (tc) {
-      for (int ch = 0; ch < 4; ++ch) aux.push_back((int32_t)o.q[ch]);
-      aux.push_back((int32_t)o.colour);
-      any_colour |= o.colour != 0;
-    }
-    n_max = std::max(n_max, o.n);
-    const uint8_t* table = h_blobs[f] + o.off_table;
-    ADFrame r = a_dec_row(o, body_off, h_out_offsets[f], chunks, o.nc, o.n, attr_u32(table + 4 * (o.nc - 1)));
-    r.max_error = (int32_t)o.qstep;   // q where the near-lossless kinds keep e
-    tab.push_back(r);
-    order.push_back(A2Order{h_cell_offsets[f] - cell0, o.n, (int32_t)blocks, o.slod});
     vals_max = std::max(vals_max, o.n * o.c);
-    for (int64_t k = 0; k < o.nc; ++k) cw_max = std::max<int64_t>(cw_max, attr_u32(table + 4 * k));
-    body_off += a_round(h_lens[f] - o.off_p0, 16);
-    chunks += o.nc;
-    blocks += nblk(o.n, 256);
-    nctx_max = std::max<int64_t>(nctx_max, o.nctx);
+    if (!tc) continue;
+    for (int ch = 0; ch < 4; ++ch) aux.push_back((int32_t)o.q[ch]);
+    aux.push_back((int32_t)o.colour);
+    any_colour |= o.colour != 0;
   }
-  const int64_t cells_all = h_cell_offsets[n_frames] - cell0;
-  const int32_t* cells = d_cells + 3 * cell0;
-  const int nf = (int)tab.size();
-  hipStream_t st = ctx->stream;
-  const size_t ftab_b = pcc_align((size_t)nf * sizeof(ADFrame)), ord_b = pcc_align((size_t)nf * sizeof(A2Order));
-  const size_t aux_b = tc ? pcc_align((size_t)nf * 20) : 0;
-  const size_t tab_b = ftab_b + ord_b + aux_b;
+  d.order = order.data();
+  if (tc) d.aux = aux.data();
+  const int nf = d.nf;
   const size_t keys_b = pcc_align((size_t)cells_all * 8), u32_b = pcc_align((size_t)cells_all * 4), pk_b = pcc_align((size_t)cells_all * 2);
   const size_t hist_b = pcc_align((size_t)blocks * kATBins * 4), bins_b = pcc_align((size_t)nf * 2 * kATBins * 4);
-  const size_t val_b = pcc_align((size_t)bytes * 8), status_b = pcc_align((size_t)nf * 4 + 64);
-  PCC_TRY(pcc_arena_reserve(ctx, tab_b + pcc_align((size_t)bodies + 16) + (d_out ? 1 : 2) * pcc_align((size_t)bytes) + val_b + keys_b + u32_b +
-                                     pk_b + hist_b + bins_b + status_b + 8192));
-  uint8_t* d_in = (uint8_t*)pcc_arena_alloc(ctx, tab_b + (size_t)bodies + 16);
-  uint8_t* out = d_out ? d_out : (uint8_t*)pcc_arena_alloc(ctx, (size_t)bytes);
-  uint8_t* x = (uint8_t*)pcc_arena_alloc(ctx, (size_t)bytes);
+  const size_t val_b = pcc_align((size_t)d.bytes * 8), status_b = pcc_align((size_t)nf * 4 + 64);
+  PCC_TRY(a_dec_plan(d, d_out ? 1 : 2, val_b + keys_b + u32_b + pk_b + hist_b + bins_b + status_b + 8192));
+  hipStream_t st = ctx->stream;
+  uint8_t* x = (uint8_t*)pcc_arena_alloc(ctx, (size_t)d.bytes);
   int64_t* val = (int64_t*)pcc_arena_alloc(ctx, val_b);
   uint64_t* keys = (uint64_t*)pcc_arena_alloc(ctx, keys_b);
   uint32_t* inv = (uint32_t*)pcc_arena_alloc(ctx, u32_b);
@@ -2041,59 +2152,28 @@ static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const
   uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, hist_b);
   uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, bins_b);
   int32_t* status = (int32_t*)pcc_arena_alloc(ctx, status_b);
-  if (!d_in || !out || !x || !val || !keys || !inv || !packed || !hist || !bins || !status) return PCC_E_NOMEM;
-  PccProfScope prof(ctx, "attr_decode_transform", points, nf, chunks, 0);
-  const size_t in_b = tab_b + (size_t)bodies;
-  uint8_t *down, *back;
-  PCC_TRY(a_dec_stage(ctx, h_out, in_b, bytes, (size_t)nf * (2 * kATBins + 1) * 4, &down, &back));
-  uint8_t* stage = (uint8_t*)ctx->stage;
-  memcpy(stage, tab.data(), (size_t)nf * sizeof(ADFrame));
-  memcpy(stage + ftab_b, order.data(), (size_t)nf * sizeof(A2Order));
-  if (tc) memcpy(stage + ftab_b + ord_b, aux.data(), (size_t)nf * 20);
-  for (int f = 0, k = 0; f < n_frames; ++f) {
-    const AttrCInfo& o = info[(size_t)f];
-    if (o.n == 0) continue;
-    memcpy(stage + tab_b + tab[(size_t)k++].body_off, h_blobs[f] + o.off_p0, (size_t)(h_lens[f] - o.off_p0));
-  }
-  PCC_HIP(hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
+  if (!x || !val || !keys || !inv || !packed || !hist || !bins || !status) return PCC_E_NOMEM;
+  PccProfScope prof(ctx, "attr_decode_transform", d.points, nf, d.chunks, 0);
+  const size_t bins_back = (size_t)nf * 2 * kATBins * 4;   // read back: the sublevels' starts and counts | status
+  PCC_TRY(a_dec_send(d, bins_back + (size_t)nf * 4));
   PCC_HIP(hipMemsetAsync(status, 0, (size_t)nf * 4, st));
-  const ADFrame* d_tab = (const ADFrame*)d_in;
-  const A2Order* d_ord = (const A2Order*)(d_in + ftab_b);
-  const int32_t* d_aux = tc ? (const int32_t*)(d_in + ftab_b + ord_b) : nullptr;
-  PCC_TRY(a_launch_dec<true>(st, chunks, d_in, tab_b, nf, nctx_max, cw_max, x, status));
+  const ADFrame* d_tab = (const ADFrame*)d.d_in;
+  const A2Order* d_ord = (const A2Order*)(d.d_in + d.ord_at);
+  const int32_t* d_aux = tc ? (const int32_t*)(d.d_in + d.aux_at) : nullptr;
+  PCC_TRY(a_launch_dec<true>(d, x, status));
   unsigned grid[kATBins];
-  PCC_TRY(a_t_order(st, true, (const void*)cells, keys, d_ord, nf, blocks, packed, hist, bins, inv, (uint32_t*)back, grid));
+  PCC_TRY(a_t_order(st, true, (const void*)cells, keys, d_ord, nf, blocks, packed, hist, bins, inv, (uint32_t*)d.back, grid));
   hipLaunchKernelGGL(k_at_root, dim3(nblk(4 * (int64_t)nf, 256)), dim3(256), 0, st, d_tab, nf, (const uint8_t*)x, val);
   PCC_CHECK_LAUNCH();
-  for (int t = kATBins - 2; t >= 0; --t) {
-    if (!grid[t]) continue;
-    if (tc)
-      hipLaunchKernelGGL((k_at_lift<false, const int32_t*>), dim3(grid[t], (unsigned)nf), dim3(256), 0, st, (const uint64_t*)keys, d_ord,
-                         (const uint32_t*)bins, (const uint32_t*)inv, t, (const AFrame*)nullptr, (uint16_t*)nullptr, (uint16_t*)nullptr, d_tab,
-                         (const uint8_t*)x, val, status, d_aux);
-    else
-      hipLaunchKernelGGL(k_at_lift<false>, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, (const uint64_t*)keys, d_ord, (const uint32_t*)bins,
-                         (const uint32_t*)inv, t, (const AFrame*)nullptr, (uint16_t*)nullptr, (uint16_t*)nullptr, d_tab, (const uint8_t*)x, val,
-                         status);
-    PCC_CHECK_LAUNCH();
-  }
+  for (int t = kATBins - 2; t >= 0; --t)
+    if (grid[t])
+      PCC_TRY(a_launch_lift<false>(st, grid[t], nf, keys, d_ord, bins, inv, t, nullptr, nullptr, nullptr, d_tab, x, val, status, d_aux));
   if (any_colour)
-    hipLaunchKernelGGL(k_ac_store, dim3(nblk(n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, d_aux, (const int64_t*)val, out);
+    hipLaunchKernelGGL(k_ac_store, dim3(nblk(d.n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, d_aux, (const int64_t*)val, d.out);
   else
-    hipLaunchKernelGGL(k_at_store, dim3(nblk(vals_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, (const int64_t*)val, out);
+    hipLaunchKernelGGL(k_at_store, dim3(nblk(vals_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, (const int64_t*)val, d.out);
   PCC_CHECK_LAUNCH();
-  int32_t* h_status = (int32_t*)back + (size_t)nf * 2 * kATBins;
-  if (down) PCC_HIP(hipMemcpyAsync(down, out, (size_t)bytes, hipMemcpyDeviceToHost, st));
-  PCC_HIP(hipMemcpyAsync(h_status, status, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
-  PCC_HIP(hipStreamSynchronize(st));
-  for (int f = 0, k = 0; f < n_frames; ++f) {
-    if (info[(size_t)f].n == 0) continue;
-    const int32_t bad = h_status[k++];
-    PCC_REQUIRE(bad == 0, PCC_E_STREAM, "%s: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state, 8 = keys)", who, f,
-                bad);
-  }
-  a_copy_out(h_out, down, bytes);
-  return PCC_OK;
+  return a_dec_finish(d, status, (size_t)nf * 4, bins_back, bins_back, ", 8 = keys");
 }
 
 // ---- version 2: levels of detail ----------------------------------------------------------------------------------
@@ -2101,12 +2181,9 @@ extern "C" int pcc_attr_lod_info(const uint8_t* h_in, int64_t len, int lod, int6
   PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "pcc_attr_lod_info: level of detail %d outside 0 .. %d", lod, kAttrMaxLod);
   PCC_REQUIRE(h_in && len >= 2 && h_in[0] == 'A', PCC_E_STREAM, "pcc_attr_lod_info: not an attribute blob (len=%lld)", (long long)len);
   bool scal = false, nl = false, xc = false;
-  PCC_REQUIRE(!attr_t_kind(h_in[1]), PCC_E_ARG,
-              "pcc_attr_lod_info: attribute blob version 19 (a transform-coded blob has no level-of-detail prefixes: the weights of its "
-              "transform need every point)");
-  PCC_REQUIRE(!attr_c_kind(h_in[1]), PCC_E_ARG,
-              "pcc_attr_lod_info: attribute blob version 21 (a transform-coded blob has no level-of-detail prefixes: the weights of its "
-              "transform need every point)");
+  PCC_REQUIRE(!attr_t_kind(h_in[1]) && !attr_c_kind(h_in[1]), PCC_E_ARG,
+              "pcc_attr_lod_info: attribute blob version %d (a transform-coded blob has no level-of-detail prefixes: the weights of its "
+              "transform need every point)", (int)h_in[1]);
   PCC_REQUIRE(attr_kind(h_in[1], &scal, &nl, &xc) && scal, PCC_E_ARG,
               "pcc_attr_lod_info: attribute blob version %d (levels of detail are a property of version 2)", (int)h_in[1]);
   Attr2Info o;
@@ -2129,39 +2206,28 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   PCC_REQUIRE(ctx && h_blobs && h_lens && h_out_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
               "%s: bad argument (n_frames=%d)", who, n_frames);
   PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "%s: level of detail %d outside 0 .. %d", who, lod, kAttrMaxLod);
-  // version 19 (one version per call, the first blob's): its own decoder, at lod 0
-  bool any_t = false;
-  for (int f = 0; f < n_frames; ++f) any_t |= a_is_version(h_blobs[f], h_lens[f], kAttrTVersion);
-  if (any_t) {
+  // versions 19 and 21 (one version per call): their own decoder, at lod 0
+  for (const int tv : {kAttrTVersion, kAttrCVersion}) {
+    bool any = false;
+    for (int f = 0; f < n_frames; ++f) any |= a_is_version(h_blobs[f], h_lens[f], tv);
+    if (!any) continue;
     for (int f = 0; f < n_frames; ++f)
-      PCC_REQUIRE(a_is_version(h_blobs[f], h_lens[f], kAttrTVersion), PCC_E_ARG,
-                  "%s: frame %d: attribute blobs of version 19 and of another version in one call (one version per call)", who, f);
-    PCC_REQUIRE(lod == 0, PCC_E_ARG, "%s: attribute blob version 19 at level of detail %d (it decodes at 0 only)", who, lod);
-    return a_t_decode_frames(who, ctx, h_blobs, h_lens, n_frames, d_cells, h_cell_offsets, d_out, h_out, cap_bytes, h_out_offsets, h_format);
-  }
-  // version 21 likewise
-  bool any_c = false;
-  for (int f = 0; f < n_frames; ++f) any_c |= a_is_version(h_blobs[f], h_lens[f], kAttrCVersion);
-  if (any_c) {
-    for (int f = 0; f < n_frames; ++f)
-      PCC_REQUIRE(a_is_version(h_blobs[f], h_lens[f], kAttrCVersion), PCC_E_ARG,
-                  "%s: frame %d: attribute blobs of version 21 and of another version in one call (one version per call)", who, f);
-    PCC_REQUIRE(lod == 0, PCC_E_ARG, "%s: attribute blob version 21 at level of detail %d (it decodes at 0 only)", who, lod);
+      PCC_REQUIRE(a_is_version(h_blobs[f], h_lens[f], tv), PCC_E_ARG,
+                  "%s: frame %d: attribute blobs of version %d and of another version in one call (one version per call)", who, f, tv);
+    PCC_REQUIRE(lod == 0, PCC_E_ARG, "%s: attribute blob version %d at level of detail %d (it decodes at 0 only)", who, tv, lod);
     return a_t_decode_frames(who, ctx, h_blobs, h_lens, n_frames, d_cells, h_cell_offsets, d_out, h_out, cap_bytes, h_out_offsets, h_format,
-                             true);
+                             tv == kAttrCVersion);
   }
   // the blobs of a call are of one version, the first blob's: 2, or 7 (k_a2_walk<true> scales and clamps), or their
   // cross-channel forms 11 and 14 (k_ax_inv between the decoder and the walk)
   const int kinds[4] = {2, 7, 11, 14};
   const int mine = a_call_version(h_blobs[0], h_lens[0], kinds);
   const bool nl = mine == 7 || mine == 14, xc = mine == 11 || mine == 14;
+  ADecCall d = a_dec_call(who, ctx, h_blobs, n_frames, d_out, h_out, cap_bytes, h_out_offsets, h_format);
   std::vector<Attr2Info> info((size_t)n_frames);
-  std::vector<Attr2Plan> plan((size_t)n_frames);
-  int64_t bytes = 0, bodies = 0, points = 0;
-  h_out_offsets[0] = 0;
   for (int f = 0; f < n_frames; ++f) {
     Attr2Info& o = info[(size_t)f];
-    Attr2Plan& pl = plan[(size_t)f];
+    Attr2Plan pl;
     PCC_TRY(a_mixed_version(who, f, h_blobs[f], h_lens[f], kinds, mine));
     const int rc = attr2_parse_kind(h_blobs[f], h_lens[f], lod, true, nl, &o, &pl, xc);
     if (rc != PCC_OK) return a_wrap_error(who, f, rc);
@@ -2172,77 +2238,41 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
     }
     PCC_REQUIRE(o.slod + lod <= kAttrMaxLod, PCC_E_ARG,
                 "%s: frame %d: level of detail %d of cells the sender coded at its level %d: beyond %d", who, f, lod, o.slod, kAttrMaxLod);
-    if (h_format) h_format[f] = o.bpv | (o.c << 8);
-    bytes = a_round(bytes + pl.m * o.c * o.bpv, 16);
-    points += pl.m;
-    h_out_offsets[f + 1] = bytes;
-    if (pl.m) bodies += a_round(pl.bytes - o.off_p0, 16);
+    a_dec_count(d, f, ADecIn{&o, pl.m, pl.chunks, pl.last_words, pl.bytes - o.off_p0, o.max_error, lod + o.slod});   // the level's bytes only
   }
-  PCC_REQUIRE(points < ((int64_t)1 << 31), PCC_E_ARG, "%s: the blobs announce %lld values in all", who, (long long)points);
-  if (bytes == 0 || (!d_out && !h_out)) return PCC_OK;
-  PCC_REQUIRE(d_cells && h_cell_offsets && h_cell_offsets[0] >= 0, PCC_E_ARG, "%s: the cells of the frames are needed", who);
-  PCC_REQUIRE(cap_bytes >= bytes, PCC_E_NOMEM, "%s: %lld bytes, capacity %lld", who, (long long)bytes, (long long)cap_bytes);
-  std::vector<ADFrame> tab;
+  bool idle;
+  PCC_TRY(a_dec_counted(d, "values", &idle));
+  if (idle) return PCC_OK;
   std::vector<A2Order> order;
   std::vector<int32_t> cross;   // the masks of versions 11 and 14
-  int64_t body_off = 0, chunks = 0, nctx_max = 0, cw_max = 0, blocks = 0, n_max = 0;
-  const int64_t cell0 = h_cell_offsets[0];
-  for (int f = 0; f < n_frames; ++f) {
-    const Attr2Info& o = info[(size_t)f];
-    const Attr2Plan& pl = plan[(size_t)f];
-    if (pl.m == 0) continue;
-    tab.push_back(a_dec_row(o, body_off, h_out_offsets[f], chunks, pl.chunks, pl.m, pl.last_words));
-    order.push_back(A2Order{h_cell_offsets[f] - cell0, pl.m, (int32_t)blocks, lod + o.slod});
-    cross.push_back(o.cross);
-    n_max = std::max(n_max, pl.m);
-    for (int64_t k = 0; k + 1 < pl.chunks; ++k) cw_max = std::max<int64_t>(cw_max, attr_u32(h_blobs[f] + o.off_table + 4 * k));
-    cw_max = std::max<int64_t>(cw_max, pl.last_words);
-    body_off += a_round(pl.bytes - o.off_p0, 16);
-    chunks += pl.chunks;
-    blocks += nblk(pl.m, 256);
-    nctx_max = std::max<int64_t>(nctx_max, o.nctx);
-  }
-  const int64_t cells_all = h_cell_offsets[n_frames] - cell0;
-  const int32_t* cells = d_cells + 3 * cell0;
-  const int nf = (int)tab.size();
-  hipStream_t st = ctx->stream;
-  // the rows, then (versions 11 and 14) the masks | the order rows
-  const size_t ftab_b = pcc_align((size_t)nf * (sizeof(ADFrame) + (xc ? 4 : 0))), ord_b = pcc_align((size_t)nf * sizeof(A2Order));
-  const size_t tab_b = ftab_b + ord_b;
+  int64_t blocks, cells_all;
+  const int32_t* cells;
+  PCC_TRY(a_dec_order(d, d_cells, h_cell_offsets, &order, &blocks, &cells_all, &cells));
+  for (int f = 0; f < n_frames; ++f)
+    if (d.in[(size_t)f].n_dec) cross.push_back(info[(size_t)f].cross);
+  d.order = order.data();
+  if (xc) d.masks = cross.data();
+  const int nf = d.nf;
   const size_t keys_b = pcc_align((size_t)cells_all * 8), u32_b = pcc_align((size_t)cells_all * 4), pk_b = pcc_align((size_t)cells_all * 2);
   // 17 bin bases per frame | 16 counts per frame | status per frame: the last two come back in one copy
   const size_t hist_b = pcc_align((size_t)blocks * kA2Bins * 4), bins_b = pcc_align((size_t)nf * 34 * 4 + 64);
-  PCC_TRY(pcc_arena_reserve(ctx, tab_b + pcc_align((size_t)bodies + 16) + (d_out ? 1 : 2) * pcc_align((size_t)bytes) + keys_b +
-                                     2 * u32_b + pk_b + hist_b + bins_b + 8192));
-  uint8_t* d_in = (uint8_t*)pcc_arena_alloc(ctx, tab_b + (size_t)bodies + 16);
-  uint8_t* out = d_out ? d_out : (uint8_t*)pcc_arena_alloc(ctx, (size_t)bytes);
-  uint8_t* resid = (uint8_t*)pcc_arena_alloc(ctx, (size_t)bytes);
+  PCC_TRY(a_dec_plan(d, d_out ? 1 : 2, keys_b + 2 * u32_b + pk_b + hist_b + bins_b + 8192));
+  hipStream_t st = ctx->stream;
+  uint8_t* resid = (uint8_t*)pcc_arena_alloc(ctx, (size_t)d.bytes);
   uint64_t* keys = (uint64_t*)pcc_arena_alloc(ctx, keys_b);
   uint32_t* rank = (uint32_t*)pcc_arena_alloc(ctx, u32_b);
   uint32_t* first = (uint32_t*)pcc_arena_alloc(ctx, u32_b);
   uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, pk_b);
   uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, hist_b);
   uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, bins_b);
-  if (!d_in || !out || !resid || !keys || !rank || !first || !packed || !hist || !bins) return PCC_E_NOMEM;
+  if (!resid || !keys || !rank || !first || !packed || !hist || !bins) return PCC_E_NOMEM;
   uint32_t* counts = bins + (size_t)nf * kA2Bins;
   int32_t* status = (int32_t*)(counts + (size_t)nf * 16);
-  PccProfScope prof(ctx, "attr_decode_lod", points, nf, chunks, 0);
-  const size_t in_b = tab_b + (size_t)bodies;
-  uint8_t *down, *back;
-  PCC_TRY(a_dec_stage(ctx, h_out, in_b, bytes, (size_t)nf * 17 * 4, &down, &back));
-  uint8_t* stage = (uint8_t*)ctx->stage;
-  memcpy(stage, tab.data(), (size_t)nf * sizeof(ADFrame));
-  if (xc) memcpy(stage + (size_t)nf * sizeof(ADFrame), cross.data(), (size_t)nf * 4);
-  memcpy(stage + ftab_b, order.data(), (size_t)nf * sizeof(A2Order));
-  for (int f = 0, k = 0; f < n_frames; ++f) {
-    if (plan[(size_t)f].m == 0) continue;
-    const Attr2Info& o = info[(size_t)f];
-    memcpy(stage + tab_b + tab[(size_t)k++].body_off, h_blobs[f] + o.off_p0, (size_t)(plan[(size_t)f].bytes - o.off_p0));   // the level's bytes only
-  }
-  PCC_HIP(hipMemcpyAsync(d_in, stage, in_b, hipMemcpyHostToDevice, st));
+  PccProfScope prof(ctx, "attr_decode_lod", d.points, nf, d.chunks, 0);
+  PCC_TRY(a_dec_send(d, (size_t)nf * 17 * 4));
   PCC_HIP(hipMemsetAsync(status, 0, (size_t)nf * 4, st));
-  const ADFrame* d_tab = (const ADFrame*)d_in;
-  const A2Order* d_ord = (const A2Order*)(d_in + ftab_b);
+  const ADFrame* d_tab = (const ADFrame*)d.d_in;
+  const A2Order* d_ord = (const A2Order*)(d.d_in + d.ord_at);
   // the introduction order of the cells: nothing of it depends on the attribute stream
   hipLaunchKernelGGL(k_a2_size<true>, dim3((unsigned)blocks), dim3(256), 0, st, (const void*)cells, d_ord, nf, keys, packed, hist);
   PCC_CHECK_LAUNCH();
@@ -2252,32 +2282,24 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
                      (const uint32_t*)hist, (const uint32_t*)bins, (const AFrame*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr,
                      rank, first);
   PCC_CHECK_LAUNCH();
-  PCC_TRY(a_launch_dec<true>(st, chunks, d_in, tab_b, nf, nctx_max, cw_max, resid, status));
+  PCC_TRY(a_launch_dec<true>(d, resid, status));
   if (xc) {
-    hipLaunchKernelGGL(k_ax_inv, dim3(nblk(n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab,
-                       (const int32_t*)(d_in + (size_t)nf * sizeof(ADFrame)), resid);
+    hipLaunchKernelGGL(k_ax_inv, dim3(nblk(d.n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, (const int32_t*)(d.d_in + d.masks_at()), resid);
     PCC_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL((nl ? k_a2_walk<true> : k_a2_walk<false>), dim3((unsigned)blocks), dim3(256), 0, st, d_ord, nf, d_tab,
-                     (const uint32_t*)rank, (const uint32_t*)first, (const uint8_t*)resid, out, status);
+                     (const uint32_t*)rank, (const uint32_t*)first, (const uint8_t*)resid, d.out, status);
   PCC_CHECK_LAUNCH();
-  uint32_t* h_counts = (uint32_t*)back;
-  int32_t* h_status = (int32_t*)(h_counts + (size_t)nf * 16);
-  if (down) PCC_HIP(hipMemcpyAsync(down, out, (size_t)bytes, hipMemcpyDeviceToHost, st));
-  PCC_HIP(hipMemcpyAsync(h_counts, counts, (size_t)nf * 17 * 4, hipMemcpyDeviceToHost, st));
-  PCC_HIP(hipStreamSynchronize(st));
-  for (int f = 0, k = 0; f < n_frames; ++f) {
-    if (plan[(size_t)f].m == 0) continue;
-    // the coarser levels' counts of the header against those of the cells themselves
+  // counts and status come back in one copy; per frame, the coarser levels' counts of the header against those of the
+  // cells themselves, then its status
+  const auto counts_match = [&](int f, int k) -> int {
+    const uint32_t* h_counts = (const uint32_t*)d.back + 16 * k;
     for (int j = 0; lod + j <= kAttrMaxLod; ++j)
-      PCC_REQUIRE((int64_t)h_counts[16 * k + j] == info[(size_t)f].cells[lod + j], PCC_E_STREAM,
+      PCC_REQUIRE((int64_t)h_counts[j] == info[(size_t)f].cells[lod + j], PCC_E_STREAM,
                   "%s: frame %d: attribute blob: level of detail %d announces %lld values, the cells give %u", who, f, lod + j,
-                  (long long)info[(size_t)f].cells[lod + j], h_counts[16 * k + j]);
-    const int32_t bad = h_status[k++];
-    PCC_REQUIRE(bad == 0, PCC_E_STREAM,
-                "%s: frame %d: attribute blob: corrupt stream (status %d: 1 = words, 4 = final state, 8 = predictor chain%s)", who, f, bad,
-                nl ? ", 16 = reconstruction out of range" : "");
-  }
-  a_copy_out(h_out, down, bytes);
-  return PCC_OK;
+                  (long long)info[(size_t)f].cells[lod + j], h_counts[j]);
+    return PCC_OK;
+  };
+  return a_dec_finish(d, counts, (size_t)nf * 17 * 4, 0, (size_t)nf * 16 * 4,
+                      nl ? ", 8 = predictor chain, 16 = reconstruction out of range" : ", 8 = predictor chain", counts_match);
 }

@@ -373,7 +373,7 @@ static inline int attr2_parse(const uint8_t* b, int64_t len, int lod, bool need_
 //   u32 words[n_chunks] | chunk payloads                  (n == 0: the 12 bytes up to payload_len = 0; they record no q)
 //
 // Byte 19 keeps the odd parity of the eight bytes above, so it differs from each of them in two bits; it is not one of
-// attr_kind's and has its own predicate (attr_t_kind) and parser (attr_t_parse).
+// attr_kind's and has its own predicate (attr_t_kind) and parser (attr_t_parse, over attr_tc_parse below).
 // The frame's n distinct points in Morton order, their 48-bit keys key_i (biased by 32768 >> slod) and merged values v_i
 // per channel; H = 2^(8 bpv - 1), mask = 2 H - 1, q = qstep in 1 .. H - 1:
 //   sublevel of introduction   b(0) = 48; b(i) = hb(key_i xor key_{i-1}) in 0 .. 47: point i is the first leaf of the
@@ -409,63 +409,6 @@ struct AttrTInfo : AttrInfo {
 
 static inline bool attr_t_kind(int version) { return version == kAttrTVersion; }
 
-// b[0 .. len): the whole blob, and nothing behind it; or (prefix: pcc_attr_info) the blob or a prefix of it that reaches q
-// (16 bytes), of which every part of the header that is there is checked as the whole blob's is — S and n_chunks against
-// n and the blob's announced length, p0, the chunk table against that length.  Nothing beyond b[len) is read.
-static inline int attr_t_parse(const uint8_t* b, int64_t len, AttrTInfo* o, bool prefix = false) {
-  ATTR2_REQUIRE(b && len >= kAttrHead && b[0] == 'A' && attr_t_kind(b[1]), "attribute blob v19: bad header (len=%lld)", (long long)len);
-  o->version = kAttrTVersion;
-  o->max_error = 0;
-  o->cross = 0;
-  o->qstep = 0;
-  o->bpv = b[2] & 15;
-  o->slod = b[2] >> 4;
-  o->c = b[3];
-  ATTR2_REQUIRE((o->bpv == 1 || o->bpv == 2) && o->c >= 1 && o->c <= 4 && o->slod <= kAttrMaxLod,
-                "attribute blob v19: %d bytes per value, %d channels", o->bpv, o->c);
-  o->nctx = attr_contexts(o->bpv, o->c);
-  o->n = (int64_t)attr_u32(b + 4);
-  const int64_t payload = (int64_t)attr_u32(b + 8), total = kAttrHead + payload;
-  ATTR2_REQUIRE(prefix ? len <= total : len == total, "attribute blob v19: payload of %lld bytes in a blob of %lld", (long long)payload,
-                (long long)len);
-  o->S = o->nc = 0;
-  o->off_p0 = o->off_table = o->off_payload = kAttrHead;
-  o->payload_words = 0;
-  if (o->n == 0) {
-    ATTR2_REQUIRE(payload == 0, "attribute blob v19: no points, %lld bytes of payload", (long long)payload);
-    return PCC_OK;
-  }
-  o->off_p0 = kAttrTHead;
-  o->off_table = o->off_p0 + 2 * (int64_t)o->nctx;
-  ATTR2_REQUIRE(o->n < ((int64_t)1 << 27) && payload >= o->off_table - kAttrHead + 4 + 2 * 3 * kAttrLanes,
-                "attribute blob v19: %lld points, payload %lld", (long long)o->n, (long long)payload);
-  ATTR2_REQUIRE(len >= kAttrHead + 4, "attribute blob v19: truncated in front of qstep (len=%lld)", (long long)len);
-  o->qstep = attr_u32(b + kAttrHead);
-  ATTR2_REQUIRE(o->qstep >= 1 && o->qstep <= attr_max_error(o->bpv), "attribute blob v19: qstep %u with %d bytes per value", o->qstep,
-                o->bpv);
-  if (len < kAttrTHead && prefix) return PCC_OK;
-  ATTR2_REQUIRE(len >= kAttrTHead, "attribute blob v19: truncated header");
-  o->S = (int64_t)attr_u32(b + kAttrHead + 4);
-  o->nc = (int64_t)attr_u32(b + kAttrHead + 8);
-  ATTR2_REQUIRE(o->S >= 1 && o->S * o->c <= kAttrMaxValues && o->nc >= 1 && o->nc <= o->n && kAttrLanes * o->S * o->nc >= o->n &&
-                    kAttrLanes * o->S * (o->nc - 1) < o->n,
-                "attribute blob v19: %lld points in %lld chunks of 64 x %lld", (long long)o->n, (long long)o->nc, (long long)o->S);
-  ATTR2_REQUIRE(total - o->off_table >= 4 * o->nc, "attribute blob v19: truncated chunk table");
-  if (len < o->off_table && prefix) return PCC_OK;
-  ATTR2_REQUIRE(len >= o->off_table, "attribute blob v19: truncated header");
-  uint32_t bad_p = 0;
-  ATTR2_REQUIRE(attr_check_p0(b, o->off_p0, o->nctx, &bad_p), "attribute blob v19: initial probability %u", bad_p);
-  if (len - o->off_table < 4 * o->nc && prefix) return PCC_OK;
-  int64_t words = 0, bad_k = 0, bad_cw = 0;
-  ATTR2_REQUIRE(attr_sum_chunks(b + o->off_table, o->nc, o->bpv, &words, &bad_k, &bad_cw), "attribute blob v19: chunk %lld has %lld words",
-                (long long)bad_k, (long long)bad_cw);
-  o->off_payload = o->off_table + 4 * o->nc;
-  o->payload_words = words;
-  ATTR2_REQUIRE(o->off_payload + 2 * words == total, "attribute blob v19: chunks take %lld bytes, blob has %lld", (long long)(2 * words),
-                (long long)(total - o->off_payload));
-  return PCC_OK;
-}
-
 // ---- version 21: transform-coded attributes with a colour transform and one step per channel ------------------------
 // A tenth kind (compress(..., qstep=(q0, q1, ..)) and compress(..., qstep=q, colour="ycocg")): version 19 with a colour
 // word and c steps where version 19 keeps its one q:
@@ -475,7 +418,7 @@ static inline int attr_t_parse(const uint8_t* b, int64_t len, AttrTInfo* o, bool
 //                                                          neither colour nor steps)
 //
 // Byte 21 = 10101b has odd parity as the nine bytes above, so it differs from each of them in two bits; it has its own
-// predicate (attr_c_kind) and parser (attr_c_parse), and every other parser refuses it.
+// predicate (attr_c_kind) and parser (attr_c_parse, over attr_tc_parse below), and every other parser refuses it.
 // Everything is version 19's — keys, sublevels, pairs, weights, forward and inverse lift, the mean, coding order,
 // entropy stage, the clamp of an index at H - 1 — except:
 //   steps      q[ch] in 1 .. H - 1 for every channel ch < c; the step of a pair in channel ch is
@@ -504,67 +447,85 @@ struct AttrCInfo : AttrTInfo {
 static inline bool attr_c_kind(int version) { return version == kAttrCVersion; }
 static inline int attr_c_head(int c) { return kAttrHead + 4 + 4 * c + 8; }   // .. | u32 colour | u32 q[c] | u32 S | u32 n_chunks
 
-// b[0 .. len): the whole blob, and nothing behind it; or (prefix: pcc_attr_info, pcc_attr_transform_info) the blob or a
-// prefix of it that reaches q[c - 1] (16 + 4 c bytes), of which every part of the header that is there is checked as the
-// whole blob's is.  Nothing beyond b[len) is read.
-static inline int attr_c_parse(const uint8_t* b, int64_t len, AttrCInfo* o, bool prefix = false) {
-  ATTR2_REQUIRE(b && len >= kAttrHead && b[0] == 'A' && attr_c_kind(b[1]), "attribute blob v21: bad header (len=%lld)", (long long)len);
-  o->version = kAttrCVersion;
+// ---- versions 19 and 21: one parser ----------------------------------------------------------------------------------
+// b[0 .. len): the whole blob, and nothing behind it; or (prefix: pcc_attr_info, pcc_attr_qstep, pcc_attr_transform_info)
+// the blob or a prefix of it that reaches its last step (q of version 19: 16 bytes; q[c - 1] of version 21: 16 + 4 c),
+// of which every part of the header that is there is checked as the whole blob's is — S and n_chunks against n and the
+// blob's announced length, p0, the chunk table against that length.  Nothing beyond b[len) is read.
+// oc: where version 21's colour word and steps go (o itself as an AttrCInfo); nullptr: version 19.  The two heads differ
+// in what stands between payload_len and S: one q, or the colour word and c steps.
+static inline int attr_tc_parse(const uint8_t* b, int64_t len, AttrTInfo* o, AttrCInfo* oc, bool prefix) {
+  const int v = oc ? kAttrCVersion : kAttrTVersion;
+  ATTR2_REQUIRE(b && len >= kAttrHead && b[0] == 'A' && b[1] == v, "attribute blob v%d: bad header (len=%lld)", v, (long long)len);
+  o->version = v;
   o->max_error = 0;
   o->cross = 0;
   o->qstep = 0;
-  o->colour = 0;
-  for (int ch = 0; ch < 4; ++ch) o->q[ch] = 0;
+  if (oc) oc->colour = 0;
+  for (int ch = 0; oc && ch < 4; ++ch) oc->q[ch] = 0;
   o->bpv = b[2] & 15;
   o->slod = b[2] >> 4;
   o->c = b[3];
   ATTR2_REQUIRE((o->bpv == 1 || o->bpv == 2) && o->c >= 1 && o->c <= 4 && o->slod <= kAttrMaxLod,
-                "attribute blob v21: %d bytes per value, %d channels", o->bpv, o->c);
+                "attribute blob v%d: %d bytes per value, %d channels", v, o->bpv, o->c);
   o->nctx = attr_contexts(o->bpv, o->c);
   o->n = (int64_t)attr_u32(b + 4);
   const int64_t payload = (int64_t)attr_u32(b + 8), total = kAttrHead + payload;
-  ATTR2_REQUIRE(prefix ? len <= total : len == total, "attribute blob v21: payload of %lld bytes in a blob of %lld", (long long)payload,
+  ATTR2_REQUIRE(prefix ? len <= total : len == total, "attribute blob v%d: payload of %lld bytes in a blob of %lld", v, (long long)payload,
                 (long long)len);
   o->S = o->nc = 0;
   o->off_p0 = o->off_table = o->off_payload = kAttrHead;
   o->payload_words = 0;
   if (o->n == 0) {
-    ATTR2_REQUIRE(payload == 0, "attribute blob v21: no points, %lld bytes of payload", (long long)payload);
+    ATTR2_REQUIRE(payload == 0, "attribute blob v%d: no points, %lld bytes of payload", v, (long long)payload);
     return PCC_OK;
   }
-  const int head = attr_c_head(o->c);
+  const int head = oc ? attr_c_head(o->c) : kAttrTHead;   // S and n_chunks are its last 8 bytes
   o->off_p0 = head;
   o->off_table = o->off_p0 + 2 * (int64_t)o->nctx;
   ATTR2_REQUIRE(o->n < ((int64_t)1 << 27) && payload >= o->off_table - kAttrHead + 4 + 2 * 3 * kAttrLanes,
-                "attribute blob v21: %lld points, payload %lld", (long long)o->n, (long long)payload);
-  ATTR2_REQUIRE(len >= head - 8, "attribute blob v21: truncated in front of its steps (len=%lld)", (long long)len);
-  o->colour = attr_u32(b + kAttrHead);
-  ATTR2_REQUIRE(o->colour <= 1 && (o->colour == 0 || o->c >= 3), "attribute blob v21: colour transform %u with %d channels", o->colour,
-                o->c);
-  for (int ch = 0; ch < o->c; ++ch) {
-    o->q[ch] = attr_u32(b + kAttrHead + 4 + 4 * ch);
-    ATTR2_REQUIRE(o->q[ch] >= 1 && o->q[ch] <= attr_max_error(o->bpv), "attribute blob v21: qstep %u of channel %d with %d bytes per value",
-                  o->q[ch], ch, o->bpv);
+                "attribute blob v%d: %lld points, payload %lld", v, (long long)o->n, (long long)payload);
+  ATTR2_REQUIRE(len >= head - 8, "attribute blob v%d: truncated in front of %s (len=%lld)", v, oc ? "its steps" : "qstep", (long long)len);
+  if (oc) {
+    oc->colour = attr_u32(b + kAttrHead);
+    ATTR2_REQUIRE(oc->colour <= 1 && (oc->colour == 0 || o->c >= 3), "attribute blob v21: colour transform %u with %d channels", oc->colour,
+                  o->c);
+    for (int ch = 0; ch < o->c; ++ch) {
+      oc->q[ch] = attr_u32(b + kAttrHead + 4 + 4 * ch);
+      ATTR2_REQUIRE(oc->q[ch] >= 1 && oc->q[ch] <= attr_max_error(o->bpv), "attribute blob v21: qstep %u of channel %d with %d bytes per value",
+                    oc->q[ch], ch, o->bpv);
+    }
+  } else {
+    o->qstep = attr_u32(b + kAttrHead);
+    ATTR2_REQUIRE(o->qstep >= 1 && o->qstep <= attr_max_error(o->bpv), "attribute blob v19: qstep %u with %d bytes per value", o->qstep,
+                  o->bpv);
   }
   if (len < head && prefix) return PCC_OK;
-  ATTR2_REQUIRE(len >= head, "attribute blob v21: truncated header");
+  ATTR2_REQUIRE(len >= head, "attribute blob v%d: truncated header", v);
   o->S = (int64_t)attr_u32(b + head - 8);
   o->nc = (int64_t)attr_u32(b + head - 4);
   ATTR2_REQUIRE(o->S >= 1 && o->S * o->c <= kAttrMaxValues && o->nc >= 1 && o->nc <= o->n && kAttrLanes * o->S * o->nc >= o->n &&
                     kAttrLanes * o->S * (o->nc - 1) < o->n,
-                "attribute blob v21: %lld points in %lld chunks of 64 x %lld", (long long)o->n, (long long)o->nc, (long long)o->S);
-  ATTR2_REQUIRE(total - o->off_table >= 4 * o->nc, "attribute blob v21: truncated chunk table");
+                "attribute blob v%d: %lld points in %lld chunks of 64 x %lld", v, (long long)o->n, (long long)o->nc, (long long)o->S);
+  ATTR2_REQUIRE(total - o->off_table >= 4 * o->nc, "attribute blob v%d: truncated chunk table", v);
   if (len < o->off_table && prefix) return PCC_OK;
-  ATTR2_REQUIRE(len >= o->off_table, "attribute blob v21: truncated header");
+  ATTR2_REQUIRE(len >= o->off_table, "attribute blob v%d: truncated header", v);
   uint32_t bad_p = 0;
-  ATTR2_REQUIRE(attr_check_p0(b, o->off_p0, o->nctx, &bad_p), "attribute blob v21: initial probability %u", bad_p);
+  ATTR2_REQUIRE(attr_check_p0(b, o->off_p0, o->nctx, &bad_p), "attribute blob v%d: initial probability %u", v, bad_p);
   if (len - o->off_table < 4 * o->nc && prefix) return PCC_OK;
   int64_t words = 0, bad_k = 0, bad_cw = 0;
-  ATTR2_REQUIRE(attr_sum_chunks(b + o->off_table, o->nc, o->bpv, &words, &bad_k, &bad_cw), "attribute blob v21: chunk %lld has %lld words",
+  ATTR2_REQUIRE(attr_sum_chunks(b + o->off_table, o->nc, o->bpv, &words, &bad_k, &bad_cw), "attribute blob v%d: chunk %lld has %lld words", v,
                 (long long)bad_k, (long long)bad_cw);
   o->off_payload = o->off_table + 4 * o->nc;
   o->payload_words = words;
-  ATTR2_REQUIRE(o->off_payload + 2 * words == total, "attribute blob v21: chunks take %lld bytes, blob has %lld", (long long)(2 * words),
+  ATTR2_REQUIRE(o->off_payload + 2 * words == total, "attribute blob v%d: chunks take %lld bytes, blob has %lld", v, (long long)(2 * words),
                 (long long)(total - o->off_payload));
   return PCC_OK;
+}
+
+static inline int attr_t_parse(const uint8_t* b, int64_t len, AttrTInfo* o, bool prefix = false) {
+  return attr_tc_parse(b, len, o, nullptr, prefix);
+}
+static inline int attr_c_parse(const uint8_t* b, int64_t len, AttrCInfo* o, bool prefix = false) {
+  return attr_tc_parse(b, len, o, o, prefix);
 }
