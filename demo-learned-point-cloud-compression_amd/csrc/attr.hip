@@ -57,6 +57,15 @@
 // k_at_lift<false, const int32_t*>, and k_ac_store in place of k_at_store where a frame of the call has colour = 1.
 // tests/attr_colour_ref.py restates the kind in numpy.
 //
+// Version 22 (attr_blob.h has the rule and the layout): version 21 under weights a decoder at a cut can form, its levels
+// of detail 0 .. K prefixes of the blob.  Encoder: version 21's launches, behind the order stage k_as_flag (the K-cell
+// firsts) and the device-wide scan, k_as_counts (version 2's 16 counts, from the sublevels' counts), k_as_lift<true> in
+// place of k_at_lift, and k_a_pack<true, true, false, true, const int32_t*, int> for the head; the K-cell totals are
+// sums of the sublevel counts that the order stage's one synchronisation already brings back.  Decoder
+// (pcc_attr_decode_frames_lod at lod 0 .. K, against the cells of that lod): the order stage on the cell keys, the lane
+// decoder on the level's prefix as version 2's, the cells' counts against the head's, k_as_flag and the scan, k_at_root,
+// k_as_lift<false> per occupied sublevel, k_as_store.  tests/attr_scalable_ref.py restates the kind in numpy.
+//
 // Host side: the kinds share one encode sequence (a_encode_frames over an AEncKind, the entry point's kind resolved
 // once) and one decode-call skeleton (ADecCall: accounting, rows, layout, upload, status) under the three decoders, each
 // of which keeps its parser, its side tables, its arena arrays and its kernels; DESIGN.md, "attr.hip: one encode path,
@@ -338,6 +347,9 @@ __global__ __launch_bounds__(64) void k_a_enc(const uint16_t* __restrict__ merge
 // kernels that read it (Aux = const int32_t*); the instantiations without it keep their arguments
 __device__ __forceinline__ const int32_t* a_aux() { return nullptr; }
 __device__ __forceinline__ const int32_t* a_aux(const int32_t* p) { return p; }
+// version 22: the sender's K behind the table (Aux = const int32_t*, int)
+__device__ __forceinline__ const int32_t* a_aux(const int32_t* p, int) { return p; }
+__device__ __forceinline__ int a_aux_k(const int32_t*, int k) { return k; }
 
 // the blobs, assembled where `out_all` points (pinned host memory), frame f's at out_off: frame f owns workgroups
 // [cb + f, cb + f + nc + 1) — workgroup k < nc of them moves chunk k, workgroup nc writes the header; len_out[f] =
@@ -347,7 +359,8 @@ __device__ __forceinline__ const int32_t* a_aux(const int32_t* p) { return p; }
 // cross_all[f] = m != 0 gets the cross form of the version byte and its mask above the channels of byte 3.  TR (with NL
 // and without V2): version 19's head — version 4's with q = h.e where e stands, byte 19 and the slod nibble.  TC (with
 // TR): version 21's head — byte 21, and where q stands the colour word and the frame's c steps (aux_all[5 f + 4] and
-// aux_all[5 f + ch], a_aux(aux...)), everything else c words later
+// aux_all[5 f + ch], a_aux(aux...)), everything else c words later.  SC (with V2, NL, TR and TC; Aux = const int32_t*,
+// int): version 22's head — byte 22, K behind the steps and version 2's 16 counts behind K
 template <bool V2, bool NL = false, bool XC = false, bool TR = false, typename... Aux>
 __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ work_all, const AFrame* __restrict__ tab, int nf,
                                                 const uint16_t* __restrict__ states_all, const uint16_t* __restrict__ lens_all,
@@ -355,7 +368,7 @@ __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ wor
                                                 uint8_t* __restrict__ out_all, long long* __restrict__ len_out,
                                                 const uint32_t* __restrict__ cells_all, int slod,
                                                 const int32_t* __restrict__ cross_all, Aux... aux) {
-  constexpr bool TC = sizeof...(Aux) > 0;
+  constexpr bool TC = sizeof...(Aux) > 0, SC = sizeof...(Aux) > 1;
   __shared__ unsigned long long s_sum[256];
   __shared__ uint32_t s_off[kLanes + 1];
   const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].cb + i; });
@@ -375,7 +388,7 @@ __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ wor
   const unsigned long long before = s_sum[0];
   constexpr int X0 = NL ? 1 : 0;
   int X = X0;
-  if constexpr (TC) X = 1 + h.c;
+  if constexpr (TC) X = 1 + h.c + (SC ? 1 : 0);
   const unsigned long long head = (unsigned long long)((V2 ? kAttr2Head : kAttrHead + 8) + 4 * X) + 2ull * h.nctx + 4ull * nc;
   if (k == nc) {
     const unsigned long long total = head + before * 2;
@@ -396,10 +409,11 @@ __global__ __launch_bounds__(256) void k_a_pack(const uint16_t* __restrict__ wor
       o32[1] = (uint32_t)h.n;
       o32[2] = (uint32_t)(total - kAttrHead);
       if constexpr (TC) {
-        out[1] = (uint8_t)kAttrCVersion;
+        out[1] = (uint8_t)(SC ? kAttrSVersion : kAttrCVersion);
         const int32_t* aux_all = a_aux(aux...);
         o32[3] = (uint32_t)aux_all[5 * f + 4];
         for (int ch = 0; ch < h.c; ++ch) o32[4 + ch] = (uint32_t)aux_all[5 * f + ch];
+        if constexpr (SC) o32[4 + h.c] = (uint32_t)a_aux_k(aux...);
       } else if constexpr (NL) {
         o32[3] = (uint32_t)h.e;
       }
@@ -1090,12 +1104,14 @@ __device__ __forceinline__ int64_t at_floor_div(int64_t a, int64_t w) {
 
 // s = max(2, isqrt(floor(q^2 w / (wa wb)))): the quotient is at most 2 q^2 < 2^31, which a double holds exactly; the
 // root's estimate is corrected in integers
-__device__ __forceinline__ int64_t at_step(int64_t q, int64_t wa, int64_t wb) {
-  const uint64_t v = (uint64_t)(q * q) * (uint64_t)(wa + wb) / ((uint64_t)wa * (uint64_t)wb);
+__device__ __forceinline__ int64_t at_root2(uint64_t v) {   // max(2, isqrt(v)), v < 2^52
   uint64_t r = (uint64_t)sqrt((double)v);
   while (r * r > v) --r;
   while ((r + 1) * (r + 1) <= v) ++r;
   return r < 2 ? 2 : (int64_t)r;
+}
+__device__ __forceinline__ int64_t at_step(int64_t q, int64_t wa, int64_t wb) {
+  return at_root2((uint64_t)(q * q) * (uint64_t)(wa + wb) / ((uint64_t)wa * (uint64_t)wb));
 }
 
 // The pairs of sublevel t, frame = blockIdx.y: thread j takes place bins[..][t] + j of the frame's coding order, point
@@ -1245,6 +1261,145 @@ __global__ __launch_bounds__(256) void k_ac_store(const ADFrame* __restrict__ ta
   for (int ch = 0; ch < c; ++ch) a_store(o, bpv, (uint32_t)x[ch], ch);
 }
 
+// ---- version 22: weights a decoder at a cut can form (attr_blob.h states the rule) ---------------------------------
+// Behind the order stage, over the same rows and blocks.  K: the frame's deepest cut (etab[f].e for the encoder, whose
+// call has one K; dtab[f].max_error for the decoder, whose blobs each bring their own).  lod3 = 3 j for a decoder at cut
+// j (its bins are sublevels t - 3 j), 0 for the encoder.
+//
+// flags[pt0 + i] = 1 where point (cell) i is the first of its K-cell, that is where its sublevel is 3 K or higher; the
+// call's last point also clears the one word behind the flags, so that their exclusive scan g has an entry for every
+// frame's end
+__global__ __launch_bounds__(256) void k_as_flag(const A2Order* __restrict__ tab, int nf, const uint16_t* __restrict__ packed,
+                                                 const AFrame* __restrict__ etab, const ADFrame* __restrict__ dtab, int lod3,
+                                                 uint32_t* __restrict__ flags) {
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].blk0; });
+  const A2Order& h = tab[f];
+  const int64_t i = ((int64_t)blockIdx.x - h.blk0) * blockDim.x + threadIdx.x;
+  if (i >= h.n) return;
+  const int K = etab ? etab[f].e : dtab[f].max_error;
+  flags[h.pt0 + i] = (int)(packed[h.pt0 + i] >> 8) + lod3 >= 3 * K ? 1u : 0u;
+  if (f == nf - 1 && i == h.n - 1) flags[h.pt0 + h.n] = 0u;
+}
+
+// encoder: version 2's 16 counts from the sublevels' starts and counts, cells[16 f + k] = #{i : b(i) >= 3 k}
+__global__ __launch_bounds__(256) void k_as_counts(const uint32_t* __restrict__ bins, int nf, uint32_t* __restrict__ cells) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x, f = t >> 4, k = t & 15;
+  if (f >= nf) return;
+  cells[t] = bins[f * 2 * kATBins + 3 * k] + bins[f * 2 * kATBins + kATBins + 3 * k];
+}
+
+// k_at_lift under version 22's weights, one thread per pair for all channels, the same places, searches and arrays.
+// g: the exclusive scan of k_as_flag's flags over the call's points (differences inside a frame count its K-cells).
+// Bin t of the call's keys is the absolute sublevel t + lod3.  At 3 K and above: two lower bounds and two differences
+// of g; below: one lower bound, no hi, weights 1 : 1 and a step that depends on the sublevel alone.  M from the
+// frame's K-cell count (the points of sublevel 3 K and above, in bins) and the blob's n.
+template <bool ENC>
+__global__ __launch_bounds__(256) void k_as_lift(const uint64_t* __restrict__ keys_all, const A2Order* __restrict__ tab,
+                                                 const uint32_t* __restrict__ bins, const uint32_t* __restrict__ inv, int t,
+                                                 const uint32_t* __restrict__ g_all, int lod3, const AFrame* __restrict__ etab,
+                                                 uint16_t* __restrict__ val_e, uint16_t* __restrict__ idx,
+                                                 const ADFrame* __restrict__ dtab, const uint8_t* __restrict__ x_all,
+                                                 int64_t* __restrict__ val_d, int32_t* __restrict__ status_all,
+                                                 const int32_t* __restrict__ aux_all) {
+  const int f = blockIdx.y;
+  const A2Order& h = tab[f];
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= (int64_t)bins[f * 2 * kATBins + kATBins + t]) return;
+  const int64_t r = (int64_t)bins[f * 2 * kATBins + t] + j;
+  if (r >= h.n) return;
+  const int64_t i = inv[h.pt0 + r];
+  if (i <= 0 || i >= h.n) return;
+  const uint64_t* keys = keys_all + h.pt0;
+  const uint32_t* g = g_all + h.pt0;
+  const int bit = t + (ENC ? h.shift : 0);   // <= 47
+  const int K3 = 3 * (ENC ? etab[f].e : dtab[f].max_error), ta = t + lod3, tk = K3 - lod3;   // 0 <= tk <= 45
+  const bool inside = ta < K3;
+  const uint64_t key = keys[i], low = (1ull << bit) - 1ull;
+  const uint64_t t_lo = key & ~((low << 1) | 1ull), t_hi = (key | low) + 1ull;
+  int64_t lo = 0, hi = i;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < t_lo) lo = mid + 1; else hi = mid;
+  }
+  int64_t ca = 1, cb = 1, M = 1;
+  if (!inside) {
+    int64_t a = i + 1, b = h.n;
+    while (a < b) {
+      const int64_t mid = (a + b) >> 1;
+      if (keys[mid] < t_hi) a = mid + 1; else b = mid;
+    }
+    const int64_t gi = g[i], C = (int64_t)bins[f * 2 * kATBins + tk] + bins[f * 2 * kATBins + kATBins + tk];
+    const int64_t n_all = ENC ? h.n : dtab[f].n;
+    ca = gi - (int64_t)g[lo];
+    cb = (int64_t)g[a] - gi;
+    M = C > 0 ? std::max<int64_t>(1, (2 * n_all + C) / (2 * C)) : 1;
+  }
+  const bool broken = lo >= i || ca < 1 || cb < 1;   // cannot happen with sorted, distinct keys
+  const int64_t w = ca + cb;
+  const int c = ENC ? etab[f].c : dtab[f].c;
+  // s[ch] = max(2, isqrt(v)): v = floor(q^2 w / (ca cb M)) <= 2 q^2, or floor(2 q^2 / 2^floor(2 t / 3))
+  const auto step = [&](int ch) -> int64_t {
+    const uint64_t q = (uint64_t)aux_all[5 * f + ch], q2 = q * q;
+    return at_root2(inside ? (2 * q2) >> (2 * ta / 3) : q2 * (uint64_t)w / ((uint64_t)ca * (uint64_t)cb * (uint64_t)M));
+  };
+  if constexpr (ENC) {
+    const AFrame& fr = etab[f];
+    if (broken) return;
+    const int64_t H = (int64_t)1 << (8 * fr.bpv - 1);
+    const uint32_t mask = (1u << (8 * fr.bpv)) - 1u;
+    uint16_t* v = val_e + fr.val_off;
+    for (int ch = 0; ch < c; ++ch) {
+      const int64_t s = step(ch);
+      const int64_t va = v[lo * c + ch], hh = (int64_t)v[i * c + ch] - va;
+      v[lo * c + ch] = (uint16_t)(va + (inside ? hh >> 1 : at_floor_div(cb * hh, w)));
+      const int64_t m = std::min<int64_t>(((hh < 0 ? -hh : hh) + s / 2) / s, H - 1);
+      idx[fr.val_off + r * c + ch] = (uint16_t)((uint32_t)(hh < 0 ? -m : m) & mask);
+    }
+  } else {
+    const ADFrame& fr = dtab[f];
+    if (broken) {
+      atomicOr(status_all + f, 8);
+      return;
+    }
+    const int bpv = fr.bpv;
+    const uint8_t* x = x_all + fr.out_off + r * c * bpv;
+    int64_t* v = val_d + fr.out_off;
+    for (int ch = 0; ch < c; ++ch) {
+      const int64_t hh = (int64_t)a_load_s(x, bpv, ch) * step(ch);   // |x| < 2^15, s < 2^17; cb < 2^27: no product leaves int64
+      const int64_t va = v[lo * c + ch] - (inside ? hh >> 1 : at_floor_div(cb * hh, w));
+      v[lo * c + ch] = va;
+      v[i * c + ch] = va + hh;
+    }
+  }
+}
+
+// decoder, behind the last sublevel: k_ac_store over the frame's n_dec cells of a level of detail (h.n stays the whole
+// blob's values for the lane decoder).  A copy: a body shared by the two kernels compiles k_ac_store to other instructions
+__global__ __launch_bounds__(256) void k_as_store(const ADFrame* __restrict__ tab, const int32_t* __restrict__ aux_all,
+                                                  const int64_t* __restrict__ val, uint8_t* __restrict__ out_all) {
+  const int f = blockIdx.y;
+  const ADFrame& h = tab[f];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= h.n_dec) return;
+  const int c = h.c, bpv = h.bpv;
+  const int64_t mask = ((int64_t)1 << (8 * bpv)) - 1;
+  int x[4] = {0, 0, 0, 0};
+  for (int ch = 0; ch < c; ++ch) {
+    const int64_t a = val[h.out_off + i * c + ch];
+    x[ch] = (int)(a < 0 ? 0 : (a > mask ? mask : a));
+  }
+  if (c >= 3 && aux_all[5 * f + 4] == 1) {
+    const int H = 1 << (8 * bpv - 1), m = (int)mask;
+    const int co = 2 * (x[1] - H), cg = 2 * (x[2] - H), t = x[0] - (cg >> 1);
+    const int G = cg + t, B = t - (co >> 1), R = B + co;
+    x[0] = R < 0 ? 0 : (R > m ? m : R);
+    x[1] = G < 0 ? 0 : (G > m ? m : G);
+    x[2] = B < 0 ? 0 : (B > m ? m : B);
+  }
+  uint8_t* o = out_all + h.out_off + i * c * bpv;
+  for (int ch = 0; ch < c; ++ch) a_store(o, bpv, (uint32_t)x[ch], ch);
+}
+
 }  // namespace
 
 static inline int64_t a_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
@@ -1291,6 +1446,21 @@ static int a_t_order(hipStream_t st, bool from_cells, const void* src, uint64_t*
   return PCC_OK;
 }
 
+// version 22, what encoder and decoder share behind the order stage: the K-cell firsts of the call's points (k_as_flag)
+// and their exclusive scan, *g (points + 1 entries).  a_s_cells_bytes: what the two arrays and the scan take of the arena
+static size_t a_s_cells_bytes(int64_t points) { return 2 * pcc_align((size_t)(points + 1) * 4) + pcc_scan_scratch_bytes(points + 1) + 512; }
+static int a_s_cells(pcc_ctx* ctx, hipStream_t st, const A2Order* d_ord, int nf, int64_t blocks, const uint16_t* packed, const AFrame* etab,
+                     const ADFrame* dtab, int lod3, int64_t points, const uint32_t** g) {
+  uint32_t* flags = (uint32_t*)pcc_arena_alloc(ctx, (size_t)(points + 1) * 4);
+  uint32_t* scan = (uint32_t*)pcc_arena_alloc(ctx, (size_t)(points + 1) * 4);
+  if (!flags || !scan) return PCC_E_NOMEM;
+  hipLaunchKernelGGL(k_as_flag, dim3((unsigned)blocks), dim3(256), 0, st, d_ord, nf, packed, etab, dtab, lod3, flags);
+  PCC_CHECK_LAUNCH();
+  PCC_TRY(pcc_scan_exclusive_u32(ctx, flags, scan, points + 1, nullptr));
+  *g = scan;
+  return PCC_OK;
+}
+
 // one sublevel of the lift over all frames of a call: forward (ENC; etab, merged, idx) or inverse (dtab, x, val,
 // status).  d_aux (version 21): the frames' steps and colour words; the lift then takes a step per channel from it
 template <bool ENC>
@@ -1309,9 +1479,11 @@ static int a_launch_lift(hipStream_t st, unsigned blocks, int nf, const uint64_t
 
 // version 19, encoder, behind k_a_merge: the order stage, one k_at_lift<true> per occupied sublevel bottom-up over the
 // merged values in place, and the mean; idx then holds x in coding order where the PRED = false coder reads it
+// version 22 (points >= 0: the call's points; cells_out receives where the frames' 16 counts lie): k_as_flag and the
+// scan behind the order stage, k_as_lift in place of k_at_lift, and k_as_counts for the head
 static int a_t_forward(pcc_ctx* ctx, hipStream_t st, const uint64_t* d_keys, const A2Order* d_ord, const AFrame* d_tab, int nf,
                        int64_t blocks, size_t pk_b, size_t hist_b, size_t bins_b, size_t link_b, uint16_t* merged,
-                       uint16_t* idx, uint32_t* h_bins, const int32_t* d_aux) {
+                       uint16_t* idx, uint32_t* h_bins, const int32_t* d_aux, int64_t points = -1, uint32_t** cells_out = nullptr) {
   uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, pk_b);
   uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, hist_b);
   uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, bins_b);
@@ -1319,9 +1491,25 @@ static int a_t_forward(pcc_ctx* ctx, hipStream_t st, const uint64_t* d_keys, con
   if (!packed || !hist || !bins || !inv) return PCC_E_NOMEM;
   unsigned grid[kATBins];
   PCC_TRY(a_t_order(st, false, (const void*)d_keys, nullptr, d_ord, nf, blocks, packed, hist, bins, inv, h_bins, grid));
-  for (int t = 0; t < kATBins - 1; ++t)
-    if (grid[t])
+  const uint32_t* g = nullptr;
+  if (points >= 0) {
+    PCC_TRY(a_s_cells(ctx, st, d_ord, nf, blocks, packed, d_tab, nullptr, 0, points, &g));
+    *cells_out = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nf * 64);
+    if (!*cells_out) return PCC_E_NOMEM;
+    hipLaunchKernelGGL(k_as_counts, dim3(nblk(16 * (int64_t)nf, 256)), dim3(256), 0, st, (const uint32_t*)bins, nf, *cells_out);
+    PCC_CHECK_LAUNCH();
+  }
+  for (int t = 0; t < kATBins - 1; ++t) {
+    if (!grid[t]) continue;
+    if (g) {
+      hipLaunchKernelGGL(k_as_lift<true>, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, d_keys, d_ord, (const uint32_t*)bins,
+                         (const uint32_t*)inv, t, g, 0, d_tab, merged, idx, (const ADFrame*)nullptr, (const uint8_t*)nullptr,
+                         (int64_t*)nullptr, (int32_t*)nullptr, d_aux);
+      PCC_CHECK_LAUNCH();
+    } else {
       PCC_TRY(a_launch_lift<true>(st, grid[t], nf, d_keys, d_ord, bins, inv, t, d_tab, merged, idx, nullptr, nullptr, nullptr, nullptr, d_aux));
+    }
+  }
   hipLaunchKernelGGL(k_at_mean, dim3(nblk(4 * (int64_t)nf, 256)), dim3(256), 0, st, d_tab, nf, (const uint16_t*)merged, idx);
   PCC_CHECK_LAUNCH();
   return PCC_OK;
@@ -1336,6 +1524,7 @@ static int a_t_forward(pcc_ctx* ctx, hipStream_t st, const uint64_t* d_keys, con
 //   7         x   x            max_error   order stage (kept), k_a7_quant
 //   19            x   x        qstep       [k_ac_fwd,] order stage at bit granularity, lift, mean (a_t_forward)
 //   21            x   x   x    1 (unread)  as 19, the steps and the colour word in the aux table
+//   22            x   x   x    K           as 21 with k_as_flag, the scan and k_as_lift; version 2's counts in the head
 // nl: an index stream with one u32 (e, q, or the colour word) directly behind payload_len, so versions 19 and 21 run as
 // version 4 does with a_t_forward in place of k_a4_quant.  A frame with a mask in h_cross is coded as the cross form
 // of the call's version (8, 11, 13, 14)
@@ -1347,20 +1536,22 @@ struct AEncKind {
   const int32_t* h_cross;    // per frame the cross-channel mask m (0: the frame's plain kind), or nullptr
   const int32_t* h_qsteps;   // version 21: q[4]
   int colour;                // version 21: 0 | 1
+  int K;                     // version 22: the deepest cut (0: another kind)
   bool keyed() const { return v2 || tr; }   // d_keys and key_shift are read
 };
 static AEncKind a_kind_plain(int version, int64_t n_kept, int max_error, const int32_t* h_cross) {
   const bool v2 = version == 2, nl = max_error > 0;
-  return AEncKind{attr_version(v2, nl, false), v2, nl, false, false, max_error, n_kept, h_cross, nullptr, 0};
+  return AEncKind{attr_version(v2, nl, false), v2, nl, false, false, max_error, n_kept, h_cross, nullptr, 0, 0};
 }
-static AEncKind a_kind_transform(int64_t n_kept, int qstep, const int32_t* h_qsteps, int colour) {
+static AEncKind a_kind_transform(int64_t n_kept, int qstep, const int32_t* h_qsteps, int colour, int K = 0) {
   const bool tc = h_qsteps != nullptr;
-  return AEncKind{tc ? kAttrCVersion : kAttrTVersion, false, true, true, tc, tc ? 1 : qstep, n_kept, nullptr, h_qsteps, colour};
+  return AEncKind{K ? kAttrSVersion : (tc ? kAttrCVersion : kAttrTVersion), false, true, true, tc, K ? K : (tc ? 1 : qstep), n_kept, nullptr,
+                  h_qsteps, colour, K};
 }
 
 // bytes of a blob in front of its chunk payloads: the kind's head, p0 and the chunk table
 static int64_t a_head_bytes(const AEncKind& k, int c, int nctx, int64_t nc) {
-  const int64_t head = k.tc ? attr_c_head(c) : (k.tr ? kAttrTHead : (k.v2 ? kAttr2Head : kAttrHead + 8) + (k.nl ? 4 : 0));
+  const int64_t head = k.K ? attr_s_head(c) : k.tc ? attr_c_head(c) : (k.tr ? kAttrTHead : (k.v2 ? kAttr2Head : kAttrHead + 8) + (k.nl ? 4 : 0));
   return head + 2 * nctx + 4 * nc;
 }
 
@@ -1377,7 +1568,7 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
                            const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
                            const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys,
                            int key_shift, uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
-  const bool v2 = k.v2, nl = k.nl, tr = k.tr, tc = k.tc, keyed = k.keyed(), drops = k.n_kept >= 0;
+  const bool v2 = k.v2, nl = k.nl, tr = k.tr, tc = k.tc, sc = k.K > 0, keyed = k.keyed(), drops = k.n_kept >= 0;
   PCC_REQUIRE(ctx && h_value_offsets && h_format && h_rows && h_points && h_out && h_offsets && n_frames >= 1 &&
                   n_frames <= 65535 && n_unique >= 0 && cap >= 0,
               PCC_E_ARG, "%s: bad argument (n_frames=%d)", who, n_frames);
@@ -1389,6 +1580,8 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
               PCC_E_ARG, "%s: %lld rows, %lld points", who, (long long)n_keys, (long long)n_unique);
   PCC_REQUIRE(!keyed || (key_shift >= 0 && key_shift <= 45 && key_shift % 3 == 0 && (n_keys == 0 || d_keys)), PCC_E_ARG,
               "%s: bad argument (key_shift=%d)", who, key_shift);
+  PCC_REQUIRE(!sc || k.K + key_shift / 3 <= kAttrMaxLod, PCC_E_ARG, "%s: scalable_to %d with key_shift %d: beyond level of detail %d", who,
+              k.K, key_shift, kAttrMaxLod);
   std::vector<AFrame> tab;
   std::vector<A2Order> order;
   std::vector<int> frame_of;
@@ -1488,7 +1681,7 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
     const size_t x8_b = xc && !v2 && !nl ? merged_b : 0;   // version 8: the run residuals
     // version 19's order stage: packed | hist (49 per block) | starts and counts (98 per frame); inv is one of nl_b's links
     const size_t thist_b = pcc_align((size_t)merge_blocks * kATBins * 4), tbins_b = pcc_align((size_t)nf * 2 * kATBins * 4);
-    const size_t tr_b = tr ? pk_b + thist_b + tbins_b : 0;
+    const size_t tr_b = (tr ? pk_b + thist_b + tbins_b : 0) + (sc ? a_s_cells_bytes(u) + pcc_align((size_t)nf * 64) : 0);
     PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + order_b + nl_b + x8_b + tr_b + 8192));
     AFrame* d_tab = (AFrame*)pcc_arena_alloc(ctx, tab_b);
     uint16_t* merged = (uint16_t*)pcc_arena_alloc(ctx, merged_b);
@@ -1555,7 +1748,7 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
         PCC_CHECK_LAUNCH();
       }
       PCC_TRY(a_t_forward(ctx, st, d_keys, d_ord, (const AFrame*)d_tab, nf, merge_blocks, pk_b, thist_b, tbins_b, link_b, merged, src,
-                          (uint32_t*)(stage + tcnt_at), d_aux));
+                          (uint32_t*)(stage + tcnt_at), d_aux, sc ? u : -1, &cells));
     } else if (nl && !v2) {
       hipLaunchKernelGGL(k_a4_quant, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const uint16_t*)merged,
                          (const AFrame*)d_tab, src);
@@ -1582,7 +1775,12 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
       hipLaunchKernelGGL(k_a_enc<PRED>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)src, (const AFrame*)d_tab, nf,
                          (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
       PCC_CHECK_LAUNCH();
-      if constexpr (TC)
+      if constexpr (TC && V2)
+        hipLaunchKernelGGL((k_a_pack<V2, NL, XC, TR, const int32_t*, int>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st,
+                           (const uint16_t*)work, (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d,
+                           (const uint32_t*)words, (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3,
+                           d_cross, d_aux, k.K);
+      else if constexpr (TC)
         hipLaunchKernelGGL((k_a_pack<V2, NL, XC, TR, const int32_t*>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st,
                            (const uint16_t*)work, (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d,
                            (const uint32_t*)words, (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3,
@@ -1607,6 +1805,7 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
       case 14: rc = a_code(ACoder<true, true, true>{}); break;
       case kAttrTVersion: rc = a_code(ACoder<false, true, false, true>{}); break;
       case kAttrCVersion: rc = a_code(ACoder<false, true, false, true, true>{}); break;
+      case kAttrSVersion: rc = a_code(ACoder<true, true, false, true, true>{}); break;   // V2: the 16 counts in the head
     }
     PCC_TRY(rc);
     PCC_HIP(hipStreamSynchronize(st));
@@ -1714,6 +1913,18 @@ extern "C" int pcc_attr_encode_frames_transform2(pcc_ctx* ctx, const void* d_val
                          h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets);
 }
 
+extern "C" int pcc_attr_encode_frames_transform3(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
+                                                 const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
+                                                 const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, int64_t n_kept,
+                                                 const uint64_t* d_keys, int key_shift, const int32_t h_qstep[4], int colour,
+                                                 int scalable_to, uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
+  PCC_REQUIRE(n_kept >= -1 && h_qstep && (colour == 0 || colour == 1) && scalable_to >= 1 && scalable_to <= kAttrMaxLod, PCC_E_ARG,
+              "pcc_attr_encode_frames_transform3: bad argument (n_kept=%lld colour=%d scalable_to=%d)", (long long)n_kept, colour, scalable_to);
+  return a_encode_frames("pcc_attr_encode_frames_transform3", a_kind_transform(n_kept, 0, h_qstep, colour, scalable_to), ctx, d_values,
+                         h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap,
+                         h_offsets);
+}
+
 // host only: the version byte and byte 3 of a head, checked: its kind, channels and mask
 static int a_head_kind(const char* who, const uint8_t* h_in, int64_t len, bool* scal, bool* nl, bool* xc, int* c, int* m) {
   PCC_REQUIRE(h_in && len >= kAttrHead && h_in[0] == 'A', PCC_E_STREAM, "%s: not an attribute blob (len=%lld)", who, (long long)len);
@@ -1756,8 +1967,26 @@ extern "C" int pcc_attr_transform_info(const uint8_t* h_in, int64_t len, int32_t
   o.colour = 0;
   for (int ch = 0; ch < 4; ++ch) o.q[ch] = 0;
   if (attr_c_kind(ver)) PCC_TRY(attr_c_parse(h_in, len, &o, true));
+  if (attr_s_kind(ver)) {   // version 22 keeps them where version 21 does
+    AttrSInfo s;
+    PCC_TRY(attr_s_parse(h_in, len, 0, kAttrSHead, &s, nullptr));
+    o.colour = s.colour;
+    for (int ch = 0; ch < 4; ++ch) o.q[ch] = s.q[ch];
+  }
   if (h_colour) *h_colour = (int32_t)o.colour;
   for (int ch = 0; h_qstep && ch < 4; ++ch) h_qstep[ch] = (int32_t)o.q[ch];
+  return PCC_OK;
+}
+
+// host only: K of a version-22 head (h_in may be a prefix that reaches K: 20 + 4 c bytes), 0 for every other kind and
+// for a blob without points
+extern "C" int pcc_attr_scalable_to(const uint8_t* h_in, int64_t len, int32_t* h_scalable_to) {
+  int32_t ver = 0;
+  PCC_TRY(pcc_attr_info(h_in, len, &ver, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+  AttrSInfo s;
+  s.K = 0;
+  if (attr_s_kind(ver)) PCC_TRY(attr_s_parse(h_in, len, 0, kAttrSHead, &s, nullptr));
+  if (h_scalable_to) *h_scalable_to = s.K;
   return PCC_OK;
 }
 
@@ -1768,7 +1997,17 @@ extern "C" int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_versio
   int ver, bpv, c, m, slod;
   int64_t n;
   uint32_t e = 0;
-  if (h_in && len >= kAttrHead && h_in[0] == 'A' && (attr_t_kind(h_in[1]) || attr_c_kind(h_in[1]))) {
+  if (h_in && len >= kAttrHead && h_in[0] == 'A' && attr_s_kind(h_in[1])) {
+    // version 22: its own parser; K through pcc_attr_scalable_to, steps and colour through pcc_attr_transform_info
+    AttrSInfo o;
+    const int rc = attr_s_parse(h_in, len, 0, kAttrSHead, &o, nullptr);
+    if (rc != PCC_OK) {
+      const std::string msg = pcc_last_error();
+      pcc_set_error("pcc_attr_info: %s", msg.c_str());
+      return rc;
+    }
+    ver = o.version, bpv = o.bpv, c = o.c, n = o.n, slod = o.slod, scal = true;
+  } else if (h_in && len >= kAttrHead && h_in[0] == 'A' && (attr_t_kind(h_in[1]) || attr_c_kind(h_in[1]))) {
     // versions 19 and 21: their own parser; q through pcc_attr_qstep, steps and colour through pcc_attr_transform_info
     AttrCInfo o;
     const int rc = attr_tc_parse(h_in, len, &o, attr_c_kind(h_in[1]) ? &o : nullptr, true);
@@ -2101,14 +2340,31 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
 // Against the cells its geometry decode left in HBM, as version 2's at lod 0: the order stage over the cells' keys, the
 // lane decoder (x in coding order), the root, one k_at_lift<false> per occupied sublevel top-down, clamp and store.
 // tc: a call of version-21 blobs — their steps and colour words in a table behind the order rows (aux: 5 words per
-// frame), the lift with a step per channel, and k_ac_store in place of k_at_store where a frame has the colour transform
+// frame), the lift with a step per channel, and k_ac_store in place of k_at_store where a frame has the colour transform.
+// Version 22, at level of detail lod (0 for the other two): the cells are those of the geometry at lod, biased by
+// 32768 >> (slod + lod); the lane decoder reads the level's prefix as version 2's does; k_as_flag and the scan behind
+// the order stage, whose counts must be the head's; k_as_lift over the sublevels of the cells' keys (47 - 3 lod .. 0),
+// each frame under its own K (the row's max_error); k_as_store over the cells
 static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
                              const int32_t* d_cells, const int64_t* h_cell_offsets, uint8_t* d_out, uint8_t* h_out, int64_t cap_bytes,
-                             int64_t* h_out_offsets, int32_t* h_format, bool tc) {
+                             int64_t* h_out_offsets, int32_t* h_format, int version, int lod) {
+  const bool sc = attr_s_kind(version), tc = sc || attr_c_kind(version);
   ADecCall d = a_dec_call(who, ctx, h_blobs, n_frames, d_out, h_out, cap_bytes, h_out_offsets, h_format);
-  std::vector<AttrCInfo> info((size_t)n_frames);
+  std::vector<AttrSInfo> info((size_t)n_frames);
   for (int f = 0; f < n_frames; ++f) {
-    AttrCInfo& o = info[(size_t)f];
+    AttrSInfo& o = info[(size_t)f];
+    if (sc) {
+      Attr2Plan pl;
+      const int rc = attr_s_parse(h_blobs[f], h_lens[f], lod, kAttrSDecode, &o, &pl);
+      if (rc != PCC_OK) return a_wrap_error(who, f, rc);
+      if (h_cell_offsets) {
+        const int64_t m = h_cell_offsets[f + 1] - h_cell_offsets[f];
+        PCC_REQUIRE(m == pl.m, PCC_E_STREAM, "%s: frame %d: the attribute blob has %lld values at level of detail %d, its geometry %lld cells",
+                    who, f, (long long)pl.m, lod, (long long)m);
+      }
+      a_dec_count(d, f, ADecIn{&o, pl.m, pl.chunks, pl.last_words, pl.bytes - o.off_p0, (uint32_t)o.K, lod + o.slod});   // K where e is kept
+      continue;
+    }
     const int rc = attr_tc_parse(h_blobs[f], h_lens[f], &o, tc ? &o : nullptr, false);
     if (rc != PCC_OK) return a_wrap_error(who, f, rc);
     if (h_cell_offsets) {
@@ -2128,7 +2384,7 @@ static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const
   const int32_t* cells;
   PCC_TRY(a_dec_order(d, d_cells, h_cell_offsets, &order, &blocks, &cells_all, &cells));
   bool any_colour = false;
-  for (const AttrCInfo& o : info) {
+  for (const AttrSInfo& o : info) {
     if (o.n == 0) continue;
     vals_max = std::max(vals_max, o.n * o.c);
     if (!tc) continue;
@@ -2142,7 +2398,7 @@ static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const
   const size_t keys_b = pcc_align((size_t)cells_all * 8), u32_b = pcc_align((size_t)cells_all * 4), pk_b = pcc_align((size_t)cells_all * 2);
   const size_t hist_b = pcc_align((size_t)blocks * kATBins * 4), bins_b = pcc_align((size_t)nf * 2 * kATBins * 4);
   const size_t val_b = pcc_align((size_t)d.bytes * 8), status_b = pcc_align((size_t)nf * 4 + 64);
-  PCC_TRY(a_dec_plan(d, d_out ? 1 : 2, val_b + keys_b + u32_b + pk_b + hist_b + bins_b + status_b + 8192));
+  PCC_TRY(a_dec_plan(d, d_out ? 1 : 2, val_b + keys_b + u32_b + pk_b + hist_b + bins_b + status_b + (sc ? a_s_cells_bytes(cells_all) : 0) + 8192));
   hipStream_t st = ctx->stream;
   uint8_t* x = (uint8_t*)pcc_arena_alloc(ctx, (size_t)d.bytes);
   int64_t* val = (int64_t*)pcc_arena_alloc(ctx, val_b);
@@ -2163,12 +2419,38 @@ static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const
   PCC_TRY(a_launch_dec<true>(d, x, status));
   unsigned grid[kATBins];
   PCC_TRY(a_t_order(st, true, (const void*)cells, keys, d_ord, nf, blocks, packed, hist, bins, inv, (uint32_t*)d.back, grid));
+  const uint32_t* g = nullptr;
+  if (sc) {
+    // the counts of the cells themselves (read back behind the order stage's synchronisation) against the head's, level by
+    // level from lod up: count[K] among them, which M is formed from
+    for (int f = 0, k = 0; f < n_frames; ++f) {
+      if (d.in[(size_t)f].n_dec == 0) continue;
+      const uint32_t* hb = (const uint32_t*)d.back + (size_t)k++ * 2 * kATBins;
+      for (int j = lod; j <= kAttrMaxLod; ++j) {
+        const int64_t own = (int64_t)hb[3 * (j - lod)] + hb[kATBins + 3 * (j - lod)];
+        PCC_REQUIRE(own == info[(size_t)f].cells[j], PCC_E_STREAM,
+                    "%s: frame %d: attribute blob: level of detail %d announces %lld values, the cells give %lld", who, f, j,
+                    (long long)info[(size_t)f].cells[j], (long long)own);
+      }
+    }
+    PCC_TRY(a_s_cells(ctx, st, d_ord, nf, blocks, packed, nullptr, d_tab, 3 * lod, cells_all, &g));
+  }
   hipLaunchKernelGGL(k_at_root, dim3(nblk(4 * (int64_t)nf, 256)), dim3(256), 0, st, d_tab, nf, (const uint8_t*)x, val);
   PCC_CHECK_LAUNCH();
-  for (int t = kATBins - 2; t >= 0; --t)
-    if (grid[t])
+  for (int t = kATBins - 2; t >= 0; --t) {
+    if (!grid[t]) continue;
+    if (sc) {
+      hipLaunchKernelGGL(k_as_lift<false>, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, (const uint64_t*)keys, d_ord, (const uint32_t*)bins,
+                         (const uint32_t*)inv, t, g, 3 * lod, (const AFrame*)nullptr, (uint16_t*)nullptr, (uint16_t*)nullptr, d_tab,
+                         (const uint8_t*)x, val, status, d_aux);
+      PCC_CHECK_LAUNCH();
+    } else {
       PCC_TRY(a_launch_lift<false>(st, grid[t], nf, keys, d_ord, bins, inv, t, nullptr, nullptr, nullptr, d_tab, x, val, status, d_aux));
-  if (any_colour)
+    }
+  }
+  if (sc)
+    hipLaunchKernelGGL(k_as_store, dim3(nblk(d.n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, d_aux, (const int64_t*)val, d.out);
+  else if (any_colour)
     hipLaunchKernelGGL(k_ac_store, dim3(nblk(d.n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, d_aux, (const int64_t*)val, d.out);
   else
     hipLaunchKernelGGL(k_at_store, dim3(nblk(vals_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, (const int64_t*)val, d.out);
@@ -2181,6 +2463,19 @@ extern "C" int pcc_attr_lod_info(const uint8_t* h_in, int64_t len, int lod, int6
   PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "pcc_attr_lod_info: level of detail %d outside 0 .. %d", lod, kAttrMaxLod);
   PCC_REQUIRE(h_in && len >= 2 && h_in[0] == 'A', PCC_E_STREAM, "pcc_attr_lod_info: not an attribute blob (len=%lld)", (long long)len);
   bool scal = false, nl = false, xc = false;
+  if (attr_s_kind(h_in[1])) {   // version 22: its own parser, version 2's plan; a level above its K is PCC_E_ARG
+    AttrSInfo o;
+    Attr2Plan pl;
+    const int rc = attr_s_parse(h_in, len, lod, kAttrSPlan, &o, &pl);
+    if (rc != PCC_OK) {
+      const std::string m = pcc_last_error();
+      pcc_set_error("pcc_attr_lod_info: %s", m.c_str());
+      return rc;
+    }
+    if (h_bytes) *h_bytes = pl.bytes;
+    if (h_values) *h_values = pl.m;
+    return PCC_OK;
+  }
   PCC_REQUIRE(!attr_t_kind(h_in[1]) && !attr_c_kind(h_in[1]), PCC_E_ARG,
               "pcc_attr_lod_info: attribute blob version %d (a transform-coded blob has no level-of-detail prefixes: the weights of its "
               "transform need every point)", (int)h_in[1]);
@@ -2206,17 +2501,18 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   PCC_REQUIRE(ctx && h_blobs && h_lens && h_out_offsets && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
               "%s: bad argument (n_frames=%d)", who, n_frames);
   PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "%s: level of detail %d outside 0 .. %d", who, lod, kAttrMaxLod);
-  // versions 19 and 21 (one version per call): their own decoder, at lod 0
-  for (const int tv : {kAttrTVersion, kAttrCVersion}) {
+  // versions 19, 21 and 22 (one version per call): their own decoder, the first two at lod 0, 22 up to every blob's K
+  for (const int tv : {kAttrTVersion, kAttrCVersion, kAttrSVersion}) {
     bool any = false;
     for (int f = 0; f < n_frames; ++f) any |= a_is_version(h_blobs[f], h_lens[f], tv);
     if (!any) continue;
     for (int f = 0; f < n_frames; ++f)
       PCC_REQUIRE(a_is_version(h_blobs[f], h_lens[f], tv), PCC_E_ARG,
                   "%s: frame %d: attribute blobs of version %d and of another version in one call (one version per call)", who, f, tv);
-    PCC_REQUIRE(lod == 0, PCC_E_ARG, "%s: attribute blob version %d at level of detail %d (it decodes at 0 only)", who, tv, lod);
-    return a_t_decode_frames(who, ctx, h_blobs, h_lens, n_frames, d_cells, h_cell_offsets, d_out, h_out, cap_bytes, h_out_offsets, h_format,
-                             tv == kAttrCVersion);
+    PCC_REQUIRE(lod == 0 || attr_s_kind(tv), PCC_E_ARG, "%s: attribute blob version %d at level of detail %d (it decodes at 0 only)", who,
+                tv, lod);
+    return a_t_decode_frames(who, ctx, h_blobs, h_lens, n_frames, d_cells, h_cell_offsets, d_out, h_out, cap_bytes, h_out_offsets, h_format, tv,
+                             lod);
   }
   // the blobs of a call are of one version, the first blob's: 2, or 7 (k_a2_walk<true> scales and clamps), or their
   // cross-channel forms 11 and 14 (k_ax_inv between the decoder and the walk)

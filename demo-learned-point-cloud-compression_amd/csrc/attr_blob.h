@@ -1,6 +1,7 @@
 // attr_blob.h — the header of an attribute blob (attr.hip), parsed and checked on the host before anything is reserved
 // or launched.  Plain C++ (no HIP): tests/fuzz/fuzz_attr_header.cpp, fuzz_attr2_header.cpp, fuzz_attr_nl_header.cpp,
-// fuzz_attr_cross_header.cpp, fuzz_attr_transform_header.cpp and fuzz_attr_colour_header.cpp put it under the sanitizers.
+// fuzz_attr_cross_header.cpp, fuzz_attr_transform_header.cpp, fuzz_attr_colour_header.cpp and
+// fuzz_attr_scalable_header.cpp put it under the sanitizers.
 //
 // Every size the decoder reserves or reads follows from what this parse accepted: the chunk table must add up to the
 // blob's own length, so a header cannot announce more words than the blob holds; n is bounded by the chunks
@@ -265,6 +266,42 @@ struct Attr2Plan {
     }                              \
   } while (0)
 
+// the plan of level of detail `lod` of a blob whose header o holds (S, the chunk table at off_table, off_payload,
+// payload_words): m values, the first m of the coding order (lod 0: all n, the whole blob of `total` bytes).  b[0 .. len)
+// reaches the chunk table; need_all: the plan's bytes must be there, else only the last needed chunk's length table
+static inline int attr_lod_plan(const uint8_t* b, int64_t len, int lod, bool need_all, int tag, const AttrInfo& o, int64_t m, int64_t total,
+                                Attr2Plan* pl) {
+  const uint8_t* q = b + o.off_table;
+  if (lod == 0) {
+    const int64_t last = (int64_t)attr_u32(q + 4 * (o.nc - 1));
+    pl->m = o.n;
+    pl->chunks = o.nc;
+    pl->lanes = kAttrLanes;
+    pl->bytes = total;
+    pl->last_off = o.payload_words - last;
+    pl->last_words = last;
+    return PCC_OK;
+  }
+  pl->m = m;
+  const int64_t lanes = (pl->m + o.S - 1) / o.S, cs = (lanes - 1) / kAttrLanes, ls = (lanes - 1) % kAttrLanes;
+  for (int64_t k = 0; k < cs; ++k) pl->last_off += (int64_t)attr_u32(q + 4 * k);
+  const int64_t cw = (int64_t)attr_u32(q + 4 * cs);
+  const int64_t at = o.off_payload + 2 * pl->last_off;   // the chunk: 128 state words, then its length table
+  ATTR2_REQUIRE(len >= at + 2 * 3 * kAttrLanes, "attribute blob v%d: truncated in front of the length table of chunk %lld", tag,
+                (long long)cs);
+  int64_t run = 3 * kAttrLanes;
+  for (int64_t l = 0; l <= ls; ++l) run += (int64_t)b[at + 4 * kAttrLanes + 2 * l] | ((int64_t)b[at + 4 * kAttrLanes + 2 * l + 1] << 8);
+  ATTR2_REQUIRE(run <= cw, "attribute blob v%d: the runs of chunk %lld take %lld words of its %lld", tag, (long long)cs, (long long)run,
+                (long long)cw);
+  pl->chunks = cs + 1;
+  pl->lanes = ls + 1;
+  pl->last_words = run;
+  pl->bytes = at + 2 * run;
+  ATTR2_REQUIRE(!need_all || pl->bytes <= len, "attribute blob v%d: truncated (level of detail %d needs %lld bytes, %lld are here)", tag, lod,
+                (long long)pl->bytes, (long long)len);
+  return PCC_OK;
+}
+
 // b[0 .. len): the blob, or a prefix of it.  need_all: the decoder's form — the plan's bytes must be present (lod 0: the
 // blob, whole and nothing behind it); otherwise (pcc_attr_lod_info) the bytes must only reach what the plan is computed
 // from, the last needed chunk's length table.  Nothing beyond b[len) is read.
@@ -329,35 +366,7 @@ static inline int attr2_parse_kind(const uint8_t* b, int64_t len, int lod, bool 
   o->payload_words = words;
   ATTR2_REQUIRE(o->off_payload + 2 * words == total, "attribute blob v%d: chunks take %lld bytes, blob has %lld", tag,
                 (long long)(2 * words), (long long)(total - o->off_payload));
-  // the plan
-  if (lod == 0) {
-    const int64_t last = (int64_t)attr_u32(q + 4 * (o->nc - 1));
-    pl->m = o->n;
-    pl->chunks = o->nc;
-    pl->lanes = kAttrLanes;
-    pl->bytes = total;
-    pl->last_off = words - last;
-    pl->last_words = last;
-    return PCC_OK;
-  }
-  pl->m = o->cells[lod];
-  const int64_t lanes = (pl->m + o->S - 1) / o->S, cs = (lanes - 1) / kAttrLanes, ls = (lanes - 1) % kAttrLanes;
-  for (int64_t k = 0; k < cs; ++k) pl->last_off += (int64_t)attr_u32(q + 4 * k);
-  const int64_t cw = (int64_t)attr_u32(q + 4 * cs);
-  const int64_t at = o->off_payload + 2 * pl->last_off;   // the chunk: 128 state words, then its length table
-  ATTR2_REQUIRE(len >= at + 2 * 3 * kAttrLanes, "attribute blob v%d: truncated in front of the length table of chunk %lld", tag,
-                (long long)cs);
-  int64_t run = 3 * kAttrLanes;
-  for (int64_t l = 0; l <= ls; ++l) run += (int64_t)b[at + 4 * kAttrLanes + 2 * l] | ((int64_t)b[at + 4 * kAttrLanes + 2 * l + 1] << 8);
-  ATTR2_REQUIRE(run <= cw, "attribute blob v%d: the runs of chunk %lld take %lld words of its %lld", tag, (long long)cs, (long long)run,
-                (long long)cw);
-  pl->chunks = cs + 1;
-  pl->lanes = ls + 1;
-  pl->last_words = run;
-  pl->bytes = at + 2 * run;
-  ATTR2_REQUIRE(!need_all || pl->bytes <= len, "attribute blob v%d: truncated (level of detail %d needs %lld bytes, %lld are here)", tag, lod,
-                (long long)pl->bytes, (long long)len);
-  return PCC_OK;
+  return attr_lod_plan(b, len, lod, need_all, tag, *o, o->cells[lod], total, pl);
 }
 
 static inline int attr2_parse(const uint8_t* b, int64_t len, int lod, bool need_all, Attr2Info* o, Attr2Plan* pl) {
@@ -528,4 +537,133 @@ static inline int attr_t_parse(const uint8_t* b, int64_t len, AttrTInfo* o, bool
 }
 static inline int attr_c_parse(const uint8_t* b, int64_t len, AttrCInfo* o, bool prefix = false) {
   return attr_tc_parse(b, len, o, o, prefix);
+}
+
+// ---- version 22: transform-coded attributes with level-of-detail prefixes -------------------------------------------
+// An eleventh kind (compress(..., qstep=.., scalable_to=K)): version 21 with weights that a decoder at a cut can form,
+// so that the coefficients of every level of detail 0 .. K are a prefix of the blob as version 2's values are.
+//
+//   'A' 22 (bpv | slod << 4) c | u32 n | u32 payload_len | u32 colour | u32 q[c] | u32 K | u32 count[16] | u32 S |
+//   u32 n_chunks | u16 p0[nctx] | u32 words[n_chunks] | chunk payloads      (n == 0: the 12 bytes up to payload_len = 0)
+//
+// Byte 22 = 10110b has odd parity as the ten bytes above; it has its own predicate (attr_s_kind) and parser
+// (attr_s_parse), and every other parser refuses it.  count[j] = #{i : b(i) >= 3 j}: version 2's cells[j].
+// Everything is version 21's — keys, sublevels b(i), pairs lo / hi, x[0], coding order, entropy stage, the clamp of an
+// index at H - 1, the colour word, one step q[ch] per channel — except the weights and the steps.  K = the sender's
+// deepest cut, 1 <= K, slod + K <= 15:
+//   K-cells    first(i) = 1 if i == 0 or key_i >> 3 K != key_{i-1} >> 3 K (that is b(i) >= 3 K); g(i) = the number of
+//              firsts among points 0 .. i - 1, C = g(n) = count[K].  A node split at bit t >= 3 K begins and ends on
+//              K-cell boundaries: g(b) - g(a) is the number of K-cells in [a, b)
+//   scale      M = max(1, floor((2 n + C) / (2 C))): the rounded mean number of points in a K-cell
+//   t >= 3 K   ca = g(i) - g(lo), cb = g(hi) - g(i), w = ca + cb take the places of version 19's wa, wb, w in both
+//              lifts; s[ch] = max(2, isqrt(floor(q[ch]^2 w / (ca cb M))))      (q^2 w < 2^58, ca cb M < 2^55)
+//   t < 3 K    (inside a K-cell; hi is not needed) forward val[lo] += floor(h / 2), inverse va = val[lo] - floor(h^ / 2);
+//              s[ch] = max(2, isqrt(floor(2 q[ch]^2 / 2^floor(2 t / 3))))
+// A decoder at a cut j, 0 <= j <= K, runs the same procedure on the m_j = count[j] cell keys kappa = key >> 3 j of its
+// geometry at lod j (biased by 32768 >> (slod + j)): b'(r) = hb(kappa_r xor kappa_{r-1}), the absolute sublevel
+// t = b' + 3 j, K-cells kappa >> 3 (K - j), the first m_j coefficients of the coding order, the inverse over sublevels
+// 47 .. 3 j, M from the head's n and count[K].  Row r is the node value of cell r — the cell's mean under the rule's
+// weights — clamped and colour-inverted as version 21's values are.  Cells that give another number of K-cells than
+// count[K] are PCC_E_STREAM.  The prefix of lod j is version 2's (attr_lod_plan).  tests/attr_scalable_ref.py restates
+// the kind in numpy.
+constexpr int kAttrSVersion = 22;
+
+struct AttrSInfo : AttrCInfo {
+  int K;               // the deepest cut (0: a blob without points)
+  int64_t cells[16];   // count[j]
+};
+
+static inline bool attr_s_kind(int version) { return version == kAttrSVersion; }
+// .. | u32 colour | u32 q[c] | u32 K | u32 count[16] | u32 S | u32 n_chunks
+static inline int attr_s_head(int c) { return kAttrHead + 4 + 4 * c + 4 + 64 + 8; }
+
+enum AttrSMode {
+  kAttrSDecode,   // the decoder's form: the plan's bytes must be there (lod 0: the blob, whole and nothing behind it)
+  kAttrSPlan,     // pcc_attr_lod_info: the blob or a prefix that reaches the last needed chunk's length table
+  kAttrSHead      // pcc_attr_info and its kin: the blob or a prefix that reaches K (20 + 4 c bytes); no plan, lod unread
+};
+
+// Nothing beyond b[len) is read.  lod above K: PCC_E_ARG (modes kAttrSDecode and kAttrSPlan)
+static inline int attr_s_parse(const uint8_t* b, int64_t len, int lod, AttrSMode mode, AttrSInfo* o, Attr2Plan* pl) {
+  const int v = kAttrSVersion;
+  ATTR2_REQUIRE(b && len >= kAttrHead && b[0] == 'A' && b[1] == v, "attribute blob v%d: bad header (len=%lld)", v, (long long)len);
+  o->version = v;
+  o->max_error = 0;
+  o->cross = 0;
+  o->qstep = 0;
+  o->colour = 0;
+  o->K = 0;
+  for (int ch = 0; ch < 4; ++ch) o->q[ch] = 0;
+  for (int k = 0; k < 16; ++k) o->cells[k] = 0;
+  o->bpv = b[2] & 15;
+  o->slod = b[2] >> 4;
+  o->c = b[3];
+  ATTR2_REQUIRE((o->bpv == 1 || o->bpv == 2) && o->c >= 1 && o->c <= 4, "attribute blob v%d: %d bytes per value, %d channels", v, o->bpv,
+                o->c);
+  o->nctx = attr_contexts(o->bpv, o->c);
+  o->n = (int64_t)attr_u32(b + 4);
+  const int64_t payload = (int64_t)attr_u32(b + 8), total = kAttrHead + payload;
+  ATTR2_REQUIRE(len <= total, "attribute blob v%d: payload of %lld bytes in a blob of %lld", v, (long long)payload, (long long)len);
+  ATTR2_REQUIRE(!(mode == kAttrSDecode && lod == 0) || len == total, "attribute blob v%d: truncated (%lld bytes of %lld)", v, (long long)len,
+                (long long)total);
+  o->S = o->nc = 0;
+  o->off_p0 = o->off_table = o->off_payload = kAttrHead;
+  o->payload_words = 0;
+  if (pl) {
+    pl->lod = lod;
+    pl->m = pl->chunks = pl->lanes = pl->last_off = pl->last_words = 0;
+    pl->bytes = kAttrHead;
+  }
+  if (o->n == 0) {
+    ATTR2_REQUIRE(payload == 0, "attribute blob v%d: no points, %lld bytes of payload", v, (long long)payload);
+    return PCC_OK;
+  }
+  const int head = attr_s_head(o->c), at_k = kAttrHead + 4 + 4 * o->c;
+  o->off_p0 = head;
+  o->off_table = o->off_p0 + 2 * (int64_t)o->nctx;
+  ATTR2_REQUIRE(o->n < ((int64_t)1 << 27) && payload >= o->off_table - kAttrHead + 4 + 2 * 3 * kAttrLanes,
+                "attribute blob v%d: %lld points, payload %lld", v, (long long)o->n, (long long)payload);
+  ATTR2_REQUIRE(len >= at_k + 4, "attribute blob v%d: truncated in front of scalable_to (len=%lld)", v, (long long)len);
+  o->colour = attr_u32(b + kAttrHead);
+  ATTR2_REQUIRE(o->colour <= 1 && (o->colour == 0 || o->c >= 3), "attribute blob v%d: colour transform %u with %d channels", v, o->colour,
+                o->c);
+  for (int ch = 0; ch < o->c; ++ch) {
+    o->q[ch] = attr_u32(b + kAttrHead + 4 + 4 * ch);
+    ATTR2_REQUIRE(o->q[ch] >= 1 && o->q[ch] <= attr_max_error(o->bpv), "attribute blob v%d: qstep %u of channel %d with %d bytes per value", v,
+                  o->q[ch], ch, o->bpv);
+  }
+  const uint32_t K = attr_u32(b + at_k);
+  ATTR2_REQUIRE(K >= 1 && (int64_t)K + o->slod <= kAttrMaxLod, "attribute blob v%d: scalable_to %u with the sender's level of detail %d", v, K,
+                o->slod);
+  o->K = (int)K;
+  if (mode == kAttrSHead && len < o->off_table) return PCC_OK;
+  ATTR2_REQUIRE(len >= o->off_table, "attribute blob v%d: truncated header", v);
+  for (int k = 0; k < 16; ++k) {
+    o->cells[k] = (int64_t)attr_u32(b + at_k + 4 + 4 * k);
+    ATTR2_REQUIRE(k == 0 ? o->cells[0] == o->n : (o->cells[k] >= 1 && o->cells[k] <= o->cells[k - 1] && 8 * o->cells[k] >= o->cells[k - 1]),
+                  "attribute blob v%d: level of detail %d has %lld values", v, k, (long long)o->cells[k]);
+  }
+  o->S = (int64_t)attr_u32(b + head - 8);
+  o->nc = (int64_t)attr_u32(b + head - 4);
+  ATTR2_REQUIRE(o->S >= 1 && o->S * o->c <= kAttrMaxValues && o->nc >= 1 && o->nc <= o->n && kAttrLanes * o->S * o->nc >= o->n &&
+                    kAttrLanes * o->S * (o->nc - 1) < o->n,
+                "attribute blob v%d: %lld points in %lld chunks of 64 x %lld", v, (long long)o->n, (long long)o->nc, (long long)o->S);
+  uint32_t bad_p = 0;
+  ATTR2_REQUIRE(attr_check_p0(b, o->off_p0, o->nctx, &bad_p), "attribute blob v%d: initial probability %u", v, bad_p);
+  ATTR2_REQUIRE(total - o->off_table >= 4 * o->nc, "attribute blob v%d: truncated chunk table", v);
+  if (mode == kAttrSHead && len - o->off_table < 4 * o->nc) return PCC_OK;
+  ATTR2_REQUIRE(len - o->off_table >= 4 * o->nc, "attribute blob v%d: truncated inside the chunk table", v);
+  int64_t words = 0, bad_k = 0, bad_cw = 0;
+  ATTR2_REQUIRE(attr_sum_chunks(b + o->off_table, o->nc, o->bpv, &words, &bad_k, &bad_cw), "attribute blob v%d: chunk %lld has %lld words", v,
+                (long long)bad_k, (long long)bad_cw);
+  o->off_payload = o->off_table + 4 * o->nc;
+  o->payload_words = words;
+  ATTR2_REQUIRE(o->off_payload + 2 * words == total, "attribute blob v%d: chunks take %lld bytes, blob has %lld", v, (long long)(2 * words),
+                (long long)(total - o->off_payload));
+  if (mode == kAttrSHead) return PCC_OK;
+  if (lod < 0 || lod > o->K) {
+    pcc_set_error("attribute blob v%d: level of detail %d beyond its scalable_to %d", v, lod, o->K);
+    return PCC_E_ARG;
+  }
+  return attr_lod_plan(b, len, lod, mode == kAttrSDecode, v, *o, o->cells[lod], total, pl);
 }

@@ -59,6 +59,15 @@ step: on recorded camera colour it is shorter AND closer at q = 16 than plain RG
     blobs, attr_blobs = codec.compress(frames, attributes=rgbi, qstep=(8, 8, 8, 40))         # a step per channel, no transform
     GeometryCodec.attr_info(attr_blobs[0])       # version 21: "qstep" a tuple of c steps, "colour" "ycocg" or None
 
+Version 22 is version 21 under weights that a decoder holding only a geometry prefix can form: the sender names its
+deepest cut K, and levels of detail 0 .. K are prefixes of the blob, as version 2's are, at a few per cent more bytes
+than version 19 at equal error.  Row j at a level is the mean of cell j under the kind's weights.
+
+    blobs, attr_blobs = codec.compress(frames, attributes=rgb, qstep=16, colour="ycocg", scalable_to=3)   # version 22
+    abytes, values = GeometryCodec.attr_lod_info(attr_blobs[0], 2)             # host only; lod <= K
+    cells, coarse = codec.decompress([b[:GeometryCodec.lod_info(b, 2)[0]] for b in blobs],
+                                     [a[:GeometryCodec.attr_lod_info(a, 2)[0]] for a in attr_blobs], lod=2)
+
 Metric frames (include/pcc.h has the rule): float32 points in the caller's unit, from the host or from this codec's
 device, are put on the lattice by the codec, q = rint((x - origin) / voxel) per coordinate in float32; rows without a
 return (NaN / Inf) can be dropped, and the row index says which decoded row every input row became.
@@ -95,7 +104,7 @@ import numpy as np
 import torch
 
 from ._abi import check, PccError, PCC_E_RANGE
-from .runtime import Runtime, _ptr, ATTR_RUN_KINDS, ATTR_TRANSFORM_KINDS
+from .runtime import Runtime, _ptr, ATTR_RUN_KINDS, ATTR_TRANSFORM_KINDS, ATTR_SCALABLE_TRANSFORM_KIND
 
 MAX_FRAMES = 65535      # the batch-index range of pcc_morton_keys
 MAX_LOD = 15            # levels of detail 0 .. 15 (csrc/octree2_blob.h)
@@ -227,7 +236,8 @@ class GeometryCodec:
 
     @staticmethod
     def attr_lod_info(attr_blob, lod):
-        """(bytes, values) of level of detail `lod` of a version-2 attribute blob (compress(..., scalable=True)):
+        """(bytes, values) of level of detail `lod` of a version-2 attribute blob (compress(..., scalable=True)), or of a
+        version-22 blob (compress(..., qstep=q, scalable_to=K); lod <= K, PccError above):
         attr_blob[:bytes] is the shortest prefix that decompress(..., lod=lod) reads, `values` the rows it gives (the
         cells of the frame's geometry at that lod).  Host only; `attr_blob` may be a prefix that reaches the last needed
         chunk's length table."""
@@ -240,7 +250,8 @@ class GeometryCodec:
         and version 19; a blob without points records none), scalable, lod (the sender's); a cross-channel kind adds
         cross_channel, the tuple of channel indices coded against the channel before them (a plain kind's dict has no
         such key), version 19 adds qstep (0 in a blob without points), version 21 qstep as a tuple of one step per
-        channel and colour, "ycocg" or None (zeros and None in a blob without points).
+        channel and colour, "ycocg" or None (zeros and None in a blob without points), version 22 those two, scalable
+        True and scalable_to, its K (0 in a blob without points).
         Host only; `attr_blob` may be a prefix of 16 bytes or more (version 21: 16 + 4 channels)."""
         return Runtime.attr_info(bytes(attr_blob))
 
@@ -320,6 +331,26 @@ class GeometryCodec:
         return 1, steps, int(colour is not None)
 
     @staticmethod
+    def _check_scalable_to(scalable_to, lod, qstep, steps, attrs, max_error, scalable, cross):
+        """scalable_to of compress -> (steps, K): None and the steps as they were for the calls of before; else version
+        22, K an integer in 1 .. 15 - lod and one step per channel of the widest frame"""
+        if scalable_to is None:
+            return steps, None
+        if isinstance(scalable_to, bool) or not isinstance(scalable_to, (int, np.integer)):
+            raise TypeError(f"scalable_to must be an integer in 1 .. {15 - lod}, got {scalable_to!r}")
+        K = int(scalable_to)
+        if not 1 <= K <= 15 - lod:
+            raise ValueError(f"scalable_to must be an integer in 1 .. {15 - lod} (15 - lod), got {K}")
+        if max_error or cross is not None or scalable:
+            raise ValueError("scalable_to with max_error, cross_channel or scalable=True: it is the deepest level-of-detail prefix "
+                             "of transform-coded attributes (qstep=), which have none of the three")
+        if not qstep:
+            raise ValueError("scalable_to is the deepest level-of-detail prefix of transform-coded attributes: it needs qstep=")
+        if steps is None:      # an integer qstep serves every channel, as it does with colour=
+            steps = [qstep] * max(a.shape[1] for a in attrs)
+        return steps, K
+
+    @staticmethod
     def _check_cross(cross_channel, attrs):
         """cross_channel of compress -> one mask per frame (bit ch - 1: channel ch against ch - 1), or None for False"""
         if cross_channel is False:
@@ -347,7 +378,8 @@ class GeometryCodec:
         return masks
 
     def compress(self, frames, attributes=None, lod=0, scalable=False, *, voxel=None, origin=(0.0, 0.0, 0.0),
-                 invalid="raise", return_index=False, max_error=0, cross_channel=False, qstep=0, colour=None):
+                 invalid="raise", return_index=False, max_error=0, cross_channel=False, qstep=0, colour=None,
+                 scalable_to=None):
         """frames: a sequence of int16 / int32 [n_f, 3] arrays -> a list of bytes, one version-2 blob per frame.
         Duplicate points are removed (as np.unique), out-of-range coordinates raise PccError (PCC_E_RANGE).
         lod = k > 0: the sender's side of a level of detail — blob f is the version-2 blob of the distinct cells
@@ -391,6 +423,13 @@ class GeometryCodec:
         ValueError.  Both refuse max_error, scalable=True and cross_channel as qstep does, and combine with lod=k,
         float32 / device frames, invalid="drop" and return_index as it does.  An integer qstep without colour stays
         version 19, the bytes of before.
+        scalable_to = K (with qstep; an integer in 1 .. 15 - lod; bool or non-integer: TypeError; out of range, without
+        qstep, or with max_error, cross_channel or scalable=True: ValueError): attribute blob version 22 (include/pcc.h
+        has the rule) — version 21 under weights that a decoder at a cut can form (K-cell counts above K, the level
+        alone inside a K-cell), so that levels of detail 0 .. K are prefixes of the blob (attr_lod_info,
+        decompress(..., lod=j)) at a few per cent more bytes than version 19 at equal error.  An integer qstep serves
+        every channel; colour=, lod=k, float32 / device frames, invalid="drop" and return_index combine with it as with
+        version 21.  None, the default, writes the bytes of before.
 
         Frame types: numpy int16 / int32 as above, numpy float32, or torch tensors of those three dtypes on the host or
         on this codec's device; all frames of a call integer or all float32, all on the host or all on the device
@@ -423,8 +462,9 @@ class GeometryCodec:
         max_error = self._check_max_error(max_error, attrs)
         cross = self._check_cross(cross_channel, attrs)
         qstep, steps, colour = self._check_colour(qstep, colour, attrs, max_error, scalable, cross)
-        if steps is not None:      # version 21: the steps travel where the one step did
-            qstep = (steps, colour)
+        steps, scalable_to = self._check_scalable_to(scalable_to, lod, qstep, steps, attrs, max_error, scalable, cross)
+        if steps is not None:      # versions 21 and 22: the steps travel where the one step did
+            qstep = (steps, colour, scalable_to)
         nb = len(frames)
 
         def result(blobs, attr_blobs=None, index=None):
@@ -563,9 +603,10 @@ class GeometryCodec:
         formats = [a.dtype.itemsize | (a.shape[1] << 8) for a in attrs]
         points = [struct.unpack_from("<I", b, 4)[0] for b in blobs]
         n_kept = front.n_keep if front.n_keep < front.n else None      # None: no row was dropped
-        steps, colour = qstep if isinstance(qstep, tuple) else (qstep, None)      # version 21: (steps, colour)
+        # versions 21 and 22: (steps, colour[, K])
+        steps, colour, to = (tuple(qstep) + (None,))[:3] if isinstance(qstep, tuple) else (qstep, None, None)
         return rt.attr_encode_frames(values, offs, formats, _ends(front.sizes), points, front.perm, front.rows, front.n_unique,
-                                     version, front.keys, key_shift, n_kept, max_error, cross, steps, colour)
+                                     version, front.keys, key_shift, n_kept, max_error, cross, steps, colour, to)
 
     def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0, *, voxel=None, origin=(0.0, 0.0, 0.0)):
         """version-2 blobs -> a list of int32 [n_f, 3] point sets in Morton order: numpy arrays (output="numpy") or
@@ -579,8 +620,10 @@ class GeometryCodec:
         4 / 7 of compress(..., max_error=e), their cross-channel forms 8 / 11 / 13 / 14 of compress(...,
         cross_channel=...), transform-coded 19 of compress(..., qstep=q) and 21 of compress(..., qstep=(..)) or
         colour="ycocg") is read from the blob; version 7 behaves as version 2 and its prefixes do, every value within e,
-        and a cross-channel kind returns what its plain kind returns.  The ten kinds may be mixed at lod 0; an attribute
-        blob of version 1, 4, 8, 13, 19 or 21 at lod > 0 raises ValueError naming the frame.
+        and a cross-channel kind returns what its plain kind returns.  Version 22 (compress(..., qstep=q,
+        scalable_to=K)) decodes at lod 0 .. K, from whole blobs or attr_lod_info's prefixes: row j is the mean of cell j
+        under the kind's weights; lod > K raises ValueError naming the frame and K.  The eleven kinds may be mixed at
+        lod 0; an attribute blob of version 1, 4, 8, 13, 19 or 21 at lod > 0 raises ValueError naming the frame.
         voxel (with origin): the point sets come back as float32 [n_f, 3] in the caller's unit instead of int32,
         x = origin + t * voxel, one float32 multiplication and then one addition on the device (include/pcc.h has the
         rule): t the lattice index at lod 0 and, at lod k, the centre of the cell's lattice points
@@ -608,6 +651,12 @@ class GeometryCodec:
                                  "its transform are the point counts under every node, which a decoder at a cut does not "
                                  "have; store version 2, 7, 11 or 14 (compress(..., scalable=True)) or ship coarse "
                                  "attributes with compress(frames, attributes=..., lod=k, qstep=q)")
+            for f, b in enumerate(attr_blobs):      # version 22: up to the K its sender chose
+                if lod and kind[f] == ATTR_SCALABLE_TRANSFORM_KIND and len(b) >= 8 and struct.unpack_from("<I", b, 4)[0]:
+                    to = Runtime.attr_info(b)["scalable_to"]
+                    if lod > to:
+                        raise ValueError(f"frame {f}: attributes of blob version 22 with scalable_to = {to} cannot be decoded at "
+                                         f"lod {lod}: its sender chose {to} as the deepest cut")
             if lod and any(v1):
                 raise ValueError(f"frame {v1.index(True)}: attributes of blob version {kind[v1.index(True)]} cannot be decoded at lod > 0: it "
                                  "is one predictive stream in full-resolution Morton order, so neither its bytes nor "

@@ -708,7 +708,8 @@ class Runtime:
         return (views, pts) if whole else views
 
     def attr_encode_frames(self, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique,
-                           version=1, keys=None, key_shift=0, n_kept=None, max_error=0, cross=None, qstep=0, colour=None):
+                           version=1, keys=None, key_shift=0, n_kept=None, max_error=0, cross=None, qstep=0, colour=None,
+                           scalable_to=None):
         """attribute blobs (csrc/attr.hip) of len(formats) frames at once (pcc_attr_encode_frames): `values` a
         device uint8 tensor with frame f's [rows_f, c_f] values at byte value_offsets[f], formats[f] = bytes per value |
         c_f << 8, row_offsets (n_frames + 1) the frames' rows among the call's keys, perm / run_starts what
@@ -725,11 +726,15 @@ class Runtime:
         version 2 takes them; `version` is not read, and max_error or a cross-channel mask beside it raise ValueError.
         qstep a sequence of up to 4 integers, or colour=1 beside any qstep (pcc_attr_encode_frames_transform2): blob
         version 21, one step per channel (a frame reads its first c_f; an integer serves every channel) and, with
-        colour=1, the luma / chroma transform in front of the lift (include/pcc.h has the rule); the library checks both."""
+        colour=1, the luma / chroma transform in front of the lift (include/pcc.h has the rule); the library checks both.
+        scalable_to = K beside a qstep (pcc_attr_encode_frames_transform3): blob version 22, version 21 under weights a
+        decoder at a cut can form, its levels of detail 0 .. K prefixes of the blob; the library checks K."""
         if version not in (1, 2):
             raise ValueError(f"attribute blob version {version!r}: 1 or 2")
         steps = None
-        if colour or not isinstance(qstep, (int, np.integer)):
+        if scalable_to is not None and isinstance(qstep, (int, np.integer)) and int(qstep) == 0:
+            raise ValueError("scalable_to (attribute blob version 22) needs qstep")
+        if colour or scalable_to is not None or not isinstance(qstep, (int, np.integer)):
             steps = [int(qstep)] * 4 if isinstance(qstep, (int, np.integer)) else [int(q) for q in qstep]
             if not 1 <= len(steps) <= 4:
                 raise ValueError(f"attribute blob version 21: {len(steps)} steps, at most 4")
@@ -749,7 +754,11 @@ class Runtime:
                 (C.c_int64 * (nf + 1))(*row_offsets), (C.c_int64 * nf)(*points), nf, _ptr(perm), _ptr(run_starts), n_unique)
         if cross is not None and len(cross) != nf:
             raise ValueError(f"{len(cross)} cross-channel masks for {nf} frames")
-        if steps is not None:
+        if scalable_to is not None:
+            check(self.lib.pcc_attr_encode_frames_transform3(*head, -1 if n_kept is None else int(n_kept), _ptr(keys), int(key_shift),
+                                                             (C.c_int32 * 4)(*steps), int(colour or 0), int(scalable_to), _np_ptr(out),
+                                                             cap, offs), "pcc_attr_encode_frames_transform3")
+        elif steps is not None:
             check(self.lib.pcc_attr_encode_frames_transform2(*head, -1 if n_kept is None else int(n_kept), _ptr(keys), int(key_shift),
                                                              (C.c_int32 * 4)(*steps), int(colour or 0), _np_ptr(out), cap, offs),
                   "pcc_attr_encode_frames_transform2")
@@ -778,8 +787,9 @@ class Runtime:
 
     @staticmethod
     def attr_lod_info(blob, lod):
-        """(bytes, values) of level of detail `lod` (0 .. 15) of a version-2 attribute blob (pcc_attr_lod_info, host
-        only): the shortest prefix that decodes at that level, and the rows it gives.  `blob` may itself be a prefix
+        """(bytes, values) of level of detail `lod` (0 .. 15) of a version-2 attribute blob, or of one of version 7, 11, 14
+        or 22 (22: up to its scalable_to) (pcc_attr_lod_info, host only): the shortest prefix that decodes at that level,
+        and the rows it gives.  `blob` may itself be a prefix
         that reaches the last needed chunk's length table."""
         buf = np.frombuffer(blob, dtype=np.uint8)
         nbytes, values = C.c_int64(0), C.c_int64(0)
@@ -794,7 +804,8 @@ class Runtime:
         lossless, and version 19), scalable, lod (the sender's); for the cross-channel kinds also cross_channel, the tuple
         of channels coded against the channel before them (pcc_attr_cross_mask); for version 19 also qstep
         (pcc_attr_qstep; 0 in a blob without points); for version 21 qstep, a tuple of one step per channel, and colour,
-        "ycocg" or None (pcc_attr_transform_info; zeros and None in a blob without points)"""
+        "ycocg" or None (pcc_attr_transform_info; zeros and None in a blob without points); for version 22 those two and
+        scalable_to, its deepest level-of-detail prefix (pcc_attr_scalable_to; 0 in a blob without points)"""
         buf = np.frombuffer(blob, dtype=np.uint8)
         v = [C.c_int32(0) for _ in range(6)]
         n = C.c_int64(0)
@@ -810,11 +821,15 @@ class Runtime:
             q = C.c_int32(0)
             check(_abi.lib().pcc_attr_qstep(_np_ptr(buf), buf.shape[0], C.byref(q)), "pcc_attr_qstep")
             info["qstep"] = q.value
-        if info["version"] == ATTR_COLOUR_KIND:
+        if info["version"] in (ATTR_COLOUR_KIND, ATTR_SCALABLE_TRANSFORM_KIND):
             col, steps = C.c_int32(0), (C.c_int32 * 4)()
             check(_abi.lib().pcc_attr_transform_info(_np_ptr(buf), buf.shape[0], C.byref(col), steps), "pcc_attr_transform_info")
             info["qstep"] = tuple(int(q) for q in steps[:info["channels"]])
             info["colour"] = "ycocg" if col.value else None
+        if info["version"] == ATTR_SCALABLE_TRANSFORM_KIND:
+            k = C.c_int32(0)
+            check(_abi.lib().pcc_attr_scalable_to(_np_ptr(buf), buf.shape[0], C.byref(k)), "pcc_attr_scalable_to")
+            info["scalable_to"] = k.value
         return info
 
     def attr_decode_frames(self, blobs, points=None, device=False, lod=None, cells=None):
@@ -824,7 +839,7 @@ class Runtime:
         (optional): frame f's geometry point count, checked against the blob before anything is launched.
         lod = k (0 .. 15) with cells (pcc_attr_decode_frames_lod): blobs of version 2, or of 7, 11 or 14, or prefixes of them (attr_lod_info)
         -> row j the value of the j-th cell of the frame's geometry at that lod; lod = 0 with cells also reads whole
-        blobs of version 19 or of version 21, whose transform needs the frame's keys (a call of them at lod > 0: PccError); `cells` the device tensors
+        blobs of version 19 or of version 21, whose transform needs the frame's keys (a call of them at lod > 0: PccError), and lod = 0 .. K reads blobs of version 22 or their prefixes (K: every blob's scalable_to); `cells` the device tensors
         octree_decode_frames(..., device=True, lod=k) returned for the same frames (views of one tensor)."""
         nb = len(blobs)
         if nb == 0:
@@ -889,6 +904,8 @@ ATTR_TRANSFORM_KIND = 19
 # version 19 with a colour transform and one step per channel: decoded as version 19 is
 ATTR_COLOUR_KIND = 21
 ATTR_TRANSFORM_KINDS = (ATTR_TRANSFORM_KIND, ATTR_COLOUR_KIND)
+# version 21 under weights a decoder at a cut can form: decodes at lod 0 .. its scalable_to, from prefixes
+ATTR_SCALABLE_TRANSFORM_KIND = 22
 
 OCTREE_V2_MIN_LEAVES = 65536     # include/pcc.h PCC_OCTREE_V2_MIN_LEAVES
 OCTREE_V3_MIN_LEAVES = 8192      # include/pcc.h PCC_OCTREE_V3_MIN_LEAVES

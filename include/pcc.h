@@ -1137,6 +1137,74 @@ int pcc_attr_encode_frames_transform2(pcc_ctx* ctx, const void* d_values,
 int pcc_attr_transform_info(const uint8_t* h_in, int64_t len, int32_t* h_colour,
                             int32_t h_qstep[4]);
 
+/* Transform-coded attributes with level-of-detail prefixes: attribute blob
+ * version 22, an eleventh kind.  Versions 19 and 21 weigh a split by the
+ * leaves under its two children, which a decoder that holds a geometry prefix
+ * cannot count.  Version 22 is version 21 under weights such a decoder can
+ * form: the sender names its deepest cut K; above K a split is weighed by the
+ * K-cells under its children, inside a K-cell by its level alone.
+ *
+ * The rule (tests/attr_scalable_ref.py restates it in numpy).  Everything is
+ * version 21's -- keys, sublevels b(i), the pairs lo / hi, x[0], the coding
+ * order, the entropy stage, the clamp of an index at H - 1, the colour word,
+ * one step q[ch] per channel -- except the weights, the steps and the head.
+ * Per frame: n distinct points in Morton order, keys key_i biased by
+ * 32768 >> slod; K = scalable_to, 1 <= K, slod + K <= 15.
+ *   K-cells: first(i) = 1 if i == 0 or key_i >> 3 K != key_{i-1} >> 3 K.
+ *     g(i) = the number of firsts among points 0 .. i - 1; C = g(n).  A node
+ *     split at bit t >= 3 K begins and ends on K-cell boundaries, so
+ *     g(b) - g(a) is the exact number of K-cells in [a, b).
+ *   Scale: M = max(1, floor((2 n + C) / (2 C))), the rounded mean number of
+ *     points in a K-cell.
+ *   The pair of point i at t = b(i) >= 3 K: ca = g(i) - g(lo),
+ *     cb = g(hi) - g(i), w = ca + cb stand where version 19 has wa, wb, w in
+ *     both lifts.  s[ch] = max(2, isqrt(floor(q[ch]^2 w / (ca cb M)))).
+ *     q^2 w < 2^58; ca cb M < 2^55 because M (ca + cb) <= n + C / 2.
+ *   A pair at t < 3 K (inside a K-cell; hi is not needed):
+ *     forward val[lo] += floor(h / 2); inverse va = val[lo] - floor(h^ / 2);
+ *     s[ch] = max(2, isqrt(floor(2 q[ch]^2 / 2^floor(2 t / 3)))).
+ *   Decoding at a cut j, 0 <= j <= K: the same procedure on the m_j = count[j]
+ *     cell keys kappa = key >> 3 j that the geometry decode at lod j leaves,
+ *     biased by 32768 >> (slod + j).  b'(r) = hb(kappa_r xor kappa_{r-1}), the
+ *     absolute sublevel t = b' + 3 j; K-cells are kappa >> 3 (K - j); the
+ *     coefficients are the first m_j of the coding order; the inverse runs
+ *     over sublevels 47 .. 3 j; M from the head's n and count[K].  Row r is
+ *     the node value of cell r -- the cell's mean under the rule's weights,
+ *     not version 2's sample of the Morton-first point -- clamped, then
+ *     colour-inverted as version 21's values are.  Cells that give another
+ *     count at a level from j up than the head (count[K] among them):
+ *     PCC_E_STREAM.
+ *   Layout: 'A' 22 (bpv | slod << 4) c | u32 n | u32 payload_len | u32 colour |
+ *     u32 q[c] | u32 K | u32 count[16] | u32 S | u32 n_chunks | u16 p0[nctx] |
+ *     u32 words[n_chunks] | chunk payloads.  count[j] = #{i : b(i) >= 3 j},
+ *     version 2's.  n = 0: the 12-byte head alone.  Byte 22 = 10110b keeps the
+ *     odd parity of the ten other version bytes.  The prefix of lod j is
+ *     version 2's, from count[j], S and the last needed chunk's length table.
+ *   _encode_frames_transform3 : the arguments of _transform2 and scalable_to
+ *     = K in 1 .. 15 - key_shift / 3 (else PCC_E_ARG).  Launches: version
+ *     21's, one pass that flags the K-cell firsts and the device-wide scan
+ *     behind the coding order, the 16 counts for the head, and the lift under
+ *     the new weights in place of version 21's.  No further synchronisation.
+ *   pcc_attr_decode_frames_lod reads version 22 at lod 0 .. K of every blob of
+ *     the call (one version per call; blobs or the prefixes pcc_attr_lod_info
+ *     names; lod > K: PCC_E_ARG), against the cells of the geometry at lod.
+ *   pcc_attr_lod_info accepts version 22 for lod <= K, PCC_E_ARG above.
+ *   pcc_attr_info reports version 22 with scalable = 1, from the blob or a
+ *     prefix that reaches K (20 + 4 c bytes); pcc_attr_transform_info its
+ *     colour word and steps; pcc_attr_scalable_to: host only, K of such a
+ *     head, 0 for every other kind and for a blob without points. */
+int pcc_attr_encode_frames_transform3(pcc_ctx* ctx, const void* d_values,
+                                      const int64_t* h_value_offsets,
+                                      const int32_t* h_format, const int64_t* h_rows,
+                                      const int64_t* h_points, int n_frames,
+                                      const uint32_t* d_perm,
+                                      const uint32_t* d_run_starts, int64_t n_unique,
+                                      int64_t n_kept, const uint64_t* d_keys,
+                                      int key_shift, const int32_t h_qstep[4],
+                                      int colour, int scalable_to, uint8_t* h_out,
+                                      int64_t cap, int64_t* h_offsets);
+int pcc_attr_scalable_to(const uint8_t* h_in, int64_t len, int32_t* h_scalable_to);
+
 /* ---- exact nearest neighbours on the lattice: the D1 metric (csrc/nn.hip, the walk in csrc/nn_cells.h) -- */
 
 /* The rule (tests/nn_ref.py restates it in numpy).  For a frame f there are
