@@ -103,6 +103,9 @@ PROTOTYPES = {
     "pcc_attr_encode_frames_transform3": (i32, [vp, vp, pi64, pi32, pi64, pi64, i32, vp, vp, i64, i64, vp, i32, pi32, i32, i32, vp,
                                                 i64, pi64]),
     "pcc_attr_scalable_to": (i32, [vp, i64, pi32]),
+    "pcc_attr_rate_ladder": (i32, [pi32, i32, i32, pi32, pi32]),
+    "pcc_attr_encode_frames_rate": (i32, [vp, vp, pi64, pi32, pi64, pi64, i32, vp, vp, i64, i64, vp, i32, pi32, i32, i32, pi64, i64,
+                                          vp, i64, pi64, pi32]),
     "pcc_nn_frames": (i32, [vp, vp, i64, vp, i64, i32, vp, vp, vp]),
     "pcc_nn_attr_sse_frames": (i32, [vp, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp]),
     "pcc_nn_replay_host": (i32, [vp, i64, vp, i64, vp, vp, vp]),

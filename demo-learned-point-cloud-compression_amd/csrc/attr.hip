@@ -66,6 +66,13 @@
 // decoder on the level's prefix as version 2's, the cells' counts against the head's, k_as_flag and the scan, k_at_root,
 // k_as_lift<false> per occupied sublevel, k_as_store.  tests/attr_scalable_ref.py restates the kind in numpy.
 //
+// Versions 19 and 21 under a byte target per frame (pcc_attr_encode_frames_rate; include/pcc.h has the ladder and the
+// search): no format of its own.  Merge, colour transform and order stage as above, k_ar_lift (k_at_lift<true> without
+// its quantiser: the raw differences and the pairs' weights stay) and k_ar_mean once; then per stage of the search
+// k_ar_quant over a table of candidate rows (a frame at a rung) and k_a_stats / k_a_enc<false> over the rows as frames
+// of their own; the rows' lengths from their chunks' words; k_ar_gather and k_a_pack<.., TR[, const int32_t*]> over the
+// winners alone.  tests/attr_rate_ref.py restates ladder and search in numpy.
+//
 // Host side: the kinds share one encode sequence (a_encode_frames over an AEncKind, the entry point's kind resolved
 // once) and one decode-call skeleton (ADecCall: accounting, rows, layout, upload, status) under the three decoders, each
 // of which keeps its parser, its side tables, its arena arrays and its kernels; DESIGN.md, "attr.hip: one encode path,
@@ -1400,6 +1407,112 @@ __global__ __launch_bounds__(256) void k_as_store(const ADFrame* __restrict__ ta
   for (int ch = 0; ch < c; ++ch) a_store(o, bpv, (uint32_t)x[ch], ch);
 }
 
+// ---- versions 19 and 21 under a byte target (include/pcc.h states the ladder and the search) ------------------------
+// The forward lift does not depend on the step: k_ar_lift is the encoder branch of k_at_lift without its quantiser and
+// runs once per call; k_ar_quant then forms the indices of any number of candidate rows (a frame at a rung of its
+// ladder) from what it left, and the rows go through k_a_stats / k_a_enc<false> as frames of their own.
+//
+// k_ar_lift: launched as k_at_lift<true> is.  val = the merged values, lifted in place; the raw difference hh of the
+// point at place r to hh_all[val_off + r c + ch] (|hh| < 2^16), the pair's weights to wts[pt0 + r] (wa, wb < 2^27)
+__global__ __launch_bounds__(256) void k_ar_lift(const uint64_t* __restrict__ keys_all, const A2Order* __restrict__ tab,
+                                                 const uint32_t* __restrict__ bins, const uint32_t* __restrict__ inv, int t,
+                                                 const AFrame* __restrict__ etab, uint16_t* __restrict__ val,
+                                                 int32_t* __restrict__ hh_all, uint2* __restrict__ wts) {
+  const int f = blockIdx.y;
+  const A2Order& h = tab[f];
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= (int64_t)bins[f * 2 * kATBins + kATBins + t]) return;
+  const int64_t r = (int64_t)bins[f * 2 * kATBins + t] + j;
+  if (r >= h.n) return;
+  const int64_t i = inv[h.pt0 + r];
+  if (i <= 0 || i >= h.n) return;
+  const uint64_t* keys = keys_all + h.pt0;
+  const int bit = t + h.shift;   // <= 47
+  const uint64_t key = keys[i], low = (1ull << bit) - 1ull;
+  const uint64_t t_lo = key & ~((low << 1) | 1ull), t_hi = (key | low) + 1ull;
+  int64_t lo = 0, hi = i;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < t_lo) lo = mid + 1; else hi = mid;
+  }
+  int64_t a = i + 1, b = h.n;
+  while (a < b) {
+    const int64_t mid = (a + b) >> 1;
+    if (keys[mid] < t_hi) a = mid + 1; else b = mid;
+  }
+  const int64_t wa = i - lo, wb = a - i, w = wa + wb;
+  if (wa < 1) return;   // cannot happen: the keys are sorted and distinct
+  const AFrame& fr = etab[f];
+  const int c = fr.c;
+  wts[h.pt0 + r] = make_uint2((uint32_t)wa, (uint32_t)wb);
+  uint16_t* v = val + fr.val_off;
+  for (int ch = 0; ch < c; ++ch) {
+    const int64_t va = v[lo * c + ch], hh = (int64_t)v[i * c + ch] - va;
+    v[lo * c + ch] = (uint16_t)(va + at_floor_div(wb * hh, w));
+    hh_all[fr.val_off + r * c + ch] = (int32_t)hh;
+  }
+}
+
+// behind the last sublevel: val[0] - H to place 0, where k_at_mean leaves x[0]; one thread per (frame, channel)
+__global__ __launch_bounds__(256) void k_ar_mean(const AFrame* __restrict__ tab, int nf, const uint16_t* __restrict__ val,
+                                                 int32_t* __restrict__ hh_all) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x, f = t >> 2, ch = t & 3;
+  if (f >= nf || ch >= tab[f].c) return;
+  const AFrame& h = tab[f];
+  hh_all[h.val_off + ch] = (int32_t)val[h.val_off + ch] - (1 << (8 * h.bpv - 1));
+}
+
+// one candidate row: frame `src_off / pt0` at the steps q
+struct ARRow {
+  int64_t src_off;   // the frame's differences, hh_all[src_off + r c + ch]
+  int64_t pt0;       // its places among the call's points, wts[pt0 + r]
+  int64_t dst_off;   // the row's indices, idx[dst_off + r c + ch]: the val_off of the row's AFrame
+  int64_t vals;      // n c
+  int32_t blk0;      // the row owns blocks [blk0, blk0 + ceil(vals / 256)) of its launch
+  int32_t c, bpv, pad;
+  int32_t q[4];
+};
+
+// the quantiser of k_at_lift over the rows [0, nr) of a launch, one thread per value, neighbouring threads neighbouring
+// values: 4 bytes in (the weights of a point are read by its c threads from one line), 2 bytes out.  Place 0 is copied
+__global__ __launch_bounds__(256) void k_ar_quant(const ARRow* __restrict__ rows, int nr, const int32_t* __restrict__ hh_all,
+                                                  const uint2* __restrict__ wts, uint16_t* __restrict__ idx) {
+  const int row = o2_find(nr, blockIdx.x, [&](int i) { return (int64_t)rows[i].blk0; });
+  const ARRow& h = rows[row];
+  const int64_t k = ((int64_t)blockIdx.x - h.blk0) * blockDim.x + threadIdx.x;
+  if (k >= h.vals) return;
+  const int c = h.c;
+  const int64_t r = k / c;
+  const int ch = (int)(k - r * c);
+  const int64_t H = (int64_t)1 << (8 * h.bpv - 1);
+  const uint32_t mask = (1u << (8 * h.bpv)) - 1u;
+  const int64_t hh = hh_all[h.src_off + k];
+  int64_t x = hh;
+  if (r > 0) {
+    const uint2 wt = wts[h.pt0 + r];
+    const int64_t s = at_step(h.q[ch], wt.x, wt.y);
+    const int64_t m = std::min<int64_t>(((hh < 0 ? -hh : hh) + s / 2) / s, H - 1);
+    x = hh < 0 ? -m : m;
+  }
+  idx[h.dst_off + k] = (uint16_t)((uint32_t)x & mask);
+}
+
+// the winners' chunk words, final states and lane lengths, from where the coder left them (chunk src of the call's
+// candidate chunks) to a table that k_a_pack can walk (chunk dst); pick = blockIdx.y
+struct ARPick {
+  int32_t src, dst, nc, pad;
+};
+__global__ __launch_bounds__(256) void k_ar_gather(const ARPick* __restrict__ picks, const uint32_t* __restrict__ words,
+                                                   const uint16_t* __restrict__ states, const uint16_t* __restrict__ lens,
+                                                   uint32_t* __restrict__ words_o, uint16_t* __restrict__ states_o,
+                                                   uint16_t* __restrict__ lens_o) {
+  const ARPick p = picks[blockIdx.y];
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < (int64_t)p.nc) words_o[p.dst + t] = words[p.src + t];
+  if (t < (int64_t)p.nc * kLanes) lens_o[(int64_t)p.dst * kLanes + t] = lens[(int64_t)p.src * kLanes + t];
+  if (t < (int64_t)p.nc * 2 * kLanes) states_o[(int64_t)p.dst * 2 * kLanes + t] = states[(int64_t)p.src * 2 * kLanes + t];
+}
+
 }  // namespace
 
 static inline int64_t a_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
@@ -1562,26 +1675,82 @@ struct ACoder {
   static constexpr bool PRED = !V2 && !NL && !XC;   // only version 1 predicts inside the run, and not beside cross-channel frames
 };
 
+// the arguments every encode entry point shares, checked; *n_keys = the sorted keys that belong to kept rows (no run may
+// reach a dropped row's key)
+static int a_check_call(const char* who, const AEncKind& k, pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
+                        const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames, const uint32_t* d_perm,
+                        const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys, int key_shift, uint8_t* h_out,
+                        int64_t cap, int64_t* h_offsets, int64_t* n_keys) {
+  const bool drops = k.n_kept >= 0;
+  PCC_REQUIRE(ctx && h_value_offsets && h_format && h_rows && h_points && h_out && h_offsets && n_frames >= 1 &&
+                  n_frames <= 65535 && n_unique >= 0 && cap >= 0,
+              PCC_E_ARG, "%s: bad argument (n_frames=%d)", who, n_frames);
+  PCC_REQUIRE(!drops || k.n_kept <= h_rows[n_frames], PCC_E_ARG, "%s: %lld kept rows of %lld", who, (long long)k.n_kept,
+              (long long)h_rows[n_frames]);
+  *n_keys = drops ? k.n_kept : h_rows[n_frames];
+  PCC_REQUIRE(h_rows[0] == 0 && h_rows[n_frames] < ((int64_t)1 << 27) && n_unique <= *n_keys &&
+                  (*n_keys == 0 || (d_values && d_perm && d_run_starts)),
+              PCC_E_ARG, "%s: %lld rows, %lld points", who, (long long)*n_keys, (long long)n_unique);
+  PCC_REQUIRE(!k.keyed() || (key_shift >= 0 && key_shift <= 45 && key_shift % 3 == 0 && (*n_keys == 0 || d_keys)), PCC_E_ARG,
+              "%s: bad argument (key_shift=%d)", who, key_shift);
+  PCC_REQUIRE(!k.K || k.K + key_shift / 3 <= kAttrMaxLod, PCC_E_ARG, "%s: scalable_to %d with key_shift %d: beyond level of detail %d", who,
+              k.K, key_shift, kAttrMaxLod);
+  return PCC_OK;
+}
+
+// frame f of an encode call, checked as its kind asks.  *r: its row of the coder's table but for its places in the
+// call's arrays (u0, val_off, rec_off, ctx_off, out_off, cb, sb, mb), which the caller counts; r->n = 0: no points, no row
+static int a_check_frame(const char* who, const AEncKind& k, int f, const int64_t* h_value_offsets, const int32_t* h_format,
+                         const int64_t* h_rows, const int64_t* h_points, AFrame* r) {
+  const int bpv = h_format[f] & 0xFF, c = h_format[f] >> 8;
+  const int64_t rows = h_rows[f + 1] - h_rows[f], n = h_points[f];
+  PCC_REQUIRE((bpv == 1 || bpv == 2) && c >= 1 && c <= 4, PCC_E_ARG, "%s: frame %d: format %d", who, f,
+              h_format[f]);
+  PCC_REQUIRE(rows >= 0 && n >= 0 && n <= rows && ((n == 0) == (rows == 0) || (k.n_kept >= 0 && n == 0)) &&
+                  h_value_offsets[f] >= 0, PCC_E_ARG,
+              "%s: frame %d: %lld rows, %lld points", who, f, (long long)rows, (long long)n);
+  PCC_REQUIRE(!k.nl || k.tc || (uint32_t)k.e <= attr_max_error(bpv), PCC_E_ARG,
+              "%s: frame %d: %s %d with %d bytes per value (at most %u)", who, f, k.tr ? "qstep" : "max_error", k.e, bpv,
+              attr_max_error(bpv));
+  if (k.tc) {
+    for (int ch = 0; ch < c; ++ch)
+      PCC_REQUIRE(k.h_qsteps[ch] >= 1 && (uint32_t)k.h_qsteps[ch] <= attr_max_error(bpv), PCC_E_ARG,
+                  "%s: frame %d: qstep %d of channel %d with %d bytes per value (1 .. %u)", who, f, k.h_qsteps[ch], ch, bpv,
+                  attr_max_error(bpv));
+    PCC_REQUIRE(!k.colour || c >= 3, PCC_E_ARG, "%s: frame %d: the colour transform needs 3 channels, the frame has %d", who, f, c);
+  }
+  const int32_t m = k.h_cross ? k.h_cross[f] : 0;
+  PCC_REQUIRE(m >= 0 && m < (1 << (c - 1)), PCC_E_ARG, "%s: frame %d: cross-channel mask %d with %d channels", who, f, m, c);
+  int64_t S, nc;
+  attr_layout(n, c, &S, &nc);
+  *r = AFrame{};
+  r->e = k.e;
+  r->in_off = h_value_offsets[f];
+  r->row0 = h_rows[f];
+  r->rows = rows;
+  r->n = n;
+  r->c = c;
+  r->bpv = bpv;
+  r->nctx = attr_contexts(bpv, c);
+  r->T = (int32_t)(S * c * attr_positions(bpv));
+  // a coded decision emits at most one word: the bound follows the frame's decisions, not its chunks' regions
+  r->out_cap = a_head_bytes(k, c, r->nctx, nc) + 2 * (3 * kLanes * nc + std::min<int64_t>(nc * kLanes * r->T, (int64_t)attr_positions(bpv) * c * n));
+  r->S = (int32_t)S;
+  r->nc = (int32_t)nc;
+  r->sn = (int32_t)std::min<unsigned>(nblk(n, 256), 256u);
+  return PCC_OK;
+}
+
 // the encoder of every kind: k_a_merge, the kind's passes of the table above, k_ax_fwd in a call with any m != 0 among
 // its frames with points (every frame is then coded with PRED = false), counting pass, coder, blobs
 static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
                            const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames,
                            const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys,
                            int key_shift, uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
-  const bool v2 = k.v2, nl = k.nl, tr = k.tr, tc = k.tc, sc = k.K > 0, keyed = k.keyed(), drops = k.n_kept >= 0;
-  PCC_REQUIRE(ctx && h_value_offsets && h_format && h_rows && h_points && h_out && h_offsets && n_frames >= 1 &&
-                  n_frames <= 65535 && n_unique >= 0 && cap >= 0,
-              PCC_E_ARG, "%s: bad argument (n_frames=%d)", who, n_frames);
-  PCC_REQUIRE(!drops || k.n_kept <= h_rows[n_frames], PCC_E_ARG, "%s: %lld kept rows of %lld", who, (long long)k.n_kept,
-              (long long)h_rows[n_frames]);
-  const int64_t n_keys = drops ? k.n_kept : h_rows[n_frames];   // no run may reach a dropped row's key
-  PCC_REQUIRE(h_rows[0] == 0 && h_rows[n_frames] < ((int64_t)1 << 27) && n_unique <= n_keys &&
-                  (n_keys == 0 || (d_values && d_perm && d_run_starts)),
-              PCC_E_ARG, "%s: %lld rows, %lld points", who, (long long)n_keys, (long long)n_unique);
-  PCC_REQUIRE(!keyed || (key_shift >= 0 && key_shift <= 45 && key_shift % 3 == 0 && (n_keys == 0 || d_keys)), PCC_E_ARG,
-              "%s: bad argument (key_shift=%d)", who, key_shift);
-  PCC_REQUIRE(!sc || k.K + key_shift / 3 <= kAttrMaxLod, PCC_E_ARG, "%s: scalable_to %d with key_shift %d: beyond level of detail %d", who,
-              k.K, key_shift, kAttrMaxLod);
+  const bool v2 = k.v2, nl = k.nl, tr = k.tr, tc = k.tc, sc = k.K > 0, keyed = k.keyed();
+  int64_t n_keys = 0;
+  PCC_TRY(a_check_call(who, k, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys,
+                       key_shift, h_out, cap, h_offsets, &n_keys));
   std::vector<AFrame> tab;
   std::vector<A2Order> order;
   std::vector<int> frame_of;
@@ -1592,26 +1761,12 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
   int64_t run_threads = 0;   // k_a4_quant: the most (run, channel) pairs of a frame
   int64_t u = 0, vals = 0, rec_words = 0, out_bytes = 0, chunks = 0, stats_blocks = 0, merge_blocks = 0, ctxs = 0, nctx_max = 0;
   for (int f = 0; f < n_frames; ++f) {
-    const int bpv = h_format[f] & 0xFF, c = h_format[f] >> 8;
-    const int64_t rows = h_rows[f + 1] - h_rows[f], n = h_points[f];
-    PCC_REQUIRE((bpv == 1 || bpv == 2) && c >= 1 && c <= 4, PCC_E_ARG, "%s: frame %d: format %d", who, f,
-                h_format[f]);
-    PCC_REQUIRE(rows >= 0 && n >= 0 && n <= rows && ((n == 0) == (rows == 0) || (drops && n == 0)) &&
-                    h_value_offsets[f] >= 0, PCC_E_ARG,
-                "%s: frame %d: %lld rows, %lld points", who, f, (long long)rows, (long long)n);
-    PCC_REQUIRE(!nl || tc || (uint32_t)k.e <= attr_max_error(bpv), PCC_E_ARG,
-                "%s: frame %d: %s %d with %d bytes per value (at most %u)", who, f, tr ? "qstep" : "max_error", k.e, bpv,
-                attr_max_error(bpv));
-    if (tc) {
-      for (int ch = 0; ch < c; ++ch)
-        PCC_REQUIRE(k.h_qsteps[ch] >= 1 && (uint32_t)k.h_qsteps[ch] <= attr_max_error(bpv), PCC_E_ARG,
-                    "%s: frame %d: qstep %d of channel %d with %d bytes per value (1 .. %u)", who, f, k.h_qsteps[ch], ch, bpv,
-                    attr_max_error(bpv));
-      PCC_REQUIRE(!k.colour || c >= 3, PCC_E_ARG, "%s: frame %d: the colour transform needs 3 channels, the frame has %d", who, f, c);
-    }
-    const int32_t m = k.h_cross ? k.h_cross[f] : 0;
-    PCC_REQUIRE(m >= 0 && m < (1 << (c - 1)), PCC_E_ARG, "%s: frame %d: cross-channel mask %d with %d channels", who, f, m, c);
+    AFrame r;
+    PCC_TRY(a_check_frame(who, k, f, h_value_offsets, h_format, h_rows, h_points, &r));
+    const int c = r.c;
+    const int64_t n = r.n, nc = r.nc;
     if (n == 0) continue;
+    const int32_t m = k.h_cross ? k.h_cross[f] : 0;
     cross.push_back(m);
     xc |= m != 0;
     if (tc) {
@@ -1619,30 +1774,13 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
       aux.push_back(k.colour);
     }
     n_max = std::max(n_max, n);
-    AFrame r;
-    int64_t S, nc;
-    attr_layout(n, c, &S, &nc);
-    r.e = k.e;
-    r.in_off = h_value_offsets[f];
-    r.row0 = h_rows[f];
-    r.rows = rows;
     r.u0 = u;
-    r.n = n;
     r.val_off = vals;
     r.rec_off = rec_words;
-    r.c = c;
-    r.bpv = bpv;
-    r.nctx = attr_contexts(bpv, c);
     r.ctx_off = (int32_t)ctxs;
-    r.T = (int32_t)(S * c * attr_positions(bpv));
-    // a coded decision emits at most one word: the bound follows the frame's decisions, not its chunks' regions
-    r.out_cap = a_head_bytes(k, c, r.nctx, nc) + 2 * (3 * kLanes * nc + std::min<int64_t>(nc * kLanes * r.T, (int64_t)attr_positions(bpv) * c * n));
     r.out_off = out_bytes;
-    r.S = (int32_t)S;
-    r.nc = (int32_t)nc;
     r.cb = (int32_t)chunks;
     r.sb = (int32_t)stats_blocks;
-    r.sn = (int32_t)std::min<unsigned>(nblk(n, 256), 256u);
     r.mb = (int32_t)merge_blocks;
     tab.push_back(r);
     order.push_back(A2Order{u, n, r.mb, key_shift});
@@ -1923,6 +2061,462 @@ extern "C" int pcc_attr_encode_frames_transform3(pcc_ctx* ctx, const void* d_val
   return a_encode_frames("pcc_attr_encode_frames_transform3", a_kind_transform(n_kept, 0, h_qstep, colour, scalable_to), ctx, d_values,
                          h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap,
                          h_offsets);
+}
+
+// ---- versions 19 and 21 under a byte target per frame (include/pcc.h states the ladder and the search) --------------
+constexpr int kARMaxRungs = 64;                         // uint16, q = 1: 61
+constexpr int64_t kARScratchDefault = (int64_t)1 << 30;   // scratch_limit = 0
+
+// the ladder of base steps q[0 .. c): steps[j][ch] (0 behind c); returns J
+static int a_r_ladder(const int32_t* q, int c, int bpv, int32_t (*steps)[4]) {
+  static const int64_t mul[4] = {16, 19, 23, 27};
+  const int64_t top = ((int64_t)1 << (8 * bpv - 1)) - 1;
+  for (int j = 0; j < kARMaxRungs; ++j) {
+    bool last = true;
+    for (int ch = 0; ch < 4; ++ch) {
+      const int64_t s = ch < c ? std::min<int64_t>(top, (((int64_t)q[ch] * mul[j % 4]) << (j / 4)) >> 4) : 0;
+      steps[j][ch] = (int32_t)s;
+      last &= ch >= c || s == top;
+    }
+    if (last) return j + 1;
+  }
+  return kARMaxRungs;   // not reached: q >= 1 is at H - 1 from rung 60 on
+}
+
+extern "C" int pcc_attr_rate_ladder(const int32_t h_qstep[4], int c, int bpv, int32_t* h_steps, int32_t* h_rungs) {
+  PCC_REQUIRE(h_qstep && h_steps && h_rungs && (bpv == 1 || bpv == 2) && c >= 1 && c <= 4, PCC_E_ARG,
+              "pcc_attr_rate_ladder: bad argument (c=%d bpv=%d)", c, bpv);
+  for (int ch = 0; ch < c; ++ch)
+    PCC_REQUIRE(h_qstep[ch] >= 1 && (uint32_t)h_qstep[ch] <= attr_max_error(bpv), PCC_E_ARG,
+                "pcc_attr_rate_ladder: qstep %d of channel %d with %d bytes per value (1 .. %u)", h_qstep[ch], ch, bpv, attr_max_error(bpv));
+  *h_rungs = a_r_ladder(h_qstep, c, bpv, reinterpret_cast<int32_t(*)[4]>(h_steps));
+  return PCC_OK;
+}
+
+// a candidate row on the host: frame fi (of the frames with points) at rung `rung`
+struct ARCand {
+  int fi, rung;
+  int64_t cb, ctx_off;     // its chunks among the call's candidate chunks, its contexts among the call's
+  int64_t idx_off, rec_off, work_off;   // in the scratch block, 16-bit words from its start
+  int epoch;               // the scratch block's turn that holds them
+  int64_t len;             // bytes of the blob it would give
+};
+
+// the scratch block of the candidate rows' indices, records and word regions: groups of rows take it in turn; a group
+// that does not fit behind the ones before it starts the block over, and what those left is gone
+struct ARScratch {
+  size_t cap = 0, used = 0;
+  int epoch = 0;
+};
+
+extern "C" int pcc_attr_encode_frames_rate(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets, const int32_t* h_format,
+                                           const int64_t* h_rows, const int64_t* h_points, int n_frames, const uint32_t* d_perm,
+                                           const uint32_t* d_run_starts, int64_t n_unique, int64_t n_kept, const uint64_t* d_keys,
+                                           int key_shift, const int32_t h_qstep[4], int per_channel, int colour,
+                                           const int64_t* h_target, int64_t scratch_limit, uint8_t* h_out, int64_t cap,
+                                           int64_t* h_offsets, int32_t* h_rung) {
+  const char* who = "pcc_attr_encode_frames_rate";
+  PCC_REQUIRE(n_kept >= -1 && h_qstep && h_target && (colour == 0 || colour == 1) && (per_channel == 0 || per_channel == 1) &&
+                  (per_channel || (!colour && h_qstep[0] >= 1)) && scratch_limit >= 0,
+              PCC_E_ARG, "%s: bad argument (n_kept=%lld per_channel=%d colour=%d scratch_limit=%lld)", who, (long long)n_kept, per_channel,
+              colour, (long long)scratch_limit);
+  const bool tc = per_channel != 0;
+  const AEncKind kind = a_kind_transform(n_kept, h_qstep[0], tc ? h_qstep : nullptr, colour);
+  int64_t n_keys = 0;
+  PCC_TRY(a_check_call(who, kind, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys,
+                       key_shift, h_out, cap, h_offsets, &n_keys));
+
+  // the frames with points: their rows as a_encode_frames lays them out, their ladders, their stage-1 rungs
+  struct Lad {
+    int32_t steps[kARMaxRungs][4];
+    int J;
+  };
+  std::vector<AFrame> tab;
+  std::vector<A2Order> order;
+  std::vector<int> frame_of;
+  std::vector<int32_t> aux;
+  std::vector<Lad> lad;
+  int64_t n_max = 0, u = 0, vals = 0, out_bytes = 0, merge_blocks = 0, nctx_max = 0;
+  int64_t rows_max = 0, chunks_max = 0, ctxs_max = 0;   // candidate rows the call may code, their chunks and contexts
+  size_t row_need_max = 0, need_all = 0;                // scratch of the largest row, of all rows at once
+  auto row_need = [](const AFrame& r) { return pcc_align((size_t)r.n * r.c * 2) + 2 * pcc_align((size_t)r.nc * kLanes * r.T * 2); };
+  for (int f = 0; f < n_frames; ++f) {
+    AFrame r;
+    PCC_TRY(a_check_frame(who, kind, f, h_value_offsets, h_format, h_rows, h_points, &r));
+    PCC_REQUIRE(h_target[f] >= 1, PCC_E_ARG, "%s: frame %d: a target of %lld bytes (at least 1)", who, f, (long long)h_target[f]);
+    const int c = r.c, bpv = r.bpv;
+    const int64_t n = r.n, nc = r.nc;
+    if (n == 0) continue;
+    int32_t q[4];
+    for (int ch = 0; ch < 4; ++ch) q[ch] = ch < c ? h_qstep[tc ? ch : 0] : 0;
+    lad.emplace_back();
+    lad.back().J = a_r_ladder(q, c, bpv, lad.back().steps);
+    for (int ch = 0; ch < 4; ++ch) aux.push_back(q[ch]);
+    aux.push_back(colour);
+    n_max = std::max(n_max, n);
+    r.u0 = u;               // a candidate row's places among the coder's arrays are its own (code_rows)
+    r.val_off = vals;
+    r.out_off = out_bytes;
+    r.mb = (int32_t)merge_blocks;
+    tab.push_back(r);
+    order.push_back(A2Order{u, n, r.mb, key_shift});
+    frame_of.push_back(f);
+    const int64_t rows_f = (lad.back().J + 3) / 4 + 1 + 3 + 1;   // stage 1 | stage 2 | once more at the end
+    rows_max += rows_f;
+    chunks_max += rows_f * nc;
+    ctxs_max += rows_f * r.nctx;
+    row_need_max = std::max(row_need_max, row_need(r));
+    need_all += (size_t)(rows_f - 1) * row_need(r);
+    u += n;
+    vals += n * c;
+    out_bytes += a_round(r.out_cap, 16);
+    merge_blocks += nblk(n, 256);
+    nctx_max = std::max<int64_t>(nctx_max, r.nctx);
+  }
+  PCC_REQUIRE(u == n_unique, PCC_E_ARG, "%s: the frames have %lld points, the runs %lld", who, (long long)u, (long long)n_unique);
+  const int nf = (int)tab.size();
+  std::vector<int64_t> len_of((size_t)n_frames, kAttrHead);
+  std::vector<int64_t> off_of((size_t)n_frames, -1);
+  std::vector<int> rung_of((size_t)n_frames, -1);
+  hipStream_t st = ctx->stream;
+  if (nf > 0) {
+    ARScratch scr;
+    scr.cap = std::max(row_need_max, std::min(need_all, (size_t)(scratch_limit ? scratch_limit : kARScratchDefault)));
+    // device tables: the frames' rows | steps and colour | order rows || per candidate row an AFrame and an ARRow ||
+    // the winners' rows, their steps and colour, their picks
+    ATables lay;
+    lay.add((size_t)nf * sizeof(AFrame));
+    const size_t aux_at = lay.add((size_t)nf * 20), ord_at = lay.add((size_t)nf * sizeof(A2Order));
+    const size_t base_end = lay.end;
+    const size_t crow_at = lay.add((size_t)rows_max * sizeof(AFrame)), qrow_at = lay.add((size_t)rows_max * sizeof(ARRow));
+    const size_t wrow_at = lay.add((size_t)nf * sizeof(AFrame)), waux_at = lay.add((size_t)nf * 20);
+    const size_t pick_at = lay.add((size_t)nf * sizeof(ARPick)), tab_b = lay.bytes;
+    int64_t win_chunks = 0;
+    for (const AFrame& r : tab) win_chunks += r.nc;
+    auto small_of = [](int64_t chunks) { return pcc_align((size_t)chunks * (4 + 2 * kLanes * 2 + kLanes * 2)); };
+    const size_t merged_b = merged_b_of(vals), hh_b = pcc_align((size_t)vals * 4), wts_b = pcc_align((size_t)u * 8);
+    const size_t cnt_b = pcc_align((size_t)ctxs_max * 8), p0_b = pcc_align((size_t)ctxs_max * 2);
+    const size_t pk_b = pcc_align((size_t)u * 2), link_b = pcc_align((size_t)u * 4);
+    const size_t thist_b = pcc_align((size_t)merge_blocks * kATBins * 4), tbins_b = pcc_align((size_t)nf * 2 * kATBins * 4);
+    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + hh_b + wts_b + cnt_b + p0_b + small_of(chunks_max) + small_of(win_chunks) + pk_b +
+                                       link_b + thist_b + tbins_b + scr.cap + 8192));
+    uint8_t* d_tabs = (uint8_t*)pcc_arena_alloc(ctx, tab_b);
+    uint16_t* merged = (uint16_t*)pcc_arena_alloc(ctx, merged_b);
+    int32_t* hh = (int32_t*)pcc_arena_alloc(ctx, hh_b);
+    uint2* wts = (uint2*)pcc_arena_alloc(ctx, wts_b);
+    uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, cnt_b);
+    uint16_t* p0 = (uint16_t*)pcc_arena_alloc(ctx, p0_b);
+    char* small = (char*)pcc_arena_alloc(ctx, small_of(chunks_max));
+    char* wsmall = (char*)pcc_arena_alloc(ctx, small_of(win_chunks));
+    uint16_t* scratch = (uint16_t*)pcc_arena_alloc(ctx, scr.cap);
+    if (!d_tabs || !merged || !hh || !wts || !cnt || !p0 || !small || !wsmall || !scratch) return PCC_E_NOMEM;
+    uint32_t* words = (uint32_t*)small;
+    uint16_t* states = (uint16_t*)(small + (size_t)chunks_max * 4);
+    uint16_t* lens_d = states + (size_t)chunks_max * 2 * kLanes;
+    uint32_t* wwords = (uint32_t*)wsmall;
+    uint16_t* wstates = (uint16_t*)(wsmall + (size_t)win_chunks * 4);
+    uint16_t* wlens = wstates + (size_t)win_chunks * 2 * kLanes;
+    const AFrame* d_tab = (const AFrame*)d_tabs;
+    const int32_t* d_aux = (const int32_t*)(d_tabs + aux_at);
+    const A2Order* d_ord = (const A2Order*)(d_tabs + ord_at);
+    const AFrame* d_crow = (const AFrame*)(d_tabs + crow_at);
+    const ARRow* d_qrow = (const ARRow*)(d_tabs + qrow_at);
+    // staging: the tables on their way to the device | the blobs | their lengths | the sublevels' bins | the chunks' words
+    const size_t lens_at = tab_b + (size_t)out_bytes, tcnt_at = lens_at + (size_t)nf * 8 + 64;
+    const size_t hwords_at = tcnt_at + pcc_align((size_t)nf * 2 * kATBins * 4);
+    PCC_TRY(o2_stage_reserve(ctx, hwords_at + (size_t)chunks_max * 4 + 64));
+    uint8_t* stage = (uint8_t*)ctx->stage;
+    memcpy(stage, tab.data(), (size_t)nf * sizeof(AFrame));
+    memcpy(stage + aux_at, aux.data(), (size_t)nf * 20);
+    memcpy(stage + ord_at, order.data(), (size_t)nf * sizeof(A2Order));
+    long long* len_dev = (long long*)(stage + lens_at);
+    const uint32_t* h_words = (const uint32_t*)(stage + hwords_at);
+    PccProfScope prof(ctx, "attr_encode_rate", u, nf, rows_max, 0);
+    PCC_HIP(hipMemcpyAsync(d_tabs, stage, base_end, hipMemcpyHostToDevice, st));
+    PCC_HIP(hipMemsetAsync(cnt, 0, (size_t)ctxs_max * 8, st));
+    hipLaunchKernelGGL(k_a_merge, dim3((unsigned)merge_blocks), dim3(256), 0, st, (const uint8_t*)d_values, d_tab, nf, d_perm, d_run_starts,
+                       n_unique, n_keys, merged);
+    PCC_CHECK_LAUNCH();
+    if (colour) {
+      hipLaunchKernelGGL(k_ac_fwd, dim3(nblk(n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, d_aux, merged);
+      PCC_CHECK_LAUNCH();
+    }
+    // the order stage and the lift, once for every rung
+    {
+      uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, pk_b);
+      uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, thist_b);
+      uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, tbins_b);
+      uint32_t* inv = (uint32_t*)pcc_arena_alloc(ctx, link_b);
+      if (!packed || !hist || !bins || !inv) return PCC_E_NOMEM;
+      unsigned grid[kATBins];
+      PCC_TRY(a_t_order(st, false, (const void*)d_keys, nullptr, d_ord, nf, merge_blocks, packed, hist, bins, inv, (uint32_t*)(stage + tcnt_at),
+                        grid));
+      for (int t = 0; t < kATBins - 1; ++t) {
+        if (!grid[t]) continue;
+        hipLaunchKernelGGL(k_ar_lift, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, d_keys, d_ord, (const uint32_t*)bins, (const uint32_t*)inv,
+                           t, d_tab, merged, hh, wts);
+        PCC_CHECK_LAUNCH();
+      }
+      hipLaunchKernelGGL(k_ar_mean, dim3(nblk(4 * (int64_t)nf, 256)), dim3(256), 0, st, d_tab, nf, (const uint16_t*)merged, hh);
+      PCC_CHECK_LAUNCH();
+    }
+
+    // candidate rows: laid out, uploaded and coded stage by stage
+    std::vector<ARCand> cand;
+    std::vector<AFrame> crow;   // cand[i]'s row of the coder's table
+    std::vector<ARRow> qrow;    // and of the quantiser's
+    int64_t chunks_used = 0, ctxs_used = 0;
+    const size_t lds = 4096 * 4 + (size_t)(nctx_max + 1) * kLanes * 2;
+    PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // codes the rows `want` (frame, rung) in groups that fit the scratch block; appends them to cand
+    auto code_rows = [&](const std::vector<std::pair<int, int>>& want) -> int {
+      const size_t first = cand.size();
+      PCC_REQUIRE(first + want.size() <= (size_t)rows_max, PCC_E_NOMEM, "%s: %zu candidate rows, room for %lld", who, first + want.size(),
+                  (long long)rows_max);
+      struct Group {
+        size_t r0, r1, base;   // rows, where the group starts in the scratch block (bytes)
+        int64_t rec_words, quant_blocks, stats_blocks, chunks, cb;
+      };
+      std::vector<Group> groups;
+      for (size_t w = 0; w < want.size();) {
+        size_t w1 = w, bytes = 0;
+        while (w1 < want.size() && scr.used + bytes + row_need(tab[(size_t)want[w1].first]) <= scr.cap) bytes += row_need(tab[(size_t)want[w1++].first]);
+        if (w1 == w) {   // the block starts over: one row always fits
+          scr.used = 0;
+          ++scr.epoch;
+          continue;
+        }
+        Group g{first + w, first + w1, scr.used, 0, 0, 0, 0, chunks_used};
+        size_t idx_b = 0;
+        for (size_t i = w; i < w1; ++i) {
+          const AFrame& b = tab[(size_t)want[i].first];
+          idx_b += pcc_align((size_t)b.n * b.c * 2);
+          g.rec_words += (int64_t)(pcc_align((size_t)b.nc * kLanes * b.T * 2) / 2);
+        }
+        size_t idx_at = g.base / 2, rec_at = (g.base + idx_b) / 2;   // 16-bit words from the block's start
+        for (size_t i = w; i < w1; ++i) {
+          const int fi = want[i].first, rung = want[i].second;
+          const AFrame& b = tab[(size_t)fi];
+          ARCand cd{fi, rung, chunks_used, ctxs_used, (int64_t)idx_at, (int64_t)rec_at, (int64_t)rec_at + g.rec_words, scr.epoch, 0};
+          AFrame r = b;
+          r.val_off = cd.idx_off;
+          r.rec_off = cd.rec_off;
+          r.ctx_off = (int32_t)cd.ctx_off;
+          r.cb = (int32_t)g.chunks;
+          r.sb = (int32_t)g.stats_blocks;
+          ARRow q{b.val_off, order[(size_t)fi].pt0, cd.idx_off, b.n * b.c, (int32_t)g.quant_blocks, b.c, b.bpv, 0, {0, 0, 0, 0}};
+          for (int ch = 0; ch < 4; ++ch) q.q[ch] = lad[(size_t)fi].steps[rung][ch];
+          cand.push_back(cd);
+          crow.push_back(r);
+          qrow.push_back(q);
+          g.chunks += b.nc;
+          g.stats_blocks += b.sn;
+          g.quant_blocks += nblk(b.n * b.c, 256);
+          chunks_used += b.nc;
+          ctxs_used += b.nctx;
+          idx_at += pcc_align((size_t)b.n * b.c * 2) / 2;
+          rec_at += pcc_align((size_t)b.nc * kLanes * b.T * 2) / 2;
+        }
+        scr.used += bytes;
+        groups.push_back(g);
+        w = w1;
+      }
+      const size_t nr = want.size();
+      memcpy(stage + crow_at + first * sizeof(AFrame), crow.data() + first, nr * sizeof(AFrame));
+      memcpy(stage + qrow_at + first * sizeof(ARRow), qrow.data() + first, nr * sizeof(ARRow));
+      PCC_HIP(hipMemcpyAsync(d_tabs + crow_at + first * sizeof(AFrame), stage + crow_at + first * sizeof(AFrame), nr * sizeof(AFrame),
+                             hipMemcpyHostToDevice, st));
+      PCC_HIP(hipMemcpyAsync(d_tabs + qrow_at + first * sizeof(ARRow), stage + qrow_at + first * sizeof(ARRow), nr * sizeof(ARRow),
+                             hipMemcpyHostToDevice, st));
+      for (const Group& g : groups) {
+        const int n_r = (int)(g.r1 - g.r0);
+        hipLaunchKernelGGL(k_ar_quant, dim3((unsigned)g.quant_blocks), dim3(256), 0, st, d_qrow + g.r0, n_r, (const int32_t*)hh,
+                           (const uint2*)wts, scratch);
+        PCC_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_a_stats<false>, dim3((unsigned)g.stats_blocks), dim3(256), 0, st, (const uint16_t*)scratch, d_crow + g.r0, n_r, cnt);
+        PCC_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_a_enc<false>, dim3((unsigned)g.chunks), dim3(64), lds, st, (const uint16_t*)scratch, d_crow + g.r0, n_r,
+                           (const uint32_t*)cnt, scratch, scratch + g.rec_words, states + g.cb * 2 * kLanes, lens_d + g.cb * kLanes,
+                           words + g.cb, p0);
+        PCC_CHECK_LAUNCH();
+      }
+      return PCC_OK;
+    };
+    // the lengths of the rows cand[first ..): one read-back of their chunks' words, one synchronisation
+    auto read_lens = [&](size_t first) -> int {
+      if (first == cand.size()) return PCC_OK;
+      const int64_t c0 = cand[first].cb;
+      PCC_HIP(hipMemcpyAsync((void*)(h_words + c0), words + c0, (size_t)(chunks_used - c0) * 4, hipMemcpyDeviceToHost, st));
+      PCC_HIP(hipStreamSynchronize(st));
+      for (size_t i = first; i < cand.size(); ++i) {
+        const AFrame& b = tab[(size_t)cand[i].fi];
+        int64_t w = 0;
+        for (int64_t k = 0; k < b.nc; ++k) w += ((volatile const uint32_t*)h_words)[cand[i].cb + k];
+        cand[i].len = a_head_bytes(kind, b.c, b.nctx, b.nc) + 2 * w;
+      }
+      return PCC_OK;
+    };
+
+    // stage 1: the rungs of A = { j : j % 4 == 0 } and J - 1
+    std::vector<std::pair<int, int>> want;
+    std::vector<size_t> s1_at((size_t)nf + 1);
+    for (int i = 0; i < nf; ++i) {
+      s1_at[(size_t)i] = want.size();
+      const int J = lad[(size_t)i].J;
+      for (int j = 0; j < J; j += 4) want.emplace_back(i, j);
+      if ((J - 1) % 4) want.emplace_back(i, J - 1);
+    }
+    s1_at[(size_t)nf] = want.size();
+    PCC_TRY(code_rows(want));
+    PCC_TRY(read_lens(0));
+    // the search, stage 1: win[i] = the frame's row where it is decided; else stage 2 codes the rungs inside (a', a)
+    std::vector<int64_t> win((size_t)nf, -1), s2_fall((size_t)nf, -1);
+    want.clear();
+    for (int i = 0; i < nf; ++i) {
+      const int64_t B = h_target[frame_of[(size_t)i]];
+      size_t a = s1_at[(size_t)i];
+      while (a < s1_at[(size_t)i + 1] && cand[a].len > B) ++a;
+      if (a == s1_at[(size_t)i + 1]) win[(size_t)i] = (int64_t)a - 1;   // nothing fits: rung J - 1, over its target
+      else if (a == s1_at[(size_t)i] || cand[a].rung - cand[a - 1].rung == 1) win[(size_t)i] = (int64_t)a;
+      else {
+        s2_fall[(size_t)i] = (int64_t)a;
+        for (int j = cand[a - 1].rung + 1; j < cand[a].rung; ++j) want.emplace_back(i, j);
+      }
+    }
+    if (!want.empty()) {
+      const size_t s2 = cand.size();
+      PCC_TRY(code_rows(want));
+      PCC_TRY(read_lens(s2));
+      for (size_t r = s2; r < cand.size(); ++r) {
+        const int i = cand[r].fi;
+        if (win[(size_t)i] < 0 && cand[r].len <= h_target[frame_of[(size_t)i]]) win[(size_t)i] = (int64_t)r;
+      }
+      for (int i = 0; i < nf; ++i)
+        if (win[(size_t)i] < 0) win[(size_t)i] = s2_fall[(size_t)i];
+    }
+    // the winners whose word regions the scratch block no longer holds are coded once more, in groups as above; every
+    // group of winners is assembled (k_ar_gather, k_a_pack) before the next one may take the block
+    std::vector<int> held, lost;
+    for (int i = 0; i < nf; ++i) (cand[(size_t)win[(size_t)i]].epoch == scr.epoch ? held : lost).push_back(i);
+    std::vector<AFrame> wrow;
+    std::vector<ARPick> picks;
+    std::vector<int32_t> waux;
+    struct Batch {
+      int r0, r1;          // winners' rows [r0, r1) of the pack tables
+      int64_t cb, chunks;  // their chunks in the winners' small arrays
+      int64_t nc_max;
+    };
+    std::vector<Batch> batches;
+    int64_t wchunks = 0;
+    auto add_batch = [&](const std::vector<int>& frames, const std::vector<int64_t>& rows) {
+      Batch b{(int)wrow.size(), (int)(wrow.size() + frames.size()), wchunks, 0, 0};
+      for (size_t k = 0; k < frames.size(); ++k) {
+        const ARCand& cd = cand[(size_t)rows[k]];
+        AFrame r = tab[(size_t)frames[k]];
+        r.e = tc ? kind.e : lad[(size_t)cd.fi].steps[cd.rung][0];
+        r.rec_off = cd.work_off;
+        r.ctx_off = (int32_t)cd.ctx_off;
+        r.cb = (int32_t)b.chunks;
+        picks.push_back(ARPick{(int32_t)cd.cb, (int32_t)(b.cb + b.chunks), r.nc, 0});
+        for (int ch = 0; ch < 4; ++ch) waux.push_back(lad[(size_t)cd.fi].steps[cd.rung][ch]);
+        waux.push_back(colour);
+        wrow.push_back(r);
+        b.chunks += r.nc;
+        b.nc_max = std::max<int64_t>(b.nc_max, r.nc);
+        rung_of[(size_t)frame_of[(size_t)frames[k]]] = cd.rung;
+      }
+      wchunks += b.chunks;
+      batches.push_back(b);
+    };
+    auto pack_batch = [&](const Batch& b) -> int {
+      const int n_r = b.r1 - b.r0;
+      const AFrame* d_wrow = (const AFrame*)(d_tabs + wrow_at) + b.r0;
+      hipLaunchKernelGGL(k_ar_gather, dim3(nblk(b.nc_max * 2 * kLanes, 256), (unsigned)n_r), dim3(256), 0, st,
+                         (const ARPick*)(d_tabs + pick_at) + b.r0, (const uint32_t*)words, (const uint16_t*)states, (const uint16_t*)lens_d,
+                         wwords, wstates, wlens);
+      PCC_CHECK_LAUNCH();
+      const unsigned blocks = (unsigned)(b.chunks + n_r);
+      if (tc)
+        hipLaunchKernelGGL((k_a_pack<false, true, false, true, const int32_t*>), dim3(blocks), dim3(256), 0, st, (const uint16_t*)scratch, d_wrow,
+                           n_r, (const uint16_t*)(wstates + b.cb * 2 * kLanes), (const uint16_t*)(wlens + b.cb * kLanes),
+                           (const uint32_t*)(wwords + b.cb), (const uint16_t*)p0, stage + tab_b, len_dev + b.r0, (const uint32_t*)nullptr,
+                           key_shift / 3, (const int32_t*)nullptr, (const int32_t*)(d_tabs + waux_at) + 5 * b.r0);
+      else
+        hipLaunchKernelGGL((k_a_pack<false, true, false, true>), dim3(blocks), dim3(256), 0, st, (const uint16_t*)scratch, d_wrow, n_r,
+                           (const uint16_t*)(wstates + b.cb * 2 * kLanes), (const uint16_t*)(wlens + b.cb * kLanes),
+                           (const uint32_t*)(wwords + b.cb), (const uint16_t*)p0, stage + tab_b, len_dev + b.r0, (const uint32_t*)nullptr,
+                           key_shift / 3, (const int32_t*)nullptr);
+      PCC_CHECK_LAUNCH();
+      return PCC_OK;
+    };
+    auto send_winners = [&](size_t r0) -> int {   // the pack tables' rows [r0, ..) to the device
+      const size_t n_r = wrow.size() - r0;
+      memcpy(stage + wrow_at + r0 * sizeof(AFrame), wrow.data() + r0, n_r * sizeof(AFrame));
+      memcpy(stage + waux_at + r0 * 20, waux.data() + 5 * r0, n_r * 20);
+      memcpy(stage + pick_at + r0 * sizeof(ARPick), picks.data() + r0, n_r * sizeof(ARPick));
+      PCC_HIP(hipMemcpyAsync(d_tabs + wrow_at + r0 * sizeof(AFrame), stage + wrow_at + r0 * sizeof(AFrame), n_r * sizeof(AFrame),
+                             hipMemcpyHostToDevice, st));
+      PCC_HIP(hipMemcpyAsync(d_tabs + waux_at + r0 * 20, stage + waux_at + r0 * 20, n_r * 20, hipMemcpyHostToDevice, st));
+      PCC_HIP(hipMemcpyAsync(d_tabs + pick_at + r0 * sizeof(ARPick), stage + pick_at + r0 * sizeof(ARPick), n_r * sizeof(ARPick),
+                             hipMemcpyHostToDevice, st));
+      return PCC_OK;
+    };
+    std::vector<int> win_row_of;   // the frame (with points) behind every row of the pack tables
+    if (!held.empty()) {
+      std::vector<int64_t> rows;
+      for (int i : held) rows.push_back(win[(size_t)i]);
+      add_batch(held, rows);
+      win_row_of = held;
+      PCC_TRY(send_winners(0));
+      PCC_TRY(pack_batch(batches.back()));
+    }
+    for (size_t k = 0; k < lost.size();) {
+      // as many of them as one turn of the block holds
+      size_t k1 = k, bytes = 0;
+      while (k1 < lost.size() && bytes + row_need(tab[(size_t)lost[k1]]) <= scr.cap) bytes += row_need(tab[(size_t)lost[k1++]]);
+      scr.used = scr.cap;   // this group starts the block over
+      want.clear();
+      std::vector<int> frames(lost.begin() + (long)k, lost.begin() + (long)k1);
+      for (int i : frames) want.emplace_back(i, cand[(size_t)win[(size_t)i]].rung);
+      const size_t first = cand.size();
+      PCC_TRY(code_rows(want));
+      std::vector<int64_t> rows;
+      for (size_t r = first; r < cand.size(); ++r) rows.push_back((int64_t)r);
+      const size_t w0 = wrow.size();
+      add_batch(frames, rows);
+      win_row_of.insert(win_row_of.end(), frames.begin(), frames.end());
+      PCC_TRY(send_winners(w0));
+      PCC_TRY(pack_batch(batches.back()));
+      k = k1;
+    }
+    PCC_HIP(hipStreamSynchronize(st));
+    for (size_t r = 0; r < win_row_of.size(); ++r) {
+      const int i = win_row_of[r], f = frame_of[(size_t)i];
+      const long long total = ((volatile long long*)len_dev)[r];
+      PCC_REQUIRE(total >= 0 && total <= tab[(size_t)i].out_cap, PCC_E_NOMEM, "%s: frame %d: blob beyond its bound", who, f);
+      len_of[(size_t)f] = total;
+      off_of[(size_t)f] = (int64_t)tab_b + tab[(size_t)i].out_off;
+    }
+  }
+  int64_t total = 0;
+  for (int f = 0; f < n_frames; ++f) total += len_of[(size_t)f];
+  PCC_REQUIRE(total <= cap, PCC_E_NOMEM, "%s: %lld bytes of blobs, capacity %lld", who, (long long)total, (long long)cap);
+  h_offsets[0] = 0;
+  for (int f = 0; f < n_frames; ++f) {
+    uint8_t* dst = h_out + h_offsets[f];
+    if (off_of[(size_t)f] >= 0) {
+      memcpy(dst, (const uint8_t*)ctx->stage + off_of[(size_t)f], (size_t)len_of[(size_t)f]);
+    } else {   // no points: the 12-byte empty blob
+      memset(dst, 0, kAttrHead);
+      dst[0] = 'A';
+      dst[1] = (uint8_t)kind.version;
+      dst[2] = (uint8_t)((h_format[f] & 0xFF) | ((key_shift / 3) << 4));
+      dst[3] = (uint8_t)(h_format[f] >> 8);
+    }
+    h_offsets[f + 1] = h_offsets[f] + len_of[(size_t)f];
+    if (h_rung) h_rung[f] = rung_of[(size_t)f];
+  }
+  return PCC_OK;
 }
 
 // host only: the version byte and byte 3 of a head, checked: its kind, channels and mask

@@ -68,6 +68,15 @@ than version 19 at equal error.  Row j at a level is the mean of cell j under th
     cells, coarse = codec.decompress([b[:GeometryCodec.lod_info(b, 2)[0]] for b in blobs],
                                      [a[:GeometryCodec.attr_lod_info(a, 2)[0]] for a in attr_blobs], lod=2)
 
+A byte budget for versions 19 and 21: qstep is the finest setting the sender accepts, and every frame is coded at the
+first coarser one of a quarter-octave ladder that a fixed search (include/pcc.h) finds under its target, in one call.
+The blob is the one the plain call writes at those steps; no format and no decoder is new.
+
+    blobs, attr_blobs = codec.compress(frames, attributes=rgb, qstep=(4, 8, 8), colour="ycocg", target_bytes=6000)
+    GeometryCodec.attr_info(attr_blobs[0])["qstep"]                            # what the frame got, e.g. (23, 46, 46)
+    GeometryCodec.rate_ladder((4, 8, 8), np.uint8)                             # host only: the 21 settings to choose from
+    blobs, attr_blobs = codec.compress(frames, attributes=rgb, qstep=8, target_frame_bytes=16000)   # geometry + attributes
+
 Metric frames (include/pcc.h has the rule): float32 points in the caller's unit, from the host or from this codec's
 device, are put on the lattice by the codec, q = rint((x - origin) / voxel) per coordinate in float32; rows without a
 return (NaN / Inf) can be dropped, and the row index says which decoded row every input row became.
@@ -145,6 +154,7 @@ class GeometryCodec:
     def __init__(self, device=0):
         self.rt = Runtime(device)
         self._lock = threading.Lock()
+        self.rate_scratch_limit = 0      # bytes of scratch a budgeted compress may take for its candidate rows; 0: the library's default
 
     def close(self):
         self.rt.close()
@@ -351,6 +361,47 @@ class GeometryCodec:
         return steps, K
 
     @staticmethod
+    def rate_ladder(qstep, dtype, channels=None):
+        """the steps that compress(..., qstep=qstep, target_bytes=B) may choose from, finest first: a list of J tuples
+        of one step per channel (include/pcc.h has the rule: quarter octaves from qstep up to the coarsest step of
+        `dtype`, uint8 or uint16).  qstep an integer (channels then says how many it serves, default 1) or one step per
+        channel.  Host only."""
+        bpv = np.dtype(dtype).itemsize
+        if np.dtype(dtype) not in (np.dtype(np.uint8), np.dtype(np.uint16)):
+            raise TypeError(f"attributes are uint8 or uint16, got {np.dtype(dtype)}")
+        if isinstance(qstep, (tuple, list)):
+            if channels is not None and int(channels) != len(qstep):
+                raise ValueError(f"qstep has {len(qstep)} steps for {channels} channels")
+            channels = len(qstep)
+        return Runtime.attr_rate_ladder(qstep, bpv, 1 if channels is None else int(channels))
+
+    @staticmethod
+    def _check_rate(target_bytes, target_frame_bytes, nb, qstep, scalable_to):
+        """target_bytes / target_frame_bytes of compress -> (one target per frame, whether it bounds geometry and
+        attributes together), or (None, False) for the calls of before"""
+        if target_bytes is None and target_frame_bytes is None:
+            return None, False
+        if target_bytes is not None and target_frame_bytes is not None:
+            raise ValueError("target_bytes bounds a frame's attribute blob, target_frame_bytes its two blobs together: choose one of the two")
+        name, t = ("target_bytes", target_bytes) if target_bytes is not None else ("target_frame_bytes", target_frame_bytes)
+        seq = list(t) if isinstance(t, (tuple, list, np.ndarray)) else None
+        for v in ([t] if seq is None else seq):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an integer >= 1 or a sequence of one per frame, got {t!r}")
+        if seq is not None and len(seq) != nb:
+            raise ValueError(f"{name} has {len(seq)} entries for {nb} frames")
+        targets = [int(v) for v in (seq if seq is not None else [t] * nb)]
+        for f, v in enumerate(targets):
+            if v < 1:
+                raise ValueError(f"frame {f}: {name} must be at least 1, got {v}")
+        if not qstep:
+            raise ValueError(f"{name} chooses the steps of transform-coded attributes from qstep upwards: it needs qstep= (and attributes=)")
+        if scalable_to is not None:
+            raise ValueError(f"{name} with scalable_to: the lift of attribute blob version 22 has other weights, a byte target "
+                             "covers versions 19 and 21 only")
+        return targets, target_frame_bytes is not None
+
+    @staticmethod
     def _check_cross(cross_channel, attrs):
         """cross_channel of compress -> one mask per frame (bit ch - 1: channel ch against ch - 1), or None for False"""
         if cross_channel is False:
@@ -379,7 +430,7 @@ class GeometryCodec:
 
     def compress(self, frames, attributes=None, lod=0, scalable=False, *, voxel=None, origin=(0.0, 0.0, 0.0),
                  invalid="raise", return_index=False, max_error=0, cross_channel=False, qstep=0, colour=None,
-                 scalable_to=None):
+                 scalable_to=None, target_bytes=None, target_frame_bytes=None):
         """frames: a sequence of int16 / int32 [n_f, 3] arrays -> a list of bytes, one version-2 blob per frame.
         Duplicate points are removed (as np.unique), out-of-range coordinates raise PccError (PCC_E_RANGE).
         lod = k > 0: the sender's side of a level of detail — blob f is the version-2 blob of the distinct cells
@@ -430,6 +481,18 @@ class GeometryCodec:
         decompress(..., lod=j)) at a few per cent more bytes than version 19 at equal error.  An integer qstep serves
         every channel; colour=, lod=k, float32 / device frames, invalid="drop" and return_index combine with it as with
         version 21.  None, the default, writes the bytes of before.
+        target_bytes = B (with qstep; an integer >= 1 or a sequence of one per frame; bool or non-integer: TypeError;
+        below 1, another length than the frames, without qstep, or with scalable_to: ValueError): a byte budget for the
+        attribute blobs.  qstep is then the finest setting the sender accepts; every frame is coded at the first setting
+        of the ladder rate_ladder(qstep, dtype) that the search of include/pcc.h finds with len(attr_blobs[f]) <= B
+        (quarter-octave steps, all channels coarsened together), in one call: merge, colour transform and lift run once,
+        the candidates are coded side by side.  The blob is byte for byte the one compress writes at those steps
+        (version 19 or 21; attr_info(blob)["qstep"] says which it got); a frame that the coarsest setting does not bring
+        under B gets that setting and is longer than B.  target_frame_bytes = B bounds len(blobs[f]) +
+        len(attr_blobs[f]) the same way: the attributes get what the frame's geometry blob leaves.  The two exclude each
+        other.  Both combine with colour, lod=k, float32 / device frames, invalid="drop" and return_index as qstep
+        does.  rate_scratch_limit (an attribute of the codec, bytes; 0: the library's default of 1 GiB) bounds the scratch
+        of the candidates; the bytes do not depend on it.  None, the default, writes the bytes of before.
 
         Frame types: numpy int16 / int32 as above, numpy float32, or torch tensors of those three dtypes on the host or
         on this codec's device; all frames of a call integer or all float32, all on the host or all on the device
@@ -463,8 +526,10 @@ class GeometryCodec:
         cross = self._check_cross(cross_channel, attrs)
         qstep, steps, colour = self._check_colour(qstep, colour, attrs, max_error, scalable, cross)
         steps, scalable_to = self._check_scalable_to(scalable_to, lod, qstep, steps, attrs, max_error, scalable, cross)
+        targets, whole = self._check_rate(target_bytes, target_frame_bytes, len(frames), qstep, scalable_to)
         if steps is not None:      # versions 21 and 22: the steps travel where the one step did
             qstep = (steps, colour, scalable_to)
+        rate = None if targets is None else (targets, whole, int(self.rate_scratch_limit))
         nb = len(frames)
 
         def result(blobs, attr_blobs=None, index=None):
@@ -483,7 +548,7 @@ class GeometryCodec:
             blobs = rt.octree_encode_frames(front.keys, nb, 3 * lod)
             attr_blobs = index = None
             if attrs is not None:
-                attr_blobs = self._encode_attributes(rt, attrs, blobs, front, version, 3 * lod, max_error, cross, qstep)
+                attr_blobs = self._encode_attributes(rt, attrs, blobs, front, version, 3 * lod, max_error, cross, qstep, rate)
             if return_index:
                 first_run = torch.empty(nb, dtype=torch.int64, pin_memory=True)
                 np.cumsum([0] + [struct.unpack_from("<I", b, 4)[0] for b in blobs[:-1]], out=first_run.numpy())
@@ -588,7 +653,7 @@ class GeometryCodec:
         return _split(index, sizes)
 
     @staticmethod
-    def _encode_attributes(rt, attrs, blobs, front, version, key_shift, max_error, cross=None, qstep=0):
+    def _encode_attributes(rt, attrs, blobs, front, version, key_shift, max_error, cross=None, qstep=0, rate=None):
         # the values as they come, frame by frame at 16-byte offsets, in one upload; the merge into Morton order
         # happens on the device from the sort's permutation and the runs of equal keys
         offs, at = [], 0
@@ -605,6 +670,12 @@ class GeometryCodec:
         n_kept = front.n_keep if front.n_keep < front.n else None      # None: no row was dropped
         # versions 21 and 22: (steps, colour[, K])
         steps, colour, to = (tuple(qstep) + (None,))[:3] if isinstance(qstep, tuple) else (qstep, None, None)
+        if rate is not None:      # a byte target: the steps from `steps` upwards that the search chooses, frame by frame
+            targets, whole, limit = rate
+            if whole:      # what the geometry blob leaves; nothing left: a target no blob meets, the coarsest steps
+                targets = [max(1, t - len(b)) for t, b in zip(targets, blobs)]
+            return rt.attr_encode_frames_rate(values, offs, formats, _ends(front.sizes), points, front.perm, front.rows, front.n_unique,
+                                              front.keys, key_shift, n_kept, steps, colour, targets, limit)[0]
         return rt.attr_encode_frames(values, offs, formats, _ends(front.sizes), points, front.perm, front.rows, front.n_unique,
                                      version, front.keys, key_shift, n_kept, max_error, cross, steps, colour, to)
 

@@ -728,7 +728,9 @@ class Runtime:
         version 21, one step per channel (a frame reads its first c_f; an integer serves every channel) and, with
         colour=1, the luma / chroma transform in front of the lift (include/pcc.h has the rule); the library checks both.
         scalable_to = K beside a qstep (pcc_attr_encode_frames_transform3): blob version 22, version 21 under weights a
-        decoder at a cut can form, its levels of detail 0 .. K prefixes of the blob; the library checks K."""
+        decoder at a cut can form, its levels of detail 0 .. K prefixes of the blob; the library checks K.
+        A byte target per frame for versions 19 and 21 is a call of its own, attr_encode_frames_rate: it takes these
+        arguments and writes the blob this call writes at the steps it chooses."""
         if version not in (1, 2):
             raise ValueError(f"attribute blob version {version!r}: 1 or 2")
         steps = None
@@ -784,6 +786,51 @@ class Runtime:
             check(self.lib.pcc_attr_encode_frames_v2(*head, _ptr(keys), int(key_shift), _np_ptr(out), cap, offs),
                   "pcc_attr_encode_frames_v2")
         return [out[offs[f]:offs[f + 1]].tobytes() for f in range(nf)]
+
+    def attr_encode_frames_rate(self, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique, keys,
+                                key_shift, n_kept, qstep, colour, targets, scratch_limit=0, cap=None):
+        """attr_encode_frames(..., qstep=, colour=) under a byte target per frame (pcc_attr_encode_frames_rate;
+        include/pcc.h has the ladder and the search): blob f is the version 19 (an integer qstep without colour) or 21
+        blob of the coarsened steps that the search chooses for targets[f] >= 1, qstep itself being the finest.  ->
+        (blobs, rungs): rungs[f] the rung of the ladder frame f got (rate_ladder), -1 for a frame without points.  A
+        frame that no rung brings under its target gets the last rung and is longer than its target.  scratch_limit
+        (bytes; 0: the library's default, 1 GiB) bounds the scratch of the candidate rows; bytes and rungs do not depend
+        on it.  cap: the room for the blobs (None: what attr_encode_frames takes)."""
+        per_channel = bool(colour) or not isinstance(qstep, (int, np.integer))
+        steps = [int(qstep)] * 4 if isinstance(qstep, (int, np.integer)) else [int(q) for q in qstep]
+        if not 1 <= len(steps) <= 4:
+            raise ValueError(f"attribute blob version 21: {len(steps)} steps, at most 4")
+        steps += [0] * (4 - len(steps))
+        nf = len(formats)
+        if len(targets) != nf:
+            raise ValueError(f"{len(targets)} targets for {nf} frames")
+        if cap is None:
+            cap = 0
+            for fmt, n in zip(formats, points):
+                bpv, c = fmt & 0xFF, fmt >> 8
+                cap += 96 + 2 * 80 * bpv * c + 388 * (n // 64 + 1) + 32 * bpv * c * n
+        out = np.empty(max(int(cap), 1), dtype=np.uint8)
+        offs = (C.c_int64 * (nf + 1))()
+        rungs = (C.c_int32 * nf)()
+        check(self.lib.pcc_attr_encode_frames_rate(
+            self.ctx, _ptr(values), (C.c_int64 * nf)(*value_offsets), (C.c_int32 * nf)(*formats), (C.c_int64 * (nf + 1))(*row_offsets),
+            (C.c_int64 * nf)(*points), nf, _ptr(perm), _ptr(run_starts), n_unique, -1 if n_kept is None else int(n_kept), _ptr(keys),
+            int(key_shift), (C.c_int32 * 4)(*steps), int(per_channel), int(colour or 0), (C.c_int64 * nf)(*[int(t) for t in targets]),
+            int(scratch_limit), _np_ptr(out), int(cap), offs, rungs), "pcc_attr_encode_frames_rate")
+        return [out[offs[f]:offs[f + 1]].tobytes() for f in range(nf)], list(rungs)
+
+    @staticmethod
+    def attr_rate_ladder(qstep, bpv, channels):
+        """the ladder of steps that a byte target walks from the base steps `qstep` (an integer, or one step per channel)
+        for values of bpv bytes and `channels` channels (pcc_attr_rate_ladder, host only): a list of J tuples"""
+        steps = [int(qstep)] * 4 if isinstance(qstep, (int, np.integer)) else [int(q) for q in qstep]
+        if not 1 <= len(steps) <= 4:
+            raise ValueError(f"{len(steps)} steps, at most 4")
+        steps += [0] * (4 - len(steps))
+        out = (C.c_int32 * 256)()
+        J = C.c_int32(0)
+        check(_abi.lib().pcc_attr_rate_ladder((C.c_int32 * 4)(*steps), int(channels), int(bpv), out, C.byref(J)), "pcc_attr_rate_ladder")
+        return [tuple(out[4 * j + ch] for ch in range(int(channels))) for j in range(J.value)]
 
     @staticmethod
     def attr_lod_info(blob, lod):

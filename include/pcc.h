@@ -1205,6 +1205,75 @@ int pcc_attr_encode_frames_transform3(pcc_ctx* ctx, const void* d_values,
                                       int64_t cap, int64_t* h_offsets);
 int pcc_attr_scalable_to(const uint8_t* h_in, int64_t len, int32_t* h_scalable_to);
 
+/* Versions 19 and 21 under a byte target per frame.  No blob format changes:
+ * a frame coded under a target is, byte for byte, the version 19 or 21 blob
+ * that _encode_frames_transform / _transform2 write at the steps the search
+ * below chooses.  tests/attr_rate_ref.py restates the rule in numpy.
+ *
+ * Ladder.  For a frame of c channels and bpv bytes per value, H = 2^(8 bpv - 1),
+ * base steps q[ch] in 1 .. H - 1 (the caller's qstep, the finest it accepts)
+ * and the quarter-octave multipliers m = (16, 19, 23, 27), rung j = 0, 1, ..
+ * has the steps
+ *     q_j[ch] = min(H - 1, ((q[ch] * m[j % 4]) << (j / 4)) >> 4).
+ * The ladder ends with the first rung whose steps are all H - 1, that rung
+ * included; J is the number of rungs (at most 61: uint16, q = 1).  Rung 0 is
+ * q itself; rungs may repeat (they give the same blob).  uint8, q = (32):
+ * 32 38 46 54 64 76 92 108 127, J = 9.
+ *
+ * Length.  len_f(j) = the length of the blob that the existing call writes for
+ * frame f at the steps of rung j, everything else (colour, key_shift, dropped
+ * rows) as in this call.
+ *
+ * Search.  Lengths are not monotone in the step, so the procedure is the rule.
+ * Per frame f with target B_f >= 1:
+ *   1. A = { j : j % 4 == 0 } and J - 1, ascending.
+ *   2. a = the first rung of A with len_f(a) <= B_f.
+ *   3. No rung of A fits: the frame gets rung J - 1 and is over its target;
+ *      the call does not fail.
+ *   4. a = 0: the frame gets rung 0.
+ *   5. Otherwise, with a' the rung of A in front of a: the first j in
+ *      a' < j < a with len_f(j) <= B_f, or a where there is none.
+ * A frame without points gets the 12-byte empty blob, whatever its target.
+ *
+ *   pcc_attr_rate_ladder : host only.  h_steps [64][4] receives the ladder
+ *     (0 behind channel c), *h_rungs = J.  c outside 1 .. 4, bpv outside
+ *     {1, 2}, a step < 1 or >= H: PCC_E_ARG.
+ *   pcc_attr_encode_frames_rate : the arguments of _transform2 up to
+ *     key_shift, then h_qstep[4], per_channel (0: version 19 from h_qstep[0],
+ *     colour must be 0; 1: version 21 from h_qstep[0 .. c - 1] and colour),
+ *     h_target[n_frames] and scratch_limit.  h_rung (nullable) receives the
+ *     rung of every frame, -1 for a frame without points.  Checks and
+ *     messages are _transform2's; a target < 1: PCC_E_ARG naming the frame;
+ *     more bytes than cap: PCC_E_NOMEM, nothing written; the ctx stays usable
+ *     after an error.  Version 22 has other weights and is not offered.
+ *     The forward lift does not depend on the step, so merge, colour
+ *     transform, coding order and lift run once; a quantiser pass then forms
+ *     the indices of candidate rows (a frame at a rung), which the coder's
+ *     counting pass and lane coder take as frames of their own, all rows of a
+ *     stage in one launch each.  Stage 1 codes the rungs of A of every frame,
+ *     stage 2 the at most three rungs of step 5; a row's length is its head
+ *     plus twice the sum of its chunks' words, so only the winners' blobs are
+ *     assembled.  Synchronisations: the coding order's, one per stage (stage
+ *     2 only where a frame reaches step 5), the blobs' lengths.
+ *     scratch_limit (bytes; 0: 1 GiB): a candidate row takes its indices and
+ *     two record arrays of n_chunks * 64 * T words (about 190 MB for a
+ *     1M-point RGB frame).  The rows of a stage are coded in groups that fit
+ *     the limit, one row always allowed; a winner whose group had to give its
+ *     scratch to a later one is coded once more before assembly.  Bytes and
+ *     rungs do not depend on the limit. */
+int pcc_attr_rate_ladder(const int32_t h_qstep[4], int c, int bpv, int32_t* h_steps,
+                         int32_t* h_rungs);
+int pcc_attr_encode_frames_rate(pcc_ctx* ctx, const void* d_values,
+                                const int64_t* h_value_offsets, const int32_t* h_format,
+                                const int64_t* h_rows, const int64_t* h_points,
+                                int n_frames, const uint32_t* d_perm,
+                                const uint32_t* d_run_starts, int64_t n_unique,
+                                int64_t n_kept, const uint64_t* d_keys, int key_shift,
+                                const int32_t h_qstep[4], int per_channel, int colour,
+                                const int64_t* h_target, int64_t scratch_limit,
+                                uint8_t* h_out, int64_t cap, int64_t* h_offsets,
+                                int32_t* h_rung);
+
 /* ---- exact nearest neighbours on the lattice: the D1 metric (csrc/nn.hip, the walk in csrc/nn_cells.h) -- */
 
 /* The rule (tests/nn_ref.py restates it in numpy).  For a frame f there are
