@@ -64,7 +64,7 @@
 // sums of the sublevel counts that the order stage's one synchronisation already brings back.  Decoder
 // (pcc_attr_decode_frames_lod at lod 0 .. K, against the cells of that lod): the order stage on the cell keys, the lane
 // decoder on the level's prefix as version 2's, the cells' counts against the head's, k_as_flag and the scan, k_at_root,
-// k_as_lift<false> per occupied sublevel, k_as_store.  tests/attr_scalable_ref.py restates the kind in numpy.
+// k_as_lift<false> per occupied sublevel, k_ac_store.  tests/attr_scalable_ref.py restates the kind in numpy.
 //
 // Versions 19 and 21 under a byte target per frame (pcc_attr_encode_frames_rate; include/pcc.h has the ladder and the
 // search): no format of its own.  Merge, colour transform and order stage as above, k_ar_lift (k_at_lift<true> without
@@ -76,7 +76,9 @@
 // Host side: the kinds share one encode sequence (a_encode_frames over an AEncKind, the entry point's kind resolved
 // once) and one decode-call skeleton (ADecCall: accounting, rows, layout, upload, status) under the three decoders, each
 // of which keeps its parser, its side tables, its arena arrays and its kernels; DESIGN.md, "attr.hip: one encode path,
-// shared decode helpers" and "attr.hip: the host code of kinds 8 to 21, folded".
+// shared decode helpers", "attr.hip: the host code of kinds 8 to 21, folded" and "attr.hip: version 22 and the byte
+// budget, folded".  The two encode entry points (a_encode_frames, pcc_attr_encode_frames_rate) share their front
+// (a_enc_front over an AEncPlan) and their tail (a_enc_emit).
 #include "common.h"
 #include "lanerans.h"
 #include "attr_blob.h"
@@ -1121,10 +1123,56 @@ __device__ __forceinline__ int64_t at_step(int64_t q, int64_t wa, int64_t wb) {
   return at_root2((uint64_t)(q * q) * (uint64_t)(wa + wb) / ((uint64_t)wa * (uint64_t)wb));
 }
 
+// The pair that thread j = blockIdx.x blockDim.x + threadIdx.x takes at sublevel t of frame f (h = tab[f]): place r =
+// bins[..][t] + j of the frame's coding order, point i = inv[place], and lo, the first key of the frame not below
+// key_i with its bits bit and lower cleared (bit = t + shift <= 47; shift: the low bits of an encoder's keys that are
+// not the cells').  false: no pair (j beyond the sublevel's count, or a place or point outside the frame: cannot
+// happen).  t_hi: the first key beyond the subtree of key_i above bit, what at_upper searches for
+struct ATPair {
+  int64_t r, i, lo;
+  uint64_t t_hi;
+};
+__device__ __forceinline__ bool at_pair(const uint64_t* __restrict__ keys, const A2Order& h, const uint32_t* __restrict__ bins,
+                                        const uint32_t* __restrict__ inv, int f, int t, int shift, ATPair& p) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= (int64_t)bins[f * 2 * kATBins + kATBins + t]) return false;
+  p.r = (int64_t)bins[f * 2 * kATBins + t] + j;
+  if (p.r >= h.n) return false;
+  p.i = inv[h.pt0 + p.r];
+  if (p.i <= 0 || p.i >= h.n) return false;
+  const int bit = t + shift;
+  const uint64_t key = keys[p.i], low = (1ull << bit) - 1ull;
+  const uint64_t t_lo = key & ~((low << 1) | 1ull);
+  p.t_hi = (key | low) + 1ull;
+  int64_t lo = 0, hi = p.i;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < t_lo) lo = mid + 1; else hi = mid;
+  }
+  p.lo = lo;
+  return true;
+}
+// the end of the pair's right half: the first key of the frame behind key_i that is not below t_hi (n: none)
+__device__ __forceinline__ int64_t at_upper(const uint64_t* __restrict__ keys, int64_t i, int64_t n, uint64_t t_hi) {
+  int64_t a = i + 1, b = n;
+  while (a < b) {
+    const int64_t mid = (a + b) >> 1;
+    if (keys[mid] < t_hi) a = mid + 1; else b = mid;
+  }
+  return a;
+}
+
+// the index of a difference hh under step s, wrapped to the value width: sgn(hh) min((|hh| + s / 2) / s, H - 1)
+__device__ __forceinline__ uint32_t at_quant(int64_t hh, int64_t s, int64_t H, uint32_t mask) {
+  const int64_t m = std::min<int64_t>(((hh < 0 ? -hh : hh) + s / 2) / s, H - 1);
+  return (uint32_t)(hh < 0 ? -m : m) & mask;
+}
+
 // The pairs of sublevel t, frame = blockIdx.y: thread j takes place bins[..][t] + j of the frame's coding order, point
-// i = inv[place]; lo and hi by two binary searches in the frame's keys (sh: the low bits of an encoder's keys that are
-// not the cells').  ENC: val = the frame's merged values, lifted in place (a node's value lies between its children's,
-// so it stays a uint16), the index to the point's place of idx, wrapped to the value width.  Otherwise (decoder): x_all
+// i = inv[place]; lo and hi by two binary searches in the frame's keys (at_pair, at_upper; an encoder's keys carry
+// key_shift low bits that are not the cells').  ENC: val = the frame's merged values, lifted in place (a node's value
+// lies between its children's, so it stays a uint16), the index (at_quant) to the point's place of idx, wrapped to the
+// value width.  Otherwise (decoder): x_all
 // the decoded indices in coding order (bpv bytes each, at out_off), val_all int64 [n][c] at element out_off; status |= 8
 // where the keys give a pair without a left or a right leaf (keys that are not sorted and distinct).  PC (version 21):
 // one step per channel, q[ch] = aux_all[5 f + ch], in place of the frame's one q (Aux = const int32_t*, one argument
@@ -1139,26 +1187,10 @@ __global__ __launch_bounds__(256) void k_at_lift(const uint64_t* __restrict__ ke
   [[maybe_unused]] const int32_t* aux_all = a_aux(aux...);
   const int f = blockIdx.y;
   const A2Order& h = tab[f];
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= (int64_t)bins[f * 2 * kATBins + kATBins + t]) return;
-  const int64_t r = (int64_t)bins[f * 2 * kATBins + t] + j;
-  if (r >= h.n) return;
-  const int64_t i = inv[h.pt0 + r];
-  if (i <= 0 || i >= h.n) return;
   const uint64_t* keys = keys_all + h.pt0;
-  const int bit = t + (ENC ? h.shift : 0);   // <= 47
-  const uint64_t key = keys[i], low = (1ull << bit) - 1ull;
-  const uint64_t t_lo = key & ~((low << 1) | 1ull), t_hi = (key | low) + 1ull;
-  int64_t lo = 0, hi = i;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < t_lo) lo = mid + 1; else hi = mid;
-  }
-  int64_t a = i + 1, b = h.n;
-  while (a < b) {
-    const int64_t mid = (a + b) >> 1;
-    if (keys[mid] < t_hi) a = mid + 1; else b = mid;
-  }
+  ATPair p;
+  if (!at_pair(keys, h, bins, inv, f, t, ENC ? h.shift : 0, p)) return;
+  const int64_t r = p.r, i = p.i, lo = p.lo, a = at_upper(keys, i, h.n, p.t_hi);
   const int64_t wa = i - lo, wb = a - i, w = wa + wb;
   if constexpr (ENC) {
     const AFrame& fr = etab[f];
@@ -1172,8 +1204,7 @@ __global__ __launch_bounds__(256) void k_at_lift(const uint64_t* __restrict__ ke
       if constexpr (PC) s = at_step(aux_all[5 * f + ch], wa, wb);
       const int64_t va = v[lo * c + ch], hh = (int64_t)v[i * c + ch] - va;
       v[lo * c + ch] = (uint16_t)(va + at_floor_div(wb * hh, w));
-      const int64_t m = std::min<int64_t>(((hh < 0 ? -hh : hh) + s / 2) / s, H - 1);
-      idx[fr.val_off + r * c + ch] = (uint16_t)((uint32_t)(hh < 0 ? -m : m) & mask);
+      idx[fr.val_off + r * c + ch] = (uint16_t)at_quant(hh, s, H, mask);
     }
   } else {
     const ADFrame& fr = dtab[f];
@@ -1241,14 +1272,16 @@ __global__ __launch_bounds__(256) void k_ac_fwd(const AFrame* __restrict__ tab, 
   v[2] = (uint16_t)((cg >> 1) + H);
 }
 
-// decoder, in place of k_at_store for a call with a colour frame: k_at_store's clamp, the inverse colour transform of
-// a frame whose aux_all[5 f + 4] is 1, the second clamp and the narrowing store; frame = blockIdx.y, one thread per point
+// decoder, in place of k_at_store for a call with a colour frame (version 21) and for every call of version 22:
+// k_at_store's clamp, the inverse colour transform of a frame whose aux_all[5 f + 4] is 1, the second clamp and the
+// narrowing store; frame = blockIdx.y, one thread per value of the frame's n_dec points (versions 19 and 21: all of
+// them, n_dec = n; version 22: its cells at the level of detail, while h.n stays the whole blob's for the lane decoder)
 __global__ __launch_bounds__(256) void k_ac_store(const ADFrame* __restrict__ tab, const int32_t* __restrict__ aux_all,
                                                   const int64_t* __restrict__ val, uint8_t* __restrict__ out_all) {
   const int f = blockIdx.y;
   const ADFrame& h = tab[f];
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= h.n) return;
+  if (i >= h.n_dec) return;
   const int c = h.c, bpv = h.bpv;
   const int64_t mask = ((int64_t)1 << (8 * bpv)) - 1;
   int x[4] = {0, 0, 0, 0};
@@ -1310,31 +1343,16 @@ __global__ __launch_bounds__(256) void k_as_lift(const uint64_t* __restrict__ ke
                                                  const int32_t* __restrict__ aux_all) {
   const int f = blockIdx.y;
   const A2Order& h = tab[f];
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= (int64_t)bins[f * 2 * kATBins + kATBins + t]) return;
-  const int64_t r = (int64_t)bins[f * 2 * kATBins + t] + j;
-  if (r >= h.n) return;
-  const int64_t i = inv[h.pt0 + r];
-  if (i <= 0 || i >= h.n) return;
   const uint64_t* keys = keys_all + h.pt0;
   const uint32_t* g = g_all + h.pt0;
-  const int bit = t + (ENC ? h.shift : 0);   // <= 47
+  ATPair p;
+  if (!at_pair(keys, h, bins, inv, f, t, ENC ? h.shift : 0, p)) return;
+  const int64_t r = p.r, i = p.i, lo = p.lo;
   const int K3 = 3 * (ENC ? etab[f].e : dtab[f].max_error), ta = t + lod3, tk = K3 - lod3;   // 0 <= tk <= 45
   const bool inside = ta < K3;
-  const uint64_t key = keys[i], low = (1ull << bit) - 1ull;
-  const uint64_t t_lo = key & ~((low << 1) | 1ull), t_hi = (key | low) + 1ull;
-  int64_t lo = 0, hi = i;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < t_lo) lo = mid + 1; else hi = mid;
-  }
   int64_t ca = 1, cb = 1, M = 1;
   if (!inside) {
-    int64_t a = i + 1, b = h.n;
-    while (a < b) {
-      const int64_t mid = (a + b) >> 1;
-      if (keys[mid] < t_hi) a = mid + 1; else b = mid;
-    }
+    const int64_t a = at_upper(keys, i, h.n, p.t_hi);
     const int64_t gi = g[i], C = (int64_t)bins[f * 2 * kATBins + tk] + bins[f * 2 * kATBins + kATBins + tk];
     const int64_t n_all = ENC ? h.n : dtab[f].n;
     ca = gi - (int64_t)g[lo];
@@ -1359,8 +1377,7 @@ __global__ __launch_bounds__(256) void k_as_lift(const uint64_t* __restrict__ ke
       const int64_t s = step(ch);
       const int64_t va = v[lo * c + ch], hh = (int64_t)v[i * c + ch] - va;
       v[lo * c + ch] = (uint16_t)(va + (inside ? hh >> 1 : at_floor_div(cb * hh, w)));
-      const int64_t m = std::min<int64_t>(((hh < 0 ? -hh : hh) + s / 2) / s, H - 1);
-      idx[fr.val_off + r * c + ch] = (uint16_t)((uint32_t)(hh < 0 ? -m : m) & mask);
+      idx[fr.val_off + r * c + ch] = (uint16_t)at_quant(hh, s, H, mask);
     }
   } else {
     const ADFrame& fr = dtab[f];
@@ -1380,33 +1397,6 @@ __global__ __launch_bounds__(256) void k_as_lift(const uint64_t* __restrict__ ke
   }
 }
 
-// decoder, behind the last sublevel: k_ac_store over the frame's n_dec cells of a level of detail (h.n stays the whole
-// blob's values for the lane decoder).  A copy: a body shared by the two kernels compiles k_ac_store to other instructions
-__global__ __launch_bounds__(256) void k_as_store(const ADFrame* __restrict__ tab, const int32_t* __restrict__ aux_all,
-                                                  const int64_t* __restrict__ val, uint8_t* __restrict__ out_all) {
-  const int f = blockIdx.y;
-  const ADFrame& h = tab[f];
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= h.n_dec) return;
-  const int c = h.c, bpv = h.bpv;
-  const int64_t mask = ((int64_t)1 << (8 * bpv)) - 1;
-  int x[4] = {0, 0, 0, 0};
-  for (int ch = 0; ch < c; ++ch) {
-    const int64_t a = val[h.out_off + i * c + ch];
-    x[ch] = (int)(a < 0 ? 0 : (a > mask ? mask : a));
-  }
-  if (c >= 3 && aux_all[5 * f + 4] == 1) {
-    const int H = 1 << (8 * bpv - 1), m = (int)mask;
-    const int co = 2 * (x[1] - H), cg = 2 * (x[2] - H), t = x[0] - (cg >> 1);
-    const int G = cg + t, B = t - (co >> 1), R = B + co;
-    x[0] = R < 0 ? 0 : (R > m ? m : R);
-    x[1] = G < 0 ? 0 : (G > m ? m : G);
-    x[2] = B < 0 ? 0 : (B > m ? m : B);
-  }
-  uint8_t* o = out_all + h.out_off + i * c * bpv;
-  for (int ch = 0; ch < c; ++ch) a_store(o, bpv, (uint32_t)x[ch], ch);
-}
-
 // ---- versions 19 and 21 under a byte target (include/pcc.h states the ladder and the search) ------------------------
 // The forward lift does not depend on the step: k_ar_lift is the encoder branch of k_at_lift without its quantiser and
 // runs once per call; k_ar_quant then forms the indices of any number of candidate rows (a frame at a rung of its
@@ -1420,26 +1410,10 @@ __global__ __launch_bounds__(256) void k_ar_lift(const uint64_t* __restrict__ ke
                                                  int32_t* __restrict__ hh_all, uint2* __restrict__ wts) {
   const int f = blockIdx.y;
   const A2Order& h = tab[f];
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= (int64_t)bins[f * 2 * kATBins + kATBins + t]) return;
-  const int64_t r = (int64_t)bins[f * 2 * kATBins + t] + j;
-  if (r >= h.n) return;
-  const int64_t i = inv[h.pt0 + r];
-  if (i <= 0 || i >= h.n) return;
   const uint64_t* keys = keys_all + h.pt0;
-  const int bit = t + h.shift;   // <= 47
-  const uint64_t key = keys[i], low = (1ull << bit) - 1ull;
-  const uint64_t t_lo = key & ~((low << 1) | 1ull), t_hi = (key | low) + 1ull;
-  int64_t lo = 0, hi = i;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < t_lo) lo = mid + 1; else hi = mid;
-  }
-  int64_t a = i + 1, b = h.n;
-  while (a < b) {
-    const int64_t mid = (a + b) >> 1;
-    if (keys[mid] < t_hi) a = mid + 1; else b = mid;
-  }
+  ATPair p;
+  if (!at_pair(keys, h, bins, inv, f, t, h.shift, p)) return;
+  const int64_t r = p.r, i = p.i, lo = p.lo, a = at_upper(keys, i, h.n, p.t_hi);
   const int64_t wa = i - lo, wb = a - i, w = wa + wb;
   if (wa < 1) return;   // cannot happen: the keys are sorted and distinct
   const AFrame& fr = etab[f];
@@ -1487,14 +1461,12 @@ __global__ __launch_bounds__(256) void k_ar_quant(const ARRow* __restrict__ rows
   const int64_t H = (int64_t)1 << (8 * h.bpv - 1);
   const uint32_t mask = (1u << (8 * h.bpv)) - 1u;
   const int64_t hh = hh_all[h.src_off + k];
-  int64_t x = hh;
+  uint32_t x = (uint32_t)hh & mask;
   if (r > 0) {
     const uint2 wt = wts[h.pt0 + r];
-    const int64_t s = at_step(h.q[ch], wt.x, wt.y);
-    const int64_t m = std::min<int64_t>(((hh < 0 ? -hh : hh) + s / 2) / s, H - 1);
-    x = hh < 0 ? -m : m;
+    x = at_quant(hh, at_step(h.q[ch], wt.x, wt.y), H, mask);
   }
-  idx[h.dst_off + k] = (uint16_t)((uint32_t)x & mask);
+  idx[h.dst_off + k] = (uint16_t)x;
 }
 
 // the winners' chunk words, final states and lane lengths, from where the coder left them (chunk src of the call's
@@ -1574,13 +1546,38 @@ static int a_s_cells(pcc_ctx* ctx, hipStream_t st, const A2Order* d_ord, int nf,
   return PCC_OK;
 }
 
+// the encoder's order stage of versions 19 and up: its arrays over the call's points (u of them in `blocks` blocks of
+// nf frames) from the arena, and a_t_order over the distinct sorted keys
+struct ATOrder {
+  uint16_t* packed;
+  uint32_t *hist, *bins, *inv;
+  unsigned grid[kATBins];
+};
+static size_t a_t_order_bytes(int64_t u, int64_t blocks, int nf) {
+  return pcc_align((size_t)u * 2) + pcc_align((size_t)blocks * kATBins * 4) + pcc_align((size_t)nf * 2 * kATBins * 4) + pcc_align((size_t)u * 4);
+}
+static int a_t_order_enc(pcc_ctx* ctx, hipStream_t st, const uint64_t* d_keys, const A2Order* d_ord, int nf, int64_t blocks, int64_t u,
+                         uint32_t* h_bins, ATOrder* o) {
+  o->packed = (uint16_t*)pcc_arena_alloc(ctx, pcc_align((size_t)u * 2));
+  o->hist = (uint32_t*)pcc_arena_alloc(ctx, pcc_align((size_t)blocks * kATBins * 4));
+  o->bins = (uint32_t*)pcc_arena_alloc(ctx, pcc_align((size_t)nf * 2 * kATBins * 4));
+  o->inv = (uint32_t*)pcc_arena_alloc(ctx, pcc_align((size_t)u * 4));
+  if (!o->packed || !o->hist || !o->bins || !o->inv) return PCC_E_NOMEM;
+  return a_t_order(st, false, (const void*)d_keys, nullptr, d_ord, nf, blocks, o->packed, o->hist, o->bins, o->inv, h_bins, o->grid);
+}
+
 // one sublevel of the lift over all frames of a call: forward (ENC; etab, merged, idx) or inverse (dtab, x, val,
-// status).  d_aux (version 21): the frames' steps and colour words; the lift then takes a step per channel from it
+// status).  d_aux (version 21): the frames' steps and colour words; the lift then takes a step per channel from it.
+// g (version 22, with d_aux): the scan of the K-cell firsts, and k_as_lift at lod3 in place of k_at_lift
 template <bool ENC>
 static int a_launch_lift(hipStream_t st, unsigned blocks, int nf, const uint64_t* keys, const A2Order* d_ord, const uint32_t* bins,
                          const uint32_t* inv, int t, const AFrame* etab, uint16_t* merged, uint16_t* idx, const ADFrame* dtab,
-                         const uint8_t* x, int64_t* val, int32_t* status, const int32_t* d_aux) {
-  if (d_aux)
+                         const uint8_t* x, int64_t* val, int32_t* status, const int32_t* d_aux, const uint32_t* g = nullptr,
+                         int lod3 = 0) {
+  if (g)
+    hipLaunchKernelGGL(k_as_lift<ENC>, dim3(blocks, (unsigned)nf), dim3(256), 0, st, keys, d_ord, bins, inv, t, g, lod3, etab, merged, idx, dtab,
+                       x, val, status, d_aux);
+  else if (d_aux)
     hipLaunchKernelGGL((k_at_lift<ENC, const int32_t*>), dim3(blocks, (unsigned)nf), dim3(256), 0, st, keys, d_ord, bins, inv, t, etab, merged,
                        idx, dtab, x, val, status, d_aux);
   else
@@ -1592,36 +1589,25 @@ static int a_launch_lift(hipStream_t st, unsigned blocks, int nf, const uint64_t
 
 // version 19, encoder, behind k_a_merge: the order stage, one k_at_lift<true> per occupied sublevel bottom-up over the
 // merged values in place, and the mean; idx then holds x in coding order where the PRED = false coder reads it
-// version 22 (points >= 0: the call's points; cells_out receives where the frames' 16 counts lie): k_as_flag and the
-// scan behind the order stage, k_as_lift in place of k_at_lift, and k_as_counts for the head
+// version 22 (cells_out: receives where the frames' 16 counts lie): k_as_flag and the scan behind the order stage,
+// k_as_lift in place of k_at_lift, and k_as_counts for the head
 static int a_t_forward(pcc_ctx* ctx, hipStream_t st, const uint64_t* d_keys, const A2Order* d_ord, const AFrame* d_tab, int nf,
-                       int64_t blocks, size_t pk_b, size_t hist_b, size_t bins_b, size_t link_b, uint16_t* merged,
-                       uint16_t* idx, uint32_t* h_bins, const int32_t* d_aux, int64_t points = -1, uint32_t** cells_out = nullptr) {
-  uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, pk_b);
-  uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, hist_b);
-  uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, bins_b);
-  uint32_t* inv = (uint32_t*)pcc_arena_alloc(ctx, link_b);
-  if (!packed || !hist || !bins || !inv) return PCC_E_NOMEM;
-  unsigned grid[kATBins];
-  PCC_TRY(a_t_order(st, false, (const void*)d_keys, nullptr, d_ord, nf, blocks, packed, hist, bins, inv, h_bins, grid));
+                       int64_t blocks, int64_t points, uint16_t* merged, uint16_t* idx, uint32_t* h_bins, const int32_t* d_aux,
+                       uint32_t** cells_out = nullptr) {
+  ATOrder o;
+  PCC_TRY(a_t_order_enc(ctx, st, d_keys, d_ord, nf, blocks, points, h_bins, &o));
   const uint32_t* g = nullptr;
-  if (points >= 0) {
-    PCC_TRY(a_s_cells(ctx, st, d_ord, nf, blocks, packed, d_tab, nullptr, 0, points, &g));
+  if (cells_out) {
+    PCC_TRY(a_s_cells(ctx, st, d_ord, nf, blocks, o.packed, d_tab, nullptr, 0, points, &g));
     *cells_out = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nf * 64);
     if (!*cells_out) return PCC_E_NOMEM;
-    hipLaunchKernelGGL(k_as_counts, dim3(nblk(16 * (int64_t)nf, 256)), dim3(256), 0, st, (const uint32_t*)bins, nf, *cells_out);
+    hipLaunchKernelGGL(k_as_counts, dim3(nblk(16 * (int64_t)nf, 256)), dim3(256), 0, st, (const uint32_t*)o.bins, nf, *cells_out);
     PCC_CHECK_LAUNCH();
   }
   for (int t = 0; t < kATBins - 1; ++t) {
-    if (!grid[t]) continue;
-    if (g) {
-      hipLaunchKernelGGL(k_as_lift<true>, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, d_keys, d_ord, (const uint32_t*)bins,
-                         (const uint32_t*)inv, t, g, 0, d_tab, merged, idx, (const ADFrame*)nullptr, (const uint8_t*)nullptr,
-                         (int64_t*)nullptr, (int32_t*)nullptr, d_aux);
-      PCC_CHECK_LAUNCH();
-    } else {
-      PCC_TRY(a_launch_lift<true>(st, grid[t], nf, d_keys, d_ord, bins, inv, t, d_tab, merged, idx, nullptr, nullptr, nullptr, nullptr, d_aux));
-    }
+    if (!o.grid[t]) continue;
+    PCC_TRY(a_launch_lift<true>(st, o.grid[t], nf, d_keys, d_ord, o.bins, o.inv, t, d_tab, merged, idx, nullptr, nullptr, nullptr, nullptr, d_aux,
+                                g));
   }
   hipLaunchKernelGGL(k_at_mean, dim3(nblk(4 * (int64_t)nf, 256)), dim3(256), 0, st, d_tab, nf, (const uint16_t*)merged, idx);
   PCC_CHECK_LAUNCH();
@@ -1668,10 +1654,10 @@ static int64_t a_head_bytes(const AEncKind& k, int c, int nctx, int64_t nc) {
   return head + 2 * nctx + 4 * nc;
 }
 
-// the template arguments of a kind's coder: k_a_stats / k_a_enc<PRED>, k_a_pack<V2, NL, XC[, TR[, const int32_t*]]>
-template <bool V2_, bool NL_, bool XC_, bool TR_ = false, bool TC_ = false>
+// the template arguments of a kind's coder: k_a_stats / k_a_enc<PRED>, k_a_pack<V2, NL, XC, TR> (a_launch_pack)
+template <bool V2_, bool NL_, bool XC_, bool TR_ = false>
 struct ACoder {
-  static constexpr bool V2 = V2_, NL = NL_, XC = XC_, TR = TR_, TC = TC_;
+  static constexpr bool V2 = V2_, NL = NL_, XC = XC_, TR = TR_;
   static constexpr bool PRED = !V2 && !NL && !XC;   // only version 1 predicts inside the run, and not beside cross-channel frames
 };
 
@@ -1741,6 +1727,144 @@ static int a_check_frame(const char* who, const AEncKind& k, int f, const int64_
   return PCC_OK;
 }
 
+// What the encode entry points share of a call: its arguments checked and its frames laid out.  The frames with points
+// (nf of them; frame_of: which of the call's) get a row of the coder's table with their places among the call's points,
+// merged values, merge blocks and output staging; the places among the coder's own arrays (rec_off, ctx_off, cb, sb) are
+// the caller's, which codes the frames once (a_encode_frames) or as candidate rows (pcc_attr_encode_frames_rate)
+struct AEncPlan {
+  int64_t n_keys = 0;           // the sorted keys that belong to kept rows (a_check_call)
+  std::vector<AFrame> tab;
+  std::vector<A2Order> order;   // their order rows (read by the keyed kinds)
+  std::vector<int> frame_of;
+  std::vector<int32_t> cross;   // their masks
+  std::vector<int32_t> aux;     // the transform kinds: their q[4] and the colour word (version 19: q in every channel)
+  bool xc = false;              // one of the masks is not 0
+  int64_t n_max = 0;            // the most points of a frame
+  int64_t u = 0, vals = 0, out_bytes = 0, merge_blocks = 0, nctx_max = 0;
+  int nf() const { return (int)tab.size(); }
+};
+
+// a_check_call, then frame by frame a_check_frame, the frame's row where it has points (row: nullptr where it has none)
+// and per_frame(f, row): the caller's own checks of frame f and its places in row; last the points against the runs
+template <typename PerFrame>
+static int a_enc_front(const char* who, const AEncKind& k, pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
+                       const int32_t* h_format, const int64_t* h_rows, const int64_t* h_points, int n_frames, const uint32_t* d_perm,
+                       const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys, int key_shift, uint8_t* h_out, int64_t cap,
+                       int64_t* h_offsets, AEncPlan* pl, PerFrame&& per_frame) {
+  PCC_TRY(a_check_call(who, k, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys,
+                       key_shift, h_out, cap, h_offsets, &pl->n_keys));
+  for (int f = 0; f < n_frames; ++f) {
+    AFrame r;
+    PCC_TRY(a_check_frame(who, k, f, h_value_offsets, h_format, h_rows, h_points, &r));
+    AFrame* row = nullptr;
+    if (r.n > 0) {
+      const int32_t m = k.h_cross ? k.h_cross[f] : 0;
+      pl->cross.push_back(m);
+      pl->xc |= m != 0;
+      if (k.tr) {
+        for (int ch = 0; ch < 4; ++ch) pl->aux.push_back(ch < r.c ? (k.h_qsteps ? k.h_qsteps[ch] : k.e) : 0);
+        pl->aux.push_back(k.colour);
+      }
+      r.u0 = pl->u;
+      r.val_off = pl->vals;
+      r.out_off = pl->out_bytes;
+      r.mb = (int32_t)pl->merge_blocks;
+      pl->tab.push_back(r);
+      pl->order.push_back(A2Order{r.u0, r.n, r.mb, key_shift});
+      pl->frame_of.push_back(f);
+      pl->n_max = std::max(pl->n_max, r.n);
+      pl->u += r.n;
+      pl->vals += r.n * r.c;
+      pl->out_bytes += a_round(r.out_cap, 16);
+      pl->merge_blocks += nblk(r.n, 256);
+      pl->nctx_max = std::max<int64_t>(pl->nctx_max, r.nctx);
+      row = &pl->tab.back();
+    }
+    PCC_TRY(per_frame(f, row));
+  }
+  PCC_REQUIRE(pl->u == n_unique, PCC_E_ARG, "%s: the frames have %lld points, the runs %lld", who, (long long)pl->u, (long long)n_unique);
+  return PCC_OK;
+}
+
+// the blobs of a call on their way out: frame f's length (the empty blob's where it has no points) and where it lies in
+// the staging (-1: nowhere)
+struct AEncOut {
+  std::vector<int64_t> len_of, off_of;
+  explicit AEncOut(int n_frames) : len_of((size_t)n_frames, kAttrHead), off_of((size_t)n_frames, -1) {}
+  // row i of the plan: the length k_a_pack reported for it, its blob at out_off behind the tab_b bytes of tables
+  int take(const char* who, const AEncPlan& pl, int i, long long total, size_t tab_b) {
+    const AFrame& r = pl.tab[(size_t)i];
+    const int f = pl.frame_of[(size_t)i];
+    PCC_REQUIRE(total >= 0 && total <= r.out_cap, PCC_E_NOMEM, "%s: frame %d: blob beyond its bound", who, f);
+    len_of[(size_t)f] = total;
+    off_of[(size_t)f] = (int64_t)tab_b + r.out_off;
+    return PCC_OK;
+  }
+};
+
+// the end of an encode call: the blobs against the capacity, out of the staging one behind the other, the 12-byte
+// empty blob of a frame without points (its kind's version byte, or the cross form's under a mask), and h_offsets
+static int a_enc_emit(const char* who, const AEncKind& k, pcc_ctx* ctx, const int32_t* h_format, int n_frames, int key_shift,
+                      const AEncOut& o, uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
+  int64_t total = 0;
+  for (int f = 0; f < n_frames; ++f) total += o.len_of[(size_t)f];
+  PCC_REQUIRE(total <= cap, PCC_E_NOMEM, "%s: %lld bytes of blobs, capacity %lld", who, (long long)total, (long long)cap);
+  h_offsets[0] = 0;
+  for (int f = 0; f < n_frames; ++f) {
+    uint8_t* dst = h_out + h_offsets[f];
+    if (o.off_of[(size_t)f] >= 0) {
+      memcpy(dst, (const uint8_t*)ctx->stage + o.off_of[(size_t)f], (size_t)o.len_of[(size_t)f]);
+    } else {
+      const int32_t m = k.h_cross ? k.h_cross[f] : 0;
+      memset(dst, 0, kAttrHead);
+      dst[0] = 'A';
+      dst[1] = (uint8_t)(m ? attr_version(k.v2, k.nl, true) : k.version);
+      dst[2] = (uint8_t)((h_format[f] & 0xFF) | (k.keyed() ? (key_shift / 3) << 4 : 0));
+      dst[3] = (uint8_t)((h_format[f] >> 8) | (m << 4));
+    }
+    h_offsets[f + 1] = h_offsets[f] + o.len_of[(size_t)f];
+  }
+  return PCC_OK;
+}
+
+// what k_a_enc leaves per chunk besides the words: one array of the arena, carved into the chunks' word counts | their
+// lanes' final states | their lanes' lengths
+struct ASmall {
+  uint32_t* words = nullptr;
+  uint16_t *states = nullptr, *lens = nullptr;
+  static size_t bytes(int64_t chunks) { return pcc_align((size_t)chunks * (4 + 2 * kLanes * 2 + kLanes * 2)); }
+  ASmall() = default;
+  ASmall(char* p, int64_t chunks)
+      : words((uint32_t*)p), states((uint16_t*)(p + (size_t)chunks * 4)), lens(states + (size_t)chunks * 2 * kLanes) {}
+  ASmall from(int64_t cb) const {   // the same arrays from chunk cb on
+    ASmall s = *this;
+    s.words += cb, s.states += cb * 2 * kLanes, s.lens += cb * kLanes;
+    return s;
+  }
+};
+
+// k_a_pack over `blocks` workgroups (the rows' chunks and one per row) in the Aux form of the kind: version 22's (TR with
+// V2: d_aux, K), version 21's (TR and a table d_aux), or none
+template <bool V2, bool NL, bool XC, bool TR>
+static int a_launch_pack(hipStream_t st, unsigned blocks, const uint16_t* work, const AFrame* d_tab, int nf, const ASmall& sm,
+                         const uint16_t* p0, uint8_t* out, long long* len_out, const uint32_t* cells, int slod, const int32_t* d_cross,
+                         const int32_t* d_aux, int K) {
+  const auto launch = [&](auto kernel, auto... aux) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, work, d_tab, nf, (const uint16_t*)sm.states, (const uint16_t*)sm.lens,
+                       (const uint32_t*)sm.words, p0, out, len_out, cells, slod, d_cross, aux...);
+  };
+  if constexpr (TR && V2) {
+    launch(k_a_pack<V2, NL, XC, TR, const int32_t*, int>, d_aux, K);
+  } else if constexpr (TR) {
+    if (d_aux) launch(k_a_pack<V2, NL, XC, TR, const int32_t*>, d_aux);
+    else launch(k_a_pack<V2, NL, XC, TR>);
+  } else {
+    launch(k_a_pack<V2, NL, XC, TR>);
+  }
+  PCC_CHECK_LAUNCH();
+  return PCC_OK;
+}
+
 // the encoder of every kind: k_a_merge, the kind's passes of the table above, k_ax_fwd in a call with any m != 0 among
 // its frames with points (every frame is then coded with PRED = false), counting pass, coder, blobs
 static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
@@ -1748,59 +1872,27 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
                            const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique, const uint64_t* d_keys,
                            int key_shift, uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
   const bool v2 = k.v2, nl = k.nl, tr = k.tr, tc = k.tc, sc = k.K > 0, keyed = k.keyed();
-  int64_t n_keys = 0;
-  PCC_TRY(a_check_call(who, k, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys,
-                       key_shift, h_out, cap, h_offsets, &n_keys));
-  std::vector<AFrame> tab;
-  std::vector<A2Order> order;
-  std::vector<int> frame_of;
-  std::vector<int32_t> cross;   // the masks of the frames with points
-  std::vector<int32_t> aux;     // version 21: q[4] and the colour word of the frames with points
-  bool xc = false;              // one of them is not 0
-  int64_t n_max = 0;            // k_ax_fwd: the most points of a frame
+  AEncPlan pl;
   int64_t run_threads = 0;   // k_a4_quant: the most (run, channel) pairs of a frame
-  int64_t u = 0, vals = 0, rec_words = 0, out_bytes = 0, chunks = 0, stats_blocks = 0, merge_blocks = 0, ctxs = 0, nctx_max = 0;
-  for (int f = 0; f < n_frames; ++f) {
-    AFrame r;
-    PCC_TRY(a_check_frame(who, k, f, h_value_offsets, h_format, h_rows, h_points, &r));
-    const int c = r.c;
-    const int64_t n = r.n, nc = r.nc;
-    if (n == 0) continue;
-    const int32_t m = k.h_cross ? k.h_cross[f] : 0;
-    cross.push_back(m);
-    xc |= m != 0;
-    if (tc) {
-      for (int ch = 0; ch < 4; ++ch) aux.push_back(ch < c ? k.h_qsteps[ch] : 0);
-      aux.push_back(k.colour);
-    }
-    n_max = std::max(n_max, n);
-    r.u0 = u;
-    r.val_off = vals;
-    r.rec_off = rec_words;
-    r.ctx_off = (int32_t)ctxs;
-    r.out_off = out_bytes;
-    r.cb = (int32_t)chunks;
-    r.sb = (int32_t)stats_blocks;
-    r.mb = (int32_t)merge_blocks;
-    tab.push_back(r);
-    order.push_back(A2Order{u, n, r.mb, key_shift});
-    frame_of.push_back(f);
-    run_threads = std::max<int64_t>(run_threads, nc * kLanes * c);
-    u += n;
-    vals += n * c;
-    rec_words += nc * kLanes * r.T;
-    out_bytes += a_round(r.out_cap, 16);
-    chunks += nc;
-    stats_blocks += r.sn;
-    merge_blocks += nblk(n, 256);
-    ctxs += r.nctx;
-    nctx_max = std::max<int64_t>(nctx_max, r.nctx);
-  }
-  PCC_REQUIRE(u == n_unique, PCC_E_ARG, "%s: the frames have %lld points, the runs %lld", who, (long long)u,
-              (long long)n_unique);
-  const int nf = (int)tab.size();
-  std::vector<int64_t> len_of((size_t)n_frames, kAttrHead);
-  std::vector<int64_t> off_of((size_t)n_frames, -1);
+  int64_t rec_words = 0, chunks = 0, stats_blocks = 0, ctxs = 0;
+  PCC_TRY(a_enc_front(who, k, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys,
+                      key_shift, h_out, cap, h_offsets, &pl, [&](int, AFrame* r) -> int {
+                        if (!r) return PCC_OK;
+                        r->rec_off = rec_words;
+                        r->ctx_off = (int32_t)ctxs;
+                        r->cb = (int32_t)chunks;
+                        r->sb = (int32_t)stats_blocks;
+                        run_threads = std::max<int64_t>(run_threads, (int64_t)r->nc * kLanes * r->c);
+                        rec_words += (int64_t)r->nc * kLanes * r->T;
+                        chunks += r->nc;
+                        stats_blocks += r->sn;
+                        ctxs += r->nctx;
+                        return PCC_OK;
+                      }));
+  const int nf = pl.nf();
+  const bool xc = pl.xc;
+  const int64_t u = pl.u, vals = pl.vals, merge_blocks = pl.merge_blocks, n_max = pl.n_max;
+  AEncOut out(n_frames);
   hipStream_t st = ctx->stream;
   if (nf > 0) {
     // the rows | the masks (a call with cross-channel frames) | steps and colour (version 21) | the order rows
@@ -1809,17 +1901,16 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
     const size_t cross_at = lay.add(xc ? (size_t)nf * 4 : 0), aux_at = lay.add(tc ? (size_t)nf * 20 : 0);
     const size_t ord_at = lay.add(keyed ? (size_t)nf * sizeof(A2Order) : 0), tab_b = lay.bytes;
     const size_t merged_b = merged_b_of(vals), cnt_b = pcc_align((size_t)ctxs * 8), p0_b = pcc_align((size_t)ctxs * 2);
-    const size_t rec_b = pcc_align((size_t)rec_words * 2), small_b = pcc_align((size_t)chunks * (4 + 2 * kLanes * 2 + kLanes * 2));
+    const size_t rec_b = pcc_align((size_t)rec_words * 2), small_b = ASmall::bytes(chunks);
     // the order stage's (versions 2 and 7): packed | hist | 17 bin bases, then 16 counts per frame; rank, first (7)
     const size_t pk_b = pcc_align((size_t)u * 2), hist_b = pcc_align((size_t)merge_blocks * kA2Bins * 4);
     const size_t bins_b = pcc_align((size_t)nf * 33 * 4), link_b = pcc_align((size_t)u * 4);
     // src is one more array of the merged values' size.  The sum counts it twice for version 2 and the links for
-    // version 4 too: it is what these calls have always reserved, and no call reserves less than it did
-    const size_t order_b = v2 ? 2 * merged_b + pk_b + hist_b + bins_b : 0, nl_b = nl ? merged_b + 2 * link_b : 0;
+    // version 4 too (one of them beside a_t_order_bytes', which has version 19's): it is what these calls have always
+    // reserved, and no call reserves less than it did
+    const size_t order_b = v2 ? 2 * merged_b + pk_b + hist_b + bins_b : 0, nl_b = nl ? merged_b + (tr ? 1 : 2) * link_b : 0;
     const size_t x8_b = xc && !v2 && !nl ? merged_b : 0;   // version 8: the run residuals
-    // version 19's order stage: packed | hist (49 per block) | starts and counts (98 per frame); inv is one of nl_b's links
-    const size_t thist_b = pcc_align((size_t)merge_blocks * kATBins * 4), tbins_b = pcc_align((size_t)nf * 2 * kATBins * 4);
-    const size_t tr_b = (tr ? pk_b + thist_b + tbins_b : 0) + (sc ? a_s_cells_bytes(u) + pcc_align((size_t)nf * 64) : 0);
+    const size_t tr_b = (tr ? a_t_order_bytes(u, merge_blocks, nf) : 0) + (sc ? a_s_cells_bytes(u) + pcc_align((size_t)nf * 64) : 0);
     PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + order_b + nl_b + x8_b + tr_b + 8192));
     AFrame* d_tab = (AFrame*)pcc_arena_alloc(ctx, tab_b);
     uint16_t* merged = (uint16_t*)pcc_arena_alloc(ctx, merged_b);
@@ -1832,27 +1923,25 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
     // a call with cross-channel frames: the run residuals (8) and all of these after k_ax_fwd
     uint16_t* src = v2 || nl || xc ? (uint16_t*)pcc_arena_alloc(ctx, merged_b) : merged;
     if (!d_tab || !merged || !cnt || !p0 || !rec || !work || !small || !src) return PCC_E_NOMEM;
-    uint32_t* words = (uint32_t*)small;
-    uint16_t* states = (uint16_t*)(small + (size_t)chunks * 4);
-    uint16_t* lens_d = states + (size_t)chunks * 2 * kLanes;
+    const ASmall sm(small, chunks);
     const A2Order* d_ord = (const A2Order*)((const uint8_t*)d_tab + ord_at);
     const int32_t* d_cross = xc ? (const int32_t*)((const uint8_t*)d_tab + cross_at) : nullptr;
     const int32_t* d_aux = tc ? (const int32_t*)((const uint8_t*)d_tab + aux_at) : nullptr;
     // staging: the table on its way to the device | the blobs | their lengths
-    const size_t lens_at = tab_b + (size_t)out_bytes;
+    const size_t lens_at = tab_b + (size_t)pl.out_bytes;
     const size_t tcnt_at = lens_at + (size_t)nf * 8 + 64;   // version 19: the sublevels' starts and counts, read back
     PCC_TRY(o2_stage_reserve(ctx, tcnt_at + (tr ? (size_t)nf * 2 * kATBins * 4 : 0) + 64));
     uint8_t* stage = (uint8_t*)ctx->stage;
-    memcpy(stage, tab.data(), (size_t)nf * sizeof(AFrame));
-    if (xc) memcpy(stage + cross_at, cross.data(), (size_t)nf * 4);
-    if (tc) memcpy(stage + aux_at, aux.data(), (size_t)nf * 20);
-    if (keyed) memcpy(stage + ord_at, order.data(), (size_t)nf * sizeof(A2Order));
+    memcpy(stage, pl.tab.data(), (size_t)nf * sizeof(AFrame));
+    if (xc) memcpy(stage + cross_at, pl.cross.data(), (size_t)nf * 4);
+    if (tc) memcpy(stage + aux_at, pl.aux.data(), (size_t)nf * 20);
+    if (keyed) memcpy(stage + ord_at, pl.order.data(), (size_t)nf * sizeof(A2Order));
     long long* len_dev = (long long*)(stage + lens_at);
     PccProfScope prof(ctx, "attr_encode", u, nf, chunks, 0);
     PCC_HIP(hipMemcpyAsync(d_tab, stage, lay.end, hipMemcpyHostToDevice, st));
     PCC_HIP(hipMemsetAsync(cnt, 0, (size_t)ctxs * 8, st));
     hipLaunchKernelGGL(k_a_merge, dim3((unsigned)merge_blocks), dim3(256), 0, st, (const uint8_t*)d_values, (const AFrame*)d_tab, nf,
-                       d_perm, d_run_starts, n_unique, n_keys, merged);
+                       d_perm, d_run_starts, n_unique, pl.n_keys, merged);
     PCC_CHECK_LAUNCH();
     // the introduction order of the frames' points.  keep = false (version 2): the residuals against the predictors go
     // to src; keep (version 7): places and predictors are kept for k_a7_quant
@@ -1885,8 +1974,8 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
         hipLaunchKernelGGL(k_ac_fwd, dim3(nblk(n_max, 256), (unsigned)nf), dim3(256), 0, st, (const AFrame*)d_tab, d_aux, merged);
         PCC_CHECK_LAUNCH();
       }
-      PCC_TRY(a_t_forward(ctx, st, d_keys, d_ord, (const AFrame*)d_tab, nf, merge_blocks, pk_b, thist_b, tbins_b, link_b, merged, src,
-                          (uint32_t*)(stage + tcnt_at), d_aux, sc ? u : -1, &cells));
+      PCC_TRY(a_t_forward(ctx, st, d_keys, d_ord, (const AFrame*)d_tab, nf, merge_blocks, u, merged, src, (uint32_t*)(stage + tcnt_at), d_aux,
+                          sc ? &cells : nullptr));
     } else if (nl && !v2) {
       hipLaunchKernelGGL(k_a4_quant, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const uint16_t*)merged,
                          (const AFrame*)d_tab, src);
@@ -1903,36 +1992,22 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
       PCC_CHECK_LAUNCH();
     }
     // counting pass, coder, blobs
-    const size_t lds = 4096 * 4 + (size_t)(nctx_max + 1) * kLanes * 2;   // <= 98 KB (c = 4, uint16)
+    const size_t lds = 4096 * 4 + (size_t)(pl.nctx_max + 1) * kLanes * 2;   // <= 98 KB (c = 4, uint16)
     auto a_code = [&](auto coder) -> int {
       using K = decltype(coder);
-      constexpr bool V2 = K::V2, NL = K::NL, XC = K::XC, TR = K::TR, TC = K::TC, PRED = K::PRED;
+      constexpr bool PRED = K::PRED;
       hipLaunchKernelGGL(k_a_stats<PRED>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint16_t*)src, (const AFrame*)d_tab, nf, cnt);
       PCC_CHECK_LAUNCH();
       PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<PRED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL(k_a_enc<PRED>, dim3((unsigned)chunks), dim3(64), lds, st, (const uint16_t*)src, (const AFrame*)d_tab, nf,
-                         (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
+                         (const uint32_t*)cnt, rec, work, sm.states, sm.lens, sm.words, p0);
       PCC_CHECK_LAUNCH();
-      if constexpr (TC && V2)
-        hipLaunchKernelGGL((k_a_pack<V2, NL, XC, TR, const int32_t*, int>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st,
-                           (const uint16_t*)work, (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d,
-                           (const uint32_t*)words, (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3,
-                           d_cross, d_aux, k.K);
-      else if constexpr (TC)
-        hipLaunchKernelGGL((k_a_pack<V2, NL, XC, TR, const int32_t*>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st,
-                           (const uint16_t*)work, (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d,
-                           (const uint32_t*)words, (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3,
-                           d_cross, d_aux);
-      else
-        hipLaunchKernelGGL((k_a_pack<V2, NL, XC, TR>), dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work,
-                           (const AFrame*)d_tab, nf, (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words,
-                           (const uint16_t*)p0, stage + tab_b, len_dev, (const uint32_t*)cells, key_shift / 3, d_cross);
-      PCC_CHECK_LAUNCH();
-      return PCC_OK;
+      return a_launch_pack<K::V2, K::NL, K::XC, K::TR>(st, (unsigned)(chunks + nf), work, d_tab, nf, sm, p0, stage + tab_b, len_dev, cells,
+                                                       key_shift / 3, d_cross, d_aux, k.K);
     };
     // by the version byte of the call's frames with a mask, where it has any, else of its plain frames
     int rc = PCC_E_ARG;
-    switch (xc ? attr_version(v2, nl, true) : k.version) {   //   V2     NL     XC     TR    TC
+    switch (xc ? attr_version(v2, nl, true) : k.version) {   //   V2     NL     XC     TR
       case 1: rc = a_code(ACoder<false, false, false>{}); break;
       case 2: rc = a_code(ACoder<true, false, false>{}); break;
       case 4: rc = a_code(ACoder<false, true, false>{}); break;
@@ -1941,40 +2016,15 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
       case 11: rc = a_code(ACoder<true, false, true>{}); break;
       case 13: rc = a_code(ACoder<false, true, true>{}); break;
       case 14: rc = a_code(ACoder<true, true, true>{}); break;
-      case kAttrTVersion: rc = a_code(ACoder<false, true, false, true>{}); break;
-      case kAttrCVersion: rc = a_code(ACoder<false, true, false, true, true>{}); break;
-      case kAttrSVersion: rc = a_code(ACoder<true, true, false, true, true>{}); break;   // V2: the 16 counts in the head
+      case kAttrTVersion:
+      case kAttrCVersion: rc = a_code(ACoder<false, true, false, true>{}); break;   // 21: with its table (d_aux)
+      case kAttrSVersion: rc = a_code(ACoder<true, true, false, true>{}); break;    // V2: the 16 counts in the head
     }
     PCC_TRY(rc);
     PCC_HIP(hipStreamSynchronize(st));
-    for (int i = 0; i < nf; ++i) {
-      const long long total = ((volatile long long*)len_dev)[i];
-      PCC_REQUIRE(total >= 0 && total <= tab[(size_t)i].out_cap, PCC_E_NOMEM,
-                  "%s: frame %d: blob beyond its bound", who, frame_of[(size_t)i]);
-      len_of[(size_t)frame_of[(size_t)i]] = total;
-      off_of[(size_t)frame_of[(size_t)i]] = (int64_t)tab_b + tab[(size_t)i].out_off;
-    }
+    for (int i = 0; i < nf; ++i) PCC_TRY(out.take(who, pl, i, ((volatile long long*)len_dev)[i], tab_b));
   }
-  int64_t total = 0;
-  for (int f = 0; f < n_frames; ++f) total += len_of[(size_t)f];
-  PCC_REQUIRE(total <= cap, PCC_E_NOMEM, "%s: %lld bytes of blobs, capacity %lld", who, (long long)total,
-              (long long)cap);
-  h_offsets[0] = 0;
-  for (int f = 0; f < n_frames; ++f) {
-    uint8_t* dst = h_out + h_offsets[f];
-    if (off_of[(size_t)f] >= 0) {
-      memcpy(dst, (const uint8_t*)ctx->stage + off_of[(size_t)f], (size_t)len_of[(size_t)f]);
-    } else {   // no points: the 12-byte empty blob
-      const int32_t m = k.h_cross ? k.h_cross[f] : 0;
-      memset(dst, 0, kAttrHead);
-      dst[0] = 'A';
-      dst[1] = (uint8_t)(m ? attr_version(v2, nl, true) : k.version);
-      dst[2] = (uint8_t)((h_format[f] & 0xFF) | (keyed ? (key_shift / 3) << 4 : 0));
-      dst[3] = (uint8_t)((h_format[f] >> 8) | (m << 4));
-    }
-    h_offsets[f + 1] = h_offsets[f] + len_of[(size_t)f];
-  }
-  return PCC_OK;
+  return a_enc_emit(who, k, ctx, h_format, n_frames, key_shift, out, h_out, cap, h_offsets);
 }
 
 extern "C" int pcc_attr_encode_frames(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets, const int32_t* h_format,
@@ -2093,6 +2143,12 @@ extern "C" int pcc_attr_rate_ladder(const int32_t h_qstep[4], int c, int bpv, in
   return PCC_OK;
 }
 
+// a frame's ladder: the steps of its J rungs
+struct ARLadder {
+  int32_t steps[kARMaxRungs][4];
+  int J;
+};
+
 // a candidate row on the host: frame fi (of the frames with points) at rung `rung`
 struct ARCand {
   int fi, rung;
@@ -2108,6 +2164,345 @@ struct ARScratch {
   size_t cap = 0, used = 0;
   int epoch = 0;
 };
+// what a candidate row of frame r takes of it
+static size_t a_r_row_need(const AFrame& r) { return pcc_align((size_t)r.n * r.c * 2) + 2 * pcc_align((size_t)r.nc * kLanes * r.T * 2); }
+
+// rows [r0, r1) of a host vector (`per` elements a row) to their place behind `at` of the staging and on to the same
+// place of the device's tables
+template <typename T>
+static int a_send_rows(hipStream_t st, uint8_t* stage, uint8_t* d_tabs, size_t at, const std::vector<T>& v, size_t r0, size_t r1,
+                       size_t per = 1) {
+  const size_t off = at + r0 * per * sizeof(T), bytes = (r1 - r0) * per * sizeof(T);
+  memcpy(stage + off, v.data() + r0 * per, bytes);
+  PCC_HIP(hipMemcpyAsync(d_tabs + off, stage + off, bytes, hipMemcpyHostToDevice, st));
+  return PCC_OK;
+}
+
+// one call under a byte target: what its stages share
+struct ARCall {
+  const char* who;
+  pcc_ctx* ctx;
+  hipStream_t st;
+  const AEncKind* kind;
+  const AEncPlan* pl;            // the frames with points: their rows (the places of a candidate row among the coder's
+                                 // arrays are its own, a_r_code_rows), order rows, steps and colour
+  std::vector<ARLadder> lad;     // their ladders
+  int64_t rows_max = 0, chunks_max = 0, ctxs_max = 0;   // candidate rows the call may code, their chunks and contexts
+  size_t row_need_max = 0, need_all = 0;                // scratch of the largest row, of all rows at once
+  ARScratch scr;
+  // the device's tables: the frames' rows | steps and colour | order rows || per candidate row an AFrame and an ARRow ||
+  // the winners' rows, their steps and colour, their picks.  The staging: the tables on their way to the device | the
+  // blobs | their lengths | the sublevels' bins | the chunks' words
+  uint8_t *d_tabs = nullptr, *stage = nullptr;
+  size_t aux_at = 0, ord_at = 0, base_end = 0, crow_at = 0, qrow_at = 0, wrow_at = 0, waux_at = 0, pick_at = 0, tab_b = 0, tcnt_at = 0;
+  long long* len_dev = nullptr;
+  const uint32_t* h_words = nullptr;
+  // the arena
+  uint16_t *merged = nullptr, *p0 = nullptr, *scratch = nullptr;
+  int32_t* hh = nullptr;
+  uint2* wts = nullptr;
+  uint32_t* cnt = nullptr;
+  ASmall small, wsmall;          // of the candidate rows' chunks, of the winners'
+  size_t lds = 0;                // k_a_enc's
+  // the candidate rows, in the order they were coded
+  std::vector<ARCand> cand;
+  std::vector<AFrame> crow;      // cand[i]'s row of the coder's table
+  std::vector<ARRow> qrow;       // and of the quantiser's
+  int64_t chunks_used = 0, ctxs_used = 0;
+  // the winners' rows of the pack tables
+  std::vector<AFrame> wrow;
+  std::vector<ARPick> picks;
+  std::vector<int32_t> waux;
+  std::vector<int> win_row_of;   // the frame (with points) behind every one of them
+  int64_t wchunks = 0;
+};
+
+// tables, arena and staging of the call; the frames' tables lie in the staging, ready to go
+static int a_r_setup(ARCall& c, int64_t scratch_limit) {
+  const AEncPlan& pl = *c.pl;
+  const int nf = pl.nf();
+  c.scr.cap = std::max(c.row_need_max, std::min(c.need_all, (size_t)(scratch_limit ? scratch_limit : kARScratchDefault)));
+  ATables lay;
+  lay.add((size_t)nf * sizeof(AFrame));
+  c.aux_at = lay.add((size_t)nf * 20), c.ord_at = lay.add((size_t)nf * sizeof(A2Order));
+  c.base_end = lay.end;
+  c.crow_at = lay.add((size_t)c.rows_max * sizeof(AFrame)), c.qrow_at = lay.add((size_t)c.rows_max * sizeof(ARRow));
+  c.wrow_at = lay.add((size_t)nf * sizeof(AFrame)), c.waux_at = lay.add((size_t)nf * 20);
+  c.pick_at = lay.add((size_t)nf * sizeof(ARPick)), c.tab_b = lay.bytes;
+  int64_t win_chunks = 0;
+  for (const AFrame& r : pl.tab) win_chunks += r.nc;
+  const size_t merged_b = merged_b_of(pl.vals), hh_b = pcc_align((size_t)pl.vals * 4), wts_b = pcc_align((size_t)pl.u * 8);
+  const size_t cnt_b = pcc_align((size_t)c.ctxs_max * 8), p0_b = pcc_align((size_t)c.ctxs_max * 2);
+  PCC_TRY(pcc_arena_reserve(c.ctx, c.tab_b + merged_b + hh_b + wts_b + cnt_b + p0_b + ASmall::bytes(c.chunks_max) + ASmall::bytes(win_chunks) +
+                                       a_t_order_bytes(pl.u, pl.merge_blocks, nf) + c.scr.cap + 8192));
+  c.d_tabs = (uint8_t*)pcc_arena_alloc(c.ctx, c.tab_b);
+  c.merged = (uint16_t*)pcc_arena_alloc(c.ctx, merged_b);
+  c.hh = (int32_t*)pcc_arena_alloc(c.ctx, hh_b);
+  c.wts = (uint2*)pcc_arena_alloc(c.ctx, wts_b);
+  c.cnt = (uint32_t*)pcc_arena_alloc(c.ctx, cnt_b);
+  c.p0 = (uint16_t*)pcc_arena_alloc(c.ctx, p0_b);
+  char* small = (char*)pcc_arena_alloc(c.ctx, ASmall::bytes(c.chunks_max));
+  char* wsmall = (char*)pcc_arena_alloc(c.ctx, ASmall::bytes(win_chunks));
+  c.scratch = (uint16_t*)pcc_arena_alloc(c.ctx, c.scr.cap);
+  if (!c.d_tabs || !c.merged || !c.hh || !c.wts || !c.cnt || !c.p0 || !small || !wsmall || !c.scratch) return PCC_E_NOMEM;
+  c.small = ASmall(small, c.chunks_max);
+  c.wsmall = ASmall(wsmall, win_chunks);
+  const size_t lens_at = c.tab_b + (size_t)pl.out_bytes;
+  c.tcnt_at = lens_at + (size_t)nf * 8 + 64;
+  const size_t hwords_at = c.tcnt_at + pcc_align((size_t)nf * 2 * kATBins * 4);
+  PCC_TRY(o2_stage_reserve(c.ctx, hwords_at + (size_t)c.chunks_max * 4 + 64));
+  c.stage = (uint8_t*)c.ctx->stage;
+  memcpy(c.stage, pl.tab.data(), (size_t)nf * sizeof(AFrame));
+  memcpy(c.stage + c.aux_at, pl.aux.data(), (size_t)nf * 20);
+  memcpy(c.stage + c.ord_at, pl.order.data(), (size_t)nf * sizeof(A2Order));
+  c.len_dev = (long long*)(c.stage + lens_at);
+  c.h_words = (const uint32_t*)(c.stage + hwords_at);
+  c.lds = 4096 * 4 + (size_t)(pl.nctx_max + 1) * kLanes * 2;
+  return PCC_OK;
+}
+
+// what does not depend on the step, once for every rung: the tables up, merge, colour transform, the order stage, the
+// lift without its quantiser and the mean
+static int a_r_lift(ARCall& c, const void* d_values, const uint32_t* d_perm, const uint32_t* d_run_starts, int64_t n_unique,
+                    const uint64_t* d_keys) {
+  const AEncPlan& pl = *c.pl;
+  const int nf = pl.nf();
+  hipStream_t st = c.st;
+  const AFrame* d_tab = (const AFrame*)c.d_tabs;
+  const int32_t* d_aux = (const int32_t*)(c.d_tabs + c.aux_at);
+  const A2Order* d_ord = (const A2Order*)(c.d_tabs + c.ord_at);
+  PCC_HIP(hipMemcpyAsync(c.d_tabs, c.stage, c.base_end, hipMemcpyHostToDevice, st));
+  PCC_HIP(hipMemsetAsync(c.cnt, 0, (size_t)c.ctxs_max * 8, st));
+  hipLaunchKernelGGL(k_a_merge, dim3((unsigned)pl.merge_blocks), dim3(256), 0, st, (const uint8_t*)d_values, d_tab, nf, d_perm, d_run_starts,
+                     n_unique, pl.n_keys, c.merged);
+  PCC_CHECK_LAUNCH();
+  if (c.kind->colour) {
+    hipLaunchKernelGGL(k_ac_fwd, dim3(nblk(pl.n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, d_aux, c.merged);
+    PCC_CHECK_LAUNCH();
+  }
+  ATOrder o;
+  PCC_TRY(a_t_order_enc(c.ctx, st, d_keys, d_ord, nf, pl.merge_blocks, pl.u, (uint32_t*)(c.stage + c.tcnt_at), &o));
+  for (int t = 0; t < kATBins - 1; ++t) {
+    if (!o.grid[t]) continue;
+    hipLaunchKernelGGL(k_ar_lift, dim3(o.grid[t], (unsigned)nf), dim3(256), 0, st, d_keys, d_ord, (const uint32_t*)o.bins, (const uint32_t*)o.inv,
+                       t, d_tab, c.merged, c.hh, c.wts);
+    PCC_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_ar_mean, dim3(nblk(4 * (int64_t)nf, 256)), dim3(256), 0, st, d_tab, nf, (const uint16_t*)c.merged, c.hh);
+  PCC_CHECK_LAUNCH();
+  return PCC_OK;
+}
+
+// lays out the rows `want` (frame, rung) in groups that fit the scratch block, appends them to cand, sends their table
+// rows and codes them group by group: k_ar_quant, k_a_stats, k_a_enc
+static int a_r_code_rows(ARCall& c, const std::vector<std::pair<int, int>>& want) {
+  const std::vector<AFrame>& tab = c.pl->tab;
+  ARScratch& scr = c.scr;
+  const size_t first = c.cand.size();
+  PCC_REQUIRE(first + want.size() <= (size_t)c.rows_max, PCC_E_NOMEM, "%s: %zu candidate rows, room for %lld", c.who, first + want.size(),
+              (long long)c.rows_max);
+  struct Group {
+    size_t r0, r1, base;   // rows, where the group starts in the scratch block (bytes)
+    int64_t rec_words, quant_blocks, stats_blocks, chunks, cb;
+  };
+  std::vector<Group> groups;
+  for (size_t w = 0; w < want.size();) {
+    size_t w1 = w, bytes = 0;
+    while (w1 < want.size() && scr.used + bytes + a_r_row_need(tab[(size_t)want[w1].first]) <= scr.cap)
+      bytes += a_r_row_need(tab[(size_t)want[w1++].first]);
+    if (w1 == w) {   // the block starts over: one row always fits
+      scr.used = 0;
+      ++scr.epoch;
+      continue;
+    }
+    Group g{first + w, first + w1, scr.used, 0, 0, 0, 0, c.chunks_used};
+    size_t idx_b = 0;
+    for (size_t i = w; i < w1; ++i) {
+      const AFrame& b = tab[(size_t)want[i].first];
+      idx_b += pcc_align((size_t)b.n * b.c * 2);
+      g.rec_words += (int64_t)(pcc_align((size_t)b.nc * kLanes * b.T * 2) / 2);
+    }
+    size_t idx_at = g.base / 2, rec_at = (g.base + idx_b) / 2;   // 16-bit words from the block's start
+    for (size_t i = w; i < w1; ++i) {
+      const int fi = want[i].first, rung = want[i].second;
+      const AFrame& b = tab[(size_t)fi];
+      ARCand cd{fi, rung, c.chunks_used, c.ctxs_used, (int64_t)idx_at, (int64_t)rec_at, (int64_t)rec_at + g.rec_words, scr.epoch, 0};
+      AFrame r = b;
+      r.val_off = cd.idx_off;
+      r.rec_off = cd.rec_off;
+      r.ctx_off = (int32_t)cd.ctx_off;
+      r.cb = (int32_t)g.chunks;
+      r.sb = (int32_t)g.stats_blocks;
+      ARRow q{b.val_off, c.pl->order[(size_t)fi].pt0, cd.idx_off, b.n * b.c, (int32_t)g.quant_blocks, b.c, b.bpv, 0, {0, 0, 0, 0}};
+      for (int ch = 0; ch < 4; ++ch) q.q[ch] = c.lad[(size_t)fi].steps[rung][ch];
+      c.cand.push_back(cd);
+      c.crow.push_back(r);
+      c.qrow.push_back(q);
+      g.chunks += b.nc;
+      g.stats_blocks += b.sn;
+      g.quant_blocks += nblk(b.n * b.c, 256);
+      c.chunks_used += b.nc;
+      c.ctxs_used += b.nctx;
+      idx_at += pcc_align((size_t)b.n * b.c * 2) / 2;
+      rec_at += pcc_align((size_t)b.nc * kLanes * b.T * 2) / 2;
+    }
+    scr.used += bytes;
+    groups.push_back(g);
+    w = w1;
+  }
+  PCC_TRY(a_send_rows(c.st, c.stage, c.d_tabs, c.crow_at, c.crow, first, c.crow.size()));
+  PCC_TRY(a_send_rows(c.st, c.stage, c.d_tabs, c.qrow_at, c.qrow, first, c.qrow.size()));
+  const AFrame* d_crow = (const AFrame*)(c.d_tabs + c.crow_at);
+  const ARRow* d_qrow = (const ARRow*)(c.d_tabs + c.qrow_at);
+  for (const Group& g : groups) {
+    const int n_r = (int)(g.r1 - g.r0);
+    const ASmall sm = c.small.from(g.cb);
+    hipLaunchKernelGGL(k_ar_quant, dim3((unsigned)g.quant_blocks), dim3(256), 0, c.st, d_qrow + g.r0, n_r, (const int32_t*)c.hh,
+                       (const uint2*)c.wts, c.scratch);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_a_stats<false>, dim3((unsigned)g.stats_blocks), dim3(256), 0, c.st, (const uint16_t*)c.scratch, d_crow + g.r0, n_r,
+                       c.cnt);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_a_enc<false>, dim3((unsigned)g.chunks), dim3(64), c.lds, c.st, (const uint16_t*)c.scratch, d_crow + g.r0, n_r,
+                       (const uint32_t*)c.cnt, c.scratch, c.scratch + g.rec_words, sm.states, sm.lens, sm.words, c.p0);
+    PCC_CHECK_LAUNCH();
+  }
+  return PCC_OK;
+}
+
+// the lengths of the rows cand[first ..): one read-back of their chunks' words, one synchronisation
+static int a_r_read_lens(ARCall& c, size_t first) {
+  if (first == c.cand.size()) return PCC_OK;
+  const int64_t c0 = c.cand[first].cb;
+  PCC_HIP(hipMemcpyAsync((void*)(c.h_words + c0), c.small.words + c0, (size_t)(c.chunks_used - c0) * 4, hipMemcpyDeviceToHost, c.st));
+  PCC_HIP(hipStreamSynchronize(c.st));
+  for (size_t i = first; i < c.cand.size(); ++i) {
+    const AFrame& b = c.pl->tab[(size_t)c.cand[i].fi];
+    int64_t w = 0;
+    for (int64_t k = 0; k < b.nc; ++k) w += ((volatile const uint32_t*)c.h_words)[c.cand[i].cb + k];
+    c.cand[i].len = a_head_bytes(*c.kind, b.c, b.nctx, b.nc) + 2 * w;
+  }
+  return PCC_OK;
+}
+
+// host only, stage 1 of the search (tests/attr_rate_ref.py): a frame's rows cand[a0, a1) at the rungs of A, rising, under
+// the target B.  The row that wins; or -1 and *fall, the first row that fits, which wins unless stage 2 finds a rung that
+// fits among those between the rung of the row in front of it and its own
+static int64_t a_r_stage1(const std::vector<ARCand>& cand, size_t a0, size_t a1, int64_t B, int64_t* fall) {
+  size_t a = a0;
+  while (a < a1 && cand[a].len > B) ++a;
+  if (a == a1) return (int64_t)a - 1;   // nothing fits: rung J - 1, over its target
+  if (a == a0 || cand[a].rung - cand[a - 1].rung == 1) return (int64_t)a;
+  *fall = (int64_t)a;
+  return -1;
+}
+
+// the two-stage search: win[i] = the row of cand that frame i (with points) gets
+static int a_r_search(ARCall& c, const int64_t* h_target, std::vector<int64_t>* win_out) {
+  const int nf = c.pl->nf();
+  const std::vector<int>& frame_of = c.pl->frame_of;
+  PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds));
+  // stage 1: the rungs of A = { j : j % 4 == 0 } and J - 1
+  std::vector<std::pair<int, int>> want;
+  std::vector<size_t> s1_at((size_t)nf + 1);
+  for (int i = 0; i < nf; ++i) {
+    s1_at[(size_t)i] = want.size();
+    const int J = c.lad[(size_t)i].J;
+    for (int j = 0; j < J; j += 4) want.emplace_back(i, j);
+    if ((J - 1) % 4) want.emplace_back(i, J - 1);
+  }
+  s1_at[(size_t)nf] = want.size();
+  PCC_TRY(a_r_code_rows(c, want));
+  PCC_TRY(a_r_read_lens(c, 0));
+  // stage 2 codes the rungs inside (a', a) of the frames that stage 1 leaves open; the first of them that fits wins
+  std::vector<int64_t>& win = *win_out;
+  std::vector<int64_t> s2_fall((size_t)nf, -1);
+  win.assign((size_t)nf, -1);
+  want.clear();
+  for (int i = 0; i < nf; ++i) {
+    int64_t& a = s2_fall[(size_t)i];
+    win[(size_t)i] = a_r_stage1(c.cand, s1_at[(size_t)i], s1_at[(size_t)i + 1], h_target[frame_of[(size_t)i]], &a);
+    if (win[(size_t)i] >= 0) continue;
+    for (int j = c.cand[(size_t)a - 1].rung + 1; j < c.cand[(size_t)a].rung; ++j) want.emplace_back(i, j);
+  }
+  if (want.empty()) return PCC_OK;
+  const size_t s2 = c.cand.size();
+  PCC_TRY(a_r_code_rows(c, want));
+  PCC_TRY(a_r_read_lens(c, s2));
+  for (size_t r = s2; r < c.cand.size(); ++r) {
+    const int i = c.cand[r].fi;
+    if (win[(size_t)i] < 0 && c.cand[r].len <= h_target[frame_of[(size_t)i]]) win[(size_t)i] = (int64_t)r;
+  }
+  for (int i = 0; i < nf; ++i)
+    if (win[(size_t)i] < 0) win[(size_t)i] = s2_fall[(size_t)i];
+  return PCC_OK;
+}
+
+// one batch of winners: frames[k] (with points) at its row rows[k] of cand, whose word regions the scratch block holds.
+// Their rows of the pack tables, sent; k_ar_gather and k_a_pack over them; rung_of[the call's frame] = the rung
+static int a_r_pack_batch(ARCall& c, const std::vector<int>& frames, const std::vector<int64_t>& rows, int key_shift, std::vector<int>* rung_of) {
+  const size_t r0 = c.wrow.size();
+  const int n_r = (int)frames.size();
+  const int64_t cb = c.wchunks;   // the batch's chunks in the winners' small arrays
+  int64_t chunks = 0, nc_max = 0;
+  for (size_t k = 0; k < frames.size(); ++k) {
+    const ARCand& cd = c.cand[(size_t)rows[k]];
+    const int32_t* steps = c.lad[(size_t)cd.fi].steps[cd.rung];
+    AFrame r = c.pl->tab[(size_t)frames[k]];
+    r.e = c.kind->tc ? c.kind->e : steps[0];
+    r.rec_off = cd.work_off;
+    r.ctx_off = (int32_t)cd.ctx_off;
+    r.cb = (int32_t)chunks;
+    c.picks.push_back(ARPick{(int32_t)cd.cb, (int32_t)(cb + chunks), r.nc, 0});
+    for (int ch = 0; ch < 4; ++ch) c.waux.push_back(steps[ch]);
+    c.waux.push_back(c.kind->colour);
+    c.wrow.push_back(r);
+    chunks += r.nc;
+    nc_max = std::max<int64_t>(nc_max, r.nc);
+    (*rung_of)[(size_t)c.pl->frame_of[(size_t)frames[k]]] = cd.rung;
+  }
+  c.wchunks += chunks;
+  c.win_row_of.insert(c.win_row_of.end(), frames.begin(), frames.end());
+  PCC_TRY(a_send_rows(c.st, c.stage, c.d_tabs, c.wrow_at, c.wrow, r0, c.wrow.size()));
+  PCC_TRY(a_send_rows(c.st, c.stage, c.d_tabs, c.waux_at, c.waux, r0, c.wrow.size(), 5));
+  PCC_TRY(a_send_rows(c.st, c.stage, c.d_tabs, c.pick_at, c.picks, r0, c.picks.size()));
+  hipLaunchKernelGGL(k_ar_gather, dim3(nblk(nc_max * 2 * kLanes, 256), (unsigned)n_r), dim3(256), 0, c.st,
+                     (const ARPick*)(c.d_tabs + c.pick_at) + r0, (const uint32_t*)c.small.words, (const uint16_t*)c.small.states,
+                     (const uint16_t*)c.small.lens, c.wsmall.words, c.wsmall.states, c.wsmall.lens);
+  PCC_CHECK_LAUNCH();
+  return a_launch_pack<false, true, false, true>(c.st, (unsigned)(chunks + n_r), c.scratch, (const AFrame*)(c.d_tabs + c.wrow_at) + r0, n_r,
+                                                 c.wsmall.from(cb), c.p0, c.stage + c.tab_b, c.len_dev + r0, nullptr, key_shift / 3, nullptr,
+                                                 c.kind->tc ? (const int32_t*)(c.d_tabs + c.waux_at) + 5 * r0 : nullptr, 0);
+}
+
+// the winners to blobs: those whose word regions the scratch block still holds in one batch; the others coded once
+// more, as many at a time as one turn of the block holds, every batch packed before the next one may take the block
+static int a_r_pack_winners(ARCall& c, const std::vector<int64_t>& win, int key_shift, std::vector<int>* rung_of) {
+  const std::vector<AFrame>& tab = c.pl->tab;
+  std::vector<int> held, lost;
+  for (int i = 0; i < c.pl->nf(); ++i) (c.cand[(size_t)win[(size_t)i]].epoch == c.scr.epoch ? held : lost).push_back(i);
+  if (!held.empty()) {
+    std::vector<int64_t> rows;
+    for (int i : held) rows.push_back(win[(size_t)i]);
+    PCC_TRY(a_r_pack_batch(c, held, rows, key_shift, rung_of));
+  }
+  std::vector<std::pair<int, int>> want;
+  for (size_t k = 0; k < lost.size();) {
+    size_t k1 = k, bytes = 0;
+    while (k1 < lost.size() && bytes + a_r_row_need(tab[(size_t)lost[k1]]) <= c.scr.cap) bytes += a_r_row_need(tab[(size_t)lost[k1++]]);
+    c.scr.used = c.scr.cap;   // this group starts the block over
+    want.clear();
+    const std::vector<int> frames(lost.begin() + (long)k, lost.begin() + (long)k1);
+    for (int i : frames) want.emplace_back(i, c.cand[(size_t)win[(size_t)i]].rung);
+    const size_t first = c.cand.size();
+    PCC_TRY(a_r_code_rows(c, want));
+    std::vector<int64_t> rows;
+    for (size_t r = first; r < c.cand.size(); ++r) rows.push_back((int64_t)r);
+    PCC_TRY(a_r_pack_batch(c, frames, rows, key_shift, rung_of));
+    k = k1;
+  }
+  return PCC_OK;
+}
 
 extern "C" int pcc_attr_encode_frames_rate(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets, const int32_t* h_format,
                                            const int64_t* h_rows, const int64_t* h_points, int n_frames, const uint32_t* d_perm,
@@ -2120,403 +2515,51 @@ extern "C" int pcc_attr_encode_frames_rate(pcc_ctx* ctx, const void* d_values, c
                   (per_channel || (!colour && h_qstep[0] >= 1)) && scratch_limit >= 0,
               PCC_E_ARG, "%s: bad argument (n_kept=%lld per_channel=%d colour=%d scratch_limit=%lld)", who, (long long)n_kept, per_channel,
               colour, (long long)scratch_limit);
-  const bool tc = per_channel != 0;
-  const AEncKind kind = a_kind_transform(n_kept, h_qstep[0], tc ? h_qstep : nullptr, colour);
-  int64_t n_keys = 0;
-  PCC_TRY(a_check_call(who, kind, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys,
-                       key_shift, h_out, cap, h_offsets, &n_keys));
-
-  // the frames with points: their rows as a_encode_frames lays them out, their ladders, their stage-1 rungs
-  struct Lad {
-    int32_t steps[kARMaxRungs][4];
-    int J;
-  };
-  std::vector<AFrame> tab;
-  std::vector<A2Order> order;
-  std::vector<int> frame_of;
-  std::vector<int32_t> aux;
-  std::vector<Lad> lad;
-  int64_t n_max = 0, u = 0, vals = 0, out_bytes = 0, merge_blocks = 0, nctx_max = 0;
-  int64_t rows_max = 0, chunks_max = 0, ctxs_max = 0;   // candidate rows the call may code, their chunks and contexts
-  size_t row_need_max = 0, need_all = 0;                // scratch of the largest row, of all rows at once
-  auto row_need = [](const AFrame& r) { return pcc_align((size_t)r.n * r.c * 2) + 2 * pcc_align((size_t)r.nc * kLanes * r.T * 2); };
-  for (int f = 0; f < n_frames; ++f) {
-    AFrame r;
-    PCC_TRY(a_check_frame(who, kind, f, h_value_offsets, h_format, h_rows, h_points, &r));
-    PCC_REQUIRE(h_target[f] >= 1, PCC_E_ARG, "%s: frame %d: a target of %lld bytes (at least 1)", who, f, (long long)h_target[f]);
-    const int c = r.c, bpv = r.bpv;
-    const int64_t n = r.n, nc = r.nc;
-    if (n == 0) continue;
-    int32_t q[4];
-    for (int ch = 0; ch < 4; ++ch) q[ch] = ch < c ? h_qstep[tc ? ch : 0] : 0;
-    lad.emplace_back();
-    lad.back().J = a_r_ladder(q, c, bpv, lad.back().steps);
-    for (int ch = 0; ch < 4; ++ch) aux.push_back(q[ch]);
-    aux.push_back(colour);
-    n_max = std::max(n_max, n);
-    r.u0 = u;               // a candidate row's places among the coder's arrays are its own (code_rows)
-    r.val_off = vals;
-    r.out_off = out_bytes;
-    r.mb = (int32_t)merge_blocks;
-    tab.push_back(r);
-    order.push_back(A2Order{u, n, r.mb, key_shift});
-    frame_of.push_back(f);
-    const int64_t rows_f = (lad.back().J + 3) / 4 + 1 + 3 + 1;   // stage 1 | stage 2 | once more at the end
-    rows_max += rows_f;
-    chunks_max += rows_f * nc;
-    ctxs_max += rows_f * r.nctx;
-    row_need_max = std::max(row_need_max, row_need(r));
-    need_all += (size_t)(rows_f - 1) * row_need(r);
-    u += n;
-    vals += n * c;
-    out_bytes += a_round(r.out_cap, 16);
-    merge_blocks += nblk(n, 256);
-    nctx_max = std::max<int64_t>(nctx_max, r.nctx);
-  }
-  PCC_REQUIRE(u == n_unique, PCC_E_ARG, "%s: the frames have %lld points, the runs %lld", who, (long long)u, (long long)n_unique);
-  const int nf = (int)tab.size();
-  std::vector<int64_t> len_of((size_t)n_frames, kAttrHead);
-  std::vector<int64_t> off_of((size_t)n_frames, -1);
+  const AEncKind kind = a_kind_transform(n_kept, h_qstep[0], per_channel ? h_qstep : nullptr, colour);
+  AEncPlan pl;
+  ARCall c;
+  c.who = who, c.ctx = ctx, c.kind = &kind, c.pl = &pl;
+  // per frame its target, checked; per frame with points its ladder and what its candidate rows may take
+  PCC_TRY(a_enc_front(who, kind, ctx, d_values, h_value_offsets, h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys,
+                      key_shift, h_out, cap, h_offsets, &pl, [&](int f, AFrame* r) -> int {
+                        PCC_REQUIRE(h_target[f] >= 1, PCC_E_ARG, "%s: frame %d: a target of %lld bytes (at least 1)", who, f,
+                                    (long long)h_target[f]);
+                        if (!r) return PCC_OK;
+                        c.lad.emplace_back();
+                        c.lad.back().J = a_r_ladder(&pl.aux[pl.aux.size() - 5], r->c, r->bpv, c.lad.back().steps);
+                        const int64_t rows_f = (c.lad.back().J + 3) / 4 + 1 + 3 + 1;   // stage 1 | stage 2 | once more at the end
+                        c.rows_max += rows_f;
+                        c.chunks_max += rows_f * r->nc;
+                        c.ctxs_max += rows_f * r->nctx;
+                        c.row_need_max = std::max(c.row_need_max, a_r_row_need(*r));
+                        c.need_all += (size_t)(rows_f - 1) * a_r_row_need(*r);
+                        return PCC_OK;
+                      }));
+  const int nf = pl.nf();
+  AEncOut out(n_frames);
   std::vector<int> rung_of((size_t)n_frames, -1);
-  hipStream_t st = ctx->stream;
   if (nf > 0) {
-    ARScratch scr;
-    scr.cap = std::max(row_need_max, std::min(need_all, (size_t)(scratch_limit ? scratch_limit : kARScratchDefault)));
-    // device tables: the frames' rows | steps and colour | order rows || per candidate row an AFrame and an ARRow ||
-    // the winners' rows, their steps and colour, their picks
-    ATables lay;
-    lay.add((size_t)nf * sizeof(AFrame));
-    const size_t aux_at = lay.add((size_t)nf * 20), ord_at = lay.add((size_t)nf * sizeof(A2Order));
-    const size_t base_end = lay.end;
-    const size_t crow_at = lay.add((size_t)rows_max * sizeof(AFrame)), qrow_at = lay.add((size_t)rows_max * sizeof(ARRow));
-    const size_t wrow_at = lay.add((size_t)nf * sizeof(AFrame)), waux_at = lay.add((size_t)nf * 20);
-    const size_t pick_at = lay.add((size_t)nf * sizeof(ARPick)), tab_b = lay.bytes;
-    int64_t win_chunks = 0;
-    for (const AFrame& r : tab) win_chunks += r.nc;
-    auto small_of = [](int64_t chunks) { return pcc_align((size_t)chunks * (4 + 2 * kLanes * 2 + kLanes * 2)); };
-    const size_t merged_b = merged_b_of(vals), hh_b = pcc_align((size_t)vals * 4), wts_b = pcc_align((size_t)u * 8);
-    const size_t cnt_b = pcc_align((size_t)ctxs_max * 8), p0_b = pcc_align((size_t)ctxs_max * 2);
-    const size_t pk_b = pcc_align((size_t)u * 2), link_b = pcc_align((size_t)u * 4);
-    const size_t thist_b = pcc_align((size_t)merge_blocks * kATBins * 4), tbins_b = pcc_align((size_t)nf * 2 * kATBins * 4);
-    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + hh_b + wts_b + cnt_b + p0_b + small_of(chunks_max) + small_of(win_chunks) + pk_b +
-                                       link_b + thist_b + tbins_b + scr.cap + 8192));
-    uint8_t* d_tabs = (uint8_t*)pcc_arena_alloc(ctx, tab_b);
-    uint16_t* merged = (uint16_t*)pcc_arena_alloc(ctx, merged_b);
-    int32_t* hh = (int32_t*)pcc_arena_alloc(ctx, hh_b);
-    uint2* wts = (uint2*)pcc_arena_alloc(ctx, wts_b);
-    uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, cnt_b);
-    uint16_t* p0 = (uint16_t*)pcc_arena_alloc(ctx, p0_b);
-    char* small = (char*)pcc_arena_alloc(ctx, small_of(chunks_max));
-    char* wsmall = (char*)pcc_arena_alloc(ctx, small_of(win_chunks));
-    uint16_t* scratch = (uint16_t*)pcc_arena_alloc(ctx, scr.cap);
-    if (!d_tabs || !merged || !hh || !wts || !cnt || !p0 || !small || !wsmall || !scratch) return PCC_E_NOMEM;
-    uint32_t* words = (uint32_t*)small;
-    uint16_t* states = (uint16_t*)(small + (size_t)chunks_max * 4);
-    uint16_t* lens_d = states + (size_t)chunks_max * 2 * kLanes;
-    uint32_t* wwords = (uint32_t*)wsmall;
-    uint16_t* wstates = (uint16_t*)(wsmall + (size_t)win_chunks * 4);
-    uint16_t* wlens = wstates + (size_t)win_chunks * 2 * kLanes;
-    const AFrame* d_tab = (const AFrame*)d_tabs;
-    const int32_t* d_aux = (const int32_t*)(d_tabs + aux_at);
-    const A2Order* d_ord = (const A2Order*)(d_tabs + ord_at);
-    const AFrame* d_crow = (const AFrame*)(d_tabs + crow_at);
-    const ARRow* d_qrow = (const ARRow*)(d_tabs + qrow_at);
-    // staging: the tables on their way to the device | the blobs | their lengths | the sublevels' bins | the chunks' words
-    const size_t lens_at = tab_b + (size_t)out_bytes, tcnt_at = lens_at + (size_t)nf * 8 + 64;
-    const size_t hwords_at = tcnt_at + pcc_align((size_t)nf * 2 * kATBins * 4);
-    PCC_TRY(o2_stage_reserve(ctx, hwords_at + (size_t)chunks_max * 4 + 64));
-    uint8_t* stage = (uint8_t*)ctx->stage;
-    memcpy(stage, tab.data(), (size_t)nf * sizeof(AFrame));
-    memcpy(stage + aux_at, aux.data(), (size_t)nf * 20);
-    memcpy(stage + ord_at, order.data(), (size_t)nf * sizeof(A2Order));
-    long long* len_dev = (long long*)(stage + lens_at);
-    const uint32_t* h_words = (const uint32_t*)(stage + hwords_at);
-    PccProfScope prof(ctx, "attr_encode_rate", u, nf, rows_max, 0);
-    PCC_HIP(hipMemcpyAsync(d_tabs, stage, base_end, hipMemcpyHostToDevice, st));
-    PCC_HIP(hipMemsetAsync(cnt, 0, (size_t)ctxs_max * 8, st));
-    hipLaunchKernelGGL(k_a_merge, dim3((unsigned)merge_blocks), dim3(256), 0, st, (const uint8_t*)d_values, d_tab, nf, d_perm, d_run_starts,
-                       n_unique, n_keys, merged);
-    PCC_CHECK_LAUNCH();
-    if (colour) {
-      hipLaunchKernelGGL(k_ac_fwd, dim3(nblk(n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, d_aux, merged);
-      PCC_CHECK_LAUNCH();
-    }
-    // the order stage and the lift, once for every rung
-    {
-      uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, pk_b);
-      uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, thist_b);
-      uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, tbins_b);
-      uint32_t* inv = (uint32_t*)pcc_arena_alloc(ctx, link_b);
-      if (!packed || !hist || !bins || !inv) return PCC_E_NOMEM;
-      unsigned grid[kATBins];
-      PCC_TRY(a_t_order(st, false, (const void*)d_keys, nullptr, d_ord, nf, merge_blocks, packed, hist, bins, inv, (uint32_t*)(stage + tcnt_at),
-                        grid));
-      for (int t = 0; t < kATBins - 1; ++t) {
-        if (!grid[t]) continue;
-        hipLaunchKernelGGL(k_ar_lift, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, d_keys, d_ord, (const uint32_t*)bins, (const uint32_t*)inv,
-                           t, d_tab, merged, hh, wts);
-        PCC_CHECK_LAUNCH();
-      }
-      hipLaunchKernelGGL(k_ar_mean, dim3(nblk(4 * (int64_t)nf, 256)), dim3(256), 0, st, d_tab, nf, (const uint16_t*)merged, hh);
-      PCC_CHECK_LAUNCH();
-    }
-
-    // candidate rows: laid out, uploaded and coded stage by stage
-    std::vector<ARCand> cand;
-    std::vector<AFrame> crow;   // cand[i]'s row of the coder's table
-    std::vector<ARRow> qrow;    // and of the quantiser's
-    int64_t chunks_used = 0, ctxs_used = 0;
-    const size_t lds = 4096 * 4 + (size_t)(nctx_max + 1) * kLanes * 2;
-    PCC_HIP(hipFuncSetAttribute((const void*)k_a_enc<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    // codes the rows `want` (frame, rung) in groups that fit the scratch block; appends them to cand
-    auto code_rows = [&](const std::vector<std::pair<int, int>>& want) -> int {
-      const size_t first = cand.size();
-      PCC_REQUIRE(first + want.size() <= (size_t)rows_max, PCC_E_NOMEM, "%s: %zu candidate rows, room for %lld", who, first + want.size(),
-                  (long long)rows_max);
-      struct Group {
-        size_t r0, r1, base;   // rows, where the group starts in the scratch block (bytes)
-        int64_t rec_words, quant_blocks, stats_blocks, chunks, cb;
-      };
-      std::vector<Group> groups;
-      for (size_t w = 0; w < want.size();) {
-        size_t w1 = w, bytes = 0;
-        while (w1 < want.size() && scr.used + bytes + row_need(tab[(size_t)want[w1].first]) <= scr.cap) bytes += row_need(tab[(size_t)want[w1++].first]);
-        if (w1 == w) {   // the block starts over: one row always fits
-          scr.used = 0;
-          ++scr.epoch;
-          continue;
-        }
-        Group g{first + w, first + w1, scr.used, 0, 0, 0, 0, chunks_used};
-        size_t idx_b = 0;
-        for (size_t i = w; i < w1; ++i) {
-          const AFrame& b = tab[(size_t)want[i].first];
-          idx_b += pcc_align((size_t)b.n * b.c * 2);
-          g.rec_words += (int64_t)(pcc_align((size_t)b.nc * kLanes * b.T * 2) / 2);
-        }
-        size_t idx_at = g.base / 2, rec_at = (g.base + idx_b) / 2;   // 16-bit words from the block's start
-        for (size_t i = w; i < w1; ++i) {
-          const int fi = want[i].first, rung = want[i].second;
-          const AFrame& b = tab[(size_t)fi];
-          ARCand cd{fi, rung, chunks_used, ctxs_used, (int64_t)idx_at, (int64_t)rec_at, (int64_t)rec_at + g.rec_words, scr.epoch, 0};
-          AFrame r = b;
-          r.val_off = cd.idx_off;
-          r.rec_off = cd.rec_off;
-          r.ctx_off = (int32_t)cd.ctx_off;
-          r.cb = (int32_t)g.chunks;
-          r.sb = (int32_t)g.stats_blocks;
-          ARRow q{b.val_off, order[(size_t)fi].pt0, cd.idx_off, b.n * b.c, (int32_t)g.quant_blocks, b.c, b.bpv, 0, {0, 0, 0, 0}};
-          for (int ch = 0; ch < 4; ++ch) q.q[ch] = lad[(size_t)fi].steps[rung][ch];
-          cand.push_back(cd);
-          crow.push_back(r);
-          qrow.push_back(q);
-          g.chunks += b.nc;
-          g.stats_blocks += b.sn;
-          g.quant_blocks += nblk(b.n * b.c, 256);
-          chunks_used += b.nc;
-          ctxs_used += b.nctx;
-          idx_at += pcc_align((size_t)b.n * b.c * 2) / 2;
-          rec_at += pcc_align((size_t)b.nc * kLanes * b.T * 2) / 2;
-        }
-        scr.used += bytes;
-        groups.push_back(g);
-        w = w1;
-      }
-      const size_t nr = want.size();
-      memcpy(stage + crow_at + first * sizeof(AFrame), crow.data() + first, nr * sizeof(AFrame));
-      memcpy(stage + qrow_at + first * sizeof(ARRow), qrow.data() + first, nr * sizeof(ARRow));
-      PCC_HIP(hipMemcpyAsync(d_tabs + crow_at + first * sizeof(AFrame), stage + crow_at + first * sizeof(AFrame), nr * sizeof(AFrame),
-                             hipMemcpyHostToDevice, st));
-      PCC_HIP(hipMemcpyAsync(d_tabs + qrow_at + first * sizeof(ARRow), stage + qrow_at + first * sizeof(ARRow), nr * sizeof(ARRow),
-                             hipMemcpyHostToDevice, st));
-      for (const Group& g : groups) {
-        const int n_r = (int)(g.r1 - g.r0);
-        hipLaunchKernelGGL(k_ar_quant, dim3((unsigned)g.quant_blocks), dim3(256), 0, st, d_qrow + g.r0, n_r, (const int32_t*)hh,
-                           (const uint2*)wts, scratch);
-        PCC_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_a_stats<false>, dim3((unsigned)g.stats_blocks), dim3(256), 0, st, (const uint16_t*)scratch, d_crow + g.r0, n_r, cnt);
-        PCC_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_a_enc<false>, dim3((unsigned)g.chunks), dim3(64), lds, st, (const uint16_t*)scratch, d_crow + g.r0, n_r,
-                           (const uint32_t*)cnt, scratch, scratch + g.rec_words, states + g.cb * 2 * kLanes, lens_d + g.cb * kLanes,
-                           words + g.cb, p0);
-        PCC_CHECK_LAUNCH();
-      }
-      return PCC_OK;
-    };
-    // the lengths of the rows cand[first ..): one read-back of their chunks' words, one synchronisation
-    auto read_lens = [&](size_t first) -> int {
-      if (first == cand.size()) return PCC_OK;
-      const int64_t c0 = cand[first].cb;
-      PCC_HIP(hipMemcpyAsync((void*)(h_words + c0), words + c0, (size_t)(chunks_used - c0) * 4, hipMemcpyDeviceToHost, st));
-      PCC_HIP(hipStreamSynchronize(st));
-      for (size_t i = first; i < cand.size(); ++i) {
-        const AFrame& b = tab[(size_t)cand[i].fi];
-        int64_t w = 0;
-        for (int64_t k = 0; k < b.nc; ++k) w += ((volatile const uint32_t*)h_words)[cand[i].cb + k];
-        cand[i].len = a_head_bytes(kind, b.c, b.nctx, b.nc) + 2 * w;
-      }
-      return PCC_OK;
-    };
-
-    // stage 1: the rungs of A = { j : j % 4 == 0 } and J - 1
-    std::vector<std::pair<int, int>> want;
-    std::vector<size_t> s1_at((size_t)nf + 1);
-    for (int i = 0; i < nf; ++i) {
-      s1_at[(size_t)i] = want.size();
-      const int J = lad[(size_t)i].J;
-      for (int j = 0; j < J; j += 4) want.emplace_back(i, j);
-      if ((J - 1) % 4) want.emplace_back(i, J - 1);
-    }
-    s1_at[(size_t)nf] = want.size();
-    PCC_TRY(code_rows(want));
-    PCC_TRY(read_lens(0));
-    // the search, stage 1: win[i] = the frame's row where it is decided; else stage 2 codes the rungs inside (a', a)
-    std::vector<int64_t> win((size_t)nf, -1), s2_fall((size_t)nf, -1);
-    want.clear();
-    for (int i = 0; i < nf; ++i) {
-      const int64_t B = h_target[frame_of[(size_t)i]];
-      size_t a = s1_at[(size_t)i];
-      while (a < s1_at[(size_t)i + 1] && cand[a].len > B) ++a;
-      if (a == s1_at[(size_t)i + 1]) win[(size_t)i] = (int64_t)a - 1;   // nothing fits: rung J - 1, over its target
-      else if (a == s1_at[(size_t)i] || cand[a].rung - cand[a - 1].rung == 1) win[(size_t)i] = (int64_t)a;
-      else {
-        s2_fall[(size_t)i] = (int64_t)a;
-        for (int j = cand[a - 1].rung + 1; j < cand[a].rung; ++j) want.emplace_back(i, j);
-      }
-    }
-    if (!want.empty()) {
-      const size_t s2 = cand.size();
-      PCC_TRY(code_rows(want));
-      PCC_TRY(read_lens(s2));
-      for (size_t r = s2; r < cand.size(); ++r) {
-        const int i = cand[r].fi;
-        if (win[(size_t)i] < 0 && cand[r].len <= h_target[frame_of[(size_t)i]]) win[(size_t)i] = (int64_t)r;
-      }
-      for (int i = 0; i < nf; ++i)
-        if (win[(size_t)i] < 0) win[(size_t)i] = s2_fall[(size_t)i];
-    }
-    // the winners whose word regions the scratch block no longer holds are coded once more, in groups as above; every
-    // group of winners is assembled (k_ar_gather, k_a_pack) before the next one may take the block
-    std::vector<int> held, lost;
-    for (int i = 0; i < nf; ++i) (cand[(size_t)win[(size_t)i]].epoch == scr.epoch ? held : lost).push_back(i);
-    std::vector<AFrame> wrow;
-    std::vector<ARPick> picks;
-    std::vector<int32_t> waux;
-    struct Batch {
-      int r0, r1;          // winners' rows [r0, r1) of the pack tables
-      int64_t cb, chunks;  // their chunks in the winners' small arrays
-      int64_t nc_max;
-    };
-    std::vector<Batch> batches;
-    int64_t wchunks = 0;
-    auto add_batch = [&](const std::vector<int>& frames, const std::vector<int64_t>& rows) {
-      Batch b{(int)wrow.size(), (int)(wrow.size() + frames.size()), wchunks, 0, 0};
-      for (size_t k = 0; k < frames.size(); ++k) {
-        const ARCand& cd = cand[(size_t)rows[k]];
-        AFrame r = tab[(size_t)frames[k]];
-        r.e = tc ? kind.e : lad[(size_t)cd.fi].steps[cd.rung][0];
-        r.rec_off = cd.work_off;
-        r.ctx_off = (int32_t)cd.ctx_off;
-        r.cb = (int32_t)b.chunks;
-        picks.push_back(ARPick{(int32_t)cd.cb, (int32_t)(b.cb + b.chunks), r.nc, 0});
-        for (int ch = 0; ch < 4; ++ch) waux.push_back(lad[(size_t)cd.fi].steps[cd.rung][ch]);
-        waux.push_back(colour);
-        wrow.push_back(r);
-        b.chunks += r.nc;
-        b.nc_max = std::max<int64_t>(b.nc_max, r.nc);
-        rung_of[(size_t)frame_of[(size_t)frames[k]]] = cd.rung;
-      }
-      wchunks += b.chunks;
-      batches.push_back(b);
-    };
-    auto pack_batch = [&](const Batch& b) -> int {
-      const int n_r = b.r1 - b.r0;
-      const AFrame* d_wrow = (const AFrame*)(d_tabs + wrow_at) + b.r0;
-      hipLaunchKernelGGL(k_ar_gather, dim3(nblk(b.nc_max * 2 * kLanes, 256), (unsigned)n_r), dim3(256), 0, st,
-                         (const ARPick*)(d_tabs + pick_at) + b.r0, (const uint32_t*)words, (const uint16_t*)states, (const uint16_t*)lens_d,
-                         wwords, wstates, wlens);
-      PCC_CHECK_LAUNCH();
-      const unsigned blocks = (unsigned)(b.chunks + n_r);
-      if (tc)
-        hipLaunchKernelGGL((k_a_pack<false, true, false, true, const int32_t*>), dim3(blocks), dim3(256), 0, st, (const uint16_t*)scratch, d_wrow,
-                           n_r, (const uint16_t*)(wstates + b.cb * 2 * kLanes), (const uint16_t*)(wlens + b.cb * kLanes),
-                           (const uint32_t*)(wwords + b.cb), (const uint16_t*)p0, stage + tab_b, len_dev + b.r0, (const uint32_t*)nullptr,
-                           key_shift / 3, (const int32_t*)nullptr, (const int32_t*)(d_tabs + waux_at) + 5 * b.r0);
-      else
-        hipLaunchKernelGGL((k_a_pack<false, true, false, true>), dim3(blocks), dim3(256), 0, st, (const uint16_t*)scratch, d_wrow, n_r,
-                           (const uint16_t*)(wstates + b.cb * 2 * kLanes), (const uint16_t*)(wlens + b.cb * kLanes),
-                           (const uint32_t*)(wwords + b.cb), (const uint16_t*)p0, stage + tab_b, len_dev + b.r0, (const uint32_t*)nullptr,
-                           key_shift / 3, (const int32_t*)nullptr);
-      PCC_CHECK_LAUNCH();
-      return PCC_OK;
-    };
-    auto send_winners = [&](size_t r0) -> int {   // the pack tables' rows [r0, ..) to the device
-      const size_t n_r = wrow.size() - r0;
-      memcpy(stage + wrow_at + r0 * sizeof(AFrame), wrow.data() + r0, n_r * sizeof(AFrame));
-      memcpy(stage + waux_at + r0 * 20, waux.data() + 5 * r0, n_r * 20);
-      memcpy(stage + pick_at + r0 * sizeof(ARPick), picks.data() + r0, n_r * sizeof(ARPick));
-      PCC_HIP(hipMemcpyAsync(d_tabs + wrow_at + r0 * sizeof(AFrame), stage + wrow_at + r0 * sizeof(AFrame), n_r * sizeof(AFrame),
-                             hipMemcpyHostToDevice, st));
-      PCC_HIP(hipMemcpyAsync(d_tabs + waux_at + r0 * 20, stage + waux_at + r0 * 20, n_r * 20, hipMemcpyHostToDevice, st));
-      PCC_HIP(hipMemcpyAsync(d_tabs + pick_at + r0 * sizeof(ARPick), stage + pick_at + r0 * sizeof(ARPick), n_r * sizeof(ARPick),
-                             hipMemcpyHostToDevice, st));
-      return PCC_OK;
-    };
-    std::vector<int> win_row_of;   // the frame (with points) behind every row of the pack tables
-    if (!held.empty()) {
-      std::vector<int64_t> rows;
-      for (int i : held) rows.push_back(win[(size_t)i]);
-      add_batch(held, rows);
-      win_row_of = held;
-      PCC_TRY(send_winners(0));
-      PCC_TRY(pack_batch(batches.back()));
-    }
-    for (size_t k = 0; k < lost.size();) {
-      // as many of them as one turn of the block holds
-      size_t k1 = k, bytes = 0;
-      while (k1 < lost.size() && bytes + row_need(tab[(size_t)lost[k1]]) <= scr.cap) bytes += row_need(tab[(size_t)lost[k1++]]);
-      scr.used = scr.cap;   // this group starts the block over
-      want.clear();
-      std::vector<int> frames(lost.begin() + (long)k, lost.begin() + (long)k1);
-      for (int i : frames) want.emplace_back(i, cand[(size_t)win[(size_t)i]].rung);
-      const size_t first = cand.size();
-      PCC_TRY(code_rows(want));
-      std::vector<int64_t> rows;
-      for (size_t r = first; r < cand.size(); ++r) rows.push_back((int64_t)r);
-      const size_t w0 = wrow.size();
-      add_batch(frames, rows);
-      win_row_of.insert(win_row_of.end(), frames.begin(), frames.end());
-      PCC_TRY(send_winners(w0));
-      PCC_TRY(pack_batch(batches.back()));
-      k = k1;
-    }
-    PCC_HIP(hipStreamSynchronize(st));
-    for (size_t r = 0; r < win_row_of.size(); ++r) {
-      const int i = win_row_of[r], f = frame_of[(size_t)i];
-      const long long total = ((volatile long long*)len_dev)[r];
-      PCC_REQUIRE(total >= 0 && total <= tab[(size_t)i].out_cap, PCC_E_NOMEM, "%s: frame %d: blob beyond its bound", who, f);
-      len_of[(size_t)f] = total;
-      off_of[(size_t)f] = (int64_t)tab_b + tab[(size_t)i].out_off;
-    }
+    c.st = ctx->stream;
+    PCC_TRY(a_r_setup(c, scratch_limit));
+    PccProfScope prof(ctx, "attr_encode_rate", pl.u, nf, c.rows_max, 0);
+    PCC_TRY(a_r_lift(c, d_values, d_perm, d_run_starts, n_unique, d_keys));
+    std::vector<int64_t> win;
+    PCC_TRY(a_r_search(c, h_target, &win));
+    PCC_TRY(a_r_pack_winners(c, win, key_shift, &rung_of));
+    PCC_HIP(hipStreamSynchronize(c.st));
+    for (size_t r = 0; r < c.win_row_of.size(); ++r)
+      PCC_TRY(out.take(who, pl, c.win_row_of[r], ((volatile long long*)c.len_dev)[r], c.tab_b));
   }
-  int64_t total = 0;
-  for (int f = 0; f < n_frames; ++f) total += len_of[(size_t)f];
-  PCC_REQUIRE(total <= cap, PCC_E_NOMEM, "%s: %lld bytes of blobs, capacity %lld", who, (long long)total, (long long)cap);
-  h_offsets[0] = 0;
-  for (int f = 0; f < n_frames; ++f) {
-    uint8_t* dst = h_out + h_offsets[f];
-    if (off_of[(size_t)f] >= 0) {
-      memcpy(dst, (const uint8_t*)ctx->stage + off_of[(size_t)f], (size_t)len_of[(size_t)f]);
-    } else {   // no points: the 12-byte empty blob
-      memset(dst, 0, kAttrHead);
-      dst[0] = 'A';
-      dst[1] = (uint8_t)kind.version;
-      dst[2] = (uint8_t)((h_format[f] & 0xFF) | ((key_shift / 3) << 4));
-      dst[3] = (uint8_t)(h_format[f] >> 8);
-    }
-    h_offsets[f + 1] = h_offsets[f] + len_of[(size_t)f];
-    if (h_rung) h_rung[f] = rung_of[(size_t)f];
-  }
+  PCC_TRY(a_enc_emit(who, kind, ctx, h_format, n_frames, key_shift, out, h_out, cap, h_offsets));
+  for (int f = 0; h_rung && f < n_frames; ++f) h_rung[f] = rung_of[(size_t)f];
   return PCC_OK;
+}
+
+// a parser's error, named by the entry point
+static int a_wrap_error(const char* who, int rc) {
+  const std::string m = pcc_last_error();
+  pcc_set_error("%s: %s", who, m.c_str());
+  return rc;
 }
 
 // host only: the version byte and byte 3 of a head, checked: its kind, channels and mask
@@ -2595,21 +2638,13 @@ extern "C" int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_versio
     // version 22: its own parser; K through pcc_attr_scalable_to, steps and colour through pcc_attr_transform_info
     AttrSInfo o;
     const int rc = attr_s_parse(h_in, len, 0, kAttrSHead, &o, nullptr);
-    if (rc != PCC_OK) {
-      const std::string msg = pcc_last_error();
-      pcc_set_error("pcc_attr_info: %s", msg.c_str());
-      return rc;
-    }
+    if (rc != PCC_OK) return a_wrap_error("pcc_attr_info", rc);
     ver = o.version, bpv = o.bpv, c = o.c, n = o.n, slod = o.slod, scal = true;
   } else if (h_in && len >= kAttrHead && h_in[0] == 'A' && (attr_t_kind(h_in[1]) || attr_c_kind(h_in[1]))) {
     // versions 19 and 21: their own parser; q through pcc_attr_qstep, steps and colour through pcc_attr_transform_info
     AttrCInfo o;
     const int rc = attr_tc_parse(h_in, len, &o, attr_c_kind(h_in[1]) ? &o : nullptr, true);
-    if (rc != PCC_OK) {
-      const std::string msg = pcc_last_error();
-      pcc_set_error("pcc_attr_info: %s", msg.c_str());
-      return rc;
-    }
+    if (rc != PCC_OK) return a_wrap_error("pcc_attr_info", rc);
     ver = o.version, bpv = o.bpv, c = o.c, n = o.n, slod = o.slod;
   } else {
     PCC_TRY(a_head_kind("pcc_attr_info", h_in, len, &scal, &nl, &xc, &c, &m));
@@ -2938,7 +2973,7 @@ extern "C" int pcc_attr_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blob
 // Version 22, at level of detail lod (0 for the other two): the cells are those of the geometry at lod, biased by
 // 32768 >> (slod + lod); the lane decoder reads the level's prefix as version 2's does; k_as_flag and the scan behind
 // the order stage, whose counts must be the head's; k_as_lift over the sublevels of the cells' keys (47 - 3 lod .. 0),
-// each frame under its own K (the row's max_error); k_as_store over the cells
+// each frame under its own K (the row's max_error); k_ac_store over the cells
 static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
                              const int32_t* d_cells, const int64_t* h_cell_offsets, uint8_t* d_out, uint8_t* h_out, int64_t cap_bytes,
                              int64_t* h_out_offsets, int32_t* h_format, int version, int lod) {
@@ -3033,18 +3068,9 @@ static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const
   PCC_CHECK_LAUNCH();
   for (int t = kATBins - 2; t >= 0; --t) {
     if (!grid[t]) continue;
-    if (sc) {
-      hipLaunchKernelGGL(k_as_lift<false>, dim3(grid[t], (unsigned)nf), dim3(256), 0, st, (const uint64_t*)keys, d_ord, (const uint32_t*)bins,
-                         (const uint32_t*)inv, t, g, 3 * lod, (const AFrame*)nullptr, (uint16_t*)nullptr, (uint16_t*)nullptr, d_tab,
-                         (const uint8_t*)x, val, status, d_aux);
-      PCC_CHECK_LAUNCH();
-    } else {
-      PCC_TRY(a_launch_lift<false>(st, grid[t], nf, keys, d_ord, bins, inv, t, nullptr, nullptr, nullptr, d_tab, x, val, status, d_aux));
-    }
+    PCC_TRY(a_launch_lift<false>(st, grid[t], nf, keys, d_ord, bins, inv, t, nullptr, nullptr, nullptr, d_tab, x, val, status, d_aux, g, 3 * lod));
   }
-  if (sc)
-    hipLaunchKernelGGL(k_as_store, dim3(nblk(d.n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, d_aux, (const int64_t*)val, d.out);
-  else if (any_colour)
+  if (sc || any_colour)
     hipLaunchKernelGGL(k_ac_store, dim3(nblk(d.n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, d_aux, (const int64_t*)val, d.out);
   else
     hipLaunchKernelGGL(k_at_store, dim3(nblk(vals_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, (const int64_t*)val, d.out);
@@ -3056,33 +3082,22 @@ static int a_t_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const
 extern "C" int pcc_attr_lod_info(const uint8_t* h_in, int64_t len, int lod, int64_t* h_bytes, int64_t* h_values) {
   PCC_REQUIRE(lod >= 0 && lod <= kAttrMaxLod, PCC_E_ARG, "pcc_attr_lod_info: level of detail %d outside 0 .. %d", lod, kAttrMaxLod);
   PCC_REQUIRE(h_in && len >= 2 && h_in[0] == 'A', PCC_E_STREAM, "pcc_attr_lod_info: not an attribute blob (len=%lld)", (long long)len);
-  bool scal = false, nl = false, xc = false;
+  Attr2Plan pl;
+  int rc;
   if (attr_s_kind(h_in[1])) {   // version 22: its own parser, version 2's plan; a level above its K is PCC_E_ARG
     AttrSInfo o;
-    Attr2Plan pl;
-    const int rc = attr_s_parse(h_in, len, lod, kAttrSPlan, &o, &pl);
-    if (rc != PCC_OK) {
-      const std::string m = pcc_last_error();
-      pcc_set_error("pcc_attr_lod_info: %s", m.c_str());
-      return rc;
-    }
-    if (h_bytes) *h_bytes = pl.bytes;
-    if (h_values) *h_values = pl.m;
-    return PCC_OK;
+    rc = attr_s_parse(h_in, len, lod, kAttrSPlan, &o, &pl);
+  } else {
+    bool scal = false, nl = false, xc = false;
+    PCC_REQUIRE(!attr_t_kind(h_in[1]) && !attr_c_kind(h_in[1]), PCC_E_ARG,
+                "pcc_attr_lod_info: attribute blob version %d (a transform-coded blob has no level-of-detail prefixes: the weights of its "
+                "transform need every point)", (int)h_in[1]);
+    PCC_REQUIRE(attr_kind(h_in[1], &scal, &nl, &xc) && scal, PCC_E_ARG,
+                "pcc_attr_lod_info: attribute blob version %d (levels of detail are a property of version 2)", (int)h_in[1]);
+    Attr2Info o;
+    rc = attr2_parse_kind(h_in, len, lod, false, nl, &o, &pl, xc);
   }
-  PCC_REQUIRE(!attr_t_kind(h_in[1]) && !attr_c_kind(h_in[1]), PCC_E_ARG,
-              "pcc_attr_lod_info: attribute blob version %d (a transform-coded blob has no level-of-detail prefixes: the weights of its "
-              "transform need every point)", (int)h_in[1]);
-  PCC_REQUIRE(attr_kind(h_in[1], &scal, &nl, &xc) && scal, PCC_E_ARG,
-              "pcc_attr_lod_info: attribute blob version %d (levels of detail are a property of version 2)", (int)h_in[1]);
-  Attr2Info o;
-  Attr2Plan pl;
-  const int rc = attr2_parse_kind(h_in, len, lod, false, nl, &o, &pl, xc);
-  if (rc != PCC_OK) {
-    const std::string m = pcc_last_error();
-    pcc_set_error("pcc_attr_lod_info: %s", m.c_str());
-    return rc;
-  }
+  if (rc != PCC_OK) return a_wrap_error("pcc_attr_lod_info", rc);
   if (h_bytes) *h_bytes = pl.bytes;
   if (h_values) *h_values = pl.m;
   return PCC_OK;

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import attr_rate_ref as R
+import attr_ref as A
 from conftest import ROOT, pkg, random_cloud
 
 
@@ -177,6 +178,76 @@ def test_small_frames_in_one_call(geo):
     assert rungs[0] == 0 and rungs[3] == -1
     rungs, _ = o.check([one - 1, 10 ** 6, o.length(2, 13), 50, o.length(4, 2)])
     assert rungs[0] == o.J - 1 and rungs[1] == 0 and rungs[3] == -1
+
+
+def _check_with_rungs(o, targets, monkeypatch):
+    """o.check(targets), and the rungs the library itself reported for the call"""
+    got = []
+    real = o.geo.rt.attr_encode_frames_rate
+
+    def record(*a, **k):
+        blobs, rungs = real(*a, **k)
+        got.append(list(rungs))
+        return blobs, rungs
+
+    with monkeypatch.context() as m:
+        m.setattr(o.geo.rt, "attr_encode_frames_rate", record)
+        want, (gb, ab) = o.check(targets)
+    assert got == [want], (got, want)
+    return want, ab
+
+
+def _row_need(n, c, bpv):
+    """scratch bytes of one candidate row: its indices and its two regions of one word per decision, each on 256 bytes"""
+    S, nc = A.layout(n, c)
+    words = nc * A.LANES * S * c * A.positions(bpv)
+    return -(-n * c * 2 // 256) * 256 + 2 * (-(-words * 2 // 256) * 256)
+
+
+@pytest.mark.gpu
+def test_small_frames_under_a_scratch_limit(geo, monkeypatch):
+    """test_small_frames_in_one_call's frames with the candidate rows in groups: an empty frame between frames whose
+    winners are coded once more"""
+    rng = np.random.default_rng(77)
+    dtype = np.dtype(np.uint8)
+    frames = [_cloud(rng, 1), _cloud(rng, 2), _cloud(rng, 64), np.zeros((0, 3), np.int32), _cloud(rng, 65)]
+    attrs = [_colour(rng, len(p), 3, dtype) for p in frames]
+    o = _Oracle(geo, frames, attrs, (4, 8, 8), colour="ycocg")
+    one = o.length(0, 0)
+    lists = [[one, o.length(1, 9), o.length(2, 6), 1, o.length(4, 19)], [one - 1, 10 ** 6, o.length(2, 13), 50, o.length(4, 2)]]
+    # a row's scratch from its frame's distinct points; twice the largest row's: every group holds two rows or more,
+    # and stage 1 alone (its rungs for each of the four frames with points) needs several times as much
+    need = [_row_need(len(np.unique(p, axis=0)), 3, 1) for p in frames if len(p)]
+    middle = 2 * max(need)
+    assert middle < len(R.stage1(o.J)) * sum(need) // 2
+    want = [_check_with_rungs(o, targets, monkeypatch) for targets in lists]
+    assert [w[0][3] for w in want] == [-1, -1] and want[0][0][0] == 0 and want[1][0][0] == o.J - 1
+    try:
+        for limit in (1, middle):
+            geo.rate_scratch_limit = limit
+            for targets, (rungs, blobs) in zip(lists, want):
+                assert _check_with_rungs(o, targets, monkeypatch) == (rungs, blobs), limit
+    finally:
+        geo.rate_scratch_limit = 0
+
+
+@pytest.mark.gpu
+def test_two_chunks_under_a_scratch_limit_between_empty_frames(geo, monkeypatch):
+    """test_four_channels_across_the_chunk_boundary's frame with a frame without points in front of it and behind it"""
+    rng = np.random.default_rng(78)
+    empty = np.zeros((0, 3), np.int32)
+    frames = [empty, _cloud(rng, 8193), empty]
+    attrs = [np.zeros((0, 4), np.uint8), _colour(rng, 8193, 4, np.dtype(np.uint8)), np.zeros((0, 4), np.uint8)]
+    o = _Oracle(geo, frames, attrs, (4, 8, 8, 16), colour="ycocg")
+    assert o.J == 21
+    try:
+        for limit in (1, 0):
+            geo.rate_scratch_limit = limit
+            for k in (7, 20):
+                rungs, ab = _check_with_rungs(o, [1, o.length(1, k), 10 ** 6], monkeypatch)
+                assert rungs == [-1, k, -1] and len(ab[0]) == len(ab[2]) == 12, (limit, k, rungs)
+    finally:
+        geo.rate_scratch_limit = 0
 
 
 @pytest.mark.gpu
