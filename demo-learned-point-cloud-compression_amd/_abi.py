@@ -34,6 +34,11 @@ class PccCloudInfo(C.Structure):
                 ("q_g", C.c_double), ("q_a", C.c_double)]
 
 
+# what every attribute encode entry point begins with: ctx, values, value offsets, formats, row offsets, points, n_frames,
+# perm, run starts, n_unique; _AEV with the blob version behind ctx
+_AE = [vp, vp, pi64, pi32, pi64, pi64, i32, vp, vp, i64]
+_AEV = _AE[:1] + [i32] + _AE[1:]
+
 # name -> (restype, argtypes); every symbol declared in include/pcc.h
 PROTOTYPES = {
     "pcc_codec_create": (vp, [vp, C.c_size_t, i32, vp]),
@@ -80,32 +85,28 @@ PROTOTYPES = {
     "pcc_morton_keys_frames_f32": (i32, [vp, vp, i64, vp, i32, f32, pf32, i32, vp, vp]),
     "pcc_rows_index": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, i32, vp]),
     "pcc_points_to_metric": (i32, [vp, vp, i64, i32, f32, pf32, vp]),
-    "pcc_attr_encode_frames_kept": (i32, [vp, i32, vp, pi64, pi32, pi64, pi64, i32, vp, vp, i64, i64, vp, i32, vp, i64, pi64]),
+    "pcc_attr_encode_frames_kept": (i32, _AEV + [i64, vp, i32, vp, i64, pi64]),
     "pcc_octree_encode_frames": (i32, [vp, vp, i64, i32, i32, vp, i64, pi64]),
     "pcc_octree_decode_frames": (i32, [vp, C.POINTER(C.c_void_p), pi64, i32, vp, vp, i64, pi64]),
     "pcc_octree_decode_frames_lod": (i32, [vp, C.POINTER(C.c_void_p), pi64, i32, i32, vp, vp, i64, pi64]),
     "pcc_octree_lod_info": (i32, [vp, i64, i32, pi64, pi64]),
-    "pcc_attr_encode_frames": (i32, [vp, vp, pi64, pi32, pi64, pi64, i32, vp, vp, i64, vp, i64, pi64]),
+    "pcc_attr_encode_frames": (i32, _AE + [vp, i64, pi64]),
     "pcc_attr_decode_frames": (i32, [vp, C.POINTER(C.c_void_p), pi64, i32, pi64, vp, vp, i64, pi64, pi32]),
     "pcc_attr_lod_info": (i32, [vp, i64, i32, pi64, pi64]),
-    "pcc_attr_encode_frames_v2": (i32, [vp, vp, pi64, pi32, pi64, pi64, i32, vp, vp, i64, vp, i32, vp, i64, pi64]),
+    "pcc_attr_encode_frames_v2": (i32, _AE + [vp, i32, vp, i64, pi64]),
     "pcc_attr_decode_frames_lod": (i32, [vp, C.POINTER(C.c_void_p), pi64, i32, i32, vp, pi64, vp, vp, i64, pi64, pi32]),
-    "pcc_attr_encode_frames_nl": (i32, [vp, i32, vp, pi64, pi32, pi64, pi64, i32, vp, vp, i64, i64, vp, i32, i32, vp, i64, pi64]),
+    "pcc_attr_encode_frames_nl": (i32, _AEV + [i64, vp, i32, i32, vp, i64, pi64]),
     "pcc_attr_info": (i32, [vp, i64, pi32, pi32, pi32, pi64, pi32, pi32, pi32]),
-    "pcc_attr_encode_frames_cross": (i32, [vp, i32, vp, pi64, pi32, pi64, pi64, i32, vp, vp, i64, i64, vp, i32, i32, pi32, vp, i64,
-                                           pi64]),
+    "pcc_attr_encode_frames_cross": (i32, _AEV + [i64, vp, i32, i32, pi32, vp, i64, pi64]),
     "pcc_attr_cross_mask": (i32, [vp, i64, pi32]),
-    "pcc_attr_encode_frames_transform": (i32, [vp, vp, pi64, pi32, pi64, pi64, i32, vp, vp, i64, i64, vp, i32, i32, vp, i64, pi64]),
+    "pcc_attr_encode_frames_transform": (i32, _AE + [i64, vp, i32, i32, vp, i64, pi64]),
     "pcc_attr_qstep": (i32, [vp, i64, pi32]),
-    "pcc_attr_encode_frames_transform2": (i32, [vp, vp, pi64, pi32, pi64, pi64, i32, vp, vp, i64, i64, vp, i32, pi32, i32, vp, i64,
-                                                pi64]),
+    "pcc_attr_encode_frames_transform2": (i32, _AE + [i64, vp, i32, pi32, i32, vp, i64, pi64]),
     "pcc_attr_transform_info": (i32, [vp, i64, pi32, pi32]),
-    "pcc_attr_encode_frames_transform3": (i32, [vp, vp, pi64, pi32, pi64, pi64, i32, vp, vp, i64, i64, vp, i32, pi32, i32, i32, vp,
-                                                i64, pi64]),
+    "pcc_attr_encode_frames_transform3": (i32, _AE + [i64, vp, i32, pi32, i32, i32, vp, i64, pi64]),
     "pcc_attr_scalable_to": (i32, [vp, i64, pi32]),
     "pcc_attr_rate_ladder": (i32, [pi32, i32, i32, pi32, pi32]),
-    "pcc_attr_encode_frames_rate": (i32, [vp, vp, pi64, pi32, pi64, pi64, i32, vp, vp, i64, i64, vp, i32, pi32, i32, i32, pi64, i64,
-                                          vp, i64, pi64, pi32]),
+    "pcc_attr_encode_frames_rate": (i32, _AE + [i64, vp, i32, pi32, i32, i32, pi64, i64, vp, i64, pi64, pi32]),
     "pcc_nn_frames": (i32, [vp, vp, i64, vp, i64, i32, vp, vp, vp]),
     "pcc_nn_attr_sse_frames": (i32, [vp, vp, vp, i64, vp, vp, i64, i32, i32, i32, vp]),
     "pcc_nn_replay_host": (i32, [vp, i64, vp, i64, vp, vp, vp]),

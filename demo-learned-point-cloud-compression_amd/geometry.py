@@ -113,7 +113,7 @@ import numpy as np
 import torch
 
 from ._abi import check, PccError, PCC_E_RANGE
-from .runtime import Runtime, _ptr, ATTR_RUN_KINDS, ATTR_TRANSFORM_KINDS, ATTR_SCALABLE_TRANSFORM_KIND
+from .runtime import Runtime, AttrCoding, _ptr, ATTR_RUN_KINDS, ATTR_TRANSFORM_KINDS, ATTR_SCALABLE_TRANSFORM_KIND
 
 MAX_FRAMES = 65535      # the batch-index range of pcc_morton_keys
 MAX_LOD = 15            # levels of detail 0 .. 15 (csrc/octree2_blob.h)
@@ -128,6 +128,17 @@ def _split(whole, sizes):
     """the rows of a call, frame behind frame -> one view of `whole` per frame"""
     ends = _ends(sizes)
     return [whole[a:b] for a, b in zip(ends[:-1], ends[1:])]
+
+
+def _frames_out(rt, whole, sizes, to_host):
+    """the rows of a call in one device tensor -> one view per frame: of that tensor, or (to_host) of one pinned host
+    copy of it, behind one rt.sync()"""
+    if to_host:
+        host = torch.empty(whole.shape, dtype=whole.dtype, pin_memory=True)
+        host.copy_(whole, non_blocking=True)
+        whole = host.numpy()
+    rt.sync()      # the host copy is complete; a device result may be read from the caller's stream at once
+    return _split(whole, sizes)
 
 
 class QstepLengthError(ValueError, TypeError):
@@ -511,7 +522,6 @@ class GeometryCodec:
         [n_f], index[f][i] the row of decompress(blobs)[f] that input row i became (duplicates share a row; with lod = k
         the row of the cell), -1 for a dropped row; numpy arrays for host frames, device tensors for device frames."""
         lod = self._check_lod(lod)
-        version = 2 if scalable else 1
         frames, is_float, on_device = self._check_frames(frames)
         if invalid not in ("raise", "drop"):
             raise ValueError(f"invalid must be 'raise' or 'drop', got {invalid!r}")
@@ -522,15 +532,11 @@ class GeometryCodec:
         elif voxel is not None:
             raise ValueError("voxel= with integer frames: they are on the lattice already")
         attrs = None if attributes is None else self._check_attributes(frames, attributes)
-        max_error = self._check_max_error(max_error, attrs)
-        cross = self._check_cross(cross_channel, attrs)
-        qstep, steps, colour = self._check_colour(qstep, colour, attrs, max_error, scalable, cross)
-        steps, scalable_to = self._check_scalable_to(scalable_to, lod, qstep, steps, attrs, max_error, scalable, cross)
-        targets, whole = self._check_rate(target_bytes, target_frame_bytes, len(frames), qstep, scalable_to)
-        if steps is not None:      # versions 21 and 22: the steps travel where the one step did
-            qstep = (steps, colour, scalable_to)
-        rate = None if targets is None else (targets, whole, int(self.rate_scratch_limit))
         nb = len(frames)
+        coding = self._attr_coding(attrs, nb, lod, scalable, max_error, cross_channel, qstep, colour, scalable_to, target_bytes,
+                                   target_frame_bytes)
+        if coding is not None and coding.targets is not None:
+            coding = coding._replace(scratch_limit=int(self.rate_scratch_limit))
 
         def result(blobs, attr_blobs=None, index=None):
             out = (blobs,) if attrs is None else (blobs, attr_blobs)
@@ -544,11 +550,13 @@ class GeometryCodec:
             front = self._front(rt, frames, is_float, on_device, caller, "GeometryCodec.compress", lod, voxel, origin,
                                 invalid == "drop")
             if front.n_keep == 0:
-                return result(*self._nothing_coded(rt, front, attrs, version, max_error, return_index, on_device, cross, qstep))
+                return result(*self._nothing_coded(rt, front, attrs, coding, return_index, on_device))
             blobs = rt.octree_encode_frames(front.keys, nb, 3 * lod)
             attr_blobs = index = None
             if attrs is not None:
-                attr_blobs = self._encode_attributes(rt, attrs, blobs, front, version, 3 * lod, max_error, cross, qstep, rate)
+                if target_frame_bytes is not None:      # what the geometry blob leaves; nothing left: a target no blob meets, the coarsest steps
+                    coding = coding._replace(targets=tuple(max(1, t - len(b)) for t, b in zip(coding.targets, blobs)))
+                attr_blobs = self._encode_attributes(rt, attrs, blobs, front, 3 * lod, coding)
             if return_index:
                 first_run = torch.empty(nb, dtype=torch.int64, pin_memory=True)
                 np.cumsum([0] + [struct.unpack_from("<I", b, 4)[0] for b in blobs[:-1]], out=first_run.numpy())
@@ -556,6 +564,23 @@ class GeometryCodec:
                                       rt.to_device(first_run), nb)
                 index = self._split_index(index, front.sizes, on_device)
             return result(blobs, attr_blobs, index)
+
+    @staticmethod
+    def _attr_coding(attrs, nb, lod, scalable, max_error, cross_channel, qstep, colour, scalable_to, target_bytes, target_frame_bytes):
+        """the attribute keywords of compress -> the AttrCoding its attribute blobs are written under, None without
+        attributes: the checkers run, and raise, with and without them.  A target is the keyword's: what a frame's
+        geometry blob takes of target_frame_bytes comes off where the blobs are known, and the codec's scratch limit is
+        compress's to add."""
+        G = GeometryCodec
+        max_error = G._check_max_error(max_error, attrs)
+        cross = G._check_cross(cross_channel, attrs)
+        qstep, steps, colour = G._check_colour(qstep, colour, attrs, max_error, scalable, cross)
+        steps, scalable_to = G._check_scalable_to(scalable_to, lod, qstep, steps, attrs, max_error, scalable, cross)
+        targets, _ = G._check_rate(target_bytes, target_frame_bytes, nb, qstep, scalable_to)
+        if attrs is None:
+            return None
+        # versions 21 and 22: a step per channel; else the one integer step of version 19, or 0
+        return AttrCoding.of(2 if scalable else 1, max_error, cross, qstep if steps is None else steps, colour, scalable_to, targets)
 
     def _front(self, rt, frames, is_float, on_device, caller, where, lod=0, voxel=None, origin=None, drop=False):
         """the frames of a call -> _Front: stage, keys, sorted / distinct.  Called under `with self._lock, self.rt`;
@@ -633,11 +658,11 @@ class GeometryCodec:
         distinct = keys if n_u.value == n_keep else rt.gather_rows(keys, rows[:n_u.value])
         return front._replace(perm=perm, sorted_keys=keys, rows=rows, n_unique=n_u.value, keys=distinct)
 
-    def _nothing_coded(self, rt, front, attrs, version, max_error, return_index, on_device, cross=None, qstep=0):
+    def _nothing_coded(self, rt, front, attrs, coding, return_index, on_device):
         """(blobs, attribute blobs, index) of a call none of whose rows is coded: the empty blobs, the attribute blobs
-        of frames without points, and -1 for every input row"""
+        of frames without points (whatever the targets), and -1 for every input row"""
         blobs = rt.octree_encode_frames(rt.empty((0,), torch.int64), front.nb)
-        attr_blobs = None if attrs is None else self._encode_attributes(rt, attrs, blobs, front, version, 0, max_error, cross, qstep)
+        attr_blobs = None if attrs is None else self._encode_attributes(rt, attrs, blobs, front, 0, coding._replace(targets=None))
         if not return_index:
             return blobs, attr_blobs, None
         index = torch.full((front.n,), -1, dtype=torch.int32, device=rt.device)
@@ -653,7 +678,7 @@ class GeometryCodec:
         return _split(index, sizes)
 
     @staticmethod
-    def _encode_attributes(rt, attrs, blobs, front, version, key_shift, max_error, cross=None, qstep=0, rate=None):
+    def _encode_attributes(rt, attrs, blobs, front, key_shift, coding):
         # the values as they come, frame by frame at 16-byte offsets, in one upload; the merge into Morton order
         # happens on the device from the sort's permutation and the runs of equal keys
         offs, at = [], 0
@@ -668,16 +693,11 @@ class GeometryCodec:
         formats = [a.dtype.itemsize | (a.shape[1] << 8) for a in attrs]
         points = [struct.unpack_from("<I", b, 4)[0] for b in blobs]
         n_kept = front.n_keep if front.n_keep < front.n else None      # None: no row was dropped
-        # versions 21 and 22: (steps, colour[, K])
-        steps, colour, to = (tuple(qstep) + (None,))[:3] if isinstance(qstep, tuple) else (qstep, None, None)
-        if rate is not None:      # a byte target: the steps from `steps` upwards that the search chooses, frame by frame
-            targets, whole, limit = rate
-            if whole:      # what the geometry blob leaves; nothing left: a target no blob meets, the coarsest steps
-                targets = [max(1, t - len(b)) for t, b in zip(targets, blobs)]
-            return rt.attr_encode_frames_rate(values, offs, formats, _ends(front.sizes), points, front.perm, front.rows, front.n_unique,
-                                              front.keys, key_shift, n_kept, steps, colour, targets, limit)[0]
-        return rt.attr_encode_frames(values, offs, formats, _ends(front.sizes), points, front.perm, front.rows, front.n_unique,
-                                     version, front.keys, key_shift, n_kept, max_error, cross, steps, colour, to)
+        call = (values, offs, formats, _ends(front.sizes), points, front.perm, front.rows, front.n_unique, front.keys, key_shift, n_kept)
+        if coding.targets is None:
+            return rt._attr_encode(coding, *call)[0]
+        # a byte target: the steps from qstep upwards that the search chooses, frame by frame, through the public binding
+        return rt.attr_encode_frames_rate(*call, coding.qstep, coding.colour, list(coding.targets), coding.scratch_limit)[0]
 
     def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0, *, voxel=None, origin=(0.0, 0.0, 0.0)):
         """version-2 blobs -> a list of int32 [n_f, 3] point sets in Morton order: numpy arrays (output="numpy") or
@@ -772,13 +792,7 @@ class GeometryCodec:
         tensor, or of one host copy of it (12 B per point, as the int32 result's)"""
         if whole is None:
             return []
-        pts = rt.points_to_metric(whole, lod, voxel, origin)
-        if output == "numpy":
-            host = torch.empty(pts.shape, dtype=torch.float32, pin_memory=True)
-            host.copy_(pts, non_blocking=True)
-            pts = host.numpy()
-        rt.sync()      # the host copy is complete; a device result may be read from the caller's stream at once
-        return _split(pts, [int(c.shape[0]) for c in cells])
+        return _frames_out(rt, rt.points_to_metric(whole, lod, voxel, origin), [int(c.shape[0]) for c in cells], output == "numpy")
 
     @staticmethod
     def _sorted_values(rt, attrs, perm, dtype, channels):
@@ -855,13 +869,7 @@ class GeometryCodec:
             # the distinct row of every input row: rows_index with no frame's rows taken off
             index = rt.rows_index(front.perm, front.n_keep, front.rows, front.n_unique, front.offsets.data_ptr(),
                                   torch.zeros(nb, dtype=torch.int64, device=rt.device), nb)
-            out = rt.gather_rows(distinct, index)
-            if output == "numpy":
-                host = torch.empty(out.shape, dtype=torch.float32, pin_memory=True)
-                host.copy_(out, non_blocking=True)
-                out = host.numpy()
-            rt.sync()      # the host copy is complete; a device result may be read from the caller's stream at once
-            return _split(out, sizes)
+            return _frames_out(rt, rt.gather_rows(distinct, index), sizes, output == "numpy")
 
     @staticmethod
     def _check_normals(frames, normals):

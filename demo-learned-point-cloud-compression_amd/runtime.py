@@ -11,6 +11,7 @@ import ctypes as C
 import os
 import struct
 import threading
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -684,28 +685,32 @@ class Runtime:
         lod = int(lod)
         if lod == 0:      # today's call, by its own name
             name = "pcc_octree_decode_frames"
-            call = lambda *a: self.lib.pcc_octree_decode_frames(self.ctx, ptrs, lens, nb, *a)
+            call = lambda *a: self.lib.pcc_octree_decode_frames(self.ctx, ptrs, lens, nb, *a, offs)
         else:
             name = "pcc_octree_decode_frames_lod"
-            call = lambda *a: self.lib.pcc_octree_decode_frames_lod(self.ctx, ptrs, lens, nb, lod, *a)
+            call = lambda *a: self.lib.pcc_octree_decode_frames_lod(self.ctx, ptrs, lens, nb, lod, *a, offs)
         bufs = [np.frombuffer(b, dtype=np.uint8) for b in blobs]
         ptrs = (C.c_void_p * nb)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
         lens = (C.c_int64 * nb)(*[b.shape[0] for b in bufs])
         offs = (C.c_int64 * (nb + 1))()
-        check(call(None, None, 0, offs), name)
-        total = offs[nb]
-        if device:
-            pts = self.empty((total, 3), torch.int32)
-            if total:
-                check(call(_ptr(pts), None, total, offs),
-                      name)
-        else:   # pinned: the library copies the points straight into it (torch's host cache keeps the pages mapped)
-            pts = torch.empty((total, 3), dtype=torch.int32, pin_memory=True).numpy()
-            if total:
-                check(call(None, _np_ptr(pts), total, offs),
-                      name)
+        pts = self._sized_output(call, name, offs, lambda total: (total, 3), torch.int32, device)
         views = [pts[offs[f]:offs[f + 1]] for f in range(nb)]
         return (views, pts) if whole else views
+
+    def _sized_output(self, call, name, offs, shape, dtype, device):
+        """the two phases of a frame decoder's output: call(None, None, 0) for the sizes, which it leaves in `offs`; then
+        shape(total) of `dtype` on the device, or pinned on the host, where the library copies straight into it (torch's
+        host cache keeps the pages mapped); then call(device output, host output, total), only if there is any -> the
+        tensor, or the numpy view of the pinned one"""
+        check(call(None, None, 0), name)
+        total = offs[len(offs) - 1]
+        if device:
+            out = self.empty(shape(total), dtype)
+        else:
+            out = torch.empty(shape(total), dtype=dtype, pin_memory=True).numpy()
+        if total:
+            check(call(_ptr(out), None, total) if device else call(None, _np_ptr(out), total), name)
+        return out
 
     def attr_encode_frames(self, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique,
                            version=1, keys=None, key_shift=0, n_kept=None, max_error=0, cross=None, qstep=0, colour=None,
@@ -731,61 +736,9 @@ class Runtime:
         decoder at a cut can form, its levels of detail 0 .. K prefixes of the blob; the library checks K.
         A byte target per frame for versions 19 and 21 is a call of its own, attr_encode_frames_rate: it takes these
         arguments and writes the blob this call writes at the steps it chooses."""
-        if version not in (1, 2):
-            raise ValueError(f"attribute blob version {version!r}: 1 or 2")
-        steps = None
-        if scalable_to is not None and isinstance(qstep, (int, np.integer)) and int(qstep) == 0:
-            raise ValueError("scalable_to (attribute blob version 22) needs qstep")
-        if colour or scalable_to is not None or not isinstance(qstep, (int, np.integer)):
-            steps = [int(qstep)] * 4 if isinstance(qstep, (int, np.integer)) else [int(q) for q in qstep]
-            if not 1 <= len(steps) <= 4:
-                raise ValueError(f"attribute blob version 21: {len(steps)} steps, at most 4")
-            steps += [0] * (4 - len(steps))
-            qstep = 1
-        max_error, qstep = int(max_error), int(qstep)
-        if qstep and (max_error or (cross is not None and any(cross))):
-            raise ValueError("qstep (attribute blob versions 19 and 21) has no near-lossless and no cross-channel form")
-        nf = len(formats)
-        cap = 0
-        for fmt, n in zip(formats, points):
-            bpv, c = fmt & 0xFF, fmt >> 8
-            cap += 96 + 2 * 80 * bpv * c + 388 * (n // 64 + 1) + 32 * bpv * c * n
-        out = np.empty(cap, dtype=np.uint8)
-        offs = (C.c_int64 * (nf + 1))()
-        head = (self.ctx, _ptr(values), (C.c_int64 * nf)(*value_offsets), (C.c_int32 * nf)(*formats),
-                (C.c_int64 * (nf + 1))(*row_offsets), (C.c_int64 * nf)(*points), nf, _ptr(perm), _ptr(run_starts), n_unique)
-        if cross is not None and len(cross) != nf:
-            raise ValueError(f"{len(cross)} cross-channel masks for {nf} frames")
-        if scalable_to is not None:
-            check(self.lib.pcc_attr_encode_frames_transform3(*head, -1 if n_kept is None else int(n_kept), _ptr(keys), int(key_shift),
-                                                             (C.c_int32 * 4)(*steps), int(colour or 0), int(scalable_to), _np_ptr(out),
-                                                             cap, offs), "pcc_attr_encode_frames_transform3")
-        elif steps is not None:
-            check(self.lib.pcc_attr_encode_frames_transform2(*head, -1 if n_kept is None else int(n_kept), _ptr(keys), int(key_shift),
-                                                             (C.c_int32 * 4)(*steps), int(colour or 0), _np_ptr(out), cap, offs),
-                  "pcc_attr_encode_frames_transform2")
-        elif qstep:
-            check(self.lib.pcc_attr_encode_frames_transform(*head, -1 if n_kept is None else int(n_kept), _ptr(keys), int(key_shift),
-                                                            qstep, _np_ptr(out), cap, offs), "pcc_attr_encode_frames_transform")
-        elif cross is not None and any(cross):
-            check(self.lib.pcc_attr_encode_frames_cross(head[0], version, *head[1:], -1 if n_kept is None else int(n_kept),
-                                                        _ptr(keys) if version == 2 else None, int(key_shift), max_error,
-                                                        (C.c_int32 * nf)(*[int(m) for m in cross]), _np_ptr(out), cap, offs),
-                  "pcc_attr_encode_frames_cross")
-        elif max_error:
-            check(self.lib.pcc_attr_encode_frames_nl(head[0], version, *head[1:], -1 if n_kept is None else int(n_kept),
-                                                     _ptr(keys) if version == 2 else None, int(key_shift), max_error,
-                                                     _np_ptr(out), cap, offs), "pcc_attr_encode_frames_nl")
-        elif n_kept is not None:
-            check(self.lib.pcc_attr_encode_frames_kept(head[0], version, *head[1:], int(n_kept), _ptr(keys) if version == 2
-                                                       else None, int(key_shift), _np_ptr(out), cap, offs),
-                  "pcc_attr_encode_frames_kept")
-        elif version == 1:
-            check(self.lib.pcc_attr_encode_frames(*head, _np_ptr(out), cap, offs), "pcc_attr_encode_frames")
-        else:
-            check(self.lib.pcc_attr_encode_frames_v2(*head, _ptr(keys), int(key_shift), _np_ptr(out), cap, offs),
-                  "pcc_attr_encode_frames_v2")
-        return [out[offs[f]:offs[f + 1]].tobytes() for f in range(nf)]
+        coding = AttrCoding.of(version, max_error, cross, qstep, colour, scalable_to)
+        return self._attr_encode(coding, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique, keys,
+                                 key_shift, n_kept)[0]
 
     def attr_encode_frames_rate(self, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique, keys,
                                 key_shift, n_kept, qstep, colour, targets, scratch_limit=0, cap=None):
@@ -796,40 +749,54 @@ class Runtime:
         frame that no rung brings under its target gets the last rung and is longer than its target.  scratch_limit
         (bytes; 0: the library's default, 1 GiB) bounds the scratch of the candidate rows; bytes and rungs do not depend
         on it.  cap: the room for the blobs (None: what attr_encode_frames takes)."""
-        per_channel = bool(colour) or not isinstance(qstep, (int, np.integer))
-        steps = [int(qstep)] * 4 if isinstance(qstep, (int, np.integer)) else [int(q) for q in qstep]
-        if not 1 <= len(steps) <= 4:
-            raise ValueError(f"attribute blob version 21: {len(steps)} steps, at most 4")
-        steps += [0] * (4 - len(steps))
-        nf = len(formats)
-        if len(targets) != nf:
-            raise ValueError(f"{len(targets)} targets for {nf} frames")
+        coding = AttrCoding.of(qstep=qstep, colour=colour, targets=targets, scratch_limit=scratch_limit)
+        return self._attr_encode(coding, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique, keys,
+                                 key_shift, n_kept, cap)
+
+    def _attr_encode(self, coding, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique, keys, key_shift,
+                     n_kept, cap=None):
+        """the one binding of the nine attribute encode entry points: the arrays of a call as attr_encode_frames takes
+        them, and the AttrCoding that says which blobs to write -> (blobs, rungs), rungs None without a byte target"""
+        c, nf = coding, len(formats)
+        if c.cross is not None and len(c.cross) != nf:
+            raise ValueError(f"{len(c.cross)} cross-channel masks for {nf} frames")
+        if c.targets is not None and len(c.targets) != nf:
+            raise ValueError(f"{len(c.targets)} targets for {nf} frames")
         if cap is None:
             cap = 0
             for fmt, n in zip(formats, points):
-                bpv, c = fmt & 0xFF, fmt >> 8
-                cap += 96 + 2 * 80 * bpv * c + 388 * (n // 64 + 1) + 32 * bpv * c * n
+                bpv, ch = fmt & 0xFF, fmt >> 8
+                cap += 96 + 2 * 80 * bpv * ch + 388 * (n // 64 + 1) + 32 * bpv * ch * n
         out = np.empty(max(int(cap), 1), dtype=np.uint8)
         offs = (C.c_int64 * (nf + 1))()
-        rungs = (C.c_int32 * nf)()
-        check(self.lib.pcc_attr_encode_frames_rate(
-            self.ctx, _ptr(values), (C.c_int64 * nf)(*value_offsets), (C.c_int32 * nf)(*formats), (C.c_int64 * (nf + 1))(*row_offsets),
-            (C.c_int64 * nf)(*points), nf, _ptr(perm), _ptr(run_starts), n_unique, -1 if n_kept is None else int(n_kept), _ptr(keys),
-            int(key_shift), (C.c_int32 * 4)(*steps), int(per_channel), int(colour or 0), (C.c_int64 * nf)(*[int(t) for t in targets]),
-            int(scratch_limit), _np_ptr(out), int(cap), offs, rungs), "pcc_attr_encode_frames_rate")
-        return [out[offs[f]:offs[f + 1]].tobytes() for f in range(nf)], list(rungs)
+        kind = c.entry(n_kept is not None)
+        versioned = kind in ("_kept", "_nl", "_cross")      # the plain family: the version behind ctx, keys for version 2 alone
+        args = [self.ctx, _ptr(values), (C.c_int64 * nf)(*value_offsets), (C.c_int32 * nf)(*formats), (C.c_int64 * (nf + 1))(*row_offsets),
+                (C.c_int64 * nf)(*points), nf, _ptr(perm), _ptr(run_starts), n_unique]
+        if versioned:
+            args.insert(1, c.version)
+        if kind == "_v2":
+            args += [_ptr(keys), int(key_shift)]
+        elif kind:
+            args += [-1 if n_kept is None else int(n_kept), None if versioned and c.version == 1 else _ptr(keys), int(key_shift)]
+        four = None if c.steps is None else (C.c_int32 * 4)(*c.four(c.steps))
+        args += {"": (), "_v2": (), "_kept": (), "_nl": (c.max_error,),
+                 "_cross": (c.max_error, None if c.cross is None else (C.c_int32 * nf)(*c.cross)),
+                 "_transform": (c.steps and c.steps[0],), "_transform2": (four, c.colour), "_transform3": (four, c.colour, c.scalable_to),
+                 "_rate": (four, int(c.per_channel), c.colour, None if c.targets is None else (C.c_int64 * nf)(*c.targets),
+                           c.scratch_limit)}[kind]
+        rungs = (C.c_int32 * nf)() if kind == "_rate" else None
+        name = "pcc_attr_encode_frames" + kind
+        check(getattr(self.lib, name)(*args, _np_ptr(out), int(cap), offs, *(() if rungs is None else (rungs,))), name)
+        return [out[offs[f]:offs[f + 1]].tobytes() for f in range(nf)], None if rungs is None else list(rungs)
 
     @staticmethod
     def attr_rate_ladder(qstep, bpv, channels):
         """the ladder of steps that a byte target walks from the base steps `qstep` (an integer, or one step per channel)
         for values of bpv bytes and `channels` channels (pcc_attr_rate_ladder, host only): a list of J tuples"""
-        steps = [int(qstep)] * 4 if isinstance(qstep, (int, np.integer)) else [int(q) for q in qstep]
-        if not 1 <= len(steps) <= 4:
-            raise ValueError(f"{len(steps)} steps, at most 4")
-        steps += [0] * (4 - len(steps))
         out = (C.c_int32 * 256)()
         J = C.c_int32(0)
-        check(_abi.lib().pcc_attr_rate_ladder((C.c_int32 * 4)(*steps), int(channels), int(bpv), out, C.byref(J)), "pcc_attr_rate_ladder")
+        check(_abi.lib().pcc_attr_rate_ladder((C.c_int32 * 4)(*AttrCoding.four(qstep)), int(channels), int(bpv), out, C.byref(J)), "pcc_attr_rate_ladder")
         return [tuple(out[4 * j + ch] for ch in range(int(channels))) for j in range(J.value)]
 
     @staticmethod
@@ -920,16 +887,7 @@ class Runtime:
             coffs = (C.c_int64 * (nb + 1))(*cell_offs)
             call = lambda *a: self.lib.pcc_attr_decode_frames_lod(self.ctx, ptrs, lens, nb, int(lod), C.c_void_p(base), coffs,
                                                                   *a, offs, fmt)
-        check(call(None, None, 0), name)
-        total = offs[nb]
-        if device:
-            out = self.empty((max(total, 16),), torch.uint8)
-            if total:
-                check(call(_ptr(out), None, total), name)
-        else:   # pinned: the library copies the values straight into it
-            out = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True).numpy()
-            if total:
-                check(call(None, _np_ptr(out), total), name)
+        out = self._sized_output(call, name, offs, lambda total: (max(total, 16),), torch.uint8, device)
         res = []
         for f in range(nb):
             bpv, c = fmt[f] & 0xFF, fmt[f] >> 8
@@ -953,6 +911,67 @@ ATTR_COLOUR_KIND = 21
 ATTR_TRANSFORM_KINDS = (ATTR_TRANSFORM_KIND, ATTR_COLOUR_KIND)
 # version 21 under weights a decoder at a cut can form: decodes at lod 0 .. its scalable_to, from prefixes
 ATTR_SCALABLE_TRANSFORM_KIND = 22
+
+class AttrCoding(NamedTuple):
+    """What kind of attribute blob an encode call writes, resolved and normalised once: what travels from
+    GeometryCodec.compress to the one binding of the encode entry points, Runtime._attr_encode."""
+    version: int = 1               # 1 or 2: the plain family (2: coarser levels of detail are prefixes)
+    max_error: int = 0             # e > 0: the near-lossless kind of that version
+    cross: tuple = None            # one cross-channel mask per frame, or None
+    steps: tuple = None            # transform-coded: 1 to 4 quantiser steps, an integer step four times; None: not
+    per_channel: bool = False      # False: the one integer step of version 19; True: versions 21 / 22, a step per channel
+    colour: int = 0                # 1: the luma / chroma transform in front of the lift
+    scalable_to: int = None        # K: version 22, levels of detail 0 .. K are prefixes
+    targets: tuple = None          # a byte target per frame: the steps are the finest the search may choose
+    scratch_limit: int = 0         # bytes of scratch for the candidates of a byte target; 0: the library's default
+
+    @staticmethod
+    def four(qstep, what=""):
+        """the four steps the library takes: an integer serves all four channels, a sequence is padded with zeros to 4"""
+        steps = [int(qstep)] * 4 if isinstance(qstep, (int, np.integer)) else [int(q) for q in qstep]
+        if not 1 <= len(steps) <= 4:
+            raise ValueError(f"{what}{len(steps)} steps, at most 4")
+        return steps + [0] * (4 - len(steps))
+
+    @classmethod
+    def of(cls, version=1, max_error=0, cross=None, qstep=0, colour=None, scalable_to=None, targets=None, scratch_limit=0):
+        """the record of the loose keywords of Runtime.attr_encode_frames and attr_encode_frames_rate; what contradicts
+        itself raises ValueError here, what needs the number of frames in Runtime._attr_encode"""
+        if version not in (1, 2):
+            raise ValueError(f"attribute blob version {version!r}: 1 or 2")
+        one = isinstance(qstep, (int, np.integer))      # one integer step
+        if scalable_to is not None and one and int(qstep) == 0:
+            raise ValueError("scalable_to (attribute blob version 22) needs qstep")
+        per_channel = bool(colour) or scalable_to is not None or not one
+        steps = None
+        if per_channel or int(qstep) or targets is not None:
+            steps = tuple(cls.four(qstep, "attribute blob version 21: ")[:4 if one else len(qstep)])
+        if steps is not None and (int(max_error) or (cross is not None and any(cross))):
+            raise ValueError("qstep (attribute blob versions 19 and 21) has no near-lossless and no cross-channel form")
+        return cls(version, int(max_error), None if cross is None else tuple(int(m) for m in cross), steps, per_channel,
+                   int(colour or 0), None if scalable_to is None else int(scalable_to),
+                   None if targets is None else tuple(int(t) for t in targets), int(scratch_limit))
+
+    @property
+    def qstep(self):
+        """the qstep keyword that gives these steps"""
+        return 0 if self.steps is None else self.steps if self.per_channel else self.steps[0]
+
+    def entry(self, dropped):
+        """which of the nine entry points codes this record, as the suffix of pcc_attr_encode_frames; `dropped`: the call
+        left rows out (n_kept).  The first match wins."""
+        for hit, kind in ((self.targets is not None, "_rate"),
+                          (self.scalable_to is not None, "_transform3"),
+                          (self.steps is not None and self.per_channel, "_transform2"),
+                          (self.steps is not None, "_transform"),
+                          (self.cross is not None and any(self.cross), "_cross"),      # all masks 0: the plain kinds below
+                          (self.max_error, "_nl"),
+                          (dropped, "_kept"),
+                          (self.version == 1, "")):
+            if hit:
+                return kind
+        return "_v2"
+
 
 OCTREE_V2_MIN_LEAVES = 65536     # include/pcc.h PCC_OCTREE_V2_MIN_LEAVES
 OCTREE_V3_MIN_LEAVES = 8192      # include/pcc.h PCC_OCTREE_V3_MIN_LEAVES

@@ -301,7 +301,7 @@ def test_mixed_kinds_and_refusals(batches):
         front = geo._front(rt, geo._check_frames(frames[:2])[0], False, False, None, "test")
         for a, steps, colour in ((attrs[:2], [5, 0, 5], 0), (attrs[:2], [5, 128, 5], 1), (attrs[:2], [5, 5, 5], 2), (two, [5, 5], 1)):
             with pytest.raises(abi.PccError) as e:
-                G._encode_attributes(rt, a, gb[:2], front, 1, 0, 0, None, (steps, colour))
+                G._encode_attributes(rt, a, gb[:2], front, 0, pkg("runtime").AttrCoding.of(qstep=steps, colour=colour))
             assert e.value.code == abi.PCC_E_ARG and ("frame 0" in str(e.value) or colour == 2), str(e.value)
 
 

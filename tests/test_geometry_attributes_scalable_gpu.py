@@ -265,7 +265,7 @@ def test_mixed_kinds_and_refusals(geo):
         front = geo._front(rt, geo._check_frames(frames[:2])[0], False, False, None, "test")
         for key_shift, K in ((0, 0), (0, 16), (3 * 11, 5)):
             with pytest.raises(abi.PccError) as e:
-                G._encode_attributes(rt, attrs[:2], gb[:2], front, 1, key_shift, 0, None, ([5, 5, 5], 0, K))
+                G._encode_attributes(rt, attrs[:2], gb[:2], front, key_shift, pkg("runtime").AttrCoding.of(qstep=[5, 5, 5], colour=0, scalable_to=K))
             assert e.value.code == abi.PCC_E_ARG, str(e.value)
 
 

@@ -3,7 +3,8 @@ with nothing to code returns.
 
 The C entry points of a call, in order, with every argument that is a plain number: recorded through a proxy in place
 of geo.rt.lib and compared with lists recorded once, with this proxy and these inputs, on the commit before the front
-ends of compress and distortion became one.  torch's own launches (cat, the lod mask, zeros, full) do not pass the
+ends of compress and distortion became one (the attribute cases: on the commit before a call's attribute settings
+became one record, runtime.AttrCoding, which guards the dispatch among the nine encode entry points).  torch's own launches (cat, the lod mask, zeros, full) do not pass the
 proxy.  The blobs themselves are held to the oracle and to the numpy restatements by the other geometry tests.
 """
 import ctypes as C
@@ -52,7 +53,7 @@ VOXEL = 0.5
 def inputs():
     """four frames: 300 rows of int32 (the corners of the range, 40 repeated rows), no row, one row, 257 rows of
     int16 (one past a workgroup of 256); the same lattice times VOXEL as float32, five NaN rows in frame 0 and frame 2
-    NaN alone; uint8 x 3 attributes for both"""
+    NaN alone; uint8 x 3 attributes for both, and behind those two draws for the integer frames"""
     rng = np.random.default_rng(20)
     base = np.concatenate([random_cloud(rng, 258, extent=1000, lo=-500)[:, 1:], [[-32768] * 3, [32767] * 3]]).astype(np.int32)
     f0 = np.concatenate([base, base[:40]])[rng.permutation(300)]
@@ -63,7 +64,8 @@ def inputs():
     floats[0] = np.concatenate([floats[0][:100], np.full((5, 3), np.nan, np.float32), floats[0][100:]])
     floats[2] = np.full((1, 3), np.nan, np.float32)
     attrs = lambda frames: [rng.integers(0, 256, (f.shape[0], 3)).astype(np.uint8) for f in frames]      # noqa: E731
-    return {"ints": ints, "distinct": distinct, "floats": floats, "float_attrs": attrs(floats), "distinct_attrs": attrs(distinct)}
+    return {"ints": ints, "distinct": distinct, "floats": floats, "float_attrs": attrs(floats), "distinct_attrs": attrs(distinct),
+            "int_attrs": attrs(ints)}
 
 
 def on_device(geo, frames):
@@ -75,6 +77,9 @@ def centres(geo, frames, k=1):
     return [(c << k) + ((1 << k) >> 1) for c in geo.decompress(geo.compress(frames), lod=k)]
 
 
+# the attribute settings that reach an encode entry point of their own (max_error's is in FLOAT_KW)
+ATTR_KW = [{}, dict(scalable=True), dict(cross_channel=True), dict(qstep=8), dict(qstep=(4, 8, 8), colour="ycocg"),
+           dict(qstep=8, scalable_to=2), dict(qstep=(4, 8, 8), colour="ycocg", target_bytes=400)]
 FLOAT_KW = dict(voxel=VOXEL, invalid="drop", lod=2, scalable=True, max_error=1, return_index=True)
 
 
@@ -92,6 +97,9 @@ def cases(geo, x):
         "distortion": lambda: geo.distortion(x["ints"], ctr, peak=65535),
         "distortion with attributes": lambda: geo.distortion(x["distinct"], ctr_distinct, attributes_a=x["distinct_attrs"],
                                                              attributes_b=ctr_attrs),
+        **{"attributes" + (": " + ", ".join(kw) if kw else ""): lambda kw=kw: geo.compress(x["ints"], attributes=x["int_attrs"], **kw)
+           for kw in ATTR_KW},
+        "attributes: rows dropped": lambda: geo.compress(x["floats"], attributes=x["float_attrs"], voxel=VOXEL, invalid="drop"),
     }
 
 
@@ -176,7 +184,27 @@ EXPECTED = {
         ("pcc_nn_attr_sse_frames", 517, 518, 1, 4, 4),
         ("pcc_sync",),
     ],
+    "attributes: rows dropped": [
+        ("pcc_morton_keys_frames_f32", 563, 4, 0.5, 1),
+        ("pcc_sort_pairs", 563, 0),
+        ("pcc_keys_to_coords", 557),
+        ("pcc_unique_rows", 557),
+        ("pcc_gather_rows", 517, 8),
+        ("pcc_octree_encode_frames", 517, 4, 0, 25173),
+        ("pcc_attr_encode_frames_kept", 1, 4, 517, 557, 0, 56592),
+    ],
 }
+# the integer frames with attributes: the six calls of "integer host", then the encode entry point of the settings;
+# recorded, as the lists above, on the commit before the attribute settings of a call became one record
+EXPECTED.update({name: EXPECTED["integer host"] + [call] for name, call in {
+    "attributes": ("pcc_attr_encode_frames", 4, 518, 56688),
+    "attributes: scalable": ("pcc_attr_encode_frames_v2", 4, 518, 0, 56688),
+    "attributes: cross_channel": ("pcc_attr_encode_frames_cross", 1, 4, 518, -1, 0, 0, 56688),
+    "attributes: qstep": ("pcc_attr_encode_frames_transform", 4, 518, -1, 0, 8, 56688),
+    "attributes: qstep, colour": ("pcc_attr_encode_frames_transform2", 4, 518, -1, 0, 1, 56688),
+    "attributes: qstep, scalable_to": ("pcc_attr_encode_frames_transform3", 4, 518, -1, 0, 0, 2, 56688),
+    "attributes: qstep, colour, target_bytes": ("pcc_attr_encode_frames_rate", 4, 518, -1, 0, 1, 1, 0, 56688),
+}.items()})
 
 
 @pytest.fixture(scope="module")
