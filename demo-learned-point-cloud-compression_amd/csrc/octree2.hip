@@ -47,6 +47,7 @@
 #include "common.h"
 #include "lanerans.h"
 #include "octree2_blob.h"
+#include "octree4.h"
 
 #include <string.h>
 
@@ -70,8 +71,8 @@ __device__ __forceinline__ int lane_rank(unsigned long long bal) {
 struct O2Layout {
   int64_t S, nc;
 };
-static O2Layout o2_layout(int64_t n_nodes) {
-  int64_t c = (n_nodes + (int64_t)kLanes * kSMax - 1) / ((int64_t)kLanes * kSMax);
+static O2Layout o2_layout(int64_t n_nodes, int64_t s_max = kSMax) {
+  int64_t c = (n_nodes + (int64_t)kLanes * s_max - 1) / ((int64_t)kLanes * s_max);
   if (c < 1) c = 1;
   int64_t s = (n_nodes + kLanes * c - 1) / (kLanes * c);
   s = (s + 3) / 4 * 4;
@@ -92,9 +93,23 @@ struct O2Frame {
   int32_t origin[3];
 };
 
-// zeros and ones seen per context over the whole frame: cnt[216 f + 2 ctx + bit]; frame f takes blocks [sb, sb + sn)
+// What version 4 (a predicted frame: octree4.hip, include/pcc.h) adds to the coder's three kernels, REF = true: the
+// reference byte of every node beside its occupancy byte (same offsets), which splits every context in three, and what
+// identifies the reference in the header.  REF = false is version 2 and reads none of it.
+struct O2Ref {
+  const uint8_t* rb;
+  const uint32_t* ref_n;               // per frame of the call
+  const unsigned long long* ref_sum;
+};
+// r of decision j: 0 = the reference byte is 0, 1 = it is not and its bit j is 0, 2 = its bit j is 1
+__device__ __forceinline__ int o4_r(uint32_t rbyte, int j) { return rbyte == 0u ? 0 : 1 + (int)((rbyte >> j) & 1u); }
+
+// zeros and ones seen per context over the whole frame: cnt[2 KC f + 2 ctx + bit] (KC = 108, or 324 with REF); frame f
+// takes blocks [sb, sb + sn)
+template <bool REF>
 __global__ __launch_bounds__(256) void k_o2_stats(const uint8_t* __restrict__ occ_all, const O2Frame* __restrict__ tab, int nf,
-                                                  uint32_t* __restrict__ cnt_all) {
+                                                  uint32_t* __restrict__ cnt_all, O2Ref ref) {
+  constexpr int kCtx = REF ? 3 * kO2Ctx : kO2Ctx;
   __shared__ uint32_t s_cnt[2 * kCtx];
   const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].sb; });
   const uint8_t* occ = occ_all + tab[f].occ_off;
@@ -105,12 +120,15 @@ __global__ __launch_bounds__(256) void k_o2_stats(const uint8_t* __restrict__ oc
   __syncthreads();
   for (int64_t node = b * blockDim.x + threadIdx.x; node < n_nodes; node += nb * blockDim.x) {
     const uint32_t byte = occ[node];
+    uint32_t rbyte = 0;
+    if constexpr (REF) rbyte = ref.rb[tab[f].occ_off + node];
     const int cls = node >= start_last ? 0 : (node >= start_prev ? 1 : 2);
     int ones = 0;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const uint32_t bit = (byte >> j) & 1u;
-      if (!(j == 7 && ones == 0)) atomicAdd(&s_cnt[2 * (cls * 36 + j * (j + 1) / 2 + ones) + bit], 1u);
+      const int r108 = REF ? 108 * o4_r(rbyte, j) : 0;
+      if (!(j == 7 && ones == 0)) atomicAdd(&s_cnt[2 * (r108 + cls * 36 + j * (j + 1) / 2 + ones) + bit], 1u);
       ones += (int)bit;
     }
   }
@@ -126,11 +144,13 @@ __global__ __launch_bounds__(256) void k_o2_stats(const uint8_t* __restrict__ oc
 // and the word counts; words_out[chunk] = 192 + sum of the counts.  Every global access of the coding loop is
 // unconditional (rans_gpu.hip's rule).  Block = chunk of the call: frame f owns blocks [cb, cb + nc); its records and
 // word regions start rec_off words in, states / lens / words_out are indexed by the call's chunk.
+template <bool REF>
 __global__ __launch_bounds__(64) void k_o2_enc(const uint8_t* __restrict__ occ_all, const O2Frame* __restrict__ tab, int nf,
                                                const uint32_t* __restrict__ cnt_all, uint16_t* __restrict__ rec_all,
                                                uint16_t* __restrict__ work_all, uint16_t* __restrict__ states,
                                                uint16_t* __restrict__ lens, uint32_t* __restrict__ words_out,
-                                               uint16_t* __restrict__ p0_all) {
+                                               uint16_t* __restrict__ p0_all, O2Ref ref) {
+  constexpr int kCtx = REF ? 3 * kO2Ctx : kO2Ctx;
   __shared__ uint16_t s_model[(kCtx + 1) * kLanes];   // [ctx][lane]; row kCtx takes the writes of decisions that are not coded
   __shared__ uint16_t s_p0[kCtx];
   __shared__ __attribute__((aligned(16))) uint32_t s_rcp[4096];
@@ -161,20 +181,30 @@ __global__ __launch_bounds__(64) void k_o2_enc(const uint8_t* __restrict__ occ_a
   const int64_t node0 = (c * kLanes + lane) * S;   // a multiple of 4: four nodes per dword
   const int64_t last_dw = (n_nodes - 1) >> 2;
   uint32_t dw_next = occ32[(node0 >> 2) < last_dw ? (node0 >> 2) : last_dw];
+  const uint32_t* rb32 = nullptr;
+  uint32_t rdw_next = 0;
+  if constexpr (REF) {
+    rb32 = reinterpret_cast<const uint32_t*>(ref.rb + tab[f].occ_off);
+    rdw_next = rb32[(node0 >> 2) < last_dw ? (node0 >> 2) : last_dw];
+  }
   for (int s = 0; s < S; s += 4) {
     const uint32_t dw = dw_next;
     dw_next = occ32[((node0 + s + 4) >> 2) < last_dw ? ((node0 + s + 4) >> 2) : last_dw];
+    const uint32_t rdw = rdw_next;
+    if constexpr (REF) rdw_next = rb32[((node0 + s + 4) >> 2) < last_dw ? ((node0 + s + 4) >> 2) : last_dw];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int64_t node = node0 + s + q;
       const bool valid = node < n_nodes;
       const uint32_t byte = (dw >> (8 * q)) & 0xFFu;
+      const uint32_t rbyte = REF ? (rdw >> (8 * q)) & 0xFFu : 0u;
       const int cls = node >= start_last ? 0 : (node >= start_prev ? 1 : 2);
       uint32_t p[8];
       int at[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        at[j] = (cls * 36 + j * (j + 1) / 2 + __popc(byte & ((1u << j) - 1u))) * kLanes + lane;
+        const int r108 = REF ? 108 * o4_r(rbyte, j) : 0;
+        at[j] = (r108 + cls * 36 + j * (j + 1) / 2 + __popc(byte & ((1u << j) - 1u))) * kLanes + lane;
         p[j] = s_model[at[j]];
       }
       uint32_t r[8];
@@ -258,11 +288,15 @@ __global__ __launch_bounds__(64) void k_o2_enc(const uint8_t* __restrict__ occ_a
 // the blobs, assembled where `out_all` points (pinned host memory: the bytes cross PCIe as the kernel writes them),
 // frame f's at out_off: frame f owns workgroups [cb + f, cb + f + nc + 1) — workgroup c < nc of them moves chunk c
 // (states, length table, the 64 runs), workgroup nc writes the header; len_out[f] = bytes, or -1 (out_cap)
+// (REF: the header of version 4 — ref_n and ref_sum behind the chunk count, 324 initial probabilities)
+template <bool REF>
 __global__ __launch_bounds__(256) void k_o2_pack(const uint16_t* __restrict__ work_all, const O2Frame* __restrict__ tab, int nf,
                                                  const uint16_t* __restrict__ states_all, const uint16_t* __restrict__ lens_all,
                                                  const uint32_t* __restrict__ words_all, const uint32_t* __restrict__ counts_all,
                                                  const uint16_t* __restrict__ p0_all, uint8_t* __restrict__ out_all,
-                                                 long long* __restrict__ len_out) {
+                                                 long long* __restrict__ len_out, O2Ref ref) {
+  constexpr int kCtx = REF ? 3 * kO2Ctx : kO2Ctx;
+  constexpr int kRefWords = REF ? 3 : 0;   // ref_n, ref_sum
   __shared__ unsigned long long s_sum[256];
   __shared__ uint32_t s_off[kLanes + 1];
   const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].cb + i; });
@@ -285,7 +319,7 @@ __global__ __launch_bounds__(256) void k_o2_pack(const uint16_t* __restrict__ wo
     __syncthreads();
   }
   const unsigned long long before = s_sum[0];
-  const unsigned long long head = (unsigned long long)kHeader + 4ull * h.depth + 8ull + 2ull * kCtx + 4ull * nc;
+  const unsigned long long head = (unsigned long long)kHeader + 4ull * h.depth + 8ull + 4ull * kRefWords + 2ull * kCtx + 4ull * nc;
   if (c == nc) {
     const unsigned long long total = head + before * 2;
     const bool fits = (long long)total <= cap;
@@ -296,7 +330,7 @@ __global__ __launch_bounds__(256) void k_o2_pack(const uint16_t* __restrict__ wo
     if (!fits) return;
     uint32_t* o32 = reinterpret_cast<uint32_t*>(out);
     if (threadIdx.x == 0) {
-      o32[0] = (uint32_t)'O' | (2u << 8) | ((uint32_t)h.depth << 16);
+      o32[0] = (uint32_t)'O' | ((REF ? 4u : 2u) << 8) | ((uint32_t)h.depth << 16);
       o32[1] = h.n_points;
       o32[2] = (uint32_t)h.origin[0];
       o32[3] = (uint32_t)h.origin[1];
@@ -304,11 +338,20 @@ __global__ __launch_bounds__(256) void k_o2_pack(const uint16_t* __restrict__ wo
       o32[5] = (uint32_t)(total - kHeader);
       o32[6 + h.depth] = (uint32_t)h.S;
       o32[7 + h.depth] = (uint32_t)h.nc;
+      if constexpr (REF) {
+        o32[8 + h.depth] = ref.ref_n[f];
+        o32[9 + h.depth] = (uint32_t)ref.ref_sum[f];
+        o32[10 + h.depth] = (uint32_t)(ref.ref_sum[f] >> 32);
+      }
     }
     if ((int)threadIdx.x < h.depth) o32[6 + threadIdx.x] = counts[threadIdx.x];
-    uint16_t* o16 = reinterpret_cast<uint16_t*>(o32 + 8 + h.depth);
-    if ((int)threadIdx.x < kCtx) o16[threadIdx.x] = p0[threadIdx.x];
-    uint32_t* tab = o32 + 8 + h.depth + kCtx / 2;
+    uint16_t* o16 = reinterpret_cast<uint16_t*>(o32 + 8 + kRefWords + h.depth);
+    if constexpr (REF) {
+      for (int i = threadIdx.x; i < kCtx; i += 256) o16[i] = p0[i];
+    } else {
+      if ((int)threadIdx.x < kCtx) o16[threadIdx.x] = p0[threadIdx.x];
+    }
+    uint32_t* tab = o32 + 8 + kRefWords + h.depth + kCtx / 2;
     for (int64_t j = threadIdx.x; j < nc; j += blockDim.x) tab[j] = words[j];
     return;
   }
@@ -646,9 +689,16 @@ struct O2In {   // one frame of an encode call: leaves d_keys[lo, lo + n) (n >= 
 // blobs of version 2 of the frames fr[0 .. nf): the levels of all frames (launches independent of nf), ONE
 // synchronisation for all level counts (they size the chunks), the coder's three launches over all frames' chunks,
 // ONE synchronisation for all blob lengths.  Blob f is left in the pinned staging at (*offs)[f], (*lens)[f] bytes.
+//
+// pred (version 4, octree4.hip): every frame of the batch is a predicted frame, pred[f] the keys of its reference
+// (d_keys[ref_lo, ref_lo + ref_n), Morton-sorted and distinct after the key shift).  One step is added in front of the
+// coder's launches: the reference byte of every node.
 static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, const O2In* fr, int nf,
-                           std::vector<int64_t>* offs, std::vector<int64_t>* lens) {
+                           std::vector<int64_t>* offs, std::vector<int64_t>* lens, const O4Pred* pred = nullptr) {
   hipStream_t st = ctx->stream;
+  const int KC = pred ? 3 * kCtx : kCtx;
+  const int64_t s_max = pred ? kO4SMax : kSMax;
+  const int64_t ref_head = pred ? 12 : 0;
   const int64_t small_max = pcc_octree_small_max();
   // levels: the frames of the single-workgroup form first, then those of the wave form
   std::vector<PccOctFrame> lt((size_t)nf);
@@ -656,7 +706,7 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
   int ns = 0, nl = 0;
   for (int f = 0; f < nf; ++f) ns += fr[f].n <= small_max ? 1 : 0;
   int64_t occ_bytes = 0, waves = 0, leaves = 0;
-  size_t coder_b = 3 * 256 + 4096;
+  size_t coder_b = 3 * 256 + 4096, ref_b = 0, scan_b = 0;
   for (int f = 0, is = 0, il = 0; f < nf; ++f) {
     const O2In& g = fr[f];
     PCC_REQUIRE(g.n >= 1 && g.depth >= 1 && g.depth <= 16 && key_shift + 3 * g.depth <= 48, PCC_E_ARG,
@@ -678,20 +728,32 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
     // would drop what the first holds: the arena is reserved for the node counts of surfaces and sweeps (<= 2.5 nodes
     // per leaf); a sparser batch (up to `depth` nodes per leaf) takes a block of its own for this call
     const int64_t guess = std::min<int64_t>(cap_of[(size_t)f], 5 * g.n / 2 + 64 * g.depth + 4096);
-    const O2Layout l = o2_layout(guess);
+    const O2Layout l = o2_layout(guess, s_max);
     coder_b += (size_t)l.nc * (8 * l.S * kLanes * 2 * 2 + 4 + 3 * kLanes * 2);   // records, word regions, tables
+    if (pred) {   // (the scans of the child counts take their block sums from the arena, frame after frame)
+      ref_b = std::max(ref_b, o4_ref_scratch_bytes(guess, g.n));
+      scan_b += pcc_scan_scratch_bytes(cap_of[(size_t)f]) + 512;
+    }
   }
   nl = nf - ns;
   PCC_REQUIRE(leaves < ((int64_t)1 << 27) && occ_bytes < ((int64_t)1 << 32), PCC_E_ARG, "octree blob v2: %lld leaves in %d frames",
               (long long)leaves, nf);
   const size_t lt_b = pcc_align((size_t)nf * sizeof(PccOctFrame)), ct_b = pcc_align((size_t)nf * sizeof(O2Frame));
   const size_t counts_b = pcc_align((size_t)nf * PCC_OCT_CSTRIDE * 4);
-  PCC_TRY(pcc_arena_reserve(ctx, (size_t)occ_bytes + 16 + counts_b + pcc_align((size_t)nf * 2 * kCtx * 4) + pcc_align((size_t)nf * kCtx * 2) +
-                                     lt_b + ct_b + pcc_octree_frames_scratch(waves, nl) + coder_b + 16384));
+  const size_t pred_b = pred ? pcc_align((size_t)occ_bytes + 16) + 2 * pcc_align((size_t)nf * 8) + ref_b + scan_b + 4096 : 0;
+  PCC_TRY(pcc_arena_reserve(ctx, (size_t)occ_bytes + 16 + counts_b + pcc_align((size_t)nf * 2 * KC * 4) + pcc_align((size_t)nf * KC * 2) +
+                                     lt_b + ct_b + pcc_octree_frames_scratch(waves, nl) + coder_b + pred_b + 16384));
   uint8_t* occ = (uint8_t*)pcc_arena_alloc(ctx, (size_t)occ_bytes + 16);
   uint32_t* counts = (uint32_t*)pcc_arena_alloc(ctx, counts_b);
-  uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nf * 2 * kCtx * 4);
-  uint16_t* p0 = (uint16_t*)pcc_arena_alloc(ctx, (size_t)nf * kCtx * 2);
+  uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nf * 2 * KC * 4);
+  uint16_t* p0 = (uint16_t*)pcc_arena_alloc(ctx, (size_t)nf * KC * 2);
+  O2Ref ref{nullptr, nullptr, nullptr};
+  if (pred) {
+    ref.rb = (const uint8_t*)pcc_arena_alloc(ctx, (size_t)occ_bytes + 16);
+    ref.ref_n = (const uint32_t*)pcc_arena_alloc(ctx, (size_t)nf * 4);
+    ref.ref_sum = (const unsigned long long*)pcc_arena_alloc(ctx, (size_t)nf * 8);
+    if (!ref.rb || !ref.ref_n || !ref.ref_sum) return PCC_E_NOMEM;
+  }
   PccOctFrame* d_lt = (PccOctFrame*)pcc_arena_alloc(ctx, lt_b);
   O2Frame* d_ct = (O2Frame*)pcc_arena_alloc(ctx, ct_b);
   if (!occ || !counts || !cnt || !p0 || !d_lt || !d_ct) return PCC_E_NOMEM;
@@ -702,9 +764,11 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
   PCC_TRY(pcc_octree_frames_async(ctx, d_keys, key_shift, lt.data(), d_lt, ns, nl, occ, counts));
   uint32_t* hc = (uint32_t*)((char*)ctx->stage + lt_b);
   PCC_HIP(hipMemcpyAsync(hc, counts, (size_t)nf * PCC_OCT_CSTRIDE * 4, hipMemcpyDeviceToHost, st));
-  PCC_HIP(hipMemsetAsync(cnt, 0, (size_t)nf * 2 * kCtx * 4, st));
+  PCC_HIP(hipMemsetAsync(cnt, 0, (size_t)nf * 2 * KC * 4, st));
   PCC_HIP(hipStreamSynchronize(st));
   // the coder's table from the level counts
+  std::vector<uint32_t> level_counts;   // (version 4 reads them again behind the staging's next reservation)
+  if (pred) level_counts.assign(hc, hc + (size_t)nf * PCC_OCT_CSTRIDE);
   std::vector<O2Frame> ct((size_t)nf);
   int64_t rec_words = 0, out_bytes = 0, chunks = 0, stats_blocks = 0;
   for (int f = 0; f < nf; ++f) {
@@ -715,9 +779,9 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
     PCC_REQUIRE(c[0] == 1, PCC_E_ARG, "pcc_octree2_encode: keys exceed 3*depth bits (root level has %u nodes)", c[0]);
     PCC_REQUIRE(n_nodes <= cap_of[(size_t)f], PCC_E_NOMEM, "pcc_octree2_encode: %lld nodes for %lld leaves", (long long)n_nodes,
                 (long long)fr[f].n);
-    const O2Layout lay = o2_layout(n_nodes);
+    const O2Layout lay = o2_layout(n_nodes, s_max);
     const int64_t T = 8 * lay.S, cap_words = 3 * kLanes + kLanes * T;   // bound of a chunk in the blob
-    const int64_t head = kHeader + 4 * depth + 8 + 2 * kCtx + 4 * lay.nc;
+    const int64_t head = kHeader + 4 * depth + 8 + ref_head + 2 * KC + 4 * lay.nc;
     O2Frame& r = ct[(size_t)f];
     r.occ_off = 0;   // below, from the levels' table
     r.n_nodes = n_nodes;
@@ -748,19 +812,25 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
   } own;
   const size_t rec_b = pcc_align((size_t)rec_words * 2), work_b = rec_b;   // [chunk][step][lane] / [chunk][lane][T]
   const size_t small_b = pcc_align((size_t)chunks * (4 + 2 * kLanes * 2 + kLanes * 2));   // words | states | lens
+  // version 4: the scratch of the reference bytes, sized by the largest frame's nodes (the frames take it in turn)
+  size_t ref_need = 0;
+  if (pred)
+    for (int f = 0; f < nf; ++f) ref_need = std::max(ref_need, o4_ref_scratch_bytes(ct[(size_t)f].n_nodes, fr[f].n));
   uint16_t *rec, *work;
-  char* small;
-  if (pcc_align(ctx->arena_off) + rec_b + work_b + small_b + 1024 <= ctx->arena_cap) {
+  char *small, *ref_scratch;
+  if (pcc_align(ctx->arena_off) + rec_b + work_b + small_b + ref_need + scan_b + 2048 <= ctx->arena_cap) {
     rec = (uint16_t*)pcc_arena_alloc(ctx, rec_b);
     work = (uint16_t*)pcc_arena_alloc(ctx, work_b);
     small = (char*)pcc_arena_alloc(ctx, small_b);
+    ref_scratch = (char*)pcc_arena_alloc(ctx, ref_need + 256);
   } else {
-    PCC_HIP(hipMalloc(&own.p, rec_b + work_b + small_b));
+    PCC_HIP(hipMalloc(&own.p, rec_b + work_b + small_b + ref_need + 256));
     rec = (uint16_t*)own.p;
     work = (uint16_t*)((char*)own.p + rec_b);
     small = (char*)own.p + rec_b + work_b;
+    ref_scratch = small + small_b;
   }
-  if (!rec || !work || !small) return PCC_E_NOMEM;
+  if (!rec || !work || !small || !ref_scratch) return PCC_E_NOMEM;
   uint32_t* words = (uint32_t*)small;
   uint16_t* states = (uint16_t*)(small + (size_t)chunks * 4);
   uint16_t* lens_d = states + (size_t)chunks * 2 * kLanes;
@@ -771,15 +841,45 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
   memcpy(stage, ct.data(), (size_t)nf * sizeof(O2Frame));
   PCC_HIP(hipMemcpyAsync(d_ct, stage, (size_t)nf * sizeof(O2Frame), hipMemcpyHostToDevice, st));
   long long* len_dev = (long long*)(stage + lens_at);
-  hipLaunchKernelGGL(k_o2_stats, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nf, cnt);
-  PCC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_o2_enc, dim3((unsigned)chunks), dim3(64), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nf,
-                     (const uint32_t*)cnt, rec, work, states, lens_d, words, p0);
-  PCC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_o2_pack, dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work, (const O2Frame*)d_ct, nf,
-                     (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words, (const uint32_t*)counts,
-                     (const uint16_t*)p0, stage + ct_b, len_dev);
-  PCC_CHECK_LAUNCH();
+  if (pred) {
+    std::vector<O4RefJob> jobs((size_t)nf);
+    for (int f = 0; f < nf; ++f) {
+      O4RefJob& j = jobs[(size_t)f];
+      const uint32_t* c = level_counts.data() + (size_t)PCC_OCT_CSTRIDE * f;
+      j.occ_off = ct[(size_t)f].occ_off;
+      j.n_points = fr[f].n;
+      j.depth = fr[f].depth;
+      int64_t run = 0;
+      for (int L = 0; L <= 16; ++L) {
+        j.off[L] = run;
+        if (L < j.depth) run += (int64_t)c[L];
+      }
+      for (int a = 0; a < 3; ++a) j.origin[a] = fr[f].origin[a];
+      j.ref_lo = pred[f].ref_lo;
+      j.ref_n = pred[f].ref_n;
+    }
+    PCC_TRY(o4_ref_bytes_async(ctx, d_keys, key_shift, jobs.data(), nf, occ, (uint8_t*)ref.rb, (uint32_t*)ref.ref_n,
+                               (unsigned long long*)ref.ref_sum, ref_scratch, ref_need + 256));
+    hipLaunchKernelGGL(k_o2_stats<true>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nf, cnt, ref);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_o2_enc<true>, dim3((unsigned)chunks), dim3(64), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nf,
+                       (const uint32_t*)cnt, rec, work, states, lens_d, words, p0, ref);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_o2_pack<true>, dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work, (const O2Frame*)d_ct, nf,
+                       (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words, (const uint32_t*)counts,
+                       (const uint16_t*)p0, stage + ct_b, len_dev, ref);
+    PCC_CHECK_LAUNCH();
+  } else {
+    hipLaunchKernelGGL(k_o2_stats<false>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nf, cnt, ref);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_o2_enc<false>, dim3((unsigned)chunks), dim3(64), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nf,
+                       (const uint32_t*)cnt, rec, work, states, lens_d, words, p0, ref);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_o2_pack<false>, dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work, (const O2Frame*)d_ct, nf,
+                       (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words, (const uint32_t*)counts,
+                       (const uint16_t*)p0, stage + ct_b, len_dev, ref);
+    PCC_CHECK_LAUNCH();
+  }
   PCC_HIP(hipStreamSynchronize(st));
   offs->resize((size_t)nf);
   lens->resize((size_t)nf);
@@ -1002,16 +1102,16 @@ int pcc_octree2_decode(pcc_ctx* ctx, const uint8_t* h_in, int64_t len, int32_t* 
 }
 
 // ---- C-ABI: many frames per call (include/pcc.h) ----------------------------------------------------------------------
-extern "C" int pcc_octree_encode_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int key_shift,
-                                        uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
-  PCC_REQUIRE(ctx && h_out && h_offsets && n >= 0 && (n == 0 || d_keys) && n < ((int64_t)1 << 27) && n_frames >= 1 &&
-                  n_frames <= 65535 && key_shift >= 0 && key_shift % 3 == 0 && key_shift <= 45 && cap >= 0,
-              PCC_E_ARG, "pcc_octree_encode_frames: bad argument (n=%lld n_frames=%d key_shift=%d)", (long long)n, n_frames,
-              key_shift);
+// the frames of an encode call: offs[f] = first key of frame f (offs[n_frames] = n), ends[2 f], ends[2 f + 1] = a frame's
+// first and last key; the keys are checked (sorted, distinct after the key shift, frame index).  One synchronisation.
+static int o2_frame_bounds(const char* who, pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int key_shift,
+                           std::vector<int64_t>* offs_out, std::vector<uint64_t>* ends_out) {
   hipStream_t st = ctx->stream;
-  std::vector<int64_t> offs((size_t)n_frames + 1, 0);
-  std::vector<uint64_t> ends((size_t)2 * n_frames, 0);
-  if (n > 0) {   // frame boundaries, every frame's end keys and the checks of the keys: one synchronisation
+  std::vector<int64_t>& offs = *offs_out;
+  std::vector<uint64_t>& ends = *ends_out;
+  offs.assign((size_t)n_frames + 1, 0);
+  ends.assign((size_t)2 * n_frames, 0);
+  if (n > 0) {
     const size_t offs_b = (size_t)(n_frames + 1) * 8, ends_b = (size_t)n_frames * 16, rd_b = offs_b + ends_b + 8;
     PCC_TRY(pcc_arena_reserve(ctx, rd_b + 256));
     uint8_t* rd = (uint8_t*)pcc_arena_alloc(ctx, rd_b);
@@ -1030,12 +1130,24 @@ extern "C" int pcc_octree_encode_frames(pcc_ctx* ctx, const uint64_t* d_keys, in
     const uint8_t* h = (const uint8_t*)ctx->stage;
     int32_t flag;
     memcpy(&flag, h + offs_b + ends_b, 4);
-    PCC_REQUIRE(!(flag & 4), PCC_E_ARG, "pcc_octree_encode_frames: a key's frame index is not below n_frames=%d", n_frames);
-    PCC_REQUIRE(!(flag & 2), PCC_E_ARG, "pcc_octree_encode_frames: keys not sorted (pcc_sort_pairs)");
-    PCC_REQUIRE(!(flag & 1), PCC_E_DUP, "pcc_octree_encode_frames: duplicate keys (after the key shift of %d)", key_shift);
+    PCC_REQUIRE(!(flag & 4), PCC_E_ARG, "%s: a key's frame index is not below n_frames=%d", who, n_frames);
+    PCC_REQUIRE(!(flag & 2), PCC_E_ARG, "%s: keys not sorted (pcc_sort_pairs)", who);
+    PCC_REQUIRE(!(flag & 1), PCC_E_DUP, "%s: duplicate keys (after the key shift of %d)", who, key_shift);
     memcpy(offs.data(), h, offs_b);
     memcpy(ends.data(), h + offs_b, ends_b);
   }
+  return PCC_OK;
+}
+
+extern "C" int pcc_octree_encode_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int key_shift,
+                                        uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
+  PCC_REQUIRE(ctx && h_out && h_offsets && n >= 0 && (n == 0 || d_keys) && n < ((int64_t)1 << 27) && n_frames >= 1 &&
+                  n_frames <= 65535 && key_shift >= 0 && key_shift % 3 == 0 && key_shift <= 45 && cap >= 0,
+              PCC_E_ARG, "pcc_octree_encode_frames: bad argument (n=%lld n_frames=%d key_shift=%d)", (long long)n, n_frames,
+              key_shift);
+  std::vector<int64_t> offs;
+  std::vector<uint64_t> ends;
+  PCC_TRY(o2_frame_bounds("pcc_octree_encode_frames", ctx, d_keys, n, n_frames, key_shift, &offs, &ends));
   std::vector<O2In> fr;
   std::vector<int> frame_of;
   for (int f = 0; f < n_frames; ++f) {
@@ -1069,6 +1181,65 @@ extern "C" int pcc_octree_encode_frames(pcc_ctx* ctx, const uint64_t* d_keys, in
       dst[1] = 2;
     }
     h_offsets[f + 1] = h_offsets[f] + len_of[(size_t)f];
+  }
+  return PCC_OK;
+}
+
+// Inter-frame coding (include/pcc.h has the rule of version 4): the reference of a frame is the frame in front of it
+// in the call — lossless coding makes the original the decoded frame, so all frames still encode side by side: the
+// intra frames in one batch of version 2, the predicted ones in one batch of version 4.
+extern "C" int pcc_octree_encode_frames_inter(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int key_shift,
+                                              int intra_period, int ref_first, uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
+  const char* who = "pcc_octree_encode_frames_inter";
+  PCC_REQUIRE(ctx && h_out && h_offsets && n >= 0 && (n == 0 || d_keys) && n < ((int64_t)1 << 27) && n_frames >= 1 &&
+                  n_frames <= 65535 && key_shift >= 0 && key_shift % 3 == 0 && key_shift <= 45 && cap >= 0 && intra_period >= 0 &&
+                  (ref_first == 0 || ref_first == 1),
+              PCC_E_ARG, "%s: bad argument (n=%lld n_frames=%d key_shift=%d intra_period=%d ref_first=%d)", who, (long long)n,
+              n_frames, key_shift, intra_period, ref_first);
+  std::vector<int64_t> offs;
+  std::vector<uint64_t> ends;
+  PCC_TRY(o2_frame_bounds(who, ctx, d_keys, n, n_frames, key_shift, &offs, &ends));
+  std::vector<O2In> fr[2];            // [0] intra, [1] predicted
+  std::vector<int> frame_of[2];
+  std::vector<O4Pred> pred;
+  for (int f = ref_first; f < n_frames; ++f) {
+    const int64_t lo = offs[(size_t)f], hi = offs[(size_t)f + 1];
+    if (hi <= lo) continue;
+    const int g = f - ref_first;     // its place among the coded frames
+    const bool intra = intra_period > 0 ? g % intra_period == 0 : f == 0;
+    const int64_t ref_n = f > 0 ? lo - offs[(size_t)f - 1] : 0;
+    const int k = !intra && ref_n > 0 ? 1 : 0;   // a frame whose reference has no points is written as version 2
+    O2In in;
+    in.lo = lo;
+    in.n = hi - lo;
+    octree_root(ends[2 * (size_t)f], ends[2 * (size_t)f + 1], key_shift, &in.depth, in.origin);
+    fr[k].push_back(in);
+    frame_of[k].push_back(f);
+    if (k) pred.push_back(O4Pred{offs[(size_t)f - 1], ref_n});
+  }
+  // blob f; frames without keys get the 24-byte empty blob, the reference of ref_first none
+  std::vector<std::vector<uint8_t>> blob((size_t)n_frames);
+  for (int f = ref_first; f < n_frames; ++f) {
+    blob[(size_t)f].assign((size_t)kHeader, 0);
+    blob[(size_t)f][0] = 'O';
+    blob[(size_t)f][1] = 2;
+  }
+  for (int k = 0; k < 2; ++k) {
+    if (fr[k].empty()) continue;
+    std::vector<int64_t> boff, blen;
+    PCC_TRY(o2_encode_batch(ctx, d_keys, key_shift, fr[k].data(), (int)fr[k].size(), &boff, &blen, k ? pred.data() : nullptr));
+    for (size_t i = 0; i < fr[k].size(); ++i) {
+      const uint8_t* src = (const uint8_t*)ctx->stage + boff[i];
+      blob[(size_t)frame_of[k][i]].assign(src, src + blen[i]);
+    }
+  }
+  int64_t total = 0;
+  for (const auto& b : blob) total += (int64_t)b.size();
+  PCC_REQUIRE(total <= cap, PCC_E_NOMEM, "%s: %lld bytes of blobs, capacity %lld", who, (long long)total, (long long)cap);
+  h_offsets[0] = 0;
+  for (int f = 0; f < n_frames; ++f) {
+    if (!blob[(size_t)f].empty()) memcpy(h_out + h_offsets[f], blob[(size_t)f].data(), blob[(size_t)f].size());
+    h_offsets[f + 1] = h_offsets[f] + (int64_t)blob[(size_t)f].size();
   }
   return PCC_OK;
 }

@@ -1,0 +1,591 @@
+// octree4.hip — octree blob version 4: a frame of a sequence coded against the frame before it (a P-frame).
+//
+// The rule is version 2's (octree2.hip) with the context of every decision split in three by the node's REFERENCE BYTE:
+// bit j of it says whether the reference — a set of distinct lattice points, for a sequence the decoded frame before —
+// has a point inside the cube of the node's child octant j (include/pcc.h has the rule in full, octree4_blob.h the
+// header).  About a fifth of a LiDAR sweep's geometry bytes go (DESIGN.md 6c-inter has the measurements).
+//
+// Encoder: the coder's three launches are octree2.hip's, instantiated with the reference byte (k_o2_stats / k_o2_enc /
+// k_o2_pack <true>); this file adds the step in front of them, o4_ref_bytes_async — every node's cell from the child
+// counts (one scan, one pass that links every child to its parent, a walk up the links), then one bounded binary
+// search per child cube over the reference's sorted keys: a cube of the lattice is a contiguous range of Morton keys.
+//
+// Decoder: a context that depends on where a node lies cannot be formed before the levels above the node are decoded,
+// so version 2's one launch over all nodes is not available.  A predicted frame is decoded level by level, every wait a
+// kernel boundary, the launch sizes from the header's level table (no host synchronisation per level).  Per level L:
+//   scan of the child counts of level L - 1 and k_o4_link   the (parent, octant) link of every node of level L
+//   k_o4_ref                                                their cells (a walk up L links) and reference bytes
+//   k_o4_dec                                                the entropy decode of the level's nodes: the chunks that
+//                                                           hold nodes of the level, one wave each
+// A lane whose run of S nodes straddles the boundary between two levels leaves its rANS state, its word position and
+// its model in global memory and picks them up in the next launch (at most one lane per boundary; two slots used in
+// turn, because the lane that picks up and the lane that leaves may differ).  Behind the last level one more scan and
+// link give the leaves, and k_o4_points walks every leaf up to the root, as version 2 does.  The chain I P P .. decodes
+// frame after frame on the stream: the keys of a decoded frame are the reference of the next.
+//
+// What the stream announces is never trusted: every size comes from the header's checks (octree4_blob.h), every
+// store is to an index below a bound the host sized the array from, every read of the stream is clamped to the chunk.
+#include "common.h"
+#include "lanerans.h"
+#include "octree2_blob.h"
+#include "octree4.h"
+#include "octree4_blob.h"
+
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+namespace {
+
+constexpr int kC4 = kO4Ctx;
+constexpr uint32_t kL = 1u << 16;
+constexpr uint64_t kMask48 = ((uint64_t)1 << 48) - 1;
+// the decoder's window of 16-bit words in LDS: 20 KB beside the 41.6 KB of models (325 rows x 64 lanes x 2 B).  It
+// holds the runs of the lanes that decode in the launch; a span that does not fit is read from the stream in place
+constexpr int kO4Win = 10240;
+
+// the levels of one frame's tree and where its cubes lie
+struct O4Tree {
+  int64_t off[18];        // level L = nodes [off[L], off[L + 1]); off[depth] = nodes, off[depth + 1] = nodes + leaves
+  int32_t depth;
+  int32_t origin[3];      // of the root cube, in the units of the frame's points
+  int32_t bias;           // reference key = Morton key of (point + bias) per axis
+  int32_t key_shift;      // of the reference keys as they are stored
+};
+
+// the term of a point in ref_sum
+__device__ __forceinline__ unsigned long long o4_sum_term(int x, int y, int z) {
+  return ((unsigned long long)((uint32_t)x & 0xFFFFu) << 32) | ((unsigned long long)((uint32_t)y & 0xFFFFu) << 16) |
+         (unsigned long long)((uint32_t)z & 0xFFFFu);
+}
+__device__ __forceinline__ void o4_sum_add(unsigned long long term, unsigned long long* sum) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) term += __shfl_xor(term, d, 64);
+  if ((threadIdx.x & 63) == 0 && term) atomicAdd(sum, term);
+}
+
+// ref_sum of the reference keys[0 .. n) of an encode call (coordinates as a decoder returns them: the key's cell under
+// the key shift, minus its bias)
+__global__ __launch_bounds__(256) void k_o4_keysum(const uint64_t* __restrict__ keys, int64_t n, int shift, int bias,
+                                                   unsigned long long* __restrict__ sum) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned long long term = 0;
+  if (i < n) {
+    const uint64_t k = (keys[i] & kMask48) >> shift;
+    term = o4_sum_term((int)pcc_compact3(k >> 2) - bias, (int)pcc_compact3(k >> 1) - bias, (int)pcc_compact3(k) - bias);
+  }
+  o4_sum_add(term, sum);
+}
+
+// the keys (bias 32768) and ref_sum of decoded points, which must be distinct and in Morton order: status |= 32
+__global__ __launch_bounds__(256) void k_o4_keys(const int32_t* __restrict__ pts, int64_t n, uint64_t* __restrict__ keys,
+                                                 unsigned long long* __restrict__ sum, int32_t* __restrict__ status) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned long long term = 0;
+  if (i < n) {
+    const int x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+    const uint64_t k = pcc_morton(0, x, y, z);
+    bool bad = x < -32768 || x > 32767 || y < -32768 || y > 32767 || z < -32768 || z > 32767;
+    if (i > 0) bad = bad || pcc_morton(0, pts[3 * i - 3], pts[3 * i - 2], pts[3 * i - 1]) >= k;
+    if (bad) atomicOr(status, 32);
+    keys[i] = k;
+    term = o4_sum_term(x, y, z);
+  }
+  o4_sum_add(term, sum);
+}
+
+// status |= 16 where the reference at hand is not the one the blob was coded against
+__global__ void k_o4_refcheck(const unsigned long long* __restrict__ sum, unsigned long long want, int32_t* __restrict__ status) {
+  if (*sum != want) atomicOr(status, 16);
+}
+
+__global__ __launch_bounds__(256) void k_o4_popc(const uint8_t* __restrict__ occ, int64_t n, uint32_t* __restrict__ pc) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) pc[i] = (uint32_t)__popc((uint32_t)occ[i]);
+}
+
+// link[child] = parent << 3 | octant for the children of nodes [a, a + cnt): excl is the exclusive scan of their child
+// counts, their children are the nodes (or leaves) from child_base on and must end at child_end exactly: status |= 8
+__global__ __launch_bounds__(256) void k_o4_link(const uint8_t* __restrict__ occ, const uint32_t* __restrict__ excl, int64_t a,
+                                                 int64_t cnt, int64_t child_base, int64_t child_end, uint32_t* __restrict__ link,
+                                                 int32_t* __restrict__ status) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= cnt) return;
+  const uint32_t byte = occ[a + i];
+  const int64_t first = child_base + (int64_t)excl[i];
+  if (i == cnt - 1 && first + __popc(byte) != child_end) atomicOr(status, 8);
+  int k = 0;
+  for (int j = 0; j < 8; ++j)
+    if ((byte >> j) & 1u) {
+      const int64_t child = first + k;
+      if (child < child_end) link[child] = ((uint32_t)(a + i) << 3) | (uint32_t)j;
+      ++k;
+    }
+}
+
+// the reference byte of nodes [a, b): the node's cell from a walk up its links, then for every child octant whether
+// the reference holds a key inside the child's cube — the cube of side 2^s at a corner that is a multiple of 2^s in
+// biased coordinates is the key range [G, G + 8^s), so two lower bounds over the sorted keys answer a child
+__global__ __launch_bounds__(256) void k_o4_ref(const uint32_t* __restrict__ link, O4Tree t, int64_t a, int64_t b,
+                                                const uint64_t* __restrict__ ref_keys, int64_t n_ref, uint8_t* __restrict__ rb) {
+  const int64_t i = a + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= b) return;
+  int L = 0;
+  while (L + 1 < t.depth && i >= t.off[L + 1]) ++L;
+  uint64_t code = 0;
+  uint32_t idx = (uint32_t)i;
+  const uint32_t n_nodes = (uint32_t)t.off[t.depth];
+  for (int d = 0; d < L; ++d) {
+    const uint32_t l = link[idx < n_nodes ? idx : 0u];
+    code |= (uint64_t)(l & 7u) << (3 * d);
+    idx = l >> 3;
+  }
+  const int s = t.depth - L - 1;   // a child's cube has side 2^s
+  const uint32_t cx = (pcc_compact3(code >> 2) << (s + 1)) + (uint32_t)(t.origin[0] + t.bias);
+  const uint32_t cy = (pcc_compact3(code >> 1) << (s + 1)) + (uint32_t)(t.origin[1] + t.bias);
+  const uint32_t cz = (pcc_compact3(code) << (s + 1)) + (uint32_t)(t.origin[2] + t.bias);
+  const int shift = t.key_shift;
+  auto lower = [&](int64_t lo, uint64_t target) {
+    int64_t hi = n_ref;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (((ref_keys[mid] & kMask48) >> shift) < target) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+  };
+  // every child's own corner: a child's cube (s <= 15 - lod) is aligned under any bias that is a multiple of its side,
+  // the node's own cube need not be (the root of a frame of cells under bias 32768), so the eight ranges are searched
+  // one by one
+  uint32_t byte = 0;
+  for (int j = 0; j < 8; ++j) {
+    const uint32_t jx = (uint32_t)((j >> 2) & 1) << s, jy = (uint32_t)((j >> 1) & 1) << s, jz = (uint32_t)(j & 1) << s;
+    const uint64_t G = (pcc_spread3(cx + jx) << 2) | (pcc_spread3(cy + jy) << 1) | pcc_spread3(cz + jz);
+    const int64_t lo = lower(0, G), hi = lower(lo, G + ((uint64_t)1 << (3 * s)));
+    byte |= hi > lo ? 1u << j : 0u;
+  }
+  rb[i] = (uint8_t)byte;
+}
+
+// every leaf walks up its `depth` links: the octants on the way are its cell inside the root cube
+__global__ __launch_bounds__(256) void k_o4_points(const uint32_t* __restrict__ link, O4Tree t, int32_t* __restrict__ points,
+                                                   int32_t* __restrict__ status) {
+  const int64_t n_nodes = t.off[t.depth], n_points = t.off[t.depth + 1] - n_nodes;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_points) return;
+  uint64_t code = 0;
+  uint32_t idx = (uint32_t)(n_nodes + e);
+  for (int d = 0; d < t.depth; ++d) {
+    const uint32_t l = link[idx];   // a link holds a node of the frame (or 0)
+    code |= (uint64_t)(l & 7u) << (3 * d);
+    idx = l >> 3;
+  }
+  if (idx != 0u) atomicOr(status, 8);
+  points[3 * e] = (int32_t)pcc_compact3(code >> 2) + t.origin[0];
+  points[3 * e + 1] = (int32_t)pcc_compact3(code >> 1) + t.origin[1];
+  points[3 * e + 2] = (int32_t)pcc_compact3(code) + t.origin[2];
+}
+
+// what k_o4_dec needs of a frame
+struct O4Dec {
+  int64_t table_off, payload_off;      // in the body (p0 | chunk table | payload)
+  int64_t n_nodes, start_last, start_prev;
+  int32_t S;
+};
+constexpr int kCarryWords = 512;   // 32-bit words per slot: state, word position, 324 probabilities
+
+// The nodes [a, b) of one level: block = chunk c_lo + blockIdx.x, every lane the part of its run of S nodes that lies in
+// the level.  occ[node] receives the byte, pcl[node - a] its child count; status |= 1 words, 2 an empty node.
+// carry: two slots; slot_in holds what the lane that began its run in an earlier level left, slot_out takes what the
+// lane that goes on in a later level leaves.
+__global__ __launch_bounds__(64) void k_o4_dec(const uint8_t* __restrict__ body, O4Dec d, int64_t a, int64_t b, int64_t c_lo,
+                                               const uint8_t* __restrict__ rb, uint8_t* __restrict__ occ, uint32_t* __restrict__ pcl,
+                                               uint32_t* __restrict__ carry, int slot_in, int slot_out,
+                                               int32_t* __restrict__ status) {
+  __shared__ uint16_t s_model[(kC4 + 1) * kLanes];   // [ctx][lane]; row kC4 takes the writes of decisions that are not coded
+  __shared__ uint16_t s_words[kO4Win];
+  const int lane = threadIdx.x;
+  const int64_t c = c_lo + blockIdx.x;
+  const uint16_t* p0 = reinterpret_cast<const uint16_t*>(body);
+  const uint32_t* table = reinterpret_cast<const uint32_t*>(body + d.table_off);
+  const uint16_t* payload = reinterpret_cast<const uint16_t*>(body + d.payload_off);
+  const int S = d.S;
+  const int64_t n_nodes = d.n_nodes;
+  unsigned long long before = 0;
+  for (int64_t j = lane; j < c; j += kLanes) before += table[j];
+  for (int sh = 32; sh >= 1; sh >>= 1) before += __shfl_xor(before, sh, 64);
+  const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)table[c]);
+  const uint16_t* p = payload + before;   // the chunk table's sum is the payload's length (o4_parse): the chunk is inside it
+  if (cw < 3u * kLanes) {
+    if (lane == 0) atomicOr(status, 1);
+    return;
+  }
+  const uint32_t my_len = p[2 * kLanes + lane];
+  uint32_t incl = my_len;
+#pragma unroll
+  for (int sh = 1; sh < 64; sh <<= 1) {
+    const uint32_t o = (uint32_t)__shfl_up((int)incl, sh, 64);
+    incl += lane >= sh ? o : 0u;
+  }
+  if (3u * kLanes + (uint32_t)__shfl((int)incl, 63, 64) != cw) {   // wave-uniform
+    if (lane == 0) atomicOr(status, 1);
+    return;
+  }
+  const uint32_t rbase = 3u * kLanes + incl - my_len, rend = rbase + my_len;
+  const int64_t node0 = (c * kLanes + lane) * S;
+  const int64_t lo = node0 > a ? node0 : a, hi = node0 + S < b ? node0 + S : b;
+  const bool active = lo < hi;
+  const bool carry_in = active && lo > node0;                   // the run began in an earlier level
+  const bool carry_out = active && hi < node0 + S && hi < n_nodes;   // and goes on in a later one
+  const unsigned long long act_mask = __ballot(active);
+  if (act_mask == 0ull) return;
+  int bad = (node0 >= n_nodes && my_len != 0u) ? 1 : 0;   // a lane without nodes has no words
+  // the model: the frame's initial probabilities, or what the lane left behind
+  for (int ctx = 0; ctx < kC4; ++ctx) s_model[ctx * kLanes + lane] = p0[ctx];
+  uint32_t x = (uint32_t)p[2 * lane] | ((uint32_t)p[2 * lane + 1] << 16);
+  uint32_t pos = rbase;
+  if (carry_in) {
+    const uint32_t* cin = carry + (size_t)slot_in * kCarryWords;
+    x = cin[0];
+    pos = cin[1];
+    for (int ctx = 0; ctx < kC4; ctx += 2) {
+      const uint32_t v = cin[2 + (ctx >> 1)];
+      s_model[ctx * kLanes + lane] = (uint16_t)v;
+      s_model[(ctx + 1) * kLanes + lane] = (uint16_t)(v >> 16);
+    }
+  }
+  // the words of the lanes that decode here, in LDS when they fit
+  const int first_lane = (int)__builtin_ctzll(act_mask), last_lane = 63 - (int)__builtin_clzll(act_mask);
+  const uint32_t w_lo = (uint32_t)__shfl((int)rbase, first_lane, 64), w_hi = (uint32_t)__shfl((int)rend, last_lane, 64);
+  const bool in_lds = w_hi > w_lo && w_hi - w_lo <= (uint32_t)kO4Win;   // wave-uniform
+  if (in_lds)
+    for (uint32_t i = lane; i < w_hi - w_lo; i += kLanes) s_words[i] = p[w_lo + i];
+  __syncthreads();
+  auto word_at = [&](uint32_t i) -> uint32_t {
+    if (in_lds) {
+      const uint32_t ic = i < w_lo ? w_lo : (i >= w_hi ? w_hi - 1u : i);
+      return s_words[ic - w_lo];
+    }
+    return p[i < cw ? i : cw - 1u];   // a lane at the end of its run looks one word too far: never used
+  };
+  uint32_t nextw = word_at(pos);
+  // steps [s_lo, s_hi) of the runs: what some lane of the wave decodes
+  int s_lo = active ? (int)(lo - node0) : S, s_hi = active ? (int)(hi - node0) : 0;
+#pragma unroll
+  for (int sh = 32; sh >= 1; sh >>= 1) {
+    s_lo = min(s_lo, __shfl_xor(s_lo, sh, 64));
+    s_hi = max(s_hi, __shfl_xor(s_hi, sh, 64));
+  }
+  const int a_dummy = kC4 * kLanes + lane;
+  // As in version 2's decoder, the model entry of the NEXT decision is requested before the current one is decoded —
+  // both candidates (the ones so far, and one more) — so that the LDS round trip is not on the chain from state to
+  // state; the reference byte of a node is requested two nodes ahead.  (Two decisions never share a model row: the
+  // row is r, level class, bit position and ones so far.)
+  auto rb_at = [&](int64_t node) -> uint32_t { return (active && node >= lo && node < hi) ? (uint32_t)rb[node] : 0u; };
+  auto row0_of = [&](int64_t node, uint32_t rbyte) -> int {   // the row of a node's decision 0
+    return (rbyte == 0u ? 0 : 108 * (1 + (int)(rbyte & 1u))) + (node >= d.start_last ? 0 : (node >= d.start_prev ? 1 : 2)) * 36;
+  };
+  uint32_t rbyte = rb_at(node0 + s_lo), rbyte_next = rb_at(node0 + s_lo + 1);
+  uint32_t p_cur = s_model[row0_of(node0 + s_lo, rbyte) * kLanes + lane];
+  for (int s = s_lo; s < s_hi; ++s) {
+    const int64_t node = node0 + s;
+    const bool valid = active && node >= lo && node < hi;
+    const uint32_t rbyte_after = rb_at(node + 2);
+    const int cbase = (node >= d.start_last ? 0 : (node >= d.start_prev ? 1 : 2)) * 36;
+    int ones = 0;
+    uint32_t byte = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int r = rbyte == 0u ? 0 : 1 + (int)((rbyte >> j) & 1u);
+      const bool act = valid && !(j == 7 && ones == 0);
+      const int at = act ? (r * 108 + cbase + j * (j + 1) / 2 + ones) * kLanes + lane : a_dummy;
+      uint32_t c0, c1 = 0;
+      if (j < 7) {
+        const int rn = rbyte == 0u ? 0 : 1 + (int)((rbyte >> (j + 1)) & 1u);
+        const int an = (rn * 108 + cbase + (j + 1) * (j + 2) / 2 + ones) * kLanes + lane;
+        c0 = s_model[an];
+        c1 = s_model[an + kLanes];
+      } else {
+        c0 = s_model[row0_of(node + 1, rbyte_next) * kLanes + lane];   // decision 0 of the next node
+      }
+      const uint32_t p1 = p_cur;
+      const uint32_t cum = x & 4095u;
+      const uint32_t dbit = cum >= 4096u - p1 ? 1u : 0u;
+      const uint32_t start = dbit ? 4096u - p1 : 0u, freq = dbit ? p1 : 4096u - p1;
+      const uint32_t xn = freq * (x >> 12) + cum - start;
+      x = act ? xn : x;
+      s_model[at] = (uint16_t)o2_adapt(p1, dbit);
+      const uint32_t bit = act ? dbit : (valid ? 1u : 0u);   // else: the implied bit
+      const bool need = act && x < kL;
+      bad |= (need && pos >= rend) ? 1 : 0;
+      x = need ? (x << 16) | nextw : x;
+      pos += need ? 1u : 0u;
+      nextw = word_at(pos);
+      ones += (int)bit;
+      byte |= bit << j;
+      p_cur = (j < 7 && bit) ? c1 : c0;
+    }
+    rbyte = rbyte_next;
+    rbyte_next = rbyte_after;
+    if (valid) {   // node < b <= n_nodes: inside the arrays the host sized from the header
+      bad |= byte == 0u ? 2 : 0;
+      occ[node] = (uint8_t)byte;
+      pcl[node - a] = (uint32_t)__popc(byte);
+    }
+  }
+  if (carry_out) {
+    uint32_t* cout = carry + (size_t)slot_out * kCarryWords;
+    cout[0] = x;
+    cout[1] = pos;
+    for (int ctx = 0; ctx < kC4; ctx += 2)
+      cout[2 + (ctx >> 1)] = (uint32_t)s_model[ctx * kLanes + lane] | ((uint32_t)s_model[(ctx + 1) * kLanes + lane] << 16);
+  } else if (active && pos != rend) {
+    bad |= 1;   // the run is complete: every word of it consumed
+  }
+  const unsigned long long b1 = __ballot((bad & 1) != 0), b2 = __ballot((bad & 2) != 0);
+  if (lane == 0 && (b1 | b2) != 0ull) atomicOr(status, (b1 ? 1 : 0) | (b2 ? 2 : 0));
+}
+
+inline int64_t o4_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+}  // namespace
+
+// ======================================================================== encoder: the reference bytes
+size_t o4_ref_scratch_bytes(int64_t n_nodes, int64_t n_points) {
+  return 2 * pcc_align((size_t)n_nodes * 4) + pcc_align((size_t)(n_nodes + n_points) * 4) + 1024;
+}
+
+int o4_ref_bytes_async(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, const O4RefJob* jobs, int nf, const uint8_t* occ,
+                       uint8_t* rb, uint32_t* ref_n, unsigned long long* ref_sum, char* scratch, size_t scratch_b) {
+  hipStream_t st = ctx->stream;
+  for (int f = 0; f < nf; ++f) PCC_HIP(hipMemsetD32Async((hipDeviceptr_t)(ref_n + f), (int)(uint32_t)jobs[f].ref_n, 1, st));
+  PCC_HIP(hipMemsetAsync(ref_sum, 0, (size_t)nf * 8, st));
+  const int bias = 32768 >> (key_shift / 3);
+  for (int f = 0; f < nf; ++f) {
+    const O4RefJob& j = jobs[f];
+    const int64_t N = j.off[j.depth];
+    PCC_REQUIRE(o4_ref_scratch_bytes(N, j.n_points) <= scratch_b && j.ref_n >= 1, PCC_E_NOMEM,
+                "octree blob v4: frame %d: scratch of the reference bytes", f);
+    uint32_t* pc = (uint32_t*)scratch;
+    uint32_t* excl = (uint32_t*)(scratch + pcc_align((size_t)N * 4));
+    uint32_t* link = (uint32_t*)(scratch + 2 * pcc_align((size_t)N * 4));
+    O4Tree t;
+    for (int L = 0; L < 18; ++L) t.off[L] = L <= j.depth ? j.off[L] : N + j.n_points;
+    t.depth = j.depth;
+    for (int a = 0; a < 3; ++a) t.origin[a] = j.origin[a];
+    t.bias = bias;
+    t.key_shift = key_shift;
+    const uint8_t* o = occ + j.occ_off;
+    PCC_HIP(hipMemsetAsync(link, 0, 4, st));   // the root's link; every other node's is written
+    hipLaunchKernelGGL(k_o4_popc, dim3(nblk(N, 256)), dim3(256), 0, st, o, N, pc);
+    PCC_CHECK_LAUNCH();
+    PCC_TRY(pcc_scan_exclusive_u32(ctx, pc, excl, N, nullptr));
+    // the whole tree at once: the first child of node i is node 1 + (child counts in front of i); the encoder's own
+    // bytes need no check, the status word is the scratch's tail
+    int32_t* st_dummy = (int32_t*)(scratch + scratch_b - 256);
+    hipLaunchKernelGGL(k_o4_link, dim3(nblk(N, 256)), dim3(256), 0, st, o, (const uint32_t*)excl, (int64_t)0, N, (int64_t)1,
+                       N + j.n_points, link, st_dummy);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_o4_ref, dim3(nblk(N, 256)), dim3(256), 0, st, (const uint32_t*)link, t, (int64_t)0, N, d_keys + j.ref_lo,
+                       j.ref_n, rb + j.occ_off);
+    PCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_o4_keysum, dim3(nblk(j.ref_n, 256)), dim3(256), 0, st, d_keys + j.ref_lo, j.ref_n, key_shift, bias,
+                       ref_sum + f);
+    PCC_CHECK_LAUNCH();
+  }
+  return PCC_OK;
+}
+
+// ======================================================================== decoder
+// one predicted frame, queued on the stream: d_body = p0 | chunk table | payload of the blob (on the device), the
+// reference's keys (bias 32768, sorted) and its sum as k_o4_keys left them -> the frame's points.  The arena is this
+// frame's: reserved here.
+static int o4_decode_one(pcc_ctx* ctx, const O4Info& o, const uint8_t* d_body, const uint64_t* d_ref_keys, int64_t n_ref,
+                         const unsigned long long* d_ref_sum, int32_t* d_points, int32_t* d_status) {
+  hipStream_t st = ctx->stream;
+  const int64_t N = o.n_nodes, n = o.n;
+  int64_t max_level = 1;
+  size_t scan_b = 0;
+  for (int L = 0; L < o.depth; ++L) {
+    max_level = std::max(max_level, o.level_n[L]);
+    scan_b += pcc_scan_scratch_bytes(o.level_n[L]) + 512;
+  }
+  PCC_TRY(pcc_arena_reserve(ctx, 2 * pcc_align((size_t)N + 16) + 2 * pcc_align((size_t)max_level * 4 + 16) +
+                                     pcc_align((size_t)(N + n) * 4) + pcc_align(2 * kCarryWords * 4) + scan_b + 8192));
+  uint8_t* occ = (uint8_t*)pcc_arena_alloc(ctx, (size_t)N + 16);
+  uint8_t* rb = (uint8_t*)pcc_arena_alloc(ctx, (size_t)N + 16);
+  uint32_t* pcl = (uint32_t*)pcc_arena_alloc(ctx, (size_t)max_level * 4 + 16);
+  uint32_t* excl = (uint32_t*)pcc_arena_alloc(ctx, (size_t)max_level * 4 + 16);
+  uint32_t* link = (uint32_t*)pcc_arena_alloc(ctx, (size_t)(N + n) * 4);
+  uint32_t* carry = (uint32_t*)pcc_arena_alloc(ctx, 2 * kCarryWords * 4);
+  if (!occ || !rb || !pcl || !excl || !link || !carry) return PCC_E_NOMEM;
+  O4Tree t;
+  int64_t run = 0;
+  for (int L = 0; L < 18; ++L) {
+    t.off[L] = run;
+    if (L < o.depth) run += o.level_n[L];
+    else if (L == o.depth) run += n;
+  }
+  t.depth = o.depth;
+  for (int a = 0; a < 3; ++a) t.origin[a] = o.origin[a];
+  t.bias = 32768;
+  t.key_shift = 0;
+  O4Dec d;
+  d.table_off = o.off_table - o.off_p0;
+  d.payload_off = o.off_payload - o.off_p0;
+  d.n_nodes = N;
+  d.start_last = N - o.level_n[o.depth - 1];
+  d.start_prev = o.depth >= 2 ? d.start_last - o.level_n[o.depth - 2] : 0;
+  d.S = (int32_t)o.S;
+  hipLaunchKernelGGL(k_o4_refcheck, dim3(1), dim3(1), 0, st, d_ref_sum, (unsigned long long)o.ref_sum, d_status);
+  PCC_CHECK_LAUNCH();
+  PCC_HIP(hipMemsetAsync(link, 0, (size_t)(N + n) * 4, st));
+  const int64_t per_chunk = (int64_t)kLanes * o.S;
+  for (int L = 0; L <= o.depth; ++L) {
+    const int64_t a = t.off[L], b = t.off[L + 1];
+    if (L > 0) {   // the links of this level's nodes (L == depth: of the leaves) from the child counts of the level above
+      const int64_t pa = t.off[L - 1], cnt = a - pa;
+      PCC_TRY(pcc_scan_exclusive_u32(ctx, pcl, excl, cnt, nullptr));
+      hipLaunchKernelGGL(k_o4_link, dim3(nblk(cnt, 256)), dim3(256), 0, st, (const uint8_t*)occ, (const uint32_t*)excl, pa, cnt, a, b,
+                         link, d_status);
+      PCC_CHECK_LAUNCH();
+    }
+    if (L == o.depth) break;
+    hipLaunchKernelGGL(k_o4_ref, dim3(nblk(b - a, 256)), dim3(256), 0, st, (const uint32_t*)link, t, a, b, d_ref_keys, n_ref, rb);
+    PCC_CHECK_LAUNCH();
+    const int64_t c_lo = a / per_chunk, c_hi = (b - 1) / per_chunk;   // < nc: the header's check of S and nc
+    hipLaunchKernelGGL(k_o4_dec, dim3((unsigned)(c_hi - c_lo + 1)), dim3(64), 0, st, d_body, d, a, b, c_lo, (const uint8_t*)rb, occ,
+                       pcl, carry, (L + 1) & 1, L & 1, d_status);
+    PCC_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_o4_points, dim3(nblk(n, 256)), dim3(256), 0, st, (const uint32_t*)link, t, d_points, d_status);
+  PCC_CHECK_LAUNCH();
+  return PCC_OK;
+}
+
+static int o4_named(int rc, const char* who, int frame) {
+  const std::string m = pcc_last_error();
+  pcc_set_error("%s: frame %d: %s", who, frame, m.c_str());
+  return rc;
+}
+
+extern "C" int pcc_octree_decode_frames_ref(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
+                                            const int32_t* d_ref_points, int64_t n_ref, int32_t* d_points, int32_t* h_points,
+                                            int64_t cap_points, int64_t* h_point_offsets) {
+  const char* who = "pcc_octree_decode_frames_ref";
+  PCC_REQUIRE(ctx && h_blobs && h_lens && h_point_offsets && n_frames >= 1 && n_frames <= 65535 && n_ref >= 0 &&
+                  n_ref < ((int64_t)1 << 27) && (n_ref == 0 || d_ref_points),
+              PCC_E_ARG, "%s: bad argument (n_frames=%d n_ref=%lld)", who, n_frames, (long long)n_ref);
+  const int nb = n_frames;
+  std::vector<int> ver((size_t)nb);
+  std::vector<O4Info> info((size_t)nb);
+  int64_t points = 0, bodies = 0, max_n = n_ref;
+  h_point_offsets[0] = 0;
+  for (int f = 0; f < nb; ++f) {
+    const int v = pcc_octree_inter_info(h_blobs[f], h_lens[f], &ver[(size_t)f], &info[(size_t)f].n, nullptr, nullptr);
+    if (v != PCC_OK) return o4_named(v, who, f);
+    if (ver[(size_t)f] == 4) {
+      const int rc = o4_parse(h_blobs[f], h_lens[f], &info[(size_t)f]);
+      if (rc != PCC_OK) return o4_named(rc, who, f);
+      bodies += o4_round(h_lens[f] - info[(size_t)f].off_p0, 16);
+    }
+    points += info[(size_t)f].n;
+    max_n = std::max(max_n, info[(size_t)f].n);
+    h_point_offsets[f + 1] = points;
+  }
+  PCC_REQUIRE(points < ((int64_t)1 << 31), PCC_E_ARG, "%s: the blobs announce %lld points in all", who, (long long)points);
+  if (points == 0 || (!d_points && !h_points)) return PCC_OK;
+  PCC_REQUIRE(cap_points >= points, PCC_E_NOMEM, "%s: %lld points, capacity %lld", who, (long long)points, (long long)cap_points);
+  // what a predicted frame is coded against: the frame decoded before it, for blob 0 the caller's
+  for (int f = 0; f < nb; ++f) {
+    if (ver[(size_t)f] != 4) continue;
+    const int64_t have = f == 0 ? n_ref : info[(size_t)f - 1].n;
+    PCC_REQUIRE(f > 0 || n_ref > 0, PCC_E_ARG, "%s: frame 0: a predicted frame (blob version 4) needs its reference", who);
+    PCC_REQUIRE(have == (int64_t)info[(size_t)f].ref_n, PCC_E_ARG,
+                "%s: frame %d: the reference differs: it has %lld points, the blob was coded against %u", who, f, (long long)have,
+                info[(size_t)f].ref_n);
+  }
+  // the call's own block (the arena is each frame's in turn): points | keys of the reference | bodies | sums | status
+  struct Own {
+    void* p = nullptr;
+    ~Own() { if (p) (void)hipFree(p); }
+  } own;
+  const size_t pts_b = d_points ? 0 : pcc_align((size_t)points * 12), keys_b = pcc_align((size_t)max_n * 8 + 16);
+  const size_t bodies_b = pcc_align((size_t)bodies + 16), sums_b = pcc_align((size_t)nb * 8), stat_b = pcc_align((size_t)nb * 4);
+  PCC_HIP(hipMalloc(&own.p, pts_b + keys_b + bodies_b + sums_b + stat_b));
+  char* base = (char*)own.p;
+  int32_t* pts = d_points ? d_points : (int32_t*)base;
+  uint64_t* keys = (uint64_t*)(base + pts_b);
+  uint8_t* d_bodies = (uint8_t*)(base + pts_b + keys_b);
+  unsigned long long* sums = (unsigned long long*)(base + pts_b + keys_b + bodies_b);
+  int32_t* status = (int32_t*)(base + pts_b + keys_b + bodies_b + sums_b);
+  hipStream_t st = ctx->stream;
+  PccProfScope prof(ctx, "octree4_decode", points, nb, 0, 0);
+  PCC_HIP(hipMemsetAsync(sums, 0, sums_b + stat_b, st));
+  int64_t body_at = 0;
+  for (int f = 0; f < nb; ++f) {
+    const O4Info& o = info[(size_t)f];
+    int32_t* out = pts + 3 * h_point_offsets[f];
+    if (o.n == 0) continue;
+    if (ver[(size_t)f] != 4) {   // an intra frame: version 2's decoder, to its place in the output
+      int64_t offs2[2];
+      const int rc = pcc_octree_decode_frames(ctx, h_blobs + f, h_lens + f, 1, out, nullptr, o.n, offs2);
+      if (rc != PCC_OK) {
+        const std::string m = pcc_last_error();
+        pcc_set_error("%s: frame %d: %s", who, f, m.c_str());
+        return rc;
+      }
+      continue;
+    }
+    const int32_t* ref = f == 0 ? d_ref_points : pts + 3 * h_point_offsets[f - 1];
+    const int64_t rn = (int64_t)o.ref_n;
+    hipLaunchKernelGGL(k_o4_keys, dim3(nblk(rn, 256)), dim3(256), 0, st, ref, rn, keys, sums + f, status + f);
+    PCC_CHECK_LAUNCH();
+    const int64_t body_b = h_lens[f] - o.off_p0;
+    PCC_HIP(hipMemcpyAsync(d_bodies + body_at, h_blobs[f] + o.off_p0, (size_t)body_b, hipMemcpyHostToDevice, st));
+    PCC_TRY(o4_decode_one(ctx, o, d_bodies + body_at, keys, rn, sums + f, out, status + f));
+    body_at += o4_round(body_b, 16);
+  }
+  std::vector<int32_t> h_status((size_t)nb);
+  PCC_HIP(hipMemcpyAsync(h_status.data(), status, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+  PCC_HIP(hipStreamSynchronize(st));
+  for (int f = 0; f < nb; ++f) {
+    const int32_t bad = h_status[(size_t)f];
+    PCC_REQUIRE(!(bad & 32), PCC_E_ARG, "%s: frame %d: the reference is not a set of distinct int16 points in Morton order", who, f);
+    PCC_REQUIRE(!(bad & 16), PCC_E_ARG, "%s: frame %d: the reference differs from the one the blob was coded against (ref_sum)", who, f);
+    PCC_REQUIRE(bad == 0, PCC_E_STREAM, "%s: frame %d: octree blob v4: corrupt stream (status %d: 1 = words, 2 = empty node, 8 = counts)",
+                who, f, bad);
+  }
+  if (h_points) {
+    PCC_HIP(hipMemcpyAsync(h_points, pts, (size_t)points * 12, hipMemcpyDeviceToHost, st));
+    PCC_HIP(hipStreamSynchronize(st));
+  }
+  return PCC_OK;
+}
+
+// host only: what the head of a geometry blob of version 2 or 4 says
+extern "C" int pcc_octree_inter_info(const uint8_t* h_in, int64_t len, int* version, int64_t* points, int* predicted,
+                                     int64_t* ref_points) {
+  if (!h_in || len < kO4Header || h_in[0] != 'O' || (h_in[1] != 2 && h_in[1] != 4)) {
+    pcc_set_error("pcc_octree_inter_info: not an octree blob of version 2 or 4 (len=%lld)", (long long)len);
+    return PCC_E_STREAM;
+  }
+  int64_t n = 0, rn = 0;
+  if (h_in[1] == 2) {
+    O2Info o;
+    O2Plan pl;
+    PCC_TRY(o2_parse(h_in, len, 0, true, &o, &pl));
+    n = o.n;
+  } else {
+    O4Info o;
+    PCC_TRY(o4_parse(h_in, len, &o));
+    n = o.n;
+    rn = (int64_t)o.ref_n;
+  }
+  if (version) *version = h_in[1];
+  if (points) *points = n;
+  if (predicted) *predicted = h_in[1] == 4 ? 1 : 0;
+  if (ref_points) *ref_points = rn;
+  return PCC_OK;
+}

@@ -18,6 +18,21 @@ Levels of detail (csrc/octree2_blob.h has the rule): a stored blob holds every c
     cells = codec.decompress([b[:nbytes]], lod=2)        # int32 [cells, 3]: the distinct points >> 2, Morton order
     blobs = codec.compress(frames, lod=2)                # the sender's side: blobs of those cells themselves
 
+Inter-frame prediction (octree blob version 4, csrc/octree4.hip; include/pcc.h has the rule): a frame coded against
+the frame before it — every context of version 2 split in three by whether the previous frame has points in the
+node's cube and in the child's — about a fifth shorter for consecutive LiDAR sweeps (DESIGN.md 6c has the figures).
+A predicted frame decodes level by level and only behind its reference, so a chain decodes frame after frame.
+
+    blobs = codec.compress(frames, predict="previous")                     # frame 0 intra (version 2), the others predicted
+    blobs = codec.compress(frames, predict="previous", intra_period=10)    # frames 0, 10, 20, .. are random-access points
+    GeometryCodec.geometry_info(blobs[1])      # {"version": 4, "points": n, "predicted": True, "reference_points": n_0}; host only
+    frames = codec.decompress(blobs)                                       # any mix of versions 2 and 4
+    (b,) = codec.compress([pts_t], predict="previous", reference=pts_t_minus_1)    # a streaming sender: one frame per call
+    (pts_t,) = codec.decompress([b], reference=pts_t_minus_1)              # the receiver keeps its last decoded frame
+
+Not built: decoding version 4 at lod > 0 (the format allows it), choosing per frame the shorter of versions 2 and 4,
+motion compensation, prediction of attributes (they see only the decoded Morton order and are coded as before).
+
 Attributes are lossless (attribute blob version 1, csrc/attr.hip), one blob per frame beside its geometry blob; the
 values of duplicate points merge to their rounded mean per channel, (sum + cnt // 2) // cnt.
 
@@ -441,7 +456,7 @@ class GeometryCodec:
 
     def compress(self, frames, attributes=None, lod=0, scalable=False, *, voxel=None, origin=(0.0, 0.0, 0.0),
                  invalid="raise", return_index=False, max_error=0, cross_channel=False, qstep=0, colour=None,
-                 scalable_to=None, target_bytes=None, target_frame_bytes=None):
+                 scalable_to=None, target_bytes=None, target_frame_bytes=None, predict=None, intra_period=None, reference=None):
         """frames: a sequence of int16 / int32 [n_f, 3] arrays -> a list of bytes, one version-2 blob per frame.
         Duplicate points are removed (as np.unique), out-of-range coordinates raise PccError (PCC_E_RANGE).
         lod = k > 0: the sender's side of a level of detail — blob f is the version-2 blob of the distinct cells
@@ -520,9 +535,22 @@ class GeometryCodec:
         effect on integer frames.
         return_index=True appends `index` to the result, (blobs, index) or (blobs, attr_blobs, index): index[f] is int32
         [n_f], index[f][i] the row of decompress(blobs)[f] that input row i became (duplicates share a row; with lod = k
-        the row of the cell), -1 for a dropped row; numpy arrays for host frames, device tensors for device frames."""
+        the row of the cell), -1 for a dropped row; numpy arrays for host frames, device tensors for device frames.
+        predict="previous" (any other value but None: ValueError): inter-frame prediction — every frame but the intra
+        ones is a blob of version 4 (include/pcc.h has the rule), coded against the frame in front of it in the call,
+        about a fifth shorter for consecutive LiDAR sweeps; decompress needs the frames in front of it back to an intra
+        frame (geometry_info says which blobs those are).  intra_period = G (an integer >= 1; bool or non-integer:
+        TypeError; below 1, or without predict: ValueError): frames 0, G, 2 G, .. are intra (version 2, the bytes of
+        before); None: frame 0 alone.  reference (without predict: ValueError): one frame of the same kind and place as
+        `frames`, put through the same front end (voxel, invalid, duplicates, lod) as frame -1 of the call, so that
+        frame 0 is predicted too — a streaming sender codes one frame per call against the last.  A frame without
+        points stays the 24-byte blob, and the frame behind it (or behind a reference without points) is intra.
+        Attributes of every kind, lod=k (frame and reference are both the cells), float32 and device frames,
+        return_index and the byte targets combine with it as before: they see the decoded Morton order alone.  The
+        defaults write the bytes of before."""
         lod = self._check_lod(lod)
         frames, is_float, on_device = self._check_frames(frames)
+        intra_period, reference = self._check_predict(predict, intra_period, reference, is_float, on_device, len(frames))
         if invalid not in ("raise", "drop"):
             raise ValueError(f"invalid must be 'raise' or 'drop', got {invalid!r}")
         if is_float:
@@ -551,7 +579,11 @@ class GeometryCodec:
                                 invalid == "drop")
             if front.n_keep == 0:
                 return result(*self._nothing_coded(rt, front, attrs, coding, return_index, on_device))
-            blobs = rt.octree_encode_frames(front.keys, nb, 3 * lod)
+            if predict is None:
+                blobs = rt.octree_encode_frames(front.keys, nb, 3 * lod)
+            else:
+                blobs = self._encode_predicted(rt, front, nb, lod, intra_period, reference, is_float, on_device, caller, voxel,
+                                               origin, invalid == "drop")
             attr_blobs = index = None
             if attrs is not None:
                 if target_frame_bytes is not None:      # what the geometry blob leaves; nothing left: a target no blob meets, the coarsest steps
@@ -564,6 +596,48 @@ class GeometryCodec:
                                       rt.to_device(first_run), nb)
                 index = self._split_index(index, front.sizes, on_device)
             return result(blobs, attr_blobs, index)
+
+    def _check_predict(self, predict, intra_period, reference, is_float, on_device, nb):
+        """predict, intra_period and reference of compress -> (the period the library takes: 0 = frame 0 alone, the
+        reference as _check_frames returns a frame, or None)"""
+        if predict is not None and not (isinstance(predict, str) and predict == "previous"):
+            raise ValueError(f"predict must be None or 'previous', got {predict!r}")
+        if intra_period is not None:
+            if isinstance(intra_period, bool) or not isinstance(intra_period, (int, np.integer)):
+                raise TypeError(f"intra_period must be an integer >= 1, got {intra_period!r}")
+            if intra_period < 1:
+                raise ValueError(f"intra_period must be an integer >= 1, got {intra_period}")
+            if predict is None:
+                raise ValueError("intra_period is the distance of the intra frames under prediction: it needs predict='previous'")
+        if reference is None:
+            return int(intra_period or 0), None
+        if predict is None:
+            raise ValueError("reference is what frame 0 is predicted from: it needs predict='previous'")
+        try:
+            (ref,), ref_float, ref_device = self._check_frames([reference])
+        except (TypeError, ValueError) as e:
+            raise type(e)("reference: " + str(e).replace("frame 0: ", "")) from None
+        if nb and (ref_float != is_float or ref_device != on_device):
+            raise ValueError("reference: one frame of the same kind (integer or float32) and place (host or device) as the frames")
+        return int(intra_period or 0), ref
+
+    def _encode_predicted(self, rt, front, nb, lod, intra_period, reference, is_float, on_device, caller, voxel, origin, drop):
+        """the geometry blobs of a call under predict='previous': the call's distinct keys, behind the reference's as
+        frame 0 of the library's call where there is one"""
+        if reference is not None:
+            ref = self._front(rt, [reference], is_float, on_device, caller, "GeometryCodec.compress (reference)", lod, voxel,
+                              origin, drop)
+            if ref.n_keep:      # (a reference without points predicts nothing: frame 0 is intra)
+                keys = torch.cat([ref.keys, front.keys + (1 << 48)])
+                return rt.octree_encode_frames_inter(keys, nb + 1, 3 * lod, intra_period, ref_first=True)
+        return rt.octree_encode_frames_inter(front.keys, nb, 3 * lod, intra_period)
+
+    @staticmethod
+    def geometry_info(blob):
+        """what the head of a geometry blob of version 2 or 4 says: {"version", "points", "predicted",
+        "reference_points"} — predicted False marks a random-access point of a sequence, a predicted blob decodes
+        only behind the frame it was coded against, whose point count is reference_points.  Host only; the blob whole."""
+        return Runtime.octree_inter_info(bytes(blob))
 
     @staticmethod
     def _attr_coding(attrs, nb, lod, scalable, max_error, cross_channel, qstep, colour, scalable_to, target_bytes, target_frame_bytes):
@@ -699,7 +773,7 @@ class GeometryCodec:
         # a byte target: the steps from qstep upwards that the search chooses, frame by frame, through the public binding
         return rt.attr_encode_frames_rate(*call, coding.qstep, coding.colour, list(coding.targets), coding.scratch_limit)[0]
 
-    def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0, *, voxel=None, origin=(0.0, 0.0, 0.0)):
+    def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0, *, voxel=None, origin=(0.0, 0.0, 0.0), reference=None):
         """version-2 blobs -> a list of int32 [n_f, 3] point sets in Morton order: numpy arrays (output="numpy") or
         device tensors (output="device", on this codec's device).  With attr_blobs (compress(..., attributes=...)):
         (point sets, attributes), attributes[f] an [n_f, c] array in its original dtype, row i belonging to point i; an
@@ -719,7 +793,12 @@ class GeometryCodec:
         x = origin + t * voxel, one float32 multiplication and then one addition on the device (include/pcc.h has the
         rule): t the lattice index at lod 0 and, at lod k, the centre of the cell's lattice points
         (c << k) + (2^k - 1) / 2 — a half-integer, not the integer centre above, which stays the centre in lattice
-        units.  The blobs do not hold voxel or origin: pass what compress was given.  Attributes are unchanged."""
+        units.  The blobs do not hold voxel or origin: pass what compress was given.  Attributes are unchanged.
+        Blobs of version 4 (compress(..., predict="previous")) may stand among the blobs: each is decoded against the
+        frame decoded before it in the call, blob 0 against `reference` — an int16 / int32 [n, 3] lattice frame, numpy or
+        on this codec's device, in any row order and with duplicates: the decoded frame before it.  Without the
+        reference, or with another one than the sender's, PccError names the frame.  Version 4 decodes at lod 0: at
+        lod > 0 ValueError names the frame.  A call without a version-4 blob is the call of before."""
         if isinstance(attr_blobs, str):      # decompress(blobs, "device"), as before attributes
             attr_blobs, output = None, attr_blobs
         if output not in ("numpy", "device"):
@@ -730,6 +809,18 @@ class GeometryCodec:
         blobs = [bytes(b) for b in blobs]
         if len(blobs) > MAX_FRAMES:
             raise ValueError(f"{len(blobs)} blobs in one call, at most {MAX_FRAMES}")
+        ref_device = False
+        if reference is not None:
+            try:
+                (reference,), ref_float, ref_device = self._check_frames([reference])
+            except (TypeError, ValueError) as e:
+                raise type(e)("reference: " + str(e).replace("frame 0: ", "")) from None
+            if ref_float:
+                raise TypeError("reference: expected the int16 / int32 lattice frame that was decoded before blob 0, got float32")
+        predicted = [f for f, b in enumerate(blobs) if len(b) > 1 and b[1] == 4]
+        if predicted and lod:
+            raise ValueError(f"frame {predicted[0]}: blob version 4 (a predicted frame) decodes at lod 0 only; lod {lod} needs "
+                             "the sender's compress(..., lod=k, predict='previous')")
         if attr_blobs is not None:
             attr_blobs = [bytes(b) for b in attr_blobs]
             if len(attr_blobs) != len(blobs):
@@ -753,15 +844,24 @@ class GeometryCodec:
                                  "is one predictive stream in full-resolution Morton order, so neither its bytes nor "
                                  "its decoding can be cut; store version 2, 7, 11 or 14 (compress(..., scalable=True)) or ship "
                                  "coarse attributes with compress(frames, attributes=..., lod=k)")
+        caller = torch.cuda.current_stream(self.rt.device) if (predicted and ref_device) else None
         with self._lock, self.rt as rt:
+            if predicted:      # the new entry point, and the reference as a decode returns it: distinct, Morton order
+                ref = None
+                if reference is not None and reference.shape[0]:
+                    front = self._front(rt, [reference], False, ref_device, caller, "GeometryCodec.decompress (reference)")
+                    ref = rt.keys_to_coords(front.keys)[:, 1:].contiguous()
+                decode = lambda blobs, device, lod, whole=False: rt.octree_decode_frames_ref(blobs, ref, device=device, whole=whole)   # noqa: E731
+            else:
+                decode = lambda blobs, device, lod, whole=False: rt.octree_decode_frames(blobs, device=device, lod=lod, whole=whole)   # noqa: E731
             # version 2 reads the cells where the geometry decode left them: on the device
             one_call = attr_blobs is not None and all(v1) and len(set(kind)) == 1
             on_device = attr_blobs is not None and not one_call
             if voxel is not None:      # the points in the caller's unit, dequantised where the decode left them
-                cells, whole = rt.octree_decode_frames(blobs, device=True, lod=lod, whole=True)
+                cells, whole = decode(blobs, device=True, lod=lod, whole=True)
                 frames = self._metric_frames(rt, cells, whole, lod, voxel, origin, output)
             else:
-                frames = rt.octree_decode_frames(blobs, device=(output == "device" or on_device), lod=lod)
+                frames = decode(blobs, device=(output == "device" or on_device), lod=lod)
                 cells = frames
             if attr_blobs is None:
                 return frames

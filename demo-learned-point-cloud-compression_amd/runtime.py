@@ -697,6 +697,50 @@ class Runtime:
         views = [pts[offs[f]:offs[f + 1]] for f in range(nb)]
         return (views, pts) if whole else views
 
+    def octree_encode_frames_inter(self, keys, n_frames, key_shift=0, intra_period=0, ref_first=False):
+        """octree_encode_frames with inter-frame prediction (pcc_octree_encode_frames_inter; include/pcc.h has the
+        rule): every frame but the intra ones — the coded frames g with g % intra_period == 0, or with intra_period 0
+        the first frame of the keys alone — is a blob of version 4, coded against the frame in front of it.
+        ref_first: frame 0 of the keys is only the reference of frame 1 and gets no blob: n_frames - 1 blobs."""
+        n = keys.shape[0]
+        cap = 8192 * n_frames + 17 * max(n, 1)
+        out = np.empty(cap, dtype=np.uint8)
+        offs = (C.c_int64 * (n_frames + 1))()
+        check(self.lib.pcc_octree_encode_frames_inter(self.ctx, _ptr(keys), n, n_frames, key_shift, int(intra_period),
+                                                      1 if ref_first else 0, _np_ptr(out), cap, offs),
+              "pcc_octree_encode_frames_inter")
+        return [out[offs[f]:offs[f + 1]].tobytes() for f in range(1 if ref_first else 0, n_frames)]
+
+    def octree_decode_frames_ref(self, blobs, reference=None, device=False, whole=False):
+        """blobs of versions 2 and 4 in any mix -> one int32 [n_f, 3] array per blob, as octree_decode_frames
+        (pcc_octree_decode_frames_ref).  The reference of a version-4 blob is the frame decoded before it; for blob 0 it
+        is `reference`, an int32 [n, 3] device tensor of distinct points in Morton order, as a decode returns them."""
+        nb = len(blobs)
+        if nb == 0:
+            return ([], None) if whole else []
+        bufs = [np.frombuffer(b, dtype=np.uint8) for b in blobs]
+        ptrs = (C.c_void_p * nb)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
+        lens = (C.c_int64 * nb)(*[b.shape[0] for b in bufs])
+        offs = (C.c_int64 * (nb + 1))()
+        n_ref = 0 if reference is None else int(reference.shape[0])
+        ref_ptr = _ptr(reference) if n_ref else None
+        call = lambda *a: self.lib.pcc_octree_decode_frames_ref(self.ctx, ptrs, lens, nb, ref_ptr, n_ref, *a, offs)
+        pts = self._sized_output(call, "pcc_octree_decode_frames_ref", offs, lambda total: (total, 3), torch.int32, device)
+        views = [pts[offs[f]:offs[f + 1]] for f in range(nb)]
+        return (views, pts) if whole else views
+
+    @staticmethod
+    def octree_inter_info(blob):
+        """what the head of a geometry blob of version 2 or 4 says (pcc_octree_inter_info, host only; the blob whole):
+        {"version", "points", "predicted", "reference_points"}"""
+        buf = np.frombuffer(blob, dtype=np.uint8)
+        version, predicted = C.c_int(0), C.c_int(0)
+        points, ref_points = C.c_int64(0), C.c_int64(0)
+        check(_abi.lib().pcc_octree_inter_info(_np_ptr(buf) if buf.shape[0] else None, buf.shape[0], C.byref(version),
+                                               C.byref(points), C.byref(predicted), C.byref(ref_points)), "pcc_octree_inter_info")
+        return {"version": version.value, "points": points.value, "predicted": bool(predicted.value),
+                "reference_points": ref_points.value}
+
     def _sized_output(self, call, name, offs, shape, dtype, device):
         """the two phases of a frame decoder's output: call(None, None, 0) for the sizes, which it leaves in `offs`; then
         shape(total) of `dtype` on the device, or pinned on the host, where the library copies straight into it (torch's

@@ -124,6 +124,42 @@ def lidar_sweep(n_beams=64, n_az=1800, seed=0, voxel=0.02):
     return frame(pts, rng)
 
 
+def lidar_sequence(n_frames, n_beams=64, n_az=1800, seed=0, velocity=(0, 0, 0), dt=0.1, voxel=0.02):
+    """consecutive sweeps of one scene (inter-frame geometry coding): lidar_sweep's scene — ground plane + 30 boxes —
+    under the one scene seed `seed`, frame t cast from the sensor position t * dt * velocity (metres, metres / second)
+    with its own noise seed, the points in the sensor's frame as a LiDAR reports them.  A list of n_frames frames."""
+    scene = np.random.default_rng(seed)
+    boxes = []
+    h = 1.73
+    for _ in range(30):
+        c = np.array([scene.uniform(-40, 40), scene.uniform(-40, 40), scene.uniform(-h, 0.5)])
+        half = np.array([scene.uniform(0.5, 4), scene.uniform(0.5, 4), scene.uniform(0.5, 2)])
+        boxes.append((c - half, c + half))
+    el = np.deg2rad(np.linspace(-24.8, 2.0, n_beams))
+    az = np.linspace(0, 2 * np.pi, n_az, endpoint=False)
+    el, az = np.meshgrid(el, az, indexing="ij")
+    d = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], -1).reshape(-1, 3)
+    out = []
+    for f in range(n_frames):
+        rng = np.random.default_rng([seed, f + 1])
+        pos = f * dt * np.asarray(velocity, dtype=np.float64)
+        t = np.full(d.shape[0], np.inf)
+        down = d[:, 2] < -1e-3
+        t[down] = -(h + pos[2]) / d[down, 2]
+        for lo, hi in boxes:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                t1, t2 = (lo - pos) / d, (hi - pos) / d
+            tn, tf = np.minimum(t1, t2).max(1), np.maximum(t1, t2).min(1)
+            hit = (tn < tf) & (tn > 0.5)
+            t = np.where(hit & (tn < t), tn, t)
+        ok = np.isfinite(t) & (t > 0) & (t < 80)
+        p = d[ok] * t[ok, None] + rng.normal(0, 0.005, (ok.sum(), 3))
+        pts = np.rint(p / voxel).astype(np.int64)
+        pts = pts[(np.abs(pts) < 32000).all(1)]
+        out.append(frame(pts, rng))
+    return out
+
+
 def lidar_intensity(points, seed=0):
     """intensity (reflectance) of a sweep's points, uint8 [n]: range r = 0.02 |p| metres; reflectivity 0.3 on the ground
     (0.02 z < -1.55), else a seeded uniform value in [0.1, 0.9] per 2-m cell floor(p / 100);

@@ -736,6 +736,75 @@ int pcc_octree_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs,
                                  int32_t* d_points, int32_t* h_points,
                                  int64_t cap_points, int64_t* h_point_offsets);
 
+/* Inter-frame geometry coding: octree blob version 4, a PREDICTED frame
+ * (csrc/octree4.hip, csrc/octree4_blob.h).  Version 4 is version 2 with three
+ * changes; the tree, the root cube, the breadth-first numbering, the dealing
+ * of nodes in runs of S to the 64 lanes of a chunk, the per-lane rANS states,
+ * word runs, length table, chunk table, the p0 formula, the adaptation and the
+ * implied eighth bit are version 2's.
+ *   'O' 4 depth 0 | u32 n | i32 origin[3] | u32 payload_len |
+ *   u32 level_n[depth] | u32 S | u32 n_chunks | u32 ref_n | u64 ref_sum |
+ *   u16 p0[324] | u32 words[n_chunks] | chunks
+ * Reference byte: R, the reference, is a set of distinct lattice points in the
+ *   units of the frame.  Bit j of a node's reference byte is 1 exactly when R
+ *   holds a point inside the cube of the node's child octant j (octants as in
+ *   version 2: x is the top bit).  Purely geometric: R's own root cube and
+ *   depth do not matter, and a node out of R's reach has reference byte 0.
+ *   With key_shift = 3 k (the sender's side of a level of detail) frame and
+ *   reference are both the cells at lod k.
+ * Context of decision j of a node: r * 108 + (version 2's context), r = 0
+ *   where the node's reference byte is 0, 1 where it is not and its bit j is
+ *   0, 2 where its bit j is 1.  p0[324] from the frame's counts per context
+ *   with version 2's formula; a context never seen gets that of (0, 0).
+ * ref_n = |R|; ref_sum = the sum over R's points of
+ *   ((x & 0xFFFF) << 32) | ((y & 0xFFFF) << 16) | (z & 0xFFFF) mod 2^64, the
+ *   coordinates as a decoder returns them.  A decoder that holds another
+ *   reference refuses the blob.
+ * S: the encoder deals runs of at most 256 nodes (version 2: 512), because a
+ *   level's launch of the decoder lasts up to 8 S dependent steps of a wave;
+ *   a decoder takes S from the header, any multiple of 4 in 4 .. 512.
+ * A frame without points stays the 24-byte version-2 blob; a frame whose
+ *   reference has no points is written as version 2.  The levels above a cut
+ *   are still a prefix of the bytes; decoding version 4 at lod > 0 is not
+ *   built (the format allows it: a reference byte above the cut needs only the
+ *   reference's cells at that lod).
+ *   _encode_frames_inter : pcc_octree_encode_frames whose frames are coded
+ *     against the frame in front of them in the call.  intra_period = G >= 1:
+ *     the coded frames g with g % G == 0 are version 2; 0: only the first
+ *     frame of the keys is.  ref_first = 1: frame 0 of the keys is only the
+ *     reference of frame 1: it gets no blob (h_offsets[1] == h_offsets[0]) and
+ *     does not count in g.  Lossless coding makes the original the decoded
+ *     frame, so all frames encode side by side: the intra frames in one batch,
+ *     the predicted ones in another with one search kernel in front.
+ *   _decode_frames_ref : any mix of versions 2 and 4.  The reference of a
+ *     version-4 blob is the frame decoded before it in the call, for blob 0
+ *     d_ref_points: int32 [n_ref,3], distinct, in Morton order, as a decode
+ *     returns them.  A version-4 blob 0 without a reference, or a reference
+ *     other than the one a blob was coded against (ref_n on the host, ref_sum
+ *     and the order of d_ref_points on the device, read with the call's last
+ *     synchronisation): PCC_E_ARG naming the frame.  A predicted frame decodes
+ *     level by level, every wait a kernel boundary, launch sizes from the
+ *     header alone; a damaged blob is PCC_E_STREAM naming the frame, and no
+ *     access leaves what the header checks sized.  Outputs as
+ *     pcc_octree_decode_frames'.
+ *   _inter_info : host only, versions 2 and 4: version, points, predicted
+ *     (0 / 1) and ref_points (0 for version 2), each nullable; the blob must
+ *     be whole.
+ * pcc_octree_decode_frames, _decode_frames_lod, _lod_info, _blob_version and
+ * the one-blob entries go on refusing version 4. */
+int pcc_octree_encode_frames_inter(pcc_ctx* ctx, const uint64_t* d_keys,
+                                   int64_t n, int n_frames, int key_shift,
+                                   int intra_period, int ref_first,
+                                   uint8_t* h_out, int64_t cap,
+                                   int64_t* h_offsets);
+int pcc_octree_decode_frames_ref(pcc_ctx* ctx, const uint8_t* const* h_blobs,
+                                 const int64_t* h_lens, int n_frames,
+                                 const int32_t* d_ref_points, int64_t n_ref,
+                                 int32_t* d_points, int32_t* h_points,
+                                 int64_t cap_points, int64_t* h_point_offsets);
+int pcc_octree_inter_info(const uint8_t* h_in, int64_t len, int* version,
+                          int64_t* points, int* predicted, int64_t* ref_points);
+
 /* Lossless per-point attributes of such a sequence (near-lossless ones with a
  * bounded error: pcc_attr_encode_frames_nl below) (csrc/attr.hip: attribute
  * blob version 1, one per frame, its layout in that file's header): uint8 or

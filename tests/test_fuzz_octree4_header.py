@@ -1,0 +1,27 @@
+"""The version-4 octree blob's header parser (csrc/octree4_blob.h), which reads untrusted bytes before anything is
+reserved or launched, under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU: damaged blobs and blobs cut
+anywhere give error codes, an accepted header sizes nothing beyond the bytes present, and no sanitizer reports."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "demo-learned-point-cloud-compression_amd", "csrc")
+
+
+def test_octree4_header_parser_under_sanitizers(tmp_path):
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    exe = str(tmp_path / "fuzz_octree4_header")
+    src = os.path.join(ROOT, "tests", "fuzz", "fuzz_octree4_header.cpp")
+    build = subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-std=c++17",
+                            "-w", "-I", CSRC, "-I", os.path.join(ROOT, "include"), src, "-o", exe], capture_output=True, text=True)
+    if build.returncode != 0 and "sanitize" in build.stderr:
+        pytest.skip("this toolchain has no sanitizer runtime")
+    assert build.returncode == 0, build.stderr[-2000:]
+    run = subprocess.run([exe, "20000"], capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, (run.stdout[-1000:], run.stderr[-3000:])
+    assert "fuzz:" in run.stdout and "ERROR" not in run.stderr and "runtime error" not in run.stderr

@@ -1,0 +1,84 @@
+#!/usr/bin/env python3
+"""Inter-frame geometry coding (octree blob version 4) on one MI355X: a sequence of LiDAR sweeps,
+workloads.lidar_sequence(10, 64, 1800), with the sensor at rest and at 10 m/s.  Per velocity, in one run: bytes per
+frame of version 2 and of version 4; encode and decode milliseconds per frame of each, from Morton-sorted keys in HBM
+to blobs on the host and back to host coordinates (version 2 through pcc_octree_encode_frames /
+pcc_octree_decode_frames, unchanged); and the decode time of one predicted sweep for runs of at most 128, 256 and 512
+nodes per lane (the blobs of the other two bounds come from the reference coder of tests/octree_inter_ref.py, the
+decoder takes S from the header).  PROFILE=1 adds the device time of the calls.  One JSON line per velocity."""
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+PKG = "demo-learned-point-cloud-compression_amd"
+
+
+def timed(fn, reps):
+    """median wall milliseconds of fn() behind two warm-up calls, and its last result"""
+    t = []
+    for it in range(reps + 2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        t1 = time.perf_counter()
+        if it >= 2:
+            t.append(t1 - t0)
+    return 1e3 * float(np.median(t)), out
+
+
+def main():
+    importlib.import_module(PKG)
+    wl = importlib.import_module(PKG + ".workloads")
+    rtm = importlib.import_module(PKG + ".runtime")
+    rt = rtm.Runtime(0)
+    reps = int(os.environ.get("REPS", "10"))
+    n_frames = int(os.environ.get("FRAMES", "10"))
+    s_bounds = [int(s) for s in os.environ.get("SMAX", "128,256,512").split(",") if s]
+    with rt:
+        for velocity in ((0, 0, 0), (10, 0, 0)):
+            frames = [f["points"].astype(np.int32) for f in wl.lidar_sequence(n_frames, 64, 1800, velocity=velocity)]
+            coords = np.concatenate([np.concatenate([np.full((p.shape[0], 1), f, np.int32), p], 1) for f, p in enumerate(frames)])
+            keys = rt.morton_keys(rt.to_device(coords))
+            rt.sort_pairs(keys)
+            res = {"velocity": velocity, "frames": n_frames, "points": [int(p.shape[0]) for p in frames]}
+            enc2, b2 = timed(lambda: rt.octree_encode_frames(keys, n_frames), reps)
+            enc4, b4 = timed(lambda: rt.octree_encode_frames_inter(keys, n_frames), reps)
+            dec2, p2 = timed(lambda: rt.octree_decode_frames(b2), reps)
+            dec4, p4 = timed(lambda: rt.octree_decode_frames_ref(b4), reps)
+            assert all(np.array_equal(a, b) for a, b in zip(p2, p4))
+            res["v2"] = {"bytes": [len(b) for b in b2], "encode_ms_per_frame": enc2 / n_frames, "decode_ms_per_frame": dec2 / n_frames}
+            res["v4"] = {"bytes": [len(b) for b in b4], "encode_ms_per_frame": enc4 / n_frames, "decode_ms_per_frame": dec4 / n_frames,
+                         "bytes_ratio_predicted": sum(len(b) for b in b4[1:]) / sum(len(b) for b in b2[1:])}
+            # one predicted sweep, one call: blob 1 against frame 0 on the device; beside it one version-2 sweep, one call
+            ref = rt.to_device(p2[0])
+            one2, _ = timed(lambda: rt.octree_decode_frames(b2[1:2]), reps)
+            res["one_sweep_decode_ms"] = {"v2": one2}
+            if s_bounds:
+                import octree_inter_ref as ref4
+                for smax in s_bounds:
+                    blob = b4[1] if smax == 256 else ref4.encode(frames[1], frames[0], smax=smax)
+                    ms, got = timed(lambda: rt.octree_decode_frames_ref([blob], ref), reps)
+                    assert np.array_equal(got[0], p2[1])
+                    h = ref4.header(blob)
+                    res["one_sweep_decode_ms"]["v4 S<=%d" % smax] = {"ms": ms, "S": h["S"], "chunks": h["nc"], "bytes": len(blob)}
+            if os.environ.get("PROFILE"):
+                rt.prof_enable(True, reserve=64)
+                rt.octree_encode_frames_inter(keys, n_frames)
+                rt.octree_decode_frames_ref(b4[1:2], ref)
+                torch.cuda.synchronize()
+                res["device_ms"] = [(op, round(ms, 4)) for op, ms, _ in rt.prof_records()]
+                rt.prof_enable(False)
+            print(json.dumps(res), flush=True)
+    rt.close()
+
+
+if __name__ == "__main__":
+    main()
