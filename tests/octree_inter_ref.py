@@ -107,11 +107,21 @@ def _layout(n_nodes, smax):
     return S, nc
 
 
-def encode_payload(levels, rb, n_ctx, smax):
-    """(S, nc, p0, chunks): the lanes' rANS streams of the occupancy bytes under contexts r * 108 + version 2's"""
+def _forced_layout(n_nodes, S):
+    """a layout the format allows and no encoder of the project chooses: any multiple of 4 in 4 .. 512 as S, minimal
+    or not; the chunk count is what S makes it"""
+    if S != int(S) or S % 4 or not 4 <= S <= 512:
+        raise ValueError("S must be a multiple of 4 in 4 .. 512")
+    return int(S), max(1, -(-n_nodes // (LANES * int(S))))
+
+
+def encode_payload(levels, rb, n_ctx, smax, S=None):
+    """(S, nc, p0, chunks): the lanes' rANS streams of the occupancy bytes under contexts r * 108 + version 2's.
+    S=None: the encoder's layout under the bound smax; else S nodes per lane as given (lanes behind the last node
+    carry the initial state and no words)"""
     occ = [b for lv in levels for b in lv]
     depth, n_nodes = len(levels), len(occ)
-    S, nc = _layout(n_nodes, smax)
+    S, nc = _layout(n_nodes, smax) if S is None else _forced_layout(n_nodes, S)
     start_last = n_nodes - len(levels[-1])
     start_prev = start_last - len(levels[-2]) if depth >= 2 else 0
 
@@ -156,14 +166,15 @@ def encode_payload(levels, rb, n_ctx, smax):
     return S, nc, p0, chunks
 
 
-def encode(points, reference, bias=BIAS, split=True, smax=SMAX4):
+def encode(points, reference, bias=BIAS, split=True, smax=SMAX4, S=None):
     """blob version 4 of `points` (int [n,3], duplicates allowed) against the points `reference`.  split=False: the
-    empty context split (every r = 0, 108 entries of p0), whose payload is version 2's."""
+    empty context split (every r = 0, 108 entries of p0), whose payload is version 2's.  S: a forced layout
+    (encode_payload), for blobs a decoder must read and the project's encoder never writes."""
     levels, cells, depth, org, n = build_tree(points, bias)
     ref = reference if isinstance(reference, Reference) else Reference(reference, bias)
     n_nodes = sum(len(lv) for lv in levels)
     rb = reference_bytes(cells, depth, org, ref) if split else [0] * n_nodes
-    S, nc, p0, chunks = encode_payload(levels, rb, CTX4 if split else CTX2, smax)
+    S, nc, p0, chunks = encode_payload(levels, rb, CTX4 if split else CTX2, smax, S)
     body = b"".join(struct.pack("<I", len(lv)) for lv in levels) + struct.pack("<II", S, nc)
     body += struct.pack("<IQ", ref.n, ref.sum)
     body += struct.pack("<%dH" % len(p0), *p0) + b"".join(struct.pack("<I", len(ch)) for ch in chunks)

@@ -112,6 +112,88 @@ def test_header_fields():
     assert hb["nc"] == -(-sum(hb["level_n"]) // (64 * 256)) >= 2 and hb["S"] <= 256 and hb["S"] % 4 == 0
 
 
+# ------------------------------------------------------------------ layouts the format allows and the encoder never chooses
+def _small_frame():
+    """about 1.5k nodes at depth 16"""
+    rng = np.random.default_rng(14)
+    a = np.unique(rng.integers(-150, 150, (420, 3)), axis=0)
+    return a[:270], a[200:]
+
+
+@pytest.mark.parametrize("S", [4, 8, 64, 132, 512])
+def test_forced_layout_round_trip(S):
+    """S = 64 is not minimal for this frame (24 lanes of one chunk would do with S = 24): lanes 24 .. 63 hold no node"""
+    pts, ref = _small_frame()
+    blob = ref4.encode(pts, ref, S=S)
+    h = ref4.header(blob)
+    n_nodes = sum(h["level_n"])
+    assert 1400 <= n_nodes <= 1600
+    assert h["S"] == S and h["nc"] == max(1, -(-n_nodes // (64 * S)))
+    assert {4: h["nc"] > 1, 8: h["nc"] > 1, 64: h["nc"] == 1 and -(-n_nodes // 64) < 64, 132: h["nc"] == 1, 512: h["nc"] == 1}[S]
+    dec = ref4.decode(blob, ref)
+    assert np.array_equal(np.unique(dec, axis=0), pts) and np.all(np.diff(ref4.morton(dec + 32768)) > 0)
+    # a lane whose first node lies behind the last: the initial state and no words
+    words = struct.unpack_from("<192H", blob, h["off_payload"] + 2 * sum(struct.unpack_from("<%dI" % (h["nc"] - 1), blob, h["off_table"])))
+    for lane in range(64):
+        if (64 * (h["nc"] - 1) + lane) * S >= n_nodes:
+            assert words[2 * lane:2 * lane + 2] == (0, 1) and words[128 + lane] == 0
+
+
+def test_forced_layout_of_the_encoders_own_choice_is_the_same_blob():
+    pts, ref = _small_frame()
+    for frame in (pts, pts[:9], random_cloud(np.random.default_rng(6), 7000, extent=4000, lo=-2000)[:, 1:]):
+        n_nodes = sum(len(lv) for lv in ref4.build_tree(frame)[0])
+        S0, nc0 = ref4._layout(n_nodes, 256)
+        blob = ref4.encode(frame, ref)
+        assert ref4.encode(frame, ref, S=S0) == blob and (ref4.header(blob)["S"], ref4.header(blob)["nc"]) == (S0, nc0)
+    assert ref4.encode(pts, ref, smax=512, S=None) == ref4.encode(pts, ref, smax=512)
+
+
+@pytest.mark.parametrize("S", [0, 2, 6, 516, -4, 4.5])
+def test_forced_layout_outside_the_format_is_refused(S):
+    pts, ref = _small_frame()
+    with pytest.raises(ValueError, match="multiple of 4"):
+        ref4.encode(pts, ref, S=S)
+
+
+def test_the_parsers_boundary_of_S_and_the_chunk_count():
+    """o4_parse through geometry_info: S any multiple of 4 in 4 .. 512 with 64 S (nc - 1) < nodes <= 64 S nc"""
+    G = _geo_class()
+    PccError = pkg("_abi").PccError
+    pts, ref = _small_frame()
+    n_nodes = sum(len(lv) for lv in ref4.build_tree(pts)[0])
+    want = {"version": 4, "points": len(pts), "predicted": True, "reference_points": len(ref)}
+    for S in (4, 512):
+        assert G.geometry_info(ref4.encode(pts, ref, S=S)) == want
+
+    def rewritten(blob, S=None, nc=None):
+        b, h = bytearray(blob), ref4.header(blob)
+        struct.pack_into("<II", b, 24 + 4 * h["depth"], h["S"] if S is None else S, h["nc"] if nc is None else nc)
+        return bytes(b)
+
+    def refused(bad):
+        with pytest.raises(PccError) as e:
+            G.geometry_info(bad)
+        assert e.value.code == pkg("_abi").PCC_E_STREAM
+
+    one = ref4.encode(pts, ref, S=512)                    # one chunk
+    assert ref4.header(one)["nc"] == 1 and n_nodes <= 64 * 24
+    for S in (0, 2, 6, 516, 1 << 31, (1 << 32) - 4):
+        refused(rewritten(one, S=S))
+    for S in (24, 28, 256, 508):                          # one chunk of any S that holds the nodes: the table is still one entry
+        assert G.geometry_info(rewritten(one, S=S)) == want
+    refused(rewritten(one, S=20))                         # 64 * 20 < nodes: one chunk does not hold them
+    refused(rewritten(one, nc=0))
+    refused(rewritten(one, nc=2))
+    many = ref4.encode(pts, ref, S=4)
+    nc = ref4.header(many)["nc"]
+    assert nc == -(-n_nodes // 256) >= 5
+    refused(rewritten(many, nc=nc - 1))
+    refused(rewritten(many, nc=nc + 1))
+    refused(rewritten(many, S=8))                         # 64 * 8 * (nc - 1) >= nodes: the last chunk would hold none
+    assert 64 * 8 * (nc - 1) >= n_nodes
+
+
 def test_ref_sum_of_three_points_by_hand():
     """(1, 2, 3) -> 0x0001_0002_0003; (-1, 0, 32767) -> 0xFFFF_0000_7FFF; (-32768, 5, -2) -> 0x8000_0005_FFFE;
     the first two add to 0x1_0000_0002_8002, the third makes 0x1_8000_0008_8000"""

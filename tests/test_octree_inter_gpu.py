@@ -1,7 +1,22 @@
 """Octree blob version 4 on the GPU (csrc/octree4.hip, the <true> forms of csrc/octree2.hip's coder kernels) against
 the reference coder of octree_inter_ref.py, byte for byte, and its decoder against np.unique of the frames: the level
 boundaries a lane, a chunk and a dword of four nodes can straddle, root cubes that differ, chains of frames, the
-combinations with the other keywords of GeometryCodec, damaged blobs, and one full-size sequence."""
+combinations with the other keywords of GeometryCodec, damaged blobs, and one full-size sequence.
+
+The decoder reads a format, not this project's encoder (kO4SMax = 256, the smallest S for the chunk count), so one block
+of tests decodes blobs of the reference coder under layouts the encoder never writes (octree_inter_ref.encode's smax=
+and S=), each test asserting from the blob the property it is there for:
+  a word span beyond the LDS window   a half-occupied 64 x 64 x 48 box as one chunk of S = 440: the widest level's lanes
+                                      span 12 433 words against kO4Win = 10 240, so k_o4_dec reads the stream in place;
+                                      the encoder's own blob of the frame (S = 220, two chunks) spans 7 069
+  S at both ends of what o4_parse     23 017 nodes at S = 4 (90 chunks: more than the 64 a wave sums of the chunk table
+  accepts                             in one round), S = 8 (45) and S = 512 (1)
+  a layout that is not minimal        2 164 nodes at S = 256 and S = 512: one chunk, lanes 9 .. 63 (5 .. 63) without nodes
+  a level on a chunk boundary         S = 4: level 11 begins at node 256; a deepest level that begins at node 1 792
+  the encoder's second chunk          16 384 nodes (S = 256, one chunk, no slack) and 16 385 (S = 132, two chunks, lanes
+                                      61 .. 63 of the second empty), at depth 6 and at depth 16; through the GPU encoder
+  damage on these paths               a flipped word, a flipped state and a short chunk on the in-place path, a word in
+                                      a lane without nodes, an S rewritten to another the parser accepts: PCC_E_STREAM"""
 import struct
 
 import numpy as np
@@ -121,6 +136,240 @@ def test_level_boundaries(geo, name):
     else:
         assert off[depth - 1] % 4 == int(name.split()[3])
     _pair(geo, frame, _boundary_cloud(BOUNDARY_SEEDS[name] + 100))
+
+
+# ------------------------------------------------------------------ layouts and word spans the encoder never emits
+K_O4_WIN = 10240      # kO4Win of csrc/octree4.hip: the decoder's window of 16-bit words in LDS
+
+
+def _decode_only(geo, frame, reference, **layout):
+    """a blob of the reference coder under a layout of its own (smax=, S=) through the GPU decoder and the reference
+    decoder"""
+    blob = ref4.encode(frame, reference, **layout)
+    want = _morton_sorted(frame)
+    (dec,) = geo.decompress([blob], reference=reference)
+    assert dec.dtype == np.int32 and np.array_equal(dec, want), ref4.header(blob)
+    assert np.array_equal(ref4.decode(blob, reference), want)
+    return blob
+
+
+def _chunk(blob, c):
+    """(byte offset of chunk c, its 64 lane lengths)"""
+    h = ref4.header(blob)
+    table = struct.unpack_from("<%dI" % h["nc"], blob, h["off_table"])
+    at = h["off_payload"] + 2 * sum(table[:c])
+    return at, np.array(struct.unpack_from("<64H", blob, at + 2 * 128), np.int64)
+
+
+def _word_spans(blob):
+    """w_hi - w_lo as k_o4_dec forms it, for every launch (level) and every chunk of it: from the first word of the
+    first lane that holds a node of the level to the last word of the last such lane"""
+    h = ref4.header(blob)
+    S = h["S"]
+    off = np.cumsum([0] + h["level_n"])
+    out = []
+    for c in range(h["nc"]):
+        _, lens = _chunk(blob, c)
+        end = np.cumsum(lens)
+        node0 = (64 * c + np.arange(64)) * S
+        for L in range(h["depth"]):
+            act = np.nonzero(np.maximum(node0, off[L]) < np.minimum(node0 + S, off[L + 1]))[0]
+            if len(act):
+                out.append(int(end[act[-1]] - (end - lens)[act[0]]))
+    return out
+
+
+_cache = {}
+
+
+def _half_box():
+    """a half-occupied box, the most words a node can cost: 98 051 points, 28 065 nodes, depth 16"""
+    if "box" not in _cache:
+        g = np.stack(np.meshgrid(np.arange(64), np.arange(64), np.arange(48), indexing="ij"), -1).reshape(-1, 3).astype(np.int32)
+        rng = np.random.default_rng(7)
+        frame = g[rng.random(len(g)) < 0.5] - 32
+        reference = g[rng.random(len(g)) < 0.1] - 31
+        _cache["box"] = (frame, reference)
+    return _cache["box"]
+
+
+def _scattered():
+    """5 999 points, 23 017 nodes, depth 16"""
+    if "scattered" not in _cache:
+        rng = np.random.default_rng(3)
+        frame = np.unique(rng.integers(-150, 150, (6000, 3)), axis=0).astype(np.int32)
+        reference = rng.integers(-150, 150, (3000, 3)).astype(np.int32)
+        _cache["scattered"] = (frame, reference)
+    return _cache["scattered"]
+
+
+def _checked(geo, key, frame, reference, **layout):
+    """_decode_only, once per blob of the module"""
+    if key not in _cache:
+        _cache[key] = _decode_only(geo, frame, reference, **layout)
+    return _cache[key]
+
+
+def test_word_span_beyond_the_lds_window(geo):
+    """one chunk of S = 440 (smax=512): the widest level's lanes span 12 433 words, more than kO4Win = 10 240, so
+    k_o4_dec reads the stream in place; the encoder's own layout of the same frame (S = 220, two chunks, 7 069 words)
+    stays inside the window"""
+    frame, reference = _half_box()
+    blob = _checked(geo, "box512", frame, reference, smax=512)
+    h = ref4.header(blob)
+    assert (h["S"], h["nc"]) == (440, 1), h
+    widest = max(_word_spans(blob))
+    print("half box, smax=512: S", h["S"], "chunks", h["nc"], "bytes", len(blob), "widest span", widest)
+    assert widest > K_O4_WIN, "widest span %d words does not exceed kO4Win = %d: the in-place path is not run" % (widest, K_O4_WIN)
+    (own,) = geo.compress([frame], predict="previous", reference=reference)
+    assert own == ref4.encode(frame, reference)
+    ho = ref4.header(own)
+    widest_own = max(_word_spans(own))
+    print("half box, the encoder's layout: S", ho["S"], "chunks", ho["nc"], "widest span", widest_own)
+    assert ho["nc"] == 2 and 0 < widest_own <= K_O4_WIN, "widest span %d words against kO4Win = %d" % (widest_own, K_O4_WIN)
+    assert np.array_equal(geo.decompress([own], reference=reference)[0], _morton_sorted(frame))
+
+
+@pytest.mark.parametrize("S", [4, 8, 512])
+def test_s_at_the_ends_and_more_than_64_chunks(geo, S):
+    """S = 4: 90 chunks, so the sum of the chunk table in front of a chunk takes a second round of the wave"""
+    frame, reference = _scattered()
+    h = ref4.header(_checked(geo, "scattered%d" % S, frame, reference, S=S))
+    n_nodes = sum(h["level_n"])
+    print("scattered: nodes", n_nodes, "S", S, "chunks", h["nc"])
+    assert h["S"] == S and h["nc"] == -(-n_nodes // (64 * S))
+    if S == 4:
+        assert h["nc"] > 64
+    if S == 512:
+        assert h["nc"] == 1
+
+
+@pytest.mark.parametrize("S", [256, 512])
+def test_a_layout_that_is_not_minimal(geo, S):
+    """about 2k nodes dealt 256 or 512 to a lane: one chunk whose lanes from 9 (5) on hold no node"""
+    frame, reference = _boundary_cloud(0), _boundary_cloud(100)
+    blob = _checked(geo, "sparse%d" % S, frame, reference, S=S)
+    h = ref4.header(blob)
+    n_nodes = sum(h["level_n"])
+    assert h["nc"] == 1 and 8 * 256 < n_nodes <= 9 * 256      # lanes 9 .. 63 of S = 256 begin behind the last node
+    _, lens = _chunk(blob, 0)
+    assert np.all(lens[-(-n_nodes // S):] == 0) and np.all(lens[:-(-n_nodes // S)] > 0)
+
+
+# as BOUNDARY_SEEDS, the same search: the first cloud with a level (beyond the first two) that begins at node 256, the
+# first node of chunk 1 under S = 4, and the first cloud whose DEEPEST level begins at a chunk's first node under S = 4 or 8
+CHUNK_BOUNDARY_SEEDS = {"level 11 begins at node 256 = 64 * 4": (18, 4), "the deepest level begins at node 1792 = 7 * 64 * 4": (40, 4)}
+
+
+@pytest.mark.parametrize("name", list(CHUNK_BOUNDARY_SEEDS))
+def test_a_level_on_a_chunk_boundary(geo, name):
+    """the lane in front of the boundary ends its run and leaves nothing behind, the launch of the level begins at a
+    chunk's own states"""
+    seed, S = CHUNK_BOUNDARY_SEEDS[name]
+    frame = _boundary_cloud(seed)
+    levels, _, depth, _, _ = ref4.build_tree(frame)
+    off = np.cumsum([0] + [len(lv) for lv in levels])
+    if "deepest" in name:
+        assert off[depth - 1] % (64 * S) == 0 and off[depth - 1] == 1792
+    else:
+        assert any(off[L] % (64 * S) == 0 for L in range(2, depth)) and off[11] == 256
+    _decode_only(geo, frame, _boundary_cloud(seed + 100), S=S)
+
+
+# prefixes of one shuffled cloud, found by bisection on the CPU with octree_inter_ref.build_tree: the longest with
+# 16 384 nodes (one chunk of S = 256, every lane full) and the next (two chunks of S = 132, the last lanes empty); under
+# the shift the cube straddles the origin (depth 16) and ten levels of one node move the prefixes
+CHUNK_SWITCH = {"depth 6": (0, 14260, 14261), "depth 16": (-32, 14153, 14154)}
+
+
+@pytest.mark.parametrize("delta", [0, 1])
+@pytest.mark.parametrize("name", list(CHUNK_SWITCH))
+def test_either_side_of_the_encoders_second_chunk(geo, name, delta):
+    shift, full, _ = CHUNK_SWITCH[name]
+    assert CHUNK_SWITCH[name][2] == full + 1
+    rng = np.random.default_rng(1)
+    pts = np.unique(rng.integers(0, 64, (26000, 3)), axis=0).astype(np.int32)
+    pts = pts[rng.permutation(len(pts))]
+    frame, reference = pts[:full + delta] + shift, pts[20000:] + 1
+    levels, _, depth, _, _ = ref4.build_tree(frame)
+    n_nodes = sum(len(lv) for lv in levels)
+    assert depth == int(name.split()[1]) and n_nodes == 16384 + delta
+    blob = _pair(geo, frame, reference)
+    h = ref4.header(blob)
+    assert (h["S"], h["nc"]) == ((256, 1), (132, 2))[delta]
+    _, lens = _chunk(blob, h["nc"] - 1)
+    if delta:      # chunk 1: 7 937 nodes, 60 lanes of 132 and one of 17; lanes 61 .. 63 hold none
+        assert np.all(lens[61:] == 0) and np.all(lens[:61] > 0)
+    else:
+        assert np.all(lens > 0)
+
+
+def test_damaged_blobs_on_the_new_paths(geo):
+    """as test_damaged_blobs_are_errors, on blobs that run the in-place word path, a lane without nodes and a layout
+    of another S: PCC_E_STREAM, and the call after it decodes"""
+    abi = pkg("_abi")
+    G = type(geo)
+
+    def flip(blob, at, bit=0x10):
+        b = bytearray(blob)
+        b[at] ^= bit
+        return bytes(b)
+
+    def refused(name, bad, blob, frame, reference):
+        with pytest.raises(abi.PccError) as e:
+            geo.decompress([bad], reference=reference)
+            pytest.fail(name + " decoded")
+        assert e.value.code == abi.PCC_E_STREAM, (name, str(e.value))
+        assert np.array_equal(geo.decompress([blob], reference=reference)[0], _morton_sorted(frame)), name
+
+    # the blob whose widest span is read in place
+    frame, reference = _half_box()
+    blob = _checked(geo, "box512", frame, reference, smax=512)
+    assert max(_word_spans(blob)) > K_O4_WIN
+    h = ref4.header(blob)
+    at, lens = _chunk(blob, 0)
+    assert lens[30] > 100
+    shortened = bytearray(blob)      # the chunk one word shorter, the tables left as they are
+    del shortened[at + 2 * 192:at + 2 * 192 + 2]
+    struct.pack_into("<I", shortened, 20, len(shortened) - 24)
+    cases = {"a flipped payload word in lane 30's run": flip(blob, at + 2 * (192 + int(lens[:30].sum()) + 40)),
+             "a flipped state": flip(blob, at + 1), "a shortened chunk": bytes(shortened)}
+    for name, bad in cases.items():
+        refused(name, bad, blob, frame, reference)
+
+    # a lane without nodes that announces a word: the parser has nothing against it
+    frame, reference = _boundary_cloud(0), _boundary_cloud(100)
+    blob = _checked(geo, "sparse256", frame, reference, S=256)
+    h = ref4.header(blob)
+    at, lens = _chunk(blob, 0)
+    assert h["nc"] == 1 and 63 * 256 >= sum(h["level_n"]) and lens[62] == 0 and lens[63] == 0
+    bad = bytearray(blob) + struct.pack("<H", 0x1234)
+    struct.pack_into("<H", bad, at + 2 * (128 + 63), 1)
+    struct.pack_into("<I", bad, h["off_table"], struct.unpack_from("<I", blob, h["off_table"])[0] + 1)
+    struct.pack_into("<I", bad, 20, len(bad) - 24)
+    assert G.geometry_info(bytes(bad)) == G.geometry_info(blob)
+    refused("a word in a lane without nodes", bytes(bad), blob, frame, reference)
+
+    # another S in the header that the parser accepts: every node is dealt to another lane
+    def another_s(blob, S):
+        h = ref4.header(blob)
+        n_nodes = sum(h["level_n"])
+        assert S != h["S"] and S % 4 == 0 and 64 * S * (h["nc"] - 1) < n_nodes <= 64 * S * h["nc"]
+        b = bytearray(blob)
+        struct.pack_into("<I", b, 24 + 4 * h["depth"], S)
+        assert G.geometry_info(bytes(b)) == G.geometry_info(blob)
+        return bytes(b)
+
+    # (the 45 chunks of S = 8 and the 90 of S = 4 of the scattered frame admit no other S; its one chunk of S = 512
+    # admits 360 .. 508)
+    frame, reference = _scattered()
+    blob = _checked(geo, "scattered512", frame, reference, S=512)
+    for S in (360, 508):
+        refused("S = 512 rewritten to %d" % S, another_s(blob, S), blob, frame, reference)
+    frame, reference = _boundary_cloud(0)[:160], _boundary_cloud(100)      # 881 nodes: two chunks under S = 8 and under S = 12
+    blob = _checked(geo, "small8", frame, reference, S=8)
+    assert ref4.header(blob)["nc"] == 2
+    refused("S = 8 rewritten to 12", another_s(blob, 12), blob, frame, reference)
 
 
 # ------------------------------------------------------------------ chains
