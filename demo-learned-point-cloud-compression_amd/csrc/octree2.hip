@@ -691,7 +691,7 @@ struct O2In {   // one frame of an encode call: leaves d_keys[lo, lo + n) (n >= 
 // ONE synchronisation for all blob lengths.  Blob f is left in the pinned staging at (*offs)[f], (*lens)[f] bytes.
 //
 // pred (version 4, octree4.hip): every frame of the batch is a predicted frame, pred[f] the keys of its reference
-// (d_keys[ref_lo, ref_lo + ref_n), Morton-sorted and distinct after the key shift).  One step is added in front of the
+// (ref_n keys on the device, Morton-sorted and distinct after the key shift).  One step is added in front of the
 // coder's launches: the reference byte of every node.
 static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, const O2In* fr, int nf,
                            std::vector<int64_t>* offs, std::vector<int64_t>* lens, const O4Pred* pred = nullptr) {
@@ -855,10 +855,10 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
         if (L < j.depth) run += (int64_t)c[L];
       }
       for (int a = 0; a < 3; ++a) j.origin[a] = fr[f].origin[a];
-      j.ref_lo = pred[f].ref_lo;
+      j.ref_keys = pred[f].ref_keys;
       j.ref_n = pred[f].ref_n;
     }
-    PCC_TRY(o4_ref_bytes_async(ctx, d_keys, key_shift, jobs.data(), nf, occ, (uint8_t*)ref.rb, (uint32_t*)ref.ref_n,
+    PCC_TRY(o4_ref_bytes_async(ctx, key_shift, jobs.data(), nf, occ, (uint8_t*)ref.rb, (uint32_t*)ref.ref_n,
                                (unsigned long long*)ref.ref_sum, ref_scratch, ref_need + 256));
     hipLaunchKernelGGL(k_o2_stats<true>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nf, cnt, ref);
     PCC_CHECK_LAUNCH();
@@ -1186,26 +1186,28 @@ extern "C" int pcc_octree_encode_frames(pcc_ctx* ctx, const uint64_t* d_keys, in
 }
 
 // Inter-frame coding (include/pcc.h has the rule of version 4): the reference of a frame is the frame in front of it
-// in the call — lossless coding makes the original the decoded frame, so all frames still encode side by side: the
-// intra frames in one batch of version 2, the predicted ones in one batch of version 4.
-extern "C" int pcc_octree_encode_frames_inter(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int key_shift,
-                                              int intra_period, int ref_first, uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
-  const char* who = "pcc_octree_encode_frames_inter";
-  PCC_REQUIRE(ctx && h_out && h_offsets && n >= 0 && (n == 0 || d_keys) && n < ((int64_t)1 << 27) && n_frames >= 1 &&
-                  n_frames <= 65535 && key_shift >= 0 && key_shift % 3 == 0 && key_shift <= 45 && cap >= 0 && intra_period >= 0 &&
-                  (ref_first == 0 || ref_first == 1),
-              PCC_E_ARG, "%s: bad argument (n=%lld n_frames=%d key_shift=%d intra_period=%d ref_first=%d)", who, (long long)n,
-              n_frames, key_shift, intra_period, ref_first);
+// in the call, or with history > 1 the union of its window, the up to `history` frames in front of it — lossless
+// coding makes the original the decoded frame, so all frames still encode side by side: the intra frames in one batch
+// of version 2, the predicted ones in one batch of version 4.  The unions of all windows of more than one frame are
+// formed first, in one merge (o4_merge_async) and one synchronisation for their sizes; a call without such a window
+// queues what it queued before history.
+static int o2_encode_frames_inter(const char* who, pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int key_shift,
+                                  int intra_period, int n_ref_frames, int history, uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
   std::vector<int64_t> offs;
   std::vector<uint64_t> ends;
   PCC_TRY(o2_frame_bounds(who, ctx, d_keys, n, n_frames, key_shift, &offs, &ends));
   std::vector<O2In> fr[2];            // [0] intra, [1] predicted
   std::vector<int> frame_of[2];
   std::vector<O4Pred> pred;
-  for (int f = ref_first; f < n_frames; ++f) {
+  std::vector<int> window;            // of the predicted frames
+  std::vector<O4MergeJob> jobs;       // of those with a window of more than one frame
+  std::vector<size_t> job_pred;
+  std::vector<char> is_intra((size_t)n_frames, 0);   // coded frames written as version 2
+  int64_t merged = 0;
+  for (int f = n_ref_frames; f < n_frames; ++f) {
     const int64_t lo = offs[(size_t)f], hi = offs[(size_t)f + 1];
     if (hi <= lo) continue;
-    const int g = f - ref_first;     // its place among the coded frames
+    const int g = f - n_ref_frames;     // its place among the coded frames
     const bool intra = intra_period > 0 ? g % intra_period == 0 : f == 0;
     const int64_t ref_n = f > 0 ? lo - offs[(size_t)f - 1] : 0;
     const int k = !intra && ref_n > 0 ? 1 : 0;   // a frame whose reference has no points is written as version 2
@@ -1215,11 +1217,59 @@ extern "C" int pcc_octree_encode_frames_inter(pcc_ctx* ctx, const uint64_t* d_ke
     octree_root(ends[2 * (size_t)f], ends[2 * (size_t)f + 1], key_shift, &in.depth, in.origin);
     fr[k].push_back(in);
     frame_of[k].push_back(f);
-    if (k) pred.push_back(O4Pred{offs[(size_t)f - 1], ref_n});
+    is_intra[(size_t)f] = k ? 0 : 1;
+    if (!k) continue;
+    // the window: back from f - 1, up to `history` frames, not past a frame without points, not past an intra frame
+    int W = 1;
+    while (W < history && !is_intra[(size_t)(f - W)] && f - W - 1 >= 0 && offs[(size_t)(f - W)] > offs[(size_t)(f - W - 1)]) ++W;
+    window.push_back(W);
+    if (W == 1) {
+      pred.push_back(O4Pred{d_keys + offs[(size_t)f - 1], ref_n});
+      continue;
+    }
+    const int64_t keys = lo - offs[(size_t)(f - W)];
+    PCC_REQUIRE(keys < ((int64_t)1 << 27), PCC_E_ARG, "%s: frame %d: the %d frames of its window hold %lld keys", who, g, W,
+                (long long)keys);
+    O4MergeJob j;
+    j.nl = W;
+    j.out = nullptr;   // below: its place in the call's block, `merged` keys in
+    for (int i = 0; i < W; ++i) {
+      j.list[i] = d_keys + offs[(size_t)(f - W + i)];
+      j.n[i] = offs[(size_t)(f - W + i + 1)] - offs[(size_t)(f - W + i)];
+    }
+    job_pred.push_back(pred.size());
+    pred.push_back(O4Pred{nullptr, merged});
+    jobs.push_back(j);
+    merged += keys;
   }
-  // blob f; frames without keys get the 24-byte empty blob, the reference of ref_first none
+  struct Own {   // the unions and the merge's scratch; the table on its way to the device
+    void* p = nullptr;
+    ~Own() { if (p) (void)hipFree(p); }
+  } own;
+  std::vector<O4MergeDev> tab(jobs.size());
+  if (!jobs.empty()) {
+    PCC_REQUIRE(merged + 1 < ((int64_t)1 << 31), PCC_E_ARG, "%s: the windows of the call hold %lld keys in all", who, (long long)merged);
+    const size_t union_b = pcc_align((size_t)merged * 8), scratch_b = o4_merge_scratch_bytes(merged, (int)jobs.size());
+    PCC_HIP(hipMalloc(&own.p, union_b + scratch_b));
+    for (size_t i = 0; i < jobs.size(); ++i) {
+      jobs[i].out = (uint64_t*)own.p + pred[job_pred[i]].ref_n;
+      pred[job_pred[i]].ref_keys = jobs[i].out;
+    }
+    uint32_t* d_counts = nullptr;
+    std::vector<uint32_t> counts(jobs.size());
+    int rc = o4_merge_async(ctx, jobs.data(), (int)jobs.size(), key_shift, (char*)own.p + union_b, scratch_b, tab.data(), &d_counts);
+    if (rc == PCC_OK && hipMemcpyAsync(counts.data(), d_counts, counts.size() * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
+      pcc_set_error("%s: reading the sizes of the merged references failed", who);
+      rc = PCC_E_HIP;
+    }
+    const bool synced = hipStreamSynchronize(ctx->stream) == hipSuccess;   // (also what keeps `tab` and `counts` until the copies are done)
+    PCC_TRY(rc);
+    PCC_REQUIRE(synced, PCC_E_HIP, "%s: the merge of the reference windows failed", who);
+    for (size_t i = 0; i < jobs.size(); ++i) pred[job_pred[i]].ref_n = (int64_t)counts[i];
+  }
+  // blob f; frames without keys get the 24-byte empty blob, the reference frames none
   std::vector<std::vector<uint8_t>> blob((size_t)n_frames);
-  for (int f = ref_first; f < n_frames; ++f) {
+  for (int f = n_ref_frames; f < n_frames; ++f) {
     blob[(size_t)f].assign((size_t)kHeader, 0);
     blob[(size_t)f][0] = 'O';
     blob[(size_t)f][1] = 2;
@@ -1231,6 +1281,7 @@ extern "C" int pcc_octree_encode_frames_inter(pcc_ctx* ctx, const uint64_t* d_ke
     for (size_t i = 0; i < fr[k].size(); ++i) {
       const uint8_t* src = (const uint8_t*)ctx->stage + boff[i];
       blob[(size_t)frame_of[k][i]].assign(src, src + blen[i]);
+      if (k) blob[(size_t)frame_of[k][i]][3] = (uint8_t)(window[i] - 1);   // byte 3 of version 4's head: W - 1
     }
   }
   int64_t total = 0;
@@ -1242,6 +1293,29 @@ extern "C" int pcc_octree_encode_frames_inter(pcc_ctx* ctx, const uint64_t* d_ke
     h_offsets[f + 1] = h_offsets[f] + (int64_t)blob[(size_t)f].size();
   }
   return PCC_OK;
+}
+
+extern "C" int pcc_octree_encode_frames_inter_hist(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int key_shift,
+                                                   int intra_period, int n_ref_frames, int history, uint8_t* h_out, int64_t cap,
+                                                   int64_t* h_offsets) {
+  const char* who = "pcc_octree_encode_frames_inter_hist";
+  PCC_REQUIRE(ctx && h_out && h_offsets && n >= 0 && (n == 0 || d_keys) && n < ((int64_t)1 << 27) && n_frames >= 1 &&
+                  n_frames <= 65535 && key_shift >= 0 && key_shift % 3 == 0 && key_shift <= 45 && cap >= 0 && intra_period >= 0 &&
+                  history >= 1 && history <= kO4MaxWindow && n_ref_frames >= 0 && n_ref_frames <= history && n_ref_frames < n_frames,
+              PCC_E_ARG, "%s: bad argument (n=%lld n_frames=%d key_shift=%d intra_period=%d n_ref_frames=%d history=%d)", who,
+              (long long)n, n_frames, key_shift, intra_period, n_ref_frames, history);
+  return o2_encode_frames_inter(who, ctx, d_keys, n, n_frames, key_shift, intra_period, n_ref_frames, history, h_out, cap, h_offsets);
+}
+
+extern "C" int pcc_octree_encode_frames_inter(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int key_shift,
+                                              int intra_period, int ref_first, uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
+  const char* who = "pcc_octree_encode_frames_inter";
+  PCC_REQUIRE(ctx && h_out && h_offsets && n >= 0 && (n == 0 || d_keys) && n < ((int64_t)1 << 27) && n_frames >= 1 &&
+                  n_frames <= 65535 && key_shift >= 0 && key_shift % 3 == 0 && key_shift <= 45 && cap >= 0 && intra_period >= 0 &&
+                  (ref_first == 0 || ref_first == 1),
+              PCC_E_ARG, "%s: bad argument (n=%lld n_frames=%d key_shift=%d intra_period=%d ref_first=%d)", who, (long long)n,
+              n_frames, key_shift, intra_period, ref_first);
+  return o2_encode_frames_inter(who, ctx, d_keys, n, n_frames, key_shift, intra_period, ref_first, 1, h_out, cap, h_offsets);
 }
 
 static int o2_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,

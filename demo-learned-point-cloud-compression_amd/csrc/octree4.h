@@ -10,9 +10,11 @@ struct pcc_ctx;
 // level's launch of the decoder lasts up to 8 S dependent steps of a wave
 constexpr int kO4SMax = 256;
 
-// the reference of a predicted frame of an encode call: the keys d_keys[ref_lo, ref_lo + ref_n) (ref_n >= 1)
+// the reference of a predicted frame of an encode call: ref_n >= 1 keys on the device, strictly increasing under the
+// key shift — the frame in front of it among the call's keys, or the union of its window (o4_merge_async)
 struct O4Pred {
-  int64_t ref_lo, ref_n;
+  const uint64_t* ref_keys;
+  int64_t ref_n;
 };
 
 // one predicted frame whose nodes want their reference bytes: its occupancy bytes (root first) at occ + occ_off, level
@@ -20,7 +22,8 @@ struct O4Pred {
 struct O4RefJob {
   int64_t occ_off, n_points;
   int64_t off[17];
-  int64_t ref_lo, ref_n;
+  const uint64_t* ref_keys;
+  int64_t ref_n;
   int32_t depth;
   int32_t origin[3];
 };
@@ -29,5 +32,34 @@ struct O4RefJob {
 size_t o4_ref_scratch_bytes(int64_t n_nodes, int64_t n_points);
 // rb + occ_off receives the reference byte of every node of every job, ref_n[f] / ref_sum[f] what identifies job f's
 // reference.  Queued on the context's stream; the jobs take `scratch` (the largest job's bytes) in turn.
-int o4_ref_bytes_async(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, const O4RefJob* jobs, int nf, const uint8_t* occ,
+int o4_ref_bytes_async(pcc_ctx* ctx, int key_shift, const O4RefJob* jobs, int nf, const uint8_t* occ,
                        uint8_t* rb, uint32_t* ref_n, unsigned long long* ref_sum, char* scratch, size_t scratch_b);
+
+// ---- the merged reference of a window of more than one frame (history > 1; include/pcc.h has the rule) ---------------
+constexpr int kO4MaxWindow = 8;
+
+// one union: up to 8 lists of keys on the device, each strictly increasing under (key & mask48) >> key_shift -> out,
+// the strictly increasing union (of equal keys the one of the first list that holds it), room for all lists' keys
+struct O4MergeJob {
+  const uint64_t* list[kO4MaxWindow];
+  int64_t n[kO4MaxWindow];
+  int32_t nl;
+  uint64_t* out;
+};
+// the job as the kernels read it: list i = elements [off[i], off[i + 1]) of the job, the job's elements from `base`
+// on among the call's
+struct O4MergeDev {
+  const uint64_t* list[kO4MaxWindow];
+  int64_t off[kO4MaxWindow + 1];
+  int64_t base;
+  uint64_t* out;
+  int32_t nl;
+};
+// device scratch of a call whose jobs hold `total` keys in all (total >= 1, total + 1 < 2^31)
+size_t o4_merge_scratch_bytes(int64_t total, int nj);
+// All jobs in three steps queued on the context's stream, whatever their number: keep flags, one scan, scatter.
+// *d_counts (in the scratch) receives the size of every union.  h_tab[nj] is the table on its way to the device: the
+// caller keeps it until its next synchronisation.  RESERVES THE ARENA (the scan's block sums): the caller holds
+// nothing in it.
+int o4_merge_async(pcc_ctx* ctx, const O4MergeJob* jobs, int nj, int key_shift, char* scratch, size_t scratch_b,
+                   O4MergeDev* h_tab, uint32_t** d_counts);

@@ -23,6 +23,12 @@
 // link give the leaves, and k_o4_points walks every leaf up to the root, as version 2 does.  The chain I P P .. decodes
 // frame after frame on the stream: the keys of a decoded frame are the reference of the next.
 //
+// A window of several frames (history > 1; byte 3 of the head holds the frames of the window - 1): the reference is the
+// union of the window's frames, formed on the device by a merge of their sorted distinct keys (k_o4_merge_flag, one
+// scan, k_o4_merge_scatter; pcc_merge_keys) — for all predicted frames of an encode call in one go, and frame after
+// frame in a decode call, which keeps the keys of the last frames it decoded.  Everything behind the merge sees a
+// reference of more keys and nothing else.
+//
 // What the stream announces is never trusted: every size comes from the header's checks (octree4_blob.h), every
 // store is to an index below a bound the host sized the array from, every read of the stream is clamped to the chunk.
 #include "common.h"
@@ -101,6 +107,91 @@ __global__ void k_o4_refcheck(const unsigned long long* __restrict__ sum, unsign
   if (*sum != want) atomicOr(status, 16);
 }
 
+// keys compared by (key & mask48) >> shift, under which they increase: the first of keys[lo, n) that is not below
+// `target` (n: all are)
+__device__ __forceinline__ int64_t o4_lower(const uint64_t* __restrict__ keys, int64_t n, uint64_t target, int shift,
+                                            int64_t lo = 0) {
+  int64_t hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (((keys[mid] & kMask48) >> shift) < target) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// ---- the union of a window's key lists (history > 1): a merge, not a sort.  Element g of the call = element idx of
+// list i of job j; what it is compared by is k_o4_ref's (key & mask48) >> shift, under which every list is strictly
+// increasing.  An element is KEPT when no list in front of its own holds an equal key; the scan of the keep flags over
+// all elements of the call gives, by differences, the kept elements below any place of any list, and a kept element's
+// place in its union is the sum of those over the job's lists: no atomics, the same output every run.
+
+// element g < total -> its job, list and index there (the jobs' bases increase from 0, every job has an element)
+__device__ __forceinline__ void o4_mg_locate(const O4MergeDev* __restrict__ tab, int nj, int64_t g, int* job, int* list, int64_t* idx) {
+  int lo = 0, hi = nj - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].base <= g) lo = mid; else hi = mid - 1;
+  }
+  const O4MergeDev& J = tab[lo];
+  const int64_t e = g - J.base;
+  int i = 0;
+  while (i + 1 < J.nl && e >= J.off[i + 1]) ++i;
+  *job = lo;
+  *list = i;
+  *idx = e - J.off[i];
+}
+
+// flags[g] = element g is kept; flags[total] = 0, so that the exclusive scan's entry `total` is the sum
+__global__ __launch_bounds__(256) void k_o4_merge_flag(const O4MergeDev* __restrict__ tab, int nj, int64_t total, int shift,
+                                                       uint32_t* __restrict__ flags) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g > total) return;
+  if (g == total) {
+    flags[g] = 0u;
+    return;
+  }
+  int job, i;
+  int64_t idx;
+  o4_mg_locate(tab, nj, g, &job, &i, &idx);
+  const O4MergeDev& J = tab[job];
+  const uint64_t k = (J.list[i][idx] & kMask48) >> shift;
+  uint32_t keep = 1u;
+  for (int l = 0; l < i; ++l) {
+    const int64_t n = J.off[l + 1] - J.off[l];
+    const int64_t at = o4_lower(J.list[l], n, k, shift);
+    if (at < n && ((J.list[l][at] & kMask48) >> shift) == k) keep = 0u;
+  }
+  flags[g] = keep;
+}
+
+// excl: the exclusive scan of the flags, total + 1 entries.  A kept element goes to (kept elements with a smaller key,
+// list by list); the first element of a job leaves the union's size
+__global__ __launch_bounds__(256) void k_o4_merge_scatter(const O4MergeDev* __restrict__ tab, int nj, int64_t total, int shift,
+                                                          const uint32_t* __restrict__ excl, uint32_t* __restrict__ counts) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  int job, i;
+  int64_t idx;
+  o4_mg_locate(tab, nj, g, &job, &i, &idx);
+  const O4MergeDev& J = tab[job];
+  if (g == J.base) counts[job] = excl[J.base + J.off[J.nl]] - excl[J.base];
+  if (excl[g + 1] == excl[g]) return;
+  const uint64_t key = J.list[i][idx];
+  const uint64_t k = (key & kMask48) >> shift;
+  int64_t pos = 0;
+  for (int l = 0; l < J.nl; ++l) {
+    const int64_t below = l == i ? idx : o4_lower(J.list[l], J.off[l + 1] - J.off[l], k, shift);
+    const int64_t b = J.base + J.off[l];
+    pos += (int64_t)(excl[b + below] - excl[b]);
+  }
+  J.out[pos] = key;   // pos < kept elements of the job <= its elements: the room the caller gave
+}
+
+// status |= 16 where the union at hand has another size than the blob's ref_n
+__global__ void k_o4_countcheck(const uint32_t* __restrict__ count, uint32_t want, int32_t* __restrict__ status) {
+  if (*count != want) atomicOr(status, 16);
+}
+
 __global__ __launch_bounds__(256) void k_o4_popc(const uint8_t* __restrict__ occ, int64_t n, uint32_t* __restrict__ pc) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) pc[i] = (uint32_t)__popc((uint32_t)occ[i]);
@@ -147,14 +238,6 @@ __global__ __launch_bounds__(256) void k_o4_ref(const uint32_t* __restrict__ lin
   const uint32_t cy = (pcc_compact3(code >> 1) << (s + 1)) + (uint32_t)(t.origin[1] + t.bias);
   const uint32_t cz = (pcc_compact3(code) << (s + 1)) + (uint32_t)(t.origin[2] + t.bias);
   const int shift = t.key_shift;
-  auto lower = [&](int64_t lo, uint64_t target) {
-    int64_t hi = n_ref;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (((ref_keys[mid] & kMask48) >> shift) < target) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-  };
   // every child's own corner: a child's cube (s <= 15 - lod) is aligned under any bias that is a multiple of its side,
   // the node's own cube need not be (the root of a frame of cells under bias 32768), so the eight ranges are searched
   // one by one
@@ -162,7 +245,7 @@ __global__ __launch_bounds__(256) void k_o4_ref(const uint32_t* __restrict__ lin
   for (int j = 0; j < 8; ++j) {
     const uint32_t jx = (uint32_t)((j >> 2) & 1) << s, jy = (uint32_t)((j >> 1) & 1) << s, jz = (uint32_t)(j & 1) << s;
     const uint64_t G = (pcc_spread3(cx + jx) << 2) | (pcc_spread3(cy + jy) << 1) | pcc_spread3(cz + jz);
-    const int64_t lo = lower(0, G), hi = lower(lo, G + ((uint64_t)1 << (3 * s)));
+    const int64_t lo = o4_lower(ref_keys, n_ref, G, shift), hi = o4_lower(ref_keys, n_ref, G + ((uint64_t)1 << (3 * s)), shift, lo);
     byte |= hi > lo ? 1u << j : 0u;
   }
   rb[i] = (uint8_t)byte;
@@ -356,7 +439,7 @@ size_t o4_ref_scratch_bytes(int64_t n_nodes, int64_t n_points) {
   return 2 * pcc_align((size_t)n_nodes * 4) + pcc_align((size_t)(n_nodes + n_points) * 4) + 1024;
 }
 
-int o4_ref_bytes_async(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, const O4RefJob* jobs, int nf, const uint8_t* occ,
+int o4_ref_bytes_async(pcc_ctx* ctx, int key_shift, const O4RefJob* jobs, int nf, const uint8_t* occ,
                        uint8_t* rb, uint32_t* ref_n, unsigned long long* ref_sum, char* scratch, size_t scratch_b) {
   hipStream_t st = ctx->stream;
   for (int f = 0; f < nf; ++f) PCC_HIP(hipMemsetD32Async((hipDeviceptr_t)(ref_n + f), (int)(uint32_t)jobs[f].ref_n, 1, st));
@@ -387,13 +470,105 @@ int o4_ref_bytes_async(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, cons
     hipLaunchKernelGGL(k_o4_link, dim3(nblk(N, 256)), dim3(256), 0, st, o, (const uint32_t*)excl, (int64_t)0, N, (int64_t)1,
                        N + j.n_points, link, st_dummy);
     PCC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_o4_ref, dim3(nblk(N, 256)), dim3(256), 0, st, (const uint32_t*)link, t, (int64_t)0, N, d_keys + j.ref_lo,
+    hipLaunchKernelGGL(k_o4_ref, dim3(nblk(N, 256)), dim3(256), 0, st, (const uint32_t*)link, t, (int64_t)0, N, j.ref_keys,
                        j.ref_n, rb + j.occ_off);
     PCC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_o4_keysum, dim3(nblk(j.ref_n, 256)), dim3(256), 0, st, d_keys + j.ref_lo, j.ref_n, key_shift, bias,
+    hipLaunchKernelGGL(k_o4_keysum, dim3(nblk(j.ref_n, 256)), dim3(256), 0, st, j.ref_keys, j.ref_n, key_shift, bias,
                        ref_sum + f);
     PCC_CHECK_LAUNCH();
   }
+  return PCC_OK;
+}
+
+// ======================================================================== the merged reference of a window
+size_t o4_merge_scratch_bytes(int64_t total, int nj) {
+  return pcc_align((size_t)(total + 1) * 4 + 16) + pcc_align((size_t)nj * sizeof(O4MergeDev)) + pcc_align((size_t)nj * 4);
+}
+
+int o4_merge_async(pcc_ctx* ctx, const O4MergeJob* jobs, int nj, int key_shift, char* scratch, size_t scratch_b, O4MergeDev* h_tab,
+                   uint32_t** d_counts) {
+  hipStream_t st = ctx->stream;
+  int64_t total = 0;
+  for (int j = 0; j < nj; ++j) {
+    const O4MergeJob& g = jobs[j];
+    O4MergeDev& d = h_tab[j];
+    PCC_REQUIRE(g.nl >= 1 && g.nl <= kO4MaxWindow && g.out, PCC_E_ARG, "merge of key lists: job %d has %d lists", j, g.nl);
+    d.base = total;
+    d.out = g.out;
+    d.nl = g.nl;
+    int64_t run = 0;
+    for (int i = 0; i <= kO4MaxWindow; ++i) {
+      d.off[i] = run;
+      if (i < kO4MaxWindow) d.list[i] = i < g.nl ? g.list[i] : nullptr;
+      if (i < g.nl) {
+        PCC_REQUIRE(g.n[i] >= 0 && (g.n[i] == 0 || g.list[i]), PCC_E_ARG, "merge of key lists: job %d, list %d", j, i);
+        run += g.n[i];
+      }
+    }
+    PCC_REQUIRE(run >= 1, PCC_E_ARG, "merge of key lists: job %d has no keys", j);
+    total += run;
+  }
+  PCC_REQUIRE(nj >= 1 && total + 1 < ((int64_t)1 << 31) && o4_merge_scratch_bytes(total, nj) <= scratch_b, PCC_E_ARG,
+              "merge of key lists: %lld keys in %d jobs", (long long)total, nj);
+  uint32_t* flags = (uint32_t*)scratch;
+  O4MergeDev* d_tab = (O4MergeDev*)(scratch + pcc_align((size_t)(total + 1) * 4 + 16));
+  uint32_t* counts = (uint32_t*)((char*)d_tab + pcc_align((size_t)nj * sizeof(O4MergeDev)));
+  PCC_TRY(pcc_arena_reserve(ctx, pcc_scan_scratch_bytes(total + 1) + 1024));
+  PCC_HIP(hipMemcpyAsync(d_tab, h_tab, (size_t)nj * sizeof(O4MergeDev), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_o4_merge_flag, dim3(nblk(total + 1, 256)), dim3(256), 0, st, (const O4MergeDev*)d_tab, nj, total, key_shift, flags);
+  PCC_CHECK_LAUNCH();
+  PCC_TRY(pcc_scan_exclusive_u32(ctx, flags, flags, total + 1, nullptr));
+  hipLaunchKernelGGL(k_o4_merge_scatter, dim3(nblk(total, 256)), dim3(256), 0, st, (const O4MergeDev*)d_tab, nj, total, key_shift,
+                     (const uint32_t*)flags, counts);
+  PCC_CHECK_LAUNCH();
+  *d_counts = counts;
+  return PCC_OK;
+}
+
+namespace {
+// a block of the call's own, and host memory on its way to the device: both outlive what the stream still holds
+struct O4Own {
+  hipStream_t st;
+  void* p = nullptr;
+  std::vector<O4MergeDev> tab;
+  explicit O4Own(hipStream_t s) : st(s) {}
+  ~O4Own() {
+    if (!tab.empty()) (void)hipStreamSynchronize(st);
+    if (p) (void)hipFree(p);
+  }
+};
+}  // namespace
+
+extern "C" int pcc_merge_keys(pcc_ctx* ctx, const uint64_t* const* d_lists, const int64_t* h_n, int n_lists, int key_shift,
+                              uint64_t* d_out, int64_t cap, int64_t* h_count) {
+  const char* who = "pcc_merge_keys";
+  PCC_REQUIRE(ctx && d_lists && h_n && h_count && n_lists >= 1 && n_lists <= kO4MaxWindow && key_shift >= 0 && key_shift % 3 == 0 &&
+                  key_shift <= 45 && cap >= 0,
+              PCC_E_ARG, "%s: bad argument (n_lists=%d key_shift=%d)", who, n_lists, key_shift);
+  O4MergeJob job;
+  int64_t total = 0;
+  for (int i = 0; i < n_lists; ++i) {
+    PCC_REQUIRE(h_n[i] >= 0 && h_n[i] < ((int64_t)1 << 27) && (h_n[i] == 0 || d_lists[i]), PCC_E_ARG, "%s: list %d has %lld keys", who, i,
+                (long long)h_n[i]);
+    job.list[i] = d_lists[i];
+    job.n[i] = h_n[i];
+    total += h_n[i];
+  }
+  job.nl = n_lists;
+  job.out = d_out;
+  *h_count = 0;
+  if (total == 0) return PCC_OK;
+  PCC_REQUIRE(d_out && cap >= total, PCC_E_NOMEM, "%s: %lld keys in the lists, room for %lld", who, (long long)total, (long long)cap);
+  O4Own own(ctx->stream);
+  const size_t scratch_b = o4_merge_scratch_bytes(total, 1);
+  PCC_HIP(hipMalloc(&own.p, scratch_b));
+  own.tab.resize(1);
+  uint32_t* d_count = nullptr;
+  PCC_TRY(o4_merge_async(ctx, &job, 1, key_shift, (char*)own.p, scratch_b, own.tab.data(), &d_count));
+  uint32_t count = 0;
+  PCC_HIP(hipMemcpyAsync(&count, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+  PCC_HIP(hipStreamSynchronize(ctx->stream));
+  *h_count = (int64_t)count;
   return PCC_OK;
 }
 
@@ -470,24 +645,27 @@ static int o4_named(int rc, const char* who, int frame) {
   return rc;
 }
 
-extern "C" int pcc_octree_decode_frames_ref(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
-                                            const int32_t* d_ref_points, int64_t n_ref, int32_t* d_points, int32_t* h_points,
-                                            int64_t cap_points, int64_t* h_point_offsets) {
-  const char* who = "pcc_octree_decode_frames_ref";
-  PCC_REQUIRE(ctx && h_blobs && h_lens && h_point_offsets && n_frames >= 1 && n_frames <= 65535 && n_ref >= 0 &&
-                  n_ref < ((int64_t)1 << 27) && (n_ref == 0 || d_ref_points),
-              PCC_E_ARG, "%s: bad argument (n_frames=%d n_ref=%lld)", who, n_frames, (long long)n_ref);
+// The frames of a decode call have positions: the caller's references (oldest first), then the blobs' frames.  A
+// version-4 blob whose byte 3 holds W - 1 is coded against the union of the W frames in front of its own.
+static int o4_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
+                            const int32_t* const* d_refs, const int64_t* n_ref, int n_refs, int32_t* d_points, int32_t* h_points,
+                            int64_t cap_points, int64_t* h_point_offsets) {
   const int nb = n_frames;
   std::vector<int> ver((size_t)nb);
   std::vector<O4Info> info((size_t)nb);
-  int64_t points = 0, bodies = 0, max_n = n_ref;
+  int64_t points = 0, bodies = 0, max_n = 0;
+  for (int r = 0; r < n_refs; ++r) max_n = std::max(max_n, n_ref[r]);
   h_point_offsets[0] = 0;
+  int max_w = 1;
   for (int f = 0; f < nb; ++f) {
     const int v = pcc_octree_inter_info(h_blobs[f], h_lens[f], &ver[(size_t)f], &info[(size_t)f].n, nullptr, nullptr);
     if (v != PCC_OK) return o4_named(v, who, f);
     if (ver[(size_t)f] == 4) {
       const int rc = o4_parse(h_blobs[f], h_lens[f], &info[(size_t)f]);
       if (rc != PCC_OK) return o4_named(rc, who, f);
+      PCC_REQUIRE(info[(size_t)f].window <= kO4MaxWindow, PCC_E_STREAM, "%s: frame %d: octree blob v4: a window of %d frames (byte 3), at most %d",
+                  who, f, info[(size_t)f].window, kO4MaxWindow);
+      max_w = std::max(max_w, info[(size_t)f].window);
       bodies += o4_round(h_lens[f] - info[(size_t)f].off_p0, 16);
     }
     points += info[(size_t)f].n;
@@ -497,32 +675,55 @@ extern "C" int pcc_octree_decode_frames_ref(pcc_ctx* ctx, const uint8_t* const* 
   PCC_REQUIRE(points < ((int64_t)1 << 31), PCC_E_ARG, "%s: the blobs announce %lld points in all", who, (long long)points);
   if (points == 0 || (!d_points && !h_points)) return PCC_OK;
   PCC_REQUIRE(cap_points >= points, PCC_E_NOMEM, "%s: %lld points, capacity %lld", who, (long long)points, (long long)cap_points);
-  // what a predicted frame is coded against: the frame decoded before it, for blob 0 the caller's
+  // what a predicted frame is coded against: the frames decoded before it, in front of blob 0 the caller's
+  auto n_at = [&](int q) { return q < n_refs ? n_ref[q] : info[(size_t)(q - n_refs)].n; };
+  int64_t max_window = 0;   // keys of the largest window of more than one frame
   for (int f = 0; f < nb; ++f) {
     if (ver[(size_t)f] != 4) continue;
-    const int64_t have = f == 0 ? n_ref : info[(size_t)f - 1].n;
-    PCC_REQUIRE(f > 0 || n_ref > 0, PCC_E_ARG, "%s: frame 0: a predicted frame (blob version 4) needs its reference", who);
-    PCC_REQUIRE(have == (int64_t)info[(size_t)f].ref_n, PCC_E_ARG,
-                "%s: frame %d: the reference differs: it has %lld points, the blob was coded against %u", who, f, (long long)have,
-                info[(size_t)f].ref_n);
+    const O4Info& o = info[(size_t)f];
+    const int p = n_refs + f, W = o.window;
+    PCC_REQUIRE(p > 0 || W > 1, PCC_E_ARG, "%s: frame 0: a predicted frame (blob version 4) needs its reference", who);
+    PCC_REQUIRE(W <= p, PCC_E_ARG, "%s: frame %d: a predicted frame (blob version 4) needs %d frames in front of it, %d are here", who, f,
+                W, p);
+    if (W == 1) {
+      PCC_REQUIRE(n_at(p - 1) == (int64_t)o.ref_n, PCC_E_ARG,
+                  "%s: frame %d: the reference differs: it has %lld points, the blob was coded against %u", who, f,
+                  (long long)n_at(p - 1), o.ref_n);
+      continue;
+    }
+    int64_t most = 0, sum = 0;
+    for (int q = p - W; q < p; ++q) {
+      most = std::max(most, n_at(q));
+      sum += n_at(q);
+    }
+    PCC_REQUIRE(most <= (int64_t)o.ref_n && (int64_t)o.ref_n <= sum && sum < ((int64_t)1 << 27), PCC_E_ARG,
+                "%s: frame %d: the reference differs: the %d frames in front of it have %lld .. %lld distinct points, the blob was coded "
+                "against %u",
+                who, f, W, (long long)most, (long long)sum, o.ref_n);
+    max_window = std::max(max_window, sum);
   }
-  // the call's own block (the arena is each frame's in turn): points | keys of the reference | bodies | sums | status
-  struct Own {
-    void* p = nullptr;
-    ~Own() { if (p) (void)hipFree(p); }
-  } own;
-  const size_t pts_b = d_points ? 0 : pcc_align((size_t)points * 12), keys_b = pcc_align((size_t)max_n * 8 + 16);
-  const size_t bodies_b = pcc_align((size_t)bodies + 16), sums_b = pcc_align((size_t)nb * 8), stat_b = pcc_align((size_t)nb * 4);
-  PCC_HIP(hipMalloc(&own.p, pts_b + keys_b + bodies_b + sums_b + stat_b));
+  // the call's own block (the arena is each frame's in turn): points | keys of the last max_w frames | a window's union
+  // and the merge's scratch | bodies | sums (per position, per blob) | status
+  hipStream_t st = ctx->stream;
+  O4Own own(st);
+  const int npos = n_refs + nb;
+  const size_t pts_b = d_points ? 0 : pcc_align((size_t)points * 12), slot_b = pcc_align((size_t)max_n * 8 + 16);
+  const size_t keys_b = (size_t)max_w * slot_b, union_b = max_window ? pcc_align((size_t)max_window * 8 + 16) : 0;
+  const size_t merge_b = max_window ? o4_merge_scratch_bytes(max_window, 1) : 0;
+  const size_t bodies_b = pcc_align((size_t)bodies + 16), sums_b = pcc_align((size_t)(npos + nb) * 8), stat_b = pcc_align((size_t)nb * 4);
+  PCC_HIP(hipMalloc(&own.p, pts_b + keys_b + union_b + merge_b + bodies_b + sums_b + stat_b));
   char* base = (char*)own.p;
   int32_t* pts = d_points ? d_points : (int32_t*)base;
-  uint64_t* keys = (uint64_t*)(base + pts_b);
-  uint8_t* d_bodies = (uint8_t*)(base + pts_b + keys_b);
-  unsigned long long* sums = (unsigned long long*)(base + pts_b + keys_b + bodies_b);
-  int32_t* status = (int32_t*)(base + pts_b + keys_b + bodies_b + sums_b);
-  hipStream_t st = ctx->stream;
+  char* ring = base + pts_b;
+  uint64_t* merged = (uint64_t*)(ring + keys_b);
+  char* merge_scratch = ring + keys_b + union_b;
+  uint8_t* d_bodies = (uint8_t*)(merge_scratch + merge_b);
+  unsigned long long* sums = (unsigned long long*)((char*)d_bodies + bodies_b);   // [npos] of the frames, [nb] of the unions
+  int32_t* status = (int32_t*)((char*)sums + sums_b);
+  own.tab.reserve((size_t)nb);   // (the merges' tables stay where they are until the synchronisation)
   PccProfScope prof(ctx, "octree4_decode", points, nb, 0, 0);
   PCC_HIP(hipMemsetAsync(sums, 0, sums_b + stat_b, st));
+  std::vector<char> keyed((size_t)npos, 0);
   int64_t body_at = 0;
   for (int f = 0; f < nb; ++f) {
     const O4Info& o = info[(size_t)f];
@@ -538,13 +739,39 @@ extern "C" int pcc_octree_decode_frames_ref(pcc_ctx* ctx, const uint8_t* const* 
       }
       continue;
     }
-    const int32_t* ref = f == 0 ? d_ref_points : pts + 3 * h_point_offsets[f - 1];
+    const int p = n_refs + f, W = o.window;
+    auto keys_of = [&](int q) { return (uint64_t*)(ring + (size_t)(q % max_w) * slot_b); };
+    for (int q = p - W; q < p; ++q) {   // the keys of the window's frames, each formed once
+      if (keyed[(size_t)q] || n_at(q) == 0) continue;
+      const int32_t* src = q < n_refs ? d_refs[q] : pts + 3 * h_point_offsets[q - n_refs];
+      hipLaunchKernelGGL(k_o4_keys, dim3(nblk(n_at(q), 256)), dim3(256), 0, st, src, n_at(q), keys_of(q), sums + q, status + f);
+      PCC_CHECK_LAUNCH();
+      keyed[(size_t)q] = 1;
+    }
+    const uint64_t* ref_keys = keys_of(p - 1);
+    const unsigned long long* ref_sum = sums + (p - 1);
     const int64_t rn = (int64_t)o.ref_n;
-    hipLaunchKernelGGL(k_o4_keys, dim3(nblk(rn, 256)), dim3(256), 0, st, ref, rn, keys, sums + f, status + f);
-    PCC_CHECK_LAUNCH();
+    if (W > 1) {   // the union of the window: its size and its sum are compared on the device (status 16)
+      O4MergeJob job;
+      job.nl = W;
+      job.out = merged;
+      for (int i = 0; i < W; ++i) {
+        job.list[i] = keys_of(p - W + i);
+        job.n[i] = n_at(p - W + i);
+      }
+      own.tab.emplace_back();
+      uint32_t* d_count = nullptr;
+      PCC_TRY(o4_merge_async(ctx, &job, 1, 0, merge_scratch, merge_b, &own.tab.back(), &d_count));
+      hipLaunchKernelGGL(k_o4_countcheck, dim3(1), dim3(1), 0, st, (const uint32_t*)d_count, o.ref_n, status + f);
+      PCC_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_o4_keysum, dim3(nblk(rn, 256)), dim3(256), 0, st, (const uint64_t*)merged, rn, 0, 32768, sums + npos + f);
+      PCC_CHECK_LAUNCH();
+      ref_keys = merged;
+      ref_sum = sums + npos + f;
+    }
     const int64_t body_b = h_lens[f] - o.off_p0;
     PCC_HIP(hipMemcpyAsync(d_bodies + body_at, h_blobs[f] + o.off_p0, (size_t)body_b, hipMemcpyHostToDevice, st));
-    PCC_TRY(o4_decode_one(ctx, o, d_bodies + body_at, keys, rn, sums + f, out, status + f));
+    PCC_TRY(o4_decode_one(ctx, o, d_bodies + body_at, ref_keys, rn, ref_sum, out, status + f));
     body_at += o4_round(body_b, 16);
   }
   std::vector<int32_t> h_status((size_t)nb);
@@ -562,6 +789,31 @@ extern "C" int pcc_octree_decode_frames_ref(pcc_ctx* ctx, const uint8_t* const* 
     PCC_HIP(hipStreamSynchronize(st));
   }
   return PCC_OK;
+}
+
+extern "C" int pcc_octree_decode_frames_refs(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
+                                             const int32_t* const* d_ref_points, const int64_t* n_ref, int n_refs, int32_t* d_points,
+                                             int32_t* h_points, int64_t cap_points, int64_t* h_point_offsets) {
+  const char* who = "pcc_octree_decode_frames_refs";
+  PCC_REQUIRE(ctx && h_blobs && h_lens && h_point_offsets && n_frames >= 1 && n_frames <= 65535 && n_refs >= 0 &&
+                  n_refs <= kO4MaxWindow && (n_refs == 0 || (d_ref_points && n_ref)),
+              PCC_E_ARG, "%s: bad argument (n_frames=%d n_refs=%d)", who, n_frames, n_refs);
+  for (int r = 0; r < n_refs; ++r)
+    PCC_REQUIRE(n_ref[r] >= 0 && n_ref[r] < ((int64_t)1 << 27) && (n_ref[r] == 0 || d_ref_points[r]), PCC_E_ARG,
+                "%s: bad argument (reference %d: n_ref=%lld)", who, r, (long long)n_ref[r]);
+  return o4_decode_frames(who, ctx, h_blobs, h_lens, n_frames, d_ref_points, n_ref, n_refs, d_points, h_points, cap_points,
+                          h_point_offsets);
+}
+
+extern "C" int pcc_octree_decode_frames_ref(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
+                                            const int32_t* d_ref_points, int64_t n_ref, int32_t* d_points, int32_t* h_points,
+                                            int64_t cap_points, int64_t* h_point_offsets) {
+  const char* who = "pcc_octree_decode_frames_ref";
+  PCC_REQUIRE(ctx && h_blobs && h_lens && h_point_offsets && n_frames >= 1 && n_frames <= 65535 && n_ref >= 0 &&
+                  n_ref < ((int64_t)1 << 27) && (n_ref == 0 || d_ref_points),
+              PCC_E_ARG, "%s: bad argument (n_frames=%d n_ref=%lld)", who, n_frames, (long long)n_ref);
+  return o4_decode_frames(who, ctx, h_blobs, h_lens, n_frames, &d_ref_points, &n_ref, n_ref > 0 ? 1 : 0, d_points, h_points, cap_points,
+                          h_point_offsets);
 }
 
 // host only: what the head of a geometry blob of version 2 or 4 says

@@ -2,10 +2,12 @@
 // its header, parsed and checked against the blob's length before anything is reserved or launched.  Plain C++ (no
 // HIP): tests/fuzz/fuzz_octree4_header.cpp puts it under the sanitizers.
 //
-//   'O' 4 depth 0 | u32 n | i32 origin[3] | u32 payload_len |
+//   'O' 4 depth (W - 1) | u32 n | i32 origin[3] | u32 payload_len |
 //   u32 level_n[depth] | u32 S | u32 n_chunks | u32 ref_n | u64 ref_sum | u16 p0[324] | u32 words[n_chunks] | chunks
 //   chunk           = 64 x (state lo, state hi) | u16 len[64] | words of lane 0 | words of lane 1 | ..
 //
+// W - 1: the reference is the union of the W decoded frames in front of the blob's (0: the one frame, the bytes of
+// before history=; the parser records any value, the decode entries refuse a window above 8).
 // Version 2 (octree2_blob.h) with a context split in three by the reference byte of the node; a version-4 blob always
 // has points (a frame without points is the 24-byte version-2 blob) and is read whole (lod 0).  The checks are version
 // 2's: every level at most 8 times the one above and at most n, the chunk count what S and the node count make it, the
@@ -25,6 +27,7 @@ constexpr int kO4Lanes = 64;
 
 struct O4Info {
   int depth;
+  int window;             // W: byte 3 + 1
   int64_t n, n_nodes, S, nc, level_n[16];
   int32_t origin[3];
   uint32_t ref_n;
@@ -48,6 +51,7 @@ static inline uint32_t o4_u32(const uint8_t* p) {
 static inline int o4_parse(const uint8_t* h_in, int64_t len, O4Info* o) {
   O4_REQUIRE(h_in && len >= kO4Header && h_in[0] == 'O' && h_in[1] == 4, "octree blob v4: bad header");
   o->depth = h_in[2];
+  o->window = (int)h_in[3] + 1;
   o->n = (int64_t)o4_u32(h_in + 4);
   for (int a = 0; a < 3; ++a) o->origin[a] = (int32_t)o4_u32(h_in + 8 + 4 * a);
   const int64_t payload = (int64_t)o4_u32(h_in + 20);

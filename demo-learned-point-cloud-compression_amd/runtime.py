@@ -729,6 +729,52 @@ class Runtime:
         views = [pts[offs[f]:offs[f + 1]] for f in range(nb)]
         return (views, pts) if whole else views
 
+    def octree_encode_frames_inter_hist(self, keys, n_frames, key_shift=0, intra_period=0, n_ref_frames=0, history=1):
+        """octree_encode_frames_inter with windows of up to `history` (1 .. 8) frames
+        (pcc_octree_encode_frames_inter_hist; include/pcc.h has the rule): a predicted frame is coded against the union
+        of the frames of its window, byte 3 of its blob holds their number - 1.  The first n_ref_frames (0 .. history)
+        frames of the keys are only references and get no blob: n_frames - n_ref_frames blobs."""
+        n = keys.shape[0]
+        cap = 8192 * n_frames + 17 * max(n, 1)
+        out = np.empty(cap, dtype=np.uint8)
+        offs = (C.c_int64 * (n_frames + 1))()
+        check(self.lib.pcc_octree_encode_frames_inter_hist(self.ctx, _ptr(keys), n, n_frames, key_shift, int(intra_period),
+                                                           int(n_ref_frames), int(history), _np_ptr(out), cap, offs),
+              "pcc_octree_encode_frames_inter_hist")
+        return [out[offs[f]:offs[f + 1]].tobytes() for f in range(int(n_ref_frames), n_frames)]
+
+    def octree_decode_frames_refs(self, blobs, references=(), device=False, whole=False):
+        """octree_decode_frames_ref with up to 8 references, oldest first (pcc_octree_decode_frames_refs): each an int32
+        [n, 3] device tensor of distinct points in Morton order.  A version-4 blob says in its byte 3 how many of the
+        frames in front of it — the references, then the frames decoded in the call — its reference is the union of."""
+        nb = len(blobs)
+        if nb == 0:
+            return ([], None) if whole else []
+        bufs = [np.frombuffer(b, dtype=np.uint8) for b in blobs]
+        ptrs = (C.c_void_p * nb)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
+        lens = (C.c_int64 * nb)(*[b.shape[0] for b in bufs])
+        offs = (C.c_int64 * (nb + 1))()
+        nr = len(references)
+        ref_ptrs = (C.c_void_p * max(nr, 1))(*[_ptr(r) if r.shape[0] else None for r in references])
+        ref_n = (C.c_int64 * max(nr, 1))(*[int(r.shape[0]) for r in references])
+        call = lambda *a: self.lib.pcc_octree_decode_frames_refs(self.ctx, ptrs, lens, nb, ref_ptrs, ref_n, nr, *a, offs)
+        pts = self._sized_output(call, "pcc_octree_decode_frames_refs", offs, lambda total: (total, 3), torch.int32, device)
+        views = [pts[offs[f]:offs[f + 1]] for f in range(nb)]
+        return (views, pts) if whole else views
+
+    def merge_keys(self, lists, key_shift=0):
+        """the union of 1 .. 8 lists of Morton keys (pcc_merge_keys): int64 device tensors, each strictly increasing
+        under (key & (2^48 - 1)) >> key_shift -> one int64 device tensor, strictly increasing under the same comparison;
+        of equal keys the one of the first list that holds it is kept, bits from 48 up are carried along."""
+        nl = len(lists)
+        total = sum(int(k.shape[0]) for k in lists)
+        out = torch.empty(max(total, 1), dtype=torch.int64, device=self.device)
+        ptrs = (C.c_void_p * max(nl, 1))(*[_ptr(k) if k.shape[0] else None for k in lists])
+        ns = (C.c_int64 * max(nl, 1))(*[int(k.shape[0]) for k in lists])
+        count = C.c_int64(0)
+        check(self.lib.pcc_merge_keys(self.ctx, ptrs, ns, nl, int(key_shift), _ptr(out), total, C.byref(count)), "pcc_merge_keys")
+        return out[:count.value]
+
     @staticmethod
     def octree_inter_info(blob):
         """what the head of a geometry blob of version 2 or 4 says (pcc_octree_inter_info, host only; the blob whole):

@@ -742,7 +742,7 @@ int pcc_octree_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs,
  * of nodes in runs of S to the 64 lanes of a chunk, the per-lane rANS states,
  * word runs, length table, chunk table, the p0 formula, the adaptation and the
  * implied eighth bit are version 2's.
- *   'O' 4 depth 0 | u32 n | i32 origin[3] | u32 payload_len |
+ *   'O' 4 depth (W-1) | u32 n | i32 origin[3] | u32 payload_len |
  *   u32 level_n[depth] | u32 S | u32 n_chunks | u32 ref_n | u64 ref_sum |
  *   u16 p0[324] | u32 words[n_chunks] | chunks
  * Reference byte: R, the reference, is a set of distinct lattice points in the
@@ -790,6 +790,49 @@ int pcc_octree_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs,
  *   _inter_info : host only, versions 2 and 4: version, points, predicted
  *     (0 / 1) and ref_points (0 for version 2), each nullable; the blob must
  *     be whole.
+ * The window (history = K, 1 <= K <= 8): R may be the union of several frames.
+ *   Every frame of a call has a position: the leading reference frames first,
+ *   then the coded frames; reference frames get no blob.  A predicted frame t
+ *   has a window of W_t frames, 1 <= W_t <= K: the W_t frames directly in
+ *   front of it.  The window never reaches back past the latest intra frame
+ *   (that frame itself may be in it) and never past a frame without points
+ *   (the frame behind an empty frame is intra, as before); so among the
+ *   reference frames only the trailing run of non-empty ones exists, and at
+ *   most K of them count.  Which frames are intra is decided as before
+ *   (intra_period, frame 0 without a reference, the empty-frame rule).  R is
+ *   the set of distinct lattice points of the window's frames (with key_shift
+ *   = 3 k: cells), ref_n = |R|, ref_sum the sum over R.  Byte 3 of the head
+ *   holds W_t - 1, so K = 1 writes the bytes of before and a decoder reads
+ *   from the blob how many decoded frames to merge.  The header's parser
+ *   accepts any byte 3; the decode entries refuse a window above 8
+ *   (PCC_E_STREAM naming the frame).
+ *   _encode_frames_inter_hist : _encode_frames_inter with the first
+ *     n_ref_frames (0 .. history) frames of the keys as references and
+ *     windows of up to `history` frames.  _encode_frames_inter is its
+ *     (ref_first, 1) form; a call in which no window exceeds one frame queues
+ *     what that entry queues.  The unions of all larger windows are formed on
+ *     the device in one merge (pcc_merge_keys' kernels) with ONE host
+ *     synchronisation more per call, for their sizes.  The keys of a window's
+ *     frames must total fewer than 2^27: PCC_E_ARG naming the frame.
+ *   _decode_frames_refs : _decode_frames_ref with n_refs (0 .. 8) references,
+ *     oldest first, d_ref_points[r] as d_ref_points there, n_ref[r] >= 0.  The
+ *     call keeps the keys of the last decoded frames, merges the W a blob asks
+ *     for and takes ref_sum over the union.  For W > 1 the host can only bound
+ *     ref_n (the largest of the window's frames <= ref_n <= their sum, checked
+ *     before anything is sized); equality is checked on the device with
+ *     ref_sum.  A window that reaches in front of the first frame at hand:
+ *     PCC_E_ARG "needs W frames in front of it, n are here".
+ *     _decode_frames_ref is its form with at most one reference.
+ *   pcc_merge_keys : the union of 1 .. 8 lists of keys on the device, each
+ *     strictly increasing under (key & (2^48 - 1)) >> key_shift (bits from 48
+ *     up, the frame index of a call's keys, are carried along and not
+ *     compared) -> d_out [cap >= the lists' keys in all], strictly increasing
+ *     under the same comparison; of equal keys the one of the first list that
+ *     holds it is kept.  d_lists is a host array of device pointers.  A merge,
+ *     not a sort: one thread per element, binary searches in the other lists,
+ *     one scan of the keep flags, a scatter to computed places — no atomics,
+ *     the same output on every run.  *h_count = the union's size (one
+ *     synchronisation).
  * pcc_octree_decode_frames, _decode_frames_lod, _lod_info, _blob_version and
  * the one-blob entries go on refusing version 4. */
 int pcc_octree_encode_frames_inter(pcc_ctx* ctx, const uint64_t* d_keys,
@@ -804,6 +847,21 @@ int pcc_octree_decode_frames_ref(pcc_ctx* ctx, const uint8_t* const* h_blobs,
                                  int64_t cap_points, int64_t* h_point_offsets);
 int pcc_octree_inter_info(const uint8_t* h_in, int64_t len, int* version,
                           int64_t* points, int* predicted, int64_t* ref_points);
+int pcc_octree_encode_frames_inter_hist(pcc_ctx* ctx, const uint64_t* d_keys,
+                                        int64_t n, int n_frames, int key_shift,
+                                        int intra_period, int n_ref_frames,
+                                        int history, uint8_t* h_out,
+                                        int64_t cap, int64_t* h_offsets);
+int pcc_octree_decode_frames_refs(pcc_ctx* ctx, const uint8_t* const* h_blobs,
+                                  const int64_t* h_lens, int n_frames,
+                                  const int32_t* const* d_ref_points,
+                                  const int64_t* n_ref, int n_refs,
+                                  int32_t* d_points, int32_t* h_points,
+                                  int64_t cap_points,
+                                  int64_t* h_point_offsets);
+int pcc_merge_keys(pcc_ctx* ctx, const uint64_t* const* d_lists,
+                   const int64_t* h_n, int n_lists, int key_shift,
+                   uint64_t* d_out, int64_t cap, int64_t* h_count);
 
 /* Lossless per-point attributes of such a sequence (near-lossless ones with a
  * bounded error: pcc_attr_encode_frames_nl below) (csrc/attr.hip: attribute

@@ -5,7 +5,14 @@ frame of version 2 and of version 4; encode and decode milliseconds per frame of
 to blobs on the host and back to host coordinates (version 2 through pcc_octree_encode_frames /
 pcc_octree_decode_frames, unchanged); and the decode time of one predicted sweep for runs of at most 128, 256 and 512
 nodes per lane (the blobs of the other two bounds come from the reference coder of tests/octree_inter_ref.py, the
-decoder takes S from the header).  PROFILE=1 adds the device time of the calls.  One JSON line per velocity."""
+decoder takes S from the header).  PROFILE=1 adds the device time of the calls.  One JSON line per velocity.
+
+--history K: the window of compress(..., history=) instead — for every window of 1 .. K frames on the same sweeps, bytes
+per predicted frame and encode and decode milliseconds per frame (history 1 through the entries of before), one JSON
+line per velocity, also written to profiles/geometry_history.json (--out: elsewhere).  PROFILE=1 adds the device time
+of one encode and one decode call at the largest window.  --calls N: only N encode and N decode calls at a window of K
+itself, sensor at rest (for a rocprofv3 --kernel-trace --stats run of its own)."""
+import argparse
 import importlib
 import json
 import os
@@ -34,13 +41,76 @@ def timed(fn, reps):
     return 1e3 * float(np.median(t)), out
 
 
+def history_calls(rt, wl, k, calls, n_frames):
+    frames = [f["points"].astype(np.int32) for f in wl.lidar_sequence(n_frames, 64, 1800)]
+    coords = np.concatenate([np.concatenate([np.full((p.shape[0], 1), f, np.int32), p], 1) for f, p in enumerate(frames)])
+    keys = rt.morton_keys(rt.to_device(coords))
+    rt.sort_pairs(keys)
+    for _ in range(calls):
+        blobs = rt.octree_encode_frames_inter(keys, n_frames) if k == 1 else rt.octree_encode_frames_inter_hist(keys, n_frames, history=k)
+        got = rt.octree_decode_frames_ref(blobs) if k == 1 else rt.octree_decode_frames_refs(blobs)
+    torch.cuda.synchronize()
+    print(json.dumps({"history": k, "calls": calls, "bytes": [len(b) for b in blobs], "points": [int(p.shape[0]) for p in got]}))
+
+
+def history(rt, wl, k_max, reps, n_frames, out):
+    lines = []
+    for velocity in ((0, 0, 0), (10, 0, 0)):
+        frames = [f["points"].astype(np.int32) for f in wl.lidar_sequence(n_frames, 64, 1800, velocity=velocity)]
+        coords = np.concatenate([np.concatenate([np.full((p.shape[0], 1), f, np.int32), p], 1) for f, p in enumerate(frames)])
+        keys = rt.morton_keys(rt.to_device(coords))
+        rt.sort_pairs(keys)
+        _, b2 = timed(lambda: rt.octree_encode_frames(keys, n_frames), 1)
+        want = rt.octree_decode_frames(b2)
+        res = {"velocity": velocity, "frames": n_frames, "points": [int(p.shape[0]) for p in frames],
+               "v2_bytes_per_frame": sum(len(b) for b in b2[1:]) / (n_frames - 1), "history": {}}
+        for k in range(1, k_max + 1):
+            if k == 1:
+                encode, decode = (lambda: rt.octree_encode_frames_inter(keys, n_frames)), rt.octree_decode_frames_ref
+            else:
+                encode, decode = (lambda: rt.octree_encode_frames_inter_hist(keys, n_frames, history=k)), rt.octree_decode_frames_refs
+            enc, blobs = timed(encode, reps)
+            dec, got = timed(lambda: decode(blobs), reps)
+            assert all(np.array_equal(a, b) for a, b in zip(got, want))
+            assert [b[3] + 1 for b in blobs[1:]] == [min(f, k) for f in range(1, n_frames)]
+            per = sum(len(b) for b in blobs[1:]) / (n_frames - 1)
+            res["history"][str(k)] = {"bytes_per_predicted_frame": per, "bytes_ratio_predicted": per / res["v2_bytes_per_frame"],
+                                      "bytes_last_frame": len(blobs[-1]), "encode_ms_per_frame": enc / n_frames,
+                                      "decode_ms_per_frame": dec / n_frames}
+        if os.environ.get("PROFILE"):
+            rt.prof_enable(True, reserve=64)
+            decode(encode())
+            torch.cuda.synchronize()
+            res["device_ms"] = [(op, round(ms, 4)) for op, ms, _ in rt.prof_records()]
+            rt.prof_enable(False)
+        lines.append(json.dumps(res))
+        print(lines[-1], flush=True)
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--history", type=int, default=0, metavar="K", help="measure windows of 1 .. K frames (1 .. 8)")
+    ap.add_argument("--calls", type=int, default=0, metavar="N", help="with --history: N encode and decode calls at K alone")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "geometry_history.json"))
+    args = ap.parse_args()
+    if not 0 <= args.history <= 8:
+        ap.error("--history takes 1 .. 8")
     importlib.import_module(PKG)
     wl = importlib.import_module(PKG + ".workloads")
     rtm = importlib.import_module(PKG + ".runtime")
     rt = rtm.Runtime(0)
     reps = int(os.environ.get("REPS", "10"))
     n_frames = int(os.environ.get("FRAMES", "10"))
+    if args.history:
+        with rt:
+            if args.calls:
+                history_calls(rt, wl, args.history, args.calls, n_frames)
+            else:
+                history(rt, wl, args.history, reps, n_frames, args.out)
+        rt.close()
+        return
     s_bounds = [int(s) for s in os.environ.get("SMAX", "128,256,512").split(",") if s]
     with rt:
         for velocity in ((0, 0, 0), (10, 0, 0)):
