@@ -541,7 +541,8 @@ int pcc_rans_decode_range(const uint8_t* h_in, int64_t len, const int32_t* h_idx
  * decoder cannot read it, this library's decoders read both versions.
  *   tables : the CDF set in HBM (the arguments of pcc_rans_encode), made once
  *   d_sym  : int32 [n_streams, n]; d_idx uint8 [n_streams, n] table index per
- *            symbol, or NULL: index = position / idx_run (channel-major arrays)
+ *            symbol, or NULL: index = position / idx_run (channel-major arrays).
+ *            The coder's domain: symbol - offset of its table fits int32.
  *   d_out  : n_streams streams at d_out + s * cap_each (device, 4-byte aligned);
  *            pcc_rans_dev_bound(n) bytes always suffice; h_lens[s] = bytes
  * encode synchronises the stream once (the lengths); decode does not: it takes
