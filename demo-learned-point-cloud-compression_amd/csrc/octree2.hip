@@ -48,6 +48,7 @@
 #include "lanerans.h"
 #include "octree2_blob.h"
 #include "octree4.h"
+#include "octree4_blob.h"
 
 #include <string.h>
 
@@ -1339,12 +1340,20 @@ extern "C" int pcc_octree_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* 
                           h_point_offsets);
 }
 
-// host only: what level `lod` of a version-2 blob needs (bytes of its shortest prefix) and gives (cells)
+// host only: what level `lod` of a version-2 or version-4 blob needs (bytes of its shortest prefix) and gives (cells)
 extern "C" int pcc_octree_lod_info(const uint8_t* h_in, int64_t len, int lod, int64_t* h_bytes, int64_t* h_cells) {
   PCC_REQUIRE(lod >= 0 && lod <= kO2MaxLod, PCC_E_ARG, "pcc_octree_lod_info: level of detail %d outside 0 .. %d", lod, kO2MaxLod);
+  if (h_in && len >= kO4Header && h_in[0] == 'O' && h_in[1] == 4) {   // a predicted frame: the same formulas over its offsets
+    O4Info o4;
+    O4Plan pl4;
+    PCC_TRY(o4_parse_lod(h_in, len, lod, false, &o4, &pl4));
+    if (h_bytes) *h_bytes = pl4.bytes;
+    if (h_cells) *h_cells = pl4.m;
+    return PCC_OK;
+  }
   const int v = pcc_octree_blob_version(h_in, len);
   if (v < 0) return v;
-  PCC_REQUIRE(v == 2, PCC_E_ARG, "pcc_octree_lod_info: blob version %d (levels of detail are a property of version 2)", v);
+  PCC_REQUIRE(v == 2, PCC_E_ARG, "pcc_octree_lod_info: blob version %d (levels of detail are a property of versions 2 and 4)", v);
   O2Info o;
   O2Plan pl;
   PCC_TRY(o2_parse(h_in, len, lod, false, &o, &pl));

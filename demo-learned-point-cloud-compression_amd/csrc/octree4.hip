@@ -29,8 +29,16 @@
 // frame in a decode call, which keeps the keys of the last frames it decoded.  Everything behind the merge sees a
 // reference of more keys and nothing else.
 //
+// A level of detail (lod = k > 0; octree4_blob.h has the plan): a prefix of the blob holds the levels above the cut
+// Lc = max(depth - k, 0), and a node above the cut has child cubes of side >= 2^k, unions of whole lod-k cells, so its
+// reference byte needs only the reference's CELLS at lod k.  pcc_octree_decode_frames_refs_lod keeps the keys of the
+// cells' corners (k_o4_keys with a shift), decodes levels 0 .. Lc - 1 with arrays sized from N' and m, and k_o4_cells
+// writes the m cells; the last lane of level Lc - 1 may stop in the middle of its run.  ref_n and ref_sum describe
+// full-resolution points and are not compared at a cut.  The lod-0 entries queue what they queued before.
+//
 // What the stream announces is never trusted: every size comes from the header's checks (octree4_blob.h), every
-// store is to an index below a bound the host sized the array from, every read of the stream is clamped to the chunk.
+// store is to an index below a bound the host sized the array from, every read of the stream is clamped to the chunk
+// and to the words of it that are present (a prefix ends inside its last needed chunk).
 #include "common.h"
 #include "lanerans.h"
 #include "octree2_blob.h"
@@ -85,16 +93,23 @@ __global__ __launch_bounds__(256) void k_o4_keysum(const uint64_t* __restrict__ 
   o4_sum_add(term, sum);
 }
 
-// the keys (bias 32768) and ref_sum of decoded points, which must be distinct and in Morton order: status |= 32
-__global__ __launch_bounds__(256) void k_o4_keys(const int32_t* __restrict__ pts, int64_t n, uint64_t* __restrict__ keys,
+// the keys (bias 32768) and ref_sum of decoded points, which must be distinct and in Morton order: status |= 32.  At a
+// level of detail (lod > 0) the rows are cells, each in [-(32768 >> lod), (32768 >> lod) - 1], and a cell's key is that
+// of its corner, the point cell << lod (the sum is then of the cells, and nobody reads it)
+__global__ __launch_bounds__(256) void k_o4_keys(const int32_t* __restrict__ pts, int64_t n, int lod, uint64_t* __restrict__ keys,
                                                  unsigned long long* __restrict__ sum, int32_t* __restrict__ status) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   unsigned long long term = 0;
   if (i < n) {
     const int x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    const uint64_t k = pcc_morton(0, x, y, z);
-    bool bad = x < -32768 || x > 32767 || y < -32768 || y > 32767 || z < -32768 || z > 32767;
-    if (i > 0) bad = bad || pcc_morton(0, pts[3 * i - 3], pts[3 * i - 2], pts[3 * i - 1]) >= k;
+    const int lim = 32768 >> lod;
+    bool bad = x < -lim || x >= lim || y < -lim || y >= lim || z < -lim || z >= lim;
+    // (a row out of range gives some key; the call is refused with status 32 whatever was decoded against it)
+    auto key_of = [lod](int cx, int cy, int cz) {   // (shifts of the bit patterns: a row may hold anything)
+      return pcc_morton(0, (int)((uint32_t)cx << lod), (int)((uint32_t)cy << lod), (int)((uint32_t)cz << lod));
+    };
+    const uint64_t k = key_of(x, y, z);
+    if (i > 0) bad = bad || key_of(pts[3 * i - 3], pts[3 * i - 2], pts[3 * i - 1]) >= k;
     if (bad) atomicOr(status, 32);
     keys[i] = k;
     term = o4_sum_term(x, y, z);
@@ -218,11 +233,15 @@ __global__ __launch_bounds__(256) void k_o4_link(const uint8_t* __restrict__ occ
 
 // the reference byte of nodes [a, b): the node's cell from a walk up its links, then for every child octant whether
 // the reference holds a key inside the child's cube — the cube of side 2^s at a corner that is a multiple of 2^s in
-// biased coordinates is the key range [G, G + 8^s), so two lower bounds over the sorted keys answer a child
+// biased coordinates is the key range [G, G + 8^s), so two lower bounds over the sorted keys answer a child.
+// n_ref_dev (or nullptr): where a merge left the size of the union that the keys are, when the host cannot know it (a
+// window at a level of detail); n_ref is then the room the keys have.
 __global__ __launch_bounds__(256) void k_o4_ref(const uint32_t* __restrict__ link, O4Tree t, int64_t a, int64_t b,
-                                                const uint64_t* __restrict__ ref_keys, int64_t n_ref, uint8_t* __restrict__ rb) {
+                                                const uint64_t* __restrict__ ref_keys, int64_t n_ref,
+                                                const uint32_t* __restrict__ n_ref_dev, uint8_t* __restrict__ rb) {
   const int64_t i = a + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= b) return;
+  if (n_ref_dev) n_ref = (int64_t)*n_ref_dev < n_ref ? (int64_t)*n_ref_dev : n_ref;
   int L = 0;
   while (L + 1 < t.depth && i >= t.off[L + 1]) ++L;
   uint64_t code = 0;
@@ -270,10 +289,33 @@ __global__ __launch_bounds__(256) void k_o4_points(const uint32_t* __restrict__ 
   points[3 * e + 2] = (int32_t)pcc_compact3(code) + t.origin[2];
 }
 
+// At a cut (lod > 0): t.off[Lc] = N' nodes were decoded and t.off[Lc + 1] - N' cells hang below them.  Every cell walks
+// up its Lc links; the octants on the way are its place among the cells of side 2^lod inside the root cube, whose
+// corner is a multiple of 2^lod: the global cell index is ((cell << lod) + origin) >> lod, version 2's convention.
+// Lc = 0: the one cell is the root cube's, origin >> lod.
+__global__ __launch_bounds__(256) void k_o4_cells(const uint32_t* __restrict__ link, O4Tree t, int Lc, int lod,
+                                                  int32_t* __restrict__ cells, int32_t* __restrict__ status) {
+  const int64_t n_dec = t.off[Lc], m = t.off[Lc + 1] - n_dec;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= m) return;
+  uint64_t code = 0;
+  uint32_t idx = (uint32_t)(n_dec + e);
+  for (int d = 0; d < Lc; ++d) {
+    const uint32_t l = link[idx];   // a link holds one of the N' nodes (or 0)
+    code |= (uint64_t)(l & 7u) << (3 * d);
+    idx = l >> 3;
+  }
+  if (Lc > 0 && idx != 0u) atomicOr(status, 8);
+  cells[3 * e] = (int32_t)(((int64_t)pcc_compact3(code >> 2) << lod) + t.origin[0]) >> lod;
+  cells[3 * e + 1] = (int32_t)(((int64_t)pcc_compact3(code >> 1) << lod) + t.origin[1]) >> lod;
+  cells[3 * e + 2] = (int32_t)(((int64_t)pcc_compact3(code) << lod) + t.origin[2]) >> lod;
+}
+
 // what k_o4_dec needs of a frame
 struct O4Dec {
   int64_t table_off, payload_off;      // in the body (p0 | chunk table | payload)
   int64_t n_nodes, start_last, start_prev;
+  int64_t words_here;                  // 16-bit words of the payload that are present (a prefix holds fewer than the table's sum)
   int32_t S;
 };
 constexpr int kCarryWords = 512;   // 32-bit words per slot: state, word position, 324 probabilities
@@ -299,11 +341,16 @@ __global__ __launch_bounds__(64) void k_o4_dec(const uint8_t* __restrict__ body,
   for (int64_t j = lane; j < c; j += kLanes) before += table[j];
   for (int sh = 32; sh >= 1; sh >>= 1) before += __shfl_xor(before, sh, 64);
   const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)table[c]);
-  const uint16_t* p = payload + before;   // the chunk table's sum is the payload's length (o4_parse): the chunk is inside it
-  if (cw < 3u * kLanes) {
+  // The chunk table's sum is the payload's length (o4_parse_lod), and of a whole blob all of it is here.  Of a prefix
+  // the last needed chunk is here as far as its lane l* (the host's plan): states and length table must be, and no word
+  // is read behind the `here` that are
+  if (cw < 3u * kLanes || before + 3ull * kLanes > (unsigned long long)d.words_here) {   // wave-uniform
     if (lane == 0) atomicOr(status, 1);
     return;
   }
+  const uint16_t* p = payload + before;
+  const unsigned long long left = (unsigned long long)d.words_here - before;
+  const uint32_t here = left < (unsigned long long)cw ? (uint32_t)left : cw;
   const uint32_t my_len = p[2 * kLanes + lane];
   uint32_t incl = my_len;
 #pragma unroll
@@ -323,6 +370,10 @@ __global__ __launch_bounds__(64) void k_o4_dec(const uint8_t* __restrict__ body,
   const bool carry_out = active && hi < node0 + S && hi < n_nodes;   // and goes on in a later one
   const unsigned long long act_mask = __ballot(active);
   if (act_mask == 0ull) return;
+  if (__ballot(active && rend > here) != 0ull) {   // a lane that decodes owns words that are not here (never a whole blob's)
+    if (lane == 0) atomicOr(status, 1);
+    return;
+  }
   int bad = (node0 >= n_nodes && my_len != 0u) ? 1 : 0;   // a lane without nodes has no words
   // the model: the frame's initial probabilities, or what the lane left behind
   for (int ctx = 0; ctx < kC4; ++ctx) s_model[ctx * kLanes + lane] = p0[ctx];
@@ -350,7 +401,7 @@ __global__ __launch_bounds__(64) void k_o4_dec(const uint8_t* __restrict__ body,
       const uint32_t ic = i < w_lo ? w_lo : (i >= w_hi ? w_hi - 1u : i);
       return s_words[ic - w_lo];
     }
-    return p[i < cw ? i : cw - 1u];   // a lane at the end of its run looks one word too far: never used
+    return p[i < here ? i : here - 1u];   // a lane at the end of its run looks one word too far: never used
   };
   uint32_t nextw = word_at(pos);
   // steps [s_lo, s_hi) of the runs: what some lane of the wave decodes
@@ -471,7 +522,7 @@ int o4_ref_bytes_async(pcc_ctx* ctx, int key_shift, const O4RefJob* jobs, int nf
                        N + j.n_points, link, st_dummy);
     PCC_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_o4_ref, dim3(nblk(N, 256)), dim3(256), 0, st, (const uint32_t*)link, t, (int64_t)0, N, j.ref_keys,
-                       j.ref_n, rb + j.occ_off);
+                       j.ref_n, (const uint32_t*)nullptr, rb + j.occ_off);
     PCC_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_o4_keysum, dim3(nblk(j.ref_n, 256)), dim3(256), 0, st, j.ref_keys, j.ref_n, key_shift, bias,
                        ref_sum + f);
@@ -573,16 +624,36 @@ extern "C" int pcc_merge_keys(pcc_ctx* ctx, const uint64_t* const* d_lists, cons
 }
 
 // ======================================================================== decoder
-// one predicted frame, queued on the stream: d_body = p0 | chunk table | payload of the blob (on the device), the
-// reference's keys (bias 32768, sorted) and its sum as k_o4_keys left them -> the frame's points.  The arena is this
-// frame's: reserved here.
-static int o4_decode_one(pcc_ctx* ctx, const O4Info& o, const uint8_t* d_body, const uint64_t* d_ref_keys, int64_t n_ref,
-                         const unsigned long long* d_ref_sum, int32_t* d_points, int32_t* d_status) {
+// one predicted frame, queued on the stream: d_body = p0 | chunk table | payload of the blob as far as the plan's bytes
+// (on the device), the reference's keys (bias 32768, sorted) and its sum as k_o4_keys left them -> the frame's points.
+// At a cut (pl.lod > 0): levels 0 .. Lc - 1 alone, every array sized from N' and m, the keys those of the reference's
+// cells' corners (d_ref_count: the size of a window's union, where the host does not know it) -> the frame's m cells;
+// ref_sum is of full-resolution points and is not compared.  The arena is this frame's: reserved here.
+static int o4_decode_one(pcc_ctx* ctx, const O4Info& o, const O4Plan& pl, const uint8_t* d_body, const uint64_t* d_ref_keys,
+                         int64_t n_ref, const uint32_t* d_ref_count, const unsigned long long* d_ref_sum, int32_t* d_points,
+                         int32_t* d_status) {
   hipStream_t st = ctx->stream;
-  const int64_t N = o.n_nodes, n = o.n;
+  const int64_t N = pl.n_dec, n = pl.m;
+  const int Lc = pl.Lc, lod = pl.lod;
+  O4Tree t;
+  int64_t run = 0;
+  for (int L = 0; L < 18; ++L) {
+    t.off[L] = run;
+    if (L < Lc) run += o.level_n[L];
+    else if (L == Lc) run += n;
+  }
+  t.depth = o.depth;
+  for (int a = 0; a < 3; ++a) t.origin[a] = o.origin[a];
+  t.bias = 32768;
+  t.key_shift = 0;
+  if (Lc == 0) {   // (lod >= depth) nothing to decode: the root cube is the one cell
+    hipLaunchKernelGGL(k_o4_cells, dim3(1), dim3(256), 0, st, (const uint32_t*)nullptr, t, 0, lod, d_points, d_status);
+    PCC_CHECK_LAUNCH();
+    return PCC_OK;
+  }
   int64_t max_level = 1;
   size_t scan_b = 0;
-  for (int L = 0; L < o.depth; ++L) {
+  for (int L = 0; L < Lc; ++L) {
     max_level = std::max(max_level, o.level_n[L]);
     scan_b += pcc_scan_scratch_bytes(o.level_n[L]) + 512;
   }
@@ -595,46 +666,44 @@ static int o4_decode_one(pcc_ctx* ctx, const O4Info& o, const uint8_t* d_body, c
   uint32_t* link = (uint32_t*)pcc_arena_alloc(ctx, (size_t)(N + n) * 4);
   uint32_t* carry = (uint32_t*)pcc_arena_alloc(ctx, 2 * kCarryWords * 4);
   if (!occ || !rb || !pcl || !excl || !link || !carry) return PCC_E_NOMEM;
-  O4Tree t;
-  int64_t run = 0;
-  for (int L = 0; L < 18; ++L) {
-    t.off[L] = run;
-    if (L < o.depth) run += o.level_n[L];
-    else if (L == o.depth) run += n;
-  }
-  t.depth = o.depth;
-  for (int a = 0; a < 3; ++a) t.origin[a] = o.origin[a];
-  t.bias = 32768;
-  t.key_shift = 0;
   O4Dec d;
   d.table_off = o.off_table - o.off_p0;
   d.payload_off = o.off_payload - o.off_p0;
-  d.n_nodes = N;
-  d.start_last = N - o.level_n[o.depth - 1];
+  d.n_nodes = o.n_nodes;   // of the whole tree: the level classes and the lanes' runs are the whole tree's
+  d.start_last = o.n_nodes - o.level_n[o.depth - 1];
   d.start_prev = o.depth >= 2 ? d.start_last - o.level_n[o.depth - 2] : 0;
+  d.words_here = lod == 0 ? o.payload_words : pl.last_off + pl.last_words;
   d.S = (int32_t)o.S;
-  hipLaunchKernelGGL(k_o4_refcheck, dim3(1), dim3(1), 0, st, d_ref_sum, (unsigned long long)o.ref_sum, d_status);
-  PCC_CHECK_LAUNCH();
+  if (lod == 0) {
+    hipLaunchKernelGGL(k_o4_refcheck, dim3(1), dim3(1), 0, st, d_ref_sum, (unsigned long long)o.ref_sum, d_status);
+    PCC_CHECK_LAUNCH();
+  }
   PCC_HIP(hipMemsetAsync(link, 0, (size_t)(N + n) * 4, st));
   const int64_t per_chunk = (int64_t)kLanes * o.S;
-  for (int L = 0; L <= o.depth; ++L) {
+  for (int L = 0; L <= Lc; ++L) {
     const int64_t a = t.off[L], b = t.off[L + 1];
-    if (L > 0) {   // the links of this level's nodes (L == depth: of the leaves) from the child counts of the level above
+    if (L > 0) {   // the links of this level's nodes (L == Lc: of the leaves, or cells) from the child counts of the level above
       const int64_t pa = t.off[L - 1], cnt = a - pa;
       PCC_TRY(pcc_scan_exclusive_u32(ctx, pcl, excl, cnt, nullptr));
       hipLaunchKernelGGL(k_o4_link, dim3(nblk(cnt, 256)), dim3(256), 0, st, (const uint8_t*)occ, (const uint32_t*)excl, pa, cnt, a, b,
                          link, d_status);
       PCC_CHECK_LAUNCH();
     }
-    if (L == o.depth) break;
-    hipLaunchKernelGGL(k_o4_ref, dim3(nblk(b - a, 256)), dim3(256), 0, st, (const uint32_t*)link, t, a, b, d_ref_keys, n_ref, rb);
+    if (L == Lc) break;
+    hipLaunchKernelGGL(k_o4_ref, dim3(nblk(b - a, 256)), dim3(256), 0, st, (const uint32_t*)link, t, a, b, d_ref_keys, n_ref,
+                       d_ref_count, rb);
     PCC_CHECK_LAUNCH();
-    const int64_t c_lo = a / per_chunk, c_hi = (b - 1) / per_chunk;   // < nc: the header's check of S and nc
+    // < nc: the header's check of S and nc; at a cut <= c*, and the last lane of level Lc - 1 may stop in the middle of
+    // its run: it leaves a carry that nothing picks up
+    const int64_t c_lo = a / per_chunk, c_hi = (b - 1) / per_chunk;
     hipLaunchKernelGGL(k_o4_dec, dim3((unsigned)(c_hi - c_lo + 1)), dim3(64), 0, st, d_body, d, a, b, c_lo, (const uint8_t*)rb, occ,
                        pcl, carry, (L + 1) & 1, L & 1, d_status);
     PCC_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(k_o4_points, dim3(nblk(n, 256)), dim3(256), 0, st, (const uint32_t*)link, t, d_points, d_status);
+  if (lod == 0)
+    hipLaunchKernelGGL(k_o4_points, dim3(nblk(n, 256)), dim3(256), 0, st, (const uint32_t*)link, t, d_points, d_status);
+  else
+    hipLaunchKernelGGL(k_o4_cells, dim3(nblk(n, 256)), dim3(256), 0, st, (const uint32_t*)link, t, Lc, lod, d_points, d_status);
   PCC_CHECK_LAUNCH();
   return PCC_OK;
 }
@@ -647,36 +716,55 @@ static int o4_named(int rc, const char* who, int frame) {
 
 // The frames of a decode call have positions: the caller's references (oldest first), then the blobs' frames.  A
 // version-4 blob whose byte 3 holds W - 1 is coded against the union of the W frames in front of its own.
+// lod > 0: blobs or prefixes of them, the references and every decoded frame the CELLS at that lod.  The keys the call
+// keeps are those of the cells' corners, under which the range search and the merge run as they do at lod 0.  ref_n and
+// ref_sum describe full-resolution points that nobody here holds: they are not compared, on the host or on the device
+// (include/pcc.h says what a wrong reference then gives); every bound comes from the header's checks, the prefix's
+// length and the rows at hand.  lod 0 queues what it queued before levels of detail.
 static int o4_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
-                            const int32_t* const* d_refs, const int64_t* n_ref, int n_refs, int32_t* d_points, int32_t* h_points,
-                            int64_t cap_points, int64_t* h_point_offsets) {
+                            const int32_t* const* d_refs, const int64_t* n_ref, int n_refs, int lod, int32_t* d_points,
+                            int32_t* h_points, int64_t cap_points, int64_t* h_point_offsets) {
   const int nb = n_frames;
   std::vector<int> ver((size_t)nb);
   std::vector<O4Info> info((size_t)nb);
+  std::vector<O4Plan> plan((size_t)nb);
+  std::vector<int64_t> rows((size_t)nb);   // points, or cells, of every frame
   int64_t points = 0, bodies = 0, max_n = 0;
   for (int r = 0; r < n_refs; ++r) max_n = std::max(max_n, n_ref[r]);
   h_point_offsets[0] = 0;
   int max_w = 1;
   for (int f = 0; f < nb; ++f) {
-    const int v = pcc_octree_inter_info(h_blobs[f], h_lens[f], &ver[(size_t)f], &info[(size_t)f].n, nullptr, nullptr);
-    if (v != PCC_OK) return o4_named(v, who, f);
+    if (lod == 0) {
+      const int v = pcc_octree_inter_info(h_blobs[f], h_lens[f], &ver[(size_t)f], &rows[(size_t)f], nullptr, nullptr);
+      if (v != PCC_OK) return o4_named(v, who, f);
+    } else if (h_blobs[f] && h_lens[f] >= kO2Header && h_blobs[f][0] == 'O' && h_blobs[f][1] == 2) {
+      O2Info o2;
+      O2Plan pl2;
+      const int rc = o2_parse(h_blobs[f], h_lens[f], lod, true, &o2, &pl2);
+      if (rc != PCC_OK) return o4_named(rc, who, f);
+      ver[(size_t)f] = 2;
+      rows[(size_t)f] = pl2.m;
+    } else {
+      ver[(size_t)f] = 4;   // or no blob of the two versions: o4_parse_lod's "bad header"
+    }
     if (ver[(size_t)f] == 4) {
-      const int rc = o4_parse(h_blobs[f], h_lens[f], &info[(size_t)f]);
+      const int rc = o4_parse_lod(h_blobs[f], h_lens[f], lod, true, &info[(size_t)f], &plan[(size_t)f]);
       if (rc != PCC_OK) return o4_named(rc, who, f);
       PCC_REQUIRE(info[(size_t)f].window <= kO4MaxWindow, PCC_E_STREAM, "%s: frame %d: octree blob v4: a window of %d frames (byte 3), at most %d",
                   who, f, info[(size_t)f].window, kO4MaxWindow);
       max_w = std::max(max_w, info[(size_t)f].window);
-      bodies += o4_round(h_lens[f] - info[(size_t)f].off_p0, 16);
+      rows[(size_t)f] = plan[(size_t)f].m;
+      bodies += o4_round(plan[(size_t)f].bytes - info[(size_t)f].off_p0, 16);
     }
-    points += info[(size_t)f].n;
-    max_n = std::max(max_n, info[(size_t)f].n);
+    points += rows[(size_t)f];
+    max_n = std::max(max_n, rows[(size_t)f]);
     h_point_offsets[f + 1] = points;
   }
   PCC_REQUIRE(points < ((int64_t)1 << 31), PCC_E_ARG, "%s: the blobs announce %lld points in all", who, (long long)points);
   if (points == 0 || (!d_points && !h_points)) return PCC_OK;
   PCC_REQUIRE(cap_points >= points, PCC_E_NOMEM, "%s: %lld points, capacity %lld", who, (long long)points, (long long)cap_points);
   // what a predicted frame is coded against: the frames decoded before it, in front of blob 0 the caller's
-  auto n_at = [&](int q) { return q < n_refs ? n_ref[q] : info[(size_t)(q - n_refs)].n; };
+  auto n_at = [&](int q) { return q < n_refs ? n_ref[q] : rows[(size_t)(q - n_refs)]; };
   int64_t max_window = 0;   // keys of the largest window of more than one frame
   for (int f = 0; f < nb; ++f) {
     if (ver[(size_t)f] != 4) continue;
@@ -686,9 +774,10 @@ static int o4_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const*
     PCC_REQUIRE(W <= p, PCC_E_ARG, "%s: frame %d: a predicted frame (blob version 4) needs %d frames in front of it, %d are here", who, f,
                 W, p);
     if (W == 1) {
-      PCC_REQUIRE(n_at(p - 1) == (int64_t)o.ref_n, PCC_E_ARG,
+      PCC_REQUIRE(lod > 0 || n_at(p - 1) == (int64_t)o.ref_n, PCC_E_ARG,
                   "%s: frame %d: the reference differs: it has %lld points, the blob was coded against %u", who, f,
                   (long long)n_at(p - 1), o.ref_n);
+      PCC_REQUIRE(n_at(p - 1) >= 1, PCC_E_ARG, "%s: frame %d: the reference differs: it has no cells", who, f);
       continue;
     }
     int64_t most = 0, sum = 0;
@@ -696,7 +785,7 @@ static int o4_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const*
       most = std::max(most, n_at(q));
       sum += n_at(q);
     }
-    PCC_REQUIRE(most <= (int64_t)o.ref_n && (int64_t)o.ref_n <= sum && sum < ((int64_t)1 << 27), PCC_E_ARG,
+    PCC_REQUIRE((lod > 0 ? most >= 1 : most <= (int64_t)o.ref_n && (int64_t)o.ref_n <= sum) && sum < ((int64_t)1 << 27), PCC_E_ARG,
                 "%s: frame %d: the reference differs: the %d frames in front of it have %lld .. %lld distinct points, the blob was coded "
                 "against %u",
                 who, f, W, (long long)most, (long long)sum, o.ref_n);
@@ -727,11 +816,13 @@ static int o4_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const*
   int64_t body_at = 0;
   for (int f = 0; f < nb; ++f) {
     const O4Info& o = info[(size_t)f];
+    const O4Plan& pl = plan[(size_t)f];
     int32_t* out = pts + 3 * h_point_offsets[f];
-    if (o.n == 0) continue;
+    if (rows[(size_t)f] == 0) continue;
     if (ver[(size_t)f] != 4) {   // an intra frame: version 2's decoder, to its place in the output
       int64_t offs2[2];
-      const int rc = pcc_octree_decode_frames(ctx, h_blobs + f, h_lens + f, 1, out, nullptr, o.n, offs2);
+      const int rc = lod == 0 ? pcc_octree_decode_frames(ctx, h_blobs + f, h_lens + f, 1, out, nullptr, rows[(size_t)f], offs2)
+                              : pcc_octree_decode_frames_lod(ctx, h_blobs + f, h_lens + f, 1, lod, out, nullptr, rows[(size_t)f], offs2);
       if (rc != PCC_OK) {
         const std::string m = pcc_last_error();
         pcc_set_error("%s: frame %d: %s", who, f, m.c_str());
@@ -744,34 +835,42 @@ static int o4_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const*
     for (int q = p - W; q < p; ++q) {   // the keys of the window's frames, each formed once
       if (keyed[(size_t)q] || n_at(q) == 0) continue;
       const int32_t* src = q < n_refs ? d_refs[q] : pts + 3 * h_point_offsets[q - n_refs];
-      hipLaunchKernelGGL(k_o4_keys, dim3(nblk(n_at(q), 256)), dim3(256), 0, st, src, n_at(q), keys_of(q), sums + q, status + f);
+      hipLaunchKernelGGL(k_o4_keys, dim3(nblk(n_at(q), 256)), dim3(256), 0, st, src, n_at(q), lod, keys_of(q), sums + q, status + f);
       PCC_CHECK_LAUNCH();
       keyed[(size_t)q] = 1;
     }
     const uint64_t* ref_keys = keys_of(p - 1);
     const unsigned long long* ref_sum = sums + (p - 1);
-    const int64_t rn = (int64_t)o.ref_n;
-    if (W > 1) {   // the union of the window: its size and its sum are compared on the device (status 16)
+    const uint32_t* ref_count = nullptr;
+    int64_t rn = lod == 0 ? (int64_t)o.ref_n : n_at(p - 1);
+    if (W > 1) {   // the union of the window: at lod 0 its size and its sum are compared on the device (status 16)
       O4MergeJob job;
       job.nl = W;
       job.out = merged;
+      int64_t sum = 0;
       for (int i = 0; i < W; ++i) {
         job.list[i] = keys_of(p - W + i);
         job.n[i] = n_at(p - W + i);
+        sum += job.n[i];
       }
       own.tab.emplace_back();
       uint32_t* d_count = nullptr;
       PCC_TRY(o4_merge_async(ctx, &job, 1, 0, merge_scratch, merge_b, &own.tab.back(), &d_count));
-      hipLaunchKernelGGL(k_o4_countcheck, dim3(1), dim3(1), 0, st, (const uint32_t*)d_count, o.ref_n, status + f);
-      PCC_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_o4_keysum, dim3(nblk(rn, 256)), dim3(256), 0, st, (const uint64_t*)merged, rn, 0, 32768, sums + npos + f);
-      PCC_CHECK_LAUNCH();
+      if (lod == 0) {
+        hipLaunchKernelGGL(k_o4_countcheck, dim3(1), dim3(1), 0, st, (const uint32_t*)d_count, o.ref_n, status + f);
+        PCC_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_o4_keysum, dim3(nblk(rn, 256)), dim3(256), 0, st, (const uint64_t*)merged, rn, 0, 32768, sums + npos + f);
+        PCC_CHECK_LAUNCH();
+      } else {   // the union's size stays on the device: the search reads it there, below the room the union has
+        ref_count = d_count;
+        rn = sum;
+      }
       ref_keys = merged;
       ref_sum = sums + npos + f;
     }
-    const int64_t body_b = h_lens[f] - o.off_p0;
+    const int64_t body_b = pl.bytes - o.off_p0;
     PCC_HIP(hipMemcpyAsync(d_bodies + body_at, h_blobs[f] + o.off_p0, (size_t)body_b, hipMemcpyHostToDevice, st));
-    PCC_TRY(o4_decode_one(ctx, o, d_bodies + body_at, ref_keys, rn, ref_sum, out, status + f));
+    PCC_TRY(o4_decode_one(ctx, o, pl, d_bodies + body_at, ref_keys, rn, ref_count, ref_sum, out, status + f));
     body_at += o4_round(body_b, 16);
   }
   std::vector<int32_t> h_status((size_t)nb);
@@ -779,7 +878,10 @@ static int o4_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const*
   PCC_HIP(hipStreamSynchronize(st));
   for (int f = 0; f < nb; ++f) {
     const int32_t bad = h_status[(size_t)f];
-    PCC_REQUIRE(!(bad & 32), PCC_E_ARG, "%s: frame %d: the reference is not a set of distinct int16 points in Morton order", who, f);
+    if (lod == 0)
+      PCC_REQUIRE(!(bad & 32), PCC_E_ARG, "%s: frame %d: the reference is not a set of distinct int16 points in Morton order", who, f);
+    else
+      PCC_REQUIRE(!(bad & 32), PCC_E_ARG, "%s: frame %d: the reference is not a set of distinct cells of lod %d in Morton order", who, f, lod);
     PCC_REQUIRE(!(bad & 16), PCC_E_ARG, "%s: frame %d: the reference differs from the one the blob was coded against (ref_sum)", who, f);
     PCC_REQUIRE(bad == 0, PCC_E_STREAM, "%s: frame %d: octree blob v4: corrupt stream (status %d: 1 = words, 2 = empty node, 8 = counts)",
                 who, f, bad);
@@ -801,7 +903,23 @@ extern "C" int pcc_octree_decode_frames_refs(pcc_ctx* ctx, const uint8_t* const*
   for (int r = 0; r < n_refs; ++r)
     PCC_REQUIRE(n_ref[r] >= 0 && n_ref[r] < ((int64_t)1 << 27) && (n_ref[r] == 0 || d_ref_points[r]), PCC_E_ARG,
                 "%s: bad argument (reference %d: n_ref=%lld)", who, r, (long long)n_ref[r]);
-  return o4_decode_frames(who, ctx, h_blobs, h_lens, n_frames, d_ref_points, n_ref, n_refs, d_points, h_points, cap_points,
+  return o4_decode_frames(who, ctx, h_blobs, h_lens, n_frames, d_ref_points, n_ref, n_refs, 0, d_points, h_points, cap_points,
+                          h_point_offsets);
+}
+
+// _decode_frames_refs at a level of detail: the references are CELLS at that lod (include/pcc.h has the rule)
+extern "C" int pcc_octree_decode_frames_refs_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,
+                                                 const int32_t* const* d_ref_cells, const int64_t* n_ref, int n_refs, int lod,
+                                                 int32_t* d_points, int32_t* h_points, int64_t cap_points, int64_t* h_point_offsets) {
+  const char* who = "pcc_octree_decode_frames_refs_lod";
+  PCC_REQUIRE(ctx && h_blobs && h_lens && h_point_offsets && n_frames >= 1 && n_frames <= 65535 && n_refs >= 0 &&
+                  n_refs <= kO4MaxWindow && (n_refs == 0 || (d_ref_cells && n_ref)),
+              PCC_E_ARG, "%s: bad argument (n_frames=%d n_refs=%d)", who, n_frames, n_refs);
+  PCC_REQUIRE(lod >= 0 && lod <= kO2MaxLod, PCC_E_ARG, "%s: level of detail %d outside 0 .. %d", who, lod, kO2MaxLod);
+  for (int r = 0; r < n_refs; ++r)
+    PCC_REQUIRE(n_ref[r] >= 0 && n_ref[r] < ((int64_t)1 << 27) && (n_ref[r] == 0 || d_ref_cells[r]), PCC_E_ARG,
+                "%s: bad argument (reference %d: n_ref=%lld)", who, r, (long long)n_ref[r]);
+  return o4_decode_frames(who, ctx, h_blobs, h_lens, n_frames, d_ref_cells, n_ref, n_refs, lod, d_points, h_points, cap_points,
                           h_point_offsets);
 }
 
@@ -812,8 +930,8 @@ extern "C" int pcc_octree_decode_frames_ref(pcc_ctx* ctx, const uint8_t* const* 
   PCC_REQUIRE(ctx && h_blobs && h_lens && h_point_offsets && n_frames >= 1 && n_frames <= 65535 && n_ref >= 0 &&
                   n_ref < ((int64_t)1 << 27) && (n_ref == 0 || d_ref_points),
               PCC_E_ARG, "%s: bad argument (n_frames=%d n_ref=%lld)", who, n_frames, (long long)n_ref);
-  return o4_decode_frames(who, ctx, h_blobs, h_lens, n_frames, &d_ref_points, &n_ref, n_ref > 0 ? 1 : 0, d_points, h_points, cap_points,
-                          h_point_offsets);
+  return o4_decode_frames(who, ctx, h_blobs, h_lens, n_frames, &d_ref_points, &n_ref, n_ref > 0 ? 1 : 0, 0, d_points, h_points,
+                          cap_points, h_point_offsets);
 }
 
 // host only: what the head of a geometry blob of version 2 or 4 says
@@ -830,8 +948,14 @@ extern "C" int pcc_octree_inter_info(const uint8_t* h_in, int64_t len, int* vers
     PCC_TRY(o2_parse(h_in, len, 0, true, &o, &pl));
     n = o.n;
   } else {
+    // the whole blob, or exactly the prefix that pcc_octree_lod_info names for some level of detail
     O4Info o;
-    PCC_TRY(o4_parse(h_in, len, &o));
+    O4Plan pl;
+    const int64_t blob = kO4Header + (int64_t)o4_u32(h_in + 20);
+    bool prefix = false;
+    for (int k = 1; k <= kO2MaxLod && !prefix && len < blob; ++k)
+      prefix = o4_parse_lod(h_in, len, k, true, &o, &pl) == PCC_OK && pl.bytes == len;
+    if (!prefix) PCC_TRY(o4_parse(h_in, len, &o));
     n = o.n;
     rn = (int64_t)o.ref_n;
   }

@@ -40,8 +40,16 @@ predicted frame with the sensor at rest, 10 % at 10 m/s; th
     (b,) = codec.compress([f2], predict="previous", history=2, reference=[f0, f1])     # streaming: the last K frames, oldest first
     (f2,) = codec.decompress([b], reference=[f0, f1])
 
-Not built: decoding version 4 at lod > 0 (the format allows it), choosing per frame the shorter of versions 2 and 4,
-motion compensation, prediction of attributes (they see only the decoded Morton order and are coded as before).
+Predicted frames keep their levels of detail: lod_info answers for version 4 too, and a prefix decodes against the
+CELLS of the frames in front of it (a cube above the cut is a union of whole cells), never touching the deep levels.
+
+    cut = [b[:GeometryCodec.lod_info(b, 2)[0]] for b in blobs]             # a chain I P P .., every blob cut at lod 2
+    cells = codec.decompress(cut, lod=2)                                   # what version 2's prefixes give
+    (c_t,) = codec.decompress([cut[t]], lod=2, reference=c_t_minus_1, reference_lod=2)   # streaming: the cells of before
+    (c_t,) = codec.decompress([cut[t]], lod=2, reference=pts_t_minus_1, reference_lod=0) # or lattice points
+
+Not built: choosing per frame the shorter of versions 2 and 4, motion compensation, prediction of attributes (they see
+only the decoded Morton order and are coded as before).
 
 Attributes are lossless (attribute blob version 1, csrc/attr.hip), one blob per frame beside its geometry blob; the
 values of duplicate points merge to their rounded mean per channel, (sum + cnt // 2) // cnt.
@@ -276,9 +284,9 @@ class GeometryCodec:
 
     @staticmethod
     def lod_info(blob, lod):
-        """(bytes, cells) of level of detail `lod` of a version-2 blob: blob[:bytes] is the shortest prefix that
-        decompress(..., lod=lod) reads, `cells` the rows it gives.  Host only (no GPU needed); `blob` may be a prefix
-        that reaches the last needed chunk's length table."""
+        """(bytes, cells) of level of detail `lod` of a version-2 or version-4 blob: blob[:bytes] is the shortest prefix
+        that decompress(..., lod=lod) reads, `cells` the rows it gives.  Host only (no GPU needed); `blob` may be a
+        prefix that reaches the last needed chunk's length table (lod 0 of a version-4 blob: the whole blob)."""
         return Runtime.octree_lod_info(bytes(blob), GeometryCodec._check_lod(lod))
 
     @staticmethod
@@ -679,7 +687,8 @@ class GeometryCodec:
     def geometry_info(blob):
         """what the head of a geometry blob of version 2 or 4 says: {"version", "points", "predicted",
         "reference_points"} — predicted False marks a random-access point of a sequence, a predicted blob decodes
-        only behind the frame it was coded against, whose point count is reference_points.  Host only; the blob whole."""
+        only behind the frame it was coded against, whose point count is reference_points.  Host only; the blob whole,
+        or for version 4 exactly a prefix that lod_info names."""
         return Runtime.octree_inter_info(bytes(blob))
 
     @staticmethod
@@ -816,7 +825,8 @@ class GeometryCodec:
         # a byte target: the steps from qstep upwards that the search chooses, frame by frame, through the public binding
         return rt.attr_encode_frames_rate(*call, coding.qstep, coding.colour, list(coding.targets), coding.scratch_limit)[0]
 
-    def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0, *, voxel=None, origin=(0.0, 0.0, 0.0), reference=None):
+    def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0, *, voxel=None, origin=(0.0, 0.0, 0.0), reference=None,
+                   reference_lod=None):
         """version-2 blobs -> a list of int32 [n_f, 3] point sets in Morton order: numpy arrays (output="numpy") or
         device tensors (output="device", on this codec's device).  With attr_blobs (compress(..., attributes=...)):
         (point sets, attributes), attributes[f] an [n_f, c] array in its original dtype, row i belonging to point i; an
@@ -842,8 +852,16 @@ class GeometryCodec:
         on this codec's device, in any row order and with duplicates: the decoded frame before it; or, for blobs of
         compress(..., history=K), a list or tuple of the up to 8 frames decoded before it, oldest first — a blob says
         itself (reference_frames) how many of the frames in front of it its reference is the union of.  Without the
-        reference, or with another one than the sender's, PccError names the frame.  Version 4 decodes at lod 0: at
-        lod > 0 ValueError names the frame.  A call without a version-4 blob is the call of before."""
+        reference, or with another one than the sender's, PccError names the frame.
+        Version 4 at lod = k > 0: blobs or their lod_info prefixes, chains, intra_period mixes and history windows as at
+        lod 0, to the same cells as version 2's; scalable attribute blobs decode beside them.  A predicted frame is then
+        decoded against the CELLS of the frames in front of it, so `reference` needs reference_lod to say what its rows
+        are: reference_lod=k, the cells that the decompress(..., lod=k) before returned (a receiver that never held
+        full resolution), or reference_lod=0, lattice points, whose cells the codec forms on the device.  Without it
+        ValueError names the first version-4 frame; any other value is a ValueError.  A cut cannot verify the
+        reference (the blob's count and sum describe full-resolution points): a wrong one is a PccError where the
+        stream's counts do not add up and otherwise rows of wrong cells.  A call without a version-4 blob is the call
+        of before."""
         if isinstance(attr_blobs, str):      # decompress(blobs, "device"), as before attributes
             attr_blobs, output = None, attr_blobs
         if output not in ("numpy", "device"):
@@ -868,9 +886,17 @@ class GeometryCodec:
             if ref_float:
                 raise TypeError("reference: expected the int16 / int32 lattice frame that was decoded before blob 0, got float32")
         predicted = [f for f, b in enumerate(blobs) if len(b) > 1 and b[1] == 4]
-        if predicted and lod:
-            raise ValueError(f"frame {predicted[0]}: blob version 4 (a predicted frame) decodes at lod 0 only; lod {lod} needs "
-                             "the sender's compress(..., lod=k, predict='previous')")
+        if reference_lod is not None:
+            if (not isinstance(reference_lod, (int, np.integer)) or isinstance(reference_lod, bool) or reference is None
+                    or int(reference_lod) not in (0, lod)):
+                raise ValueError(f"reference_lod says what the rows of reference= are at lod {lod}: {lod} (the cells of a "
+                                 f"decompress at that lod) or 0 (lattice points), got {reference_lod!r}"
+                                 + ("" if reference is not None else " without a reference"))
+            reference_lod = int(reference_lod)
+        elif predicted and lod and reference is not None:
+            raise ValueError(f"frame {predicted[0]}: blob version 4 (a predicted frame) at lod {lod}: the rows of reference= may be "
+                             f"cells or lattice points; say which with reference_lod={lod} (the cells that "
+                             f"decompress(..., lod={lod}) returned) or reference_lod=0 (lod 0 lattice points)")
         if attr_blobs is not None:
             attr_blobs = [bytes(b) for b in attr_blobs]
             if len(attr_blobs) != len(blobs):
@@ -896,7 +922,23 @@ class GeometryCodec:
                                  "coarse attributes with compress(frames, attributes=..., lod=k)")
         caller = torch.cuda.current_stream(self.rt.device) if (predicted and ref_device) else None
         with self._lock, self.rt as rt:
-            if predicted:      # the new entry point, and the reference as a decode returns it: distinct, Morton order
+            if predicted and lod:      # at a cut: the references are cells, given or formed here from lattice points
+                refs = []
+                if reference is not None:
+                    frames_in = list(reference) if several else [reference]
+                    front = self._front(rt, frames_in, False, ref_device, caller, "GeometryCodec.decompress (reference)",
+                                        lod if reference_lod == 0 else 0)
+                    refs = [torch.empty((0, 3), dtype=torch.int32, device=rt.device)] * len(frames_in)
+                    if front.n_keep:      # distinct and in Morton order, split by the frame index of the keys
+                        coords = rt.keys_to_coords(front.keys)
+                        ends = torch.searchsorted(coords[:, 0].contiguous(), torch.arange(len(frames_in) + 1, device=rt.device,
+                                                                                          dtype=coords.dtype)).tolist()
+                        shift = lod if reference_lod == 0 else 0      # a masked key's coordinates are the cell's corner
+                        refs = [(coords[a:b, 1:] >> shift).contiguous() for a, b in zip(ends[:-1], ends[1:])]
+                    if not several and not refs[0].shape[0]:
+                        refs = []
+                decode = lambda blobs, device, lod, whole=False: rt.octree_decode_frames_refs_lod(blobs, refs, lod, device=device, whole=whole)   # noqa: E731
+            elif predicted:      # the new entry point, and the reference as a decode returns it: distinct, Morton order
                 ref = None
                 if several:      # each as a decode returns it; one front end for all, split by the frame index of the keys
                     front = self._front(rt, reference, False, ref_device, caller, "GeometryCodec.decompress (reference)")

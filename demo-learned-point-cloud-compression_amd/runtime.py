@@ -665,9 +665,9 @@ class Runtime:
 
     @staticmethod
     def octree_lod_info(blob, lod):
-        """(bytes, cells) of level of detail `lod` (0 .. 15) of a version-2 blob (pcc_octree_lod_info, host only): the
-        shortest prefix of the blob that decodes at that level, and the cells it gives.  `blob` may itself be a prefix
-        that reaches the last needed chunk's length table."""
+        """(bytes, cells) of level of detail `lod` (0 .. 15) of a version-2 or version-4 blob (pcc_octree_lod_info, host
+        only): the shortest prefix of the blob that decodes at that level, and the cells it gives.  `blob` may itself be
+        a prefix that reaches the last needed chunk's length table."""
         buf = np.frombuffer(blob, dtype=np.uint8)
         nbytes, cells = C.c_int64(0), C.c_int64(0)
         check(_abi.lib().pcc_octree_lod_info(_np_ptr(buf) if buf.shape[0] else None, buf.shape[0], int(lod),
@@ -762,6 +762,25 @@ class Runtime:
         views = [pts[offs[f]:offs[f + 1]] for f in range(nb)]
         return (views, pts) if whole else views
 
+    def octree_decode_frames_refs_lod(self, blobs, references=(), lod=0, device=False, whole=False):
+        """octree_decode_frames_refs at a level of detail (pcc_octree_decode_frames_refs_lod): blobs of versions 2 and 4
+        or prefixes of them (octree_lod_info) -> the cells points >> lod of every frame.  lod > 0: the references are
+        CELLS at that lod, int32 [n, 3] device tensors, distinct and in Morton order, as this call returns them."""
+        nb = len(blobs)
+        if nb == 0:
+            return ([], None) if whole else []
+        bufs = [np.frombuffer(b, dtype=np.uint8) for b in blobs]
+        ptrs = (C.c_void_p * nb)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
+        lens = (C.c_int64 * nb)(*[b.shape[0] for b in bufs])
+        offs = (C.c_int64 * (nb + 1))()
+        nr = len(references)
+        ref_ptrs = (C.c_void_p * max(nr, 1))(*[_ptr(r) if r.shape[0] else None for r in references])
+        ref_n = (C.c_int64 * max(nr, 1))(*[int(r.shape[0]) for r in references])
+        call = lambda *a: self.lib.pcc_octree_decode_frames_refs_lod(self.ctx, ptrs, lens, nb, ref_ptrs, ref_n, nr, int(lod), *a, offs)
+        pts = self._sized_output(call, "pcc_octree_decode_frames_refs_lod", offs, lambda total: (total, 3), torch.int32, device)
+        views = [pts[offs[f]:offs[f + 1]] for f in range(nb)]
+        return (views, pts) if whole else views
+
     def merge_keys(self, lists, key_shift=0):
         """the union of 1 .. 8 lists of Morton keys (pcc_merge_keys): int64 device tensors, each strictly increasing
         under (key & (2^48 - 1)) >> key_shift -> one int64 device tensor, strictly increasing under the same comparison;
@@ -777,8 +796,9 @@ class Runtime:
 
     @staticmethod
     def octree_inter_info(blob):
-        """what the head of a geometry blob of version 2 or 4 says (pcc_octree_inter_info, host only; the blob whole):
-        {"version", "points", "predicted", "reference_points"}"""
+        """what the head of a geometry blob of version 2 or 4 says (pcc_octree_inter_info, host only; the blob whole, or
+        for version 4 exactly a prefix that octree_lod_info names): {"version", "points", "predicted",
+        "reference_points"}"""
         buf = np.frombuffer(blob, dtype=np.uint8)
         version, predicted = C.c_int(0), C.c_int(0)
         points, ref_points = C.c_int64(0), C.c_int64(0)

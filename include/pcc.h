@@ -716,7 +716,9 @@ int pcc_octree_decode_frames(pcc_ctx* ctx, const uint8_t* const* h_blobs,
  *     level `lod` needs and gives.  h_in may be the blob or any prefix long
  *     enough to answer (it must reach the last needed chunk's length table);
  *     a shorter one, or a damaged header: PCC_E_STREAM; another blob version
- *     or lod outside 0 .. 15: PCC_E_ARG.
+ *     or lod outside 0 .. 15: PCC_E_ARG.  A version-4 blob (below) answers
+ *     with the same formulas over its own offsets; its lod 0 is the whole
+ *     blob and wants the whole blob.
  *   _decode_frames_lod : pcc_octree_decode_frames at a level of detail: blobs
  *     or prefixes of them, every frame at the same lod (outside 0 .. 15:
  *     PCC_E_ARG); pcc_octree_decode_frames is its lod = 0 call.  A prefix even
@@ -765,10 +767,24 @@ int pcc_octree_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs,
  *   level's launch of the decoder lasts up to 8 S dependent steps of a wave;
  *   a decoder takes S from the header, any multiple of 4 in 4 .. 512.
  * A frame without points stays the 24-byte version-2 blob; a frame whose
- *   reference has no points is written as version 2.  The levels above a cut
- *   are still a prefix of the bytes; decoding version 4 at lod > 0 is not
- *   built (the format allows it: a reference byte above the cut needs only the
- *   reference's cells at that lod).
+ *   reference has no points is written as version 2.
+ * Levels of detail: the levels above a cut are a prefix of the bytes, as in
+ *   version 2: cut level, cells m, nodes needed N' and the shortest prefix are
+ *   the formulas above with off_payload = 24 + 4 depth + 20 + 648 + 4 nc
+ *   (pcc_octree_lod_info answers for both versions).  A node above the cut at
+ *   lod k has child cubes of side >= 2^k; the root corner is a multiple of
+ *   2^depth in biased coordinates and 32768 a multiple of 2^k, so every such
+ *   cube is a union of whole lod-k cells and "R has a point in the cube" is
+ *   "R has a cell in the cube": the prefix decodes against the reference's
+ *   CELLS at lod k alone (a cell c is searched as the point c << k), to the
+ *   cells p >> k of the frame in Morton order.  k >= depth: nothing is
+ *   decoded, the one cell is origin >> k.  What a cut cannot verify: ref_n
+ *   and ref_sum describe full-resolution points, which a decoder that holds
+ *   cells cannot form; at lod > 0 they are not compared.  A wrong reference at
+ *   a cut is PCC_E_STREAM where the counts do not add up (a lane's words, an
+ *   empty node, the children of a level) and otherwise m rows of wrong cells;
+ *   it is never a store outside an array: every bound comes from the header's
+ *   checks, the prefix's length and the rows at hand.
  *   _encode_frames_inter : pcc_octree_encode_frames whose frames are coded
  *     against the frame in front of them in the call.  intra_period = G >= 1:
  *     the coded frames g with g % G == 0 are version 2; 0: only the first
@@ -790,7 +806,8 @@ int pcc_octree_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs,
  *     pcc_octree_decode_frames'.
  *   _inter_info : host only, versions 2 and 4: version, points, predicted
  *     (0 / 1) and ref_points (0 for version 2), each nullable; the blob must
- *     be whole.
+ *     be whole, or for version 4 exactly the prefix that pcc_octree_lod_info
+ *     names for some lod.
  * The window (history = K, 1 <= K <= 8): R may be the union of several frames.
  *   Every frame of a call has a position: the leading reference frames first,
  *   then the coded frames; reference frames get no blob.  A predicted frame t
@@ -824,6 +841,21 @@ int pcc_octree_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs,
  *     ref_sum.  A window that reaches in front of the first frame at hand:
  *     PCC_E_ARG "needs W frames in front of it, n are here".
  *     _decode_frames_ref is its form with at most one reference.
+ *   _decode_frames_refs_lod : _decode_frames_refs at a level of detail (lod
+ *     outside 0 .. 15: PCC_E_ARG; 0 is _decode_frames_refs itself, launch for
+ *     launch).  lod > 0: blobs of versions 2 and 4 or prefixes of them, and
+ *     d_ref_cells[r] are CELLS at that lod: int32 [n_ref,3], each in
+ *     [-(32768 >> lod), (32768 >> lod) - 1], distinct, in Morton order, as
+ *     this call or _decode_frames_lod returns them (anything else: PCC_E_ARG
+ *     naming the frame).  The result is every frame's cells; a version-2 blob
+ *     of the call goes through _decode_frames_lod.  Levels 0 .. Lc-1 alone are
+ *     decoded, arrays are sized from N' and m, only the prefix is uploaded and
+ *     the decoder reads no word behind it; the children of level Lc-1 must
+ *     number level_n[Lc] (PCC_E_STREAM).  A prefix even two bytes short is
+ *     PCC_E_STREAM ("truncated") naming the frame, before anything is
+ *     reserved or launched.  ref_n and ref_sum are not compared (above); a
+ *     window's union is formed from the cells' keys and its size stays on the
+ *     device.
  *   pcc_merge_keys : the union of 1 .. 8 lists of keys on the device, each
  *     strictly increasing under (key & (2^48 - 1)) >> key_shift (bits from 48
  *     up, the frame index of a call's keys, are carried along and not
@@ -834,8 +866,8 @@ int pcc_octree_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs,
  *     one scan of the keep flags, a scatter to computed places — no atomics,
  *     the same output on every run.  *h_count = the union's size (one
  *     synchronisation).
- * pcc_octree_decode_frames, _decode_frames_lod, _lod_info, _blob_version and
- * the one-blob entries go on refusing version 4. */
+ * pcc_octree_decode_frames, _decode_frames_lod, _blob_version and the one-blob
+ * entries go on refusing version 4. */
 int pcc_octree_encode_frames_inter(pcc_ctx* ctx, const uint64_t* d_keys,
                                    int64_t n, int n_frames, int key_shift,
                                    int intra_period, int ref_first,
@@ -860,6 +892,14 @@ int pcc_octree_decode_frames_refs(pcc_ctx* ctx, const uint8_t* const* h_blobs,
                                   int32_t* d_points, int32_t* h_points,
                                   int64_t cap_points,
                                   int64_t* h_point_offsets);
+int pcc_octree_decode_frames_refs_lod(pcc_ctx* ctx,
+                                      const uint8_t* const* h_blobs,
+                                      const int64_t* h_lens, int n_frames,
+                                      const int32_t* const* d_ref_cells,
+                                      const int64_t* n_ref, int n_refs,
+                                      int lod, int32_t* d_points,
+                                      int32_t* h_points, int64_t cap_points,
+                                      int64_t* h_point_offsets);
 int pcc_merge_keys(pcc_ctx* ctx, const uint64_t* const* d_lists,
                    const int64_t* h_n, int n_lists, int key_shift,
                    uint64_t* d_out, int64_t cap, int64_t* h_count);

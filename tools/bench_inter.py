@@ -11,7 +11,13 @@ decoder takes S from the header).  PROFILE=1 adds the device time of the calls. 
 per predicted frame and encode and decode milliseconds per frame (history 1 through the entries of before), one JSON
 line per velocity, also written to profiles/geometry_history.json (--out: elsewhere).  PROFILE=1 adds the device time
 of one encode and one decode call at the largest window.  --calls N: only N encode and N decode calls at a window of K
-itself, sensor at rest (for a rocprofv3 --kernel-trace --stats run of its own)."""
+itself, sensor at rest (for a rocprofv3 --kernel-trace --stats run of its own).
+
+--lod k (or a list, 0,1,2,3): predicted frames at a level of detail — the ten blobs of compress(..., predict="previous")
+(with --history K: windows of up to K frames, K itself, not 1 .. K) cut to their lod_info prefixes and decoded in one
+call to every frame's cells, checked against np.unique(frame >> k): decode milliseconds per frame, prefix bytes and
+cells per frame, beside version 2's prefixes of the same frames.  lod 0 goes through the entries of before.  One JSON
+line per velocity and lod, also appended to profiles/geometry_inter_lod.json (--out: elsewhere)."""
 import argparse
 import importlib
 import json
@@ -89,20 +95,63 @@ def history(rt, wl, k_max, reps, n_frames, out):
         f.write("\n".join(lines) + "\n")
 
 
+def lod(rt, wl, lods, k_hist, reps, n_frames, out):
+    with open(out, "a") as sink:
+        for velocity in ((0, 0, 0), (10, 0, 0)):
+            frames = [f["points"].astype(np.int32) for f in wl.lidar_sequence(n_frames, 64, 1800, velocity=velocity)]
+            coords = np.concatenate([np.concatenate([np.full((p.shape[0], 1), f, np.int32), p], 1) for f, p in enumerate(frames)])
+            keys = rt.morton_keys(rt.to_device(coords))
+            rt.sort_pairs(keys)
+            b2 = rt.octree_encode_frames(keys, n_frames)
+            b4 = rt.octree_encode_frames_inter(keys, n_frames) if k_hist == 1 else rt.octree_encode_frames_inter_hist(keys, n_frames, history=k_hist)
+            for k in lods:
+                cut2 = [b[:rt.octree_lod_info(b, k)[0]] for b in b2]
+                cut4 = [b[:rt.octree_lod_info(b, k)[0]] for b in b4]
+                if k == 0:
+                    decode4 = rt.octree_decode_frames_ref if k_hist == 1 else rt.octree_decode_frames_refs
+                else:
+                    decode4 = lambda blobs: rt.octree_decode_frames_refs_lod(blobs, (), k)      # noqa: E731
+                dec2, want = timed(lambda: rt.octree_decode_frames(cut2, lod=k), reps)
+                dec4, got = timed(lambda: decode4(cut4), reps)
+                assert all(np.array_equal(a, b) for a, b in zip(got, want))
+                assert all(len(a) == len(np.unique(f >> k, axis=0)) for a, f in zip(got, frames))
+                res = {"velocity": velocity, "frames": n_frames, "history": k_hist, "lod": k,
+                       "cells_per_frame": sum(len(a) for a in got) / n_frames,
+                       "v2": {"prefix_bytes_per_frame": sum(map(len, cut2)) / n_frames, "decode_ms_per_frame": dec2 / n_frames},
+                       "v4": {"prefix_bytes_per_frame": sum(map(len, cut4)) / n_frames,
+                              "prefix_bytes_per_predicted_frame": sum(map(len, cut4[1:])) / (n_frames - 1),
+                              "blob_bytes_per_predicted_frame": sum(map(len, b4[1:])) / (n_frames - 1),
+                              "decode_ms_per_frame": dec4 / n_frames}}
+                line = json.dumps(res)
+                print(line, flush=True)
+                sink.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--lod", default="", metavar="k", help="measure predicted frames cut at lod k (0 .. 15, or a list: 0,1,2,3)")
     ap.add_argument("--history", type=int, default=0, metavar="K", help="measure windows of 1 .. K frames (1 .. 8)")
     ap.add_argument("--calls", type=int, default=0, metavar="N", help="with --history: N encode and decode calls at K alone")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "geometry_history.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/geometry_history.json, with --lod profiles/geometry_inter_lod.json")
     args = ap.parse_args()
     if not 0 <= args.history <= 8:
         ap.error("--history takes 1 .. 8")
+    lods = [int(k) for k in args.lod.split(",") if k]
+    if any(not 0 <= k <= 15 for k in lods):
+        ap.error("--lod takes 0 .. 15")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "geometry_inter_lod.json" if lods else "geometry_history.json")
     importlib.import_module(PKG)
     wl = importlib.import_module(PKG + ".workloads")
     rtm = importlib.import_module(PKG + ".runtime")
     rt = rtm.Runtime(0)
     reps = int(os.environ.get("REPS", "10"))
     n_frames = int(os.environ.get("FRAMES", "10"))
+    if lods:
+        with rt:
+            lod(rt, wl, lods, max(args.history, 1), reps, n_frames, args.out)
+        rt.close()
+        return
     if args.history:
         with rt:
             if args.calls:
