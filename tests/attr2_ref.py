@@ -5,10 +5,14 @@ version 1's (fixed slots with a validity mask, all lanes stepped side by side). 
 
     encode(points, values, bpv, bias=32768) -> blob     points int [n, 3] distinct (any order), values int [n] / [n, c]
                                                         row i belonging to points[i]; bias 32768 >> k: the points
-                                                        are the cells of a sender's side lod k
+                                                        are the cells of a sender's side lod k; layout=(S, n_chunks)
+                                                        and p0= as attr_ref.encode takes them
     decode(blob_or_prefix, cells, lod)      -> (values int64 [m, c], bpv): cells int [m, 3] = the distinct points >> lod
                                                (any order); row j belongs to the j-th cell in Morton order
     lod_info(blob_or_prefix, lod)           -> (bytes, values)
+    status(blob_or_prefix, m)               -> the lane decoder's status word for the first m values (attr_ref.status)
+decode, lod_info and status take any_layout=True: (S, n_chunks) may be any the parser accepts (attr_ref.check_layout);
+without it they insist on the encoder's layout(n, c).
     intro(keys)                             -> (s, order, first) of Morton-sorted distinct keys
     keys_of(points, bias)                   -> 48-bit Morton keys (x bits at 3i + 2, y at 3i + 1, z at 3i)
 """
@@ -16,7 +20,8 @@ import struct
 
 import numpy as np
 
-from attr_ref import BUCKETS, HEAD, L, LANES, _adapt, _as2d, _bucket, _p0, _slots, contexts, layout, positions
+from attr_ref import (BUCKETS, HEAD, L, LANES, _adapt, _as2d, _bucket, _p0, _slots, check_layout, contexts, layout, pick_layout, pick_p0,
+                      positions)
 
 HEAD2 = HEAD + 64 + 8          # 'A' 2 bpv c | n | payload_len | cells[16] | S | n_chunks
 
@@ -51,8 +56,8 @@ def intro(keys):
     return s, order, first
 
 
-def _runs(r, n, c):
-    S, nc = layout(n, c)
+def _runs(r, n, c, given=None):
+    S, nc = pick_layout(n, c, given)
     R = nc * LANES
     runs = np.zeros((R * S, c), np.int64)
     runs[:n] = r
@@ -63,7 +68,7 @@ def _runs(r, n, c):
     return S, nc, runs, bk, valid
 
 
-def encode(points, values, bpv, bias=32768):
+def encode(points, values, bpv, bias=32768, layout=None, p0=None):
     v = _as2d(values)
     n, c = v.shape
     slod = 15 - int(bias).bit_length() + 1
@@ -80,7 +85,7 @@ def encode(points, values, bpv, bias=32768):
     pred[0] = 0
     r = (((v - pred + half) & mask) - half)[order]                     # residuals in introduction order
     cells = [int((s >= k).sum()) for k in range(16)]
-    S, nc, runs, bk, valid = _runs(r, n, c)
+    S, nc, runs, bk, valid = _runs(r, n, c, layout)
     R = nc * LANES
     nctx = contexts(bpv, c)
     c0 = np.zeros(nctx, np.int64)
@@ -94,7 +99,7 @@ def encode(points, values, bpv, bias=32768):
         o = np.argsort(~ok, axis=1, kind="stable")
         K = ok.sum(1)
         per.append((np.take_along_axis(ctx, o, 1)[:, :K.max()], np.take_along_axis(bit, o, 1)[:, :K.max()], K))
-    p0 = _p0(c0, c1)
+    p0 = pick_p0(_p0(c0, c1), p0)
     T = max(p[0].shape[1] for p in per)
     cx = np.zeros((R, T), np.int64)
     bt = np.zeros((R, T), np.int64)
@@ -135,7 +140,7 @@ def encode(points, values, bpv, bias=32768):
     return head + struct.pack("<I", len(body)) + body
 
 
-def _header(blob):
+def _header(blob, any_layout=False):
     assert len(blob) >= HEAD and blob[0] == ord("A") and blob[1] == 2, "not an attribute blob of version 2"
     bpv, slod, c = blob[2] & 15, blob[2] >> 4, blob[3]
     assert bpv in (1, 2) and 1 <= c <= 4
@@ -147,7 +152,10 @@ def _header(blob):
     cells = struct.unpack_from("<16I", blob, HEAD)
     S, nc = struct.unpack_from("<II", blob, HEAD + 64)
     assert cells[0] == n and all(b <= a and 8 * b >= a for a, b in zip(cells, cells[1:])) and cells[15] >= 1
-    assert (S, nc) == layout(n, c)
+    if any_layout:
+        check_layout(n, c, S, nc)
+    else:
+        assert (S, nc) == layout(n, c)
     off_table = HEAD2 + 2 * contexts(bpv, c)
     assert len(blob) >= off_table + 4 * nc, "truncated chunk table"
     words = struct.unpack_from("<%dI" % nc, blob, off_table)
@@ -155,11 +163,11 @@ def _header(blob):
     return bpv, c, n, (cells, S, nc, words, off_table + 4 * nc, slod)
 
 
-def lod_info(blob, lod):
+def lod_info(blob, lod, any_layout=False):
     """(bytes, values): blob[:bytes] is the shortest prefix that decodes at `lod`; `blob` may be a prefix that reaches
     the last needed chunk's length table"""
     assert 0 <= lod <= 15
-    bpv, c, n, h = _header(blob)
+    bpv, c, n, h = _header(blob, any_layout)
     if n == 0:
         return HEAD, 0
     cells, S, nc, words, off_payload, _ = h
@@ -176,15 +184,32 @@ def lod_info(blob, lod):
     return start + 2 * run, m
 
 
-def _residuals(blob, m):
+def _residuals(blob, m, any_layout=False):
     """the first m residuals [m, c] of the introduction sequence from the bytes lod_info names"""
-    bpv, c, n, (cells, S, nc, words, at, _) = _header(blob)
+    out, bpv, bad = _lanes(blob, m, any_layout, True, False)
+    assert bad == 0
+    return out, bpv
+
+
+def status(blob, m, any_layout=False, whole=None):
+    """the status word the lane decoder leaves for the first m values of this frame, bits as attr_ref.status states
+    them; a lane whose run the level cuts short is exempt from the checks at its end.  whole: the last needed chunk is
+    there with all its words, as at lod 0 (the default when m is every value of the blob), not only up to the last
+    needed lane's run"""
+    n = struct.unpack_from("<I", blob, 4)[0]
+    return _lanes(blob, m, any_layout, False, m == n if whole is None else whole)[2]
+
+
+def _lanes(blob, m, any_layout, strict, whole_last):
+    """-> (residuals, bpv, status); strict: a stream that would set a status bit stops at an assert instead"""
+    bpv, c, n, (cells, S, nc, words, at, _) = _header(blob, any_layout)
     nctx, P, kmax = contexts(bpv, c), positions(bpv), 8 * bpv - 1
     p0 = np.array(struct.unpack_from("<%dH" % nctx, blob, HEAD2), np.int64)
     assert ((p0 >= 16) & (p0 <= 4080)).all()
     lanes_needed = -(-m // S)
     out = np.zeros((nc * LANES * S, c), np.int64)
     lanes = np.arange(LANES)
+    bad = 0
     for k in range(-(-lanes_needed // LANES)):
         full = np.clip(n - (k * LANES + lanes) * S, 0, S)                # the lane's run in the whole blob
         npts = np.clip(m - (k * LANES + lanes) * S, 0, S)                # what this level takes of it
@@ -193,8 +218,14 @@ def _residuals(blob, m):
         hw = np.frombuffer(blob, "<u2", 192, at).astype(np.int64)
         x = hw[0:128:2] | (hw[1:128:2] << 16)
         ln = hw[128:192]
-        assert 192 + ln.sum() == words[k]
+        assert not strict or 192 + ln.sum() == words[k]
         have = 192 + int(ln[:last + 1].sum())
+        if whole_last or k + 1 < -(-lanes_needed // LANES):
+            have = words[k]
+        if 192 + ln.sum() != words[k]:
+            bad |= 1
+            at += 2 * words[k]
+            continue
         assert len(blob) >= at + 2 * have, "truncated"
         w = np.frombuffer(blob, "<u2", have, at).astype(np.int64)
         at += 2 * words[k]
@@ -214,7 +245,8 @@ def _residuals(blob, m):
             x = np.where(act, freq * (x >> 12) + cum - np.where(bit == 1, 4096 - p1, 0), x)
             model[lanes[act], ctx[act]] = _adapt(p1, bit)[act]
             need = act & (x < L)
-            assert not (need & (pos >= end)).any(), "a lane ran out of words"
+            assert not strict or not (need & (pos >= end)).any(), "a lane ran out of words"
+            bad |= 1 if (need & (pos >= end)).any() else 0
             x = np.where(need, (x << 16) | w[np.minimum(pos, have - 1)], x)
             pos += need
             ph0, ph1, ph2, ph3 = phase == 0, phase == 1, phase == 2, phase == 3
@@ -236,20 +268,21 @@ def _residuals(blob, m):
             s = np.where(fin & (chn == c), s + 1, s)
             chn = np.where(chn == c, 0, chn)
         whole = npts == full                                             # lanes whose run this level takes entirely
-        assert (pos == end)[whole].all() and (x == L)[whole].all(), "corrupt chunk"
-    return out[:m], bpv
+        assert not strict or ((pos == end)[whole].all() and (x == L)[whole].all()), "corrupt chunk"
+        bad |= (0 if (pos == end)[whole].all() else 1) | (0 if (x == L)[whole].all() else 4)
+    return out[:m], bpv, bad
 
 
-def decode(blob, cells, lod=0):
+def decode(blob, cells, lod=0, any_layout=False):
     cells = np.asarray(cells, np.int64).reshape(-1, 3)
-    bpv, c, n, h = _header(blob)
+    bpv, c, n, h = _header(blob, any_layout)
     m = cells.shape[0]
     if n == 0:
         assert m == 0
         return np.zeros((0, c), np.int64), bpv
     assert m == h[0][lod], "the blob has %d values at lod %d, the geometry %d cells" % (h[0][lod], lod, m)
-    assert len(blob) >= lod_info(blob, lod)[0], "truncated"
-    r, _ = _residuals(blob, m)
+    assert len(blob) >= lod_info(blob, lod, any_layout)[0], "truncated"
+    r, _ = _residuals(blob, m, any_layout)
     assert h[5] + lod <= 15
     keys = np.sort(keys_of(cells, 32768 >> (h[5] + lod)))
     s, order, first = intro(keys)

@@ -17,6 +17,7 @@ port of the kernels.
     lod_info(blob_or_prefix, lod)                           -> (bytes, values) of a version 11 / 14 (or 2 / 7) blob
     info(blob)                                              -> attr_nl_ref.info's dict, for a cross kind with its own
                                                                version and cross_channel, a tuple of channel indices
+encode takes layout=(S, n_chunks) and p0=, decode and lod_info any_layout=True, as attr_nl_ref's do.
 """
 import struct
 
@@ -25,7 +26,7 @@ import numpy as np
 import attr2_ref
 import attr_nl_ref
 import attr_ref
-from attr_ref import HEAD, LANES, _as2d, layout
+from attr_ref import HEAD, LANES, _as2d, pick_layout
 
 CROSS_OF = {1: 8, 2: 11, 4: 13, 7: 14}
 PLAIN_OF = {v: k for k, v in CROSS_OF.items()}
@@ -67,19 +68,19 @@ def inverse(x, m, bpv):
     return w
 
 
-def _runs(a, n, c):
-    S, nc = layout(n, c)
+def _runs(a, n, c, given=None):
+    S, nc = pick_layout(n, c, given)
     runs = np.zeros((nc * LANES * S, c), np.int64)
     runs[:n] = a
     return runs.reshape(nc * LANES, S, c)
 
 
-def encode(values, bpv, cross, e=0, points=None, bias=32768):
+def encode(values, bpv, cross, e=0, points=None, bias=32768, layout=None, p0=None):
     v = _as2d(values)
     n, c = v.shape
     m = mask_of(cross, c)
     if m == 0:
-        return attr_nl_ref.encode(v, bpv, e, points, bias)
+        return attr_nl_ref.encode(v, bpv, e, points, bias, layout, p0)
     scal, nl = points is not None, e > 0
     if nl:
         attr_nl_ref._check_e(e, bpv)
@@ -92,7 +93,7 @@ def encode(values, bpv, cross, e=0, points=None, bias=32768):
         return head + struct.pack("<I", 0)
     body = struct.pack("<I", e) if nl else b""
     if not scal:                                                            # the lane runs of the Morton order
-        w = attr_nl_ref.indices4(v, e)[0] if nl else attr_ref._resid(_runs(v, n, c), bpv)[0].reshape(-1, c)[:n]
+        w = attr_nl_ref.indices4(v, e, layout)[0] if nl else attr_ref._resid(_runs(v, n, c, layout), bpv)[0].reshape(-1, c)[:n]
     else:                                                                   # the introduction order
         keys = attr2_ref.keys_of(points, bias)
         srt = np.argsort(keys, kind="stable")
@@ -105,7 +106,7 @@ def encode(values, bpv, cross, e=0, points=None, bias=32768):
             pred[0] = 0
             w = _wrap(v - pred, bpv)[order]
         body += struct.pack("<16I", *[int((s >= k).sum()) for k in range(16)])
-    body += attr_nl_ref._code(forward(w, m, bpv), bpv)
+    body += attr_nl_ref._code(forward(w, m, bpv), bpv, layout, p0)
     return head + struct.pack("<I", len(body)) + body
 
 
@@ -128,16 +129,16 @@ def info(blob):
     return i
 
 
-def lod_info(blob, lod):
+def lod_info(blob, lod, any_layout=False):
     if blob[1] not in PLAIN_OF:
-        return attr_nl_ref.lod_info(blob, lod)
+        return attr_nl_ref.lod_info(blob, lod, any_layout)
     assert blob[1] in (11, 14)
-    return attr_nl_ref.lod_info(_plain_head(blob)[0], lod)
+    return attr_nl_ref.lod_info(_plain_head(blob)[0], lod, any_layout)
 
 
-def decode(blob, cells=None, lod=0):
+def decode(blob, cells=None, lod=0, any_layout=False):
     if blob[1] not in PLAIN_OF:
-        return attr_nl_ref.decode(blob, cells, lod)
+        return attr_nl_ref.decode(blob, cells, lod, any_layout)
     i = info(blob)
     m = _plain_head(blob)[1]
     bpv, c, n, e = i["bpv"], i["channels"], i["points"], i["max_error"]
@@ -156,7 +157,8 @@ def decode(blob, cells=None, lod=0):
         for _ in range(15):
             counts.append(max(1, -(-counts[-1] // 8)))
         b2 = bytes([blob[0], 2, bpv, c]) + blob[4:8] + struct.pack("<I", plen - x4 + 64) + struct.pack("<16I", *counts) + body
-        w = _runs(inverse(attr2_ref._residuals(b2, n)[0], m, bpv), n, c)
+        x = attr2_ref._residuals(b2, n, any_layout)[0]
+        w = _runs(inverse(x, m, bpv), n, c, struct.unpack_from("<II", blob, HEAD + x4))   # the header's: checked by the reader
         vh = np.zeros_like(w)
         for s in range(w.shape[1]):                                         # all runs side by side
             p = 0 if s == 0 else (vh[:, 0] if s == 1 else (vh[:, s - 1] + vh[:, s - 2] + 1) >> 1)
@@ -165,11 +167,11 @@ def decode(blob, cells=None, lod=0):
     else:
         cells = np.asarray(cells, np.int64).reshape(-1, 3)
         b2 = bytes([blob[0], 2, blob[2], c]) + blob[4:8] + struct.pack("<I", plen - x4) + body
-        _, _, _, h = attr2_ref._header(b2)
+        _, _, _, h = attr2_ref._header(b2, any_layout)
         k = cells.shape[0]
         assert k == h[0][lod], "the blob has %d values at lod %d, the geometry %d cells" % (h[0][lod], lod, k)
-        assert len(b2) >= attr2_ref.lod_info(b2, lod)[0], "truncated"
-        x = attr2_ref._residuals(b2, k)[0]
+        assert len(b2) >= attr2_ref.lod_info(b2, lod, any_layout)[0], "truncated"
+        x = attr2_ref._residuals(b2, k, any_layout)[0]
         assert h[5] + lod <= 15
         keys = np.sort(attr2_ref.keys_of(cells, 32768 >> (h[5] + lod)))
         s, order, first = attr2_ref.intro(keys)

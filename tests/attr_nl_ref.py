@@ -16,6 +16,8 @@ decoder here strips that word and reads the indices with attr2_ref's reader.  No
                                                         through to attr_ref / attr2_ref
     lod_info(blob_or_prefix, lod)                    -> (bytes, values) of a version 7 (or 2) blob
     info(blob)                                       -> dict(version, bpv, channels, points, max_error, scalable, lod)
+encode takes layout=(S, n_chunks) and p0= as attr_ref.encode does (version 4's closed loop runs over the lanes of that
+layout); decode and lod_info take any_layout=True as attr2_ref's do, without it they insist on the encoder's layout.
 """
 import struct
 
@@ -23,7 +25,7 @@ import numpy as np
 
 import attr2_ref
 import attr_ref
-from attr_ref import HEAD, L, LANES, _adapt, _as2d, _bucket, _p0, _slots, contexts, layout
+from attr_ref import HEAD, L, LANES, _adapt, _as2d, _bucket, _p0, _slots, contexts, pick_layout, pick_p0
 
 
 def quantise(d, e):
@@ -35,11 +37,11 @@ def _check_e(e, bpv):
     assert isinstance(e, (int, np.integer)) and 1 <= e < 1 << (8 * bpv - 1), "max_error %r with %d bytes per value" % (e, bpv)
 
 
-def _code(r, bpv):
+def _code(r, bpv, layout=None, p0=None):
     """indices r int64 [n, c] in coding order, n > 0 -> S | n_chunks | p0 | chunk table | chunk payloads: r dealt to lanes
     and chunks, each lane coding its run with the bucket of the channel's previous |r| in the run as context"""
     n, c = r.shape
-    S, nc = layout(n, c)
+    S, nc = pick_layout(n, c, layout)
     R = nc * LANES
     runs = np.zeros((R * S, c), np.int64)
     runs[:n] = r
@@ -58,7 +60,7 @@ def _code(r, bpv):
         Kc = ok.sum(1)
         o = np.argsort(~ok, axis=1, kind="stable")[:, :Kc.max()]            # every run's coded decisions first
         per.append((np.take_along_axis(ctx, o, 1), np.take_along_axis(bit, o, 1), Kc))
-    p0 = _p0(c0, c1)
+    p0 = pick_p0(_p0(c0, c1), p0)
     K = np.concatenate([p[2] for p in per])
     T = int(K.max())
     cx = np.zeros((R, T), np.int64)
@@ -98,10 +100,10 @@ def _code(r, bpv):
     return body + b"".join(struct.pack("<%dH" % len(ch), *ch) for ch in chunks)
 
 
-def indices4(v, e):
+def indices4(v, e, layout=None):
     """version 4: merged values v int64 [n, c] in Morton order -> (j [n, c], v^ [n, c] unclamped)"""
     n, c = v.shape
-    S, nc = layout(n, c)
+    S, nc = pick_layout(n, c, layout)
     R = nc * LANES
     runs = np.zeros((R * S, c), np.int64)
     runs[:n] = v
@@ -131,18 +133,18 @@ def indices7(v, s, first, e):
     return j, vh
 
 
-def encode(values, bpv, e, points=None, bias=32768):
+def encode(values, bpv, e, points=None, bias=32768, layout=None, p0=None):
     v = _as2d(values)
     n, c = v.shape
     if e == 0:
-        return attr_ref.encode(v, bpv) if points is None else attr2_ref.encode(points, v, bpv, bias)
+        return attr_ref.encode(v, bpv, layout, p0) if points is None else attr2_ref.encode(points, v, bpv, bias, layout, p0)
     _check_e(e, bpv)
     assert n == 0 or (v.min() >= 0 and v.max() < 1 << (8 * bpv))
     if points is None:
         head = bytes([ord("A"), 4, bpv, c]) + struct.pack("<I", n)
         if n == 0:
             return head + struct.pack("<I", 0)
-        body = struct.pack("<I", e) + _code(indices4(v, e)[0], bpv)
+        body = struct.pack("<I", e) + _code(indices4(v, e, layout)[0], bpv, layout, p0)
         return head + struct.pack("<I", len(body)) + body
     slod = 15 - int(bias).bit_length() + 1
     assert bias == 32768 >> slod
@@ -155,7 +157,7 @@ def encode(values, bpv, e, points=None, bias=32768):
     s, order, first = attr2_ref.intro(keys)
     j, _ = indices7(v, s, first, e)
     cells = [int((s >= k).sum()) for k in range(16)]
-    body = struct.pack("<I", e) + struct.pack("<16I", *cells) + _code(j[order], bpv)     # indices in introduction order
+    body = struct.pack("<I", e) + struct.pack("<16I", *cells) + _code(j[order], bpv, layout, p0)     # indices in introduction order
     return head + struct.pack("<I", len(body)) + body
 
 
@@ -184,20 +186,20 @@ def _lossless_shape(blob):
     return bytes([blob[0], 2]) + blob[2:8] + struct.pack("<I", plen - 4) + blob[HEAD + 4:], i["max_error"]
 
 
-def lod_info(blob, lod):
+def lod_info(blob, lod, any_layout=False):
     if blob[1] == 2:
-        return attr2_ref.lod_info(blob, lod)
+        return attr2_ref.lod_info(blob, lod, any_layout)
     b2, _ = _lossless_shape(blob)
-    nbytes, m = attr2_ref.lod_info(b2, lod)
+    nbytes, m = attr2_ref.lod_info(b2, lod, any_layout)
     return (nbytes + 4 if m else nbytes), m
 
 
-def decode(blob, cells=None, lod=0):
+def decode(blob, cells=None, lod=0, any_layout=False):
     ver = blob[1]
     if ver == 1:
         return attr_ref.decode(blob)
     if ver == 2:
-        return attr2_ref.decode(blob, cells, lod)
+        return attr2_ref.decode(blob, cells, lod, any_layout)
     i = info(blob)
     bpv, c, n, e = i["bpv"], i["channels"], i["points"], i["max_error"]
     mask, q = (1 << (8 * bpv)) - 1, 2 * e + 1
@@ -214,8 +216,8 @@ def decode(blob, cells=None, lod=0):
         for _ in range(15):
             counts.append(max(1, -(-counts[-1] // 8)))
         b2 = bytes([blob[0], 2, bpv, c]) + blob[4:8] + struct.pack("<I", plen - 4 + 64) + struct.pack("<16I", *counts) + blob[HEAD + 4:]
-        j = attr2_ref._residuals(b2, n)[0]                                  # signed, as the binarisation holds them
-        S, nc = layout(n, c)
+        j = attr2_ref._residuals(b2, n, any_layout)[0]                      # signed, as the binarisation holds them
+        S, nc = struct.unpack_from("<II", blob, HEAD + 4)                   # the header's: _residuals has checked them
         runs = np.zeros((nc * LANES * S, c), np.int64)
         runs[:n] = j
         runs = runs.reshape(nc * LANES, S, c)
@@ -229,14 +231,14 @@ def decode(blob, cells=None, lod=0):
     assert ver == 7
     cells = np.asarray(cells, np.int64).reshape(-1, 3)
     b2, e = _lossless_shape(blob)
-    _, _, _, h = attr2_ref._header(b2)
+    _, _, _, h = attr2_ref._header(b2, any_layout)
     m = cells.shape[0]
     if n == 0:
         assert m == 0
         return np.zeros((0, c), np.int64), bpv
     assert m == h[0][lod], "the blob has %d values at lod %d, the geometry %d cells" % (h[0][lod], lod, m)
-    assert len(b2) >= attr2_ref.lod_info(b2, lod)[0], "truncated"
-    j = attr2_ref._residuals(b2, m)[0]
+    assert len(b2) >= attr2_ref.lod_info(b2, lod, any_layout)[0], "truncated"
+    j = attr2_ref._residuals(b2, m, any_layout)[0]
     assert h[5] + lod <= 15
     keys = np.sort(attr2_ref.keys_of(cells, 32768 >> (h[5] + lod)))
     s, order, first = attr2_ref.intro(keys)

@@ -3,7 +3,12 @@ in numpy: a value's binarisation as 16 bpv fixed slots with a validity mask, and
 stepped side by side.  Not a port of the kernels, which walk one lane's values with a loop per decision.
 
     encode(values, bpv)              -> blob                          values int [n] or [n, c]
+                                        layout=(S, n_chunks): any layout the parser accepts (check_layout) in place
+                                        of layout(n, c); p0=: the initial table, nctx entries or one for all, in
+                                        place of the counted one.  The coding is the same for every layout and table
     decode(blob)                     -> (values int64 [n, c], bpv)
+    status(blob)                     -> the decoder's status word of the frame (csrc/attr.hip, above ADFrame): the
+                                        OR over chunks and lanes of 1 = words, 4 = final state; 0 for a sound blob
     single_stream_bytes(values, bpv) -> bytes of the frame as ONE lane: same model, same p0, one final state (the
                                         ideal code length of its decisions rounded up to words, its 4-byte state and
                                         the one-chunk header)
@@ -34,6 +39,32 @@ def layout(n, c):
     smax = MAX_VALUES // c
     k = max(1, -(-n // (LANES * smax)))
     return max(1, -(-n // (LANES * k))), k
+
+
+def check_layout(n, c, S, nc):
+    """the four conditions under which the parsers of csrc/attr_blob.h take (S, chunks) for n > 0 points of c channels"""
+    assert S >= 1, (S, nc)
+    assert S * c <= MAX_VALUES, (S, c)
+    assert 1 <= nc <= n, (nc, n)
+    assert LANES * S * (nc - 1) < n <= LANES * S * nc, (n, S, nc)
+
+
+def pick_layout(n, c, given=None):
+    """layout(n, c), or the (S, chunks) given if the parsers take it"""
+    if given is None:
+        return layout(n, c)
+    S, nc = (int(a) for a in given)
+    check_layout(n, c, S, nc)
+    return S, nc
+
+
+def pick_p0(counted, given=None):
+    """the counted table, or the one given: an entry per context or one for all, each in [16, 4080]"""
+    if given is None:
+        return counted
+    p0 = np.broadcast_to(np.asarray(given, np.int64), counted.shape).copy()
+    assert ((p0 >= 16) & (p0 <= 4080)).all()
+    return p0
 
 
 def _bucket(m):
@@ -94,13 +125,13 @@ def _as2d(values):
     return v[:, None] if v.ndim == 1 else v
 
 
-def encode(values, bpv):
+def encode(values, bpv, layout=None, p0=None):
     v = _as2d(values)
     n, c = v.shape
     head = bytes([ord("A"), 1, bpv, c]) + struct.pack("<I", n)
     if n == 0:
         return head + struct.pack("<I", 0)
-    S, nc = layout(n, c)
+    S, nc = pick_layout(n, c, layout)
     R = nc * LANES
     runs = np.zeros((R * S, c), np.int64)
     runs[:n] = v
@@ -120,7 +151,7 @@ def encode(values, bpv):
         order = np.argsort(~ok, axis=1, kind="stable")
         K = ok.sum(1)
         per.append((np.take_along_axis(ctx, order, 1)[:, :K.max()], np.take_along_axis(bit, order, 1)[:, :K.max()], K))
-    p0 = _p0(c0, c1)
+    p0 = pick_p0(_p0(c0, c1), p0)
     T = max(p[0].shape[1] for p in per)
     cx = np.zeros((R, T), np.int64)
     bt = np.zeros((R, T), np.int64)
@@ -166,13 +197,29 @@ def encode(values, bpv):
 def decode(blob):
     """blob -> (values int64 [n, c], bpv): every lane a state machine over its binarisation, all 64 lanes of a chunk
     stepped together"""
+    out, bpv, bad = _decode(blob, True)
+    assert bad == 0
+    return out, bpv
+
+
+def status(blob):
+    """the status word the lane decoder leaves for this frame: bit 1 = a chunk whose 192 + sum of len is not its table
+    entry (it is then not decoded), a lane that needs a word at or behind the end of its run (it goes on with the
+    chunk's words by position, the last of them again and again), a lane that ends in front of the end of its run;
+    bit 4 = a lane that does not end in the state 2^16"""
+    return _decode(blob, False)[2]
+
+
+def _decode(blob, strict):
+    """-> (values, bpv, status); strict: a stream that would set a status bit stops at an assert instead"""
     tag, ver, bpv, c = blob[0], blob[1], blob[2], blob[3]
     assert tag == ord("A") and ver == 1 and bpv in (1, 2) and 1 <= c <= 4
     n, plen = struct.unpack_from("<II", blob, 4)
     assert HEAD + plen == len(blob)
     if n == 0:
-        return np.zeros((0, c), np.int64), bpv
+        return np.zeros((0, c), np.int64), bpv, 0
     S, nc = struct.unpack_from("<II", blob, HEAD)
+    check_layout(n, c, S, nc)
     nctx, P, kmax = contexts(bpv, c), positions(bpv), 8 * bpv - 1
     mask = (1 << (8 * bpv)) - 1
     at = HEAD + 8
@@ -182,12 +229,16 @@ def decode(blob):
     at += 4 * nc
     out = np.zeros((nc * LANES * S, c), np.int64)
     lanes = np.arange(LANES)
+    bad = 0
     for k in range(nc):
         w = np.array(struct.unpack_from("<%dH" % cw[k], blob, at), np.int64)
         at += 2 * cw[k]
         x = w[0:128:2] | (w[1:128:2] << 16)
         ln = w[128:192]
-        assert 192 + ln.sum() == cw[k]
+        assert not strict or 192 + ln.sum() == cw[k]
+        if 192 + ln.sum() != cw[k]:
+            bad |= 1
+            continue
         pos = 192 + np.concatenate([[0], np.cumsum(ln)[:-1]])
         end = pos + ln
         npts = np.clip(n - (k * LANES + lanes) * S, 0, S)
@@ -205,7 +256,8 @@ def decode(blob):
             x = np.where(act, freq * (x >> 12) + cum - np.where(bit == 1, 4096 - p1, 0), x)
             model[lanes[act], ctx[act]] = _adapt(p1, bit)[act]
             need = act & (x < L)
-            assert not (need & (pos >= end)).any(), "a lane ran out of words"
+            assert not strict or not (need & (pos >= end)).any(), "a lane ran out of words"
+            bad |= 1 if (need & (pos >= end)).any() else 0
             x = np.where(need, (x << 16) | w[np.minimum(pos, cw[k] - 1)], x)
             pos += need
             # the next place in the binarisation; done = the value is complete, m its magnitude
@@ -232,8 +284,9 @@ def decode(blob):
             chn = np.where(fin, chn + 1, chn)
             s = np.where(fin & (chn == c), s + 1, s)
             chn = np.where(chn == c, 0, chn)
-        assert (pos == end).all() and (x == L).all(), "corrupt chunk"
-    return out[:n], bpv
+        assert not strict or ((pos == end).all() and (x == L).all()), "corrupt chunk"
+        bad |= (0 if (pos == end).all() else 1) | (0 if (x == L).all() else 4)
+    return out[:n], bpv, bad
 
 
 def single_stream_bytes(values, bpv):
