@@ -115,10 +115,23 @@ def _forced_layout(n_nodes, S):
     return int(S), max(1, -(-n_nodes // (LANES * int(S))))
 
 
-def encode_payload(levels, rb, n_ctx, smax, S=None):
+def rans_lane(steps):
+    """(final state, words in the order a decoder consumes them) of a lane's decisions [(probability of a one, bit)]"""
+    x, words = 1 << 16, []
+    for p1, bit in reversed(steps):
+        freq, start = (p1, 4096 - p1) if bit else (4096 - p1, 0)
+        if x >= freq << 20:
+            words.append(x & 0xFFFF)
+            x >>= 16
+        x = ((x // freq) << 12) + x % freq + start
+    return x, words[::-1]
+
+
+def encode_payload(levels, rb, n_ctx, smax, S=None, p0=None, lane=rans_lane):
     """(S, nc, p0, chunks): the lanes' rANS streams of the occupancy bytes under contexts r * 108 + version 2's.
     S=None: the encoder's layout under the bound smax; else S nodes per lane as given (lanes behind the last node
-    carry the initial state and no words)"""
+    carry the initial state and no words).  p0: the initial table as given instead of the counted one; lane: another
+    writer of a lane's decisions (octree2_layout_ref has one)"""
     occ = [b for lv in levels for b in lv]
     depth, n_nodes = len(levels), len(occ)
     S, nc = _layout(n_nodes, smax) if S is None else _forced_layout(n_nodes, S)
@@ -139,7 +152,9 @@ def encode_payload(levels, rb, n_ctx, smax, S=None):
     for i in range(n_nodes):
         for ctx, bit in decisions(i):
             (c1 if bit else c0)[ctx] += 1
-    p0 = [_p0(c0[k], c1[k]) for k in range(n_ctx)]
+    p0 = [_p0(c0[k], c1[k]) for k in range(n_ctx)] if p0 is None else [int(v) for v in p0]
+    if len(p0) != n_ctx or not all(16 <= v <= 4080 for v in p0):
+        raise ValueError("p0: %d probabilities in 16 .. 4080" % n_ctx)
     chunks = []
     for c in range(nc):
         states, lens, runs = [], [], []
@@ -152,16 +167,10 @@ def encode_payload(levels, rb, n_ctx, smax, S=None):
                 for ctx, bit in decisions(i):
                     steps.append((model[ctx], bit))
                     model[ctx] = _adapt(model[ctx], bit)
-            x, words = 1 << 16, []
-            for p1, bit in reversed(steps):
-                freq, start = (p1, 4096 - p1) if bit else (4096 - p1, 0)
-                if x >= freq << 20:
-                    words.append(x & 0xFFFF)
-                    x >>= 16
-                x = ((x // freq) << 12) + x % freq + start
+            x, words = lane(steps)
             states += [x & 0xFFFF, x >> 16]
             lens.append(len(words))
-            runs += words[::-1]
+            runs += words
         chunks.append(states + lens + runs)
     return S, nc, p0, chunks
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import attr_ref
+import octree2_layout_ref
 from conftest import ROOT, pkg
 from test_geometry_frames import _cloud, _mixed_frames, _unique
 
@@ -17,28 +18,10 @@ LODS = (0, 1, 2, 3, 5, 9, 15)
 
 # ------------------------------------------------------------------ the rule, restated from the blob's bytes alone
 def _rule(blob, k):
-    """(bytes, cells) of level of detail k, read off the bytes of a well-formed version-2 blob"""
-    n = struct.unpack_from("<I", blob, 4)[0]
-    if n == 0:
-        return 24, 0
-    if k == 0:
-        return len(blob), n
-    d = blob[2]
-    level_n = struct.unpack_from(f"<{d}I", blob, 24)
-    S, nc = struct.unpack_from("<2I", blob, 24 + 4 * d)
-    off_table = 24 + 4 * d + 8 + 2 * 108
-    words = struct.unpack_from(f"<{nc}I", blob, off_table)
-    off_payload = off_table + 4 * nc
-    Lc = max(d - k, 0)
-    m = level_n[Lc] if Lc > 0 else 1
-    need = sum(level_n[:Lc])
-    if need == 0:
-        return off_payload, m
-    lanes = -(-need // S)
-    c, l = (lanes - 1) // 64, (lanes - 1) % 64
-    start = off_payload + 2 * sum(words[:c])
-    lens = np.frombuffer(blob, "<u2", 64, start + 2 * 128)
-    return start + 2 * (192 + int(lens[:l + 1].sum())), m
+    """(bytes, cells) of level of detail k, read off the bytes of a well-formed version-2 blob (the restatement of the
+    rule is octree2_layout_ref.plan: one copy for this file and for the tests of the decoder under forced layouts)"""
+    p = octree2_layout_ref.plan(blob, k)
+    return p["bytes"], p["cells"]
 
 
 def _cells(points, k):
