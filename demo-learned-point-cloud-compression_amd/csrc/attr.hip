@@ -73,6 +73,13 @@
 // of their own; the rows' lengths from their chunks' words; k_ar_gather and k_a_pack<.., TR[, const int32_t*]> over the
 // winners alone.  tests/attr_rate_ref.py restates ladder and search in numpy.
 //
+// Versions 25 and 26 (attr_blob.h has the rule): version 2's stream over the residuals of a predictor from up to three
+// Morton-first points of the coarser cells around a point.  The kernels are attr_nbr.h's.  Encoder: version 2's launches
+// with k_an_place in place of k_a2_place (and k_ax_fwd<false> for a frame of version 26); k_a_pack writes version 2's /
+// 11's head and a_enc_emit sets the version byte.  Decoder (pcc_attr_decode_frames_lod): the order stage with k_an_plan in
+// place of k_a2_place, k_a_dec<true> (k_ax_inv), then k_an_recon once per occupied size of introduction, 16 down to 0.
+// tests/attr_nbr_ref.py restates both kinds in numpy.
+//
 // Host side: the kinds share one encode sequence (a_encode_frames over an AEncKind, the entry point's kind resolved
 // once) and one decode-call skeleton (ADecCall: accounting, rows, layout, upload, status) under the three decoders, each
 // of which keeps its parser, its side tables, its arena arrays and its kernels; DESIGN.md, "attr.hip: one encode path,
@@ -1487,6 +1494,8 @@ __global__ __launch_bounds__(256) void k_ar_gather(const ARPick* __restrict__ pi
 
 }  // namespace
 
+#include "attr_nbr.h"   // versions 25 and 26: k_an_place, k_an_plan, k_an_recon
+
 static inline int64_t a_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 static inline size_t merged_b_of(int64_t vals) { return pcc_align((size_t)vals * 2); }
 
@@ -1636,11 +1645,19 @@ struct AEncKind {
   const int32_t* h_qsteps;   // version 21: q[4]
   int colour;                // version 21: 0 | 1
   int K;                     // version 22: the deepest cut (0: another kind)
+  bool nbr = false;          // versions 25 / 26: version 2's call with k_an_place for k_a2_place and their version bytes
   bool keyed() const { return v2 || tr; }   // d_keys and key_shift are read
 };
 static AEncKind a_kind_plain(int version, int64_t n_kept, int max_error, const int32_t* h_cross) {
   const bool v2 = version == 2, nl = max_error > 0;
   return AEncKind{attr_version(v2, nl, false), v2, nl, false, false, max_error, n_kept, h_cross, nullptr, 0, 0};
+}
+// versions 25 and 26: version 2's kind under the neighbour predictor
+static AEncKind a_kind_nbr(int64_t n_kept, const int32_t* h_cross) {
+  AEncKind k = a_kind_plain(2, n_kept, 0, h_cross);
+  k.version = kAttrNVersion;
+  k.nbr = true;
+  return k;
 }
 static AEncKind a_kind_transform(int64_t n_kept, int qstep, const int32_t* h_qsteps, int colour, int K = 0) {
   const bool tc = h_qsteps != nullptr;
@@ -1814,11 +1831,13 @@ static int a_enc_emit(const char* who, const AEncKind& k, pcc_ctx* ctx, const in
     uint8_t* dst = h_out + h_offsets[f];
     if (o.off_of[(size_t)f] >= 0) {
       memcpy(dst, (const uint8_t*)ctx->stage + o.off_of[(size_t)f], (size_t)o.len_of[(size_t)f]);
+      // versions 25 / 26: k_a_pack wrote version 2's / 11's head, which is theirs but for the version byte
+      if (k.nbr) dst[1] = (uint8_t)attr_version(true, false, dst[1] == attr_version(true, false, true), true);
     } else {
       const int32_t m = k.h_cross ? k.h_cross[f] : 0;
       memset(dst, 0, kAttrHead);
       dst[0] = 'A';
-      dst[1] = (uint8_t)(m ? attr_version(k.v2, k.nl, true) : k.version);
+      dst[1] = (uint8_t)(m ? attr_version(k.v2, k.nl, true, k.nbr) : k.version);
       dst[2] = (uint8_t)((h_format[f] & 0xFF) | (k.keyed() ? (key_shift / 3) << 4 : 0));
       dst[3] = (uint8_t)((h_format[f] >> 8) | (m << 4));
     }
@@ -1961,6 +1980,12 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
       PCC_CHECK_LAUNCH();
       hipLaunchKernelGGL(k_a2_scan, dim3((unsigned)nf), dim3(256), 0, st, d_ord, hist, bins, cells);
       PCC_CHECK_LAUNCH();
+      if (k.nbr) {   // versions 25 / 26: the residuals against the neighbour predictor, in one pass of its own
+        hipLaunchKernelGGL(k_an_place, dim3((unsigned)merge_blocks), dim3(256), 0, st, d_keys, d_ord, nf, (const uint16_t*)packed,
+                           (const uint32_t*)hist, (const uint32_t*)bins, (const AFrame*)d_tab, (const uint16_t*)merged, src);
+        PCC_CHECK_LAUNCH();
+        return PCC_OK;
+      }
       const auto place = keep ? k_a2_place<true, true> : k_a2_place<true, false>;
       hipLaunchKernelGGL(place, dim3((unsigned)merge_blocks), dim3(256), 0, st, d_keys, d_ord, nf, (const uint16_t*)packed,
                          (const uint32_t*)hist, (const uint32_t*)bins, (const AFrame*)d_tab, (const uint16_t*)merged,
@@ -2007,7 +2032,8 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
     };
     // by the version byte of the call's frames with a mask, where it has any, else of its plain frames
     int rc = PCC_E_ARG;
-    switch (xc ? attr_version(v2, nl, true) : k.version) {   //   V2     NL     XC     TR
+    // (versions 25 / 26 are coded, packed and laid out as 2 / 11)
+    switch (xc ? attr_version(v2, nl, true) : (k.nbr ? 2 : k.version)) {   //   V2     NL     XC     TR
       case 1: rc = a_code(ACoder<false, false, false>{}); break;
       case 2: rc = a_code(ACoder<true, false, false>{}); break;
       case 4: rc = a_code(ACoder<false, true, false>{}); break;
@@ -2077,6 +2103,15 @@ extern "C" int pcc_attr_encode_frames_cross(pcc_ctx* ctx, int version, const voi
   return a_encode_frames("pcc_attr_encode_frames_cross", a_kind_plain(version, n_kept, max_error, h_cross), ctx, d_values, h_value_offsets,
                          h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, version == 2 ? d_keys : nullptr,
                          version == 2 ? key_shift : 0, h_out, cap, h_offsets);
+}
+
+extern "C" int pcc_attr_encode_frames_nbr(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets, const int32_t* h_format,
+                                          const int64_t* h_rows, const int64_t* h_points, int n_frames, const uint32_t* d_perm,
+                                          const uint32_t* d_run_starts, int64_t n_unique, int64_t n_kept, const uint64_t* d_keys,
+                                          int key_shift, const int32_t* h_cross, uint8_t* h_out, int64_t cap, int64_t* h_offsets) {
+  PCC_REQUIRE(n_kept >= -1, PCC_E_ARG, "pcc_attr_encode_frames_nbr: bad argument (n_kept=%lld)", (long long)n_kept);
+  return a_encode_frames("pcc_attr_encode_frames_nbr", a_kind_nbr(n_kept, h_cross), ctx, d_values, h_value_offsets, h_format, h_rows,
+                         h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets);
 }
 
 extern "C" int pcc_attr_encode_frames_transform(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
@@ -2565,7 +2600,8 @@ static int a_wrap_error(const char* who, int rc) {
 // host only: the version byte and byte 3 of a head, checked: its kind, channels and mask
 static int a_head_kind(const char* who, const uint8_t* h_in, int64_t len, bool* scal, bool* nl, bool* xc, int* c, int* m) {
   PCC_REQUIRE(h_in && len >= kAttrHead && h_in[0] == 'A', PCC_E_STREAM, "%s: not an attribute blob (len=%lld)", who, (long long)len);
-  PCC_REQUIRE(attr_kind(h_in[1], scal, nl, xc), PCC_E_STREAM, "%s: attribute blob version %d", who, (int)h_in[1]);
+  bool nbr;   // versions 25 / 26 stand beside 2 / 11 here: scalable, lossless, 26 with a mask
+  PCC_REQUIRE(attr_kind(h_in[1], scal, nl, xc, &nbr), PCC_E_STREAM, "%s: attribute blob version %d", who, (int)h_in[1]);
   const int bpv = *scal ? h_in[2] & 15 : h_in[2];
   PCC_REQUIRE((bpv == 1 || bpv == 2) && attr_channels(h_in[3], *xc, c, m), PCC_E_STREAM, "%s: %d bytes per value, %d channels%s", who,
               bpv, *c, *xc ? ", or their mask" : "");
@@ -2670,15 +2706,17 @@ extern "C" int pcc_attr_info(const uint8_t* h_in, int64_t len, int32_t* h_versio
 // ---- what the three decoders share -----------------------------------------------------------------------------------
 static bool a_is_version(const uint8_t* b, int64_t len, int version) { return b && len >= 2 && b[0] == 'A' && b[1] == version; }
 
-// the version of a call's blobs: the first blob's when it is one of the entry point's four, else the first of them
-static int a_call_version(const uint8_t* b, int64_t len, const int (&kinds)[4]) {
+// the version of a call's blobs: the first blob's when it is one of the entry point's kinds, else the first of them
+template <int N>
+static int a_call_version(const uint8_t* b, int64_t len, const int (&kinds)[N]) {
   for (int k : kinds)
     if (a_is_version(b, len, k)) return k;
   return kinds[0];
 }
 
 // the blobs of a call are of one version, `mine`: the entry point's other versions are refused by name
-static int a_mixed_version(const char* who, int f, const uint8_t* b, int64_t len, const int (&kinds)[4], int mine) {
+template <int N>
+static int a_mixed_version(const char* who, int f, const uint8_t* b, int64_t len, const int (&kinds)[N], int mine) {
   for (int other : kinds)
     PCC_REQUIRE(other == mine || !a_is_version(b, len, other), PCC_E_ARG,
                 "%s: frame %d: attribute blob version %d in a call of version %d blobs (one version per call)", who, f, other, mine);
@@ -3088,14 +3126,14 @@ extern "C" int pcc_attr_lod_info(const uint8_t* h_in, int64_t len, int lod, int6
     AttrSInfo o;
     rc = attr_s_parse(h_in, len, lod, kAttrSPlan, &o, &pl);
   } else {
-    bool scal = false, nl = false, xc = false;
+    bool scal = false, nl = false, xc = false, nbr = false;
     PCC_REQUIRE(!attr_t_kind(h_in[1]) && !attr_c_kind(h_in[1]), PCC_E_ARG,
                 "pcc_attr_lod_info: attribute blob version %d (a transform-coded blob has no level-of-detail prefixes: the weights of its "
                 "transform need every point)", (int)h_in[1]);
-    PCC_REQUIRE(attr_kind(h_in[1], &scal, &nl, &xc) && scal, PCC_E_ARG,
+    PCC_REQUIRE(attr_kind(h_in[1], &scal, &nl, &xc, &nbr) && scal, PCC_E_ARG,
                 "pcc_attr_lod_info: attribute blob version %d (levels of detail are a property of version 2)", (int)h_in[1]);
     Attr2Info o;
-    rc = attr2_parse_kind(h_in, len, lod, false, nl, &o, &pl, xc);
+    rc = attr2_parse_kind(h_in, len, lod, false, nl, &o, &pl, xc, nbr);
   }
   if (rc != PCC_OK) return a_wrap_error("pcc_attr_lod_info", rc);
   if (h_bytes) *h_bytes = pl.bytes;
@@ -3124,17 +3162,19 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
                              lod);
   }
   // the blobs of a call are of one version, the first blob's: 2, or 7 (k_a2_walk<true> scales and clamps), or their
-  // cross-channel forms 11 and 14 (k_ax_inv between the decoder and the walk)
-  const int kinds[4] = {2, 7, 11, 14};
+  // cross-channel forms 11 and 14 (k_ax_inv between the decoder and the walk), or 25 or its cross form 26 (k_an_plan for
+  // k_a2_place, and k_an_recon size by size for the walk)
+  const int kinds[6] = {2, 7, 11, 14, kAttrNVersion, kAttrNXVersion};
   const int mine = a_call_version(h_blobs[0], h_lens[0], kinds);
-  const bool nl = mine == 7 || mine == 14, xc = mine == 11 || mine == 14;
+  const bool nbr = mine == kAttrNVersion || mine == kAttrNXVersion;
+  const bool nl = mine == 7 || mine == 14, xc = mine == 11 || mine == 14 || mine == kAttrNXVersion;
   ADecCall d = a_dec_call(who, ctx, h_blobs, n_frames, d_out, h_out, cap_bytes, h_out_offsets, h_format);
   std::vector<Attr2Info> info((size_t)n_frames);
   for (int f = 0; f < n_frames; ++f) {
     Attr2Info& o = info[(size_t)f];
     Attr2Plan pl;
     PCC_TRY(a_mixed_version(who, f, h_blobs[f], h_lens[f], kinds, mine));
-    const int rc = attr2_parse_kind(h_blobs[f], h_lens[f], lod, true, nl, &o, &pl, xc);
+    const int rc = attr2_parse_kind(h_blobs[f], h_lens[f], lod, true, nl, &o, &pl, xc, nbr);
     if (rc != PCC_OK) return a_wrap_error(who, f, rc);
     if (h_cell_offsets) {
       const int64_t m = h_cell_offsets[f + 1] - h_cell_offsets[f];
@@ -3161,12 +3201,14 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   const size_t keys_b = pcc_align((size_t)cells_all * 8), u32_b = pcc_align((size_t)cells_all * 4), pk_b = pcc_align((size_t)cells_all * 2);
   // 17 bin bases per frame | 16 counts per frame | status per frame: the last two come back in one copy
   const size_t hist_b = pcc_align((size_t)blocks * kA2Bins * 4), bins_b = pcc_align((size_t)nf * 34 * 4 + 64);
-  PCC_TRY(a_dec_plan(d, d_out ? 1 : 2, keys_b + 2 * u32_b + pk_b + hist_b + bins_b + 8192));
+  // versions 25 / 26: `rank` holds the inverse of the places and `first` every cell's choice, 3 words
+  const size_t first_b = nbr ? pcc_align((size_t)cells_all * 12) : u32_b;
+  PCC_TRY(a_dec_plan(d, d_out ? 1 : 2, keys_b + u32_b + first_b + pk_b + hist_b + bins_b + 8192));
   hipStream_t st = ctx->stream;
   uint8_t* resid = (uint8_t*)pcc_arena_alloc(ctx, (size_t)d.bytes);
   uint64_t* keys = (uint64_t*)pcc_arena_alloc(ctx, keys_b);
   uint32_t* rank = (uint32_t*)pcc_arena_alloc(ctx, u32_b);
-  uint32_t* first = (uint32_t*)pcc_arena_alloc(ctx, u32_b);
+  uint32_t* first = (uint32_t*)pcc_arena_alloc(ctx, first_b);
   uint16_t* packed = (uint16_t*)pcc_arena_alloc(ctx, pk_b);
   uint32_t* hist = (uint32_t*)pcc_arena_alloc(ctx, hist_b);
   uint32_t* bins = (uint32_t*)pcc_arena_alloc(ctx, bins_b);
@@ -3183,18 +3225,43 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   PCC_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_a2_scan, dim3((unsigned)nf), dim3(256), 0, st, d_ord, hist, bins, counts);
   PCC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_a2_place<false>, dim3((unsigned)blocks), dim3(256), 0, st, (const uint64_t*)keys, d_ord, nf, (const uint16_t*)packed,
-                     (const uint32_t*)hist, (const uint32_t*)bins, (const AFrame*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr,
-                     rank, first);
+  if (nbr) {
+    hipLaunchKernelGGL(k_an_plan, dim3((unsigned)blocks), dim3(256), 0, st, (const uint64_t*)keys, d_ord, nf, (const uint16_t*)packed,
+                       (const uint32_t*)hist, (const uint32_t*)bins, rank, first);
+  } else {
+    hipLaunchKernelGGL(k_a2_place<false>, dim3((unsigned)blocks), dim3(256), 0, st, (const uint64_t*)keys, d_ord, nf, (const uint16_t*)packed,
+                       (const uint32_t*)hist, (const uint32_t*)bins, (const AFrame*)nullptr, (const uint16_t*)nullptr, (uint16_t*)nullptr,
+                       rank, first);
+  }
   PCC_CHECK_LAUNCH();
   PCC_TRY(a_launch_dec<true>(d, resid, status));
   if (xc) {
     hipLaunchKernelGGL(k_ax_inv, dim3(nblk(d.n_max, 256), (unsigned)nf), dim3(256), 0, st, d_tab, (const int32_t*)(d.d_in + d.masks_at()), resid);
     PCC_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL((nl ? k_a2_walk<true> : k_a2_walk<false>), dim3((unsigned)blocks), dim3(256), 0, st, d_ord, nf, d_tab,
-                     (const uint32_t*)rank, (const uint32_t*)first, (const uint8_t*)resid, d.out, status);
-  PCC_CHECK_LAUNCH();
+  if (nbr) {
+    // sizes 16 .. 0 of the cells, each over its range of the introduction order, all frames in one grid.  The grid of a
+    // size comes from the heads' counts (size j of the cells: cells[lod + j] - cells[lod + j + 1], point 0 alone at 16),
+    // which the parser bounded and counts_match holds against the cells below; the ranges themselves are the order
+    // stage's, on the device.  A size without a point in any frame is not launched
+    for (int s = kA2Bins - 1; s >= 0; --s) {
+      int64_t most = 0;
+      for (int f = 0; f < n_frames; ++f) {
+        if (d.in[(size_t)f].n_dec == 0) continue;
+        const int64_t* c = info[(size_t)f].cells;
+        const int j = lod + s;
+        most = std::max<int64_t>(most, s == 16 ? 1 : (j > kAttrMaxLod ? 0 : c[j] - (j < kAttrMaxLod ? c[j + 1] : 1)));
+      }
+      if (most == 0) continue;
+      hipLaunchKernelGGL(k_an_recon, dim3(nblk(most, 256), (unsigned)nf), dim3(256), 0, st, d_ord, d_tab, (const uint32_t*)bins, s,
+                         (const uint32_t*)rank, (const uint32_t*)first, (const uint8_t*)resid, d.out, status);
+      PCC_CHECK_LAUNCH();
+    }
+  } else {
+    hipLaunchKernelGGL((nl ? k_a2_walk<true> : k_a2_walk<false>), dim3((unsigned)blocks), dim3(256), 0, st, d_ord, nf, d_tab,
+                       (const uint32_t*)rank, (const uint32_t*)first, (const uint8_t*)resid, d.out, status);
+    PCC_CHECK_LAUNCH();
+  }
   // counts and status come back in one copy; per frame, the coarser levels' counts of the header against those of the
   // cells themselves, then its status
   const auto counts_match = [&](int f, int k) -> int {
@@ -3206,5 +3273,6 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
     return PCC_OK;
   };
   return a_dec_finish(d, counts, (size_t)nf * 17 * 4, 0, (size_t)nf * 16 * 4,
-                      nl ? ", 8 = predictor chain, 16 = reconstruction out of range" : ", 8 = predictor chain", counts_match);
+                      nl ? ", 8 = predictor chain, 16 = reconstruction out of range" : (nbr ? ", 8 = index outside the frame" : ", 8 = predictor chain"),
+                      counts_match);
 }

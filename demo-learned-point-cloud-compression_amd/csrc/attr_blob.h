@@ -1,7 +1,7 @@
 // attr_blob.h — the header of an attribute blob (attr.hip), parsed and checked on the host before anything is reserved
 // or launched.  Plain C++ (no HIP): tests/fuzz/fuzz_attr_header.cpp, fuzz_attr2_header.cpp, fuzz_attr_nl_header.cpp,
-// fuzz_attr_cross_header.cpp, fuzz_attr_transform_header.cpp, fuzz_attr_colour_header.cpp and
-// fuzz_attr_scalable_header.cpp put it under the sanitizers.
+// fuzz_attr_cross_header.cpp, fuzz_attr_transform_header.cpp, fuzz_attr_colour_header.cpp,
+// fuzz_attr_scalable_header.cpp and fuzz_attr_nbr_header.cpp put it under the sanitizers.
 //
 // Every size the decoder reserves or reads follows from what this parse accepted: the chunk table must add up to the
 // blob's own length, so a header cannot announce more words than the blob holds; n is bounded by the chunks
@@ -61,6 +61,33 @@
 // does: a cross kind decodes to the values of the plain kind of the same call, at every level of detail, and the
 // near-lossless bound holds unchanged.  Binarisation, model, p0, S, chunks, word runs and the prefix rule are unchanged.
 // tests/attr_cross_ref.py restates the four kinds in numpy.
+//
+// Neighbour-predicted kinds, versions 25 and 26 (attr2_parse_kind with nbr = true; 26 is the cross form of 25 as 11 is
+// of 2; 25 = 11001b and 26 = 11010b keep the odd parity of the eleven bytes 1, 2, 4, 7, 8, 11, 13, 14, 19, 21, 22 and so
+// differ from each in two bits): lossless and scalable.  Layout, chunks, coder, contexts, model, introduction order,
+// cells[], slod and the prefix rule are version 2's, byte for byte; only the predictor differs.
+//   'A' 25 (bpv | slod << 4) c | u32 n | u32 payload_len | u32 cells[16] | u32 S | u32 n_chunks | u16 p0[nctx] |
+//   u32 words[n_chunks] | chunk payloads      (n == 0: the 12-byte head; version 26: byte 3 = c | m << 4 as version 11)
+// Coordinates are biased by 32768 >> slod; the lattice is [0, 65536 >> slod) per axis.
+//   candidates of i > 0   s = s(i), P its biased coordinates, u = P >> s, C = P >> (s + 1).  For each o in {-1, 0, 1}^3
+//                         whose cell C + o of side 2^(s + 1) lies inside the lattice (every axis: 0 <= C + o and
+//                         (C + o) << (s + 1) below the lattice's side), j(o) = the frame's Morton-first point inside that
+//                         cell, if it holds one: one lower bound over the sorted keys.  o = 0 is version 2's first(i) and
+//                         always exists.  Every candidate was introduced at a size >= s + 1; its Morton index may be
+//                         above i
+//   choice                d(o) = |(P_j >> s) - u|^2, an integer in 1 .. 27 (never 0: i and j are the first points of
+//                         different cells of side 2^s).  The up to three candidates with the smallest (d, Morton index
+//                         of j) are kept, each with the weight w = floor(65536 / d)
+//   predictor             per channel p = floor((2 sum(w v_j) + sum(w)) / (2 sum(w))), in 64-bit integers (three weights
+//                         of 65536 times a uint16 do not fit 32 bits)
+//   residual              r = ((v_i - p + h) & mask) - h; point 0 is coded against 0
+// The residuals go in introduction order through version 2's coder (no prediction inside the run; contexts = channel,
+// bucket of the channel's previous residual in the lane's run, position).  Version 26: the cross rule above applied to
+// these residuals.  Level of detail k: a point present at level k has s >= k, and u, C, the candidate cells and d are
+// functions of P >> s and P >> (s + 1), which the cells P >> k give; the candidates' values are exact, the kind being
+// lossless.  So a decoder runs the same rule on the cells of its geometry, biased by 32768 >> (slod + k), the sizes
+// 16 down to 0 one after the other (a point's candidates are all of larger sizes); row j is the value of the
+// Morton-first point of cell j, the shortest prefix is version 2's.  tests/attr_nbr_ref.py restates both kinds in numpy.
 #pragma once
 #include <stdint.h>
 
@@ -84,7 +111,7 @@ ATTR_HD static inline int attr_positions(int bpv) { return 16 * bpv; }
 ATTR_HD static inline int attr_contexts(int bpv, int c) { return c * kAttrBuckets * attr_positions(bpv); }
 
 struct AttrInfo {
-  int version;          // 1 | 4 | 8 | 13 (attr_parse_kind), 2 | 7 | 11 | 14 (attr2_parse_kind)
+  int version;          // 1 | 4 | 8 | 13 (attr_parse_kind), 2 | 7 | 11 | 14 | 25 | 26 (attr2_parse_kind)
   uint32_t max_error;   // e of versions 4, 7, 13 and 14 (0: lossless, and every blob without points)
   int cross;            // m of the cross-channel kinds (bit ch - 1: channel ch is coded against ch - 1), 0: a plain kind
   int bpv, c, nctx;
@@ -122,6 +149,20 @@ static inline bool attr_kind(int version, bool* scalable, bool* nl, bool* cross)
 }
 ATTR_HD static inline int attr_version(bool scalable, bool nl, bool cross) {
   return cross ? (scalable ? (nl ? 14 : 11) : (nl ? 13 : 8)) : (scalable ? (nl ? 7 : 2) : (nl ? 4 : 1));
+}
+
+// the ten lossless-or-bounded kinds: the eight above and versions 25 / 26, which are scalable, lossless, and *nbr
+constexpr int kAttrNVersion = 25, kAttrNXVersion = 26;
+static inline bool attr_kind(int version, bool* scalable, bool* nl, bool* cross, bool* nbr) {
+  *nbr = version == kAttrNVersion || version == kAttrNXVersion;
+  if (!*nbr) return attr_kind(version, scalable, nl, cross);
+  *scalable = true;
+  *nl = false;
+  *cross = version == kAttrNXVersion;
+  return true;
+}
+ATTR_HD static inline int attr_version(bool scalable, bool nl, bool cross, bool nbr) {
+  return nbr ? (cross ? kAttrNXVersion : kAttrNVersion) : attr_version(scalable, nl, cross);
 }
 
 // byte 3 of a head: c channels (1 .. 4) and, in a cross kind, the mask m above them (m != 0, bits below c - 1 only); a
@@ -306,10 +347,12 @@ static inline int attr_lod_plan(const uint8_t* b, int64_t len, int lod, bool nee
 // blob, whole and nothing behind it); otherwise (pcc_attr_lod_info) the bytes must only reach what the plan is computed
 // from, the last needed chunk's length table.  Nothing beyond b[len) is read.
 // Version 2 (nl = false) or 7 (nl = true, x = 4 bytes of max_error in front of cells[16]); cross: their cross-channel
-// forms 11 and 14, the mask above the channels of byte 3.
+// forms 11 and 14, the mask above the channels of byte 3.  nbr (with nl = false): versions 25 and 26, version 2's and
+// 11's layout under their own version bytes.
 static inline int attr2_parse_kind(const uint8_t* b, int64_t len, int lod, bool need_all, bool nl, Attr2Info* o, Attr2Plan* pl,
-                                   bool cross = false) {
-  const int tag = attr_version(true, nl, cross), x = nl ? 4 : 0;
+                                   bool cross = false, bool nbr = false) {
+  const int tag = attr_version(true, nl, cross, nbr), x = nl ? 4 : 0;
+  ATTR2_REQUIRE(!(nbr && nl), "attribute blob v%d: no near-lossless form", tag);
   ATTR2_REQUIRE(b && len >= kAttrHead && b[0] == 'A' && b[1] == tag, "attribute blob v%d: bad header (len=%lld)", tag, (long long)len);
   o->version = tag;
   o->max_error = 0;

@@ -1148,6 +1148,72 @@ int pcc_attr_encode_frames_cross(pcc_ctx* ctx, int version, const void* d_values
                                  int64_t cap, int64_t* h_offsets);
 int pcc_attr_cross_mask(const uint8_t* h_in, int64_t len, int32_t* h_mask);
 
+/* Lossless attributes predicted from 3-D neighbours: attribute blob version
+ * 25 and its cross-channel form 26.  Versions 1 and 2 predict along one
+ * dimension (the Morton run; the one Morton-first point of the next larger
+ * cell); this kind looks sideways in space and is about a tenth smaller on
+ * colour.  Layout, chunks, coder, contexts, model, introduction order,
+ * cells[], slod and the level-of-detail prefixes are version 2's, byte for
+ * byte; only the predictor differs.  25 = 11001b and 26 = 11010b keep the odd
+ * parity of the eleven bytes 1, 2, 4, 7, 8, 11, 13, 14, 19, 21, 22 and differ
+ * from each of them in at least two bits.
+ *
+ * The rule (tests/attr_nbr_ref.py restates it in numpy).  Notation is version
+ * 2's: n distinct points in Morton order, 48-bit keys, size of introduction
+ * s(i), cells[], introduction order, slod.  Coordinates are biased by
+ * 32768 >> slod; the lattice is [0, 65536 >> slod) per axis.
+ *   Head: 'A' 25 (bpv | slod << 4) c | n | payload_len | cells[16] | S |
+ *     n_chunks | p0 | words[] | chunks — version 2's with another version
+ *     byte.  Version 26 puts the mask above the channels in byte 3 (c | m <<
+ *     4) exactly as 11 does over 2.  An empty frame is the 12-byte head.
+ *   Candidates of point i > 0: s = s(i), P its biased coordinates, u = P >> s,
+ *     C = P >> (s + 1).  For each o in {-1, 0, 1}^3 whose cell C + o of side
+ *     2^(s + 1) lies inside the lattice (per axis 0 <= C + o and
+ *     (C + o) << (s + 1) below the lattice's side), j(o) is the frame's
+ *     Morton-first point inside that cell, if the cell holds one: one lower
+ *     bound over the sorted keys.  o = 0 is version 2's first(i) and always
+ *     exists.  Every candidate was introduced at a size >= s + 1; its Morton
+ *     index may be above i.
+ *   Choice: d(o) = |(P_j >> s) - u|^2, an integer in 1 .. 27, never 0 (i and j
+ *     are the first points of different cells of side 2^s).  The up to three
+ *     candidates with the smallest (d, Morton index of j) are kept, each with
+ *     the weight w = floor(65536 / d).
+ *   Predictor per channel: p = floor((2 sum(w v_j) + sum(w)) / (2 sum(w))) in
+ *     64-bit integers (three weights of 65536 times a uint16 value do not fit
+ *     32 bits).  Residual r = ((v_i - p + h) & mask) - h, h = 2^(8 bpv - 1);
+ *     point 0 is coded against 0.
+ *   Order and coding: the residuals go in introduction order through version
+ *     2's coder — no prediction inside the run; contexts = channel, bucket of
+ *     the channel's previous residual in the lane's run, position.
+ *   Version 26: the cross rule above applied to these residuals.
+ *   Level of detail k: a point present at level k has s >= k, and u, C, the
+ *     candidate cells and d are functions of P >> s and P >> (s + 1), which
+ *     the cells P >> k give; the candidates' values are exact, because the
+ *     kind is lossless.  So the decoder runs the same rule on its geometry's
+ *     cells, biased by 32768 >> (slod + k) (slod + k <= 15), reconstructing
+ *     the sizes 16 down to 0 one after the other.  Row j is the value of the
+ *     Morton-first point of cell j, as version 2 defines it; the shortest
+ *     prefix is version 2's formula.
+ *   _encode_frames_nbr : pcc_attr_encode_frames_cross's arguments without
+ *     version and max_error; h_cross may be NULL (every frame version 25);
+ *     else a frame with m != 0 is version 26.  n_kept = -1: no row dropped.
+ *     The other encode entry points refuse what they refused before.
+ *   pcc_attr_decode_frames_lod and pcc_attr_lod_info read 25 and 26 beside
+ *     2, 7, 11 and 14, still one version per call; pcc_attr_info reports the
+ *     version byte with scalable = 1 and max_error = 0, pcc_attr_cross_mask
+ *     the mask of a version-26 head.  A damaged blob gives PCC_E_STREAM or
+ *     wrong values: every candidate index comes from a search over the
+ *     decoder's own cells, none from the stream. */
+int pcc_attr_encode_frames_nbr(pcc_ctx* ctx, const void* d_values,
+                               const int64_t* h_value_offsets,
+                               const int32_t* h_format, const int64_t* h_rows,
+                               const int64_t* h_points, int n_frames,
+                               const uint32_t* d_perm,
+                               const uint32_t* d_run_starts, int64_t n_unique,
+                               int64_t n_kept, const uint64_t* d_keys,
+                               int key_shift, const int32_t* h_cross /* may be NULL */,
+                               uint8_t* h_out, int64_t cap, int64_t* h_offsets);
+
 /* Transform-coded attributes: attribute blob version 19, a ninth kind, lossy,
  * for rates below about a byte per point, where a near-lossless predictive
  * coder (a staircase on the prediction error) is the wrong tool.  An integer

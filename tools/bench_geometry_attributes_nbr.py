@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Attributes predicted from 3-D neighbours (attribute blob versions 25 / 26) beside the other lossless kinds: bytes,
+bits per value and times of versions 1, 2 and 25 (and of their cross-channel forms 8, 11 and 26 on RGB) for
+  - the intensity of KITTI-like sweeps (workloads.lidar_sweep(seed=s), lidar_intensity(seed=s)),
+  - the RGB of the 1M-point room (workloads.room()), the same frame B times,
+  - a GOP of the recorded ZED frames (tests/golden/zed_seq25.npz, frames 0 .. B - 1),
+with B = 1 and 8 frames per call.  In one process and alternating between the kinds, ms per call (median of --reps
+behind --warmup calls, with the fastest and slowest): GeometryCodec.compress(attributes=) and decompress at lod 0, and
+for the scalable kinds decompress of the shortest prefixes (geometry and attributes) at lod 1 .. 3.  Host arrays in,
+host arrays out.  Every kind's decode at lod 0 is checked once against version 1's.
+
+--kinds 1,2 (for a build without versions 25 / 26) restricts the kinds.  Writes one JSON object (stdout, and --out)."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = "demo-learned-point-cloud-compression_amd"
+LODS = (1, 2, 3)
+# version: the keywords of compress that write it
+KINDS = {1: {}, 2: {"scalable": True}, 25: {"predictor": "neighbours"},
+         8: {"cross_channel": True}, 11: {"scalable": True, "cross_channel": True}, 26: {"predictor": "neighbours", "cross_channel": True}}
+SCALABLE = (2, 11, 25, 26)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="1,8")
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--kinds", default="1,2,25,8,11,26")
+    ap.add_argument("--inputs", default="sweep_intensity,room_rgb,zed_gop_rgb")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    pkg = importlib.import_module(PKG)
+    wl = importlib.import_module(PKG + ".workloads")
+    G = pkg.GeometryCodec
+    codec = G()
+    batches = [int(b) for b in args.batches.split(",")]
+    kinds = [int(k) for k in args.kinds.split(",")]
+    top = max(batches)
+    inputs = {}
+    if "sweep_intensity" in args.inputs:
+        sweeps = [wl.lidar_sweep(seed=s)["points"] for s in range(top)]
+        inputs["sweep_intensity"] = (sweeps, [wl.lidar_intensity(p, seed=s) for s, p in enumerate(sweeps)])
+    if "room_rgb" in args.inputs:
+        room = wl.room(1_000_000, seed=0)
+        inputs["room_rgb"] = ([room["points"]] * top, [np.rint(255 * room["colors"]).astype(np.uint8)] * top)
+    if "zed_gop_rgb" in args.inputs:
+        with np.load(os.path.join(ROOT, "tests", "golden", "zed_seq25.npz")) as f:
+            inputs["zed_gop_rgb"] = ([f[f"points_{i}"].astype(np.int32) for i in range(top)], [f[f"colors_u8_{i}"] for i in range(top)])
+    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "kinds": kinds, "inputs": {}}
+    for name, (frames, attrs) in inputs.items():
+        rgb = attrs[0].ndim == 2 and attrs[0].shape[1] > 1
+        mine = [k for k in kinds if rgb or k in (1, 2, 25)]
+        out = {"B": {}}
+        for B in batches:
+            fr, at = frames[:B], attrs[:B]
+            blobs, pre, jobs = {}, {}, {}
+            want = None
+            for k in mine:
+                g, blobs[k] = codec.compress(fr, attributes=at, **KINDS[k])
+                vals = codec.decompress(g, blobs[k])[1]
+                want = vals if want is None else want
+                assert all(np.array_equal(x, y) for x, y in zip(vals, want)), (name, k)
+                jobs[f"enc_v{k}"] = (lambda k: lambda: codec.compress(fr, attributes=at, **KINDS[k]))(k)
+                jobs[f"dec_v{k}"] = (lambda k: lambda: codec.decompress(g, blobs[k]))(k)
+                for lod in LODS if k in SCALABLE else ():
+                    pre[k, lod] = ([b[:G.lod_info(b, lod)[0]] for b in g], [b[:G.attr_lod_info(b, lod)[0]] for b in blobs[k]])
+                    jobs[f"dec_v{k}_lod{lod}"] = (lambda k, lod: lambda: codec.decompress(*pre[k, lod], lod=lod))(k, lod)
+            names = list(jobs)
+            t = {n: [] for n in names}
+            for it in range(args.warmup + args.reps):
+                for n in (names if it % 2 == 0 else names[::-1]):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    jobs[n]()
+                    dt = time.perf_counter() - t0
+                    if it >= args.warmup:
+                        t[n].append(dt)
+            values = sum(int(np.frombuffer(b[4:8], "<u4")[0]) for b in blobs[mine[0]]) * (attrs[0].shape[1] if attrs[0].ndim == 2 else 1)
+            r = {"points": values // (attrs[0].shape[1] if attrs[0].ndim == 2 else 1), "geometry_bytes": sum(len(b) for b in g),
+                 "ms": {n: round(1e3 * float(np.median(v)), 4) for n, v in t.items()},
+                 "spread_ms": {n: [round(1e3 * min(v), 4), round(1e3 * max(v), 4)] for n, v in t.items()},
+                 "bytes": {f"v{k}": sum(len(b) for b in blobs[k]) for k in mine},
+                 "bits_per_value": {f"v{k}": round(8 * sum(len(b) for b in blobs[k]) / values, 4) for k in mine},
+                 "prefix_bytes": {f"v{k}_lod{lod}": sum(len(b) for b in pre[k, lod][1]) for (k, lod) in pre}}
+            out["B"][str(B)] = r
+            print(name, f"B={B}", json.dumps(r), flush=True)
+        res["inputs"][name] = out
+    codec.close()
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
