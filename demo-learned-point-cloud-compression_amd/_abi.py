@@ -108,6 +108,7 @@ PROTOTYPES = {
     "pcc_attr_encode_frames_cross": (i32, _AEV + [i64, vp, i32, i32, pi32, vp, i64, pi64]),
     "pcc_attr_cross_mask": (i32, [vp, i64, pi32]),
     "pcc_attr_encode_frames_nbr": (i32, _AE + [i64, vp, i32, pi32, vp, i64, pi64]),
+    "pcc_attr_encode_frames_nbr_nl": (i32, _AE + [i64, vp, i32, i32, pi32, vp, i64, pi64]),
     "pcc_attr_encode_frames_transform": (i32, _AE + [i64, vp, i32, i32, vp, i64, pi64]),
     "pcc_attr_qstep": (i32, [vp, i64, pi32]),
     "pcc_attr_encode_frames_transform2": (i32, _AE + [i64, vp, i32, pi32, i32, vp, i64, pi64]),

@@ -80,6 +80,12 @@
 // place of k_a2_place, k_a_dec<true> (k_ax_inv), then k_an_recon once per occupied size of introduction, 16 down to 0.
 // tests/attr_nbr_ref.py restates both kinds in numpy.
 //
+// Versions 28 and 31 (attr_blob.h has the rule): version 7's stream over the indices of the same predictor in a closed
+// loop, over decoded values.  The kernels are attr_nbr.h's.  Encoder: version 7's launches with k_anl_plan in place of
+// k_a2_place<true, true> and k_anl_quant, once per size of introduction 16 down to 0, in place of k_a7_quant (k_ax_fwd<false>
+// for a frame of version 31); k_a_pack writes version 7's / 14's head and a_enc_emit sets the version byte.  Decoder: the
+// launches of 25 / 26 with k_anl_recon.  tests/attr_nbr_nl_ref.py restates both kinds in numpy.
+//
 // Host side: the kinds share one encode sequence (a_encode_frames over an AEncKind, the entry point's kind resolved
 // once) and one decode-call skeleton (ADecCall: accounting, rows, layout, upload, status) under the three decoders, each
 // of which keeps its parser, its side tables, its arena arrays and its kernels; DESIGN.md, "attr.hip: one encode path,
@@ -1494,7 +1500,7 @@ __global__ __launch_bounds__(256) void k_ar_gather(const ARPick* __restrict__ pi
 
 }  // namespace
 
-#include "attr_nbr.h"   // versions 25 and 26: k_an_place, k_an_plan, k_an_recon
+#include "attr_nbr.h"   // versions 25, 26, 28 and 31: k_an_place, k_an_plan, k_an_recon; k_anl_plan, k_anl_quant, k_anl_recon
 
 static inline int64_t a_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 static inline size_t merged_b_of(int64_t vals) { return pcc_align((size_t)vals * 2); }
@@ -1645,7 +1651,8 @@ struct AEncKind {
   const int32_t* h_qsteps;   // version 21: q[4]
   int colour;                // version 21: 0 | 1
   int K;                     // version 22: the deepest cut (0: another kind)
-  bool nbr = false;          // versions 25 / 26: version 2's call with k_an_place for k_a2_place and their version bytes
+  bool nbr = false;          // versions 25 / 26: version 2's call with k_an_place for k_a2_place and their version bytes;
+                             // with nl, versions 28 / 31: version 7's call with k_anl_plan and k_anl_quant size by size
   bool keyed() const { return v2 || tr; }   // d_keys and key_shift are read
 };
 static AEncKind a_kind_plain(int version, int64_t n_kept, int max_error, const int32_t* h_cross) {
@@ -1656,6 +1663,13 @@ static AEncKind a_kind_plain(int version, int64_t n_kept, int max_error, const i
 static AEncKind a_kind_nbr(int64_t n_kept, const int32_t* h_cross) {
   AEncKind k = a_kind_plain(2, n_kept, 0, h_cross);
   k.version = kAttrNVersion;
+  k.nbr = true;
+  return k;
+}
+// versions 28 and 31: version 7's kind under the neighbour predictor's closed loop
+static AEncKind a_kind_nbr_nl(int64_t n_kept, int max_error, const int32_t* h_cross) {
+  AEncKind k = a_kind_plain(2, n_kept, max_error, h_cross);
+  k.version = kAttrNLVersion;
   k.nbr = true;
   return k;
 }
@@ -1832,7 +1846,8 @@ static int a_enc_emit(const char* who, const AEncKind& k, pcc_ctx* ctx, const in
     if (o.off_of[(size_t)f] >= 0) {
       memcpy(dst, (const uint8_t*)ctx->stage + o.off_of[(size_t)f], (size_t)o.len_of[(size_t)f]);
       // versions 25 / 26: k_a_pack wrote version 2's / 11's head, which is theirs but for the version byte
-      if (k.nbr) dst[1] = (uint8_t)attr_version(true, false, dst[1] == attr_version(true, false, true), true);
+      // (versions 28 / 31: version 7's / 14's)
+      if (k.nbr) dst[1] = (uint8_t)attr_version(true, k.nl, dst[1] == attr_version(true, k.nl, true), true);
     } else {
       const int32_t m = k.h_cross ? k.h_cross[f] : 0;
       memset(dst, 0, kAttrHead);
@@ -1930,7 +1945,9 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
     const size_t order_b = v2 ? 2 * merged_b + pk_b + hist_b + bins_b : 0, nl_b = nl ? merged_b + (tr ? 1 : 2) * link_b : 0;
     const size_t x8_b = xc && !v2 && !nl ? merged_b : 0;   // version 8: the run residuals
     const size_t tr_b = (tr ? a_t_order_bytes(u, merge_blocks, nf) : 0) + (sc ? a_s_cells_bytes(u) + pcc_align((size_t)nf * 64) : 0);
-    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + order_b + nl_b + x8_b + tr_b + 8192));
+    // versions 28 / 31: the reconstructions (one more array of the merged values' size), every point's choice, 3 words
+    const size_t picks_b = pcc_align((size_t)u * 12), nbr_nl_b = k.nbr && nl ? merged_b + picks_b : 0;
+    PCC_TRY(pcc_arena_reserve(ctx, tab_b + merged_b + cnt_b + p0_b + 2 * rec_b + small_b + order_b + nl_b + x8_b + tr_b + nbr_nl_b + 8192));
     AFrame* d_tab = (AFrame*)pcc_arena_alloc(ctx, tab_b);
     uint16_t* merged = (uint16_t*)pcc_arena_alloc(ctx, merged_b);
     uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, cnt_b);
@@ -1980,10 +1997,32 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
       PCC_CHECK_LAUNCH();
       hipLaunchKernelGGL(k_a2_scan, dim3((unsigned)nf), dim3(256), 0, st, d_ord, hist, bins, cells);
       PCC_CHECK_LAUNCH();
-      if (k.nbr) {   // versions 25 / 26: the residuals against the neighbour predictor, in one pass of its own
+      if (k.nbr && !nl) {   // versions 25 / 26: the residuals against the neighbour predictor, in one pass of its own
         hipLaunchKernelGGL(k_an_place, dim3((unsigned)merge_blocks), dim3(256), 0, st, d_keys, d_ord, nf, (const uint16_t*)packed,
                            (const uint32_t*)hist, (const uint32_t*)bins, (const AFrame*)d_tab, (const uint16_t*)merged, src);
         PCC_CHECK_LAUNCH();
+        return PCC_OK;
+      }
+      if (k.nbr) {
+        // versions 28 / 31: every point's choice once (rank holds the inverse of the places), then the closed loop size
+        // by size, all frames in one grid.  The host has no count per size and does not wait for one: a frame of n
+        // points on a lattice of L bits per axis has at most min(n, 8^(L - s)) points of size s < L, point 0 alone at
+        // 16 and none between, so sizes L .. 15 are not launched and the others get a grid of that bound; the ranges
+        // themselves are the order stage's, on the device, and a block beyond a range returns at once
+        uint32_t* picks = (uint32_t*)pcc_arena_alloc(ctx, picks_b);
+        uint16_t* recon = (uint16_t*)pcc_arena_alloc(ctx, merged_b);
+        if (!picks || !recon) return PCC_E_NOMEM;
+        hipLaunchKernelGGL(k_anl_plan, dim3((unsigned)merge_blocks), dim3(256), 0, st, d_keys, d_ord, nf, (const uint16_t*)packed,
+                           (const uint32_t*)hist, (const uint32_t*)bins, rank, picks);
+        PCC_CHECK_LAUNCH();
+        const int L = 16 - key_shift / 3;
+        for (int s = kA2Bins - 1; s >= 0; --s) {
+          if (s < 16 && s >= L) continue;
+          const int64_t most = s == 16 ? 1 : (3 * (L - s) >= 27 ? n_max : std::min<int64_t>(n_max, (int64_t)1 << (3 * (L - s))));
+          hipLaunchKernelGGL(k_anl_quant, dim3(nblk(most, 256), (unsigned)nf), dim3(256), 0, st, d_ord, (const AFrame*)d_tab,
+                             (const uint32_t*)bins, s, (const uint32_t*)rank, (const uint32_t*)picks, (const uint16_t*)merged, recon, src);
+          PCC_CHECK_LAUNCH();
+        }
         return PCC_OK;
       }
       const auto place = keep ? k_a2_place<true, true> : k_a2_place<true, false>;
@@ -2005,7 +2044,7 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
       hipLaunchKernelGGL(k_a4_quant, dim3(nblk(run_threads, 256), (unsigned)nf), dim3(256), 0, st, (const uint16_t*)merged,
                          (const AFrame*)d_tab, src);
       PCC_CHECK_LAUNCH();
-    } else if (nl) {
+    } else if (nl && !k.nbr) {
       hipLaunchKernelGGL(k_a7_quant, dim3((unsigned)merge_blocks), dim3(256), 0, st, d_ord, nf, (const AFrame*)d_tab,
                          (const uint16_t*)merged, (const uint32_t*)rank, (const uint32_t*)first, src);
       PCC_CHECK_LAUNCH();
@@ -2032,8 +2071,8 @@ static int a_encode_frames(const char* who, const AEncKind& k, pcc_ctx* ctx, con
     };
     // by the version byte of the call's frames with a mask, where it has any, else of its plain frames
     int rc = PCC_E_ARG;
-    // (versions 25 / 26 are coded, packed and laid out as 2 / 11)
-    switch (xc ? attr_version(v2, nl, true) : (k.nbr ? 2 : k.version)) {   //   V2     NL     XC     TR
+    // (versions 25 / 26 are coded, packed and laid out as 2 / 11, versions 28 / 31 as 7 / 14)
+    switch (xc ? attr_version(v2, nl, true) : (k.nbr ? attr_version(true, nl, false) : k.version)) {   //   V2     NL     XC     TR
       case 1: rc = a_code(ACoder<false, false, false>{}); break;
       case 2: rc = a_code(ACoder<true, false, false>{}); break;
       case 4: rc = a_code(ACoder<false, true, false>{}); break;
@@ -2112,6 +2151,17 @@ extern "C" int pcc_attr_encode_frames_nbr(pcc_ctx* ctx, const void* d_values, co
   PCC_REQUIRE(n_kept >= -1, PCC_E_ARG, "pcc_attr_encode_frames_nbr: bad argument (n_kept=%lld)", (long long)n_kept);
   return a_encode_frames("pcc_attr_encode_frames_nbr", a_kind_nbr(n_kept, h_cross), ctx, d_values, h_value_offsets, h_format, h_rows,
                          h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets);
+}
+
+extern "C" int pcc_attr_encode_frames_nbr_nl(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets, const int32_t* h_format,
+                                             const int64_t* h_rows, const int64_t* h_points, int n_frames, const uint32_t* d_perm,
+                                             const uint32_t* d_run_starts, int64_t n_unique, int64_t n_kept, const uint64_t* d_keys,
+                                             int key_shift, int max_error, const int32_t* h_cross, uint8_t* h_out, int64_t cap,
+                                             int64_t* h_offsets) {
+  PCC_REQUIRE(n_kept >= -1 && max_error >= 1, PCC_E_ARG, "pcc_attr_encode_frames_nbr_nl: bad argument (n_kept=%lld max_error=%d)",
+              (long long)n_kept, max_error);
+  return a_encode_frames("pcc_attr_encode_frames_nbr_nl", a_kind_nbr_nl(n_kept, max_error, h_cross), ctx, d_values, h_value_offsets,
+                         h_format, h_rows, h_points, n_frames, d_perm, d_run_starts, n_unique, d_keys, key_shift, h_out, cap, h_offsets);
 }
 
 extern "C" int pcc_attr_encode_frames_transform(pcc_ctx* ctx, const void* d_values, const int64_t* h_value_offsets,
@@ -2600,8 +2650,8 @@ static int a_wrap_error(const char* who, int rc) {
 // host only: the version byte and byte 3 of a head, checked: its kind, channels and mask
 static int a_head_kind(const char* who, const uint8_t* h_in, int64_t len, bool* scal, bool* nl, bool* xc, int* c, int* m) {
   PCC_REQUIRE(h_in && len >= kAttrHead && h_in[0] == 'A', PCC_E_STREAM, "%s: not an attribute blob (len=%lld)", who, (long long)len);
-  bool nbr;   // versions 25 / 26 stand beside 2 / 11 here: scalable, lossless, 26 with a mask
-  PCC_REQUIRE(attr_kind(h_in[1], scal, nl, xc, &nbr), PCC_E_STREAM, "%s: attribute blob version %d", who, (int)h_in[1]);
+  bool nbr;   // versions 25 / 26 stand beside 2 / 11 here (scalable, lossless, 26 with a mask), 28 / 31 beside 7 / 14
+  PCC_REQUIRE(attr_kind12(h_in[1], scal, nl, xc, &nbr), PCC_E_STREAM, "%s: attribute blob version %d", who, (int)h_in[1]);
   const int bpv = *scal ? h_in[2] & 15 : h_in[2];
   PCC_REQUIRE((bpv == 1 || bpv == 2) && attr_channels(h_in[3], *xc, c, m), PCC_E_STREAM, "%s: %d bytes per value, %d channels%s", who,
               bpv, *c, *xc ? ", or their mask" : "");
@@ -3130,7 +3180,7 @@ extern "C" int pcc_attr_lod_info(const uint8_t* h_in, int64_t len, int lod, int6
     PCC_REQUIRE(!attr_t_kind(h_in[1]) && !attr_c_kind(h_in[1]), PCC_E_ARG,
                 "pcc_attr_lod_info: attribute blob version %d (a transform-coded blob has no level-of-detail prefixes: the weights of its "
                 "transform need every point)", (int)h_in[1]);
-    PCC_REQUIRE(attr_kind(h_in[1], &scal, &nl, &xc, &nbr) && scal, PCC_E_ARG,
+    PCC_REQUIRE(attr_kind12(h_in[1], &scal, &nl, &xc, &nbr) && scal, PCC_E_ARG,
                 "pcc_attr_lod_info: attribute blob version %d (levels of detail are a property of version 2)", (int)h_in[1]);
     Attr2Info o;
     rc = attr2_parse_kind(h_in, len, lod, false, nl, &o, &pl, xc, nbr);
@@ -3164,10 +3214,11 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
   // the blobs of a call are of one version, the first blob's: 2, or 7 (k_a2_walk<true> scales and clamps), or their
   // cross-channel forms 11 and 14 (k_ax_inv between the decoder and the walk), or 25 or its cross form 26 (k_an_plan for
   // k_a2_place, and k_an_recon size by size for the walk)
-  const int kinds[6] = {2, 7, 11, 14, kAttrNVersion, kAttrNXVersion};
+  // (28 / 31: the launches of 25 / 26 with k_anl_recon, which scales and clamps as the walk of version 7 does)
+  const int kinds[8] = {2, 7, 11, 14, kAttrNVersion, kAttrNXVersion, kAttrNLVersion, kAttrNLXVersion};
   const int mine = a_call_version(h_blobs[0], h_lens[0], kinds);
-  const bool nbr = mine == kAttrNVersion || mine == kAttrNXVersion;
-  const bool nl = mine == 7 || mine == 14, xc = mine == 11 || mine == 14 || mine == kAttrNXVersion;
+  bool scal, nl, xc, nbr;
+  attr_kind12(mine, &scal, &nl, &xc, &nbr);
   ADecCall d = a_dec_call(who, ctx, h_blobs, n_frames, d_out, h_out, cap_bytes, h_out_offsets, h_format);
   std::vector<Attr2Info> info((size_t)n_frames);
   for (int f = 0; f < n_frames; ++f) {
@@ -3253,7 +3304,7 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
         most = std::max<int64_t>(most, s == 16 ? 1 : (j > kAttrMaxLod ? 0 : c[j] - (j < kAttrMaxLod ? c[j + 1] : 1)));
       }
       if (most == 0) continue;
-      hipLaunchKernelGGL(k_an_recon, dim3(nblk(most, 256), (unsigned)nf), dim3(256), 0, st, d_ord, d_tab, (const uint32_t*)bins, s,
+      hipLaunchKernelGGL((nl ? k_anl_recon : k_an_recon), dim3(nblk(most, 256), (unsigned)nf), dim3(256), 0, st, d_ord, d_tab, (const uint32_t*)bins, s,
                          (const uint32_t*)rank, (const uint32_t*)first, (const uint8_t*)resid, d.out, status);
       PCC_CHECK_LAUNCH();
     }
@@ -3273,6 +3324,7 @@ extern "C" int pcc_attr_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_
     return PCC_OK;
   };
   return a_dec_finish(d, counts, (size_t)nf * 17 * 4, 0, (size_t)nf * 16 * 4,
-                      nl ? ", 8 = predictor chain, 16 = reconstruction out of range" : (nbr ? ", 8 = index outside the frame" : ", 8 = predictor chain"),
+                      nbr ? (nl ? ", 8 = index outside the frame, 16 = reconstruction out of range" : ", 8 = index outside the frame")
+                          : (nl ? ", 8 = predictor chain, 16 = reconstruction out of range" : ", 8 = predictor chain"),
                       counts_match);
 }

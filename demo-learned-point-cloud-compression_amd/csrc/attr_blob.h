@@ -1,7 +1,7 @@
 // attr_blob.h — the header of an attribute blob (attr.hip), parsed and checked on the host before anything is reserved
 // or launched.  Plain C++ (no HIP): tests/fuzz/fuzz_attr_header.cpp, fuzz_attr2_header.cpp, fuzz_attr_nl_header.cpp,
 // fuzz_attr_cross_header.cpp, fuzz_attr_transform_header.cpp, fuzz_attr_colour_header.cpp,
-// fuzz_attr_scalable_header.cpp and fuzz_attr_nbr_header.cpp put it under the sanitizers.
+// fuzz_attr_scalable_header.cpp, fuzz_attr_nbr_header.cpp and fuzz_attr_nbr_nl_header.cpp put it under the sanitizers.
 //
 // Every size the decoder reserves or reads follows from what this parse accepted: the chunk table must add up to the
 // blob's own length, so a header cannot announce more words than the blob holds; n is bounded by the chunks
@@ -88,6 +88,23 @@
 // lossless.  So a decoder runs the same rule on the cells of its geometry, biased by 32768 >> (slod + k), the sizes
 // 16 down to 0 one after the other (a point's candidates are all of larger sizes); row j is the value of the
 // Morton-first point of cell j, the shortest prefix is version 2's.  tests/attr_nbr_ref.py restates both kinds in numpy.
+//
+// Bounded-error neighbour kinds, versions 28 and 31 (attr2_parse_kind with nbr = true and nl = true; 31 is the cross form
+// of 28 as 14 is of 7; 28 = 11100b and 31 = 11111b keep the odd parity of the thirteen bytes above): |v - v^| <= e,
+// scalable.  The layout is version 7's (14's), byte for byte, under the version byte: max_error behind payload_len,
+// cells[16], S, n_chunks, p0, chunk table, chunks, slod in byte 2, the mask in the high nibble of byte 3; the prefix rule
+// is version 7's.  Candidates, d, the tie-break on (d, Morton index) and w = floor(65536 / d) are version 25's: functions
+// of the geometry alone.  q = 2 e + 1, mask = 2^(8 bpv) - 1.
+//   predictor             point 0: p = 0.  i > 0: per channel p = floor((2 sum(w v^_j) + sum(w)) / (2 sum(w))) over its
+//                         candidates' DECODED values v^_j (clamped, what a decoder returns), in 64-bit integers
+//   index                 j_i = sgn(d) floor((|d| + e) / q), d = v_i - p: no wrap (|d| <= mask, so |j_i| < 2^(8 bpv - 1))
+//   decoded value         v^_i = clip(p + j_i q, 0, mask); v_i is in range, so |v_i - v^_i| <= e
+// A closed loop: the encoder forms v^ size by size, 16 down to 0, since every candidate was introduced at a larger size.
+// The j go in introduction order through version 7's coder; version 31 applies the cross rule to them.  Level of detail
+// k: a point present at level k has s >= k and its candidates sizes >= s + 1, so a decoder at a cut forms the same p
+// from its cells alone; row j is v^ of the Morton-first point of cell j, within e of the row versions 25 / 26 return at
+// that lod.  A decoder forms p + j q in 64 bits (a damaged uint16 stream at e = 32767 reaches 2^31), clamps, and reports
+// a sum outside [-e, mask + e], which no encoder's reconstruction is.  tests/attr_nbr_nl_ref.py restates both in numpy.
 #pragma once
 #include <stdint.h>
 
@@ -111,8 +128,8 @@ ATTR_HD static inline int attr_positions(int bpv) { return 16 * bpv; }
 ATTR_HD static inline int attr_contexts(int bpv, int c) { return c * kAttrBuckets * attr_positions(bpv); }
 
 struct AttrInfo {
-  int version;          // 1 | 4 | 8 | 13 (attr_parse_kind), 2 | 7 | 11 | 14 | 25 | 26 (attr2_parse_kind)
-  uint32_t max_error;   // e of versions 4, 7, 13 and 14 (0: lossless, and every blob without points)
+  int version;          // 1 | 4 | 8 | 13 (attr_parse_kind), 2 | 7 | 11 | 14 | 25 | 26 | 28 | 31 (attr2_parse_kind)
+  uint32_t max_error;   // e of versions 4, 7, 13, 14, 28 and 31 (0: lossless, and every blob without points)
   int cross;            // m of the cross-channel kinds (bit ch - 1: channel ch is coded against ch - 1), 0: a plain kind
   int bpv, c, nctx;
   int64_t n, S, nc;
@@ -161,8 +178,21 @@ static inline bool attr_kind(int version, bool* scalable, bool* nl, bool* cross,
   *cross = version == kAttrNXVersion;
   return true;
 }
+// versions 28 / 31, the bounded-error forms of 25 / 26 (nbr with nl): scalable too
+constexpr int kAttrNLVersion = 28, kAttrNLXVersion = 31;
 ATTR_HD static inline int attr_version(bool scalable, bool nl, bool cross, bool nbr) {
-  return nbr ? (cross ? kAttrNXVersion : kAttrNVersion) : attr_version(scalable, nl, cross);
+  return nbr ? (nl ? (cross ? kAttrNLXVersion : kAttrNLVersion) : (cross ? kAttrNXVersion : kAttrNVersion)) : attr_version(scalable, nl, cross);
+}
+// the two bounded-error neighbour kinds have a predicate of their own, and the twelve kinds one over both: the
+// predicates above answer for their eight and ten bytes as before
+static inline bool attr_nbr_nl_kind(int version, bool* cross) {
+  *cross = version == kAttrNLXVersion;
+  return version == kAttrNLVersion || version == kAttrNLXVersion;
+}
+static inline bool attr_kind12(int version, bool* scalable, bool* nl, bool* cross, bool* nbr) {
+  if (!attr_nbr_nl_kind(version, cross)) return attr_kind(version, scalable, nl, cross, nbr);
+  *scalable = *nl = *nbr = true;
+  return true;
 }
 
 // byte 3 of a head: c channels (1 .. 4) and, in a cross kind, the mask m above them (m != 0, bits below c - 1 only); a
@@ -347,12 +377,11 @@ static inline int attr_lod_plan(const uint8_t* b, int64_t len, int lod, bool nee
 // blob, whole and nothing behind it); otherwise (pcc_attr_lod_info) the bytes must only reach what the plan is computed
 // from, the last needed chunk's length table.  Nothing beyond b[len) is read.
 // Version 2 (nl = false) or 7 (nl = true, x = 4 bytes of max_error in front of cells[16]); cross: their cross-channel
-// forms 11 and 14, the mask above the channels of byte 3.  nbr (with nl = false): versions 25 and 26, version 2's and
-// 11's layout under their own version bytes.
+// forms 11 and 14, the mask above the channels of byte 3.  nbr: versions 25 and 26 (nl = false) and 28 and 31 (nl = true),
+// the layouts of 2, 11, 7 and 14 under their own version bytes.
 static inline int attr2_parse_kind(const uint8_t* b, int64_t len, int lod, bool need_all, bool nl, Attr2Info* o, Attr2Plan* pl,
                                    bool cross = false, bool nbr = false) {
   const int tag = attr_version(true, nl, cross, nbr), x = nl ? 4 : 0;
-  ATTR2_REQUIRE(!(nbr && nl), "attribute blob v%d: no near-lossless form", tag);
   ATTR2_REQUIRE(b && len >= kAttrHead && b[0] == 'A' && b[1] == tag, "attribute blob v%d: bad header (len=%lld)", tag, (long long)len);
   o->version = tag;
   o->max_error = 0;

@@ -1,5 +1,6 @@
-// attr_nbr.h — the kernels of attribute blob versions 25 and 26 (attr_blob.h states the rule): lossless values in
-// version 2's introduction order, each predicted from up to three Morton-first points of the coarser cells around it.
+// attr_nbr.h — the kernels of attribute blob versions 25, 26, 28 and 31 (attr_blob.h states the rules).  25 / 26: lossless
+// values in version 2's introduction order, each predicted from up to three Morton-first points of the coarser cells
+// around it; 28 / 31, at the end of this comment, their bounded-error forms.
 // Included by attr.hip behind its own kernels, whose frame rows (AFrame, ADFrame, A2Order), order stage (k_a2_size,
 // k_a2_scan) and value accessors (a_load, a_store) it uses; nothing in here is launched for another kind.
 //
@@ -10,6 +11,11 @@
 // k_a_dec<true> (and k_ax_inv), then k_an_recon once per size of introduction 16 .. 0 that holds a point in any frame of
 // the call, over that size's range of the introduction order: a point's candidates are all of larger sizes, so every
 // value it reads was written by an earlier launch.  Every wait is a kernel boundary.
+//
+// Versions 28 and 31, their bounded-error forms (a closed loop: the predictor runs over decoded values).  Encoder:
+// k_anl_plan behind the order stage keeps every point's choice as k_an_plan does, then k_anl_quant once per size of
+// introduction, 16 down to 0, quantises that size against the reconstructions of the larger sizes and writes its own.
+// Decoder: the launches of 25 / 26 with k_anl_recon, k_an_recon's body with the index scaled and the sum clamped.
 #pragma once
 
 namespace {
@@ -136,10 +142,16 @@ __global__ __launch_bounds__(256) void k_an_plan(const uint64_t* __restrict__ ke
 // host sized the grid from.  value = (predictor of the kept choice over the values written so far + residual) & mask,
 // to the cell's row of out.  resid_all / out_all: the frames' [m][c] values of bpv bytes at out_off, residuals in
 // introduction order / values in Morton order.  status |= 8 where an index is outside the frame
-__global__ __launch_bounds__(256) void k_an_recon(const A2Order* __restrict__ tab, const ADFrame* __restrict__ ftab,
-                                                  const uint32_t* __restrict__ bins, int s, const uint32_t* __restrict__ inv,
-                                                  const uint32_t* __restrict__ picks, const uint8_t* __restrict__ resid_all,
-                                                  uint8_t* __restrict__ out_all, int32_t* __restrict__ status_all) {
+//
+// NL (versions 28 / 31): resid_all holds the indices j, sign-extended from the value width; the predictor runs over the
+// clamped values written so far, value = clip(p + j q, 0, mask) with the sum in 64 bits (|j| <= 2^15 and q < 2^16: a
+// damaged stream reaches 2^31), clamped as k_a2_walk<true> clamps; status |= 16 where the sum lies outside [-e, mask + e],
+// which no encoder's reconstruction does
+template <bool NL>
+__device__ __forceinline__ void an_recon(const A2Order* __restrict__ tab, const ADFrame* __restrict__ ftab,
+                                         const uint32_t* __restrict__ bins, int s, const uint32_t* __restrict__ inv,
+                                         const uint32_t* __restrict__ picks, const uint8_t* __restrict__ resid_all,
+                                         uint8_t* __restrict__ out_all, int32_t* __restrict__ status_all) {
   const int f = blockIdx.y;
   const A2Order& h = tab[f];
   const ADFrame& a = ftab[f];
@@ -168,9 +180,96 @@ __global__ __launch_bounds__(256) void k_an_recon(const A2Order* __restrict__ ta
   an_predict(pick, c, [&](uint32_t j, int ch) { return a_load(out + (int64_t)j * c * bpv, bpv, ch); }, p);
   const uint8_t* x = resid_all + a.out_off + r * c * bpv;
   uint8_t* o = out + (int64_t)i * c * bpv;
+  if constexpr (!NL) {
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch)
+      if (ch < c) a_store(o, bpv, (p[ch] + a_load(x, bpv, ch)) & mask, ch);
+  } else {
+    const int64_t e = a.max_error, q = 2 * e + 1;
+    bool far = false;
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch)
+      if (ch < c) {
+        const int64_t y = (int64_t)p[ch] + (int64_t)a_load_s(x, bpv, ch) * q;
+        far |= y < -e || y > (int64_t)mask + e;
+        a_store(o, bpv, (uint32_t)(y < 0 ? 0 : (y > (int64_t)mask ? (int64_t)mask : y)), ch);
+      }
+    if (far) atomicOr(status_all + f, 16);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_an_recon(const A2Order* __restrict__ tab, const ADFrame* __restrict__ ftab,
+                                                  const uint32_t* __restrict__ bins, int s, const uint32_t* __restrict__ inv,
+                                                  const uint32_t* __restrict__ picks, const uint8_t* __restrict__ resid_all,
+                                                  uint8_t* __restrict__ out_all, int32_t* __restrict__ status_all) {
+  an_recon<false>(tab, ftab, bins, s, inv, picks, resid_all, out_all, status_all);
+}
+__global__ __launch_bounds__(256) void k_anl_recon(const A2Order* __restrict__ tab, const ADFrame* __restrict__ ftab,
+                                                   const uint32_t* __restrict__ bins, int s, const uint32_t* __restrict__ inv,
+                                                   const uint32_t* __restrict__ picks, const uint8_t* __restrict__ resid_all,
+                                                   uint8_t* __restrict__ out_all, int32_t* __restrict__ status_all) {
+  an_recon<true>(tab, ftab, bins, s, inv, picks, resid_all, out_all, status_all);
+}
+
+// ---- versions 28 and 31: the encoder's closed loop ------------------------------------------------------------------
+// Encoder, over the call's keys, behind the order stage: k_an_plan's two arrays from the encoder's keys (ksh = key_shift).
+// The 27 searches of every point run here, once, at full occupancy; the launches below only gather
+__global__ __launch_bounds__(256) void k_anl_plan(const uint64_t* __restrict__ keys_all, const A2Order* __restrict__ tab, int nf,
+                                                  const uint16_t* __restrict__ packed, const uint32_t* __restrict__ hist,
+                                                  const uint32_t* __restrict__ bins, uint32_t* __restrict__ inv,
+                                                  uint32_t* __restrict__ picks) {
+  const int f = o2_find(nf, blockIdx.x, [&](int i) { return (int64_t)tab[i].blk0; });
+  const A2Order& h = tab[f];
+  const int64_t i = ((int64_t)blockIdx.x - h.blk0) * blockDim.x + threadIdx.x;
+  if (i >= h.n) return;
+  const uint32_t pk = packed[h.pt0 + i];
+  const int s = (int)(pk >> 8);
+  const int64_t r = (int64_t)bins[f * kA2Bins + s] + hist[(int64_t)blockIdx.x * kA2Bins + s] + (pk & 255u);
+  if (r < h.n) inv[h.pt0 + r] = (uint32_t)i;
+  uint32_t pick[3] = {kANone, kANone, kANone};
+  if (i > 0) an_choose(keys_all + h.pt0, h.n, i, s, h.shift, 16 - h.shift / 3, pick);
+  uint32_t* o = picks + 3 * (h.pt0 + i);
+  o[0] = pick[0];
+  o[1] = pick[1];
+  o[2] = pick[2];
+}
+
+// Encoder, size s of the introduction order, in k_an_recon's shape: frame = blockIdx.y, one thread per place of the
+// frame's range of the order stage.  The point's predictor over the reconstructions of its kept choice (all of larger
+// sizes: written by earlier launches), its index j = a_quant(v - p) to its place of idx, wrapped to the value width, and
+// its own reconstruction clip(p + j q, 0, mask) to its Morton index of recon.  merged / recon / idx: uint16 [n][c] per
+// frame at val_off; recon in Morton order, idx in introduction order.  |p + j q| < 2^18: int holds it
+__global__ __launch_bounds__(256) void k_anl_quant(const A2Order* __restrict__ tab, const AFrame* __restrict__ ftab,
+                                                   const uint32_t* __restrict__ bins, int s, const uint32_t* __restrict__ inv,
+                                                   const uint32_t* __restrict__ picks, const uint16_t* __restrict__ merged,
+                                                   uint16_t* __restrict__ recon, uint16_t* __restrict__ idx) {
+  const int f = blockIdx.y;
+  const A2Order& h = tab[f];
+  const AFrame& a = ftab[f];
+  const int64_t start = bins[f * kA2Bins + s], end = std::min<int64_t>(s > 0 ? (int64_t)bins[f * kA2Bins + s - 1] : h.n, h.n);
+  const int64_t r = start + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= end) return;
+  const uint32_t i = inv[h.pt0 + r];
+  if (i >= h.n) return;   // cannot happen: the places are a permutation of the frame's points
+  const int c = a.c, e = a.e, q = 2 * e + 1;
+  const int mask = (1 << (8 * a.bpv)) - 1;
+  uint32_t pick[3], p[4];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    pick[k] = picks[3 * (h.pt0 + i) + k];
+    if (pick[k] != kANone && (int64_t)(pick[k] & ((1u << kANIndexBits) - 1u)) >= h.n) pick[k] = kANone;   // cannot happen (an_choose)
+  }
+  uint16_t* vh = recon + a.val_off;
+  an_predict(pick, c, [&](uint32_t j, int ch) { return (uint32_t)vh[(int64_t)j * c + ch]; }, p);
+  const uint16_t* v = merged + a.val_off + (int64_t)i * c;
 #pragma unroll
   for (int ch = 0; ch < 4; ++ch)
-    if (ch < c) a_store(o, bpv, (p[ch] + a_load(x, bpv, ch)) & mask, ch);
+    if (ch < c) {
+      const int j = a_quant((int)v[ch] - (int)p[ch], e, q);
+      const int y = (int)p[ch] + j * q;
+      idx[a.val_off + r * c + ch] = (uint16_t)((uint32_t)j & (uint32_t)mask);
+      vh[(int64_t)i * c + ch] = (uint16_t)(y < 0 ? 0 : (y > mask ? mask : y));
+    }
 }
 
 }  // namespace

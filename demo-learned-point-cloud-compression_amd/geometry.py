@@ -89,6 +89,12 @@ Morton-first points of the coarser cells around its point; about a tenth smaller
     blobs, attr_blobs = codec.compress(frames, attributes=rgb, predictor="neighbours")   # with lod, cross_channel
     GeometryCodec.attr_info(attr_blobs[0])["predictor"]                                  # "neighbours"; absent from other kinds
 
+Their bounded-error forms (versions 28 and 31): version 7's layout and prefixes, the same candidates in a closed loop over
+decoded values, |v - v^| <= max_error; 11 to 25 % smaller than versions 7 and 14 on colour at max_error 1 .. 8:
+
+    blobs, attr_blobs = codec.compress(frames, attributes=rgb, predictor="bounded-neighbours", max_error=2)
+    GeometryCodec.attr_info(attr_blobs[0])      # "predictor": "neighbours", "max_error": 2, "scalable": True
+
 Transform-coded attributes (attribute blob versions 19 and 21, include/pcc.h has the rule): lossy, for rates below about
 a byte per point.  Version 21 decorrelates colour first (luma and two chroma differences) and gives every channel its own
 step: on recorded camera colour it is shorter AND closer at q = 16 than plain RGB at q = 32.
@@ -299,7 +305,7 @@ class GeometryCodec:
     @staticmethod
     def attr_lod_info(attr_blob, lod):
         """(bytes, values) of level of detail `lod` of a version-2 attribute blob (compress(..., scalable=True)), of a
-        version-25 / 26 blob (compress(..., predictor="neighbours")), or of a
+        version-25 / 26 or 28 / 31 blob (compress(..., predictor="neighbours" / "bounded-neighbours")), or of a
         version-22 blob (compress(..., qstep=q, scalable_to=K); lod <= K, PccError above):
         attr_blob[:bytes] is the shortest prefix that decompress(..., lod=lod) reads, `values` the rows it gives (the
         cells of the frame's geometry at that lod).  Host only; `attr_blob` may be a prefix that reaches the last needed
@@ -315,7 +321,8 @@ class GeometryCodec:
         such key), version 19 adds qstep (0 in a blob without points), version 21 qstep as a tuple of one step per
         channel and colour, "ycocg" or None (zeros and None in a blob without points), version 22 those two, scalable
         True and scalable_to, its K (0 in a blob without points); versions 25 and 26 add predictor, "neighbours" (no other
-        kind's dict has the key), 26 also cross_channel.
+        kind's dict has the key), 26 also cross_channel; versions 28 and 31 the same predictor beside their max_error >= 1
+        and scalable True, 31 also cross_channel.
         Host only; `attr_blob` may be a prefix of 16 bytes or more (version 21: 16 + 4 channels)."""
         return Runtime.attr_info(bytes(attr_blob))
 
@@ -484,23 +491,32 @@ class GeometryCodec:
 
     @staticmethod
     def _check_predictor(predictor, attrs, max_error, qstep, colour, scalable_to, target_bytes, target_frame_bytes):
-        """predictor of compress -> True for "neighbours" (attribute blob versions 25 / 26), False for None"""
+        """predictor of compress -> "neighbours" (attribute blob versions 25 / 26), "bounded-neighbours" (28 / 31, which
+        need max_error >= 1), or None"""
         if predictor is None:
-            return False
+            return None
         if not isinstance(predictor, str):
-            raise TypeError(f"predictor must be None or 'neighbours', got {predictor!r}")
-        if predictor != "neighbours":
-            raise ValueError(f"predictor must be None or 'neighbours', got {predictor!r}")
+            raise TypeError(f"predictor must be None or 'neighbours' or 'bounded-neighbours', got {predictor!r}")
+        if predictor not in ("neighbours", "bounded-neighbours"):
+            raise ValueError(f"predictor must be None or 'neighbours' or 'bounded-neighbours', got {predictor!r}")
         if attrs is None:
             raise ValueError("predictor predicts the values of attributes: it needs attributes=")
-        for name, given in (("max_error", bool(max_error)), ("qstep", not isinstance(qstep, (int, np.integer)) or bool(qstep)),
+        bounded = predictor == "bounded-neighbours"
+        if bounded and not GeometryCodec._check_max_error(max_error, attrs):
+            raise ValueError("predictor='bounded-neighbours' needs max_error >= 1 (attribute blob versions 28 and 31 bound every "
+                             "value's error by it); predictor='neighbours' is the lossless kind")
+        for name, given in (("max_error", bool(max_error) and not bounded),
+                            ("qstep", not isinstance(qstep, (int, np.integer)) or bool(qstep)),
                             ("colour", colour is not None), ("scalable_to", scalable_to is not None),
                             ("target_bytes", target_bytes is not None), ("target_frame_bytes", target_frame_bytes is not None)):
+            if given and bounded:
+                raise ValueError(f"predictor='bounded-neighbours' with {name}: attribute blob versions 28 and 31 bound every "
+                                 "value's error by max_error, they have no transform-coded form and no byte target")
             if given:
                 raise ValueError(f"predictor='neighbours' with {name}: attribute blob versions 25 and 26 are lossless, the "
-                                 "predictor from 3-D neighbours has no near-lossless and no transform-coded form (a "
-                                 "closed loop over three candidates of other sizes is not built)")
-        return True
+                                 "predictor from 3-D neighbours has no transform-coded form; its near-lossless form is "
+                                 "predictor='bounded-neighbours' with max_error (attribute blob versions 28 and 31)")
+        return predictor
 
     def compress(self, frames, attributes=None, lod=0, scalable=False, *, voxel=None, origin=(0.0, 0.0, 0.0),
                  invalid="raise", return_index=False, max_error=0, cross_channel=False, qstep=0, colour=None,
@@ -609,7 +625,15 @@ class GeometryCodec:
         or False beside it changes nothing.  It combines with lod=k, float32 / device frames, invalid="drop",
         return_index, predict= / history= (geometry only) and cross_channel; with max_error, qstep, colour, scalable_to,
         target_bytes or target_frame_bytes: ValueError saying why (the kind is lossless and has no transform-coded
-        form).  None, the default, writes the bytes of before."""
+        form).  None, the default, writes the bytes of before.
+        predictor="bounded-neighbours" with max_error=e >= 1 (without it, or with e = 0: ValueError, "neighbours" is the
+        lossless kind): attribute blobs of version 28, version 7's layout and prefixes with the same three candidates in
+        a closed loop — every value is predicted from its candidates' decoded values, the error of the prediction is
+        quantised with step 2 e + 1, and no decoded value is off by more than e; 11 to 25 % smaller than version 7 on
+        colour at e = 1 .. 8.  Version 31 is its cross-channel form.  Always cuttable (scalable= changes nothing); a row
+        at lod k is within e of the row predictor="neighbours" gives there.  It combines with what "neighbours" combines
+        with; qstep, colour, scalable_to, target_bytes or target_frame_bytes beside it: ValueError naming the keyword.
+        max_error's own checks (type, sign, the dtype's 2^(8 bpv - 1)) are unchanged."""
         lod = self._check_lod(lod)
         frames, is_float, on_device = self._check_frames(frames)
         intra_period, reference, history = self._check_predict(predict, intra_period, reference, is_float, on_device, len(frames),
@@ -627,8 +651,10 @@ class GeometryCodec:
         neighbours = self._check_predictor(predictor, attrs, max_error, qstep, colour, scalable_to, target_bytes, target_frame_bytes)
         coding = self._attr_coding(attrs, nb, lod, scalable, max_error, cross_channel, qstep, colour, scalable_to, target_bytes,
                                    target_frame_bytes)
-        if neighbours:
+        if neighbours == "neighbours":
             coding = coding._replace(version=2, neighbours=True)
+        elif neighbours:
+            coding = coding._replace(version=2, neighbours_nl=True)
         if coding is not None and coding.targets is not None:
             coding = coding._replace(scratch_limit=int(self.rate_scratch_limit))
 
@@ -882,7 +908,8 @@ class GeometryCodec:
         and a cross-channel kind returns what its plain kind returns.  Version 22 (compress(..., qstep=q,
         scalable_to=K)) decodes at lod 0 .. K, from whole blobs or attr_lod_info's prefixes: row j is the mean of cell j
         under the kind's weights; lod > K raises ValueError naming the frame and K.  Versions 25 / 26 (compress(...,
-        predictor="neighbours")) decode at every lod as versions 2 / 11 do.  The thirteen kinds may be mixed at
+        predictor="neighbours")) decode at every lod as versions 2 / 11 do, versions 28 / 31 (predictor=
+        "bounded-neighbours") as 7 / 14 do, every value within their e.  The fifteen kinds may be mixed at
         lod 0; an attribute blob of version 1, 4, 8, 13, 19 or 21 at lod > 0 raises ValueError naming the frame.
         voxel (with origin): the point sets come back as float32 [n_f, 3] in the caller's unit instead of int32,
         x = origin + t * voxel, one float32 multiplication and then one addition on the device (include/pcc.h has the

@@ -865,7 +865,7 @@ class Runtime:
 
     def _attr_encode(self, coding, values, value_offsets, formats, row_offsets, points, perm, run_starts, n_unique, keys, key_shift,
                      n_kept, cap=None):
-        """the one binding of the ten attribute encode entry points: the arrays of a call as attr_encode_frames takes
+        """the one binding of the eleven attribute encode entry points: the arrays of a call as attr_encode_frames takes
         them, and the AttrCoding that says which blobs to write -> (blobs, rungs), rungs None without a byte target"""
         c, nf = coding, len(formats)
         if c.cross is not None and len(c.cross) != nf:
@@ -892,6 +892,7 @@ class Runtime:
         four = None if c.steps is None else (C.c_int32 * 4)(*c.four(c.steps))
         args += {"": (), "_v2": (), "_kept": (), "_nl": (c.max_error,),
                  "_nbr": (None if c.cross is None or not any(c.cross) else (C.c_int32 * nf)(*c.cross),),
+                 "_nbr_nl": (c.max_error, None if c.cross is None or not any(c.cross) else (C.c_int32 * nf)(*c.cross)),
                  "_cross": (c.max_error, None if c.cross is None else (C.c_int32 * nf)(*c.cross)),
                  "_transform": (c.steps and c.steps[0],), "_transform2": (four, c.colour), "_transform3": (four, c.colour, c.scalable_to),
                  "_rate": (four, int(c.per_channel), c.colour, None if c.targets is None else (C.c_int64 * nf)(*c.targets),
@@ -931,7 +932,8 @@ class Runtime:
         (pcc_attr_qstep; 0 in a blob without points); for version 21 qstep, a tuple of one step per channel, and colour,
         "ycocg" or None (pcc_attr_transform_info; zeros and None in a blob without points); for version 22 those two and
         scalable_to, its deepest level-of-detail prefix (pcc_attr_scalable_to; 0 in a blob without points); for versions
-        25 and 26 also predictor, the string "neighbours" (pcc_attr_info's version byte)"""
+        25, 26, 28 and 31 also predictor, the string "neighbours" (pcc_attr_info's version byte; 28 and 31 with their
+        max_error >= 1)"""
         buf = np.frombuffer(blob, dtype=np.uint8)
         v = [C.c_int32(0) for _ in range(6)]
         n = C.c_int64(0)
@@ -965,7 +967,7 @@ class Runtime:
         point i (pcc_attr_decode_frames: versions 1, 4, 8 and 13, one version per call): numpy arrays, or views of one device
         tensor (device=True).  points[f]
         (optional): frame f's geometry point count, checked against the blob before anything is launched.
-        lod = k (0 .. 15) with cells (pcc_attr_decode_frames_lod): blobs of version 2, or of 7, 11, 14, 25 or 26, or prefixes of them (attr_lod_info)
+        lod = k (0 .. 15) with cells (pcc_attr_decode_frames_lod): blobs of version 2, or of 7, 11, 14, 25, 26, 28 or 31, or prefixes of them (attr_lod_info)
         -> row j the value of the j-th cell of the frame's geometry at that lod; lod = 0 with cells also reads whole
         blobs of version 19 or of version 21, whose transform needs the frame's keys (a call of them at lod > 0: PccError), and lod = 0 .. K reads blobs of version 22 or their prefixes (K: every blob's scalable_to); `cells` the device tensors
         octree_decode_frames(..., device=True, lod=k) returned for the same frames (views of one tensor)."""
@@ -1017,9 +1019,10 @@ class Runtime:
 # the kinds of attribute blob by version byte (csrc/attr_blob.h): those one lane run predicts through, which decode at
 # lod 0 only (pcc_attr_decode_frames), and the cross-channel forms 8, 11, 13, 14 of 1, 2, 4, 7
 ATTR_RUN_KINDS = (1, 4, 8, 13)
-ATTR_CROSS_KINDS = (8, 11, 13, 14, 26)
-# lossless and scalable under the predictor from 3-D neighbours, and its cross-channel form: decoded as version 2's family is
-ATTR_NEIGHBOUR_KINDS = (25, 26)
+ATTR_CROSS_KINDS = (8, 11, 13, 14, 26, 31)
+# scalable under the predictor from 3-D neighbours: lossless and its cross-channel form, bounded-error (a closed loop
+# over decoded values) and its cross-channel form; decoded as version 2's family is
+ATTR_NEIGHBOUR_KINDS = (25, 26, 28, 31)
 # the transform-coded kind: it decodes against the cells as version 2's family does, but at lod 0 only
 ATTR_TRANSFORM_KIND = 19
 # version 19 with a colour transform and one step per channel: decoded as version 19 is
@@ -1041,6 +1044,7 @@ class AttrCoding(NamedTuple):
     targets: tuple = None          # a byte target per frame: the steps are the finest the search may choose
     scratch_limit: int = 0         # bytes of scratch for the candidates of a byte target; 0: the library's default
     neighbours: bool = False       # versions 25 / 26: version 2's family under the predictor from 3-D neighbours
+    neighbours_nl: bool = False    # versions 28 / 31: that predictor in a closed loop, every error within max_error >= 1
 
     @staticmethod
     def four(qstep, what=""):
@@ -1052,7 +1056,7 @@ class AttrCoding(NamedTuple):
 
     @classmethod
     def of(cls, version=1, max_error=0, cross=None, qstep=0, colour=None, scalable_to=None, targets=None, scratch_limit=0,
-           neighbours=False):
+           neighbours=False, neighbours_nl=False):
         """the record of the loose keywords of Runtime.attr_encode_frames and attr_encode_frames_rate; what contradicts
         itself raises ValueError here, what needs the number of frames in Runtime._attr_encode"""
         if version not in (1, 2):
@@ -1068,10 +1072,14 @@ class AttrCoding(NamedTuple):
             raise ValueError("qstep (attribute blob versions 19 and 21) has no near-lossless and no cross-channel form")
         if neighbours and (steps is not None or int(max_error) or scalable_to is not None):
             raise ValueError("the predictor from 3-D neighbours (attribute blob versions 25 and 26) is lossless: it has no "
-                             "near-lossless and no transform-coded form")
+                             "transform-coded form, and its near-lossless form is neighbours_nl (versions 28 and 31)")
+        if neighbours_nl and (neighbours or steps is not None or int(max_error) < 1 or scalable_to is not None or targets is not None):
+            raise ValueError("the bounded-error predictor from 3-D neighbours (attribute blob versions 28 and 31) needs max_error "
+                             ">= 1 and has no lossless record (that is neighbours), no transform-coded form and no byte target")
         return cls(version, int(max_error), None if cross is None else tuple(int(m) for m in cross), steps, per_channel,
                    int(colour or 0), None if scalable_to is None else int(scalable_to),
-                   None if targets is None else tuple(int(t) for t in targets), int(scratch_limit), bool(neighbours))
+                   None if targets is None else tuple(int(t) for t in targets), int(scratch_limit), bool(neighbours),
+                   bool(neighbours_nl))
 
     @property
     def qstep(self):
@@ -1079,9 +1087,10 @@ class AttrCoding(NamedTuple):
         return 0 if self.steps is None else self.steps if self.per_channel else self.steps[0]
 
     def entry(self, dropped):
-        """which of the ten entry points codes this record, as the suffix of pcc_attr_encode_frames; `dropped`: the call
+        """which of the eleven entry points codes this record, as the suffix of pcc_attr_encode_frames; `dropped`: the call
         left rows out (n_kept).  The first match wins."""
-        for hit, kind in ((self.neighbours, "_nbr"),
+        for hit, kind in ((self.neighbours_nl, "_nbr_nl"),
+                          (self.neighbours, "_nbr"),
                           (self.targets is not None, "_rate"),
                           (self.scalable_to is not None, "_transform3"),
                           (self.steps is not None and self.per_channel, "_transform2"),

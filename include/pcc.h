@@ -1214,6 +1214,64 @@ int pcc_attr_encode_frames_nbr(pcc_ctx* ctx, const void* d_values,
                                int key_shift, const int32_t* h_cross /* may be NULL */,
                                uint8_t* h_out, int64_t cap, int64_t* h_offsets);
 
+/* Near-lossless attributes predicted from 3-D neighbours: attribute blob
+ * version 28 and its cross-channel form 31, the bounded-error forms of 25 and
+ * 26 as 7 and 14 are of 2 and 11.  Version 7 predicts every value from one
+ * point, first(i); this kind predicts it from up to three, and is 11 to 25 %
+ * smaller on colour at e = 1 .. 8.  28 = 11100b and 31 = 11111b keep the odd
+ * parity of the thirteen bytes in use.
+ *
+ * Layout: version 7's (14's), byte for byte, under the version byte:
+ *     'A' 28 (bpv | slod << 4) c | n | payload_len | max_error | cells[16] |
+ *     S | n_chunks | p0 | words[] | chunks
+ *   slod in byte 2; version 31: byte 3 = c | m << 4 as version 14 has it.  An
+ *   empty frame is the 12-byte head.  The prefix rule is version 7's.
+ * The rule (tests/attr_nbr_nl_ref.py restates it in numpy):
+ *   Candidates, distances d, the tie-break on (d, Morton index) and the
+ *     weights w = floor(65536 / d) are version 25's: functions of the geometry
+ *     alone.  e = max_error >= 1, q = 2 e + 1, mask = 2^(8 bpv) - 1.
+ *   Point 0 has p = 0.  Every other point i has, per channel,
+ *     p = floor((2 sum(w v^_j) + sum(w)) / (2 sum(w))) over its candidates'
+ *     DECODED values v^_j, the clamped values a decoder returns, in 64-bit
+ *     integers.
+ *   Index: j_i = sgn(d) floor((|d| + e) / q) with d = v_i - p.  There is no
+ *     wrap: |d| <= mask, so |j_i| < 2^(8 bpv - 1).
+ *   Decoded value: v^_i = clip(p + j_i q, 0, mask).  p + j_i q is within e of
+ *     v_i and v_i is in range, so |v_i - v^_i| <= e.
+ *   A closed loop: every candidate was introduced at a larger size than its
+ *     point, so both sides form v^ size by size, 16 down to 0.
+ *   The j go in introduction order through version 7's coder (contexts =
+ *     channel, bucket of the channel's previous index in the lane's run,
+ *     position).  Version 31 applies version 14's cross rule to them.
+ *   Level of detail k: a point present at level k has size s >= k, and its
+ *     candidates were introduced at sizes >= s + 1, so a decoder at a cut
+ *     forms the same p from its cells alone.  Row j is v^ of the Morton-first
+ *     point of cell j: within e of the row versions 25 / 26 return at that
+ *     lod.
+ *   A decoder forms p + j q in 64 bits (a damaged uint16 stream at e = 32767
+ *     reaches 2^31), clamps to [0, mask], and reports PCC_E_STREAM where the
+ *     sum lies outside [-e, mask + e], which no encoder's reconstruction
+ *     does.  No index comes from the stream.
+ *   _encode_frames_nbr_nl : pcc_attr_encode_frames_nbr's arguments with
+ *     max_error (1 .. 2^(8 bpv - 1) - 1 of every frame) in front of h_cross,
+ *     which may be NULL (every frame version 28); else a frame with m != 0 is
+ *     version 31.
+ *   pcc_attr_decode_frames_lod and pcc_attr_lod_info read 28 and 31 beside
+ *     2, 7, 11, 14, 25 and 26, still one version per call; pcc_attr_info
+ *     reports the version byte with scalable = 1 and the head's max_error,
+ *     pcc_attr_cross_mask the mask of a version-31 head.  Every other entry
+ *     point refuses the two bytes as it refuses any byte it does not know. */
+int pcc_attr_encode_frames_nbr_nl(pcc_ctx* ctx, const void* d_values,
+                                  const int64_t* h_value_offsets,
+                                  const int32_t* h_format, const int64_t* h_rows,
+                                  const int64_t* h_points, int n_frames,
+                                  const uint32_t* d_perm,
+                                  const uint32_t* d_run_starts, int64_t n_unique,
+                                  int64_t n_kept, const uint64_t* d_keys,
+                                  int key_shift, int max_error,
+                                  const int32_t* h_cross /* may be NULL */,
+                                  uint8_t* h_out, int64_t cap, int64_t* h_offsets);
+
 /* Transform-coded attributes: attribute blob version 19, a ninth kind, lossy,
  * for rates below about a byte per point, where a near-lossless predictive
  * coder (a staircase on the prediction error) is the wrong tool.  An integer

@@ -9,6 +9,10 @@ behind --warmup calls, with the fastest and slowest): GeometryCodec.compress(att
 for the scalable kinds decompress of the shortest prefixes (geometry and attributes) at lod 1 .. 3.  Host arrays in,
 host arrays out.  Every kind's decode at lod 0 is checked once against version 1's.
 
+--max-error E (E >= 1) measures the bounded-error family instead: versions 7 and 28 (and their cross-channel forms 14 and
+31 on RGB), compress(..., max_error=E) with scalable=True against predictor="bounded-neighbours"; every decode is checked
+once against the e-bound to the lossless decode.  Lossless kinds may be listed beside them (--kinds 2,7,25,28).
+
 --kinds 1,2 (for a build without versions 25 / 26) restricts the kinds.  Writes one JSON object (stdout, and --out)."""
 import argparse
 import importlib
@@ -27,7 +31,11 @@ LODS = (1, 2, 3)
 # version: the keywords of compress that write it
 KINDS = {1: {}, 2: {"scalable": True}, 25: {"predictor": "neighbours"},
          8: {"cross_channel": True}, 11: {"scalable": True, "cross_channel": True}, 26: {"predictor": "neighbours", "cross_channel": True}}
-SCALABLE = (2, 11, 25, 26)
+# the bounded-error kinds: the same with max_error=E (--max-error)
+BOUNDED = {7: {"scalable": True}, 28: {"predictor": "bounded-neighbours"},
+           14: {"scalable": True, "cross_channel": True}, 31: {"predictor": "bounded-neighbours", "cross_channel": True}}
+SCALABLE = (2, 11, 25, 26, 7, 14, 28, 31)
+PLAIN = (1, 2, 25, 7, 28)      # the kinds of a one-channel input
 
 
 def main():
@@ -35,7 +43,8 @@ def main():
     ap.add_argument("--batches", default="1,8")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--kinds", default="1,2,25,8,11,26")
+    ap.add_argument("--kinds", default=None, help="default 1,2,25,8,11,26; with --max-error 7,28,14,31")
+    ap.add_argument("--max-error", type=int, default=0)
     ap.add_argument("--inputs", default="sweep_intensity,room_rgb,zed_gop_rgb")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -44,7 +53,10 @@ def main():
     G = pkg.GeometryCodec
     codec = G()
     batches = [int(b) for b in args.batches.split(",")]
-    kinds = [int(k) for k in args.kinds.split(",")]
+    kinds = [int(k) for k in (args.kinds or ("7,28,14,31" if args.max_error else "1,2,25,8,11,26")).split(",")]
+    if any(k in BOUNDED for k in kinds) and args.max_error < 1:
+        ap.error("kinds 7, 14, 28 and 31 need --max-error E >= 1")
+    how = {**KINDS, **{k: dict(kw, max_error=args.max_error) for k, kw in BOUNDED.items()}}
     top = max(batches)
     inputs = {}
     if "sweep_intensity" in args.inputs:
@@ -56,21 +68,22 @@ def main():
     if "zed_gop_rgb" in args.inputs:
         with np.load(os.path.join(ROOT, "tests", "golden", "zed_seq25.npz")) as f:
             inputs["zed_gop_rgb"] = ([f[f"points_{i}"].astype(np.int32) for i in range(top)], [f[f"colors_u8_{i}"] for i in range(top)])
-    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "kinds": kinds, "inputs": {}}
+    res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "kinds": kinds, "max_error": args.max_error,
+           "inputs": {}}
     for name, (frames, attrs) in inputs.items():
         rgb = attrs[0].ndim == 2 and attrs[0].shape[1] > 1
-        mine = [k for k in kinds if rgb or k in (1, 2, 25)]
+        mine = [k for k in kinds if rgb or k in PLAIN]
         out = {"B": {}}
         for B in batches:
             fr, at = frames[:B], attrs[:B]
             blobs, pre, jobs = {}, {}, {}
-            want = None
+            want = codec.decompress(*codec.compress(fr, attributes=at))[1]      # version 1's decode: the merged values
             for k in mine:
-                g, blobs[k] = codec.compress(fr, attributes=at, **KINDS[k])
+                g, blobs[k] = codec.compress(fr, attributes=at, **how[k])
                 vals = codec.decompress(g, blobs[k])[1]
-                want = vals if want is None else want
-                assert all(np.array_equal(x, y) for x, y in zip(vals, want)), (name, k)
-                jobs[f"enc_v{k}"] = (lambda k: lambda: codec.compress(fr, attributes=at, **KINDS[k]))(k)
+                bound = args.max_error if k in BOUNDED else 0
+                assert all(np.abs(x.astype(np.int64) - y.astype(np.int64)).max(initial=0) <= bound for x, y in zip(vals, want)), (name, k)
+                jobs[f"enc_v{k}"] = (lambda k: lambda: codec.compress(fr, attributes=at, **how[k]))(k)
                 jobs[f"dec_v{k}"] = (lambda k: lambda: codec.decompress(g, blobs[k]))(k)
                 for lod in LODS if k in SCALABLE else ():
                     pre[k, lod] = ([b[:G.lod_info(b, lod)[0]] for b in g], [b[:G.attr_lod_info(b, lod)[0]] for b in blobs[k]])
