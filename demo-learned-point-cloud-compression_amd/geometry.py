@@ -1315,6 +1315,82 @@ class GeometryCodec:
         raise ValueError(f"frame {f}: {sizes[f] - int(counts[f])} duplicate points in {side}: attributes are compared point by "
                          "point, so both sides must be free of duplicates (a decoded frame is)")
 
+    def transfer(self, frames_from, attributes, frames_to, output="numpy", return_counts=False):
+        """The attributes of one geometry carried onto another (recolouring), frame by frame on the device
+        (pcc_attr_transfer_frames; include/pcc.h has the rule) -> one array per frame, row i the value of row i of
+        frames_to[f] as given: [n_to] for attributes given as [n], [n_to, c] otherwise, in the attributes' dtype.
+
+        Every source row is assigned to its nearest target point and every target takes the rounded mean
+        (sum + count // 2) // count of the rows assigned to it — the merge rule of compress for duplicate points; a target
+        that no source row chose takes the merged value of its nearest source point.  Nearest is exact, ties go to the
+        Morton-first point (the rule of distortion).  Rows of frames_to that share a point share its value.
+        frames_from, frames_to: as distortion takes them, int16 / int32, numpy or torch, all on the host or all on this
+        codec's device, the same number on both sides; float32 frames raise TypeError.  attributes: host uint8 / uint16
+        [n] or [n, c] per frame of frames_from, as compress takes them.  A frame with targets and no source raises
+        ValueError naming the frame; a frame without targets gives [0] / [0, c].
+        output: "numpy" arrays, or "device": views of one tensor on this codec's device.  return_counts=True:
+        (values, counts), counts[f] a uint32 [n_to]: the source rows assigned to the row's point, 0 where the value is
+        the fallback."""
+        if output not in ("numpy", "device"):
+            raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
+        ff, float_f, dev_f = self._check_frames(frames_from)
+        ft, float_t, dev_t = self._check_frames(frames_to)
+        if float_f or float_t:
+            raise TypeError("transfer: float32 frames: pass lattice points (int16 / int32) — the input of compress, or "
+                            "what decompress returns without voxel=")
+        if len(ff) != len(ft):
+            raise ValueError(f"transfer: {len(ff)} frames against {len(ft)}")
+        if ff and dev_f != dev_t:
+            raise ValueError("transfer: one side on the host, the other on the device: the frames of a call are all on "
+                             "the host or all on the device")
+        attributes = list(attributes)
+        flat = [np.ndim(a) == 1 for a in attributes]
+        attrs = self._check_attributes(ff, attributes)
+        nb = len(ff)
+        sizes_f = [int(a.shape[0]) for a in ff]
+        sizes_t = [int(a.shape[0]) for a in ft]
+        for f, (ns, nt) in enumerate(zip(sizes_f, sizes_t)):
+            if nt and not ns:
+                raise ValueError(f"frame {f}: {nt} points against an empty source: there is no value to transfer")
+        if nb == 0:
+            return ([], []) if return_counts else []
+        to_host = output == "numpy"
+        # the call's common format: rows of 4 or 8 bytes (pcc_gather_rows), absent channels 0
+        dtype = np.uint16 if any(a.dtype == np.uint16 for a in attrs) else np.uint8
+        channels = max(a.shape[1] for a in attrs)
+        channels = 4 if dtype == np.uint8 or channels > 2 else 2
+        if sum(sizes_t) == 0:
+            values = torch.empty((0, channels), dtype=torch.uint8 if dtype == np.uint8 else torch.uint16,
+                                 device="cpu" if to_host else self.rt.device)
+            counts = torch.empty((0,), dtype=torch.int32, device=values.device)
+            if to_host:
+                values, counts = values.numpy(), counts.numpy()
+            values, counts = _split(values, sizes_t), _split(counts, sizes_t)
+        else:
+            caller = torch.cuda.current_stream(self.rt.device) if dev_f else None
+            with self._lock, self.rt as rt:
+                front_f = self._front(rt, ff, False, dev_f, caller, "GeometryCodec.transfer")
+                front_t = self._front(rt, ft, False, dev_t, caller, "GeometryCodec.transfer")
+                _, row_st, _ = rt.nn_frames(front_f.sorted_keys, front_t.keys, nb, want_dist=False)
+                _, row_ts, _ = rt.nn_frames(front_t.keys, front_f.keys, nb, want_dist=False)
+                sv = self._sorted_values(rt, attrs, front_f.perm, dtype, channels)
+                distinct, cnt = rt.attr_transfer_frames(front_f.sorted_keys, front_f.rows, front_f.n_unique, sv, row_st, row_ts,
+                                                        nb, want_count=return_counts)
+                # the distinct row of every target row as given: rows_index with no frame's rows taken off
+                index = rt.rows_index(front_t.perm, front_t.n_keep, front_t.rows, front_t.n_unique, front_t.offsets.data_ptr(),
+                                      torch.zeros(nb, dtype=torch.int64, device=rt.device), nb)
+                values = _frames_out(rt, rt.gather_rows(distinct, index), sizes_t, to_host)
+                counts = _frames_out(rt, rt.gather_rows(cnt, index), sizes_t, to_host) if return_counts else None
+        out = []
+        for v, a, one in zip(values, attrs, flat):
+            v = v[:, 0] if one else v[:, :a.shape[1]]
+            if a.dtype != dtype:      # a uint8 frame in a call that also holds uint16 frames
+                v = v.astype(a.dtype) if to_host else v.contiguous().view(torch.uint8).reshape(v.shape + (2,))[..., 0]      # the low bytes
+            out.append(v)
+        if not return_counts:
+            return out
+        return out, [c.view(np.uint32 if to_host else torch.uint32) for c in counts]
+
     @staticmethod
     def _named(first, call):
         """a run of frames decoded in a call of its own: the frame an error names counts from the run's first frame"""

@@ -242,6 +242,27 @@ class Runtime:
               "pcc_nn_attr_sse_frames")
         return self._u64_rows(sse)
 
+    def attr_transfer_frames(self, skeys, sruns, n_su, svalues, row_st, row_ts, n_frames, out=None, want_count=True):
+        """the values of a source side carried onto the distinct points of a target side (pcc_attr_transfer_frames, the
+        rule of include/pcc.h).  skeys: the sorted source keys, duplicates allowed; sruns / n_su: pcc_unique_rows over
+        them; svalues: a uint8 or uint16 [n_s, c] device tensor in the order of skeys; row_st int32 [n_s]: nn_frames'
+        rows of skeys among the target's distinct keys; row_ts int32 [n_t]: its rows of those keys among the distinct
+        source keys.  Returns (out, count): out [n_t, c] of the values' dtype (or `out`, a device tensor of at least
+        n_t c values of it, written in place), count an int32 [n_t] device tensor holding uint32 values, None unless
+        wanted.  Does not synchronise."""
+        n_s, n_t = int(skeys.shape[0]), int(row_ts.shape[0])
+        if svalues.dtype not in (torch.uint8, torch.uint16) or svalues.dim() != 2 or svalues.shape[0] != n_s or \
+                row_st.shape[0] != n_s or (out is not None and (out.dtype != svalues.dtype or out.numel() < n_t * svalues.shape[1])):
+            raise ValueError(f"attr_transfer_frames: values {tuple(svalues.shape)} {svalues.dtype} for {n_s} source rows")
+        c = int(svalues.shape[1])
+        if out is None:
+            out = self.empty((n_t, c), svalues.dtype)
+        count = self.empty((n_t,), torch.int32) if want_count else None
+        check(self.lib.pcc_attr_transfer_frames(self.ctx, _ptr(skeys), n_s, _ptr(sruns), int(n_su), _ptr(svalues), _ptr(row_st),
+                                                _ptr(row_ts), n_t, svalues.element_size(), c, int(n_frames), _ptr(out), _ptr(count)),
+              "pcc_attr_transfer_frames")
+        return out, count
+
     def knn_frames(self, keys, n_frames, k, want_rows=False, want_dist=False, want_cov=False, want_normals=True,
                    viewpoint=None):
         """the k nearest neighbours of every point of a frame among the frame's own points, their scatter matrix and

@@ -1691,6 +1691,61 @@ int pcc_knn_replay_host(const uint64_t* h_keys, int64_t n, int k, int32_t* h_row
                         uint64_t* h_sqdist, int64_t* h_cov, float* h_normals,
                         uint32_t* h_nodes);
 
+/* ---- attribute transfer onto another geometry: recolouring (csrc/transfer.hip) -- */
+
+/* The rule (tests/transfer_ref.py restates it in numpy, on tests/nn_ref.py).
+ * Per frame there are two sides:
+ *   source  S, a multiset of lattice points, every row with a value of 1 .. 4
+ *           channels, uint8 or uint16; duplicates count row by row, as the
+ *           queries of pcc_nn_frames do;
+ *   target  T, distinct lattice points in Morton order.
+ * Two searches under the rule of pcc_nn_frames above, ties to the SMALLEST row:
+ *   backward  b(s) = the row of the nearest target of source row s;
+ *   forward   f(t) = the row of the nearest DISTINCT source point of target t
+ *             (rows among the frame's distinct source points in Morton order).
+ * For a target t let B(t) = { s : b(s) = t } and cnt(t) = |B(t)|.  Per channel
+ *   cnt > 0   out[t] = (sum over s in B(t) of v[s] + cnt / 2) / cnt, the
+ *             project's merge rule for duplicate points (integer division, the
+ *             sum in 64 bits: 2^27 rows * 65535 < 2^43);
+ *   cnt == 0  out[t] = the merged value of the distinct source point f(t): the
+ *             same rounded mean over its run of duplicate rows;
+ *   a frame without a source (f(t) = -1): out[t] = 0, cnt = 0.
+ * The sums are integers, so the result does not depend on the order in which
+ * they are formed: it is the same from run to run.
+ *
+ *   pcc_attr_transfer_frames : runs no search; both row arrays are outputs of
+ *     pcc_nn_frames, so a caller that holds the pairing already (for
+ *     pcc_nn_attr_sse_frames) pays for it once.  d_skeys [n_s]: the source
+ *     keys, sorted, duplicates allowed; d_sruns [n_su]: the first sorted row
+ *     of every distinct source point (pcc_unique_rows), a run ending where the
+ *     next begins, the last at n_s; d_svalues [n_s][channels]: the values in
+ *     the order of d_skeys, bpv = 1 (uint8) or 2 (uint16) bytes each;
+ *     d_row_st [n_s]: pcc_nn_frames' rows of d_skeys among the n_t distinct
+ *     target keys; d_row_ts [n_t]: its rows of the target keys among the n_su
+ *     distinct source keys.  Rows are counted over the whole call, as
+ *     pcc_nn_frames counts them, and a pairing never leaves its frame, so the
+ *     frames of a call do not mix.  d_out [n_t][channels]; d_count [n_t]
+ *     (nullable): cnt.
+ *     Two launches on the context's stream and no synchronisation: one thread
+ *     per source row adds its values to a zeroed uint64 [n_t][channels + 1]
+ *     accumulator in the context's scratch (runs of equal adjacent target rows
+ *     are summed inside the wave first, then one 64-bit integer atomic per
+ *     channel and one for the count per run), then one thread per target
+ *     forms the mean or takes the fallback.
+ *     Checked (PCC_E_ARG, pcc_last_error says which): n_s, n_t <= 2^27,
+ *     n_su <= n_s and 0 only with it, n_frames in 1 .. 65535, bpv 1 or 2,
+ *     channels 1 .. 4, null arrays.  n_t = 0 launches nothing; n_s = 0 zeroes
+ *     d_out and d_count.  Nothing read from an array indexes outside one: a
+ *     d_row_st entry outside [0, n_t) or a source key whose frame index is
+ *     not below n_frames adds nothing, a d_row_ts entry outside [0, n_su)
+ *     gives 0, a run is cut at n_s. */
+int pcc_attr_transfer_frames(pcc_ctx* ctx, const uint64_t* d_skeys, int64_t n_s,
+                             const uint32_t* d_sruns, int64_t n_su,
+                             const void* d_svalues, const int32_t* d_row_st,
+                             const int32_t* d_row_ts, int64_t n_t, int bpv,
+                             int channels, int n_frames, void* d_out,
+                             uint32_t* d_count);
+
 /* ---- whole-GOP entry points ------------------------------ */
 
 /* replaces: CompressionPipeline.compress() (sender/encoder/codec_pipeline.py:
