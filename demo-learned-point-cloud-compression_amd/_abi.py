@@ -124,6 +124,7 @@ PROTOTYPES = {
     "pcc_nn_d2_frames": (i32, [vp, vp, vp, i64, vp, i64, vp, vp, i32, vp, vp]),
     "pcc_knn_replay_host": (i32, [vp, i64, i32, vp, vp, vp, vp, vp]),
     "pcc_attr_transfer_frames": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp, vp]),
+    "pcc_attr_stage_frames": (i32, [vp, vp, vp, vp, vp, i32, C.c_double, i32, i32, vp, vp, i64, vp]),
     "pcc_abi_version": (i32, []),
     "pcc_last_error": (C.c_char_p, []),
     "pcc_create": (vp, [i32, vp]),

@@ -133,6 +133,20 @@ return (NaN / Inf) can be dropped, and the row index says which decoded row ever
 
 voxel and origin are not written into any blob: the caller carries the grid.
 
+Attributes from where they lie (include/pcc.h has the rule, csrc/attr_stage.hip the kernel): uint8 / uint16 tensors on
+this codec's device are read there, and float32 / float64 values, host or device, are quantised on the device,
+v = clip(rint(x * s), 0, peak) in their own precision; compress, distortion and transfer take both.
+
+    blobs, attr_blobs = codec.compress(frames, attributes=[t0, t1, ...])       # torch uint8 / uint16 on the codec's device
+    blobs, attr_blobs = codec.compress(frames, attributes=[interleaved[:, 4:7]])   # a view with contiguous rows: no copy
+    with rt:                                                                   # the capture step's Runtime: its stream is waited for
+        f = capture.voxelize(rt, xyzrgba, output="device")                     # int32 points, float64 colours in [0, 1]
+        blobs, attr_blobs = codec.compress([f["points"]], attributes=[f["colors"]], attribute_scale=255)
+    moved = codec.transfer(frames, attrs, lossy, output="device")              # and on into compress / distortion, on the device
+    rep = codec.distortion(frames, frames, normals_a=codec.normals(frames, output="device"))
+
+The scale is not written into any blob either: decompress returns the integers.
+
 Distortion (include/pcc.h has the rule): what a lossy setting costs, as the D1 (point-to-point) figures of MPEG's
 pc_error, by exact nearest neighbours on the device; lattice frames from the host or from this codec's device.
 
@@ -158,8 +172,8 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from ._abi import check, PccError, PCC_E_RANGE
-from .runtime import Runtime, AttrCoding, _ptr, ATTR_RUN_KINDS, ATTR_TRANSFORM_KINDS, ATTR_SCALABLE_TRANSFORM_KIND
+from ._abi import check, PccError, PCC_E_ARG, PCC_E_RANGE
+from .runtime import Runtime, AttrCoding, _ptr, ATTR_RUN_KINDS, ATTR_TRANSFORM_KINDS, ATTR_SCALABLE_TRANSFORM_KIND, ATTR_SRC_KINDS
 
 MAX_FRAMES = 65535      # the batch-index range of pcc_morton_keys
 MAX_HISTORY = 8         # frames a predicted frame's reference may be the union of (kO4MaxWindow, csrc/octree4.h)
@@ -208,6 +222,24 @@ class _Front(NamedTuple):
     keys: object = None          # the distinct keys (sorted_keys itself where there is no duplicate)
 
 
+class _Attr(NamedTuple):
+    """A frame's attributes that reach the coders through pcc_attr_stage_frames (include/pcc.h has the rule): a tensor on
+    the codec's device, or a host float array.  shape, dtype and nbytes answer as the uint8 / uint16 array it becomes."""
+    src: object      # [n, c]: a device tensor whose rows lie `pitch` elements apart, or a C-contiguous host array
+    kind: int        # ATTR_SRC_KINDS: what a value of src is
+    pitch: int
+    shape: tuple     # (n, c)
+    dtype: object    # the numpy dtype of the values after staging
+
+    @property
+    def nbytes(self):
+        return self.shape[0] * self.shape[1] * self.dtype.itemsize
+
+    @property
+    def on_device(self):
+        return isinstance(self.src, torch.Tensor)
+
+
 class GeometryCodec:
     def __init__(self, device=0):
         self.rt = Runtime(device)
@@ -216,6 +248,12 @@ class GeometryCodec:
 
     def close(self):
         self.rt.close()
+
+    @property
+    def _device(self):
+        """this codec's device; None for an instance without a Runtime (the keyword checks run without one)"""
+        rt = getattr(self, "rt", None)
+        return None if rt is None else rt.device
 
     def _check_frames(self, frames):
         """-> (frames, is_float, on_device): numpy arrays (host) or tensors on this codec's device, all integer (int16 /
@@ -270,23 +308,107 @@ class GeometryCodec:
         return float(v), tuple(float(x) for x in o)
 
     @staticmethod
-    def _check_attributes(frames, attributes):
+    def _check_attribute_scale(scale, dtype, given):
+        """attribute_scale and attribute_dtype of a call -> (s as a float, the numpy dtype float values become), or
+        (None, None) without a scale; `given`: whether the call has attributes"""
+        if scale is None:
+            if dtype is not None:
+                raise ValueError("attribute_dtype is what float attributes become: it needs attribute_scale=")
+            return None, None
+        if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)):
+            raise TypeError(f"attribute_scale must be a number, got {scale!r}")
+        s = float(scale)
+        if not (np.isfinite(s) and 0.0 < s <= 65535.0):
+            raise ValueError(f"attribute_scale must be a finite number with 0 < s <= 65535, got {scale!r}")
+        if not given:
+            raise ValueError("attribute_scale quantises float attributes: it needs attributes")
+        if dtype is None:
+            return s, np.dtype(np.uint8 if s <= 255.0 else np.uint16)
+        try:
+            dtype = np.dtype(dtype)
+        except TypeError:
+            dtype = None
+        if dtype not in (np.dtype(np.uint8), np.dtype(np.uint16)):
+            raise ValueError("attribute_dtype must be np.uint8 or np.uint16")
+        return s, dtype
+
+    @staticmethod
+    def _check_attributes(frames, attributes, device=None, scale=None, dtype=None):
+        """-> one entry per frame: host uint8 / uint16 arrays become C-contiguous [n, c] numpy arrays, as before; tensors
+        on `device` (the codec's) and float arrays (scale: attribute_scale, dtype: what they become) become _Attr
+        records, which reach the device layouts through pcc_attr_stage_frames.  All on the host or all on the device."""
         attributes = list(attributes)
         if len(attributes) != len(frames):
             raise ValueError(f"{len(attributes)} attribute arrays for {len(frames)} frames")
-        out = []
+        out, places = [], []
         for f, (a, p) in enumerate(zip(attributes, frames)):
-            a = np.asarray(a)
-            if a.dtype not in (np.uint8, np.uint16):
-                raise TypeError(f"frame {f}: expected uint8 or uint16 attributes, got {a.dtype}")
+            on_device = False
+            if isinstance(a, torch.Tensor) and a.device.type != "cpu":
+                if device is None or a.device != device:
+                    raise ValueError(f"frame {f}: attributes on {a.device}, this codec runs on {device}")
+                on_device, a = True, a.detach()
+            elif isinstance(a, torch.Tensor):
+                a = a.detach().numpy()
+            else:
+                a = np.asarray(a)
+            name = str(a.dtype).replace("torch.", "")
+            if name in ("float32", "float64"):
+                if scale is None:
+                    raise TypeError(f"frame {f}: expected uint8 or uint16 attributes, got {name}; float values are quantised "
+                                    "under attribute_scale=s, v = clip(rint(x * s), 0, peak)")
+            elif name not in ("uint8", "uint16"):
+                raise TypeError(f"frame {f}: expected uint8 or uint16 attributes, got {name}")
+            elif scale is not None:
+                raise ValueError(f"frame {f}: attribute_scale with {name} attributes: integer values are taken as they are")
+            places.append(on_device)
+            if places[-1] != places[0]:
+                raise ValueError(f"frame {f}: attributes on the {'device' if places[-1] else 'host'}, frame 0's on the "
+                                 f"{'device' if places[0] else 'host'}: the attributes of a call are all on the host or "
+                                 "all on the device")
             if a.ndim == 1:
                 a = a[:, None]
             if a.ndim != 2 or not 1 <= a.shape[1] <= 4:
-                raise ValueError(f"frame {f}: expected attributes of shape [n] or [n, c] with 1 <= c <= 4, got {a.shape}")
+                raise ValueError(f"frame {f}: expected attributes of shape [n] or [n, c] with 1 <= c <= 4, got {tuple(a.shape)}")
             if a.shape[0] != p.shape[0]:
                 raise ValueError(f"frame {f}: {a.shape[0]} attribute rows for {p.shape[0]} points")
-            out.append(np.ascontiguousarray(a.astype(a.dtype.newbyteorder("<"), copy=False)))
+            n, c = int(a.shape[0]), int(a.shape[1])
+            if not on_device:
+                a = np.ascontiguousarray(a.astype(a.dtype.newbyteorder("<"), copy=False))
+                if scale is None:      # host integers: the path and the bytes of before
+                    out.append(a)
+                    continue
+                pitch = c
+            else:
+                if (c > 1 and a.stride(1) != 1) or (n > 1 and a.stride(0) < c):
+                    a = a.contiguous()      # a [:, 4:7] view goes in by its pitch; a transposed or broadcast one is copied
+                pitch = max(int(a.stride(0)), c) if n > 1 else c
+            out.append(_Attr(a, ATTR_SRC_KINDS[name], pitch, (n, c), np.dtype(name) if scale is None else dtype))
         return out
+
+    @staticmethod
+    def _staged(attrs):
+        """whether the attributes of a call go through pcc_attr_stage_frames (all or none do)"""
+        return bool(attrs) and isinstance(attrs[0], _Attr)
+
+    @staticmethod
+    def _stage_attributes(rt, attrs, caller, scale, channels=0, perm=None, dtype=None):
+        """_Attr records -> Runtime.attr_stage_frames' result: packed (channels 0) for the coders, or sorted rows of
+        `dtype` under the sort's permutation.  Device sources are read behind whatever the caller's stream still does
+        to them."""
+        if attrs[0].on_device:
+            rt.stream.wait_stream(caller)
+        bpv = np.dtype(dtype).itemsize if channels else max(a.dtype.itemsize if a.kind >= 2 else 1 for a in attrs)
+        return rt.attr_stage_frames([(a.src, a.kind, a.shape[1], a.pitch) for a in attrs], _ends([a.shape[0] for a in attrs]),
+                                    1.0 if scale is None else scale, bpv, channels, perm)
+
+    @staticmethod
+    def _check_stage_status(status, where):
+        """the status word of pcc_attr_stage_frames, read behind a synchronisation the call has had"""
+        bits = int(status.item())
+        if bits & 1:
+            raise PccError(PCC_E_RANGE, f"{where} (pcc_attr_stage_frames)", "non-finite attribute value (NaN or Inf)")
+        if bits & 2:
+            raise PccError(PCC_E_ARG, f"{where} (pcc_attr_stage_frames)", "a row of the permutation outside the call")
 
     @staticmethod
     def _check_lod(lod):
@@ -521,7 +643,7 @@ class GeometryCodec:
     def compress(self, frames, attributes=None, lod=0, scalable=False, *, voxel=None, origin=(0.0, 0.0, 0.0),
                  invalid="raise", return_index=False, max_error=0, cross_channel=False, qstep=0, colour=None,
                  scalable_to=None, target_bytes=None, target_frame_bytes=None, predict=None, intra_period=None, reference=None,
-                 history=None, predictor=None):
+                 history=None, predictor=None, attribute_scale=None, attribute_dtype=None):
         """frames: a sequence of int16 / int32 [n_f, 3] arrays -> a list of bytes, one version-2 blob per frame.
         Duplicate points are removed (as np.unique), out-of-range coordinates raise PccError (PCC_E_RANGE).
         lod = k > 0: the sender's side of a level of detail — blob f is the version-2 blob of the distinct cells
@@ -588,8 +710,20 @@ class GeometryCodec:
         Frame types: numpy int16 / int32 as above, numpy float32, or torch tensors of those three dtypes on the host or
         on this codec's device; all frames of a call integer or all float32, all on the host or all on the device
         (ValueError naming the frame otherwise; a tensor on another device: ValueError; float64: TypeError).  Device
-        frames are not staged through the host.  Attributes stay host arrays with every frame type (device-resident
-        attribute tensors are not supported).
+        frames are not staged through the host.
+        Attribute types: numpy uint8 / uint16 as above (the staging and the bytes of before), or torch tensors of those
+        two dtypes on this codec's device, read where they lie (pcc_attr_stage_frames; include/pcc.h has the rule): a
+        view whose rows are contiguous, such as t[:, 4:7] of an interleaved tensor, goes in by its pitch, any other view
+        is made contiguous first.  The attributes of a call are all on the host or all on the device (ValueError naming
+        the frame; a tensor on another device: ValueError), whatever the place of the frames.  The caller's current
+        stream is waited for before the first read, as it is for device frames.
+        attribute_scale = s (a finite number, 0 < s <= 65535; bool or not a number: TypeError; out of range, without
+        attributes, or beside integer attributes: ValueError): the attributes are float32 / float64, on the host or on
+        the device, and every value becomes clip(rint(x * s), 0, peak) in its own precision, ties to even, on the device
+        for both places, so both give the same blobs.  attribute_dtype: np.uint8 or np.uint16 (anything else:
+        ValueError), what they become; the default is uint8 where s <= 255, else uint16.  A NaN or Inf value raises
+        PccError (PCC_E_RANGE).  s is not written into a blob: decompress returns the integers and the caller carries s,
+        as it carries voxel.  Float attributes without attribute_scale, and any other dtype (int32, float16): TypeError.
         voxel, origin: float32 frames are points in the caller's unit and need voxel > 0; the codec codes the lattice
         points q = rint((x - origin) / voxel), per coordinate in float32 (include/pcc.h has the rule; voxel and origin
         are narrowed to float32 once, and the blobs are those of compress([q])).  Neither is written into a blob.
@@ -646,7 +780,8 @@ class GeometryCodec:
             voxel, origin = self._check_grid(voxel, origin, "compress")
         elif voxel is not None:
             raise ValueError("voxel= with integer frames: they are on the lattice already")
-        attrs = None if attributes is None else self._check_attributes(frames, attributes)
+        scale, attr_dtype = self._check_attribute_scale(attribute_scale, attribute_dtype, attributes is not None)
+        attrs = None if attributes is None else self._check_attributes(frames, attributes, self._device, scale, attr_dtype)
         nb = len(frames)
         neighbours = self._check_predictor(predictor, attrs, max_error, qstep, colour, scalable_to, target_bytes, target_frame_bytes)
         coding = self._attr_coding(attrs, nb, lod, scalable, max_error, cross_channel, qstep, colour, scalable_to, target_bytes,
@@ -665,12 +800,13 @@ class GeometryCodec:
             return out[0] if len(out) == 1 else out
         if nb == 0:
             return result([], [], [])
-        caller = torch.cuda.current_stream(self.rt.device) if on_device else None      # inside `with rt` it is the codec's
+        attrs_on_device = self._staged(attrs) and attrs[0].on_device
+        caller = torch.cuda.current_stream(self.rt.device) if on_device or attrs_on_device else None      # inside `with rt` it is the codec's
         with self._lock, self.rt as rt:
             front = self._front(rt, frames, is_float, on_device, caller, "GeometryCodec.compress", lod, voxel, origin,
                                 invalid == "drop")
             if front.n_keep == 0:
-                return result(*self._nothing_coded(rt, front, attrs, coding, return_index, on_device))
+                return result(*self._nothing_coded(rt, front, attrs, coding, return_index, on_device, caller, scale))
             if predict is None:
                 blobs = rt.octree_encode_frames(front.keys, nb, 3 * lod)
             else:
@@ -680,7 +816,7 @@ class GeometryCodec:
             if attrs is not None:
                 if target_frame_bytes is not None:      # what the geometry blob leaves; nothing left: a target no blob meets, the coarsest steps
                     coding = coding._replace(targets=tuple(max(1, t - len(b)) for t, b in zip(coding.targets, blobs)))
-                attr_blobs = self._encode_attributes(rt, attrs, blobs, front, 3 * lod, coding)
+                attr_blobs = self._encode_attributes(rt, attrs, blobs, front, 3 * lod, coding, caller, scale)
             if return_index:
                 first_run = torch.empty(nb, dtype=torch.int64, pin_memory=True)
                 np.cumsum([0] + [struct.unpack_from("<I", b, 4)[0] for b in blobs[:-1]], out=first_run.numpy())
@@ -851,11 +987,12 @@ class GeometryCodec:
         distinct = keys if n_u.value == n_keep else rt.gather_rows(keys, rows[:n_u.value])
         return front._replace(perm=perm, sorted_keys=keys, rows=rows, n_unique=n_u.value, keys=distinct)
 
-    def _nothing_coded(self, rt, front, attrs, coding, return_index, on_device):
+    def _nothing_coded(self, rt, front, attrs, coding, return_index, on_device, caller=None, scale=None):
         """(blobs, attribute blobs, index) of a call none of whose rows is coded: the empty blobs, the attribute blobs
         of frames without points (whatever the targets), and -1 for every input row"""
         blobs = rt.octree_encode_frames(rt.empty((0,), torch.int64), front.nb)
-        attr_blobs = None if attrs is None else self._encode_attributes(rt, attrs, blobs, front, 0, coding._replace(targets=None))
+        attr_blobs = None if attrs is None else self._encode_attributes(rt, attrs, blobs, front, 0, coding._replace(targets=None),
+                                                                                 caller, scale)
         if not return_index:
             return blobs, attr_blobs, None
         index = torch.full((front.n,), -1, dtype=torch.int32, device=rt.device)
@@ -871,26 +1008,36 @@ class GeometryCodec:
         return _split(index, sizes)
 
     @staticmethod
-    def _encode_attributes(rt, attrs, blobs, front, key_shift, coding):
+    def _encode_attributes(rt, attrs, blobs, front, key_shift, coding, caller=None, scale=None):
         # the values as they come, frame by frame at 16-byte offsets, in one upload; the merge into Morton order
         # happens on the device from the sort's permutation and the runs of equal keys
-        offs, at = [], 0
-        for a in attrs:
-            offs.append(at)
-            at += (a.nbytes + 15) // 16 * 16
-        host = torch.empty(max(at, 16), dtype=torch.uint8, pin_memory=True)
-        h = host.numpy()
-        for o, a in zip(offs, attrs):
-            h[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
-        values = rt.to_device(host) if at else None
+        status = None
+        if GeometryCodec._staged(attrs):      # device tensors and float values: the same layout, written by one kernel
+            values, offs, status = GeometryCodec._stage_attributes(rt, attrs, caller, scale)
+            if scale is None:
+                status = None      # integers as they are: nothing to report
+        else:
+            offs, at = [], 0
+            for a in attrs:
+                offs.append(at)
+                at += (a.nbytes + 15) // 16 * 16
+            host = torch.empty(max(at, 16), dtype=torch.uint8, pin_memory=True)
+            h = host.numpy()
+            for o, a in zip(offs, attrs):
+                h[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+            values = rt.to_device(host) if at else None
         formats = [a.dtype.itemsize | (a.shape[1] << 8) for a in attrs]
         points = [struct.unpack_from("<I", b, 4)[0] for b in blobs]
         n_kept = front.n_keep if front.n_keep < front.n else None      # None: no row was dropped
         call = (values, offs, formats, _ends(front.sizes), points, front.perm, front.rows, front.n_unique, front.keys, key_shift, n_kept)
         if coding.targets is None:
-            return rt._attr_encode(coding, *call)[0]
-        # a byte target: the steps from qstep upwards that the search chooses, frame by frame, through the public binding
-        return rt.attr_encode_frames_rate(*call, coding.qstep, coding.colour, list(coding.targets), coding.scratch_limit)[0]
+            attr_blobs = rt._attr_encode(coding, *call)[0]
+        else:
+            # a byte target: the steps from qstep upwards that the search chooses, frame by frame, through the public binding
+            attr_blobs = rt.attr_encode_frames_rate(*call, coding.qstep, coding.colour, list(coding.targets), coding.scratch_limit)[0]
+        if status is not None:      # behind the encode's own synchronisation
+            GeometryCodec._check_stage_status(status, "GeometryCodec.compress")
+        return attr_blobs
 
     def decompress(self, blobs, attr_blobs=None, output="numpy", lod=0, *, voxel=None, origin=(0.0, 0.0, 0.0), reference=None,
                    reference_lod=None):
@@ -1081,6 +1228,17 @@ class GeometryCodec:
         return rt.gather_rows(dev, perm)
 
     @staticmethod
+    def _sorted_any(rt, attrs, perm, dtype, channels, caller, scale, statuses):
+        """_sorted_values for host integer attributes; device tensors and float values in one pass of
+        pcc_attr_stage_frames instead, whose status word joins `statuses` for the caller to read behind its next
+        synchronisation"""
+        if not GeometryCodec._staged(attrs):
+            return GeometryCodec._sorted_values(rt, attrs, perm, dtype, channels)
+        values, _, status = GeometryCodec._stage_attributes(rt, attrs, caller, scale, channels, perm, dtype)
+        statuses.append(status)
+        return values
+
+    @staticmethod
     def _check_k(k, name):
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 3 <= k <= 32:
             raise ValueError(f"{name} must be an integer in 3 .. 32, got {k!r}")
@@ -1143,30 +1301,52 @@ class GeometryCodec:
             return _frames_out(rt, rt.gather_rows(distinct, index), sizes, output == "numpy")
 
     @staticmethod
-    def _check_normals(frames, normals):
-        """given normals: one finite float32 [n_f, 3] host array per frame"""
+    def _check_normals(frames, normals, device=None):
+        """given normals: one finite float32 [n_f, 3] array per frame, all on the host or all tensors on `device` (the
+        codec's, as normals(output="device") returns them).  Device tensors are not read here: _device_normals checks
+        that they are finite, on the codec's stream."""
         normals = list(normals)
         if len(normals) != len(frames):
             raise ValueError(f"{len(normals)} normal arrays for {len(frames)} frames")
-        out = []
+        out, places = [], []
         for f, (a, p) in enumerate(zip(normals, frames)):
-            if isinstance(a, torch.Tensor):
-                if a.device.type != "cpu":
-                    raise TypeError(f"frame {f}: normals are host arrays, got a tensor on {a.device}")
+            on_device = isinstance(a, torch.Tensor) and a.device.type != "cpu"
+            if on_device:
+                if device is None or a.device != device:
+                    raise ValueError(f"frame {f}: normals on {a.device}, this codec runs on {device}")
+                a = a.detach()
+            elif isinstance(a, torch.Tensor):
                 a = a.detach().numpy()
-            a = np.asarray(a)
-            if a.dtype != np.float32:
+            else:
+                a = np.asarray(a)
+            places.append(on_device)
+            if places[-1] != places[0]:
+                raise ValueError(f"frame {f}: normals on the {'device' if on_device else 'host'}, frame 0's on the "
+                                 f"{'device' if places[0] else 'host'}: the normals of a call are all on the host or all on "
+                                 "the device")
+            if str(a.dtype).replace("torch.", "") != "float32":
                 raise TypeError(f"frame {f}: expected float32 normals, got {a.dtype}")
             if a.ndim != 2 or a.shape[1] != 3:
-                raise ValueError(f"frame {f}: expected normals of shape [n, 3], got {a.shape}")
+                raise ValueError(f"frame {f}: expected normals of shape [n, 3], got {tuple(a.shape)}")
             if a.shape[0] != p.shape[0]:
                 raise ValueError(f"frame {f}: {a.shape[0]} normals for {p.shape[0]} points")
-            if not np.isfinite(a).all():
+            if not on_device and not np.isfinite(a).all():
                 raise ValueError(f"frame {f}: non-finite normal")
-            out.append(np.ascontiguousarray(a))
+            out.append(a if on_device else np.ascontiguousarray(a))
         return out
 
-    def distortion(self, frames_a, frames_b, attributes_a=None, attributes_b=None, peak=None, normals_a=None, normal_k=16):
+    @staticmethod
+    def _device_normals(rt, given, caller):
+        """given normals on the device -> one float32 [n, 3] tensor of the call's rows, behind the caller's stream; a
+        non-finite one raises ValueError naming its frame (one flag per frame, one read-back)"""
+        rt.stream.wait_stream(caller)
+        finite = torch.stack([torch.isfinite(a).all() for a in given]).tolist()
+        if not all(finite):
+            raise ValueError(f"frame {finite.index(False)}: non-finite normal")
+        return torch.cat(given, 0).contiguous()
+
+    def distortion(self, frames_a, frames_b, attributes_a=None, attributes_b=None, peak=None, normals_a=None, normal_k=16, *,
+                   attribute_scale=None, attribute_dtype=None):
         """The D1 (point-to-point) distortion between two sequences of lattice frames, frame by frame, by exact nearest
         neighbours on the device (pcc_nn_frames; include/pcc.h has the rule) -> one dict per frame:
 
@@ -1188,13 +1368,17 @@ class GeometryCodec:
         compress was given, or decompress without voxel= returns; metric distances are these times voxel^2.  A frame
         pair with points on one side and none on the other raises ValueError naming the frame; two empty frames give
         0.0 and inf.  Cells of a level of detail compare as their centres: (cells << k) + ((1 << k) >> 1).
-        attributes_a, attributes_b: host uint8 / uint16 [n] or [n, c] per frame, as compress takes them, dtype and
-        channel count equal per frame pair; both sides must then be free of duplicate points (ValueError naming the
-        frame): the typical call compares a lossless decode with a lossy one.
+        attributes_a, attributes_b: uint8 / uint16 [n] or [n, c] per frame, as compress takes them — host arrays or
+        tensors on this codec's device (both sides in one place), or float32 / float64 with attribute_scale= and
+        attribute_dtype= as compress reads them — dtype and channel count equal per frame pair; both sides must then be
+        free of duplicate points (ValueError naming the frame): the typical call compares a lossless decode with a lossy
+        one.  Device attributes are widened and brought into the sorted order in one pass (pcc_attr_stage_frames).
         normals_a: only side A (the original) carries normals, as with pc_error -n.  "estimate": the normals of A's
         distinct points from their normal_k (3 .. 32) nearest neighbours, as normals() gives them; A may hold duplicates,
-        a frame of A with 1 or 2 distinct points raises ValueError.  Or one finite float32 [n_f, 3] host array per frame,
-        row i the normal of row i of A, used as given: A must then be free of duplicate points."""
+        a frame of A with 1 or 2 distinct points raises ValueError.  Or one finite float32 [n_f, 3] array per frame, all
+        host arrays or all tensors on this codec's device (what normals(output="device") returns), row i the normal of
+        row i of A, used as given: A must then be free of duplicate points; a non-finite normal raises ValueError naming
+        the frame."""
         fa, float_a, dev_a = self._check_frames(frames_a)
         fb, float_b, dev_b = self._check_frames(frames_b)
         if float_a or float_b:
@@ -1211,9 +1395,15 @@ class GeometryCodec:
                                      and np.isfinite(peak) and peak > 0):
             raise ValueError(f"distortion: peak must be a positive number (grid extent - 1), got {peak!r}")
         attrs_a = attrs_b = None
+        scale, attr_dtype = self._check_attribute_scale(attribute_scale, attribute_dtype, attributes_a is not None)
         if attributes_a is not None:
-            attrs_a = self._check_attributes(fa, attributes_a)
-            attrs_b = self._check_attributes(fb, attributes_b)
+            attrs_a = self._check_attributes(fa, attributes_a, self._device, scale, attr_dtype)
+            attrs_b = self._check_attributes(fb, attributes_b, self._device, scale, attr_dtype)
+            places = [self._staged(x) and x[0].on_device for x in (attrs_a, attrs_b)]
+            if attrs_a and places[0] != places[1]:
+                raise ValueError(f"frame 0: attributes_a on the {'device' if places[0] else 'host'}, attributes_b on the "
+                                 f"{'device' if places[1] else 'host'}: the attributes of a call are all on the host or all "
+                                 "on the device")
             for f, (a, b) in enumerate(zip(attrs_a, attrs_b)):
                 if a.dtype != b.dtype or a.shape[1] != b.shape[1]:
                     raise ValueError(f"frame {f}: {a.dtype} attributes of {a.shape[1]} channels against {b.dtype} of "
@@ -1224,7 +1414,7 @@ class GeometryCodec:
                 raise ValueError(f"normals_a must be 'estimate' or one float32 [n, 3] array per frame, got {normals_a!r}")
             normal_k = self._check_k(normal_k, "normal_k")
         elif normals_a is not None:
-            given = self._check_normals(fa, normals_a)
+            given = self._check_normals(fa, normals_a, self._device)
         nb = len(fa)
         sizes_a = [int(a.shape[0]) for a in fa]
         sizes_b = [int(b.shape[0]) for b in fb]
@@ -1237,8 +1427,12 @@ class GeometryCodec:
         sse_ab = sse_ba = None
         d2_ab = d2_ba = [0.0] * nb
         if sum(sizes_a):
-            caller = torch.cuda.current_stream(self.rt.device) if dev_a else None
+            given_on_device = bool(given) and isinstance(given[0], torch.Tensor)
+            attrs_on_device = self._staged(attrs_a) and attrs_a[0].on_device
+            caller = torch.cuda.current_stream(self.rt.device) if dev_a or attrs_on_device or given_on_device else None
             with self._lock, self.rt as rt:
+                if given_on_device:
+                    given = self._device_normals(rt, given, caller)
                 front_a = self._front(rt, fa, False, dev_a, caller, "GeometryCodec.distortion")
                 front_b = self._front(rt, fb, False, dev_b, caller, "GeometryCodec.distortion")
                 if attrs_a is not None:
@@ -1257,10 +1451,13 @@ class GeometryCodec:
                     dtype = np.uint16 if any(a.dtype == np.uint16 for a in attrs_a) else np.uint8
                     channels = max(a.shape[1] for a in attrs_a)
                     channels = 4 if dtype == np.uint8 or channels > 2 else 2      # rows of 4 or 8 bytes (pcc_gather_rows)
-                    va = self._sorted_values(rt, attrs_a, front_a.perm, dtype, channels)
-                    vb = self._sorted_values(rt, attrs_b, front_b.perm, dtype, channels)
+                    statuses = []
+                    va = self._sorted_any(rt, attrs_a, front_a.perm, dtype, channels, caller, scale, statuses)
+                    vb = self._sorted_any(rt, attrs_b, front_b.perm, dtype, channels, caller, scale, statuses)
                     sse_ab = rt.nn_attr_sse_frames(front_a.sorted_keys, row_ab, va, vb, nb)
                     sse_ba = rt.nn_attr_sse_frames(front_b.sorted_keys, row_ba, vb, va, nb)
+                    for status in statuses:      # behind the synchronisation of the sums
+                        self._check_stage_status(status, "GeometryCodec.distortion")
         elif attrs_a is not None:
             sse_ab = sse_ba = [[0] * 4] * nb
         report = []
@@ -1296,6 +1493,8 @@ class GeometryCodec:
             normals = rt.knn_frames(front_a.keys, nb, normal_k)[3]
             if front_a.n_unique != front_a.n_keep:
                 of_query = rt.lookup(front_a.keys, front_a.sorted_keys)
+        elif isinstance(given, torch.Tensor):      # the call's rows on the device already (_device_normals)
+            normals = rt.gather_rows(given, front_a.perm)
         else:
             host = torch.empty((front_a.n, 3), dtype=torch.float32, pin_memory=True)
             np.concatenate(given, axis=0, out=host.numpy())
@@ -1315,7 +1514,8 @@ class GeometryCodec:
         raise ValueError(f"frame {f}: {sizes[f] - int(counts[f])} duplicate points in {side}: attributes are compared point by "
                          "point, so both sides must be free of duplicates (a decoded frame is)")
 
-    def transfer(self, frames_from, attributes, frames_to, output="numpy", return_counts=False):
+    def transfer(self, frames_from, attributes, frames_to, output="numpy", return_counts=False, *, attribute_scale=None,
+                 attribute_dtype=None):
         """The attributes of one geometry carried onto another (recolouring), frame by frame on the device
         (pcc_attr_transfer_frames; include/pcc.h has the rule) -> one array per frame, row i the value of row i of
         frames_to[f] as given: [n_to] for attributes given as [n], [n_to, c] otherwise, in the attributes' dtype.
@@ -1325,9 +1525,10 @@ class GeometryCodec:
         that no source row chose takes the merged value of its nearest source point.  Nearest is exact, ties go to the
         Morton-first point (the rule of distortion).  Rows of frames_to that share a point share its value.
         frames_from, frames_to: as distortion takes them, int16 / int32, numpy or torch, all on the host or all on this
-        codec's device, the same number on both sides; float32 frames raise TypeError.  attributes: host uint8 / uint16
-        [n] or [n, c] per frame of frames_from, as compress takes them.  A frame with targets and no source raises
-        ValueError naming the frame; a frame without targets gives [0] / [0, c].
+        codec's device, the same number on both sides; float32 frames raise TypeError.  attributes: uint8 / uint16
+        [n] or [n, c] per frame of frames_from, as compress takes them: host arrays, tensors on this codec's device, or
+        float32 / float64 values with attribute_scale= (and attribute_dtype=), the result then in the dtype they become.
+        A frame with targets and no source raises ValueError naming the frame; a frame without targets gives [0] / [0, c].
         output: "numpy" arrays, or "device": views of one tensor on this codec's device.  return_counts=True:
         (values, counts), counts[f] a uint32 [n_to]: the source rows assigned to the row's point, 0 where the value is
         the fallback."""
@@ -1344,8 +1545,9 @@ class GeometryCodec:
             raise ValueError("transfer: one side on the host, the other on the device: the frames of a call are all on "
                              "the host or all on the device")
         attributes = list(attributes)
-        flat = [np.ndim(a) == 1 for a in attributes]
-        attrs = self._check_attributes(ff, attributes)
+        flat = [(a.dim() if isinstance(a, torch.Tensor) else np.ndim(a)) == 1 for a in attributes]
+        scale, attr_dtype = self._check_attribute_scale(attribute_scale, attribute_dtype, True)
+        attrs = self._check_attributes(ff, attributes, self._device, scale, attr_dtype)
         nb = len(ff)
         sizes_f = [int(a.shape[0]) for a in ff]
         sizes_t = [int(a.shape[0]) for a in ft]
@@ -1367,13 +1569,15 @@ class GeometryCodec:
                 values, counts = values.numpy(), counts.numpy()
             values, counts = _split(values, sizes_t), _split(counts, sizes_t)
         else:
-            caller = torch.cuda.current_stream(self.rt.device) if dev_f else None
+            attrs_on_device = self._staged(attrs) and attrs[0].on_device
+            caller = torch.cuda.current_stream(self.rt.device) if dev_f or attrs_on_device else None
             with self._lock, self.rt as rt:
                 front_f = self._front(rt, ff, False, dev_f, caller, "GeometryCodec.transfer")
                 front_t = self._front(rt, ft, False, dev_t, caller, "GeometryCodec.transfer")
                 _, row_st, _ = rt.nn_frames(front_f.sorted_keys, front_t.keys, nb, want_dist=False)
                 _, row_ts, _ = rt.nn_frames(front_t.keys, front_f.keys, nb, want_dist=False)
-                sv = self._sorted_values(rt, attrs, front_f.perm, dtype, channels)
+                statuses = []
+                sv = self._sorted_any(rt, attrs, front_f.perm, dtype, channels, caller, scale, statuses)
                 distinct, cnt = rt.attr_transfer_frames(front_f.sorted_keys, front_f.rows, front_f.n_unique, sv, row_st, row_ts,
                                                         nb, want_count=return_counts)
                 # the distinct row of every target row as given: rows_index with no frame's rows taken off
@@ -1381,6 +1585,8 @@ class GeometryCodec:
                                       torch.zeros(nb, dtype=torch.int64, device=rt.device), nb)
                 values = _frames_out(rt, rt.gather_rows(distinct, index), sizes_t, to_host)
                 counts = _frames_out(rt, rt.gather_rows(cnt, index), sizes_t, to_host) if return_counts else None
+                for status in statuses:      # behind the synchronisation of _frames_out
+                    self._check_stage_status(status, "GeometryCodec.transfer")
         out = []
         for v, a, one in zip(values, attrs, flat):
             v = v[:, 0] if one else v[:, :a.shape[1]]

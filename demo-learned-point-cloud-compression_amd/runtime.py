@@ -263,6 +263,55 @@ class Runtime:
               "pcc_attr_transfer_frames")
         return out, count
 
+    def attr_stage_frames(self, sources, row_offsets, scale=1.0, bpv=1, channels=0, perm=None):
+        """per-point attributes from where they lie into the layout a consumer reads (pcc_attr_stage_frames, the rule of
+        include/pcc.h).  sources: per frame (src, kind, c, pitch) — src a 2-D device tensor (its data_ptr is the frame's
+        first value; pitch in elements) or a C-contiguous host array of the kind's dtype, which goes up raw in the one
+        pinned upload that carries the row offsets and the per-frame table; kind one of ATTR_SRC_KINDS' values.
+        row_offsets: the n_frames + 1 row offsets of the call.  scale: s of the rule, read for float kinds; bpv: bytes
+        per value of float sources (packed) or of every row (sorted).
+        channels == 0, packed: -> (values, value_offsets, status): a uint8 device tensor with frame f tight at
+        value_offsets[f] (16-aligned) in its own width, as attr_encode_frames takes them (None for a call without a
+        row).  channels 2 or 4, sorted: perm, the sort's permutation of the call's rows -> (values, None, status), values
+        [n, channels] uint8 / uint16.  status: an int32 [1] device tensor, bit 0 a non-finite value, bit 1 a perm entry
+        outside the call; not read here.  Does not synchronise."""
+        nf, n = len(sources), int(row_offsets[-1])
+        rec = np.dtype([("src", "<u8"), ("pitch", "<i8"), ("out", "<i8"), ("kind", "<i4"), ("c", "<i4")])
+        table_at = 8 * (nf + 1)
+        at = raw_at = (table_at + rec.itemsize * nf + 15) // 16 * 16
+        raws = []      # (frame, offset in the upload, host array)
+        for f, (src, _, _, _) in enumerate(sources):
+            if not isinstance(src, torch.Tensor) and src.size:
+                raws.append((f, at, src))
+                at += (src.nbytes + 15) // 16 * 16
+        host = torch.empty(at, dtype=torch.uint8, pin_memory=True)
+        h = host.numpy()
+        h[table_at + rec.itemsize * nf:raw_at] = 0
+        h[:table_at].view(np.int64)[:] = row_offsets
+        table = h[table_at:table_at + rec.itemsize * nf].view(rec)
+        dev = self.empty((at,), torch.uint8)      # before the table is written: the raw rows' addresses lie in it
+        out_at = 0
+        for f, (src, kind, c, pitch) in enumerate(sources):
+            rows = int(row_offsets[f + 1] - row_offsets[f])
+            own = (1, 2, bpv, bpv)[kind]
+            table[f] = (src.data_ptr() if isinstance(src, torch.Tensor) and rows else 0, pitch, out_at, kind, c)
+            out_at += (rows * c * own + 15) // 16 * 16
+        for f, o, a in raws:
+            h[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+            table["src"][f] = dev.data_ptr() + o
+        dev.copy_(host, non_blocking=True)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if channels:
+            out = self.empty((n, channels), torch.uint8 if bpv == 1 else torch.uint16)
+            nbytes = n * channels * bpv
+        else:
+            out = self.empty((max(out_at, 16),), torch.uint8) if n else None
+            nbytes = out_at if n else 0
+        check(self.lib.pcc_attr_stage_frames(self.ctx, C.c_void_p(host.data_ptr() + table_at), C.c_void_p(dev.data_ptr() + table_at),
+                                             C.c_void_p(host.data_ptr()), C.c_void_p(dev.data_ptr()), nf, float(scale), int(bpv),
+                                             int(channels), _ptr(perm), _ptr(out), nbytes, _ptr(status)), "pcc_attr_stage_frames")
+        return out, None if channels else table["out"].tolist(), status
+
     def knn_frames(self, keys, n_frames, k, want_rows=False, want_dist=False, want_cov=False, want_normals=True,
                    viewpoint=None):
         """the k nearest neighbours of every point of a frame among the frame's own points, their scatter matrix and
@@ -1051,6 +1100,8 @@ ATTR_COLOUR_KIND = 21
 ATTR_TRANSFORM_KINDS = (ATTR_TRANSFORM_KIND, ATTR_COLOUR_KIND)
 # version 21 under weights a decoder at a cut can form: decodes at lod 0 .. its scalable_to, from prefixes
 ATTR_SCALABLE_TRANSFORM_KIND = 22
+# what a value of an attribute source is (PCC_ATTR_SRC_* of include/pcc.h), by the name of its dtype
+ATTR_SRC_KINDS = {"uint8": 0, "uint16": 1, "float32": 2, "float64": 3}
 
 class AttrCoding(NamedTuple):
     """What kind of attribute blob an encode call writes, resolved and normalised once: what travels from

@@ -1746,6 +1746,75 @@ int pcc_attr_transfer_frames(pcc_ctx* ctx, const uint64_t* d_skeys, int64_t n_s,
                              int channels, int n_frames, void* d_out,
                              uint32_t* d_count);
 
+/* ---- attributes from where they lie on the device (csrc/attr_stage.hip) ---- */
+
+/* The rule (tests/attr_stage_ref.py restates it in numpy).  A per-point value
+ * reaches the attribute coders, pcc_nn_attr_sse_frames and
+ * pcc_attr_transfer_frames as a uint8 or uint16.
+ *   Integer sources (uint8, uint16) are taken as they are; a uint8 value in a
+ *   uint16 destination is zero-extended.
+ *   Float sources (float32, float64) are quantised with a scale s, per value:
+ *     v = clamp(rint(x * s), 0, peak),  peak = 255 (uint8) or 65535 (uint16)
+ *   in the source's own precision: one IEEE multiplication (__fmul_rn /
+ *   __dmul_rn, nothing contracted), round-half-to-even, and the clamp on the
+ *   float before it becomes an integer.  s is narrowed to float32 once for
+ *   float32 sources and used as a double for float64 sources.  -0.0 and
+ *   denormals give 0; a finite x whose product overflows gives 0 or peak by
+ *   its sign.  A non-finite x (NaN, +-Inf) sets status bit 0 and its output is
+ *   unspecified: an error for the caller (PCC_E_RANGE in GeometryCodec), as a
+ *   non-finite coordinate is.  s is not written into any blob: the caller
+ *   carries it, as it carries voxel.
+ *
+ *   pcc_attr_stage_frames : one launch on the context's stream, one thread per
+ *     row, no synchronisation, no scratch.  Per frame one record: d_src, the
+ *     first value of the frame's first row on the device; kind, what a value
+ *     is; channels c_f in 1 .. 4; pitch >= c_f, the distance of two rows in
+ *     ELEMENTS (a [:, 4:7] view of an interleaved array needs no copy);
+ *     out_offset (packed mode).  The records and the n_frames + 1 row offsets
+ *     (frame f = rows [offs[f], offs[f + 1]) of the call, offs[0] = 0) are
+ *     given twice, as the host arrays that are checked and as the copies on
+ *     the device that the kernel reads: a caller uploads both in one piece.
+ *     Two modes:
+ *       packed (channels == 0, d_perm NULL): frame f's rows tight as
+ *         [rows_f][c_f] at byte out_offset[f] of d_out — 16-aligned and
+ *         ascending, the d_values / h_value_offsets layout of
+ *         pcc_attr_encode_frames and its siblings.  An integer source keeps
+ *         its width, a float source gets bpv bytes per value.  Bytes between
+ *         two frames are not written.
+ *       sorted (channels 2 or 4 with bpv * channels == 4 or 8): d_out
+ *         [n][channels] of bpv bytes per value; row i is source row d_perm[i]
+ *         of the call, widened, channels c_f and above 0 — what
+ *         pcc_nn_attr_sse_frames and pcc_attr_transfer_frames take, in place of
+ *         a widening on the host, an upload and pcc_gather_rows.  A d_perm
+ *         entry >= n reads nothing, writes a zero row and sets status bit 1.
+ *     d_status: one int32 on the device, zeroed by the caller, OR-ed into.
+ *     Checked (PCC_E_ARG, pcc_last_error says which, nothing launched): null
+ *     arrays, n_frames outside 1 .. 65535, 2^27 rows or more, descending row
+ *     offsets, a bad kind, a channel count outside 1 .. 4 (sorted: above
+ *     channels), a pitch below c_f, a source not aligned to its elements, a
+ *     uint16 source into uint8 rows (sorted), value offsets that are not
+ *     16-aligned or overlap, more output than out_bytes, a d_out that is not
+ *     16-aligned, and a non-finite or non-positive scale when a float source
+ *     is present.  n == 0 launches nothing. */
+#define PCC_ATTR_SRC_U8 0
+#define PCC_ATTR_SRC_U16 1
+#define PCC_ATTR_SRC_F32 2
+#define PCC_ATTR_SRC_F64 3
+typedef struct pcc_attr_stage_frame {
+  const void* d_src;
+  int64_t pitch;      /* elements between two rows, >= channels */
+  int64_t out_offset; /* packed mode: the frame's first byte in d_out */
+  int32_t kind;       /* PCC_ATTR_SRC_* */
+  int32_t channels;   /* 1 .. 4 */
+} pcc_attr_stage_frame; /* 32 bytes */
+int pcc_attr_stage_frames(pcc_ctx* ctx, const pcc_attr_stage_frame* h_frames,
+                          const pcc_attr_stage_frame* d_frames,
+                          const int64_t* h_row_offsets,
+                          const int64_t* d_row_offsets, int n_frames,
+                          double scale, int bpv, int channels,
+                          const uint32_t* d_perm, void* d_out,
+                          int64_t out_bytes, int32_t* d_status);
+
 /* ---- whole-GOP entry points ------------------------------ */
 
 /* replaces: CompressionPipeline.compress() (sender/encoder/codec_pipeline.py:
