@@ -97,6 +97,8 @@ PROTOTYPES = {
     "pcc_octree_decode_frames_refs_lod": (i32, [vp, C.POINTER(C.c_void_p), pi64, i32, C.POINTER(C.c_void_p), pi64, i32, i32, vp, vp, i64,
                                                 pi64]),
     "pcc_merge_keys": (i32, [vp, C.POINTER(C.c_void_p), pi64, i32, i32, vp, i64, pi64]),
+    "pcc_octree_encode_frames_inter_best": (i32, [vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, pi64]),
+    "pcc_merge_keys_nested": (i32, [vp, C.POINTER(C.c_void_p), pi64, i32, i32, vp, i64, pi64]),
     "pcc_octree_lod_info": (i32, [vp, i64, i32, pi64, pi64]),
     "pcc_attr_encode_frames": (i32, _AE + [vp, i64, pi64]),
     "pcc_attr_decode_frames": (i32, [vp, C.POINTER(C.c_void_p), pi64, i32, pi64, vp, vp, i64, pi64, pi32]),

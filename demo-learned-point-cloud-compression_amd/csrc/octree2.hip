@@ -49,6 +49,7 @@
 #include "octree2_blob.h"
 #include "octree4.h"
 #include "octree4_blob.h"
+#include "octree_best_host.h"
 
 #include <string.h>
 
@@ -92,6 +93,12 @@ struct O2Frame {
   int32_t depth;
   uint32_t n_points;
   int32_t origin[3];
+  // A frame of the table is a CODING JOB over a tree, and several jobs may share one (the candidates of a frame under
+  // pcc_octree_encode_frames_inter_best, each against another reference): `tree` is where the call's level counts hold
+  // the tree's, rb_off where the job's own reference bytes lie (version 4).  One job per tree: tree = the job, rb_off =
+  // occ_off.
+  int32_t tree;
+  int64_t rb_off;
 };
 
 // What version 4 (a predicted frame: octree4.hip, include/pcc.h) adds to the coder's three kernels, REF = true: the
@@ -122,7 +129,7 @@ __global__ __launch_bounds__(256) void k_o2_stats(const uint8_t* __restrict__ oc
   for (int64_t node = b * blockDim.x + threadIdx.x; node < n_nodes; node += nb * blockDim.x) {
     const uint32_t byte = occ[node];
     uint32_t rbyte = 0;
-    if constexpr (REF) rbyte = ref.rb[tab[f].occ_off + node];
+    if constexpr (REF) rbyte = ref.rb[tab[f].rb_off + node];
     const int cls = node >= start_last ? 0 : (node >= start_prev ? 1 : 2);
     int ones = 0;
 #pragma unroll
@@ -185,7 +192,7 @@ __global__ __launch_bounds__(64) void k_o2_enc(const uint8_t* __restrict__ occ_a
   const uint32_t* rb32 = nullptr;
   uint32_t rdw_next = 0;
   if constexpr (REF) {
-    rb32 = reinterpret_cast<const uint32_t*>(ref.rb + tab[f].occ_off);
+    rb32 = reinterpret_cast<const uint32_t*>(ref.rb + tab[f].rb_off);
     rdw_next = rb32[(node0 >> 2) < last_dw ? (node0 >> 2) : last_dw];
   }
   for (int s = 0; s < S; s += 4) {
@@ -307,7 +314,7 @@ __global__ __launch_bounds__(256) void k_o2_pack(const uint16_t* __restrict__ wo
   const uint16_t* states = states_all + h.cb * 2 * kLanes;
   const uint16_t* lens = lens_all + h.cb * kLanes;
   const uint32_t* words = words_all + h.cb;
-  const uint32_t* counts = counts_all + (int64_t)PCC_OCT_CSTRIDE * f;
+  const uint32_t* counts = counts_all + (int64_t)PCC_OCT_CSTRIDE * h.tree;
   const uint16_t* p0 = p0_all + kCtx * (int64_t)f;
   uint8_t* out = out_all + h.out_off;
   unsigned long long part = 0;
@@ -670,6 +677,22 @@ int o2_stage_reserve(pcc_ctx* ctx, size_t bytes) {
   return PCC_OK;
 }
 
+// the same with the first `keep` bytes of the staging carried over where it grows (what an earlier batch of the call
+// left there)
+static int o2_stage_reserve_keep(pcc_ctx* ctx, size_t bytes, size_t keep) {
+  if (bytes <= ctx->stage_cap || keep == 0) return o2_stage_reserve(ctx, bytes);
+  size_t want = ctx->stage_cap;
+  while (want < bytes) want *= 2;
+  PCC_HIP(hipStreamSynchronize(ctx->stream));
+  void* grown = nullptr;
+  PCC_HIP(hipHostMalloc(&grown, want, hipHostMallocDefault));
+  memcpy(grown, ctx->stage, std::min(keep, ctx->stage_cap));
+  (void)hipHostFree(ctx->stage);
+  ctx->stage = grown;
+  ctx->stage_cap = want;
+  return PCC_OK;
+}
+
 // ======================================================================== entry points (internal + C-ABI)
 
 static inline int64_t o2_round(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
@@ -694,9 +717,19 @@ struct O2In {   // one frame of an encode call: leaves d_keys[lo, lo + n) (n >= 
 // pred (version 4, octree4.hip): every frame of the batch is a predicted frame, pred[f] the keys of its reference
 // (ref_n keys on the device, Morton-sorted and distinct after the key shift).  One step is added in front of the
 // coder's launches: the reference byte of every node.
+//
+// job_tree (with pred; pcc_octree_encode_frames_inter_best): the batch holds nj CODING JOBS over the nf trees, job j a
+// blob of frame job_tree[j] against pred[j] — the levels of a frame are built once and shared by its candidates, every
+// job has its own reference bytes, context counts, probabilities and chunks.  offs, lens and pred are then per job.
+// stage_base: the batch leaves the first stage_base bytes of the staging as they are (an earlier batch's blobs) and
+// works behind them.  Without the two the batch queues what it queued before them.
 static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, const O2In* fr, int nf,
-                           std::vector<int64_t>* offs, std::vector<int64_t>* lens, const O4Pred* pred = nullptr) {
+                           std::vector<int64_t>* offs, std::vector<int64_t>* lens, const O4Pred* pred = nullptr,
+                           const int* job_tree = nullptr, int n_jobs = 0, size_t stage_base = 0) {
   hipStream_t st = ctx->stream;
+  const int nj = job_tree ? n_jobs : nf;
+  auto tree_of = [&](int j) { return job_tree ? job_tree[j] : j; };
+  PCC_REQUIRE(nj >= 1 && (!job_tree || pred), PCC_E_ARG, "octree blob v2: a batch of %d jobs", nj);
   const int KC = pred ? 3 * kCtx : kCtx;
   const int64_t s_max = pred ? kO4SMax : kSMax;
   const int64_t ref_head = pred ? 12 : 0;
@@ -708,6 +741,7 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
   for (int f = 0; f < nf; ++f) ns += fr[f].n <= small_max ? 1 : 0;
   int64_t occ_bytes = 0, waves = 0, leaves = 0;
   size_t coder_b = 3 * 256 + 4096, ref_b = 0, scan_b = 0;
+  std::vector<size_t> coder_of((size_t)nf), scan_of((size_t)nf);
   for (int f = 0, is = 0, il = 0; f < nf; ++f) {
     const O2In& g = fr[f];
     PCC_REQUIRE(g.n >= 1 && g.depth >= 1 && g.depth <= 16 && key_shift + 3 * g.depth <= 48, PCC_E_ARG,
@@ -730,49 +764,62 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
     // per leaf); a sparser batch (up to `depth` nodes per leaf) takes a block of its own for this call
     const int64_t guess = std::min<int64_t>(cap_of[(size_t)f], 5 * g.n / 2 + 64 * g.depth + 4096);
     const O2Layout l = o2_layout(guess, s_max);
-    coder_b += (size_t)l.nc * (8 * l.S * kLanes * 2 * 2 + 4 + 3 * kLanes * 2);   // records, word regions, tables
+    coder_of[(size_t)f] = (size_t)l.nc * (8 * l.S * kLanes * 2 * 2 + 4 + 3 * kLanes * 2);   // records, word regions, tables
     if (pred) {   // (the scans of the child counts take their block sums from the arena, frame after frame)
       ref_b = std::max(ref_b, o4_ref_scratch_bytes(guess, g.n));
-      scan_b += pcc_scan_scratch_bytes(cap_of[(size_t)f]) + 512;
+      scan_of[(size_t)f] = pcc_scan_scratch_bytes(cap_of[(size_t)f]) + 512;
     }
+  }
+  int64_t rb_bytes = 0;   // the jobs' reference bytes, each job's as many as its tree's occupancy bytes
+  std::vector<int64_t> rb_off((size_t)nj);
+  for (int j = 0; j < nj; ++j) {
+    const int t = tree_of(j);
+    PCC_REQUIRE(t >= 0 && t < nf, PCC_E_ARG, "octree blob v2: job %d codes frame %d of %d", j, t, nf);
+    coder_b += coder_of[(size_t)t];
+    scan_b += scan_of[(size_t)t];
+    rb_off[(size_t)j] = rb_bytes;
+    rb_bytes += cap_of[(size_t)t];
   }
   nl = nf - ns;
   PCC_REQUIRE(leaves < ((int64_t)1 << 27) && occ_bytes < ((int64_t)1 << 32), PCC_E_ARG, "octree blob v2: %lld leaves in %d frames",
               (long long)leaves, nf);
-  const size_t lt_b = pcc_align((size_t)nf * sizeof(PccOctFrame)), ct_b = pcc_align((size_t)nf * sizeof(O2Frame));
+  const size_t lt_b = pcc_align((size_t)nf * sizeof(PccOctFrame)), ct_b = pcc_align((size_t)nj * sizeof(O2Frame));
   const size_t counts_b = pcc_align((size_t)nf * PCC_OCT_CSTRIDE * 4);
-  const size_t pred_b = pred ? pcc_align((size_t)occ_bytes + 16) + 2 * pcc_align((size_t)nf * 8) + ref_b + scan_b + 4096 : 0;
-  PCC_TRY(pcc_arena_reserve(ctx, (size_t)occ_bytes + 16 + counts_b + pcc_align((size_t)nf * 2 * KC * 4) + pcc_align((size_t)nf * KC * 2) +
+  const size_t pred_b = pred ? pcc_align((size_t)rb_bytes + 16) + 2 * pcc_align((size_t)nj * 8) + ref_b + scan_b + 4096 : 0;
+  PCC_TRY(pcc_arena_reserve(ctx, (size_t)occ_bytes + 16 + counts_b + pcc_align((size_t)nj * 2 * KC * 4) + pcc_align((size_t)nj * KC * 2) +
                                      lt_b + ct_b + pcc_octree_frames_scratch(waves, nl) + coder_b + pred_b + 16384));
   uint8_t* occ = (uint8_t*)pcc_arena_alloc(ctx, (size_t)occ_bytes + 16);
   uint32_t* counts = (uint32_t*)pcc_arena_alloc(ctx, counts_b);
-  uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nf * 2 * KC * 4);
-  uint16_t* p0 = (uint16_t*)pcc_arena_alloc(ctx, (size_t)nf * KC * 2);
+  uint32_t* cnt = (uint32_t*)pcc_arena_alloc(ctx, (size_t)nj * 2 * KC * 4);
+  uint16_t* p0 = (uint16_t*)pcc_arena_alloc(ctx, (size_t)nj * KC * 2);
   O2Ref ref{nullptr, nullptr, nullptr};
   if (pred) {
-    ref.rb = (const uint8_t*)pcc_arena_alloc(ctx, (size_t)occ_bytes + 16);
-    ref.ref_n = (const uint32_t*)pcc_arena_alloc(ctx, (size_t)nf * 4);
-    ref.ref_sum = (const unsigned long long*)pcc_arena_alloc(ctx, (size_t)nf * 8);
+    ref.rb = (const uint8_t*)pcc_arena_alloc(ctx, (size_t)rb_bytes + 16);
+    ref.ref_n = (const uint32_t*)pcc_arena_alloc(ctx, (size_t)nj * 4);
+    ref.ref_sum = (const unsigned long long*)pcc_arena_alloc(ctx, (size_t)nj * 8);
     if (!ref.rb || !ref.ref_n || !ref.ref_sum) return PCC_E_NOMEM;
   }
   PccOctFrame* d_lt = (PccOctFrame*)pcc_arena_alloc(ctx, lt_b);
   O2Frame* d_ct = (O2Frame*)pcc_arena_alloc(ctx, ct_b);
   if (!occ || !counts || !cnt || !p0 || !d_lt || !d_ct) return PCC_E_NOMEM;
   PccProfScope prof(ctx, "octree2_encode", leaves, fr[0].depth, nf > 1 ? nf : 0, 0);
-  PCC_TRY(o2_stage_reserve(ctx, lt_b + counts_b));
-  memcpy(ctx->stage, lt.data(), (size_t)nf * sizeof(PccOctFrame));
-  PCC_HIP(hipMemcpyAsync(d_lt, ctx->stage, (size_t)nf * sizeof(PccOctFrame), hipMemcpyHostToDevice, st));
+  PCC_TRY(o2_stage_reserve_keep(ctx, stage_base + lt_b + counts_b, stage_base));
+  memcpy((char*)ctx->stage + stage_base, lt.data(), (size_t)nf * sizeof(PccOctFrame));
+  PCC_HIP(hipMemcpyAsync(d_lt, (char*)ctx->stage + stage_base, (size_t)nf * sizeof(PccOctFrame), hipMemcpyHostToDevice, st));
   PCC_TRY(pcc_octree_frames_async(ctx, d_keys, key_shift, lt.data(), d_lt, ns, nl, occ, counts));
-  uint32_t* hc = (uint32_t*)((char*)ctx->stage + lt_b);
+  uint32_t* hc = (uint32_t*)((char*)ctx->stage + stage_base + lt_b);
   PCC_HIP(hipMemcpyAsync(hc, counts, (size_t)nf * PCC_OCT_CSTRIDE * 4, hipMemcpyDeviceToHost, st));
-  PCC_HIP(hipMemsetAsync(cnt, 0, (size_t)nf * 2 * KC * 4, st));
+  PCC_HIP(hipMemsetAsync(cnt, 0, (size_t)nj * 2 * KC * 4, st));
   PCC_HIP(hipStreamSynchronize(st));
   // the coder's table from the level counts
   std::vector<uint32_t> level_counts;   // (version 4 reads them again behind the staging's next reservation)
   if (pred) level_counts.assign(hc, hc + (size_t)nf * PCC_OCT_CSTRIDE);
-  std::vector<O2Frame> ct((size_t)nf);
+  std::vector<O2Frame> ct((size_t)nj);
+  std::vector<int64_t> occ_of((size_t)nf);
+  for (const PccOctFrame& r : lt) occ_of[(size_t)r.slot] = r.occ_off;
   int64_t rec_words = 0, out_bytes = 0, chunks = 0, stats_blocks = 0;
-  for (int f = 0; f < nf; ++f) {
+  for (int j = 0; j < nj; ++j) {
+    const int f = tree_of(j);
     const uint32_t* c = hc + (size_t)PCC_OCT_CSTRIDE * f;
     const int depth = fr[f].depth;
     int64_t n_nodes = 0;
@@ -783,8 +830,10 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
     const O2Layout lay = o2_layout(n_nodes, s_max);
     const int64_t T = 8 * lay.S, cap_words = 3 * kLanes + kLanes * T;   // bound of a chunk in the blob
     const int64_t head = kHeader + 4 * depth + 8 + ref_head + 2 * KC + 4 * lay.nc;
-    O2Frame& r = ct[(size_t)f];
-    r.occ_off = 0;   // below, from the levels' table
+    O2Frame& r = ct[(size_t)j];
+    r.occ_off = occ_of[(size_t)f];
+    r.tree = f;
+    r.rb_off = job_tree ? rb_off[(size_t)j] : r.occ_off;
     r.n_nodes = n_nodes;
     r.start_last = n_nodes - (int64_t)c[depth - 1];
     r.start_prev = depth >= 2 ? r.start_last - (int64_t)c[depth - 2] : 0;
@@ -806,7 +855,8 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
     chunks += lay.nc;
     stats_blocks += r.sn;
   }
-  for (const PccOctFrame& r : lt) ct[(size_t)r.slot].occ_off = r.occ_off;
+  PCC_REQUIRE(chunks + nj < ((int64_t)1 << 31) && stats_blocks < ((int64_t)1 << 31), PCC_E_ARG,
+              "octree blob v2: %lld chunks in %d jobs", (long long)chunks, nj);
   struct Own {   // the rare block of its own, freed on every way out
     void* p = nullptr;
     ~Own() { if (p) (void)hipFree(p); }
@@ -816,7 +866,7 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
   // version 4: the scratch of the reference bytes, sized by the largest frame's nodes (the frames take it in turn)
   size_t ref_need = 0;
   if (pred)
-    for (int f = 0; f < nf; ++f) ref_need = std::max(ref_need, o4_ref_scratch_bytes(ct[(size_t)f].n_nodes, fr[f].n));
+    for (int j = 0; j < nj; ++j) ref_need = std::max(ref_need, o4_ref_scratch_bytes(ct[(size_t)j].n_nodes, fr[tree_of(j)].n));
   uint16_t *rec, *work;
   char *small, *ref_scratch;
   if (pcc_align(ctx->arena_off) + rec_b + work_b + small_b + ref_need + scan_b + 2048 <= ctx->arena_cap) {
@@ -837,17 +887,19 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
   uint16_t* lens_d = states + (size_t)chunks * 2 * kLanes;
   // staging: the coder's table on its way to the device | the blobs | their lengths
   const size_t lens_at = ct_b + (size_t)out_bytes;
-  PCC_TRY(o2_stage_reserve(ctx, lens_at + (size_t)nf * 8 + 64));
-  uint8_t* stage = (uint8_t*)ctx->stage;
-  memcpy(stage, ct.data(), (size_t)nf * sizeof(O2Frame));
-  PCC_HIP(hipMemcpyAsync(d_ct, stage, (size_t)nf * sizeof(O2Frame), hipMemcpyHostToDevice, st));
+  PCC_TRY(o2_stage_reserve_keep(ctx, stage_base + lens_at + (size_t)nj * 8 + 64, stage_base));
+  uint8_t* stage = (uint8_t*)ctx->stage + stage_base;
+  memcpy(stage, ct.data(), (size_t)nj * sizeof(O2Frame));
+  PCC_HIP(hipMemcpyAsync(d_ct, stage, (size_t)nj * sizeof(O2Frame), hipMemcpyHostToDevice, st));
   long long* len_dev = (long long*)(stage + lens_at);
   if (pred) {
-    std::vector<O4RefJob> jobs((size_t)nf);
-    for (int f = 0; f < nf; ++f) {
-      O4RefJob& j = jobs[(size_t)f];
+    std::vector<O4RefJob> jobs((size_t)nj);
+    for (int q = 0; q < nj; ++q) {
+      const int f = tree_of(q);
+      O4RefJob& j = jobs[(size_t)q];
       const uint32_t* c = level_counts.data() + (size_t)PCC_OCT_CSTRIDE * f;
-      j.occ_off = ct[(size_t)f].occ_off;
+      j.occ_off = ct[(size_t)q].occ_off;
+      j.rb_off = ct[(size_t)q].rb_off;
       j.n_points = fr[f].n;
       j.depth = fr[f].depth;
       int64_t run = 0;
@@ -856,38 +908,38 @@ static int o2_encode_batch(pcc_ctx* ctx, const uint64_t* d_keys, int key_shift, 
         if (L < j.depth) run += (int64_t)c[L];
       }
       for (int a = 0; a < 3; ++a) j.origin[a] = fr[f].origin[a];
-      j.ref_keys = pred[f].ref_keys;
-      j.ref_n = pred[f].ref_n;
+      j.ref_keys = pred[q].ref_keys;
+      j.ref_n = pred[q].ref_n;
     }
-    PCC_TRY(o4_ref_bytes_async(ctx, key_shift, jobs.data(), nf, occ, (uint8_t*)ref.rb, (uint32_t*)ref.ref_n,
+    PCC_TRY(o4_ref_bytes_async(ctx, key_shift, jobs.data(), nj, occ, (uint8_t*)ref.rb, (uint32_t*)ref.ref_n,
                                (unsigned long long*)ref.ref_sum, ref_scratch, ref_need + 256));
-    hipLaunchKernelGGL(k_o2_stats<true>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nf, cnt, ref);
+    hipLaunchKernelGGL(k_o2_stats<true>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nj, cnt, ref);
     PCC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_o2_enc<true>, dim3((unsigned)chunks), dim3(64), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nf,
+    hipLaunchKernelGGL(k_o2_enc<true>, dim3((unsigned)chunks), dim3(64), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nj,
                        (const uint32_t*)cnt, rec, work, states, lens_d, words, p0, ref);
     PCC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_o2_pack<true>, dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work, (const O2Frame*)d_ct, nf,
+    hipLaunchKernelGGL(k_o2_pack<true>, dim3((unsigned)(chunks + nj)), dim3(256), 0, st, (const uint16_t*)work, (const O2Frame*)d_ct, nj,
                        (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words, (const uint32_t*)counts,
                        (const uint16_t*)p0, stage + ct_b, len_dev, ref);
     PCC_CHECK_LAUNCH();
   } else {
-    hipLaunchKernelGGL(k_o2_stats<false>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nf, cnt, ref);
+    hipLaunchKernelGGL(k_o2_stats<false>, dim3((unsigned)stats_blocks), dim3(256), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nj, cnt, ref);
     PCC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_o2_enc<false>, dim3((unsigned)chunks), dim3(64), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nf,
+    hipLaunchKernelGGL(k_o2_enc<false>, dim3((unsigned)chunks), dim3(64), 0, st, (const uint8_t*)occ, (const O2Frame*)d_ct, nj,
                        (const uint32_t*)cnt, rec, work, states, lens_d, words, p0, ref);
     PCC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_o2_pack<false>, dim3((unsigned)(chunks + nf)), dim3(256), 0, st, (const uint16_t*)work, (const O2Frame*)d_ct, nf,
+    hipLaunchKernelGGL(k_o2_pack<false>, dim3((unsigned)(chunks + nj)), dim3(256), 0, st, (const uint16_t*)work, (const O2Frame*)d_ct, nj,
                        (const uint16_t*)states, (const uint16_t*)lens_d, (const uint32_t*)words, (const uint32_t*)counts,
                        (const uint16_t*)p0, stage + ct_b, len_dev, ref);
     PCC_CHECK_LAUNCH();
   }
   PCC_HIP(hipStreamSynchronize(st));
-  offs->resize((size_t)nf);
-  lens->resize((size_t)nf);
-  for (int f = 0; f < nf; ++f) {
+  offs->resize((size_t)nj);
+  lens->resize((size_t)nj);
+  for (int f = 0; f < nj; ++f) {
     const long long total = ((volatile long long*)len_dev)[f];
-    PCC_REQUIRE(total >= 0 && total <= ct[(size_t)f].out_cap, PCC_E_NOMEM, "octree blob v2: frame %d: blob beyond its bound", f);
-    (*offs)[(size_t)f] = (int64_t)ct_b + ct[(size_t)f].out_off;
+    PCC_REQUIRE(total >= 0 && total <= ct[(size_t)f].out_cap, PCC_E_NOMEM, "octree blob v2: frame %d: blob beyond its bound", tree_of(f));
+    (*offs)[(size_t)f] = (int64_t)(stage_base + ct_b) + ct[(size_t)f].out_off;
     (*lens)[(size_t)f] = total;
   }
   return PCC_OK;
@@ -1317,6 +1369,133 @@ extern "C" int pcc_octree_encode_frames_inter(pcc_ctx* ctx, const uint64_t* d_ke
               PCC_E_ARG, "%s: bad argument (n=%lld n_frames=%d key_shift=%d intra_period=%d ref_first=%d)", who, (long long)n,
               n_frames, key_shift, intra_period, ref_first);
   return o2_encode_frames_inter(who, ctx, d_keys, n, n_frames, key_shift, intra_period, ref_first, 1, h_out, cap, h_offsets);
+}
+
+// Intra or a window, chosen per frame (include/pcc.h has the rule; octree_best_host.h its host side).  Lossless coding
+// makes the original the decoded frame, so the choice for one frame changes nothing for another, and every candidate
+// of every frame is coded side by side: one batch of version 2 over the coded frames with points, one batch of version
+// 4 over all (frame, W) jobs, the levels of a frame built once in it.  In front of them the unions W = 2 .. Wmax of
+// every frame in one nested pass (o4_nest_async) and one synchronisation for their sizes.  The version-2 blobs stay in
+// the staging while the second batch works behind them; after its last synchronisation all lengths are on the host,
+// and only the winners are copied out.
+extern "C" int pcc_octree_encode_frames_inter_best(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int key_shift,
+                                                   int intra_period, int n_ref_frames, int history, uint8_t* h_out, int64_t cap,
+                                                   int64_t* h_offsets) {
+  const char* who = "pcc_octree_encode_frames_inter_best";
+  PCC_REQUIRE(ctx && h_out && h_offsets && n >= 0 && (n == 0 || d_keys) && n < ((int64_t)1 << 27) && n_frames >= 1 &&
+                  n_frames <= 65535 && key_shift >= 0 && key_shift % 3 == 0 && key_shift <= 45 && cap >= 0 && intra_period >= 0 &&
+                  history >= 1 && history <= kO4MaxWindow && n_ref_frames >= 0 && n_ref_frames <= history && n_ref_frames < n_frames,
+              PCC_E_ARG, "%s: bad argument (n=%lld n_frames=%d key_shift=%d intra_period=%d n_ref_frames=%d history=%d)", who,
+              (long long)n, n_frames, key_shift, intra_period, n_ref_frames, history);
+  std::vector<int64_t> offs;
+  std::vector<uint64_t> ends;
+  PCC_TRY(o2_frame_bounds(who, ctx, d_keys, n, n_frames, key_shift, &offs, &ends));
+  std::vector<int> wmax;
+  o4_best_windows(offs.data(), n_frames, n_ref_frames, intra_period, history, &wmax);
+  std::vector<O2In> fr[2];         // [0] every coded frame with points, [1] those with a window
+  std::vector<int> frame_of[2];
+  std::vector<int> job_tree, job_w;   // the version-4 jobs: index into fr[1], window
+  std::vector<O4Pred> pred;
+  std::vector<O4NestJob> nests;       // of the frames with Wmax >= 2
+  std::vector<size_t> nest_job;       // the job of a nest's window 1
+  int64_t room = 0, listed = 0;       // keys: of all unions, of all nests' lists
+  for (int f = n_ref_frames; f < n_frames; ++f) {
+    if (wmax[(size_t)f] < 0) continue;
+    O2In in;
+    in.lo = offs[(size_t)f];
+    in.n = offs[(size_t)f + 1] - in.lo;
+    octree_root(ends[2 * (size_t)f], ends[2 * (size_t)f + 1], key_shift, &in.depth, in.origin);
+    fr[0].push_back(in);
+    frame_of[0].push_back(f);
+    const int Wm = wmax[(size_t)f];
+    if (Wm == 0) continue;
+    const int64_t keys = offs[(size_t)f] - offs[(size_t)(f - Wm)];
+    PCC_REQUIRE(keys < ((int64_t)1 << 27), PCC_E_ARG, "%s: frame %d: the %d frames of its window hold %lld keys", who, f - n_ref_frames, Wm,
+                (long long)keys);
+    O4NestJob nj;
+    nj.nl = Wm;
+    int64_t run = 0;
+    for (int W = 1; W <= Wm; ++W) {   // list W - 1 = the frame W in front; union W's place in the call's block: below
+      nj.list[W - 1] = d_keys + offs[(size_t)(f - W)];
+      nj.n[W - 1] = offs[(size_t)(f - W + 1)] - offs[(size_t)(f - W)];
+      run += nj.n[W - 1];
+      nj.out[W - 1] = nullptr;
+      job_tree.push_back((int)fr[1].size());
+      job_w.push_back(W);
+      pred.push_back(W == 1 ? O4Pred{nj.list[0], nj.n[0]} : O4Pred{nullptr, room});
+      if (W >= 2) room += run;
+    }
+    if (Wm >= 2) {
+      nest_job.push_back(pred.size() - (size_t)Wm);
+      nests.push_back(nj);
+      listed += run;
+      PCC_REQUIRE(room < ((int64_t)1 << 31) && listed + 1 < ((int64_t)1 << 31), PCC_E_ARG,
+                  "%s: frame %d: the windows of the call hold %lld keys in all", who, f - n_ref_frames, (long long)room);
+    }
+    fr[1].push_back(in);
+    frame_of[1].push_back(f);
+  }
+  struct Own {   // the unions and the nested pass's scratch
+    void* p = nullptr;
+    ~Own() { if (p) (void)hipFree(p); }
+  } own;
+  std::vector<O4MergeDev> tab(nests.size());
+  std::vector<O4NestOut> outs(nests.size());
+  if (!nests.empty()) {
+    // before anything of the candidates is launched: one block for the unions, sum over frames and W of the keys of the
+    // windows' lists (the bound of sum |U_W|, whose sizes only the pass itself gives), and the pass's scratch
+    const size_t union_b = pcc_align((size_t)room * 8), scratch_b = o4_nest_scratch_bytes(listed, (int)nests.size());
+    if (hipMalloc(&own.p, union_b + scratch_b) != hipSuccess) {
+      (void)hipGetLastError();
+      own.p = nullptr;
+      pcc_set_error("%s: the unions of the call's windows do not fit: %lld keys in %d frames' windows take %lld bytes of device memory", who,
+                    (long long)room, (int)nests.size(), (long long)(union_b + scratch_b));
+      return PCC_E_NOMEM;
+    }
+    for (size_t i = 0; i < nests.size(); ++i)
+      for (int W = 2; W <= nests[i].nl; ++W) {
+        O4Pred& p = pred[nest_job[i] + (size_t)W - 1];
+        nests[i].out[W - 1] = (uint64_t*)own.p + p.ref_n;
+        p.ref_keys = nests[i].out[W - 1];
+      }
+    uint32_t* d_counts = nullptr;
+    std::vector<uint32_t> counts(nests.size() * kO4MaxWindow);
+    int rc = o4_nest_async(ctx, nests.data(), (int)nests.size(), key_shift, (char*)own.p + union_b, scratch_b, tab.data(), outs.data(),
+                           &d_counts);
+    if (rc == PCC_OK && hipMemcpyAsync(counts.data(), d_counts, counts.size() * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
+      pcc_set_error("%s: reading the sizes of the merged references failed", who);
+      rc = PCC_E_HIP;
+    }
+    const bool synced = hipStreamSynchronize(ctx->stream) == hipSuccess;   // (also what keeps `tab`, `outs` and `counts` until the copies are done)
+    PCC_TRY(rc);
+    PCC_REQUIRE(synced, PCC_E_HIP, "%s: the merge of the reference windows failed", who);
+    for (size_t i = 0; i < nests.size(); ++i)
+      for (int W = 2; W <= nests[i].nl; ++W) pred[nest_job[i] + (size_t)W - 1].ref_n = (int64_t)counts[i * kO4MaxWindow + (size_t)W - 1];
+  }
+  std::vector<O4BestCand> cands;
+  size_t stage_used = 0;
+  if (!fr[0].empty()) {
+    std::vector<int64_t> boff, blen;
+    PCC_TRY(o2_encode_batch(ctx, d_keys, key_shift, fr[0].data(), (int)fr[0].size(), &boff, &blen));
+    for (size_t i = 0; i < fr[0].size(); ++i) {
+      cands.push_back(O4BestCand{frame_of[0][i], 0, boff[i], blen[i]});
+      stage_used = std::max(stage_used, (size_t)(boff[i] + blen[i]));
+    }
+  }
+  if (!job_tree.empty()) {
+    std::vector<int64_t> boff, blen;
+    PCC_TRY(o2_encode_batch(ctx, d_keys, key_shift, fr[1].data(), (int)fr[1].size(), &boff, &blen, pred.data(), job_tree.data(),
+                            (int)job_tree.size(), (size_t)o2_round((int64_t)stage_used, 256)));
+    for (size_t j = 0; j < job_tree.size(); ++j) cands.push_back(O4BestCand{frame_of[1][(size_t)job_tree[j]], job_w[j], boff[j], blen[j]});
+  }
+  std::vector<int64_t> choice;
+  o4_best_choose(cands.data(), (int64_t)cands.size(), n_frames, &choice);
+  int64_t need = 0;
+  const int64_t wrote = o4_best_copy((const uint8_t*)ctx->stage, (int64_t)ctx->stage_cap, cands.data(), choice.data(), n_frames, n_ref_frames,
+                                     h_out, cap, h_offsets, &need);
+  PCC_REQUIRE(wrote != -2, PCC_E_HIP, "%s: a blob outside the staging", who);
+  PCC_REQUIRE(wrote >= 0, PCC_E_NOMEM, "%s: %lld bytes of blobs, capacity %lld", who, (long long)need, (long long)cap);
+  return PCC_OK;
 }
 
 static int o2_decode_frames(const char* who, pcc_ctx* ctx, const uint8_t* const* h_blobs, const int64_t* h_lens, int n_frames,

@@ -27,7 +27,9 @@
 // union of the window's frames, formed on the device by a merge of their sorted distinct keys (k_o4_merge_flag, one
 // scan, k_o4_merge_scatter; pcc_merge_keys) — for all predicted frames of an encode call in one go, and frame after
 // frame in a decode call, which keeps the keys of the last frames it decoded.  Everything behind the merge sees a
-// reference of more keys and nothing else.
+// reference of more keys and nothing else.  pcc_octree_encode_frames_inter_best codes a frame against EVERY window
+// 1 .. Wmax and keeps the shortest blob: its unions are nested, and one pass forms them all (k_o4_nest_scatter behind
+// the merge's flags and scan; pcc_merge_keys_nested).
 //
 // A level of detail (lod = k > 0; octree4_blob.h has the plan): a prefix of the blob holds the levels above the cut
 // Lc = max(depth - k, 0), and a node above the cut has child cubes of side >= 2^k, unions of whole lod-k cells, so its
@@ -200,6 +202,37 @@ __global__ __launch_bounds__(256) void k_o4_merge_scatter(const O4MergeDev* __re
     pos += (int64_t)(excl[b + below] - excl[b]);
   }
   J.out[pos] = key;   // pos < kept elements of the job <= its elements: the room the caller gave
+}
+
+// The nested unions of a job whose lists stand newest first (octree4.h): the flags and their scan are the merge's — a
+// key is kept where no list in front of its own, a newer one, holds it — and a kept key of list i belongs to every
+// union W > i.  Its place there is the kept keys below it in lists 0 .. W - 1, a running sum over the lists: one search
+// per list for all unions, where a merge per union would search W lists each.  The first element of a job leaves the
+// sizes: the kept keys of lists 0 .. W - 1, which lie in front of off[W].
+__global__ __launch_bounds__(256) void k_o4_nest_scatter(const O4MergeDev* __restrict__ tab, const O4NestOut* __restrict__ outs, int nj,
+                                                         int64_t total, int shift, const uint32_t* __restrict__ excl,
+                                                         uint32_t* __restrict__ counts) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  int job, i;
+  int64_t idx;
+  o4_mg_locate(tab, nj, g, &job, &i, &idx);
+  const O4MergeDev& J = tab[job];
+  if (g == J.base)
+    for (int W = 1; W <= kO4MaxWindow; ++W)
+      counts[(int64_t)kO4MaxWindow * job + W - 1] = W <= J.nl ? excl[J.base + J.off[W]] - excl[J.base] : 0u;
+  if (excl[g + 1] == excl[g]) return;
+  const uint64_t key = J.list[i][idx];
+  const uint64_t k = (key & kMask48) >> shift;
+  int64_t pos = 0;
+  for (int l = 0; l < J.nl; ++l) {
+    const int64_t below = l == i ? idx : o4_lower(J.list[l], J.off[l + 1] - J.off[l], k, shift);
+    const int64_t b = J.base + J.off[l];
+    pos += (int64_t)(excl[b + below] - excl[b]);
+    if (l < i) continue;
+    uint64_t* o = outs[job].out[l];   // union l + 1
+    if (o) o[pos] = key;              // pos < kept keys of lists 0 .. l <= their keys: the room the caller gave
+  }
 }
 
 // status |= 16 where the union at hand has another size than the blob's ref_n
@@ -511,18 +544,20 @@ int o4_ref_bytes_async(pcc_ctx* ctx, int key_shift, const O4RefJob* jobs, int nf
     t.bias = bias;
     t.key_shift = key_shift;
     const uint8_t* o = occ + j.occ_off;
-    PCC_HIP(hipMemsetAsync(link, 0, 4, st));   // the root's link; every other node's is written
-    hipLaunchKernelGGL(k_o4_popc, dim3(nblk(N, 256)), dim3(256), 0, st, o, N, pc);
-    PCC_CHECK_LAUNCH();
-    PCC_TRY(pcc_scan_exclusive_u32(ctx, pc, excl, N, nullptr));
-    // the whole tree at once: the first child of node i is node 1 + (child counts in front of i); the encoder's own
-    // bytes need no check, the status word is the scratch's tail
-    int32_t* st_dummy = (int32_t*)(scratch + scratch_b - 256);
-    hipLaunchKernelGGL(k_o4_link, dim3(nblk(N, 256)), dim3(256), 0, st, o, (const uint32_t*)excl, (int64_t)0, N, (int64_t)1,
-                       N + j.n_points, link, st_dummy);
-    PCC_CHECK_LAUNCH();
+    if (f == 0 || jobs[f - 1].occ_off != j.occ_off) {   // (else: the tree of the job before, its links still in the scratch)
+      PCC_HIP(hipMemsetAsync(link, 0, 4, st));   // the root's link; every other node's is written
+      hipLaunchKernelGGL(k_o4_popc, dim3(nblk(N, 256)), dim3(256), 0, st, o, N, pc);
+      PCC_CHECK_LAUNCH();
+      PCC_TRY(pcc_scan_exclusive_u32(ctx, pc, excl, N, nullptr));
+      // the whole tree at once: the first child of node i is node 1 + (child counts in front of i); the encoder's own
+      // bytes need no check, the status word is the scratch's tail
+      int32_t* st_dummy = (int32_t*)(scratch + scratch_b - 256);
+      hipLaunchKernelGGL(k_o4_link, dim3(nblk(N, 256)), dim3(256), 0, st, o, (const uint32_t*)excl, (int64_t)0, N, (int64_t)1,
+                         N + j.n_points, link, st_dummy);
+      PCC_CHECK_LAUNCH();
+    }
     hipLaunchKernelGGL(k_o4_ref, dim3(nblk(N, 256)), dim3(256), 0, st, (const uint32_t*)link, t, (int64_t)0, N, j.ref_keys,
-                       j.ref_n, (const uint32_t*)nullptr, rb + j.occ_off);
+                       j.ref_n, (const uint32_t*)nullptr, rb + j.rb_off);
     PCC_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_o4_keysum, dim3(nblk(j.ref_n, 256)), dim3(256), 0, st, j.ref_keys, j.ref_n, key_shift, bias,
                        ref_sum + f);
@@ -576,6 +611,55 @@ int o4_merge_async(pcc_ctx* ctx, const O4MergeJob* jobs, int nj, int key_shift, 
   return PCC_OK;
 }
 
+size_t o4_nest_scratch_bytes(int64_t total, int nj) {
+  return o4_merge_scratch_bytes(total, nj) + pcc_align((size_t)nj * sizeof(O4NestOut)) + pcc_align((size_t)nj * kO4MaxWindow * 4);
+}
+
+int o4_nest_async(pcc_ctx* ctx, const O4NestJob* jobs, int nj, int key_shift, char* scratch, size_t scratch_b, O4MergeDev* h_tab,
+                  O4NestOut* h_out, uint32_t** d_counts) {
+  hipStream_t st = ctx->stream;
+  int64_t total = 0;
+  for (int j = 0; j < nj; ++j) {
+    const O4NestJob& g = jobs[j];
+    O4MergeDev& d = h_tab[j];
+    PCC_REQUIRE(g.nl >= 1 && g.nl <= kO4MaxWindow, PCC_E_ARG, "nested unions of key lists: job %d has %d lists", j, g.nl);
+    d.base = total;
+    d.out = nullptr;
+    d.nl = g.nl;
+    int64_t run = 0;
+    for (int i = 0; i <= kO4MaxWindow; ++i) {
+      d.off[i] = run;
+      if (i < kO4MaxWindow) {
+        d.list[i] = i < g.nl ? g.list[i] : nullptr;
+        h_out[j].out[i] = i < g.nl ? g.out[i] : nullptr;
+      }
+      if (i < g.nl) {
+        PCC_REQUIRE(g.n[i] >= 0 && (g.n[i] == 0 || g.list[i]), PCC_E_ARG, "nested unions of key lists: job %d, list %d", j, i);
+        run += g.n[i];
+      }
+    }
+    PCC_REQUIRE(run >= 1, PCC_E_ARG, "nested unions of key lists: job %d has no keys", j);
+    total += run;
+  }
+  PCC_REQUIRE(nj >= 1 && total + 1 < ((int64_t)1 << 31) && o4_nest_scratch_bytes(total, nj) <= scratch_b, PCC_E_ARG,
+              "nested unions of key lists: %lld keys in %d jobs", (long long)total, nj);
+  uint32_t* flags = (uint32_t*)scratch;
+  O4MergeDev* d_tab = (O4MergeDev*)(scratch + pcc_align((size_t)(total + 1) * 4 + 16));
+  O4NestOut* d_out = (O4NestOut*)(scratch + o4_merge_scratch_bytes(total, nj));
+  uint32_t* counts = (uint32_t*)((char*)d_out + pcc_align((size_t)nj * sizeof(O4NestOut)));
+  PCC_TRY(pcc_arena_reserve(ctx, pcc_scan_scratch_bytes(total + 1) + 1024));
+  PCC_HIP(hipMemcpyAsync(d_tab, h_tab, (size_t)nj * sizeof(O4MergeDev), hipMemcpyHostToDevice, st));
+  PCC_HIP(hipMemcpyAsync(d_out, h_out, (size_t)nj * sizeof(O4NestOut), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_o4_merge_flag, dim3(nblk(total + 1, 256)), dim3(256), 0, st, (const O4MergeDev*)d_tab, nj, total, key_shift, flags);
+  PCC_CHECK_LAUNCH();
+  PCC_TRY(pcc_scan_exclusive_u32(ctx, flags, flags, total + 1, nullptr));
+  hipLaunchKernelGGL(k_o4_nest_scatter, dim3(nblk(total, 256)), dim3(256), 0, st, (const O4MergeDev*)d_tab, (const O4NestOut*)d_out, nj,
+                     total, key_shift, (const uint32_t*)flags, counts);
+  PCC_CHECK_LAUNCH();
+  *d_counts = counts;
+  return PCC_OK;
+}
+
 namespace {
 // a block of the call's own, and host memory on its way to the device: both outlive what the stream still holds
 struct O4Own {
@@ -589,6 +673,43 @@ struct O4Own {
   }
 };
 }  // namespace
+
+extern "C" int pcc_merge_keys_nested(pcc_ctx* ctx, const uint64_t* const* d_lists, const int64_t* h_n, int n_lists, int key_shift,
+                                     uint64_t* d_out, int64_t cap, int64_t* h_counts) {
+  const char* who = "pcc_merge_keys_nested";
+  PCC_REQUIRE(ctx && d_lists && h_n && h_counts && n_lists >= 1 && n_lists <= kO4MaxWindow && key_shift >= 0 && key_shift % 3 == 0 &&
+                  key_shift <= 45 && cap >= 0,
+              PCC_E_ARG, "%s: bad argument (n_lists=%d key_shift=%d)", who, n_lists, key_shift);
+  O4NestJob job;
+  int64_t total = 0, room = 0;
+  for (int i = 0; i < n_lists; ++i) {
+    PCC_REQUIRE(h_n[i] >= 0 && h_n[i] < ((int64_t)1 << 27) && (h_n[i] == 0 || d_lists[i]), PCC_E_ARG, "%s: list %d has %lld keys", who, i,
+                (long long)h_n[i]);
+    job.list[i] = d_lists[i];
+    job.n[i] = h_n[i];
+    job.out[i] = d_out ? d_out + room : nullptr;   // union i + 1: behind the rooms of the narrower ones
+    total += h_n[i];
+    room += total;
+    h_counts[i] = 0;
+  }
+  job.nl = n_lists;
+  if (total == 0) return PCC_OK;
+  PCC_REQUIRE(total < ((int64_t)1 << 27), PCC_E_ARG, "%s: %lld keys in the lists", who, (long long)total);
+  PCC_REQUIRE(d_out && cap >= room, PCC_E_NOMEM, "%s: the unions take room for %lld keys, %lld are given", who, (long long)room,
+              (long long)cap);
+  O4Own own(ctx->stream);
+  const size_t scratch_b = o4_nest_scratch_bytes(total, 1);
+  PCC_HIP(hipMalloc(&own.p, scratch_b));
+  own.tab.resize(1);
+  O4NestOut h_out;   // (on its way to the device until the synchronisation below, or own's)
+  uint32_t* d_counts = nullptr;
+  PCC_TRY(o4_nest_async(ctx, &job, 1, key_shift, (char*)own.p, scratch_b, own.tab.data(), &h_out, &d_counts));
+  uint32_t counts[kO4MaxWindow];
+  PCC_HIP(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, ctx->stream));
+  PCC_HIP(hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < n_lists; ++i) h_counts[i] = (int64_t)counts[i];
+  return PCC_OK;
+}
 
 extern "C" int pcc_merge_keys(pcc_ctx* ctx, const uint64_t* const* d_lists, const int64_t* h_n, int n_lists, int key_shift,
                               uint64_t* d_out, int64_t cap, int64_t* h_count) {

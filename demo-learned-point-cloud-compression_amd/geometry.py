@@ -48,8 +48,18 @@ CELLS of the frames in front of it (a cube above the cut is a union of whole cel
     (c_t,) = codec.decompress([cut[t]], lod=2, reference=c_t_minus_1, reference_lod=2)   # streaming: the cells of before
     (c_t,) = codec.decompress([cut[t]], lod=2, reference=pts_t_minus_1, reference_lod=0) # or lattice points
 
-Not built: choosing per frame the shorter of versions 2 and 4, motion compensation, prediction of attributes (they see
-only the decoded Morton order and are coded as before).
+predict="best" writes every frame as the SHORTEST of its candidates (include/pcc.h has the rule): its version-2 blob
+and its version-4 blobs against the windows 1 .. what history=K gives it; of equal lengths version 2, then the smaller
+window.  Recorded camera frames mostly stay version 2, LiDAR sweeps take a window, and a sender need not guess.  Every
+blob is byte for byte one that predict=None or predict="previous" writes, so decompress, geometry_info,
+reference_frames and lod_info take the sequence as it is.  The random-access points are the SCHEDULED intra frames
+(frame 0, intra_period): a version-2 blob chosen for its length decodes alone, but a frame behind it may reach past it.
+
+    blobs = codec.compress(frames, predict="best", history=4)              # intra_period, reference as under "previous"
+    [GeometryCodec.reference_frames(b) for b in blobs]                     # 0 = version 2, W = the window chosen
+
+Not built: motion compensation, prediction of attributes (they see only the decoded Morton order and are coded as
+before).
 
 Attributes are lossless (attribute blob version 1, csrc/attr.hip), one blob per frame beside its geometry blob; the
 values of duplicate points merge to their rounded mean per channel, (sum + cnt // 2) // cnt.
@@ -751,6 +761,14 @@ class GeometryCodec:
         Attributes of every kind, lod=k (frame and reference are both the cells), float32 and device frames,
         return_index and the byte targets combine with it as before: they see the decoded Morton order alone.  The
         defaults write the bytes of before.
+        predict="best": intra_period, reference and history mean what they mean under "previous", and every coded
+        frame that is not a scheduled intra frame is written as the shortest of its candidates — its version-2 blob
+        and, for W in 1 .. the window history=K gives it (None and 1: W = 1 alone), its version-4 blob against the
+        union of the W frames in front of it; of equal lengths version 2, then the smaller W.  Every blob is byte for
+        byte the one predict=None or predict="previous", history=W writes for the frame.  A version-2 blob written by
+        choice cuts no window: the frames behind it may reach past it, and only the scheduled intra frames are
+        random-access points.  It combines with everything "previous" combines with; target_frame_bytes reads the
+        lengths after the choice.
         predictor="neighbours" (with attributes; another string: ValueError, another type: TypeError): lossless
         attribute blobs of version 25 (include/pcc.h has the rule) — version 2's layout and prefixes, every value
         predicted from up to three Morton-first points of the coarser cells around its point instead of from one, about
@@ -811,7 +829,7 @@ class GeometryCodec:
                 blobs = rt.octree_encode_frames(front.keys, nb, 3 * lod)
             else:
                 blobs = self._encode_predicted(rt, front, nb, lod, intra_period, reference, is_float, on_device, caller, voxel,
-                                               origin, invalid == "drop", history)
+                                               origin, invalid == "drop", history, predict == "best")
             attr_blobs = index = None
             if attrs is not None:
                 if target_frame_bytes is not None:      # what the geometry blob leaves; nothing left: a target no blob meets, the coarsest steps
@@ -828,8 +846,8 @@ class GeometryCodec:
     def _check_predict(self, predict, intra_period, reference, is_float, on_device, nb, history=None):
         """predict, intra_period, reference and history of compress -> (the period the library takes: 0 = frame 0
         alone; the references as _check_frames returns frames, oldest first, or None; the window K)"""
-        if predict is not None and not (isinstance(predict, str) and predict == "previous"):
-            raise ValueError(f"predict must be None or 'previous', got {predict!r}")
+        if predict is not None and not (isinstance(predict, str) and predict in ("previous", "best")):
+            raise ValueError(f"predict must be None, 'previous' or 'best', got {predict!r}")
         if intra_period is not None:
             if isinstance(intra_period, bool) or not isinstance(intra_period, (int, np.integer)):
                 raise TypeError(f"intra_period must be an integer >= 1, got {intra_period!r}")
@@ -861,18 +879,22 @@ class GeometryCodec:
         return int(intra_period or 0), refs, history
 
     def _encode_predicted(self, rt, front, nb, lod, intra_period, reference, is_float, on_device, caller, voxel, origin, drop,
-                          history=1):
-        """the geometry blobs of a call under predict='previous': the call's distinct keys, behind the references' as
-        the first frames of the library's call where there are any.  history 1 is the call of before."""
+                          history=1, best=False):
+        """the geometry blobs of a call under predict='previous' or, best, 'best': the call's distinct keys, behind the
+        references' as the first frames of the library's call where there are any.  history 1 is the call of before."""
         m = 0 if reference is None else len(reference)
         if m:
             ref = self._front(rt, reference, is_float, on_device, caller, "GeometryCodec.compress (reference)", lod, voxel,
                               origin, drop)
             if ref.n_keep:      # (references without points predict nothing: frame 0 is intra)
                 keys = torch.cat([ref.keys, front.keys + (m << 48)])
+                if best:
+                    return rt.octree_encode_frames_inter_best(keys, nb + m, 3 * lod, intra_period, m, history)
                 if history == 1:
                     return rt.octree_encode_frames_inter(keys, nb + 1, 3 * lod, intra_period, ref_first=True)
                 return rt.octree_encode_frames_inter_hist(keys, nb + m, 3 * lod, intra_period, m, history)
+        if best:
+            return rt.octree_encode_frames_inter_best(front.keys, nb, 3 * lod, intra_period, 0, history)
         if history == 1:
             return rt.octree_encode_frames_inter(front.keys, nb, 3 * lod, intra_period)
         return rt.octree_encode_frames_inter_hist(front.keys, nb, 3 * lod, intra_period, 0, history)
@@ -890,8 +912,10 @@ class GeometryCodec:
     def geometry_info(blob):
         """what the head of a geometry blob of version 2 or 4 says: {"version", "points", "predicted",
         "reference_points"} — predicted False marks a random-access point of a sequence, a predicted blob decodes
-        only behind the frame it was coded against, whose point count is reference_points.  Host only; the blob whole,
-        or for version 4 exactly a prefix that lod_info names."""
+        only behind the frame it was coded against, whose point count is reference_points.  Under
+        compress(..., predict="best") that holds for the scheduled intra frames alone: a version-2 blob chosen for its
+        length decodes alone too, but a frame behind it may reach past it.  Host only; the blob whole, or for version 4
+        exactly a prefix that lod_info names."""
         return Runtime.octree_inter_info(bytes(blob))
 
     @staticmethod

@@ -813,6 +813,20 @@ class Runtime:
               "pcc_octree_encode_frames_inter_hist")
         return [out[offs[f]:offs[f + 1]].tobytes() for f in range(int(n_ref_frames), n_frames)]
 
+    def octree_encode_frames_inter_best(self, keys, n_frames, key_shift=0, intra_period=0, n_ref_frames=0, history=1):
+        """octree_encode_frames_inter_hist's arguments, every frame written as the shortest of its candidates
+        (pcc_octree_encode_frames_inter_best; include/pcc.h has the rule): its version-2 blob and its version-4 blobs
+        against the windows 1 .. what `history` gives it; of equal lengths version 2, then the smaller window.  A
+        version-2 blob written by choice cuts no window behind it."""
+        n = keys.shape[0]
+        cap = 8192 * n_frames + 17 * max(n, 1)
+        out = np.empty(cap, dtype=np.uint8)
+        offs = (C.c_int64 * (n_frames + 1))()
+        check(self.lib.pcc_octree_encode_frames_inter_best(self.ctx, _ptr(keys), n, n_frames, key_shift, int(intra_period),
+                                                           int(n_ref_frames), int(history), _np_ptr(out), cap, offs),
+              "pcc_octree_encode_frames_inter_best")
+        return [out[offs[f]:offs[f + 1]].tobytes() for f in range(int(n_ref_frames), n_frames)]
+
     def octree_decode_frames_refs(self, blobs, references=(), device=False, whole=False):
         """octree_decode_frames_ref with up to 8 references, oldest first (pcc_octree_decode_frames_refs): each an int32
         [n, 3] device tensor of distinct points in Morton order.  A version-4 blob says in its byte 3 how many of the
@@ -863,6 +877,22 @@ class Runtime:
         count = C.c_int64(0)
         check(self.lib.pcc_merge_keys(self.ctx, ptrs, ns, nl, int(key_shift), _ptr(out), total, C.byref(count)), "pcc_merge_keys")
         return out[:count.value]
+
+    def merge_keys_nested(self, lists, key_shift=0):
+        """the nested unions of 1 .. 8 lists of Morton keys, NEWEST FIRST (pcc_merge_keys_nested): lists as merge_keys
+        takes them -> [union 1, .., union len(lists)], union W that of lists[:W], int64 device tensors (views of one),
+        formed in one pass; of equal keys the one of the first list that holds it is kept."""
+        nl = len(lists)
+        sizes = [int(k.shape[0]) for k in lists]
+        rooms = list(np.cumsum(sizes)) if nl else []
+        out = torch.empty(max(int(sum(rooms)), 1), dtype=torch.int64, device=self.device)
+        ptrs = (C.c_void_p * max(nl, 1))(*[_ptr(k) if k.shape[0] else None for k in lists])
+        ns = (C.c_int64 * max(nl, 1))(*sizes)
+        counts = (C.c_int64 * max(nl, 1))()
+        check(self.lib.pcc_merge_keys_nested(self.ctx, ptrs, ns, nl, int(key_shift), _ptr(out), int(sum(rooms)), counts),
+              "pcc_merge_keys_nested")
+        starts = [int(sum(rooms[:w])) for w in range(nl)]
+        return [out[starts[w]:starts[w] + counts[w]] for w in range(nl)]
 
     @staticmethod
     def octree_inter_info(blob):

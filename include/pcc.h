@@ -856,6 +856,58 @@ int pcc_octree_decode_frames_lod(pcc_ctx* ctx, const uint8_t* const* h_blobs,
  *     reserved or launched.  ref_n and ref_sum are not compared (above); a
  *     window's union is formed from the cells' keys and its size stays on the
  *     device.
+ * Intra or a window, chosen per frame (_encode_frames_inter_best): positions,
+ *   reference frames, the scheduled intra frames (intra_period, frame 0
+ *   without a reference) and the empty-frame rule are those of history = K.
+ *   For a coded frame t with points that is not a scheduled intra frame (nor
+ *   behind a frame without points), Wmax_t is the window history = K gives it:
+ *   up to K frames directly in front, not past a scheduled intra frame (which
+ *   may be in it), not past a frame without points.  Its candidates are the
+ *   version-2 blob of the frame and, for every W in 1 .. Wmax_t, the version-4
+ *   blob against the union of the W frames in front of it, byte 3 = W - 1.
+ *   The frame gets the SHORTEST candidate; of equal lengths version 2 wins,
+ *   then the smaller W.  A version-2 blob written by choice does not cut the
+ *   windows of the frames behind it: only scheduled intra frames and frames
+ *   without points do.  Every blob written is byte for byte the blob that
+ *   _encode_frames / _encode_frames_inter_hist write for that frame with that
+ *   version and window, and the decode entries take such sequences as they
+ *   are: a blob says its version and its window itself, and a decoder merges
+ *   the W positions in front of a blob whatever their versions.
+ *   Random access: the random-access points of such a sequence are its
+ *   SCHEDULED intra frames.  A version-2 blob chosen for its length decodes
+ *   alone, but a frame behind it may reach past it, so a decoder that starts
+ *   there may lack frames a later blob needs.
+ *   _encode_frames_inter_best : the arguments of _encode_frames_inter_hist;
+ *     history is the largest window tried.  Lossless coding makes the original
+ *     the decoded frame, so the choice for one frame changes nothing for any
+ *     other, and all candidates of all frames are coded side by side: ONE
+ *     version-2 batch over the coded frames with points, ONE version-4 batch
+ *     over every (frame, W) candidate in which the occupancy levels of a frame
+ *     are built once and shared by its candidates (each has its own reference
+ *     bytes, counts, probabilities and lane coder run).  The unions W = 2 ..
+ *     Wmax of a frame are nested, U_W = U_(W-1) + frame t - W, and are formed
+ *     in one pass for all frames and all W (pcc_merge_keys_nested's kernels).
+ *     Host synchronisations are those of _encode_frames_inter_hist: the frame
+ *     bounds, the union sizes, level counts and lengths of each batch.  All
+ *     candidates' lengths are then on the host; only the winners are copied
+ *     out of the pinned staging.  Limits: fewer than 2^27 keys in a window,
+ *     fewer than 2^31 in the unions of a call (PCC_E_ARG naming the frame).
+ *     The unions take one block of device memory, 8 bytes per key of the sum
+ *     over frames and W >= 2 of the keys of the W frames (the bound of the sum
+ *     of |U_W|); a call whose block does not fit returns PCC_E_NOMEM saying
+ *     so before any candidate is launched.
+ *   pcc_merge_keys_nested : n_lists (1 .. 8) lists as pcc_merge_keys takes
+ *     them, NEWEST FIRST: union W, W = 1 .. n_lists, is the union of lists 0 ..
+ *     W - 1.  All of them in one pass: the keep flags (a key is kept where no
+ *     list in front of its own holds an equal one) and their scan are the
+ *     merge's, and the scatter places a kept key of list i into every union
+ *     W > i at the kept keys below it in lists 0 .. W - 1 — one search per
+ *     list and key where a merge per union takes W.  Union W is written at
+ *     d_out + sum over V < W of (h_n[0] + .. + h_n[V - 1]), with room for the
+ *     keys of its lists; cap >= the sum of those rooms (PCC_E_NOMEM).
+ *     h_counts[W - 1] = |union W| (one synchronisation).  As a set of compared
+ *     keys union W is pcc_merge_keys of lists 0 .. W - 1; of equal keys the
+ *     newest list's is kept.
  *   pcc_merge_keys : the union of 1 .. 8 lists of keys on the device, each
  *     strictly increasing under (key & (2^48 - 1)) >> key_shift (bits from 48
  *     up, the frame index of a call's keys, are carried along and not
@@ -903,6 +955,14 @@ int pcc_octree_decode_frames_refs_lod(pcc_ctx* ctx,
 int pcc_merge_keys(pcc_ctx* ctx, const uint64_t* const* d_lists,
                    const int64_t* h_n, int n_lists, int key_shift,
                    uint64_t* d_out, int64_t cap, int64_t* h_count);
+int pcc_octree_encode_frames_inter_best(pcc_ctx* ctx, const uint64_t* d_keys,
+                                        int64_t n, int n_frames, int key_shift,
+                                        int intra_period, int n_ref_frames,
+                                        int history, uint8_t* h_out,
+                                        int64_t cap, int64_t* h_offsets);
+int pcc_merge_keys_nested(pcc_ctx* ctx, const uint64_t* const* d_lists,
+                          const int64_t* h_n, int n_lists, int key_shift,
+                          uint64_t* d_out, int64_t cap, int64_t* h_counts);
 
 /* Lossless per-point attributes of such a sequence (near-lossless ones with a
  * bounded error: pcc_attr_encode_frames_nl below) (csrc/attr.hip: attribute
