@@ -340,3 +340,6 @@ extern "C" int pcc_knn_replay_host(const uint64_t* h_keys, int64_t n, int k, int
   else knn_replay<32>(h_keys, n, k, h_rows, h_sqdist, h_cov, h_normals, h_nodes);
   return PCC_OK;
 }
+
+// ---------------------------------------------------------------- outlier removal behind the same search
+#include "outlier.h"

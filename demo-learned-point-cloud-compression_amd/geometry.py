@@ -170,6 +170,15 @@ matrix of its k nearest neighbours, found exactly on the device; for shading, re
 
     normals = codec.normals(frames, k=16, viewpoint=(0, 0, 0))      # float32 [n_f, 3] per frame, row i = input row i
 
+Outlier removal (include/pcc.h has both rules): the pre-step of a capture pipeline, on the device — flying pixels and
+isolated returns are the most expensive points an octree codes.  Verdicts per frame over its distinct lattice points by
+exact k nearest neighbours, decided in integers; the rows returned are the caller's own, in input order.
+
+    kept = codec.filter(frames, method="statistical", k=16, std_ratio=2.0)      # Open3D's remove_statistical_outlier
+    kept, attrs = codec.filter(frames, attributes=rgb, method="radius", min_neighbours=4, radius2=9)
+    kept, mask, report = codec.filter(frames, return_mask=True, return_report=True, output="device")
+    blobs = codec.compress(codec.filter(frames))
+
 One Runtime (ctx + stream) per codec; calls on the same instance are serialised, instances on different threads run
 side by side.
 """
@@ -1323,6 +1332,159 @@ class GeometryCodec:
             index = rt.rows_index(front.perm, front.n_keep, front.rows, front.n_unique, front.offsets.data_ptr(),
                                   torch.zeros(nb, dtype=torch.int64, device=rt.device), nb)
             return _frames_out(rt, rt.gather_rows(distinct, index), sizes, output == "numpy")
+
+    @staticmethod
+    def _check_filter(method, k, std_ratio, min_neighbours, radius2):
+        """the rule's keywords of filter -> ("statistical", k, R = rint(256 std_ratio)) or ("radius", m, radius2)"""
+        if not (isinstance(method, str) and method in ("statistical", "radius")):
+            raise ValueError(f"method must be 'statistical' or 'radius', got {method!r}")
+        if method == "statistical":
+            for name, v in (("min_neighbours", min_neighbours), ("radius2", radius2)):
+                if v is not None:
+                    raise ValueError(f"{name} is a keyword of method='radius', not of method='statistical'")
+            k = GeometryCodec._check_k(16 if k is None else k, "k")
+            std_ratio = 2.0 if std_ratio is None else std_ratio
+            if isinstance(std_ratio, bool) or not isinstance(std_ratio, (int, float, np.integer, np.floating)):
+                raise TypeError(f"std_ratio must be a number in 0 .. 255, got {std_ratio!r}")
+            if not (np.isfinite(std_ratio) and 0 <= std_ratio <= 255):
+                raise ValueError(f"std_ratio must be a number in 0 .. 255, got {std_ratio!r}")
+            return method, k, Runtime.outlier_ratio(std_ratio)
+        for name, v in (("k", k), ("std_ratio", std_ratio)):
+            if v is not None:
+                raise ValueError(f"{name} is a keyword of method='statistical', not of method='radius'")
+        m = 4 if min_neighbours is None else min_neighbours
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
+            raise TypeError(f"min_neighbours must be an integer in 1 .. 31, got {m!r}")
+        if not 1 <= m <= 31:
+            raise ValueError(f"min_neighbours must be an integer in 1 .. 31, got {m!r}")
+        if radius2 is None:
+            raise ValueError("method='radius' needs radius2=, the squared radius in lattice units")
+        if isinstance(radius2, bool) or not isinstance(radius2, (int, np.integer)):
+            raise TypeError(f"radius2 must be a non-negative integer (squared lattice units), got {radius2!r}")
+        if radius2 < 0:
+            raise ValueError(f"radius2 must be a non-negative integer (squared lattice units), got {radius2!r}")
+        return method, int(m), int(radius2)
+
+    def filter(self, frames, attributes=None, method="statistical", k=None, std_ratio=None, min_neighbours=None, radius2=None,
+               return_mask=False, return_report=False, output="numpy", *, voxel=None, origin=(0.0, 0.0, 0.0), invalid="raise"):
+        """Outlier removal in front of compress, on the device (include/pcc.h has both rules): the rows of every frame
+        that are surface, in input order, as the caller gave them (dtype and values untouched) -> `kept`, one array per
+        frame; (kept, attrs) with attributes; then `mask` (return_mask) and `report` (return_report) behind them.
+        The verdicts are formed per frame over the frame's distinct lattice points by exact k nearest neighbours;
+        duplicate rows share their point's verdict.
+        method="statistical" (Open3D's remove_statistical_outlier): k, an integer in 3 .. 32 (default 16), the point
+        itself included; std_ratio, a number in 0 .. 255 (default 2.0), taken as R / 256 with R = rint(256 std_ratio).  A
+        point's score is the sum of floor(16 sqrt(d2)) over its neighbours, and a point stays iff its score is at most
+        mean + std_ratio * (sample standard deviation) of its frame's scores, decided exactly in integers.
+        method="radius" (remove_radius_outlier): a point stays iff at least min_neighbours (1 .. 31, default 4) OTHER
+        points of its frame lie within radius2, a non-negative integer in squared lattice units.
+        A keyword of the other method, an unknown method, a value out of range: ValueError; a bool or a value of the
+        wrong type: TypeError (k: ValueError, as normals raises).
+        frames: int16 / int32 lattice frames, or float32 frames with voxel= / origin= / invalid= exactly as compress
+        quantises them (the verdict is formed on the lattice, the rows returned are the caller's floats; a row dropped
+        under invalid="drop" is not kept); numpy or torch, all on the host or all on this codec's device.
+        attributes: one array per frame as compress takes them (uint8 / uint16 / float32 / float64, [n] or [n, c] with
+        c <= 4, host or device, views with a pitch): the kept rows come back as given, nothing is quantised or merged.
+        return_mask: bool [n_f] per frame, row i the verdict of input row i.  return_report: per frame a dict of Python
+        ints, "points" (distinct), "kept" (distinct kept), "rows_kept", and under "statistical" also "k_eff", "S1",
+        "S2", "threshold".  output: "numpy" arrays, or "device": tensors on this codec's device.
+        An empty frame comes back empty; a frame of one point is kept whole under "statistical" and dropped whole under
+        "radius"."""
+        method, p0, p1 = self._check_filter(method, k, std_ratio, min_neighbours, radius2)
+        if output not in ("numpy", "device"):
+            raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
+        if invalid not in ("raise", "drop"):
+            raise ValueError(f"invalid must be 'raise' or 'drop', got {invalid!r}")
+        frames, is_float, on_device = self._check_frames(frames)
+        if is_float:
+            if voxel is None:
+                raise ValueError("float32 frames need voxel=, the edge of a lattice cell in the frames' unit")
+            voxel, origin = self._check_grid(voxel, origin, "filter")
+        elif voxel is not None:
+            raise ValueError("voxel= with integer frames: they are on the lattice already")
+        attrs = flat = None
+        if attributes is not None:
+            attributes = list(attributes)
+            floats = [str(a.dtype if hasattr(a, "dtype") else np.asarray(a).dtype).replace("torch.", "") in ("float32", "float64")
+                      for a in attributes]
+            if any(floats) and not all(floats):
+                raise ValueError("the attributes of a call are all integer (uint8 / uint16) or all float")
+            # float values pass the checks as under a scale; nothing is quantised here
+            attrs = self._check_attributes(frames, attributes, self._device, 1.0 if any(floats) else None, np.dtype(np.uint8))
+            attrs = [a.src if isinstance(a, _Attr) else a for a in attrs]
+            flat = [getattr(a, "ndim", 2) == 1 for a in attributes]
+
+        def result(kept, kept_attrs, mask, report):
+            out = (kept,) if attrs is None else (kept, kept_attrs)
+            if return_mask:
+                out += (mask,)
+            if return_report:
+                out += (report,)
+            return out[0] if len(out) == 1 else out
+        nb = len(frames)
+        if nb == 0:
+            return result([], [], [], [])
+        statistical = method == "statistical"
+        attrs_on_device = attrs is not None and isinstance(attrs[0], torch.Tensor)
+        caller = torch.cuda.current_stream(self.rt.device) if on_device or attrs_on_device else None
+        with self._lock, self.rt as rt:
+            front = self._front(rt, frames, is_float, on_device, caller, "GeometryCodec.filter", 0, voxel, origin, invalid == "drop")
+            if attrs_on_device:
+                rt.stream.wait_stream(caller)
+            points, kept_points = [0] * nb, [0] * nb
+            sums = [(0, 0, 0)] * nb
+            thresholds = [Runtime.OUTLIER_KEEP_ALL] * nb
+            if front.n_keep == 0:
+                mask = torch.zeros(front.n, dtype=torch.uint8, device=rt.device)
+                kept_rows, ends = None, [0] * (nb + 1)
+            else:
+                if statistical:
+                    scores, sums = rt.outlier_scores_frames(front.keys, nb, p0)      # the call's synchronisation for the threshold
+                    thresholds = [Runtime.outlier_threshold(cnt, s1, s2, p1) for s1, s2, cnt in sums]
+                    keep, counts = rt.outlier_mask_frames(front.keys, nb, scores, thresholds)
+                    points = [cnt for _, _, cnt in sums]
+                else:
+                    keep, counts = rt.outlier_radius_frames(front.keys, nb, p0, p1)
+                # the distinct row of every input row: rows_index with no frame's rows taken off
+                index = rt.rows_index(front.perm, front.n_keep, front.rows, front.n_unique, front.offsets.data_ptr(),
+                                      torch.zeros(nb, dtype=torch.int64, device=rt.device), nb)
+                mask, kept_rows, ends = rt.outlier_compact_rows(index, keep, front.offsets.data_ptr(), nb)
+                rt.sync()      # the sizes of the result
+                ends = ends.cpu().tolist()
+                if statistical:
+                    kept_points = counts.cpu().tolist()
+                else:
+                    points, kept_points = (list(c) for c in zip(*counts.cpu().tolist()))
+            host_mask = None
+            if not on_device or (attrs is not None and not attrs_on_device) or (return_mask and output == "numpy"):
+                host_mask = _split(mask.cpu().numpy().view(np.bool_), front.sizes)
+
+            def take(a, f):
+                """the kept rows of frame f's array a, where it lies; then where `output` wants it"""
+                if isinstance(a, torch.Tensor):
+                    a2 = a if a.dim() == 2 else a[:, None]
+                    if a2.shape[1] > 1 and a2.stride(1) != 1:
+                        a2 = a2.contiguous()
+                    got = a2[:0] if ends[f + 1] == ends[f] else rt.take_rows(a2, kept_rows[ends[f]:ends[f + 1]])
+                    got = got.reshape((-1,) + tuple(a.shape[1:]))
+                    return got if output == "device" else got.cpu().numpy()
+                got = a[host_mask[f]]
+                return rt.to_device(got) if output == "device" else got
+            kept = [take(a, f) for f, a in enumerate(frames)]
+            kept_attrs = None if attrs is None else [take(a[:, 0] if flat[f] else a, f) for f, a in enumerate(attrs)]
+            masks = None
+            if return_mask:
+                masks = host_mask if output == "numpy" else _split(mask.view(torch.bool), front.sizes)
+            report = None
+            if return_report:
+                report = []
+                for f in range(nb):
+                    rep = {"points": int(points[f]), "kept": int(kept_points[f]), "rows_kept": int(ends[f + 1] - ends[f])}
+                    if statistical:
+                        rep.update(k_eff=min(p0, int(points[f])), S1=int(sums[f][0]), S2=int(sums[f][1]), threshold=int(thresholds[f]))
+                    report.append(rep)
+            rt.sync()      # a device result may be read from the caller's stream at once
+            return result(kept, kept_attrs, masks, report)
 
     @staticmethod
     def _check_normals(frames, normals, device=None):

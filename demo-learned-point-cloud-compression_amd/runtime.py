@@ -8,6 +8,7 @@ One Runtime per in-flight compress()/decompress() call (the reference runs up
 to three concurrent calls, sender/encoder/encoder.py:50).
 """
 import ctypes as C
+import math
 import os
 import struct
 import threading
@@ -328,6 +329,114 @@ class Runtime:
         check(self.lib.pcc_knn_frames(self.ctx, _ptr(keys), n, int(n_frames), k, _ptr(rows), _ptr(sqdist), _ptr(cov),
                                       _ptr(normals), vp), "pcc_knn_frames")
         return rows, sqdist, cov, normals
+
+    # ------------------------------------------------------------ outlier removal (the rules of include/pcc.h)
+    OUTLIER_KEEP_ALL = (1 << 64) - 1      # the threshold of a frame with fewer than 2 points
+
+    @staticmethod
+    def outlier_ratio(std_ratio):
+        """R = rint(256 std_ratio) of the statistical rule, std_ratio in 0 .. 255"""
+        return int(np.rint(256.0 * float(std_ratio)))
+
+    @staticmethod
+    def outlier_threshold(n, s1, s2, ratio):
+        """T of the statistical rule in Python integers: the largest t with n t <= S1 or
+        65536 (n - 1) (n t - S1)^2 <= R^2 n (n S2 - S1^2); n < 2 keeps everything.  Host only."""
+        n, s1, s2, ratio = int(n), int(s1), int(s2), int(ratio)
+        if n < 2:
+            return Runtime.OUTLIER_KEEP_ALL
+        return (s1 + math.isqrt(ratio * ratio * n * (n * s2 - s1 * s1) // (65536 * (n - 1)))) // n
+
+    def outlier_scores_frames(self, keys, n_frames, k):
+        """the statistical rule's scores (pcc_outlier_scores_frames).  keys: sorted distinct Morton keys on the device.
+        Returns (scores, sums): scores an int64 [n] device tensor holding the uint64 q_i, sums a list of (S1, S2, n) per
+        frame as Python ints, S2 joined from its two halves.  Synchronises."""
+        n = int(keys.shape[0])
+        scores = self.empty((n,), torch.int64)
+        sums = self.empty((int(n_frames), 4), torch.int64)
+        check(self.lib.pcc_outlier_scores_frames(self.ctx, _ptr(keys), n, int(n_frames), int(k), _ptr(scores), _ptr(sums)),
+              "pcc_outlier_scores_frames")
+        return scores, [(s1, lo + (hi << 32), cnt) for s1, lo, hi, cnt in self._u64_rows(sums)]
+
+    def outlier_mask_frames(self, keys, n_frames, scores, thresholds):
+        """keep = q <= T[frame] (pcc_outlier_mask_frames).  thresholds: n_frames Python ints below 2^64.  Returns (keep
+        uint8 [n], kept int64 [n_frames]) as device tensors.  Synchronises once, in front of the kernel (the checks of
+        the keys); the results are on this runtime's stream."""
+        n = int(keys.shape[0])
+        host = torch.empty(int(n_frames), dtype=torch.int64, pin_memory=True)
+        host.numpy().view(np.uint64)[:] = np.array([int(t) for t in thresholds], dtype=np.uint64)
+        keep = self.empty((n,), torch.uint8)
+        kept = self.empty((int(n_frames),), torch.int64)
+        check(self.lib.pcc_outlier_mask_frames(self.ctx, _ptr(keys), n, int(n_frames), _ptr(scores), _ptr(self.to_device(host)),
+                                               _ptr(keep), _ptr(kept)), "pcc_outlier_mask_frames")
+        return keep, kept
+
+    def outlier_radius_frames(self, keys, n_frames, min_neighbours, radius2):
+        """the radius rule (pcc_outlier_radius_frames).  Returns (keep uint8 [n], counts int64 [n_frames, 2]: points and
+        kept points per frame) as device tensors.  Synchronises once, in front of the search."""
+        n = int(keys.shape[0])
+        keep = self.empty((n,), torch.uint8)
+        counts = self.empty((int(n_frames), 2), torch.int64)
+        check(self.lib.pcc_outlier_radius_frames(self.ctx, _ptr(keys), n, int(n_frames), int(min_neighbours),
+                                                 min(int(radius2), Runtime.OUTLIER_KEEP_ALL), _ptr(keep), _ptr(counts)),
+              "pcc_outlier_radius_frames")
+        return keep, counts
+
+    def outlier_compact_rows(self, index, keep, offsets_ptr, n_frames):
+        """verdicts on distinct points -> the input rows of a call (pcc_outlier_compact_rows).  index: rows_index' result
+        with no frame's rows taken off; keep: uint8 per distinct point; offsets_ptr: the input rows' frame offsets on the
+        device.  Returns (mask uint8 [n], kept_rows int32 [n], kept_offsets int64 [n_frames + 1]) as device tensors:
+        kept_rows holds, for the kept rows in input order, the row's place inside its frame.  Does not synchronise."""
+        n = int(index.shape[0])
+        mask = self.empty((n,), torch.uint8)
+        kept_rows = self.empty((n,), torch.int32)
+        kept_offsets = self.empty((int(n_frames) + 1,), torch.int64)
+        check(self.lib.pcc_outlier_compact_rows(self.ctx, _ptr(index), n, _ptr(keep), int(keep.shape[0]), C.c_void_p(offsets_ptr),
+                                                int(n_frames), _ptr(mask), _ptr(kept_rows), _ptr(kept_offsets)),
+              "pcc_outlier_compact_rows")
+        return mask, kept_rows, kept_offsets
+
+    def take_rows(self, src, rows):
+        """the rows `rows` (an int32 device tensor holding uint32 indices) of the 2-D device tensor src, whose rows are
+        contiguous and may lie a pitch apart: pcc_gather_rows for tight rows of a multiple of 4 bytes, else
+        pcc_gather_rows_pitched"""
+        n, c = int(rows.shape[0]), int(src.shape[1])
+        row_bytes = c * src.element_size()
+        pitch = (int(src.stride(0)) if src.shape[0] > 1 else c) * src.element_size()
+        dst = self.empty((n, c), src.dtype)
+        if n == 0:
+            return dst
+        if pitch == row_bytes and row_bytes % 4 == 0:
+            check(self.lib.pcc_gather_rows(self.ctx, _ptr(src), _ptr(rows), n, row_bytes, _ptr(dst)), "pcc_gather_rows")
+        else:
+            check(self.lib.pcc_gather_rows_pitched(self.ctx, C.c_void_p(src.data_ptr()), int(src.shape[0]), pitch, _ptr(rows), n, row_bytes,
+                                                   _ptr(dst)), "pcc_gather_rows_pitched")
+        return dst
+
+    @staticmethod
+    def outlier_replay_host(keys, n_frames, k=3, min_neighbours=1, radius2=0, thresholds=None):
+        """both rules on the host (pcc_outlier_replay_host: the kernels' functions compiled for the host; no GPU
+        needed, not a product path).  keys: a uint64 numpy array, sorted and distinct.  Returns a dict: scores uint64
+        [n], sums [(S1, S2, n)] per frame, nodes uint32 [n]; keep uint8 [n] where thresholds (n_frames Python ints) are
+        given; keep_radius / nodes_radius under the bounded search, keep_unbounded / nodes_unbounded under the k-NN
+        search itself."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        n = int(keys.shape[0])
+        u64, u32, u8 = (lambda: np.zeros(n, np.uint64)), (lambda: np.zeros(n, np.uint32)), (lambda: np.zeros(n, np.uint8))
+        out = {"scores": u64(), "nodes": u32(), "keep_radius": u8(), "nodes_radius": u32(), "keep_unbounded": u8(),
+               "nodes_unbounded": u32()}
+        sums = np.zeros((int(n_frames), 4), np.uint64)
+        th = None if thresholds is None else np.array([int(t) for t in thresholds], dtype=np.uint64)
+        if th is not None:
+            out["keep"] = u8()
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        check(_abi.lib().pcc_outlier_replay_host(ptr(keys), n, int(n_frames), int(k), int(min_neighbours),
+                                                 min(int(radius2), Runtime.OUTLIER_KEEP_ALL), ptr(th), ptr(out["scores"]),
+                                                 ptr(sums), ptr(out.get("keep")), ptr(out["nodes"]), ptr(out["keep_radius"]),
+                                                 ptr(out["nodes_radius"]), ptr(out["keep_unbounded"]),
+                                                 ptr(out["nodes_unbounded"])), "pcc_outlier_replay_host")
+        out["sums"] = [(s1, lo + (hi << 32), cnt) for s1, lo, hi, cnt in sums.tolist()]
+        return out
 
     def nn_d2_frames(self, qkeys, row, rkeys, normals, n_frames, normal_row=None, want_proj=False):
         """the D2 (point-to-plane) side of a pairing (pcc_nn_d2_frames): row, nn_frames' rows of qkeys among rkeys;

@@ -1751,6 +1751,115 @@ int pcc_knn_replay_host(const uint64_t* h_keys, int64_t n, int k, int32_t* h_row
                         uint64_t* h_sqdist, int64_t* h_cov, float* h_normals,
                         uint32_t* h_nodes);
 
+/* ---- outlier removal by exact k-NN (csrc/outlier.h, behind csrc/knn.hip's search) -- */
+
+/* The rules (tests/outlier_ref.py restates them in Python integers).  Both are
+ * per frame, over the frame's n DISTINCT lattice points in Morton order (n
+ * sorted distinct keys, as pcc_knn_frames takes them); only points of the same
+ * frame are neighbours.
+ *
+ * Statistical (k in 3 .. 32, std_ratio >= 0).  The neighbours of a point are
+ * those of pcc_knn_frames at that k: the point itself at distance 0 (Open3D's
+ * nb_neighbors convention), k_eff = min(k, n), ties to the smaller row.
+ *   score      q_i = sum over j < k_eff of floor(16 sqrt(d2_ij)), an unsigned
+ *              integer.  Each term is the exact integer square root of d2 << 8
+ *              (d2 <= 3 * 65535^2, so d2 << 8 < 2^42): sqrt in float64 followed
+ *              by the fix-up  while (r*r > x) --r; while ((r+1)*(r+1) <= x) ++r;
+ *              so the result does not rest on how any sqrt rounds.  All points
+ *              of a frame share k_eff: comparing sums is comparing Open3D's
+ *              mean distances.  q_i < 32 * 2^21 = 2^26.
+ *   frame sums S1 = sum q_i and S2 = sum q_i^2, exact integers, independent of
+ *              the order of summation.  S1 < 2^53.  q_i^2 < 2^52 times
+ *              n <= 2^27 does not fit one word: the device accumulates
+ *              sum (q_i^2 & 0xffffffff) and sum (q_i^2 >> 32) in two uint64 and
+ *              the host joins them, S2 = lo + (hi << 32).
+ *   threshold  on the host, in arbitrary-precision integers, between the two
+ *              kernels.  R = rint(256 * std_ratio), std_ratio <= 255.  T is the
+ *              largest integer t with
+ *                n t <= S1   or   65536 (n - 1) (n t - S1)^2 <= R^2 n (n S2 - S1^2),
+ *              that is t <= mean + (R / 256) std with the sample standard
+ *              deviation (divisor n - 1) that Open3D uses.  In closed form
+ *                T = (S1 + isqrt(R^2 n (n S2 - S1^2) div (65536 (n - 1)))) div n.
+ *              A frame with n < 2 keeps everything: T = 2^64 - 1.  T is never
+ *              formed in floating point or on the device (the products pass
+ *              2^128).
+ *   verdict    point i is kept iff q_i <= T.
+ *
+ * Radius (min_neighbours m in 1 .. 31, radius2 a non-negative integer in
+ * squared lattice units).  Point i is kept iff at least m OTHER points of its
+ * frame lie at d2 <= radius2; equivalently n > m and slot m of its k-NN list
+ * at k = m + 1 (slot 0 is the point itself) has d2 <= radius2.  With
+ * m = nb_points this is Open3D's remove_radius_outlier (which counts the point
+ * itself and asks for more than nb_points).  radius2 above 3 * 65535^2 is legal
+ * and keeps every frame of more than m points.
+ *
+ *   pcc_outlier_scores_frames : d_keys: n sorted distinct keys of n_frames
+ *     frames.  One thread per point runs pcc_knn_frames' search and forms q_i
+ *     in the same thread; d_scores [n] takes q_i and d_sums [n_frames][4]
+ *     (zeroed by the call) takes S1, sum (q^2 & 0xffffffff), sum (q^2 >> 32) and
+ *     the frame's n.  Nothing of shape [n][k] is written.  Checked before
+ *     anything is launched (one synchronisation), as pcc_knn_frames checks:
+ *     k in 3 .. 32, n <= 2^27, n_frames in 1 .. 65535 (PCC_E_ARG); keys not
+ *     sorted (PCC_E_ARG) or not distinct (PCC_E_DUP); a frame index not below
+ *     n_frames (PCC_E_RANGE).  n = 0 launches nothing (the sums are zeroed).
+ *   pcc_outlier_mask_frames : d_keep [n] = q_i <= d_threshold[frame of i]
+ *     (1 / 0), d_kept [n_frames] (zeroed by the call) the kept points of every
+ *     frame.  d_threshold: n_frames uint64 on the device.  The same checks.
+ *   pcc_outlier_radius_frames : the radius rule; d_keep [n], d_counts
+ *     [n_frames][2] (zeroed by the call): the frame's n and its kept points.
+ *     The search holds m + 1 entries and its pruning bound never exceeds
+ *     radius2 + 1, so a point stops after the cells within its radius; the
+ *     verdict is the unbounded search's.  min_neighbours in 1 .. 31
+ *     (PCC_E_ARG), otherwise the same checks.
+ *   pcc_outlier_compact_rows : from verdicts on distinct points to the input
+ *     rows of a call.  d_index [n]: pcc_rows_index' result with no frame's rows
+ *     taken off (the distinct row of every input row over the whole call, -1
+ *     for a dropped row); d_keep [n_keys]; d_offsets [n_frames + 1]: the input
+ *     rows' frame offsets.  d_mask [n] (nullable): the verdict of every input
+ *     row; d_kept_rows [n]: for the kept rows in input order, the row's place
+ *     inside its own frame; d_kept_offsets [n_frames + 1]: the kept rows in
+ *     front of every frame, and their total.  No synchronisation.
+ *   pcc_gather_rows_pitched : d_dst row t (tight) = row d_rows[t] of d_src,
+ *     whose n_src rows of row_bytes lie pitch_bytes apart; any row_bytes up to
+ *     4096 (pcc_gather_rows takes multiples of 4 of tight rows only).  A row
+ *     not below n_src is written as zeros.
+ *   pcc_outlier_isqrt_host : floor(sqrt(x)) as the score forms it, x < 2^42
+ *     (2^64 - 1 above).  Host only.
+ *   pcc_outlier_replay_host : host only, no ctx.  The kernels' functions
+ *     compiled for the host, row by row on the calling thread; every output is
+ *     nullable.  h_scores [n], h_sums [n_frames][4], h_nodes [n] (the nodes the
+ *     score's search tried); h_keep [n] = h_scores <= h_threshold[frame] (needs
+ *     both); h_keep_radius / h_nodes_radius [n]: the radius rule under the
+ *     bounded search; h_keep_unbounded / h_nodes_unbounded [n]: under
+ *     pcc_knn_frames' own search.  k, min_neighbours, n, n_frames as above
+ *     (PCC_E_ARG, PCC_E_DUP, PCC_E_RANGE).  Not a product path. */
+int pcc_outlier_scores_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n,
+                              int n_frames, int k, uint64_t* d_scores,
+                              uint64_t* d_sums);
+int pcc_outlier_mask_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n,
+                            int n_frames, const uint64_t* d_scores,
+                            const uint64_t* d_threshold, uint8_t* d_keep,
+                            uint64_t* d_kept);
+int pcc_outlier_radius_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n,
+                              int n_frames, int min_neighbours, uint64_t radius2,
+                              uint8_t* d_keep, uint64_t* d_counts);
+int pcc_outlier_compact_rows(pcc_ctx* ctx, const int32_t* d_index, int64_t n,
+                             const uint8_t* d_keep, int64_t n_keys,
+                             const int64_t* d_offsets, int n_frames,
+                             uint8_t* d_mask, uint32_t* d_kept_rows,
+                             int64_t* d_kept_offsets);
+int pcc_gather_rows_pitched(pcc_ctx* ctx, const void* d_src, int64_t n_src,
+                            int64_t pitch_bytes, const uint32_t* d_rows,
+                            int64_t n, int row_bytes, void* d_dst);
+uint64_t pcc_outlier_isqrt_host(uint64_t x);
+int pcc_outlier_replay_host(const uint64_t* h_keys, int64_t n, int n_frames, int k,
+                            int min_neighbours, uint64_t radius2,
+                            const uint64_t* h_threshold, uint64_t* h_scores,
+                            uint64_t* h_sums, uint8_t* h_keep, uint32_t* h_nodes,
+                            uint8_t* h_keep_radius, uint32_t* h_nodes_radius,
+                            uint8_t* h_keep_unbounded,
+                            uint32_t* h_nodes_unbounded);
+
 /* ---- attribute transfer onto another geometry: recolouring (csrc/transfer.hip) -- */
 
 /* The rule (tests/transfer_ref.py restates it in numpy, on tests/nn_ref.py).
