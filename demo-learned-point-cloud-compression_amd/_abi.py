@@ -132,6 +132,9 @@ PROTOTYPES = {
     "pcc_gather_rows_pitched": (i32, [vp, vp, i64, i64, vp, i64, i32, vp]),
     "pcc_outlier_isqrt_host": (C.c_uint64, [C.c_uint64]),
     "pcc_outlier_replay_host": (i32, [vp, i64, i32, i32, i32, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pcc_cluster_frames": (i32, [vp, vp, i64, i32, i32, C.c_uint64, i64, vp, vp, vp]),
+    "pcc_cluster_replay_host": (i32, [vp, i64, i32, i32, C.c_uint64, i64, vp, vp, vp, vp, vp, vp]),
+    "pcc_cluster_replay_host_reversed": (i32, [vp, i64, i32, i32, C.c_uint64, i64, vp, vp, vp, vp, vp, vp]),
     "pcc_attr_transfer_frames": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp, vp]),
     "pcc_attr_stage_frames": (i32, [vp, vp, vp, vp, vp, i32, C.c_double, i32, i32, vp, vp, i64, vp]),
     "pcc_abi_version": (i32, []),

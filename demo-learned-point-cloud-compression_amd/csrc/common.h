@@ -93,6 +93,9 @@ void pcc_wcache_free(pcc_ctx* ctx);
 int pcc_morton_keys_batch(pcc_ctx* ctx, const int32_t* d_coords, int64_t n, int n_batch, uint64_t* d_keys, int32_t* d_flag);
 // sort.hip: pcc_sort_pairs on given key bytes only (no look at the keys, no host round trip)
 int pcc_sort_pairs_bytes(pcc_ctx* ctx, uint64_t* d_keys, uint32_t* d_perm, int64_t n, unsigned byte_mask);
+// sort.hip: the same without a reservation of its own, inside a caller's that holds pcc_sort_scratch_bytes(n) more
+size_t pcc_sort_scratch_bytes(int64_t n);
+int pcc_sort_pairs_bytes_reserved(pcc_ctx* ctx, uint64_t* d_keys, uint32_t* d_perm, int64_t n, unsigned byte_mask);
 // sort.hip: canonical order + rows in that order of a small coordinate set given by its Morton keys
 int64_t pcc_sort_small_max();
 int pcc_sort_keys_canonical(pcc_ctx* ctx, const uint64_t* d_mkeys, int64_t n, uint32_t* d_perm, int32_t* d_sorted_coords);

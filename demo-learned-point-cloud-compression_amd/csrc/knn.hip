@@ -22,6 +22,7 @@
 #include "nn_cells.h"
 #include <algorithm>
 #include <math.h>
+#include <vector>
 
 #define KNN_NO_DIST (~0ull)
 #define KNN_NO_ROW 0x7FFFFFFF
@@ -343,3 +344,6 @@ extern "C" int pcc_knn_replay_host(const uint64_t* h_keys, int64_t n, int k, int
 
 // ---------------------------------------------------------------- outlier removal behind the same search
 #include "outlier.h"
+
+// ---------------------------------------------------------------- DBSCAN clusters: the radius rule's core points, united
+#include "cluster.h"

@@ -135,3 +135,13 @@ int nn_check_and_offsets(pcc_ctx* ctx, const char* who, const char* a_key, const
                          const uint64_t* d_qkeys, int64_t n_q, int n_frames, const int64_t** offs);
 // the same refusals for the host replays: PCC_E_ARG for unsorted, PCC_E_DUP for equal keys
 int nn_host_sorted_distinct(const char* who, const char* keys, const uint64_t* h_keys, int64_t n);
+
+// ---------------------------------------------------------------- defined in knn.hip (cluster.h), for cluster.hip
+// the parameter ranges of the clustering rule, and the two halves of its launches around the numbering's sort
+int cluster_args(const char* who, int64_t n, int n_frames, int m, uint64_t radius2, int64_t min_points);
+int cluster_components(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, const int64_t* offs, int n_frames, int m, uint64_t radius2,
+                       int64_t min_points, uint8_t* core, uint32_t* parent, uint32_t* size, uint64_t* core_counts, int32_t* root,
+                       uint64_t* skeys);
+int cluster_finish(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, const int64_t* offs, int n_frames, const uint64_t* skeys,
+                   const uint32_t* perm, const uint8_t* core, int32_t* label_of, int32_t* d_labels, uint32_t* d_sizes,
+                   uint64_t* d_counts);

@@ -631,6 +631,15 @@ int pcc_sort_pairs_bytes(pcc_ctx* ctx, uint64_t* d_keys, uint32_t* d_perm, int64
   return sort_pairs_impl(ctx, d_keys, d_perm, n, 0, nullptr, nullptr, nullptr, byte_mask);
 }
 
+// internal (common.h): the same inside a reservation of the caller's, which holds pcc_sort_scratch_bytes(n) beside the
+// caller's own arrays: nothing is reserved here, so what the caller has in the arena stays (cluster.h)
+size_t pcc_sort_scratch_bytes(int64_t n) { return sort_scratch_bytes(n); }
+int pcc_sort_pairs_bytes_reserved(pcc_ctx* ctx, uint64_t* d_keys, uint32_t* d_perm, int64_t n, unsigned byte_mask) {
+  PCC_REQUIRE(ctx && (n == 0 || (d_keys && d_perm)) && byte_mask != 0 && byte_mask < 256 && n < ((int64_t)1 << 31), PCC_E_ARG,
+              "pcc_sort_pairs_bytes_reserved: bad argument");
+  return sort_pairs_impl(ctx, d_keys, d_perm, n, 0, nullptr, nullptr, nullptr, byte_mask);
+}
+
 extern "C" int pcc_sort_pairs(pcc_ctx* ctx, uint64_t* d_keys, uint32_t* d_perm, int64_t n,
                               int is_signed) {
   PCC_REQUIRE(ctx && (n == 0 || (d_keys && d_perm)), PCC_E_ARG, "pcc_sort_pairs: null arg");

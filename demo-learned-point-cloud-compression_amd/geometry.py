@@ -179,6 +179,14 @@ exact k nearest neighbours, decided in integers; the rows returned are the calle
     kept, mask, report = codec.filter(frames, return_mask=True, return_report=True, output="device")
     blobs = codec.compress(codec.filter(frames))
 
+Clusters (include/pcc.h has the rule): what a k-NN score cannot see — blobs of flying pixels along a depth edge, a
+detached piece of background — by DBSCAN on the device: connected components of the points within a radius of each
+other, numbered by size, as a function of the point set alone.
+
+    labels = codec.cluster(frames, radius2=3, min_points=50)      # int32 [n_f] per frame, row i = input row i, noise -1
+    subject = [f[l == 0] for f, l in zip(frames, labels)]          # the largest cluster; l >= 0: without small debris
+    labels, report = codec.cluster(frames, radius2=3, min_neighbours=4, return_report=True, output="device")
+
 One Runtime (ctx + stream) per codec; calls on the same instance are serialised, instances on different threads run
 side by side.
 """
@@ -1485,6 +1493,78 @@ class GeometryCodec:
                     report.append(rep)
             rt.sync()      # a device result may be read from the caller's stream at once
             return result(kept, kept_attrs, masks, report)
+
+    @staticmethod
+    def _check_cluster(radius2, min_neighbours, min_points):
+        """the rule's keywords of cluster -> (radius2, m, min_points) as Python ints"""
+        if radius2 is None:
+            raise ValueError("cluster needs radius2=, the squared radius in lattice units (an integer in 0 .. 4096)")
+        for name, v, lo, hi, rng in (("radius2", radius2, 0, 4096, "0 .. 4096 (squared lattice units)"),
+                                     ("min_neighbours", min_neighbours, 0, 31, "0 .. 31"),
+                                     ("min_points", min_points, 1, 1 << 27, "1 .. 2^27")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an integer in {rng}, got {v!r}")
+            if not lo <= v <= hi:
+                raise ValueError(f"{name} must be an integer in {rng}, got {v!r}")
+        return int(radius2), int(min_neighbours), int(min_points)
+
+    def cluster(self, frames, radius2=None, min_neighbours=0, min_points=1, return_report=False, output="numpy", *, voxel=None,
+                origin=(0.0, 0.0, 0.0), invalid="raise"):
+        """DBSCAN clusters of every frame, on the device (include/pcc.h has the rule) -> `labels`, one int32 [n_f] per
+        frame, row i the label of INPUT row i; (labels, report) with return_report.
+        The rule runs per frame over the frame's distinct lattice points: a point is a core point iff at least
+        min_neighbours (0 .. 31) OTHER points lie within radius2 (an integer in 0 .. 4096, squared lattice units, required);
+        core points within radius2 of each other share a cluster; any other point joins its nearest core point within
+        radius2 (the Morton-first among equidistant ones) or is noise; a cluster of fewer than min_points (1 .. 2^27)
+        points is noise as a whole.  Clusters are numbered by size, largest first (equal sizes by their Morton-first
+        point), noise is -1: frames[f][labels[f] == 0] is the subject, frames[f][labels[f] >= 0] the frame without
+        small debris.  min_neighbours=0 is plain Euclidean clustering (connected components).  The result depends on
+        the point set alone.  Duplicate rows share their point's label; a row dropped under invalid="drop" gets -1.
+        A bool or a value of the wrong type: TypeError; a value out of range: ValueError naming the keyword.  Coarser
+        radii: cluster coarser points (p >> k).
+        frames: int16 / int32 lattice frames, or float32 frames with voxel= / origin= / invalid= exactly as compress
+        quantises them; numpy or torch, all on the host or all on this codec's device.
+        return_report: per frame a dict of Python ints, "points" (distinct), "core", "clusters", "noise" (distinct
+        points), and "sizes", the clusters' sizes in label order.  output: "numpy" arrays, or "device": tensors on this
+        codec's device.  An empty frame gives an empty array; a frame of one point is one cluster of size 1 at
+        min_neighbours=0 and noise above."""
+        radius2, m, min_points = self._check_cluster(radius2, min_neighbours, min_points)
+        if output not in ("numpy", "device"):
+            raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
+        if invalid not in ("raise", "drop"):
+            raise ValueError(f"invalid must be 'raise' or 'drop', got {invalid!r}")
+        frames, is_float, on_device = self._check_frames(frames)
+        if is_float:
+            if voxel is None:
+                raise ValueError("float32 frames need voxel=, the edge of a lattice cell in the frames' unit")
+            voxel, origin = self._check_grid(voxel, origin, "cluster")
+        elif voxel is not None:
+            raise ValueError("voxel= with integer frames: they are on the lattice already")
+        nb = len(frames)
+        if nb == 0:
+            return ([], []) if return_report else []
+        caller = torch.cuda.current_stream(self.rt.device) if on_device else None
+        with self._lock, self.rt as rt:
+            front = self._front(rt, frames, is_float, on_device, caller, "GeometryCodec.cluster", 0, voxel, origin, invalid == "drop")
+            counts, sizes = [[0, 0, 0, 0]] * nb, [[] for _ in range(nb)]
+            if front.n_keep == 0:
+                rows = torch.full((front.n,), -1, dtype=torch.int32, device=rt.device)
+            else:
+                labels, d_sizes, d_counts = rt.cluster_frames(front.keys, nb, m, radius2, min_points, want_sizes=return_report)
+                # the distinct row of every input row: rows_index with no frame's rows taken off
+                index = rt.rows_index(front.perm, front.n_keep, front.rows, front.n_unique, front.offsets.data_ptr(),
+                                      torch.zeros(nb, dtype=torch.int64, device=rt.device), nb)
+                rows = torch.where(index >= 0, labels[index.clamp(min=0).long()], torch.full_like(index, -1))
+                if return_report:
+                    counts = rt._u64_rows(d_counts)      # the call's synchronisation for the counts
+                    firsts = _ends([c[0] for c in counts])      # where every frame's distinct points, and its sizes, begin
+                    live = [d_sizes[firsts[f]:firsts[f] + counts[f][2]] for f in range(nb)]
+                    sizes = _split(torch.cat(live).cpu().numpy().view(np.uint32).tolist(), [c[2] for c in counts])
+            out = _frames_out(rt, rows, front.sizes, output == "numpy")
+        if not return_report:
+            return out
+        return out, [{"points": int(c[0]), "core": int(c[1]), "clusters": int(c[2]), "noise": int(c[3]), "sizes": list(s)}
+                     for c, s in zip(counts, sizes)]
 
     @staticmethod
     def _check_normals(frames, normals, device=None):

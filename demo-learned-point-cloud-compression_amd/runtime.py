@@ -438,6 +438,41 @@ class Runtime:
         out["sums"] = [(s1, lo + (hi << 32), cnt) for s1, lo, hi, cnt in sums.tolist()]
         return out
 
+    # ------------------------------------------------------------ DBSCAN clusters (the rule of include/pcc.h)
+    def cluster_frames(self, keys, n_frames, min_neighbours, radius2, min_points, want_sizes=True):
+        """the clusters of every frame (pcc_cluster_frames).  keys: sorted distinct Morton keys on the device.  Returns
+        (labels int32 [n], sizes int32 [n] holding uint32 values: frame f's sizes in label order from the frame's first
+        row on, None unless wanted; counts int64 [n_frames, 4]: points, core points, clusters, noise points) as device
+        tensors.  Synchronises once, in front of the kernels (the checks of the keys); the results are on this
+        runtime's stream."""
+        n = int(keys.shape[0])
+        labels = self.empty((n,), torch.int32)
+        sizes = self.empty((n,), torch.int32) if want_sizes else None
+        counts = self.empty((int(n_frames), 4), torch.int64)
+        check(self.lib.pcc_cluster_frames(self.ctx, _ptr(keys), n, int(n_frames), int(min_neighbours), int(radius2), int(min_points),
+                                          _ptr(labels), _ptr(sizes), _ptr(counts)), "pcc_cluster_frames")
+        return labels, sizes, counts
+
+    @staticmethod
+    def cluster_replay_host(keys, n_frames, min_neighbours=0, radius2=0, min_points=1, reversed_order=False):
+        """the clustering rule on the host (pcc_cluster_replay_host: the kernels' functions compiled for the host; no
+        GPU needed, not a product path).  keys: a uint64 numpy array, sorted and distinct.  Returns a dict: labels int32
+        [n], sizes uint32 [n], counts [[points, core, clusters, noise]] per frame as Python ints, core uint8 [n], root
+        int32 [n] (rows of the call, -1 without a component), nodes uint32 [n].  reversed_order: the unions of every
+        frame issued from its last row to its first (pcc_cluster_replay_host_reversed)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        n = int(keys.shape[0])
+        out = {"labels": np.zeros(n, np.int32), "sizes": np.zeros(n, np.uint32), "core": np.zeros(n, np.uint8),
+               "root": np.zeros(n, np.int32), "nodes": np.zeros(n, np.uint32)}
+        counts = np.zeros((max(int(n_frames), 0), 4), np.uint64)
+        ptr = lambda a: C.c_void_p(a.ctypes.data)
+        name = "pcc_cluster_replay_host_reversed" if reversed_order else "pcc_cluster_replay_host"
+        check(getattr(_abi.lib(), name)(ptr(keys), n, int(n_frames), int(min_neighbours), int(radius2), int(min_points),
+                                        ptr(out["labels"]), ptr(out["sizes"]), ptr(counts), ptr(out["core"]), ptr(out["root"]),
+                                        ptr(out["nodes"])), name)
+        out["counts"] = counts.tolist()
+        return out
+
     def nn_d2_frames(self, qkeys, row, rkeys, normals, n_frames, normal_row=None, want_proj=False):
         """the D2 (point-to-plane) side of a pairing (pcc_nn_d2_frames): row, nn_frames' rows of qkeys among rkeys;
         normals a float32 [m, 3] device tensor; normal_row an int32 [n_q] device tensor, the row of normals to use for

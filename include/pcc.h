@@ -1860,6 +1860,82 @@ int pcc_outlier_replay_host(const uint64_t* h_keys, int64_t n, int n_frames, int
                             uint8_t* h_keep_unbounded,
                             uint32_t* h_nodes_unbounded);
 
+/* ---- DBSCAN clusters by union-find (csrc/cluster.h, behind csrc/knn.hip's search) -- */
+
+/* The rule (tests/cluster_ref.py restates it in Python integers).  It is per
+ * frame, over the frame's n DISTINCT lattice points in Morton order (n sorted
+ * distinct keys, as pcc_knn_frames takes them); only points of the same frame
+ * are neighbours.  Parameters: radius2, an integer in 0 .. 4096 (squared
+ * lattice units); min_neighbours m in 0 .. 31; min_points in 1 .. 2^27.
+ *   1 core points   point i is a core point iff at least m OTHER points lie at
+ *                   d2 <= radius2: the radius rule of pcc_outlier_radius_frames,
+ *                   word for word.  With m = 0 every point is a core point and
+ *                   the rule is plain Euclidean clustering (connected
+ *                   components; PCL's EuclideanClusterExtraction).
+ *   2 edges         two core points i and j are joined iff d2(i, j) <= radius2
+ *                   (inclusive).
+ *   3 components    the connected components of the core points.  The root of
+ *                   a component is its smallest row: its Morton-first core
+ *                   point.
+ *   4 border points a point that is not a core point belongs to the component
+ *                   of its nearest core point with d2 <= radius2; among
+ *                   equidistant core points the SMALLEST row wins.  A point
+ *                   with no such core point is noise.  A border point never
+ *                   joins two components.  (DBSCAN, Open3D's cluster_dbscan,
+ *                   with the one order-dependent choice of the textbook
+ *                   algorithm made deterministic.)
+ *   5 size, pruning the size of a component is its core points plus its border
+ *                   points; a component with size < min_points is noise as a
+ *                   whole.
+ *   6 numbering     the components that remain are numbered 0 .. K-1 by (size
+ *                   descending, root row ascending): label 0 is the largest
+ *                   cluster.  Every noise point has label -1.
+ * The result is a function of the point set alone: not of scheduling, of the
+ * order of input rows, or of which frames share a call.
+ * radius2 above 4096 is PCC_E_ARG, as a condition and not a measurement: a
+ * point's walk visits every point within its radius, and radius 64 bounds
+ * that work per thread.  Coarser needs cluster coarser points, p >> k.
+ *
+ *   pcc_cluster_frames : d_keys: n sorted distinct keys of n_frames frames.
+ *     d_labels int32 [n]; d_sizes uint32 [n], nullable: frame f's K_f sizes in
+ *     label order from the frame's first row on, the rest zero; d_counts
+ *     [n_frames][4] (zeroed by the call): points, core points, clusters K,
+ *     noise points.  Core flags by pcc_outlier_radius_frames' kernel (m = 0: a
+ *     fill); one walk per point under the constant bound radius2, in which a
+ *     core point unites with the core points in front of it (lock-free
+ *     union-find, the larger root under the smaller; relaxed agent-scope
+ *     atomics only, no fence, no waiting) and any other point keeps its
+ *     nearest core point; no list of neighbours is written.  A second launch
+ *     flattens; sizes, the min_points cut, the numbering (one stable sort) and
+ *     the counts follow on the device, with no host array of size n.  Checks
+ *     and refusals are those of pcc_outlier_radius_frames (one synchronisation
+ *     in front), and min_neighbours, radius2, min_points in their ranges
+ *     (PCC_E_ARG; pcc_last_error names the argument).  n = 0 launches nothing
+ *     (the counts are zeroed).  After an error the ctx stays usable.  The
+ *     counts are the caller's to read behind a synchronisation of its own.
+ *   pcc_cluster_replay_host : host only, no ctx.  The kernels' functions
+ *     compiled for the host, row by row on the calling thread; every output is
+ *     nullable.  h_labels, h_sizes, h_counts as above; h_core uint8 [n];
+ *     h_root int32 [n]: the root row (a row of the call) of the point's
+ *     component before pruning and numbering, -1 for a point without one;
+ *     h_nodes [n]: the nodes each walk tried.  Not a product path.
+ *   pcc_cluster_replay_host_reversed : the same with every frame's walks, and
+ *     so the unions, issued from the last row to the first: the result must
+ *     not differ. */
+int pcc_cluster_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames,
+                       int min_neighbours, uint64_t radius2, int64_t min_points,
+                       int32_t* d_labels, uint32_t* d_sizes, uint64_t* d_counts);
+int pcc_cluster_replay_host(const uint64_t* h_keys, int64_t n, int n_frames,
+                            int min_neighbours, uint64_t radius2, int64_t min_points,
+                            int32_t* h_labels, uint32_t* h_sizes, uint64_t* h_counts,
+                            uint8_t* h_core, int32_t* h_root, uint32_t* h_nodes);
+int pcc_cluster_replay_host_reversed(const uint64_t* h_keys, int64_t n, int n_frames,
+                                     int min_neighbours, uint64_t radius2,
+                                     int64_t min_points, int32_t* h_labels,
+                                     uint32_t* h_sizes, uint64_t* h_counts,
+                                     uint8_t* h_core, int32_t* h_root,
+                                     uint32_t* h_nodes);
+
 /* ---- attribute transfer onto another geometry: recolouring (csrc/transfer.hip) -- */
 
 /* The rule (tests/transfer_ref.py restates it in numpy, on tests/nn_ref.py).
