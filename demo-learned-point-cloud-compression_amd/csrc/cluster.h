@@ -253,11 +253,8 @@ int cluster_components(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, const in
   hipLaunchKernelGGL(k_cluster_init, grid, block, 0, st, n, parent, size, m == 0 ? core : (uint8_t*)nullptr);
   PCC_CHECK_LAUNCH();
   if (m > 0) {      // the radius rule is the core-point test, word for word
-    unsigned long long* counts = (unsigned long long*)core_counts;
-    PCC_HIP(hipMemsetAsync(counts, 0, (size_t)n_frames * 16, st));
-    if (m + 1 <= 8) hipLaunchKernelGGL(k_outlier_radius<8>, grid, block, 0, st, d_keys, n, offs, m, radius2, core, counts);
-    else if (m + 1 <= 16) hipLaunchKernelGGL(k_outlier_radius<16>, grid, block, 0, st, d_keys, n, offs, m, radius2, core, counts);
-    else hipLaunchKernelGGL(k_outlier_radius<32>, grid, block, 0, st, d_keys, n, offs, m, radius2, core, counts);
+    PCC_HIP(hipMemsetAsync(core_counts, 0, (size_t)n_frames * 16, st));
+    outlier_radius_launch(st, d_keys, n, offs, m, radius2, core, core_counts);
     PCC_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(k_cluster_walk, grid, block, 0, st, d_keys, n, offs, (const uint8_t*)core, parent, radius2, root);
@@ -270,14 +267,13 @@ int cluster_components(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, const in
   return PCC_OK;
 }
 
-//   cluster_finish: skeys sorted, perm the sort's permutation -> labels in place of the roots, sizes (nullable) and
-//   counts, both zeroed here.  label_of: n words of scratch (the parents' array: the flatten is behind us).
+//   cluster_finish: skeys sorted, perm the sort's permutation -> labels in place of the roots, sizes (nullable, zeroed
+//   here) and counts (zeroed by the entry).  label_of: n words of scratch (the parents' array: the flatten is behind us).
 int cluster_finish(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, const int64_t* offs, int n_frames, const uint64_t* skeys,
                    const uint32_t* perm, const uint8_t* core, int32_t* label_of, int32_t* d_labels, uint32_t* d_sizes,
                    uint64_t* d_counts) {
   hipStream_t st = ctx->stream;
   const dim3 grid(nblk(n, 256)), block(256);
-  PCC_HIP(hipMemsetAsync(d_counts, 0, (size_t)n_frames * 32, st));
   if (d_sizes) PCC_HIP(hipMemsetAsync(d_sizes, 0, (size_t)n * 4, st));
   PCC_HIP(hipMemsetAsync(label_of, 0xFF, (size_t)n * 4, st));
   hipLaunchKernelGGL(k_cluster_number, grid, block, 0, st, skeys, perm, n, n_frames, offs, label_of, d_sizes);
@@ -290,37 +286,32 @@ int cluster_finish(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, const int64_
 
 // ---------------------------------------------------------------- the host replay
 // host only, no ctx: the kernels' functions row by row on the calling thread.  Not a product path.
-template <int CAP>
-static void cluster_replay_core(const uint64_t* h_keys, int64_t flo, int64_t fhi, int m, uint64_t radius2, uint8_t* core) {
-  for (int64_t i = flo; i < fhi; ++i) core[i] = outlier_radius_point<CAP>(h_keys, flo, fhi, i, m, radius2, true, nullptr) ? 1 : 0;
-}
-
 static int cluster_replay(const char* who, const uint64_t* h_keys, int64_t n, int n_frames, int m, uint64_t radius2, int64_t min_points,
                           bool reversed, int32_t* h_labels, uint32_t* h_sizes, uint64_t* h_counts, uint8_t* h_core, int32_t* h_root,
                           uint32_t* h_nodes) {
   PCC_TRY(cluster_args(who, n, n_frames, m, radius2, min_points));
   PCC_REQUIRE(n == 0 || h_keys, PCC_E_ARG, "%s: null keys", who);
   PCC_TRY(nn_host_sorted_distinct(who, "keys", h_keys, n));
-  PCC_REQUIRE(n == 0 || (int)(h_keys[n - 1] >> 48) < n_frames, PCC_E_RANGE, "%s: a key's frame index is not below n_frames=%d", who,
-              n_frames);
-  if (h_counts) std::fill(h_counts, h_counts + 4 * (size_t)n_frames, 0ull);
-  if (h_sizes) std::fill(h_sizes, h_sizes + n, 0u);
-  if (n == 0) return PCC_OK;
-  std::vector<uint8_t> core((size_t)n, 1);
-  std::vector<uint32_t> parent((size_t)n), size((size_t)n, 0u);
-  std::vector<int32_t> root((size_t)n), label_of((size_t)n, -1);
+  std::vector<uint8_t> core;
+  std::vector<uint32_t> parent, size;
+  std::vector<int32_t> root, label_of;
   std::vector<int64_t> order;
-  for (int64_t i = 0; i < n; ++i) parent[i] = (uint32_t)i;
-  int64_t flo = 0;
-  while (flo < n) {
-    const uint64_t frame = h_keys[flo] & ~NN_KEY48;
-    const int64_t fhi = std::upper_bound(h_keys + flo, h_keys + n, frame | NN_KEY48) - h_keys;
-    const int f = (int)(frame >> 48);
-    if (m > 0) {
-      if (m + 1 <= 8) cluster_replay_core<8>(h_keys, flo, fhi, m, radius2, core.data());
-      else if (m + 1 <= 16) cluster_replay_core<16>(h_keys, flo, fhi, m, radius2, core.data());
-      else cluster_replay_core<32>(h_keys, flo, fhi, m, radius2, core.data());
-    }
+  const auto ready = [&] {
+    if (h_counts) std::fill(h_counts, h_counts + 4 * (size_t)n_frames, 0ull);
+    if (h_sizes) std::fill(h_sizes, h_sizes + n, 0u);
+    core = std::vector<uint8_t>((size_t)n, 1);
+    parent = std::vector<uint32_t>((size_t)n);
+    size = std::vector<uint32_t>((size_t)n, 0u);
+    root = std::vector<int32_t>((size_t)n);
+    label_of = std::vector<int32_t>((size_t)n, -1);
+    for (int64_t i = 0; i < n; ++i) parent[i] = (uint32_t)i;
+  };
+  return knn_host_frames(who, h_keys, n, n_frames, ready, [&](int f, int64_t flo, int64_t fhi) {
+    if (m > 0)
+      knn_with_cap(m + 1, [&](auto cap) {
+        for (int64_t i = flo; i < fhi; ++i)
+          core[i] = outlier_radius_point<decltype(cap)::value>(h_keys, flo, fhi, i, m, radius2, true, nullptr) ? 1 : 0;
+      });
     for (int64_t t = flo; t < fhi; ++t) {      // reversed: the unions arrive in the opposite order
       const int64_t i = reversed ? fhi - 1 - (t - flo) : t;
       const uint32_t nodes = cluster_point(h_keys, flo, fhi, i, core.data(), parent.data(), radius2, root.data());
@@ -353,9 +344,7 @@ static int cluster_replay(const char* who, const uint64_t* h_keys, int64_t n, in
       uint64_t* out = h_counts + 4 * (size_t)f;
       out[0] = (uint64_t)(fhi - flo); out[1] = n_core; out[2] = order.size(); out[3] = n_noise;
     }
-    flo = fhi;
-  }
-  return PCC_OK;
+  });
 }
 
 extern "C" int pcc_cluster_replay_host(const uint64_t* h_keys, int64_t n, int n_frames, int min_neighbours, uint64_t radius2,

@@ -13,20 +13,15 @@ extern "C" int pcc_cluster_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t 
                                   int64_t min_points, int32_t* d_labels, uint32_t* d_sizes, uint64_t* d_counts) {
   PCC_REQUIRE(ctx, PCC_E_ARG, "pcc_cluster_frames: null ctx");
   PCC_TRY(cluster_args("pcc_cluster_frames", n, n_frames, min_neighbours, radius2, min_points));
-  PCC_REQUIRE(n == 0 || d_keys, PCC_E_ARG, "pcc_cluster_frames: null keys");
-  PCC_REQUIRE(d_counts && (n == 0 || d_labels), PCC_E_ARG, "pcc_cluster_frames: null output");
-  hipStream_t st = ctx->stream;
-  if (n == 0) {
-    PCC_HIP(hipMemsetAsync(d_counts, 0, (size_t)n_frames * 32, st));
-    return PCC_OK;
-  }
   // One reservation for the whole call in front: the checks reserve again (less, so the arena stays where it is) and
   // take the first rows; the arrays below follow them, and the sort runs inside what is left.
   const size_t n4 = pcc_align((size_t)n * 4);
-  PCC_TRY(pcc_arena_reserve(ctx, pcc_align((size_t)(n_frames + 1) * 8) + 1024 + pcc_align((size_t)n) + 3 * n4 + pcc_align((size_t)n * 8) +
-                                     pcc_align((size_t)n_frames * 16) + pcc_sort_scratch_bytes(n)));
-  const int64_t* offs;
-  PCC_TRY(nn_check_and_offsets(ctx, "pcc_cluster_frames", "a key's", "keys", d_keys, n, nullptr, 0, n_frames, &offs));
+  const size_t whole = pcc_align((size_t)(n_frames + 1) * 8) + 1024 + pcc_align((size_t)n) + 3 * n4 + pcc_align((size_t)n * 8) +
+                       pcc_align((size_t)n_frames * 16) + pcc_sort_scratch_bytes(n);
+  const int64_t* offs;      // the ranges are cluster_args' above; knn_entry zeroes d_counts and reserves before the key checks
+  PCC_TRY(knn_entry(ctx, "pcc_cluster_frames", KNN_NO_RANGE, d_keys, n, n_frames,
+                    {"null keys", d_counts && (n == 0 || d_labels), "null output"}, d_counts, 32, whole, &offs));
+  if (!offs) return PCC_OK;
   uint8_t* core = (uint8_t*)pcc_arena_alloc(ctx, (size_t)n);
   uint32_t* parent = (uint32_t*)pcc_arena_alloc(ctx, (size_t)n * 4);      // behind the flatten: the labels of the roots
   uint32_t* size = (uint32_t*)pcc_arena_alloc(ctx, (size_t)n * 4);

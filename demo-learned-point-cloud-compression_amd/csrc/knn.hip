@@ -12,6 +12,8 @@
 //          (2^64 - 1, INT32_MAX): until the list holds k_eff = min(k, frame rows) entries nothing is pruned.
 //   seed   the k_eff rows around the query's place in key order, clamped to the frame's rows, fill the list before the
 //          walk starts; the walk passes over them (seeded), so no row enters twice.  The seed loop counts k_eff rows.
+//   host   knn_with_cap picks the capacity for every launch and replay of this file, knn_entry is what every entry on
+//          one key array does in front of its launches, knn_host_frames the replays' walk over the frames.
 //
 // Epilogue, same thread: C = m sum d d^T - (sum d)(sum d)^T over the m = k_eff neighbours in int64 (below 2^46), then
 // a unit eigenvector of its smallest eigenvalue in float64 — eigenvalues in closed form (trigonometric), the vector
@@ -22,6 +24,7 @@
 #include "nn_cells.h"
 #include <algorithm>
 #include <math.h>
+#include <type_traits>
 #include <vector>
 
 #define KNN_NO_DIST (~0ull)
@@ -67,13 +70,18 @@ __host__ __device__ static inline void knn_insert(KnnList<CAP>& L, uint64_t d, i
   }
 }
 
-// the k-NN bound of nn_walk: the list's last slot; the seed rows [s0, s1) are in the list already
-template <int CAP>
+// the k-NN bound of nn_walk: the list's last slot; the seed rows [s0, s1) are in the list already.  CAPPED (the radius
+// search): never beyond cap = radius2 + 1, and at the cap no row wins a tie (bound_row -1): a cell at box distance
+// radius2 + 1 holds no point within the radius.  Not CAPPED: cap is not read, and a last slot that is still free
+// answers (2^64 - 1, KNN_NO_ROW) by itself.
+template <int CAP, bool CAPPED>
 struct KnnBest {
   KnnList<CAP>& L;
   int64_t s0, s1;
-  __host__ __device__ uint64_t bound() const { return L.d[CAP - 1]; }
-  __host__ __device__ int64_t bound_row() const { return L.r[CAP - 1]; }
+  uint64_t cap;
+  __host__ __device__ bool below_cap() const { return !CAPPED || L.d[CAP - 1] < cap; }
+  __host__ __device__ uint64_t bound() const { return below_cap() ? L.d[CAP - 1] : cap; }
+  __host__ __device__ int64_t bound_row() const { return below_cap() ? (int64_t)L.r[CAP - 1] : -1; }
   __host__ __device__ bool seeded(int64_t r) const { return r >= s0 && r < s1; }
   __host__ __device__ void offer(uint64_t d, int64_t r) { knn_insert(L, d, (int32_t)r); }
 };
@@ -90,7 +98,7 @@ __host__ __device__ static inline uint32_t knn_search(const uint64_t* __restrict
   int64_t s0 = lo - k_eff / 2;      // the seed rows [s0, s1) inside [flo, fhi)
   if (s0 > fhi - k_eff) s0 = fhi - k_eff;
   if (s0 < flo) s0 = flo;
-  KnnBest<CAP> b = {L, s0, s0 + k_eff};
+  KnnBest<CAP, false> b = {L, s0, s0 + k_eff, 0};
   for (int64_t r = b.s0; r < b.s1; ++r) knn_insert(L, nn_d2(qx, qy, qz, keys[r]), (int32_t)r);
   if (k_eff == n_f) return (uint32_t)k_eff;      // the seed was the whole frame
   return (uint32_t)k_eff + nn_walk(keys, flo, fhi, qx, qy, qz, b);
@@ -287,59 +295,91 @@ __global__ __launch_bounds__(256) void k_knn_frames(const uint64_t* __restrict__
   (void)knn_point<CAP>(keys, flo, fhi, i, k, rows, sqdist, cov, normals, has_vp != 0, vx, vy, vz);
 }
 
-// ---------------------------------------------------------------- C-ABI (include/pcc.h)
-template <int CAP>
-static void knn_launch(hipStream_t st, const uint64_t* d_keys, int64_t n, const int64_t* offs, int k, int32_t* d_rows,
-                       uint64_t* d_sqdist, int64_t* d_cov, float* d_normals, const int32_t* vp) {
-  hipLaunchKernelGGL(k_knn_frames<CAP>, dim3(nblk(n, 256)), dim3(256), 0, st, d_keys, n, offs, k, d_rows, d_sqdist, d_cov,
-                     d_normals, vp ? 1 : 0, vp ? vp[0] : 0, vp ? vp[1] : 0, vp ? vp[2] : 0);
+// ---------------------------------------------------------------- what the entries and the replays share
+// the capacity of a list of `len` entries (k, or m + 1 under the radius rule): fn(std::integral_constant<int, CAP>),
+// CAP the smallest of 8 / 16 / 32 that holds it
+template <typename Fn>
+static inline void knn_with_cap(int len, Fn fn) {
+  if (len <= 8) fn(std::integral_constant<int, 8>());
+  else if (len <= 16) fn(std::integral_constant<int, 16>());
+  else fn(std::integral_constant<int, 32>());
 }
 
+// What an entry on one key array does in front of its launches, in the order of its refusals (nn_cells.h declares it
+// and its two records for cluster.hip): the ranges of the call and of the rule's integer k, the null pointers (the
+// keys, then the entry's own), the per-frame output d_frame (nullable) zeroed, frame_bytes a frame, and for n > 0 the
+// arena (reserve: the bytes of the whole call, 0: what the checks take) and the key checks.  *offs: the first row of
+// every frame; nullptr for n == 0, nothing to do.
+int knn_entry(pcc_ctx* ctx, const char* who, KnnRange k, const uint64_t* d_keys, int64_t n, int n_frames, KnnNulls nulls,
+              void* d_frame, size_t frame_bytes, size_t reserve, const int64_t** offs) {
+  const bool call_ok = ctx && n >= 0 && n <= NN_MAX_KEYS && n_frames >= 1 && n_frames <= 65535;
+  if (k.name)
+    PCC_REQUIRE(call_ok && k.v >= k.lo && k.v <= k.hi, PCC_E_ARG,
+                "%s: bad argument (n=%lld n_frames=%d %s=%d; %s in %d .. %d, at most 2^27 keys, 1 .. 65535 frames)", who, (long long)n,
+                n_frames, k.name, k.v, k.name, k.lo, k.hi);
+  else
+    PCC_REQUIRE(call_ok, PCC_E_ARG, "%s: bad argument (n=%lld n_frames=%d; at most 2^27 keys, 1 .. 65535 frames)", who, (long long)n,
+                n_frames);
+  PCC_REQUIRE(n == 0 || d_keys, PCC_E_ARG, "%s: %s", who, nulls.keys);
+  PCC_REQUIRE(nulls.others_ok, PCC_E_ARG, "%s: %s", who, nulls.others);
+  *offs = nullptr;
+  if (n > 0) {
+    if (reserve) PCC_TRY(pcc_arena_reserve(ctx, reserve));
+    PCC_TRY(nn_check_and_offsets(ctx, who, "a key's", "keys", d_keys, n, nullptr, 0, n_frames, offs));
+  }
+  if (d_frame) PCC_HIP(hipMemsetAsync(d_frame, 0, (size_t)n_frames * frame_bytes, ctx->stream));
+  return PCC_OK;
+}
+
+// host: the refusal of a frame index that is not below n_frames (65536: every index is); behind it ready(), where a
+// replay zeroes and sizes what it fills; then the frames of the sorted keys one after the other, body(f, flo, fhi) for
+// the rows [flo, fhi) of frame f
+template <typename Ready, typename Body>
+static int knn_host_frames(const char* who, const uint64_t* h_keys, int64_t n, int n_frames, Ready ready, Body body) {
+  PCC_REQUIRE(n == 0 || (int)(h_keys[n - 1] >> 48) < n_frames, PCC_E_RANGE, "%s: a key's frame index is not below n_frames=%d", who,
+              n_frames);
+  ready();
+  int64_t flo = 0;
+  while (flo < n) {
+    const uint64_t frame = h_keys[flo] & ~NN_KEY48;
+    const int64_t fhi = std::upper_bound(h_keys + flo, h_keys + n, frame | NN_KEY48) - h_keys;
+    body((int)(frame >> 48), flo, fhi);
+    flo = fhi;
+  }
+  return PCC_OK;
+}
+
+// ---------------------------------------------------------------- C-ABI (include/pcc.h)
 extern "C" int pcc_knn_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int k, int32_t* d_rows,
                               uint64_t* d_sqdist, int64_t* d_cov, float* d_normals, const int32_t* h_viewpoint) {
-  PCC_REQUIRE(ctx && k >= 3 && k <= 32 && n >= 0 && n <= NN_MAX_KEYS && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
-              "pcc_knn_frames: bad argument (n=%lld n_frames=%d k=%d; k in 3 .. 32, at most 2^27 keys, 1 .. 65535 frames)",
-              (long long)n, n_frames, k);
-  PCC_REQUIRE(n == 0 || d_keys, PCC_E_ARG, "pcc_knn_frames: null keys");
-  if (n == 0) return PCC_OK;
-  hipStream_t st = ctx->stream;
   const int64_t* offs;
-  PCC_TRY(nn_check_and_offsets(ctx, "pcc_knn_frames", "a key's", "keys", d_keys, n, nullptr, 0, n_frames, &offs));
-  if (!d_rows && !d_sqdist && !d_cov && !d_normals) return PCC_OK;
+  PCC_TRY(knn_entry(ctx, "pcc_knn_frames", {"k", k, 3, 32}, d_keys, n, n_frames, {"null keys", true, ""}, nullptr, 0, 0, &offs));
+  if (!offs || (!d_rows && !d_sqdist && !d_cov && !d_normals)) return PCC_OK;
   PccProfScope prof(ctx, "knn_frames", n, k, n_frames, 0);
-  if (k <= 8) knn_launch<8>(st, d_keys, n, offs, k, d_rows, d_sqdist, d_cov, d_normals, h_viewpoint);
-  else if (k <= 16) knn_launch<16>(st, d_keys, n, offs, k, d_rows, d_sqdist, d_cov, d_normals, h_viewpoint);
-  else knn_launch<32>(st, d_keys, n, offs, k, d_rows, d_sqdist, d_cov, d_normals, h_viewpoint);
+  const int32_t* vp = h_viewpoint;
+  knn_with_cap(k, [&](auto cap) {
+    hipLaunchKernelGGL(k_knn_frames<decltype(cap)::value>, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, d_keys, n, offs, k, d_rows,
+                       d_sqdist, d_cov, d_normals, vp ? 1 : 0, vp ? vp[0] : 0, vp ? vp[1] : 0, vp ? vp[2] : 0);
+  });
   PCC_CHECK_LAUNCH();
   return PCC_OK;
 }
 
 // host only, no ctx: knn_point for every row on the calling thread — the kernel's traversal and epilogue, for counting
 // the nodes it tries and for checks where there is no device.  Not a product path.
-template <int CAP>
-static void knn_replay(const uint64_t* h_keys, int64_t n, int k, int32_t* h_rows, uint64_t* h_sqdist, int64_t* h_cov,
-                       float* h_normals, uint32_t* h_nodes) {
-  int64_t flo = 0;
-  while (flo < n) {
-    const uint64_t frame = h_keys[flo] & ~NN_KEY48;
-    const int64_t fhi = std::upper_bound(h_keys + flo, h_keys + n, frame | NN_KEY48) - h_keys;
-    for (int64_t i = flo; i < fhi; ++i) {
-      const uint32_t nodes = knn_point<CAP>(h_keys, flo, fhi, i, k, h_rows, h_sqdist, h_cov, h_normals, false, 0, 0, 0);
-      if (h_nodes) h_nodes[i] = nodes;
-    }
-    flo = fhi;
-  }
-}
-
 extern "C" int pcc_knn_replay_host(const uint64_t* h_keys, int64_t n, int k, int32_t* h_rows, uint64_t* h_sqdist, int64_t* h_cov,
                                    float* h_normals, uint32_t* h_nodes) {
   PCC_REQUIRE(k >= 3 && k <= 32 && n >= 0 && n <= NN_MAX_KEYS && (n == 0 || h_keys), PCC_E_ARG,
               "pcc_knn_replay_host: bad argument (n=%lld k=%d; k in 3 .. 32, at most 2^27 keys)", (long long)n, k);
   PCC_TRY(nn_host_sorted_distinct("pcc_knn_replay_host", "keys", h_keys, n));
-  if (k <= 8) knn_replay<8>(h_keys, n, k, h_rows, h_sqdist, h_cov, h_normals, h_nodes);
-  else if (k <= 16) knn_replay<16>(h_keys, n, k, h_rows, h_sqdist, h_cov, h_normals, h_nodes);
-  else knn_replay<32>(h_keys, n, k, h_rows, h_sqdist, h_cov, h_normals, h_nodes);
-  return PCC_OK;
+  return knn_host_frames("pcc_knn_replay_host", h_keys, n, 65536, [] {}, [&](int, int64_t flo, int64_t fhi) {
+    knn_with_cap(k, [&](auto cap) {
+      for (int64_t i = flo; i < fhi; ++i) {
+        const uint32_t nodes = knn_point<decltype(cap)::value>(h_keys, flo, fhi, i, k, h_rows, h_sqdist, h_cov, h_normals, false, 0, 0, 0);
+        if (h_nodes) h_nodes[i] = nodes;
+      }
+    });
+  });
 }
 
 // ---------------------------------------------------------------- outlier removal behind the same search

@@ -1,6 +1,7 @@
 // nn_cells.h — what the 1-NN search (nn.hip) and the k-NN search (knn.hip) share: distances on the biased lattice of
-// the Morton keys, the lower-bound search over sorted keys, the walk over the implicit octree, the per-frame rounds of
-// a wave, and the declarations of the key checks that nn.hip defines for both.
+// the Morton keys, the lower-bound search over sorted keys, the walk over the implicit octree, the per-frame rounds
+// of a wave, and the declarations of the key checks that nn.hip defines for both and of what knn.hip
+// defines for cluster.hip.
 #pragma once
 #include "common.h"
 
@@ -137,6 +138,20 @@ int nn_check_and_offsets(pcc_ctx* ctx, const char* who, const char* a_key, const
 int nn_host_sorted_distinct(const char* who, const char* keys, const uint64_t* h_keys, int64_t n);
 
 // ---------------------------------------------------------------- defined in knn.hip (cluster.h), for cluster.hip
+// what every entry on one key array does in front of its launches (knn.hip has the order and the arguments)
+struct KnnRange {      // the rule's integer of an entry as its refusal names it, and the range it must lie in
+  const char* name;
+  int v, lo, hi;
+};
+#define KNN_NO_RANGE KnnRange{nullptr, 0, 0, 0}      // an entry without such an integer, or one that has checked its own
+struct KnnNulls {      // the entry's words for null keys; whether its own pointers are there, and its words where not
+  const char* keys;
+  bool others_ok;
+  const char* others;
+};
+__attribute__((visibility("hidden")))      // the library's own: no new name among its dynamic symbols
+int knn_entry(pcc_ctx* ctx, const char* who, KnnRange k, const uint64_t* d_keys, int64_t n, int n_frames, KnnNulls nulls,
+              void* d_frame, size_t frame_bytes, size_t reserve, const int64_t** offs);
 // the parameter ranges of the clustering rule, and the two halves of its launches around the numbering's sort
 int cluster_args(const char* who, int64_t n, int n_frames, int m, uint64_t radius2, int64_t min_points);
 int cluster_components(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, const int64_t* offs, int n_frames, int m, uint64_t radius2,

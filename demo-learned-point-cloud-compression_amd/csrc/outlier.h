@@ -9,8 +9,8 @@
 //                      lane with 64-bit atomics; they are integers, so the order does not matter.
 //   k_outlier_mask     keep = q <= T[frame], and the frame's kept count the same way.
 //   k_outlier_radius   the list holds m + 1 entries (the point itself first) and the walk's bound is
-//                      min(last slot, radius2 + 1): a cell farther than the radius is never entered, so an isolated
-//                      point stops after the cells inside its radius.  Seeds enter the list wherever they lie; beyond
+//                      min(last slot, radius2 + 1) (KnnBest<CAP, true>): a cell farther than the radius is never
+//                      entered, so an isolated point stops after the cells inside its radius.  Seeds enter the list wherever they lie; beyond
 //                      the radius they leave the bound at radius2 + 1.  Every point within the radius lies in cells
 //                      whose box distance is at most radius2, below that bound, so it is pruned only by a list whose
 //                      last slot is already nearer: slot m ends at d2 <= radius2 exactly when the unbounded search's does.
@@ -50,21 +50,10 @@ __host__ __device__ static inline uint64_t outlier_score_point(const uint64_t* _
 
 __host__ __device__ static inline bool outlier_keep(uint64_t q, uint64_t threshold) { return q <= threshold; }
 
-// the bound of the radius search: the list's last slot, but never beyond cap = radius2 + 1.  At the cap no row wins a
-// tie (bound_row -1): a cell at box distance radius2 + 1 holds no point within the radius.
-template <int CAP>
-struct KnnRadiusBest {
-  KnnList<CAP>& L;
-  int64_t s0, s1;
-  uint64_t cap;
-  __host__ __device__ uint64_t bound() const { return L.d[CAP - 1] < cap ? L.d[CAP - 1] : cap; }
-  __host__ __device__ int64_t bound_row() const { return L.d[CAP - 1] < cap ? (int64_t)L.r[CAP - 1] : -1; }
-  __host__ __device__ bool seeded(int64_t r) const { return r >= s0 && r < s1; }
-  __host__ __device__ void offer(uint64_t d, int64_t r) { knn_insert(L, d, (int32_t)r); }
-};
-
 // whether row i has at least m other points of its frame [flo, fhi) within radius2 (<= OUTLIER_D2_MAX): slot m of its
-// list of m + 1.  bounded: under KnnRadiusBest; else knn_search itself.  *nodes: the nodes tried, as knn_search counts.
+// list of m + 1.  bounded: knn_search's seed and walk under KnnBest<CAP, true>, written out here — through the shared
+// function k_outlier_radius<8> took two more registers and lost a wave of occupancy; else knn_search itself.
+// *nodes: the nodes tried, as knn_search counts.
 template <int CAP>
 __host__ __device__ static inline bool outlier_radius_point(const uint64_t* __restrict__ keys, int64_t flo, int64_t fhi, int64_t i,
                                                             int m, uint64_t radius2, bool bounded, uint32_t* nodes) {
@@ -83,7 +72,7 @@ __host__ __device__ static inline bool outlier_radius_point(const uint64_t* __re
     int64_t s0 = lo - k_eff / 2;      // knn_search's seed rows
     if (s0 > fhi - k_eff) s0 = fhi - k_eff;
     if (s0 < flo) s0 = flo;
-    KnnRadiusBest<CAP> b = {L, s0, s0 + k_eff, radius2 + 1};
+    KnnBest<CAP, true> b = {L, s0, s0 + k_eff, radius2 + 1};
     for (int64_t r = b.s0; r < b.s1; ++r) knn_insert(L, nn_d2(qx, qy, qz, keys[r]), (int32_t)r);
     tried = (uint32_t)k_eff;
     if (k_eff != n_f) tried += nn_walk(keys, flo, fhi, qx, qy, qz, b);
@@ -91,6 +80,9 @@ __host__ __device__ static inline bool outlier_radius_point(const uint64_t* __re
   if (nodes) *nodes = tried;
   return L.d[CAP - 1] <= radius2;      // a free slot holds 2^64 - 1: a frame of at most m points keeps nothing
 }
+
+// radius2 as the searches take it: no two points lie farther apart than OUTLIER_D2_MAX
+static inline uint64_t outlier_radius2(uint64_t radius2) { return radius2 < OUTLIER_D2_MAX ? radius2 : OUTLIER_D2_MAX; }
 
 // ---------------------------------------------------------------- kernels
 template <int CAP>
@@ -208,78 +200,51 @@ __global__ void k_gather_rows_pitched(const T* __restrict__ src, int64_t n_src, 
 }
 
 // ---------------------------------------------------------------- C-ABI (include/pcc.h)
-static int outlier_args(pcc_ctx* ctx, const char* who, const uint64_t* d_keys, int64_t n, int n_frames, int k, int k_lo, int k_hi,
-                        const char* k_name) {
-  PCC_REQUIRE(ctx && k >= k_lo && k <= k_hi && n >= 0 && n <= NN_MAX_KEYS && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
-              "%s: bad argument (n=%lld n_frames=%d %s=%d; %s in %d .. %d, at most 2^27 keys, 1 .. 65535 frames)", who, (long long)n,
-              n_frames, k_name, k, k_name, k_lo, k_hi);
-  PCC_REQUIRE(n == 0 || d_keys, PCC_E_ARG, "%s: null keys", who);
-  return PCC_OK;
-}
-
 extern "C" int pcc_outlier_scores_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int k, uint64_t* d_scores,
                                          uint64_t* d_sums) {
-  PCC_TRY(outlier_args(ctx, "pcc_outlier_scores_frames", d_keys, n, n_frames, k, 3, 32, "k"));
-  PCC_REQUIRE(d_sums && (n == 0 || d_scores), PCC_E_ARG, "pcc_outlier_scores_frames: null output");
-  hipStream_t st = ctx->stream;
-  if (n == 0) {
-    PCC_HIP(hipMemsetAsync(d_sums, 0, (size_t)n_frames * 32, st));
-    return PCC_OK;
-  }
   const int64_t* offs;
-  PCC_TRY(nn_check_and_offsets(ctx, "pcc_outlier_scores_frames", "a key's", "keys", d_keys, n, nullptr, 0, n_frames, &offs));
-  PCC_HIP(hipMemsetAsync(d_sums, 0, (size_t)n_frames * 32, st));
+  PCC_TRY(knn_entry(ctx, "pcc_outlier_scores_frames", {"k", k, 3, 32}, d_keys, n, n_frames,
+                    {"null keys", d_sums && (n == 0 || d_scores), "null output"}, d_sums, 32, 0, &offs));
+  if (!offs) return PCC_OK;
   PccProfScope prof(ctx, "outlier_scores", n, k, n_frames, 0);
-  const dim3 grid(nblk(n, 256)), block(256);
-  unsigned long long* sums = (unsigned long long*)d_sums;
-  if (k <= 8) hipLaunchKernelGGL(k_outlier_scores<8>, grid, block, 0, st, d_keys, n, offs, k, d_scores, sums);
-  else if (k <= 16) hipLaunchKernelGGL(k_outlier_scores<16>, grid, block, 0, st, d_keys, n, offs, k, d_scores, sums);
-  else hipLaunchKernelGGL(k_outlier_scores<32>, grid, block, 0, st, d_keys, n, offs, k, d_scores, sums);
+  knn_with_cap(k, [&](auto cap) {
+    hipLaunchKernelGGL(k_outlier_scores<decltype(cap)::value>, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, d_keys, n, offs, k,
+                       d_scores, (unsigned long long*)d_sums);
+  });
   PCC_CHECK_LAUNCH();
   return PCC_OK;
 }
 
 extern "C" int pcc_outlier_mask_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, const uint64_t* d_scores,
                                        const uint64_t* d_threshold, uint8_t* d_keep, uint64_t* d_kept) {
-  PCC_REQUIRE(ctx && n >= 0 && n <= NN_MAX_KEYS && n_frames >= 1 && n_frames <= 65535, PCC_E_ARG,
-              "pcc_outlier_mask_frames: bad argument (n=%lld n_frames=%d; at most 2^27 keys, 1 .. 65535 frames)", (long long)n,
-              n_frames);
-  PCC_REQUIRE(d_kept && d_threshold && (n == 0 || (d_keys && d_scores && d_keep)), PCC_E_ARG, "pcc_outlier_mask_frames: null arg");
-  hipStream_t st = ctx->stream;
-  if (n == 0) {
-    PCC_HIP(hipMemsetAsync(d_kept, 0, (size_t)n_frames * 8, st));
-    return PCC_OK;
-  }
   const int64_t* offs;      // the checks: a frame index indexes d_threshold and d_kept
-  PCC_TRY(nn_check_and_offsets(ctx, "pcc_outlier_mask_frames", "a key's", "keys", d_keys, n, nullptr, 0, n_frames, &offs));
-  PCC_HIP(hipMemsetAsync(d_kept, 0, (size_t)n_frames * 8, st));
+  PCC_TRY(knn_entry(ctx, "pcc_outlier_mask_frames", KNN_NO_RANGE, d_keys, n, n_frames,
+                    {"null arg", d_kept && d_threshold && (n == 0 || (d_scores && d_keep)), "null arg"}, d_kept, 8, 0, &offs));
+  if (!offs) return PCC_OK;
   PccProfScope prof(ctx, "outlier_mask", n, n_frames, 0, 0);
-  hipLaunchKernelGGL(k_outlier_mask, dim3(nblk(n, 256)), dim3(256), 0, st, d_keys, n, d_scores, d_threshold, d_keep,
+  hipLaunchKernelGGL(k_outlier_mask, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, d_keys, n, d_scores, d_threshold, d_keep,
                      (unsigned long long*)d_kept);
   PCC_CHECK_LAUNCH();
   return PCC_OK;
 }
 
+// the radius rule's kernel for a list of m + 1: the entry below, and the core flags of cluster.h; counts is zeroed
+static void outlier_radius_launch(hipStream_t st, const uint64_t* d_keys, int64_t n, const int64_t* offs, int m, uint64_t radius2,
+                                  uint8_t* d_keep, uint64_t* d_counts) {
+  knn_with_cap(m + 1, [&](auto cap) {
+    hipLaunchKernelGGL(k_outlier_radius<decltype(cap)::value>, dim3(nblk(n, 256)), dim3(256), 0, st, d_keys, n, offs, m, radius2,
+                       d_keep, (unsigned long long*)d_counts);
+  });
+}
+
 extern "C" int pcc_outlier_radius_frames(pcc_ctx* ctx, const uint64_t* d_keys, int64_t n, int n_frames, int min_neighbours,
                                          uint64_t radius2, uint8_t* d_keep, uint64_t* d_counts) {
-  PCC_TRY(outlier_args(ctx, "pcc_outlier_radius_frames", d_keys, n, n_frames, min_neighbours, 1, 31, "min_neighbours"));
-  PCC_REQUIRE(d_counts && (n == 0 || d_keep), PCC_E_ARG, "pcc_outlier_radius_frames: null output");
-  hipStream_t st = ctx->stream;
-  if (n == 0) {
-    PCC_HIP(hipMemsetAsync(d_counts, 0, (size_t)n_frames * 16, st));
-    return PCC_OK;
-  }
   const int64_t* offs;
-  PCC_TRY(nn_check_and_offsets(ctx, "pcc_outlier_radius_frames", "a key's", "keys", d_keys, n, nullptr, 0, n_frames, &offs));
-  PCC_HIP(hipMemsetAsync(d_counts, 0, (size_t)n_frames * 16, st));
+  PCC_TRY(knn_entry(ctx, "pcc_outlier_radius_frames", {"min_neighbours", min_neighbours, 1, 31}, d_keys, n, n_frames,
+                    {"null keys", d_counts && (n == 0 || d_keep), "null output"}, d_counts, 16, 0, &offs));
+  if (!offs) return PCC_OK;
   PccProfScope prof(ctx, "outlier_radius", n, min_neighbours, n_frames, 0);
-  const int m = min_neighbours;
-  const uint64_t r2 = radius2 < OUTLIER_D2_MAX ? radius2 : OUTLIER_D2_MAX;      // no two points lie farther apart
-  const dim3 grid(nblk(n, 256)), block(256);
-  unsigned long long* counts = (unsigned long long*)d_counts;
-  if (m + 1 <= 8) hipLaunchKernelGGL(k_outlier_radius<8>, grid, block, 0, st, d_keys, n, offs, m, r2, d_keep, counts);
-  else if (m + 1 <= 16) hipLaunchKernelGGL(k_outlier_radius<16>, grid, block, 0, st, d_keys, n, offs, m, r2, d_keep, counts);
-  else hipLaunchKernelGGL(k_outlier_radius<32>, grid, block, 0, st, d_keys, n, offs, m, r2, d_keep, counts);
+  outlier_radius_launch(ctx->stream, d_keys, n, offs, min_neighbours, outlier_radius2(radius2), d_keep, d_counts);
   PCC_CHECK_LAUNCH();
   return PCC_OK;
 }
@@ -339,31 +304,6 @@ extern "C" int pcc_gather_rows_pitched(pcc_ctx* ctx, const void* d_src, int64_t 
 
 // ---------------------------------------------------------------- the host replay
 // host only, no ctx: the kernels' functions for every row on the calling thread.  Not a product path.
-template <int CAP>
-static void outlier_replay_scores(const uint64_t* h_keys, int64_t flo, int64_t fhi, int k, uint64_t* h_scores, uint64_t* sums,
-                                  uint32_t* h_nodes) {
-  for (int64_t i = flo; i < fhi; ++i) {
-    uint32_t nodes;
-    const uint64_t q = outlier_score_point<CAP>(h_keys, flo, fhi, i, k, &nodes), sq = q * q;
-    if (h_scores) h_scores[i] = q;
-    if (h_nodes) h_nodes[i] = nodes;
-    if (sums) {
-      sums[0] += q; sums[1] += sq & 0xFFFFFFFFull; sums[2] += sq >> 32; sums[3] += 1;
-    }
-  }
-}
-
-template <int CAP>
-static void outlier_replay_radius(const uint64_t* h_keys, int64_t flo, int64_t fhi, int m, uint64_t radius2, bool bounded,
-                                  uint8_t* h_keep, uint32_t* h_nodes) {
-  for (int64_t i = flo; i < fhi; ++i) {
-    uint32_t nodes;
-    const bool keep = outlier_radius_point<CAP>(h_keys, flo, fhi, i, m, radius2, bounded, &nodes);
-    if (h_keep) h_keep[i] = keep ? 1 : 0;
-    if (h_nodes) h_nodes[i] = nodes;
-  }
-}
-
 extern "C" uint64_t pcc_outlier_isqrt_host(uint64_t x) { return x < (1ull << 42) ? outlier_isqrt(x) : ~0ull; }
 
 extern "C" int pcc_outlier_replay_host(const uint64_t* h_keys, int64_t n, int n_frames, int k, int min_neighbours, uint64_t radius2,
@@ -379,33 +319,39 @@ extern "C" int pcc_outlier_replay_host(const uint64_t* h_keys, int64_t n, int n_
               (long long)n, n_frames, k, m);
   PCC_REQUIRE(!h_keep || (h_threshold && h_scores), PCC_E_ARG, "pcc_outlier_replay_host: keep bytes need thresholds and scores");
   PCC_TRY(nn_host_sorted_distinct("pcc_outlier_replay_host", "keys", h_keys, n));
-  PCC_REQUIRE(n == 0 || (int)(h_keys[n - 1] >> 48) < n_frames, PCC_E_RANGE,
-              "pcc_outlier_replay_host: a key's frame index is not below n_frames=%d", n_frames);
-  if (h_sums) std::fill(h_sums, h_sums + 4 * (size_t)n_frames, 0ull);
-  const uint64_t r2 = radius2 < OUTLIER_D2_MAX ? radius2 : OUTLIER_D2_MAX;
-  int64_t flo = 0;
-  while (flo < n) {
-    const uint64_t frame = h_keys[flo] & ~NN_KEY48;
-    const int64_t fhi = std::upper_bound(h_keys + flo, h_keys + n, frame | NN_KEY48) - h_keys;
-    const int f = (int)(frame >> 48);
+  const uint64_t r2 = outlier_radius2(radius2);
+  const auto ready = [&] {
+    if (h_sums) std::fill(h_sums, h_sums + 4 * (size_t)n_frames, 0ull);
+  };
+  return knn_host_frames("pcc_outlier_replay_host", h_keys, n, n_frames, ready, [&](int f, int64_t flo, int64_t fhi) {
     uint64_t* sums = h_sums ? h_sums + 4 * (size_t)f : nullptr;
-    if (h_scores || h_sums || h_nodes) {
-      if (k <= 8) outlier_replay_scores<8>(h_keys, flo, fhi, k, h_scores, sums, h_nodes);
-      else if (k <= 16) outlier_replay_scores<16>(h_keys, flo, fhi, k, h_scores, sums, h_nodes);
-      else outlier_replay_scores<32>(h_keys, flo, fhi, k, h_scores, sums, h_nodes);
-    }
+    if (h_scores || h_sums || h_nodes)
+      knn_with_cap(k, [&](auto cap) {
+        for (int64_t i = flo; i < fhi; ++i) {
+          uint32_t nodes;
+          const uint64_t q = outlier_score_point<decltype(cap)::value>(h_keys, flo, fhi, i, k, &nodes), sq = q * q;
+          if (h_scores) h_scores[i] = q;
+          if (h_nodes) h_nodes[i] = nodes;
+          if (sums) {
+            sums[0] += q; sums[1] += sq & 0xFFFFFFFFull; sums[2] += sq >> 32; sums[3] += 1;
+          }
+        }
+      });
     if (h_keep)
       for (int64_t i = flo; i < fhi; ++i) h_keep[i] = outlier_keep(h_scores[i], h_threshold[f]) ? 1 : 0;
     for (int pass = 0; pass < 2; ++pass) {
       const bool bounded = pass == 0;
       uint8_t* keep = bounded ? h_keep_radius : h_keep_unbounded;
-      uint32_t* nodes = bounded ? h_nodes_radius : h_nodes_unbounded;
-      if (!keep && !nodes) continue;
-      if (m + 1 <= 8) outlier_replay_radius<8>(h_keys, flo, fhi, m, r2, bounded, keep, nodes);
-      else if (m + 1 <= 16) outlier_replay_radius<16>(h_keys, flo, fhi, m, r2, bounded, keep, nodes);
-      else outlier_replay_radius<32>(h_keys, flo, fhi, m, r2, bounded, keep, nodes);
+      uint32_t* tried = bounded ? h_nodes_radius : h_nodes_unbounded;
+      if (!keep && !tried) continue;
+      knn_with_cap(m + 1, [&](auto cap) {
+        for (int64_t i = flo; i < fhi; ++i) {
+          uint32_t nodes;
+          const bool kept = outlier_radius_point<decltype(cap)::value>(h_keys, flo, fhi, i, m, r2, bounded, &nodes);
+          if (keep) keep[i] = kept ? 1 : 0;
+          if (tried) tried[i] = nodes;
+        }
+      });
     }
-    flo = fhi;
-  }
-  return PCC_OK;
+  });
 }

@@ -335,6 +335,58 @@ class GeometryCodec:
         return float(v), tuple(float(x) for x in o)
 
     @staticmethod
+    def _check_output(output):
+        if output not in ("numpy", "device"):
+            raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
+
+    @staticmethod
+    def _check_invalid(invalid):
+        if invalid not in ("raise", "drop"):
+            raise ValueError(f"invalid must be 'raise' or 'drop', got {invalid!r}")
+
+    @staticmethod
+    def _check_voxel(is_float, voxel, origin, what):
+        """the grid of a call that takes lattice or float32 frames -> (voxel, origin): float32 frames need one (as
+        _check_grid narrows it), integer frames refuse one"""
+        if is_float:
+            if voxel is None:
+                raise ValueError("float32 frames need voxel=, the edge of a lattice cell in the frames' unit")
+            return GeometryCodec._check_grid(voxel, origin, what)
+        if voxel is not None:
+            raise ValueError("voxel= with integer frames: they are on the lattice already")
+        return voxel, origin
+
+    def _check_two_sides(self, frames_a, frames_b, where, hint=""):
+        """the frames of both sides of distortion and transfer -> (frames, on_device) of side A, then of side B: lattice
+        points, as many frames on one side as on the other, both on the host or both on the device; hint: the call's
+        own last words to a caller with float32 frames"""
+        fa, float_a, dev_a = self._check_frames(frames_a)
+        fb, float_b, dev_b = self._check_frames(frames_b)
+        if float_a or float_b:
+            raise TypeError(f"{where}: float32 frames: pass lattice points (int16 / int32) — the input of compress, or "
+                            f"what decompress returns without voxel={hint}")
+        if len(fa) != len(fb):
+            raise ValueError(f"{where}: {len(fa)} frames against {len(fb)}")
+        if fa and dev_a != dev_b:
+            raise ValueError(f"{where}: one side on the host, the other on the device: the frames of a call are all on "
+                             "the host or all on the device")
+        return fa, dev_a, fb, dev_b
+
+    @staticmethod
+    def _common_format(attrs):
+        """the common format of a call's attributes -> (dtype, channels): uint16 if any frame is, rows of 4 or 8 bytes
+        (pcc_gather_rows), absent channels 0"""
+        dtype = np.uint16 if any(a.dtype == np.uint16 for a in attrs) else np.uint8
+        channels = max(a.shape[1] for a in attrs)
+        return dtype, 4 if dtype == np.uint8 or channels > 2 else 2
+
+    @staticmethod
+    def _input_rows(rt, front):
+        """the distinct row of every input row of a front end: rows_index with no frame's rows taken off"""
+        return rt.rows_index(front.perm, front.n_keep, front.rows, front.n_unique, front.offsets.data_ptr(),
+                             torch.zeros(front.nb, dtype=torch.int64, device=rt.device), front.nb)
+
+    @staticmethod
     def _check_attribute_scale(scale, dtype, given):
         """attribute_scale and attribute_dtype of a call -> (s as a float, the numpy dtype float values become), or
         (None, None) without a scale; `given`: whether the call has attributes"""
@@ -807,14 +859,8 @@ class GeometryCodec:
         frames, is_float, on_device = self._check_frames(frames)
         intra_period, reference, history = self._check_predict(predict, intra_period, reference, is_float, on_device, len(frames),
                                                                history)
-        if invalid not in ("raise", "drop"):
-            raise ValueError(f"invalid must be 'raise' or 'drop', got {invalid!r}")
-        if is_float:
-            if voxel is None:
-                raise ValueError("float32 frames need voxel=, the edge of a lattice cell in the frames' unit")
-            voxel, origin = self._check_grid(voxel, origin, "compress")
-        elif voxel is not None:
-            raise ValueError("voxel= with integer frames: they are on the lattice already")
+        self._check_invalid(invalid)
+        voxel, origin = self._check_voxel(is_float, voxel, origin, "compress")
         scale, attr_dtype = self._check_attribute_scale(attribute_scale, attribute_dtype, attributes is not None)
         attrs = None if attributes is None else self._check_attributes(frames, attributes, self._device, scale, attr_dtype)
         nb = len(frames)
@@ -1121,8 +1167,7 @@ class GeometryCodec:
         of before."""
         if isinstance(attr_blobs, str):      # decompress(blobs, "device"), as before attributes
             attr_blobs, output = None, attr_blobs
-        if output not in ("numpy", "device"):
-            raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
+        self._check_output(output)
         lod = self._check_lod(lod)
         if voxel is not None:
             voxel, origin = self._check_grid(voxel, origin, "decompress")
@@ -1317,8 +1362,7 @@ class GeometryCodec:
                                        for v in vp):
                 raise ValueError(f"viewpoint must be three integers in lattice units, got {viewpoint!r}")
             viewpoint = [int(v) for v in vp]
-        if output not in ("numpy", "device"):
-            raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
+        self._check_output(output)
         frames, is_float, on_device = self._check_frames(frames)
         if is_float:
             raise TypeError("normals: float32 frames: pass lattice points (int16 / int32) — the input of compress, or "
@@ -1336,10 +1380,7 @@ class GeometryCodec:
             front = self._front(rt, frames, False, on_device, caller, "GeometryCodec.normals")
             self._refuse_few(front, "frames")
             distinct = rt.knn_frames(front.keys, nb, k, viewpoint=viewpoint)[3]
-            # the distinct row of every input row: rows_index with no frame's rows taken off
-            index = rt.rows_index(front.perm, front.n_keep, front.rows, front.n_unique, front.offsets.data_ptr(),
-                                  torch.zeros(nb, dtype=torch.int64, device=rt.device), nb)
-            return _frames_out(rt, rt.gather_rows(distinct, index), sizes, output == "numpy")
+            return _frames_out(rt, rt.gather_rows(distinct, self._input_rows(rt, front)), sizes, output == "numpy")
 
     @staticmethod
     def _check_filter(method, k, std_ratio, min_neighbours, radius2):
@@ -1399,17 +1440,10 @@ class GeometryCodec:
         An empty frame comes back empty; a frame of one point is kept whole under "statistical" and dropped whole under
         "radius"."""
         method, p0, p1 = self._check_filter(method, k, std_ratio, min_neighbours, radius2)
-        if output not in ("numpy", "device"):
-            raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
-        if invalid not in ("raise", "drop"):
-            raise ValueError(f"invalid must be 'raise' or 'drop', got {invalid!r}")
+        self._check_output(output)
+        self._check_invalid(invalid)
         frames, is_float, on_device = self._check_frames(frames)
-        if is_float:
-            if voxel is None:
-                raise ValueError("float32 frames need voxel=, the edge of a lattice cell in the frames' unit")
-            voxel, origin = self._check_grid(voxel, origin, "filter")
-        elif voxel is not None:
-            raise ValueError("voxel= with integer frames: they are on the lattice already")
+        voxel, origin = self._check_voxel(is_float, voxel, origin, "filter")
         attrs = flat = None
         if attributes is not None:
             attributes = list(attributes)
@@ -1453,10 +1487,7 @@ class GeometryCodec:
                     points = [cnt for _, _, cnt in sums]
                 else:
                     keep, counts = rt.outlier_radius_frames(front.keys, nb, p0, p1)
-                # the distinct row of every input row: rows_index with no frame's rows taken off
-                index = rt.rows_index(front.perm, front.n_keep, front.rows, front.n_unique, front.offsets.data_ptr(),
-                                      torch.zeros(nb, dtype=torch.int64, device=rt.device), nb)
-                mask, kept_rows, ends = rt.outlier_compact_rows(index, keep, front.offsets.data_ptr(), nb)
+                mask, kept_rows, ends = rt.outlier_compact_rows(self._input_rows(rt, front), keep, front.offsets.data_ptr(), nb)
                 rt.sync()      # the sizes of the result
                 ends = ends.cpu().tolist()
                 if statistical:
@@ -1529,17 +1560,10 @@ class GeometryCodec:
         codec's device.  An empty frame gives an empty array; a frame of one point is one cluster of size 1 at
         min_neighbours=0 and noise above."""
         radius2, m, min_points = self._check_cluster(radius2, min_neighbours, min_points)
-        if output not in ("numpy", "device"):
-            raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
-        if invalid not in ("raise", "drop"):
-            raise ValueError(f"invalid must be 'raise' or 'drop', got {invalid!r}")
+        self._check_output(output)
+        self._check_invalid(invalid)
         frames, is_float, on_device = self._check_frames(frames)
-        if is_float:
-            if voxel is None:
-                raise ValueError("float32 frames need voxel=, the edge of a lattice cell in the frames' unit")
-            voxel, origin = self._check_grid(voxel, origin, "cluster")
-        elif voxel is not None:
-            raise ValueError("voxel= with integer frames: they are on the lattice already")
+        voxel, origin = self._check_voxel(is_float, voxel, origin, "cluster")
         nb = len(frames)
         if nb == 0:
             return ([], []) if return_report else []
@@ -1551,9 +1575,7 @@ class GeometryCodec:
                 rows = torch.full((front.n,), -1, dtype=torch.int32, device=rt.device)
             else:
                 labels, d_sizes, d_counts = rt.cluster_frames(front.keys, nb, m, radius2, min_points, want_sizes=return_report)
-                # the distinct row of every input row: rows_index with no frame's rows taken off
-                index = rt.rows_index(front.perm, front.n_keep, front.rows, front.n_unique, front.offsets.data_ptr(),
-                                      torch.zeros(nb, dtype=torch.int64, device=rt.device), nb)
+                index = self._input_rows(rt, front)
                 rows = torch.where(index >= 0, labels[index.clamp(min=0).long()], torch.full_like(index, -1))
                 if return_report:
                     counts = rt._u64_rows(d_counts)      # the call's synchronisation for the counts
@@ -1645,16 +1667,8 @@ class GeometryCodec:
         host arrays or all tensors on this codec's device (what normals(output="device") returns), row i the normal of
         row i of A, used as given: A must then be free of duplicate points; a non-finite normal raises ValueError naming
         the frame."""
-        fa, float_a, dev_a = self._check_frames(frames_a)
-        fb, float_b, dev_b = self._check_frames(frames_b)
-        if float_a or float_b:
-            raise TypeError("distortion: float32 frames: pass lattice points (int16 / int32) — the input of compress, or "
-                            "what decompress returns without voxel=; metric distances are lattice distances times voxel^2")
-        if len(fa) != len(fb):
-            raise ValueError(f"distortion: {len(fa)} frames against {len(fb)}")
-        if fa and dev_a != dev_b:
-            raise ValueError("distortion: one side on the host, the other on the device: the frames of a call are all on "
-                             "the host or all on the device")
+        fa, dev_a, fb, dev_b = self._check_two_sides(frames_a, frames_b, "distortion",
+                                                     "; metric distances are lattice distances times voxel^2")
         if (attributes_a is None) != (attributes_b is None):
             raise ValueError("distortion: attributes on one side only")
         if peak is not None and not (isinstance(peak, (int, float, np.integer, np.floating)) and not isinstance(peak, bool)
@@ -1714,9 +1728,7 @@ class GeometryCodec:
                 if normals_a is not None:
                     d2_ab, d2_ba = self._d2_sums(rt, front_a, front_b, row_ab, row_ba, given, normal_k)
                 if attrs_a is not None:
-                    dtype = np.uint16 if any(a.dtype == np.uint16 for a in attrs_a) else np.uint8
-                    channels = max(a.shape[1] for a in attrs_a)
-                    channels = 4 if dtype == np.uint8 or channels > 2 else 2      # rows of 4 or 8 bytes (pcc_gather_rows)
+                    dtype, channels = self._common_format(attrs_a)
                     statuses = []
                     va = self._sorted_any(rt, attrs_a, front_a.perm, dtype, channels, caller, scale, statuses)
                     vb = self._sorted_any(rt, attrs_b, front_b.perm, dtype, channels, caller, scale, statuses)
@@ -1774,8 +1786,7 @@ class GeometryCodec:
         """ValueError naming the first frame of `side` whose sorted keys hold a duplicate (the distinct count says so)"""
         if front.n_unique == front.n_keep:
             return
-        sizes = front.sizes
-        counts = np.bincount(((front.keys >> 48) & 0xFFFF).cpu().numpy(), minlength=len(sizes))
+        sizes, counts = front.sizes, GeometryCodec._frame_counts(front.keys, front.nb)
         f = next(f for f, (n, u) in enumerate(zip(sizes, counts)) if u < n)
         raise ValueError(f"frame {f}: {sizes[f] - int(counts[f])} duplicate points in {side}: attributes are compared point by "
                          "point, so both sides must be free of duplicates (a decoded frame is)")
@@ -1798,18 +1809,8 @@ class GeometryCodec:
         output: "numpy" arrays, or "device": views of one tensor on this codec's device.  return_counts=True:
         (values, counts), counts[f] a uint32 [n_to]: the source rows assigned to the row's point, 0 where the value is
         the fallback."""
-        if output not in ("numpy", "device"):
-            raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
-        ff, float_f, dev_f = self._check_frames(frames_from)
-        ft, float_t, dev_t = self._check_frames(frames_to)
-        if float_f or float_t:
-            raise TypeError("transfer: float32 frames: pass lattice points (int16 / int32) — the input of compress, or "
-                            "what decompress returns without voxel=")
-        if len(ff) != len(ft):
-            raise ValueError(f"transfer: {len(ff)} frames against {len(ft)}")
-        if ff and dev_f != dev_t:
-            raise ValueError("transfer: one side on the host, the other on the device: the frames of a call are all on "
-                             "the host or all on the device")
+        self._check_output(output)
+        ff, dev_f, ft, dev_t = self._check_two_sides(frames_from, frames_to, "transfer")
         attributes = list(attributes)
         flat = [(a.dim() if isinstance(a, torch.Tensor) else np.ndim(a)) == 1 for a in attributes]
         scale, attr_dtype = self._check_attribute_scale(attribute_scale, attribute_dtype, True)
@@ -1823,10 +1824,7 @@ class GeometryCodec:
         if nb == 0:
             return ([], []) if return_counts else []
         to_host = output == "numpy"
-        # the call's common format: rows of 4 or 8 bytes (pcc_gather_rows), absent channels 0
-        dtype = np.uint16 if any(a.dtype == np.uint16 for a in attrs) else np.uint8
-        channels = max(a.shape[1] for a in attrs)
-        channels = 4 if dtype == np.uint8 or channels > 2 else 2
+        dtype, channels = self._common_format(attrs)
         if sum(sizes_t) == 0:
             values = torch.empty((0, channels), dtype=torch.uint8 if dtype == np.uint8 else torch.uint16,
                                  device="cpu" if to_host else self.rt.device)
@@ -1846,9 +1844,7 @@ class GeometryCodec:
                 sv = self._sorted_any(rt, attrs, front_f.perm, dtype, channels, caller, scale, statuses)
                 distinct, cnt = rt.attr_transfer_frames(front_f.sorted_keys, front_f.rows, front_f.n_unique, sv, row_st, row_ts,
                                                         nb, want_count=return_counts)
-                # the distinct row of every target row as given: rows_index with no frame's rows taken off
-                index = rt.rows_index(front_t.perm, front_t.n_keep, front_t.rows, front_t.n_unique, front_t.offsets.data_ptr(),
-                                      torch.zeros(nb, dtype=torch.int64, device=rt.device), nb)
+                index = self._input_rows(rt, front_t)      # of every target row as given
                 values = _frames_out(rt, rt.gather_rows(distinct, index), sizes_t, to_host)
                 counts = _frames_out(rt, rt.gather_rows(cnt, index), sizes_t, to_host) if return_counts else None
                 for status in statuses:      # behind the synchronisation of _frames_out
